@@ -12,6 +12,12 @@ Prints ONE JSON line (rank 0).  ``roofline.achieved`` = algorithmic bytes per
 launch (reference dtypes) / average kernel time from HIP
 events recorded on the stream the kernel runs on.  ``cpu_baseline`` = the
 oracle (restated FusedMM-semantics CPU kernel, OpenMP) on this box's host cores.
+
+A plain run sets up, warms up, times exactly --steps steps and prints the line.
+``--full`` adds everything else it measures: the cold-cache launch and copy rate
+of the roofline object, the backward figure, ``cpu_baseline`` and the ``extra``
+configurations.  ``--dump-outputs DIR`` writes what the last timed step computed
+as DIR/out.npy (and DIR/arg.npy for max / min), a seeded sample of rows when large.
 """
 from __future__ import annotations
 
@@ -53,6 +59,13 @@ def parse():
     p.add_argument("--chunk", type=int, default=1024, help="tasks: edges per task")
     p.add_argument("--short", type=int, default=128, help="tasks: rows shorter than this are not sliced")
     p.add_argument("--tune", default="", help="debug: comma list of key=value for isplib_hip_tune (9, 12: isplib_hip_tune_experimental)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline does not need: the cold-cache launch and the device copy rate of the "
+                        "roofline object, the backward figure, the CPU baseline and the other BASELINE.json configs (`extra`; "
+                        "at N > 1 the multi-GPU configurations).  Without it a run sets up, warms up, times --steps steps "
+                        "and prints the line")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (dump_outputs)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-extra", action="store_true", help="skip the other BASELINE.json configs (the `extra` array)")
     p.add_argument("--no-backward", action="store_true")
@@ -60,7 +73,10 @@ def parse():
                    "profiles/traffic.json (reddit-{mean,max,min}-k64-weighted, reddit-sum-k128-weighted, reddit-sum-k{32,41}-unit, "
                    "reddit-sddmm-k128, reddit-fusedmm-{sigmoid,tdist}-k128, gcn-epoch, scaling-emulated-{reddit,products}, "
                    "products-{chunglu,sbm}-sum-k256-{plain,ordered}), and print it instead of the metric line")
-    return p.parse_args()
+    a = p.parse_args()
+    if not a.full:
+        a.no_cpu_baseline = a.no_extra = a.no_backward = True
+    return a
 
 
 def cpu_baseline(rowptr, col, x, nnz):
@@ -123,6 +139,35 @@ def apply_tune(cabi, spec: str) -> None:
         rc = (cabi.exp_lib().isplib_hip_tune_experimental if key >= 9 else cabi.lib().isplib_hip_tune)(key, value)
         if rc != 0:
             raise SystemExit(f"bench.py: --tune {kv}: unknown knob or value")
+
+
+DUMP_BUDGET_BYTES = 48 << 20     # --dump-outputs: bytes written in all (a sample of rows beyond it)
+
+
+def sample_outputs(out, arg=None, budget=DUMP_BUDGET_BYTES, seed=0):
+    """What a caller of the timed path receives -- `out` (float32) and, for max / min, `arg` (int64 positions, returned as
+    float64: exact below 2**53) -- as host arrays {name: ndarray}.  When both together exceed `budget` bytes, the same
+    fixed, seeded sample of whole rows of each (np.random.default_rng(seed), sorted row indices; the same rows for the
+    same shape on every run) stands in for them."""
+    import numpy as np
+    m, k = out.shape
+    row_bytes = k * 4 + (k * 8 if arg is not None else 0)
+    rows = None
+    if m * row_bytes > budget:
+        rows = np.sort(np.random.default_rng(seed).choice(m, max(1, budget // row_bytes), replace=False))
+        rows = torch.from_numpy(rows).to(out.device)
+    pick = (lambda t: t) if rows is None else (lambda t: t.index_select(0, rows))
+    res = {"out": pick(out).float().cpu().numpy()}
+    if arg is not None:
+        res["arg"] = pick(arg).double().cpu().numpy()
+    return res
+
+
+def dump_outputs(path: str, arrays) -> None:
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), arr)
 
 
 def _time_launches(fn, reps=5, warm=2):
@@ -1348,7 +1393,8 @@ def main():
     broken = None          # N > 1: why the run stopped short of its optional parts (the measured result still stands)
 
     def run_timed(step):
-        """W warm-up steps, then exactly K timed steps between barrier + synchronize on both sides; seconds, max over ranks."""
+        """W warm-up steps, then exactly K timed steps between barrier + synchronize on both sides; seconds, max over ranks,
+        the events' milliseconds and, with --dump-outputs, what the last timed step computed (rank 0: its own rows)."""
         for _ in range(a.warmup):
             step()
         torch.cuda.synchronize()
@@ -1367,7 +1413,8 @@ def main():
             t = torch.tensor([secs], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             secs = float(t.item())
-        return secs, [s_.elapsed_time(e_) for s_, e_ in ev]
+        outputs = sample_outputs(out, arg) if a.dump_outputs and rank == 0 else None
+        return secs, [s_.elapsed_time(e_) for s_, e_ in ev], outputs
 
     def single_step(i=None):
         if i is not None:
@@ -1617,14 +1664,14 @@ def main():
             times[name] = clock(fn)
         chosen = min(times, key=times.get)
         note(f"north_star form: {chosen}; {a.warmup} warm-up + {a.steps} timed steps")
-        elapsed, kern_ms = run_timed(make_step(chosen, safe[chosen]))
+        elapsed, kern_ms, outputs = run_timed(make_step(chosen, safe[chosen]))
         res = build_result(elapsed, kern_ms, chosen, times)
         guard.offer(res)
         note(f"result held by the guard: {elapsed / a.steps * 1e3:.3f} ms/step ({chosen})")
 
         # ---- 2. optional exchange schedules: each under its own deadline, none of them can lose the result ----------
         def explore(explore_until):
-            nonlocal chosen, elapsed, kern_ms, res
+            nonlocal chosen, elapsed, kern_ms, outputs, res
             if os.environ.get("ISPLIB_OVERLAP", "1") == "0" or guard.elapsed() + t_candidate >= explore_until:
                 return
             guard.arm("plans of the optional exchange schedules", t_candidate)
@@ -1682,9 +1729,9 @@ def main():
             if best != chosen and times[best] < 0.97 * times[chosen]:
                 guard.arm(f"timed steps of '{best}'", t_candidate)
                 note(f"'{best}' is faster ({times[best]:.3f} against {times[chosen]:.3f} ms): {a.warmup} warm-up + {a.steps} timed steps")
-                elapsed2, kern2 = run_timed(make_step(best, optional[best]))
+                elapsed2, kern2, outs2 = run_timed(make_step(best, optional[best]))
                 if elapsed2 < elapsed:
-                    chosen, elapsed, kern_ms = best, elapsed2, kern2
+                    chosen, elapsed, kern_ms, outputs = best, elapsed2, kern2, outs2
                     res = build_result(elapsed, kern_ms, chosen, times)
                     guard.offer(res)
                 elif res is not None:
@@ -1703,13 +1750,15 @@ def main():
             print(f"[bench] N={world}: " + ", ".join(f"{n_} {t_:.3f} ms/step" for n_, t_ in times.items()) + f" -> {chosen}",
                   file=sys.stderr, flush=True)
     else:
-        elapsed, kern_ms = run_timed(single_step)
+        elapsed, kern_ms, outputs = run_timed(single_step)
+    if outputs is not None:
+        dump_outputs(a.dump_outputs, outputs)
 
-    # SURVEY.md 8(d) extras, outside the timed region, N=1 only: (i) the same launch with L2 + Infinity Cache
+    # SURVEY.md 8(d) extras, outside the timed region, N=1 and --full only: (i) the same launch with L2 + Infinity Cache
     # flushed first (a 1 GiB fill evicts the 256 MiB MALL), (ii) this box's device-to-device copy rate, the
     # "measured peak" the roofline fraction is also quoted against.
     cold_ms = copy_gbps = None
-    if not multi:
+    if not multi and a.full:
         scratch = torch.empty(1 << 28, dtype=torch.float32, device=dev)
         colds = []
         for _ in range(3):
@@ -1732,7 +1781,7 @@ def main():
         copy_gbps = 10 * 2 * half * 4 / (s0.elapsed_time(e0) * 1e-3) / 1e9      # bytes read + written
         del scratch
 
-    # backward of SpMM-sum = the same kernel on A^T (csrc/fusedmm.cpp:285); reported beside the metric
+    # backward of SpMM-sum = the same kernel on A^T (csrc/fusedmm.cpp:285); reported beside the metric (--full)
     bwd = None
     if not multi and not a.no_backward and a.reduce == "sum":
         colptr, _, row_t, val_t = cabi.csr2csc(rowptr, col, val, n, want_perm=False, want_val=val is not None)

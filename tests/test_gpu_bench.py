@@ -63,7 +63,7 @@ def test_one_rank_rccl_rehearsal_prints_exactly_one_line_on_stdout(gpu):
 
 
 def test_default_line_carries_the_contract_fields(gpu):
-    """The JSON line of `python bench.py` (one GPU): every field the driver's contract names, the `roofline` and
+    """The JSON line of `python bench.py --full` (one GPU): every field the driver's contract names, the `roofline` and
     `cpu_baseline` objects, and the secondary gather ceiling -- on a scaled graph so that the oracle's leg takes seconds."""
     import json
     import subprocess
@@ -71,7 +71,7 @@ def test_default_line_carries_the_contract_fields(gpu):
     env = dict(os.environ)
     for name in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "ISPLIB_BENCH_FORCE_DIST"):
         env.pop(name, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--scale", "0.05", "--no-extra"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "4", "--warmup", "2", "--scale", "0.05", "--no-extra"]
     proc = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=420)
     assert proc.returncode == 0, proc.stderr[-2000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.strip()]
@@ -96,6 +96,44 @@ def test_default_line_carries_the_contract_fields(gpu):
         assert key in cpu, key
     assert cpu["kind"] in ("port", "reference") and cpu["unit"] == "edges/s" and cpu["cores"] >= 1 and cpu["value"] > 0
     assert abs(rec["value"] - int(rec["config"]["workload"].split("nnz=")[1].split(")")[0]) / (rec["ms_per_step"] * 1e-3)) < 1e-6 * rec["value"]
+
+
+def test_plain_line_times_only_the_steps_and_dumps_the_last_one(gpu, oracle_mod, tmp_path):
+    """`python bench.py` without --full: the headline fields only (no backward, CPU baseline, cold-cache probe or `extra`),
+    exactly --steps timed steps, and --dump-outputs writes the last step's output: the whole array at this size, equal
+    to the oracle's SpMM on the same seeded inputs, and the same bits from a second run."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    from isplib_amd import synth
+    env = dict(os.environ)
+    for name in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "ISPLIB_BENCH_FORCE_DIST"):
+        env.pop(name, None)
+    outs = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--scale", "0.05",
+               "--dump-outputs", str(d)]
+        proc = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
+        assert proc.returncode == 0, proc.stderr[-2000:]
+        lines = [ln for ln in proc.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, proc.stdout[:1000]
+        rec = json.loads(lines[0])
+        assert (rec["steps"], rec["warmup"]) == (3, 1) and rec["ms_per_step"] > 0 and rec["dtype"] == "f32"
+        assert rec["metric"] == "edges_aggregated_per_sec" and rec["unit"] == "edges/s" and rec["higher_is_better"] is True
+        assert not {"cpu_baseline", "backward", "extra"} & set(rec)
+        assert rec["roofline"]["kernel_cold_cache_ms"] is None and rec["roofline"]["peak_measured_copy"] is None
+        assert sorted(os.listdir(d)) == ["out.npy"]
+        outs.append(np.load(d / "out.npy"))
+    rowptr, col, n = synth.dataset_like("reddit", device=gpu, scale=0.05)
+    x = synth.features(n, 128, device=gpu)
+    assert outs[0].dtype == np.float32 and outs[0].shape == (n, 128)
+    rp, cl, xx = rowptr.cpu().numpy(), col.cpu().numpy(), x.cpu().numpy()
+    ref, _ = oracle_mod.spmm_fw(rp, cl, np.ones(cl.size, np.float32), xx, "sum")
+    mag, _ = oracle_mod.spmm_fw(rp, cl, np.ones(cl.size, np.float32), np.abs(xx), "sum")
+    assert np.all(np.abs(outs[0] - ref) <= 1e-5 * mag + 1e-30)
+    assert np.array_equal(outs[0], outs[1])
 
 
 def test_epoch_emulated_block_times_sampled_ranks_and_models_the_exchange(gpu):

@@ -549,6 +549,32 @@ def test_bench_self_launches_one_rank_per_gpu_and_refuses_missing_gpus():
     assert r.returncode != 0 and "WORLD_SIZE=2" in (r.stderr + r.stdout)
 
 
+def test_bench_output_sample_is_whole_rows_seeded_and_within_budget(tmp_path):
+    """`bench.py --dump-outputs`: outputs that fit are written whole; larger ones as a seeded sample of whole rows (the same
+    rows of `out` and `arg`, the same rows on every call), within the byte budget, float32 values and float64 positions."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    out = torch.arange(1000 * 8, dtype=torch.float32).reshape(1000, 8)
+    arg = torch.arange(1000 * 8, dtype=torch.int64).reshape(1000, 8) + (1 << 40)
+    whole = bench.sample_outputs(out, arg)
+    assert set(whole) == {"out", "arg"} and whole["out"].dtype == np.float32 and whole["arg"].dtype == np.float64
+    assert np.array_equal(whole["out"], out.numpy()) and np.array_equal(whole["arg"].astype(np.int64), arg.numpy())
+    budget = 100 * (8 * 4 + 8 * 8)
+    part = bench.sample_outputs(out, arg, budget=budget)
+    assert part["out"].shape == (100, 8) and part["out"].nbytes + part["arg"].nbytes <= budget
+    rows = part["out"][:, 0].astype(np.int64) // 8
+    assert np.all(np.diff(rows) > 0) and np.array_equal(part["out"], out.numpy()[rows])
+    assert np.array_equal(part["arg"].astype(np.int64), arg.numpy()[rows])
+    again = bench.sample_outputs(out, arg, budget=budget)
+    assert np.array_equal(again["out"], part["out"]) and np.array_equal(again["arg"], part["arg"])
+    assert set(bench.sample_outputs(out, budget=budget)) == {"out"}
+    bench.dump_outputs(str(tmp_path / "d"), part)
+    assert sorted(os.listdir(tmp_path / "d")) == ["arg.npy", "out.npy"]
+    assert np.array_equal(np.load(tmp_path / "d" / "out.npy"), part["out"])
+
+
 def _slice_table_np(rowptr, col, n, slices):
     w = -(-n // slices)
     m = rowptr.size - 1
