@@ -445,6 +445,13 @@ int    fusedMM_csr_ordered_hip(int32_t imessage, int64_t m, int64_t n, int64_t k
                                const int32_t *row_order /*[dev] m | NULL*/, const float *y, int64_t ldy, float *z,
                                int64_t ldz, int64_t *z_arg, void *stream);
 
+/* 1 when fusedMM_csr_hip (rows in index order) switches to the 128-column panel form above for a dense operand of n rows
+ * with leading dimension ldy (n * ldy * 4 > 256 MiB; it applies to k > 128 on 16-byte rows), else 0.  A caller that must
+ * reproduce the bits of a call on another operand size -- a row shard reading a padded gather buffer of more rows than
+ * the single-device operand -- runs fusedMM_csr_ordered_hip with the identity order where only its own size is past
+ * the switch: that launch never panels and is otherwise the index-order one. */
+int    isplib_plain_panels(int64_t n, int64_t ldy);
+
 /* The order for fusedMM_csr_ordered_hip, found on the device (square graphs): synchronous label propagation -- every
  * row takes the label most of its stored entries' columns carry, ties by a per-round hash of the label, at most `rounds`
  * rounds (8 is plenty; it stops when fewer than 1 % of the rows change) -- then the rows sorted by label, index order

@@ -56,7 +56,7 @@ EXPORTS = (
     "isplib_fusedmm_stream_geometry", "isplib_suggest_fusedmm_stream", "isplib_stream_plan_build_fusedmm_hip", "fusedMM_csr_udef_stream_hip",
     "isplib_row_scale_hip", "isplib_masked_scale_colsum_hip", "isplib_masked_scale_colsum_workspace_bytes",
     "fusedMM_csr_ordered_hip", "isplib_community_order_hip", "isplib_community_order_workspace_bytes", "isplib_order_locality_hip",
-    "isplib_graph_set_row_order",
+    "isplib_graph_set_row_order", "isplib_plain_panels",
 )
 
 # include/isplib_hip_experimental.h (libisplib_hip_exp.so): forms measured slower than the defaults; tests and experiment scripts only
@@ -238,6 +238,8 @@ def lib() -> ctypes.CDLL:
         L.isplib_graph_set_row_order.argtypes = [_vp, _vp, _vp]
         L.fusedMM_csr_ordered_hip.restype = ctypes.c_int
         L.fusedMM_csr_ordered_hip.argtypes = [_i32, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp]
+        L.isplib_plain_panels.restype = ctypes.c_int
+        L.isplib_plain_panels.argtypes = [_i64, _i64]
         L.isplib_suggest_stream.restype = ctypes.c_int
         L.isplib_suggest_stream.argtypes = [_i64, _i64, _i64, _i64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
         L.isplib_suggest_stream_weighted.restype = ctypes.c_int
@@ -397,6 +399,11 @@ def fusedMM_csr_ordered_hip(imessage: int, rowptr, col, val, order, y, z, z_arg=
     return st
 
 
+def plain_panels(n: int, ldy: int) -> bool:
+    """Whether fusedMM_csr_hip in index order runs K > 128 in 128-column panels for an [n, ldy] operand (isplib_plain_panels)."""
+    return bool(lib().isplib_plain_panels(int(n), int(ldy)))
+
+
 def spmm_ordered(rowptr, col, val, order, y, reduce: str = "sum"):
     """Allocate the outputs and call the ordered plain kernel; returns (out, arg|None)."""
     y = y.contiguous()
@@ -407,11 +414,41 @@ def spmm_ordered(rowptr, col, val, order, y, reduce: str = "sum"):
     return out, arg
 
 
+def reads_x(imessage: int) -> bool:
+    """Whether the generic pipeline reads the left operand x for this word (fusedmm_general.hip: needs_x)."""
+    vop, rop = imessage & 0xF, imessage & 0xF0
+    return vop != VOP["copy_rhs"] or rop in (ROP["dot"], ROP["add_lhs"], ROP["norml"])
+
+
+def check_fusedmm_operands(imessage: int, m: int, x, y, plan=None, x_read: Optional[bool] = None) -> None:
+    """Shapes of the FusedMM operands, checked before any library call: the kernels read x[i, :k] for every row i < m
+    and y[j, :k] for every stored column id j, and the C entries cannot know how many rows either tensor has.  y is
+    2-D; x, where the word reads it (`x_read`: the kernel's own rule, default reads_x), is [m, k]; a plan must have been
+    built for m rows over y's rows."""
+    if y.dim() != 2:
+        raise ValueError(f"isplib_amd: `y` must be 2-D [n, k], got shape {tuple(y.shape)}")
+    k = y.size(1)
+    if x_read is None:
+        x_read = reads_x(int(imessage))
+    if x is not None and x_read and (x.dim() != 2 or tuple(x.shape) != (m, k)):
+        raise ValueError(f"isplib_amd: `x` must be [m, k] = [{m}, {k}] for this message word, got shape {tuple(x.shape)}")
+    if plan is not None:
+        cols, rows = getattr(plan, "cols", None), getattr(plan, "rows", None)
+        if cols is not None and int(cols) != y.size(0):
+            raise ValueError(f"isplib_amd: the plan was built for {cols} columns, `y` has {y.size(0)} rows")
+        if rows is not None and int(rows) != m:
+            raise ValueError(f"isplib_amd: the plan was built for {rows} rows, the graph has {m}")
+        seg_off = getattr(plan, "seg_off", None)
+        if seg_off is not None and seg_off.numel() != plan.slices * m + 1:
+            raise ValueError(f"isplib_amd: the task plan was built for {(seg_off.numel() - 1) // max(plan.slices, 1)} rows, the graph has {m}")
+
+
 def fusedmm(imessage: int, rowptr, col, val, x, y, sop_udef="none", sop_param: float = 0.0, check: bool = True, plan=None):
     """The generic FusedMM pipeline (fusedMM_csr_udef_hip): z[i,:] = AOP_j VSC(SOP(ROP(VOP(x_i, y_j))), .) over the
     stored entries of row i.  `imessage` is a word built from VOP/ROP/SOP/VSC/AOP (or PATTERNS[name][0]);
     `sop_udef` names the built-in function a SOP_UDEF stage stands for.  With `plan` (isplib_amd.plan.TaskPlan) the
     task form runs (fusedMM_csr_udef_tasks_hip).  Returns (status, z, z_arg | None)."""
+    check_fusedmm_operands(imessage, rowptr.numel() - 1, x, y, plan)
     rowptr = _dev(rowptr, "rowptr", torch.int64)
     col = _dev(col, "col", torch.int64)
     if val is not None:
@@ -460,6 +497,9 @@ def fusedmm_stream_geometry(streams: int = 2):
 def fusedmm_stream(imessage: int, rowptr, nnz: int, plan, x, y, sop_udef="none", sop_param: float = 0.0, check: bool = True):
     """The two SDDMM-fused words on the stream front end (fusedMM_csr_udef_stream_hip); `plan`: a NativeStreamPlan built with
     fusedmm=True.  Returns (status, z)."""
+    if x is None:
+        raise ValueError("isplib_amd: the stream FusedMM words read `x`")
+    check_fusedmm_operands(imessage, rowptr.numel() - 1, x, y, plan, x_read=True)   # the kernel loads x[i] of every owned row
     rowptr = _dev(rowptr, "rowptr", torch.int64)
     x, y = _dev(x, "x", torch.float32), _dev(y, "y", torch.float32)
     m, n, k = rowptr.numel() - 1, y.size(0), y.size(1)

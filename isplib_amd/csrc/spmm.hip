@@ -414,6 +414,11 @@ static int launch_op(const SpmmArgs &a, hipStream_t st) {
 
 using namespace isplib;
 
+// The index-order launch runs K > 128 in 128-column panels (launch_vec) when the dense operand is beyond the Infinity Cache.
+extern "C" int isplib_plain_panels(int64_t n, int64_t ldy) {
+   return (n > 0 && ldy > 0 && (double)n * (double)ldy * 4.0 > 256.0 * 1048576.0) ? 1 : 0;
+}
+
 static int spmm_entry(int32_t imessage, int64_t m, int64_t n, int64_t k, int64_t nnz, const float *val,
                       const int64_t *indx, const int64_t *pntrb, const int64_t *pntre, const float *y, int64_t ldy,
                       float beta, float *z, int64_t ldz, int64_t *z_arg, const int64_t *sliceptr, int slices,
@@ -453,7 +458,7 @@ static int spmm_entry(int32_t imessage, int64_t m, int64_t n, int64_t k, int64_t
    a.sliceptr = nullptr; a.slices = 1; a.slice_first = 0; a.slice_count = 0; a.combine = 0;
    a.part_val = nullptr; a.part_idx = nullptr;
    a.row_order = row_order;
-   a.auto_panels = (!row_order && !sliceptr && (double)n * (double)ldy * 4.0 > 256.0 * 1048576.0) ? 1 : 0;
+   a.auto_panels = (!row_order && !sliceptr && isplib_plain_panels(n, ldy)) ? 1 : 0;
    if (sliceptr) {
       if (slices < 1 || slices > ISPLIB_MAX_SLICES) return fail(ISPLIB_FAIL, "fusedMM_csr_sliced_hip: slices must be in [1, 4096]");
       const size_t need = isplib_spmm_sliced_workspace_bytes(imessage, m, k, slices);

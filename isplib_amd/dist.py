@@ -57,6 +57,7 @@ class RowPartition:
                  rank: int, world: int, cuts: Optional[List[int]] = None, group=None):
         m = rowptr.numel() - 1
         self.rank, self.world, self.group = rank, world, group
+        self.ncols = ncols
         self.row_cuts = cuts if cuts is not None else nnz_balanced_cuts(rowptr, world)
         # X (ncols rows) is sharded with the same boundaries when A is square, evenly otherwise
         if ncols == m:
@@ -138,10 +139,26 @@ class RowPartition:
         self.all_gather(x_shard, buf)
         out = torch.empty((self.rows, k), dtype=torch.float32, device=x_shard.device)
         arg = torch.empty((self.rows, k), dtype=torch.int64, device=x_shard.device) if reduce in ("max", "min") else None
-        cabi.fusedMM_csr_hip(cabi.MESSAGE[reduce], self.rowptr, self.col_padded, self.val, buf, out, arg)
+        self.plain_spmm(cabi.MESSAGE[reduce], buf, out, arg)
         if arg is not None:
             arg = self.global_arg(arg)
         return out, arg
+
+    def plain_spmm(self, imessage: int, buf: torch.Tensor, out: torch.Tensor, arg: Optional[torch.Tensor] = None):
+        """The plain kernel on the gathered buffer, bit for bit the rows of the single-device fusedMM_csr_hip call on the
+        unpadded [ncols, K] operand.  That launch switches to its 128-column panel form (a row's sums associated over two
+        slots) by the size of the dense operand (isplib_plain_panels), and the buffer has world * max_rows >= ncols rows:
+        where only the padded size is past the switch, the shard runs the identity order, which never panels and is
+        otherwise the same launch."""
+        from . import cabi
+        if cabi.plain_panels(self.ncols_padded, buf.stride(0)) and not cabi.plain_panels(self.ncols, buf.size(1)):
+            order = self.__dict__.get("_identity_order")
+            if order is None or order.device != buf.device:
+                order = self._identity_order = torch.arange(self.rows, dtype=torch.int32, device=buf.device)
+            cabi.fusedMM_csr_ordered_hip(imessage, self.rowptr, self.col_padded, self.val, order, buf, out, arg)
+        else:
+            cabi.fusedMM_csr_hip(imessage, self.rowptr, self.col_padded, self.val, buf, out, arg)
+        return out
 
     # ---- overlapped form: local column slices run while the all-gather is in flight ----------------
 
@@ -498,7 +515,7 @@ def _local_spmm(self, ops, buf: torch.Tensor, out: torch.Tensor, reduce: str = "
     elif kind == "tasks":
         cabi.fusedMM_csr_tasks_hip(msg, self.rowptr, self.col_padded, self.val, plan, buf, out, arg, work)
     else:
-        cabi.fusedMM_csr_hip(msg, self.rowptr, self.col_padded, self.val, buf, out, arg)
+        self.plain_spmm(msg, buf, out, arg)
     return out
 
 

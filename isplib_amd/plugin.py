@@ -326,9 +326,16 @@ def fusedmm(src, x: Optional[torch.Tensor], y: torch.Tensor, pattern="sigmoid_em
         word, fn = cabi.PATTERNS[pattern]
     else:
         word, fn = int(pattern), (sop_udef or "none")
+    if y.dim() != 2:
+        raise ValueError(f"isplib_amd: `y` must be 2-D [n, k], got shape {tuple(y.shape)}")
     st = _storage_of(src, y)
     k = y.size(1)
     m_rows = st._rowptr.numel() - 1
+    # before any library call: the kernels read x[i] for every row and y[j] for every stored column id, and the plans
+    # cached on the storage were built for its column count
+    cabi.check_fusedmm_operands(word, m_rows, x, y)
+    if y.size(0) != st._sparse_sizes[1]:
+        raise ValueError(f"isplib_amd: `y` must have one row per column of the sparse matrix ({st._sparse_sizes[1]}), got {y.size(0)}")
     # the two hot SDDMM-fused words on graphs with work for the whole chip: the stream front end (rows of x and z resident in
     # LDS; include/isplib_hip.h: fusedMM_csr_udef_stream_hip) -- Reddit shape K=128: 6.3 ms on the task list below
     geom = None

@@ -1034,3 +1034,82 @@ def test_exchange_schedules_park_local_kernel_errors_until_their_collectives_are
     with pytest.raises(Exception) as info:           # (no GPU here: the schedule's own first kernel call fails -- THAT is what surfaces)
         part.spmm_pipelined(x, out, ([(0, 4)], [torch.zeros((part.max_rows, 4))], [torch.zeros((part.ncols_padded, 4))], object(), None), "sum")
     assert "stale" not in str(info.value) and part._parked is None
+
+
+def test_fusedmm_wrappers_refuse_misshaped_operands_before_any_library_call(monkeypatch):
+    """The FusedMM kernels read x[i, :k] for every row i of the graph and y[j, :k] for every stored column id j; the C
+    entries cannot know either tensor's row count, so a wrong-shaped operand is an out-of-bounds device read unless the
+    wrapper refuses it.  cabi.fusedmm, cabi.fusedmm_stream and plugin.fusedmm raise ValueError on a wrong x (rows,
+    width, 1-D), a 1-D y, and a plan built for another shape -- before the library is touched (it is stubbed here so
+    that any call fails).  Correct shapes get past the check (to the GPU-tensor check or the stubbed library)."""
+    import isplib_amd
+    from isplib_amd import cabi
+
+    class LibraryCalled(Exception):
+        pass
+
+    def no_library(*a, **k):
+        raise LibraryCalled()
+    monkeypatch.setattr(cabi, "lib", no_library)
+    m, n, k = 6, 5, 8
+    rowptr = torch.tensor([0, 2, 3, 3, 5, 6, 8], dtype=torch.int64)
+    col = torch.tensor([0, 4, 1, 2, 3, 4, 0, 1], dtype=torch.int64)
+    x, y = torch.ones((m, k)), torch.ones((n, k))
+    sig = cabi.PATTERNS["sigmoid_embedding"][0]
+    tdist = cabi.PATTERNS["tdist_embedding"][0]
+    bad_x = {"rows": torch.ones((m + 1, k)), "fewer rows": torch.ones((m - 1, k)), "width": torch.ones((m, k + 4)),
+             "1-D": torch.ones(m * k), "3-D": torch.ones((1, m, k))}
+    bad_y = {"1-D": torch.ones(n * k), "3-D": torch.ones((1, n, k))}
+    stream_plan = types.SimpleNamespace(rows=m, cols=n, slices=1)
+    task_plan = types.SimpleNamespace(slices=2, seg_off=torch.zeros(2 * m + 1, dtype=torch.int32))
+
+    # the generic pipeline (plain and task forms); copy_lhs, add, dot and norml words read x
+    for word in (sig, tdist, cabi.VOP["copy_lhs"] | cabi.AOP["add"], cabi.VOP["copy_rhs"] | cabi.ROP["norml"] | cabi.SOP["copy"] | cabi.AOP["max"]):
+        for plan in (None, task_plan):
+            for name, xb in bad_x.items():
+                with pytest.raises(ValueError, match="`x`"):
+                    cabi.fusedmm(word, rowptr, col, None, xb, y, sop_udef="sigmoid", plan=plan)
+            for name, yb in bad_y.items():
+                with pytest.raises(ValueError, match="`y`"):
+                    cabi.fusedmm(word, rowptr, col, None, x, yb, sop_udef="sigmoid", plan=plan)
+            with pytest.raises(RuntimeError, match="GPU tensor"):           # well-shaped: on to the device check
+                cabi.fusedmm(word, rowptr, col, None, x, y, sop_udef="sigmoid", plan=plan)
+    with pytest.raises(RuntimeError, match="GPU tensor"):                       # x is not read: its shape is not the kernel's business
+        cabi.fusedmm(cabi.MSG_SPMM_SUM, rowptr, col, None, bad_x["rows"], y)
+    for seg_rows in (m - 1, m + 1):                                               # a task plan built for another row count
+        other = types.SimpleNamespace(slices=2, seg_off=torch.zeros(2 * seg_rows + 1, dtype=torch.int32))
+        with pytest.raises(ValueError, match="plan"):
+            cabi.fusedmm(sig, rowptr, col, None, x, y, sop_udef="sigmoid", plan=other)
+
+    # the stream front end: it loads x[i] of every row it owns, whatever the word
+    for word in (sig, tdist, cabi.MSG_SPMM_SUM):
+        for name, xb in bad_x.items():
+            with pytest.raises(ValueError, match="`x`"):
+                cabi.fusedmm_stream(word, rowptr, col.numel(), stream_plan, xb, y, sop_udef="sigmoid")
+        for name, yb in bad_y.items():
+            with pytest.raises(ValueError, match="`y`"):
+                cabi.fusedmm_stream(word, rowptr, col.numel(), stream_plan, x, yb, sop_udef="sigmoid")
+        with pytest.raises(ValueError, match="`x`"):
+            cabi.fusedmm_stream(word, rowptr, col.numel(), stream_plan, None, y, sop_udef="sigmoid")
+        for plan in (types.SimpleNamespace(rows=m, cols=n + 1, slices=1), types.SimpleNamespace(rows=m, cols=n - 1, slices=1),
+                     types.SimpleNamespace(rows=m + 1, cols=n, slices=1)):
+            with pytest.raises(ValueError, match="plan"):                     # built for another shape
+                cabi.fusedmm_stream(word, rowptr, col.numel(), plan, x, y, sop_udef="sigmoid")
+        with pytest.raises(RuntimeError, match="GPU tensor"):
+            cabi.fusedmm_stream(word, rowptr, col.numel(), stream_plan, x, y, sop_udef="sigmoid")
+
+    # the plug-in: the same checks, and y's rows against the sparse matrix's column count
+    adj = isplib_amd.SparseTensor.from_csr(rowptr, col, None, (m, n), validate=False)
+    for pattern in ("sigmoid_embedding", "tdist_embedding", "attention_sum"):
+        for name, xb in bad_x.items():
+            with pytest.raises(ValueError, match="`x`"):
+                isplib_amd.fusedmm(adj, xb, y, pattern)
+        for name, yb in bad_y.items():
+            with pytest.raises(ValueError, match="`y`"):
+                isplib_amd.fusedmm(adj, x, yb, pattern)
+        for rows in (n - 1, n + 1):
+            with pytest.raises(ValueError, match="`y`"):
+                isplib_amd.fusedmm(adj, x, torch.ones((rows, k)), pattern)
+        with pytest.raises(LibraryCalled):                                      # well-shaped: on to the schedule rule
+            isplib_amd.fusedmm(adj, x, y, pattern)
+    assert not cabi.reads_x(cabi.MSG_SPMM_SUM) and all(cabi.reads_x(w) for w in (sig, tdist, cabi.VOP["add"] | cabi.AOP["max"]))
