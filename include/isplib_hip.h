@@ -73,6 +73,36 @@ extern "C" {
 int         isplib_hip_abi_version(void);
 const char *isplib_hip_last_error(void);   /* thread-local, "" if none */
 
+/* ---- address domains of the kernel families ------------------------------------------------------------------------
+ * Every schedule has a hard domain set by how its kernel forms addresses.  This is its ONE statement: the entries below
+ * refuse a call outside their domain (ISPLIB_FAIL; the generic pipeline ISPLIB_NO_OPT_IMPL), and every layer that picks a
+ * schedule for a call -- the isplib_suggest_stream* rules, the isplib_graph_* handle, the torch op layer, the Python
+ * layers through the mirror in isplib_amd/cabi.py -- asks the same predicates with the leading dimension the call will really use, so a
+ * shape is never offered a schedule whose entry then refuses it.  _MAX: the largest value served; _END: the first refused. */
+#define ISPLIB_DENSE_BYTES_MAX         0xE0000000u  /* 3.5 GiB: n*ldy*4 of a dense operand read through one buffer descriptor */
+#define ISPLIB_DENSE_OOB_OFFSET        0xF0000000u  /* a byte offset such a descriptor answers with 0 (masked lanes carry it);
+                                                       + any column offset (< 2^24) stays < 2^32: never wraps */
+#define ISPLIB_STREAM_N_END            (1 << 24)    /* stream words are (local row << 24) | column, multiplied in 24 bits */
+#define ISPLIB_STREAM_LDY_END          (1 << 22)    /* ... by a row pitch in BYTES that has to fit 24 bits too */
+#define ISPLIB_STREAM_NNZ_END          (1LL << 31)  /* 32-bit CSR positions in a stream plan */
+#define ISPLIB_STREAM_MINMAX_BYTES_END 0x80000000u  /* 2 GiB: lanes past column k of the max / min stream kernel carry 2^31 */
+#define ISPLIB_K_MIN                   4            /* every entry that takes a plan; narrower operands: fusedMM_csr_hip */
+#define ISPLIB_SDDMM_TASKS_K_MAX       1024         /* isplib_sddmm_csr_tasks_hip holds g[row, :] in registers */
+
+/* n rows of ldy floats take at most `bytes` bytes (exact for any operands: no product is formed) */
+static inline int isplib_rows_within(int64_t n, int64_t ldy, uint64_t bytes) { return n <= 0 || ldy <= (int64_t)(bytes / 4 / (uint64_t)n); }
+/* the dense operand fits one buffer descriptor: what every entry but the plain kernel's needs */
+static inline int isplib_dense_in_descriptor(int64_t n, int64_t ldy) { return isplib_rows_within(n, ldy, ISPLIB_DENSE_BYTES_MAX); }
+/* the task-list entries (fusedMM_csr_tasks_hip, _epilogue_hip) serve an n x k operand at leading dimension ldy */
+static inline int isplib_tasks_serve(int64_t n, int64_t k, int64_t ldy) { return k >= ISPLIB_K_MIN && isplib_dense_in_descriptor(n, ldy); }
+/* isplib_sddmm_csr_tasks_hip does */
+static inline int isplib_sddmm_tasks_serve(int64_t n, int64_t k, int64_t ldy) { return k <= ISPLIB_SDDMM_TASKS_K_MAX && isplib_tasks_serve(n, k, ldy); }
+/* the stream entries (fusedMM_csr_stream_hip; minmax != 0: fusedMM_csr_stream_minmax_hip) and the builders of their plans do */
+static inline int isplib_stream_serves(int64_t n, int64_t k, int64_t ldy, int64_t nnz, int minmax) {
+   return isplib_tasks_serve(n, k, ldy) && n < ISPLIB_STREAM_N_END && ldy < ISPLIB_STREAM_LDY_END && nnz < ISPLIB_STREAM_NNZ_END &&
+          (!minmax || isplib_rows_within(n, ldy, ISPLIB_STREAM_MINMAX_BYTES_END - 1u));
+}
+
 /*
  * The one convention of this path that nothing in the reference tree pins: what an EMPTY row of a max / min SpMM holds.
  * The reference launcher pre-fills the output with lowest() / max() and the positions with nnz (csrc/fusedmm.cpp:147-150,
@@ -232,7 +262,7 @@ int    fusedMM_csr_sliced_phase_hip(int32_t imessage, int64_t m, int64_t n, int6
  *   (s' = (s % 8) * (slices / 8) + s / 8), slices*m + 1 entries.
  * Each task writes one partial row into the workspace (isplib_spmm_tasks_workspace_bytes);
  * a second kernel folds a row's partials in ascending CSR order.  Same results and conventions
- * as fusedMM_csr_hip; requires k >= 4 and n*ldy*4 <= 3.5 GiB.
+ * as fusedMM_csr_hip; domain: isplib_tasks_serve(n, k, ldy) -- k >= ISPLIB_K_MIN, n*ldy*4 <= ISPLIB_DENSE_BYTES_MAX.
  */
 typedef struct isplib_task_plan_info {
    int64_t n_tasks;
@@ -338,8 +368,9 @@ int    isplib_masked_scale_colsum_hip(int64_t n, int64_t k, const float *dz, int
  * isplib_spmm_stream_geometry reports the rows per wave the kernel of a slot width is built for and the waves the
  * device holds at once (what waves_per_gen should be: persistent waves only stay on the same slices -- and the slices
  * in the L2 -- when they all start together).
- * Requirements: k >= 4 (any k: a last vector that would reach past column k is shifted back to end there; rows need
- * only 4-byte alignment), n < 2^24 and ldy < 2^22 (24-bit address arithmetic per edge), n*ldy*4 <= 3.5 GiB.
+ * Domain: isplib_stream_serves(n, k, ldy, nnz, 0) -- k >= ISPLIB_K_MIN (any k: a last vector that would reach past column
+ * k is shifted back to end there; rows need only 4-byte alignment), n < ISPLIB_STREAM_N_END and ldy < ISPLIB_STREAM_LDY_END
+ * (24-bit address arithmetic per edge), n*ldy*4 <= ISPLIB_DENSE_BYTES_MAX; the plan builders need nnz < ISPLIB_STREAM_NNZ_END.
  */
 typedef struct isplib_stream_plan {
    int64_t rows, cols;              /* m, n of the graph the plan was built for */
@@ -384,7 +415,7 @@ int    isplib_suggest_stream_weighted(int64_t m, int64_t n, int64_t nnz, int64_t
  * position) pairs into their fold.  Slots of 64 columns (streams = 4) or, for k <= 32, of 32 columns (streams = 8), with
  * half the rows per wave of the sum kernel, so max / min plans are built for isplib_spmm_stream_minmax_geometry -- isplib_stream_plan_build_minmax_hip
  * does that and returns ISPLIB_FAIL for a graph with an unsorted row (use the task list) -- and are not interchangeable
- * with sum plans.  nnz < 2^31.  z_arg (may be NULL): [m][ldz] int64 CSR positions, nnz = empty row.  With z_arg = NULL the
+ * with sum plans.  Domain: isplib_stream_serves(n, k, ldy, nnz, 1) -- the sum entry's and n*ldy*4 < ISPLIB_STREAM_MINMAX_BYTES_END.  z_arg (may be NULL): [m][ldz] int64 CSR positions, nnz = empty row.  With z_arg = NULL the
  * launch is a values-only one: no position is tracked at all (a quarter of the loop's vector instructions), same plan,
  * same values bit for bit. */
 int    isplib_spmm_stream_minmax_geometry(int streams /* 4 | 8 */, int *rows_per_wave /*out*/, int *waves_resident /*out*/);
@@ -416,7 +447,7 @@ int    fusedMM_csr_stream_hip(int32_t imessage /* ISPLIB_MSG_SPMM_SUM | _MEAN */
  * the user function).  Plans: isplib_stream_plan_build_fusedmm_hip (its own geometry: isplib_fusedmm_stream_geometry; streams
  * 2 / 4 / 8 = slots of 128 / 64 / 32 columns); isplib_suggest_fusedmm_stream is the rule (0: stay on the task list);
  * workspace: isplib_spmm_stream_workspace_bytes(plan).  k a multiple of 4, ldx and ldz multiples of 4, x and z 16-byte
- * aligned, n < 2^24, n*ldy*4 <= 3.5 GiB.  Other words return ISPLIB_NO_OPT_IMPL.
+ * aligned, n < ISPLIB_STREAM_N_END, ldy < ISPLIB_STREAM_LDY_END, n*ldy*4 <= ISPLIB_DENSE_BYTES_MAX.  Other words return ISPLIB_NO_OPT_IMPL.
  */
 int    isplib_fusedmm_stream_geometry(int streams, int *rows_per_wave /*out*/, int *waves_resident /*out*/);
 int    isplib_suggest_fusedmm_stream(int32_t imessage, int64_t m, int64_t n, int64_t nnz, int64_t k, int *streams, int *slices, int *chunk);
@@ -530,7 +561,8 @@ int isplib_sddmm_csr_hip(int64_t m, int64_t k, const int64_t *indx,
                          const float *y, int64_t ldy, const float *g,
                          int64_t ldg, int mean, float *dval, void *stream);
 /* The same over the task plan of the SpMM (one wave per task, XCD-lane grouping -> the L2 affinity of
- * the task-list SpMM; dval is per edge, so no workspace and no combine).  4 <= k <= 1024. */
+ * the task-list SpMM; dval is per edge, so no workspace and no combine).  Domain: isplib_sddmm_tasks_serve(n, k, ldy) --
+ * ISPLIB_K_MIN <= k <= ISPLIB_SDDMM_TASKS_K_MAX, n*ldy*4 <= ISPLIB_DENSE_BYTES_MAX. */
 int isplib_sddmm_csr_tasks_hip(int64_t m, int64_t n, int64_t k, const int64_t *indx,
                                const int32_t *indx32 /*optional, as in fusedMM_csr_tasks_hip*/,
                                const int64_t *pntrb, const int64_t *pntre,

@@ -24,7 +24,7 @@ extern "C" {
  * waves, and only their partial rows (n_parts of them) pass through the workspace.  No atomics: a row's tasks are
  * folded by one wave in ascending CSR order, results are bitwise reproducible and max/min ties go to the lowest
  * CSR position.  Requires column-sorted rows, k % 4 == 0, ldy % 4 == 0, ldz % 4 == 0, y and z 16-byte aligned,
- * n*ldy*4 <= 3.5 GiB (otherwise use fusedMM_csr_tasks_hip / fusedMM_csr_hip).
+ * n*ldy*4 <= ISPLIB_DENSE_BYTES_MAX (otherwise use fusedMM_csr_tasks_hip / fusedMM_csr_hip).
  *   plan (host struct, device arrays; isplib_amd/plan.py builds it on the device):
  *     wave w of generation g = global wave g*waves_per_gen + w;
  *     wave_row [wave][slot]  row of the slot, -1 = unused      wave_part[wave][slot]  -1 = whole row, else partial row id
@@ -63,7 +63,7 @@ int    fusedMM_csr_sweep_hip(int32_t imessage, int64_t m, int64_t n, int64_t k, 
  * and the same front end; the wave's rows of g sit in LDS where the SpMM keeps its accumulators, every step yields one
  * dot product per slot, and a batch's results are stored through `perm` once.  k is swept in panels of 256 / streams
  * columns; later panels add to what earlier ones stored.  Plain stores by the one owner of every edge: bitwise
- * reproducible.  k >= 4, n < 2^24, ldy < 2^22, n*ldy*4 <= 3.5 GiB, nnz < 2^31. */
+ * reproducible.  Domain: isplib_stream_serves(n, k, ldy, nnz, 0) of include/isplib_hip.h. */
 int    isplib_sddmm_stream_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *pntrb, const int64_t *pntre,
                                const isplib_stream_plan *plan /*host*/, const float *y, int64_t ldy,
                                const float *g /*[dev] m x ldg*/, int64_t ldg, int mean, float *dval /*[dev] nnz*/, void *stream);

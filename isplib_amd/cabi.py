@@ -23,8 +23,20 @@ MSG_SPMM_MAX = 0x2 | 0x00 | 0x100 | 0x1000 | 0x20000
 MSG_SPMM_MIN = 0x2 | 0x00 | 0x100 | 0x1000 | 0x30000
 MESSAGE = {"sum": MSG_SPMM_SUM, "add": MSG_SPMM_SUM, "mean": MSG_SPMM_MEAN, "max": MSG_SPMM_MAX, "min": MSG_SPMM_MIN}
 
+# status codes (csrc/fusedMM.h:105-114 of the reference + one for HIP runtime errors), under the header's names and short ones
 SUCCESS, FAIL, NOT_ENOUGH_MEM, NO_OPT_IMPL, HIP_ERROR = 0, 1, -1, 128, 256
 UNDEFINED_USER_FUNCTION = 64
+ISPLIB_SUCCESS, ISPLIB_FAIL, ISPLIB_NOT_ENOUGH_MEM, ISPLIB_NO_OPT_IMPL, ISPLIB_HIP_ERROR = SUCCESS, FAIL, NOT_ENOUGH_MEM, NO_OPT_IMPL, HIP_ERROR
+
+# the address domains of the kernel families (the header's section of that name is the contract; tests/test_host.py compares)
+DENSE_BYTES_MAX = 7 * 2 ** 29           # n * ldy * 4 of a dense operand read through one buffer descriptor: 3.5 GiB
+DENSE_OOB_OFFSET = 15 * 2 ** 28         # a byte offset such a descriptor answers with 0
+STREAM_N_END = 2 ** 24                  # the stream schedules: n <, ldy <, nnz <
+STREAM_LDY_END = 2 ** 22
+STREAM_NNZ_END = 2 ** 31
+STREAM_MINMAX_BYTES_END = 2 ** 31       # max / min on the stream schedule: n * ldy * 4 < 2 GiB
+K_MIN = 4                               # every entry that takes a plan
+SDDMM_TASKS_K_MAX = 1024
 
 # FusedMM stage flags (csrc/fusedMM.h:18-74) and the built-in SOP_UDEF menu (enum isplib_sop_udef)
 VOP = {"copy_lhs": 0x1, "copy_rhs": 0x2, "add": 0x3, "subl": 0x4, "subr": 0x5, "max": 0x6, "min": 0x7, "udef": 0xF}
@@ -293,10 +305,6 @@ def exp_lib() -> ctypes.CDLL:
 
 def last_error() -> str:
     return lib().isplib_hip_last_error().decode()
-
-
-# status codes of include/isplib_hip.h (csrc/fusedMM.h:105-114 of the reference)
-ISPLIB_SUCCESS, ISPLIB_FAIL, ISPLIB_NOT_ENOUGH_MEM, ISPLIB_NO_OPT_IMPL, ISPLIB_HIP_ERROR = 0, 1, -1, 128, 256
 
 
 class IsplibError(RuntimeError):

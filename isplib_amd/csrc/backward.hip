@@ -128,7 +128,6 @@ __global__ __launch_bounds__(WAVES * 64) void sddmm_csr_kernel(const SddmmArgs a
 // One wave per task: the task's edges all lie in one column slice, tasks are grouped by XCD lane, so
 // the gathers of y enjoy the same L2 affinity as the task-list SpMM -- and since dval is per edge,
 // no partials and no combine are needed at all.  g[row, :] sits in registers for the whole task.
-constexpr unsigned SD_BUF_LIMIT = 0xE0000000u, SD_BUF_OOB = 0xF0000000u;
 typedef __attribute__((__vector_size__(4 * sizeof(int)))) int sd_v4i_t;
 
 struct SddmmTaskArgs {
@@ -173,7 +172,7 @@ __global__ __launch_bounds__(WAVES * 64, NCH == 1 ? 8 : 1) void sddmm_task_kerne
       int vfirst = 0;
       const bool ok = c < (int)a.k;
       if (ok && c + 4 > (int)a.k) { vfirst = c + 4 - (int)a.k; c = (int)a.k - 4; }
-      cbyte[j] = ok ? (unsigned)c * 4u : SD_BUF_OOB;
+      cbyte[j] = ok ? (unsigned)c * 4u : BUF_OOB;
       const float *gr = a.g + (size_t)row * (size_t)a.ldg + c;
 #pragma unroll
       for (int v = 0; v < 4; v++) gv[j][v] = (ok && v >= vfirst) ? gr[v] : 0.0f;
@@ -190,7 +189,7 @@ __global__ __launch_bounds__(WAVES * 64, NCH == 1 ? 8 : 1) void sddmm_task_kerne
    const int my_step = lane / EPS;
    for (int64_t base = b; base < e; base += 64) {
       const int64_t p = base + lane;
-      const unsigned off_l = p < e ? (a.indx32 ? (unsigned)a.indx32[p] : (unsigned)a.indx[p]) * ldyb : SD_BUF_OOB;
+      const unsigned off_l = p < e ? (a.indx32 ? (unsigned)a.indx32[p] : (unsigned)a.indx[p]) * ldyb : BUF_OOB;
       const int64_t left = e - base;
       const int cnt = left < 64 ? (int)left : 64;
       float old = 0.0f, res = 0.0f;
@@ -203,7 +202,7 @@ __global__ __launch_bounds__(WAVES * 64, NCH == 1 ? 8 : 1) void sddmm_task_kerne
             const unsigned off = (unsigned)__shfl((int)off_l, (s + u * G + g) & 63);
 #pragma unroll
             for (int j = 0; j < NCH; j++) {
-               const unsigned o = cbyte[j] >= SD_BUF_OOB ? SD_BUF_OOB : off + cbyte[j];
+               const unsigned o = cbyte[j] >= BUF_OOB ? BUF_OOB : off + cbyte[j];
                yv[u][j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)o, 0, 0);
             }
          }
@@ -306,9 +305,9 @@ extern "C" int isplib_sddmm_csr_tasks_hip(int64_t m, int64_t n, int64_t k, const
    clear_error();
    if (m < 0 || n < 0 || k < 0 || n_tasks < 0) return fail(ISPLIB_FAIL, "isplib_sddmm_csr_tasks_hip: negative dimension");
    if (m == 0 || n_tasks == 0) return ISPLIB_SUCCESS;
-   if (k < 4 || k > 1024) return fail(ISPLIB_FAIL, "isplib_sddmm_csr_tasks_hip: 4 <= k <= 1024 required (use isplib_sddmm_csr_hip)");
+   if (k < ISPLIB_K_MIN || k > ISPLIB_SDDMM_TASKS_K_MAX) return fail(ISPLIB_FAIL, "isplib_sddmm_csr_tasks_hip: 4 <= k <= 1024 required (use isplib_sddmm_csr_hip)");
    const unsigned long long yb = (unsigned long long)n * (unsigned long long)ldy * 4ull;
-   if (yb > SD_BUF_LIMIT) return fail(ISPLIB_FAIL, "isplib_sddmm_csr_tasks_hip: dense operand larger than 3.5 GiB");
+   if (!isplib_dense_in_descriptor(n, ldy)) return fail(ISPLIB_FAIL, "isplib_sddmm_csr_tasks_hip: dense operand larger than 3.5 GiB");
    if (!indx || !pntrb || !pntre || !task_row || !task_b || !task_len || !lane_off_host || !y || !g || !dval)
       return fail(ISPLIB_FAIL, "isplib_sddmm_csr_tasks_hip: null operand");
    if (ldy < k || ldg < k) return fail(ISPLIB_FAIL, "isplib_sddmm_csr_tasks_hip: leading dimension smaller than k");

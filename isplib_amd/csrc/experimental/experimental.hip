@@ -623,7 +623,7 @@ extern "C" int fusedMM_csr_sweep_hip(int32_t imessage, int64_t m, int64_t n, int
       return fail(ISPLIB_FAIL, "fusedMM_csr_sweep_hip: k, ldy, ldz must be multiples of 4 and y, z 16-byte aligned (use fusedMM_csr_tasks_hip)");
    if (ldy < k || ldz < k) return fail(ISPLIB_FAIL, "fusedMM_csr_sweep_hip: leading dimension smaller than k");
    const unsigned long long yb = (unsigned long long)n * (unsigned long long)ldy * 4ull;
-   if (yb > BUF_LIMIT) return fail(ISPLIB_FAIL, "fusedMM_csr_sweep_hip: dense operand larger than 3.5 GiB (use fusedMM_csr_hip)");
+   if (!isplib_dense_in_descriptor(n, ldy)) return fail(ISPLIB_FAIL, "fusedMM_csr_sweep_hip: dense operand larger than 3.5 GiB (use fusedMM_csr_hip)");
    if (!pntrb || !pntre || !z || !y || (nnz > 0 && !indx) || !plan->wave_row || !plan->wave_part || !plan->wave_task_off ||
        (plan->n_tasks > 0 && (!plan->task_b || !plan->task_meta)) || (plan->n_hub > 0 && (!plan->hub_row || !plan->hub_off)))
       return fail(ISPLIB_FAIL, "fusedMM_csr_sweep_hip: null operand");
@@ -710,17 +710,17 @@ extern "C" int isplib_sddmm_stream_hip(int64_t m, int64_t n, int64_t k, int64_t 
    if (m == 0 || nnz == 0) return ISPLIB_SUCCESS;
    if (!plan) return fail(ISPLIB_FAIL, "isplib_sddmm_stream_hip: plan is required");
    if (plan->rows != m || plan->cols != n) return fail(ISPLIB_FAIL, "isplib_sddmm_stream_hip: the plan was built for another shape");
-   if (n >= (1LL << 24) || ldy >= (1LL << 22)) return fail(ISPLIB_FAIL, "isplib_sddmm_stream_hip: n must be < 2^24 and ldy < 2^22 (24-bit address arithmetic)");
-   if (nnz >= (1LL << 31)) return fail(ISPLIB_FAIL, "isplib_sddmm_stream_hip: nnz < 2^31 required (32-bit CSR positions in the plan)");
+   if (n >= ISPLIB_STREAM_N_END || ldy >= ISPLIB_STREAM_LDY_END) return fail(ISPLIB_FAIL, "isplib_sddmm_stream_hip: n must be < 2^24 and ldy < 2^22 (24-bit address arithmetic)");
+   if (nnz >= ISPLIB_STREAM_NNZ_END) return fail(ISPLIB_FAIL, "isplib_sddmm_stream_hip: nnz < 2^31 required (32-bit CSR positions in the plan)");
    if (plan->streams != 2 && plan->streams != 4 && plan->streams != 8)
       return fail(ISPLIB_FAIL, "isplib_sddmm_stream_hip: bad plan geometry (streams 2, 4 or 8)");
    if (plan->gens < 1 || plan->waves_per_gen < 1 || plan->rows_per_wave != stream_geom(plan->streams).nvmax)
       return fail(ISPLIB_FAIL, "isplib_sddmm_stream_hip: bad plan geometry (a sum / mean plan of isplib_spmm_stream_geometry is required)");
    if (plan->n_steps > 0 && !plan->perm) return fail(ISPLIB_FAIL, "isplib_sddmm_stream_hip: the plan's perm array is required (the CSR position of every word)");
-   if (k < 4) return fail(ISPLIB_FAIL, "isplib_sddmm_stream_hip: k >= 4 required (use isplib_sddmm_csr_hip)");
+   if (k < ISPLIB_K_MIN) return fail(ISPLIB_FAIL, "isplib_sddmm_stream_hip: k >= 4 required (use isplib_sddmm_csr_hip)");
    if (ldy < k || ldg < k) return fail(ISPLIB_FAIL, "isplib_sddmm_stream_hip: leading dimension smaller than k");
    const unsigned long long yb = (unsigned long long)n * (unsigned long long)ldy * 4ull;
-   if (yb > BUF_LIMIT) return fail(ISPLIB_FAIL, "isplib_sddmm_stream_hip: dense operand larger than 3.5 GiB (use isplib_sddmm_csr_hip)");
+   if (!isplib_dense_in_descriptor(n, ldy)) return fail(ISPLIB_FAIL, "isplib_sddmm_stream_hip: dense operand larger than 3.5 GiB (use isplib_sddmm_csr_hip)");
    if (!pntrb || !pntre || !y || !g || !dval || !plan->wave_row || !plan->wave_step_off || (plan->n_steps > 0 && !plan->words))
       return fail(ISPLIB_FAIL, "isplib_sddmm_stream_hip: null operand");
    SweepArgs a = {};
@@ -795,17 +795,17 @@ extern "C" int fusedMM_csr_hybrid_hip(int32_t imessage, int64_t m, int64_t n, in
    if (!hp) return fail(ISPLIB_FAIL, "fusedMM_csr_hybrid_hip: plan is required");
    const isplib_stream_plan *plan = &hp->cold;
    if (plan->rows != m || plan->cols != n) return fail(ISPLIB_FAIL, "fusedMM_csr_hybrid_hip: the plan was built for another shape");
-   if (n >= (1LL << 24) || ldy >= (1LL << 22)) return fail(ISPLIB_FAIL, "fusedMM_csr_hybrid_hip: n must be < 2^24 and ldy < 2^22 (24-bit address arithmetic)");
+   if (n >= ISPLIB_STREAM_N_END || ldy >= ISPLIB_STREAM_LDY_END) return fail(ISPLIB_FAIL, "fusedMM_csr_hybrid_hip: n must be < 2^24 and ldy < 2^22 (24-bit address arithmetic)");
    if (plan->streams != 4 && plan->streams != 8) return fail(ISPLIB_FAIL, "fusedMM_csr_hybrid_hip: bad plan geometry (streams 4 or 8)");
    const HybridGeom ge = hybrid_geom(plan->streams);
    if (plan->gens < 1 || plan->waves_per_gen < 8 || (plan->waves_per_gen % 8) != 0 || plan->rows_per_wave != ge.nvmax ||
        hp->table_rows != ge.ht || hp->hot_cap > ge.hwr * (64 / plan->streams) || plan->slices < 1)
       return fail(ISPLIB_FAIL, "fusedMM_csr_hybrid_hip: bad plan geometry (isplib_spmm_hybrid_geometry reports rows per wave, table rows and the hot-step cap; waves_per_gen must be a multiple of 8)");
    if (plan->vals) return fail(ISPLIB_FAIL, "fusedMM_csr_hybrid_hip: unit weights only (weighted graphs: fusedMM_csr_stream_hip)");
-   if (k < 4) return fail(ISPLIB_FAIL, "fusedMM_csr_hybrid_hip: k >= 4 required (use fusedMM_csr_hip)");
+   if (k < ISPLIB_K_MIN) return fail(ISPLIB_FAIL, "fusedMM_csr_hybrid_hip: k >= 4 required (use fusedMM_csr_hip)");
    if (ldy < k || ldz < k) return fail(ISPLIB_FAIL, "fusedMM_csr_hybrid_hip: leading dimension smaller than k");
    const unsigned long long yb = (unsigned long long)n * (unsigned long long)ldy * 4ull;
-   if (yb > BUF_LIMIT) return fail(ISPLIB_FAIL, "fusedMM_csr_hybrid_hip: dense operand larger than 3.5 GiB (use fusedMM_csr_hip)");
+   if (!isplib_dense_in_descriptor(n, ldy)) return fail(ISPLIB_FAIL, "fusedMM_csr_hybrid_hip: dense operand larger than 3.5 GiB (use fusedMM_csr_hip)");
    if (!pntrb || !pntre || !z || !y || !plan->wave_row || !plan->wave_part || !plan->wave_step_off || (plan->n_steps > 0 && !plan->words) ||
        (plan->n_hub > 0 && (!plan->hub_row || !plan->hub_off)) || !hp->hot_rows || !hp->hot_step_off || (hp->n_hot_steps > 0 && !hp->hot_words))
       return fail(ISPLIB_FAIL, "fusedMM_csr_hybrid_hip: null operand");

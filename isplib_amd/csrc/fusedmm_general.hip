@@ -18,7 +18,6 @@
 
 namespace isplib {
 
-constexpr unsigned GEN_BUF_LIMIT = 0xE0000000u, GEN_BUF_OOB = 0xF0000000u;   // as gather.h's BUF_LIMIT / BUF_OOB
 typedef __attribute__((__vector_size__(4 * sizeof(int)))) int gen_v4i_t;
 
 struct GenArgs {
@@ -121,7 +120,7 @@ __global__ __launch_bounds__(WAVES * 64) void fusedmm_general_kernel(const GenAr
 #pragma unroll
    for (int j = 0; j < NCH; j++) {
       const int c = (j * LPR + lc) * 4;
-      cbyte[j] = c < (int)a.k ? (unsigned)c * 4u : GEN_BUF_OOB;
+      cbyte[j] = c < (int)a.k ? (unsigned)c * 4u : BUF_OOB;
 #pragma unroll
       for (int v = 0; v < 4; v++) {
          ok[j][v] = c + v < (int)a.k;
@@ -150,7 +149,7 @@ __global__ __launch_bounds__(WAVES * 64) void fusedmm_general_kernel(const GenAr
    const unsigned ldyb = (unsigned)a.ldy * 4u;
    for (int64_t base = eb; base < ee; base += 64) {
       const int64_t p = base + lane;
-      const unsigned off_l = p < ee ? (a.indx32 ? (unsigned)a.indx32[p] : (unsigned)a.indx[p]) * ldyb : GEN_BUF_OOB;
+      const unsigned off_l = p < ee ? (a.indx32 ? (unsigned)a.indx32[p] : (unsigned)a.indx[p]) * ldyb : BUF_OOB;
       const float a_l = (p < ee && a.val) ? a.val[p] : 1.0f;
       const int64_t left = ee - base;
       const int cnt = left < 64 ? (int)left : 64;
@@ -161,11 +160,11 @@ __global__ __launch_bounds__(WAVES * 64) void fusedmm_general_kernel(const GenAr
 #pragma unroll
          for (int u = 0; u < U; u++) {
             const int src = (s0 + u * G + g) & 63;
-            const unsigned off = (unsigned)__shfl((int)off_l, src);        // dead edges carry GEN_BUF_OOB: they read 0
+            const unsigned off = (unsigned)__shfl((int)off_l, src);        // dead edges carry BUF_OOB: they read 0
             aij[u] = __shfl(a_l, src);
 #pragma unroll
             for (int j = 0; j < NCH; j++) {
-               const unsigned o = cbyte[j] >= GEN_BUF_OOB ? GEN_BUF_OOB : off + cbyte[j];
+               const unsigned o = cbyte[j] >= BUF_OOB ? BUF_OOB : off + cbyte[j];
                yv[u][j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)o, 0, 0);
             }
          }
@@ -338,7 +337,7 @@ static int general_entry(int32_t imessage, int64_t m, int64_t n, int64_t k, int6
    if (k > 1024) return fail(ISPLIB_NO_OPT_IMPL, "fusedMM_csr_udef_hip: the generic pipeline holds a row in registers, k <= 1024");
    if (beta != 0.0f) return fail(ISPLIB_FAIL, "fusedMM_csr_udef_hip: beta must be 0 (z is write-only)");
    if (m == 0 || k == 0) return ISPLIB_SUCCESS;
-   if (plan.task_row && k < 4) return fail(ISPLIB_FAIL, "fusedMM_csr_udef_tasks_hip: k >= 4 required (use fusedMM_csr_udef_hip)");
+   if (plan.task_row && k < ISPLIB_K_MIN) return fail(ISPLIB_FAIL, "fusedMM_csr_udef_tasks_hip: k >= 4 required (use fusedMM_csr_udef_hip)");
    const bool needs_x = a.vop != G_VOP_COPY_RHS || a.rop == G_ROP_DOT || a.rop == G_ROP_ADD_LHS || a.rop == G_ROP_NORML;
    if (!pntrb || !pntre || !z || (nnz > 0 && (!indx || !y)) || (needs_x && !x))
       return fail(ISPLIB_FAIL, "fusedMM_csr_udef_hip: null operand");
@@ -347,7 +346,7 @@ static int general_entry(int32_t imessage, int64_t m, int64_t n, int64_t k, int6
    a.x = needs_x ? x : nullptr; a.ldx = ldx; a.y = y; a.ldy = ldy; a.z = z; a.ldz = ldz; a.z_arg = z_arg;
    a.sop_udef = sop_udef; a.sop_param = sop_param;
    const unsigned long long yb = (unsigned long long)n * (unsigned long long)ldy * 4ull;
-   if (yb > GEN_BUF_LIMIT) return fail(ISPLIB_NO_OPT_IMPL, "fusedMM_csr_udef_hip: dense operand larger than 3.5 GiB");
+   if (!isplib_dense_in_descriptor(n, ldy)) return fail(ISPLIB_NO_OPT_IMPL, "fusedMM_csr_udef_hip: dense operand larger than 3.5 GiB");
    a.ybytes = (unsigned)yb;
    const int word = imessage & 0xFFFFF;
    const int pat = word == (0x2 | 0x10 | 0xF00 | 0x1000 | 0x10000) ? 1 : word == (0x5 | 0x50 | 0xF00 | 0x1000 | 0x10000) ? 2 : 0;

@@ -217,8 +217,8 @@ extern "C" int isplib_suggest_fusedmm_stream(int32_t imessage, int64_t m, int64_
    //   K=64 : 4 / 8 / 16 / 24 / 32 slices 2.10 / 1.91 / 1.88 / 1.92 / 1.96;  chunk 1457 / 2914 / 5828: 1.87 / 1.88 / 2.17
    //   K=32 : 2 / 4 / 8 / 12 / 16 slices 1.08 / 1.04 / 1.04 / 1.07 / 1.08;   chunk 1457 / 2914 / 5828: 1.02 / 1.04 / 1.31
    clear_error();
-   if (!stream_pattern(imessage) || m <= 0 || n <= 0 || nnz < (1LL << 22) || nnz >= (1LL << 31) || k < 4 || k > 128 || (k % 4) != 0 || n >= (1LL << 24)) return 0;
-   if (!stream_domain_ok(n, k, nnz)) return 0;
+   if (!stream_pattern(imessage) || m <= 0 || n <= 0 || nnz < STREAM_MIN_NNZ || k > 128 || (k % 4) != 0) return 0;
+   if (!isplib_stream_serves(n, k, k, nnz, 0)) return 0;
    const int st = k <= 32 ? 8 : (k <= 64 ? 4 : 2);
    int rpw = 0, resident = 0;
    if (isplib_fusedmm_stream_geometry(st, &rpw, &resident) != ISPLIB_SUCCESS) return 0;
@@ -251,13 +251,13 @@ extern "C" int fusedMM_csr_udef_stream_hip(int32_t imessage, int64_t m, int64_t 
    if (plan->streams != 2 && plan->streams != 4 && plan->streams != 8) return fail(ISPLIB_FAIL, "fusedMM_csr_udef_stream_hip: bad plan geometry (streams 2, 4 or 8)");
    if (plan->gens < 1 || plan->waves_per_gen < 1 || plan->rows_per_wave != gen_stream_geom(plan->streams).nvmax)
       return fail(ISPLIB_FAIL, "fusedMM_csr_udef_stream_hip: bad plan geometry (a plan of isplib_stream_plan_build_fusedmm_hip is required)");
-   if (k < 4 || (k % 4) != 0 || k > 256 / plan->streams)
+   if (k < ISPLIB_K_MIN || (k % 4) != 0 || k > 256 / plan->streams)
       return fail(ISPLIB_FAIL, "fusedMM_csr_udef_stream_hip: k must be a multiple of 4 within the plan's slot width (256 / streams columns); use fusedMM_csr_udef_tasks_hip");
    if (ldy < k || ldz < k || ldx < k || (ldx % 4) != 0 || (ldz % 4) != 0 || ((uintptr_t)x & 15) != 0 || ((uintptr_t)z & 15) != 0)
       return fail(ISPLIB_FAIL, "fusedMM_csr_udef_stream_hip: ldx, ldz multiples of 4 and >= k, x and z 16-byte aligned");
-   if (n >= (1LL << 24) || ldy >= (1LL << 22)) return fail(ISPLIB_FAIL, "fusedMM_csr_udef_stream_hip: n must be < 2^24 and ldy < 2^22 (24-bit address arithmetic)");
+   if (n >= ISPLIB_STREAM_N_END || ldy >= ISPLIB_STREAM_LDY_END) return fail(ISPLIB_FAIL, "fusedMM_csr_udef_stream_hip: n must be < 2^24 and ldy < 2^22 (24-bit address arithmetic)");
    const unsigned long long yb = (unsigned long long)n * (unsigned long long)ldy * 4ull;
-   if (yb > BUF_LIMIT) return fail(ISPLIB_FAIL, "fusedMM_csr_udef_stream_hip: dense operand larger than 3.5 GiB");
+   if (!isplib_dense_in_descriptor(n, ldy)) return fail(ISPLIB_FAIL, "fusedMM_csr_udef_stream_hip: dense operand larger than 3.5 GiB");
    if (!pntrb || !pntre || !x || !y || !z || !plan->wave_row || !plan->wave_part || !plan->wave_step_off || (plan->n_steps > 0 && !plan->words) ||
        (plan->n_hub > 0 && (!plan->hub_row || !plan->hub_off)))
       return fail(ISPLIB_FAIL, "fusedMM_csr_udef_stream_hip: null operand");

@@ -8,6 +8,8 @@
 #include <float.h>
 #include <limits.h>
 
+#include "../../include/isplib_hip.h"
+
 namespace isplib {
 
 enum { OP_ADD = 0, OP_MAX = 1, OP_MIN = 2 };
@@ -145,8 +147,8 @@ __device__ __forceinline__ void wave_edges(const Args &a, int64_t row_b, int64_t
 //   * out-of-range lanes carry an offset past the descriptor's size: the hardware range
 //     check returns 0 for them, so the loop has no branches and no exec-mask flips;
 //   * HAS_VAL = false (unit weights) never touches the value stream and adds instead of fma.
-constexpr unsigned BUF_LIMIT = 0xE0000000u;   // bytes addressable; offsets >= BUF_OOB read as 0
-constexpr unsigned BUF_OOB = 0xF0000000u;     // + any column offset (< 2^24) stays < 2^32: never wraps
+constexpr unsigned BUF_LIMIT = ISPLIB_DENSE_BYTES_MAX;   // bytes addressable; offsets >= BUF_OOB read as 0
+constexpr unsigned BUF_OOB = ISPLIB_DENSE_OOB_OFFSET;    // + any column offset (< 2^24) stays < 2^32: never wraps
 
 typedef __attribute__((__vector_size__(4 * sizeof(int)))) int v4i_t;
 

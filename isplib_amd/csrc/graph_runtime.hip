@@ -410,8 +410,7 @@ static int skew_adjusted(Side &s, int slices, hipStream_t st, int cap = 64) {
 static int side_stream_plan(isplib_graph *g, Side &s, const float *val, int64_t k, int64_t ldy, hipStream_t st, Side::Stream **out) {
    *out = nullptr;
    int st_streams = 0, st_slices = 0, st_chunk = 0;
-   const bool y_in_one_descriptor = (double)s.n * (double)ldy * 4.0 <= 3.5 * 1073741824.0;      // with the caller's ldy, not k
-   if (g->forced_slices >= 0 || s.stream_refused || ldy >= (1LL << 22) || !y_in_one_descriptor ||
+   if (g->forced_slices >= 0 || s.stream_refused || !isplib_stream_serves(s.n, k, ldy, s.nnz, 0) ||      // with the caller's ldy: the rule only sees k
        !isplib_suggest_stream_weighted(s.m, s.n, s.nnz, k, val != nullptr, &st_streams, &st_slices, &st_chunk))
       return ISPLIB_SUCCESS;
    st_slices = skew_adjusted(s, st_slices, st, 512);      // no degree skew: slices closer to the L2 size (31 -> 47: 3.21 -> 3.00 ms)
@@ -444,7 +443,6 @@ static int run_side(isplib_graph *g, Side &s, const float *val, int32_t imessage
    const int minmax = (imessage & 0xF0000) != ISPLIB_AOP_ADD;
    // sum / mean on graphs with work for the whole chip: the stream schedule (rows resident in LDS, the plan's own copy of
    // the edges), unless a slice count was forced
-   const bool y_in_one_descriptor = (double)s.n * (double)ldy * 4.0 <= 3.5 * 1073741824.0;      // with the caller's ldy, not k
    if (!minmax) {
       Side::Stream *sp = nullptr;
       int rc = side_stream_plan(g, s, val, k, ldy, st, &sp);
@@ -487,8 +485,7 @@ static int run_side(isplib_graph *g, Side &s, const float *val, int32_t imessage
    int mm_streams = 0, mm_slices = 0, mm_chunk = 0;
    // (the max / min entry admits dense operands under 2 GiB WITH THE CALLER'S ldy -- lanes past column k carry 2^31 in their
    // column term -- while the rule only sees k: a padded leading dimension that crosses it stays on the task list)
-   const bool y_under_2gib = (double)s.n * (double)ldy * 4.0 < 2147483648.0;
-   if (minmax && g->forced_slices < 0 && !s.minmax_stream_refused && ldy < (1LL << 22) && y_in_one_descriptor && y_under_2gib &&
+   if (minmax && g->forced_slices < 0 && !s.minmax_stream_refused && isplib_stream_serves(s.n, k, ldy, s.nnz, 1) &&
        isplib_suggest_stream_minmax(s.m, s.n, s.nnz, k, &mm_streams, &mm_slices, &mm_chunk)) {
       mm_slices = skew_adjusted(s, mm_slices, st, 512);
       const uint64_t key = (1ULL << 63) | ((uint64_t)mm_streams << 48) | ((uint64_t)mm_slices << 32) | (uint64_t)(uint32_t)mm_chunk;
@@ -522,7 +519,7 @@ static int run_side(isplib_graph *g, Side &s, const float *val, int32_t imessage
       }
    }
    int slices = g->forced_slices >= 0 ? g->forced_slices : isplib_suggest_slices(s.m, s.n, s.nnz, k, minmax);
-   if (k < 4 || (double)s.n * (double)ldy * 4.0 > 3.5 * 1073741824.0) slices = 0;      // outside the task entry's domain
+   if (!isplib_tasks_serve(s.n, k, ldy)) slices = 0;      // outside the task entry's domain
    if (g->forced_slices < 0) slices = skew_adjusted(s, slices, st);
    if (slices > 0 && g->forced_slices < 0) {
       // The panel rule halves the slice count to make tasks long enough.  If they are long anyway (hub-dominated
@@ -683,7 +680,7 @@ extern "C" int isplib_graph_sddmm(isplib_graph *g, int mean, int64_t k, const fl
    // (The forward's stream plan could serve dA too -- isplib_sddmm_stream_hip, now in the experimental library: built,
    // parity-tested, and slower than the task list below on every shape measured: Reddit shape K=128 4.04 ms against 3.54.)
    int slices = g->forced_slices >= 0 ? g->forced_slices : isplib_suggest_slices_whole_rows(s.m, s.n, s.nnz, k);
-   if (k < 4 || k > 1024 || (double)s.n * (double)ldy * 4.0 > 3.5 * 1073741824.0) slices = 0;
+   if (!isplib_sddmm_tasks_serve(s.n, k, ldy)) slices = 0;
    if (slices > 0) {
       auto it = s.plans.find(slices);
       if (it == s.plans.end()) {

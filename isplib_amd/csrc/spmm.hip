@@ -453,7 +453,7 @@ static int spmm_entry(int32_t imessage, int64_t m, int64_t n, int64_t k, int64_t
    a.nblk = 0;
    {
       const unsigned long long yb = (unsigned long long)n * (unsigned long long)ldy * 4ull;
-      a.ybytes = (yb <= BUF_LIMIT && g_addr_mode != 0) ? (unsigned)yb : 0u;
+      a.ybytes = (isplib_dense_in_descriptor(n, ldy) && g_addr_mode != 0) ? (unsigned)yb : 0u;
    }
    a.sliceptr = nullptr; a.slices = 1; a.slice_first = 0; a.slice_count = 0; a.combine = 0;
    a.part_val = nullptr; a.part_idx = nullptr;

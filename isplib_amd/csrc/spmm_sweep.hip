@@ -493,8 +493,8 @@ extern "C" int isplib_suggest_stream_weighted(int64_t m, int64_t n, int64_t nnz,
    //     rows: 0.3 -- such graphs stay on the plain kernel);
    //   * rows longer than ~0.3 of a stream's share of the edges are dealt to several virtual rows (chunk).
    clear_error();
-   if (m <= 0 || n <= 0 || nnz <= 0 || k < 4 || n >= (1LL << 24) || nnz < (1LL << 22)) return 0;
-   if (!stream_domain_ok(n, k, nnz)) return 0;         // what the entry and the plan builder would refuse: not offered
+   if (m <= 0 || n <= 0 || nnz < STREAM_MIN_NNZ) return 0;
+   if (!isplib_stream_serves(n, k, k, nnz, 0)) return 0;         // what the entry and the plan builder would refuse: not offered
    int st = k <= 32 ? 8 : (k <= 64 ? 4 : (k < 128 ? 2 : 4));
    if (weighted && k >= 128 && (k % 128) == 0) st = 2;
    int rpw = 0, resident = 0;
@@ -522,8 +522,8 @@ extern "C" int isplib_suggest_stream_minmax(int64_t m, int64_t n, int64_t nnz, i
    // 24: 0.94.  Rows cut at ~0.85 of a stream's share on 64-column slots (chunk 3000: 1.81, 2057: 1.84, 1028: 1.91), ~0.6
    // on 32-column ones (2057: 0.873, 3000: 0.890).  Task list: 2.35 / 1.96 (K=128 weighted 3.71 against 4.54).
    clear_error();
-   if (m <= 0 || n <= 0 || nnz <= 0 || k < 4 || n >= (1LL << 24) || nnz < (1LL << 22) || nnz >= (1LL << 31)) return 0;
-   if (!stream_domain_ok(n, k, nnz) || (unsigned long long)n * (unsigned long long)k * 4ull >= (1ull << 31)) return 0;   // the max / min entry: under 2 GiB
+   if (m <= 0 || n <= 0 || nnz < STREAM_MIN_NNZ) return 0;
+   if (!isplib_stream_serves(n, k, k, nnz, 1)) return 0;         // the max / min entry: under 2 GiB
    const int st = k <= 32 ? 8 : 4;
    int rpw = 0, resident = 0;
    if (isplib_spmm_stream_minmax_geometry(st, &rpw, &resident) != ISPLIB_SUCCESS || rpw <= 0 || resident <= 0) return 0;
@@ -553,21 +553,21 @@ static int stream_run(int32_t imessage, int64_t m, int64_t n, int64_t k, int64_t
    if (m == 0 || k == 0) return ISPLIB_SUCCESS;
    if (!plan) return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: plan is required");
    if (plan->rows != m || plan->cols != n) return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: the plan was built for another shape");
-   if (n >= (1LL << 24) || ldy >= (1LL << 22)) return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: n must be < 2^24 and ldy < 2^22 (24-bit address arithmetic)");
+   if (n >= ISPLIB_STREAM_N_END || ldy >= ISPLIB_STREAM_LDY_END) return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: n must be < 2^24 and ldy < 2^22 (24-bit address arithmetic)");
    if (plan->streams != 2 && plan->streams != 4 && plan->streams != 8)
       return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: bad plan geometry (streams 2, 4 or 8)");
    if (mm && plan->streams != 4 && plan->streams != 8) return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: max / min run on 4- or 8-stream plans (isplib_spmm_stream_minmax_geometry)");
    if (plan->gens < 1 || plan->waves_per_gen < 1 || plan->rows_per_wave != stream_geom(plan->streams, mm).nvmax)
       return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: bad plan geometry (rows_per_wave must be what isplib_spmm_stream_geometry / _minmax_geometry reports)");
    if (mm && plan->n_steps > 0 && !plan->perm) return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: max / min need the plan's perm array (the winners' CSR positions)");
-   if (mm && nnz >= (1LL << 31)) return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: max / min need nnz < 2^31");
+   if (mm && nnz >= ISPLIB_STREAM_NNZ_END) return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: max / min need nnz < 2^31");
    if (mm && ep) return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: the epilogue is defined for sum / mean only");
-   if (mm && (unsigned long long)n * (unsigned long long)ldy * 4ull >= (1ull << 31))
+   if (mm && !isplib_rows_within(n, ldy, ISPLIB_STREAM_MINMAX_BYTES_END - 1u))
       return fail(ISPLIB_FAIL, "fusedMM_csr_stream_minmax_hip: dense operand of 2 GiB or more (use fusedMM_csr_tasks_hip)");
-   if (k < 4) return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: k >= 4 required (use fusedMM_csr_hip)");
+   if (k < ISPLIB_K_MIN) return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: k >= 4 required (use fusedMM_csr_hip)");
    if (ldy < k || ldz < k) return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: leading dimension smaller than k");
    const unsigned long long yb = (unsigned long long)n * (unsigned long long)ldy * 4ull;
-   if (yb > BUF_LIMIT) return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: dense operand larger than 3.5 GiB (use fusedMM_csr_hip)");
+   if (!isplib_dense_in_descriptor(n, ldy)) return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: dense operand larger than 3.5 GiB (use fusedMM_csr_hip)");
    if (!pntrb || !pntre || !z || !y || !plan->wave_row || !plan->wave_part || !plan->wave_step_off ||
        (plan->n_steps > 0 && !plan->words) || (plan->n_hub > 0 && (!plan->hub_row || !plan->hub_off)))
       return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: null operand");

@@ -296,10 +296,10 @@ static int tasks_entry(int32_t imessage, int64_t m, int64_t n, int64_t k, int64_
    if (m < 0 || n < 0 || k < 0 || nnz < 0 || n_tasks < 0) return fail(ISPLIB_FAIL, "fusedMM_csr_tasks_hip: negative dimension");
    if (m == 0 || k == 0) return ISPLIB_SUCCESS;
    if (slices < 1 || slices > ISPLIB_MAX_SLICES) return fail(ISPLIB_FAIL, "fusedMM_csr_tasks_hip: slices must be in [1, 4096]");
-   if (k < 4) return fail(ISPLIB_FAIL, "fusedMM_csr_tasks_hip: k >= 4 required (use fusedMM_csr_hip)");
+   if (k < ISPLIB_K_MIN) return fail(ISPLIB_FAIL, "fusedMM_csr_tasks_hip: k >= 4 required (use fusedMM_csr_hip)");
    if (ldy < k || ldz < k) return fail(ISPLIB_FAIL, "fusedMM_csr_tasks_hip: leading dimension smaller than k");
    const unsigned long long yb = (unsigned long long)n * (unsigned long long)ldy * 4ull;
-   if (yb > BUF_LIMIT) return fail(ISPLIB_FAIL, "fusedMM_csr_tasks_hip: dense operand larger than 3.5 GiB (use fusedMM_csr_hip)");
+   if (!isplib_dense_in_descriptor(n, ldy)) return fail(ISPLIB_FAIL, "fusedMM_csr_tasks_hip: dense operand larger than 3.5 GiB (use fusedMM_csr_hip)");
    if (!pntrb || !pntre || !z || !seg_off || !lane_off_host || (n_tasks > 0 && (!task_row || !task_b || !task_len || !indx || !y)))
       return fail(ISPLIB_FAIL, "fusedMM_csr_tasks_hip: null operand");
    const size_t need = isplib_spmm_tasks_workspace_bytes(imessage, n_tasks, k);

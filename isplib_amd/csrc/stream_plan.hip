@@ -254,7 +254,7 @@ static int stream_plan_build(int64_t m, int64_t n, int64_t nnz, const int64_t *r
    if (!out) return fail(ISPLIB_FAIL, "isplib_stream_plan_build_hip: out is NULL");
    memset(out, 0, sizeof(*out));
    if (m <= 0 || n <= 0 || nnz < 0 || !rowptr || (nnz > 0 && !col)) return fail(ISPLIB_FAIL, "isplib_stream_plan_build_hip: bad operand");
-   if (n >= (1LL << 24) || nnz >= (1LL << 31) || m >= (1LL << 31)) return fail(ISPLIB_FAIL, "isplib_stream_plan_build_hip: n < 2^24, nnz < 2^31, m < 2^31 required");
+   if (n >= ISPLIB_STREAM_N_END || nnz >= ISPLIB_STREAM_NNZ_END || m >= (1LL << 31)) return fail(ISPLIB_FAIL, "isplib_stream_plan_build_hip: n < 2^24, nnz < 2^31, m < 2^31 required");
    if (slices < 1 || slices > 4096 || chunk < 1 || chunk >= (1 << 24)) return fail(ISPLIB_FAIL, "isplib_stream_plan_build_hip: slices in [1, 4096], chunk in [1, 2^24)");
    if (waves_per_gen <= 0) waves_per_gen = resident;
    const int per = rpw / streams;

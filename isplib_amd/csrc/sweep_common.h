@@ -271,12 +271,11 @@ static inline int device_cus() {
    return cus;
 }
 
-// The domain of the stream entries and of isplib_stream_plan_build_hip, with ldy = k (a contiguous dense operand; callers
-// with a padded leading dimension check n * ldy themselves): the dense operand inside one buffer descriptor (3.5 GiB) and
-// 32-bit edge positions.  A shape outside it is simply not offered the schedule -- it runs on the task list or the plain
-// kernel as before the stream schedule existed -- instead of being offered and then refused with an error.
-static bool stream_domain_ok(int64_t n, int64_t k, int64_t nnz) {
-   return (unsigned long long)n * (unsigned long long)k * 4ull <= (unsigned long long)BUF_LIMIT && nnz < (1LL << 31);
-}
+// The isplib_suggest_*stream* rules offer a shape the stream schedule only when (a) its entry and plan builder would serve
+// it -- isplib_stream_serves (include/isplib_hip.h) with ldy = k, a contiguous dense operand; callers with a padded leading
+// dimension ask it again with theirs -- so that a shape outside the domain runs on the task list or the plain kernel as
+// before the stream schedule existed instead of being offered and then refused with an error, and (b) the graph has work
+// for the whole chip: at least this many stored entries (a measured rule, not an address domain).
+constexpr int64_t STREAM_MIN_NNZ = 4 * 1048576;
 
 }  // namespace isplib

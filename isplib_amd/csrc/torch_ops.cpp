@@ -248,6 +248,15 @@ bool spmm_through_handle(int32_t msg, const Tensor &rowptr, const Tensor &col, c
    return true;
 }
 
+// The pitch (floats per row) a gathered [N, K] operand of the stream schedule should be read at: 48 for 33..47 columns (the
+// GCN's 41 classes) on large graphs, K otherwise.  What the address pipeline charges for is the 128-byte line a gather
+// touches, and a 164-byte row at its packed pitch straddles 2.25 of them on average, at a 192-byte pitch exactly 2 -- Reddit
+// shape K=41: 1.365 -> 1.285 ms, the copy 0.015 (scripts/exp_round4.py k41; 176 B: no gain, 256 B: 1.314).  The wider
+// operand has to stay inside the max / min stream entry's 2 GiB.
+static int64_t gather_pitch(int64_t N, int64_t K, bool stream) {
+   return (stream && K > 32 && K < 48 && N >= (1 << 16) && isplib_rows_within(N, 48, ISPLIB_STREAM_MINMAX_BYTES_END - 1u)) ? 48 : K;
+}
+
 // want_arg = false (max / min through the *_values operators: nobody will ask which edge won): on a stream plan the
 // launch then leaves the positions out altogether (isplib_hip.h: fusedMM_csr_stream_minmax_hip with z_arg = NULL) and the
 // second tensor of the result is undefined; every other schedule computes them as always
@@ -275,28 +284,23 @@ std::tuple<Tensor, Tensor> spmm_fw(const Tensor &rowptr_, const Tensor &col_, co
    if (reduction == R_MIN) msg = ISPLIB_MSG_SPMM_MIN;
    if (reduction == R_MEAN) msg = ISPLIB_MSG_SPMM_MEAN;
    const int64_t *rp = rowptr.data_ptr<int64_t>();
-   const bool tasks_fit = K >= 4 && (double)N * (double)K * 4.0 <= 3.5 * 1073741824.0;
+   const bool tasks_fit = isplib_tasks_serve(N, K, K);
    // (a stream plan for a shape outside the stream entry's domain -- dense operand over 3.5 GiB, k < 4 -- is not an error:
    // the graph is served by the kernels below, which read `col` / `value`)
    const bool minmax_op = reduction == R_MAX || reduction == R_MIN;      // (the max / min stream entry serves dense operands under 2 GiB)
-   const bool on_stream = is_stream_plan(plan) && M > 0 && K >= 4 && (double)N * (double)K * 4.0 <= 3.5 * 1073741824.0 &&
-                          !(minmax_op && (double)N * (double)K * 4.0 >= 2.0 * 1073741824.0);
+   const bool on_stream = is_stream_plan(plan) && M > 0 && isplib_stream_serves(N, K, K, nnz, minmax_op);
    if (minmax_op && (want_arg || !on_stream)) arg = at::empty({M, K}, rowptr.options());
    if (on_stream) {
       // the plan carries the edges (and the weights) in its own order: `col` / `value` are not read
       const isplib_stream_plan sp = stream_plan_of(plan);
-      // A line-friendly pitch for 33..47 columns (the GCN's 41 classes): what the address pipeline charges for is the
-      // 128-byte line a gather touches, and a 164-byte row at its packed pitch straddles 2.25 of them on average, at a
-      // 192-byte pitch exactly 2 -- Reddit shape K=41: 1.365 -> 1.285 ms, the copy 0.015 (scripts/exp_round4.py k41;
-      // 176 B: no gain, 256 B: 1.314).  Only the gathered operand is copied; the output stays packed.
+      // a line-friendly pitch for 33..47 columns: only the gathered operand is copied, the output stays packed
       const float *y = mat.data_ptr<float>();
-      int64_t ldy = K;
+      const int64_t ldy = gather_pitch(N, K, true);
       Tensor pitched;
-      if (K > 32 && K < 48 && N >= (1 << 16) && (double)N * 48.0 * 4.0 < 2.0 * 1073741824.0) {
-         pitched = at::empty({N, 48}, mat.options());
+      if (ldy != K) {
+         pitched = at::empty({N, ldy}, mat.options());
          pitched.narrow(1, 0, K).copy_(mat);
          y = pitched.data_ptr<float>();
-         ldy = 48;
       }
       if (reduction == R_MAX || reduction == R_MIN) {
          TORCH_CHECK(sp.perm != nullptr, "isplib: max / min on a stream plan need its permutation (a 9-element plan)");
@@ -419,7 +423,7 @@ Tensor sddmm(const Tensor &rowptr, const Tensor &col, const Tensor &mat, const T
          return dval;
       }
    }
-   if (is_task_plan(plan) && K >= 4 && K <= 1024 && (double)N * (double)K * 4.0 <= 3.5 * 1073741824.0) {
+   if (is_task_plan(plan) && isplib_sddmm_tasks_serve(N, K, K)) {
       const int st = isplib_sddmm_csr_tasks_hip(M, N, K, col.data_ptr<int64_t>(), plan_col32(plan, col), rp, rp + 1, plan[0].numel(),
                                                 plan[0].data_ptr<int32_t>(), plan[1].data_ptr<int64_t>(),
                                                 plan[2].data_ptr<int32_t>(), plan[4].data_ptr<int64_t>(),
@@ -442,13 +446,13 @@ static bool row_strided(const Tensor &t) { return t.dim() == 2 && t.stride(1) ==
 Tensor epilogue_spmm(const Tensor &rowptr, const Tensor &col, const Plan &plan, const Tensor &y_, const Tensor &self_,
                      const Tensor &row_scale, const Tensor &bias, bool relu) {
    const int64_t M = rowptr.numel() - 1, N = y_.size(0), K = y_.size(1), nnz = col.numel();
-   const bool tasks_fit = is_task_plan(plan) && K >= 4 && M > 0 && (double)N * (double)K * 4.0 <= 3.5 * 1073741824.0;
+   const bool tasks_fit = is_task_plan(plan) && M > 0 && isplib_tasks_serve(N, K, K);
    if (is_stream_plan(plan) && M > 0 && K >= 4) {
       // the stream kernel applies the same epilogue when it writes a finished row (hub rows: in their fold)
       c10::DeviceGuard guard(y_.device());
       const Tensor y = row_strided(y_) ? y_ : y_.contiguous();          // the gather's own pitch is kept (GcnNormSpmm)
       const int64_t ldy = N > 1 ? y.stride(0) : K;
-      TORCH_CHECK((double)N * (double)ldy * 4.0 <= 3.5 * 1073741824.0, "isplib: dense operand beyond one buffer descriptor");
+      TORCH_CHECK(isplib_dense_in_descriptor(N, ldy), "isplib: dense operand beyond one buffer descriptor");
       const Tensor self = self_.defined() ? (row_strided(self_) ? self_ : self_.contiguous()) : Tensor();
       const Tensor rs = row_scale.defined() ? row_scale.contiguous() : Tensor();
       const Tensor bs = bias.defined() ? bias.contiguous() : Tensor();
@@ -686,13 +690,6 @@ class SpmmMinMax : public torch::autograd::Function<SpmmMinMax<RED>> {
       return {Variable(), Variable(), grad_value, grad_mat, Variable()};
    }
 };
-
-// The pitch (floats per row) a gathered [N, K] operand of the stream schedule should be written at: 48 for 33..47 columns
-// on large graphs (a 164-byte row at its packed pitch straddles 2.25 cache lines on average, at 192 bytes exactly 2: spmm_fw
-// above copies for the same reason); K otherwise.
-static int64_t gather_pitch(int64_t N, int64_t K, bool stream) {
-   return (stream && K > 32 && K < 48 && N >= (1 << 16) && (double)N * 48.0 * 4.0 < 2.0 * 1073741824.0) ? 48 : K;
-}
 
 // y = D^-1/2 X in one pass (isplib_row_scale_hip), written at the gather's pitch: a [N, K] view
 static Tensor gcn_row_scale(const Tensor &mat_, const Tensor &dinv_, bool stream) {

@@ -379,7 +379,7 @@ def build_stream_plan(rowptr: torch.Tensor, col: torch.Tensor, val: Optional[tor
     width is built for (isplib_spmm_stream_geometry; minmax: isplib_spmm_stream_minmax_geometry, whose plans are their
     own).  None when n >= 2^24.  (Rows need not be column-sorted: the stream order -- slice, row, CSR position -- is the
     plan's own.)"""
-    if ncols >= (1 << 24):
+    if ncols >= cabi.STREAM_N_END:
         return None
     if minmax:
         # the kernel's tie rule (first strictly better candidate in stream order = lowest CSR position) holds for rows
@@ -408,7 +408,7 @@ def build_stream_plan_native(rowptr: torch.Tensor, col: torch.Tensor, ncols: int
     stay in the library's allocation; the returned StreamPlan holds zero-copy views of them and the owning object.
     Unit weights (`set_values` gathers through `perm` as for a torch-built plan).  None where the builder declines
     (n >= 2^24, nnz >= 2^31, max / min on rows that are not column-sorted)."""
-    if ncols >= (1 << 24) or col.numel() >= (1 << 31):
+    if ncols >= cabi.STREAM_N_END or col.numel() >= cabi.STREAM_NNZ_END:
         return None
     try:
         native = cabi.NativeStreamPlan(rowptr, col, None, ncols, streams, slices, chunk, 0, minmax)
@@ -599,7 +599,7 @@ def build_hybrid_plan(rowptr: torch.Tensor, col: torch.Tensor, ncols: int, slice
                       hot_cap: Optional[int] = None, min_refs: int = 2) -> Optional[HybridPlan]:
     """Hybrid plan of a graph on the device (unit weights); geometry defaults to what the kernel of this slot width is built
     for (isplib_spmm_hybrid_geometry).  None when n >= 2^24 or nnz >= 2^31."""
-    if ncols >= (1 << 24) or col.numel() >= (1 << 31):
+    if ncols >= cabi.STREAM_N_END or col.numel() >= cabi.STREAM_NNZ_END:
         return None
     rpw, resident, ht, cap = cabi.hybrid_geometry(streams)
     arrays = hybrid_plan_arrays(rowptr, col, ncols, slices, resident if waves_per_gen is None else waves_per_gen,

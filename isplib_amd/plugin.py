@@ -206,7 +206,8 @@ def choose_stream(storage: SparseStorage, m: int, n: int, k: int, weighted: bool
     ISPLIB_STREAM=0 disables it, ISPLIB_SLICES (the task list's override) disables it too: explicit schedules win."""
     if os.environ.get("ISPLIB_STREAM", "1") == "0" or os.environ.get("ISPLIB_SLICES") is not None:
         return None
-    if k < 4 or n >= (1 << 24):
+    from . import cabi
+    if k < cabi.K_MIN or n >= cabi.STREAM_N_END:
         return None
     forced = os.environ.get("ISPLIB_STREAM_GEOM")          # "streams:slices:chunk": tests and experiments
     if forced:
@@ -229,7 +230,8 @@ def choose_stream_minmax(storage: SparseStorage, m: int, n: int, k: int):
     plan builder has the last word), else None.  Same switches as choose_stream."""
     if os.environ.get("ISPLIB_STREAM", "1") == "0" or os.environ.get("ISPLIB_SLICES") is not None:
         return None
-    if k < 4 or n >= (1 << 24) or storage._col.numel() >= (1 << 31):
+    from . import cabi
+    if k < cabi.K_MIN or n >= cabi.STREAM_N_END or storage._col.numel() >= cabi.STREAM_NNZ_END:
         return None
     forced = os.environ.get("ISPLIB_STREAM_MINMAX_GEOM")   # "streams:slices:chunk": tests and experiments
     if forced:
@@ -456,7 +458,7 @@ class iSpLibPlugin:
         rule = stream_minmax_rule(s, m_rows, x.size(0), k) if minmax else stream_rule(s, m_rows, x.size(0), k, s._value is not None)
         stream_off = os.environ.get("ISPLIB_STREAM", "1") == "0" or os.environ.get("ISPLIB_SLICES") is not None
         cands = []
-        if rule is not None and not stream_off and k >= 4 and x.size(0) < (1 << 24):
+        if rule is not None and not stream_off:
             st, sl, ch = rule
             for f in stream_slices:
                 cands.append(("stream", st, max(1, min(512, int(sl * f + 0.5))), ch))

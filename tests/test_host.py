@@ -485,6 +485,45 @@ def test_stream_rule_offers_only_what_the_stream_entries_accept():
     assert cabi.suggest_stream_minmax(n, n, nnz, 32)[:2] == (8, 9)
     assert not offered(L.isplib_suggest_stream_minmax, 1_100_000, 1_100_000, 500_000_000, 512)   # 2.25 GB: the max / min entry stops at 2 GiB
     assert offered(L.isplib_suggest_stream, 1_100_000, 1_100_000, 500_000_000, 512)
+    # exactly at every limit of the domain (include/isplib_hip.h, "address domains"): offered just inside, not just outside
+    for fn in (L.isplib_suggest_stream, L.isplib_suggest_stream_minmax):
+        assert offered(fn, 1000, cabi.STREAM_N_END - 1, 1 << 30, 16)              # n < 2^24 (1 GiB of y, few long rows)
+        assert not offered(fn, 1000, cabi.STREAM_N_END, 1 << 30, 16)
+        assert offered(fn, 232965, 232965, cabi.STREAM_NNZ_END - 1, 64)           # nnz < 2^31
+        assert not offered(fn, 232965, 232965, cabi.STREAM_NNZ_END, 64)
+    n_at = cabi.DENSE_BYTES_MAX // (1024 * 4)                                     # 917,504 rows of 1024 floats: 3.5 GiB exactly
+    assert n_at * 1024 * 4 == cabi.DENSE_BYTES_MAX
+    assert offered(L.isplib_suggest_stream, n_at, n_at, 500_000_000, 1024)        # n * k * 4 <= 3.5 GiB: the limit itself is served
+    assert not offered(L.isplib_suggest_stream, n_at + 1, n_at + 1, 500_000_000, 1024)
+    n_at = cabi.STREAM_MINMAX_BYTES_END // (512 * 4)                              # 1,048,576 rows of 512 floats: 2 GiB exactly
+    assert n_at * 512 * 4 == cabi.STREAM_MINMAX_BYTES_END
+    assert offered(L.isplib_suggest_stream_minmax, n_at - 1, n_at - 1, 500_000_000, 512)   # max / min: n * k * 4 < 2 GiB
+    assert not offered(L.isplib_suggest_stream_minmax, n_at, n_at, 500_000_000, 512)
+    assert offered(L.isplib_suggest_stream, n_at, n_at, 500_000_000, 512)         # (sum / mean go on to 3.5 GiB)
+
+
+def test_cabi_mirrors_the_headers_limits_and_status_codes():
+    """include/isplib_hip.h is the one statement of the kernel families' address domains and of the status codes; the names
+    isplib_amd.cabi gives the Python layers carry the header's values, and both spellings of a status code are one value."""
+    from isplib_amd import cabi
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "isplib_hip.h")).read(), flags=re.S)
+    header = {}
+    for name, expr in re.findall(r"^#define\s+ISPLIB_(\w+)[ \t]+(\S.*?)\s*$", text, flags=re.M):
+        expr = re.sub(r"(?<=[0-9a-fA-F])(?:ull|ULL|ll|LL|u|U)\b", "", expr)       # integer suffixes
+        if re.fullmatch(r"[0-9a-fA-FxX()<\s-]+", expr):                           # literals and shifts; not the composed message words
+            header[name] = eval(expr)
+    limits = ("DENSE_BYTES_MAX", "DENSE_OOB_OFFSET", "STREAM_N_END", "STREAM_LDY_END", "STREAM_NNZ_END", "STREAM_MINMAX_BYTES_END",
+              "K_MIN", "SDDMM_TASKS_K_MAX")
+    codes = ("SUCCESS", "FAIL", "NOT_ENOUGH_MEM", "UNDEFINED_USER_FUNCTION", "NO_OPT_IMPL", "HIP_ERROR")
+    for name in limits + codes:
+        assert name in header, f"ISPLIB_{name} is not a plain constant of include/isplib_hip.h"
+        assert getattr(cabi, name) == header[name], name
+    for name in codes:
+        if name != "UNDEFINED_USER_FUNCTION":
+            assert getattr(cabi, "ISPLIB_" + name) == header[name], name
+    assert (header["DENSE_BYTES_MAX"], header["STREAM_MINMAX_BYTES_END"]) == (7 << 29, 1 << 31)        # 3.5 GiB, 2 GiB
+    assert (header["STREAM_N_END"], header["STREAM_LDY_END"], header["STREAM_NNZ_END"]) == (2 ** 24, 2 ** 22, 2 ** 31)
+    assert (header["K_MIN"], header["SDDMM_TASKS_K_MAX"]) == (4, 1024)
 
 
 def test_degree_skew_adjustment_of_the_slice_rule():
