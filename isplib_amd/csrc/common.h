@@ -18,12 +18,18 @@ inline int fail(int code, const char *msg) {
    return code;
 }
 
+inline int fail(int code, const char *entry, const char *msg) {      // "<entry>: <msg>"
+   snprintf(error_buffer(), 512, "%s: %s", entry, msg);
+   return code;
+}
+
 inline int hip_fail(hipError_t e, const char *what) {
    snprintf(error_buffer(), 512, "%s: %s", what, hipGetErrorString(e));
    return ISPLIB_HIP_ERROR;
 }
 
-inline int check_launch(const char *what) {
+// (out of line: one copy per library, not one per launch site)
+__attribute__((noinline)) inline int check_launch(const char *what) {
    const hipError_t e = hipGetLastError();
    return e == hipSuccess ? ISPLIB_SUCCESS : hip_fail(e, what);
 }

@@ -13,10 +13,8 @@ namespace isplib {
 
 // LDS of one workgroup (4 waves x NVMAX rows x one panel row, values and for max / min the ids) and the workgroups
 // a CU holds at once: the launch bound (one wave of each workgroup per SIMD) and the plan's wave count follow from it
-template <int OP, int LPR, int NVMAX> constexpr int sweep_lds_bytes() { return (OP == OP_ADD ? 1 : 2) * 4 * NVMAX * LPR * 4 * 4; }
-template <int OP, int LPR, int NVMAX> constexpr int sweep_wgs_per_cu() {
-   return 163840 / sweep_lds_bytes<OP, LPR, NVMAX>() < 8 ? 163840 / sweep_lds_bytes<OP, LPR, NVMAX>() : 8;
-}
+constexpr int sweep_lds_bytes(bool add, int lpr, int nvmax) { return (add ? 1 : 2) * stream_lds_bytes(lpr, nvmax); }
+template <int OP, int LPR, int NVMAX> constexpr int sweep_wgs_per_cu() { return lds_wgs_per_cu(sweep_lds_bytes(OP == OP_ADD, LPR, NVMAX), 8); }
 
 template <int OP, int LPR, int ADDR, int NVMAX>
 __global__ __launch_bounds__(256, (sweep_wgs_per_cu<OP, LPR, NVMAX>())) void spmm_sweep_kernel(const SweepArgs a) {
@@ -323,7 +321,7 @@ __global__ __launch_bounds__(512, 2) void spmm_hybrid_kernel(const SweepArgs a) 
    constexpr int HS = 64 / G;                             // hot steps held by one word register
    constexpr int SHARE = HT / WAVES, SI = SHARE / G;      // table rows / DMA instructions of one wave per slice
    static_assert(NVMAX <= 256 && NVMAX % G == 0 && HT % (WAVES * G) == 0 && SHARE <= 64 && HT <= 65536, "geometry");
-   static_assert((WAVES * WAVE_FLOATS + HT * PANEL) * 4 <= 163840, "accumulators + table must fit the CU's LDS");
+   static_assert((WAVES * WAVE_FLOATS + HT * PANEL) * 4 <= CU_LDS_BYTES, "accumulators + table must fit the CU's LDS");
    static_assert(U + NBW <= 63, "counted vmcnt wait");
    __shared__ __attribute__((aligned(16))) float s_all[WAVES * WAVE_FLOATS + HT * PANEL];
    const int lane = threadIdx.x & 63;
@@ -562,13 +560,8 @@ static int launch_sweep_op(const SweepArgs &a, int nvmax, hipStream_t st) {
 // waves of one launch that are resident together (what a plan's waves_per_gen should not exceed)
 static int sweep_resident_waves(bool add, int64_t pk, int nvmax, int cus) {
    const int lpr = pk <= 32 ? 8 : (pk <= 64 ? 16 : 32);
-   const int lds = (add ? 1 : 2) * 4 * nvmax * lpr * 4 * 4;
-   int wgs = 163840 / lds;
-   if (wgs > 8) wgs = 8;
-   return cus * wgs * 4;
+   return cus * lds_wgs_per_cu(sweep_lds_bytes(add, lpr, nvmax), 8) * 4;
 }
-
-
 
 int g_sweep_panel = 64;     // tuning knob (isplib_hip_tune_experimental(9, w)): column-panel width of the sweep schedule, 32 / 64 / 128
 
@@ -579,16 +572,11 @@ using namespace isplib;
 extern "C" int isplib_spmm_sweep_resident_waves(int32_t imessage, int64_t k, int rows_per_wave) {
    clear_error();
    if (k <= 0 || (rows_per_wave != 8 && rows_per_wave != 16 && rows_per_wave != 32)) return 0;
-   int dev = 0, cus = 0;
-   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
-      (void)hipGetLastError();
-      cus = 256;                                          // MI355X
-   }
    const bool add = (imessage & 0xF0000) == ISPLIB_AOP_ADD;
    int panel = g_sweep_panel;
    if (panel != 32 && panel != 64 && panel != 128) panel = 64;
    if (!add && panel > 64) panel = 64;
-   return sweep_resident_waves(add, k < panel ? k : panel, rows_per_wave, cus);
+   return sweep_resident_waves(add, k < panel ? k : panel, rows_per_wave, device_cus());
 }
 
 extern "C" size_t isplib_spmm_sweep_workspace_bytes(int32_t imessage, const isplib_sweep_plan *plan, int64_t k) {
@@ -641,13 +629,9 @@ extern "C" int fusedMM_csr_sweep_hip(int32_t imessage, int64_t m, int64_t n, int
    a.task_b = plan->task_b; a.task_meta = plan->task_meta;
    a.wave_base = 0; a.wave_count = 0;
    a.hub_row = plan->hub_row; a.hub_off = plan->hub_off; a.n_hub = plan->n_hub;
-   a.ep_row_scale = a.ep_self = a.ep_bias = nullptr; a.ep_ld_self = 0; a.ep_relu = 0;
-   if (ep) {
-      if (aop != ISPLIB_AOP_ADD) return fail(ISPLIB_FAIL, "fusedMM_csr_sweep_hip: the epilogue is defined for sum / mean only");
-      if (ep->self && ep->ld_self < k) return fail(ISPLIB_FAIL, "fusedMM_csr_sweep_hip: ld_self smaller than k");
-      a.ep_row_scale = ep->row_scale; a.ep_self = ep->self; a.ep_ld_self = ep->ld_self; a.ep_bias = ep->bias;
-      a.ep_relu = ep->relu ? 1 : 0;
-   }
+   if (ep && aop != ISPLIB_AOP_ADD) return fail(ISPLIB_FAIL, "fusedMM_csr_sweep_hip: the epilogue is defined for sum / mean only");
+   const int rc_ep = set_epilogue("fusedMM_csr_sweep_hip", ep, a);
+   if (rc_ep) return rc_ep;
    const int64_t pk_max = k < 128 ? k : 128;
    const size_t plane = ((size_t)(plan->n_parts > 0 ? plan->n_parts : 0) * (size_t)pk_max * sizeof(float) + 255) & ~(size_t)255;
    a.part_val = (float *)workspace;
@@ -669,36 +653,25 @@ extern "C" int fusedMM_csr_sweep_hip(int32_t imessage, int64_t m, int64_t n, int
       p.ep_bias = a.ep_bias ? a.ep_bias + c0 : nullptr;
       p.z_arg = z_arg ? z_arg + c0 : nullptr;
       p.ybytes = (unsigned)(yb - (unsigned long long)c0 * 4ull);
-      for (int gen = 0; gen < plan->gens; gen++) {
-         p.wave_base = gen * plan->waves_per_gen;
-         p.wave_count = plan->waves_per_gen;
-         int rc;
-         if (aop == ISPLIB_AOP_ADD) rc = val ? launch_sweep_op<OP_ADD, 2>(p, plan->rows_per_wave, st) : launch_sweep_op<OP_ADD, 1>(p, plan->rows_per_wave, st);
-         else if (aop == ISPLIB_AOP_MAX) rc = val ? launch_sweep_op<OP_MAX, 2>(p, plan->rows_per_wave, st) : launch_sweep_op<OP_MAX, 1>(p, plan->rows_per_wave, st);
-         else rc = val ? launch_sweep_op<OP_MIN, 2>(p, plan->rows_per_wave, st) : launch_sweep_op<OP_MIN, 1>(p, plan->rows_per_wave, st);
-         if (rc) return rc;
-      }
-      if (plan->n_hub > 0) {
-         int64_t blocks = (plan->n_hub * (p.k / 4) + 255) / 256;
-         if (blocks > 4096) blocks = 4096;
-         if (aop == ISPLIB_AOP_ADD) hipLaunchKernelGGL((sweep_hub_fold_kernel<OP_ADD, 4>), dim3((unsigned)blocks), dim3(256), 0, st, p);
-         else if (aop == ISPLIB_AOP_MAX) hipLaunchKernelGGL((sweep_hub_fold_kernel<OP_MAX, 4>), dim3((unsigned)blocks), dim3(256), 0, st, p);
-         else hipLaunchKernelGGL((sweep_hub_fold_kernel<OP_MIN, 4>), dim3((unsigned)blocks), dim3(256), 0, st, p);
-         const int rc = check_launch("sweep_hub_fold_kernel");
-         if (rc) return rc;
-      }
+      int rc = run_generations(plan->gens, plan->waves_per_gen, p, [&](const SweepArgs &q) {
+         if (aop == ISPLIB_AOP_ADD) return val ? launch_sweep_op<OP_ADD, 2>(q, plan->rows_per_wave, st) : launch_sweep_op<OP_ADD, 1>(q, plan->rows_per_wave, st);
+         if (aop == ISPLIB_AOP_MAX) return val ? launch_sweep_op<OP_MAX, 2>(q, plan->rows_per_wave, st) : launch_sweep_op<OP_MAX, 1>(q, plan->rows_per_wave, st);
+         return val ? launch_sweep_op<OP_MIN, 2>(q, plan->rows_per_wave, st) : launch_sweep_op<OP_MIN, 1>(q, plan->rows_per_wave, st);
+      });
+      if (!rc) rc = aop == ISPLIB_AOP_ADD ? launch_hub_fold<OP_ADD, false>(p, st)
+                  : aop == ISPLIB_AOP_MAX ? launch_hub_fold<OP_MAX, false>(p, st) : launch_hub_fold<OP_MIN, false>(p, st);
+      if (rc) return rc;
    }
    return ISPLIB_SUCCESS;
 }
 
 // ---- SDDMM on the stream front end: entry ---------------------------------------------------------------------------
-template <int LPR, bool ACCUM>
+template <int STREAMS, bool ACCUM>
 static int launch_sddmm_stream(const SweepArgs &a, hipStream_t st) {
+   constexpr StreamGeom ge = stream_geom(STREAM_SUM, STREAMS);      // a sum / mean plan
    const unsigned blocks = (unsigned)((a.wave_count + 3) / 4);
    if (blocks == 0) return ISPLIB_SUCCESS;
-   if constexpr (LPR == 32) hipLaunchKernelGGL((sddmm_stream_kernel<32, 32, 1, 2, ACCUM>), dim3(blocks), dim3(256), 0, st, a);
-   else if constexpr (LPR == 16) hipLaunchKernelGGL((sddmm_stream_kernel<16, ISPLIB_STREAM_NV4, ISPLIB_STREAM_NBW4, ISPLIB_STREAM_WGS4, ACCUM>), dim3(blocks), dim3(256), 0, st, a);
-   else hipLaunchKernelGGL((sddmm_stream_kernel<8, ISPLIB_STREAM_NV8, ISPLIB_STREAM_NBW8, ISPLIB_STREAM_WGS8, ACCUM>), dim3(blocks), dim3(256), 0, st, a);
+   hipLaunchKernelGGL((sddmm_stream_kernel<ge.lpr, ge.nvmax, ge.nbw, ge.wgs, ACCUM>), dim3(blocks), dim3(256), 0, st, a);
    return check_launch("sddmm_stream_kernel");
 }
 
@@ -706,31 +679,16 @@ extern "C" int isplib_sddmm_stream_hip(int64_t m, int64_t n, int64_t k, int64_t 
                                        const isplib_stream_plan *plan, const float *y, int64_t ldy, const float *g, int64_t ldg,
                                        int mean, float *dval, void *stream) {
    clear_error();
-   if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, "isplib_sddmm_stream_hip: negative dimension");
-   if (m == 0 || nnz == 0) return ISPLIB_SUCCESS;
-   if (!plan) return fail(ISPLIB_FAIL, "isplib_sddmm_stream_hip: plan is required");
-   if (plan->rows != m || plan->cols != n) return fail(ISPLIB_FAIL, "isplib_sddmm_stream_hip: the plan was built for another shape");
-   if (n >= ISPLIB_STREAM_N_END || ldy >= ISPLIB_STREAM_LDY_END) return fail(ISPLIB_FAIL, "isplib_sddmm_stream_hip: n must be < 2^24 and ldy < 2^22 (24-bit address arithmetic)");
-   if (nnz >= ISPLIB_STREAM_NNZ_END) return fail(ISPLIB_FAIL, "isplib_sddmm_stream_hip: nnz < 2^31 required (32-bit CSR positions in the plan)");
-   if (plan->streams != 2 && plan->streams != 4 && plan->streams != 8)
-      return fail(ISPLIB_FAIL, "isplib_sddmm_stream_hip: bad plan geometry (streams 2, 4 or 8)");
-   if (plan->gens < 1 || plan->waves_per_gen < 1 || plan->rows_per_wave != stream_geom(plan->streams).nvmax)
-      return fail(ISPLIB_FAIL, "isplib_sddmm_stream_hip: bad plan geometry (a sum / mean plan of isplib_spmm_stream_geometry is required)");
-   if (plan->n_steps > 0 && !plan->perm) return fail(ISPLIB_FAIL, "isplib_sddmm_stream_hip: the plan's perm array is required (the CSR position of every word)");
-   if (k < ISPLIB_K_MIN) return fail(ISPLIB_FAIL, "isplib_sddmm_stream_hip: k >= 4 required (use isplib_sddmm_csr_hip)");
-   if (ldy < k || ldg < k) return fail(ISPLIB_FAIL, "isplib_sddmm_stream_hip: leading dimension smaller than k");
-   const unsigned long long yb = (unsigned long long)n * (unsigned long long)ldy * 4ull;
-   if (!isplib_dense_in_descriptor(n, ldy)) return fail(ISPLIB_FAIL, "isplib_sddmm_stream_hip: dense operand larger than 3.5 GiB (use isplib_sddmm_csr_hip)");
-   if (!pntrb || !pntre || !y || !g || !dval || !plan->wave_row || !plan->wave_step_off || (plan->n_steps > 0 && !plan->words))
-      return fail(ISPLIB_FAIL, "isplib_sddmm_stream_hip: null operand");
-   SweepArgs a = {};
-   a.empty_init = empty_row_init();
-   a.k = k; a.nnz = nnz; a.pntrb = pntrb; a.pntre = pntre;
-   a.y = y; a.ldy = ldy; a.ybytes = (unsigned)yb;
+   const char *entry = "isplib_sddmm_stream_hip";
+   const StreamCall c = {entry, "isplib_sddmm_csr_hip", STREAM_SUM, m, n, k, nnz, /* empty */ m == 0 || nnz == 0, pntrb, pntre, plan, y, ldy,
+                         /* ld_other */ ldg, /* others */ g && dval, /* hub_fold */ false, /* no workspace */ nullptr, 0, 0};
+   bool done;
+   const int rc = check_stream_call(c, &done);
+   if (done) return rc;
+   if (nnz >= ISPLIB_STREAM_NNZ_END) return fail(ISPLIB_FAIL, entry, "nnz < 2^31 required (32-bit CSR positions in the plan)");
+   if (plan->n_steps > 0 && !plan->perm) return fail(ISPLIB_FAIL, entry, "the plan's perm array is required (the CSR position of every word)");
+   SweepArgs a = stream_args(c, nullptr, 0);
    a.mean = mean ? 1 : 0;
-   a.ids = plan->perm;
-   a.wave_row = plan->wave_row; a.wave_part = plan->wave_part;
-   a.words = plan->words; a.wave_step_off = plan->wave_step_off; a.null_word = (unsigned)n;
    a.g = g; a.ldg = ldg; a.dval = dval;
    hipStream_t st = (hipStream_t)stream;
    const int64_t pw = 256 / plan->streams;
@@ -747,33 +705,38 @@ extern "C" int isplib_sddmm_stream_hip(int64_t m, int64_t n, int64_t k, int64_t 
       }
       p.y = y + at;
       p.g = g + at;
-      p.ybytes = (unsigned)(yb - (unsigned long long)at * 4ull);
-      for (int gen = 0; gen < plan->gens; gen++) {
-         p.wave_base = gen * plan->waves_per_gen;
-         p.wave_count = plan->waves_per_gen;
-         int rc;
-         if (plan->streams == 2) rc = first ? launch_sddmm_stream<32, false>(p, st) : launch_sddmm_stream<32, true>(p, st);
-         else if (plan->streams == 4) rc = first ? launch_sddmm_stream<16, false>(p, st) : launch_sddmm_stream<16, true>(p, st);
-         else rc = first ? launch_sddmm_stream<8, false>(p, st) : launch_sddmm_stream<8, true>(p, st);
-         if (rc) return rc;
-      }
+      p.ybytes = a.ybytes - (unsigned)at * 4u;
+      const int rc_gen = run_generations(plan->gens, plan->waves_per_gen, p, [&](const SweepArgs &q) {
+         if (plan->streams == 2) return first ? launch_sddmm_stream<2, false>(q, st) : launch_sddmm_stream<2, true>(q, st);
+         if (plan->streams == 4) return first ? launch_sddmm_stream<4, false>(q, st) : launch_sddmm_stream<4, true>(q, st);
+         return first ? launch_sddmm_stream<8, false>(q, st) : launch_sddmm_stream<8, true>(q, st);
+      });
+      if (rc_gen) return rc_gen;
       first = false;
    }
    return ISPLIB_SUCCESS;
 }
 
 // ---- hybrid form: entry ---------------------------------------------------------------------------------------------
-struct HybridGeom { int nvmax, nbw, ht, hwr; };
-static HybridGeom hybrid_geom(int streams) {
-   if (streams == 8) return {ISPLIB_HYB8_NV, ISPLIB_HYB8_NBW, ISPLIB_HYB8_HT, ISPLIB_HYB8_HWR};
-   return {ISPLIB_HYB4_NV, ISPLIB_HYB4_NBW, ISPLIB_HYB4_HT, ISPLIB_HYB4_HWR};
+// the hot side of the geometry: table rows (the last one zero) and hot-word registers; the cold side is a row of the stream table
+struct HybridGeom { int ht, hwr; };
+constexpr HybridGeom hybrid_geom(int streams) {
+   return streams == 8 ? HybridGeom{ISPLIB_HYB8_HT, ISPLIB_HYB8_HWR} : HybridGeom{ISPLIB_HYB4_HT, ISPLIB_HYB4_HWR};
+}
+
+template <int STREAMS>
+static int launch_hybrid(const SweepArgs &p, hipStream_t st) {
+   constexpr StreamGeom ge = stream_geom(STREAM_HYBRID, STREAMS);
+   constexpr HybridGeom hot = hybrid_geom(STREAMS);
+   hipLaunchKernelGGL((spmm_hybrid_kernel<ge.lpr, ge.nvmax, ge.nbw, hot.ht, hot.hwr>), dim3((unsigned)(p.wave_count / 8)), dim3(512), 0, st, p);
+   return check_launch("spmm_hybrid_kernel");
 }
 
 extern "C" int isplib_spmm_hybrid_geometry(int streams, int *rows_per_wave, int *waves_resident, int *table_rows, int *hot_cap) {
    clear_error();
    if (streams != 4 && streams != 8) return fail(ISPLIB_FAIL, "isplib_spmm_hybrid_geometry: streams must be 4 (64-column slots) or 8 (32-column slots)");
    const HybridGeom ge = hybrid_geom(streams);
-   if (rows_per_wave) *rows_per_wave = ge.nvmax;
+   if (rows_per_wave) *rows_per_wave = stream_geom(STREAM_HYBRID, streams).nvmax;
    if (waves_resident) *waves_resident = device_cus() * 8;            // one workgroup of 8 waves per CU
    if (table_rows) *table_rows = ge.ht;
    if (hot_cap) *hot_cap = ge.hwr * (64 / streams);
@@ -788,83 +751,28 @@ extern "C" int fusedMM_csr_hybrid_hip(int32_t imessage, int64_t m, int64_t n, in
                                       const int64_t *pntre, const isplib_hybrid_plan *hp, const float *y, int64_t ldy, float *z,
                                       int64_t ldz, void *workspace, size_t workspace_bytes, const isplib_epilogue *ep, void *stream) {
    clear_error();
-   if (imessage != ISPLIB_MSG_SPMM_SUM && imessage != ISPLIB_MSG_SPMM_MEAN)
-      return fail(ISPLIB_NO_OPT_IMPL, "fusedMM_csr_hybrid_hip: sum and mean only");
-   if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, "fusedMM_csr_hybrid_hip: negative dimension");
-   if (m == 0 || k == 0) return ISPLIB_SUCCESS;
-   if (!hp) return fail(ISPLIB_FAIL, "fusedMM_csr_hybrid_hip: plan is required");
-   const isplib_stream_plan *plan = &hp->cold;
-   if (plan->rows != m || plan->cols != n) return fail(ISPLIB_FAIL, "fusedMM_csr_hybrid_hip: the plan was built for another shape");
-   if (n >= ISPLIB_STREAM_N_END || ldy >= ISPLIB_STREAM_LDY_END) return fail(ISPLIB_FAIL, "fusedMM_csr_hybrid_hip: n must be < 2^24 and ldy < 2^22 (24-bit address arithmetic)");
-   if (plan->streams != 4 && plan->streams != 8) return fail(ISPLIB_FAIL, "fusedMM_csr_hybrid_hip: bad plan geometry (streams 4 or 8)");
-   const HybridGeom ge = hybrid_geom(plan->streams);
-   if (plan->gens < 1 || plan->waves_per_gen < 8 || (plan->waves_per_gen % 8) != 0 || plan->rows_per_wave != ge.nvmax ||
-       hp->table_rows != ge.ht || hp->hot_cap > ge.hwr * (64 / plan->streams) || plan->slices < 1)
-      return fail(ISPLIB_FAIL, "fusedMM_csr_hybrid_hip: bad plan geometry (isplib_spmm_hybrid_geometry reports rows per wave, table rows and the hot-step cap; waves_per_gen must be a multiple of 8)");
-   if (plan->vals) return fail(ISPLIB_FAIL, "fusedMM_csr_hybrid_hip: unit weights only (weighted graphs: fusedMM_csr_stream_hip)");
-   if (k < ISPLIB_K_MIN) return fail(ISPLIB_FAIL, "fusedMM_csr_hybrid_hip: k >= 4 required (use fusedMM_csr_hip)");
-   if (ldy < k || ldz < k) return fail(ISPLIB_FAIL, "fusedMM_csr_hybrid_hip: leading dimension smaller than k");
-   const unsigned long long yb = (unsigned long long)n * (unsigned long long)ldy * 4ull;
-   if (!isplib_dense_in_descriptor(n, ldy)) return fail(ISPLIB_FAIL, "fusedMM_csr_hybrid_hip: dense operand larger than 3.5 GiB (use fusedMM_csr_hip)");
-   if (!pntrb || !pntre || !z || !y || !plan->wave_row || !plan->wave_part || !plan->wave_step_off || (plan->n_steps > 0 && !plan->words) ||
-       (plan->n_hub > 0 && (!plan->hub_row || !plan->hub_off)) || !hp->hot_rows || !hp->hot_step_off || (hp->n_hot_steps > 0 && !hp->hot_words))
-      return fail(ISPLIB_FAIL, "fusedMM_csr_hybrid_hip: null operand");
-   if (plan->n_parts > 0) {
-      if (!workspace || workspace_bytes < isplib_spmm_stream_workspace_bytes(plan)) return fail(ISPLIB_NOT_ENOUGH_MEM, "fusedMM_csr_hybrid_hip: workspace too small");
-      if (((uintptr_t)workspace & 255) != 0) return fail(ISPLIB_FAIL, "fusedMM_csr_hybrid_hip: workspace must be 256-byte aligned");
-   }
-   SweepArgs a = {};
-   a.empty_init = empty_row_init();
-   a.k = k; a.nnz = nnz; a.pntrb = pntrb; a.pntre = pntre;
-   a.y = y; a.ldy = ldy; a.ybytes = (unsigned)yb; a.z = z; a.ldz = ldz;
+   const char *entry = "fusedMM_csr_hybrid_hip";
+   if (imessage != ISPLIB_MSG_SPMM_SUM && imessage != ISPLIB_MSG_SPMM_MEAN) return fail(ISPLIB_NO_OPT_IMPL, entry, "sum and mean only");
+   const isplib_stream_plan *plan = hp ? &hp->cold : nullptr;
+   const StreamCall c = {entry, "fusedMM_csr_hip", STREAM_HYBRID, m, n, k, nnz, /* empty */ m == 0 || k == 0, pntrb, pntre, plan, y, ldy,
+                         /* ld_other */ ldz, /* others */ z && hp && hp->hot_rows && hp->hot_step_off && (hp->n_hot_steps <= 0 || hp->hot_words),
+                         /* hub_fold */ true, workspace, workspace_bytes, isplib_spmm_stream_workspace_bytes(plan)};
+   bool done;
+   int rc = check_stream_call(c, &done);
+   if (done) return rc;
+   const HybridGeom hot = hybrid_geom(plan->streams);
+   if (plan->waves_per_gen < 8 || (plan->waves_per_gen % 8) != 0 || hp->table_rows != hot.ht || hp->hot_cap > hot.hwr * (64 / plan->streams) || plan->slices < 1)
+      return fail(ISPLIB_FAIL, entry, "bad plan geometry (isplib_spmm_hybrid_geometry reports rows per wave, table rows and the hot-step cap; waves_per_gen must be a multiple of 8)");
+   if (plan->vals) return fail(ISPLIB_FAIL, entry, "unit weights only (weighted graphs: fusedMM_csr_stream_hip)");
+   if ((rc = check_stream_workspace(c)) != ISPLIB_SUCCESS) return rc;
+   SweepArgs a = stream_args(c, z, ldz);
    a.mean = imessage == ISPLIB_MSG_SPMM_MEAN ? 1 : 0;
-   a.abs_ids = 1;
-   a.wave_row = plan->wave_row; a.wave_part = plan->wave_part;
-   a.words = plan->words; a.wave_step_off = plan->wave_step_off; a.null_word = (unsigned)n;
-   a.hub_row = plan->hub_row; a.hub_off = plan->hub_off; a.n_hub = plan->n_hub;
    a.hot_rows = hp->hot_rows; a.hot_words = hp->hot_words; a.hot_step_off = hp->hot_step_off; a.slices = plan->slices;
-   a.part_val = (float *)workspace;
-   if (ep) {
-      if (ep->self && ep->ld_self < k) return fail(ISPLIB_FAIL, "fusedMM_csr_hybrid_hip: ld_self smaller than k");
-      a.ep_row_scale = ep->row_scale; a.ep_self = ep->self; a.ep_ld_self = ep->ld_self; a.ep_bias = ep->bias;
-      a.ep_relu = ep->relu ? 1 : 0;
-   }
+   if ((rc = set_epilogue(entry, ep, a)) != ISPLIB_SUCCESS) return rc;
    hipStream_t st = (hipStream_t)stream;
-   const int64_t pw = 256 / plan->streams;
-   for (int64_t c0 = 0; c0 < k; c0 += pw) {
-      SweepArgs p = a;
-      p.k = (k - c0) < pw ? (k - c0) : pw;
-      if (p.k < 4) {
-         p.k = 4;
-         c0 = k - 4;
-      }
-      p.y = y + c0;
-      p.z = z + c0;
-      p.ep_self = a.ep_self ? a.ep_self + c0 : nullptr;
-      p.ep_bias = a.ep_bias ? a.ep_bias + c0 : nullptr;
-      p.ybytes = (unsigned)(yb - (unsigned long long)c0 * 4ull);
-      for (int gen = 0; gen < plan->gens; gen++) {
-         p.wave_base = gen * plan->waves_per_gen;
-         p.wave_count = plan->waves_per_gen;
-         const unsigned blocks = (unsigned)(p.wave_count / 8);
-         if (plan->streams == 4)
-            hipLaunchKernelGGL((spmm_hybrid_kernel<16, ISPLIB_HYB4_NV, ISPLIB_HYB4_NBW, ISPLIB_HYB4_HT, ISPLIB_HYB4_HWR>), dim3(blocks), dim3(512), 0, st, p);
-         else
-            hipLaunchKernelGGL((spmm_hybrid_kernel<8, ISPLIB_HYB8_NV, ISPLIB_HYB8_NBW, ISPLIB_HYB8_HT, ISPLIB_HYB8_HWR>), dim3(blocks), dim3(512), 0, st, p);
-         const int rc = check_launch("spmm_hybrid_kernel");
-         if (rc) return rc;
-      }
-      if (plan->n_hub > 0) {
-         const bool v4 = (p.k % 4) == 0 && (p.ldz % 4) == 0 && ((uintptr_t)p.z & 15) == 0 && (!p.ep_self || ((p.ep_ld_self % 4) == 0 && ((uintptr_t)p.ep_self & 15) == 0));
-         int64_t blocks = (plan->n_hub * (v4 ? p.k / 4 : p.k) + 255) / 256;
-         if (blocks > 4096) blocks = 4096;
-         if (v4) hipLaunchKernelGGL((sweep_hub_fold_kernel<OP_ADD, 4>), dim3((unsigned)blocks), dim3(256), 0, st, p);
-         else hipLaunchKernelGGL((sweep_hub_fold_kernel<OP_ADD, 1>), dim3((unsigned)blocks), dim3(256), 0, st, p);
-         const int rc = check_launch("sweep_hub_fold_kernel");
-         if (rc) return rc;
-      }
-   }
-   return ISPLIB_SUCCESS;
+   return run_stream_panels(plan, a,
+      [&](const SweepArgs &p) { return plan->streams == 4 ? launch_hybrid<4>(p, st) : launch_hybrid<8>(p, st); },
+      [&](const SweepArgs &p) { return launch_hub_fold<OP_ADD, true>(p, st); });
 }
 
 extern "C" int isplib_internal_set_sddmm_panel_cols(int cols);      // libisplib_hip.so (spmm.hip); not a public entry

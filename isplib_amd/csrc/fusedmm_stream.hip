@@ -36,14 +36,6 @@ __device__ __forceinline__ float sop_menu(int kind, float s, float p) {
    }
 }
 
-// geometry per slot width: rows per wave (without the spare row), 64-word batch registers, workgroups per CU
-struct GenStreamGeom { int nvmax, nbw, wgs; };
-static inline GenStreamGeom gen_stream_geom(int streams) {
-   if (streams == 2) return {16, 1, 2};     // 128-column slots: 2 rows per gather, 32 gathers in flight
-   if (streams == 4) return {32, 2, 2};     // 64-column slots
-   return {64, 4, 2};                       // 32-column slots
-}
-
 // PAT 1: T = y_j, s = f(<x_i, y_j>);   PAT 2: T = y_j - x_i, s = f(|T|^2);   z_i += s * T
 template <int PAT, int LPR, int NVMAX, int NBW, int WGS>
 __global__ __launch_bounds__(256, (stream_wgs_per_cu<LPR, 2 * (NVMAX + 1), WGS>())) void fusedmm_stream_kernel(const SweepArgs a, const int sop_udef,
@@ -174,14 +166,19 @@ __global__ __launch_bounds__(256, (stream_wgs_per_cu<LPR, 2 * (NVMAX + 1), WGS>(
    }
 }
 
-template <int PAT>
-static int launch_fusedmm_stream(const SweepArgs &a, int streams, int sop_udef, float sop_param, hipStream_t st) {
+template <int PAT, int STREAMS>
+static int launch_fusedmm_stream(const SweepArgs &a, int sop_udef, float sop_param, hipStream_t st) {
+   constexpr StreamGeom ge = stream_geom(STREAM_FUSEDMM, STREAMS);
    const unsigned blocks = (unsigned)((a.wave_count + 3) / 4);
    if (blocks == 0) return ISPLIB_SUCCESS;
-   if (streams == 2) hipLaunchKernelGGL((fusedmm_stream_kernel<PAT, 32, 16, 1, 2>), dim3(blocks), dim3(256), 0, st, a, sop_udef, sop_param);
-   else if (streams == 4) hipLaunchKernelGGL((fusedmm_stream_kernel<PAT, 16, 32, 2, 2>), dim3(blocks), dim3(256), 0, st, a, sop_udef, sop_param);
-   else hipLaunchKernelGGL((fusedmm_stream_kernel<PAT, 8, 64, 4, 2>), dim3(blocks), dim3(256), 0, st, a, sop_udef, sop_param);
+   hipLaunchKernelGGL((fusedmm_stream_kernel<PAT, ge.lpr, ge.nvmax, ge.nbw, ge.wgs>), dim3(blocks), dim3(256), 0, st, a, sop_udef, sop_param);
    return check_launch("fusedmm_stream_kernel");
+}
+
+template <int PAT>
+static int launch_fusedmm_stream(const SweepArgs &a, int streams, int sop_udef, float sop_param, hipStream_t st) {
+   return streams == 2 ? launch_fusedmm_stream<PAT, 2>(a, sop_udef, sop_param, st)
+        : streams == 4 ? launch_fusedmm_stream<PAT, 4>(a, sop_udef, sop_param, st) : launch_fusedmm_stream<PAT, 8>(a, sop_udef, sop_param, st);
 }
 
 }  // namespace isplib
@@ -196,17 +193,7 @@ static int stream_pattern(int32_t imessage) {
 }
 
 extern "C" int isplib_fusedmm_stream_geometry(int streams, int *rows_per_wave, int *waves_resident) {
-   clear_error();
-   if (streams != 2 && streams != 4 && streams != 8) return fail(ISPLIB_FAIL, "isplib_fusedmm_stream_geometry: streams must be 2, 4 or 8");
-   const GenStreamGeom ge = gen_stream_geom(streams);
-   if (rows_per_wave) *rows_per_wave = ge.nvmax;
-   if (waves_resident) {
-      const int lds = 2 * 4 * (ge.nvmax + 1) * (64 / streams) * 4 * 4;
-      int wgs = 163840 / lds;
-      if (wgs > ge.wgs) wgs = ge.wgs;
-      *waves_resident = device_cus() * wgs * 4;
-   }
-   return ISPLIB_SUCCESS;
+   return stream_geometry("isplib_fusedmm_stream_geometry", STREAM_FUSEDMM, streams, rows_per_wave, waves_resident);
 }
 
 extern "C" int isplib_suggest_fusedmm_stream(int32_t imessage, int64_t m, int64_t n, int64_t nnz, int64_t k, int *streams, int *slices, int *chunk) {
@@ -222,16 +209,8 @@ extern "C" int isplib_suggest_fusedmm_stream(int32_t imessage, int64_t m, int64_
    const int st = k <= 32 ? 8 : (k <= 64 ? 4 : 2);
    int rpw = 0, resident = 0;
    if (isplib_fusedmm_stream_geometry(st, &rpw, &resident) != ISPLIB_SUCCESS) return 0;
-   const int64_t per_gen = (int64_t)rpw * resident;
-   const int64_t gens = (m + per_gen - 1) / per_gen;
-   if ((double)nnz / (double)gens / 8.0 < 3.0 * (double)n) return 0;
-   int sl = (int)((double)n * (1024.0 / st) / (st == 2 ? 2.6e6 : 3.8e6) + 0.5);
-   sl = sl < 1 ? 1 : (sl > 512 ? 512 : sl);
-   int64_t ch = (int64_t)((double)nnz / ((double)gens * resident * st) / 2.4);
-   ch = ch < 256 ? 256 : (ch > (1 << 20) ? (1 << 20) : ch);
+   if (!suggest_stream_geom(m, n, nnz, st, rpw, resident, st == 2 ? 2.6e6 : 3.8e6, 2.4, slices, chunk)) return 0;
    if (streams) *streams = st;
-   if (slices) *slices = sl;
-   if (chunk) *chunk = (int)ch;
    return 1;
 }
 
@@ -240,53 +219,26 @@ extern "C" int fusedMM_csr_udef_stream_hip(int32_t imessage, int64_t m, int64_t 
                                            const float *y, int64_t ldy, float *z, int64_t ldz, int sop_udef, float sop_param,
                                            void *workspace, size_t workspace_bytes, void *stream) {
    clear_error();
+   const char *entry = "fusedMM_csr_udef_stream_hip";
    const int pat = stream_pattern(imessage);
-   if (!pat) return fail(ISPLIB_NO_OPT_IMPL, "fusedMM_csr_udef_stream_hip: COPY_RHS|DOT|UDEF|MUL|ADD and SUBR|NORMR|UDEF|MUL|ADD only (other words: fusedMM_csr_udef_hip)");
+   if (!pat) return fail(ISPLIB_NO_OPT_IMPL, entry, "COPY_RHS|DOT|UDEF|MUL|ADD and SUBR|NORMR|UDEF|MUL|ADD only (other words: fusedMM_csr_udef_hip)");
    if (sop_udef < ISPLIB_SOP_SIGMOID || sop_udef > ISPLIB_SOP_LEAKY_EXP)
-      return fail(ISPLIB_UNDEFINED_USER_FUNCTION, "fusedMM_csr_udef_stream_hip: SOP_UDEF needs a built-in function (enum isplib_sop_udef)");
-   if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, "fusedMM_csr_udef_stream_hip: negative dimension");
-   if (m == 0 || k == 0) return ISPLIB_SUCCESS;
-   if (!plan) return fail(ISPLIB_FAIL, "fusedMM_csr_udef_stream_hip: plan is required");
-   if (plan->rows != m || plan->cols != n) return fail(ISPLIB_FAIL, "fusedMM_csr_udef_stream_hip: the plan was built for another shape");
-   if (plan->streams != 2 && plan->streams != 4 && plan->streams != 8) return fail(ISPLIB_FAIL, "fusedMM_csr_udef_stream_hip: bad plan geometry (streams 2, 4 or 8)");
-   if (plan->gens < 1 || plan->waves_per_gen < 1 || plan->rows_per_wave != gen_stream_geom(plan->streams).nvmax)
-      return fail(ISPLIB_FAIL, "fusedMM_csr_udef_stream_hip: bad plan geometry (a plan of isplib_stream_plan_build_fusedmm_hip is required)");
-   if (k < ISPLIB_K_MIN || (k % 4) != 0 || k > 256 / plan->streams)
-      return fail(ISPLIB_FAIL, "fusedMM_csr_udef_stream_hip: k must be a multiple of 4 within the plan's slot width (256 / streams columns); use fusedMM_csr_udef_tasks_hip");
-   if (ldy < k || ldz < k || ldx < k || (ldx % 4) != 0 || (ldz % 4) != 0 || ((uintptr_t)x & 15) != 0 || ((uintptr_t)z & 15) != 0)
-      return fail(ISPLIB_FAIL, "fusedMM_csr_udef_stream_hip: ldx, ldz multiples of 4 and >= k, x and z 16-byte aligned");
-   if (n >= ISPLIB_STREAM_N_END || ldy >= ISPLIB_STREAM_LDY_END) return fail(ISPLIB_FAIL, "fusedMM_csr_udef_stream_hip: n must be < 2^24 and ldy < 2^22 (24-bit address arithmetic)");
-   const unsigned long long yb = (unsigned long long)n * (unsigned long long)ldy * 4ull;
-   if (!isplib_dense_in_descriptor(n, ldy)) return fail(ISPLIB_FAIL, "fusedMM_csr_udef_stream_hip: dense operand larger than 3.5 GiB");
-   if (!pntrb || !pntre || !x || !y || !z || !plan->wave_row || !plan->wave_part || !plan->wave_step_off || (plan->n_steps > 0 && !plan->words) ||
-       (plan->n_hub > 0 && (!plan->hub_row || !plan->hub_off)))
-      return fail(ISPLIB_FAIL, "fusedMM_csr_udef_stream_hip: null operand");
-   if (plan->n_parts > 0) {
-      if (!workspace || workspace_bytes < ((size_t)plan->n_parts * (size_t)k * sizeof(float))) return fail(ISPLIB_NOT_ENOUGH_MEM, "fusedMM_csr_udef_stream_hip: workspace too small");
-      if (((uintptr_t)workspace & 255) != 0) return fail(ISPLIB_FAIL, "fusedMM_csr_udef_stream_hip: workspace must be 256-byte aligned");
-   }
-   SweepArgs a = {};
-   a.k = k; a.nnz = nnz; a.pntrb = pntrb; a.pntre = pntre;
-   a.y = y; a.ldy = ldy; a.ybytes = (unsigned)yb; a.z = z; a.ldz = ldz;
+      return fail(ISPLIB_UNDEFINED_USER_FUNCTION, entry, "SOP_UDEF needs a built-in function (enum isplib_sop_udef)");
+   const StreamCall c = {entry, "fusedMM_csr_udef_tasks_hip", STREAM_FUSEDMM, m, n, k, nnz, /* empty */ m == 0 || k == 0, pntrb, pntre, plan, y, ldy,
+                         /* ld_other */ ldz, /* others */ x && z, /* hub_fold */ true, workspace, workspace_bytes, (size_t)(plan ? plan->n_parts : 0) * (size_t)k * sizeof(float)};
+   bool done;
+   int rc = check_stream_call(c, &done);
+   if (done) return rc;
+   if ((k % 4) != 0 || k > 256 / plan->streams)
+      return fail(ISPLIB_FAIL, entry, "k must be a multiple of 4 within the plan's slot width (256 / streams columns); use fusedMM_csr_udef_tasks_hip");
+   if (ldx < k || (ldx % 4) != 0 || (ldz % 4) != 0 || ((uintptr_t)x & 15) != 0 || ((uintptr_t)z & 15) != 0)
+      return fail(ISPLIB_FAIL, entry, "ldx, ldz multiples of 4 and >= k, x and z 16-byte aligned");
+   if ((rc = check_stream_workspace(c)) != ISPLIB_SUCCESS) return rc;
+   SweepArgs a = stream_args(c, z, ldz);
    a.g = x; a.ldg = ldx;
-   a.abs_ids = 1;
-   a.wave_row = plan->wave_row; a.wave_part = plan->wave_part;
-   a.words = plan->words; a.wave_step_off = plan->wave_step_off; a.null_word = (unsigned)n;
-   a.hub_row = plan->hub_row; a.hub_off = plan->hub_off; a.n_hub = plan->n_hub;
-   a.part_val = (float *)workspace;
    hipStream_t st = (hipStream_t)stream;
-   for (int gen = 0; gen < plan->gens; gen++) {
-      a.wave_base = gen * plan->waves_per_gen;
-      a.wave_count = plan->waves_per_gen;
-      const int rc = pat == 1 ? launch_fusedmm_stream<1>(a, plan->streams, sop_udef, sop_param, st) : launch_fusedmm_stream<2>(a, plan->streams, sop_udef, sop_param, st);
-      if (rc) return rc;
-   }
-   if (plan->n_hub > 0) {
-      int64_t blocks = (plan->n_hub * (k / 4) + 255) / 256;
-      if (blocks > 4096) blocks = 4096;
-      hipLaunchKernelGGL((sweep_hub_fold_kernel<OP_ADD, 4>), dim3((unsigned)blocks), dim3(256), 0, st, a);
-      const int rc = check_launch("sweep_hub_fold_kernel");
-      if (rc) return rc;
-   }
-   return ISPLIB_SUCCESS;
+   rc = run_generations(plan->gens, plan->waves_per_gen, a, [&](const SweepArgs &p) {
+      return pat == 1 ? launch_fusedmm_stream<1>(p, plan->streams, sop_udef, sop_param, st) : launch_fusedmm_stream<2>(p, plan->streams, sop_udef, sop_param, st);
+   });
+   return rc ? rc : launch_hub_fold<OP_ADD, false>(a, st);
 }

@@ -359,22 +359,50 @@ static int build_plan(isplib_graph *g, Side &s, int slices, hipStream_t st, Plan
    return rc;
 }
 
+// the side's task plan for a slice count, built on first use (a half-built one is freed); it may be unusable: see Plan
+static int side_task_plan(isplib_graph *g, Side &s, int slices, hipStream_t st, const Plan **out) {
+   auto it = s.plans.find(slices);
+   if (it == s.plans.end()) {
+      Plan p;
+      const int rc = build_plan(g, s, slices, st, p);
+      if (rc) {
+         (void)hipFree(p.task_row); (void)hipFree(p.task_len); (void)hipFree(p.seg_off); (void)hipFree(p.task_b);
+         return rc;
+      }
+      it = s.plans.emplace(slices, p).first;
+   }
+   *out = &it->second;
+   return ISPLIB_SUCCESS;
+}
+
+// One scalar from the device: zeroed, handed to `launch` (a flag or accumulator kernel on the stream), read back -- one small
+// allocation and one synchronisation.  false: could not be done (nothing is cached by the callers: they try again later).
+template <class T, class Launch>
+static bool device_scalar(hipStream_t st, T *host, Launch launch) {
+   T *dev = nullptr;
+   if (hipMalloc((void **)&dev, 256) != hipSuccess) { (void)hipGetLastError(); return false; }
+   bool ok = hipMemsetAsync(dev, 0, sizeof(T), st) == hipSuccess;
+   if (ok) {
+      launch(dev);
+      ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(host, dev, sizeof(T), hipMemcpyDeviceToHost, st) == hipSuccess &&
+           hipStreamSynchronize(st) == hipSuccess;
+   }
+   (void)hipFree(dev);
+   if (!ok) (void)hipGetLastError();
+   return ok;
+}
+
 // 1 if the side's own weights are all exactly 1.0f (then x * 1.0f == x bit for bit and the stream can be skipped)
 static int weights_are_unit(Side &s, hipStream_t st) {
    if (s.unit >= 0) return s.unit;
    if (!s.val || s.nnz == 0) return s.unit = 0;
-   int *flag = nullptr, host = 1;
-   if (hipMalloc((void **)&flag, 256) != hipSuccess) { (void)hipGetLastError(); return 0; }     // undecided: try again later
-   bool ok = hipMemsetAsync(flag, 0, sizeof(int), st) == hipSuccess;
-   if (ok) {
+   int other = 1;
+   const bool ok = device_scalar(st, &other, [&](int *flag) {
       const int64_t blocks = (s.nnz + 255) / 256;
       hipLaunchKernelGGL(not_all_ones_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, s.nnz, s.val, flag);
-      ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(&host, flag, sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess &&
-           hipStreamSynchronize(st) == hipSuccess;
-   }
-   (void)hipFree(flag);
-   if (!ok) { (void)hipGetLastError(); return 0; }
-   return s.unit = host ? 0 : 1;
+   });
+   if (!ok) return 0;                                     // undecided: try again later
+   return s.unit = other ? 0 : 1;
 }
 
 // The rule's 7 MB per slice leans on the popularity skew of real degree distributions (the hot rows of y stay in
@@ -384,19 +412,14 @@ static int weights_are_unit(Side &s, hipStream_t st) {
 static int skew_adjusted(Side &s, int slices, hipStream_t st, int cap = 64) {
    if (slices <= 0 || s.m <= 0 || s.nnz <= 0) return slices;
    if (s.cv2 < 0.0) {
-      double *acc = nullptr, host = 0.0;
-      if (hipMalloc((void **)&acc, 256) != hipSuccess) { (void)hipGetLastError(); return slices; }
-      bool ok = hipMemsetAsync(acc, 0, sizeof(double), st) == hipSuccess;
-      if (ok) {
+      double squares = 0.0;
+      const bool ok = device_scalar(st, &squares, [&](double *acc) {
          const int64_t blocks = (s.m + 255) / 256;
          hipLaunchKernelGGL(degree_squares_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, s.m, s.rowptr, acc);
-         ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(&host, acc, sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
-              hipStreamSynchronize(st) == hipSuccess;
-      }
-      (void)hipFree(acc);
-      if (!ok) { (void)hipGetLastError(); return slices; }
+      });
+      if (!ok) return slices;
       const double mean = (double)s.nnz / (double)s.m;
-      s.cv2 = host / (double)s.m / (mean * mean) - 1.0;
+      s.cv2 = squares / (double)s.m / (mean * mean) - 1.0;
       if (s.cv2 < 0.0) s.cv2 = 0.0;
    }
    if (s.cv2 >= 0.25) return slices;
@@ -404,160 +427,110 @@ static int skew_adjusted(Side &s, int slices, hipStream_t st, int cap = 64) {
    return more > cap ? cap : more;
 }
 
-// The side's sum / mean stream plan for width k, built on first use with the weights `val` (NULL: unit weights); *out stays
-// null where the stream schedule does not serve the shape (the rule, a forced slice count, a refusal of the builder, no
-// room for the plan): not an error, the caller's other schedules take the call.
-static int side_stream_plan(isplib_graph *g, Side &s, const float *val, int64_t k, int64_t ldy, hipStream_t st, Side::Stream **out) {
+// The side's stream plan of a family (sum / mean, or max / min: its own kernel and plan geometry, for column-sorted rows) for
+// width k, built on first use with the weights `val` (NULL: unit weights); *out stays null where the stream schedule does not
+// serve the shape (the rule, a forced slice count, a refusal of the builder, no room for the plan): not an error, the caller's
+// other schedules take the call.
+// (Both entries' domains are asked WITH THE CALLER'S ldy, the rules only see k: a padded leading dimension that crosses a limit --
+// max / min admit dense operands under 2 GiB, lanes past column k carry 2^31 in their column term -- stays on the task list.)
+static int side_stream_plan(isplib_graph *g, Side &s, bool minmax, const float *val, int64_t k, int64_t ldy, hipStream_t st, Side::Stream **out) {
    *out = nullptr;
-   int st_streams = 0, st_slices = 0, st_chunk = 0;
-   if (g->forced_slices >= 0 || s.stream_refused || !isplib_stream_serves(s.n, k, ldy, s.nnz, 0) ||      // with the caller's ldy: the rule only sees k
-       !isplib_suggest_stream_weighted(s.m, s.n, s.nnz, k, val != nullptr, &st_streams, &st_slices, &st_chunk))
+   bool &refused = minmax ? s.minmax_stream_refused : s.stream_refused;
+   int streams = 0, slices = 0, chunk = 0;
+   if (g->forced_slices >= 0 || refused || !isplib_stream_serves(s.n, k, ldy, s.nnz, minmax ? 1 : 0)) return ISPLIB_SUCCESS;
+   if (!(minmax ? isplib_suggest_stream_minmax(s.m, s.n, s.nnz, k, &streams, &slices, &chunk)
+                : isplib_suggest_stream_weighted(s.m, s.n, s.nnz, k, val != nullptr, &streams, &slices, &chunk)))
       return ISPLIB_SUCCESS;
-   st_slices = skew_adjusted(s, st_slices, st, 512);      // no degree skew: slices closer to the L2 size (31 -> 47: 3.21 -> 3.00 ms)
-   const uint64_t key = ((uint64_t)st_streams << 48) | ((uint64_t)st_slices << 32) | (uint64_t)(uint32_t)st_chunk;
+   slices = skew_adjusted(s, slices, st, 512);            // no degree skew: slices closer to the L2 size (31 -> 47: 3.21 -> 3.00 ms)
+   const uint64_t key = (minmax ? 1ULL << 63 : 0) | ((uint64_t)streams << 48) | ((uint64_t)slices << 32) | (uint64_t)(uint32_t)chunk;
    auto it = s.streams.find(key);
    if (it == s.streams.end()) {
       Side::Stream fresh;
-      const int rc = isplib_stream_plan_build_hip(s.m, s.n, s.nnz, s.rowptr, s.col, val, st_streams, st_slices, st_chunk, 0, &fresh.plan, st);
-      if (rc == ISPLIB_SUCCESS) {
-         fresh.vals_of = val; fresh.has_vals = val != nullptr; fresh.gen = g->val_gen;
-         it = s.streams.emplace(key, fresh).first;
-      } else if (rc == ISPLIB_FAIL) {
-         s.stream_refused = true;                  // outside the builder's domain: not an error of this call; the
-         clear_error();                            // task list / plain kernel serve the graph
-         return ISPLIB_SUCCESS;
-      } else if (rc != ISPLIB_NOT_ENOUGH_MEM) {
-         return rc;
-      } else {
-         clear_error();                            // no room for the plan: the task list / plain kernel need less
+      const int rc = minmax ? isplib_stream_plan_build_minmax_hip(s.m, s.n, s.nnz, s.rowptr, s.col, val, streams, slices, chunk, 0, &fresh.plan, st)
+                            : isplib_stream_plan_build_hip(s.m, s.n, s.nnz, s.rowptr, s.col, val, streams, slices, chunk, 0, &fresh.plan, st);
+      if (rc == ISPLIB_FAIL || rc == ISPLIB_NOT_ENOUGH_MEM) {
+         // not this schedule, and not an error of this call: the task list / plain kernel serve the graph.  FAIL: outside the
+         // builder's domain (max / min: rows not column-sorted), for good; no room for the plan: the others need less
+         if (rc == ISPLIB_FAIL) refused = true;
+         clear_error();
          return ISPLIB_SUCCESS;
       }
+      if (rc) return rc;
+      fresh.vals_of = val; fresh.has_vals = val != nullptr; fresh.gen = g->val_gen;
+      it = s.streams.emplace(key, fresh).first;
    }
    *out = &it->second;
    return ISPLIB_SUCCESS;
 }
 
+// The plan's copy of the weights (in stream order) made to follow `val`: other weights than last time (sum vs mean backward),
+// or new contents (isplib_graph_set_values): one gather through the plan's permutation.  park (sum / mean): see Side::Stream.
+static int refresh_stream_values(isplib_graph *g, Side::Stream *sp, const float *val, bool park, hipStream_t st) {
+   if (sp->vals_of == val && sp->has_vals == (val != nullptr) && !(val && sp->gen != g->val_gen)) return ISPLIB_SUCCESS;
+   if (park && val && sp->has_vals && sp->plan.vals) {
+      // both weighted: the copy being replaced is parked in `other`; if `other` already holds what is wanted
+      // (same source array, same generation) the two are swapped and nothing is gathered
+      float *parked = const_cast<float *>(sp->plan.vals);
+      const float *parked_of = sp->vals_of;
+      const uint64_t parked_gen = sp->gen;
+      const bool hit = sp->other && sp->other_of == val && sp->other_gen == g->val_gen;
+      sp->plan.vals = sp->other;                  // NULL: set_values allocates a fresh array
+      if (!hit) {
+         const int rc = isplib_stream_plan_set_values_hip(&sp->plan, val, st);
+         if (rc) {
+            // a fresh array may have been allocated before the gather failed: it is neither `parked` nor `other`
+            if (sp->plan.vals && sp->plan.vals != parked && sp->plan.vals != sp->other) (void)hipFree(const_cast<float *>(sp->plan.vals));
+            sp->plan.vals = parked;
+            return rc;
+         }
+      }
+      sp->other = parked; sp->other_of = parked_of; sp->other_gen = parked_gen;
+   } else {
+      const int rc = isplib_stream_plan_set_values_hip(&sp->plan, val, st);
+      if (rc) return rc;
+   }
+   sp->vals_of = val; sp->has_vals = val != nullptr; sp->gen = g->val_gen;
+   return ISPLIB_SUCCESS;
+}
+
+// One SpMM over a side: the stream schedule where it is offered (graphs with work for the whole chip, rows resident in LDS, the
+// plan's own copy of the edges), else the task list over column slices, else the plain ordered kernel.
 static int run_side(isplib_graph *g, Side &s, const float *val, int32_t imessage, int64_t k, const float *y, int64_t ldy,
                     float *z, int64_t ldz, int64_t *z_arg, hipStream_t st) {
    if (val && val == s.val && weights_are_unit(s, st) == 1) val = nullptr;
    const int minmax = (imessage & 0xF0000) != ISPLIB_AOP_ADD;
-   // sum / mean on graphs with work for the whole chip: the stream schedule (rows resident in LDS, the plan's own copy of
-   // the edges), unless a slice count was forced
-   if (!minmax) {
-      Side::Stream *sp = nullptr;
-      int rc = side_stream_plan(g, s, val, k, ldy, st, &sp);
-      if (rc) return rc;
-      if (sp) {
-         if (sp->vals_of != val || sp->has_vals != (val != nullptr) || (val && sp->gen != g->val_gen)) {
-            // other weights than last time (sum vs mean backward), or new contents (isplib_graph_set_values)
-            if (val && sp->has_vals && sp->plan.vals) {
-               // both weighted: the copy being replaced is parked in `other`; if `other` already holds what is wanted
-               // (same source array, same generation) the two are swapped and nothing is gathered
-               float *parked = const_cast<float *>(sp->plan.vals);
-               const float *parked_of = sp->vals_of;
-               const uint64_t parked_gen = sp->gen;
-               const bool hit = sp->other && sp->other_of == val && sp->other_gen == g->val_gen;
-               sp->plan.vals = sp->other;                  // NULL: set_values allocates a fresh array
-               if (!hit) {
-                  rc = isplib_stream_plan_set_values_hip(&sp->plan, val, st);
-                  if (rc) {
-                     // a fresh array may have been allocated before the gather failed: it is neither `parked` nor `other`
-                     if (sp->plan.vals && sp->plan.vals != parked && sp->plan.vals != sp->other) (void)hipFree(const_cast<float *>(sp->plan.vals));
-                     sp->plan.vals = parked;
-                     return rc;
-                  }
-               }
-               sp->other = parked; sp->other_of = parked_of; sp->other_gen = parked_gen;
-            } else {
-               rc = isplib_stream_plan_set_values_hip(&sp->plan, val, st);
-               if (rc) return rc;
-            }
-            sp->vals_of = val; sp->has_vals = val != nullptr; sp->gen = g->val_gen;
-         }
-         const size_t need = isplib_spmm_stream_workspace_bytes(&sp->plan);
-         isplib_graph::Work *w = nullptr;
-         rc = ensure_work(g, need, st, &w);
-         if (rc) return rc;
-         return fusedMM_csr_stream_hip(imessage, s.m, s.n, k, s.nnz, s.rowptr, s.rowptr + 1, &sp->plan, y, ldy, z, ldz, w->ptr, w->bytes, nullptr, st);
-      }
-   }
-   // max / min on such graphs: the stream schedule's own kernel and plan geometry, for column-sorted rows
-   int mm_streams = 0, mm_slices = 0, mm_chunk = 0;
-   // (the max / min entry admits dense operands under 2 GiB WITH THE CALLER'S ldy -- lanes past column k carry 2^31 in their
-   // column term -- while the rule only sees k: a padded leading dimension that crosses it stays on the task list)
-   if (minmax && g->forced_slices < 0 && !s.minmax_stream_refused && isplib_stream_serves(s.n, k, ldy, s.nnz, 1) &&
-       isplib_suggest_stream_minmax(s.m, s.n, s.nnz, k, &mm_streams, &mm_slices, &mm_chunk)) {
-      mm_slices = skew_adjusted(s, mm_slices, st, 512);
-      const uint64_t key = (1ULL << 63) | ((uint64_t)mm_streams << 48) | ((uint64_t)mm_slices << 32) | (uint64_t)(uint32_t)mm_chunk;
-      auto it = s.streams.find(key);
-      if (it == s.streams.end()) {
-         Side::Stream fresh;
-         const int rc = isplib_stream_plan_build_minmax_hip(s.m, s.n, s.nnz, s.rowptr, s.col, val, mm_streams, mm_slices, mm_chunk, 0, &fresh.plan, st);
-         if (rc == ISPLIB_SUCCESS) {
-            fresh.vals_of = val; fresh.has_vals = val != nullptr; fresh.gen = g->val_gen;
-            it = s.streams.emplace(key, fresh).first;
-         } else if (rc == ISPLIB_FAIL) {
-            s.minmax_stream_refused = true;           // unsorted rows (or outside the builder's domain): not an error of this call
-            clear_error();
-         } else if (rc != ISPLIB_NOT_ENOUGH_MEM) {
-            return rc;
-         }
-      }
-      if (it != s.streams.end()) {
-         Side::Stream &sp = it->second;
-         if (sp.vals_of != val || sp.has_vals != (val != nullptr) || (val && sp.gen != g->val_gen)) {
-            const int rc = isplib_stream_plan_set_values_hip(&sp.plan, val, st);
-            if (rc) return rc;
-            sp.vals_of = val; sp.has_vals = val != nullptr; sp.gen = g->val_gen;
-         }
-         const size_t need = isplib_spmm_stream_minmax_workspace_bytes(&sp.plan);
-         isplib_graph::Work *w = nullptr;
-         const int rc = ensure_work(g, need, st, &w);
-         if (rc) return rc;
-         return fusedMM_csr_stream_minmax_hip(imessage, s.m, s.n, k, s.nnz, s.rowptr, s.rowptr + 1, &sp.plan, y, ldy, z, ldz, z_arg, w->ptr,
-                                              w->bytes, st);
-      }
+   isplib_graph::Work *w = nullptr;
+   Side::Stream *sp = nullptr;
+   int rc = side_stream_plan(g, s, minmax != 0, val, k, ldy, st, &sp);
+   if (rc) return rc;
+   if (sp) {
+      if ((rc = refresh_stream_values(g, sp, val, !minmax, st)) != ISPLIB_SUCCESS) return rc;
+      const size_t need = minmax ? isplib_spmm_stream_minmax_workspace_bytes(&sp->plan) : isplib_spmm_stream_workspace_bytes(&sp->plan);
+      if ((rc = ensure_work(g, need, st, &w)) != ISPLIB_SUCCESS) return rc;
+      if (minmax)
+         return fusedMM_csr_stream_minmax_hip(imessage, s.m, s.n, k, s.nnz, s.rowptr, s.rowptr + 1, &sp->plan, y, ldy, z, ldz, z_arg, w->ptr, w->bytes, st);
+      return fusedMM_csr_stream_hip(imessage, s.m, s.n, k, s.nnz, s.rowptr, s.rowptr + 1, &sp->plan, y, ldy, z, ldz, w->ptr, w->bytes, nullptr, st);
    }
    int slices = g->forced_slices >= 0 ? g->forced_slices : isplib_suggest_slices(s.m, s.n, s.nnz, k, minmax);
    if (!isplib_tasks_serve(s.n, k, ldy)) slices = 0;      // outside the task entry's domain
    if (g->forced_slices < 0) slices = skew_adjusted(s, slices, st);
+   const Plan *p = nullptr;
    if (slices > 0 && g->forced_slices < 0) {
       // The panel rule halves the slice count to make tasks long enough.  If they are long anyway (hub-dominated
       // graphs: >= 120 edges per task on the panel plan), the whole-row plan with one pass is the better schedule.
       const int whole = isplib_suggest_slices_whole_rows(s.m, s.n, s.nnz, k);
       if (whole > slices) {
-         auto it = s.plans.find(slices);
-         if (it == s.plans.end()) {
-            Plan p;
-            const int rc = build_plan(g, s, slices, st, p);
-            if (rc) {
-               (void)hipFree(p.task_row); (void)hipFree(p.task_len); (void)hipFree(p.seg_off); (void)hipFree(p.task_b);
-               return rc;
-            }
-            it = s.plans.emplace(slices, p).first;
-         }
-         if (it->second.usable && it->second.n_tasks > 0 && (double)s.nnz / (double)it->second.n_tasks >= 120.0) slices = whole;
+         if ((rc = side_task_plan(g, s, slices, st, &p)) != ISPLIB_SUCCESS) return rc;
+         if (p->usable && p->n_tasks > 0 && (double)s.nnz / (double)p->n_tasks >= 120.0) slices = whole;
       }
    }
    if (slices > 0) {
-      auto it = s.plans.find(slices);
-      if (it == s.plans.end()) {
-         Plan p;
-         const int rc = build_plan(g, s, slices, st, p);
-         if (rc) {
-            (void)hipFree(p.task_row); (void)hipFree(p.task_len); (void)hipFree(p.seg_off); (void)hipFree(p.task_b);
-            return rc;
-         }
-         it = s.plans.emplace(slices, p).first;
-      }
-      const Plan &p = it->second;
-      if (p.usable) {
-         const size_t need = isplib_spmm_tasks_workspace_bytes(imessage, p.n_tasks, k);
-         isplib_graph::Work *w = nullptr;
-         const int rc = ensure_work(g, need, st, &w);
-         if (rc) return rc;
-         return fusedMM_csr_tasks_hip(imessage, s.m, s.n, k, s.nnz, val, s.col, s.col32, s.rowptr, s.rowptr + 1, p.n_tasks,
-                                      p.task_row, p.task_b, p.task_len, p.seg_off, slices, p.lane_off, y, ldy, z, ldz, z_arg,
+      if ((rc = side_task_plan(g, s, slices, st, &p)) != ISPLIB_SUCCESS) return rc;
+      if (p->usable) {
+         const size_t need = isplib_spmm_tasks_workspace_bytes(imessage, p->n_tasks, k);
+         if ((rc = ensure_work(g, need, st, &w)) != ISPLIB_SUCCESS) return rc;
+         return fusedMM_csr_tasks_hip(imessage, s.m, s.n, k, s.nnz, val, s.col, s.col32, s.rowptr, s.rowptr + 1, p->n_tasks,
+                                      p->task_row, p->task_b, p->task_len, p->seg_off, slices, p->lane_off, y, ldy, z, ldz, z_arg,
                                       w->ptr, w->bytes, st);
       }
    }
@@ -682,20 +655,12 @@ extern "C" int isplib_graph_sddmm(isplib_graph *g, int mean, int64_t k, const fl
    int slices = g->forced_slices >= 0 ? g->forced_slices : isplib_suggest_slices_whole_rows(s.m, s.n, s.nnz, k);
    if (!isplib_sddmm_tasks_serve(s.n, k, ldy)) slices = 0;
    if (slices > 0) {
-      auto it = s.plans.find(slices);
-      if (it == s.plans.end()) {
-         Plan p;
-         const int rc = build_plan(g, s, slices, st, p);
-         if (rc) {
-            (void)hipFree(p.task_row); (void)hipFree(p.task_len); (void)hipFree(p.seg_off); (void)hipFree(p.task_b);
-            return rc;
-         }
-         it = s.plans.emplace(slices, p).first;
-      }
-      const Plan &p = it->second;
-      if (p.usable)
-         return isplib_sddmm_csr_tasks_hip(s.m, s.n, k, s.col, s.col32, s.rowptr, s.rowptr + 1, p.n_tasks, p.task_row, p.task_b,
-                                           p.task_len, p.lane_off, y, ldy, gm, ldg, mean, dval, st);
+      const Plan *p = nullptr;
+      const int rc = side_task_plan(g, s, slices, st, &p);
+      if (rc) return rc;
+      if (p->usable)
+         return isplib_sddmm_csr_tasks_hip(s.m, s.n, k, s.col, s.col32, s.rowptr, s.rowptr + 1, p->n_tasks, p->task_row, p->task_b,
+                                           p->task_len, p->lane_off, y, ldy, gm, ldg, mean, dval, st);
    }
    return isplib_sddmm_csr_hip(s.m, k, s.col, s.rowptr, s.rowptr + 1, y, ldy, gm, ldg, mean, dval, st);
 }

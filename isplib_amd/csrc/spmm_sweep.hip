@@ -412,31 +412,31 @@ __global__ __launch_bounds__(256, (stream_wgs_per_cu<LPR, 2 * (NVMAX + 1), WGS>(
 static unsigned long long *g_dbg = nullptr;      // set by isplib_debug_wave_times; one slab per launch, four launches
 static int g_dbg_launch = 0;
 #endif
-template <int LPR, bool HAS_VAL>
+template <int STREAMS, bool HAS_VAL>
 static int launch_stream(const SweepArgs &a_in, hipStream_t st) {
+   constexpr StreamGeom ge = stream_geom(STREAM_SUM, STREAMS);
    SweepArgs a = a_in;
 #ifdef ISPLIB_EXP_WAVE_TIMES
    a.dbg = g_dbg ? g_dbg + (size_t)(g_dbg_launch++ % 4) * (size_t)a.wave_count * 4 : nullptr;
 #endif
    const unsigned blocks = (unsigned)((a.wave_count + 3) / 4);
    if (blocks == 0) return ISPLIB_SUCCESS;
-   if constexpr (LPR == 32) hipLaunchKernelGGL((spmm_stream_kernel<32, HAS_VAL, 32, 1, 2>), dim3(blocks), dim3(256), 0, st, a);
-   else if constexpr (LPR == 16) hipLaunchKernelGGL((spmm_stream_kernel<16, HAS_VAL, ISPLIB_STREAM_NV4, ISPLIB_STREAM_NBW4, ISPLIB_STREAM_WGS4>), dim3(blocks), dim3(256), 0, st, a);
-   else hipLaunchKernelGGL((spmm_stream_kernel<8, HAS_VAL, ISPLIB_STREAM_NV8, ISPLIB_STREAM_NBW8, ISPLIB_STREAM_WGS8>), dim3(blocks), dim3(256), 0, st, a);
+   hipLaunchKernelGGL((spmm_stream_kernel<ge.lpr, HAS_VAL, ge.nvmax, ge.nbw, ge.wgs>), dim3(blocks), dim3(256), 0, st, a);
    return check_launch("spmm_stream_kernel");
+}
+
+template <int OP, int STREAMS, bool HAS_VAL, bool ARG>
+static void launch_minmax_kernel(const SweepArgs &a, unsigned blocks, hipStream_t st) {
+   constexpr StreamGeom ge = stream_geom(STREAM_MINMAX, STREAMS);
+   hipLaunchKernelGGL((spmm_stream_minmax_kernel<OP, ge.lpr, HAS_VAL, ge.nvmax, ge.nbw, ge.wgs, ARG>), dim3(blocks), dim3(256), 0, st, a);
 }
 
 template <int OP, bool HAS_VAL>
 static int launch_stream_minmax(const SweepArgs &a, hipStream_t st, int streams) {
    const unsigned blocks = (unsigned)((a.wave_count + 3) / 4);
    if (blocks == 0) return ISPLIB_SUCCESS;
-   if (a.z_arg) {
-      if (streams == 8) hipLaunchKernelGGL((spmm_stream_minmax_kernel<OP, 8, HAS_VAL, ISPLIB_STREAM_MM8_NV, ISPLIB_STREAM_MM8_NBW, ISPLIB_STREAM_MM8_WGS, true>), dim3(blocks), dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((spmm_stream_minmax_kernel<OP, 16, HAS_VAL, ISPLIB_STREAM_MM_NV, ISPLIB_STREAM_MM_NBW, ISPLIB_STREAM_MM_WGS, true>), dim3(blocks), dim3(256), 0, st, a);
-   } else {                                               // values only
-      if (streams == 8) hipLaunchKernelGGL((spmm_stream_minmax_kernel<OP, 8, HAS_VAL, ISPLIB_STREAM_MM8_NV, ISPLIB_STREAM_MM8_NBW, ISPLIB_STREAM_MM8_WGS, false>), dim3(blocks), dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((spmm_stream_minmax_kernel<OP, 16, HAS_VAL, ISPLIB_STREAM_MM_NV, ISPLIB_STREAM_MM_NBW, ISPLIB_STREAM_MM_WGS, false>), dim3(blocks), dim3(256), 0, st, a);
-   }
+   if (a.z_arg) streams == 8 ? launch_minmax_kernel<OP, 8, HAS_VAL, true>(a, blocks, st) : launch_minmax_kernel<OP, 4, HAS_VAL, true>(a, blocks, st);
+   else streams == 8 ? launch_minmax_kernel<OP, 8, HAS_VAL, false>(a, blocks, st) : launch_minmax_kernel<OP, 4, HAS_VAL, false>(a, blocks, st);      // values only
    return check_launch("spmm_stream_minmax_kernel");
 }
 
@@ -447,35 +447,13 @@ using namespace isplib;
 
 // ---- stream form: entry ---------------------------------------------------------------------------------------------
 extern "C" int isplib_spmm_stream_geometry(int streams, int *rows_per_wave, int *waves_resident) {
-   clear_error();
-   if (streams != 2 && streams != 4 && streams != 8) return fail(ISPLIB_FAIL, "isplib_spmm_stream_geometry: streams must be 2, 4 or 8");
-   if (rows_per_wave) *rows_per_wave = stream_geom(streams).nvmax;
-   if (waves_resident) *waves_resident = stream_resident_waves(streams, device_cus());
-   return ISPLIB_SUCCESS;
+   return stream_geometry("isplib_spmm_stream_geometry", STREAM_SUM, streams, rows_per_wave, waves_resident);
 }
 
 extern "C" int isplib_spmm_stream_minmax_geometry(int streams, int *rows_per_wave, int *waves_resident) {
-   clear_error();
-   if (streams != 4 && streams != 8) return fail(ISPLIB_FAIL, "isplib_spmm_stream_minmax_geometry: streams must be 4 (64-column slots) or 8 (32-column slots)");
-   if (rows_per_wave) *rows_per_wave = stream_geom(streams, true).nvmax;
-   if (waves_resident) *waves_resident = stream_resident_waves(streams, device_cus(), true);
-   return ISPLIB_SUCCESS;
+   return stream_geometry("isplib_spmm_stream_minmax_geometry", STREAM_MINMAX, streams, rows_per_wave, waves_resident);
 }
 
-static int suggest_stream_geom(int64_t m, int64_t n, int64_t nnz, int st, int rpw, int resident, double slice_bytes, double chunk_div,
-                               int *slices, int *chunk) {
-   const int64_t per_gen = (int64_t)rpw * resident;
-   const int64_t gens = (m + per_gen - 1) / per_gen;
-   if ((double)nnz / (double)gens / 8.0 < 3.0 * (double)n) return 0;
-   const double panel_bytes = 1024.0 / st;
-   int sl = (int)((double)n * panel_bytes / slice_bytes + 0.5);
-   sl = sl < 1 ? 1 : (sl > 512 ? 512 : sl);
-   int64_t ch = (int64_t)((double)nnz / ((double)gens * resident * st) / chunk_div);
-   ch = ch < 256 ? 256 : (ch > (1 << 20) ? (1 << 20) : ch);
-   if (slices) *slices = sl;
-   if (chunk) *chunk = (int)ch;
-   return 1;
-}
 extern "C" int isplib_suggest_stream_weighted(int64_t m, int64_t n, int64_t nnz, int64_t k, int weighted, int *streams, int *slices, int *chunk) {
    // When does the stream schedule pay, and with which plan?  Measured on MI355X:
    //   * slots of 8 lanes (32-column panels) up to k = 32, of 16 lanes (64-column panels) up to 64 and from 128 on, of
@@ -546,94 +524,38 @@ static int stream_run(int32_t imessage, int64_t m, int64_t n, int64_t k, int64_t
                       const isplib_stream_plan *plan, const float *y, int64_t ldy, float *z, int64_t ldz, int64_t *z_arg,
                       void *workspace, size_t workspace_bytes, const isplib_epilogue *ep, void *stream) {
    clear_error();
+   const char *entry = "fusedMM_csr_stream_hip";
    const bool mm = imessage == ISPLIB_MSG_SPMM_MAX || imessage == ISPLIB_MSG_SPMM_MIN;
-   if (imessage != ISPLIB_MSG_SPMM_SUM && imessage != ISPLIB_MSG_SPMM_MEAN && !mm)
-      return fail(ISPLIB_NO_OPT_IMPL, "fusedMM_csr_stream_hip: message outside the SpMM set");
-   if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: negative dimension");
-   if (m == 0 || k == 0) return ISPLIB_SUCCESS;
-   if (!plan) return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: plan is required");
-   if (plan->rows != m || plan->cols != n) return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: the plan was built for another shape");
-   if (n >= ISPLIB_STREAM_N_END || ldy >= ISPLIB_STREAM_LDY_END) return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: n must be < 2^24 and ldy < 2^22 (24-bit address arithmetic)");
-   if (plan->streams != 2 && plan->streams != 4 && plan->streams != 8)
-      return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: bad plan geometry (streams 2, 4 or 8)");
-   if (mm && plan->streams != 4 && plan->streams != 8) return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: max / min run on 4- or 8-stream plans (isplib_spmm_stream_minmax_geometry)");
-   if (plan->gens < 1 || plan->waves_per_gen < 1 || plan->rows_per_wave != stream_geom(plan->streams, mm).nvmax)
-      return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: bad plan geometry (rows_per_wave must be what isplib_spmm_stream_geometry / _minmax_geometry reports)");
-   if (mm && plan->n_steps > 0 && !plan->perm) return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: max / min need the plan's perm array (the winners' CSR positions)");
-   if (mm && nnz >= ISPLIB_STREAM_NNZ_END) return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: max / min need nnz < 2^31");
-   if (mm && ep) return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: the epilogue is defined for sum / mean only");
+   if (imessage != ISPLIB_MSG_SPMM_SUM && imessage != ISPLIB_MSG_SPMM_MEAN && !mm) return fail(ISPLIB_NO_OPT_IMPL, entry, "message outside the SpMM set");
+   const StreamCall c = {entry, "fusedMM_csr_hip", mm ? STREAM_MINMAX : STREAM_SUM, m, n, k, nnz, /* empty */ m == 0 || k == 0, pntrb, pntre, plan, y, ldy,
+                         /* ld_other */ ldz, /* others */ z != nullptr, /* hub_fold */ true, workspace, workspace_bytes, (mm ? 2 : 1) * isplib_spmm_stream_workspace_bytes(plan)};
+   bool done;
+   int rc = check_stream_call(c, &done);
+   if (done) return rc;
+   if (mm && plan->n_steps > 0 && !plan->perm) return fail(ISPLIB_FAIL, entry, "max / min need the plan's perm array (the winners' CSR positions)");
+   if (mm && nnz >= ISPLIB_STREAM_NNZ_END) return fail(ISPLIB_FAIL, entry, "max / min need nnz < 2^31");
    if (mm && !isplib_rows_within(n, ldy, ISPLIB_STREAM_MINMAX_BYTES_END - 1u))
-      return fail(ISPLIB_FAIL, "fusedMM_csr_stream_minmax_hip: dense operand of 2 GiB or more (use fusedMM_csr_tasks_hip)");
-   if (k < ISPLIB_K_MIN) return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: k >= 4 required (use fusedMM_csr_hip)");
-   if (ldy < k || ldz < k) return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: leading dimension smaller than k");
-   const unsigned long long yb = (unsigned long long)n * (unsigned long long)ldy * 4ull;
-   if (!isplib_dense_in_descriptor(n, ldy)) return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: dense operand larger than 3.5 GiB (use fusedMM_csr_hip)");
-   if (!pntrb || !pntre || !z || !y || !plan->wave_row || !plan->wave_part || !plan->wave_step_off ||
-       (plan->n_steps > 0 && !plan->words) || (plan->n_hub > 0 && (!plan->hub_row || !plan->hub_off)))
-      return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: null operand");
-   if (plan->n_parts > 0) {
-      if (!workspace || workspace_bytes < (mm ? 2 : 1) * isplib_spmm_stream_workspace_bytes(plan)) return fail(ISPLIB_NOT_ENOUGH_MEM, "fusedMM_csr_stream_hip: workspace too small");
-      if (((uintptr_t)workspace & 255) != 0) return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: workspace must be 256-byte aligned");
-   }
-   SweepArgs a = {};
-   a.empty_init = empty_row_init();
-   a.k = k; a.nnz = nnz; a.pntrb = pntrb; a.pntre = pntre;
-   a.y = y; a.ldy = ldy; a.ybytes = (unsigned)yb; a.z = z; a.ldz = ldz; a.z_arg = z_arg;
+      return fail(ISPLIB_FAIL, "fusedMM_csr_stream_minmax_hip", "dense operand of 2 GiB or more (use fusedMM_csr_tasks_hip)");
+   if ((rc = check_stream_workspace(c)) != ISPLIB_SUCCESS) return rc;
+   SweepArgs a = stream_args(c, z, ldz);
+   a.z_arg = z_arg;
    a.mean = imessage == ISPLIB_MSG_SPMM_MEAN ? 1 : 0;
-   a.ids = plan->perm; a.abs_ids = 1;
-   a.wave_row = plan->wave_row; a.wave_part = plan->wave_part;
-   a.words = plan->words; a.vals = plan->vals; a.wave_step_off = plan->wave_step_off; a.null_word = (unsigned)n;
-   a.hub_row = plan->hub_row; a.hub_off = plan->hub_off; a.n_hub = plan->n_hub;
-   a.part_val = (float *)workspace;
    a.part_idx = mm && workspace ? (int *)((char *)workspace + isplib_spmm_stream_workspace_bytes(plan)) : nullptr;
-   if (ep) {
-      if (ep->self && ep->ld_self < k) return fail(ISPLIB_FAIL, "fusedMM_csr_stream_hip: ld_self smaller than k");
-      a.ep_row_scale = ep->row_scale; a.ep_self = ep->self; a.ep_ld_self = ep->ld_self; a.ep_bias = ep->bias;
-      a.ep_relu = ep->relu ? 1 : 0;
-   }
+   if ((rc = set_epilogue(entry, ep, a)) != ISPLIB_SUCCESS) return rc;
    hipStream_t st = (hipStream_t)stream;
-   const int64_t pw = 256 / plan->streams;                // panel width follows the plan: a slot is 64 / streams lanes x 4 floats
-   for (int64_t c0 = 0; c0 < k; c0 += pw) {
-      SweepArgs p = a;
-      p.k = (k - c0) < pw ? (k - c0) : pw;
-      if (p.k < 4) {                              // a sliver of 1-3 columns: widen it backwards (the overlap is rewritten identically)
-         p.k = 4;
-         c0 = k - 4;
-      }
-      p.y = y + c0;
-      p.z = z + c0;
-      p.ep_self = a.ep_self ? a.ep_self + c0 : nullptr;
-      p.ep_bias = a.ep_bias ? a.ep_bias + c0 : nullptr;
-      p.z_arg = z_arg ? z_arg + c0 : nullptr;
-      p.ybytes = (unsigned)(yb - (unsigned long long)c0 * 4ull);
-      for (int gen = 0; gen < plan->gens; gen++) {          // one dispatch per generation (all in one launch: measured slower, 2.73 against 2.68 ms)
-         p.wave_base = gen * plan->waves_per_gen;
-         p.wave_count = plan->waves_per_gen;
-         int rc;
-         if (imessage == ISPLIB_MSG_SPMM_MAX) rc = plan->vals ? launch_stream_minmax<OP_MAX, true>(p, st, plan->streams) : launch_stream_minmax<OP_MAX, false>(p, st, plan->streams);
-         else if (imessage == ISPLIB_MSG_SPMM_MIN) rc = plan->vals ? launch_stream_minmax<OP_MIN, true>(p, st, plan->streams) : launch_stream_minmax<OP_MIN, false>(p, st, plan->streams);
-         else if (plan->streams == 2) rc = plan->vals ? launch_stream<32, true>(p, st) : launch_stream<32, false>(p, st);
-         else if (plan->streams == 4) rc = plan->vals ? launch_stream<16, true>(p, st) : launch_stream<16, false>(p, st);
-         else rc = plan->vals ? launch_stream<8, true>(p, st) : launch_stream<8, false>(p, st);
-         if (rc) return rc;
-      }
-      if (plan->n_hub > 0) {
-         const bool v4 = (p.k % 4) == 0 && (p.ldz % 4) == 0 && ((uintptr_t)p.z & 15) == 0 && (!p.ep_self || ((p.ep_ld_self % 4) == 0 && ((uintptr_t)p.ep_self & 15) == 0));
-         int64_t blocks = (plan->n_hub * (v4 ? p.k / 4 : p.k) + 255) / 256;
-         if (blocks > 4096) blocks = 4096;
-         if (imessage == ISPLIB_MSG_SPMM_MAX) {
-            if (v4) hipLaunchKernelGGL((sweep_hub_fold_kernel<OP_MAX, 4>), dim3((unsigned)blocks), dim3(256), 0, st, p);
-            else hipLaunchKernelGGL((sweep_hub_fold_kernel<OP_MAX, 1>), dim3((unsigned)blocks), dim3(256), 0, st, p);
-         } else if (imessage == ISPLIB_MSG_SPMM_MIN) {
-            if (v4) hipLaunchKernelGGL((sweep_hub_fold_kernel<OP_MIN, 4>), dim3((unsigned)blocks), dim3(256), 0, st, p);
-            else hipLaunchKernelGGL((sweep_hub_fold_kernel<OP_MIN, 1>), dim3((unsigned)blocks), dim3(256), 0, st, p);
-         } else if (v4) hipLaunchKernelGGL((sweep_hub_fold_kernel<OP_ADD, 4>), dim3((unsigned)blocks), dim3(256), 0, st, p);
-         else hipLaunchKernelGGL((sweep_hub_fold_kernel<OP_ADD, 1>), dim3((unsigned)blocks), dim3(256), 0, st, p);
-         const int rc = check_launch("sweep_hub_fold_kernel");
-         if (rc) return rc;
-      }
-   }
-   return ISPLIB_SUCCESS;
+   const bool has_val = plan->vals != nullptr;
+   return run_stream_panels(plan, a,
+      [&](const SweepArgs &p) {
+         if (imessage == ISPLIB_MSG_SPMM_MAX) return has_val ? launch_stream_minmax<OP_MAX, true>(p, st, plan->streams) : launch_stream_minmax<OP_MAX, false>(p, st, plan->streams);
+         if (imessage == ISPLIB_MSG_SPMM_MIN) return has_val ? launch_stream_minmax<OP_MIN, true>(p, st, plan->streams) : launch_stream_minmax<OP_MIN, false>(p, st, plan->streams);
+         if (plan->streams == 2) return has_val ? launch_stream<2, true>(p, st) : launch_stream<2, false>(p, st);
+         if (plan->streams == 4) return has_val ? launch_stream<4, true>(p, st) : launch_stream<4, false>(p, st);
+         return has_val ? launch_stream<8, true>(p, st) : launch_stream<8, false>(p, st);
+      },
+      [&](const SweepArgs &p) {
+         return imessage == ISPLIB_MSG_SPMM_MAX ? launch_hub_fold<OP_MAX, true>(p, st)
+              : imessage == ISPLIB_MSG_SPMM_MIN ? launch_hub_fold<OP_MIN, true>(p, st) : launch_hub_fold<OP_ADD, true>(p, st);
+      });
 }
 
 extern "C" int fusedMM_csr_stream_hip(int32_t imessage, int64_t m, int64_t n, int64_t k, int64_t nnz,

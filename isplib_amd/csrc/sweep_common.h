@@ -238,28 +238,44 @@ __global__ __launch_bounds__(256) void sweep_hub_fold_kernel(const SweepArgs a) 
 // one after the other (L2 hit rate 48 % at 32 slices; 67-75 % with 4; the compulsory misses only with 2).  The bytes
 // in flight that keep a CU's address pipeline busy (~256 KB) therefore come from depth, not from occupancy:
 // WGS workgroups (of 4 waves, one per SIMD) per CU, each wave with U = 64 * NBW / G gathers of 1 KiB in flight.
-template <int LPR, int NVMAX, int WGS> constexpr int stream_wgs_per_cu() {
-   return 163840 / (4 * NVMAX * LPR * 4 * 4) < WGS ? 163840 / (4 * NVMAX * LPR * 4 * 4) : WGS;
-}
+//
+// The one geometry per (plan family, slot width) that the entries launch, check plans against and report: lanes per row slot
+// (64 / streams), rows per wave, 64-word batch registers, workgroups per CU, and whether a wave keeps two LDS planes of its rows
+// plus the spare row that padding words point at (max / min: values and positions; FusedMM: x_i and the accumulator).  Sum / mean
+// measured on the Reddit shape, K = 128 in 64-column panels.  nvmax 0: the family has no kernel for that
+// slot width.  The hybrid's row is its cold stream (its LDS -- 8 waves and the hot table -- is its own: experimental.hip).
+enum StreamFamily { STREAM_SUM = 0, STREAM_MINMAX, STREAM_FUSEDMM, STREAM_HYBRID, STREAM_FAMILIES };
+struct StreamGeom { int lpr, nvmax, nbw, wgs; bool two_planes; };
+constexpr StreamGeom STREAM_GEOMS[STREAM_FAMILIES][3] = {      // [family][streams = 2, 4, 8]
+   // sum / mean (and the SDDMM over their plans)
+   {{32, 32, 1, 2, false},                  // 128-column panels: U = 32 gathers of 1 KiB per wave
+    {16, ISPLIB_STREAM_NV4, ISPLIB_STREAM_NBW4, ISPLIB_STREAM_WGS4, false},
+    {8, ISPLIB_STREAM_NV8, ISPLIB_STREAM_NBW8, ISPLIB_STREAM_WGS8, false}},
+   // max / min
+   {{32, 0, 0, 0, true},
+    {16, ISPLIB_STREAM_MM_NV, ISPLIB_STREAM_MM_NBW, ISPLIB_STREAM_MM_WGS, true},
+    {8, ISPLIB_STREAM_MM8_NV, ISPLIB_STREAM_MM8_NBW, ISPLIB_STREAM_MM8_WGS, true}},
+   // the FusedMM words
+   {{32, 16, 1, 2, true},                   // 128-column slots: 2 rows per gather, 32 gathers in flight
+    {16, 32, 2, 2, true},
+    {8, 64, 4, 2, true}},
+   // the cold stream of the hybrid
+   {{32, 0, 0, 0, false},
+    {16, ISPLIB_HYB4_NV, ISPLIB_HYB4_NBW, 1, false},
+    {8, ISPLIB_HYB8_NV, ISPLIB_HYB8_NBW, 1, false}},
+};
+constexpr bool stream_count_ok(int streams) { return streams == 2 || streams == 4 || streams == 8; }
+constexpr StreamGeom stream_geom(int family, int streams) { return STREAM_GEOMS[family][streams == 2 ? 0 : (streams == 4 ? 1 : 2)]; }
 
-// the one geometry per slot width (lanes per row slot = 64 / streams) that the entry launches: rows per wave, batch
-// registers and workgroups per CU (measured on the Reddit shape, K = 128 in 64-column panels)
-struct StreamGeom { int nvmax, nbw, wgs; };
-static StreamGeom stream_geom(int streams, bool minmax = false) {
-   if (minmax) return streams == 8 ? StreamGeom{ISPLIB_STREAM_MM8_NV, ISPLIB_STREAM_MM8_NBW, ISPLIB_STREAM_MM8_WGS}
-                                   : StreamGeom{ISPLIB_STREAM_MM_NV, ISPLIB_STREAM_MM_NBW, ISPLIB_STREAM_MM_WGS};
-   if (streams == 2) return {32, 1, 2};     // 128-column panels: U = 32 gathers of 1 KiB per wave
-   if (streams == 4) return {ISPLIB_STREAM_NV4, ISPLIB_STREAM_NBW4, ISPLIB_STREAM_WGS4};
-   return {ISPLIB_STREAM_NV8, ISPLIB_STREAM_NBW8, ISPLIB_STREAM_WGS8};   // 32-column panels
-}
-
-static int stream_resident_waves(int streams, int cus, bool minmax = false) {
-   const StreamGeom ge = stream_geom(streams, minmax);
-   const int lpr = 64 / streams;
-   const int lds = minmax ? 2 * 4 * (ge.nvmax + 1) * lpr * 4 * 4 : 4 * ge.nvmax * lpr * 4 * 4;
-   int wgs = 163840 / lds;
-   if (wgs > ge.wgs) wgs = ge.wgs;
-   return cus * wgs * 4;
+// LDS of a workgroup (4 waves x rows x one panel row of LPR lanes x 4 floats), the workgroups of a CU that its 160 KB and
+// the geometry's cap admit -- the kernels' launch bound -- and the waves of a launch that are resident together
+constexpr int CU_LDS_BYTES = 163840;
+constexpr int stream_lds_bytes(int lpr, int rows) { return 4 * rows * lpr * 4 * 4; }
+constexpr int stream_lds_rows(const StreamGeom &ge) { return ge.two_planes ? 2 * (ge.nvmax + 1) : ge.nvmax; }
+constexpr int lds_wgs_per_cu(int lds_bytes, int cap) { return CU_LDS_BYTES / lds_bytes < cap ? CU_LDS_BYTES / lds_bytes : cap; }
+template <int LPR, int ROWS, int WGS> constexpr int stream_wgs_per_cu() { return lds_wgs_per_cu(stream_lds_bytes(LPR, ROWS), WGS); }
+constexpr int stream_resident_waves(const StreamGeom &ge, int cus) {
+   return cus * lds_wgs_per_cu(stream_lds_bytes(ge.lpr, stream_lds_rows(ge)), ge.wgs) * 4;
 }
 
 static inline int device_cus() {
@@ -271,11 +287,169 @@ static inline int device_cus() {
    return cus;
 }
 
+// isplib_spmm_stream_geometry, isplib_spmm_stream_minmax_geometry, isplib_fusedmm_stream_geometry
+static inline int stream_geometry(const char *entry, int family, int streams, int *rows_per_wave, int *waves_resident) {
+   clear_error();
+   if (!stream_count_ok(streams) || !stream_geom(family, streams).nvmax)
+      return fail(ISPLIB_FAIL, entry, stream_geom(family, 2).nvmax ? "streams must be 2, 4 or 8" : "streams must be 4 (64-column slots) or 8 (32-column slots)");
+   const StreamGeom ge = stream_geom(family, streams);
+   if (rows_per_wave) *rows_per_wave = ge.nvmax;
+   if (waves_resident) *waves_resident = stream_resident_waves(ge, device_cus());
+   return ISPLIB_SUCCESS;
+}
+
 // The isplib_suggest_*stream* rules offer a shape the stream schedule only when (a) its entry and plan builder would serve
 // it -- isplib_stream_serves (include/isplib_hip.h) with ldy = k, a contiguous dense operand; callers with a padded leading
 // dimension ask it again with theirs -- so that a shape outside the domain runs on the task list or the plain kernel as
 // before the stream schedule existed instead of being offered and then refused with an error, and (b) the graph has work
 // for the whole chip: at least this many stored entries (a measured rule, not an address domain).
 constexpr int64_t STREAM_MIN_NNZ = 4 * 1048576;
+
+// (c) every generation of waves sweeps the whole dense operand once per XCD, so the rows a generation holds must reuse each
+// row of it often: edges per generation and XCD >= 3 x rows of y.  Then: slices of `slice_bytes` of a panel of y, and rows
+// longer than 1 / chunk_div of a stream's share of the edges dealt to several virtual rows.
+static inline int suggest_stream_geom(int64_t m, int64_t n, int64_t nnz, int st, int rpw, int resident, double slice_bytes, double chunk_div,
+                                      int *slices, int *chunk) {
+   const int64_t per_gen = (int64_t)rpw * resident;
+   const int64_t gens = (m + per_gen - 1) / per_gen;
+   if ((double)nnz / (double)gens / 8.0 < 3.0 * (double)n) return 0;
+   const double panel_bytes = 1024.0 / st;
+   int sl = (int)((double)n * panel_bytes / slice_bytes + 0.5);
+   sl = sl < 1 ? 1 : (sl > 512 ? 512 : sl);
+   int64_t ch = (int64_t)((double)nnz / ((double)gens * resident * st) / chunk_div);
+   ch = ch < 256 ? 256 : (ch > (1 << 20) ? (1 << 20) : ch);
+   if (slices) *slices = sl;
+   if (chunk) *chunk = (int)ch;
+   return 1;
+}
+
+// ---- host side of an entry on the stream front end: one check, one fill, one driver ------------------------------------
+// What an entry was called with, as far as all of them are alike.
+struct StreamCall {
+   const char *entry;                     // its name: the prefix of every message
+   const char *instead;                   // the entry that serves what this one refuses for k or size
+   int family;                            // whose plans it runs
+   int64_t m, n, k, nnz;
+   bool empty;                            // nothing to compute: success before the plan is looked at
+   const int64_t *pntrb, *pntre;
+   const isplib_stream_plan *plan;
+   const float *y;
+   int64_t ldy;
+   int64_t ld_other;                      // the entry's other leading dimension (z; the SDDMM's g)
+   bool others;                           // the entry's other operands are all there
+   bool hub_fold;                         // hub rows leave partial rows in the workspace (not the SDDMM: it writes per edge)
+   void *workspace;
+   size_t workspace_bytes, workspace_need;
+};
+
+// Every refusal the entries share that is decided before anything is launched.  *done: nothing (more) to do, the entry returns
+// the status.  What is an entry's own (its message words before this; limits of its kernel after it) stays with the entry,
+// and the workspace comes last: a plan that is refused is refused whatever the workspace.
+static inline int check_stream_call(const StreamCall &c, bool *done) {
+   const isplib_stream_plan *plan = c.plan;
+   auto use_instead = [&](const char *what) {          // "<what> (use <the entry that serves it>)"
+      char msg[256];
+      snprintf(msg, sizeof msg, "%s (use %s)", what, c.instead);
+      return fail(ISPLIB_FAIL, c.entry, msg);
+   };
+   *done = true;
+   if (c.m < 0 || c.n < 0 || c.k < 0 || c.nnz < 0) return fail(ISPLIB_FAIL, c.entry, "negative dimension");
+   if (c.empty) return ISPLIB_SUCCESS;
+   if (!plan) return fail(ISPLIB_FAIL, c.entry, "plan is required");
+   if (plan->rows != c.m || plan->cols != c.n) return fail(ISPLIB_FAIL, c.entry, "the plan was built for another shape");
+   if (c.n >= ISPLIB_STREAM_N_END || c.ldy >= ISPLIB_STREAM_LDY_END) return fail(ISPLIB_FAIL, c.entry, "n must be < 2^24 and ldy < 2^22 (24-bit address arithmetic)");
+   if (!stream_count_ok(plan->streams)) return fail(ISPLIB_FAIL, c.entry, "bad plan geometry (streams 2, 4 or 8)");
+   if (!stream_geom(c.family, plan->streams).nvmax) return fail(ISPLIB_FAIL, c.entry, "bad plan geometry (this entry runs on 4- or 8-stream plans)");
+   if (plan->gens < 1 || plan->waves_per_gen < 1 || plan->rows_per_wave != stream_geom(c.family, plan->streams).nvmax)
+      return fail(ISPLIB_FAIL, c.entry, "bad plan geometry (rows_per_wave must be what the geometry entry of this plan family reports)");
+   if (c.k < ISPLIB_K_MIN) return use_instead("k >= 4 required");
+   if (c.ldy < c.k || c.ld_other < c.k) return fail(ISPLIB_FAIL, c.entry, "leading dimension smaller than k");
+   if (!isplib_dense_in_descriptor(c.n, c.ldy)) return use_instead("dense operand larger than 3.5 GiB");
+   if (!c.pntrb || !c.pntre || !c.y || !c.others || !plan->wave_row || !plan->wave_step_off || (plan->n_steps > 0 && !plan->words) ||
+       (c.hub_fold && (!plan->wave_part || (plan->n_hub > 0 && (!plan->hub_row || !plan->hub_off)))))
+      return fail(ISPLIB_FAIL, c.entry, "null operand");
+   *done = false;
+   return ISPLIB_SUCCESS;
+}
+
+static inline int check_stream_workspace(const StreamCall &c) {
+   if (c.plan->n_parts <= 0) return ISPLIB_SUCCESS;
+   if (!c.workspace || c.workspace_bytes < c.workspace_need) return fail(ISPLIB_NOT_ENOUGH_MEM, c.entry, "workspace too small");
+   if (((uintptr_t)c.workspace & 255) != 0) return fail(ISPLIB_FAIL, c.entry, "workspace must be 256-byte aligned");
+   return ISPLIB_SUCCESS;
+}
+
+// the kernel arguments every stream kernel reads from the plan and the dense operands (the entry adds what is its own)
+static inline SweepArgs stream_args(const StreamCall &c, float *z, int64_t ldz) {
+   const isplib_stream_plan *plan = c.plan;
+   SweepArgs a = {};
+   a.empty_init = empty_row_init();
+   a.k = c.k; a.nnz = c.nnz; a.pntrb = c.pntrb; a.pntre = c.pntre;
+   a.y = c.y; a.ldy = c.ldy; a.ybytes = (unsigned)((unsigned long long)c.n * (unsigned long long)c.ldy * 4ull); a.z = z; a.ldz = ldz;
+   a.ids = plan->perm; a.abs_ids = 1;
+   a.wave_row = plan->wave_row; a.wave_part = plan->wave_part;
+   a.words = plan->words; a.vals = plan->vals; a.wave_step_off = plan->wave_step_off; a.null_word = (unsigned)c.n;
+   a.hub_row = plan->hub_row; a.hub_off = plan->hub_off; a.n_hub = plan->n_hub;
+   a.part_val = (float *)c.workspace;
+   return a;
+}
+
+static inline int set_epilogue(const char *entry, const isplib_epilogue *ep, SweepArgs &a) {
+   if (!ep) return ISPLIB_SUCCESS;
+   if (ep->self && ep->ld_self < a.k) return fail(ISPLIB_FAIL, entry, "ld_self smaller than k");
+   a.ep_row_scale = ep->row_scale; a.ep_self = ep->self; a.ep_ld_self = ep->ld_self; a.ep_bias = ep->bias;
+   a.ep_relu = ep->relu ? 1 : 0;
+   return ISPLIB_SUCCESS;
+}
+
+// the fold of the hub rows' partial rows of one panel.  RAGGED: the entry admits panels that are not whole, 16-byte aligned
+// float4 columns (they are folded one column per thread); the others fold four columns per thread, always.
+template <int OP, bool RAGGED>
+static inline int launch_hub_fold(const SweepArgs &p, hipStream_t st) {
+   if (p.n_hub <= 0) return ISPLIB_SUCCESS;
+   const bool v4 = !RAGGED || ((p.k % 4) == 0 && (p.ldz % 4) == 0 && ((uintptr_t)p.z & 15) == 0 &&
+                               (!p.ep_self || ((p.ep_ld_self % 4) == 0 && ((uintptr_t)p.ep_self & 15) == 0)));
+   int64_t blocks = (p.n_hub * (v4 ? p.k / 4 : p.k) + 255) / 256;
+   if (blocks > 4096) blocks = 4096;
+   if (v4) hipLaunchKernelGGL((sweep_hub_fold_kernel<OP, 4>), dim3((unsigned)blocks), dim3(256), 0, st, p);
+   else if constexpr (RAGGED) hipLaunchKernelGGL((sweep_hub_fold_kernel<OP, 1>), dim3((unsigned)blocks), dim3(256), 0, st, p);
+   return check_launch("sweep_hub_fold_kernel");
+}
+
+// one dispatch per generation of resident waves (all in one launch: measured slower, 2.73 against 2.68 ms)
+template <class Launch>
+static inline int run_generations(int gens, int waves_per_gen, SweepArgs &p, Launch launch) {
+   for (int gen = 0; gen < gens; gen++) {
+      p.wave_base = gen * waves_per_gen;
+      p.wave_count = waves_per_gen;
+      const int rc = launch(p);
+      if (rc) return rc;
+   }
+   return ISPLIB_SUCCESS;
+}
+
+// column panels of the plan's slot width (a slot is 64 / streams lanes x 4 floats): every generation, then the hub fold, per panel
+template <class Launch, class Fold>
+static inline int run_stream_panels(const isplib_stream_plan *plan, const SweepArgs &a, Launch launch, Fold fold) {
+   const int64_t k = a.k, pw = 256 / plan->streams;
+   for (int64_t c0 = 0; c0 < k; c0 += pw) {
+      SweepArgs p = a;
+      p.k = (k - c0) < pw ? (k - c0) : pw;
+      if (p.k < 4) {                              // a sliver of 1-3 columns: widen it backwards (the overlap is rewritten identically)
+         p.k = 4;
+         c0 = k - 4;
+      }
+      p.y = a.y + c0;
+      p.z = a.z + c0;
+      p.ep_self = a.ep_self ? a.ep_self + c0 : nullptr;
+      p.ep_bias = a.ep_bias ? a.ep_bias + c0 : nullptr;
+      p.z_arg = a.z_arg ? a.z_arg + c0 : nullptr;
+      p.ybytes = a.ybytes - (unsigned)c0 * 4u;
+      int rc = run_generations(plan->gens, plan->waves_per_gen, p, launch);
+      if (!rc) rc = fold(p);
+      if (rc) return rc;
+   }
+   return ISPLIB_SUCCESS;
+}
 
 }  // namespace isplib

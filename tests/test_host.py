@@ -364,6 +364,160 @@ def test_task_entry_argument_validation_without_gpu():
     assert "slice range" in cabi.last_error()
 
 
+def test_stream_entries_argument_validation_without_gpu():
+    """The five entries on the stream front end (sum / mean, max / min, the FusedMM words, and in the experimental library the
+    stream SDDMM and the LDS hybrid): every rejection that is decided before a HIP call, one violation per call, over a plan
+    whose pointers are never dereferenced.  No call here may reach a launch."""
+    import ctypes
+    from isplib_amd import cabi
+    L, X = cabi.lib(), cabi.exp_lib()
+    one, al16 = ctypes.c_void_p(8), ctypes.c_void_p(16)      # never dereferenced: validation fails first
+
+    def geometry(fn, streams):
+        rpw, res = ctypes.c_int(0), ctypes.c_int(0)
+        assert fn(streams, ctypes.byref(rpw), ctypes.byref(res)) == cabi.SUCCESS
+        return rpw.value
+    rpw_sum, rpw_mm, rpw_gen = (geometry(f, 4) for f in (L.isplib_spmm_stream_geometry, L.isplib_spmm_stream_minmax_geometry,
+                                                         L.isplib_fusedmm_stream_geometry))
+    hyb = [ctypes.c_int(0) for _ in range(4)]
+    assert X.isplib_spmm_hybrid_geometry(4, *[ctypes.byref(v) for v in hyb]) == cabi.SUCCESS
+    rpw_hyb, table_rows, hot_cap = hyb[0].value, hyb[2].value, hyb[3].value
+    assert (rpw_sum, rpw_mm, rpw_gen) == (64, 32, 32)
+
+    def plan(rpw, **over):
+        p = cabi.StreamPlanStruct(rows=40, cols=40, slices=2, gens=1, waves_per_gen=8, rows_per_wave=rpw, streams=4, chunk=64,
+                                  n_steps=1, n_parts=0, n_hub=0, words=8, vals=8, wave_step_off=8, wave_row=8, wave_part=8,
+                                  hub_row=8, hub_off=8, perm=8)
+        for name, v in over.items():
+            setattr(p, name, v)
+        return p
+
+    udef_word = cabi.PATTERNS["sigmoid_embedding"][0]
+
+    # every entry as call(plan fields to override, m, n, k, nnz, ldy, y, msg, sop, ws, ws_bytes)
+    def sum_entry(pl, m, n, k, nnz, ldy, y, msg, sop, ws, wsb):
+        return L.fusedMM_csr_stream_hip(cabi.MSG_SPMM_SUM if msg is None else msg, m, n, k, nnz, one, one, ctypes.byref(plan(rpw_sum, **pl)),
+                                        y, ldy, one, k, ws, wsb, None, None)
+
+    def mm_entry(pl, m, n, k, nnz, ldy, y, msg, sop, ws, wsb):
+        return L.fusedMM_csr_stream_minmax_hip(cabi.MSG_SPMM_MAX if msg is None else msg, m, n, k, nnz, one, one,
+                                               ctypes.byref(plan(rpw_mm, **pl)), y, ldy, one, k, one, ws, wsb, None)
+
+    def udef_entry(pl, m, n, k, nnz, ldy, y, msg, sop, ws, wsb):
+        return L.fusedMM_csr_udef_stream_hip(udef_word if msg is None else msg, m, n, k, nnz, one, one, ctypes.byref(plan(rpw_gen, **pl)),
+                                             al16, 8, y, ldy, al16, 8, cabi.SOP_UDEF["sigmoid"] if sop is None else sop, 0.0, ws, wsb, None)
+
+    def sddmm_entry(pl, m, n, k, nnz, ldy, y, msg, sop, ws, wsb):
+        return X.isplib_sddmm_stream_hip(m, n, k, nnz, one, one, ctypes.byref(plan(rpw_sum, **pl)), y, ldy, one, 8, 0, one, None)
+
+    def hybrid_entry(pl, m, n, k, nnz, ldy, y, msg, sop, ws, wsb):
+        hp = cabi.HybridPlanStruct(cold=plan(rpw_hyb, **dict({"vals": None}, **pl)), table_rows=table_rows, hot_cap=hot_cap,
+                                   n_hot_steps=1, hot_rows=8, hot_words=8, hot_step_off=8, hot_perm=8)
+        return X.fusedMM_csr_hybrid_hip(cabi.MSG_SPMM_SUM if msg is None else msg, m, n, k, nnz, one, one, ctypes.byref(hp), y, ldy,
+                                        one, k, ws, wsb, None, None)
+
+    # (the two SpMM entries share one driver, which reports under the sum entry's name)
+    entries = {
+        "sum": (sum_entry, ("fusedMM_csr_stream_hip:",), rpw_mm, cabi.MSG_SPMM_MAX),
+        "minmax": (mm_entry, ("fusedMM_csr_stream_minmax_hip:", "fusedMM_csr_stream_hip:"), rpw_sum, cabi.MSG_SPMM_SUM),
+        "udef": (udef_entry, ("fusedMM_csr_udef_stream_hip:",), rpw_sum, cabi.MSG_SPMM_SUM),
+        "sddmm": (sddmm_entry, ("isplib_sddmm_stream_hip:",), rpw_mm, None),
+        "hybrid": (hybrid_entry, ("fusedMM_csr_hybrid_hip:",), rpw_mm, cabi.MSG_SPMM_MAX),
+    }
+    for name, (entry, prefixes, other_rpw, wrong_word) in entries.items():
+        def refused(status, reason=None, pl=None, m=40, n=40, k=8, nnz=100, ldy=8, y=one, msg=None, sop=None, ws=None, wsb=0):
+            got = entry(pl or {}, m, n, k, nnz, ldy, y, msg, sop, ws, wsb)
+            assert got == status, (name, reason, got, cabi.last_error())
+            assert cabi.last_error().startswith(prefixes), (name, cabi.last_error())
+            if reason:
+                assert reason in cabi.last_error(), (name, reason, cabi.last_error())
+
+        if wrong_word is not None:
+            refused(cabi.NO_OPT_IMPL, msg=wrong_word)
+        if name == "udef":
+            refused(cabi.UNDEFINED_USER_FUNCTION, "SOP_UDEF", sop=cabi.SOP_UDEF["none"])
+            refused(cabi.UNDEFINED_USER_FUNCTION, "SOP_UDEF", sop=7)
+        refused(cabi.FAIL, "another shape", m=41)
+        refused(cabi.FAIL, "another shape", n=41)
+        refused(cabi.FAIL, "24-bit address arithmetic", pl={"cols": 1 << 24}, n=1 << 24)
+        refused(cabi.FAIL, "24-bit address arithmetic", ldy=1 << 22)
+        refused(cabi.FAIL, "streams", pl={"streams": 3})
+        refused(cabi.FAIL, "bad plan geometry", pl={"rows_per_wave": other_rpw})
+        refused(cabi.FAIL, "bad plan geometry", pl={"gens": 0})
+        refused(cabi.FAIL, "bad plan geometry", pl={"waves_per_gen": 0})
+        # (the FusedMM entry has k and leading-dimension rules of its own, which these two calls break as well)
+        refused(cabi.FAIL, None if name == "udef" else "k >= 4", k=3)
+        refused(cabi.FAIL, None if name == "udef" else "leading dimension smaller than k", ldy=4)
+        if name == "minmax":
+            refused(cabi.FAIL, None, pl={"cols": 1 << 20}, n=1 << 20, ldy=1024)              # past 3.5 GiB, and past 2 GiB
+            refused(cabi.FAIL, "2 GiB", pl={"cols": 1 << 20}, n=1 << 20, ldy=640)             # 2.5 GiB: the max / min limit alone
+            refused(cabi.FAIL, "4- or 8-stream", pl={"streams": 2})
+        else:
+            refused(cabi.FAIL, "3.5 GiB", pl={"cols": 1 << 20}, n=1 << 20, ldy=1024)
+        if name in ("minmax", "sddmm"):
+            refused(cabi.FAIL, "perm", pl={"perm": None})
+        refused(cabi.FAIL, "null operand", y=None)
+        refused(cabi.FAIL, "null operand", pl={"wave_row": None})
+        refused(cabi.FAIL, "null operand", pl={"words": None})
+        if name != "sddmm":                                                                   # the SDDMM writes no partial rows
+            refused(cabi.FAIL, "null operand", pl={"n_hub": 1, "hub_off": None})
+            refused(cabi.NOT_ENOUGH_MEM, "workspace too small", pl={"n_parts": 5})
+            refused(cabi.NOT_ENOUGH_MEM, "workspace too small", pl={"n_parts": 5}, ws=ctypes.c_void_p(256), wsb=16)
+            refused(cabi.FAIL, "256-byte aligned", pl={"n_parts": 5}, ws=ctypes.c_void_p(264), wsb=1 << 20)
+            # a refusal with another status keeps its place: the message word before the plan, the plan before the workspace
+            if wrong_word is not None:
+                refused(cabi.NO_OPT_IMPL, msg=wrong_word, pl={"streams": 3, "n_parts": 5})
+            refused(cabi.FAIL, "streams", pl={"streams": 3, "n_parts": 5})
+        if name == "udef":
+            refused(cabi.UNDEFINED_USER_FUNCTION, "SOP_UDEF", sop=cabi.SOP_UDEF["none"], pl={"streams": 3})
+        assert entry({}, 0, 40, 8, 100, 8, one, None, None, None, 0) == cabi.SUCCESS, name     # m = 0: nothing to do
+        assert cabi.last_error() == ""
+        if name == "sddmm":
+            assert entry({}, 40, 40, 8, 0, 8, one, None, None, None, 0) == cabi.SUCCESS
+        else:
+            assert entry({}, 40, 40, 0, 100, 8, one, None, None, None, 0) == cabi.SUCCESS      # k = 0
+
+
+def test_stream_geometry_of_every_family():
+    """Rows per wave and resident waves of the three plan families at every slot width, the stream counts each geometry entry
+    refuses, and the FusedMM suggest rule on the Reddit shape (recorded answers: the rule is arithmetic on the geometry)."""
+    import ctypes
+    from isplib_amd import cabi
+    L = cabi.lib()
+
+    def geometry(fn, streams):
+        rpw, res = ctypes.c_int(-1), ctypes.c_int(-1)
+        rc = fn(streams, ctypes.byref(rpw), ctypes.byref(res))
+        return rc, rpw.value, res.value
+    # without a device the library assumes the MI355X's 256 CUs
+    cus = torch.cuda.get_device_properties(0).multi_processor_count if torch.cuda.is_available() else 256
+    want = {
+        "isplib_spmm_stream_geometry": {2: 32, 4: 64, 8: 128},
+        "isplib_spmm_stream_minmax_geometry": {4: 32, 8: 64},
+        "isplib_fusedmm_stream_geometry": {2: 16, 4: 32, 8: 64},
+    }
+    for name, rows in want.items():
+        fn = getattr(L, name)
+        for streams in (0, 1, 2, 3, 4, 5, 6, 8, 16):
+            rc, rpw, res = geometry(fn, streams)
+            if streams in rows:
+                assert (rc, rpw) == (cabi.SUCCESS, rows[streams]), (name, streams)
+                assert res == 8 * cus, (name, streams, res)          # two workgroups of four waves per CU
+            else:
+                assert rc == cabi.FAIL and cabi.last_error().startswith(name + ": streams must be"), (name, streams)
+                assert (rpw, res) == (-1, -1), "a refusal writes nothing"
+        assert fn(4, None, None) == cabi.SUCCESS                      # both outputs are optional
+    if cus == 256:
+        word = cabi.PATTERNS["sigmoid_embedding"][0]
+        recorded = {32: (8, 8, 1457), 64: (4, 16, 1457), 128: (2, 46, 1457)}      # (streams, slices, chunk)
+        for k, triple in recorded.items():
+            st, sl, ch = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+            assert L.isplib_suggest_fusedmm_stream(word, 232965, 232965, 114615892, k, ctypes.byref(st), ctypes.byref(sl), ctypes.byref(ch)) == 1
+            assert (st.value, sl.value, ch.value) == triple, (k, st.value, sl.value, ch.value)
+        assert L.isplib_suggest_fusedmm_stream(word, 232965, 232965, 114615892, 256, None, None, None) == 0      # wider than a slot
+        assert L.isplib_suggest_fusedmm_stream(cabi.MSG_SPMM_SUM, 232965, 232965, 114615892, 64, None, None, None) == 0
+
+
 # ---- MatrixMarket I/O (the reference tuner's graph format, README.md:147-168) -------------------
 
 def test_mtx_round_trip_and_readme_case(tmp_path):
