@@ -158,7 +158,7 @@ __global__ __launch_bounds__(WAVES * 64, NCH == 1 ? 8 : 1) void sddmm_task_kerne
    const unsigned xcd = blockIdx.x & 7u, within = blockIdx.x >> 3;
    const int64_t t = a.lane_off[xcd] + (int64_t)within * WAVES + wave;
    if (t >= a.lane_off[xcd + 1]) return;
-   __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.y), 0, (int)a.ybytes, 0x00020000);
+   __amdgpu_buffer_rsrc_t rsrc = dense_rsrc(a);
    const int row = a.task_row[t];
    const int64_t b = a.task_b[t], e = b + a.task_len[t];
    const int64_t deg = a.pntre[row] - a.pntrb[row];

@@ -36,7 +36,7 @@ __global__ __launch_bounds__(256, (sweep_wgs_per_cu<OP, LPR, NVMAX>())) void spm
       *reinterpret_cast<float4 *>(my_val + (i * 64 + lane) * 4) = make_float4(identity<OP>(), identity<OP>(), identity<OP>(), identity<OP>());
       if (OP != OP_ADD) *reinterpret_cast<int4 *>(my_idx + (i * 64 + lane) * 4) = make_int4(INT_MAX, INT_MAX, INT_MAX, INT_MAX);
    }
-   __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.y), 0, (int)a.ybytes, 0x00020000);
+   __amdgpu_buffer_rsrc_t rsrc = dense_rsrc(a);
    int ccol[1];
    bool cok[1];
    ccol[0] = lc * VEC;
@@ -143,38 +143,33 @@ __global__ __launch_bounds__(256, (sweep_wgs_per_cu<OP, LPR, NVMAX>())) void spm
 // Every edge is owned by one (wave, slot, step): plain stores, no atomics, bitwise reproducible.
 template <int LPR, int NVMAX, int NBW, int WGS, bool ACCUM>
 __global__ __launch_bounds__(256, (stream_wgs_per_cu<LPR, NVMAX, WGS>())) void sddmm_stream_kernel(const SweepArgs a) {
-   constexpr int WAVES = 4, G = 64 / LPR, PANEL = LPR * 4, U = 64 * NBW / G;
-   constexpr int PER = NVMAX / G, WAVE_FLOATS = NVMAX * PANEL;
+   using Wave = StreamWave<LPR, NVMAX, NBW>;
+   constexpr int WAVES = Wave::WAVES, G = Wave::G, PANEL = Wave::PANEL, U = Wave::U, PER = Wave::PER;
+   constexpr int WAVE_FLOATS = NVMAX * PANEL;
    constexpr int Q = LPR / 4;                            // lanes that end up with the sum of one of four steps
    static_assert(U % 4 == 0 && (4 * G) <= 64 && 64 % (4 * G) == 0, "four steps' words lie in one batch register");
    __shared__ __attribute__((aligned(16))) float s_all[WAVES * WAVE_FLOATS];
-   const int lane = threadIdx.x & 63;
-   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-   const int g = lane / LPR, lc = lane % LPR;
-   const int wl = (int)blockIdx.x * WAVES + wave;
-   if (wl >= a.wave_count) return;                       // no barrier anywhere below
-   const int64_t w = (int64_t)a.wave_base + wl;
-   float *my = s_all + wave * WAVE_FLOATS;
-   const bool cok = lc * 4 < a.k;
-   int ccol = lc * 4, vfirst = 0;
-   if (cok && ccol + 4 > (int)a.k) { vfirst = ccol + 4 - (int)a.k; ccol = (int)a.k - 4; }
-   const unsigned cbyte = (unsigned)ccol * 4u, poison = cok ? 0u : BUF_OOB;
-   float *lane_base = my + lc * 4;
+   Wave sw;
+   if (!stream_wave_id(a, sw)) return;                   // no barrier anywhere below
+   const int lane = sw.lane;
+   float *my = s_all + sw.wave * WAVE_FLOATS;
+   stream_columns<true>(a, sw);
+   float *lane_base = my + sw.lc * 4;
    // the wave's rows of g into LDS: slot q's LPR lanes hold one row of the panel; the components a shifted last vector
    // shares with its neighbour count once (zeroed here), unused local rows read as zero
 #pragma unroll 1
    for (int jj = 0; jj < PER; jj++) {
-      const int lrow = g * PER + jj;
-      const int row = a.wave_row[(size_t)w * NVMAX + lrow];
+      const int lrow = sw.g * PER + jj;
+      const int row = a.wave_row[(size_t)sw.w * NVMAX + lrow];
       float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      if (row >= 0 && cok) {
-         const float *gr = a.g + (size_t)row * (size_t)a.ldg + ccol;
+      if (row >= 0 && sw.cok) {
+         const float *gr = a.g + (size_t)row * (size_t)a.ldg + sw.ccol;
          float sc = 1.0f;
          if (a.mean) {
             const int64_t deg = a.pntre[row] - a.pntrb[row];
             sc = 1.0f / (float)(deg > 1 ? deg : 1);
          }
-         const int skip = vfirst > a.ep_relu - ccol ? vfirst : a.ep_relu - ccol;     // (ep_relu: columns an earlier panel covered)
+         const int skip = sw.vfirst > a.ep_relu - sw.ccol ? sw.vfirst : a.ep_relu - sw.ccol;     // (ep_relu: columns an earlier panel covered)
          v.x = skip > 0 ? 0.0f : gr[0] * sc;
          v.y = skip > 1 ? 0.0f : gr[1] * sc;
          v.z = skip > 2 ? 0.0f : gr[2] * sc;
@@ -182,53 +177,30 @@ __global__ __launch_bounds__(256, (stream_wgs_per_cu<LPR, NVMAX, WGS>())) void s
       }
       *reinterpret_cast<float4 *>(lane_base + lrow * PANEL) = v;
    }
-   __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.y), 0, (int)a.ybytes, 0x00020000);
-   const int64_t s0 = a.wave_step_off[w], s1 = a.wave_step_off[w + 1];
-   const int64_t nwords = (s1 - s0) * G;
-   const int32_t *wp = a.words + s0 * G;
-   const int32_t *pp = a.ids + s0 * G;
-   const unsigned ldyb = (unsigned)a.ldy * 4u;
-   const unsigned pad_word = ((unsigned)((lane % G) * PER) << 24) | a.null_word;
-   auto load_words = [&](int64_t first, unsigned (&word)[NBW]) {
-#pragma unroll
-      for (int q = 0; q < NBW; q++) {
-         const int64_t i = first + q * 64 + lane;
-         word[q] = i < nwords ? (unsigned)wp[i] : pad_word;
-      }
-   };
-   auto load_perm = [&](int64_t first, int (&pos)[NBW]) {
-#pragma unroll
-      for (int q = 0; q < NBW; q++) {
-         const int64_t i = first + q * 64 + lane;
-         pos[q] = i < nwords ? pp[i] : -1;
-      }
-   };
+   __amdgpu_buffer_rsrc_t rsrc = dense_rsrc(a);
+   stream_bounds(a, sw);
+   const int32_t *pp = a.ids + sw.s0 * G;
+   const unsigned pad_word = stream_pad_own_row(a, sw);
    unsigned w1[NBW], w2[NBW];
    int pc[NBW], pn[NBW];                                  // CSR positions of the batch being consumed and of the next
    float old[NBW], res[NBW];
    v4i_t t[U];
    unsigned la[U];
-   auto issue = [&](int u, const unsigned (&word_l)[NBW]) {
-      const unsigned word = (unsigned)__shfl((int)word_l[(u * G) / 64], (u * G) % 64 + g);
-      const unsigned o = (__umul24(word & 0xFFFFFFu, ldyb) + cbyte) | poison;
-      la[u] = (word >> 24) * (unsigned)PANEL;
-      t[u] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)o, 0, 0);
-   };
-   load_words(0, w1);
-   load_perm(0, pc);
+   stream_load_batch(sw, sw.wp, 0, pad_word, w1);
+   stream_load_batch(sw, pp, 0, -1, pc);
 #pragma unroll
-   for (int u = 0; u < U; u++) issue(u, w1);
-   load_words(64 * NBW, w1);
-   load_perm(64 * NBW, pn);
-   load_words(128 * NBW, w2);
+   for (int u = 0; u < U; u++) stream_issue<0>(sw, rsrc, w1, u, la[u], t[u]);
+   stream_load_batch(sw, sw.wp, 64 * NBW, pad_word, w1);
+   stream_load_batch(sw, pp, 64 * NBW, -1, pn);
+   stream_load_batch(sw, sw.wp, 128 * NBW, pad_word, w2);
    // the lane of the slot's group that owns step (word lane / G) % 4 of this lane's word, after the butterfly
    const int src_lane = (lane % G) * LPR + ((lane / G) % 4) * Q;
-   const int64_t nb = (nwords + 64 * NBW - 1) / (64 * NBW);
+   const int64_t nb = (sw.nwords + 64 * NBW - 1) / (64 * NBW);
    for (int64_t b = 0; b < nb; b++) {
       if (ACCUM) {
 #if defined(ISPLIB_EXP_SDDMM_STREAM_ORDER)
 #pragma unroll
-         for (int q = 0; q < NBW; q++) old[q] = a.dval[(s0 * G + b * 64 * NBW + q * 64 + lane) % a.nnz];
+         for (int q = 0; q < NBW; q++) old[q] = a.dval[(sw.s0 * G + b * 64 * NBW + q * 64 + lane) % a.nnz];
 #elif defined(ISPLIB_EXP_SDDMM_NOSTORE)
          old[0] = 0.0f;
 #else
@@ -250,10 +222,10 @@ __global__ __launch_bounds__(256, (stream_wgs_per_cu<LPR, NVMAX, WGS>())) void s
          const float4 gv = gq[u & 3];
          d[u & 3] = fmaf(__int_as_float(t[u][0]), gv.x, fmaf(__int_as_float(t[u][1]), gv.y,
                     fmaf(__int_as_float(t[u][2]), gv.z, __int_as_float(t[u][3]) * gv.w)));
-         issue(u, w1);
+         stream_issue<0>(sw, rsrc, w1, u, la[u], t[u]);
          if ((u & 3) == 3) {
             int mine;
-            const float sum = reduce_transposed<4, LPR>(d, lc, mine);
+            const float sum = reduce_transposed<4, LPR>(d, sw.lc, mine);
             const float mv = __shfl(sum, src_lane);
             constexpr int WPG = 4 * G;                   // words of four steps
             const int first = ((u - 3) * G) % 64;
@@ -262,9 +234,9 @@ __global__ __launch_bounds__(256, (stream_wgs_per_cu<LPR, NVMAX, WGS>())) void s
       }
 #if defined(ISPLIB_EXP_SDDMM_STREAM_ORDER)                  // timing experiment: results stored in stream order (coalesced), no perm
 #pragma unroll
-      for (int q = 0; q < NBW; q++) a.dval[(s0 * G + b * 64 * NBW + q * 64 + lane) % a.nnz] = res[q] + (ACCUM ? old[q] : 0.0f);
+      for (int q = 0; q < NBW; q++) a.dval[(sw.s0 * G + b * 64 * NBW + q * 64 + lane) % a.nnz] = res[q] + (ACCUM ? old[q] : 0.0f);
 #elif defined(ISPLIB_EXP_SDDMM_NOSTORE)                    // timing experiment: one store per wave instead of one per word
-      if (b + 1 == nb) a.dval[w] = res[0] + res[NBW - 1] + (ACCUM ? old[0] : 0.0f);
+      if (b + 1 == nb) a.dval[sw.w] = res[0] + res[NBW - 1] + (ACCUM ? old[0] : 0.0f);
 #else
 #pragma unroll
       for (int q = 0; q < NBW; q++)
@@ -272,8 +244,8 @@ __global__ __launch_bounds__(256, (stream_wgs_per_cu<LPR, NVMAX, WGS>())) void s
 #endif
 #pragma unroll
       for (int q = 0; q < NBW; q++) { w1[q] = w2[q]; pc[q] = pn[q]; }
-      load_words((b + 3) * 64 * NBW, w2);
-      load_perm((b + 2) * 64 * NBW, pn);
+      stream_load_batch(sw, sw.wp, (b + 3) * 64 * NBW, pad_word, w2);
+      stream_load_batch(sw, pp, (b + 2) * 64 * NBW, -1, pn);
    }
 }
 
@@ -316,62 +288,42 @@ constexpr int waitcnt_vm_lgkm0(int vm) { return (vm & 15) | (7 << 4) | (0 << 8) 
 
 template <int LPR, int NVMAX, int NBW, int HT, int HWR>
 __global__ __launch_bounds__(512, 2) void spmm_hybrid_kernel(const SweepArgs a) {
-   constexpr int WAVES = 8, G = 64 / LPR, PANEL = LPR * 4, U = 64 * NBW / G;
-   constexpr int PER = NVMAX / G, WAVE_FLOATS = NVMAX * PANEL;
+   using Wave = StreamWave<LPR, NVMAX, NBW, 8>;
+   constexpr int WAVES = Wave::WAVES, G = Wave::G, PANEL = Wave::PANEL, U = Wave::U, PER = Wave::PER;
+   constexpr int WAVE_FLOATS = NVMAX * PANEL;
    constexpr int HS = 64 / G;                             // hot steps held by one word register
    constexpr int SHARE = HT / WAVES, SI = SHARE / G;      // table rows / DMA instructions of one wave per slice
    static_assert(NVMAX <= 256 && NVMAX % G == 0 && HT % (WAVES * G) == 0 && SHARE <= 64 && HT <= 65536, "geometry");
    static_assert((WAVES * WAVE_FLOATS + HT * PANEL) * 4 <= CU_LDS_BYTES, "accumulators + table must fit the CU's LDS");
    static_assert(U + NBW <= 63, "counted vmcnt wait");
    __shared__ __attribute__((aligned(16))) float s_all[WAVES * WAVE_FLOATS + HT * PANEL];
-   const int lane = threadIdx.x & 63;
-   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-   const int g = lane / LPR, lc = lane % LPR;
-   const int wl = (int)blockIdx.x * WAVES + wave;         // the entry launches whole workgroups: wave_count % 8 == 0
-   const int64_t w = (int64_t)a.wave_base + wl;
+   Wave sw;
+   (void)stream_wave_id(a, sw);                           // the entry launches whole workgroups: wave_count % 8 == 0
+   const int lane = sw.lane, wave = sw.wave;
    float *my = s_all + wave * WAVE_FLOATS;
    float *table = s_all + WAVES * WAVE_FLOATS;
    for (int i = lane * 4; i < WAVE_FLOATS; i += 256)
       *reinterpret_cast<float4 *>(my + i) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
    for (int i = lane * 4; i < SHARE * PANEL; i += 256)    // the table too: its last row (and rows no slice fills) must read 0
       *reinterpret_cast<float4 *>(table + wave * SHARE * PANEL + i) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-   __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.y), 0, (int)a.ybytes, 0x00020000);
-   const bool cok = lc * 4 < a.k;
-   int ccol = lc * 4, vfirst = 0;
-   if (cok && ccol + 4 > (int)a.k) { vfirst = ccol + 4 - (int)a.k; ccol = (int)a.k - 4; }
-   const unsigned cbyte = (unsigned)ccol * 4u, poison = cok ? 0u : BUF_OOB;
-   float *lane_base = my + lc * 4;
-   const float *table_lane = table + lc * 4;
+   __amdgpu_buffer_rsrc_t rsrc = dense_rsrc(a);
+   stream_columns<true>(a, sw);
+   float *lane_base = my + sw.lc * 4;
+   const float *table_lane = table + sw.lc * 4;
    // the same descriptor as rsrc, as four SGPRs for the DMA's asm operand; the table's address in LDS
    const unsigned long long ybase = (unsigned long long)a.y;
    const v4i_rsrc_t rsrc_dma = {(int)(unsigned)ybase, (int)((ybase >> 32) & 0xFFFFu), (int)a.ybytes, 0x00020000};
    const unsigned table_lds = (unsigned)(size_t)(__attribute__((address_space(3))) float *)table;
-   const int64_t s0 = a.wave_step_off[w], s1 = a.wave_step_off[w + 1];
-   const int64_t nwords = (s1 - s0) * G;
-   const int32_t *wp = a.words + s0 * G;
-   const unsigned ldyb = (unsigned)a.ldy * 4u;
-   const unsigned pad_word = ((unsigned)((lane % G) * PER) << 24) | a.null_word;
+   stream_bounds(a, sw);
+   const unsigned pad_word = stream_pad_own_row(a, sw);
    const unsigned pad_hot = ((unsigned)((lane % G) * PER) << 24) | (unsigned)(HT - 1);
-   auto load_words = [&](int64_t first, unsigned (&word)[NBW]) {
-#pragma unroll
-      for (int q = 0; q < NBW; q++) {
-         const int64_t i = first + q * 64 + lane;
-         word[q] = i < nwords ? (unsigned)wp[i] : pad_word;
-      }
-   };
    unsigned wA[NBW], wB[NBW];                              // even / odd batches: used in turn, never copied (spmm_stream_kernel)
    v4i_t t[U];
    unsigned la[U];
-   auto issue = [&](int u, const unsigned (&word_l)[NBW]) {
-      const unsigned word = (unsigned)__shfl((int)word_l[(u * G) / 64], (u * G) % 64 + g);
-      const unsigned o = (__umul24(word & 0xFFFFFFu, ldyb) + cbyte) | poison;
-      la[u] = (word >> 24) * (unsigned)PANEL;
-      t[u] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)o, 0, 0);
-   };
    // hot operands of a phase: the chunk's words (HWR registers of 64, loaded a phase ahead) and the ids of the table
    // rows this wave stages (one register, two phases ahead)
    const int S = a.slices;
-   const int64_t *hoff = a.hot_step_off + w * S;
+   const int64_t *hoff = a.hot_step_off + sw.w * S;
    // chunk offsets, relative to the wave's first, 63 phases per register (entries p0 .. p0 + 63), picked by v_readlane:
    // a load of hoff[p] at the point of use would be a vector load (the compiler cannot prove the array unwritten) whose
    // wait drains the gather pipeline; the next block's register is loaded a whole block ahead
@@ -405,26 +357,20 @@ __global__ __launch_bounds__(512, 2) void spmm_hybrid_kernel(const SweepArgs a) 
    auto stage = [&](int ids) {
 #pragma unroll
       for (int j = 0; j < SI; j++) {
-         const unsigned cid = (unsigned)__shfl(ids, j * G + g);
-         const unsigned o = (__umul24(cid, ldyb) + cbyte) | poison;
+         const unsigned cid = (unsigned)__shfl(ids, j * G + sw.g);
+         const unsigned o = (__umul24(cid, sw.ldyb) + sw.cbyte) | sw.poison;
          lds_dma_b128(rsrc_dma, o, table_lds + (unsigned)((wave * SHARE + j * G) * PANEL * 4));
       }
    };
-   unsigned cur = (unsigned)(g * PER * PANEL);
+   unsigned cur = (unsigned)(sw.g * PER * PANEL);
    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-   auto flush = [&]() {
-      float4 *p = reinterpret_cast<float4 *>(lane_base + cur);
-      float4 o = *p;
-      o.x += acc[0]; o.y += acc[1]; o.z += acc[2]; o.w += acc[3];
-      *p = o;
-   };
    // prologue: the cold pipeline is filled, table 0 staged (own zeroing of the table first: DMA writes are not ordered
    // behind ds_writes), hot chunk 0 and the ids of table 1 loaded
-   load_words(0, wA);
-   load_words(64 * NBW, wB);
+   stream_load_batch(sw, sw.wp, 0, pad_word, wA);
+   stream_load_batch(sw, sw.wp, 64 * NBW, pad_word, wB);
 #pragma unroll
-   for (int u = 0; u < U; u++) issue(u, wA);
-   load_words(128 * NBW, wA);
+   for (int u = 0; u < U; u++) stream_issue<0>(sw, rsrc, wA, u, la[u], t[u]);
+   stream_load_batch(sw, sw.wp, 128 * NBW, pad_word, wA);
    int ids = load_ids(0);
    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
    stage(ids);
@@ -433,7 +379,7 @@ __global__ __launch_bounds__(512, 2) void spmm_hybrid_kernel(const SweepArgs a) 
    __builtin_amdgcn_s_waitcnt(waitcnt_vm_lgkm0(0));       // (the builtin: the compiler's wait-count pass must see it, below)
    asm volatile("s_barrier" ::: "memory");
    // the cold stream in PAIRS of batches (A, B): a phase is a whole number of pairs
-   const int64_t npairs = ((nwords + 64 * NBW - 1) / (64 * NBW) + 1) / 2;
+   const int64_t npairs = ((sw.nwords + 64 * NBW - 1) / (64 * NBW) + 1) / 2;
    int64_t b = 0;                                          // pairs done
    const int pairs_q = (int)(npairs / S), pairs_r = (int)(npairs % S);
    int pairs_err = 0;
@@ -441,16 +387,16 @@ __global__ __launch_bounds__(512, 2) void spmm_hybrid_kernel(const SweepArgs a) 
 #pragma unroll
       for (int u = 0; u < U; u++) {
          if (la[u] != cur) {
-            flush();
+            stream_flush(lane_base + cur, acc);
             cur = la[u];
             acc[0] = acc[1] = acc[2] = acc[3] = 0.0f;
          }
 #pragma unroll
          for (int v = 0; v < 4; v++) acc[v] += __int_as_float(t[u][v]);
          __builtin_amdgcn_sched_barrier(0);                // the old t[u] is consumed before the new one is issued: no copy
-         issue(u, wnext);
+         stream_issue<0>(sw, rsrc, wnext, u, la[u], t[u]);
       }
-      load_words((bb + 3) * 64 * NBW, wnext);
+      stream_load_batch(sw, sw.wp, (bb + 3) * 64 * NBW, pad_word, wnext);
    };
    for (int p = 0; p < S; p++) {
       // ---- hot chunk p: groups of four steps (four ds_bpermute, four ds_read_b128, then the adds) ----
@@ -459,7 +405,7 @@ __global__ __launch_bounds__(512, 2) void spmm_hybrid_kernel(const SweepArgs a) 
 #else
       if (hn > 0) {
 #endif
-         flush();
+         stream_flush(lane_base + cur, acc);
          acc[0] = acc[1] = acc[2] = acc[3] = 0.0f;
 #pragma unroll
          for (int q = 0; q < HWR; q++) {
@@ -470,14 +416,14 @@ __global__ __launch_bounds__(512, 2) void spmm_hybrid_kernel(const SweepArgs a) 
                unsigned wd[4];
                float4 xv[4];
 #pragma unroll
-               for (int i = 0; i < 4; i++) wd[i] = (unsigned)__shfl((int)hw[q], (j0 + i) * G + g);
+               for (int i = 0; i < 4; i++) wd[i] = (unsigned)__shfl((int)hw[q], (j0 + i) * G + sw.g);
 #pragma unroll
                for (int i = 0; i < 4; i++) xv[i] = *reinterpret_cast<const float4 *>(table_lane + (wd[i] & 0xFFFFu) * (unsigned)PANEL);
 #pragma unroll
                for (int i = 0; i < 4; i++) {
                   const unsigned lrow = (wd[i] >> 24) * (unsigned)PANEL;
                   if (lrow != cur) {
-                     flush();
+                     stream_flush(lane_base + cur, acc);
                      cur = lrow;
                      acc[0] = acc[1] = acc[2] = acc[3] = 0.0f;
                   }
@@ -485,7 +431,7 @@ __global__ __launch_bounds__(512, 2) void spmm_hybrid_kernel(const SweepArgs a) 
                }
             }
          }
-         flush();
+         stream_flush(lane_base + cur, acc);
          acc[0] = acc[1] = acc[2] = acc[3] = 0.0f;
       }
       // everyone is done with table p: the next one may land on it
@@ -516,24 +462,24 @@ __global__ __launch_bounds__(512, 2) void spmm_hybrid_kernel(const SweepArgs a) 
       __builtin_amdgcn_s_waitcnt(waitcnt_vm_lgkm0(U + NBW));
       asm volatile("s_barrier" ::: "memory");              // table p+1 complete
    }
-   flush();
+   stream_flush(lane_base + cur, acc);
 #pragma unroll 1
    for (int jj = 0; jj < PER; jj++) {
-      const int lrow = g * PER + jj;
-      const int row = a.wave_row[(size_t)w * NVMAX + lrow];
-      if (row < 0 || !cok) continue;
-      const int part = a.wave_part[(size_t)w * NVMAX + lrow];
+      const int lrow = sw.g * PER + jj;
+      const int row = a.wave_row[(size_t)sw.w * NVMAX + lrow];
+      if (row < 0 || !sw.cok) continue;
+      const int part = a.wave_part[(size_t)sw.w * NVMAX + lrow];
       const float4 t4 = *reinterpret_cast<const float4 *>(lane_base + lrow * PANEL);
       float v[4] = {t4.x, t4.y, t4.z, t4.w};
       int bi[4] = {INT_MAX, INT_MAX, INT_MAX, INT_MAX};
-      const int c = ccol;
+      const int c = sw.ccol;
       if (part >= 0) {
-         store_tail<4>(a.part_val + (size_t)part * (size_t)a.k + c, v, vfirst);
+         store_tail<4>(a.part_val + (size_t)part * (size_t)a.k + c, v, sw.vfirst);
          continue;
       }
       int64_t arg[4];
       finish_row<OP_ADD>(a, row, c, v, bi, arg);
-      store_tail<4>(a.z + (size_t)row * (size_t)a.ldz + c, v, vfirst);
+      store_tail<4>(a.z + (size_t)row * (size_t)a.ldz + c, v, sw.vfirst);
    }
 }
 
@@ -707,9 +653,7 @@ extern "C" int isplib_sddmm_stream_hip(int64_t m, int64_t n, int64_t k, int64_t 
       p.g = g + at;
       p.ybytes = a.ybytes - (unsigned)at * 4u;
       const int rc_gen = run_generations(plan->gens, plan->waves_per_gen, p, [&](const SweepArgs &q) {
-         if (plan->streams == 2) return first ? launch_sddmm_stream<2, false>(q, st) : launch_sddmm_stream<2, true>(q, st);
-         if (plan->streams == 4) return first ? launch_sddmm_stream<4, false>(q, st) : launch_sddmm_stream<4, true>(q, st);
-         return first ? launch_sddmm_stream<8, false>(q, st) : launch_sddmm_stream<8, true>(q, st);
+         return with_streams<STREAM_SUM>(plan->streams, [&](auto s) { return first ? launch_sddmm_stream<s(), false>(q, st) : launch_sddmm_stream<s(), true>(q, st); });
       });
       if (rc_gen) return rc_gen;
       first = false;
@@ -771,7 +715,7 @@ extern "C" int fusedMM_csr_hybrid_hip(int32_t imessage, int64_t m, int64_t n, in
    if ((rc = set_epilogue(entry, ep, a)) != ISPLIB_SUCCESS) return rc;
    hipStream_t st = (hipStream_t)stream;
    return run_stream_panels(plan, a,
-      [&](const SweepArgs &p) { return plan->streams == 4 ? launch_hybrid<4>(p, st) : launch_hybrid<8>(p, st); },
+      [&](const SweepArgs &p) { return with_streams<STREAM_HYBRID>(plan->streams, [&](auto s) { return launch_hybrid<s()>(p, st); }); },
       [&](const SweepArgs &p) { return launch_hub_fold<OP_ADD, true>(p, st); });
 }
 

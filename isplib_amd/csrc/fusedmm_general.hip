@@ -110,7 +110,7 @@ __global__ __launch_bounds__(WAVES * 64) void fusedmm_general_kernel(const GenAr
       ee = a.pntre[row];
    }
    const int64_t rb = a.pntrb[row], re = TASK ? ee : a.pntre[row];   // rb: origin of the row-relative edge ids
-   __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.y), 0, (int)a.ybytes, 0x00020000);
+   __amdgpu_buffer_rsrc_t rsrc = dense_rsrc(a);
 
    // this lane's columns: 4 consecutive ones per chunk, masked past k (a 16-byte load may run into the next row
    // or past the buffer -- the latter reads 0 -- and the mask drops whatever it brought)

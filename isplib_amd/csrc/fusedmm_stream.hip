@@ -40,68 +40,41 @@ __device__ __forceinline__ float sop_menu(int kind, float s, float p) {
 template <int PAT, int LPR, int NVMAX, int NBW, int WGS>
 __global__ __launch_bounds__(256, (stream_wgs_per_cu<LPR, 2 * (NVMAX + 1), WGS>())) void fusedmm_stream_kernel(const SweepArgs a, const int sop_udef,
                                                                                                              const float sop_param) {
-   constexpr int WAVES = 4, G = 64 / LPR, PANEL = LPR * 4, U = 64 * NBW / G;
-   constexpr int PER = NVMAX / G, ROWS = NVMAX + 1, WAVE_FLOATS = 2 * ROWS * PANEL, Z0 = ROWS * PANEL;
+   using Wave = StreamWave<LPR, NVMAX, NBW>;
+   constexpr int WAVES = Wave::WAVES, G = Wave::G, PANEL = Wave::PANEL, U = Wave::U, PER = Wave::PER;
+   constexpr int ROWS = NVMAX + 1, WAVE_FLOATS = 2 * ROWS * PANEL, Z0 = ROWS * PANEL;
    static_assert(U % 4 == 0 && ROWS <= 256 && NVMAX % G == 0, "four steps per butterfly; the local row is the top byte of a word");
    __shared__ __attribute__((aligned(16))) float s_all[WAVES * WAVE_FLOATS];
-   const int lane = threadIdx.x & 63;
-   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-   const int g = lane / LPR, lc = lane % LPR;
-   const int wl = (int)blockIdx.x * WAVES + wave;
-   if (wl >= a.wave_count) return;                       // no barrier anywhere below
-   const int64_t w = (int64_t)a.wave_base + wl;
-   float *my = s_all + wave * WAVE_FLOATS;
-   const bool cok = lc * 4 < a.k;                         // k % 4 == 0 (entry): a lane's four columns are all inside or all outside
-   const int ccol = lc * 4;
-   const unsigned cbyte = (unsigned)ccol * 4u, poison = cok ? 0u : BUF_OOB;
-   float *lane_x = my + lc * 4;                           // a lane's four columns of a row of x ...
-   float *lane_z = my + Z0 + lc * 4;                      // ... and of its accumulator
+   Wave sw;
+   if (!stream_wave_id(a, sw)) return;                   // no barrier anywhere below
+   float *my = s_all + sw.wave * WAVE_FLOATS;
+   stream_columns<false>(a, sw);                          // k % 4 == 0 (entry): a lane's four columns are all inside or all outside
+   float *lane_x = my + sw.lc * 4;                        // a lane's four columns of a row of x ...
+   float *lane_z = my + Z0 + sw.lc * 4;                   // ... and of its accumulator
    // the wave's rows of x into the first plane (unused local rows and the spare row: 0), zeros into the second
 #pragma unroll 1
    for (int jj = 0; jj <= PER; jj++) {
-      const int lrow = jj < PER ? g * PER + jj : NVMAX;
-      const int row = jj < PER ? a.wave_row[(size_t)w * NVMAX + lrow] : -1;
+      const int lrow = jj < PER ? sw.g * PER + jj : NVMAX;
+      const int row = jj < PER ? a.wave_row[(size_t)sw.w * NVMAX + lrow] : -1;
       float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      if (row >= 0 && cok) v = *reinterpret_cast<const float4 *>(a.g + (size_t)row * (size_t)a.ldg + ccol);
+      if (row >= 0 && sw.cok) v = *reinterpret_cast<const float4 *>(a.g + (size_t)row * (size_t)a.ldg + sw.ccol);
       *reinterpret_cast<float4 *>(lane_x + lrow * PANEL) = v;
       *reinterpret_cast<float4 *>(lane_z + lrow * PANEL) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
    }
-   __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.y), 0, (int)a.ybytes, 0x00020000);
-   const int64_t s0 = a.wave_step_off[w], s1 = a.wave_step_off[w + 1];
-   const int64_t nwords = (s1 - s0) * G;
-   const int32_t *wp = a.words + s0 * G;
-   const unsigned ldyb = (unsigned)a.ldy * 4u;
-   const unsigned pad_word = ((unsigned)NVMAX << 24) | a.null_word;      // past the end of the wave: the spare row
-   auto load_words = [&](int64_t first, unsigned (&word)[NBW]) {
-#pragma unroll
-      for (int q = 0; q < NBW; q++) {
-         const int64_t i = first + q * 64 + lane;
-         word[q] = i < nwords ? (unsigned)wp[i] : pad_word;
-      }
-   };
+   __amdgpu_buffer_rsrc_t rsrc = dense_rsrc(a);
+   stream_bounds(a, sw);
+   const unsigned pad_word = stream_pad_spare_row(a, sw);      // past the end of the wave: the spare row
    unsigned w1[NBW], w2[NBW];
    v4i_t t[U];
    unsigned la[U];
-   auto issue = [&](int u, const unsigned (&word_l)[NBW]) {
-      const unsigned word = (unsigned)__shfl((int)word_l[(u * G) / 64], (u * G) % 64 + g);
-      const unsigned o = (__umul24(word & 0xFFFFFFu, ldyb) + cbyte) | poison;
-      la[u] = (word >> 24) * (unsigned)PANEL;
-      t[u] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)o, 0, 0);
-   };
-   load_words(0, w1);
+   stream_load_batch(sw, sw.wp, 0, pad_word, w1);
 #pragma unroll
-   for (int u = 0; u < U; u++) issue(u, w1);
-   load_words(64 * NBW, w1);
-   load_words(128 * NBW, w2);
-   unsigned curz = (unsigned)(g * PER * PANEL);           // the row whose accumulator the registers hold
+   for (int u = 0; u < U; u++) stream_issue<0>(sw, rsrc, w1, u, la[u], t[u]);
+   stream_load_batch(sw, sw.wp, 64 * NBW, pad_word, w1);
+   stream_load_batch(sw, sw.wp, 128 * NBW, pad_word, w2);
+   unsigned curz = (unsigned)(sw.g * PER * PANEL);        // the row whose accumulator the registers hold
    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-   auto flush = [&]() {
-      float4 *p = reinterpret_cast<float4 *>(lane_z + curz);
-      float4 o = *p;
-      o.x += acc[0]; o.y += acc[1]; o.z += acc[2]; o.w += acc[3];
-      *p = o;
-   };
-   const int64_t nb = (nwords + 64 * NBW - 1) / (64 * NBW);
+   const int64_t nb = (sw.nwords + 64 * NBW - 1) / (64 * NBW);
    for (int64_t b = 0; b < nb; b++) {
 #pragma unroll
       for (int u0 = 0; u0 < U; u0 += 4) {
@@ -126,16 +99,16 @@ __global__ __launch_bounds__(256, (stream_wgs_per_cu<LPR, 2 * (NVMAX + 1), WGS>(
             }
          }
          int mine;
-         const float sum = reduce_transposed<4, LPR>(d, lc, mine);
+         const float sum = reduce_transposed<4, LPR>(d, sw.lc, mine);
          const float sown = sop_menu(sop_udef, sum, sop_param);      // meaningful on the lanes that own a step's sum
          float s[4];
 #pragma unroll
-         for (int q = 0; q < 4; q++) s[q] = __shfl(sown, g * LPR + transposed_owner<4, LPR>(q));
+         for (int q = 0; q < 4; q++) s[q] = __shfl(sown, sw.g * LPR + transposed_owner<4, LPR>(q));
 #pragma unroll
          for (int q = 0; q < 4; q++) {
             const int u = u0 + q;
             if (la[u] != curz) {
-               flush();
+               stream_flush(lane_z + curz, acc);
                curz = la[u];
                acc[0] = acc[1] = acc[2] = acc[3] = 0.0f;
             }
@@ -143,25 +116,25 @@ __global__ __launch_bounds__(256, (stream_wgs_per_cu<LPR, 2 * (NVMAX + 1), WGS>(
             for (int v = 0; v < 4; v++) acc[v] = fmaf(s[q], __int_as_float(t[u][v]), acc[v]);
          }
 #pragma unroll
-         for (int q = 0; q < 4; q++) issue(u0 + q, w1);
+         for (int q = 0; q < 4; q++) stream_issue<0>(sw, rsrc, w1, u0 + q, la[u0 + q], t[u0 + q]);
       }
 #pragma unroll
       for (int q = 0; q < NBW; q++) w1[q] = w2[q];
-      load_words((b + 3) * 64 * NBW, w2);
+      stream_load_batch(sw, sw.wp, (b + 3) * 64 * NBW, pad_word, w2);
    }
-   flush();
+   stream_flush(lane_z + curz, acc);
    // write-out: slot q owns the local rows [q * PER, (q + 1) * PER); its LPR lanes hold one row
    int row_[PER], part_[PER];
 #pragma unroll
    for (int jj = 0; jj < PER; jj++) {
-      row_[jj] = cok ? a.wave_row[(size_t)w * NVMAX + g * PER + jj] : -1;
-      part_[jj] = a.wave_part[(size_t)w * NVMAX + g * PER + jj];
+      row_[jj] = sw.cok ? a.wave_row[(size_t)sw.w * NVMAX + sw.g * PER + jj] : -1;
+      part_[jj] = a.wave_part[(size_t)sw.w * NVMAX + sw.g * PER + jj];
    }
 #pragma unroll
    for (int jj = 0; jj < PER; jj++) {
       if (row_[jj] < 0) continue;
-      const float4 v = *reinterpret_cast<const float4 *>(lane_z + (g * PER + jj) * PANEL);
-      float *dst = part_[jj] >= 0 ? a.part_val + (size_t)part_[jj] * (size_t)a.k + ccol : a.z + (size_t)row_[jj] * (size_t)a.ldz + ccol;
+      const float4 v = *reinterpret_cast<const float4 *>(lane_z + (sw.g * PER + jj) * PANEL);
+      float *dst = part_[jj] >= 0 ? a.part_val + (size_t)part_[jj] * (size_t)a.k + sw.ccol : a.z + (size_t)row_[jj] * (size_t)a.ldz + sw.ccol;
       *reinterpret_cast<float4 *>(dst) = v;
    }
 }
@@ -177,8 +150,7 @@ static int launch_fusedmm_stream(const SweepArgs &a, int sop_udef, float sop_par
 
 template <int PAT>
 static int launch_fusedmm_stream(const SweepArgs &a, int streams, int sop_udef, float sop_param, hipStream_t st) {
-   return streams == 2 ? launch_fusedmm_stream<PAT, 2>(a, sop_udef, sop_param, st)
-        : streams == 4 ? launch_fusedmm_stream<PAT, 4>(a, sop_udef, sop_param, st) : launch_fusedmm_stream<PAT, 8>(a, sop_udef, sop_param, st);
+   return with_streams<STREAM_FUSEDMM>(streams, [&](auto s) { return launch_fusedmm_stream<PAT, s()>(a, sop_udef, sop_param, st); });
 }
 
 }  // namespace isplib

@@ -1,7 +1,8 @@
 // gather.h -- the gather-reduce inner loops shared by every SpMM schedule (plain, column-sliced, task list):
 // vector load/store helpers, the (value, edge id) comparator of max/min, the 64-bit-address and the
 // buffer-descriptor forms of "one wave walks an edge range", the cross-slot butterfly, and the unroll /
-// occupancy choices.  Device code only; included by spmm.hip and spmm_tasks.hip.
+// occupancy choices.  Device code only; included by every translation unit that gathers rows of the dense operand (the
+// SpMM schedules, the backward and FusedMM task kernels, and through sweep_common.h the row-resident schedules).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -151,6 +152,11 @@ constexpr unsigned BUF_LIMIT = ISPLIB_DENSE_BYTES_MAX;   // bytes addressable; o
 constexpr unsigned BUF_OOB = ISPLIB_DENSE_OOB_OFFSET;    // + any column offset (< 2^24) stays < 2^32: never wraps
 
 typedef __attribute__((__vector_size__(4 * sizeof(int)))) int v4i_t;
+
+// the descriptor of the dense operand of a launch (a.y, a.ybytes): raw 32-bit byte offsets, range-checked against ybytes
+template <class Args> __device__ __forceinline__ __amdgpu_buffer_rsrc_t dense_rsrc(const Args &a) {
+   return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.y), 0, (int)a.ybytes, 0x00020000);
+}
 
 // UU gathers per slot issued back to back for the edges [s, s + G*UU) of the current 64-edge batch
 template <int OP, bool HAS_VAL, int LPR, int NCH, int UU>

@@ -15,8 +15,8 @@
 namespace isplib {
 
 // ---- stream form ------------------------------------------------------------------------------------------------
-// The sweep above still pays one latency chain per (row, slice) segment -- and with L2-sized slices a segment is
-// 15 edges.  Here a wave does not see segments at all.  The plan gives each of the G = 64 / LPR slots of a wave its
+// The round-2 sweep (experimental/experimental.hip) pays one latency chain per (row, slice) segment -- and with L2-sized
+// slices a segment is 15 edges.  Here a wave does not see segments at all.  The plan gives each of the G = 64 / LPR slots of a wave its
 // own STREAM: the edges of the slot's NVMAX / G rows, slice by slice, as 4-byte words (local row << 24 | column) in
 // the plan's own copy of the index array.  Step i of a wave gathers word i of each of its G streams -- one 1-KiB
 // buffer load, always full -- and every lane adds the four floats it receives to the running sum of the row its
@@ -26,102 +26,54 @@ namespace isplib {
 // masked tail, no per-segment bookkeeping.  Sum / mean only.
 template <int LPR, bool HAS_VAL, int NVMAX, int NBW, int WGS>
 __global__ __launch_bounds__(256, (stream_wgs_per_cu<LPR, NVMAX, WGS>())) void spmm_stream_kernel(const SweepArgs a) {
-   constexpr int WAVES = 4, G = 64 / LPR, PANEL = LPR * 4, U = 64 * NBW / G;     // a batch = NBW x 64 words = U steps
-   constexpr int PER = NVMAX / G;                         // rows of a slot
+   using Wave = StreamWave<LPR, NVMAX, NBW>;
+   constexpr int WAVES = Wave::WAVES, G = Wave::G, PANEL = Wave::PANEL, U = Wave::U, PER = Wave::PER;
    constexpr int WAVE_FLOATS = NVMAX * PANEL;
    static_assert(NVMAX <= 256 && NVMAX % G == 0, "the local row is the top byte of a word");
    __shared__ __attribute__((aligned(16))) float s_all[WAVES * WAVE_FLOATS];
-   const int lane = threadIdx.x & 63;
-   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-   const int g = lane / LPR, lc = lane % LPR;
-   const int wl = (int)blockIdx.x * WAVES + wave;
-   if (wl >= a.wave_count) return;                       // no barrier anywhere below
-   const int64_t w = (int64_t)a.wave_base + wl;
+   Wave sw;
+   if (!stream_wave_id(a, sw)) return;                   // no barrier anywhere below
+   const int lane = sw.lane;
 #ifdef ISPLIB_EXP_WAVE_TIMES
    const unsigned long long t_start = __builtin_amdgcn_s_memtime();
 #endif
-   float *my = s_all + wave * WAVE_FLOATS;
+   float *my = s_all + sw.wave * WAVE_FLOATS;
    for (int i = lane * 4; i < WAVE_FLOATS; i += 256)
       *reinterpret_cast<float4 *>(my + i) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-   __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.y), 0, (int)a.ybytes, 0x00020000);
-   // a lane holds columns lc*4 .. lc*4+3 of the panel; when k is not a multiple of 4 the last lane's vector is shifted
-   // back to END at column k (its first `vfirst` components repeat the neighbour's columns and are never stored), so
-   // no load reaches past a row and rows need only 4-byte alignment (the GCN's K = 41 runs here instead of the task list)
-   const bool cok = lc * 4 < a.k;
-   int ccol = lc * 4, vfirst = 0;
-   if (cok && ccol + 4 > (int)a.k) { vfirst = ccol + 4 - (int)a.k; ccol = (int)a.k - 4; }
-   const unsigned cbyte = (unsigned)ccol * 4u, poison = cok ? 0u : BUF_OOB;
-   float *lane_base = my + lc * 4;                        // a lane's four columns of a row are contiguous
-   const int64_t s0 = a.wave_step_off[w], s1 = a.wave_step_off[w + 1];
-   const int64_t nwords = (s1 - s0) * G;
-   const int32_t *wp = a.words + s0 * G;
-   const float *vp = HAS_VAL ? a.vals + s0 * G : nullptr;
-   const unsigned ldyb = (unsigned)a.ldy * 4u;
-   // lane i of batch register q holds word q*64 + i = (step (q*64 + i) / G, slot i % G); past the end of the wave: the
-   // padding word of the slot (column n: the gather reads 0 through the range check; the row is one of the slot's own)
-   const unsigned pad_word = ((unsigned)((lane % G) * PER) << 24) | a.null_word;
-   auto load_words = [&](int64_t first, unsigned (&word)[NBW]) {
-#pragma unroll
-      for (int q = 0; q < NBW; q++) {
-         const int64_t i = first + q * 64 + lane;
-         word[q] = i < nwords ? (unsigned)wp[i] : pad_word;
-      }
-   };
-   auto load_vals = [&](int64_t first, float (&val)[NBW]) {
-#pragma unroll
-      for (int q = 0; q < NBW; q++) {
-         const int64_t i = first + q * 64 + lane;
-         val[q] = HAS_VAL && i < nwords ? vp[i] : 0.0f;
-      }
-   };
+   __amdgpu_buffer_rsrc_t rsrc = dense_rsrc(a);
+   stream_columns<true>(a, sw);
+   float *lane_base = my + sw.lc * 4;                     // a lane's four columns of a row are contiguous
+   stream_bounds(a, sw);
+   const float *vp = HAS_VAL ? a.vals + sw.s0 * G : nullptr;
    unsigned w1[NBW], w2[NBW];                             // the words of the next batch and of the one after it
-   float v0[NBW], v1[NBW];                                // the weights of the batch being consumed and of the next: a weight is
-                                                          // needed one batch later than its word, so it is loaded one batch later
+   float v0[NBW] = {}, v1[NBW] = {};                      // the weights of the batch being consumed and of the next
    v4i_t t[U];
    unsigned la[U];
-   // one ds_bpermute hands a slot its word of the step (the LDS pipe is otherwise idle; picking it with v_readlane +
-   // v_cndmask cost 16 vector instructions per step); column * row pitch is a 24-bit multiply (n < 2^24, pitch < 2^24,
-   // product < 2^32: checked by the entry)
    // (a weight is fetched from its batch register when its gather is consumed, one step ahead: a ring of U weights
    // beside the U gathers in flight costs 30 registers)
-   auto issue = [&](int u, const unsigned (&word_l)[NBW]) {
-      const unsigned word = (unsigned)__shfl((int)word_l[(u * G) / 64], (u * G) % 64 + g);
-      const unsigned o = (__umul24(word & 0xFFFFFFu, ldyb) + cbyte) | poison;
-      la[u] = (word >> 24) * (unsigned)PANEL;
-      t[u] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)o, 0, ISPLIB_EXP_GATHER_AUX);
-   };
-   load_words(0, w1);
-   load_vals(0, v0);
+   const unsigned pad_word = stream_pad_own_row(a, sw);
+   stream_load_batch(sw, sw.wp, 0, pad_word, w1);
+   if (HAS_VAL) stream_load_batch(sw, vp, 0, 0.0f, v0);
 #pragma unroll
-   for (int u = 0; u < U; u++) issue(u, w1);
-   load_words(64 * NBW, w1);
-   load_vals(64 * NBW, v1);
-   load_words(128 * NBW, w2);
-   // The row a slot is working on keeps its running sum in registers; it moves to the slot's LDS row when the stream
-   // turns to another row (every ~deg / slices edges) and is picked up again from there when the stream comes back
-   // in the next slice.  Plain read-add-write by the only lanes that ever touch that LDS row: LDS float atomics
-   // (one ds_add_f32 per gathered float) ran 25x slower than the gathers they were meant to keep up with.
-   unsigned cur = (unsigned)(g * PER * PANEL);
+   for (int u = 0; u < U; u++) stream_issue<ISPLIB_EXP_GATHER_AUX>(sw, rsrc, w1, u, la[u], t[u]);
+   stream_load_batch(sw, sw.wp, 64 * NBW, pad_word, w1);
+   if (HAS_VAL) stream_load_batch(sw, vp, 64 * NBW, 0.0f, v1);
+   stream_load_batch(sw, sw.wp, 128 * NBW, pad_word, w2);
+   unsigned cur = (unsigned)(sw.g * PER * PANEL);         // the row whose running sum the registers hold (stream_flush)
    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-   auto flush = [&]() {
-      float4 *p = reinterpret_cast<float4 *>(lane_base + cur);
-      float4 o = *p;
-      o.x += acc[0]; o.y += acc[1]; o.z += acc[2]; o.w += acc[3];
-      *p = o;
-   };
-   const int64_t nb = (nwords + 64 * NBW - 1) / (64 * NBW);
+   const int64_t nb = (sw.nwords + 64 * NBW - 1) / (64 * NBW);
 #ifdef ISPLIB_EXP_WAVE_TIMES
    const unsigned long long t_loop = __builtin_amdgcn_s_memtime();
 #endif
    for (int64_t b = 0; b < nb; b++) {
       // the U gathers of batch b are in flight; each one consumed is replaced by the same step of batch b + 1
-      float vnext = HAS_VAL ? __shfl(v0[0], g) : 0.0f;
+      float vnext = HAS_VAL ? __shfl(v0[0], sw.g) : 0.0f;
 #pragma unroll
       for (int u = 0; u < U; u++) {
          const float vcur = vnext;
-         if (HAS_VAL && u + 1 < U) vnext = __shfl(v0[((u + 1) * G) / 64], ((u + 1) * G) % 64 + g);
+         if (HAS_VAL && u + 1 < U) vnext = __shfl(v0[((u + 1) * G) / 64], ((u + 1) * G) % 64 + sw.g);
          if (la[u] != cur) {                             // per lane: the slots of a wave change rows at different steps
-            flush();
+            stream_flush(lane_base + cur, acc);
             cur = la[u];
             acc[0] = acc[1] = acc[2] = acc[3] = 0.0f;
          }
@@ -130,14 +82,14 @@ __global__ __launch_bounds__(256, (stream_wgs_per_cu<LPR, NVMAX, WGS>())) void s
             const float x = __int_as_float(t[u][v]);
             acc[v] = HAS_VAL ? fmaf(vcur, x, acc[v]) : acc[v] + x;
          }
-         issue(u, w1);
+         stream_issue<ISPLIB_EXP_GATHER_AUX>(sw, rsrc, w1, u, la[u], t[u]);
       }
 #pragma unroll
       for (int q = 0; q < NBW; q++) { w1[q] = w2[q]; v0[q] = v1[q]; }
-      load_words((b + 3) * 64 * NBW, w2);
-      load_vals((b + 2) * 64 * NBW, v1);
+      stream_load_batch(sw, sw.wp, (b + 3) * 64 * NBW, pad_word, w2);
+      if (HAS_VAL) stream_load_batch(sw, vp, (b + 2) * 64 * NBW, 0.0f, v1);
    }
-   flush();
+   stream_flush(lane_base + cur, acc);
 #ifdef ISPLIB_EXP_WAVE_TIMES
    const unsigned long long t_loop_end = __builtin_amdgcn_s_memtime();
 #endif
@@ -147,33 +99,33 @@ __global__ __launch_bounds__(256, (stream_wgs_per_cu<LPR, NVMAX, WGS>())) void s
    int row_[PER], part_[PER];
 #pragma unroll
    for (int jj = 0; jj < PER; jj++) {
-      row_[jj] = cok ? a.wave_row[(size_t)w * NVMAX + g * PER + jj] : -1;
-      part_[jj] = a.wave_part[(size_t)w * NVMAX + g * PER + jj];
+      row_[jj] = sw.cok ? a.wave_row[(size_t)sw.w * NVMAX + sw.g * PER + jj] : -1;
+      part_[jj] = a.wave_part[(size_t)sw.w * NVMAX + sw.g * PER + jj];
    }
 #pragma unroll 4
    for (int jj = 0; jj < PER; jj++) {
-      const int lrow = g * PER + jj;
+      const int lrow = sw.g * PER + jj;
       const int row = row_[jj];
       if (row < 0) continue;
       const int part = part_[jj];
       const float4 t4 = *reinterpret_cast<const float4 *>(lane_base + lrow * PANEL);
       float v[4] = {t4.x, t4.y, t4.z, t4.w};
       int bi[4] = {INT_MAX, INT_MAX, INT_MAX, INT_MAX};
-      const int c = ccol;
+      const int c = sw.ccol;
       if (part >= 0) {
-         store_tail<4>(a.part_val + (size_t)part * (size_t)a.k + c, v, vfirst);
+         store_tail<4>(a.part_val + (size_t)part * (size_t)a.k + c, v, sw.vfirst);
          continue;
       }
       int64_t arg[4];
       finish_row<OP_ADD>(a, row, c, v, bi, arg);
-      store_tail<4>(a.z + (size_t)row * (size_t)a.ldz + c, v, vfirst);
+      store_tail<4>(a.z + (size_t)row * (size_t)a.ldz + c, v, sw.vfirst);
    }
 #ifdef ISPLIB_EXP_WAVE_TIMES
    if (a.dbg && lane == 0) {
-      a.dbg[(size_t)wl * 4 + 0] = t_start;
-      a.dbg[(size_t)wl * 4 + 1] = t_loop;
-      a.dbg[(size_t)wl * 4 + 2] = t_loop_end;
-      a.dbg[(size_t)wl * 4 + 3] = __builtin_amdgcn_s_memtime();
+      a.dbg[(size_t)sw.wl * 4 + 0] = t_start;
+      a.dbg[(size_t)sw.wl * 4 + 1] = t_loop;
+      a.dbg[(size_t)sw.wl * 4 + 2] = t_loop_end;
+      a.dbg[(size_t)sw.wl * 4 + 3] = __builtin_amdgcn_s_memtime();
    }
 #endif
 }
@@ -209,58 +161,36 @@ typedef float v2f_t __attribute__((ext_vector_type(2)));
 // same values bit for bit.  K=64 on the Reddit shape: 1.80 -> 1.6 ms with U(0,1) weights, 1.61 -> 1.4 with unit weights.
 template <int OP, int LPR, bool HAS_VAL, int NVMAX, int NBW, int WGS, bool ARG>
 __global__ __launch_bounds__(256, (stream_wgs_per_cu<LPR, 2 * (NVMAX + 1), WGS>())) void spmm_stream_minmax_kernel(const SweepArgs a) {
-   constexpr int WAVES = 4, G = 64 / LPR, PANEL = LPR * 4, U = 64 * NBW / G;
-   constexpr int PER = NVMAX / G;
+   using Wave = StreamWave<LPR, NVMAX, NBW>;
+   constexpr int WAVES = Wave::WAVES, G = Wave::G, PANEL = Wave::PANEL, U = Wave::U, PER = Wave::PER;
    constexpr int ROWS = NVMAX + 1;                        // + the spare row of the padding words
    constexpr int WAVE_DWORDS = 2 * ROWS * PANEL;          // a wave's block: the values, then their indices
    constexpr int IDX0 = ROWS * PANEL;
    constexpr int NONE = INT_MAX;                          // "no winner yet"
    static_assert(ROWS <= 256 && NVMAX % G == 0, "the local row (and the spare row) is the top byte of a word");
    __shared__ __attribute__((aligned(16))) float s_all[WAVES * WAVE_DWORDS];
-   const int lane = threadIdx.x & 63;
-   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-   const int g = lane / LPR, lc = lane % LPR;
-   const int wl = (int)blockIdx.x * WAVES + wave;
-   if (wl >= a.wave_count) return;                       // no barrier anywhere below
-   const int64_t w = (int64_t)a.wave_base + wl;
-   float *my = s_all + wave * WAVE_DWORDS;
+   Wave sw;
+   if (!stream_wave_id(a, sw)) return;                   // no barrier anywhere below
+   const int lane = sw.lane;
+   float *my = s_all + sw.wave * WAVE_DWORDS;
    for (int i = lane * 4; i < ROWS * PANEL; i += 256)
       *reinterpret_cast<float4 *>(my + i) = make_float4(identity<OP>(), identity<OP>(), identity<OP>(), identity<OP>());
    if (ARG)
       for (int i = lane * 4; i < ROWS * PANEL; i += 256)
          *reinterpret_cast<int4 *>(my + IDX0 + i) = make_int4(INT_MAX, INT_MAX, INT_MAX, INT_MAX);
-   __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.y), 0, (int)a.ybytes, 0x00020000);
-   const bool cok = lc * 4 < a.k;
-   int ccol = lc * 4, vfirst = 0;
-   if (cok && ccol + 4 > (int)a.k) { vfirst = ccol + 4 - (int)a.k; ccol = (int)a.k - 4; }
+   __amdgpu_buffer_rsrc_t rsrc = dense_rsrc(a);
+   stream_columns<true>(a, sw);
    // lanes beyond column k gather nothing: their column term is 2^31, past the end of the descriptor (the entry admits dense
    // operands under 2 GiB only, so row offset + 2^31 neither stays inside the descriptor nor wraps) -- no OR in the loop
-   const unsigned cbyte = cok ? (unsigned)ccol * 4u : 0x80000000u;
-   float *lane_base = my + lc * 4;                        // a lane's four values of a row ...
-   int *lane_idx = reinterpret_cast<int *>(my + IDX0) + lc * 4;      // ... and their indices
-   const int64_t s0 = a.wave_step_off[w], s1 = a.wave_step_off[w + 1];
-   const int64_t nwords = (s1 - s0) * G;
-   const int32_t *wp = a.words + s0 * G;
-   const float *vp = HAS_VAL ? a.vals + s0 * G : nullptr;
-   const unsigned ldyb = (unsigned)a.ldy * 4u;
-   const unsigned pad_word = ((unsigned)NVMAX << 24) | a.null_word;      // past the end of the wave: the spare row too
-   auto load_words = [&](int64_t first, unsigned (&word)[NBW]) {
-#pragma unroll
-      for (int q = 0; q < NBW; q++) {
-         const int64_t i = first + q * 64 + lane;
-         word[q] = i < nwords ? (unsigned)wp[i] : pad_word;
-      }
-   };
-   auto load_vals = [&](int64_t first, float (&val)[NBW]) {
-#pragma unroll
-      for (int q = 0; q < NBW; q++) {
-         const int64_t i = first + q * 64 + lane;
-         val[q] = HAS_VAL && i < nwords ? vp[i] : 0.0f;
-      }
-   };
-   const int g4 = g * 4;                                  // byte address of lane g for ds_bpermute
+   const unsigned cbyte = sw.cok ? sw.cbyte : 0x80000000u;
+   float *lane_base = my + sw.lc * 4;                     // a lane's four values of a row ...
+   int *lane_idx = reinterpret_cast<int *>(my + IDX0) + sw.lc * 4;   // ... and their indices
+   stream_bounds(a, sw);
+   const float *vp = HAS_VAL ? a.vals + sw.s0 * G : nullptr;
+   const unsigned pad_word = stream_pad_spare_row(a, sw);     // past the end of the wave: the spare row too
+   const int g4 = sw.g * 4;                               // byte address of lane g for ds_bpermute
    unsigned w1[NBW], w2[NBW];
-   float v0[NBW], v1[NBW];                               // the weights of the batch being consumed and of the next: a weight is
+   float v0[NBW] = {}, v1[NBW] = {};                     // the weights of the batch being consumed and of the next: a weight is
                                                          // needed one batch later than its word, so it is loaded one batch later
    v4i_t t[U];
    unsigned la[U];
@@ -274,19 +204,19 @@ __global__ __launch_bounds__(256, (stream_wgs_per_cu<LPR, 2 * (NVMAX + 1), WGS>(
    // la[u] keeps the WORD of step u as it is: its top byte, the local row, is compared byte against byte when the gather is
    // consumed (one SDWA compare) and only becomes an LDS offset inside the rare change of row -- no shift per step
    auto issue = [&](int u, unsigned word) {
-      const unsigned o = __umul24(word, ldyb) + cbyte;
+      const unsigned o = __umul24(word, sw.ldyb) + cbyte;
       la[u] = word;
       t[u] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)o, 0, 0);
    };
-   load_words(0, w1);
-   load_vals(0, v0);
+   stream_load_batch(sw, sw.wp, 0, pad_word, w1);
+   if (HAS_VAL) stream_load_batch(sw, vp, 0, 0.0f, v0);
 #pragma unroll
    for (int u = 0; u < U; u++) issue(u, fetch(u, w1));
-   load_words(64 * NBW, w1);
-   load_vals(64 * NBW, v1);
-   load_words(128 * NBW, w2);
-   unsigned cur = (unsigned)(g * PER * PANEL);            // LDS offset of the row the registers hold ...
-   unsigned curw = (unsigned)(g * PER) << 24;             // ... and that row as the top byte of a word
+   stream_load_batch(sw, sw.wp, 64 * NBW, pad_word, w1);
+   if (HAS_VAL) stream_load_batch(sw, vp, 64 * NBW, 0.0f, v1);
+   stream_load_batch(sw, sw.wp, 128 * NBW, pad_word, w2);
+   unsigned cur = (unsigned)(sw.g * PER * PANEL);         // LDS offset of the row the registers hold ...
+   unsigned curw = (unsigned)(sw.g * PER) << 24;          // ... and that row as the top byte of a word
    float acc[4];
    int bi[4];
 #pragma unroll
@@ -311,9 +241,9 @@ __global__ __launch_bounds__(256, (stream_wgs_per_cu<LPR, 2 * (NVMAX + 1), WGS>(
       acc[0] = o.x; acc[1] = o.y; acc[2] = o.z; acc[3] = o.w;
       cur = nxt;
    };
-   const int64_t nb = (nwords + 64 * NBW - 1) / (64 * NBW);
+   const int64_t nb = (sw.nwords + 64 * NBW - 1) / (64 * NBW);
    for (int64_t b = 0; b < nb; b++) {
-      const int widx0 = (int)(b * (64 * NBW)) + g;        // word index of this lane's slot at step 0 of the batch
+      const int widx0 = (int)(b * (64 * NBW)) + sw.g;        // word index of this lane's slot at step 0 of the batch
       float vnext = HAS_VAL ? __int_as_float(__builtin_amdgcn_ds_bpermute(g4, __float_as_int(v0[0]))) : 0.0f;
       // the word of the gather that REPLACES step u's is fetched one step ahead: the cross-lane read then has a whole step
       // (the row check and the compares) to land instead of being waited for straight away
@@ -350,22 +280,22 @@ __global__ __launch_bounds__(256, (stream_wgs_per_cu<LPR, 2 * (NVMAX + 1), WGS>(
       }
 #pragma unroll
       for (int q = 0; q < NBW; q++) { w1[q] = w2[q]; v0[q] = v1[q]; }
-      load_words((b + 3) * 64 * NBW, w2);
-      load_vals((b + 2) * 64 * NBW, v1);
+      stream_load_batch(sw, sw.wp, (b + 3) * 64 * NBW, pad_word, w2);
+      if (HAS_VAL) stream_load_batch(sw, vp, (b + 2) * 64 * NBW, 0.0f, v1);
    }
    *reinterpret_cast<float4 *>(lane_base + cur) = make_float4(acc[0], acc[1], acc[2], acc[3]);
    if (ARG) *reinterpret_cast<int4 *>(lane_idx + cur) = make_int4(bi[0], bi[1], bi[2], bi[3]);
    // write-out, ALL rows of the slot at once: the winners' word indices become CSR positions through the plan's permutation --
    // four dependent loads per row and lane, which a row-at-a-time loop waits for PER times over (the gather registers are free
    // by now: every load of the slot's PER rows is in flight before the first one is needed)
-   const int32_t *ids = a.ids + s0 * G;
+   const int32_t *ids = a.ids + sw.s0 * G;
    int row_[PER], part_[PER], best_[PER][4];
    float val_[PER][4];
 #pragma unroll
    for (int jj = 0; jj < PER; jj++) {
-      const int lrow = g * PER + jj;
-      row_[jj] = cok ? a.wave_row[(size_t)w * NVMAX + lrow] : -1;
-      part_[jj] = a.wave_part[(size_t)w * NVMAX + lrow];
+      const int lrow = sw.g * PER + jj;
+      row_[jj] = sw.cok ? a.wave_row[(size_t)sw.w * NVMAX + lrow] : -1;
+      part_[jj] = a.wave_part[(size_t)sw.w * NVMAX + lrow];
       const float4 t4 = *reinterpret_cast<const float4 *>(lane_base + lrow * PANEL);
       val_[jj][0] = t4.x; val_[jj][1] = t4.y; val_[jj][2] = t4.z; val_[jj][3] = t4.w;
       if constexpr (ARG) {
@@ -380,29 +310,29 @@ __global__ __launch_bounds__(256, (stream_wgs_per_cu<LPR, 2 * (NVMAX + 1), WGS>(
       for (int jj = 0; jj < PER; jj++)
 #pragma unroll
          for (int i = 0; i < 4; i++)   // (a word index outside the wave's stream -- INT_MAX = no winner -- never reaches the subscript)
-            best_[jj][i] = (row_[jj] >= 0 && (unsigned)best_[jj][i] < (unsigned)nwords) ? ids[best_[jj][i]] : INT_MAX;
+            best_[jj][i] = (row_[jj] >= 0 && (unsigned)best_[jj][i] < (unsigned)sw.nwords) ? ids[best_[jj][i]] : INT_MAX;
    }
 #pragma unroll
    for (int jj = 0; jj < PER; jj++) {
       const int row = row_[jj];
       if (row < 0) continue;
-      const int c = ccol;
+      const int c = sw.ccol;
       if (part_[jj] >= 0) {
          const size_t po = (size_t)part_[jj] * (size_t)a.k + c;
-         store_tail<4>(a.part_val + po, val_[jj], vfirst);
+         store_tail<4>(a.part_val + po, val_[jj], sw.vfirst);
          if constexpr (ARG) {
 #pragma unroll
-            for (int i = 0; i < 4; i++) if (i >= vfirst) a.part_idx[po + i] = best_[jj][i];
+            for (int i = 0; i < 4; i++) if (i >= sw.vfirst) a.part_idx[po + i] = best_[jj][i];
          }
          continue;
       }
       int64_t arg[4];
       finish_row<OP>(a, row, c, val_[jj], best_[jj], arg);
-      store_tail<4>(a.z + (size_t)row * (size_t)a.ldz + c, val_[jj], vfirst);
+      store_tail<4>(a.z + (size_t)row * (size_t)a.ldz + c, val_[jj], sw.vfirst);
       if (a.z_arg) {
          int64_t *ar = a.z_arg + (size_t)row * (size_t)a.ldz + c;
 #pragma unroll
-         for (int i = 0; i < 4; i++) if (i >= vfirst) ar[i] = arg[i];
+         for (int i = 0; i < 4; i++) if (i >= sw.vfirst) ar[i] = arg[i];
       }
    }
 }
@@ -435,9 +365,11 @@ template <int OP, bool HAS_VAL>
 static int launch_stream_minmax(const SweepArgs &a, hipStream_t st, int streams) {
    const unsigned blocks = (unsigned)((a.wave_count + 3) / 4);
    if (blocks == 0) return ISPLIB_SUCCESS;
-   if (a.z_arg) streams == 8 ? launch_minmax_kernel<OP, 8, HAS_VAL, true>(a, blocks, st) : launch_minmax_kernel<OP, 4, HAS_VAL, true>(a, blocks, st);
-   else streams == 8 ? launch_minmax_kernel<OP, 8, HAS_VAL, false>(a, blocks, st) : launch_minmax_kernel<OP, 4, HAS_VAL, false>(a, blocks, st);      // values only
-   return check_launch("spmm_stream_minmax_kernel");
+   return with_streams<STREAM_MINMAX>(streams, [&](auto s) {
+      if (a.z_arg) launch_minmax_kernel<OP, s(), HAS_VAL, true>(a, blocks, st);
+      else launch_minmax_kernel<OP, s(), HAS_VAL, false>(a, blocks, st);      // values only
+      return check_launch("spmm_stream_minmax_kernel");
+   });
 }
 
 }  // namespace isplib
@@ -548,9 +480,7 @@ static int stream_run(int32_t imessage, int64_t m, int64_t n, int64_t k, int64_t
       [&](const SweepArgs &p) {
          if (imessage == ISPLIB_MSG_SPMM_MAX) return has_val ? launch_stream_minmax<OP_MAX, true>(p, st, plan->streams) : launch_stream_minmax<OP_MAX, false>(p, st, plan->streams);
          if (imessage == ISPLIB_MSG_SPMM_MIN) return has_val ? launch_stream_minmax<OP_MIN, true>(p, st, plan->streams) : launch_stream_minmax<OP_MIN, false>(p, st, plan->streams);
-         if (plan->streams == 2) return has_val ? launch_stream<2, true>(p, st) : launch_stream<2, false>(p, st);
-         if (plan->streams == 4) return has_val ? launch_stream<4, true>(p, st) : launch_stream<4, false>(p, st);
-         return has_val ? launch_stream<8, true>(p, st) : launch_stream<8, false>(p, st);
+         return with_streams<STREAM_SUM>(plan->streams, [&](auto s) { return has_val ? launch_stream<s(), true>(p, st) : launch_stream<s(), false>(p, st); });
       },
       [&](const SweepArgs &p) {
          return imessage == ISPLIB_MSG_SPMM_MAX ? launch_hub_fold<OP_MAX, true>(p, st)

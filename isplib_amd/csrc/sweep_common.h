@@ -1,5 +1,5 @@
 // sweep_common.h -- what the kernels of the row-resident schedules share: the launch arguments, the finish of a row, the
-// fold of hub rows' partial rows and the compile-time geometry.  Included by spmm_sweep.hip (the stream schedule: the
+// fold of hub rows' partial rows, the device side of the stream front end, the compile-time geometry and the entries' host side.  Included by spmm_sweep.hip (the stream schedule: the
 // default of sum / mean / max / min), fusedmm_stream.hip (the generic FusedMM words on the same front end) and
 // experimental/experimental.hip (the sweep, hybrid and stream-SDDMM forms: measured, slower, kept out of the default library).
 #pragma once
@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include <float.h>
 #include <limits.h>
+#include <type_traits>
 
 #include "../../include/isplib_hip.h"
 #include "common.h"
@@ -135,38 +136,39 @@ struct SweepArgs {
    int ep_relu;
 };
 
-// finished value of a whole row: mean scale / epilogue (sum, mean), empty-row value and absolute arg (max, min)
-template <int OP>
-__device__ __forceinline__ void finish_row(const SweepArgs &a, int row, int c, float (&v)[4], int (&bi)[4], int64_t (&arg)[4]) {
+// finished value of a whole row: mean scale / epilogue (sum, mean), empty-row value and absolute arg (max, min),
+// of the VEC columns from c on (4 everywhere but in the single-column hub fold)
+template <int OP, int VEC>
+__device__ __forceinline__ void finish_row(const SweepArgs &a, int row, int c, float (&v)[VEC], int (&bi)[VEC], int64_t (&arg)[VEC]) {
    const int64_t rb = a.pntrb[row];
    const int64_t deg = a.pntre[row] - rb;
    if (OP == OP_ADD) {
       if (a.mean) {
          const float d = (float)(deg > 1 ? deg : 1);
 #pragma unroll
-         for (int i = 0; i < 4; i++) v[i] = v[i] / d;
+         for (int i = 0; i < VEC; i++) v[i] = v[i] / d;
       }
       if (a.ep_self) {
          const float *sr = a.ep_self + (size_t)row * (size_t)a.ep_ld_self + c;
 #pragma unroll
-         for (int i = 0; i < 4; i++) v[i] += sr[i];
+         for (int i = 0; i < VEC; i++) v[i] += sr[i];
       }
       if (a.ep_row_scale) {
          const float rs = a.ep_row_scale[row];
 #pragma unroll
-         for (int i = 0; i < 4; i++) v[i] *= rs;
+         for (int i = 0; i < VEC; i++) v[i] *= rs;
       }
       if (a.ep_bias) {
 #pragma unroll
-         for (int i = 0; i < 4; i++) v[i] += a.ep_bias[c + i];
+         for (int i = 0; i < VEC; i++) v[i] += a.ep_bias[c + i];
       }
       if (a.ep_relu) {
 #pragma unroll
-         for (int i = 0; i < 4; i++) v[i] = v[i] > 0.0f ? v[i] : 0.0f;
+         for (int i = 0; i < VEC; i++) v[i] = v[i] > 0.0f ? v[i] : 0.0f;
       }
    } else {
 #pragma unroll
-      for (int i = 0; i < 4; i++) {
+      for (int i = 0; i < VEC; i++) {
          if (deg <= 0) v[i] = a.empty_init ? identity<OP>() : 0.0f;
          arg[i] = bi[i] == INT_MAX ? a.nnz : (a.abs_ids ? (int64_t)bi[i] : rb + (int64_t)bi[i]);
       }
@@ -183,10 +185,10 @@ __global__ __launch_bounds__(256) void sweep_hub_fold_kernel(const SweepArgs a) 
    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
       const int64_t h = i / kv;
       const int c = (int)(i - h * kv) * VEC;
-      float v[4];
-      int bi[4];
+      float v[VEC];
+      int bi[VEC];
 #pragma unroll
-      for (int q = 0; q < 4; q++) { v[q] = identity<OP>(); bi[q] = INT_MAX; }
+      for (int q = 0; q < VEC; q++) { v[q] = identity<OP>(); bi[q] = INT_MAX; }
       const int p1 = a.hub_off[h + 1];
       for (int p = a.hub_off[h]; p < p1; p++) {
          const size_t po = (size_t)p * (size_t)a.k + c;
@@ -207,24 +209,9 @@ __global__ __launch_bounds__(256) void sweep_hub_fold_kernel(const SweepArgs a) 
          }
       }
       const int row = a.hub_row[h];
-      int64_t arg[4];
-      if (VEC == 4) {
-         finish_row<OP>(a, row, c, v, bi, arg);
-         store_vec<4>(a.z + (size_t)row * (size_t)a.ldz + c, v);
-      } else {                                             // one column: the row finish reads four, so do it by hand
-         const int64_t rb = a.pntrb[row], deg = a.pntre[row] - rb;
-         if (OP == OP_ADD) {
-            if (a.mean) v[0] = v[0] / (float)(deg > 1 ? deg : 1);
-            if (a.ep_self) v[0] += a.ep_self[(size_t)row * (size_t)a.ep_ld_self + c];
-            if (a.ep_row_scale) v[0] *= a.ep_row_scale[row];
-            if (a.ep_bias) v[0] += a.ep_bias[c];
-            if (a.ep_relu) v[0] = v[0] > 0.0f ? v[0] : 0.0f;
-         } else {
-            if (deg <= 0) v[0] = a.empty_init ? identity<OP>() : 0.0f;
-            arg[0] = bi[0] == INT_MAX ? a.nnz : (a.abs_ids ? (int64_t)bi[0] : rb + (int64_t)bi[0]);
-         }
-         a.z[(size_t)row * (size_t)a.ldz + c] = v[0];
-      }
+      int64_t arg[VEC];
+      finish_row<OP, VEC>(a, row, c, v, bi, arg);
+      store_vec<VEC>(a.z + (size_t)row * (size_t)a.ldz + c, v);
       if (OP != OP_ADD && a.z_arg) {
          int64_t *ar = a.z_arg + (size_t)row * (size_t)a.ldz + c;
 #pragma unroll
@@ -232,6 +219,111 @@ __global__ __launch_bounds__(256) void sweep_hub_fold_kernel(const SweepArgs a) 
       }
    }
 }
+
+// ---- device side of a kernel on the stream front end ----------------------------------------------------
+// What the stream kernels share: who a wave is, which columns a lane holds, the wave's word stream, the batch registers and the
+// gathers in flight.  What a kernel does with a gathered row -- its loop body -- is the kernel's own.
+// The position of a wave: G = 64 / LPR row slots of LPR lanes x 4 floats (one panel row each); a batch is NBW registers of 64
+// words = U steps, a step is one word per slot = one full 1-KiB gather; slot q owns the local rows [q * PER, (q + 1) * PER).
+template <int LPR_, int NVMAX_, int NBW_, int WAVES_ = 4>
+struct StreamWave {
+   static constexpr int LPR = LPR_, NVMAX = NVMAX_, NBW = NBW_, WAVES = WAVES_;
+   static constexpr int G = 64 / LPR, PANEL = LPR * 4, U = 64 * NBW / G, PER = NVMAX / G;
+   int lane, wave, g, lc;             // lane of the wave; wave of the workgroup (uniform); slot; lane of the slot
+   int wl;                            // the wave's index in the launch ...
+   int64_t w;                         // ... and in the plan
+   bool cok;                          // the lane holds columns of the panel
+   int ccol, vfirst;                  // the first of its four; leading components of its vector that are the neighbour's
+   unsigned cbyte, poison;            // column term of a gather's byte offset; what throws the offset out of range
+   int64_t s0, nwords;                // first step and number of words of the wave's stream
+   const int32_t *wp;                 // the stream
+   unsigned ldyb;                     // row pitch of y in bytes
+};
+
+// who the wave is; false: past the last wave of the launch (a kernel without barriers returns)
+template <class SW> __device__ __forceinline__ bool stream_wave_id(const SweepArgs &a, SW &sw) {
+   sw.lane = threadIdx.x & 63;
+   sw.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+   sw.g = sw.lane / SW::LPR;
+   sw.lc = sw.lane % SW::LPR;
+   sw.wl = (int)blockIdx.x * SW::WAVES + sw.wave;
+   sw.w = (int64_t)a.wave_base + sw.wl;
+   return sw.wl < a.wave_count;
+}
+
+// a lane holds columns lc*4 .. lc*4+3 of the panel; when k is not a multiple of 4 (RAGGED: the entry admits that) the last
+// lane's vector is shifted back to END at column k (its first `vfirst` components repeat the neighbour's columns and are never
+// stored), so no load reaches past a row and rows need only 4-byte alignment (the GCN's K = 41 runs here instead of the task
+// list).  Lanes beyond column k gather nothing: `poison` is OR-ed into their offsets
+template <bool RAGGED, class SW> __device__ __forceinline__ void stream_columns(const SweepArgs &a, SW &sw) {
+   sw.cok = sw.lc * 4 < a.k;
+   sw.ccol = sw.lc * 4;
+   sw.vfirst = 0;
+   if (RAGGED && sw.cok && sw.ccol + 4 > (int)a.k) { sw.vfirst = sw.ccol + 4 - (int)a.k; sw.ccol = (int)a.k - 4; }
+   sw.cbyte = (unsigned)sw.ccol * 4u;
+   sw.poison = sw.cok ? 0u : BUF_OOB;
+}
+
+// the wave's stream: steps [s0, s1) of G words each
+template <class SW> __device__ __forceinline__ void stream_bounds(const SweepArgs &a, SW &sw) {
+   sw.s0 = a.wave_step_off[sw.w];
+   const int64_t s1 = a.wave_step_off[sw.w + 1];
+   sw.nwords = (s1 - sw.s0) * SW::G;
+   sw.wp = a.words + sw.s0 * SW::G;
+   sw.ldyb = (unsigned)a.ldy * 4u;
+}
+
+// the word past the end of a wave's stream, and of the plan's padding: column n (the gather reads 0 through the range check) in
+// one of the slot's own rows (to which 0 is added), or in the spare row NVMAX of the plans whose kernels keep one (max / min,
+// where 0 would beat negative values; FusedMM)
+template <class SW> __device__ __forceinline__ unsigned stream_pad_own_row(const SweepArgs &a, const SW &sw) {
+   return ((unsigned)((sw.lane % SW::G) * SW::PER) << 24) | a.null_word;
+}
+template <class SW> __device__ __forceinline__ unsigned stream_pad_spare_row(const SweepArgs &a, const SW &) {
+   return ((unsigned)SW::NVMAX << 24) | a.null_word;
+}
+
+// one batch of a per-word array of the wave (src: its first element -- words, weights, CSR positions): lane i of batch register
+// q holds element first + q*64 + i = (step (q*64 + i) / G, slot i % G); past the end of the wave: pad.
+// Three batches of words are on the way at any time: while batch b is consumed, every gather taken is replaced by the same step
+// of batch b + 1 (the kernels' w1); w2 holds the words of batch b + 2, loaded a whole batch before the first of them is handed
+// out.  What is needed only when a gather is CONSUMED (the weights; the SDDMM's CSR positions) is needed one batch later than its
+// word, so it is loaded one batch later.  (The order of these loads stays spelled out in each kernel: it decides the register
+// allocation of the whole loop -- the weighted 128-column sum kernel went from 226 registers to 256 and four spills with the
+// weights of batches 0 and 1 loaded after the words of batch 2 instead of beside their own.)
+template <class SW, class S, class T>
+__device__ __forceinline__ void stream_load_batch(const SW &sw, const S *src, int64_t first, T pad, T (&reg)[SW::NBW]) {
+#pragma unroll
+   for (int q = 0; q < SW::NBW; q++) {
+      const int64_t i = first + q * 64 + sw.lane;
+      reg[q] = i < sw.nwords ? (T)src[i] : pad;
+   }
+}
+
+// the gather of step u of a batch.  One cross-lane read (ds_bpermute) hands a slot its word of the step (the LDS pipe is otherwise
+// idle; picking it with v_readlane + v_cndmask cost 16 vector instructions per step); column * row pitch is a 24-bit multiply
+// (n < 2^24, pitch < 2^24, product < 2^32: checked by the entry).  la: the LDS offset of the word's local row.  AUX: cache-policy
+// bits of the load (ISPLIB_EXP_GATHER_AUX)
+template <int AUX, class SW>
+__device__ __forceinline__ void stream_issue(const SW &sw, __amdgpu_buffer_rsrc_t rsrc, const unsigned (&word_l)[SW::NBW], int u, unsigned &la, v4i_t &t) {
+   const unsigned word = (unsigned)__shfl((int)word_l[(u * SW::G) / 64], (u * SW::G) % 64 + sw.g);
+   const unsigned o = (__umul24(word & 0xFFFFFFu, sw.ldyb) + sw.cbyte) | sw.poison;
+   la = (word >> 24) * (unsigned)SW::PANEL;
+   t = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)o, 0, AUX);
+}
+
+// The row a slot is working on keeps its running sum in registers; it moves to the slot's LDS row when the stream turns to
+// another row (every ~deg / slices edges) and is picked up again from there when the stream comes back in the next slice.
+// Plain read-add-write by the only lanes that ever touch that LDS row: LDS float atomics (one ds_add_f32 per gathered
+// float) ran 25x slower than the gathers they were meant to keep up with.
+__device__ __forceinline__ void stream_flush(float *lds_row, const float (&acc)[4]) {
+   float4 *p = reinterpret_cast<float4 *>(lds_row);
+   float4 o = *p;
+   o.x += acc[0]; o.y += acc[1]; o.z += acc[2]; o.w += acc[3];
+   *p = o;
+}
+// (The fetch of a slot's row ids ahead of the write-out stays in each kernel too: as a function its loads are merged and speculated
+// -- the 144 global_load_dword of the six sum kernels become 48 wider ones -- at two more SGPRs in every one of them.)
 
 // Geometry of the stream kernels.  Persistent waves only stay on the same column slices while FEW of them share a SIMD:
 // a SIMD's memory instructions go to its oldest ready wave first, so with 8 waves per SIMD the waves of a CU finish
@@ -266,6 +358,20 @@ constexpr StreamGeom STREAM_GEOMS[STREAM_FAMILIES][3] = {      // [family][strea
 };
 constexpr bool stream_count_ok(int streams) { return streams == 2 || streams == 4 || streams == 8; }
 constexpr StreamGeom stream_geom(int family, int streams) { return STREAM_GEOMS[family][streams == 2 ? 0 : (streams == 4 ? 1 : 2)]; }
+
+// a plan's `streams` as a template argument: f(std::integral_constant<int, streams>()), the launcher of a family's kernel for
+// that slot width.  Only the widths the family has a kernel for are instantiated (the entries refuse a plan of any other width
+// before anything is launched: check_stream_call)
+template <int FAMILY, class F>
+static inline int with_streams(int streams, F f) {
+   if constexpr (stream_geom(FAMILY, 2).nvmax != 0) {
+      if (streams == 2) return f(std::integral_constant<int, 2>());
+   }
+   if constexpr (stream_geom(FAMILY, 4).nvmax != 0) {
+      if (streams == 4) return f(std::integral_constant<int, 4>());
+   }
+   return f(std::integral_constant<int, 8>());
+}
 
 // LDS of a workgroup (4 waves x rows x one panel row of LPR lanes x 4 floats), the workgroups of a CU that its 160 KB and
 // the geometry's cap admit -- the kernels' launch bound -- and the waves of a launch that are resident together
