@@ -69,6 +69,73 @@ def weights(nnz, seed, kind="uniform"):
     raise ValueError(kind)
 
 
+# ---- inputs whose STREAM PLAN is known (tests/test_host.py proves it on the CPU; tests/test_gpu_stream_edges.py runs them) ----
+
+# Steps per wave of the ladder graph.  A batch of every stream kernel is U = 64 * NBW / G steps, and that is 32 for every row of
+# STREAM_GEOMS (isplib_amd/csrc/sweep_common.h: G = streams = 64 / lpr slots, NBW = G / 2 batch registers).  Three batches of words
+# are in flight and the weights trail the words by one batch, so the loop can go wrong at every multiple of 32 up to four batches
+# and one step either side of it: those are here, with the multiples of 16 (should a geometry macro halve U), 0-5 for the FusedMM
+# kernel's groups of four steps, and a wave of no steps at all.
+LADDER = (161, 129, 128, 127, 97, 96, 95, 65, 64, 63, 33, 32, 31, 17, 16, 15, 5, 4, 3, 2, 1, 0)
+
+
+def csr_of_degrees(deg, n, seed):
+    """CSR whose row i has deg[i] edges over n columns: columns ascend within a row, and every row of two or more edges holds a
+    duplicate (legal: duplicates add, and tie in max / min)."""
+    rng = np.random.default_rng(seed)
+    deg = np.asarray(deg, np.int64)
+    rowptr = np.zeros(deg.size + 1, np.int64)
+    np.cumsum(deg, out=rowptr[1:])
+    col = rng.integers(0, n, rowptr[-1]).astype(np.int64)
+    for r in range(deg.size):
+        b, e = rowptr[r], rowptr[r + 1]
+        if e - b >= 2:
+            col[b + 1] = col[b]
+        col[b:e] = np.sort(col[b:e], kind="stable")
+    return rowptr, col
+
+
+def stream_ladder(streams, lengths=LADDER, n=97, seed=0):
+    """len(lengths) * streams rows; row w * streams + s has lengths[w] edges (`lengths` descending).  The plan's deal is longest
+    first and stable, one row per stream in the first round: with waves_per_gen = len(lengths), one generation and `chunk` above
+    lengths[0], stream i gets row i, so wave w walks exactly lengths[w] steps and no word of it is padding."""
+    assert list(lengths) == sorted(lengths, reverse=True)
+    return csr_of_degrees(np.repeat(np.asarray(lengths, np.int64), streams), n, seed)
+
+
+def stream_uneven_wave(streams, length, n=97, seed=0):
+    """One wave (waves_per_gen = 1): `streams` rows of length, length // 2, 1, 0, 0, ... edges.  The wave walks `length` steps, and
+    in all slots but the first most of them are padding words."""
+    deg = ([length, length // 2, 1] + [0] * streams)[:streams]
+    return csr_of_degrees(deg, n, seed)
+
+
+def stream_shape_cases(rows_per_wave=64):
+    """Small graphs at the edges of the plan's SHAPE: [(name, rowptr, col, n, (slices, waves_per_gen, streams, chunk))].
+    `rows_per_wave`: that of the kernel family the plans are built for at 4 streams (sum / mean 64, max / min 32); the two
+    `full_gen` cases are cut to it."""
+    rpw, chunk = int(rows_per_wave), 64
+    out = []
+
+    def add(name, deg, n, geom, seed=1):
+        rowptr, col = csr_of_degrees(deg, n, seed)
+        out.append((name, rowptr, col, n, geom))
+    add("one_row_empty", [0], 1, (1, 1, 4, chunk))
+    add("one_row_one_edge", [1], 1, (1, 1, 4, chunk))
+    add("one_row_hub", [200], 1, (1, 1, 4, chunk))                          # nothing but one hub row: 4 parts of 50 edges
+    add("all_empty", [0, 0, 0], 2, (2, 2, 4, chunk))
+    add("n_below_slices", np.random.default_rng(2).poisson(5.0, 40), 3, (16, 2, 4, chunk))
+    add("hub_threshold", [chunk - 1, chunk, chunk + 1, 2 * chunk, 2 * chunk + 1], 50, (3, 2, 4, chunk))
+    add("hubs_first_and_last", [150, 3, 0, 7, 1, 9, 2, 130], 50, (3, 2, 4, chunk))
+    add("hubs_adjacent", [4, 0, 140, 190, 6, 2], 50, (3, 2, 4, chunk))
+    add("every_row_a_hub", [65, 200, 129, 70], 50, (3, 2, 4, chunk))
+    full = np.random.default_rng(3).integers(0, 9, 2 * rpw + 1)             # no hubs; empty rows among them
+    add("full_gen", full[:-1], 50, (3, 2, 4, chunk))                        # m = waves_per_gen * rows_per_wave: one generation
+    add("full_gen_plus_one", full, 50, (3, 2, 4, chunk))                    # ... and one more row: a second generation of one row
+    add("m_below_streams", [5, 0, 3], 20, (2, 2, 8, chunk))
+    return out
+
+
 # the two inputs in the reference tree with derivable answers (SURVEY.md 8c.4)
 def readme_case():
     """README.md:105-116 -- COO with a duplicate (0,0); CSR in stable torch_sparse order."""

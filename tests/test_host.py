@@ -1306,3 +1306,118 @@ def test_fusedmm_wrappers_refuse_misshaped_operands_before_any_library_call(monk
         with pytest.raises(LibraryCalled):                                      # well-shaped: on to the schedule rule
             isplib_amd.fusedmm(adj, x, y, pattern)
     assert not cabi.reads_x(cabi.MSG_SPMM_SUM) and all(cabi.reads_x(w) for w in (sig, tdist, cabi.VOP["add"] | cabi.AOP["max"]))
+
+
+# ---- the constructors of tests/cases.py whose stream plan is known: what tests/test_gpu_stream_edges.py relies on --------
+
+def _stream_families():
+    """[(family, streams, rows per wave)] from the library's geometry entries (they answer without a device)."""
+    from isplib_amd import cabi
+    fams = []
+    for family, fn, widths in (("sum", cabi.stream_geometry, (2, 4, 8)), ("minmax", cabi.stream_minmax_geometry, (4, 8)),
+                               ("fusedmm", cabi.fusedmm_stream_geometry, (2, 4, 8))):
+        fams += [(family, streams, fn(streams)[0]) for streams in widths]
+    return fams
+
+
+def _plan_of(rowptr, col, n, slices, wpg, rpw, streams, chunk, family):
+    from isplib_amd.plan import stream_plan_arrays
+    return stream_plan_arrays(torch.from_numpy(rowptr), torch.from_numpy(col), n, slices, wpg, rpw, streams, chunk,
+                              pad_row=rpw if family != "sum" else None)
+
+
+def test_stream_ladder_gives_every_wave_the_steps_it_names():
+    """cases.stream_ladder: with waves_per_gen = len(LADDER), one generation and no hub row, wave w of the plan walks exactly
+    LADDER[w] steps, none of them padding, whatever the family, the slot width and the slice count -- and LADDER holds every
+    multiple of the batch length up to four batches with both neighbours, 0-5 and a wave of no steps."""
+    assert [(f, s, r) for f, s, r in _stream_families()] == [("sum", 2, 32), ("sum", 4, 64), ("sum", 8, 128), ("minmax", 4, 32), ("minmax", 8, 64),
+                                                             ("fusedmm", 2, 16), ("fusedmm", 4, 32), ("fusedmm", 8, 64)]
+    lad = cases.LADDER
+    assert list(lad) == sorted(lad, reverse=True) and lad[-1] == 0
+    for b in (32, 64, 96, 128):
+        assert {b - 1, b, b + 1} <= set(lad)
+    assert {0, 1, 2, 3, 4, 5, 15, 16, 17} <= set(lad) and max(lad) > 4 * 32 + 32
+    for family, streams, rpw in _stream_families():
+        rowptr, col = cases.stream_ladder(streams)
+        deg = np.diff(rowptr)
+        assert rowptr.size - 1 == len(lad) * streams and np.array_equal(deg, np.repeat(lad, streams))
+        for r in range(deg.size):
+            c = col[rowptr[r]:rowptr[r + 1]]
+            assert np.all(np.diff(c) >= 0) and (c.size < 2 or np.any(np.diff(c) == 0)), "columns ascend and hold a duplicate"
+        for slices in (1, 3):
+            p = _plan_of(rowptr, col, 97, slices, len(lad), rpw, streams, 256, family)
+            assert p["gens"] == 1 and p["n_hub"] == 0 and p["n_parts"] == 0, (family, streams)
+            assert np.array_equal(np.diff(p["wave_step_off"].numpy()), lad), (family, streams)
+            assert int((p["perm"] < 0).sum()) == 0 and p["n_steps"] == sum(lad)
+            wr = p["wave_row"].numpy().reshape(len(lad), rpw)
+            per = rpw // streams
+            assert np.array_equal(wr[:, ::per].ravel(), np.arange(deg.size)), "stream i holds row i"
+
+
+@pytest.mark.parametrize("length", (1, 31, 32, 33, 64, 97))
+def test_stream_uneven_wave_is_one_wave_of_that_many_steps_mostly_padding(length):
+    for family, streams, rpw in _stream_families():
+        rowptr, col = cases.stream_uneven_wave(streams, length)
+        assert rowptr.size - 1 == streams
+        p = _plan_of(rowptr, col, 97, 2, 1, rpw, streams, 256, family)
+        assert p["gens"] == 1 and p["n_hub"] == 0
+        assert np.array_equal(p["wave_step_off"].numpy(), [0, length]), (family, streams)
+        nnz = length + length // 2 + (1 if streams > 2 else 0)
+        assert col.size == nnz and int((p["perm"] < 0).sum()) == streams * length - nnz
+        words = p["words"].numpy().astype(np.int64) & 0xFFFFFFFF
+        pad = p["perm"].numpy() < 0
+        assert np.all((words[pad] & 0xFFFFFF) == 97)
+        if family != "sum":
+            assert np.all((words[pad] >> 24) == rpw), "max / min and FusedMM plans pad with the spare row"
+
+
+def test_stream_shape_cases_have_the_plan_shapes_they_are_named_for():
+    """cases.stream_shape_cases on the sum / mean and the max / min geometry: hubs, parts and generations follow from the degrees
+    (a row over `chunk` edges is a hub of ceil(deg / chunk) parts; a generation holds waves_per_gen * rows_per_wave virtual
+    rows), the step counts of the recorded cases are the recorded ones, and every plan lists every edge once."""
+    from isplib_amd import cabi
+    steps = {"one_row_empty": 0, "one_row_one_edge": 1, "one_row_hub": 50, "all_empty": 0, "hub_threshold": 129}
+    for family, geometry in (("sum", cabi.stream_geometry), ("minmax", cabi.stream_minmax_geometry)):
+        shapes = cases.stream_shape_cases(geometry(4)[0])
+        assert len({c[0] for c in shapes}) == len(shapes) == 12
+        seen = {}
+        for name, rowptr, col, n, (slices, wpg, streams, chunk) in shapes:
+            rpw = geometry(streams)[0]
+            m, deg = rowptr.size - 1, np.diff(rowptr)
+            p = _plan_of(rowptr, col, n, slices, wpg, rpw, streams, chunk, family)
+            parts = -(-deg // chunk)
+            nv = int(np.maximum(parts, 1).sum())
+            want = dict(n_hub=int((deg > chunk).sum()), n_parts=int(parts[deg > chunk].sum()), gens=max(1, -(-nv // (wpg * rpw))))
+            assert {key: p[key] for key in want} == want, (family, name)
+            if name in steps:
+                assert p["n_steps"] == steps[name], (family, name)
+            perm = p["perm"].numpy()
+            assert np.array_equal(np.sort(perm[perm >= 0]), np.arange(col.size)), (family, name)
+            assert p["n_steps"] == int(p["wave_step_off"][-1]) and perm.size == p["n_steps"] * streams
+            wr, wp = p["wave_row"].numpy(), p["wave_part"].numpy()
+            assert np.array_equal(np.sort(wr[wr >= 0]), np.repeat(np.arange(m), np.maximum(parts, 1)))
+            assert np.array_equal(np.sort(wp[wp >= 0]), np.arange(want["n_parts"])) and np.all(wp[wr < 0] < 0)
+            assert int(p["hub_off"][-1]) == want["n_parts"] and p["hub_off"].numel() == want["n_hub"] + 1
+            seen[name] = (m, n, deg, p, want, slices, wpg, streams, rpw)
+        m, n, deg, p, want, *_ = seen["one_row_hub"]
+        assert (m, n, want["n_hub"], want["n_parts"]) == (1, 1, 1, 4)
+        assert seen["all_empty"][3]["words"].numel() == 0, "the Python builder hands the entries a null `words`"
+        m, n, deg, p, want, slices, *_ = seen["n_below_slices"]
+        assert n < slices
+        m, n, deg, p, want, *_ = seen["hub_threshold"]
+        assert list(deg) == [63, 64, 65, 128, 129] and p["hub_row"].tolist() == [2, 3, 4] and p["hub_off"].tolist() == [0, 2, 4, 7]
+        assert np.diff(p["wave_step_off"].numpy()).tolist() == [64, 65]
+        m, n, deg, p, want, *_ = seen["hubs_first_and_last"]
+        assert p["hub_row"].tolist() == [0, m - 1]
+        m, n, deg, p, want, *_ = seen["hubs_adjacent"]
+        assert p["hub_row"].tolist() == [2, 3]
+        m, n, deg, p, want, *_ = seen["every_row_a_hub"]
+        assert want["n_hub"] == m and np.array_equal(p["wave_part"].numpy() >= 0, p["wave_row"].numpy() >= 0), "no whole row"
+        m, n, deg, p, want, slices, wpg, streams, rpw = seen["full_gen"]
+        assert m == wpg * rpw and want == dict(n_hub=0, n_parts=0, gens=1) and int((p["wave_row"] < 0).sum()) == 0
+        m, n, deg, p, want, slices, wpg, streams, rpw = seen["full_gen_plus_one"]
+        assert m == wpg * rpw + 1 and want["gens"] == 2 and int((p["wave_row"] >= 0).sum()) == m
+        m, n, deg, p, want, slices, wpg, streams, rpw = seen["m_below_streams"]
+        assert m < streams and want["gens"] == 1
+        wr = p["wave_row"].numpy().reshape(wpg, rpw)
+        assert np.all(wr[1] == -1) and np.diff(p["wave_step_off"].numpy()).tolist() == [5, 0], "a wave without rows walks no steps"
