@@ -102,6 +102,22 @@ static inline int isplib_stream_serves(int64_t n, int64_t k, int64_t ldy, int64_
    return isplib_tasks_serve(n, k, ldy) && n < ISPLIB_STREAM_N_END && ldy < ISPLIB_STREAM_LDY_END && nnz < ISPLIB_STREAM_NNZ_END &&
           (!minmax || isplib_rows_within(n, ldy, ISPLIB_STREAM_MINMAX_BYTES_END - 1u));
 }
+#define ISPLIB_MINMAX_BW_PAIRS_END     0xFFFFFFFEu  /* the sort-based max / min backward: m*k (row, feature) pairs < this */
+#define ISPLIB_MINMAX_BW_KEYS_MAX      0xFFFFFFFEu  /* 32-bit sort keys: n*k destinations and one key behind them, n*k + 1 < 2^32 */
+#define ISPLIB_OWNER_WORLD_MAX         64           /* ranks of the owner-bucketed exchange: their row cuts travel as a kernel argument */
+/* rows * k is at most `most` (exact: no product is formed) */
+static inline int isplib_product_within(int64_t rows, int64_t k, uint64_t most) {
+   return rows <= 0 || k <= 0 || (uint64_t)k <= most / (uint64_t)rows;
+}
+/* the owner-bucketed exchange of the partitioned max / min backward (isplib_minmax_bw_bucket_hip) serves m x k winners cut for
+ * `world` owners at the ascending row boundaries cuts[0..world]: every owner's keys (cuts[p+1] - cuts[p]) * k + 1 < 2^32.
+ * isplib_scatter_keys_det_hip serves the same two bounds (total pairs in place of m*k, its n x k block as the one owner). */
+static inline int isplib_owner_exchange_serves(int64_t m, int64_t k, int world, const int64_t *cuts) {
+   if (world < 1 || world > ISPLIB_OWNER_WORLD_MAX || m < 0 || k < 0 || !isplib_product_within(m, k, ISPLIB_MINMAX_BW_PAIRS_END - 1u)) return 0;
+   for (int p = 0; p < world; p++)
+      if (cuts[p + 1] < cuts[p] || !isplib_product_within(cuts[p + 1] - cuts[p], k, ISPLIB_MINMAX_BW_KEYS_MAX)) return 0;
+   return 1;
+}
 
 /*
  * The one convention of this path that nothing in the reference tree pins: what an EMPTY row of a max / min SpMM holds.
@@ -551,6 +567,41 @@ int isplib_spmm_minmax_bw_det_hip(int64_t m, int64_t n, int64_t k, int64_t nnz,
 int isplib_scatter_rows_det_hip(int64_t m, int64_t n, int64_t k, int64_t lo,
                                 const int32_t *dest /*[dev] m x k*/, const float *gval /*[dev] m x k*/,
                                 float *grad_mat /*[dev] n x k*/, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * The same backward with an owner-bucketed exchange: a rank sends every other rank only the winners that land in that rank's
+ * rows, and an owner sorts about m*k / world pairs instead of all m*k (isplib_amd/dist.py, ISPLIB_DIST_MINMAX_BW=owner).
+ * Domain: isplib_owner_exchange_serves (address-domain block above).  Neither entry allocates or synchronises.
+ *
+ * Sender's half.  For every (i, c) of this rank's m x k winners:
+ *   a = arg[i,c] - edge0; no winner unless 0 <= a < nnz; d = indx[a] (GLOBAL row of the dense operand);
+ *   owner p: cuts[p] <= d < cuts[p+1] (d outside [cuts[0], cuts[world]) is dropped);
+ *   key = (d - cuts[p]) * k + c;  value = (val ? val[a] : 1) * grad_out[i,c].
+ * keys / vals [seg_off[p], seg_off[p+1]) hold owner p's pairs in ASCENDING t = i*k + c (a stable split: three launches --
+ * per-block histograms, one exclusive scan, the scatter; no atomic decides a placement, so two launches give the same bytes);
+ * seg_off[world] = number of pairs with a winner.  Nothing is written past it.  The cuts are read on the host, during the
+ * call (they travel by value).  workspace: isplib_minmax_bw_bucket_workspace_bytes bytes, 256-byte aligned (0 = not served).
+ */
+size_t isplib_minmax_bw_bucket_workspace_bytes(int64_t m, int64_t k, int world);
+int    isplib_minmax_bw_bucket_hip(int64_t m, int64_t k, int64_t nnz, int64_t edge0,
+                                   const int64_t *arg /*[dev] m x k contiguous*/, const int64_t *indx /*[dev] nnz*/,
+                                   const float *val /*[dev] nnz | NULL*/, const float *grad_out /*[dev] m x k contiguous*/,
+                                   int world, const int64_t *cuts_host /*world + 1, ascending, HOST*/,
+                                   uint32_t *keys /*[dev] m*k*/, float *vals /*[dev] m*k*/, int64_t *seg_off /*[dev] world + 1*/,
+                                   void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Receiver's half.  grad_mat[key / k, key % k] = sum of vals over equal keys IN THE ORDER GIVEN
+ * (stable sort + the ordered run sums of isplib_spmm_minmax_bw_det_hip, sorted straight from the caller's arrays).
+ * grad_mat (n x k) is zero-filled first.  keys >= n*k are ignored, never written.  Fed the owners' segments in source-rank
+ * order it forms every sum in the order isplib_scatter_rows_det_hip does: the same bits.
+ * workspace: isplib_scatter_keys_workspace_bytes bytes, 256-byte aligned (0 = not served: total >= ISPLIB_MINMAX_BW_PAIRS_END
+ * or n*k > ISPLIB_MINMAX_BW_KEYS_MAX).
+ */
+size_t isplib_scatter_keys_workspace_bytes(int64_t total, int64_t n, int64_t k);
+int    isplib_scatter_keys_det_hip(int64_t total, int64_t n, int64_t k, const uint32_t *keys /*[dev] total*/,
+                                   const float *vals /*[dev] total*/, float *grad_mat /*[dev] n x k*/,
+                                   void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * SDDMM-style value gradient of SpMM-sum / SpMM-mean:

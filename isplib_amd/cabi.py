@@ -37,6 +37,21 @@ STREAM_NNZ_END = 2 ** 31
 STREAM_MINMAX_BYTES_END = 2 ** 31       # max / min on the stream schedule: n * ldy * 4 < 2 GiB
 K_MIN = 4                               # every entry that takes a plan
 SDDMM_TASKS_K_MAX = 1024
+MINMAX_BW_PAIRS_END = 2 ** 32 - 2       # the sort-based max / min backward: m * k pairs <
+MINMAX_BW_KEYS_MAX = 2 ** 32 - 2        # ... and n * k + 1 < 2^32 sort keys
+OWNER_WORLD_MAX = 64                    # ranks of the owner-bucketed exchange
+
+
+def owner_exchange_serves(m: int, k: int, world: int, cuts) -> bool:
+    """isplib_owner_exchange_serves of the header: m x k winners split for `world` owners at the row boundaries `cuts`."""
+    if not 1 <= world <= OWNER_WORLD_MAX or m < 0 or k < 0 or m * k >= MINMAX_BW_PAIRS_END:
+        return False
+    return all(cuts[p + 1] >= cuts[p] and (cuts[p + 1] - cuts[p]) * k <= MINMAX_BW_KEYS_MAX for p in range(world))
+
+
+def scatter_keys_serves(total: int, n: int, k: int) -> bool:
+    """The domain of isplib_scatter_keys_det_hip: the same two bounds for `total` pairs into an n x k block."""
+    return 0 <= total < MINMAX_BW_PAIRS_END and n >= 0 and k >= 0 and n * k <= MINMAX_BW_KEYS_MAX
 
 # FusedMM stage flags (csrc/fusedMM.h:18-74) and the built-in SOP_UDEF menu (enum isplib_sop_udef)
 VOP = {"copy_lhs": 0x1, "copy_rhs": 0x2, "add": 0x3, "subl": 0x4, "subr": 0x5, "max": 0x6, "min": 0x7, "udef": 0xF}
@@ -65,6 +80,7 @@ EXPORTS = (
     "isplib_suggest_slices", "isplib_graph_create", "isplib_graph_set_slices", "isplib_graph_set_values", "isplib_graph_spmm", "isplib_graph_spmm_backward",
     "isplib_graph_destroy", "isplib_suggest_slices_whole_rows", "isplib_graph_sddmm",
     "fusedMM_csr_stream_hip", "isplib_spmm_stream_workspace_bytes", "isplib_spmm_stream_geometry", "isplib_suggest_stream", "isplib_suggest_stream_weighted", "isplib_stream_plan_build_hip", "isplib_stream_plan_build_minmax_hip", "fusedMM_csr_stream_minmax_hip", "isplib_spmm_stream_minmax_geometry", "isplib_suggest_stream_minmax", "isplib_spmm_stream_minmax_workspace_bytes", "isplib_stream_plan_set_values_hip", "isplib_stream_plan_free", "isplib_spmm_minmax_bw_det_hip", "isplib_spmm_minmax_bw_workspace_bytes", "isplib_scatter_rows_det_hip",
+    "isplib_minmax_bw_bucket_workspace_bytes", "isplib_minmax_bw_bucket_hip", "isplib_scatter_keys_workspace_bytes", "isplib_scatter_keys_det_hip",
     "isplib_fusedmm_stream_geometry", "isplib_suggest_fusedmm_stream", "isplib_stream_plan_build_fusedmm_hip", "fusedMM_csr_udef_stream_hip",
     "isplib_row_scale_hip", "isplib_masked_scale_colsum_hip", "isplib_masked_scale_colsum_workspace_bytes",
     "fusedMM_csr_ordered_hip", "isplib_community_order_hip", "isplib_community_order_workspace_bytes", "isplib_order_locality_hip",
@@ -220,6 +236,15 @@ def lib() -> ctypes.CDLL:
         L.isplib_masked_scale_colsum_hip.argtypes = [_i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, ctypes.c_size_t, _vp]
         L.isplib_scatter_rows_det_hip.restype = ctypes.c_int
         L.isplib_scatter_rows_det_hip.argtypes = [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]
+        L.isplib_minmax_bw_bucket_workspace_bytes.restype = ctypes.c_size_t
+        L.isplib_minmax_bw_bucket_workspace_bytes.argtypes = [_i64, _i64, ctypes.c_int]
+        L.isplib_minmax_bw_bucket_hip.restype = ctypes.c_int
+        L.isplib_minmax_bw_bucket_hip.argtypes = [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.POINTER(_i64), _vp, _vp, _vp,
+                                                  _vp, ctypes.c_size_t, _vp]
+        L.isplib_scatter_keys_workspace_bytes.restype = ctypes.c_size_t
+        L.isplib_scatter_keys_workspace_bytes.argtypes = [_i64, _i64, _i64]
+        L.isplib_scatter_keys_det_hip.restype = ctypes.c_int
+        L.isplib_scatter_keys_det_hip.argtypes = [_i64, _i64, _i64, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]
         L.isplib_stream_plan_build_hip.restype = ctypes.c_int
         L.isplib_stream_plan_build_hip.argtypes = [_i64, _i64, _i64, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                    ctypes.POINTER(StreamPlanStruct), _vp]
@@ -630,6 +655,107 @@ def scatter_rows_det(dest: torch.Tensor, gval: torch.Tensor, lo: int, n: int) ->
         work = torch.empty(max(ws, 256), dtype=torch.uint8, device=gval.device)
         _check(lib().isplib_scatter_rows_det_hip(m, n, k, int(lo), _ptr(dest), _ptr(gval), _ptr(out), _ptr(work), work.numel(),
                                                  _stream(gval.device)), "isplib_scatter_rows_det_hip")
+    return out
+
+
+def _operand(t, name: str, dtype, dims: int) -> None:
+    """Shape, dtype and layout of one operand of the owner-exchange entries; they take the tensors as they are (fixed buffers
+    of a captured graph), so nothing is converted or copied on the caller's behalf."""
+    if not isinstance(t, torch.Tensor) or t.dim() != dims:
+        raise ValueError(f"isplib_amd: `{name}` must be a {dims}-D tensor, got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    if t.dtype != dtype:
+        raise ValueError(f"isplib_amd: `{name}` must be {dtype}, got {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"isplib_amd: `{name}` must be contiguous")
+
+
+def _same_gpu(tensors) -> None:
+    first = None
+    for name, t in tensors:
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise ValueError(f"isplib_amd: `{name}` must be a GPU tensor -- there is no CPU path")
+        if first is None:
+            first = t.device
+        elif t.device != first:
+            raise ValueError(f"isplib_amd: `{name}` is on {t.device}, the other operands on {first}")
+
+
+def minmax_bw_bucket(arg, edge0: int, col, val, grad_out, cuts, out=None, workspace=None):
+    """The sender's half of the owner-bucketed max / min backward (isplib_minmax_bw_bucket_hip): this rank's [m, k] winners
+    `arg` (CSR positions; position - edge0 indexes `col` / `val`, anything outside [0, nnz) is no winner) and gradients,
+    split by the owner of the destination row `col[.]` at the row boundaries `cuts` (world + 1, ascending).  Returns
+    (keys, vals, seg_off): owner p's pairs are [seg_off[p], seg_off[p + 1]) of keys (uint32 as int32 storage:
+    (row - cuts[p]) * k + feature) and vals, in ascending (row, feature) of this rank; seg_off is a device int64 tensor.
+    `out` = (keys, vals, seg_off) and `workspace` let a caller reuse fixed buffers (graph capture)."""
+    _operand(arg, "arg", torch.int64, 2)
+    _operand(grad_out, "grad_out", torch.float32, 2)
+    if arg.shape != grad_out.shape:
+        raise ValueError(f"isplib_amd: `arg` {tuple(arg.shape)} and `grad_out` {tuple(grad_out.shape)} must have one shape [m, k]")
+    _operand(col, "col", torch.int64, 1)
+    if val is not None:
+        _operand(val, "val", torch.float32, 1)
+        if val.numel() != col.numel():
+            raise ValueError(f"isplib_amd: `val` has {val.numel()} entries, `col` {col.numel()}")
+    cuts = [int(c) for c in cuts]
+    world = len(cuts) - 1
+    if not 1 <= world <= OWNER_WORLD_MAX:
+        raise ValueError(f"isplib_amd: `cuts` must hold world + 1 boundaries for 1..{OWNER_WORLD_MAX} owners, got {len(cuts)}")
+    if any(cuts[p + 1] < cuts[p] for p in range(world)):
+        raise ValueError("isplib_amd: `cuts` must ascend")
+    m, k = arg.shape
+    if not owner_exchange_serves(m, k, world, cuts):
+        raise ValueError(f"isplib_amd: {m} x {k} winners over these cuts are outside the owner exchange's 32-bit keys (owner_exchange_serves)")
+    total = m * k
+    if out is not None:
+        keys, vals, seg_off = out
+        _operand(keys, "keys", torch.int32, 1)
+        _operand(vals, "vals", torch.float32, 1)
+        _operand(seg_off, "seg_off", torch.int64, 1)
+        if keys.numel() < total or vals.numel() < total or seg_off.numel() != world + 1:
+            raise ValueError(f"isplib_amd: `out` must hold {total} keys, {total} values and {world + 1} offsets")
+    _same_gpu((("arg", arg), ("grad_out", grad_out), ("col", col), ("val", val)) +
+              ((("keys", out[0]), ("vals", out[1]), ("seg_off", out[2])) if out is not None else ()))
+    dev = grad_out.device
+    if out is None:
+        keys = torch.empty(total, dtype=torch.int32, device=dev)
+        vals = torch.empty(total, dtype=torch.float32, device=dev)
+        seg_off = torch.empty(world + 1, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        ws = lib().isplib_minmax_bw_bucket_workspace_bytes(m, k, world)
+        if workspace is None:
+            workspace = torch.empty(max(ws, 256), dtype=torch.uint8, device=dev)
+        _check(lib().isplib_minmax_bw_bucket_hip(m, k, col.numel(), int(edge0), _ptr(arg), _ptr(col), _ptr(val), _ptr(grad_out), world,
+                                                 (_i64 * (world + 1))(*cuts), _ptr(keys), _ptr(vals), _ptr(seg_off), _ptr(workspace),
+                                                 workspace.numel(), _stream(dev)), "isplib_minmax_bw_bucket_hip")
+    return keys, vals, seg_off
+
+
+def scatter_keys_det(keys, vals, n: int, k: int, out=None, workspace=None):
+    """The receiver's half (isplib_scatter_keys_det_hip): grad[key // k, key % k] = sum of vals over equal keys in the order
+    given; keys >= n * k are ignored.  keys: int32 storage of uint32 keys, as `minmax_bw_bucket` returns them."""
+    _operand(keys, "keys", torch.int32, 1)
+    _operand(vals, "vals", torch.float32, 1)
+    if keys.numel() != vals.numel():
+        raise ValueError(f"isplib_amd: {keys.numel()} keys for {vals.numel()} values")
+    n, k, total = int(n), int(k), keys.numel()
+    if not scatter_keys_serves(total, n, k):
+        raise ValueError(f"isplib_amd: {total} pairs into {n} x {k} are outside the sort's 32-bit keys (scatter_keys_serves)")
+    if out is not None:
+        _operand(out, "out", torch.float32, 2)
+        if tuple(out.shape) != (n, k):
+            raise ValueError(f"isplib_amd: `out` must be [{n}, {k}], got {tuple(out.shape)}")
+    _same_gpu((("keys", keys), ("vals", vals), ("out", out)))
+    dev = vals.device
+    if out is None:
+        out = torch.empty((n, k), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        ws = lib().isplib_scatter_keys_workspace_bytes(total, n, k)
+        if workspace is None:
+            workspace = torch.empty(max(ws, 256), dtype=torch.uint8, device=dev)
+        _check(lib().isplib_scatter_keys_det_hip(total, n, k, _ptr(keys), _ptr(vals), _ptr(out), _ptr(workspace), workspace.numel(),
+                                                 _stream(dev)), "isplib_scatter_keys_det_hip")
     return out
 
 

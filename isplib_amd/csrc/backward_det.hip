@@ -193,7 +193,16 @@ static hipError_t pair_sort_temp(int64_t total, unsigned bits, size_t *bytes) {
 
 using namespace isplib;
 
-static int sorted_run_sums(int64_t total, uint32_t limit, void *workspace, float *grad_mat, hipStream_t st);
+static int sorted_run_sums(int64_t total, uint32_t limit, unsigned bits, const uint32_t *keys_in, const float *vals_in, uint32_t *keys_out,
+                           float *vals_out, void *tail, float *grad_mat, hipStream_t st);
+
+// the two existing entries: (key, value) pairs in the first and third plane of their workspace, sorted into the second and fourth
+static int sorted_run_sums_planes(int64_t total, uint32_t limit, void *workspace, float *grad_mat, hipStream_t st) {
+   const size_t plane = up256((size_t)total * 4);
+   char *w = (char *)workspace;
+   return sorted_run_sums(total, limit, bits_for((uint64_t)limit + 1), (const uint32_t *)w, (const float *)(w + 2 * plane), (uint32_t *)(w + plane),
+                          (float *)(w + 3 * plane), w + 4 * plane, grad_mat, st);
+}
 
 extern "C" size_t isplib_spmm_minmax_bw_workspace_bytes(int64_t m, int64_t n, int64_t k) {
    if (m <= 0 || n <= 0 || k <= 0) return 256;
@@ -241,18 +250,15 @@ extern "C" int isplib_spmm_minmax_bw_det_hip(int64_t m, int64_t n, int64_t k, in
                       keys_in, vals_in);
    const int rc = check_launch("minmax_pairs_kernel");
    if (rc) return rc;
-   return sorted_run_sums(total, limit, workspace, grad_mat, st);
+   return sorted_run_sums_planes(total, limit, workspace, grad_mat, st);
 }
 
-// the second half of both entries: the (key, value) pairs in the first and third plane of the workspace are sorted by key
-// (stable) and every run of equal keys < limit is added up in order into grad_mat[key]
-static int sorted_run_sums(int64_t total, uint32_t limit, void *workspace, float *grad_mat, hipStream_t st) {
-   const size_t plane = up256((size_t)total * 4);
-   char *w = (char *)workspace;
-   uint32_t *keys_in = (uint32_t *)w, *keys_out = (uint32_t *)(w + plane);
-   float *vals_in = (float *)(w + 2 * plane), *vals_out = (float *)(w + 3 * plane);
-   void *temp = w + 4 * plane;
-   const unsigned bits = bits_for((uint64_t)limit + 1);
+// the second half of every entry: the (key, value) pairs of keys_in / vals_in are sorted by the low `bits` bits of the key (stable)
+// into keys_out / vals_out and every run of equal keys < limit is added up in order into grad_mat[key]; `tail`: the sort's
+// scratch and the chunk sums (run_sums_tail_bytes)
+static int sorted_run_sums(int64_t total, uint32_t limit, unsigned bits, const uint32_t *keys_in, const float *vals_in, uint32_t *keys_out,
+                           float *vals_out, void *tail, float *grad_mat, hipStream_t st) {
+   void *temp = tail;
    size_t temp_bytes = 0;
    ISPLIB_HIP_TRY(pair_sort_temp(total, bits, &temp_bytes));
    int rc;
@@ -297,5 +303,57 @@ extern "C" int isplib_scatter_rows_det_hip(int64_t m, int64_t n, int64_t k, int6
                       (uint32_t *)workspace, (float *)((char *)workspace + 2 * plane));
    const int rc = check_launch("dest_pairs_kernel");
    if (rc) return rc;
-   return sorted_run_sums(total, limit, workspace, grad_mat, st);
+   return sorted_run_sums_planes(total, limit, workspace, grad_mat, st);
+}
+
+// grad_mat = 0 by a kernel of this library.  (isplib_scatter_keys_det_hip is meant to be replayed from a captured graph: a captured
+// hipMemsetAsync node was seen to fill with foreign bytes from its second replay on -- its pattern is not kept with the node -- where
+// a kernel node carries all it needs in its own arguments.)
+__global__ __launch_bounds__(256) void zero_f32_kernel(int64_t count, float *__restrict__ out) {
+   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < count; t += stride) out[t] = 0.0f;
+}
+
+// scratch behind the sorted planes: the sort's own + the two chunk sums and the chunk states
+static size_t run_sums_tail_bytes(int64_t total, size_t sort_temp) {
+   const size_t nchunks = ((size_t)total + RUN_CHUNK - 1) / RUN_CHUNK;
+   return up256(sort_temp) + 2 * up256(nchunks * 4) + up256(nchunks);
+}
+
+// The receiver's half of the owner-bucketed exchange (include/isplib_hip.h): the pairs arrive as keys already -- an owner's share of
+// every sender's winners, in source-rank order -- so there is no pair kernel and no copy: the sort reads the caller's arrays.  The
+// keys are sorted on all 32 bits: a key >= n*k (to be ignored) must not alias a destination in the low bits and cut its run in two.
+// In-range keys end up exactly where the sort of isplib_scatter_rows_det_hip leaves them (a stable sort's order of the keys < limit
+// does not depend on what sorts behind them), the 32-pair chunks cut the same array at the same places: the same bits.
+extern "C" size_t isplib_scatter_keys_workspace_bytes(int64_t total, int64_t n, int64_t k) {
+   if (total <= 0 || n <= 0 || k <= 0) return 256;
+   if ((uint64_t)total >= ISPLIB_MINMAX_BW_PAIRS_END || !isplib_product_within(n, k, ISPLIB_MINMAX_BW_KEYS_MAX)) return 0;
+   size_t temp = 0;
+   if (pair_sort_temp(total, 32, &temp) != hipSuccess) { (void)hipGetLastError(); return 0; }
+   return 2 * up256((size_t)total * 4) + run_sums_tail_bytes(total, temp) + 256;
+}
+
+extern "C" int isplib_scatter_keys_det_hip(int64_t total, int64_t n, int64_t k, const uint32_t *keys, const float *vals, float *grad_mat,
+                                           void *workspace, size_t workspace_bytes, void *stream) {
+   clear_error();
+   if (total < 0 || n < 0 || k < 0) return fail(ISPLIB_FAIL, "isplib_scatter_keys_det_hip: negative dimension");
+   hipStream_t st = (hipStream_t)stream;
+   if (!isplib_product_within(n, k, ISPLIB_MINMAX_BW_KEYS_MAX)) return fail(ISPLIB_NO_OPT_IMPL, "isplib_scatter_keys_det_hip: n*k beyond 32-bit keys");
+   if (!grad_mat && n * k > 0) return fail(ISPLIB_FAIL, "isplib_scatter_keys_det_hip: null operand");
+   if (n * k > 0) {
+      int64_t zblocks = (n * k + 255) / 256;
+      if (zblocks > 256 * 32) zblocks = 256 * 32;
+      hipLaunchKernelGGL(zero_f32_kernel, dim3((unsigned)zblocks), dim3(256), 0, st, n * k, grad_mat);
+      const int zrc = check_launch("zero_f32_kernel");
+      if (zrc) return zrc;
+   }
+   if (total == 0 || n * k == 0) return ISPLIB_SUCCESS;
+   if (!keys || !vals) return fail(ISPLIB_FAIL, "isplib_scatter_keys_det_hip: null operand");
+   const size_t need = isplib_scatter_keys_workspace_bytes(total, n, k);
+   if (need == 0) return fail(ISPLIB_NO_OPT_IMPL, "isplib_scatter_keys_det_hip: more pairs than 32-bit positions");
+   if (!workspace || workspace_bytes < need) return fail(ISPLIB_NOT_ENOUGH_MEM, "isplib_scatter_keys_det_hip: workspace too small");
+   if (((uintptr_t)workspace & 255) != 0) return fail(ISPLIB_FAIL, "isplib_scatter_keys_det_hip: workspace must be 256-byte aligned");
+   const size_t plane = up256((size_t)total * 4);
+   char *w = (char *)workspace;
+   return sorted_run_sums(total, (uint32_t)(n * k), 32, keys, vals, (uint32_t *)w, (float *)(w + plane), w + 2 * plane, grad_mat, st);
 }

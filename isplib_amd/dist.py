@@ -589,9 +589,17 @@ def _spmm_auto(self, x_local: torch.Tensor, reduce: str = "sum"):
 
 def _minmax_backward(self, arg_global: torch.Tensor, grad_out: torch.Tensor) -> torch.Tensor:
     """dX of this rank's rows of the dense operand for a max / min forward of this partition: arg_global [rows, K] as
-    `spmm_auto` returned it, grad_out [rows, K].  Two all-gathers (int32 destinations, fp32 weighted gradients; padded to
-    the longest shard), then the deterministic scatter into the rank's own rows."""
+    `spmm_auto` returned it, grad_out [rows, K].  ISPLIB_DIST_MINMAX_BW = gather (default): two all-gathers (int32
+    destinations, fp32 weighted gradients; padded to the longest shard), then the deterministic scatter into the rank's own
+    rows | owner: every rank sends each owner only the winners that land in that owner's rows (`minmax_backward_owner`);
+    the same bits."""
+    import os
     from . import cabi
+    mode = os.environ.get("ISPLIB_DIST_MINMAX_BW", "gather")
+    if mode not in ("gather", "owner"):
+        raise ValueError(f"ISPLIB_DIST_MINMAX_BW={mode!r}: expected gather | owner")
+    if mode == "owner":
+        return self.minmax_backward_owner(arg_global, grad_out)
     k = grad_out.size(1)
     ok = arg_global != self.total_nnz
     a = (arg_global - self.edge0).clamp_(0, max(self.nnz - 1, 0))
@@ -616,11 +624,72 @@ def _minmax_backward(self, arg_global: torch.Tensor, grad_out: torch.Tensor) -> 
     return self.scatter_rows(d_all, g_all, self.x_cuts[self.rank], self.x_rows)
 
 
+def _minmax_backward_owner(self, arg_global: torch.Tensor, grad_out: torch.Tensor) -> torch.Tensor:
+    """The owner-bucketed exchange of the max / min backward.  (1) `bucket_pairs` splits this rank's winners into (key, value)
+    pairs by the rank that owns the destination row, a stable split: every segment keeps ascending (row, feature).  (2) ONE
+    all-gather of the `world` segment lengths: every rank then knows the whole count matrix (one device-to-host read per
+    backward).  (3) The segments travel point to point (`batch_isend_irecv`, as `post_direct`); both ends of an empty segment
+    skip it, the own segment is a device copy; the receive buffer holds the segments in source-rank order = ascending global
+    row order.  (4) `scatter_keys` sorts what arrived (stable) and adds up every run in order: about 1 / world of the pairs,
+    and bit for bit what the all-gathered form computes.  A rank receives 8 bytes per pair it owns plus the count matrix."""
+    k = grad_out.size(1)
+    P, r = self.world, self.rank
+    dev = grad_out.device
+    self._parked = None          # an error an EARLIER exchange left behind is not this one's
+    got = []
+    self._kernel(lambda: got.extend(self.bucket_pairs(arg_global.contiguous(), self.edge0, self.col, self.val, grad_out.contiguous(),
+                                                      self.x_cuts)))
+    if got:
+        keys, vals, seg_off = got
+    else:                        # the local kernel failed (parked): the exchange still runs, with nothing to send
+        keys = torch.empty(0, dtype=torch.int32, device=dev)
+        vals = torch.empty(0, dtype=torch.float32, device=dev)
+        seg_off = torch.zeros(P + 1, dtype=torch.int64, device=dev)
+    if P == 1:
+        total = int(seg_off[-1])
+        out = []
+        self._kernel(lambda: out.append(self.scatter_keys(keys[:total], vals[:total], self.x_rows, k)))
+        self._raise_parked()
+        return out[0]
+    counts = (seg_off[1:] - seg_off[:-1]).contiguous()
+    matrix = torch.empty(P * P, dtype=torch.int64, device=dev)
+    dist.all_gather_into_tensor(matrix, counts, group=self.group)
+    matrix = matrix.cpu().view(P, P)                 # [source, owner]; the read also orders the bucket kernels before the sends
+    off = seg_off.cpu().tolist()
+    arriving = matrix[:, r].tolist()
+    at = [0]
+    for c in arriving:
+        at.append(at[-1] + c)
+    r_keys = torch.empty(at[-1], dtype=torch.int32, device=dev)
+    r_vals = torch.empty(at[-1], dtype=torch.float32, device=dev)
+    if not _p2p_is_stream_ordered(self.group, dev):  # (see post_direct: gloo's point-to-point calls know no stream)
+        torch.cuda.current_stream(dev).synchronize()
+    ops = []
+    for d in range(1, P):
+        to, src = (r + d) % P, (r - d) % P
+        if off[to + 1] > off[to]:
+            ops.append(dist.P2POp(dist.isend, keys[off[to]:off[to + 1]], to, group=self.group))
+            ops.append(dist.P2POp(dist.isend, vals[off[to]:off[to + 1]], to, group=self.group))
+        if arriving[src] > 0:
+            ops.append(dist.P2POp(dist.irecv, r_keys[at[src]:at[src + 1]], src, group=self.group))
+            ops.append(dist.P2POp(dist.irecv, r_vals[at[src]:at[src + 1]], src, group=self.group))
+    reqs = dist.batch_isend_irecv(ops) if ops else []
+    r_keys[at[r]:at[r + 1]].copy_(keys[off[r]:off[r + 1]])
+    r_vals[at[r]:at[r + 1]].copy_(vals[off[r]:off[r + 1]])
+    for req in reqs:
+        req.wait()
+    out = []
+    self._kernel(lambda: out.append(self.scatter_keys(r_keys, r_vals, self.x_rows, k)))
+    self._raise_parked()
+    return out[0]
+
+
 RowPartition.spmm_auto = _spmm_auto
 RowPartition.local_ops = _local_ops
 RowPartition.local_spmm = _local_spmm
 RowPartition.global_arg = _global_arg
 RowPartition.minmax_backward = _minmax_backward
+RowPartition.minmax_backward_owner = _minmax_backward_owner
 
 
 def _scatter_rows(dest: torch.Tensor, gval: torch.Tensor, lo: int, n: int) -> torch.Tensor:
@@ -631,3 +700,20 @@ def _scatter_rows(dest: torch.Tensor, gval: torch.Tensor, lo: int, n: int) -> to
 
 
 RowPartition.scatter_rows = staticmethod(_scatter_rows)
+
+
+def _bucket_pairs(arg, edge0, col, val, grad_out, cuts):
+    """The sender's kernel of the owner-bucketed exchange (isplib_minmax_bw_bucket_hip) -> (keys, vals, seg_off); a hook like
+    `scatter_rows`."""
+    from . import cabi
+    return cabi.minmax_bw_bucket(arg, edge0, col, val, grad_out, cuts)
+
+
+def _scatter_keys(keys, vals, n, k):
+    """The receiver's kernel (isplib_scatter_keys_det_hip); a hook like `scatter_rows`."""
+    from . import cabi
+    return cabi.scatter_keys_det(keys, vals, n, k)
+
+
+RowPartition.bucket_pairs = staticmethod(_bucket_pairs)
+RowPartition.scatter_keys = staticmethod(_scatter_keys)
