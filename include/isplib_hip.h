@@ -452,6 +452,51 @@ int    fusedMM_csr_stream_hip(int32_t imessage /* ISPLIB_MSG_SPMM_SUM | _MEAN */
                               const float *y, int64_t ldy, float *z, int64_t ldz,
                               void *workspace, size_t workspace_bytes,
                               const isplib_epilogue *epilogue /*host, may be NULL*/, void *stream);
+/*
+ * Staged column panels (sum / mean on 64-column slots only).  What a gather of a 128-byte line costs depends on the line's
+ * ADDRESS: profiles/line_classes.txt (scripts/ubench/line_classes.hip) is the table, DESIGN.md section 5 reads it.  Before the
+ * dispatches of a panel whose lines sit in a slow class, fusedMM_csr_stream_hip may copy the panel's 64 columns into the tail
+ * of its workspace -- rows at a 512-byte pitch, data in bytes 0..255 of every 512, base 512-byte aligned: the address pattern
+ * of columns 0..63 of a contiguous K=128 operand -- and gather from the copy.  Same kernel, same plan, same order of additions:
+ * the result is the same bit for bit.  The copy is made inside every call that stages; nothing is kept between calls.
+ * isplib_spmm_stream_workspace_bytes includes the staging area (cols * 512 + 512 bytes behind the partial rows, for 4-stream
+ * plans, while that is at most ISPLIB_STREAM_STAGE_BYTES_MAX); a workspace that only holds the partial rows is served
+ * unstaged.  max / min and the FusedMM words never stage.
+ * isplib_stream_stage_panel is THE rule, for the panel of columns [c0, c0 + 64) of an n x k operand at y_addr with leading
+ * dimension ldy (it looks at the address y_addr + 4 * c0, not at the column number: a column view of a wider tensor gets the
+ * answer of its own bytes); room_bytes: what the workspace holds behind the partial rows, from the first 512-byte boundary on.
+ *   eligible: a whole 64-column panel of a 4-stream plan, a row pitch that is a multiple of 512 bytes, the panel's first byte
+ *             256-byte aligned (so its two lines keep their class in every row), the copy fits (n * 512 <= room_bytes and
+ *             <= ISPLIB_STREAM_STAGE_BYTES_MAX)
+ *   mode ISPLIB_STAGE_OFF: never; ISPLIB_STAGE_FORCE: every eligible panel (A/B runs, tests); ISPLIB_STAGE_AUTO: an eligible
+ *             panel some of whose lines are in the slow class, and whose launch is large enough for the copy to pay:
+ *             nnz >= n * ISPLIB_STREAM_STAGE_MIN_DEGREE (profiles/stream_stage_panels.txt: the copy's time against the
+ *             per-panel gain).
+ *   the slow class (profiles/line_classes.txt): address bits [9:7] = 011 -- bit 10 does not matter, 111 is as fast as the
+ *             rest -- and only for lines that come from beyond the L2.  A 256-byte aligned panel holds such lines when its
+ *             address has bit 8 set (its second line then has bits [8:7] = 11) and bit 9 is clear in some row: in every
+ *             other row when the pitch is an odd multiple of 512 bytes, in every row or in none -- by bit 9 of the panel's
+ *             own address -- when the pitch is a multiple of 1024.  The copy's lines have bits [8:7] = 00 and 01: never slow.
+ * The process-wide mode is read once from the environment: ISPLIB_STREAM_STAGE=auto|0|1 (unset: auto; the A/B that made the rule
+ * the default is profiles/stream_stage_panels.txt: Reddit shape, K=128, 2.686 -> 2.528 ms).
+ */
+#define ISPLIB_STAGE_OFF   0
+#define ISPLIB_STAGE_FORCE 1
+#define ISPLIB_STAGE_AUTO  2
+#define ISPLIB_STREAM_STAGE_PITCH      512            /* bytes between rows of the staged copy */
+#define ISPLIB_STREAM_STAGE_BYTES_MAX  (1u << 30)     /* no staging area beyond 1 GiB */
+#define ISPLIB_STREAM_STAGE_MIN_DEGREE 128            /* auto: stored entries per row of y from which the copy pays: it costs 0.0204 ms and
+                                                         the panel gains 0.175 ms at nnz / n = 492, even at 57; twice that, rounded up */
+static inline int isplib_stream_stage_panel(uint64_t y_addr, int64_t ldy, int64_t c0, int64_t k, int streams, int64_t n, int64_t nnz,
+                                            uint64_t room_bytes, int mode) {
+   const uint64_t addr = y_addr + 4u * (uint64_t)c0;
+   if (mode == ISPLIB_STAGE_OFF || streams != 4 || n <= 0 || c0 < 0 || c0 + 64 > k) return 0;
+   if (((uint64_t)ldy * 4u) % ISPLIB_STREAM_STAGE_PITCH != 0 || (addr & 255u) != 0) return 0;
+   if ((uint64_t)n > ISPLIB_STREAM_STAGE_BYTES_MAX / ISPLIB_STREAM_STAGE_PITCH || (uint64_t)n * ISPLIB_STREAM_STAGE_PITCH > room_bytes) return 0;
+   if (mode == ISPLIB_STAGE_FORCE) return 1;
+   if ((addr & 256u) == 0 || ((((uint64_t)ldy * 4u) % 1024u) == 0 && (addr & 512u) != 0)) return 0;      /* no line with bits [9:7] = 011 */
+   return nnz / n >= ISPLIB_STREAM_STAGE_MIN_DEGREE;
+}
 
 /*
  * The two SDDMM-fused words of the generic pipeline that graph embedding runs on -- COPY_RHS|DOT|UDEF|MUL|ADD (sigmoid embedding,

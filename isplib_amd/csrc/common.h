@@ -11,6 +11,9 @@ namespace isplib {
 char *error_buffer();   // thread-local, 512 bytes (defined in runtime.hip)
 int empty_row_init();   // 1: an empty row of max / min keeps the reference launcher's pre-fill (isplib_hip_set_empty_row; runtime.hip)
 
+int stream_stage_mode();                     // ISPLIB_STAGE_*: staged column panels of the stream schedule (ISPLIB_STREAM_STAGE; runtime.hip)
+void stream_stage_report(unsigned panels);   // which panels the call staged (isplib_stream_stage_last)
+
 inline void clear_error() { error_buffer()[0] = '\0'; }
 
 inline int fail(int code, const char *msg) {

@@ -688,7 +688,7 @@ extern "C" int isplib_spmm_hybrid_geometry(int streams, int *rows_per_wave, int 
 }
 
 extern "C" size_t isplib_spmm_hybrid_workspace_bytes(const isplib_hybrid_plan *plan) {
-   return isplib_spmm_stream_workspace_bytes(plan ? &plan->cold : nullptr);
+   return stream_parts_bytes(plan ? &plan->cold : nullptr);
 }
 
 extern "C" int fusedMM_csr_hybrid_hip(int32_t imessage, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *pntrb,
@@ -700,7 +700,7 @@ extern "C" int fusedMM_csr_hybrid_hip(int32_t imessage, int64_t m, int64_t n, in
    const isplib_stream_plan *plan = hp ? &hp->cold : nullptr;
    const StreamCall c = {entry, "fusedMM_csr_hip", STREAM_HYBRID, m, n, k, nnz, /* empty */ m == 0 || k == 0, pntrb, pntre, plan, y, ldy,
                          /* ld_other */ ldz, /* others */ z && hp && hp->hot_rows && hp->hot_step_off && (hp->n_hot_steps <= 0 || hp->hot_words),
-                         /* hub_fold */ true, workspace, workspace_bytes, isplib_spmm_stream_workspace_bytes(plan)};
+                         /* hub_fold */ true, workspace, workspace_bytes, stream_parts_bytes(plan)};
    bool done;
    int rc = check_stream_call(c, &done);
    if (done) return rc;
@@ -716,7 +716,7 @@ extern "C" int fusedMM_csr_hybrid_hip(int32_t imessage, int64_t m, int64_t n, in
    hipStream_t st = (hipStream_t)stream;
    return run_stream_panels(plan, a,
       [&](const SweepArgs &p) { return with_streams<STREAM_HYBRID>(plan->streams, [&](auto s) { return launch_hybrid<s()>(p, st); }); },
-      [&](const SweepArgs &p) { return launch_hub_fold<OP_ADD, true>(p, st); });
+      [&](const SweepArgs &p) { return launch_hub_fold<OP_ADD, true>(p, st); }, NoStage());
 }
 
 extern "C" int isplib_internal_set_sddmm_panel_cols(int cols);      // libisplib_hip.so (spmm.hip); not a public entry

@@ -36,5 +36,31 @@ extern "C" int isplib_hip_set_empty_row(int init) {
 }
 extern "C" int isplib_hip_get_empty_row(void) { return isplib::empty_row_init(); }
 
+// Staged column panels of the stream schedule (include/isplib_hip.h, isplib_stream_stage_panel): the process-wide mode,
+// ISPLIB_STREAM_STAGE=auto|0|1 read once.  Unset: auto -- profiles/stream_stage_panels.txt holds the A/B that makes the rule the
+// default (every staged run below every parent run, the median difference 40 spreads of the parent).  The two entries below are for A/B runs and tests and are not declared in the header:
+// isplib_stream_stage_set overrides the mode (ISPLIB_STAGE_*), isplib_stream_stage_last reports which panels the last call of
+// fusedMM_csr_stream_hip on this thread staged (bit p: panel p).
+namespace isplib {
+static int g_stream_stage = -1;
+static thread_local unsigned g_stream_stage_last = 0;
+int stream_stage_mode() {
+   if (g_stream_stage < 0) {
+      const char *e = getenv("ISPLIB_STREAM_STAGE");
+      g_stream_stage = !e ? ISPLIB_STAGE_AUTO : strcmp(e, "0") == 0 ? ISPLIB_STAGE_OFF : strcmp(e, "1") == 0 ? ISPLIB_STAGE_FORCE : ISPLIB_STAGE_AUTO;
+   }
+   return g_stream_stage;
+}
+void stream_stage_report(unsigned panels) { g_stream_stage_last = panels; }
+}  // namespace isplib
+
+extern "C" int isplib_stream_stage_set(int mode) {
+   isplib::clear_error();
+   if (mode != ISPLIB_STAGE_OFF && mode != ISPLIB_STAGE_FORCE && mode != ISPLIB_STAGE_AUTO) return isplib::fail(ISPLIB_FAIL, "isplib_stream_stage_set: 0 (off), 1 (force) or 2 (auto)");
+   isplib::g_stream_stage = mode;
+   return ISPLIB_SUCCESS;
+}
+extern "C" unsigned isplib_stream_stage_last(void) { return isplib::g_stream_stage_last; }
+
 extern "C" int isplib_hip_abi_version(void) { return ISPLIB_HIP_ABI_VERSION; }
 extern "C" const char *isplib_hip_last_error(void) { return isplib::error_buffer(); }

@@ -338,6 +338,28 @@ __global__ __launch_bounds__(256, (stream_wgs_per_cu<LPR, 2 * (NVMAX + 1), WGS>(
 }
 
 
+// Staged column panel (include/isplib_hip.h, isplib_stream_stage_panel): dst[r * 128 + j] = y[r * ldy + j] for the 64 columns from
+// y on, i.e. rows at a 512-byte pitch with the data in bytes 0..255 -- the address pattern of the FIRST panel of a contiguous
+// K = 128 operand, whose lines are all in fast classes (profiles/line_classes.txt).  16 lanes x 16 bytes per row, rows of both
+// sides fully coalesced; y 16-byte aligned (the rule asks 256) and ldy a multiple of 4.
+__global__ __launch_bounds__(256) void stream_stage_copy_kernel(const float *__restrict__ y, int64_t ldy, int64_t n, float *__restrict__ dst) {
+   const int64_t total = n * 16;
+   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+      const int64_t r = i >> 4;
+      const int j = (int)(i & 15) * 4;
+      *reinterpret_cast<float4 *>(dst + r * (ISPLIB_STREAM_STAGE_PITCH / 4) + j) = *reinterpret_cast<const float4 *>(y + r * ldy + j);
+   }
+}
+
+static int launch_stage_copy(const float *y, int64_t ldy, int64_t n, float *dst, hipStream_t st) {
+   int64_t blocks = (n * 16 + 255) / 256;
+   if (blocks > 4096) blocks = 4096;
+   if (blocks <= 0) return ISPLIB_SUCCESS;
+   hipLaunchKernelGGL(stream_stage_copy_kernel, dim3((unsigned)blocks), dim3(256), 0, st, y, ldy, n, dst);
+   return check_launch("stream_stage_copy_kernel");
+}
+
 #ifdef ISPLIB_EXP_WAVE_TIMES
 static unsigned long long *g_dbg = nullptr;      // set by isplib_debug_wave_times; one slab per launch, four launches
 static int g_dbg_launch = 0;
@@ -442,14 +464,18 @@ extern "C" int isplib_suggest_stream_minmax(int64_t m, int64_t n, int64_t nnz, i
    return 1;
 }
 
+// the partial rows, then (4-stream plans: the 64-column slots of sum / mean) room for one staged column panel of any call on
+// this plan -- plan->cols rows at a 512-byte pitch, + 512 to start on a 512-byte boundary (isplib_stream_stage_panel).  The
+// function is not told k, and a call whose workspace ends before the staging area runs unstaged.
 extern "C" size_t isplib_spmm_stream_workspace_bytes(const isplib_stream_plan *plan) {
-   if (!plan || plan->n_parts <= 0) return 256;
-   const size_t pk = (size_t)(256 / (plan->streams > 0 ? plan->streams : 4));
-   return ((size_t)plan->n_parts * pk * sizeof(float) + 255) & ~(size_t)255;
+   size_t bytes = stream_parts_bytes(plan);
+   if (plan && plan->streams == 4 && plan->cols > 0 && (uint64_t)plan->cols <= (ISPLIB_STREAM_STAGE_BYTES_MAX - ISPLIB_STREAM_STAGE_PITCH) / ISPLIB_STREAM_STAGE_PITCH)
+      bytes += (size_t)plan->cols * ISPLIB_STREAM_STAGE_PITCH + ISPLIB_STREAM_STAGE_PITCH;
+   return bytes;
 }
 
 extern "C" size_t isplib_spmm_stream_minmax_workspace_bytes(const isplib_stream_plan *plan) {
-   return 2 * isplib_spmm_stream_workspace_bytes(plan);   // values, then CSR positions
+   return 2 * stream_parts_bytes(plan);   // values, then CSR positions (max / min never stage)
 }
 
 static int stream_run(int32_t imessage, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *pntrb, const int64_t *pntre,
@@ -460,7 +486,7 @@ static int stream_run(int32_t imessage, int64_t m, int64_t n, int64_t k, int64_t
    const bool mm = imessage == ISPLIB_MSG_SPMM_MAX || imessage == ISPLIB_MSG_SPMM_MIN;
    if (imessage != ISPLIB_MSG_SPMM_SUM && imessage != ISPLIB_MSG_SPMM_MEAN && !mm) return fail(ISPLIB_NO_OPT_IMPL, entry, "message outside the SpMM set");
    const StreamCall c = {entry, "fusedMM_csr_hip", mm ? STREAM_MINMAX : STREAM_SUM, m, n, k, nnz, /* empty */ m == 0 || k == 0, pntrb, pntre, plan, y, ldy,
-                         /* ld_other */ ldz, /* others */ z != nullptr, /* hub_fold */ true, workspace, workspace_bytes, (mm ? 2 : 1) * isplib_spmm_stream_workspace_bytes(plan)};
+                         /* ld_other */ ldz, /* others */ z != nullptr, /* hub_fold */ true, workspace, workspace_bytes, (mm ? 2 : 1) * stream_parts_bytes(plan)};
    bool done;
    int rc = check_stream_call(c, &done);
    if (done) return rc;
@@ -472,11 +498,32 @@ static int stream_run(int32_t imessage, int64_t m, int64_t n, int64_t k, int64_t
    SweepArgs a = stream_args(c, z, ldz);
    a.z_arg = z_arg;
    a.mean = imessage == ISPLIB_MSG_SPMM_MEAN ? 1 : 0;
-   a.part_idx = mm && workspace ? (int *)((char *)workspace + isplib_spmm_stream_workspace_bytes(plan)) : nullptr;
+   a.part_idx = mm && workspace ? (int *)((char *)workspace + stream_parts_bytes(plan)) : nullptr;
    if ((rc = set_epilogue(entry, ep, a)) != ISPLIB_SUCCESS) return rc;
    hipStream_t st = (hipStream_t)stream;
    const bool has_val = plan->vals != nullptr;
-   return run_stream_panels(plan, a,
+   // sum / mean: the staging area follows the partial rows, from the first 512-byte boundary on; a workspace without one (sized
+   // by the partial rows alone, or NULL for a plan without hub rows) leaves every panel where it is
+   const int stage_mode = mm ? ISPLIB_STAGE_OFF : stream_stage_mode();
+   float *stage_base = nullptr;
+   uint64_t stage_room = 0;
+   if (stage_mode != ISPLIB_STAGE_OFF && workspace) {
+      const uintptr_t lo = ((uintptr_t)workspace + stream_parts_bytes(plan) + (ISPLIB_STREAM_STAGE_PITCH - 1)) & ~(uintptr_t)(ISPLIB_STREAM_STAGE_PITCH - 1);
+      const uintptr_t hi = (uintptr_t)workspace + workspace_bytes;
+      if (lo < hi) { stage_base = (float *)lo; stage_room = hi - lo; }
+   }
+   unsigned staged = 0;
+   auto stage = [&](SweepArgs &p, int64_t c0) {
+      if (!isplib_stream_stage_panel((uint64_t)(uintptr_t)y, ldy, c0, k, plan->streams, n, nnz, stage_room, stage_mode)) return (int)ISPLIB_SUCCESS;
+      const int rc = launch_stage_copy(p.y, ldy, n, stage_base, st);
+      if (rc) return rc;
+      p.y = stage_base;
+      p.ldy = ISPLIB_STREAM_STAGE_PITCH / 4;
+      p.ybytes = (unsigned)((uint64_t)n * ISPLIB_STREAM_STAGE_PITCH);      // <= 1 GiB (the rule); row n, the padding words' column, is outside
+      staged |= 1u << ((c0 / 64) & 31);
+      return (int)ISPLIB_SUCCESS;
+   };
+   const int rc_run = run_stream_panels(plan, a,
       [&](const SweepArgs &p) {
          if (imessage == ISPLIB_MSG_SPMM_MAX) return has_val ? launch_stream_minmax<OP_MAX, true>(p, st, plan->streams) : launch_stream_minmax<OP_MAX, false>(p, st, plan->streams);
          if (imessage == ISPLIB_MSG_SPMM_MIN) return has_val ? launch_stream_minmax<OP_MIN, true>(p, st, plan->streams) : launch_stream_minmax<OP_MIN, false>(p, st, plan->streams);
@@ -485,7 +532,9 @@ static int stream_run(int32_t imessage, int64_t m, int64_t n, int64_t k, int64_t
       [&](const SweepArgs &p) {
          return imessage == ISPLIB_MSG_SPMM_MAX ? launch_hub_fold<OP_MAX, true>(p, st)
               : imessage == ISPLIB_MSG_SPMM_MIN ? launch_hub_fold<OP_MIN, true>(p, st) : launch_hub_fold<OP_ADD, true>(p, st);
-      });
+      }, stage);
+   if (!mm) stream_stage_report(staged);
+   return rc_run;
 }
 
 extern "C" int fusedMM_csr_stream_hip(int32_t imessage, int64_t m, int64_t n, int64_t k, int64_t nnz,

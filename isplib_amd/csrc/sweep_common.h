@@ -534,9 +534,24 @@ static inline int run_generations(int gens, int waves_per_gen, SweepArgs &p, Lau
    return ISPLIB_SUCCESS;
 }
 
-// column panels of the plan's slot width (a slot is 64 / streams lanes x 4 floats): every generation, then the hub fold, per panel
-template <class Launch, class Fold>
-static inline int run_stream_panels(const isplib_stream_plan *plan, const SweepArgs &a, Launch launch, Fold fold) {
+// the partial rows of the hub rows, at the start of every stream entry's workspace (what isplib_spmm_stream_workspace_bytes was
+// before it grew the staging area; max / min keep a second plane of the same size behind it)
+static inline size_t stream_parts_bytes(const isplib_stream_plan *plan) {
+   if (!plan || plan->n_parts <= 0) return 256;
+   const size_t pk = (size_t)(256 / (plan->streams > 0 ? plan->streams : 4));
+   return ((size_t)plan->n_parts * pk * sizeof(float) + 255) & ~(size_t)255;
+}
+
+// an entry that never stages a panel (max / min, the hybrid) passes this to run_stream_panels
+struct NoStage { int operator()(SweepArgs &, int64_t) const { return ISPLIB_SUCCESS; } };
+
+// column panels of the plan's slot width (a slot is 64 / streams lanes x 4 floats): every generation, then the hub fold, per panel.
+// stage(p, c0) runs before the panel's first dispatch, on the panel's arguments: the sum / mean entry's launches a copy of a panel
+// whose lines sit in a slow address class (isplib_stream_stage_panel, include/isplib_hip.h) and points p.y / p.ldy / p.ybytes at
+// the copy -- rows n and beyond are still outside the descriptor, so padding words still read 0; the kernel, z, the epilogue's
+// operands and the fold see no difference.
+template <class Launch, class Fold, class Stage>
+static inline int run_stream_panels(const isplib_stream_plan *plan, const SweepArgs &a, Launch launch, Fold fold, Stage stage) {
    const int64_t k = a.k, pw = 256 / plan->streams;
    for (int64_t c0 = 0; c0 < k; c0 += pw) {
       SweepArgs p = a;
@@ -551,7 +566,8 @@ static inline int run_stream_panels(const isplib_stream_plan *plan, const SweepA
       p.ep_bias = a.ep_bias ? a.ep_bias + c0 : nullptr;
       p.z_arg = a.z_arg ? a.z_arg + c0 : nullptr;
       p.ybytes = a.ybytes - (unsigned)c0 * 4u;
-      int rc = run_generations(plan->gens, plan->waves_per_gen, p, launch);
+      int rc = stage(p, c0);
+      if (!rc) rc = run_generations(plan->gens, plan->waves_per_gen, p, launch);
       if (!rc) rc = fold(p);
       if (rc) return rc;
    }
