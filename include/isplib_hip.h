@@ -102,6 +102,14 @@ static inline int isplib_stream_serves(int64_t n, int64_t k, int64_t ldy, int64_
    return isplib_tasks_serve(n, k, ldy) && n < ISPLIB_STREAM_N_END && ldy < ISPLIB_STREAM_LDY_END && nnz < ISPLIB_STREAM_NNZ_END &&
           (!minmax || isplib_rows_within(n, ldy, ISPLIB_STREAM_MINMAX_BYTES_END - 1u));
 }
+/* the 16-bit stream entry (fusedMM_csr_stream16_hip: bf16 / fp16 dense operands, sum / mean) does: the stream entry's domain with
+ * the byte sizes at 2 bytes per element, and k, ldy, ldz all even -- every 8-byte gather and store is then 4-byte aligned, the
+ * last vector of a ragged panel (shifted back to end at column k) included.  The entry also refuses a y or z base that is not
+ * 4-byte aligned.  What this refuses is served by converting the operand to fp32 (the layers above do that; nothing raises). */
+static inline int isplib_stream16_serves(int64_t n, int64_t k, int64_t ldy, int64_t ldz, int64_t nnz) {
+   return k >= ISPLIB_K_MIN && n < ISPLIB_STREAM_N_END && ldy < ISPLIB_STREAM_LDY_END && nnz < ISPLIB_STREAM_NNZ_END &&
+          isplib_rows_within(n, ldy, 2ull * ISPLIB_DENSE_BYTES_MAX) && (k % 2) == 0 && (ldy % 2) == 0 && (ldz % 2) == 0;
+}
 #define ISPLIB_MINMAX_BW_PAIRS_END     0xFFFFFFFEu  /* the sort-based max / min backward: m*k (row, feature) pairs < this */
 #define ISPLIB_MINMAX_BW_KEYS_MAX      0xFFFFFFFEu  /* 32-bit sort keys: n*k destinations and one key behind them, n*k + 1 < 2^32 */
 #define ISPLIB_OWNER_WORLD_MAX         64           /* ranks of the owner-bucketed exchange: their row cuts travel as a kernel argument */
@@ -452,6 +460,35 @@ int    fusedMM_csr_stream_hip(int32_t imessage /* ISPLIB_MSG_SPMM_SUM | _MEAN */
                               const float *y, int64_t ldy, float *z, int64_t ldz,
                               void *workspace, size_t workspace_bytes,
                               const isplib_epilogue *epilogue /*host, may be NULL*/, void *stream);
+/*
+ * The stream schedule for a dense operand of 16-bit elements (dtype: ISPLIB_DTYPE_BF16 | ISPLIB_DTYPE_F16), sum / mean.  The
+ * SAME plans as fusedMM_csr_stream_hip (sum plans of 2, 4 or 8 streams; the weights stay the plan's fp32 `vals`), the same
+ * geometry; a lane's gather is 8 bytes instead of 16, so a 64-column panel row is one 128-byte line instead of two.  Products,
+ * sums and the mean's division are formed in fp32; a finished row is rounded ONCE, to nearest even, to `dtype` (hub rows keep
+ * fp32 partial rows in the workspace and round in their fold): the result is the fp32 entry's on the widened operand, rounded
+ * -- NaN stays NaN, bf16 keeps subnormals, fp16 overflows to +-Inf.  y: n x ldy and z: m x ldz elements of `dtype`.
+ * Domain: isplib_stream16_serves(n, k, ldy, ldz, nnz), and y, z 4-byte aligned; anything outside returns ISPLIB_FAIL before any
+ * launch.  No epilogue and no staged panels.  workspace: the partial rows only (a workspace of
+ * isplib_spmm_stream_workspace_bytes(plan) bytes is accepted: the staging area it includes is not used).
+ * isplib_stream16_native_pays is the measured rule of the layers above (profiles/stream16_ab.txt): nonzero for the classes of
+ * calls (slot width x weighted plan) where EVERY run of this entry was faster than EVERY run of "convert to fp32, run the fp32
+ * entry, convert back"; a class that does not meet that keeps converting by default.  As measured NO class meets it: the 8-byte
+ * gather costs the address pipeline what the 16-byte one does (the loop is charged per gather instruction, not per line), the
+ * loop carries 17.4 vector instructions per step against 13.4, and the two conversion passes it saves cost 0.035 ms at K = 64
+ * -- so the entry is a capability (half the footprint of X, no fp32 copy), not a speed-up, and `auto` converts everywhere.
+ */
+#define ISPLIB_DTYPE_BF16 1
+#define ISPLIB_DTYPE_F16  2
+int    fusedMM_csr_stream16_hip(int32_t imessage /* ISPLIB_MSG_SPMM_SUM | _MEAN */, int dtype, int64_t m, int64_t n, int64_t k,
+                                int64_t nnz, const int64_t *pntrb, const int64_t *pntre,
+                                const isplib_stream_plan *plan /*host*/,
+                                const void *y, int64_t ldy, void *z, int64_t ldz,
+                                void *workspace, size_t workspace_bytes, void *stream);
+static inline int isplib_stream16_native_pays(int streams, int weighted) {
+   (void)streams; (void)weighted;
+   return 0;      /* measured (Reddit shape, bf16, K = 64 / 128): (4, unit), (4, weighted), (2, weighted) lose or tie; the rest unmeasured */
+}
+int    isplib_stream16_auto(int streams, int weighted);      /* the same rule as a symbol (for hosts that cannot include this header) */
 /*
  * Staged column panels (sum / mean on 64-column slots only).  What a gather of a 128-byte line costs depends on the line's
  * ADDRESS: profiles/line_classes.txt (scripts/ubench/line_classes.hip) is the table, DESIGN.md section 5 reads it.  Before the

@@ -40,6 +40,21 @@ SDDMM_TASKS_K_MAX = 1024
 MINMAX_BW_PAIRS_END = 2 ** 32 - 2       # the sort-based max / min backward: m * k pairs <
 MINMAX_BW_KEYS_MAX = 2 ** 32 - 2        # ... and n * k + 1 < 2^32 sort keys
 OWNER_WORLD_MAX = 64                    # ranks of the owner-bucketed exchange
+DTYPE_BF16, DTYPE_F16 = 1, 2            # ISPLIB_DTYPE_*: element types of fusedMM_csr_stream16_hip
+
+
+def stream16_serves(n: int, k: int, ldy: int, ldz: int, nnz: int) -> bool:
+    """isplib_stream16_serves of the header: the 16-bit stream entry (bf16 / fp16 operands, sum / mean) serves an n x k operand at
+    leading dimension ldy (elements), output pitch ldz, on a graph of nnz entries."""
+    return (k >= K_MIN and n < STREAM_N_END and ldy < STREAM_LDY_END and nnz < STREAM_NNZ_END and
+            (n <= 0 or n * ldy * 2 <= DENSE_BYTES_MAX) and k % 2 == 0 and ldy % 2 == 0 and ldz % 2 == 0)
+
+
+def stream16_native_pays(streams: int, weighted: bool) -> bool:
+    """isplib_stream16_native_pays of the header: the classes of calls (slot width x weighted plan) in which every native 16-bit run
+    measured faster than every run of the conversion route (profiles/stream16_ab.txt: none does); tests/test_half_host.py compares
+    the two."""
+    return False
 
 
 def owner_exchange_serves(m: int, k: int, world: int, cuts) -> bool:
@@ -85,6 +100,7 @@ EXPORTS = (
     "isplib_row_scale_hip", "isplib_masked_scale_colsum_hip", "isplib_masked_scale_colsum_workspace_bytes",
     "fusedMM_csr_ordered_hip", "isplib_community_order_hip", "isplib_community_order_workspace_bytes", "isplib_order_locality_hip",
     "isplib_graph_set_row_order", "isplib_plain_panels",
+    "fusedMM_csr_stream16_hip", "isplib_stream16_auto",
 )
 
 # include/isplib_hip_experimental.h (libisplib_hip_exp.so): forms measured slower than the defaults; tests and experiment scripts only
@@ -288,6 +304,11 @@ def lib() -> ctypes.CDLL:
         L.fusedMM_csr_stream_hip.restype = ctypes.c_int
         L.fusedMM_csr_stream_hip.argtypes = [_i32, _i64, _i64, _i64, _i64, _vp, _vp, ctypes.POINTER(StreamPlanStruct), _vp, _i64,
                                              _vp, _i64, _vp, ctypes.c_size_t, ctypes.POINTER(Epilogue), _vp]
+        L.fusedMM_csr_stream16_hip.restype = ctypes.c_int
+        L.fusedMM_csr_stream16_hip.argtypes = [_i32, ctypes.c_int, _i64, _i64, _i64, _i64, _vp, _vp, ctypes.POINTER(StreamPlanStruct), _vp, _i64,
+                                               _vp, _i64, _vp, ctypes.c_size_t, _vp]
+        L.isplib_stream16_auto.restype = ctypes.c_int
+        L.isplib_stream16_auto.argtypes = [ctypes.c_int, ctypes.c_int]
         _sigs_set = True
     return L
 
@@ -1055,6 +1076,66 @@ def spmm_stream(rowptr, nnz: int, plan, y, reduce: str = "sum", workspace=None, 
         ep = Epilogue(None if row_scale is None else row_scale.data_ptr(), None if self_term is None else self_term.data_ptr(),
                       k if self_term is None else self_term.stride(0), None if bias is None else bias.data_ptr(), int(bool(relu)))
     fusedMM_csr_stream_hip(MESSAGE[reduce], rowptr, nnz, plan, y, out, workspace, ep)
+    return out
+
+
+HALF_DTYPES = {torch.bfloat16: DTYPE_BF16, torch.float16: DTYPE_F16}
+
+
+def fusedMM_csr_stream16_hip(imessage: int, rowptr, nnz: int, plan, y, z, workspace=None, check: bool = True, dtype=None, k=None,
+                             ldy=None, ldz=None) -> int:
+    """Raw boundary call of the 16-bit stream SpMM (sum / mean), for operands the entry may refuse: it hands over what it is given
+    (`dtype`, `k`, `ldy`, `ldz`: override what the tensors say -- refusal tests; the entry refuses before it reads anything).
+    Callers that want their operands checked use spmm_stream16."""
+    m, n = rowptr.numel() - 1, y.size(0)
+    k = y.size(1) if k is None else int(k)
+    code = HALF_DTYPES.get(y.dtype, 0) if dtype is None else int(dtype)
+    rp = rowptr.data_ptr()
+    ps = plan.struct()
+    with torch.cuda.device(y.device):
+        st = lib().fusedMM_csr_stream16_hip(int(imessage), code, m, n, k, int(nnz), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8),
+                                            ctypes.byref(ps), _ptr(y), (y.stride(0) if n > 1 else max(k, y.stride(0))) if ldy is None else int(ldy),
+                                            _ptr(z), (z.stride(0) if m > 1 else max(k, z.stride(0))) if ldz is None else int(ldz),
+                                            _ptr(workspace), 0 if workspace is None else workspace.numel(), _stream(y.device))
+    if check:
+        _check(st, "fusedMM_csr_stream16_hip")
+    return st
+
+
+def spmm_stream16(rowptr, nnz: int, plan, y, reduce: str = "sum", workspace=None, out=None):
+    """The 16-bit stream SpMM (sum / mean) of a bf16 / fp16 `y` [n, k] on a sum plan: returns `out` [m, k] of y's dtype (allocated
+    when not given; a row-strided view is written at its own pitch).  Every operand is checked BEFORE the call -- a mis-shaped one is
+    an out-of-bounds device read: y 2-D on the GPU with unit inner stride and one row per column of the plan, rowptr with one entry
+    per row of the plan (+ 1), the shape inside isplib_stream16_serves, `out` [m, k] of the same dtype at an even pitch."""
+    if reduce not in ("sum", "add", "mean"):
+        raise ValueError(f"isplib_amd: spmm_stream16 serves sum / mean, got '{reduce}'")
+    rowptr = _dev(rowptr, "rowptr", torch.int64)
+    if not isinstance(y, torch.Tensor) or not y.is_cuda or y.dim() != 2:
+        raise ValueError("isplib_amd: `y` must be a 2-D GPU tensor [n, k]")
+    if y.dtype not in HALF_DTYPES:
+        raise TypeError(f"isplib_amd: `y` must be bfloat16 or float16, got {y.dtype} (float32: spmm_stream)")
+    n, k = y.size(0), y.size(1)
+    m = rowptr.numel() - 1
+    if k > 0 and y.stride(1) != 1:
+        raise ValueError("isplib_amd: `y` must have unit inner stride")
+    if n != plan.cols or m != plan.rows:
+        raise ValueError(f"isplib_amd: the plan was built for a {plan.rows} x {plan.cols} graph, got rowptr of {m} rows and y of {n} rows")
+    if rowptr.device != y.device:
+        raise ValueError("isplib_amd: rowptr and y are on different devices")
+    ldy = y.stride(0) if n > 1 else max(k, y.stride(0))
+    if out is None:
+        out = torch.empty((m, k), dtype=y.dtype, device=y.device)
+    elif not isinstance(out, torch.Tensor) or out.device != y.device or tuple(out.shape) != (m, k) or out.dtype != y.dtype or (k > 0 and out.stride(1) != 1):
+        raise ValueError(f"isplib_amd: `out` must be a [{m}, {k}] {y.dtype} tensor on {y.device} with unit inner stride")
+    ldz = out.stride(0) if m > 1 else max(k, out.stride(0))
+    if m > 0 and k > 0:
+        if ldy < k or ldz < k or not stream16_serves(n, k, ldy, ldz, int(nnz)):
+            raise ValueError(f"isplib_amd: outside the 16-bit stream entry's domain (isplib_stream16_serves: n={n}, k={k}, ldy={ldy}, ldz={ldz}, nnz={int(nnz)})")
+        if (y.data_ptr() | out.data_ptr()) & 3:
+            raise ValueError("isplib_amd: `y` and `out` must be 4-byte aligned")
+    if workspace is None:
+        workspace = plan.workspace()
+    fusedMM_csr_stream16_hip(MESSAGE[reduce], rowptr, nnz, plan, y, out, workspace)
     return out
 
 

@@ -446,6 +446,7 @@ struct StreamCall {
    bool hub_fold;                         // hub rows leave partial rows in the workspace (not the SDDMM: it writes per edge)
    void *workspace;
    size_t workspace_bytes, workspace_need;
+   int elt_bytes = 4;                     // bytes per element of y (2: the 16-bit entry, spmm_stream16.hip)
 };
 
 // Every refusal the entries share that is decided before anything is launched.  *done: nothing (more) to do, the entry returns
@@ -470,7 +471,7 @@ static inline int check_stream_call(const StreamCall &c, bool *done) {
       return fail(ISPLIB_FAIL, c.entry, "bad plan geometry (rows_per_wave must be what the geometry entry of this plan family reports)");
    if (c.k < ISPLIB_K_MIN) return use_instead("k >= 4 required");
    if (c.ldy < c.k || c.ld_other < c.k) return fail(ISPLIB_FAIL, c.entry, "leading dimension smaller than k");
-   if (!isplib_dense_in_descriptor(c.n, c.ldy)) return use_instead("dense operand larger than 3.5 GiB");
+   if (!isplib_rows_within(c.n, c.ldy, (uint64_t)ISPLIB_DENSE_BYTES_MAX * 4u / (uint64_t)c.elt_bytes)) return use_instead("dense operand larger than 3.5 GiB");
    if (!c.pntrb || !c.pntre || !c.y || !c.others || !plan->wave_row || !plan->wave_step_off || (plan->n_steps > 0 && !plan->words) ||
        (c.hub_fold && (!plan->wave_part || (plan->n_hub > 0 && (!plan->hub_row || !plan->hub_off)))))
       return fail(ISPLIB_FAIL, c.entry, "null operand");

@@ -63,6 +63,20 @@ void check_float(const Tensor &t, const char *name) {
    TORCH_CHECK(t.scalar_type() == at::kFloat, "isplib: `", name, "` must be float32 (csrc/fusedmm.cpp:44)");
 }
 
+// 16-bit features (bf16 / fp16) of the SpMM operators: products, sums and the mean's division in fp32, the finished row rounded
+// once to the operand's type (include/isplib_hip.h: fusedMM_csr_stream16_hip).  Everything the native entry does not serve takes
+// the CONVERSION ROUTE -- the operand to fp32, the fp32 path unchanged, the result to the operand's type -- which has the same
+// semantics by construction.  Edge weights are fp32 everywhere: a 16-bit `value` is brought to fp32 (exact).
+bool is_half(const Tensor &t) { return t.defined() && (t.scalar_type() == at::kBFloat16 || t.scalar_type() == at::kHalf); }
+
+void check_feature(const Tensor &t, const char *name) {
+   TORCH_CHECK(t.defined(), "isplib: `", name, "` is missing");
+   TORCH_CHECK(t.is_cuda(), "isplib: `", name, "` must be a GPU tensor -- isplib_amd has no CPU path");
+   TORCH_CHECK(t.scalar_type() == at::kFloat || is_half(t), "isplib: `", name, "` must be float32, bfloat16 or float16");
+}
+
+Tensor as_float(const Tensor &t) { return t.defined() && t.scalar_type() != at::kFloat ? t.to(at::kFloat) : t; }
+
 void *current_stream(const Tensor &t) { return (void *)c10::hip::getCurrentHIPStream(t.device().index()).stream(); }
 
 // ISPLIB_DEBUG=1: per-operator device time on stderr under the reference's own labels (the commented-out timers
@@ -257,6 +271,44 @@ static int64_t gather_pitch(int64_t N, int64_t K, bool stream) {
    return (stream && K > 32 && K < 48 && N >= (1 << 16) && isplib_rows_within(N, 48, ISPLIB_STREAM_MINMAX_BYTES_END - 1u)) ? 48 : K;
 }
 
+// a [N, K] matrix whose rows may sit at a wider pitch (a view of an [N, pitch] buffer): usable as it is by the stream entries
+static bool row_strided(const Tensor &t) { return t.dim() == 2 && t.stride(1) == 1 && (t.size(0) <= 1 || t.stride(0) >= t.size(1)); }
+
+std::tuple<Tensor, Tensor> spmm_fw(const Tensor &rowptr_, const Tensor &col_, const optional<Tensor> &value_,
+                                   const Tensor &mat_, int reduction, const Plan &plan, bool want_arg);
+
+// A 16-bit `mat`: the native entry when the reduction is sum / mean, the plan is a stream plan of the sum kernel's geometry and
+// isplib_stream16_serves accepts the operand as it lies (a row-strided view keeps its pitch) or packed; else the conversion route.
+std::tuple<Tensor, Tensor> spmm_fw_half(const Tensor &rowptr_, const Tensor &col_, const optional<Tensor> &value_,
+                                        const Tensor &mat_, int reduction, const Plan &plan, bool want_arg) {
+   TORCH_CHECK(mat_.dim() == 2, "isplib: `mat` must be 2-D [N, K] (csrc/fusedmm.cpp:121-122)");
+   TORCH_CHECK(rowptr_.dim() == 1 && rowptr_.numel() >= 1, "isplib: `rowptr` must be 1-D with M+1 entries");
+   const int64_t M = rowptr_.numel() - 1, N = mat_.size(0), K = mat_.size(1), nnz = col_.numel();
+   const bool sum_op = reduction == R_SUM || reduction == R_MEAN;
+   if (sum_op && is_stream_plan(plan) && plan.size() == 8 && M > 0 && K > 0 && rowptr_.device() == mat_.device()) {
+      c10::DeviceGuard guard(mat_.device());
+      const bool as_is = row_strided(mat_) && (reinterpret_cast<uintptr_t>(mat_.data_ptr()) & 3) == 0 &&
+                         isplib_stream16_serves(N, K, N > 1 ? mat_.stride(0) : K, K, nnz);
+      if (as_is || isplib_stream16_serves(N, K, K, K, nnz)) {
+         const Tensor mat = as_is ? mat_ : mat_.contiguous();
+         const int64_t ldy = N > 1 ? mat.stride(0) : K;
+         const Tensor rowptr = rowptr_.contiguous();
+         const isplib_stream_plan sp = stream_plan_of(plan);
+         Tensor out = at::empty({M, K}, mat.options());
+         const size_t ws = isplib_spmm_stream_workspace_bytes(&sp);
+         Tensor work = at::empty({(int64_t)ws}, mat.options().dtype(at::kByte));
+         const int64_t *rp = rowptr.data_ptr<int64_t>();
+         const int st = fusedMM_csr_stream16_hip(reduction == R_MEAN ? ISPLIB_MSG_SPMM_MEAN : ISPLIB_MSG_SPMM_SUM,
+                                                 mat.scalar_type() == at::kBFloat16 ? ISPLIB_DTYPE_BF16 : ISPLIB_DTYPE_F16, M, N, K, nnz, rp, rp + 1,
+                                                 &sp, mat.data_ptr(), ldy, out.data_ptr(), K, work.data_ptr(), ws, current_stream(mat));
+         check_status(st, "fusedMM_csr_stream16_hip");
+         return std::make_tuple(out, Tensor());
+      }
+   }
+   auto r = spmm_fw(rowptr_, col_, value_, mat_.to(at::kFloat), reduction, plan, want_arg);
+   return std::make_tuple(std::get<0>(r).to(mat_.scalar_type()), std::get<1>(r));
+}
+
 // want_arg = false (max / min through the *_values operators: nobody will ask which edge won): on a stream plan the
 // launch then leaves the positions out altogether (isplib_hip.h: fusedMM_csr_stream_minmax_hip with z_arg = NULL) and the
 // second tensor of the result is undefined; every other schedule computes them as always
@@ -264,7 +316,15 @@ std::tuple<Tensor, Tensor> spmm_fw(const Tensor &rowptr_, const Tensor &col_, co
                                    const Tensor &mat_, int reduction, const Plan &plan = Plan(), bool want_arg = true) {
    check_index(rowptr_, "rowptr");
    check_index(col_, "col");
-   check_float(mat_, "mat");
+   check_feature(mat_, "mat");
+   if (value_.has_value() && value_->defined() && is_half(*value_)) {         // the weights are fp32 everywhere
+      check_feature(*value_, "value");
+      return spmm_fw(rowptr_, col_, optional<Tensor>(value_->to(at::kFloat)), mat_, reduction, plan, want_arg);
+   }
+   if (is_half(mat_)) {
+      if (value_.has_value() && value_->defined()) check_float(*value_, "value");
+      return spmm_fw_half(rowptr_, col_, value_, mat_, reduction, plan, want_arg);
+   }
    TORCH_CHECK(mat_.dim() == 2, "isplib: `mat` must be 2-D [N, K] (csrc/fusedmm.cpp:121-122)");
    TORCH_CHECK(rowptr_.dim() == 1 && rowptr_.numel() >= 1, "isplib: `rowptr` must be 1-D with M+1 entries");
    c10::DeviceGuard guard(mat_.device());
@@ -383,8 +443,9 @@ struct Transposed {
 };
 
 // A^T operands built on the device (isplib/__init__.py:79-80 / :86-99 equivalents)
-Transposed build_transpose(const Tensor &rowptr, const Tensor &col, const Tensor &value, int64_t ncols, bool mean) {
+Transposed build_transpose(const Tensor &rowptr, const Tensor &col, const Tensor &value_, int64_t ncols, bool mean) {
    c10::DeviceGuard guard(col.device());
+   const Tensor value = as_float(value_);
    const int64_t M = rowptr.numel() - 1, nnz = col.numel();
    Transposed t;
    t.colptr = at::empty({ncols + 1}, rowptr.options());
@@ -404,7 +465,7 @@ Transposed build_transpose(const Tensor &rowptr, const Tensor &col, const Tensor
 Tensor sddmm(const Tensor &rowptr, const Tensor &col, const Tensor &mat, const Tensor &grad_out, bool mean,
              const std::vector<Tensor> &plan = {}, const Tensor &value = Tensor()) {
    c10::DeviceGuard guard(mat.device());
-   const Tensor g = grad_out.contiguous(), y = mat.contiguous();
+   const Tensor g = as_float(grad_out).contiguous(), y = as_float(mat).contiguous();      // 16-bit operands: dA is formed in fp32
    const int64_t M = rowptr.numel() - 1, N = y.size(0), K = y.size(1);
    Tensor dval = at::empty({col.numel()}, y.options());
    const int64_t *rp = rowptr.data_ptr<int64_t>();
@@ -440,9 +501,6 @@ Tensor sddmm(const Tensor &rowptr, const Tensor &col, const Tensor &mat, const T
 
 // sum-SpMM with unit weights and the fused epilogue out = act(row_scale * (A y + self) + bias); the fold kernel
 // applies it when a task plan is given (isplib_epilogue), otherwise it is composed from ATen ops.
-// a [N, K] matrix whose rows may sit at a wider pitch (a view of an [N, pitch] buffer): usable as it is by the stream entry
-static bool row_strided(const Tensor &t) { return t.dim() == 2 && t.stride(1) == 1 && (t.size(0) <= 1 || t.stride(0) >= t.size(1)); }
-
 Tensor epilogue_spmm(const Tensor &rowptr, const Tensor &col, const Plan &plan, const Tensor &y_, const Tensor &self_,
                      const Tensor &row_scale, const Tensor &bias, bool relu) {
    const int64_t M = rowptr.numel() - 1, N = y_.size(0), K = y_.size(1), nnz = col.numel();
@@ -549,10 +607,10 @@ class SpmmSum : public torch::autograd::Function<SpmmSum> {
    static variable_list backward(AutogradContext *ctx, variable_list grad_outs) {
       OpTimer timer("FUSEDMM_SPMM_SUM_BW", grad_outs[0]);
       const bool has_value = ctx->saved_data["has_value"].toBool();
-      auto grad_out = grad_outs[0];
       auto saved = ctx->get_saved_variables();
       auto rowptr = saved[1], col = saved[2], value = saved[3], colptr = saved[4], mat = saved[6],
            value_sel = saved[7], row_sel = saved[8];
+      auto grad_out = grad_outs[0].to(mat.scalar_type());       // a gradient of another float type is brought to mat's
 
       auto grad_value = Variable();
       if (has_value && ctx->needs_input_grad(ctx->saved_data["value_edge"].toInt()))   // :269-272 (SDDMM, commented out there)
@@ -600,10 +658,10 @@ class SpmmMean : public torch::autograd::Function<SpmmMean> {
    static variable_list backward(AutogradContext *ctx, variable_list grad_outs) {
       OpTimer timer("FUSEDMM_SPMM_MEAN_BW", grad_outs[0]);
       const bool has_value = ctx->saved_data["has_value"].toBool();
-      auto grad_out = grad_outs[0];
       auto saved = ctx->get_saved_variables();
       auto rowptr = saved[1], col = saved[2], value = saved[3], colptr = saved[5], mat = saved[7], new_row = saved[8],
            new_rowcount = saved[9];
+      auto grad_out = grad_outs[0].to(mat.scalar_type());
 
       auto grad_value = Variable();
       if (has_value && ctx->needs_input_grad(ctx->saved_data["value_edge"].toInt()))
@@ -623,9 +681,11 @@ class SpmmMean : public torch::autograd::Function<SpmmMean> {
             grad_mat = std::get<0>(spmm_fw(colptr, new_row, optional<Tensor>(new_rowcount), grad_out, R_SUM,
                                            ctx->saved_data["plan_t"].toTensorVector()));
          } else if (unit_planned) {
-            const Tensor deg = (rowptr.slice(0, 1) - rowptr.slice(0, 0, -1)).clamp_min(1).to(grad_out.scalar_type());
-            const Tensor gy = grad_out / deg.unsqueeze(1);
-            grad_mat = std::get<0>(spmm_fw(colptr, new_row, c10::nullopt, gy, R_SUM, ctx->saved_data["plan_t"].toTensorVector()));
+            // (a 16-bit dY: gy is formed and kept in fp32 -- rounding it here and the sum again would round twice -- so the
+            // SpMM on A^T takes the conversion route)
+            const Tensor deg = (rowptr.slice(0, 1) - rowptr.slice(0, 0, -1)).clamp_min(1).to(at::kFloat);
+            const Tensor gy = as_float(grad_out) / deg.unsqueeze(1);
+            grad_mat = std::get<0>(spmm_fw(colptr, new_row, c10::nullopt, gy, R_SUM, ctx->saved_data["plan_t"].toTensorVector())).to(mat.scalar_type());
          } else {
             auto t = build_transpose(rowptr, col, has_value ? value : Tensor(), mat.size(0), true);
             grad_mat = std::get<0>(spmm_fw(t.colptr, t.row_t, optional<Tensor>(t.val_t), grad_out, R_SUM));
@@ -658,14 +718,15 @@ class SpmmMinMax : public torch::autograd::Function<SpmmMinMax<RED>> {
       const bool has_value = ctx->saved_data["has_value"].toBool();
       auto saved = ctx->get_saved_variables();
       auto col = saved[0], value = saved[1], mat = saved[2], arg_out = saved[3];
-      const Tensor grad_out = grad_outs[0].contiguous();
+      const Tensor grad_out = as_float(grad_outs[0]).contiguous();      // 16-bit operands: the gradients are formed in fp32
+      if (has_value) value = as_float(value);
       // edges: rowptr 0, col 1, value 2 (if present), mat last
       const bool need_val = has_value && ctx->needs_input_grad(2);
       const bool need_mat = ctx->needs_input_grad(has_value ? 3 : 2);
       auto grad_value = Variable(), grad_mat = Variable();
       if (need_val || need_mat) {
          c10::DeviceGuard guard(mat.device());
-         const Tensor y = mat.contiguous();
+         const Tensor y = as_float(mat).contiguous();
          const int64_t M = arg_out.size(0), N = y.size(0), K = y.size(1), nnz = col.numel();
          if (need_val) grad_value = at::empty({nnz}, y.options());
          if (need_mat) grad_mat = at::empty({N, K}, y.options());
@@ -687,6 +748,7 @@ class SpmmMinMax : public torch::autograd::Function<SpmmMinMax<RED>> {
             check_status(st, "isplib_spmm_minmax_bw_hip");
          }
       }
+      if (grad_mat.defined() && is_half(mat)) grad_mat = grad_mat.to(mat.scalar_type());      // rounded once
       return {Variable(), Variable(), grad_value, grad_mat, Variable()};
    }
 };

@@ -134,6 +134,8 @@ class RowPartition:
         arg holds GLOBAL CSR positions (local position + this rank's edge offset;
         the 'no winner' sentinel becomes the global nnz)."""
         from . import cabi
+        if x_shard.dtype != torch.float32:
+            raise TypeError(f"isplib_amd: the row partition takes float32 features, got {x_shard.dtype}")
         k = x_shard.size(1)
         buf = self.gather_buffer(k, x_shard.device) if buf is None else buf
         self.all_gather(x_shard, buf)
@@ -450,6 +452,8 @@ class DistGraph:
         return self._bwd_mean
 
     def matmul(self, x_local: torch.Tensor, reduce: str = "sum") -> torch.Tensor:
+        if x_local.dtype != torch.float32:
+            raise TypeError(f"isplib_amd: DistGraph.matmul takes float32 features, got {x_local.dtype}")
         if reduce in ("sum", "add"):
             return _DistSpMM.apply(x_local, self)
         if reduce == "mean":

@@ -22,6 +22,7 @@ Differences from the reference, each a defect there:
 
 Environment: ISPLIB_SLICES=<n> forces the task list with n column slices (0: plain kernel); ISPLIB_STREAM=0 keeps
 sum / mean off the stream schedule; ISPLIB_STREAM_GEOM=streams:slices:chunk forces it with that plan geometry;
+ISPLIB_HALF=auto|native|convert picks the route of bf16 / fp16 features (half_route);
 ISPLIB_TUNE_FILE names a tuning table to load at import; ISPLIB_DEBUG=1 prints per-operator device times.
 """
 from __future__ import annotations
@@ -249,18 +250,49 @@ def stream_minmax_rule(storage: SparseStorage, m: int, n: int, k: int):
     return None if geom is None else (geom[0], skew_adjusted(storage, geom[1], cap=512), geom[2])
 
 
+HALF_DTYPES = (torch.bfloat16, torch.float16)
+
+
+def half_route(dtype, reduce: str, k: int, pitch: int, mode: Optional[str] = None, streams: Optional[int] = 4, weighted: bool = False,
+               n: int = 1, nnz: int = 0) -> str:
+    """Which way a matmul with features of `dtype` goes: "fp32" (float32: the path as it always was), "native" (bf16 / fp16 on
+    the 16-bit stream kernel, fusedMM_csr_stream16_hip) or "convert" (bf16 / fp16 through `x.float()` -> the fp32 path -> `.to(dtype)`:
+    the same result, the finished fp32 row rounded once).  Any other dtype raises TypeError.  A pure function -- no device, no
+    library call:
+      * native needs a sum / mean, a stream plan for the call (`streams` = its slot count; None: the call has none) and a shape
+        inside the entry's domain (cabi.stream16_serves) at the operand's own row pitch or, failing that, packed (pitch = k);
+      * `mode` is ISPLIB_HALF (None: read from the environment; default "auto"): "convert" always converts, "native" goes native
+        wherever the above holds, "auto" only in the classes (slot width x weighted plan) where every native run measured faster
+        than every run of the conversion route (cabi.stream16_native_pays, profiles/stream16_ab.txt).  None of them raises."""
+    if dtype == torch.float32:
+        return "fp32"
+    if dtype not in HALF_DTYPES:
+        raise TypeError(f"isplib_amd: features must be float32, bfloat16 or float16, got {dtype}")
+    from . import cabi
+    if mode is None:
+        mode = os.environ.get("ISPLIB_HALF", "auto")
+    if mode == "convert" or reduce not in ("sum", "add", "mean") or streams is None:
+        return "convert"
+    if not (cabi.stream16_serves(n, k, pitch, k, nnz) or cabi.stream16_serves(n, k, k, k, nnz)):
+        return "convert"
+    if mode == "native":
+        return "native"
+    return "native" if cabi.stream16_native_pays(int(streams), bool(weighted)) else "convert"
+
+
 def spmm_autotuned(src, other: torch.Tensor, reduce: str = "sum") -> torch.Tensor:
     """``torch_sparse.matmul(src, other, reduce)`` on the HIP path (isplib/__init__.py:48-157)."""
     if reduce not in ("sum", "add", "mean", "max", "min"):
         raise ValueError(f"isplib: unknown reduce '{reduce}' (expected sum|add|mean|max|min)")
     if not isinstance(other, torch.Tensor) or not other.is_cuda:
         raise RuntimeError("isplib_amd: `other` must be a GPU tensor -- there is no CPU path")
-    if other.dtype != torch.float32:
-        raise TypeError(f"isplib_amd: only float32 features are supported (csrc/fusedmm.cpp:44), got {other.dtype}")
+    if other.dtype != torch.float32 and other.dtype not in HALF_DTYPES:
+        raise TypeError(f"isplib_amd: features must be float32, bfloat16 or float16 (csrc/fusedmm.cpp:44 takes float32 only), got {other.dtype}")
+    half = other.dtype != torch.float32
     s = _storage_of(src, other)
     rowptr, col, value = s._rowptr, s._col, s._value
-    if value is not None and value.dtype != other.dtype:
-        value = value.to(other.dtype)                                # :63-64
+    if value is not None and value.dtype != (torch.float32 if half else other.dtype):
+        value = value.to(torch.float32 if half else other.dtype)     # :63-64 (16-bit features: the weights stay fp32)
     squeeze = other.dim() == 1
     mat = other.unsqueeze(-1) if squeeze else other
     needs_grad = torch.is_grad_enabled() and mat.requires_grad       # :69-73
@@ -276,6 +308,16 @@ def spmm_autotuned(src, other: torch.Tensor, reduce: str = "sum") -> torch.Tenso
         geom = choose_stream_minmax(s, m_rows, mat.size(0), k)
         plan = s.stream_plan(False, geom, "minmax") if geom is not None else None
     ran = ("stream",) + tuple(int(v) for v in geom) if plan is not None else None
+    if half:
+        # bf16 / fp16 features: the 16-bit stream kernel on the same plan, or the conversion route (half_route)
+        pitch = mat.stride(0) if mat.dim() == 2 and mat.size(0) > 1 and mat.stride(-1) == 1 else k
+        route = half_route(mat.dtype, reduce, k, pitch, None, None if plan is None else int(geom[0]), s._value is not None,
+                           mat.size(0), col.numel())
+        if route == "convert":
+            out = spmm_autotuned(src, other.to(torch.float32), reduce)
+            s._last_schedule = ("convert",) + tuple(s._last_schedule or ())
+            return out.to(other.dtype)
+        ran = ("stream16",) + tuple(int(v) for v in geom)
     if plan is None:
         n_sl = choose_slices(s, mat.size(0), k, reduce in ("max", "min"))
         plan = s.plan(n_sl)                                          # per-graph, built once on the device
