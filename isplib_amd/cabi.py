@@ -497,11 +497,20 @@ def check_fusedmm_operands(imessage: int, m: int, x, y, plan=None, x_read: Optio
             raise ValueError(f"isplib_amd: the task plan was built for {(seg_off.numel() - 1) // max(plan.slices, 1)} rows, the graph has {m}")
 
 
-def fusedmm(imessage: int, rowptr, col, val, x, y, sop_udef="none", sop_param: float = 0.0, check: bool = True, plan=None):
+def _fusedmm_out(out, m: int, k: int, y):
+    if out is None:
+        return torch.empty((m, k), dtype=torch.float32, device=y.device)
+    if out.dtype != torch.float32 or out.device != y.device or tuple(out.shape) != (m, k) or not out.is_contiguous():
+        raise ValueError(f"isplib_amd: `out` must be a contiguous float32 [{m}, {k}] tensor on {y.device}")
+    return out
+
+
+def fusedmm(imessage: int, rowptr, col, val, x, y, sop_udef="none", sop_param: float = 0.0, check: bool = True, plan=None, out=None):
     """The generic FusedMM pipeline (fusedMM_csr_udef_hip): z[i,:] = AOP_j VSC(SOP(ROP(VOP(x_i, y_j))), .) over the
     stored entries of row i.  `imessage` is a word built from VOP/ROP/SOP/VSC/AOP (or PATTERNS[name][0]);
     `sop_udef` names the built-in function a SOP_UDEF stage stands for.  With `plan` (isplib_amd.plan.TaskPlan) the
-    task form runs (fusedMM_csr_udef_tasks_hip).  Returns (status, z, z_arg | None)."""
+    task form runs (fusedMM_csr_udef_tasks_hip).  `out`: a contiguous fp32 [m, k] tensor to write z into (every element is
+    written; the tests hand in a NaN-filled one).  Returns (status, z, z_arg | None)."""
     check_fusedmm_operands(imessage, rowptr.numel() - 1, x, y, plan)
     rowptr = _dev(rowptr, "rowptr", torch.int64)
     col = _dev(col, "col", torch.int64)
@@ -511,7 +520,7 @@ def fusedmm(imessage: int, rowptr, col, val, x, y, sop_udef="none", sop_param: f
     if x is not None:
         x = _dev(x, "x", torch.float32)
     m, n, k = rowptr.numel() - 1, y.size(0), y.size(1)
-    z = torch.empty((m, k), dtype=torch.float32, device=y.device)
+    z = _fusedmm_out(out, m, k, y)
     arg = torch.empty((m, k), dtype=torch.int64, device=y.device) if ((imessage >> 16) & 0xF) in (2, 3) else None
     rp = rowptr.data_ptr()
     kind = SOP_UDEF[sop_udef] if isinstance(sop_udef, str) else int(sop_udef)
@@ -548,16 +557,16 @@ def fusedmm_stream_geometry(streams: int = 2):
     return int(rpw.value), int(res.value)
 
 
-def fusedmm_stream(imessage: int, rowptr, nnz: int, plan, x, y, sop_udef="none", sop_param: float = 0.0, check: bool = True):
+def fusedmm_stream(imessage: int, rowptr, nnz: int, plan, x, y, sop_udef="none", sop_param: float = 0.0, check: bool = True, out=None):
     """The two SDDMM-fused words on the stream front end (fusedMM_csr_udef_stream_hip); `plan`: a NativeStreamPlan built with
-    fusedmm=True.  Returns (status, z)."""
+    fusedmm=True; `out` as for fusedmm().  Returns (status, z)."""
     if x is None:
         raise ValueError("isplib_amd: the stream FusedMM words read `x`")
     check_fusedmm_operands(imessage, rowptr.numel() - 1, x, y, plan, x_read=True)   # the kernel loads x[i] of every owned row
     rowptr = _dev(rowptr, "rowptr", torch.int64)
     x, y = _dev(x, "x", torch.float32), _dev(y, "y", torch.float32)
     m, n, k = rowptr.numel() - 1, y.size(0), y.size(1)
-    z = torch.empty((m, k), dtype=torch.float32, device=y.device)
+    z = _fusedmm_out(out, m, k, y)
     kind = SOP_UDEF[sop_udef] if isinstance(sop_udef, str) else int(sop_udef)
     work = plan.workspace()
     rp = rowptr.data_ptr()

@@ -23,7 +23,8 @@
 namespace isplib {
 
 // (reciprocals by v_rcp_f32, 1 ulp: an IEEE division is ten vector instructions in a loop that is bound by them -- the ISA of the
-// first form of this kernel had 39 per step against the SpMM's 13 -- and the results are held to 1e-4 of the largest |z| anyway)
+// first form of this kernel had 39 per step against the SpMM's 13.  What that costs in accuracy is measured, not assumed:
+// profiles/fusedmm_sop_accuracy.txt, and DESIGN.md 4.6a for the per-element contract the results are held to)
 __device__ __forceinline__ float sop_menu(int kind, float s, float p) {
    switch (kind) {
       case ISPLIB_SOP_SIGMOID: return __builtin_amdgcn_rcpf(1.0f + __expf(-s));
