@@ -110,6 +110,19 @@ static inline int isplib_stream16_serves(int64_t n, int64_t k, int64_t ldy, int6
    return k >= ISPLIB_K_MIN && n < ISPLIB_STREAM_N_END && ldy < ISPLIB_STREAM_LDY_END && nnz < ISPLIB_STREAM_NNZ_END &&
           isplib_rows_within(n, ldy, 2ull * ISPLIB_DENSE_BYTES_MAX) && (k % 2) == 0 && (ldy % 2) == 0 && (ldz % 2) == 0;
 }
+/* the 16-bit row entry (fusedMM_csr_rows16_hip: bf16 / fp16 dense operands on the plain row-per-wave schedule, sum / mean) does:
+ * a lane's 16-byte gather holds eight columns, so k >= ISPLIB_ROWS16_K_MIN; k, ldy, ldz all even -- every 16-byte gather and store
+ * is then 4-byte aligned, the last vector of a ragged row (shifted back to end at column k) included; ONE descriptor with 32-bit
+ * byte offsets at 2 bytes per element, n*ldy*2 <= ISPLIB_DENSE_BYTES_MAX; n < 2^31 (32-bit column ids times the pitch); and
+ * k < ISPLIB_ROWS16_K_END, so that a masked lane's offset (ISPLIB_DENSE_OOB_OFFSET + its column's bytes) cannot wrap.  With a row
+ * order the entry also needs m < 2^31, and it refuses a y or z base that is not 4-byte aligned.  What this refuses is served by
+ * converting the operand to fp32 (the layers above do that; nothing raises). */
+#define ISPLIB_ROWS16_K_MIN            8
+#define ISPLIB_ROWS16_K_END            (1 << 24)
+static inline int isplib_rows16_serves(int64_t n, int64_t k, int64_t ldy, int64_t ldz) {
+   return k >= ISPLIB_ROWS16_K_MIN && k < ISPLIB_ROWS16_K_END && n < (1LL << 31) && isplib_rows_within(n, ldy, 2ull * ISPLIB_DENSE_BYTES_MAX) &&
+          (k % 2) == 0 && (ldy % 2) == 0 && (ldz % 2) == 0;
+}
 #define ISPLIB_MINMAX_BW_PAIRS_END     0xFFFFFFFEu  /* the sort-based max / min backward: m*k (row, feature) pairs < this */
 #define ISPLIB_MINMAX_BW_KEYS_MAX      0xFFFFFFFEu  /* 32-bit sort keys: n*k destinations and one key behind them, n*k + 1 < 2^32 */
 #define ISPLIB_OWNER_WORLD_MAX         64           /* ranks of the owner-bucketed exchange: their row cuts travel as a kernel argument */
@@ -489,6 +502,40 @@ static inline int isplib_stream16_native_pays(int streams, int weighted) {
    return 0;      /* measured (Reddit shape, bf16, K = 64 / 128): (4, unit), (4, weighted), (2, weighted) lose or tie; the rest unmeasured */
 }
 int    isplib_stream16_auto(int streams, int weighted);      /* the same rule as a symbol (for hosts that cannot include this header) */
+/*
+ * The plain schedule (one CSR row per wavefront, fusedMM_csr_hip / fusedMM_csr_ordered_hip) for a dense operand of 16-bit
+ * elements, sum / mean: a lane's 16-byte gather holds EIGHT columns, so a row of k columns takes half the gather instructions and
+ * half the cache lines of the fp32 kernel -- and no fp32 copy of the operand is made.  Weights are fp32 (`val`, may be NULL: unit
+ * weights); `row_order` (device, m int32, position -> row; NULL = index order) is fusedMM_csr_ordered_hip's.  The contract is
+ * fusedMM_csr_stream16_hip's: products, sums and the mean's division in fp32, the finished row rounded ONCE to nearest even -- NaN
+ * stays NaN, bf16 keeps subnormals, fp16 overflows to +-Inf; an empty row is 0.  No atomics: two launches give equal bits and any
+ * row order gives the bits of index order.  Bit equality with "convert, run fusedMM_csr_hip, convert back" is NOT promised on
+ * real-valued data: the two kernels cut a row into edge slots differently, so the fp32 value before rounding may differ in its
+ * last bits (where the fp32 sums are exact in any order, e.g. small integers, the bits are equal).
+ * Domain: isplib_rows16_serves(n, k, ldy, ldz); with a row order m < 2^31.  Refused before any launch: another message word
+ * (max / min included: ISPLIB_NO_OPT_IMPL), and with ISPLIB_FAIL another dtype, a shape outside the domain, ldy < k or ldz < k, a
+ * null operand, a y or z base that is not 4-byte aligned.  m == 0 or k == 0 succeeds without a launch.
+ * isplib_rows16_native_pays is the measured rule of the layers above (profiles/rows16_ab.txt): a class of calls is
+ * (operand beyond 256 MiB at 2 bytes per element or not) x (rows in a community order or not) x (weighted or not), and it is
+ * nonzero for a class only where EVERY run of this entry was faster than EVERY run of the conversion route on every measured
+ * shape of that class.
+ */
+int    fusedMM_csr_rows16_hip(int32_t imessage /* ISPLIB_MSG_SPMM_SUM | _MEAN */, int dtype /* ISPLIB_DTYPE_BF16 | _F16 */,
+                              int64_t m, int64_t n, int64_t k, int64_t nnz, const float *val /* fp32, may be NULL */,
+                              const int64_t *indx, const int64_t *pntrb, const int64_t *pntre,
+                              const int32_t *row_order /* optional */, const void *y, int64_t ldy, void *z, int64_t ldz, void *stream);
+static inline int isplib_rows16_native_pays(int64_t n, int64_t ldy, int ordered, int weighted) {
+   /* measured (profiles/rows16_ab.txt: ogbn-products shape, Chung-Lu and SBM twin, bf16, K = 128 / 256; inside the Infinity Cache
+    * the shape at a quarter and at a fiftieth of its size and a Cora-shaped graph, K = 16 ... 128): every class measured pays,
+    * unit and weighted alike -- beyond 256 MiB in index order 0.46-0.48 of the conversion route's time, in a community order
+    * 0.49-0.61, inside 256 MiB in index order 0.45-0.92 (the narrow, launch-bound end saves the two conversion launches).  The one
+    * class not measured (inside 256 MiB AND a community order: the layers above never look for an order there) stays on convert. */
+   const int beyond = n > 0 && ldy > 0 && (double)n * (double)ldy * 2.0 > 256.0 * 1048576.0;
+   (void)weighted;
+   return (beyond || !ordered) ? 1 : 0;
+}
+int    isplib_rows16_auto(int64_t n, int64_t ldy, int ordered, int weighted);      /* the same rule as a symbol */
+int    isplib_rows16_domain(int64_t n, int64_t k, int64_t ldy, int64_t ldz);       /* isplib_rows16_serves as a symbol */
 /*
  * Staged column panels (sum / mean on 64-column slots only).  What a gather of a 128-byte line costs depends on the line's
  * ADDRESS: profiles/line_classes.txt (scripts/ubench/line_classes.hip) is the table, DESIGN.md section 5 reads it.  Before the

@@ -57,6 +57,25 @@ def stream16_native_pays(streams: int, weighted: bool) -> bool:
     return False
 
 
+ROWS16_K_MIN, ROWS16_K_END = 8, 2 ** 24   # the 16-bit row entry: eight columns per 16-byte gather; a masked lane's offset must not wrap
+
+
+def rows16_serves(n: int, k: int, ldy: int, ldz: int) -> bool:
+    """isplib_rows16_serves of the header: the 16-bit row entry (fusedMM_csr_rows16_hip: bf16 / fp16 operands on the plain
+    row-per-wave schedule, sum / mean) serves an n x k operand at leading dimension ldy (elements) and output pitch ldz."""
+    return (ROWS16_K_MIN <= k < ROWS16_K_END and n < 2 ** 31 and (n <= 0 or n * ldy * 2 <= DENSE_BYTES_MAX) and
+            k % 2 == 0 and ldy % 2 == 0 and ldz % 2 == 0)
+
+
+def rows16_native_pays(n: int, ldy: int, ordered: bool, weighted: bool) -> bool:
+    """isplib_rows16_native_pays of the header: the classes of calls -- (operand beyond 256 MiB at 2 bytes per element or not) x
+    (rows in a community order or not) x (weighted or not) -- in which every native run measured faster than every run of the
+    conversion route (profiles/rows16_ab.txt: every measured class does; operand inside 256 MiB AND a community order was not
+    measured and stays on convert); tests/test_rows16_host.py compares the two."""
+    beyond = n > 0 and ldy > 0 and n * ldy * 2 > (256 << 20)
+    return bool(beyond or not ordered)
+
+
 def owner_exchange_serves(m: int, k: int, world: int, cuts) -> bool:
     """isplib_owner_exchange_serves of the header: m x k winners split for `world` owners at the row boundaries `cuts`."""
     if not 1 <= world <= OWNER_WORLD_MAX or m < 0 or k < 0 or m * k >= MINMAX_BW_PAIRS_END:
@@ -101,6 +120,7 @@ EXPORTS = (
     "fusedMM_csr_ordered_hip", "isplib_community_order_hip", "isplib_community_order_workspace_bytes", "isplib_order_locality_hip",
     "isplib_graph_set_row_order", "isplib_plain_panels",
     "fusedMM_csr_stream16_hip", "isplib_stream16_auto",
+    "fusedMM_csr_rows16_hip", "isplib_rows16_auto", "isplib_rows16_domain",
 )
 
 # include/isplib_hip_experimental.h (libisplib_hip_exp.so): forms measured slower than the defaults; tests and experiment scripts only
@@ -309,6 +329,12 @@ def lib() -> ctypes.CDLL:
                                                _vp, _i64, _vp, ctypes.c_size_t, _vp]
         L.isplib_stream16_auto.restype = ctypes.c_int
         L.isplib_stream16_auto.argtypes = [ctypes.c_int, ctypes.c_int]
+        L.fusedMM_csr_rows16_hip.restype = ctypes.c_int
+        L.fusedMM_csr_rows16_hip.argtypes = [_i32, ctypes.c_int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]
+        L.isplib_rows16_auto.restype = ctypes.c_int
+        L.isplib_rows16_auto.argtypes = [_i64, _i64, ctypes.c_int, ctypes.c_int]
+        L.isplib_rows16_domain.restype = ctypes.c_int
+        L.isplib_rows16_domain.argtypes = [_i64, _i64, _i64, _i64]
         _sigs_set = True
     return L
 
@@ -1145,6 +1171,71 @@ def spmm_stream16(rowptr, nnz: int, plan, y, reduce: str = "sum", workspace=None
     if workspace is None:
         workspace = plan.workspace()
     fusedMM_csr_stream16_hip(MESSAGE[reduce], rowptr, nnz, plan, y, out, workspace)
+    return out
+
+
+def fusedMM_csr_rows16_hip(imessage: int, rowptr, col, val, order, y, z, check: bool = True, dtype=None, k=None, ldy=None, ldz=None) -> int:
+    """Raw boundary call of the 16-bit row SpMM (sum / mean), for operands the entry may refuse: it hands over what it is given
+    (`dtype`, `k`, `ldy`, `ldz`: override what the tensors say -- refusal tests; the entry refuses before it reads anything).
+    Callers that want their operands checked use spmm_rows16."""
+    m, n = rowptr.numel() - 1, y.size(0)
+    k = y.size(1) if k is None else int(k)
+    code = HALF_DTYPES.get(y.dtype, 0) if dtype is None else int(dtype)
+    rp = rowptr.data_ptr()
+    with torch.cuda.device(y.device):
+        st = lib().fusedMM_csr_rows16_hip(int(imessage), code, m, n, k, col.numel(), _ptr(val), _ptr(col), ctypes.c_void_p(rp),
+                                          ctypes.c_void_p(rp + 8), _ptr(order),
+                                          _ptr(y), (y.stride(0) if n > 1 else max(k, y.stride(0))) if ldy is None else int(ldy),
+                                          _ptr(z), (z.stride(0) if m > 1 else max(k, z.stride(0))) if ldz is None else int(ldz), _stream(y.device))
+    if check:
+        _check(st, "fusedMM_csr_rows16_hip")
+    return st
+
+
+def spmm_rows16(rowptr, col, val, y, reduce: str = "sum", order=None, out=None):
+    """The 16-bit row SpMM (sum / mean) of a bf16 / fp16 `y` [n, k]: returns `out` [m, k] of y's dtype (allocated when not given; a
+    row-strided view is written at its own pitch).  `val`: fp32 weights or None; `order`: int32 [m], position -> row, or None.
+    Every operand is checked BEFORE the call -- a mis-shaped one is an out-of-bounds device read: rowptr / col int64 on y's device,
+    rowptr ascending from 0 to col.numel(), every column id inside [0, n), the shape inside isplib_rows16_serves, `out` [m, k] of
+    the same dtype at an even pitch, `order` a permutation's length."""
+    if reduce not in ("sum", "add", "mean"):
+        raise ValueError(f"isplib_amd: spmm_rows16 serves sum / mean, got '{reduce}'")
+    if not isinstance(y, torch.Tensor) or not y.is_cuda or y.dim() != 2:
+        raise ValueError("isplib_amd: `y` must be a 2-D GPU tensor [n, k]")
+    if y.dtype not in HALF_DTYPES:
+        raise TypeError(f"isplib_amd: `y` must be bfloat16 or float16, got {y.dtype} (float32: spmm)")
+    rowptr = _dev(rowptr, "rowptr", torch.int64)
+    col = _dev(col, "col", torch.int64)
+    n, k = y.size(0), y.size(1)
+    m = rowptr.numel() - 1
+    if m < 0 or rowptr.device != y.device or col.device != y.device:
+        raise ValueError("isplib_amd: rowptr (m + 1 entries), col and y must be on one device")
+    if k > 0 and y.stride(1) != 1:
+        raise ValueError("isplib_amd: `y` must have unit inner stride")
+    if val is not None:
+        val = _dev(val, "val", torch.float32)
+        if val.numel() != col.numel() or val.device != y.device:
+            raise ValueError("isplib_amd: `val` must hold one float32 weight per entry of `col`, on y's device")
+    if order is not None:
+        order = _dev(order, "order", torch.int32)
+        if order.numel() != m or order.device != y.device or (m > 0 and (int(order.min()) < 0 or int(order.max()) >= m)):
+            raise ValueError("isplib_amd: `order` must hold one int32 row in [0, m) per position, on y's device")
+    if m > 0 and (int(rowptr[0]) != 0 or int(rowptr[-1]) != col.numel() or bool((rowptr[1:] < rowptr[:-1]).any())):
+        raise ValueError("isplib_amd: rowptr must ascend from 0 to col.numel()")
+    if col.numel() > 0 and (int(col.min()) < 0 or int(col.max()) >= n):
+        raise ValueError(f"isplib_amd: column ids must lie in [0, {n})")
+    ldy = y.stride(0) if n > 1 else max(k, y.stride(0))
+    if out is None:
+        out = torch.empty((m, k), dtype=y.dtype, device=y.device)
+    elif not isinstance(out, torch.Tensor) or out.device != y.device or tuple(out.shape) != (m, k) or out.dtype != y.dtype or (k > 0 and out.stride(1) != 1):
+        raise ValueError(f"isplib_amd: `out` must be a [{m}, {k}] {y.dtype} tensor on {y.device} with unit inner stride")
+    ldz = out.stride(0) if m > 1 else max(k, out.stride(0))
+    if m > 0 and k > 0:
+        if ldy < k or ldz < k or not rows16_serves(n, k, ldy, ldz):
+            raise ValueError(f"isplib_amd: outside the 16-bit row entry's domain (isplib_rows16_serves: n={n}, k={k}, ldy={ldy}, ldz={ldz})")
+        if (y.data_ptr() | out.data_ptr()) & 3:
+            raise ValueError("isplib_amd: `y` and `out` must be 4-byte aligned")
+    fusedMM_csr_rows16_hip(MESSAGE[reduce], rowptr, col, val, order, y, out)
     return out
 
 

@@ -1,0 +1,316 @@
+// spmm_rows16.hip -- the plain schedule of the SpMM (spmm.hip: one CSR row per wavefront) for dense operands of 16-bit elements
+// (bf16, fp16): fusedMM_csr_rows16_hip, sum / mean.  The row kernel on operands beyond every cache is bound by the BYTES it gathers
+// (DESIGN.md 4.2), and a 16-bit row is half the lines: a lane's gather stays 16 bytes and now holds EIGHT columns, so a slot of LPR
+// lanes covers LPR * 8 columns and a row of K columns takes half as many gather instructions as in fp32.
+//
+// Mapping: spmm_csr_kernel's plain mode -- one row per wave, WAVES rows per workgroup, blockIdx remapped so that an XCD walks a
+// contiguous range of positions, an optional row order (position -> row), rows over long_row edges taken by all waves of the
+// workgroup with a fixed-order LDS combine in fp32.  No atomics: two launches give equal bits, and any row order gives the bits of
+// index order.
+//
+// The contract (the 16-bit stream kernel's): the halves are widened in registers, products, sums and the mean's
+// division are fp32, and the finished row is rounded ONCE, to nearest even -- NaN stays NaN, bf16 keeps subnormals, fp16 overflows
+// to +-Inf.  An empty row is 0.  No max / min, no epilogue, no column-sliced form here.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/isplib_hip.h"
+#include "common.h"
+#include "gather.h"
+#include "half16.h"
+
+namespace isplib {
+
+struct Rows16Args {
+   int64_t m, k;
+   const float *val;            // fp32 weights; null = unit weights
+   const int64_t *indx, *pntrb, *pntre;
+   const void *y;               // n x ldy elements of 2 bytes
+   int64_t ldy;
+   unsigned short *z;           // m x ldz
+   int64_t ldz;
+   int mean;                    // divide by max(deg, 1)
+   int long_row;                // rows with more edges are split across the workgroup
+   unsigned nblk;               // number of row blocks
+   unsigned ybytes;             // n*ldy*2: the descriptor's size
+   const int32_t *row_order;    // position -> row, null = the identity
+};
+
+// gathers issued back to back per slot, and the occupancy the allocator is held to -- the fp32 plain kernel's 8 waves per SIMD
+// (gather.h, min_waves_of).  Four VGPRs per gather in flight as there, but eight accumulators per chunk instead of four and eight
+// widened values: at U = 8 the unit-weight bf16 kernels spill (12-28 bytes of scratch per lane), at U = 6 every single-chunk
+// kernel fits 64 VGPRs without scratch (DESIGN.md 4.2a has the counts)
+template <int NCH> constexpr int rows16_unroll() { return NCH > 1 ? 4 : 6; }
+template <int NCH> constexpr int rows16_min_blocks() { return NCH == 1 ? 8 : 1; }
+
+// the eight finished columns of a lane as 16 bytes at p (4-byte aligned: k, the pitch and the columns are even); the first `vfirst`
+// components (even) belong to the neighbouring lane -- the last vector of a row is shifted back to end at column k -- and are skipped
+template <int ELT> __device__ __forceinline__ void store_tail16x8(unsigned short *p, const float (&r)[8], int vfirst) {
+   unsigned d[4];
+#pragma unroll
+   for (int q = 0; q < 4; q++) d[q] = narrow2<ELT>(r[2 * q], r[2 * q + 1]);
+   if (vfirst == 0 && ((uintptr_t)p & 15) == 0) {
+      *reinterpret_cast<uint4 *>(p) = make_uint4(d[0], d[1], d[2], d[3]);
+   } else {
+#pragma unroll
+      for (int q = 0; q < 4; q++)
+         if (2 * q >= vfirst) reinterpret_cast<unsigned *>(p)[q] = d[q];
+   }
+}
+
+// buf_step (gather.h) at eight 16-bit columns per 16-byte gather: UU gathers per slot back to back for the edges [s, s + G*UU) of
+// the current 64-edge batch; their values are summed among themselves first and enter the running sum as ONE term
+template <int ELT, bool HAS_VAL, int LPR, int NCH, int UU>
+__device__ __forceinline__ void rows16_step(const __amdgpu_buffer_rsrc_t rsrc, unsigned off_l, float v_l, int s, int g,
+                                            const unsigned (&cbyte)[NCH], const unsigned (&poison)[NCH], float (&acc)[NCH][8]) {
+   constexpr int G = 64 / LPR;
+   v4i_t t[UU][NCH];
+   float vv[UU];
+#pragma unroll
+   for (int u = 0; u < UU; u++) {
+      const int ei = (s + u * G + g) & 63;
+      const unsigned off = (unsigned)__shfl((int)off_l, ei);
+      if (HAS_VAL) vv[u] = __shfl(v_l, ei);
+#pragma unroll
+      for (int j = 0; j < NCH; j++) {
+         // masked edge: off = BUF_OOB, + cbyte (< 2^25) cannot wrap; masked column: OR-ed past the limit
+         const unsigned o = (off + cbyte[j]) | poison[j];
+         t[u][j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)o, 0, 0);
+      }
+   }
+#pragma unroll
+   for (int j = 0; j < NCH; j++) {
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+         float lo, hi;
+         widen2<ELT>((unsigned)t[0][j][q], lo, hi);
+         float p0 = HAS_VAL ? vv[0] * lo : lo, p1 = HAS_VAL ? vv[0] * hi : hi;
+#pragma unroll
+         for (int u = 1; u < UU; u++) {
+            widen2<ELT>((unsigned)t[u][j][q], lo, hi);
+            p0 = HAS_VAL ? fmaf(vv[u], lo, p0) : p0 + lo;
+            p1 = HAS_VAL ? fmaf(vv[u], hi, p1) : p1 + hi;
+         }
+         acc[j][2 * q] += p0;
+         acc[j][2 * q + 1] += p1;
+      }
+   }
+}
+
+// wave_edges_buf (gather.h) for this kernel: one wave walks edges [rb, re); edge metadata comes 64 per coalesced load, one 32-bit
+// multiply per edge (col * ldy * 2), handed off per step
+template <int ELT, bool HAS_VAL, int LPR, int NCH, int U>
+__device__ __forceinline__ void rows16_edges(const Rows16Args &a, const __amdgpu_buffer_rsrc_t rsrc, int64_t rb, int64_t re,
+                                             const int (&ccol)[NCH], const bool (&cok)[NCH], float (&acc)[NCH][8]) {
+   constexpr int G = 64 / LPR;
+   constexpr int UT = U >= 4 ? 2 : 1;   // tail granularity (U is a multiple of UT, so a step never passes edge 63 of its batch)
+   static_assert(U % UT == 0 && 64 % (G * UT) == 0, "a tail step must end inside the batch");
+   const int lane = threadIdx.x & 63;
+   const int g = lane / LPR;
+   const unsigned ldyb = (unsigned)a.ldy * 2u;
+   unsigned cbyte[NCH], poison[NCH];
+#pragma unroll
+   for (int j = 0; j < NCH; j++) {
+      cbyte[j] = (unsigned)ccol[j] * 2u;
+      poison[j] = cok[j] ? 0u : BUF_OOB;
+   }
+   for (int64_t base = rb; base < re; base += 64) {
+      const int64_t p = base + lane;
+      unsigned off_l = BUF_OOB;
+      float v_l = 0.0f;
+      if (p < re) {
+         off_l = (unsigned)a.indx[p] * ldyb;
+         if (HAS_VAL) v_l = a.val[p];
+      }
+      const int64_t left = re - base;
+      const int cnt = left < 64 ? (int)left : 64;
+      int s = 0;
+      for (; s + G * U <= cnt; s += G * U) rows16_step<ELT, HAS_VAL, LPR, NCH, U>(rsrc, off_l, v_l, s, g, cbyte, poison, acc);
+      for (; s < cnt; s += G * UT) rows16_step<ELT, HAS_VAL, LPR, NCH, UT>(rsrc, off_l, v_l, s, g, cbyte, poison, acc);
+   }
+}
+
+// the finished fp32 row of the g == 0 lanes: the mean's division, then rounded once and stored
+template <int ELT, int NCH>
+__device__ __forceinline__ void rows16_write(const Rows16Args &a, int64_t row, int64_t deg, const int (&ccol)[NCH],
+                                             const bool (&cok)[NCH], const int (&vfirst)[NCH], float (&acc)[NCH][8]) {
+   unsigned short *zr = a.z + (size_t)row * (size_t)a.ldz;
+   if (a.mean) {
+      const float d = (float)(deg > 1 ? deg : 1);
+#pragma unroll
+      for (int j = 0; j < NCH; j++)
+#pragma unroll
+         for (int v = 0; v < 8; v++) acc[j][v] = acc[j][v] / d;
+   }
+#pragma unroll
+   for (int j = 0; j < NCH; j++)
+      if (cok[j]) store_tail16x8<ELT>(zr + ccol[j], acc[j], vfirst[j]);
+}
+
+template <int ELT, bool HAS_VAL, int LPR, int NCH, int WAVES>
+__global__ __launch_bounds__(WAVES * 64, (rows16_min_blocks<NCH>())) void spmm_rows16_kernel(const Rows16Args a) {
+   constexpr int U = rows16_unroll<NCH>();
+   constexpr int PANEL = LPR * 8 * NCH;     // columns covered by one grid.y panel
+   __shared__ float sh_val[WAVES][PANEL];
+
+   const int lane = threadIdx.x & 63;
+   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+   const int g = lane / LPR, lc = lane % LPR;
+   __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.y), 0, (int)a.ybytes, 0x00020000);
+
+   // XCD-aware remap (spmm_csr_kernel, plain): blocks pb, pb + 8, ... share one XCD, which walks a contiguous range of row blocks
+   const unsigned pb = blockIdx.x, nb = a.nblk;
+   const unsigned xcd = pb & 7u, within = pb >> 3;
+   const unsigned per = nb >> 3, rem = nb & 7u;
+   const unsigned lb = xcd * per + (xcd < rem ? xcd : rem) + within;
+
+   // a lane's eight columns per chunk; ragged K (k % 8 != 0): the last 16-byte vector of a row is shifted back to end at column k,
+   // its first vfirst components duplicate the neighbouring lane's work and are not stored
+   int ccol[NCH], vfirst[NCH];
+   bool cok[NCH];
+#pragma unroll
+   for (int j = 0; j < NCH; j++) {
+      ccol[j] = (int)blockIdx.y * PANEL + (j * LPR + lc) * 8;
+      cok[j] = ccol[j] < a.k;
+      vfirst[j] = 0;
+      if (cok[j] && ccol[j] + 8 > (int)a.k) {
+         vfirst[j] = ccol[j] + 8 - (int)a.k;
+         ccol[j] = (int)a.k - 8;
+      }
+   }
+
+   const int64_t row0 = (int64_t)lb * WAVES;
+   const int64_t row = (a.row_order && row0 + wave < a.m) ? (int64_t)a.row_order[row0 + wave] : row0 + wave;
+
+   // phase 1: one row per wave (rows up to long_row edges)
+   if (row0 + wave < a.m) {
+      const int64_t b = a.pntrb[row], e = a.pntre[row];
+      const int64_t deg = e - b;
+      if (deg <= a.long_row) {
+         float acc[NCH][8];
+#pragma unroll
+         for (int j = 0; j < NCH; j++)
+#pragma unroll
+            for (int v = 0; v < 8; v++) acc[j][v] = 0.0f;
+         rows16_edges<ELT, HAS_VAL, LPR, NCH, U>(a, rsrc, b, e, ccol, cok, acc);
+#pragma unroll
+         for (int off = LPR; off < 64; off <<= 1)        // butterfly over the 64 / LPR edge slots, fp32
+#pragma unroll
+            for (int j = 0; j < NCH; j++)
+#pragma unroll
+               for (int v = 0; v < 8; v++) acc[j][v] += __shfl_xor(acc[j][v], off);
+         if (g == 0) rows16_write<ELT, NCH>(a, row, deg, ccol, cok, vfirst, acc);
+      }
+   }
+
+   // phase 2: long rows of this block, all waves on one row at a time (contiguous edge chunks, fixed-order LDS combine in fp32)
+   for (int r = 0; r < WAVES; r++) {
+      if (row0 + r >= a.m) break;                  // uniform over the block
+      const int64_t lr = a.row_order ? (int64_t)a.row_order[row0 + r] : row0 + r;
+      const int64_t b = a.pntrb[lr], e = a.pntre[lr];
+      const int64_t deg = e - b;
+      if (deg <= a.long_row) continue;             // uniform over the block
+      int64_t chunk = (deg + WAVES - 1) / WAVES;
+      chunk = (chunk + 63) & ~(int64_t)63;
+      int64_t cb = b + (int64_t)wave * chunk, ce = cb + chunk;
+      if (cb > e) cb = e;
+      if (ce > e) ce = e;
+      float acc[NCH][8];
+#pragma unroll
+      for (int j = 0; j < NCH; j++)
+#pragma unroll
+         for (int v = 0; v < 8; v++) acc[j][v] = 0.0f;
+      rows16_edges<ELT, HAS_VAL, LPR, NCH, U>(a, rsrc, cb, ce, ccol, cok, acc);
+#pragma unroll
+      for (int off = LPR; off < 64; off <<= 1)
+#pragma unroll
+         for (int j = 0; j < NCH; j++)
+#pragma unroll
+            for (int v = 0; v < 8; v++) acc[j][v] += __shfl_xor(acc[j][v], off);
+      if (g == 0) {
+#pragma unroll
+         for (int j = 0; j < NCH; j++)
+#pragma unroll
+            for (int v = 0; v < 8; v++) sh_val[wave][(j * LPR + lc) * 8 + v] = acc[j][v];
+      }
+      __syncthreads();
+      if (wave == 0 && g == 0) {
+#pragma unroll
+         for (int j = 0; j < NCH; j++)
+#pragma unroll
+            for (int v = 0; v < 8; v++) {
+               const int o = (j * LPR + lc) * 8 + v;
+               float t = sh_val[0][o];
+               for (int w = 1; w < WAVES; w++) t += sh_val[w][o];
+               acc[j][v] = t;
+            }
+         rows16_write<ELT, NCH>(a, lr, deg, ccol, cok, vfirst, acc);
+      }
+      __syncthreads();
+   }
+}
+
+template <int ELT, bool HAS_VAL, int LPR, int NCH>
+static int launch_rows16_cfg(const Rows16Args &a0, hipStream_t st) {
+   constexpr int WAVES = 4;
+   constexpr int PANEL = LPR * 8 * NCH;
+   Rows16Args a = a0;
+   const int64_t nb = (a.m + WAVES - 1) / WAVES;
+   if (nb > 0x7fffffffLL) return fail(ISPLIB_FAIL, "fusedMM_csr_rows16_hip", "too many row blocks for one launch");
+   a.nblk = (unsigned)nb;
+   const int64_t ny = (a.k + PANEL - 1) / PANEL;
+   if (ny > 65535) return fail(ISPLIB_FAIL, "fusedMM_csr_rows16_hip", "too many column panels for one launch");
+   hipLaunchKernelGGL((spmm_rows16_kernel<ELT, HAS_VAL, LPR, NCH, WAVES>), dim3((unsigned)nb, (unsigned)ny, 1), dim3(WAVES * 64, 1, 1), 0, st, a);
+   return check_launch("spmm_rows16_kernel");
+}
+
+// slot width by K (a slot is LPR lanes x 8 columns): 8 / 4 / 2 / 1 rows per gather instruction up to 64 / 128 / 256 / 512 columns,
+// two chunks per lane up to 1024, and 1024-column grid.y panels beyond
+template <int ELT, bool HAS_VAL>
+static int launch_rows16(const Rows16Args &a, hipStream_t st) {
+   const int64_t width = (a.k + 7) / 8;     // 16-byte vectors per row (ragged K: the last one is shifted back)
+   if (width <= 8) return launch_rows16_cfg<ELT, HAS_VAL, 8, 1>(a, st);
+   if (width <= 16) return launch_rows16_cfg<ELT, HAS_VAL, 16, 1>(a, st);
+   if (width <= 32) return launch_rows16_cfg<ELT, HAS_VAL, 32, 1>(a, st);
+   if (width <= 64) return launch_rows16_cfg<ELT, HAS_VAL, 64, 1>(a, st);
+   return launch_rows16_cfg<ELT, HAS_VAL, 64, 2>(a, st);
+}
+
+}  // namespace isplib
+
+using namespace isplib;
+
+extern "C" int isplib_rows16_auto(int64_t n, int64_t ldy, int ordered, int weighted) { return isplib_rows16_native_pays(n, ldy, ordered, weighted); }
+extern "C" int isplib_rows16_domain(int64_t n, int64_t k, int64_t ldy, int64_t ldz) { return isplib_rows16_serves(n, k, ldy, ldz); }
+
+extern "C" int fusedMM_csr_rows16_hip(int32_t imessage, int dtype, int64_t m, int64_t n, int64_t k, int64_t nnz, const float *val,
+                                      const int64_t *indx, const int64_t *pntrb, const int64_t *pntre, const int32_t *row_order,
+                                      const void *y, int64_t ldy, void *z, int64_t ldz, void *stream) {
+   clear_error();
+   const char *entry = "fusedMM_csr_rows16_hip";
+   if (imessage != ISPLIB_MSG_SPMM_SUM && imessage != ISPLIB_MSG_SPMM_MEAN)
+      return fail(ISPLIB_NO_OPT_IMPL, entry, "sum and mean only (max / min of a 16-bit operand: convert it and use fusedMM_csr_hip)");
+   if (dtype != ISPLIB_DTYPE_BF16 && dtype != ISPLIB_DTYPE_F16) return fail(ISPLIB_FAIL, entry, "dtype must be ISPLIB_DTYPE_BF16 or ISPLIB_DTYPE_F16");
+   if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
+   if (m == 0 || k == 0) return ISPLIB_SUCCESS;
+   if (ldy < k || ldz < k) return fail(ISPLIB_FAIL, entry, "leading dimension smaller than k");
+   if (!isplib_rows16_serves(n, k, ldy, ldz))
+      return fail(ISPLIB_FAIL, entry, "outside isplib_rows16_serves(n, k, ldy, ldz): 8 <= k < 2^24, k / ldy / ldz even, n < 2^31, "
+                                      "n*ldy*2 <= 3.5 GiB (convert the operand and use fusedMM_csr_hip)");
+   if (row_order && m >= (1LL << 31)) return fail(ISPLIB_FAIL, entry, "m must be < 2^31 (32-bit row order)");
+   if (!pntrb || !pntre || !z || (nnz > 0 && (!indx || !y))) return fail(ISPLIB_FAIL, entry, "null operand");
+   if ((((uintptr_t)y | (uintptr_t)z) & 3) != 0) return fail(ISPLIB_FAIL, entry, "y and z must be 4-byte aligned");
+
+   Rows16Args a;
+   a.m = m; a.k = k;
+   a.val = val; a.indx = indx; a.pntrb = pntrb; a.pntre = pntre;
+   a.y = y; a.ldy = ldy; a.z = reinterpret_cast<unsigned short *>(z); a.ldz = ldz;
+   a.mean = imessage == ISPLIB_MSG_SPMM_MEAN ? 1 : 0;
+   a.long_row = 2048;
+   a.nblk = 0;
+   a.ybytes = (unsigned)((unsigned long long)n * (unsigned long long)ldy * 2ull);
+   a.row_order = row_order;
+   hipStream_t st = (hipStream_t)stream;
+   if (dtype == ISPLIB_DTYPE_BF16) return val ? launch_rows16<ELT_BF16, true>(a, st) : launch_rows16<ELT_BF16, false>(a, st);
+   return val ? launch_rows16<ELT_F16, true>(a, st) : launch_rows16<ELT_F16, false>(a, st);
+}

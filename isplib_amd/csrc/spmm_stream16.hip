@@ -9,37 +9,13 @@
 // The contract: the result equals the fp32 computation on the widened operand, rounded once to the operand's type -- NaN stays
 // NaN, bf16 keeps subnormals, fp16 overflows to +-Inf.  No epilogue, no staged panels, no max / min here.
 #include "sweep_common.h"
+#include "half16.h"
 
 namespace isplib {
 
-enum { ELT_BF16 = ISPLIB_DTYPE_BF16, ELT_F16 = ISPLIB_DTYPE_F16 };
-
 typedef unsigned v2u_t __attribute__((ext_vector_type(2)));
 
-// two 16-bit elements of a gathered dword as floats (lo: the lower address).  bf16 is the top half of an fp32: a shift and a mask
-template <int ELT> __device__ __forceinline__ void widen2(unsigned w, float &lo, float &hi) {
-   if (ELT == ELT_BF16) {
-      lo = __uint_as_float(w << 16);
-      hi = __uint_as_float(w & 0xFFFF0000u);
-   } else {
-      lo = (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xFFFFu));
-      hi = (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16));
-   }
-}
-
-// two finished floats as one dword of two 16-bit elements, round to nearest even (the casts: v_cvt_pk_bf16_f32 / v_cvt_f16_f32 in
-// the default rounding mode -- not the packed fp16 conversion, which rounds towards zero)
-template <int ELT> __device__ __forceinline__ unsigned narrow2(float lo, float hi) {
-   unsigned short a, b;
-   if (ELT == ELT_BF16) {
-      a = __builtin_bit_cast(unsigned short, (__bf16)lo);
-      b = __builtin_bit_cast(unsigned short, (__bf16)hi);
-   } else {
-      a = __builtin_bit_cast(unsigned short, (_Float16)lo);
-      b = __builtin_bit_cast(unsigned short, (_Float16)hi);
-   }
-   return (unsigned)a | ((unsigned)b << 16);
-}
+// (widen2 / narrow2, the conversions between a gathered dword and two floats: half16.h)
 
 // the four finished columns of a lane as 8 bytes at p (4-byte aligned: k, the pitch and the columns are even); the first `vfirst`
 // components belong to the neighbouring lane (the last vector of a ragged panel is shifted back to end at column k) and are skipped

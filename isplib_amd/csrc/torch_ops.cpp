@@ -118,6 +118,14 @@ static inline bool is_stream_plan(const Plan &p) { return p.size() == 8 || p.siz
 // to the empty plan of the *_planned operators, which means "the plain kernel, please"
 static inline Plan auto_plan() { return Plan{Tensor()}; }
 static inline bool is_auto_plan(const Plan &p) { return p.size() == 1 && !p[0].defined(); }
+// 16-bit row plan (a 16-bit `mat`, sum / mean; fusedMM_csr_rows16_hip) = {row order (device int32 [M], or EMPTY int32 = index order),
+// marker (host int32 [1] = 16)}: the plug-in's decision (rows16_route) handed over with the call -- nothing is re-read from the
+// environment here.  For an fp32 `mat` (e.g. the conversion route of an operand the entry does not serve) it means what its first
+// tensor means alone: the plain kernel, in that row order
+static inline bool is_rows16_plan(const Plan &p) {
+   return p.size() == 2 && p[0].defined() && p[0].scalar_type() == at::kInt && p[1].defined() && !p[1].is_cuda() &&
+          p[1].scalar_type() == at::kInt && p[1].numel() == 1 && p[1].data_ptr<int32_t>()[0] == 16;
+}
 static inline const int32_t *plan_col32(const Plan &p, const Tensor &col) {
    if (p.size() != 6) return nullptr;
    TORCH_CHECK(p[5].scalar_type() == at::kInt && p[5].numel() == col.numel() && p[5].device() == col.device(),
@@ -277,8 +285,16 @@ static bool row_strided(const Tensor &t) { return t.dim() == 2 && t.stride(1) ==
 std::tuple<Tensor, Tensor> spmm_fw(const Tensor &rowptr_, const Tensor &col_, const optional<Tensor> &value_,
                                    const Tensor &mat_, int reduction, const Plan &plan, bool want_arg);
 
+// a 16-bit operand the native entries can read packed: contiguous AND on a 4-byte boundary.  A contiguous tensor may start 2 bytes
+// past one (an odd-element slice of a flat buffer): `contiguous()` returns it as it is, so it is copied (16 bits, a fresh allocation)
+static Tensor packed16(const Tensor &t) {
+   const Tensor c = t.contiguous();
+   return (reinterpret_cast<uintptr_t>(c.data_ptr()) & 3) == 0 ? c : c.clone(at::MemoryFormat::Contiguous);
+}
+
 // A 16-bit `mat`: the native entry when the reduction is sum / mean, the plan is a stream plan of the sum kernel's geometry and
-// isplib_stream16_serves accepts the operand as it lies (a row-strided view keeps its pitch) or packed; else the conversion route.
+// isplib_stream16_serves accepts the operand as it lies (a row-strided view keeps its pitch) or packed; the 16-bit row entry when
+// the plan is a 16-bit row plan (is_rows16_plan) and isplib_rows16_serves accepts the operand the same way; else the conversion route.
 std::tuple<Tensor, Tensor> spmm_fw_half(const Tensor &rowptr_, const Tensor &col_, const optional<Tensor> &value_,
                                         const Tensor &mat_, int reduction, const Plan &plan, bool want_arg) {
    TORCH_CHECK(mat_.dim() == 2, "isplib: `mat` must be 2-D [N, K] (csrc/fusedmm.cpp:121-122)");
@@ -290,7 +306,7 @@ std::tuple<Tensor, Tensor> spmm_fw_half(const Tensor &rowptr_, const Tensor &col
       const bool as_is = row_strided(mat_) && (reinterpret_cast<uintptr_t>(mat_.data_ptr()) & 3) == 0 &&
                          isplib_stream16_serves(N, K, N > 1 ? mat_.stride(0) : K, K, nnz);
       if (as_is || isplib_stream16_serves(N, K, K, K, nnz)) {
-         const Tensor mat = as_is ? mat_ : mat_.contiguous();
+         const Tensor mat = as_is ? mat_ : packed16(mat_);
          const int64_t ldy = N > 1 ? mat.stride(0) : K;
          const Tensor rowptr = rowptr_.contiguous();
          const isplib_stream_plan sp = stream_plan_of(plan);
@@ -302,6 +318,36 @@ std::tuple<Tensor, Tensor> spmm_fw_half(const Tensor &rowptr_, const Tensor &col
                                                  mat.scalar_type() == at::kBFloat16 ? ISPLIB_DTYPE_BF16 : ISPLIB_DTYPE_F16, M, N, K, nnz, rp, rp + 1,
                                                  &sp, mat.data_ptr(), ldy, out.data_ptr(), K, work.data_ptr(), ws, current_stream(mat));
          check_status(st, "fusedMM_csr_stream16_hip");
+         return std::make_tuple(out, Tensor());
+      }
+   }
+   if (sum_op && is_rows16_plan(plan) && M > 0 && K > 0 && rowptr_.device() == mat_.device() && col_.device() == mat_.device()) {
+      c10::DeviceGuard guard(mat_.device());
+      const bool as_is = row_strided(mat_) && (reinterpret_cast<uintptr_t>(mat_.data_ptr()) & 3) == 0 &&
+                         isplib_rows16_serves(N, K, N > 1 ? mat_.stride(0) : K, K);
+      if (as_is || isplib_rows16_serves(N, K, K, K)) {
+         const Tensor mat = as_is ? mat_ : packed16(mat_);
+         const int64_t ldy = N > 1 ? mat.stride(0) : K;
+         const Tensor rowptr = rowptr_.contiguous(), col = col_.contiguous();
+         Tensor value;
+         if (value_.has_value() && value_->defined()) {
+            value = value_->contiguous();
+            TORCH_CHECK(value.numel() == nnz, "isplib: `value` and `col` differ in length");
+         }
+         const int32_t *order = nullptr;
+         Tensor order_t;
+         if (plan[0].numel() > 0) {
+            order_t = plan[0].contiguous();
+            TORCH_CHECK(order_t.is_cuda() && order_t.numel() == M, "isplib: the row order must hold one int32 position per row");
+            order = order_t.data_ptr<int32_t>();
+         }
+         Tensor out = at::empty({M, K}, mat.options());
+         const int64_t *rp = rowptr.data_ptr<int64_t>();
+         const int st = fusedMM_csr_rows16_hip(reduction == R_MEAN ? ISPLIB_MSG_SPMM_MEAN : ISPLIB_MSG_SPMM_SUM,
+                                               mat.scalar_type() == at::kBFloat16 ? ISPLIB_DTYPE_BF16 : ISPLIB_DTYPE_F16, M, N, K, nnz,
+                                               value.defined() ? value.data_ptr<float>() : nullptr, col.data_ptr<int64_t>(), rp, rp + 1, order,
+                                               mat.data_ptr(), ldy, out.data_ptr(), K, current_stream(mat));
+         check_status(st, "fusedMM_csr_rows16_hip");
          return std::make_tuple(out, Tensor());
       }
    }
@@ -325,6 +371,8 @@ std::tuple<Tensor, Tensor> spmm_fw(const Tensor &rowptr_, const Tensor &col_, co
       if (value_.has_value() && value_->defined()) check_float(*value_, "value");
       return spmm_fw_half(rowptr_, col_, value_, mat_, reduction, plan, want_arg);
    }
+   if (is_rows16_plan(plan))      // an fp32 operand on a 16-bit row plan: the plain kernel in the plan's row order
+      return spmm_fw(rowptr_, col_, value_, mat_, reduction, plan[0].numel() > 0 ? Plan{plan[0]} : Plan(), want_arg);
    TORCH_CHECK(mat_.dim() == 2, "isplib: `mat` must be 2-D [N, K] (csrc/fusedmm.cpp:121-122)");
    TORCH_CHECK(rowptr_.dim() == 1 && rowptr_.numel() >= 1, "isplib: `rowptr` must be 1-D with M+1 entries");
    c10::DeviceGuard guard(mat_.device());

@@ -22,7 +22,7 @@ Differences from the reference, each a defect there:
 
 Environment: ISPLIB_SLICES=<n> forces the task list with n column slices (0: plain kernel); ISPLIB_STREAM=0 keeps
 sum / mean off the stream schedule; ISPLIB_STREAM_GEOM=streams:slices:chunk forces it with that plan geometry;
-ISPLIB_HALF=auto|native|convert picks the route of bf16 / fp16 features (half_route);
+ISPLIB_HALF=auto|native|convert picks the route of bf16 / fp16 features (half_route; rows16_route for calls on the plain kernel);
 ISPLIB_TUNE_FILE names a tuning table to load at import; ISPLIB_DEBUG=1 prints per-operator device times.
 """
 from __future__ import annotations
@@ -280,6 +280,44 @@ def half_route(dtype, reduce: str, k: int, pitch: int, mode: Optional[str] = Non
     return "native" if cabi.stream16_native_pays(int(streams), bool(weighted)) else "convert"
 
 
+def rows16_route(dtype, reduce: str, k: int, pitch: int, mode: Optional[str] = None, n: int = 1, ordered: bool = False,
+                 weighted: bool = False) -> str:
+    """Which way a matmul with 16-bit features goes when half_route said "convert", the call has no stream plan and the plain
+    row-per-wave kernel serves it: "rows16" (the 16-bit row kernel, fusedMM_csr_rows16_hip: no fp32 copy of the operand, half the
+    gathered bytes) or "convert".  A pure function -- no device, no library call:
+      * rows16 needs a sum / mean of bf16 / fp16 features and a shape inside the entry's domain (cabi.rows16_serves) at the
+        operand's own row pitch or, failing that, packed (pitch = k);
+      * `mode` is ISPLIB_HALF (None: read from the environment; default "auto"): "convert" always converts, "native" takes the
+        kernel wherever the above holds, "auto" only in the classes -- (operand beyond 256 MiB or not) x `ordered` (the rows come
+        in a community order) x `weighted` -- where every native run measured faster than every run of the conversion route
+        (cabi.rows16_native_pays, profiles/rows16_ab.txt).  Nothing raises."""
+    if dtype not in HALF_DTYPES or reduce not in ("sum", "add", "mean"):
+        return "convert"
+    from . import cabi
+    if mode is None:
+        mode = os.environ.get("ISPLIB_HALF", "auto")
+    if mode == "convert":
+        return "convert"
+    if cabi.rows16_serves(n, k, pitch, k):
+        ld = pitch
+    elif cabi.rows16_serves(n, k, k, k):
+        ld = k
+    else:
+        return "convert"
+    if mode == "native":
+        return "rows16"
+    return "rows16" if cabi.rows16_native_pays(n, ld, bool(ordered), bool(weighted)) else "convert"
+
+
+_ROWS16_MARK = torch.tensor([16], dtype=torch.int32)      # second tensor of a 16-bit row plan (torch_ops.cpp: is_rows16_plan)
+
+
+def _rows16_plan(s: SparseStorage, transposed: bool, k: int, device) -> list:
+    """[row order or an empty int32 tensor (index order), marker]: the plan form that sends a 16-bit operand to the row kernel."""
+    order = s.row_order(transposed, k, itemsize=2)
+    return [order[0] if order else torch.empty(0, dtype=torch.int32, device=device), _ROWS16_MARK]
+
+
 def spmm_autotuned(src, other: torch.Tensor, reduce: str = "sum") -> torch.Tensor:
     """``torch_sparse.matmul(src, other, reduce)`` on the HIP path (isplib/__init__.py:48-157)."""
     if reduce not in ("sum", "add", "mean", "max", "min"):
@@ -308,16 +346,30 @@ def spmm_autotuned(src, other: torch.Tensor, reduce: str = "sum") -> torch.Tenso
         geom = choose_stream_minmax(s, m_rows, mat.size(0), k)
         plan = s.stream_plan(False, geom, "minmax") if geom is not None else None
     ran = ("stream",) + tuple(int(v) for v in geom) if plan is not None else None
+    rows16 = False
     if half:
         # bf16 / fp16 features: the 16-bit stream kernel on the same plan, or the conversion route (half_route)
         pitch = mat.stride(0) if mat.dim() == 2 and mat.size(0) > 1 and mat.stride(-1) == 1 else k
         route = half_route(mat.dtype, reduce, k, pitch, None, None if plan is None else int(geom[0]), s._value is not None,
                            mat.size(0), col.numel())
-        if route == "convert":
+        if route == "convert" and plan is None and mat.dim() == 2 and reduce in ("sum", "add", "mean") and not s.plan(choose_slices(s, mat.size(0), k)):
+            # no stream plan, and the plain kernel would serve the fp32 call: the 16-bit row kernel where rows16_route says so.
+            # `ordered` is what the kernel will be given, so the community order (judged at 2 bytes per element) is looked for
+            # only when some answer to it can send the call there
+            weighted = s._value is not None
+            goes = lambda ordered: rows16_route(mat.dtype, reduce, k, pitch, None, mat.size(0), ordered, weighted) == "rows16"  # noqa: E731
+            if goes(False) or goes(True):
+                cand = _rows16_plan(s, False, k, mat.device)
+                if goes(cand[0].numel() > 0):
+                    plan, rows16 = cand, True
+        if rows16:
+            ran = ("rows16", "ordered") if plan[0].numel() > 0 else ("rows16",)
+        elif route == "convert":
             out = spmm_autotuned(src, other.to(torch.float32), reduce)
             s._last_schedule = ("convert",) + tuple(s._last_schedule or ())
             return out.to(other.dtype)
-        ran = ("stream16",) + tuple(int(v) for v in geom)
+        else:
+            ran = ("stream16",) + tuple(int(v) for v in geom)
     if plan is None:
         n_sl = choose_slices(s, mat.size(0), k, reduce in ("max", "min"))
         plan = s.plan(n_sl)                                          # per-graph, built once on the device
@@ -335,11 +387,21 @@ def spmm_autotuned(src, other: torch.Tensor, reduce: str = "sum") -> torch.Tenso
             unit_mean = reduce == "mean" and s._value is None
             val_t = None if unit_mean else (s.mean_val_t() if reduce == "mean" else s.val_t())
             geom_t = choose_stream(s, mat.size(0), m_rows, k, val_t is not None)
+            if rows16 and not unit_mean and geom_t is not None and \
+                    half_route(mat.dtype, reduce, k, k, None, int(geom_t[0]), val_t is not None, m_rows, col.numel()) == "convert":
+                # the operators run a 16-bit dY on a stream plan natively whatever the mode: where half_route would convert
+                # (auto: the 16-bit stream kernel never pays), the backward of a row-kernel call stays off the stream plan
+                geom_t = None
             plan_t = s.stream_plan(True, geom_t, "mean" if reduce == "mean" and not unit_mean else "sum") if geom_t is not None else None
             if plan_t is None:
                 plan_t = s.plan_t(choose_slices(s, m_rows, k, transposed=True))
                 if not plan_t:
-                    plan_t = s.row_order(True, k)
+                    # the backward (A^T dY) of a 16-bit call: the same route under the same rule, on the transposed arrays.  The
+                    # unit-weight mean backward forms dY / deg in fp32 first: an fp32 operand, its row order judged at 4 bytes
+                    if half and not unit_mean and _rows16_backward(s, mat, reduce, k, m_rows, val_t is not None):
+                        plan_t = _rows16_plan(s, True, k, mat.device)
+                    else:
+                        plan_t = s.row_order(True, k)
         if reduce == "mean":
             out = ops.fusedmm_spmm_mean_planned(rowptr, col, value, colptr, mat, row_t, val_t, plan, plan_t)
         else:
@@ -353,6 +415,13 @@ def spmm_autotuned(src, other: torch.Tensor, reduce: str = "sum") -> torch.Tenso
     else:
         out = ops.fusedmm_spmm_min_planned(rowptr, col, value, mat, plan)[0]   # :145
     return out.squeeze(-1) if squeeze else out
+
+
+def _rows16_backward(s: SparseStorage, mat: torch.Tensor, reduce: str, k: int, m_rows: int, weighted: bool) -> bool:
+    """Whether A^T dY of a 16-bit call (dY: [m_rows, k], packed, of mat's dtype) takes the 16-bit row kernel: rows16_route with the
+    transposed side's row order.  (Not asked for the unit-weight mean backward, whose operand dY / deg is fp32.)"""
+    goes = lambda ordered: rows16_route(mat.dtype, reduce, k, k, None, m_rows, ordered, weighted) == "rows16"  # noqa: E731
+    return (goes(False) or goes(True)) and goes(bool(s.row_order(True, k, itemsize=2)))
 
 
 matmul = spmm_autotuned

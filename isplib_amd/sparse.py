@@ -122,14 +122,15 @@ class SparseStorage:
         (col32, the packed column ids, once per graph)."""
         return self._plan_for(self._plans, n_slices, self._rowptr, self._col, self._sparse_sizes[1])
 
-    def row_order(self, transposed: bool, k: int):
+    def row_order(self, transposed: bool, k: int, itemsize: int = 4):
         """[order] -- the plain kernel's rows in a community order (isplib_amd/reorder.py) -- for a square graph whose dense
-        operand is larger than the Infinity Cache (n k 4 > 256 MiB) and HAS community structure, else [] (the plain
-        kernel in index order).  Looked for once per side (~0.2 s for the ogbn-products shape); ISPLIB_REORDER=0 never
-        looks.  The result is the same bits either way."""
+        operand is larger than the Infinity Cache (n k itemsize > 256 MiB; itemsize: bytes per element of the operand the kernel
+        gathers, 2 for the 16-bit row kernel) and HAS community structure, else [] (the plain kernel in index order).  Looked
+        for once per side (~0.2 s for the ogbn-products shape); ISPLIB_REORDER=0 never looks.  The result is the same bits
+        either way."""
         import os
         m, n = self._sparse_sizes
-        if m != n or n * k * 4 <= (256 << 20) or os.environ.get("ISPLIB_REORDER", "1") == "0" or self._col.numel() == 0:
+        if m != n or n * k * int(itemsize) <= (256 << 20) or os.environ.get("ISPLIB_REORDER", "1") == "0" or self._col.numel() == 0:
             return []
         cache = self.__dict__.setdefault("_row_orders", {})
         if transposed not in cache:
