@@ -537,6 +537,42 @@ static inline int isplib_rows16_native_pays(int64_t n, int64_t ldy, int ordered,
 int    isplib_rows16_auto(int64_t n, int64_t ldy, int ordered, int weighted);      /* the same rule as a symbol */
 int    isplib_rows16_domain(int64_t n, int64_t k, int64_t ldy, int64_t ldz);       /* isplib_rows16_serves as a symbol */
 /*
+ * fusedMM_csr_rows16_hip's schedule for max / min of a 16-bit dense operand: one CSR row per wavefront, 16-byte gathers of eight
+ * columns, the optional row order, no fp32 copy of the operand.  The halves are widened in registers and every comparison is fp32:
+ * the candidate of an edge is val * y (ONE fp32 multiply; val = NULL: y itself) and replaces the running value only if strictly
+ * better, so the first edge wins a tie (+0 and -0 tie) and NaN never wins -- the comparator of fusedMM_csr_hip, whose result does
+ * not depend on how a row's edges are cut into slots.  The finished fp32 winner is rounded ONCE, to nearest even.  Widening is exact,
+ * so values AND positions are BIT-EQUAL to "convert the operand, run fusedMM_csr_hip, convert back", on any data.  z: m x ldz
+ * elements of `dtype`; z_arg (may be NULL): int64 at pitch ldarg, the CSR position of the winner, nnz where nothing won.  An empty
+ * row is 0 (under isplib_hip_set_empty_row(1): the identity -+FLT_MAX, which rounds to -+Inf in both types), its position nnz; a
+ * non-empty row in which nothing wins (all NaN, or all -Inf under max / +Inf under min) keeps -+FLT_MAX -> -+Inf, position nnz.
+ * z_arg = NULL is a values-only launch: no position is tracked at all, the same value bits.  No atomics: two launches give equal
+ * bits and any row order gives the bits of index order.
+ * Domain: isplib_rows16_serves(n, k, ldy, ldz); with a row order m < 2^31.  Refused before any launch, outputs untouched: a message
+ * word other than max / min (ISPLIB_NO_OPT_IMPL), and with ISPLIB_FAIL another dtype, a negative dimension, ldy, ldz or ldarg < k,
+ * a shape outside the domain, a null operand, a y or z base that is not 4-byte aligned.  m == 0 or k == 0 succeeds without a launch.
+ * isplib_rows16_minmax_native_pays is the measured rule of the layers above (profiles/rows16_minmax_ab.txt), over
+ * the classes of isplib_rows16_native_pays x (positions wanted or not): nonzero only where EVERY run of this entry was faster than
+ * EVERY run of the conversion route on every measured shape of the class.
+ */
+int    fusedMM_csr_rows16_minmax_hip(int32_t imessage /* ISPLIB_MSG_SPMM_MAX | _MIN */, int dtype /* ISPLIB_DTYPE_BF16 | _F16 */,
+                                     int64_t m, int64_t n, int64_t k, int64_t nnz, const float *val /* fp32, may be NULL */,
+                                     const int64_t *indx, const int64_t *pntrb, const int64_t *pntre,
+                                     const int32_t *row_order /* optional */, const void *y, int64_t ldy, void *z, int64_t ldz,
+                                     int64_t *z_arg /* may be NULL */, int64_t ldarg, void *stream);
+static inline int isplib_rows16_minmax_native_pays(int64_t n, int64_t ldy, int ordered, int weighted, int want_arg) {
+   /* measured (profiles/rows16_minmax_ab.txt: rows16_ab's shapes, bf16, forward max, values only and with positions): beyond 256 MiB
+    * every class pays, unit and weighted, with and without positions -- in index order 0.45-0.51 of the conversion route's time, in a
+    * community order 0.45-0.73.  Inside 256 MiB in index order the class does NOT pay: a quarter of the products shape at K = 128
+    * (0.46-0.51), a Cora-shaped graph (0.65-0.69) and a fiftieth of the shape at K = 64 (0.71-0.89) win every run, but the fiftieth
+    * at K = 16 loses every run (1.03-1.20: two of a slot's eight lanes hold columns), so the whole class stays on convert; inside
+    * 256 MiB in a community order was not measured. */
+   const int beyond = n > 0 && ldy > 0 && (double)n * (double)ldy * 2.0 > 256.0 * 1048576.0;
+   (void)ordered; (void)weighted; (void)want_arg;
+   return beyond ? 1 : 0;
+}
+int    isplib_rows16_minmax_auto(int64_t n, int64_t ldy, int ordered, int weighted, int want_arg);   /* the same rule as a symbol */
+/*
  * Staged column panels (sum / mean on 64-column slots only).  What a gather of a 128-byte line costs depends on the line's
  * ADDRESS: profiles/line_classes.txt (scripts/ubench/line_classes.hip) is the table, DESIGN.md section 5 reads it.  Before the
  * dispatches of a panel whose lines sit in a slow class, fusedMM_csr_stream_hip may copy the panel's 64 columns into the tail

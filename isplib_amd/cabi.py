@@ -76,6 +76,14 @@ def rows16_native_pays(n: int, ldy: int, ordered: bool, weighted: bool) -> bool:
     return bool(beyond or not ordered)
 
 
+def rows16_minmax_native_pays(n: int, ldy: int, ordered: bool, weighted: bool, want_arg: bool) -> bool:
+    """isplib_rows16_minmax_native_pays of the header: the classes of calls -- those of rows16_native_pays x (positions wanted or
+    not) -- in which every run of the 16-bit max / min row kernel measured faster than every run of the conversion route
+    (profiles/rows16_minmax_ab.txt: every class beyond 256 MiB does; inside 256 MiB the index-order class loses on one measured shape
+    and the community-order class was not measured, so both stay on convert); tests/test_rows16_minmax_host.py compares the two."""
+    return bool(n > 0 and ldy > 0 and n * ldy * 2 > (256 << 20))
+
+
 def owner_exchange_serves(m: int, k: int, world: int, cuts) -> bool:
     """isplib_owner_exchange_serves of the header: m x k winners split for `world` owners at the row boundaries `cuts`."""
     if not 1 <= world <= OWNER_WORLD_MAX or m < 0 or k < 0 or m * k >= MINMAX_BW_PAIRS_END:
@@ -121,6 +129,7 @@ EXPORTS = (
     "isplib_graph_set_row_order", "isplib_plain_panels",
     "fusedMM_csr_stream16_hip", "isplib_stream16_auto",
     "fusedMM_csr_rows16_hip", "isplib_rows16_auto", "isplib_rows16_domain",
+    "fusedMM_csr_rows16_minmax_hip", "isplib_rows16_minmax_auto",
 )
 
 # include/isplib_hip_experimental.h (libisplib_hip_exp.so): forms measured slower than the defaults; tests and experiment scripts only
@@ -335,6 +344,10 @@ def lib() -> ctypes.CDLL:
         L.isplib_rows16_auto.argtypes = [_i64, _i64, ctypes.c_int, ctypes.c_int]
         L.isplib_rows16_domain.restype = ctypes.c_int
         L.isplib_rows16_domain.argtypes = [_i64, _i64, _i64, _i64]
+        L.fusedMM_csr_rows16_minmax_hip.restype = ctypes.c_int
+        L.fusedMM_csr_rows16_minmax_hip.argtypes = [_i32, ctypes.c_int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp]
+        L.isplib_rows16_minmax_auto.restype = ctypes.c_int
+        L.isplib_rows16_minmax_auto.argtypes = [_i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int]
         _sigs_set = True
     return L
 
@@ -1237,6 +1250,83 @@ def spmm_rows16(rowptr, col, val, y, reduce: str = "sum", order=None, out=None):
             raise ValueError("isplib_amd: `y` and `out` must be 4-byte aligned")
     fusedMM_csr_rows16_hip(MESSAGE[reduce], rowptr, col, val, order, y, out)
     return out
+
+
+def fusedMM_csr_rows16_minmax_hip(imessage: int, rowptr, col, val, order, y, z, z_arg=None, check: bool = True, dtype=None, k=None, ldy=None,
+                                  ldz=None, ldarg=None) -> int:
+    """Raw boundary call of the 16-bit row SpMM for max / min, for operands the entry may refuse: it hands over what it is given
+    (`dtype`, `k`, `ldy`, `ldz`, `ldarg`: override what the tensors say -- refusal tests; the entry refuses before it reads anything).
+    `z_arg` None is the values-only launch.  Callers that want their operands checked use spmm_rows16_minmax."""
+    m, n = rowptr.numel() - 1, y.size(0)
+    k = y.size(1) if k is None else int(k)
+    code = HALF_DTYPES.get(y.dtype, 0) if dtype is None else int(dtype)
+    rp = rowptr.data_ptr()
+    if ldarg is None:
+        ldarg = 0 if z_arg is None else (z_arg.stride(0) if m > 1 else max(k, z_arg.stride(0)))
+    with torch.cuda.device(y.device):
+        st = lib().fusedMM_csr_rows16_minmax_hip(int(imessage), code, m, n, k, col.numel(), _ptr(val), _ptr(col), ctypes.c_void_p(rp),
+                                                 ctypes.c_void_p(rp + 8), _ptr(order),
+                                                 _ptr(y), (y.stride(0) if n > 1 else max(k, y.stride(0))) if ldy is None else int(ldy),
+                                                 _ptr(z), (z.stride(0) if m > 1 else max(k, z.stride(0))) if ldz is None else int(ldz),
+                                                 _ptr(z_arg), int(ldarg), _stream(y.device))
+    if check:
+        _check(st, "fusedMM_csr_rows16_minmax_hip")
+    return st
+
+
+def spmm_rows16_minmax(rowptr, col, val, y, reduce: str = "max", order=None, out=None, arg=None, want_arg: bool = True):
+    """The 16-bit row SpMM for max / min of a bf16 / fp16 `y` [n, k]: returns (out, arg) -- `out` [m, k] of y's dtype and `arg` int64
+    [m, k], the CSR position of each winner (col.numel() where nothing won); both allocated when not given, row-strided views are
+    written at their own pitch.  want_arg=False (and no `arg`): the values-only launch, returns (out, None) with the same value bits.
+    `val`: fp32 weights or None; `order`: int32 [m], position -> row, or None.  Values and positions are bit-equal to the fp32 kernel's
+    on the widened operand, rounded once.  Every operand is checked BEFORE the call -- a mis-shaped one is an out-of-bounds device
+    read: rowptr / col int64 on y's device, rowptr ascending from 0 to col.numel(), every column id inside [0, n), the shape inside
+    isplib_rows16_serves, `out` [m, k] of the same dtype at an even pitch, `arg` int64 [m, k], `order` a permutation's length."""
+    if reduce not in ("max", "min"):
+        raise ValueError(f"isplib_amd: spmm_rows16_minmax serves max / min, got '{reduce}' (sum / mean: spmm_rows16)")
+    if not isinstance(y, torch.Tensor) or not y.is_cuda or y.dim() != 2:
+        raise ValueError("isplib_amd: `y` must be a 2-D GPU tensor [n, k]")
+    if y.dtype not in HALF_DTYPES:
+        raise TypeError(f"isplib_amd: `y` must be bfloat16 or float16, got {y.dtype} (float32: spmm)")
+    rowptr = _dev(rowptr, "rowptr", torch.int64)
+    col = _dev(col, "col", torch.int64)
+    n, k = y.size(0), y.size(1)
+    m = rowptr.numel() - 1
+    if m < 0 or rowptr.device != y.device or col.device != y.device:
+        raise ValueError("isplib_amd: rowptr (m + 1 entries), col and y must be on one device")
+    if k > 0 and y.stride(1) != 1:
+        raise ValueError("isplib_amd: `y` must have unit inner stride")
+    if val is not None:
+        val = _dev(val, "val", torch.float32)
+        if val.numel() != col.numel() or val.device != y.device:
+            raise ValueError("isplib_amd: `val` must hold one float32 weight per entry of `col`, on y's device")
+    if order is not None:
+        order = _dev(order, "order", torch.int32)
+        if order.numel() != m or order.device != y.device or (m > 0 and (int(order.min()) < 0 or int(order.max()) >= m)):
+            raise ValueError("isplib_amd: `order` must hold one int32 row in [0, m) per position, on y's device")
+    if m > 0 and (int(rowptr[0]) != 0 or int(rowptr[-1]) != col.numel() or bool((rowptr[1:] < rowptr[:-1]).any())):
+        raise ValueError("isplib_amd: rowptr must ascend from 0 to col.numel()")
+    if col.numel() > 0 and (int(col.min()) < 0 or int(col.max()) >= n):
+        raise ValueError(f"isplib_amd: column ids must lie in [0, {n})")
+    ldy = y.stride(0) if n > 1 else max(k, y.stride(0))
+    if out is None:
+        out = torch.empty((m, k), dtype=y.dtype, device=y.device)
+    elif not isinstance(out, torch.Tensor) or out.device != y.device or tuple(out.shape) != (m, k) or out.dtype != y.dtype or (k > 0 and out.stride(1) != 1):
+        raise ValueError(f"isplib_amd: `out` must be a [{m}, {k}] {y.dtype} tensor on {y.device} with unit inner stride")
+    if arg is None:
+        arg = torch.empty((m, k), dtype=torch.int64, device=y.device) if want_arg else None
+    elif not isinstance(arg, torch.Tensor) or arg.device != y.device or tuple(arg.shape) != (m, k) or arg.dtype != torch.int64 or (k > 0 and arg.stride(1) != 1):
+        raise ValueError(f"isplib_amd: `arg` must be a [{m}, {k}] int64 tensor on {y.device} with unit inner stride")
+    ldz = out.stride(0) if m > 1 else max(k, out.stride(0))
+    if m > 0 and k > 0:
+        if ldy < k or ldz < k or not rows16_serves(n, k, ldy, ldz):
+            raise ValueError(f"isplib_amd: outside the 16-bit row entry's domain (isplib_rows16_serves: n={n}, k={k}, ldy={ldy}, ldz={ldz})")
+        if arg is not None and m > 1 and arg.stride(0) < k:
+            raise ValueError("isplib_amd: `arg` rows must not overlap")
+        if (y.data_ptr() | out.data_ptr()) & 3:
+            raise ValueError("isplib_amd: `y` and `out` must be 4-byte aligned")
+    fusedMM_csr_rows16_minmax_hip(MESSAGE[reduce], rowptr, col, val, order, y, out, arg)
+    return out, arg
 
 
 def fusedMM_csr_stream_minmax_hip(imessage: int, rowptr, nnz: int, plan, y, z, z_arg=None, workspace=None, check: bool = True) -> int:

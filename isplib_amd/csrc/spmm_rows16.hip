@@ -43,21 +43,6 @@ struct Rows16Args {
 template <int NCH> constexpr int rows16_unroll() { return NCH > 1 ? 4 : 6; }
 template <int NCH> constexpr int rows16_min_blocks() { return NCH == 1 ? 8 : 1; }
 
-// the eight finished columns of a lane as 16 bytes at p (4-byte aligned: k, the pitch and the columns are even); the first `vfirst`
-// components (even) belong to the neighbouring lane -- the last vector of a row is shifted back to end at column k -- and are skipped
-template <int ELT> __device__ __forceinline__ void store_tail16x8(unsigned short *p, const float (&r)[8], int vfirst) {
-   unsigned d[4];
-#pragma unroll
-   for (int q = 0; q < 4; q++) d[q] = narrow2<ELT>(r[2 * q], r[2 * q + 1]);
-   if (vfirst == 0 && ((uintptr_t)p & 15) == 0) {
-      *reinterpret_cast<uint4 *>(p) = make_uint4(d[0], d[1], d[2], d[3]);
-   } else {
-#pragma unroll
-      for (int q = 0; q < 4; q++)
-         if (2 * q >= vfirst) reinterpret_cast<unsigned *>(p)[q] = d[q];
-   }
-}
-
 // buf_step (gather.h) at eight 16-bit columns per 16-byte gather: UU gathers per slot back to back for the edges [s, s + G*UU) of
 // the current 64-edge batch; their values are summed among themselves first and enter the running sum as ONE term
 template <int ELT, bool HAS_VAL, int LPR, int NCH, int UU>

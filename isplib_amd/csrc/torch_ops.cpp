@@ -118,8 +118,8 @@ static inline bool is_stream_plan(const Plan &p) { return p.size() == 8 || p.siz
 // to the empty plan of the *_planned operators, which means "the plain kernel, please"
 static inline Plan auto_plan() { return Plan{Tensor()}; }
 static inline bool is_auto_plan(const Plan &p) { return p.size() == 1 && !p[0].defined(); }
-// 16-bit row plan (a 16-bit `mat`, sum / mean; fusedMM_csr_rows16_hip) = {row order (device int32 [M], or EMPTY int32 = index order),
-// marker (host int32 [1] = 16)}: the plug-in's decision (rows16_route) handed over with the call -- nothing is re-read from the
+// 16-bit row plan (a 16-bit `mat`; sum / mean: fusedMM_csr_rows16_hip, max / min: fusedMM_csr_rows16_minmax_hip) = {row order (device int32 [M], or EMPTY int32 = index order),
+// marker (host int32 [1] = 16)}: the plug-in's decision (rows16_route, rows16_minmax_route) handed over with the call -- nothing is re-read from the
 // environment here.  For an fp32 `mat` (e.g. the conversion route of an operand the entry does not serve) it means what its first
 // tensor means alone: the plain kernel, in that row order
 static inline bool is_rows16_plan(const Plan &p) {
@@ -294,7 +294,8 @@ static Tensor packed16(const Tensor &t) {
 
 // A 16-bit `mat`: the native entry when the reduction is sum / mean, the plan is a stream plan of the sum kernel's geometry and
 // isplib_stream16_serves accepts the operand as it lies (a row-strided view keeps its pitch) or packed; the 16-bit row entry when
-// the plan is a 16-bit row plan (is_rows16_plan) and isplib_rows16_serves accepts the operand the same way; else the conversion route.
+// the plan is a 16-bit row plan (is_rows16_plan) and isplib_rows16_serves accepts the operand the same way -- for sum / mean and, through
+// its own entry, for max / min; else the conversion route.
 std::tuple<Tensor, Tensor> spmm_fw_half(const Tensor &rowptr_, const Tensor &col_, const optional<Tensor> &value_,
                                         const Tensor &mat_, int reduction, const Plan &plan, bool want_arg) {
    TORCH_CHECK(mat_.dim() == 2, "isplib: `mat` must be 2-D [N, K] (csrc/fusedmm.cpp:121-122)");
@@ -349,6 +350,42 @@ std::tuple<Tensor, Tensor> spmm_fw_half(const Tensor &rowptr_, const Tensor &col
                                                mat.data_ptr(), ldy, out.data_ptr(), K, current_stream(mat));
          check_status(st, "fusedMM_csr_rows16_hip");
          return std::make_tuple(out, Tensor());
+      }
+   }
+   // max / min on a 16-bit row plan: fusedMM_csr_rows16_minmax_hip -- values and positions bit-equal to the conversion route below,
+   // without the fp32 copy; want_arg = false is its values-only launch (the second tensor stays undefined)
+   if ((reduction == R_MAX || reduction == R_MIN) && is_rows16_plan(plan) && M > 0 && K > 0 && rowptr_.device() == mat_.device() &&
+       col_.device() == mat_.device()) {
+      c10::DeviceGuard guard(mat_.device());
+      const bool as_is = row_strided(mat_) && (reinterpret_cast<uintptr_t>(mat_.data_ptr()) & 3) == 0 &&
+                         isplib_rows16_serves(N, K, N > 1 ? mat_.stride(0) : K, K);
+      if (as_is || isplib_rows16_serves(N, K, K, K)) {
+         const Tensor mat = as_is ? mat_ : packed16(mat_);
+         const int64_t ldy = N > 1 ? mat.stride(0) : K;
+         const Tensor rowptr = rowptr_.contiguous(), col = col_.contiguous();
+         Tensor value;
+         if (value_.has_value() && value_->defined()) {
+            value = value_->contiguous();
+            TORCH_CHECK(value.numel() == nnz, "isplib: `value` and `col` differ in length");
+         }
+         const int32_t *order = nullptr;
+         Tensor order_t;
+         if (plan[0].numel() > 0) {
+            order_t = plan[0].contiguous();
+            TORCH_CHECK(order_t.is_cuda() && order_t.numel() == M, "isplib: the row order must hold one int32 position per row");
+            order = order_t.data_ptr<int32_t>();
+         }
+         Tensor out = at::empty({M, K}, mat.options());
+         Tensor arg;
+         if (want_arg) arg = at::empty({M, K}, rowptr.options());
+         const int64_t *rp = rowptr.data_ptr<int64_t>();
+         const int st = fusedMM_csr_rows16_minmax_hip(reduction == R_MAX ? ISPLIB_MSG_SPMM_MAX : ISPLIB_MSG_SPMM_MIN,
+                                                      mat.scalar_type() == at::kBFloat16 ? ISPLIB_DTYPE_BF16 : ISPLIB_DTYPE_F16, M, N, K, nnz,
+                                                      value.defined() ? value.data_ptr<float>() : nullptr, col.data_ptr<int64_t>(), rp, rp + 1,
+                                                      order, mat.data_ptr(), ldy, out.data_ptr(), K,
+                                                      arg.defined() ? arg.data_ptr<int64_t>() : nullptr, K, current_stream(mat));
+         check_status(st, "fusedMM_csr_rows16_minmax_hip");
+         return std::make_tuple(out, arg);
       }
    }
    auto r = spmm_fw(rowptr_, col_, value_, mat_.to(at::kFloat), reduction, plan, want_arg);

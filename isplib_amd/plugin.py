@@ -309,6 +309,36 @@ def rows16_route(dtype, reduce: str, k: int, pitch: int, mode: Optional[str] = N
     return "rows16" if cabi.rows16_native_pays(n, ld, bool(ordered), bool(weighted)) else "convert"
 
 
+def rows16_minmax_route(dtype, reduce: str, k: int, pitch: int, mode: Optional[str] = None, n: int = 1, ordered: bool = False,
+                        weighted: bool = False, want_arg: bool = True) -> str:
+    """Which way a max / min matmul with 16-bit features goes when the call has no stream plan and the plain row-per-wave kernel
+    serves it: "rows16" (the 16-bit max / min row kernel, fusedMM_csr_rows16_minmax_hip: no fp32 copy of the operand, half the
+    gathered bytes, values and positions bit-equal to the conversion route) or "convert".  A pure function -- no device, no library
+    call:
+      * rows16 needs a max / min of bf16 / fp16 features and a shape inside the entry's domain (cabi.rows16_serves) at the
+        operand's own row pitch or, failing that, packed (pitch = k);
+      * `mode` is ISPLIB_HALF_MINMAX (None: read from the environment; default "convert", and ISPLIB_HALF=convert wins over it):
+        "convert" always converts, "native" takes the kernel wherever the above holds, "auto" only in the classes -- those of
+        rows16_route x `want_arg` (positions wanted) -- where every native run measured faster than every run of the conversion
+        route (cabi.rows16_minmax_native_pays, profiles/rows16_minmax_ab.txt).  Nothing raises."""
+    if dtype not in HALF_DTYPES or reduce not in ("max", "min"):
+        return "convert"
+    from . import cabi
+    if mode is None:
+        mode = "convert" if os.environ.get("ISPLIB_HALF", "auto") == "convert" else os.environ.get("ISPLIB_HALF_MINMAX", "convert")
+    if mode not in ("native", "auto"):
+        return "convert"
+    if cabi.rows16_serves(n, k, pitch, k):
+        ld = pitch
+    elif cabi.rows16_serves(n, k, k, k):
+        ld = k
+    else:
+        return "convert"
+    if mode == "native":
+        return "rows16"
+    return "rows16" if cabi.rows16_minmax_native_pays(n, ld, bool(ordered), bool(weighted), bool(want_arg)) else "convert"
+
+
 _ROWS16_MARK = torch.tensor([16], dtype=torch.int32)      # second tensor of a 16-bit row plan (torch_ops.cpp: is_rows16_plan)
 
 
@@ -362,8 +392,19 @@ def spmm_autotuned(src, other: torch.Tensor, reduce: str = "sum") -> torch.Tenso
                 cand = _rows16_plan(s, False, k, mat.device)
                 if goes(cand[0].numel() > 0):
                     plan, rows16 = cand, True
+        if route == "convert" and plan is None and mat.dim() == 2 and reduce in ("max", "min") and \
+                os.environ.get("ISPLIB_HALF_MINMAX", "convert") != "convert" and not s.plan(choose_slices(s, mat.size(0), k, True)):
+            # max / min, opt-in (ISPLIB_HALF_MINMAX): the same question put to rows16_minmax_route; positions are wanted exactly when
+            # the call below goes to the *_planned operators
+            weighted = s._value is not None
+            want_arg = needs_grad or (value is not None and torch.is_grad_enabled() and value.requires_grad)
+            goes = lambda ordered: rows16_minmax_route(mat.dtype, reduce, k, pitch, None, mat.size(0), ordered, weighted, want_arg) == "rows16"  # noqa: E731
+            if goes(False) or goes(True):
+                cand = _rows16_plan(s, False, k, mat.device)
+                if goes(cand[0].numel() > 0):
+                    plan, rows16 = cand, True
         if rows16:
-            ran = ("rows16", "ordered") if plan[0].numel() > 0 else ("rows16",)
+            ran = ("rows16mm" if reduce in ("max", "min") else "rows16",) + (("ordered",) if plan[0].numel() > 0 else ())
         elif route == "convert":
             out = spmm_autotuned(src, other.to(torch.float32), reduce)
             s._last_schedule = ("convert",) + tuple(s._last_schedule or ())
