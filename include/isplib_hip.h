@@ -537,6 +537,33 @@ static inline int isplib_rows16_native_pays(int64_t n, int64_t ldy, int ordered,
 int    isplib_rows16_auto(int64_t n, int64_t ldy, int ordered, int weighted);      /* the same rule as a symbol */
 int    isplib_rows16_domain(int64_t n, int64_t k, int64_t ldy, int64_t ldz);       /* isplib_rows16_serves as a symbol */
 /*
+ * fusedMM_csr_rows16_hip with one fp32 factor per COLUMN of the sparse operand instead of one weight per edge:
+ *   z[i,:] = round16( sum over the edges e of row i of col_scale[indx[e]] * y[indx[e],:] ),   MEAN: divided by max(deg, 1).
+ * col_scale: n fp32 values in device memory.  The kernel is fusedMM_csr_rows16_hip's weighted kernel, and only the place a lane
+ * takes its edge's factor from differs (the table at the edge's column instead of val at the edge), so the result has, bit for bit,
+ * the bits of fusedMM_csr_rows16_hip given val[e] = col_scale[indx[e]] -- without an nnz-long weight stream.  The use it was built
+ * for: the backward of `mean` on an unweighted graph, A^T (diag(1 / max(deg, 1)) dY), with col_scale = 1 / max(deg, 1) of A's rows
+ * and a 16-bit dY that is never widened or scaled in memory.  Contract, determinism and row order: fusedMM_csr_rows16_hip's.
+ * Domain and refusals: fusedMM_csr_rows16_hip's, and col_scale == NULL with nnz > 0 is refused (ISPLIB_FAIL) before any launch.
+ * isplib_rows16_colscale_native_pays is the measured rule of the layers above for the unit-weight mean backward
+ * (profiles/rows16_colscale_ab.txt), over the classes (operand beyond 256 MiB at 2 bytes per element or not) x
+ * (rows in a community order or not): nonzero only where EVERY run of the backward on this entry was faster than EVERY run of the
+ * conversion route (widen dY, divide, the fp32 row kernel, narrow dX) on every measured shape of the class.
+ */
+int    fusedMM_csr_rows16_colscale_hip(int32_t imessage /* ISPLIB_MSG_SPMM_SUM | _MEAN */, int dtype /* ISPLIB_DTYPE_BF16 | _F16 */,
+                                       int64_t m, int64_t n, int64_t k, int64_t nnz, const float *col_scale /* [dev] n */,
+                                       const int64_t *indx, const int64_t *pntrb, const int64_t *pntre,
+                                       const int32_t *row_order /* optional */, const void *y, int64_t ldy, void *z, int64_t ldz, void *stream);
+static inline int isplib_rows16_colscale_native_pays(int64_t n, int64_t ldy, int ordered) {
+   /* measured (profiles/rows16_colscale_ab.txt: rows16_ab's shapes, bf16, the backward of mean on an unweighted graph): every class
+    * measured pays -- beyond 256 MiB in index order 0.54-0.65 of the conversion route's time, in a community order 0.52-0.64, inside
+    * 256 MiB in index order 0.41-0.88 (a quarter of the products shape 0.57, the launch-bound end saves three launches).  The one class
+    * not measured (inside 256 MiB AND a community order: the layers above never look for an order there) stays on convert. */
+   const int beyond = n > 0 && ldy > 0 && (double)n * (double)ldy * 2.0 > 256.0 * 1048576.0;
+   return (beyond || !ordered) ? 1 : 0;
+}
+int    isplib_rows16_colscale_auto(int64_t n, int64_t ldy, int ordered);           /* the same rule as a symbol */
+/*
  * fusedMM_csr_rows16_hip's schedule for max / min of a 16-bit dense operand: one CSR row per wavefront, 16-byte gathers of eight
  * columns, the optional row order, no fp32 copy of the operand.  The halves are widened in registers and every comparison is fp32:
  * the candidate of an edge is val * y (ONE fp32 multiply; val = NULL: y itself) and replaces the running value only if strictly

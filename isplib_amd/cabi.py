@@ -84,6 +84,15 @@ def rows16_minmax_native_pays(n: int, ldy: int, ordered: bool, weighted: bool, w
     return bool(n > 0 and ldy > 0 and n * ldy * 2 > (256 << 20))
 
 
+def rows16_colscale_native_pays(n: int, ldy: int, ordered: bool) -> bool:
+    """isplib_rows16_colscale_native_pays of the header: the classes of unit-weight mean backwards -- (dY beyond 256 MiB at 2 bytes
+    per element or not) x (rows of A^T in a community order or not) -- in which every run on the column-scaled 16-bit row kernel
+    measured faster than every run of the conversion route (profiles/rows16_colscale_ab.txt: every measured class does; dY inside
+    256 MiB AND a community order was not measured and stays on convert); tests/test_rows16_colscale_host.py compares the two."""
+    beyond = n > 0 and ldy > 0 and n * ldy * 2 > (256 << 20)
+    return bool(beyond or not ordered)
+
+
 def owner_exchange_serves(m: int, k: int, world: int, cuts) -> bool:
     """isplib_owner_exchange_serves of the header: m x k winners split for `world` owners at the row boundaries `cuts`."""
     if not 1 <= world <= OWNER_WORLD_MAX or m < 0 or k < 0 or m * k >= MINMAX_BW_PAIRS_END:
@@ -130,6 +139,7 @@ EXPORTS = (
     "fusedMM_csr_stream16_hip", "isplib_stream16_auto",
     "fusedMM_csr_rows16_hip", "isplib_rows16_auto", "isplib_rows16_domain",
     "fusedMM_csr_rows16_minmax_hip", "isplib_rows16_minmax_auto",
+    "fusedMM_csr_rows16_colscale_hip", "isplib_rows16_colscale_auto",
 )
 
 # include/isplib_hip_experimental.h (libisplib_hip_exp.so): forms measured slower than the defaults; tests and experiment scripts only
@@ -348,6 +358,10 @@ def lib() -> ctypes.CDLL:
         L.fusedMM_csr_rows16_minmax_hip.argtypes = [_i32, ctypes.c_int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp]
         L.isplib_rows16_minmax_auto.restype = ctypes.c_int
         L.isplib_rows16_minmax_auto.argtypes = [_i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+        L.fusedMM_csr_rows16_colscale_hip.restype = ctypes.c_int
+        L.fusedMM_csr_rows16_colscale_hip.argtypes = [_i32, ctypes.c_int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]
+        L.isplib_rows16_colscale_auto.restype = ctypes.c_int
+        L.isplib_rows16_colscale_auto.argtypes = [_i64, _i64, ctypes.c_int]
         _sigs_set = True
     return L
 
@@ -1213,6 +1227,14 @@ def spmm_rows16(rowptr, col, val, y, reduce: str = "sum", order=None, out=None):
     the same dtype at an even pitch, `order` a permutation's length."""
     if reduce not in ("sum", "add", "mean"):
         raise ValueError(f"isplib_amd: spmm_rows16 serves sum / mean, got '{reduce}'")
+    rowptr, col, val, order, out = _rows16_operands(rowptr, col, val, False, y, order, out)
+    fusedMM_csr_rows16_hip(MESSAGE[reduce], rowptr, col, val, order, y, out)
+    return out
+
+
+def _rows16_operands(rowptr, col, val, per_column: bool, y, order, out):
+    """The operand checks of spmm_rows16 and spmm_rows16_colscale (`per_column`: `val` is the n-entry table, not nnz weights);
+    returns (rowptr, col, val, order, out) as the entries take them."""
     if not isinstance(y, torch.Tensor) or not y.is_cuda or y.dim() != 2:
         raise ValueError("isplib_amd: `y` must be a 2-D GPU tensor [n, k]")
     if y.dtype not in HALF_DTYPES:
@@ -1225,7 +1247,13 @@ def spmm_rows16(rowptr, col, val, y, reduce: str = "sum", order=None, out=None):
         raise ValueError("isplib_amd: rowptr (m + 1 entries), col and y must be on one device")
     if k > 0 and y.stride(1) != 1:
         raise ValueError("isplib_amd: `y` must have unit inner stride")
-    if val is not None:
+    if per_column:
+        if val is None:
+            raise ValueError("isplib_amd: `scale` must be given (unit weights: spmm_rows16 with val=None)")
+        val = _dev(val, "scale", torch.float32)
+        if val.numel() != n or val.device != y.device:
+            raise ValueError("isplib_amd: `scale` must hold one float32 factor per row of `y`, on y's device")
+    elif val is not None:
         val = _dev(val, "val", torch.float32)
         if val.numel() != col.numel() or val.device != y.device:
             raise ValueError("isplib_amd: `val` must hold one float32 weight per entry of `col`, on y's device")
@@ -1248,7 +1276,36 @@ def spmm_rows16(rowptr, col, val, y, reduce: str = "sum", order=None, out=None):
             raise ValueError(f"isplib_amd: outside the 16-bit row entry's domain (isplib_rows16_serves: n={n}, k={k}, ldy={ldy}, ldz={ldz})")
         if (y.data_ptr() | out.data_ptr()) & 3:
             raise ValueError("isplib_amd: `y` and `out` must be 4-byte aligned")
-    fusedMM_csr_rows16_hip(MESSAGE[reduce], rowptr, col, val, order, y, out)
+    return rowptr, col, val, order, out
+
+
+def fusedMM_csr_rows16_colscale_hip(imessage: int, rowptr, col, scale, order, y, z, check: bool = True, dtype=None, k=None, ldy=None,
+                                    ldz=None) -> int:
+    """Raw boundary call of the column-scaled 16-bit row SpMM (sum / mean), for operands the entry may refuse: it hands over what
+    it is given (`dtype`, `k`, `ldy`, `ldz`: override what the tensors say -- refusal tests; the entry refuses before it reads
+    anything).  Callers that want their operands checked use spmm_rows16_colscale."""
+    m, n = rowptr.numel() - 1, y.size(0)
+    k = y.size(1) if k is None else int(k)
+    code = HALF_DTYPES.get(y.dtype, 0) if dtype is None else int(dtype)
+    rp = rowptr.data_ptr()
+    with torch.cuda.device(y.device):
+        st = lib().fusedMM_csr_rows16_colscale_hip(int(imessage), code, m, n, k, col.numel(), _ptr(scale), _ptr(col), ctypes.c_void_p(rp),
+                                                   ctypes.c_void_p(rp + 8), _ptr(order),
+                                                   _ptr(y), (y.stride(0) if n > 1 else max(k, y.stride(0))) if ldy is None else int(ldy),
+                                                   _ptr(z), (z.stride(0) if m > 1 else max(k, z.stride(0))) if ldz is None else int(ldz),
+                                                   _stream(y.device))
+    if check:
+        _check(st, "fusedMM_csr_rows16_colscale_hip")
+    return st
+
+
+def spmm_rows16_colscale(rowptr, col, scale, y, reduce: str = "sum", order=None, out=None):
+    """spmm_rows16 with one fp32 factor per column of the sparse operand, `scale` [n], in place of per-edge weights: the bits of
+    spmm_rows16(rowptr, col, scale[col], y, ...) without the nnz-long weight array.  The same operand checks BEFORE the call."""
+    if reduce not in ("sum", "add", "mean"):
+        raise ValueError(f"isplib_amd: spmm_rows16_colscale serves sum / mean, got '{reduce}'")
+    rowptr, col, scale, order, out = _rows16_operands(rowptr, col, scale, True, y, order, out)
+    fusedMM_csr_rows16_colscale_hip(MESSAGE[reduce], rowptr, col, scale, order, y, out)
     return out
 
 

@@ -11,6 +11,11 @@
 // The contract (the 16-bit stream kernel's): the halves are widened in registers, products, sums and the mean's
 // division are fp32, and the finished row is rounded ONCE, to nearest even -- NaN stays NaN, bf16 keeps subnormals, fp16 overflows
 // to +-Inf.  An empty row is 0.  No max / min, no epilogue, no column-sliced form here.
+//
+// Three weight modes (W_UNIT, W_EDGE, W_COL): no weights, one fp32 weight per edge (val[p]), or one fp32 factor per COLUMN taken
+// from an n-entry table (col_scale[indx[p]], fusedMM_csr_rows16_colscale_hip).  W_COL differs from W_EDGE only in where a lane's
+// factor of its edge of the 64-edge batch comes from -- one 4-byte load that depends on the index load instead of one that does
+// not -- so it computes, bit for bit, what W_EDGE computes on val[p] = col_scale[indx[p]], without the nnz-long weight stream.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -23,7 +28,7 @@ namespace isplib {
 
 struct Rows16Args {
    int64_t m, k;
-   const float *val;            // fp32 weights; null = unit weights
+   const float *val;            // fp32 weights, one per edge; null = unit weights.  W_COL: the table, one factor per column
    const int64_t *indx, *pntrb, *pntre;
    const void *y;               // n x ldy elements of 2 bytes
    int64_t ldy;
@@ -33,8 +38,11 @@ struct Rows16Args {
    int long_row;                // rows with more edges are split across the workgroup
    unsigned nblk;               // number of row blocks
    unsigned ybytes;             // n*ldy*2: the descriptor's size
+   unsigned sbytes;             // W_COL: n*4, the size of the table's descriptor (a column id outside [0, n) reads 0)
    const int32_t *row_order;    // position -> row, null = the identity
 };
+
+enum { W_UNIT = 0, W_EDGE = 1, W_COL = 2 };
 
 // gathers issued back to back per slot, and the occupancy the allocator is held to -- the fp32 plain kernel's 8 waves per SIMD
 // (gather.h, min_waves_of).  Four VGPRs per gather in flight as there, but eight accumulators per chunk instead of four and eight
@@ -84,10 +92,11 @@ __device__ __forceinline__ void rows16_step(const __amdgpu_buffer_rsrc_t rsrc, u
 
 // wave_edges_buf (gather.h) for this kernel: one wave walks edges [rb, re); edge metadata comes 64 per coalesced load, one 32-bit
 // multiply per edge (col * ldy * 2), handed off per step
-template <int ELT, bool HAS_VAL, int LPR, int NCH, int U>
-__device__ __forceinline__ void rows16_edges(const Rows16Args &a, const __amdgpu_buffer_rsrc_t rsrc, int64_t rb, int64_t re,
+template <int ELT, int WM, int LPR, int NCH, int U>
+__device__ __forceinline__ void rows16_edges(const Rows16Args &a, const __amdgpu_buffer_rsrc_t rsrc, const __amdgpu_buffer_rsrc_t srsrc, int64_t rb, int64_t re,
                                              const int (&ccol)[NCH], const bool (&cok)[NCH], float (&acc)[NCH][8]) {
    constexpr int G = 64 / LPR;
+   constexpr bool HAS_VAL = WM != W_UNIT;
    constexpr int UT = U >= 4 ? 2 : 1;   // tail granularity (U is a multiple of UT, so a step never passes edge 63 of its batch)
    static_assert(U % UT == 0 && 64 % (G * UT) == 0, "a tail step must end inside the batch");
    const int lane = threadIdx.x & 63;
@@ -105,7 +114,9 @@ __device__ __forceinline__ void rows16_edges(const Rows16Args &a, const __amdgpu
       float v_l = 0.0f;
       if (p < re) {
          off_l = (unsigned)a.indx[p] * ldyb;
-         if (HAS_VAL) v_l = a.val[p];
+         if (WM == W_EDGE) v_l = a.val[p];
+         // the column's factor: a valid id is < n < 2^28 (n*ldy*2 fits the descriptor and ldy >= 8), so id * 4 cannot wrap
+         if (WM == W_COL) v_l = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(srsrc, (int)((unsigned)a.indx[p] * 4u), 0, 0));
       }
       const int64_t left = re - base;
       const int cnt = left < 64 ? (int)left : 64;
@@ -132,7 +143,7 @@ __device__ __forceinline__ void rows16_write(const Rows16Args &a, int64_t row, i
       if (cok[j]) store_tail16x8<ELT>(zr + ccol[j], acc[j], vfirst[j]);
 }
 
-template <int ELT, bool HAS_VAL, int LPR, int NCH, int WAVES>
+template <int ELT, int WM, int LPR, int NCH, int WAVES>
 __global__ __launch_bounds__(WAVES * 64, (rows16_min_blocks<NCH>())) void spmm_rows16_kernel(const Rows16Args a) {
    constexpr int U = rows16_unroll<NCH>();
    constexpr int PANEL = LPR * 8 * NCH;     // columns covered by one grid.y panel
@@ -142,6 +153,8 @@ __global__ __launch_bounds__(WAVES * 64, (rows16_min_blocks<NCH>())) void spmm_r
    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
    const int g = lane / LPR, lc = lane % LPR;
    __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.y), 0, (int)a.ybytes, 0x00020000);
+   // W_COL: the table behind a descriptor of its own (kernel arguments only: wave-uniform); the other modes never read through it
+   __amdgpu_buffer_rsrc_t srsrc = WM == W_COL ? __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.val), 0, (int)a.sbytes, 0x00020000) : rsrc;
 
    // XCD-aware remap (spmm_csr_kernel, plain): blocks pb, pb + 8, ... share one XCD, which walks a contiguous range of row blocks
    const unsigned pb = blockIdx.x, nb = a.nblk;
@@ -177,7 +190,7 @@ __global__ __launch_bounds__(WAVES * 64, (rows16_min_blocks<NCH>())) void spmm_r
          for (int j = 0; j < NCH; j++)
 #pragma unroll
             for (int v = 0; v < 8; v++) acc[j][v] = 0.0f;
-         rows16_edges<ELT, HAS_VAL, LPR, NCH, U>(a, rsrc, b, e, ccol, cok, acc);
+         rows16_edges<ELT, WM, LPR, NCH, U>(a, rsrc, srsrc, b, e, ccol, cok, acc);
 #pragma unroll
          for (int off = LPR; off < 64; off <<= 1)        // butterfly over the 64 / LPR edge slots, fp32
 #pragma unroll
@@ -205,7 +218,7 @@ __global__ __launch_bounds__(WAVES * 64, (rows16_min_blocks<NCH>())) void spmm_r
       for (int j = 0; j < NCH; j++)
 #pragma unroll
          for (int v = 0; v < 8; v++) acc[j][v] = 0.0f;
-      rows16_edges<ELT, HAS_VAL, LPR, NCH, U>(a, rsrc, cb, ce, ccol, cok, acc);
+      rows16_edges<ELT, WM, LPR, NCH, U>(a, rsrc, srsrc, cb, ce, ccol, cok, acc);
 #pragma unroll
       for (int off = LPR; off < 64; off <<= 1)
 #pragma unroll
@@ -235,7 +248,7 @@ __global__ __launch_bounds__(WAVES * 64, (rows16_min_blocks<NCH>())) void spmm_r
    }
 }
 
-template <int ELT, bool HAS_VAL, int LPR, int NCH>
+template <int ELT, int WM, int LPR, int NCH>
 static int launch_rows16_cfg(const Rows16Args &a0, hipStream_t st) {
    constexpr int WAVES = 4;
    constexpr int PANEL = LPR * 8 * NCH;
@@ -245,20 +258,20 @@ static int launch_rows16_cfg(const Rows16Args &a0, hipStream_t st) {
    a.nblk = (unsigned)nb;
    const int64_t ny = (a.k + PANEL - 1) / PANEL;
    if (ny > 65535) return fail(ISPLIB_FAIL, "fusedMM_csr_rows16_hip", "too many column panels for one launch");
-   hipLaunchKernelGGL((spmm_rows16_kernel<ELT, HAS_VAL, LPR, NCH, WAVES>), dim3((unsigned)nb, (unsigned)ny, 1), dim3(WAVES * 64, 1, 1), 0, st, a);
+   hipLaunchKernelGGL((spmm_rows16_kernel<ELT, WM, LPR, NCH, WAVES>), dim3((unsigned)nb, (unsigned)ny, 1), dim3(WAVES * 64, 1, 1), 0, st, a);
    return check_launch("spmm_rows16_kernel");
 }
 
 // slot width by K (a slot is LPR lanes x 8 columns): 8 / 4 / 2 / 1 rows per gather instruction up to 64 / 128 / 256 / 512 columns,
 // two chunks per lane up to 1024, and 1024-column grid.y panels beyond
-template <int ELT, bool HAS_VAL>
+template <int ELT, int WM>
 static int launch_rows16(const Rows16Args &a, hipStream_t st) {
    const int64_t width = (a.k + 7) / 8;     // 16-byte vectors per row (ragged K: the last one is shifted back)
-   if (width <= 8) return launch_rows16_cfg<ELT, HAS_VAL, 8, 1>(a, st);
-   if (width <= 16) return launch_rows16_cfg<ELT, HAS_VAL, 16, 1>(a, st);
-   if (width <= 32) return launch_rows16_cfg<ELT, HAS_VAL, 32, 1>(a, st);
-   if (width <= 64) return launch_rows16_cfg<ELT, HAS_VAL, 64, 1>(a, st);
-   return launch_rows16_cfg<ELT, HAS_VAL, 64, 2>(a, st);
+   if (width <= 8) return launch_rows16_cfg<ELT, WM, 8, 1>(a, st);
+   if (width <= 16) return launch_rows16_cfg<ELT, WM, 16, 1>(a, st);
+   if (width <= 32) return launch_rows16_cfg<ELT, WM, 32, 1>(a, st);
+   if (width <= 64) return launch_rows16_cfg<ELT, WM, 64, 1>(a, st);
+   return launch_rows16_cfg<ELT, WM, 64, 2>(a, st);
 }
 
 }  // namespace isplib
@@ -268,11 +281,12 @@ using namespace isplib;
 extern "C" int isplib_rows16_auto(int64_t n, int64_t ldy, int ordered, int weighted) { return isplib_rows16_native_pays(n, ldy, ordered, weighted); }
 extern "C" int isplib_rows16_domain(int64_t n, int64_t k, int64_t ldy, int64_t ldz) { return isplib_rows16_serves(n, k, ldy, ldz); }
 
-extern "C" int fusedMM_csr_rows16_hip(int32_t imessage, int dtype, int64_t m, int64_t n, int64_t k, int64_t nnz, const float *val,
-                                      const int64_t *indx, const int64_t *pntrb, const int64_t *pntre, const int32_t *row_order,
-                                      const void *y, int64_t ldy, void *z, int64_t ldz, void *stream) {
+// the checks and the launch of both entries: `val` is the per-edge weights (wm = W_EDGE, or W_UNIT when null) or the per-column
+// table (wm = W_COL)
+static int rows16_entry(const char *entry, int wm, int32_t imessage, int dtype, int64_t m, int64_t n, int64_t k, int64_t nnz, const float *val,
+                        const int64_t *indx, const int64_t *pntrb, const int64_t *pntre, const int32_t *row_order,
+                        const void *y, int64_t ldy, void *z, int64_t ldz, void *stream) {
    clear_error();
-   const char *entry = "fusedMM_csr_rows16_hip";
    if (imessage != ISPLIB_MSG_SPMM_SUM && imessage != ISPLIB_MSG_SPMM_MEAN)
       return fail(ISPLIB_NO_OPT_IMPL, entry, "sum and mean only (max / min of a 16-bit operand: convert it and use fusedMM_csr_hip)");
    if (dtype != ISPLIB_DTYPE_BF16 && dtype != ISPLIB_DTYPE_F16) return fail(ISPLIB_FAIL, entry, "dtype must be ISPLIB_DTYPE_BF16 or ISPLIB_DTYPE_F16");
@@ -284,6 +298,7 @@ extern "C" int fusedMM_csr_rows16_hip(int32_t imessage, int dtype, int64_t m, in
                                       "n*ldy*2 <= 3.5 GiB (convert the operand and use fusedMM_csr_hip)");
    if (row_order && m >= (1LL << 31)) return fail(ISPLIB_FAIL, entry, "m must be < 2^31 (32-bit row order)");
    if (!pntrb || !pntre || !z || (nnz > 0 && (!indx || !y))) return fail(ISPLIB_FAIL, entry, "null operand");
+   if (wm == W_COL && nnz > 0 && !val) return fail(ISPLIB_FAIL, entry, "null col_scale (unit weights: fusedMM_csr_rows16_hip with val = NULL)");
    if ((((uintptr_t)y | (uintptr_t)z) & 3) != 0) return fail(ISPLIB_FAIL, entry, "y and z must be 4-byte aligned");
 
    Rows16Args a;
@@ -294,8 +309,27 @@ extern "C" int fusedMM_csr_rows16_hip(int32_t imessage, int dtype, int64_t m, in
    a.long_row = 2048;
    a.nblk = 0;
    a.ybytes = (unsigned)((unsigned long long)n * (unsigned long long)ldy * 2ull);
+   a.sbytes = wm == W_COL && val ? (unsigned)((unsigned long long)n * 4ull) : 0u;      // inside the domain n*ldy*2 fits 32 bits and ldy >= 8
    a.row_order = row_order;
    hipStream_t st = (hipStream_t)stream;
-   if (dtype == ISPLIB_DTYPE_BF16) return val ? launch_rows16<ELT_BF16, true>(a, st) : launch_rows16<ELT_BF16, false>(a, st);
-   return val ? launch_rows16<ELT_F16, true>(a, st) : launch_rows16<ELT_F16, false>(a, st);
+   const bool bf = dtype == ISPLIB_DTYPE_BF16;
+   if (wm == W_COL) return bf ? launch_rows16<ELT_BF16, W_COL>(a, st) : launch_rows16<ELT_F16, W_COL>(a, st);
+   if (val) return bf ? launch_rows16<ELT_BF16, W_EDGE>(a, st) : launch_rows16<ELT_F16, W_EDGE>(a, st);
+   return bf ? launch_rows16<ELT_BF16, W_UNIT>(a, st) : launch_rows16<ELT_F16, W_UNIT>(a, st);
+}
+
+extern "C" int fusedMM_csr_rows16_hip(int32_t imessage, int dtype, int64_t m, int64_t n, int64_t k, int64_t nnz, const float *val,
+                                      const int64_t *indx, const int64_t *pntrb, const int64_t *pntre, const int32_t *row_order,
+                                      const void *y, int64_t ldy, void *z, int64_t ldz, void *stream) {
+   return rows16_entry("fusedMM_csr_rows16_hip", val ? W_EDGE : W_UNIT, imessage, dtype, m, n, k, nnz, val, indx, pntrb, pntre, row_order, y, ldy, z,
+                       ldz, stream);
+}
+
+extern "C" int isplib_rows16_colscale_auto(int64_t n, int64_t ldy, int ordered) { return isplib_rows16_colscale_native_pays(n, ldy, ordered); }
+
+extern "C" int fusedMM_csr_rows16_colscale_hip(int32_t imessage, int dtype, int64_t m, int64_t n, int64_t k, int64_t nnz, const float *col_scale,
+                                               const int64_t *indx, const int64_t *pntrb, const int64_t *pntre, const int32_t *row_order,
+                                               const void *y, int64_t ldy, void *z, int64_t ldz, void *stream) {
+   return rows16_entry("fusedMM_csr_rows16_colscale_hip", W_COL, imessage, dtype, m, n, k, nnz, col_scale, indx, pntrb, pntre, row_order, y, ldy, z,
+                       ldz, stream);
 }

@@ -126,6 +126,12 @@ static inline bool is_rows16_plan(const Plan &p) {
    return p.size() == 2 && p[0].defined() && p[0].scalar_type() == at::kInt && p[1].defined() && !p[1].is_cuda() &&
           p[1].scalar_type() == at::kInt && p[1].numel() == 1 && p[1].data_ptr<int32_t>()[0] == 16;
 }
+// the three-element form a mean's plan_t may take: a 16-bit row plan + the fp32 device table 1 / max(deg, 1) of A's rows (the
+// plug-in's rows16_mean_bw_route said "rows16").  SpmmMean::backward reads it; everywhere else it means its first two tensors
+static inline bool is_rows16_colscale_plan(const Plan &p) {
+   return p.size() == 3 && is_rows16_plan(Plan{p[0], p[1]}) && p[2].defined() && p[2].is_cuda() && p[2].scalar_type() == at::kFloat &&
+          p[2].dim() == 1;
+}
 static inline const int32_t *plan_col32(const Plan &p, const Tensor &col) {
    if (p.size() != 6) return nullptr;
    TORCH_CHECK(p[5].scalar_type() == at::kInt && p[5].numel() == col.numel() && p[5].device() == col.device(),
@@ -390,6 +396,41 @@ std::tuple<Tensor, Tensor> spmm_fw_half(const Tensor &rowptr_, const Tensor &col
    }
    auto r = spmm_fw(rowptr_, col_, value_, mat_.to(at::kFloat), reduction, plan, want_arg);
    return std::make_tuple(std::get<0>(r).to(mat_.scalar_type()), std::get<1>(r));
+}
+
+// The unit-weight mean backward of a 16-bit dY on the column-scaled row kernel (fusedMM_csr_rows16_colscale_hip):
+// dX = A^T (diag(scale) dY) on (colptr, row_t, dY) with scale = 1 / max(deg, 1) applied per gathered row inside the kernel -- no fp32
+// dY / deg, no conversion of the result.  Undefined when the call is not served (spmm_fw_half's conditions): the caller then takes
+// the route it always took.
+static Tensor mean_bw_colscale(const Tensor &colptr_, const Tensor &row_t_, const Tensor &grad_out, const Plan &row_plan, const Tensor &scale_,
+                               int64_t rows_of_a) {
+   if (!is_half(grad_out) || !is_rows16_plan(row_plan) || grad_out.dim() != 2 || colptr_.dim() != 1 || colptr_.numel() < 1) return Tensor();
+   const int64_t M = colptr_.numel() - 1, N = grad_out.size(0), K = grad_out.size(1), nnz = row_t_.numel();
+   if (N != rows_of_a || scale_.numel() != N || M <= 0 || K <= 0 || !grad_out.is_cuda() || colptr_.device() != grad_out.device() ||
+       row_t_.device() != grad_out.device() || scale_.device() != grad_out.device() || colptr_.scalar_type() != at::kLong ||
+       row_t_.scalar_type() != at::kLong)
+      return Tensor();
+   c10::DeviceGuard guard(grad_out.device());
+   const bool as_is = row_strided(grad_out) && (reinterpret_cast<uintptr_t>(grad_out.data_ptr()) & 3) == 0 &&
+                      isplib_rows16_serves(N, K, N > 1 ? grad_out.stride(0) : K, K);
+   if (!as_is && !isplib_rows16_serves(N, K, K, K)) return Tensor();
+   const Tensor gy = as_is ? grad_out : packed16(grad_out);
+   const int64_t ldy = N > 1 ? gy.stride(0) : K;
+   const Tensor colptr = colptr_.contiguous(), row_t = row_t_.contiguous(), scale = scale_.contiguous();
+   const int32_t *order = nullptr;
+   Tensor order_t;
+   if (row_plan[0].numel() > 0) {
+      order_t = row_plan[0].contiguous();
+      TORCH_CHECK(order_t.is_cuda() && order_t.numel() == M, "isplib: the row order must hold one int32 position per row");
+      order = order_t.data_ptr<int32_t>();
+   }
+   Tensor out = at::empty({M, K}, gy.options());
+   const int64_t *cp = colptr.data_ptr<int64_t>();
+   const int st = fusedMM_csr_rows16_colscale_hip(ISPLIB_MSG_SPMM_SUM, gy.scalar_type() == at::kBFloat16 ? ISPLIB_DTYPE_BF16 : ISPLIB_DTYPE_F16,
+                                                  M, N, K, nnz, scale.data_ptr<float>(), row_t.data_ptr<int64_t>(), cp, cp + 1, order,
+                                                  gy.data_ptr(), ldy, out.data_ptr(), K, current_stream(gy));
+   check_status(st, "fusedMM_csr_rows16_colscale_hip");
+   return out;
 }
 
 // want_arg = false (max / min through the *_values operators: nobody will ask which edge won): on a stream plan the
@@ -762,15 +803,27 @@ class SpmmMean : public torch::autograd::Function<SpmmMean> {
          // of dY are scaled once (M x K elementwise) and the SUM on A^T runs with unit weights, i.e. without a weight stream
          const bool unit_planned = !has_value && colptr.defined() && new_row.defined() && !new_rowcount.defined() &&
                                    new_row.numel() == col.numel() && new_row.is_cuda();
+         // a plan_t of the three-element form (is_rows16_colscale_plan) is read by the unit_planned branch alone
+         Plan plan_t = ctx->saved_data["plan_t"].toTensorVector();
+         Tensor col_scale;
+         if (is_rows16_colscale_plan(plan_t)) {
+            col_scale = plan_t[2];
+            plan_t.pop_back();
+         }
          if (cached) {
-            grad_mat = std::get<0>(spmm_fw(colptr, new_row, optional<Tensor>(new_rowcount), grad_out, R_SUM,
-                                           ctx->saved_data["plan_t"].toTensorVector()));
+            grad_mat = std::get<0>(spmm_fw(colptr, new_row, optional<Tensor>(new_rowcount), grad_out, R_SUM, plan_t));
          } else if (unit_planned) {
-            // (a 16-bit dY: gy is formed and kept in fp32 -- rounding it here and the sum again would round twice -- so the
-            // SpMM on A^T takes the conversion route)
-            const Tensor deg = (rowptr.slice(0, 1) - rowptr.slice(0, 0, -1)).clamp_min(1).to(at::kFloat);
-            const Tensor gy = as_float(grad_out) / deg.unsqueeze(1);
-            grad_mat = std::get<0>(spmm_fw(colptr, new_row, c10::nullopt, gy, R_SUM, ctx->saved_data["plan_t"].toTensorVector())).to(mat.scalar_type());
+            // a 16-bit dY whose plan_t carries the table 1 / max(deg, 1): the column-scaled 16-bit row kernel applies it to the
+            // gathered rows of dY in fp32, inside the sum -- no fp32 copy of dY, one rounding
+            if (col_scale.defined())
+               grad_mat = mean_bw_colscale(colptr, new_row, grad_out, plan_t, col_scale, rowptr.numel() - 1);
+            if (!grad_mat.defined()) {
+               // (a 16-bit dY otherwise: gy is formed and kept in fp32 -- rounding it here and the sum again would round twice --
+               // so the SpMM on A^T takes the conversion route)
+               const Tensor deg = (rowptr.slice(0, 1) - rowptr.slice(0, 0, -1)).clamp_min(1).to(at::kFloat);
+               const Tensor gy = as_float(grad_out) / deg.unsqueeze(1);
+               grad_mat = std::get<0>(spmm_fw(colptr, new_row, c10::nullopt, gy, R_SUM, plan_t)).to(mat.scalar_type());
+            }
          } else {
             auto t = build_transpose(rowptr, col, has_value ? value : Tensor(), mat.size(0), true);
             grad_mat = std::get<0>(spmm_fw(t.colptr, t.row_t, optional<Tensor>(t.val_t), grad_out, R_SUM));

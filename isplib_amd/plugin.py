@@ -23,6 +23,8 @@ Differences from the reference, each a defect there:
 Environment: ISPLIB_SLICES=<n> forces the task list with n column slices (0: plain kernel); ISPLIB_STREAM=0 keeps
 sum / mean off the stream schedule; ISPLIB_STREAM_GEOM=streams:slices:chunk forces it with that plan geometry;
 ISPLIB_HALF=auto|native|convert picks the route of bf16 / fp16 features (half_route; rows16_route for calls on the plain kernel);
+ISPLIB_HALF_MINMAX=convert|native|auto does the same for max / min (rows16_minmax_route), ISPLIB_HALF_MEAN_BW=convert|native|auto
+for the backward of a 16-bit `mean` on an unweighted graph (rows16_mean_bw_route); both default to convert;
 ISPLIB_TUNE_FILE names a tuning table to load at import; ISPLIB_DEBUG=1 prints per-operator device times.
 """
 from __future__ import annotations
@@ -339,6 +341,30 @@ def rows16_minmax_route(dtype, reduce: str, k: int, pitch: int, mode: Optional[s
     return "rows16" if cabi.rows16_minmax_native_pays(n, ld, bool(ordered), bool(weighted), bool(want_arg)) else "convert"
 
 
+def rows16_mean_bw_route(dtype, k: int, m_rows: int, ordered: bool = False, mode: Optional[str] = None) -> str:
+    """Which way the backward of a `mean` with 16-bit features on an UNWEIGHTED graph goes when the plain row-per-wave kernel
+    serves its SpMM on A^T: "rows16" (the column-scaled 16-bit row kernel, fusedMM_csr_rows16_colscale_hip, on dY as it is: 1 / deg
+    is applied per gathered row inside the kernel -- no fp32 dY / deg, no conversion of dX) or "convert" (widen dY, divide, the fp32
+    row kernel, narrow dX).  A pure function -- no device, no library call:
+      * rows16 needs bf16 / fp16 and dY's shape, [m_rows, k] packed, inside the entry's domain (cabi.rows16_serves);
+      * `mode` is ISPLIB_HALF_MEAN_BW (None: read from the environment; default "convert", and ISPLIB_HALF=convert wins over it):
+        "convert" always converts, "native" takes the kernel wherever the above holds, "auto" only in the classes -- (dY beyond
+        256 MiB or not) x `ordered` (the rows of A^T come in a community order) -- where every native run measured faster than
+        every run of the conversion route (cabi.rows16_colscale_native_pays, profiles/rows16_colscale_ab.txt).  Nothing raises."""
+    if dtype not in HALF_DTYPES:
+        return "convert"
+    from . import cabi
+    if mode is None:
+        mode = "convert" if os.environ.get("ISPLIB_HALF", "auto") == "convert" else os.environ.get("ISPLIB_HALF_MEAN_BW", "convert")
+    if mode not in ("native", "auto"):
+        return "convert"
+    if not cabi.rows16_serves(m_rows, k, k, k):
+        return "convert"
+    if mode == "native":
+        return "rows16"
+    return "rows16" if cabi.rows16_colscale_native_pays(m_rows, k, bool(ordered)) else "convert"
+
+
 _ROWS16_MARK = torch.tensor([16], dtype=torch.int32)      # second tensor of a 16-bit row plan (torch_ops.cpp: is_rows16_plan)
 
 
@@ -438,9 +464,13 @@ def spmm_autotuned(src, other: torch.Tensor, reduce: str = "sum") -> torch.Tenso
                 plan_t = s.plan_t(choose_slices(s, m_rows, k, transposed=True))
                 if not plan_t:
                     # the backward (A^T dY) of a 16-bit call: the same route under the same rule, on the transposed arrays.  The
-                    # unit-weight mean backward forms dY / deg in fp32 first: an fp32 operand, its row order judged at 4 bytes
+                    # unit-weight mean backward forms dY / deg in fp32 first: an fp32 operand, its row order judged at 4 bytes --
+                    # unless rows16_mean_bw_route (opt-in: ISPLIB_HALF_MEAN_BW) sends it to the column-scaled 16-bit kernel, which
+                    # takes dY as it is and 1 / deg as a table
                     if half and not unit_mean and _rows16_backward(s, mat, reduce, k, m_rows, val_t is not None):
                         plan_t = _rows16_plan(s, True, k, mat.device)
+                    elif half and unit_mean and _rows16_mean_backward(s, mat, k, m_rows):
+                        plan_t = _rows16_plan(s, True, k, mat.device) + [s.inv_rowcount()]
                     else:
                         plan_t = s.row_order(True, k)
         if reduce == "mean":
@@ -462,6 +492,14 @@ def _rows16_backward(s: SparseStorage, mat: torch.Tensor, reduce: str, k: int, m
     """Whether A^T dY of a 16-bit call (dY: [m_rows, k], packed, of mat's dtype) takes the 16-bit row kernel: rows16_route with the
     transposed side's row order.  (Not asked for the unit-weight mean backward, whose operand dY / deg is fp32.)"""
     goes = lambda ordered: rows16_route(mat.dtype, reduce, k, k, None, m_rows, ordered, weighted) == "rows16"  # noqa: E731
+    return (goes(False) or goes(True)) and goes(bool(s.row_order(True, k, itemsize=2)))
+
+
+def _rows16_mean_backward(s: SparseStorage, mat: torch.Tensor, k: int, m_rows: int) -> bool:
+    """Whether the backward of a 16-bit `mean` on an unweighted graph takes the column-scaled 16-bit row kernel:
+    rows16_mean_bw_route with the transposed side's row order, judged at 2 bytes per element as in _rows16_backward (looked for
+    only when some answer to it can send the call there)."""
+    goes = lambda ordered: rows16_mean_bw_route(mat.dtype, k, m_rows, ordered) == "rows16"  # noqa: E731
     return (goes(False) or goes(True)) and goes(bool(s.row_order(True, k, itemsize=2)))
 
 

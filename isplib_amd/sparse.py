@@ -221,6 +221,14 @@ class SparseStorage:
             self._gcn_dinv = (self.rowcount() + 1).to(torch.float32).pow(-0.5)
         return self._gcn_dinv
 
+    def inv_rowcount(self) -> torch.Tensor:
+        """1 / max(rowcount, 1) per row, fp32: one fp32 division of 1 by the degree, which is what mean_val_t holds per edge of an
+        all-ones graph -- the column factors of the unit-weight mean backward on the 16-bit row kernel (plugin.py)."""
+        if getattr(self, "_inv_rowcount", None) is None:
+            deg = self.rowcount().clamp_min(1).to(torch.float32)
+            self._inv_rowcount = torch.ones((), dtype=torch.float32, device=deg.device) / deg
+        return self._inv_rowcount
+
     def mean_val_t(self) -> torch.Tensor:
         """value[csr2csc] / max(rowcount,1)[row[csr2csc]] (csrc/fusedmm.cpp:357-364)."""
         if self._mean_val_t is None or self._mean_val_t_state != self._value_state():
