@@ -1201,22 +1201,28 @@ def spmm_stream16(rowptr, nnz: int, plan, y, reduce: str = "sum", workspace=None
     return out
 
 
-def fusedMM_csr_rows16_hip(imessage: int, rowptr, col, val, order, y, z, check: bool = True, dtype=None, k=None, ldy=None, ldz=None) -> int:
-    """Raw boundary call of the 16-bit row SpMM (sum / mean), for operands the entry may refuse: it hands over what it is given
-    (`dtype`, `k`, `ldy`, `ldz`: override what the tensors say -- refusal tests; the entry refuses before it reads anything).
-    Callers that want their operands checked use spmm_rows16."""
+def _rows16_raw(symbol: str, imessage: int, rowptr, col, val, order, y, z, check, dtype, k, ldy, ldz, *tail) -> int:
+    """The raw boundary call shared by the three entries of the 16-bit row family (`tail`: an entry's own trailing arguments)."""
     m, n = rowptr.numel() - 1, y.size(0)
     k = y.size(1) if k is None else int(k)
     code = HALF_DTYPES.get(y.dtype, 0) if dtype is None else int(dtype)
     rp = rowptr.data_ptr()
     with torch.cuda.device(y.device):
-        st = lib().fusedMM_csr_rows16_hip(int(imessage), code, m, n, k, col.numel(), _ptr(val), _ptr(col), ctypes.c_void_p(rp),
-                                          ctypes.c_void_p(rp + 8), _ptr(order),
-                                          _ptr(y), (y.stride(0) if n > 1 else max(k, y.stride(0))) if ldy is None else int(ldy),
-                                          _ptr(z), (z.stride(0) if m > 1 else max(k, z.stride(0))) if ldz is None else int(ldz), _stream(y.device))
+        st = getattr(lib(), symbol)(int(imessage), code, m, n, k, col.numel(), _ptr(val), _ptr(col), ctypes.c_void_p(rp),
+                                    ctypes.c_void_p(rp + 8), _ptr(order),
+                                    _ptr(y), (y.stride(0) if n > 1 else max(k, y.stride(0))) if ldy is None else int(ldy),
+                                    _ptr(z), (z.stride(0) if m > 1 else max(k, z.stride(0))) if ldz is None else int(ldz), *tail,
+                                    _stream(y.device))
     if check:
-        _check(st, "fusedMM_csr_rows16_hip")
+        _check(st, symbol)
     return st
+
+
+def fusedMM_csr_rows16_hip(imessage: int, rowptr, col, val, order, y, z, check: bool = True, dtype=None, k=None, ldy=None, ldz=None) -> int:
+    """Raw boundary call of the 16-bit row SpMM (sum / mean), for operands the entry may refuse: it hands over what it is given
+    (`dtype`, `k`, `ldy`, `ldz`: override what the tensors say -- refusal tests; the entry refuses before it reads anything).
+    Callers that want their operands checked use spmm_rows16."""
+    return _rows16_raw("fusedMM_csr_rows16_hip", imessage, rowptr, col, val, order, y, z, check, dtype, k, ldy, ldz)
 
 
 def spmm_rows16(rowptr, col, val, y, reduce: str = "sum", order=None, out=None):
@@ -1227,14 +1233,15 @@ def spmm_rows16(rowptr, col, val, y, reduce: str = "sum", order=None, out=None):
     the same dtype at an even pitch, `order` a permutation's length."""
     if reduce not in ("sum", "add", "mean"):
         raise ValueError(f"isplib_amd: spmm_rows16 serves sum / mean, got '{reduce}'")
-    rowptr, col, val, order, out = _rows16_operands(rowptr, col, val, False, y, order, out)
+    rowptr, col, val, order, out, _ = _rows16_operands(rowptr, col, val, False, y, order, out)
     fusedMM_csr_rows16_hip(MESSAGE[reduce], rowptr, col, val, order, y, out)
     return out
 
 
-def _rows16_operands(rowptr, col, val, per_column: bool, y, order, out):
-    """The operand checks of spmm_rows16 and spmm_rows16_colscale (`per_column`: `val` is the n-entry table, not nnz weights);
-    returns (rowptr, col, val, order, out) as the entries take them."""
+def _rows16_operands(rowptr, col, val, per_column: bool, y, order, out, arg=None, want_arg: bool = False):
+    """The operand checks of spmm_rows16, spmm_rows16_minmax and spmm_rows16_colscale (`per_column`: `val` is the n-entry table, not nnz weights);
+    returns (rowptr, col, val, order, out, arg) as the entries take them.  The max / min wrapper also hands over its positions tensor
+    `arg` (allocated when `want_arg` and not given), checked in its place among the others, and gets it back; the others get None."""
     if not isinstance(y, torch.Tensor) or not y.is_cuda or y.dim() != 2:
         raise ValueError("isplib_amd: `y` must be a 2-D GPU tensor [n, k]")
     if y.dtype not in HALF_DTYPES:
@@ -1270,106 +1277,6 @@ def _rows16_operands(rowptr, col, val, per_column: bool, y, order, out):
         out = torch.empty((m, k), dtype=y.dtype, device=y.device)
     elif not isinstance(out, torch.Tensor) or out.device != y.device or tuple(out.shape) != (m, k) or out.dtype != y.dtype or (k > 0 and out.stride(1) != 1):
         raise ValueError(f"isplib_amd: `out` must be a [{m}, {k}] {y.dtype} tensor on {y.device} with unit inner stride")
-    ldz = out.stride(0) if m > 1 else max(k, out.stride(0))
-    if m > 0 and k > 0:
-        if ldy < k or ldz < k or not rows16_serves(n, k, ldy, ldz):
-            raise ValueError(f"isplib_amd: outside the 16-bit row entry's domain (isplib_rows16_serves: n={n}, k={k}, ldy={ldy}, ldz={ldz})")
-        if (y.data_ptr() | out.data_ptr()) & 3:
-            raise ValueError("isplib_amd: `y` and `out` must be 4-byte aligned")
-    return rowptr, col, val, order, out
-
-
-def fusedMM_csr_rows16_colscale_hip(imessage: int, rowptr, col, scale, order, y, z, check: bool = True, dtype=None, k=None, ldy=None,
-                                    ldz=None) -> int:
-    """Raw boundary call of the column-scaled 16-bit row SpMM (sum / mean), for operands the entry may refuse: it hands over what
-    it is given (`dtype`, `k`, `ldy`, `ldz`: override what the tensors say -- refusal tests; the entry refuses before it reads
-    anything).  Callers that want their operands checked use spmm_rows16_colscale."""
-    m, n = rowptr.numel() - 1, y.size(0)
-    k = y.size(1) if k is None else int(k)
-    code = HALF_DTYPES.get(y.dtype, 0) if dtype is None else int(dtype)
-    rp = rowptr.data_ptr()
-    with torch.cuda.device(y.device):
-        st = lib().fusedMM_csr_rows16_colscale_hip(int(imessage), code, m, n, k, col.numel(), _ptr(scale), _ptr(col), ctypes.c_void_p(rp),
-                                                   ctypes.c_void_p(rp + 8), _ptr(order),
-                                                   _ptr(y), (y.stride(0) if n > 1 else max(k, y.stride(0))) if ldy is None else int(ldy),
-                                                   _ptr(z), (z.stride(0) if m > 1 else max(k, z.stride(0))) if ldz is None else int(ldz),
-                                                   _stream(y.device))
-    if check:
-        _check(st, "fusedMM_csr_rows16_colscale_hip")
-    return st
-
-
-def spmm_rows16_colscale(rowptr, col, scale, y, reduce: str = "sum", order=None, out=None):
-    """spmm_rows16 with one fp32 factor per column of the sparse operand, `scale` [n], in place of per-edge weights: the bits of
-    spmm_rows16(rowptr, col, scale[col], y, ...) without the nnz-long weight array.  The same operand checks BEFORE the call."""
-    if reduce not in ("sum", "add", "mean"):
-        raise ValueError(f"isplib_amd: spmm_rows16_colscale serves sum / mean, got '{reduce}'")
-    rowptr, col, scale, order, out = _rows16_operands(rowptr, col, scale, True, y, order, out)
-    fusedMM_csr_rows16_colscale_hip(MESSAGE[reduce], rowptr, col, scale, order, y, out)
-    return out
-
-
-def fusedMM_csr_rows16_minmax_hip(imessage: int, rowptr, col, val, order, y, z, z_arg=None, check: bool = True, dtype=None, k=None, ldy=None,
-                                  ldz=None, ldarg=None) -> int:
-    """Raw boundary call of the 16-bit row SpMM for max / min, for operands the entry may refuse: it hands over what it is given
-    (`dtype`, `k`, `ldy`, `ldz`, `ldarg`: override what the tensors say -- refusal tests; the entry refuses before it reads anything).
-    `z_arg` None is the values-only launch.  Callers that want their operands checked use spmm_rows16_minmax."""
-    m, n = rowptr.numel() - 1, y.size(0)
-    k = y.size(1) if k is None else int(k)
-    code = HALF_DTYPES.get(y.dtype, 0) if dtype is None else int(dtype)
-    rp = rowptr.data_ptr()
-    if ldarg is None:
-        ldarg = 0 if z_arg is None else (z_arg.stride(0) if m > 1 else max(k, z_arg.stride(0)))
-    with torch.cuda.device(y.device):
-        st = lib().fusedMM_csr_rows16_minmax_hip(int(imessage), code, m, n, k, col.numel(), _ptr(val), _ptr(col), ctypes.c_void_p(rp),
-                                                 ctypes.c_void_p(rp + 8), _ptr(order),
-                                                 _ptr(y), (y.stride(0) if n > 1 else max(k, y.stride(0))) if ldy is None else int(ldy),
-                                                 _ptr(z), (z.stride(0) if m > 1 else max(k, z.stride(0))) if ldz is None else int(ldz),
-                                                 _ptr(z_arg), int(ldarg), _stream(y.device))
-    if check:
-        _check(st, "fusedMM_csr_rows16_minmax_hip")
-    return st
-
-
-def spmm_rows16_minmax(rowptr, col, val, y, reduce: str = "max", order=None, out=None, arg=None, want_arg: bool = True):
-    """The 16-bit row SpMM for max / min of a bf16 / fp16 `y` [n, k]: returns (out, arg) -- `out` [m, k] of y's dtype and `arg` int64
-    [m, k], the CSR position of each winner (col.numel() where nothing won); both allocated when not given, row-strided views are
-    written at their own pitch.  want_arg=False (and no `arg`): the values-only launch, returns (out, None) with the same value bits.
-    `val`: fp32 weights or None; `order`: int32 [m], position -> row, or None.  Values and positions are bit-equal to the fp32 kernel's
-    on the widened operand, rounded once.  Every operand is checked BEFORE the call -- a mis-shaped one is an out-of-bounds device
-    read: rowptr / col int64 on y's device, rowptr ascending from 0 to col.numel(), every column id inside [0, n), the shape inside
-    isplib_rows16_serves, `out` [m, k] of the same dtype at an even pitch, `arg` int64 [m, k], `order` a permutation's length."""
-    if reduce not in ("max", "min"):
-        raise ValueError(f"isplib_amd: spmm_rows16_minmax serves max / min, got '{reduce}' (sum / mean: spmm_rows16)")
-    if not isinstance(y, torch.Tensor) or not y.is_cuda or y.dim() != 2:
-        raise ValueError("isplib_amd: `y` must be a 2-D GPU tensor [n, k]")
-    if y.dtype not in HALF_DTYPES:
-        raise TypeError(f"isplib_amd: `y` must be bfloat16 or float16, got {y.dtype} (float32: spmm)")
-    rowptr = _dev(rowptr, "rowptr", torch.int64)
-    col = _dev(col, "col", torch.int64)
-    n, k = y.size(0), y.size(1)
-    m = rowptr.numel() - 1
-    if m < 0 or rowptr.device != y.device or col.device != y.device:
-        raise ValueError("isplib_amd: rowptr (m + 1 entries), col and y must be on one device")
-    if k > 0 and y.stride(1) != 1:
-        raise ValueError("isplib_amd: `y` must have unit inner stride")
-    if val is not None:
-        val = _dev(val, "val", torch.float32)
-        if val.numel() != col.numel() or val.device != y.device:
-            raise ValueError("isplib_amd: `val` must hold one float32 weight per entry of `col`, on y's device")
-    if order is not None:
-        order = _dev(order, "order", torch.int32)
-        if order.numel() != m or order.device != y.device or (m > 0 and (int(order.min()) < 0 or int(order.max()) >= m)):
-            raise ValueError("isplib_amd: `order` must hold one int32 row in [0, m) per position, on y's device")
-    if m > 0 and (int(rowptr[0]) != 0 or int(rowptr[-1]) != col.numel() or bool((rowptr[1:] < rowptr[:-1]).any())):
-        raise ValueError("isplib_amd: rowptr must ascend from 0 to col.numel()")
-    if col.numel() > 0 and (int(col.min()) < 0 or int(col.max()) >= n):
-        raise ValueError(f"isplib_amd: column ids must lie in [0, {n})")
-    ldy = y.stride(0) if n > 1 else max(k, y.stride(0))
-    if out is None:
-        out = torch.empty((m, k), dtype=y.dtype, device=y.device)
-    elif not isinstance(out, torch.Tensor) or out.device != y.device or tuple(out.shape) != (m, k) or out.dtype != y.dtype or (k > 0 and out.stride(1) != 1):
-        raise ValueError(f"isplib_amd: `out` must be a [{m}, {k}] {y.dtype} tensor on {y.device} with unit inner stride")
     if arg is None:
         arg = torch.empty((m, k), dtype=torch.int64, device=y.device) if want_arg else None
     elif not isinstance(arg, torch.Tensor) or arg.device != y.device or tuple(arg.shape) != (m, k) or arg.dtype != torch.int64 or (k > 0 and arg.stride(1) != 1):
@@ -1382,6 +1289,49 @@ def spmm_rows16_minmax(rowptr, col, val, y, reduce: str = "max", order=None, out
             raise ValueError("isplib_amd: `arg` rows must not overlap")
         if (y.data_ptr() | out.data_ptr()) & 3:
             raise ValueError("isplib_amd: `y` and `out` must be 4-byte aligned")
+    return rowptr, col, val, order, out, arg
+
+
+def fusedMM_csr_rows16_colscale_hip(imessage: int, rowptr, col, scale, order, y, z, check: bool = True, dtype=None, k=None, ldy=None,
+                                    ldz=None) -> int:
+    """Raw boundary call of the column-scaled 16-bit row SpMM (sum / mean), for operands the entry may refuse: it hands over what
+    it is given (`dtype`, `k`, `ldy`, `ldz`: override what the tensors say -- refusal tests; the entry refuses before it reads
+    anything).  Callers that want their operands checked use spmm_rows16_colscale."""
+    return _rows16_raw("fusedMM_csr_rows16_colscale_hip", imessage, rowptr, col, scale, order, y, z, check, dtype, k, ldy, ldz)
+
+
+def spmm_rows16_colscale(rowptr, col, scale, y, reduce: str = "sum", order=None, out=None):
+    """spmm_rows16 with one fp32 factor per column of the sparse operand, `scale` [n], in place of per-edge weights: the bits of
+    spmm_rows16(rowptr, col, scale[col], y, ...) without the nnz-long weight array.  The same operand checks BEFORE the call."""
+    if reduce not in ("sum", "add", "mean"):
+        raise ValueError(f"isplib_amd: spmm_rows16_colscale serves sum / mean, got '{reduce}'")
+    rowptr, col, scale, order, out, _ = _rows16_operands(rowptr, col, scale, True, y, order, out)
+    fusedMM_csr_rows16_colscale_hip(MESSAGE[reduce], rowptr, col, scale, order, y, out)
+    return out
+
+
+def fusedMM_csr_rows16_minmax_hip(imessage: int, rowptr, col, val, order, y, z, z_arg=None, check: bool = True, dtype=None, k=None, ldy=None,
+                                  ldz=None, ldarg=None) -> int:
+    """Raw boundary call of the 16-bit row SpMM for max / min, for operands the entry may refuse: it hands over what it is given
+    (`dtype`, `k`, `ldy`, `ldz`, `ldarg`: override what the tensors say -- refusal tests; the entry refuses before it reads anything).
+    `z_arg` None is the values-only launch.  Callers that want their operands checked use spmm_rows16_minmax."""
+    if ldarg is None:
+        m, kk = rowptr.numel() - 1, y.size(1) if k is None else int(k)
+        ldarg = 0 if z_arg is None else (z_arg.stride(0) if m > 1 else max(kk, z_arg.stride(0)))
+    return _rows16_raw("fusedMM_csr_rows16_minmax_hip", imessage, rowptr, col, val, order, y, z, check, dtype, k, ldy, ldz, _ptr(z_arg), int(ldarg))
+
+
+def spmm_rows16_minmax(rowptr, col, val, y, reduce: str = "max", order=None, out=None, arg=None, want_arg: bool = True):
+    """The 16-bit row SpMM for max / min of a bf16 / fp16 `y` [n, k]: returns (out, arg) -- `out` [m, k] of y's dtype and `arg` int64
+    [m, k], the CSR position of each winner (col.numel() where nothing won); both allocated when not given, row-strided views are
+    written at their own pitch.  want_arg=False (and no `arg`): the values-only launch, returns (out, None) with the same value bits.
+    `val`: fp32 weights or None; `order`: int32 [m], position -> row, or None.  Values and positions are bit-equal to the fp32 kernel's
+    on the widened operand, rounded once.  Every operand is checked BEFORE the call -- a mis-shaped one is an out-of-bounds device
+    read: rowptr / col int64 on y's device, rowptr ascending from 0 to col.numel(), every column id inside [0, n), the shape inside
+    isplib_rows16_serves, `out` [m, k] of the same dtype at an even pitch, `arg` int64 [m, k], `order` a permutation's length."""
+    if reduce not in ("max", "min"):
+        raise ValueError(f"isplib_amd: spmm_rows16_minmax serves max / min, got '{reduce}' (sum / mean: spmm_rows16)")
+    rowptr, col, val, order, out, arg = _rows16_operands(rowptr, col, val, False, y, order, out, arg, want_arg)
     fusedMM_csr_rows16_minmax_hip(MESSAGE[reduce], rowptr, col, val, order, y, out, arg)
     return out, arg
 

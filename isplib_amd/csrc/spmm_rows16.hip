@@ -3,10 +3,10 @@
 // (DESIGN.md 4.2), and a 16-bit row is half the lines: a lane's gather stays 16 bytes and now holds EIGHT columns, so a slot of LPR
 // lanes covers LPR * 8 columns and a row of K columns takes half as many gather instructions as in fp32.
 //
-// Mapping: spmm_csr_kernel's plain mode -- one row per wave, WAVES rows per workgroup, blockIdx remapped so that an XCD walks a
-// contiguous range of positions, an optional row order (position -> row), rows over long_row edges taken by all waves of the
-// workgroup with a fixed-order LDS combine in fp32.  No atomics: two launches give equal bits, and any row order gives the bits of
-// index order.
+// Mapping (its pieces shared with spmm_rows16_minmax.hip: rows16_common.h): spmm_csr_kernel's plain mode -- one row per wave,
+// WAVES rows per workgroup, blockIdx remapped so that an XCD walks a contiguous range of positions, an optional row order
+// (position -> row), rows over long_row edges taken by all waves of the workgroup with a fixed-order LDS combine in fp32.  No
+// atomics: two launches give equal bits, and any row order gives the bits of index order.
 //
 // The contract (the 16-bit stream kernel's): the halves are widened in registers, products, sums and the mean's
 // division are fp32, and the finished row is rounded ONCE, to nearest even -- NaN stays NaN, bf16 keeps subnormals, fp16 overflows
@@ -23,6 +23,7 @@
 #include "common.h"
 #include "gather.h"
 #include "half16.h"
+#include "rows16_common.h"
 
 namespace isplib {
 
@@ -90,40 +91,21 @@ __device__ __forceinline__ void rows16_step(const __amdgpu_buffer_rsrc_t rsrc, u
    }
 }
 
-// wave_edges_buf (gather.h) for this kernel: one wave walks edges [rb, re); edge metadata comes 64 per coalesced load, one 32-bit
-// multiply per edge (col * ldy * 2), handed off per step
+// one wave's edges [rb, re) on rows16_batches (rows16_common.h): the weight of an edge by mode, rows16_step per step
 template <int ELT, int WM, int LPR, int NCH, int U>
 __device__ __forceinline__ void rows16_edges(const Rows16Args &a, const __amdgpu_buffer_rsrc_t rsrc, const __amdgpu_buffer_rsrc_t srsrc, int64_t rb, int64_t re,
                                              const int (&ccol)[NCH], const bool (&cok)[NCH], float (&acc)[NCH][8]) {
-   constexpr int G = 64 / LPR;
-   constexpr bool HAS_VAL = WM != W_UNIT;
-   constexpr int UT = U >= 4 ? 2 : 1;   // tail granularity (U is a multiple of UT, so a step never passes edge 63 of its batch)
-   static_assert(U % UT == 0 && 64 % (G * UT) == 0, "a tail step must end inside the batch");
-   const int lane = threadIdx.x & 63;
-   const int g = lane / LPR;
-   const unsigned ldyb = (unsigned)a.ldy * 2u;
-   unsigned cbyte[NCH], poison[NCH];
-#pragma unroll
-   for (int j = 0; j < NCH; j++) {
-      cbyte[j] = (unsigned)ccol[j] * 2u;
-      poison[j] = cok[j] ? 0u : BUF_OOB;
-   }
-   for (int64_t base = rb; base < re; base += 64) {
-      const int64_t p = base + lane;
-      unsigned off_l = BUF_OOB;
-      float v_l = 0.0f;
-      if (p < re) {
-         off_l = (unsigned)a.indx[p] * ldyb;
-         if (WM == W_EDGE) v_l = a.val[p];
+   rows16_batches<LPR, NCH, U>(
+      a, rb, re, ccol, cok,
+      [&](int64_t p) {
+         if (WM == W_EDGE) return a.val[p];
          // the column's factor: a valid id is < n < 2^28 (n*ldy*2 fits the descriptor and ldy >= 8), so id * 4 cannot wrap
-         if (WM == W_COL) v_l = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(srsrc, (int)((unsigned)a.indx[p] * 4u), 0, 0));
-      }
-      const int64_t left = re - base;
-      const int cnt = left < 64 ? (int)left : 64;
-      int s = 0;
-      for (; s + G * U <= cnt; s += G * U) rows16_step<ELT, HAS_VAL, LPR, NCH, U>(rsrc, off_l, v_l, s, g, cbyte, poison, acc);
-      for (; s < cnt; s += G * UT) rows16_step<ELT, HAS_VAL, LPR, NCH, UT>(rsrc, off_l, v_l, s, g, cbyte, poison, acc);
-   }
+         if (WM == W_COL) return __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(srsrc, (int)((unsigned)a.indx[p] * 4u), 0, 0));
+         return 0.0f;
+      },
+      [&](auto uu, auto, unsigned off_l, float v_l, int s, int, int64_t, int g, const unsigned (&cbyte)[NCH], const unsigned (&poison)[NCH]) {
+         rows16_step<ELT, WM != W_UNIT, LPR, NCH, decltype(uu)::value>(rsrc, off_l, v_l, s, g, cbyte, poison, acc);
+      });
 }
 
 // the finished fp32 row of the g == 0 lanes: the mean's division, then rounded once and stored
@@ -152,30 +134,15 @@ __global__ __launch_bounds__(WAVES * 64, (rows16_min_blocks<NCH>())) void spmm_r
    const int lane = threadIdx.x & 63;
    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
    const int g = lane / LPR, lc = lane % LPR;
-   __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.y), 0, (int)a.ybytes, 0x00020000);
+   __amdgpu_buffer_rsrc_t rsrc = rows16_desc(a.y, a.ybytes);
    // W_COL: the table behind a descriptor of its own (kernel arguments only: wave-uniform); the other modes never read through it
-   __amdgpu_buffer_rsrc_t srsrc = WM == W_COL ? __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.val), 0, (int)a.sbytes, 0x00020000) : rsrc;
+   __amdgpu_buffer_rsrc_t srsrc = WM == W_COL ? rows16_desc(a.val, a.sbytes) : rsrc;
 
-   // XCD-aware remap (spmm_csr_kernel, plain): blocks pb, pb + 8, ... share one XCD, which walks a contiguous range of row blocks
-   const unsigned pb = blockIdx.x, nb = a.nblk;
-   const unsigned xcd = pb & 7u, within = pb >> 3;
-   const unsigned per = nb >> 3, rem = nb & 7u;
-   const unsigned lb = xcd * per + (xcd < rem ? xcd : rem) + within;
-
-   // a lane's eight columns per chunk; ragged K (k % 8 != 0): the last 16-byte vector of a row is shifted back to end at column k,
-   // its first vfirst components duplicate the neighbouring lane's work and are not stored
-   int ccol[NCH], vfirst[NCH];
+   int ccol[NCH], vfirst[NCH];                     // the family's column map, block remap and chunk split: rows16_common.h
    bool cok[NCH];
 #pragma unroll
-   for (int j = 0; j < NCH; j++) {
-      ccol[j] = (int)blockIdx.y * PANEL + (j * LPR + lc) * 8;
-      cok[j] = ccol[j] < a.k;
-      vfirst[j] = 0;
-      if (cok[j] && ccol[j] + 8 > (int)a.k) {
-         vfirst[j] = ccol[j] + 8 - (int)a.k;
-         ccol[j] = (int)a.k - 8;
-      }
-   }
+   for (int j = 0; j < NCH; j++) ccol[j] = rows16_column((int)blockIdx.y * PANEL + (j * LPR + lc) * 8, a.k, cok[j], vfirst[j]);
+   const unsigned lb = rows16_block(a.nblk);
 
    const int64_t row0 = (int64_t)lb * WAVES;
    const int64_t row = (a.row_order && row0 + wave < a.m) ? (int64_t)a.row_order[row0 + wave] : row0 + wave;
@@ -208,11 +175,8 @@ __global__ __launch_bounds__(WAVES * 64, (rows16_min_blocks<NCH>())) void spmm_r
       const int64_t b = a.pntrb[lr], e = a.pntre[lr];
       const int64_t deg = e - b;
       if (deg <= a.long_row) continue;             // uniform over the block
-      int64_t chunk = (deg + WAVES - 1) / WAVES;
-      chunk = (chunk + 63) & ~(int64_t)63;
-      int64_t cb = b + (int64_t)wave * chunk, ce = cb + chunk;
-      if (cb > e) cb = e;
-      if (ce > e) ce = e;
+      int64_t cb, ce;
+      rows16_chunk(b, e, wave, cb, ce);
       float acc[NCH][8];
 #pragma unroll
       for (int j = 0; j < NCH; j++)
@@ -248,30 +212,12 @@ __global__ __launch_bounds__(WAVES * 64, (rows16_min_blocks<NCH>())) void spmm_r
    }
 }
 
-template <int ELT, int WM, int LPR, int NCH>
-static int launch_rows16_cfg(const Rows16Args &a0, hipStream_t st) {
-   constexpr int WAVES = 4;
-   constexpr int PANEL = LPR * 8 * NCH;
-   Rows16Args a = a0;
-   const int64_t nb = (a.m + WAVES - 1) / WAVES;
-   if (nb > 0x7fffffffLL) return fail(ISPLIB_FAIL, "fusedMM_csr_rows16_hip", "too many row blocks for one launch");
-   a.nblk = (unsigned)nb;
-   const int64_t ny = (a.k + PANEL - 1) / PANEL;
-   if (ny > 65535) return fail(ISPLIB_FAIL, "fusedMM_csr_rows16_hip", "too many column panels for one launch");
-   hipLaunchKernelGGL((spmm_rows16_kernel<ELT, WM, LPR, NCH, WAVES>), dim3((unsigned)nb, (unsigned)ny, 1), dim3(WAVES * 64, 1, 1), 0, st, a);
-   return check_launch("spmm_rows16_kernel");
-}
-
-// slot width by K (a slot is LPR lanes x 8 columns): 8 / 4 / 2 / 1 rows per gather instruction up to 64 / 128 / 256 / 512 columns,
-// two chunks per lane up to 1024, and 1024-column grid.y panels beyond
 template <int ELT, int WM>
-static int launch_rows16(const Rows16Args &a, hipStream_t st) {
-   const int64_t width = (a.k + 7) / 8;     // 16-byte vectors per row (ragged K: the last one is shifted back)
-   if (width <= 8) return launch_rows16_cfg<ELT, WM, 8, 1>(a, st);
-   if (width <= 16) return launch_rows16_cfg<ELT, WM, 16, 1>(a, st);
-   if (width <= 32) return launch_rows16_cfg<ELT, WM, 32, 1>(a, st);
-   if (width <= 64) return launch_rows16_cfg<ELT, WM, 64, 1>(a, st);
-   return launch_rows16_cfg<ELT, WM, 64, 2>(a, st);
+static int launch_rows16(const char *entry, const Rows16Args &a, hipStream_t st) {
+   return rows16_by_width(a.k, [&](auto lpr, auto nch) {
+      constexpr int LPR = decltype(lpr)::value, NCH = decltype(nch)::value;
+      return rows16_launch<LPR, NCH>(entry, "spmm_rows16_kernel", spmm_rows16_kernel<ELT, WM, LPR, NCH, ROWS16_WAVES>, a, st);
+   });
 }
 
 }  // namespace isplib
@@ -281,41 +227,24 @@ using namespace isplib;
 extern "C" int isplib_rows16_auto(int64_t n, int64_t ldy, int ordered, int weighted) { return isplib_rows16_native_pays(n, ldy, ordered, weighted); }
 extern "C" int isplib_rows16_domain(int64_t n, int64_t k, int64_t ldy, int64_t ldz) { return isplib_rows16_serves(n, k, ldy, ldz); }
 
-// the checks and the launch of both entries: `val` is the per-edge weights (wm = W_EDGE, or W_UNIT when null) or the per-column
-// table (wm = W_COL)
+// the checks (rows16_check) and the launch of both entries: `val` is the per-edge weights (wm = W_EDGE, or W_UNIT when null) or the
+// per-column table (wm = W_COL)
 static int rows16_entry(const char *entry, int wm, int32_t imessage, int dtype, int64_t m, int64_t n, int64_t k, int64_t nnz, const float *val,
                         const int64_t *indx, const int64_t *pntrb, const int64_t *pntre, const int32_t *row_order,
                         const void *y, int64_t ldy, void *z, int64_t ldz, void *stream) {
-   clear_error();
-   if (imessage != ISPLIB_MSG_SPMM_SUM && imessage != ISPLIB_MSG_SPMM_MEAN)
-      return fail(ISPLIB_NO_OPT_IMPL, entry, "sum and mean only (max / min of a 16-bit operand: convert it and use fusedMM_csr_hip)");
-   if (dtype != ISPLIB_DTYPE_BF16 && dtype != ISPLIB_DTYPE_F16) return fail(ISPLIB_FAIL, entry, "dtype must be ISPLIB_DTYPE_BF16 or ISPLIB_DTYPE_F16");
-   if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
-   if (m == 0 || k == 0) return ISPLIB_SUCCESS;
-   if (ldy < k || ldz < k) return fail(ISPLIB_FAIL, entry, "leading dimension smaller than k");
-   if (!isplib_rows16_serves(n, k, ldy, ldz))
-      return fail(ISPLIB_FAIL, entry, "outside isplib_rows16_serves(n, k, ldy, ldz): 8 <= k < 2^24, k / ldy / ldz even, n < 2^31, "
-                                      "n*ldy*2 <= 3.5 GiB (convert the operand and use fusedMM_csr_hip)");
-   if (row_order && m >= (1LL << 31)) return fail(ISPLIB_FAIL, entry, "m must be < 2^31 (32-bit row order)");
-   if (!pntrb || !pntre || !z || (nnz > 0 && (!indx || !y))) return fail(ISPLIB_FAIL, entry, "null operand");
-   if (wm == W_COL && nnz > 0 && !val) return fail(ISPLIB_FAIL, entry, "null col_scale (unit weights: fusedMM_csr_rows16_hip with val = NULL)");
-   if ((((uintptr_t)y | (uintptr_t)z) & 3) != 0) return fail(ISPLIB_FAIL, entry, "y and z must be 4-byte aligned");
-
    Rows16Args a;
-   a.m = m; a.k = k;
-   a.val = val; a.indx = indx; a.pntrb = pntrb; a.pntre = pntre;
-   a.y = y; a.ldy = ldy; a.z = reinterpret_cast<unsigned short *>(z); a.ldz = ldz;
+   bool run;
+   const int rc = rows16_check(entry, imessage == ISPLIB_MSG_SPMM_SUM || imessage == ISPLIB_MSG_SPMM_MEAN,
+                               "sum and mean only (max / min of a 16-bit operand: convert it and use fusedMM_csr_hip)", true,
+                               wm == W_COL && nnz > 0 && !val, dtype, m, n, k, nnz, val, indx, pntrb, pntre, row_order, y, ldy, z, ldz, a, &run);
+   if (!run) return rc;
    a.mean = imessage == ISPLIB_MSG_SPMM_MEAN ? 1 : 0;
-   a.long_row = 2048;
-   a.nblk = 0;
-   a.ybytes = (unsigned)((unsigned long long)n * (unsigned long long)ldy * 2ull);
    a.sbytes = wm == W_COL && val ? (unsigned)((unsigned long long)n * 4ull) : 0u;      // inside the domain n*ldy*2 fits 32 bits and ldy >= 8
-   a.row_order = row_order;
    hipStream_t st = (hipStream_t)stream;
    const bool bf = dtype == ISPLIB_DTYPE_BF16;
-   if (wm == W_COL) return bf ? launch_rows16<ELT_BF16, W_COL>(a, st) : launch_rows16<ELT_F16, W_COL>(a, st);
-   if (val) return bf ? launch_rows16<ELT_BF16, W_EDGE>(a, st) : launch_rows16<ELT_F16, W_EDGE>(a, st);
-   return bf ? launch_rows16<ELT_BF16, W_UNIT>(a, st) : launch_rows16<ELT_F16, W_UNIT>(a, st);
+   if (wm == W_COL) return bf ? launch_rows16<ELT_BF16, W_COL>(entry, a, st) : launch_rows16<ELT_F16, W_COL>(entry, a, st);
+   if (val) return bf ? launch_rows16<ELT_BF16, W_EDGE>(entry, a, st) : launch_rows16<ELT_F16, W_EDGE>(entry, a, st);
+   return bf ? launch_rows16<ELT_BF16, W_UNIT>(entry, a, st) : launch_rows16<ELT_F16, W_UNIT>(entry, a, st);
 }
 
 extern "C" int fusedMM_csr_rows16_hip(int32_t imessage, int dtype, int64_t m, int64_t n, int64_t k, int64_t nnz, const float *val,

@@ -1,5 +1,5 @@
 // spmm_rows16_minmax.hip -- max / min of the SpMM on the plain schedule (one CSR row per wavefront) for dense operands of 16-bit
-// elements (bf16, fp16): fusedMM_csr_rows16_minmax_hip.  spmm_rows16.hip's mapping -- a lane's 16-byte gather holds EIGHT columns,
+// elements (bf16, fp16): fusedMM_csr_rows16_minmax_hip.  spmm_rows16.hip's mapping (its pieces: rows16_common.h) -- a lane's 16-byte gather holds EIGHT columns,
 // a slot of LPR lanes covers LPR * 8 columns, WAVES rows per workgroup, blockIdx remapped so that an XCD walks a contiguous range of
 // positions, an optional row order, rows over long_row edges taken by all waves of the workgroup -- with the arithmetic of the fp32
 // kernel's max / min (gather.h, buf_step): the halves are widened in registers, the candidate of an edge is val * y (ONE fp32
@@ -27,6 +27,7 @@
 #include "common.h"
 #include "gather.h"
 #include "half16.h"
+#include "rows16_common.h"
 
 namespace isplib {
 
@@ -103,41 +104,18 @@ __device__ __forceinline__ void mm16_step(const __amdgpu_buffer_rsrc_t rsrc, uns
    }
 }
 
-// wave_edges_buf (gather.h) for this kernel: one wave walks edges [rb, re) of a row that starts at CSR position row_b; edge
-// metadata comes 64 per coalesced load, one 32-bit multiply per edge (col * ldy * 2), handed off per step
+// one wave's edges [rb, re) of a row that starts at CSR position row_b, on rows16_batches (rows16_common.h): mm16_step per step
 template <int ELT, int OP, bool HAS_VAL, bool ARG, int LPR, int NCH, int U>
 __device__ __forceinline__ void mm16_edges(const Rows16MMArgs &a, const __amdgpu_buffer_rsrc_t rsrc, int64_t row_b, int64_t rb, int64_t re,
                                            const int (&ccol)[NCH], const bool (&cok)[NCH], float (&acc)[NCH][8],
                                            int (&bi)[NCH][ARG ? 8 : 1]) {
-   constexpr int G = 64 / LPR;
-   constexpr int UT = U >= 4 ? 2 : 1;   // tail granularity (U is a multiple of UT, so a step never passes edge 63 of its batch)
-   static_assert(U % UT == 0 && 64 % (G * UT) == 0, "a tail step must end inside the batch");
-   const int lane = threadIdx.x & 63;
-   const int g = lane / LPR;
-   const unsigned ldyb = (unsigned)a.ldy * 2u;
-   unsigned cbyte[NCH], poison[NCH];
-#pragma unroll
-   for (int j = 0; j < NCH; j++) {
-      cbyte[j] = (unsigned)ccol[j] * 2u;
-      poison[j] = cok[j] ? 0u : BUF_OOB;
-   }
-   for (int64_t base = rb; base < re; base += 64) {
-      const int64_t p = base + lane;
-      unsigned off_l = BUF_OOB;
-      float v_l = 0.0f;
-      if (p < re) {
-         off_l = (unsigned)a.indx[p] * ldyb;
-         if (HAS_VAL) v_l = a.val[p];
-      }
-      const int64_t left = re - base;
-      const int cnt = left < 64 ? (int)left : 64;
-      const int rel0 = (int)(base - row_b);
-      int s = 0;
-      for (; s + G * U <= cnt; s += G * U)
-         mm16_step<ELT, OP, HAS_VAL, ARG, false, LPR, NCH, U>(rsrc, off_l, v_l, s, cnt, rel0, g, cbyte, poison, acc, bi);
-      for (; s < cnt; s += G * UT)
-         mm16_step<ELT, OP, HAS_VAL, ARG, true, LPR, NCH, UT>(rsrc, off_l, v_l, s, cnt, rel0, g, cbyte, poison, acc, bi);
-   }
+   rows16_batches<LPR, NCH, U>(
+      a, rb, re, ccol, cok, [&](int64_t p) { return HAS_VAL ? a.val[p] : 0.0f; },
+      [&](auto uu, auto tail, unsigned off_l, float v_l, int s, int cnt, int64_t base, int g, const unsigned (&cbyte)[NCH],
+          const unsigned (&poison)[NCH]) {
+         mm16_step<ELT, OP, HAS_VAL, ARG, decltype(tail)::value, LPR, NCH, decltype(uu)::value>(rsrc, off_l, v_l, s, cnt, (int)(base - row_b), g, cbyte,
+                                                                                               poison, acc, bi);
+      });
 }
 
 // the values-only butterfly over the 64 / LPR edge slots: the strictly better value.  Equal values have equal bits unless they are
@@ -258,28 +236,13 @@ __global__ __launch_bounds__(WAVES * 64, (mm16_min_blocks<NCH>())) void spmm_row
    const int lane = threadIdx.x & 63;
    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
    const int g = lane / LPR, lc = lane % LPR;
-   __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.y), 0, (int)a.ybytes, 0x00020000);
+   __amdgpu_buffer_rsrc_t rsrc = rows16_desc(a.y, a.ybytes);
 
-   // XCD-aware remap (spmm_csr_kernel, plain): blocks pb, pb + 8, ... share one XCD, which walks a contiguous range of row blocks
-   const unsigned pb = blockIdx.x, nb = a.nblk;
-   const unsigned xcd = pb & 7u, within = pb >> 3;
-   const unsigned per = nb >> 3, rem = nb & 7u;
-   const unsigned lb = xcd * per + (xcd < rem ? xcd : rem) + within;
-
-   // a lane's eight columns per chunk; ragged K (k % 8 != 0): the last 16-byte vector of a row is shifted back to end at column k,
-   // its first vfirst components duplicate the neighbouring lane's work and are not stored
+   const unsigned lb = rows16_block(a.nblk);
    int ccol[NCH], vfirst[NCH];
    bool cok[NCH];
 #pragma unroll
-   for (int j = 0; j < NCH; j++) {
-      ccol[j] = (int)blockIdx.y * PANEL + (j * LPR + lc) * 8;
-      cok[j] = ccol[j] < a.k;
-      vfirst[j] = 0;
-      if (cok[j] && ccol[j] + 8 > (int)a.k) {
-         vfirst[j] = ccol[j] + 8 - (int)a.k;
-         ccol[j] = (int)a.k - 8;
-      }
-   }
+   for (int j = 0; j < NCH; j++) ccol[j] = rows16_column((int)blockIdx.y * PANEL + (j * LPR + lc) * 8, a.k, cok[j], vfirst[j]);
 
    const int64_t row0 = (int64_t)lb * WAVES;
    const int64_t row = (a.row_order && row0 + wave < a.m) ? (int64_t)a.row_order[row0 + wave] : row0 + wave;
@@ -312,11 +275,8 @@ __global__ __launch_bounds__(WAVES * 64, (mm16_min_blocks<NCH>())) void spmm_row
       const int64_t b = a.pntrb[lr], e = a.pntre[lr];
       const int64_t deg = e - b;
       if (deg <= a.long_row) continue;             // uniform over the block
-      int64_t chunk = (deg + WAVES - 1) / WAVES;
-      chunk = (chunk + 63) & ~(int64_t)63;
-      int64_t cb = b + (int64_t)wave * chunk, ce = cb + chunk;
-      if (cb > e) cb = e;
-      if (ce > e) ce = e;
+      int64_t cb, ce;
+      rows16_chunk(b, e, wave, cb, ce);
       float acc[NCH][8];
       int bi[NCH][NB];
 #pragma unroll
@@ -364,31 +324,13 @@ __global__ __launch_bounds__(WAVES * 64, (mm16_min_blocks<NCH>())) void spmm_row
    }
 }
 
-template <int ELT, int OP, bool HAS_VAL, bool ARG, int LPR, int NCH>
-static int launch_mm16_cfg(const Rows16MMArgs &a0, hipStream_t st) {
-   constexpr int WAVES = 4;
-   constexpr int PANEL = LPR * 8 * NCH;
-   Rows16MMArgs a = a0;
-   const int64_t nb = (a.m + WAVES - 1) / WAVES;
-   if (nb > 0x7fffffffLL) return fail(ISPLIB_FAIL, "fusedMM_csr_rows16_minmax_hip", "too many row blocks for one launch");
-   a.nblk = (unsigned)nb;
-   const int64_t ny = (a.k + PANEL - 1) / PANEL;
-   if (ny > 65535) return fail(ISPLIB_FAIL, "fusedMM_csr_rows16_minmax_hip", "too many column panels for one launch");
-   hipLaunchKernelGGL((spmm_rows16_minmax_kernel<ELT, OP, HAS_VAL, ARG, LPR, NCH, WAVES>), dim3((unsigned)nb, (unsigned)ny, 1),
-                      dim3(WAVES * 64, 1, 1), 0, st, a);
-   return check_launch("spmm_rows16_minmax_kernel");
-}
-
-// slot width by K, as launch_rows16 (spmm_rows16.hip): 8 / 4 / 2 / 1 rows per gather instruction up to 64 / 128 / 256 / 512 columns,
-// two chunks per lane up to 1024, and 1024-column grid.y panels beyond
 template <int ELT, int OP, bool HAS_VAL, bool ARG>
 static int launch_mm16_width(const Rows16MMArgs &a, hipStream_t st) {
-   const int64_t width = (a.k + 7) / 8;     // 16-byte vectors per row (ragged K: the last one is shifted back)
-   if (width <= 8) return launch_mm16_cfg<ELT, OP, HAS_VAL, ARG, 8, 1>(a, st);
-   if (width <= 16) return launch_mm16_cfg<ELT, OP, HAS_VAL, ARG, 16, 1>(a, st);
-   if (width <= 32) return launch_mm16_cfg<ELT, OP, HAS_VAL, ARG, 32, 1>(a, st);
-   if (width <= 64) return launch_mm16_cfg<ELT, OP, HAS_VAL, ARG, 64, 1>(a, st);
-   return launch_mm16_cfg<ELT, OP, HAS_VAL, ARG, 64, 2>(a, st);
+   return rows16_by_width(a.k, [&](auto lpr, auto nch) {
+      constexpr int LPR = decltype(lpr)::value, NCH = decltype(nch)::value;
+      return rows16_launch<LPR, NCH>("fusedMM_csr_rows16_minmax_hip", "spmm_rows16_minmax_kernel",
+                                     spmm_rows16_minmax_kernel<ELT, OP, HAS_VAL, ARG, LPR, NCH, ROWS16_WAVES>, a, st);
+   });
 }
 
 template <int ELT, int OP>
@@ -409,31 +351,15 @@ extern "C" int fusedMM_csr_rows16_minmax_hip(int32_t imessage, int dtype, int64_
                                              const int64_t *indx, const int64_t *pntrb, const int64_t *pntre, const int32_t *row_order,
                                              const void *y, int64_t ldy, void *z, int64_t ldz, int64_t *z_arg, int64_t ldarg,
                                              void *stream) {
-   clear_error();
-   const char *entry = "fusedMM_csr_rows16_minmax_hip";
-   if (imessage != ISPLIB_MSG_SPMM_MAX && imessage != ISPLIB_MSG_SPMM_MIN)
-      return fail(ISPLIB_NO_OPT_IMPL, entry, "max and min only (sum / mean of a 16-bit operand: fusedMM_csr_rows16_hip)");
-   if (dtype != ISPLIB_DTYPE_BF16 && dtype != ISPLIB_DTYPE_F16) return fail(ISPLIB_FAIL, entry, "dtype must be ISPLIB_DTYPE_BF16 or ISPLIB_DTYPE_F16");
-   if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
-   if (m == 0 || k == 0) return ISPLIB_SUCCESS;
-   if (ldy < k || ldz < k || (z_arg && ldarg < k)) return fail(ISPLIB_FAIL, entry, "leading dimension smaller than k");
-   if (!isplib_rows16_serves(n, k, ldy, ldz))
-      return fail(ISPLIB_FAIL, entry, "outside isplib_rows16_serves(n, k, ldy, ldz): 8 <= k < 2^24, k / ldy / ldz even, n < 2^31, "
-                                      "n*ldy*2 <= 3.5 GiB (convert the operand and use fusedMM_csr_hip)");
-   if (row_order && m >= (1LL << 31)) return fail(ISPLIB_FAIL, entry, "m must be < 2^31 (32-bit row order)");
-   if (!pntrb || !pntre || !z || (nnz > 0 && (!indx || !y))) return fail(ISPLIB_FAIL, entry, "null operand");
-   if ((((uintptr_t)y | (uintptr_t)z) & 3) != 0) return fail(ISPLIB_FAIL, entry, "y and z must be 4-byte aligned");
-
    Rows16MMArgs a;
-   a.m = m; a.k = k; a.nnz = nnz;
-   a.val = val; a.indx = indx; a.pntrb = pntrb; a.pntre = pntre;
-   a.y = y; a.ldy = ldy; a.z = reinterpret_cast<unsigned short *>(z); a.ldz = ldz;
+   bool run;
+   const int rc = rows16_check("fusedMM_csr_rows16_minmax_hip", imessage == ISPLIB_MSG_SPMM_MAX || imessage == ISPLIB_MSG_SPMM_MIN,
+                               "max and min only (sum / mean of a 16-bit operand: fusedMM_csr_rows16_hip)", !z_arg || ldarg >= k, false, dtype, m,
+                               n, k, nnz, val, indx, pntrb, pntre, row_order, y, ldy, z, ldz, a, &run);
+   if (!run) return rc;
+   a.nnz = nnz;
    a.z_arg = z_arg; a.ldarg = ldarg;
    a.empty_init = empty_row_init();
-   a.long_row = 2048;
-   a.nblk = 0;
-   a.ybytes = (unsigned)((unsigned long long)n * (unsigned long long)ldy * 2ull);
-   a.row_order = row_order;
    hipStream_t st = (hipStream_t)stream;
    const bool mx = imessage == ISPLIB_MSG_SPMM_MAX;
    if (dtype == ISPLIB_DTYPE_BF16) return mx ? launch_mm16<ELT_BF16, OP_MAX>(a, st) : launch_mm16<ELT_BF16, OP_MIN>(a, st);

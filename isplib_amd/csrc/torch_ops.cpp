@@ -298,6 +298,53 @@ static Tensor packed16(const Tensor &t) {
    return (reinterpret_cast<uintptr_t>(c.data_ptr()) & 3) == 0 ? c : c.clone(at::MemoryFormat::Contiguous);
 }
 
+// a row order (int32 [M], position -> row) as the entries read it
+static Tensor row_order_of(const Tensor &order_, int64_t M) {
+   const Tensor order = order_.contiguous();
+   TORCH_CHECK(order.is_cuda() && order.numel() == M, "isplib: the row order must hold one int32 position per row");
+   return order;
+}
+
+// One call of the 16-bit row family (fusedMM_csr_rows16{,_minmax,_colscale}_hip), prepared: the operand as it lies (a row-strided
+// view keeps its pitch) or packed, whichever isplib_rows16_serves accepts, the graph's arrays contiguous, the weights (`per_edge`:
+// one per edge, checked; else a table of the caller's length) and the plan's row order.  served = false: the family does not take
+// this operand, nothing was copied.  The struct keeps the tensors its pointers point into
+struct Rows16Call {
+   bool served = false;
+   Tensor mat, ptr_t, idx_t, weight_t, order_t;
+   int dtype = 0;
+   int64_t ldy = 0;
+   const int64_t *ptr = nullptr, *idx = nullptr;
+   const float *weight = nullptr;      // null = unit weights
+   const int32_t *order = nullptr;     // null = index order
+};
+
+static Rows16Call rows16_call(const Tensor &ptr_, const Tensor &idx_, const Tensor &weight_, bool per_edge, const Tensor &mat_, const Plan &plan) {
+   Rows16Call c;
+   const int64_t M = ptr_.numel() - 1, N = mat_.size(0), K = mat_.size(1);
+   const bool as_is = row_strided(mat_) && (reinterpret_cast<uintptr_t>(mat_.data_ptr()) & 3) == 0 &&
+                      isplib_rows16_serves(N, K, N > 1 ? mat_.stride(0) : K, K);
+   if (!as_is && !isplib_rows16_serves(N, K, K, K)) return c;
+   c.served = true;
+   c.mat = as_is ? mat_ : packed16(mat_);
+   c.dtype = c.mat.scalar_type() == at::kBFloat16 ? ISPLIB_DTYPE_BF16 : ISPLIB_DTYPE_F16;
+   c.ldy = N > 1 ? c.mat.stride(0) : K;
+   c.ptr_t = ptr_.contiguous();
+   c.idx_t = idx_.contiguous();
+   c.ptr = c.ptr_t.data_ptr<int64_t>();
+   c.idx = c.idx_t.data_ptr<int64_t>();
+   if (weight_.defined()) {
+      c.weight_t = weight_.contiguous();
+      TORCH_CHECK(!per_edge || c.weight_t.numel() == idx_.numel(), "isplib: `value` and `col` differ in length");
+      c.weight = c.weight_t.data_ptr<float>();
+   }
+   if (plan[0].numel() > 0) {
+      c.order_t = row_order_of(plan[0], M);
+      c.order = c.order_t.data_ptr<int32_t>();
+   }
+   return c;
+}
+
 // A 16-bit `mat`: the native entry when the reduction is sum / mean, the plan is a stream plan of the sum kernel's geometry and
 // isplib_stream16_serves accepts the operand as it lies (a row-strided view keeps its pitch) or packed; the 16-bit row entry when
 // the plan is a 16-bit row plan (is_rows16_plan) and isplib_rows16_serves accepts the operand the same way -- for sum / mean and, through
@@ -328,69 +375,27 @@ std::tuple<Tensor, Tensor> spmm_fw_half(const Tensor &rowptr_, const Tensor &col
          return std::make_tuple(out, Tensor());
       }
    }
-   if (sum_op && is_rows16_plan(plan) && M > 0 && K > 0 && rowptr_.device() == mat_.device() && col_.device() == mat_.device()) {
+   // a 16-bit row plan: fusedMM_csr_rows16_hip for sum / mean; for max / min fusedMM_csr_rows16_minmax_hip -- values and positions
+   // bit-equal to the conversion route below, without the fp32 copy; want_arg = false is its values-only launch (the second tensor
+   // stays undefined)
+   if (is_rows16_plan(plan) && M > 0 && K > 0 && rowptr_.device() == mat_.device() && col_.device() == mat_.device()) {
       c10::DeviceGuard guard(mat_.device());
-      const bool as_is = row_strided(mat_) && (reinterpret_cast<uintptr_t>(mat_.data_ptr()) & 3) == 0 &&
-                         isplib_rows16_serves(N, K, N > 1 ? mat_.stride(0) : K, K);
-      if (as_is || isplib_rows16_serves(N, K, K, K)) {
-         const Tensor mat = as_is ? mat_ : packed16(mat_);
-         const int64_t ldy = N > 1 ? mat.stride(0) : K;
-         const Tensor rowptr = rowptr_.contiguous(), col = col_.contiguous();
-         Tensor value;
-         if (value_.has_value() && value_->defined()) {
-            value = value_->contiguous();
-            TORCH_CHECK(value.numel() == nnz, "isplib: `value` and `col` differ in length");
-         }
-         const int32_t *order = nullptr;
-         Tensor order_t;
-         if (plan[0].numel() > 0) {
-            order_t = plan[0].contiguous();
-            TORCH_CHECK(order_t.is_cuda() && order_t.numel() == M, "isplib: the row order must hold one int32 position per row");
-            order = order_t.data_ptr<int32_t>();
-         }
-         Tensor out = at::empty({M, K}, mat.options());
-         const int64_t *rp = rowptr.data_ptr<int64_t>();
-         const int st = fusedMM_csr_rows16_hip(reduction == R_MEAN ? ISPLIB_MSG_SPMM_MEAN : ISPLIB_MSG_SPMM_SUM,
-                                               mat.scalar_type() == at::kBFloat16 ? ISPLIB_DTYPE_BF16 : ISPLIB_DTYPE_F16, M, N, K, nnz,
-                                               value.defined() ? value.data_ptr<float>() : nullptr, col.data_ptr<int64_t>(), rp, rp + 1, order,
-                                               mat.data_ptr(), ldy, out.data_ptr(), K, current_stream(mat));
-         check_status(st, "fusedMM_csr_rows16_hip");
-         return std::make_tuple(out, Tensor());
-      }
-   }
-   // max / min on a 16-bit row plan: fusedMM_csr_rows16_minmax_hip -- values and positions bit-equal to the conversion route below,
-   // without the fp32 copy; want_arg = false is its values-only launch (the second tensor stays undefined)
-   if ((reduction == R_MAX || reduction == R_MIN) && is_rows16_plan(plan) && M > 0 && K > 0 && rowptr_.device() == mat_.device() &&
-       col_.device() == mat_.device()) {
-      c10::DeviceGuard guard(mat_.device());
-      const bool as_is = row_strided(mat_) && (reinterpret_cast<uintptr_t>(mat_.data_ptr()) & 3) == 0 &&
-                         isplib_rows16_serves(N, K, N > 1 ? mat_.stride(0) : K, K);
-      if (as_is || isplib_rows16_serves(N, K, K, K)) {
-         const Tensor mat = as_is ? mat_ : packed16(mat_);
-         const int64_t ldy = N > 1 ? mat.stride(0) : K;
-         const Tensor rowptr = rowptr_.contiguous(), col = col_.contiguous();
-         Tensor value;
-         if (value_.has_value() && value_->defined()) {
-            value = value_->contiguous();
-            TORCH_CHECK(value.numel() == nnz, "isplib: `value` and `col` differ in length");
-         }
-         const int32_t *order = nullptr;
-         Tensor order_t;
-         if (plan[0].numel() > 0) {
-            order_t = plan[0].contiguous();
-            TORCH_CHECK(order_t.is_cuda() && order_t.numel() == M, "isplib: the row order must hold one int32 position per row");
-            order = order_t.data_ptr<int32_t>();
-         }
-         Tensor out = at::empty({M, K}, mat.options());
+      const Tensor value = value_.has_value() && value_->defined() ? *value_ : Tensor();
+      const Rows16Call c = rows16_call(rowptr_, col_, value, true, mat_, plan);
+      if (c.served) {
+         Tensor out = at::empty({M, K}, c.mat.options());
          Tensor arg;
-         if (want_arg) arg = at::empty({M, K}, rowptr.options());
-         const int64_t *rp = rowptr.data_ptr<int64_t>();
-         const int st = fusedMM_csr_rows16_minmax_hip(reduction == R_MAX ? ISPLIB_MSG_SPMM_MAX : ISPLIB_MSG_SPMM_MIN,
-                                                      mat.scalar_type() == at::kBFloat16 ? ISPLIB_DTYPE_BF16 : ISPLIB_DTYPE_F16, M, N, K, nnz,
-                                                      value.defined() ? value.data_ptr<float>() : nullptr, col.data_ptr<int64_t>(), rp, rp + 1,
-                                                      order, mat.data_ptr(), ldy, out.data_ptr(), K,
-                                                      arg.defined() ? arg.data_ptr<int64_t>() : nullptr, K, current_stream(mat));
-         check_status(st, "fusedMM_csr_rows16_minmax_hip");
+         int st;
+         if (sum_op) {
+            st = fusedMM_csr_rows16_hip(reduction == R_MEAN ? ISPLIB_MSG_SPMM_MEAN : ISPLIB_MSG_SPMM_SUM, c.dtype, M, N, K, nnz, c.weight, c.idx, c.ptr,
+                                        c.ptr + 1, c.order, c.mat.data_ptr(), c.ldy, out.data_ptr(), K, current_stream(c.mat));
+         } else {
+            if (want_arg) arg = at::empty({M, K}, rowptr_.options());
+            st = fusedMM_csr_rows16_minmax_hip(reduction == R_MAX ? ISPLIB_MSG_SPMM_MAX : ISPLIB_MSG_SPMM_MIN, c.dtype, M, N, K, nnz, c.weight, c.idx,
+                                               c.ptr, c.ptr + 1, c.order, c.mat.data_ptr(), c.ldy, out.data_ptr(), K,
+                                               arg.defined() ? arg.data_ptr<int64_t>() : nullptr, K, current_stream(c.mat));
+         }
+         check_status(st, sum_op ? "fusedMM_csr_rows16_hip" : "fusedMM_csr_rows16_minmax_hip");
          return std::make_tuple(out, arg);
       }
    }
@@ -411,24 +416,11 @@ static Tensor mean_bw_colscale(const Tensor &colptr_, const Tensor &row_t_, cons
        row_t_.scalar_type() != at::kLong)
       return Tensor();
    c10::DeviceGuard guard(grad_out.device());
-   const bool as_is = row_strided(grad_out) && (reinterpret_cast<uintptr_t>(grad_out.data_ptr()) & 3) == 0 &&
-                      isplib_rows16_serves(N, K, N > 1 ? grad_out.stride(0) : K, K);
-   if (!as_is && !isplib_rows16_serves(N, K, K, K)) return Tensor();
-   const Tensor gy = as_is ? grad_out : packed16(grad_out);
-   const int64_t ldy = N > 1 ? gy.stride(0) : K;
-   const Tensor colptr = colptr_.contiguous(), row_t = row_t_.contiguous(), scale = scale_.contiguous();
-   const int32_t *order = nullptr;
-   Tensor order_t;
-   if (row_plan[0].numel() > 0) {
-      order_t = row_plan[0].contiguous();
-      TORCH_CHECK(order_t.is_cuda() && order_t.numel() == M, "isplib: the row order must hold one int32 position per row");
-      order = order_t.data_ptr<int32_t>();
-   }
-   Tensor out = at::empty({M, K}, gy.options());
-   const int64_t *cp = colptr.data_ptr<int64_t>();
-   const int st = fusedMM_csr_rows16_colscale_hip(ISPLIB_MSG_SPMM_SUM, gy.scalar_type() == at::kBFloat16 ? ISPLIB_DTYPE_BF16 : ISPLIB_DTYPE_F16,
-                                                  M, N, K, nnz, scale.data_ptr<float>(), row_t.data_ptr<int64_t>(), cp, cp + 1, order,
-                                                  gy.data_ptr(), ldy, out.data_ptr(), K, current_stream(gy));
+   const Rows16Call c = rows16_call(colptr_, row_t_, scale_, false, grad_out, row_plan);
+   if (!c.served) return Tensor();
+   Tensor out = at::empty({M, K}, c.mat.options());
+   const int st = fusedMM_csr_rows16_colscale_hip(ISPLIB_MSG_SPMM_SUM, c.dtype, M, N, K, nnz, c.weight, c.idx, c.ptr, c.ptr + 1, c.order,
+                                                  c.mat.data_ptr(), c.ldy, out.data_ptr(), K, current_stream(c.mat));
    check_status(st, "fusedMM_csr_rows16_colscale_hip");
    return out;
 }
@@ -528,8 +520,7 @@ std::tuple<Tensor, Tensor> spmm_fw(const Tensor &rowptr_, const Tensor &col_, co
    if (plan.size() == 1 && plan[0].defined() && plan[0].scalar_type() == at::kInt && M > 0 && K > 0) {
       // a row order (int32 [M], position -> row): the plain kernel with the rows taken in that order (operands larger
       // than the Infinity Cache on graphs with community structure; fusedMM_csr_ordered_hip) -- the same bits as below
-      const Tensor order = plan[0].contiguous();
-      TORCH_CHECK(order.is_cuda() && order.numel() == M, "isplib: the row order must hold one int32 position per row");
+      const Tensor order = row_order_of(plan[0], M);
       const int st = fusedMM_csr_ordered_hip(msg, M, N, K, nnz, value.defined() ? value.data_ptr<float>() : nullptr,
                                              col.data_ptr<int64_t>(), rp, rp + 1, order.data_ptr<int32_t>(), mat.data_ptr<float>(), K,
                                              out.data_ptr<float>(), K, arg.defined() ? arg.data_ptr<int64_t>() : nullptr,

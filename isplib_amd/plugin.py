@@ -282,6 +282,30 @@ def half_route(dtype, reduce: str, k: int, pitch: int, mode: Optional[str] = Non
     return "native" if cabi.stream16_native_pays(int(streams), bool(weighted)) else "convert"
 
 
+def _rows16_gate(dtype, mode: Optional[str], opt_in: Optional[str], n: int, k: int, pitch: int, pays) -> str:
+    """The gate the three routes of the 16-bit row family share: 16-bit features, the mode, and the entry's domain
+    (cabi.rows16_serves) at the operand's own row pitch or, failing that, packed.  `mode` None is read from the environment:
+    ISPLIB_HALF (default "auto") when `opt_in` is None, else the variable `opt_in` names (default "convert"; ISPLIB_HALF=convert wins
+    over it, and only "native" / "auto" leave the conversion route).  `pays(cabi, ld)` is the route's own measured class table,
+    asked under "auto" at the pitch the entry would be given."""
+    if dtype not in HALF_DTYPES:
+        return "convert"
+    from . import cabi
+    if mode is None:
+        mode = os.environ.get("ISPLIB_HALF", "auto")
+        if opt_in is not None and mode != "convert":
+            mode = os.environ.get(opt_in, "convert")
+    if mode == "convert" or (opt_in is not None and mode not in ("native", "auto")):
+        return "convert"
+    if cabi.rows16_serves(n, k, pitch, k):
+        ld = pitch
+    elif cabi.rows16_serves(n, k, k, k):
+        ld = k
+    else:
+        return "convert"
+    return "rows16" if mode == "native" or pays(cabi, ld) else "convert"
+
+
 def rows16_route(dtype, reduce: str, k: int, pitch: int, mode: Optional[str] = None, n: int = 1, ordered: bool = False,
                  weighted: bool = False) -> str:
     """Which way a matmul with 16-bit features goes when half_route said "convert", the call has no stream plan and the plain
@@ -293,22 +317,9 @@ def rows16_route(dtype, reduce: str, k: int, pitch: int, mode: Optional[str] = N
         kernel wherever the above holds, "auto" only in the classes -- (operand beyond 256 MiB or not) x `ordered` (the rows come
         in a community order) x `weighted` -- where every native run measured faster than every run of the conversion route
         (cabi.rows16_native_pays, profiles/rows16_ab.txt).  Nothing raises."""
-    if dtype not in HALF_DTYPES or reduce not in ("sum", "add", "mean"):
+    if reduce not in ("sum", "add", "mean"):
         return "convert"
-    from . import cabi
-    if mode is None:
-        mode = os.environ.get("ISPLIB_HALF", "auto")
-    if mode == "convert":
-        return "convert"
-    if cabi.rows16_serves(n, k, pitch, k):
-        ld = pitch
-    elif cabi.rows16_serves(n, k, k, k):
-        ld = k
-    else:
-        return "convert"
-    if mode == "native":
-        return "rows16"
-    return "rows16" if cabi.rows16_native_pays(n, ld, bool(ordered), bool(weighted)) else "convert"
+    return _rows16_gate(dtype, mode, None, n, k, pitch, lambda cabi, ld: cabi.rows16_native_pays(n, ld, bool(ordered), bool(weighted)))
 
 
 def rows16_minmax_route(dtype, reduce: str, k: int, pitch: int, mode: Optional[str] = None, n: int = 1, ordered: bool = False,
@@ -323,22 +334,10 @@ def rows16_minmax_route(dtype, reduce: str, k: int, pitch: int, mode: Optional[s
         "convert" always converts, "native" takes the kernel wherever the above holds, "auto" only in the classes -- those of
         rows16_route x `want_arg` (positions wanted) -- where every native run measured faster than every run of the conversion
         route (cabi.rows16_minmax_native_pays, profiles/rows16_minmax_ab.txt).  Nothing raises."""
-    if dtype not in HALF_DTYPES or reduce not in ("max", "min"):
+    if reduce not in ("max", "min"):
         return "convert"
-    from . import cabi
-    if mode is None:
-        mode = "convert" if os.environ.get("ISPLIB_HALF", "auto") == "convert" else os.environ.get("ISPLIB_HALF_MINMAX", "convert")
-    if mode not in ("native", "auto"):
-        return "convert"
-    if cabi.rows16_serves(n, k, pitch, k):
-        ld = pitch
-    elif cabi.rows16_serves(n, k, k, k):
-        ld = k
-    else:
-        return "convert"
-    if mode == "native":
-        return "rows16"
-    return "rows16" if cabi.rows16_minmax_native_pays(n, ld, bool(ordered), bool(weighted), bool(want_arg)) else "convert"
+    return _rows16_gate(dtype, mode, "ISPLIB_HALF_MINMAX", n, k, pitch,
+                        lambda cabi, ld: cabi.rows16_minmax_native_pays(n, ld, bool(ordered), bool(weighted), bool(want_arg)))
 
 
 def rows16_mean_bw_route(dtype, k: int, m_rows: int, ordered: bool = False, mode: Optional[str] = None) -> str:
@@ -351,18 +350,7 @@ def rows16_mean_bw_route(dtype, k: int, m_rows: int, ordered: bool = False, mode
         "convert" always converts, "native" takes the kernel wherever the above holds, "auto" only in the classes -- (dY beyond
         256 MiB or not) x `ordered` (the rows of A^T come in a community order) -- where every native run measured faster than
         every run of the conversion route (cabi.rows16_colscale_native_pays, profiles/rows16_colscale_ab.txt).  Nothing raises."""
-    if dtype not in HALF_DTYPES:
-        return "convert"
-    from . import cabi
-    if mode is None:
-        mode = "convert" if os.environ.get("ISPLIB_HALF", "auto") == "convert" else os.environ.get("ISPLIB_HALF_MEAN_BW", "convert")
-    if mode not in ("native", "auto"):
-        return "convert"
-    if not cabi.rows16_serves(m_rows, k, k, k):
-        return "convert"
-    if mode == "native":
-        return "rows16"
-    return "rows16" if cabi.rows16_colscale_native_pays(m_rows, k, bool(ordered)) else "convert"
+    return _rows16_gate(dtype, mode, "ISPLIB_HALF_MEAN_BW", m_rows, k, k, lambda cabi, ld: cabi.rows16_colscale_native_pays(m_rows, k, bool(ordered)))
 
 
 _ROWS16_MARK = torch.tensor([16], dtype=torch.int32)      # second tensor of a 16-bit row plan (torch_ops.cpp: is_rows16_plan)
@@ -372,6 +360,16 @@ def _rows16_plan(s: SparseStorage, transposed: bool, k: int, device) -> list:
     """[row order or an empty int32 tensor (index order), marker]: the plan form that sends a 16-bit operand to the row kernel."""
     order = s.row_order(transposed, k, itemsize=2)
     return [order[0] if order else torch.empty(0, dtype=torch.int32, device=device), _ROWS16_MARK]
+
+
+def _rows16_plan_where(goes, s: SparseStorage, transposed: bool, k: int, device) -> Optional[list]:
+    """The 16-bit row plan of a call whose route, goes(ordered) -> bool, says "rows16", else None.  `ordered` is what the kernel
+    will be given, so the community order (judged at 2 bytes per element) is looked for only when some answer to it can send the
+    call there, and the route is then asked about the order that was found."""
+    if not (goes(False) or goes(True)):
+        return None
+    plan = _rows16_plan(s, transposed, k, device)
+    return plan if goes(plan[0].numel() > 0) else None
 
 
 def spmm_autotuned(src, other: torch.Tensor, reduce: str = "sum") -> torch.Tensor:
@@ -409,26 +407,21 @@ def spmm_autotuned(src, other: torch.Tensor, reduce: str = "sum") -> torch.Tenso
         route = half_route(mat.dtype, reduce, k, pitch, None, None if plan is None else int(geom[0]), s._value is not None,
                            mat.size(0), col.numel())
         if route == "convert" and plan is None and mat.dim() == 2 and reduce in ("sum", "add", "mean") and not s.plan(choose_slices(s, mat.size(0), k)):
-            # no stream plan, and the plain kernel would serve the fp32 call: the 16-bit row kernel where rows16_route says so.
-            # `ordered` is what the kernel will be given, so the community order (judged at 2 bytes per element) is looked for
-            # only when some answer to it can send the call there
+            # no stream plan, and the plain kernel would serve the fp32 call: the 16-bit row kernel where rows16_route says so
             weighted = s._value is not None
-            goes = lambda ordered: rows16_route(mat.dtype, reduce, k, pitch, None, mat.size(0), ordered, weighted) == "rows16"  # noqa: E731
-            if goes(False) or goes(True):
-                cand = _rows16_plan(s, False, k, mat.device)
-                if goes(cand[0].numel() > 0):
-                    plan, rows16 = cand, True
+            plan = _rows16_plan_where(lambda ordered: rows16_route(mat.dtype, reduce, k, pitch, None, mat.size(0), ordered, weighted) == "rows16",
+                                      s, False, k, mat.device)
+            rows16 = plan is not None
         if route == "convert" and plan is None and mat.dim() == 2 and reduce in ("max", "min") and \
                 os.environ.get("ISPLIB_HALF_MINMAX", "convert") != "convert" and not s.plan(choose_slices(s, mat.size(0), k, True)):
             # max / min, opt-in (ISPLIB_HALF_MINMAX): the same question put to rows16_minmax_route; positions are wanted exactly when
             # the call below goes to the *_planned operators
             weighted = s._value is not None
             want_arg = needs_grad or (value is not None and torch.is_grad_enabled() and value.requires_grad)
-            goes = lambda ordered: rows16_minmax_route(mat.dtype, reduce, k, pitch, None, mat.size(0), ordered, weighted, want_arg) == "rows16"  # noqa: E731
-            if goes(False) or goes(True):
-                cand = _rows16_plan(s, False, k, mat.device)
-                if goes(cand[0].numel() > 0):
-                    plan, rows16 = cand, True
+            plan = _rows16_plan_where(
+                lambda ordered: rows16_minmax_route(mat.dtype, reduce, k, pitch, None, mat.size(0), ordered, weighted, want_arg) == "rows16",
+                s, False, k, mat.device)
+            rows16 = plan is not None
         if rows16:
             ran = ("rows16mm" if reduce in ("max", "min") else "rows16",) + (("ordered",) if plan[0].numel() > 0 else ())
         elif route == "convert":
@@ -467,12 +460,15 @@ def spmm_autotuned(src, other: torch.Tensor, reduce: str = "sum") -> torch.Tenso
                     # unit-weight mean backward forms dY / deg in fp32 first: an fp32 operand, its row order judged at 4 bytes --
                     # unless rows16_mean_bw_route (opt-in: ISPLIB_HALF_MEAN_BW) sends it to the column-scaled 16-bit kernel, which
                     # takes dY as it is and 1 / deg as a table
-                    if half and not unit_mean and _rows16_backward(s, mat, reduce, k, m_rows, val_t is not None):
-                        plan_t = _rows16_plan(s, True, k, mat.device)
-                    elif half and unit_mean and _rows16_mean_backward(s, mat, k, m_rows):
-                        plan_t = _rows16_plan(s, True, k, mat.device) + [s.inv_rowcount()]
-                    else:
-                        plan_t = s.row_order(True, k)
+                    plan16 = None
+                    if half and not unit_mean:         # (dY: [m_rows, k], packed, of mat's dtype)
+                        weighted_t = val_t is not None
+                        plan16 = _rows16_plan_where(lambda ordered: rows16_route(mat.dtype, reduce, k, k, None, m_rows, ordered, weighted_t) == "rows16",
+                                                    s, True, k, mat.device)
+                    elif half:
+                        plan16 = _rows16_plan_where(lambda ordered: rows16_mean_bw_route(mat.dtype, k, m_rows, ordered) == "rows16", s, True, k, mat.device)
+                        plan16 = plan16 + [s.inv_rowcount()] if plan16 is not None else None
+                    plan_t = plan16 if plan16 is not None else s.row_order(True, k)
         if reduce == "mean":
             out = ops.fusedmm_spmm_mean_planned(rowptr, col, value, colptr, mat, row_t, val_t, plan, plan_t)
         else:
@@ -486,21 +482,6 @@ def spmm_autotuned(src, other: torch.Tensor, reduce: str = "sum") -> torch.Tenso
     else:
         out = ops.fusedmm_spmm_min_planned(rowptr, col, value, mat, plan)[0]   # :145
     return out.squeeze(-1) if squeeze else out
-
-
-def _rows16_backward(s: SparseStorage, mat: torch.Tensor, reduce: str, k: int, m_rows: int, weighted: bool) -> bool:
-    """Whether A^T dY of a 16-bit call (dY: [m_rows, k], packed, of mat's dtype) takes the 16-bit row kernel: rows16_route with the
-    transposed side's row order.  (Not asked for the unit-weight mean backward, whose operand dY / deg is fp32.)"""
-    goes = lambda ordered: rows16_route(mat.dtype, reduce, k, k, None, m_rows, ordered, weighted) == "rows16"  # noqa: E731
-    return (goes(False) or goes(True)) and goes(bool(s.row_order(True, k, itemsize=2)))
-
-
-def _rows16_mean_backward(s: SparseStorage, mat: torch.Tensor, k: int, m_rows: int) -> bool:
-    """Whether the backward of a 16-bit `mean` on an unweighted graph takes the column-scaled 16-bit row kernel:
-    rows16_mean_bw_route with the transposed side's row order, judged at 2 bytes per element as in _rows16_backward (looked for
-    only when some answer to it can send the call there)."""
-    goes = lambda ordered: rows16_mean_bw_route(mat.dtype, k, m_rows, ordered) == "rows16"  # noqa: E731
-    return (goes(False) or goes(True)) and goes(bool(s.row_order(True, k, itemsize=2)))
 
 
 matmul = spmm_autotuned
