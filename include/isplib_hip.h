@@ -600,6 +600,48 @@ static inline int isplib_rows16_minmax_native_pays(int64_t n, int64_t ldy, int o
 }
 int    isplib_rows16_minmax_auto(int64_t n, int64_t ldy, int ordered, int weighted, int want_arg);   /* the same rule as a symbol */
 /*
+ * The value gradient of SpMM-sum / SpMM-mean (isplib_sddmm_csr_hip) for dense operands of 16-bit elements, on the schedule of
+ * fusedMM_csr_rows16_hip: for the edges j of row i
+ *   dval[j] = <y[indx[j], :], g[i, :]> * (mean ? 1 / max(deg_i, 1) : 1).
+ * y: n x ldy and g: m x ldg elements of `dtype`, neither widened in memory (a gathered row of y is half the bytes of the fp32
+ * kernel's); dval: nnz fp32 values in CSR order -- the weights of a 16-bit call are fp32, so nothing is rounded to 16 bits.
+ * Widening is exact, products and sums are fp32, the mean multiplies the finished dot by the fp32 1.0f / deg as isplib_sddmm_csr_hip
+ * does; nothing is flushed (bf16 operands whose products are fp32 subnormals keep them).  A lane sums at most 16 products and the
+ * slot reduction adds at most 6 levels: every result lies within 1e-5 * <|y|, |g|> of the exact one (about 1.4e-6 in the worst
+ * case), and where the fp32 sums are exact in any order (small integers) it is exact.  `row_order` (device, m int32, position ->
+ * row; NULL = index order) is fusedMM_csr_ordered_hip's.  No atomics: two launches give equal bits and any row order gives the
+ * bits of index order.  Bit equality with "widen both operands, run isplib_sddmm_csr_hip" is NOT promised on real-valued data: the
+ * fp32 kernel cuts a row's columns into other slots.
+ * Domain: isplib_sddmm_rows16_serves(n, k, ldy, ldg) -- isplib_rows16_serves with ldg in the output pitch's place, and
+ * k <= ISPLIB_SDDMM_TASKS_K_MAX: a dot product cannot be cut into column panels, so g[row, :] in two chunks per lane is the widest
+ * form.  With a row order m < 2^31.  Refused before any launch with ISPLIB_FAIL, dval untouched: another dtype, a negative
+ * dimension, ldy < k or ldg < k, a shape outside the domain, a null operand, a y or g base that is not 4-byte aligned.  m == 0,
+ * k == 0 or nnz == 0 succeeds without a launch.
+ * isplib_sddmm_rows16_native_pays is the measured rule of the layers above (profiles/sddmm_rows16_ab.txt), over the
+ * classes (y beyond 256 MiB at 2 bytes per element or not) x (rows in a community order or not): nonzero only where EVERY run of
+ * this entry was faster than EVERY run of the conversion route (widen y and g, isplib_sddmm_csr_hip) on every measured shape of the
+ * class.
+ */
+int    isplib_sddmm_csr_rows16_hip(int dtype /* ISPLIB_DTYPE_BF16 | _F16 */, int64_t m, int64_t n, int64_t k, int64_t nnz,
+                                   const int64_t *indx, const int64_t *pntrb, const int64_t *pntre,
+                                   const int32_t *row_order /* optional */, const void *y, int64_t ldy,
+                                   const void *g, int64_t ldg, int mean, float *dval, void *stream);
+static inline int isplib_sddmm_rows16_serves(int64_t n, int64_t k, int64_t ldy, int64_t ldg) {
+   return k <= ISPLIB_SDDMM_TASKS_K_MAX && isplib_rows16_serves(n, k, ldy, ldg);
+}
+static inline int isplib_sddmm_rows16_native_pays(int64_t n, int64_t ldy, int ordered) {
+   /* measured (profiles/sddmm_rows16_ab.txt: rows16_ab's shapes, bf16, the backward of sum and of mean with only the weights requiring
+    * grad): beyond 256 MiB every run of both classes pays -- in index order 0.36-0.43 of the conversion route's time (0.39-0.46 of the
+    * fp32 kernel alone on operands widened beforehand), in a community order 0.21-0.25.  Inside 256 MiB in index order a quarter of
+    * the products shape at K = 128 (0.39-0.41), a fiftieth at K = 16 / 64 (0.51 / 0.29) and a Cora-shaped graph at K = 64 (0.69) win
+    * every run, but on the Cora shape at K = 16 one native run (0.038 ms, the first) lies above the fastest conversion run (0.028 ms):
+    * the class does NOT pay and stays on convert; inside 256 MiB in a community order was not measured. */
+   const int beyond = n > 0 && ldy > 0 && (double)n * (double)ldy * 2.0 > 256.0 * 1048576.0;
+   (void)ordered;
+   return beyond ? 1 : 0;
+}
+int    isplib_sddmm_rows16_auto(int64_t n, int64_t ldy, int ordered);             /* the same rule as a symbol */
+/*
  * Staged column panels (sum / mean on 64-column slots only).  What a gather of a 128-byte line costs depends on the line's
  * ADDRESS: profiles/line_classes.txt (scripts/ubench/line_classes.hip) is the table, DESIGN.md section 5 reads it.  Before the
  * dispatches of a panel whose lines sit in a slow class, fusedMM_csr_stream_hip may copy the panel's 64 columns into the tail

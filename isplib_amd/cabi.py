@@ -93,6 +93,21 @@ def rows16_colscale_native_pays(n: int, ldy: int, ordered: bool) -> bool:
     return bool(beyond or not ordered)
 
 
+def sddmm_rows16_serves(n: int, k: int, ldy: int, ldg: int) -> bool:
+    """isplib_sddmm_rows16_serves of the header: the 16-bit SDDMM row entry (isplib_sddmm_csr_rows16_hip) serves y [n, k] at leading
+    dimension ldy and g at leading dimension ldg -- the 16-bit row entry's domain, and k <= 1024 (g[row, :] sits in registers)."""
+    return k <= SDDMM_TASKS_K_MAX and rows16_serves(n, k, ldy, ldg)
+
+
+def sddmm_rows16_native_pays(n: int, ldy: int, ordered: bool) -> bool:
+    """isplib_sddmm_rows16_native_pays of the header: the classes of calls -- (y beyond 256 MiB at 2 bytes per element or not) x
+    (rows in a community order or not) -- in which every run of the 16-bit SDDMM row kernel measured faster than every run of the
+    conversion route (profiles/sddmm_rows16_ab.txt: both classes beyond 256 MiB do; inside 256 MiB the index-order class loses one
+    run on one measured shape and the community-order class was not measured, so both stay on convert);
+    tests/test_sddmm_rows16_host.py compares the two."""
+    return bool(n > 0 and ldy > 0 and n * ldy * 2 > (256 << 20))
+
+
 def owner_exchange_serves(m: int, k: int, world: int, cuts) -> bool:
     """isplib_owner_exchange_serves of the header: m x k winners split for `world` owners at the row boundaries `cuts`."""
     if not 1 <= world <= OWNER_WORLD_MAX or m < 0 or k < 0 or m * k >= MINMAX_BW_PAIRS_END:
@@ -140,6 +155,7 @@ EXPORTS = (
     "fusedMM_csr_rows16_hip", "isplib_rows16_auto", "isplib_rows16_domain",
     "fusedMM_csr_rows16_minmax_hip", "isplib_rows16_minmax_auto",
     "fusedMM_csr_rows16_colscale_hip", "isplib_rows16_colscale_auto",
+    "isplib_sddmm_csr_rows16_hip", "isplib_sddmm_rows16_auto",
 )
 
 # include/isplib_hip_experimental.h (libisplib_hip_exp.so): forms measured slower than the defaults; tests and experiment scripts only
@@ -362,6 +378,10 @@ def lib() -> ctypes.CDLL:
         L.fusedMM_csr_rows16_colscale_hip.argtypes = [_i32, ctypes.c_int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]
         L.isplib_rows16_colscale_auto.restype = ctypes.c_int
         L.isplib_rows16_colscale_auto.argtypes = [_i64, _i64, ctypes.c_int]
+        L.isplib_sddmm_csr_rows16_hip.restype = ctypes.c_int
+        L.isplib_sddmm_csr_rows16_hip.argtypes = [ctypes.c_int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, ctypes.c_int, _vp, _vp]
+        L.isplib_sddmm_rows16_auto.restype = ctypes.c_int
+        L.isplib_sddmm_rows16_auto.argtypes = [_i64, _i64, ctypes.c_int]
         _sigs_set = True
     return L
 
@@ -1307,6 +1327,77 @@ def spmm_rows16_colscale(rowptr, col, scale, y, reduce: str = "sum", order=None,
         raise ValueError(f"isplib_amd: spmm_rows16_colscale serves sum / mean, got '{reduce}'")
     rowptr, col, scale, order, out, _ = _rows16_operands(rowptr, col, scale, True, y, order, out)
     fusedMM_csr_rows16_colscale_hip(MESSAGE[reduce], rowptr, col, scale, order, y, out)
+    return out
+
+
+def isplib_sddmm_csr_rows16_hip(rowptr, col, order, y, g, dval, mean: bool = False, check: bool = True, dtype=None, k=None, ldy=None,
+                                ldg=None) -> int:
+    """Raw boundary call of the 16-bit SDDMM row entry, for operands the entry may refuse: it hands over what it is given (`dtype`,
+    `k`, `ldy`, `ldg`: override what the tensors say; `y`, `g`, `dval` may be None -- refusal tests; the entry refuses before it
+    reads anything).  Callers that want their operands checked use sddmm_rows16."""
+    some = y if y is not None else g
+    m, n = rowptr.numel() - 1, some.size(0) if y is None else y.size(0)
+    k = some.size(1) if k is None else int(k)
+    code = HALF_DTYPES.get(some.dtype, 0) if dtype is None else int(dtype)
+    rp = rowptr.data_ptr()
+    if ldy is None:
+        ldy = k if y is None else (y.stride(0) if n > 1 else max(k, y.stride(0)))
+    if ldg is None:
+        ldg = k if g is None else (g.stride(0) if m > 1 else max(k, g.stride(0)))
+    with torch.cuda.device(rowptr.device):
+        st = lib().isplib_sddmm_csr_rows16_hip(code, m, n, k, col.numel(), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8), _ptr(order),
+                                               _ptr(y), int(ldy), _ptr(g), int(ldg), 1 if mean else 0, _ptr(dval), _stream(rowptr.device))
+    if check:
+        _check(st, "isplib_sddmm_csr_rows16_hip")
+    return st
+
+
+def sddmm_rows16(rowptr, col, y, g, mean: bool = False, order=None, out=None):
+    """The value gradient of SpMM-sum / SpMM-mean for bf16 / fp16 operands, neither widened in memory: returns `out`, float32
+    [col.numel()] in CSR order (allocated when not given), out[j] = <y[col[j], :], g[i, :]> (`mean`: / max(deg_i, 1)) for the
+    entries j of row i.  `y` [n, k] and `g` [m, k] of one 16-bit dtype, row-strided views keep their pitch; `order`: int32 [m],
+    position -> row, or None.  Every operand is checked BEFORE the call -- a mis-shaped one is an out-of-bounds device read: shapes
+    and dtypes, unit inner strides, rowptr / col int64 on y's device, rowptr ascending from 0 to col.numel(), every column id inside
+    [0, n), the shape inside isplib_sddmm_rows16_serves, 4-byte aligned bases, `order` a permutation's length."""
+    if not isinstance(y, torch.Tensor) or y.dim() != 2:
+        raise ValueError("isplib_amd: `y` must be a 2-D tensor [n, k]")
+    if y.dtype not in HALF_DTYPES:
+        raise TypeError(f"isplib_amd: `y` must be bfloat16 or float16, got {y.dtype} (float32: sddmm)")
+    m = rowptr.numel() - 1
+    n, k = y.size(0), y.size(1)
+    if not isinstance(g, torch.Tensor) or g.dim() != 2 or tuple(g.shape) != (m, k):
+        raise ValueError(f"isplib_amd: `g` must be a 2-D tensor [{m}, {k}] (one row per row of the sparse operand, y's width)")
+    if g.dtype != y.dtype:
+        raise TypeError(f"isplib_amd: `g` must have y's dtype {y.dtype}, got {g.dtype}")
+    if k > 0 and (y.stride(1) != 1 or g.stride(1) != 1):
+        raise ValueError("isplib_amd: `y` and `g` must have unit inner stride")
+    if not y.is_cuda or g.device != y.device:
+        raise ValueError("isplib_amd: `y` and `g` must be GPU tensors on one device -- there is no CPU path")
+    rowptr = _dev(rowptr, "rowptr", torch.int64)
+    col = _dev(col, "col", torch.int64)
+    if m < 0 or rowptr.device != y.device or col.device != y.device:
+        raise ValueError("isplib_amd: rowptr (m + 1 entries), col and y must be on one device")
+    if order is not None:
+        order = _dev(order, "order", torch.int32)
+        if order.numel() != m or order.device != y.device or (m > 0 and (int(order.min()) < 0 or int(order.max()) >= m)):
+            raise ValueError("isplib_amd: `order` must hold one int32 row in [0, m) per position, on y's device")
+    if m > 0 and (int(rowptr[0]) != 0 or int(rowptr[-1]) != col.numel() or bool((rowptr[1:] < rowptr[:-1]).any())):
+        raise ValueError("isplib_amd: rowptr must ascend from 0 to col.numel()")
+    if col.numel() > 0 and (int(col.min()) < 0 or int(col.max()) >= n):
+        raise ValueError(f"isplib_amd: column ids must lie in [0, {n}): `y` must hold a row for every column of the sparse operand")
+    if out is None:
+        out = torch.empty(col.numel(), dtype=torch.float32, device=y.device)
+    elif not isinstance(out, torch.Tensor) or out.device != y.device or out.dtype != torch.float32 or out.dim() != 1 or \
+            out.numel() < col.numel() or not out.is_contiguous():
+        raise ValueError(f"isplib_amd: `out` must be a contiguous float32 tensor of at least {col.numel()} entries on {y.device}")
+    ldy = y.stride(0) if n > 1 else max(k, y.stride(0))
+    ldg = g.stride(0) if m > 1 else max(k, g.stride(0))
+    if m > 0 and k > 0 and col.numel() > 0:
+        if ldy < k or ldg < k or not sddmm_rows16_serves(n, k, ldy, ldg):
+            raise ValueError(f"isplib_amd: outside the 16-bit SDDMM row entry's domain (isplib_sddmm_rows16_serves: n={n}, k={k}, ldy={ldy}, ldg={ldg})")
+        if (y.data_ptr() | g.data_ptr()) & 3:
+            raise ValueError("isplib_amd: `y` and `g` must be 4-byte aligned")
+    isplib_sddmm_csr_rows16_hip(rowptr, col, order, y, g, out, mean)
     return out
 
 

@@ -132,6 +132,14 @@ static inline bool is_rows16_colscale_plan(const Plan &p) {
    return p.size() == 3 && is_rows16_plan(Plan{p[0], p[1]}) && p[2].defined() && p[2].is_cuda() && p[2].scalar_type() == at::kFloat &&
           p[2].dim() == 1;
 }
+// the three-element form the forward `plan` of a sum / mean may take: a 16-bit row plan + a second marker (host int32 [1] = 0xDA) --
+// the plug-in's rows16_da_route said "rows16": the value gradient of this call runs on isplib_sddmm_csr_rows16_hip.  The forward
+// strips it (forward_plan) before it reads the plan; SpmmSum::backward / SpmmMean::backward read it (value_grad), nobody else does
+static inline bool is_rows16_da_plan(const Plan &p) {
+   return p.size() == 3 && is_rows16_plan(Plan{p[0], p[1]}) && p[2].defined() && !p[2].is_cuda() && p[2].scalar_type() == at::kInt &&
+          p[2].numel() == 1 && p[2].data_ptr<int32_t>()[0] == 0xDA;
+}
+static inline Plan forward_plan(const Plan &p) { return is_rows16_da_plan(p) ? Plan{p[0], p[1]} : p; }
 static inline const int32_t *plan_col32(const Plan &p, const Tensor &col) {
    if (p.size() != 6) return nullptr;
    TORCH_CHECK(p[5].scalar_type() == at::kInt && p[5].numel() == col.numel() && p[5].device() == col.device(),
@@ -616,6 +624,40 @@ Tensor sddmm(const Tensor &rowptr, const Tensor &col, const Tensor &mat, const T
    return dval;
 }
 
+// The value gradient of a 16-bit sum / mean on the 16-bit SDDMM row kernel (isplib_sddmm_csr_rows16_hip): neither X nor dY is widened
+// in memory, dval is fp32.  The operands are prepared as rows16_call prepares them -- `mat` as it lies if its pitch is served, else
+// packed; dY contiguous; either copied in 16 bits if its base is 2 bytes off a 4-byte boundary.  Undefined when the call is not
+// served (nothing was launched, nothing raises): the caller then takes the route it always took.
+static Tensor sddmm_rows16(const Tensor &rowptr, const Tensor &col, const Tensor &mat, const Tensor &grad_out, bool mean, const Plan &row_plan) {
+   if (!is_half(mat) || !is_half(grad_out) || mat.scalar_type() != grad_out.scalar_type() || mat.dim() != 2 || grad_out.dim() != 2 ||
+       rowptr.dim() != 1 || rowptr.numel() < 1 || !is_rows16_plan(row_plan))
+      return Tensor();
+   const int64_t M = rowptr.numel() - 1, N = mat.size(0), K = mat.size(1), nnz = col.numel();
+   if (M <= 0 || K <= 0 || K > ISPLIB_SDDMM_TASKS_K_MAX || grad_out.size(0) != M || grad_out.size(1) != K || !mat.is_cuda() ||
+       rowptr.device() != mat.device() || col.device() != mat.device() || grad_out.device() != mat.device() ||
+       rowptr.scalar_type() != at::kLong || col.scalar_type() != at::kLong)
+      return Tensor();
+   c10::DeviceGuard guard(mat.device());
+   const Rows16Call c = rows16_call(rowptr, col, Tensor(), false, mat, row_plan);      // (served: isplib_rows16_serves at K <= 1024 is isplib_sddmm_rows16_serves)
+   if (!c.served) return Tensor();
+   const Tensor g = packed16(grad_out);
+   Tensor dval = at::empty({nnz}, mat.options().dtype(at::kFloat));
+   const int st = isplib_sddmm_csr_rows16_hip(c.dtype, M, N, K, nnz, c.idx, c.ptr, c.ptr + 1, c.order, c.mat.data_ptr(), c.ldy, g.data_ptr(), K,
+                                              mean ? 1 : 0, dval.data_ptr<float>(), current_stream(c.mat));
+   check_status(st, "isplib_sddmm_csr_rows16_hip");
+   return dval;
+}
+
+// dA of SpmmSum / SpmmMean: the 16-bit kernel when the saved forward plan carries the marker and the call is served, else sddmm()
+static Tensor value_grad(const Tensor &rowptr, const Tensor &col, const Tensor &mat, const Tensor &grad_out, bool mean, const Plan &plan,
+                         const Tensor &value) {
+   if (is_rows16_da_plan(plan)) {
+      const Tensor dval = sddmm_rows16(rowptr, col, mat, grad_out, mean, Plan{plan[0], plan[1]});
+      if (dval.defined()) return dval;
+   }
+   return sddmm(rowptr, col, mat, grad_out, mean, forward_plan(plan), value);
+}
+
 // sum-SpMM with unit weights and the fused epilogue out = act(row_scale * (A y + self) + bias); the fold kernel
 // applies it when a task plan is given (isplib_epilogue), otherwise it is composed from ATen ops.
 Tensor epilogue_spmm(const Tensor &rowptr, const Tensor &col, const Plan &plan, const Tensor &y_, const Tensor &self_,
@@ -709,7 +751,7 @@ class SpmmSum : public torch::autograd::Function<SpmmSum> {
                                 optional<Variable> row_index_select, Plan plan, Plan plan_t) {
       const bool has_value = opt_value.has_value() && opt_value->defined();
       OpTimer timer("FUSEDMM_SPMM_SUM_FW", mat);
-      auto out = std::get<0>(spmm_fw(rowptr, col, opt_value, mat, R_SUM, plan));   // :244
+      auto out = std::get<0>(spmm_fw(rowptr, col, opt_value, mat, R_SUM, forward_plan(plan)));   // :244
       ctx->saved_data["plan_t"] = plan_t;
       ctx->saved_data["plan"] = plan;
       ctx->saved_data["has_value"] = has_value;
@@ -731,7 +773,7 @@ class SpmmSum : public torch::autograd::Function<SpmmSum> {
 
       auto grad_value = Variable();
       if (has_value && ctx->needs_input_grad(ctx->saved_data["value_edge"].toInt()))   // :269-272 (SDDMM, commented out there)
-         grad_value = sddmm(rowptr, col, mat, grad_out, false, ctx->saved_data["plan"].toTensorVector(), value);
+         grad_value = value_grad(rowptr, col, mat, grad_out, false, ctx->saved_data["plan"].toTensorVector(), value);
 
       auto grad_mat = Variable();
       if (ctx->needs_input_grad(ctx->saved_data["mat_edge"].toInt())) {
@@ -759,7 +801,7 @@ class SpmmMean : public torch::autograd::Function<SpmmMean> {
                                 optional<Variable> new_row, optional<Variable> new_rowcount, Plan plan, Plan plan_t) {
       const bool has_value = opt_value.has_value() && opt_value->defined();
       OpTimer timer("FUSEDMM_SPMM_MEAN_FW", mat);
-      auto out = std::get<0>(spmm_fw(rowptr, col, opt_value, mat, R_MEAN, plan));   // :331
+      auto out = std::get<0>(spmm_fw(rowptr, col, opt_value, mat, R_MEAN, forward_plan(plan)));   // :331
       ctx->saved_data["plan_t"] = plan_t;
       ctx->saved_data["plan"] = plan;
       ctx->saved_data["has_value"] = has_value;
@@ -782,7 +824,7 @@ class SpmmMean : public torch::autograd::Function<SpmmMean> {
 
       auto grad_value = Variable();
       if (has_value && ctx->needs_input_grad(ctx->saved_data["value_edge"].toInt()))
-         grad_value = sddmm(rowptr, col, mat, grad_out, true, ctx->saved_data["plan"].toTensorVector(), value);   // :350-353
+         grad_value = value_grad(rowptr, col, mat, grad_out, true, ctx->saved_data["plan"].toTensorVector(), value);   // :350-353
 
       auto grad_mat = Variable();
       if (ctx->needs_input_grad(ctx->saved_data["mat_edge"].toInt())) {

@@ -24,7 +24,8 @@ Environment: ISPLIB_SLICES=<n> forces the task list with n column slices (0: pla
 sum / mean off the stream schedule; ISPLIB_STREAM_GEOM=streams:slices:chunk forces it with that plan geometry;
 ISPLIB_HALF=auto|native|convert picks the route of bf16 / fp16 features (half_route; rows16_route for calls on the plain kernel);
 ISPLIB_HALF_MINMAX=convert|native|auto does the same for max / min (rows16_minmax_route), ISPLIB_HALF_MEAN_BW=convert|native|auto
-for the backward of a 16-bit `mean` on an unweighted graph (rows16_mean_bw_route); both default to convert;
+for the backward of a 16-bit `mean` on an unweighted graph (rows16_mean_bw_route), ISPLIB_HALF_DA=convert|native|auto for the value
+gradient of a 16-bit sum / mean (rows16_da_route); all three default to convert;
 ISPLIB_TUNE_FILE names a tuning table to load at import; ISPLIB_DEBUG=1 prints per-operator device times.
 """
 from __future__ import annotations
@@ -353,7 +354,25 @@ def rows16_mean_bw_route(dtype, k: int, m_rows: int, ordered: bool = False, mode
     return _rows16_gate(dtype, mode, "ISPLIB_HALF_MEAN_BW", m_rows, k, k, lambda cabi, ld: cabi.rows16_colscale_native_pays(m_rows, k, bool(ordered)))
 
 
+def rows16_da_route(dtype, k: int, pitch: int, n: int, ordered: bool = False, mode: Optional[str] = None, whole_row_slices: int = 0) -> str:
+    """Which way the value gradient (dA, the SDDMM) of a sum / mean with 16-bit features goes when its forward went to the 16-bit
+    row kernel: "rows16" (the 16-bit SDDMM row kernel, isplib_sddmm_csr_rows16_hip, on X and dY as they are: no fp32 copy of either,
+    half the gathered bytes, dA in fp32) or "convert" (widen both, the fp32 SDDMM).  A pure function -- no device, no library call:
+      * rows16 needs bf16 / fp16 and X's shape, [n, k] at its own row pitch or, failing that, packed, inside the entry's domain
+        (cabi.sddmm_rows16_serves: the row kernel's, and k <= 1024);
+      * `whole_row_slices` > 0 (isplib_suggest_slices_whole_rows for the graph): the handle's task-list SDDMM keeps the graph --
+        "convert", whatever the mode;
+      * `mode` is ISPLIB_HALF_DA (None: read from the environment; default "convert", and ISPLIB_HALF=convert wins over it):
+        "convert" always converts, "native" takes the kernel wherever the above holds, "auto" only in the classes -- (X beyond
+        256 MiB or not) x `ordered` (the rows come in a community order) -- where every native run measured faster than every run
+        of the conversion route (cabi.sddmm_rows16_native_pays, profiles/sddmm_rows16_ab.txt).  Nothing raises."""
+    if whole_row_slices > 0 or k > 1024:
+        return "convert"
+    return _rows16_gate(dtype, mode, "ISPLIB_HALF_DA", n, k, pitch, lambda cabi, ld: cabi.sddmm_rows16_native_pays(n, ld, bool(ordered)))
+
+
 _ROWS16_MARK = torch.tensor([16], dtype=torch.int32)      # second tensor of a 16-bit row plan (torch_ops.cpp: is_rows16_plan)
+_ROWS16_DA_MARK = torch.tensor([0xDA], dtype=torch.int32)  # third tensor of a forward plan whose dA runs in 16 bits (is_rows16_da_plan)
 
 
 def _rows16_plan(s: SparseStorage, transposed: bool, k: int, device) -> list:
@@ -440,6 +459,14 @@ def spmm_autotuned(src, other: torch.Tensor, reduce: str = "sum") -> torch.Tenso
     if reduce in ("sum", "add", "mean"):
         colptr = val_t = row_t = None
         plan_t = []
+        if rows16 and value is not None and torch.is_grad_enabled() and value.requires_grad and \
+                os.environ.get("ISPLIB_HALF_DA", "convert") != "convert":
+            # dA of a row-kernel call, opt-in (ISPLIB_HALF_DA): rows16_da_route's answer travels with the plan as a second marker,
+            # which the operator strips before its forward and reads in its backward
+            from . import cabi
+            whole = int(cabi.lib().isplib_suggest_slices_whole_rows(m_rows, mat.size(0), col.numel(), k)) if k >= 4 else 0
+            if rows16_da_route(mat.dtype, k, pitch, mat.size(0), plan[0].numel() > 0, None, whole) == "rows16":
+                plan = list(plan) + [_ROWS16_DA_MARK]
         if needs_grad:                                               # :76-80 / :83-99 (built once per graph)
             colptr, row_t = s.colptr(), s.row_t()
             # mean: the intended pairing, val[csr2csc] / max(deg, 1) -- for an unweighted graph that is
