@@ -840,6 +840,9 @@ int    isplib_scatter_keys_det_hip(int64_t total, int64_t n, int64_t k, const ui
 /*
  * SDDMM-style value gradient of SpMM-sum / SpMM-mean:
  *   dval[j] = < y[indx[j], :], g[i, :] > * (mean ? 1/max(deg_i,1) : 1),  j in row i
+ * Every dval[j], j in [0, nnz), is written and nothing outside that range is; it lies within 1e-5 * <|y|, |g|> + 64 * 2^-149 of
+ * the exact value (exact where the fp32 sums are exact in any order), a non-finite value in column c of y or g enters it only
+ * through the product of column c, and nothing is flushed to zero.
  */
 int isplib_sddmm_csr_hip(int64_t m, int64_t k, const int64_t *indx,
                          const int64_t *pntrb, const int64_t *pntre,
@@ -847,7 +850,10 @@ int isplib_sddmm_csr_hip(int64_t m, int64_t k, const int64_t *indx,
                          int64_t ldg, int mean, float *dval, void *stream);
 /* The same over the task plan of the SpMM (one wave per task, XCD-lane grouping -> the L2 affinity of
  * the task-list SpMM; dval is per edge, so no workspace and no combine).  Domain: isplib_sddmm_tasks_serve(n, k, ldy) --
- * ISPLIB_K_MIN <= k <= ISPLIB_SDDMM_TASKS_K_MAX, n*ldy*4 <= ISPLIB_DENSE_BYTES_MAX. */
+ * ISPLIB_K_MIN <= k <= ISPLIB_SDDMM_TASKS_K_MAX, n*ldy*4 <= ISPLIB_DENSE_BYTES_MAX.  The same contract as isplib_sddmm_csr_hip for
+ * every edge a task covers: the bound, exactness on exactly summable data, a non-finite value in column c reaching an edge only
+ * through the product of column c at any k (a ragged k's shifted last vector included), no flush to zero, no write outside
+ * dval[0, nnz). */
 int isplib_sddmm_csr_tasks_hip(int64_t m, int64_t n, int64_t k, const int64_t *indx,
                                const int32_t *indx32 /*optional, as in fusedMM_csr_tasks_hip*/,
                                const int64_t *pntrb, const int64_t *pntre,

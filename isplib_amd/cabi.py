@@ -862,19 +862,63 @@ def scatter_keys_det(keys, vals, n: int, k: int, out=None, workspace=None):
     return out
 
 
-def sddmm(rowptr, col, y, g, mean: bool = False):
-    rowptr = _dev(rowptr, "rowptr", torch.int64)
-    col = _dev(col, "col", torch.int64)
-    y = _dev(y, "y", torch.float32)
-    g = _dev(g, "g", torch.float32)
+def _sddmm_operands(rowptr, col, y, g, out, check: bool, min_rows: int = 0, what: str = "the plan"):
+    """The operand checks of sddmm, sddmm_tasks and GraphHandle.sddmm, made BEFORE the call -- the entries cannot know how many rows
+    either dense operand has, so a mis-shaped one is an out-of-bounds device read: `y` [n, k] and `g` [m, k] (m = rowptr.numel() - 1)
+    float32 with unit inner stride (row-strided views keep their pitch), rowptr / col int64, everything on one GPU, n at least
+    `min_rows` (the column count `what` was built for), `out` (allocated when None) a contiguous float32 tensor of at least nnz
+    entries, and -- `check` -- every column id inside [0, n).  Returns (rowptr, col, out, ldy, ldg)."""
+    if not isinstance(y, torch.Tensor) or y.dim() != 2:
+        raise ValueError("isplib_amd: `y` must be a 2-D tensor [n, k]")
+    if y.dtype != torch.float32:
+        raise TypeError(f"isplib_amd: `y` must be float32, got {y.dtype} (bfloat16 / float16: sddmm_rows16)")
+    if not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1 or rowptr.numel() < 1 or not isinstance(col, torch.Tensor) or col.dim() != 1:
+        raise ValueError("isplib_amd: `rowptr` (m + 1 entries) and `col` must be 1-D tensors")
+    if rowptr.dtype != torch.int64 or col.dtype != torch.int64:
+        raise TypeError(f"isplib_amd: `rowptr` and `col` must be int64, got {rowptr.dtype} and {col.dtype}")
+    m, nnz = rowptr.numel() - 1, col.numel()
+    n, k = y.size(0), y.size(1)
+    if not isinstance(g, torch.Tensor) or g.dim() != 2 or tuple(g.shape) != (m, k):
+        raise ValueError(f"isplib_amd: `g` must be a 2-D tensor [{m}, {k}] (one row per row of the sparse operand, y's width), got "
+                         f"{tuple(g.shape) if isinstance(g, torch.Tensor) else type(g).__name__}")
+    if g.dtype != torch.float32:
+        raise TypeError(f"isplib_amd: `g` must be float32, got {g.dtype}")
+    if k > 0 and ((n > 0 and y.stride(1) != 1) or (m > 0 and g.stride(1) != 1)):
+        raise ValueError("isplib_amd: `y` and `g` must have unit inner stride")
+    ldy = y.stride(0) if n > 1 else max(k, y.stride(0))
+    ldg = g.stride(0) if m > 1 else max(k, g.stride(0))
+    if ldy < k or ldg < k:
+        raise ValueError(f"isplib_amd: the rows of `y` (pitch {ldy}) and `g` (pitch {ldg}) must not overlap: k = {k}")
+    if n < min_rows:
+        raise ValueError(f"isplib_amd: {what} was built for {min_rows} columns, `y` has {n} rows")
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.dim() != 1 or out.numel() < nnz or
+                            not out.is_contiguous()):
+        raise ValueError(f"isplib_amd: `out` must be a contiguous float32 tensor of at least {nnz} entries")
+    if check and nnz > 0 and (int(col.min()) < 0 or int(col.max()) >= n):
+        raise ValueError(f"isplib_amd: column ids must lie in [0, {n}): `y` must hold a row for every column of the sparse operand")
+    _same_gpu((("y", y), ("g", g), ("rowptr", rowptr), ("col", col), ("out", out)))
+    rowptr, col = rowptr.contiguous(), col.contiguous()
+    if out is None:
+        out = torch.empty(nnz, dtype=torch.float32, device=y.device)
+    return rowptr, col, out, ldy, ldg
+
+
+def sddmm(rowptr, col, y, g, mean: bool = False, *, out=None, check: bool = True):
+    """dA of SpMM-sum / SpMM-mean on the row kernel (isplib_sddmm_csr_hip): returns `out`, float32 in CSR order (allocated with
+    col.numel() entries when not given; a given one of at least that many is written in place), out[e] = <y[col[e], :], g[i, :]>
+    (`mean`: / max(deg_i, 1)) for the edges e of row i.  Row-strided views of `y` and `g` keep their pitch.  The operands are
+    checked before the call (_sddmm_operands; `check`: the column ids too -- two reductions over `col` and a synchronisation, so a
+    timed loop over a graph already checked passes check=False)."""
+    rowptr, col, out, ldy, ldg = _sddmm_operands(rowptr, col, y, g, out, check)
     m, k = rowptr.numel() - 1, y.size(1)
-    dval = torch.empty(col.numel(), dtype=torch.float32, device=y.device)
+    if col.numel() == 0:                                        # no edge, nothing to write (and an empty tensor has no address to hand over)
+        return out
     rp = rowptr.data_ptr()
     with torch.cuda.device(y.device):
-        st = lib().isplib_sddmm_csr_hip(m, k, _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8), _ptr(y), k,
-                                        _ptr(g), k, int(bool(mean)), _ptr(dval), _stream(y.device))
+        st = lib().isplib_sddmm_csr_hip(m, k, _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8), _ptr(y), ldy,
+                                        _ptr(g), ldg, int(bool(mean)), _ptr(out), _stream(y.device))
     _check(st, "isplib_sddmm_csr_hip")
-    return dval
+    return out
 
 
 def csr_row_ids(rowptr, nnz: int):
@@ -1049,22 +1093,29 @@ def sddmm_stream(rowptr, nnz: int, plan, y, g, mean: bool = False):
     return dval
 
 
-def sddmm_tasks(rowptr, col, plan, y, g, mean: bool = False):
-    """dA over the task plan of the SpMM (isplib_sddmm_csr_tasks_hip)."""
-    rowptr = _dev(rowptr, "rowptr", torch.int64)
-    col = _dev(col, "col", torch.int64)
-    y = _dev(y, "y", torch.float32)
-    g = _dev(g, "g", torch.float32)
-    m, n, k = rowptr.numel() - 1, y.size(0), y.size(1)
-    dval = torch.empty(col.numel(), dtype=torch.float32, device=y.device)
+def sddmm_tasks(rowptr, col, plan, y, g, mean: bool = False, *, out=None, check: bool = True, col32: bool = True):
+    """dA over the task plan of the SpMM (isplib_sddmm_csr_tasks_hip); `out`, `check` and the operand checks as for sddmm, and the
+    plan must have been built for this graph's rows and at most y's rows as columns.  `col32=False`: the int64 column ids
+    instead of the plan's packed 32-bit copy (indx32 = NULL)."""
+    m = rowptr.numel() - 1 if isinstance(rowptr, torch.Tensor) else -1
+    seg_off = getattr(plan, "seg_off", None)
+    if seg_off is not None and seg_off.numel() != plan.slices * m + 1:
+        raise ValueError(f"isplib_amd: the task plan was built for {(seg_off.numel() - 1) // max(plan.slices, 1)} rows, the graph has {m}")
+    rowptr, col, out, ldy, ldg = _sddmm_operands(rowptr, col, y, g, out, check, int(getattr(plan, "ncols", None) or 0), "the task plan")
+    if plan.n_tasks > 0 and plan.task_row.device != y.device:
+        raise ValueError(f"isplib_amd: the task plan is on {plan.task_row.device}, the operands on {y.device}")
+    n, k = y.size(0), y.size(1)
+    if col.numel() == 0:
+        return out
     rp = rowptr.data_ptr()
     lane = (ctypes.c_int64 * 9)(*plan.lane_off)
     with torch.cuda.device(y.device):
-        st = lib().isplib_sddmm_csr_tasks_hip(m, n, k, _ptr(col), _plan_col32(plan, col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8), plan.n_tasks,
-                                              _ptr(plan.task_row), _ptr(plan.task_b), _ptr(plan.task_len), lane, _ptr(y), k,
-                                              _ptr(g), k, int(bool(mean)), _ptr(dval), _stream(y.device))
+        st = lib().isplib_sddmm_csr_tasks_hip(m, n, k, _ptr(col), _plan_col32(plan, col) if col32 else None, ctypes.c_void_p(rp),
+                                              ctypes.c_void_p(rp + 8), plan.n_tasks, _ptr(plan.task_row), _ptr(plan.task_b),
+                                              _ptr(plan.task_len), lane, _ptr(y), ldy, _ptr(g), ldg, int(bool(mean)), _ptr(out),
+                                              _stream(y.device))
     _check(st, "isplib_sddmm_csr_tasks_hip")
-    return dval
+    return out
 
 
 def spmm_tasks_epilogue(rowptr, col, val, plan, y, reduce="sum", row_scale=None, self_term=None, bias=None, relu=False):
@@ -1627,6 +1678,7 @@ class GraphHandle:
         self.col = _dev(col, "col", torch.int64)
         self.val = None if val is None else _dev(val, "val", torch.float32)
         self.m, self.n = self.rowptr.numel() - 1, int(ncols)
+        self._cols_ok = None                                    # sddmm's column-id check, made once
         self._h = ctypes.c_void_p()
         with torch.cuda.device(self.col.device):
             _check(lib().isplib_graph_create(self.m, self.n, self.col.numel(), _ptr(self.rowptr), _ptr(self.col),
@@ -1671,14 +1723,20 @@ class GraphHandle:
                    "isplib_graph_spmm_backward")
         return dx
 
-    def sddmm(self, y: torch.Tensor, g: torch.Tensor, mean: bool = False) -> torch.Tensor:
-        y, g = _dev(y, "y", torch.float32), _dev(g, "g", torch.float32)
+    def sddmm(self, y: torch.Tensor, g: torch.Tensor, mean: bool = False, *, out=None, check: bool = True) -> torch.Tensor:
+        """dA through isplib_graph_sddmm (the task plan of the handle's slice count, else the row kernel); `out` and the operand
+        checks as for cabi.sddmm, `y` holding at least the handle's column count of rows.  `check`: the handle's column ids lie in
+        [0, ncols) -- looked at once per handle (its graph is fixed), so a timed loop pays for it in its first call only."""
+        _, _, out, ldy, ldg = _sddmm_operands(self.rowptr, self.col, y, g, out, False, self.n, "the handle")
+        if check and self._cols_ok is None:
+            self._cols_ok = self.col.numel() == 0 or (int(self.col.min()) >= 0 and int(self.col.max()) < self.n)
+        if check and not self._cols_ok:
+            raise ValueError(f"isplib_amd: the handle's column ids must lie in [0, {self.n})")
         k = y.size(1)
-        dval = torch.empty(self.col.numel(), dtype=torch.float32, device=y.device)
         with torch.cuda.device(y.device):
-            _check(lib().isplib_graph_sddmm(self._h, int(bool(mean)), k, _ptr(y), k, _ptr(g), k, _ptr(dval), _stream(y.device)),
+            _check(lib().isplib_graph_sddmm(self._h, int(bool(mean)), k, _ptr(y), ldy, _ptr(g), ldg, _ptr(out), _stream(y.device)),
                    "isplib_graph_sddmm")
-        return dval
+        return out
 
     def close(self) -> None:
         if self._h:

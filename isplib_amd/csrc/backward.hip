@@ -150,8 +150,13 @@ struct SddmmTaskArgs {
 // ACCUM: a later column panel of the same call -- the dot products of this panel are added to what the earlier panels
 // stored (the old values of a 64-edge batch are fetched before its gathers are issued, so their latency hides behind them; a
 // task's results are consecutive CSR positions, read and written coalesced)
-template <int LPR, int NCH, int WAVES, bool ACCUM>
-__global__ __launch_bounds__(WAVES * 64, NCH == 1 ? 8 : 1) void sddmm_task_kernel(const SddmmTaskArgs a) {
+// RAGGED (k % 4 != 0): a row's last 16-byte vector is shifted back to end at column k, so its first `vfirst` components are
+// columns the neighbouring lane multiplies too.  They are taken out of the gathered y AND out of g's registers: zeroing g alone
+// would turn an Inf of y into Inf * 0 = NaN where the k products give Inf (sddmm_rows16.hip does the same).  The select sits
+// behind the compile-time flag; k % 4 == 0 pays nothing.  (The ragged four-chunk form asks for eight waves per SIMD as the one-chunk
+// forms do: left alone its selects cost it eight registers and the eighth wave the whole form has, profiles/sddmm_tasks_ragged_isa.txt.)
+template <int LPR, int NCH, int WAVES, bool ACCUM, bool RAGGED>
+__global__ __launch_bounds__(WAVES * 64, (NCH == 1 || (RAGGED && NCH == 4)) ? 8 : 1) void sddmm_task_kernel(const SddmmTaskArgs a) {
    constexpr int G = 64 / LPR, U = 4;
    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
    const int g = lane / LPR, lc = lane % LPR;
@@ -166,12 +171,14 @@ __global__ __launch_bounds__(WAVES * 64, NCH == 1 ? 8 : 1) void sddmm_task_kerne
    // this lane's columns of g[row]; ragged k: the last vector is shifted back, its duplicate components zeroed
    unsigned cbyte[NCH];
    float gv[NCH][4];
+   int vf[NCH];                                                 // RAGGED: the leading components of chunk j that y drops too (0..3)
 #pragma unroll
    for (int j = 0; j < NCH; j++) {
       int c = (j * LPR + lc) * 4;
       int vfirst = 0;
       const bool ok = c < (int)a.k;
       if (ok && c + 4 > (int)a.k) { vfirst = c + 4 - (int)a.k; c = (int)a.k - 4; }
+      vf[j] = vfirst;
       cbyte[j] = ok ? (unsigned)c * 4u : BUF_OOB;
       const float *gr = a.g + (size_t)row * (size_t)a.ldg + c;
 #pragma unroll
@@ -213,7 +220,12 @@ __global__ __launch_bounds__(WAVES * 64, NCH == 1 ? 8 : 1) void sddmm_task_kerne
 #pragma unroll
             for (int j = 0; j < NCH; j++)
 #pragma unroll
-               for (int v = 0; v < 4; v++) d[u] = fmaf(__int_as_float(yv[u][j][v]), gv[j][v], d[u]);
+               for (int v = 0; v < 4; v++) {
+                  float yc = __int_as_float(yv[u][j][v]);
+                  // the shifted vector is chunk k / 4 of the row, and the launcher's widths put it in the upper half of a lane's chunks
+                  if (RAGGED && j >= NCH / 2 && v < 3) yc = v < vf[j] ? 0.0f : yc;
+                  d[u] = fmaf(yc, gv[j][v], d[u]);
+               }
          }
          int mine;
          const float sum = reduce_transposed<U, LPR>(d, lc, mine);
@@ -224,6 +236,12 @@ __global__ __launch_bounds__(WAVES * 64, NCH == 1 ? 8 : 1) void sddmm_task_kerne
    }
 }
 
+template <int LPR, int NCH, int WAVES, bool ACCUM>
+static void launch_sddmm_task_kernel(const SddmmTaskArgs &a, unsigned gx, hipStream_t st) {
+   if (a.k % 4 != 0) hipLaunchKernelGGL((sddmm_task_kernel<LPR, NCH, WAVES, ACCUM, true>), dim3(gx), dim3(WAVES * 64), 0, st, a);
+   else hipLaunchKernelGGL((sddmm_task_kernel<LPR, NCH, WAVES, ACCUM, false>), dim3(gx), dim3(WAVES * 64), 0, st, a);
+}
+
 template <int LPR, int NCH>
 static int launch_sddmm_tasks(const SddmmTaskArgs &a, hipStream_t st, bool accum = false) {
    constexpr int WAVES = 4;
@@ -232,8 +250,8 @@ static int launch_sddmm_tasks(const SddmmTaskArgs &a, hipStream_t st, bool accum
    const int64_t gx = 8 * ((most + WAVES - 1) / WAVES);
    if (gx > 0x7fffffffLL) return ISPLIB_FAIL;
    if (gx == 0) return ISPLIB_SUCCESS;
-   if (accum) hipLaunchKernelGGL((sddmm_task_kernel<LPR, NCH, WAVES, true>), dim3((unsigned)gx), dim3(WAVES * 64), 0, st, a);
-   else hipLaunchKernelGGL((sddmm_task_kernel<LPR, NCH, WAVES, false>), dim3((unsigned)gx), dim3(WAVES * 64), 0, st, a);
+   if (accum) launch_sddmm_task_kernel<LPR, NCH, WAVES, true>(a, (unsigned)gx, st);
+   else launch_sddmm_task_kernel<LPR, NCH, WAVES, false>(a, (unsigned)gx, st);
    return check_launch("sddmm_task_kernel");
 }
 

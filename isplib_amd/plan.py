@@ -36,6 +36,7 @@ class TaskPlan:
     short_row: int
     col32: Optional[torch.Tensor] = None   # int32 [nnz]: the column ids packed once per graph; the task kernels
     #                                        stream these 4 bytes per edge instead of the 8 of the int64 array
+    ncols: Optional[int] = None            # the column count the slices were cut for: a dense operand holds at least as many rows
 
     def workspace(self, reduce: str, k: int) -> torch.Tensor:
         nbytes = cabi.lib().isplib_spmm_tasks_workspace_bytes(cabi.MESSAGE[reduce], self.n_tasks, k)
@@ -80,7 +81,7 @@ def build_task_plan(rowptr: torch.Tensor, col: torch.Tensor, ncols: int, slices:
     if col32 is None:
         col32 = cabi.pack_indices(col)
     return TaskPlan(slices, n_tasks, task_row[:n_tasks], task_b[:n_tasks], task_len[:n_tasks], seg_off,
-                    [int(v) for v in info.lane_off], chunk, short_row, col32)
+                    [int(v) for v in info.lane_off], chunk, short_row, col32, int(ncols))
 
 
 @dataclass
