@@ -564,6 +564,53 @@ static inline int isplib_rows16_colscale_native_pays(int64_t n, int64_t ldy, int
 }
 int    isplib_rows16_colscale_auto(int64_t n, int64_t ldy, int ordered);           /* the same rule as a symbol */
 /*
+ * fusedMM_csr_rows16_colscale_hip's sum (col_scale == NULL: fusedMM_csr_rows16_hip's unit-weight sum) with an epilogue applied in fp32
+ * to the finished row before it is rounded ONCE:
+ *   z[i,c] = round16( act( rs_i * ( sum over the edges e of row i of cs[indx[e]] * y[indx[e],c] + ss_i * y[i,c] ) + bias[c] ) )
+ * in this order: the sum (the bits of the entries above), one fmaf(ss_i, y[i,c], sum), * rs_i, + bias[c], act(v) = v > 0 ? v : 0 when
+ * relu is nonzero (the fp32 epilogue's: -0.0 and NaN give +0.0).  Every member of the epilogue is optional; ep == NULL is all of them
+ * absent.  The use it was built for: the fused GCN layer relu(D^-1/2 (A + I) D^-1/2 X + b) of a 16-bit X, cs = ss = rs = D^-1/2 -- no
+ * pre-scaled copy of X in either width -- and its backward on A^T.  Sum only, no per-edge weights.  No atomics: two
+ * launches give equal bits, any row order the bits of index order.  An empty row gets its epilogue too (nnz == 0 launches).
+ * Domain and refusals: fusedMM_csr_rows16_hip's, and self_scale != NULL with m != n (the self row of i is y[i,:]); refused before any
+ * launch, z untouched.  m == 0 or k == 0 succeeds without a launch.
+ * isplib_rows16_gcn_native_pays is the measured rule of the layers above for the fused GCN layer (forward + backward,
+ * profiles/rows16_gcn_ab.txt), over the classes (operand beyond 256 MiB at 2 bytes per element or not) x (rows in a community order
+ * or not): nonzero only where EVERY native run was faster than EVERY run of the conversion route on every measured shape of the class.
+ */
+typedef struct isplib_epilogue16 {
+   const float *row_scale;   /* [dev] m fp32, or NULL (= 1) */
+   const float *self_scale;  /* [dev] m fp32, or NULL = no self term; non-NULL needs m == n: the self row of i is y[i,:] */
+   const float *bias;        /* [dev] k fp32, or NULL */
+   int          relu;        /* nonzero: v > 0 ? v : 0 */
+} isplib_epilogue16;
+int    fusedMM_csr_rows16_epilogue_hip(int dtype /* ISPLIB_DTYPE_BF16 | _F16 */, int64_t m, int64_t n, int64_t k, int64_t nnz,
+                                       const float *col_scale /* [dev] n, or NULL = unit */, const int64_t *indx, const int64_t *pntrb,
+                                       const int64_t *pntre, const int32_t *row_order /* optional */, const void *y, int64_t ldy, void *z,
+                                       int64_t ldz, const isplib_epilogue16 *epilogue /* host, may be NULL */, void *stream);
+static inline int isplib_rows16_gcn_native_pays(int64_t n, int64_t ldy, int ordered) {
+   /* measured (profiles/rows16_gcn_ab.txt: rows16_ab's shapes and the Reddit shape, bf16, forward + backward with bias and ReLU): beyond
+    * 256 MiB every native run is below every convert run -- in index order 0.48-0.57 of the conversion route's time, in a community order
+    * 0.28-0.37.  Inside 256 MiB in index order five shapes win (0.49-0.89) but the Reddit shape loses at K = 32 and 48 (1.9-2.2 x: the
+    * conversion route's fp32 layer runs there on the stream schedule), so the class loses; inside 256 MiB in a community order is not
+    * produced by the layers above and was not measured.  Both stay on convert. */
+   (void)ordered;
+   return (n > 0 && ldy > 0 && (double)n * (double)ldy * 2.0 > 256.0 * 1048576.0) ? 1 : 0;
+}
+int    isplib_rows16_gcn_auto(int64_t n, int64_t ldy, int ordered);                /* the same rule as a symbol */
+/*
+ * The backward's dense prologue of the fused GCN layer in 16 bits (dtype: ISPLIB_DTYPE_BF16 | _F16; dz, out, g: n x k elements of 2
+ * bytes at their pitches), one pass over dz (and out):
+ *   g[i,c] = out ? (out[i,c] > 0 ? dz[i,c] : +0) : dz[i,c]          a bit copy or +0: nothing is rounded (g may be NULL)
+ *   grad_bias[c] = sum_i widen(g[i,c])                              fp32 (may be NULL; else a workspace of
+ *                                                                   isplib_masked_colsum16_workspace_bytes(n, k) bytes, 256-byte aligned)
+ * No atomics: per-block partials folded in block order, bitwise reproducible.  With neither g nor grad_bias nothing runs.
+ */
+size_t isplib_masked_colsum16_workspace_bytes(int64_t n, int64_t k);
+int    isplib_masked_colsum16_hip(int dtype, int64_t n, int64_t k, const void *dz, int64_t lddz, const void *out /*NULL: no mask*/, int64_t ldo,
+                                  void *g /*[dev] n x ldg | NULL*/, int64_t ldg, float *grad_bias /*[dev] k fp32 | NULL*/, void *workspace,
+                                  size_t workspace_bytes, void *stream);
+/*
  * fusedMM_csr_rows16_hip's schedule for max / min of a 16-bit dense operand: one CSR row per wavefront, 16-byte gathers of eight
  * columns, the optional row order, no fp32 copy of the operand.  The halves are widened in registers and every comparison is fp32:
  * the candidate of an edge is val * y (ONE fp32 multiply; val = NULL: y itself) and replaces the running value only if strictly

@@ -93,6 +93,15 @@ def rows16_colscale_native_pays(n: int, ldy: int, ordered: bool) -> bool:
     return bool(beyond or not ordered)
 
 
+def rows16_gcn_native_pays(n: int, ldy: int, ordered: bool) -> bool:
+    """isplib_rows16_gcn_native_pays of the header: the classes of fused GCN layers (forward + backward) on 16-bit features -- (X beyond
+    256 MiB at 2 bytes per element or not) x (rows in a community order or not) -- in which every native run measured faster than every
+    run of the conversion route (profiles/rows16_gcn_ab.txt: both classes beyond 256 MiB do; inside 256 MiB the index-order class loses
+    on the Reddit shape, where the conversion route's fp32 layer runs on the stream schedule, and the community-order class was not
+    measured, so both stay on convert); tests/test_rows16_gcn_host.py compares the two."""
+    return bool(n > 0 and ldy > 0 and n * ldy * 2 > (256 << 20))
+
+
 def sddmm_rows16_serves(n: int, k: int, ldy: int, ldg: int) -> bool:
     """isplib_sddmm_rows16_serves of the header: the 16-bit SDDMM row entry (isplib_sddmm_csr_rows16_hip) serves y [n, k] at leading
     dimension ldy and g at leading dimension ldg -- the 16-bit row entry's domain, and k <= 1024 (g[row, :] sits in registers)."""
@@ -155,6 +164,7 @@ EXPORTS = (
     "fusedMM_csr_rows16_hip", "isplib_rows16_auto", "isplib_rows16_domain",
     "fusedMM_csr_rows16_minmax_hip", "isplib_rows16_minmax_auto",
     "fusedMM_csr_rows16_colscale_hip", "isplib_rows16_colscale_auto",
+    "fusedMM_csr_rows16_epilogue_hip", "isplib_rows16_gcn_auto", "isplib_masked_colsum16_hip", "isplib_masked_colsum16_workspace_bytes",
     "isplib_sddmm_csr_rows16_hip", "isplib_sddmm_rows16_auto",
 )
 
@@ -378,6 +388,14 @@ def lib() -> ctypes.CDLL:
         L.fusedMM_csr_rows16_colscale_hip.argtypes = [_i32, ctypes.c_int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]
         L.isplib_rows16_colscale_auto.restype = ctypes.c_int
         L.isplib_rows16_colscale_auto.argtypes = [_i64, _i64, ctypes.c_int]
+        L.fusedMM_csr_rows16_epilogue_hip.restype = ctypes.c_int
+        L.fusedMM_csr_rows16_epilogue_hip.argtypes = [ctypes.c_int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp]
+        L.isplib_rows16_gcn_auto.restype = ctypes.c_int
+        L.isplib_rows16_gcn_auto.argtypes = [_i64, _i64, ctypes.c_int]
+        L.isplib_masked_colsum16_workspace_bytes.restype = ctypes.c_size_t
+        L.isplib_masked_colsum16_workspace_bytes.argtypes = [_i64, _i64]
+        L.isplib_masked_colsum16_hip.restype = ctypes.c_int
+        L.isplib_masked_colsum16_hip.argtypes = [ctypes.c_int, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, ctypes.c_size_t, _vp]
         L.isplib_sddmm_csr_rows16_hip.restype = ctypes.c_int
         L.isplib_sddmm_csr_rows16_hip.argtypes = [ctypes.c_int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, ctypes.c_int, _vp, _vp]
         L.isplib_sddmm_rows16_auto.restype = ctypes.c_int
@@ -1379,6 +1397,86 @@ def spmm_rows16_colscale(rowptr, col, scale, y, reduce: str = "sum", order=None,
     rowptr, col, scale, order, out, _ = _rows16_operands(rowptr, col, scale, True, y, order, out)
     fusedMM_csr_rows16_colscale_hip(MESSAGE[reduce], rowptr, col, scale, order, y, out)
     return out
+
+
+class Epilogue16(ctypes.Structure):
+    """isplib_epilogue16 of the header."""
+    _fields_ = [("row_scale", ctypes.c_void_p), ("self_scale", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("relu", ctypes.c_int)]
+
+
+def fusedMM_csr_rows16_epilogue_hip(rowptr, col, col_scale, order, y, z, row_scale=None, self_scale=None, bias=None, relu: bool = False,
+                                    null_epilogue: bool = False, check: bool = True, dtype=None, m=None, k=None, ldy=None, ldz=None) -> int:
+    """Raw boundary call of the 16-bit row SpMM with an epilogue, for operands the entry may refuse: it hands over what it is given
+    (`dtype`, `m`, `k`, `ldy`, `ldz`: override what the tensors say -- refusal tests; the entry refuses before it reads anything;
+    `null_epilogue`: pass ep = NULL instead of a struct).  Callers that want their operands checked use spmm_rows16_epilogue."""
+    m = rowptr.numel() - 1 if m is None else int(m)
+    n = y.size(0)
+    k = y.size(1) if k is None else int(k)
+    code = HALF_DTYPES.get(y.dtype, 0) if dtype is None else int(dtype)
+    ep = Epilogue16(None if row_scale is None else row_scale.data_ptr(), None if self_scale is None else self_scale.data_ptr(),
+                    None if bias is None else bias.data_ptr(), int(bool(relu)))
+    rp = rowptr.data_ptr()
+    with torch.cuda.device(y.device):
+        st = lib().fusedMM_csr_rows16_epilogue_hip(code, m, n, k, col.numel(), _ptr(col_scale), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8),
+                                                   _ptr(order), _ptr(y), (y.stride(0) if n > 1 else max(k, y.stride(0))) if ldy is None else int(ldy),
+                                                   _ptr(z), (z.stride(0) if z.size(0) > 1 else max(k, z.stride(0))) if ldz is None else int(ldz),
+                                                   None if null_epilogue else ctypes.cast(ctypes.pointer(ep), ctypes.c_void_p), _stream(y.device))
+    if check:
+        _check(st, "fusedMM_csr_rows16_epilogue_hip")
+    return st
+
+
+def spmm_rows16_epilogue(rowptr, col, col_scale, y, row_scale=None, self_scale=None, bias=None, relu: bool = False, order=None, out=None):
+    """out[i] = round16(act(row_scale[i] * (sum_e col_scale[col[e]] * y[col[e]] + self_scale[i] * y[i]) + bias)) of a bf16 / fp16 `y`
+    [n, k] on the 16-bit row kernel (fusedMM_csr_rows16_epilogue_hip): every table is float32 and optional (`col_scale` None: unit
+    weights; `self_scale` needs a square operand).  The operand checks of spmm_rows16 and the tables' lengths, dtypes and devices are
+    checked BEFORE the call."""
+    if col_scale is None:
+        rowptr, col, _, order, out, _ = _rows16_operands(rowptr, col, None, False, y, order, out)
+    else:
+        rowptr, col, col_scale, order, out, _ = _rows16_operands(rowptr, col, col_scale, True, y, order, out)
+    m, n, k = rowptr.numel() - 1, y.size(0), y.size(1)
+    tables = {}
+    for name, t, length in (("row_scale", row_scale, m), ("self_scale", self_scale, m), ("bias", bias, k)):
+        if t is not None:
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"isplib_amd: `{name}` must be a float32 GPU tensor")
+            t = _dev(t, name, torch.float32)
+            if t.numel() != length or t.device != y.device:
+                raise ValueError(f"isplib_amd: `{name}` must hold {length} float32 values on y's device")
+        tables[name] = t
+    if self_scale is not None and m != n:
+        raise ValueError(f"isplib_amd: `self_scale` needs a square operand (the self row of i is y[i]); m={m}, n={n}")
+    fusedMM_csr_rows16_epilogue_hip(rowptr, col, col_scale, order, y, out, tables["row_scale"], tables["self_scale"], tables["bias"], relu)
+    return out
+
+
+def masked_colsum16(dz: torch.Tensor, out: Optional[torch.Tensor], want_g: bool = True, want_bias: bool = True):
+    """(g, grad_bias) of isplib_masked_colsum16_hip for bf16 / fp16 `dz` [n, k] (row-strided views keep their pitch): g = dz where
+    out > 0 else +0 (a bit select; `out` None: no mask), grad_bias = g.float().sum(0) in fp32.  Either may be left out."""
+    if not isinstance(dz, torch.Tensor) or not dz.is_cuda or dz.dim() != 2 or dz.dtype not in HALF_DTYPES:
+        raise TypeError("isplib_amd: `dz` must be a 2-D bfloat16 / float16 GPU tensor")
+    n, k = dz.shape
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != dz.dtype or out.device != dz.device or tuple(out.shape) != (n, k)):
+        raise ValueError("isplib_amd: `out` must have dz's shape, dtype and device")
+    pitches = []
+    for name, t in (("dz", dz), ("out", out)):
+        if t is not None and k > 0:
+            ld = t.stride(0) if n > 1 else max(k, t.stride(0))
+            if t.stride(1) != 1 or ld < k or ld % 2 or t.data_ptr() & 3:
+                raise ValueError(f"isplib_amd: `{name}` must have unit inner stride, an even pitch >= k and a 4-byte aligned base")
+            pitches.append(ld)
+    if k % 2:
+        raise ValueError("isplib_amd: k must be even")
+    g = torch.empty((n, k), dtype=dz.dtype, device=dz.device) if want_g else None
+    gb = torch.empty(k, dtype=torch.float32, device=dz.device) if want_bias else None
+    with torch.cuda.device(dz.device):
+        ws = lib().isplib_masked_colsum16_workspace_bytes(n, k)
+        work = torch.empty(max(ws, 256), dtype=torch.uint8, device=dz.device)
+        _check(lib().isplib_masked_colsum16_hip(HALF_DTYPES[dz.dtype], n, k, _ptr(dz), pitches[0] if pitches else k, _ptr(out),
+                                                pitches[1] if len(pitches) > 1 else k, _ptr(g), k, _ptr(gb), _ptr(work), work.numel(),
+                                                _stream(dz.device)), "isplib_masked_colsum16_hip")
+    return g, gb
 
 
 def isplib_sddmm_csr_rows16_hip(rowptr, col, order, y, g, dval, mean: bool = False, check: bool = True, dtype=None, k=None, ldy=None,

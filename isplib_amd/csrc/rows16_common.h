@@ -1,5 +1,6 @@
-// rows16_common.h -- what the 16-bit row kernels (spmm_rows16.hip: sum / mean in three weight modes, spmm_rows16_minmax.hip: max /
-// min with or without positions) decide alike, written once.  DESIGN.md 4.2a describes the mapping.
+// rows16_common.h -- what the 16-bit row kernels (spmm_rows16.hip: sum / mean in three weight modes, spmm_rows16_epilogue.hip: the sum
+// with an epilogue on the finished row, spmm_rows16_minmax.hip: max / min with or without positions) decide alike, written once.
+// DESIGN.md 4.2a describes the mapping; the summing kernels' edge step is rows16_sum.h.
 //   host    rows16_check     the refusals of every entry of the family and the argument fields all its kernels share
 //           rows16_by_width  the slot width / chunks per lane by K
 //           rows16_launch    the launch geometry and its two refusals

@@ -16,6 +16,7 @@
 // from an n-entry table (col_scale[indx[p]], fusedMM_csr_rows16_colscale_hip).  W_COL differs from W_EDGE only in where a lane's
 // factor of its edge of the 64-edge batch comes from -- one 4-byte load that depends on the index load instead of one that does
 // not -- so it computes, bit for bit, what W_EDGE computes on val[p] = col_scale[indx[p]], without the nnz-long weight stream.
+// The modes and the edge step (rows16_step) are in rows16_sum.h, shared with spmm_rows16_epilogue.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -24,6 +25,7 @@
 #include "gather.h"
 #include "half16.h"
 #include "rows16_common.h"
+#include "rows16_sum.h"
 
 namespace isplib {
 
@@ -42,54 +44,6 @@ struct Rows16Args {
    unsigned sbytes;             // W_COL: n*4, the size of the table's descriptor (a column id outside [0, n) reads 0)
    const int32_t *row_order;    // position -> row, null = the identity
 };
-
-enum { W_UNIT = 0, W_EDGE = 1, W_COL = 2 };
-
-// gathers issued back to back per slot, and the occupancy the allocator is held to -- the fp32 plain kernel's 8 waves per SIMD
-// (gather.h, min_waves_of).  Four VGPRs per gather in flight as there, but eight accumulators per chunk instead of four and eight
-// widened values: at U = 8 the unit-weight bf16 kernels spill (12-28 bytes of scratch per lane), at U = 6 every single-chunk
-// kernel fits 64 VGPRs without scratch (DESIGN.md 4.2a has the counts)
-template <int NCH> constexpr int rows16_unroll() { return NCH > 1 ? 4 : 6; }
-template <int NCH> constexpr int rows16_min_blocks() { return NCH == 1 ? 8 : 1; }
-
-// buf_step (gather.h) at eight 16-bit columns per 16-byte gather: UU gathers per slot back to back for the edges [s, s + G*UU) of
-// the current 64-edge batch; their values are summed among themselves first and enter the running sum as ONE term
-template <int ELT, bool HAS_VAL, int LPR, int NCH, int UU>
-__device__ __forceinline__ void rows16_step(const __amdgpu_buffer_rsrc_t rsrc, unsigned off_l, float v_l, int s, int g,
-                                            const unsigned (&cbyte)[NCH], const unsigned (&poison)[NCH], float (&acc)[NCH][8]) {
-   constexpr int G = 64 / LPR;
-   v4i_t t[UU][NCH];
-   float vv[UU];
-#pragma unroll
-   for (int u = 0; u < UU; u++) {
-      const int ei = (s + u * G + g) & 63;
-      const unsigned off = (unsigned)__shfl((int)off_l, ei);
-      if (HAS_VAL) vv[u] = __shfl(v_l, ei);
-#pragma unroll
-      for (int j = 0; j < NCH; j++) {
-         // masked edge: off = BUF_OOB, + cbyte (< 2^25) cannot wrap; masked column: OR-ed past the limit
-         const unsigned o = (off + cbyte[j]) | poison[j];
-         t[u][j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)o, 0, 0);
-      }
-   }
-#pragma unroll
-   for (int j = 0; j < NCH; j++) {
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-         float lo, hi;
-         widen2<ELT>((unsigned)t[0][j][q], lo, hi);
-         float p0 = HAS_VAL ? vv[0] * lo : lo, p1 = HAS_VAL ? vv[0] * hi : hi;
-#pragma unroll
-         for (int u = 1; u < UU; u++) {
-            widen2<ELT>((unsigned)t[u][j][q], lo, hi);
-            p0 = HAS_VAL ? fmaf(vv[u], lo, p0) : p0 + lo;
-            p1 = HAS_VAL ? fmaf(vv[u], hi, p1) : p1 + hi;
-         }
-         acc[j][2 * q] += p0;
-         acc[j][2 * q + 1] += p1;
-      }
-   }
-}
 
 // one wave's edges [rb, re) on rows16_batches (rows16_common.h): the weight of an edge by mode, rows16_step per step
 template <int ELT, int WM, int LPR, int NCH, int U>

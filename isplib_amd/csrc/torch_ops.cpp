@@ -999,8 +999,115 @@ class GcnNormSpmm : public torch::autograd::Function<GcnNormSpmm> {
    }
 };
 
+// ---- the same layer for a 16-bit `mat` on the 16-bit row kernel (fusedMM_csr_rows16_epilogue_hip) ----------
+// One call of the entry with col_scale = self_scale = row_scale = dinv on (ptr, idx): act(D^-1/2 (A + I) D^-1/2 mat + bias), mat as it
+// lies (rows16_call's preparation), the finished fp32 row rounded once.  Undefined when the family does not take the operand.
+static Tensor gcn_rows16(const Tensor &ptr, const Tensor &idx, const Tensor &mat, const Plan &row_plan, const Tensor &dinv, const Tensor &bias32,
+                         bool relu) {
+   const int64_t M = ptr.numel() - 1, N = mat.size(0), K = mat.size(1), nnz = idx.numel();
+   TORCH_CHECK(M == N && dinv.numel() == N, "isplib: gcn_norm_spmm needs a square graph, [N, K] features and one `dinv` entry per row");
+   TORCH_CHECK(ptr.device() == mat.device() && idx.device() == mat.device() && dinv.device() == mat.device(),
+               "isplib: gcn_norm_spmm needs its operands on one device");
+   c10::DeviceGuard guard(mat.device());
+   const Rows16Call c = rows16_call(ptr, idx, dinv, false, mat, row_plan);
+   if (!c.served) return Tensor();
+   const Tensor bs = bias32.defined() ? bias32.contiguous() : Tensor();
+   if (bs.defined()) TORCH_CHECK(bs.numel() == K && bs.scalar_type() == at::kFloat && bs.device() == mat.device(), "isplib: `bias` must have K entries");
+   Tensor out = at::empty({M, K}, c.mat.options());
+   isplib_epilogue16 ep;
+   ep.row_scale = c.weight;
+   ep.self_scale = c.weight;
+   ep.bias = bs.defined() ? bs.data_ptr<float>() : nullptr;
+   ep.relu = relu ? 1 : 0;
+   const int st = fusedMM_csr_rows16_epilogue_hip(c.dtype, M, N, K, nnz, c.weight, c.idx, c.ptr, c.ptr + 1, c.order, c.mat.data_ptr(), c.ldy,
+                                                  out.data_ptr(), K, &ep, current_stream(c.mat));
+   check_status(st, "fusedMM_csr_rows16_epilogue_hip");
+   return out;
+}
+
+// whether gcn_rows16 would serve `mat` (rows16_call's test, without preparing anything)
+static bool gcn_rows16_serves(const Tensor &rowptr, const Tensor &mat) {
+   if (!is_half(mat) || !mat.is_cuda() || mat.dim() != 2 || rowptr.dim() != 1 || rowptr.numel() - 1 != mat.size(0)) return false;
+   const int64_t N = mat.size(0), K = mat.size(1);
+   return N > 0 && K > 0 && isplib_rows16_serves(N, K, K, K);      // (packed is always possible: the pitch test of the view is rows16_call's)
+}
+
+static Plan index_order_rows16_plan(const Tensor &like) {
+   return Plan{at::empty({0}, like.options().dtype(at::kInt)), at::full({1}, 16, at::TensorOptions().dtype(at::kInt))};
+}
+
+// No fp32 [N, K] tensor in either direction: the forward allocates `out`, the backward g = dZ . [out > 0] (a bit select on the saved
+// 16-bit output, isplib_masked_colsum16_hip; without ReLU g is dZ itself) and dX.  The mask is taken from the ROUNDED output the caller
+// saw -- what a separate 16-bit relu would do: a sum that is positive in fp32 but rounds to 0 is masked.
+class GcnNormSpmm16 : public torch::autograd::Function<GcnNormSpmm16> {
+ public:
+   static variable_list forward(AutogradContext *ctx, Variable rowptr, Variable col, Variable mat, Variable dinv,
+                                optional<Variable> opt_colptr, optional<Variable> opt_row_t, Plan plan, Plan plan_t,
+                                optional<Variable> opt_bias, bool relu) {
+      check_index(rowptr, "rowptr"); check_index(col, "col"); check_feature(mat, "mat"); check_float(dinv, "dinv");
+      const Tensor bias = or_undef(opt_bias);
+      if (bias.defined()) check_feature(bias, "bias");
+      const Tensor bias32 = bias.defined() && is_half(bias) ? bias.to(at::kFloat) : bias;      // K elements
+      Tensor out = gcn_rows16(rowptr, col, mat, plan, dinv, bias32, relu);
+      TORCH_CHECK(out.defined(), "isplib: gcn_norm_spmm: the 16-bit row kernel does not serve this operand");
+      ctx->saved_data["relu"] = relu;
+      ctx->saved_data["plan_t"] = plan_t;
+      ctx->saved_data["bias_edge"] = (int64_t)(4 + (present(opt_colptr) ? 1 : 0) + (present(opt_row_t) ? 1 : 0));
+      ctx->saved_data["has_bias"] = bias.defined();
+      ctx->saved_data["bias_half"] = bias.defined() && is_half(bias);
+      ctx->save_for_backward({rowptr, col, dinv, or_undef(opt_colptr), or_undef(opt_row_t), relu ? out : Tensor()});
+      return {out};
+   }
+
+   static variable_list backward(AutogradContext *ctx, variable_list grad_outs) {
+      auto saved = ctx->get_saved_variables();
+      auto rowptr = saved[0], col = saved[1], dinv = saved[2], colptr = saved[3], row_t = saved[4], out = saved[5];
+      auto grad_bias = Variable(), grad_mat = Variable();
+      const bool need_bias = ctx->saved_data["has_bias"].toBool() && ctx->needs_input_grad(ctx->saved_data["bias_edge"].toInt());
+      const bool need_mat = ctx->needs_input_grad(2);
+      if (need_bias || need_mat) {
+         TORCH_CHECK(is_half(grad_outs[0]) && grad_outs[0].dim() == 2, "isplib: gcn_norm_spmm: `grad_out` must have the output's 16-bit dtype");
+         const Tensor dz = packed16(grad_outs[0]);
+         c10::DeviceGuard guard(dz.device());
+         Plan plan_t = ctx->saved_data["plan_t"].toTensorVector();
+         if (need_mat && (!colptr.defined() || !row_t.defined())) {
+            auto t = build_transpose(rowptr, col, Tensor(), rowptr.numel() - 1, false);
+            colptr = t.colptr; row_t = t.row_t; plan_t.clear();
+         }
+         if (!is_rows16_plan(plan_t)) plan_t = index_order_rows16_plan(dz);
+         const int64_t N = dz.size(0), K = dz.size(1);
+         const Tensor mask = ctx->saved_data["relu"].toBool() ? packed16(out) : Tensor();
+         Tensor g = dz, gb32;                                               // no ReLU: g is dZ itself, no pass writes it
+         if (mask.defined() && need_mat) g = at::empty({N, K}, dz.options());
+         if (need_bias) gb32 = at::empty({K}, dz.options().dtype(at::kFloat));
+         if (need_bias || (mask.defined() && need_mat)) {
+            const size_t ws = isplib_masked_colsum16_workspace_bytes(N, K);
+            Tensor work = at::empty({(int64_t)ws}, dz.options().dtype(at::kByte));
+            const int st = isplib_masked_colsum16_hip(dz.scalar_type() == at::kBFloat16 ? ISPLIB_DTYPE_BF16 : ISPLIB_DTYPE_F16, N, K, dz.data_ptr(), K,
+                                                      mask.defined() ? mask.data_ptr() : nullptr, K,
+                                                      mask.defined() && need_mat ? g.data_ptr() : nullptr, K,
+                                                      need_bias ? gb32.data_ptr<float>() : nullptr, work.data_ptr(), ws, current_stream(dz));
+            check_status(st, "isplib_masked_colsum16_hip");
+         }
+         if (need_bias) grad_bias = ctx->saved_data["bias_half"].toBool() ? gb32.to(dz.scalar_type()) : gb32;      // rounded once
+         if (need_mat) {
+            grad_mat = gcn_rows16(colptr, row_t, g, plan_t, dinv, Tensor(), false);      // D (A^T + I) D g
+            TORCH_CHECK(grad_mat.defined(), "isplib: gcn_norm_spmm: the 16-bit row kernel does not serve this gradient");
+         }
+      }
+      return {Variable(), Variable(), grad_mat, Variable(), Variable(), Variable(), Variable(), Variable(), grad_bias, Variable()};
+   }
+};
+
 Tensor gcn_norm_spmm(Tensor rowptr, Tensor col, Tensor mat, Tensor dinv, optional<Tensor> colptr, optional<Tensor> row_t,
                      Plan plan, Plan plan_t, optional<Tensor> bias, bool relu) {
+   // a 16-bit `mat` on a 16-bit row plan (the plug-in's rows16_gcn_route said "rows16"): the 16-bit kernel where it serves the operand,
+   // else the conversion route -- nothing raises.  Any other plan with a 16-bit `mat` is refused as it always was (check_float)
+   if (is_half(mat) && is_rows16_plan(plan)) {
+      if (gcn_rows16_serves(rowptr, mat)) return GcnNormSpmm16::apply(rowptr, col, mat, dinv, colptr, row_t, plan, plan_t, bias, relu)[0];
+      const optional<Tensor> bias32 = present(bias) && is_half(*bias) ? optional<Tensor>(bias->to(at::kFloat)) : bias;
+      return GcnNormSpmm::apply(rowptr, col, mat.to(at::kFloat), dinv, colptr, row_t, plan, plan_t, bias32, relu)[0].to(mat.scalar_type());
+   }
    return GcnNormSpmm::apply(rowptr, col, mat, dinv, colptr, row_t, plan, plan_t, bias, relu)[0];
 }
 

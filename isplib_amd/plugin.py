@@ -25,7 +25,8 @@ sum / mean off the stream schedule; ISPLIB_STREAM_GEOM=streams:slices:chunk forc
 ISPLIB_HALF=auto|native|convert picks the route of bf16 / fp16 features (half_route; rows16_route for calls on the plain kernel);
 ISPLIB_HALF_MINMAX=convert|native|auto does the same for max / min (rows16_minmax_route), ISPLIB_HALF_MEAN_BW=convert|native|auto
 for the backward of a 16-bit `mean` on an unweighted graph (rows16_mean_bw_route), ISPLIB_HALF_DA=convert|native|auto for the value
-gradient of a 16-bit sum / mean (rows16_da_route); all three default to convert;
+gradient of a 16-bit sum / mean (rows16_da_route), ISPLIB_HALF_GCN=convert|native|auto for gcn_norm_matmul on 16-bit features
+(rows16_gcn_route; unset: such a call raises, as it always did); the first three default to convert;
 ISPLIB_TUNE_FILE names a tuning table to load at import; ISPLIB_DEBUG=1 prints per-operator device times.
 """
 from __future__ import annotations
@@ -371,6 +372,21 @@ def rows16_da_route(dtype, k: int, pitch: int, n: int, ordered: bool = False, mo
     return _rows16_gate(dtype, mode, "ISPLIB_HALF_DA", n, k, pitch, lambda cabi, ld: cabi.sddmm_rows16_native_pays(n, ld, bool(ordered)))
 
 
+def rows16_gcn_route(dtype, k: int, pitch: int, n: int, ordered: bool = False, mode: Optional[str] = None) -> str:
+    """Which way gcn_norm_matmul with 16-bit features goes once ISPLIB_HALF_GCN is set: "rows16" (the 16-bit row kernel with the fused
+    epilogue, fusedMM_csr_rows16_epilogue_hip, forward and backward: X is gathered as it lies, D^-1/2 per gathered row, self loop, left
+    D^-1/2, bias and ReLU on the finished fp32 row, rounded once -- no fp32 [N, K] tensor in either direction) or "convert"
+    (`x.float()` -> the fp32 layer -> `.to(dtype)`).  A pure function -- no device, no library call:
+      * rows16 needs bf16 / fp16 and X's shape, [n, k] at its own row pitch or, failing that, packed, inside the entry's domain
+        (cabi.rows16_serves);
+      * `mode` is ISPLIB_HALF_GCN (None: read from the environment; unset counts as "convert" here -- gcn_norm_matmul itself raises
+        before it asks -- and ISPLIB_HALF=convert wins over it): "convert" always converts, "native" takes the kernel wherever the
+        above holds, "auto" only in the classes -- (X beyond 256 MiB or not) x `ordered` (the rows come in a community order) -- where
+        every native run measured faster than every run of the conversion route (cabi.rows16_gcn_native_pays,
+        profiles/rows16_gcn_ab.txt).  Nothing raises."""
+    return _rows16_gate(dtype, mode, "ISPLIB_HALF_GCN", n, k, pitch, lambda cabi, ld: cabi.rows16_gcn_native_pays(n, ld, bool(ordered)))
+
+
 _ROWS16_MARK = torch.tensor([16], dtype=torch.int32)      # second tensor of a 16-bit row plan (torch_ops.cpp: is_rows16_plan)
 _ROWS16_DA_MARK = torch.tensor([0xDA], dtype=torch.int32)  # third tensor of a forward plan whose dA runs in 16 bits (is_rows16_da_plan)
 
@@ -569,9 +585,35 @@ def gcn_norm_matmul(src, other: torch.Tensor, bias: Optional[torch.Tensor] = Non
     and ReLU are applied inside the fold kernel (include/isplib_hip.h: isplib_epilogue).  This is what a
     GCNConv(normalize=True) layer aggregates (callers: tests/dist/gcn/pyg-sparse.py:61-62); differentiable in
     `other` and `bias`.  Not part of the reference's surface."""
-    if not other.is_cuda or other.dtype != torch.float32 or other.dim() != 2:
+    half = isinstance(other, torch.Tensor) and other.dtype in HALF_DTYPES and os.environ.get("ISPLIB_HALF_GCN") is not None
+    if not other.is_cuda or (other.dtype != torch.float32 and not half) or other.dim() != 2:
         raise RuntimeError("isplib_amd: gcn_norm_matmul needs a float32 GPU matrix [N, K] -- there is no CPU path")
     s = _storage_of(src, other)
+    if half:
+        # bf16 / fp16 features, opt-in (ISPLIB_HALF_GCN): the 16-bit row kernel with the fused epilogue where rows16_gcn_route says so
+        # (the plan for A, and for A^T when a gradient can be asked for), else the conversion route
+        if s._value is not None:
+            raise ValueError("gcn_norm_matmul is defined for unweighted graphs (value=None)")
+        if s._sparse_sizes[0] != s._sparse_sizes[1]:
+            raise ValueError("gcn_norm_matmul needs a square adjacency")
+        n, k = other.size(0), other.size(1)
+        pitch = other.stride(0) if n > 1 and other.stride(1) == 1 else k
+        plan = _rows16_plan_where(lambda ordered: rows16_gcn_route(other.dtype, k, pitch, n, ordered) == "rows16", s, False, k, other.device)
+        if plan is None:
+            bias32 = bias.float() if bias is not None and bias.dtype in HALF_DTYPES else bias
+            out = gcn_norm_matmul(src, other.float(), bias32, relu)
+            s._last_schedule = ("convert",)
+            return out.to(other.dtype)
+        colptr = row_t = None
+        plan_t = []
+        if torch.is_grad_enabled() and (other.requires_grad or (bias is not None and bias.requires_grad)):
+            colptr, row_t = s.colptr(), s.row_t()
+            # dZ: [n, k] packed; the order of A^T's rows is put to the same route, and where it says no the backward keeps index order
+            plan_t = _rows16_plan_where(lambda ordered: rows16_gcn_route(other.dtype, k, k, n, ordered) == "rows16", s, True, k, other.device)
+            if plan_t is None:
+                plan_t = [torch.empty(0, dtype=torch.int32, device=other.device), _ROWS16_MARK]
+        s._last_schedule = ("rows16gcn",) + (("ordered",) if plan[0].numel() > 0 else ())
+        return torch.ops.isplib.gcn_norm_spmm(s._rowptr, s._col, other, s.gcn_dinv(), colptr, row_t, plan, plan_t, bias, relu)
     if s._value is not None:
         raise ValueError("gcn_norm_matmul is defined for unweighted graphs (value=None)")
     if s._sparse_sizes[0] != s._sparse_sizes[1]:

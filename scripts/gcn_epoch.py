@@ -6,7 +6,10 @@ report :114-125).  PyG is not in this image, so GCNConv(cached=True, normalize=F
     out = matmul(adj_t, x @ W) + b                       (aggregate AFTER the linear layer: K = 32, then C)
 with `matmul` = isplib_amd.matmul, i.e. what torch_sparse.matmul becomes after iSpLibPlugin.patch_pyg().
 
-    python scripts/gcn_epoch.py [--epochs 10] [--scale 1.0] [--hidden 32] [--model gcn|sage|gin] [--aggr sum|mean|max]
+    python scripts/gcn_epoch.py [--epochs 10] [--scale 1.0] [--hidden 32] [--model gcn|sage|gin] [--aggr sum|mean|max] [--dtype fp32|bf16|fp16]
+
+--dtype bf16 / fp16 (--model gcn, 1 GPU) holds the features and the model in 16 bits; the loss is taken in fp32.  With --normalize the
+fused layer then needs ISPLIB_HALF_GCN=native|convert|auto in the environment (unset, gcn_norm_matmul refuses 16-bit features).
 
 --model sage also runs on the 1-D row partition (N > 1 ranks: DistGraph.matmul(x, aggr) with autograd for sum / mean / max / min).
 --model sage / gin restate the other two callers (tests/cpu/graphSAGE-sparse.py:65-78, tests/cpu/gin-sparse.py:59-78):
@@ -55,10 +58,10 @@ class Net(torch.nn.Module):
             import isplib_amd
             x = isplib_amd.gcn_norm_matmul(adj_t, self.conv1.lin(x), self.conv1.bias, relu=True)
             x = F.dropout(x, training=self.training)
-            return F.log_softmax(isplib_amd.gcn_norm_matmul(adj_t, self.conv2.lin(x), self.conv2.bias), dim=1)
+            return F.log_softmax(isplib_amd.gcn_norm_matmul(adj_t, self.conv2.lin(x), self.conv2.bias).float(), dim=1)
         x = F.relu(self.conv1(x, adj_t, matmul))
         x = F.dropout(x, training=self.training)
-        return F.log_softmax(self.conv2(x, adj_t, matmul), dim=1)
+        return F.log_softmax(self.conv2(x, adj_t, matmul).float(), dim=1)      # (--dtype: the loss in fp32; a no-op on fp32)
 
 
 class SAGEConv(torch.nn.Module):
@@ -120,6 +123,7 @@ def main():
     p.add_argument("--narrow", action="store_true", help="GCN: aggregate on the narrower side of each linear layer")
     p.add_argument("--workload", choices=("reddit", "cora"), default="reddit",
                    help="graph shape; cora (N=2,708, config 1) is launch-bound: use --hipgraph; pass --features 1433 --classes 7")
+    p.add_argument("--dtype", choices=("fp32", "bf16", "fp16"), default="fp32", help="features and model in 16 bits (--model gcn, 1 GPU)")
     p.add_argument("--hipgraph", action="store_true",
                    help="capture the whole epoch (2 forwards, backward, Adam) in one hipGraph and replay it (1 GPU)")
     a = p.parse_args()
@@ -135,9 +139,14 @@ def main():
         dist.init_process_group(backend, **({"device_id": dev} if backend == "nccl" else {}))
     import isplib_amd
     from isplib_amd import synth
+    dtype = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[a.dtype]
+    if a.dtype != "fp32" and (a.model != "gcn" or world > 1):
+        raise SystemExit("--dtype bf16 / fp16: --model gcn on one GPU only")
+    if a.dtype != "fp32" and a.normalize and os.environ.get("ISPLIB_HALF_GCN") is None:
+        raise SystemExit("--dtype bf16 / fp16 with --normalize: set ISPLIB_HALF_GCN=native|convert|auto")
     rowptr, col, n = synth.dataset_like(a.workload, device=dev, scale=a.scale)
     nnz = col.numel()
-    x = synth.features(n, a.features, device=dev)
+    x = synth.features(n, a.features, device=dev).to(dtype)
     y = torch.randint(0, a.classes, (n,), device=dev)
     train_mask = torch.rand(n, device=dev) < 0.66
     n_train = int(train_mask.sum())
@@ -148,7 +157,7 @@ def main():
     elif a.model == "gin":
         model = GINNet(a.features, a.hidden, a.classes).to(dev)
     else:
-        model = Net(a.features, a.hidden, a.classes, a.normalize and world == 1, a.narrow).to(dev)   # same seed on every rank
+        model = Net(a.features, a.hidden, a.classes, a.normalize and world == 1, a.narrow).to(dev).to(dtype)   # same seed on every rank
     opt = torch.optim.Adam(model.parameters(), lr=0.01, weight_decay=5e-4, capturable=a.hipgraph)
     if a.hipgraph and world > 1:
         raise SystemExit("--hipgraph: single GPU only")
@@ -236,6 +245,7 @@ def main():
                           "epochs": a.epochs, "epoch_ms_mean": statistics.mean(times) * 1e3,
                           "epoch_ms_std": statistics.pstdev(times) * 1e3, "first_loss": losses[0],
                           "last_loss": losses[-1], "train_acc": acc, "spmm_calls_per_epoch": 6 if a.model == "gcn" else 5, "n_gpus": world, "normalize": bool(a.normalize and world == 1),
+                          "dtype": a.dtype, "half_gcn": os.environ.get("ISPLIB_HALF_GCN") if a.dtype != "fp32" else None,
                           "backend": backend if world > 1 else None}))
     if world > 1:
         dist.barrier()
