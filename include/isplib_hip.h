@@ -88,6 +88,7 @@ const char *isplib_hip_last_error(void);   /* thread-local, "" if none */
 #define ISPLIB_STREAM_MINMAX_BYTES_END 0x80000000u  /* 2 GiB: lanes past column k of the max / min stream kernel carry 2^31 */
 #define ISPLIB_K_MIN                   4            /* every entry that takes a plan; narrower operands: fusedMM_csr_hip */
 #define ISPLIB_SDDMM_TASKS_K_MAX       1024         /* isplib_sddmm_csr_tasks_hip holds g[row, :] in registers */
+#define ISPLIB_ATTENTION_K_MAX         512          /* the attention entries hold a row in registers, two chunks per lane */
 
 /* n rows of ldy floats take at most `bytes` bytes (exact for any operands: no product is formed) */
 static inline int isplib_rows_within(int64_t n, int64_t ldy, uint64_t bytes) { return n <= 0 || ldy <= (int64_t)(bytes / 4 / (uint64_t)n); }
@@ -688,6 +689,46 @@ static inline int isplib_sddmm_rows16_native_pays(int64_t n, int64_t ldy, int or
    return beyond ? 1 : 0;
 }
 int    isplib_sddmm_rows16_auto(int64_t n, int64_t ldy, int ordered);             /* the same rule as a symbol */
+/*
+ * Row-softmax attention aggregation over the stored entries e = (i, j) of a CSR matrix A [m, n], forward and backward, fp32.
+ * With x: m x ldx, y: n x ldy (k columns each) and a scalar `scale` = p:
+ *   s_e  = p <x_i, y_j>       a_e = exp(s_e - lse_i),  lse_i = log sum_{e in row i} exp(s_e)       z_i = sum_e a_e y_j
+ * and, for g = dL/dz (m x ldg),
+ *   D_i  = <g_i, z_i>         t_e = <g_i, y_j>         ds_e = a_e (t_e - D_i)
+ *   dx_i = p sum_e ds_e y_j   dy_j = sum_{e -> j} (a_e g_i + p ds_e x_i).
+ * Stored values of A are not read (attention replaces them); every stored entry is its own edge, so a duplicate counts twice; the
+ * column order inside a row is free.  An empty row has z_i = 0, lse_i = -inf, dx_i = 0 and D_i = 0; a column no entry points at has
+ * dy_j = 0.  The softmax is computed relative to a running row maximum, so no score overflows: a row of one entry returns y_j bit
+ * for bit whatever its score.  A +inf score, or a NaN anywhere in a row's operands, makes that row NaN and no other.
+ *   isplib_attention_csr_hip      writes z (m x ldz) and lse (m).
+ *   isplib_attention_bw_rows_hip  reads x, y, g, z and lse, writes dx (m x lddx) and dsum (m: D_i, which the next entry reads).
+ *   isplib_attention_bw_cols_hip  runs on the transposed structure (colb / cole: n column ranges into row_t, the row ids of the
+ *                                 entries in column-major order -- no permutation is needed, nothing per edge was stored); reads
+ *                                 x, y, g, lse and dsum, writes dy (n x lddy).
+ * Nothing is kept per edge: the backward recomputes a_e from lse_i.  Outputs are write-only and every element of every row is
+ * written (empty rows included), nothing between the rows of a pitched output.  One wave per row (per column), no atomics, a fixed
+ * order of operations: two launches give equal bits.  The entries neither allocate nor synchronise.
+ * Domain: isplib_attention_serves(rows_gathered, k, ld) for every GATHERED operand (y with n rows in the first two entries; x and
+ * g with m rows in the third): 1 <= k <= 512 (a row sits in registers, two 16-byte chunks per lane), ld >= k, rows_gathered < 2^31
+ * (32-bit row ids times the pitch) and the operand inside one buffer descriptor.  Outside the domain: ISPLIB_NO_OPT_IMPL.  A
+ * negative dimension, a null operand or a pitch of a row-resident operand or output below k: ISPLIB_FAIL.  All refusals come before
+ * any launch.  m == 0 or k == 0 (n == 0 or k == 0 in the third entry) succeeds without a launch.
+ */
+static inline int isplib_attention_serves(int64_t rows_gathered, int64_t k, int64_t ld) {
+   return k >= 1 && k <= ISPLIB_ATTENTION_K_MAX && ld >= k && rows_gathered < (1LL << 31) && isplib_dense_in_descriptor(rows_gathered, ld);
+}
+int    isplib_attention_domain(int64_t rows_gathered, int64_t k, int64_t ld);     /* isplib_attention_serves as a symbol */
+int    isplib_attention_csr_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                                const int64_t *pntre, const float *x, int64_t ldx, const float *y, int64_t ldy, float scale,
+                                float *z, int64_t ldz, float *lse /* m */, void *stream);
+int    isplib_attention_bw_rows_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                                    const int64_t *pntre, const float *x, int64_t ldx, const float *y, int64_t ldy, float scale,
+                                    const float *g, int64_t ldg, const float *z, int64_t ldz, const float *lse, float *dx,
+                                    int64_t lddx, float *dsum /* m */, void *stream);
+int    isplib_attention_bw_cols_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t, const int64_t *colb,
+                                    const int64_t *cole, const float *x, int64_t ldx, const float *y, int64_t ldy, float scale,
+                                    const float *g, int64_t ldg, const float *lse, const float *dsum, float *dy, int64_t lddy,
+                                    void *stream);
 /*
  * Staged column panels (sum / mean on 64-column slots only).  What a gather of a 128-byte line costs depends on the line's
  * ADDRESS: profiles/line_classes.txt (scripts/ubench/line_classes.hip) is the table, DESIGN.md section 5 reads it.  Before the

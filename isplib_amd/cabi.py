@@ -117,6 +117,16 @@ def sddmm_rows16_native_pays(n: int, ldy: int, ordered: bool) -> bool:
     return bool(n > 0 and ldy > 0 and n * ldy * 2 > (256 << 20))
 
 
+ATTENTION_K_MAX = 512                   # the attention entries hold a row in registers, two 16-byte chunks per lane
+
+
+def attention_serves(rows_gathered: int, k: int, ld: int) -> bool:
+    """isplib_attention_serves of the header: the attention entries (isplib_attention_csr_hip and its two backward entries) gather
+    `rows_gathered` rows of k floats at leading dimension ld through one buffer descriptor."""
+    return (1 <= k <= ATTENTION_K_MAX and ld >= k and rows_gathered < 2 ** 31 and
+            (rows_gathered <= 0 or rows_gathered * ld * 4 <= DENSE_BYTES_MAX))
+
+
 def owner_exchange_serves(m: int, k: int, world: int, cuts) -> bool:
     """isplib_owner_exchange_serves of the header: m x k winners split for `world` owners at the row boundaries `cuts`."""
     if not 1 <= world <= OWNER_WORLD_MAX or m < 0 or k < 0 or m * k >= MINMAX_BW_PAIRS_END:
@@ -166,6 +176,7 @@ EXPORTS = (
     "fusedMM_csr_rows16_colscale_hip", "isplib_rows16_colscale_auto",
     "fusedMM_csr_rows16_epilogue_hip", "isplib_rows16_gcn_auto", "isplib_masked_colsum16_hip", "isplib_masked_colsum16_workspace_bytes",
     "isplib_sddmm_csr_rows16_hip", "isplib_sddmm_rows16_auto",
+    "isplib_attention_csr_hip", "isplib_attention_bw_rows_hip", "isplib_attention_bw_cols_hip", "isplib_attention_domain",
 )
 
 # include/isplib_hip_experimental.h (libisplib_hip_exp.so): forms measured slower than the defaults; tests and experiment scripts only
@@ -400,6 +411,16 @@ def lib() -> ctypes.CDLL:
         L.isplib_sddmm_csr_rows16_hip.argtypes = [ctypes.c_int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, ctypes.c_int, _vp, _vp]
         L.isplib_sddmm_rows16_auto.restype = ctypes.c_int
         L.isplib_sddmm_rows16_auto.argtypes = [_i64, _i64, ctypes.c_int]
+        L.isplib_attention_domain.restype = ctypes.c_int
+        L.isplib_attention_domain.argtypes = [_i64, _i64, _i64]
+        L.isplib_attention_csr_hip.restype = ctypes.c_int
+        L.isplib_attention_csr_hip.argtypes = [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _vp]
+        L.isplib_attention_bw_rows_hip.restype = ctypes.c_int
+        L.isplib_attention_bw_rows_hip.argtypes = [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _i64, _vp,
+                                                   _vp, _i64, _vp, _vp]
+        L.isplib_attention_bw_cols_hip.restype = ctypes.c_int
+        L.isplib_attention_bw_cols_hip.argtypes = [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _vp, _vp,
+                                                   _i64, _vp]
         _sigs_set = True
     return L
 
@@ -1547,6 +1568,169 @@ def sddmm_rows16(rowptr, col, y, g, mean: bool = False, order=None, out=None):
         if (y.data_ptr() | g.data_ptr()) & 3:
             raise ValueError("isplib_amd: `y` and `g` must be 4-byte aligned")
     isplib_sddmm_csr_rows16_hip(rowptr, col, order, y, g, out, mean)
+    return out
+
+
+def _attn_dense(t, name: str, rows: int, k: Optional[int], what: str) -> int:
+    """One dense operand of the attention entries: 2-D float32 [rows, k] on the GPU with unit inner stride; a row-strided view keeps its
+    pitch (head views of one [N, H*d] tensor go in without a copy).  Returns the pitch in elements."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2:
+        raise ValueError(f"isplib_amd: `{name}` must be a 2-D tensor, got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    if t.dtype != torch.float32:
+        raise TypeError(f"isplib_amd: `{name}` must be float32, got {t.dtype} (the attention operator is fp32 only)")
+    if t.size(0) != rows or (k is not None and t.size(1) != k):
+        raise ValueError(f"isplib_amd: `{name}` must be [{rows}, {'k' if k is None else k}] ({what}), got {tuple(t.shape)}")
+    if t.size(1) > 0 and t.size(0) > 0 and t.stride(1) != 1:
+        raise ValueError(f"isplib_amd: `{name}` must have unit inner stride")
+    ld = t.stride(0) if t.size(0) > 1 else max(t.size(1), t.stride(0))
+    if ld < t.size(1):
+        raise ValueError(f"isplib_amd: the rows of `{name}` (pitch {ld}) must not overlap: k = {t.size(1)}")
+    return int(ld)
+
+
+def _attn_vector(t, name: str, rows: int) -> None:
+    if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.numel() != rows or t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"isplib_amd: `{name}` must be a contiguous float32 tensor of {rows} entries")
+
+
+def _attn_structure(ptr, idx, ptr_name: str, idx_name: str, id_end: int, check: bool):
+    """rowptr / col (or colptr / row_t): 1-D int64; with `check` (two reductions and a synchronisation -- a timed loop over a graph
+    already checked passes check=False) the pointer array ascends from 0 to idx.numel() and every id lies in [0, id_end)."""
+    if not isinstance(ptr, torch.Tensor) or ptr.dim() != 1 or ptr.numel() < 1 or not isinstance(idx, torch.Tensor) or idx.dim() != 1:
+        raise ValueError(f"isplib_amd: `{ptr_name}` (one entry more than it has ranges) and `{idx_name}` must be 1-D tensors")
+    if ptr.dtype != torch.int64 or idx.dtype != torch.int64:
+        raise TypeError(f"isplib_amd: `{ptr_name}` and `{idx_name}` must be int64, got {ptr.dtype} and {idx.dtype}")
+    if check and ptr.is_cuda and idx.is_cuda:
+        if int(ptr[0]) != 0 or int(ptr[-1]) != idx.numel() or bool((ptr[1:] < ptr[:-1]).any()):
+            raise ValueError(f"isplib_amd: `{ptr_name}` must ascend from 0 to {idx_name}.numel()")
+        if idx.numel() > 0 and (int(idx.min()) < 0 or int(idx.max()) >= id_end):
+            raise ValueError(f"isplib_amd: the ids of `{idx_name}` must lie in [0, {id_end}): the gathered operand must hold a row for each")
+    return ptr.contiguous(), idx.contiguous()
+
+
+def _attn_domain(rows_gathered: int, k: int, lds) -> None:
+    for ld in lds:
+        if k > 0 and not attention_serves(rows_gathered, k, ld):
+            raise ValueError(f"isplib_amd: outside the attention entries' domain (isplib_attention_serves: 1 <= k <= {ATTENTION_K_MAX}, "
+                             f"gathered rows < 2^31, rows * pitch * 4 <= 3.5 GiB), got rows={rows_gathered}, k={k}, pitch={ld}")
+
+
+def _attn_scale(scale, k: int) -> float:
+    return float(scale) if scale is not None else (1.0 / float(k) ** 0.5 if k > 0 else 1.0)
+
+
+def attention(rowptr, col, x, y, scale: Optional[float] = None, *, out=None, check: bool = True):
+    """Row-softmax attention aggregation (isplib_attention_csr_hip): over the stored entries e = (i, j) of the CSR structure,
+    s_e = scale <x_i, y_j>, a_e = softmax of s over the row's entries, z_i = sum_e a_e y_j.  Returns (z [m, k], lse [m]); an empty
+    row has z_i = 0 and lse_i = -inf.  `x` [m, k] and `y` [n, k] float32, row-strided views keep their pitch; `scale` None =
+    1 / sqrt(k); `out` = (z, lse) to write in place.  Every operand is checked BEFORE the call -- a mis-shaped one is an out-of-bounds
+    device read (`check`: also the two checks that read the structure on the device)."""
+    if not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1 or rowptr.numel() < 1:
+        raise ValueError("isplib_amd: `rowptr` (m + 1 entries) must be a 1-D tensor")
+    m = rowptr.numel() - 1
+    ldx = _attn_dense(x, "x", m, None, "one row per row of the sparse operand")
+    k = x.size(1)
+    if not isinstance(y, torch.Tensor) or y.dim() != 2:
+        raise ValueError("isplib_amd: `y` must be a 2-D tensor [n, k]")
+    n = y.size(0)
+    ldy = _attn_dense(y, "y", n, k, "x's width")
+    rowptr, col = _attn_structure(rowptr, col, "rowptr", "col", n, check)
+    if out is not None:
+        z, lse = out
+        ldz = _attn_dense(z, "out[0]", m, k, "z")
+        _attn_vector(lse, "out[1]", m)
+    _attn_domain(n, k, (ldy,))
+    _same_gpu((("x", x), ("y", y), ("rowptr", rowptr), ("col", col)) + ((("out[0]", out[0]), ("out[1]", out[1])) if out is not None else ()))
+    if out is None:
+        z = torch.empty((m, k), dtype=torch.float32, device=x.device)
+        lse = torch.empty(m, dtype=torch.float32, device=x.device)
+        ldz = max(k, 1)
+    if m == 0 or k == 0:
+        if k == 0 and m > 0:
+            lse.fill_(float("-inf"))                            # no column, no score: every row is empty
+        return z, lse
+    rp = rowptr.data_ptr()
+    with torch.cuda.device(x.device):
+        st = lib().isplib_attention_csr_hip(m, n, k, col.numel(), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8), _ptr(x), ldx,
+                                            _ptr(y), ldy, _attn_scale(scale, k), _ptr(z), ldz, _ptr(lse), _stream(x.device))
+    _check(st, "isplib_attention_csr_hip")
+    return z, lse
+
+
+def attention_bw_rows(rowptr, col, x, y, g, z, lse, scale: Optional[float] = None, *, out=None, check: bool = True):
+    """The backward of `attention` over the rows (isplib_attention_bw_rows_hip): for g = dL/dz [m, k] and the forward's z and lse,
+    D_i = <g_i, z_i>, ds_e = a_e (<g_i, y_j> - D_i) with a_e = exp(s_e - lse_i) recomputed, dx_i = scale sum_e ds_e y_j.  Returns
+    (dx [m, k], D [m]); an empty row has dx_i = 0 and D_i = 0.  `out` = (dx, D); the operand checks are attention's."""
+    if not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1 or rowptr.numel() < 1:
+        raise ValueError("isplib_amd: `rowptr` (m + 1 entries) must be a 1-D tensor")
+    m = rowptr.numel() - 1
+    ldx = _attn_dense(x, "x", m, None, "one row per row of the sparse operand")
+    k = x.size(1)
+    if not isinstance(y, torch.Tensor) or y.dim() != 2:
+        raise ValueError("isplib_amd: `y` must be a 2-D tensor [n, k]")
+    n = y.size(0)
+    ldy = _attn_dense(y, "y", n, k, "x's width")
+    ldg = _attn_dense(g, "g", m, k, "the gradient of z")
+    ldz = _attn_dense(z, "z", m, k, "the forward's output")
+    _attn_vector(lse, "lse", m)
+    rowptr, col = _attn_structure(rowptr, col, "rowptr", "col", n, check)
+    if out is not None:
+        dx, dsum = out
+        lddx = _attn_dense(dx, "out[0]", m, k, "dx")
+        _attn_vector(dsum, "out[1]", m)
+    _attn_domain(n, k, (ldy,))
+    _same_gpu((("x", x), ("y", y), ("g", g), ("z", z), ("lse", lse), ("rowptr", rowptr), ("col", col)) +
+              ((("out[0]", out[0]), ("out[1]", out[1])) if out is not None else ()))
+    if out is None:
+        dx = torch.empty((m, k), dtype=torch.float32, device=x.device)
+        dsum = torch.empty(m, dtype=torch.float32, device=x.device)
+        lddx = max(k, 1)
+    if m == 0 or k == 0:
+        if k == 0 and m > 0:
+            dsum.zero_()
+        return dx, dsum
+    rp = rowptr.data_ptr()
+    with torch.cuda.device(x.device):
+        st = lib().isplib_attention_bw_rows_hip(m, n, k, col.numel(), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8), _ptr(x), ldx,
+                                                _ptr(y), ldy, _attn_scale(scale, k), _ptr(g), ldg, _ptr(z), ldz, _ptr(lse), _ptr(dx), lddx,
+                                                _ptr(dsum), _stream(x.device))
+    _check(st, "isplib_attention_bw_rows_hip")
+    return dx, dsum
+
+
+def attention_bw_cols(colptr, row_t, x, y, g, lse, dsum, scale: Optional[float] = None, *, out=None, check: bool = True):
+    """The backward of `attention` over the columns (isplib_attention_bw_cols_hip), on the transposed structure (`colptr` [n + 1],
+    `row_t`: the row ids of the entries in column-major order, SparseStorage.colptr() / row_t()): dy_j = sum over the entries
+    e = (i, j) of column j of a_e g_i + scale ds_e x_i, with `lse` of the forward and `dsum` = D of attention_bw_rows.  Returns
+    dy [n, k]; a column no entry points at has dy_j = 0.  `out` = dy; the operand checks are attention's."""
+    if not isinstance(colptr, torch.Tensor) or colptr.dim() != 1 or colptr.numel() < 1:
+        raise ValueError("isplib_amd: `colptr` (n + 1 entries) must be a 1-D tensor")
+    n = colptr.numel() - 1
+    ldy = _attn_dense(y, "y", n, None, "one row per column of the sparse operand")
+    k = y.size(1)
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise ValueError("isplib_amd: `x` must be a 2-D tensor [m, k]")
+    m = x.size(0)
+    ldx = _attn_dense(x, "x", m, k, "y's width")
+    ldg = _attn_dense(g, "g", m, k, "the gradient of z")
+    _attn_vector(lse, "lse", m)
+    _attn_vector(dsum, "dsum", m)
+    colptr, row_t = _attn_structure(colptr, row_t, "colptr", "row_t", m, check)
+    if out is not None:
+        lddy = _attn_dense(out, "out", n, k, "dy")
+    _attn_domain(m, k, (ldx, ldg))
+    _same_gpu((("x", x), ("y", y), ("g", g), ("lse", lse), ("dsum", dsum), ("colptr", colptr), ("row_t", row_t), ("out", out)))
+    if out is None:
+        out = torch.empty((n, k), dtype=torch.float32, device=y.device)
+        lddy = max(k, 1)
+    if n == 0 or k == 0:
+        return out
+    cp = colptr.data_ptr()
+    with torch.cuda.device(y.device):
+        st = lib().isplib_attention_bw_cols_hip(m, n, k, row_t.numel(), _ptr(row_t), ctypes.c_void_p(cp), ctypes.c_void_p(cp + 8), _ptr(x), ldx,
+                                                _ptr(y), ldy, _attn_scale(scale, k), _ptr(g), ldg, _ptr(lse), _ptr(dsum), _ptr(out), lddy,
+                                                _stream(y.device))
+    _check(st, "isplib_attention_bw_cols_hip")
     return out
 
 

@@ -30,6 +30,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <initializer_list>
+#include <limits>
 #include <mutex>
 #include <tuple>
 #include <unordered_map>
@@ -1179,6 +1180,99 @@ std::tuple<Tensor, Tensor> fusedmm_spmm_min(Tensor rowptr, Tensor col, optional<
    return std::make_tuple(r[0], r[1]);
 }
 
+// ---- row-softmax attention aggregation (isplib_attention_*_hip; not an operator of the reference) ----------
+// z_i = sum_e softmax_e(scale <x_i, y_j>) y_j over the stored entries of the CSR structure.  Saved for backward: x, y, z and ONE scalar
+// per row (lse) -- the weights are recomputed, nothing of length nnz is kept.  Operands go in as they lie: a row-strided view (a head
+// of one [N, H*d] tensor) keeps its pitch; only an operand without unit inner stride is copied.
+struct AttnOperand {
+   Tensor t;
+   int64_t ld;
+};
+static AttnOperand attn_operand(const Tensor &src, const char *name, int64_t rows, int64_t k) {
+   check_float(src, name);
+   TORCH_CHECK(src.dim() == 2 && src.size(0) == rows && src.size(1) == k, "isplib: attention_spmm: `", name, "` must be [", rows, ", ", k,
+               "], got ", src.sizes());
+   const bool as_is = src.size(0) == 0 || src.size(1) == 0 || (src.stride(1) == 1 && (src.size(0) == 1 || src.stride(0) >= k));
+   const Tensor t = as_is ? src : src.contiguous();
+   return {t, t.size(0) > 1 ? t.stride(0) : std::max<int64_t>(k, 1)};
+}
+
+class AttentionSpmm : public torch::autograd::Function<AttentionSpmm> {
+ public:
+   static variable_list forward(AutogradContext *ctx, Variable rowptr, Variable col, Variable colptr, Variable row_t, Variable x, Variable y,
+                                double scale) {
+      check_index(rowptr, "rowptr"); check_index(col, "col"); check_index(colptr, "colptr"); check_index(row_t, "row_t");
+      TORCH_CHECK(x.defined() && x.dim() == 2 && y.defined() && y.dim() == 2, "isplib: attention_spmm needs 2-D `x` [M, K] and `y` [N, K]");
+      OpTimer timer("FUSEDMM_ATTENTION_FW", x);
+      const int64_t M = rowptr.numel() - 1, N = colptr.numel() - 1, K = x.size(1), nnz = col.numel();
+      TORCH_CHECK(M >= 0 && N >= 0 && row_t.numel() == nnz, "isplib: attention_spmm: `rowptr` / `colptr` need one entry more than rows / columns, "
+                                                             "`row_t` one entry per stored entry");
+      const AttnOperand xo = attn_operand(x, "x", M, K), yo = attn_operand(y, "y", N, K);
+      for (const Tensor *t : {&rowptr, &col, &colptr, &row_t, &y})
+         TORCH_CHECK(t->device() == x.device(), "isplib: attention_spmm: every operand must be on x's device");
+      TORCH_CHECK(K == 0 || isplib_attention_serves(N, K, yo.ld), "isplib: attention_spmm: outside isplib_attention_serves (1 <= K <= ",
+                  ISPLIB_ATTENTION_K_MAX, ", N < 2^31, N * pitch * 4 <= 3.5 GiB): N = ", N, ", K = ", K, ", pitch = ", yo.ld);
+      c10::DeviceGuard guard(x.device());
+      const Tensor rp = rowptr.contiguous(), cl = col.contiguous();
+      Tensor z = at::empty({M, K}, x.options()), lse = at::empty({M}, x.options());
+      if (M > 0 && K > 0) {
+         const int st = isplib_attention_csr_hip(M, N, K, nnz, cl.data_ptr<int64_t>(), rp.data_ptr<int64_t>(), rp.data_ptr<int64_t>() + 1,
+                                                 xo.t.data_ptr<float>(), xo.ld, nnz > 0 ? yo.t.data_ptr<float>() : nullptr, yo.ld, (float)scale,
+                                                 z.data_ptr<float>(), K, lse.data_ptr<float>(), current_stream(x));
+         check_status(st, "isplib_attention_csr_hip");
+      } else if (M > 0) {
+         lse.fill_(-std::numeric_limits<float>::infinity());
+      }
+      ctx->saved_data["scale"] = scale;
+      ctx->save_for_backward({rp, cl, colptr, row_t, x, y, z, lse});
+      return {z};
+   }
+
+   static variable_list backward(AutogradContext *ctx, variable_list grad_outs) {
+      OpTimer timer("FUSEDMM_ATTENTION_BW", grad_outs[0]);
+      const bool need_x = ctx->needs_input_grad(4), need_y = ctx->needs_input_grad(5);
+      auto grad_x = Variable(), grad_y = Variable();
+      if (need_x || need_y) {
+         auto saved = ctx->get_saved_variables();
+         auto rp = saved[0], cl = saved[1], colptr = saved[2].contiguous(), row_t = saved[3].contiguous(), x = saved[4], y = saved[5], z = saved[6],
+              lse = saved[7];
+         const float scale = (float)ctx->saved_data["scale"].toDouble();
+         const int64_t M = rp.numel() - 1, N = colptr.numel() - 1, K = x.size(1), nnz = cl.numel();
+         const AttnOperand xo = attn_operand(x, "x", M, K), yo = attn_operand(y, "y", N, K);
+         const AttnOperand go = attn_operand(grad_outs[0].to(at::kFloat), "grad_out", M, K);
+         c10::DeviceGuard guard(x.device());
+         // the rows kernel always runs: its D_i = <g_i, z_i> feeds the columns kernel; the columns kernel only when y asks
+         Tensor dx = at::empty({M, K}, x.options()), dsum = at::empty({M}, x.options());
+         if (M > 0 && K > 0) {
+            const int st = isplib_attention_bw_rows_hip(M, N, K, nnz, cl.data_ptr<int64_t>(), rp.data_ptr<int64_t>(), rp.data_ptr<int64_t>() + 1,
+                                                        xo.t.data_ptr<float>(), xo.ld, nnz > 0 ? yo.t.data_ptr<float>() : nullptr, yo.ld, scale,
+                                                        go.t.data_ptr<float>(), go.ld, z.data_ptr<float>(), K, lse.data_ptr<float>(),
+                                                        dx.data_ptr<float>(), K, dsum.data_ptr<float>(), current_stream(x));
+            check_status(st, "isplib_attention_bw_rows_hip");
+         }
+         if (need_x) grad_x = dx;
+         if (need_y) {
+            TORCH_CHECK(K == 0 || (isplib_attention_serves(M, K, xo.ld) && isplib_attention_serves(M, K, go.ld)),
+                        "isplib: attention_spmm backward: outside isplib_attention_serves for the gathered rows of x: M = ", M, ", K = ", K);
+            grad_y = at::empty({N, K}, y.options());
+            if (N > 0 && K > 0) {
+               const int st = isplib_attention_bw_cols_hip(M, N, K, nnz, row_t.data_ptr<int64_t>(), colptr.data_ptr<int64_t>(),
+                                                           colptr.data_ptr<int64_t>() + 1, nnz > 0 ? xo.t.data_ptr<float>() : nullptr, xo.ld,
+                                                           yo.t.data_ptr<float>(), yo.ld, scale, nnz > 0 ? go.t.data_ptr<float>() : nullptr, go.ld,
+                                                           lse.data_ptr<float>(), dsum.data_ptr<float>(), grad_y.data_ptr<float>(), K,
+                                                           current_stream(x));
+               check_status(st, "isplib_attention_bw_cols_hip");
+            }
+         }
+      }
+      return {Variable(), Variable(), Variable(), Variable(), grad_x, grad_y, Variable()};
+   }
+};
+
+Tensor attention_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor x, Tensor y, double scale) {
+   return AttentionSpmm::apply(rowptr, col, colptr, row_t, x, y, scale)[0];
+}
+
 // introspection / housekeeping of the per-graph handle cache of the reference-schema operators
 int64_t graph_cache_size() {
    std::lock_guard<std::mutex> lock(g_graph_mutex);
@@ -1227,4 +1321,5 @@ TORCH_LIBRARY(isplib, m) {
    m.def("gcn_norm_spmm(Tensor rowptr, Tensor col, Tensor mat, Tensor dinv, Tensor? colptr, Tensor? row_t, Tensor[] plan, "
          "Tensor[] plan_t, Tensor? bias, bool relu) -> Tensor",
          &gcn_norm_spmm);
+   m.def("attention_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor x, Tensor y, float scale) -> Tensor", &attention_spmm);
 }

@@ -579,6 +579,52 @@ def fusedmm(src, x: Optional[torch.Tensor], y: torch.Tensor, pattern="sigmoid_em
     return cabi.fusedmm(word, st._rowptr, st._col, st._value, x, y, sop_udef=sop_udef or fn, sop_param=sop_param, plan=plan)[1]
 
 
+def attention_matmul(src, x: torch.Tensor, y: Optional[torch.Tensor] = None, scale: Optional[float] = None) -> torch.Tensor:
+    """Row-softmax attention aggregation over the stored entries of `src` (include/isplib_hip.h, isplib_attention_csr_hip):
+    ``z[i] = sum_j softmax_j(scale * <x[i], y[j]>) y[j]`` over the entries (i, j) of row i -- the aggregation of AGNNConv and of the
+    dot-product attention of TransformerConv / graph transformers, with its autograd backward (torch.ops.isplib.attention_spmm).  The
+    stored values of `src` are not read; an empty row gives 0.  `x` [M, K], `y` [N, K] float32 GPU tensors; ``y=None`` means
+    ``y = x`` (a square `src`; ``x.grad`` receives both contributions); ``scale=None`` means ``1 / sqrt(K)``.  Row-strided views keep
+    their pitch, so multi-head use is one call per head on column views such as ``x[:, h*d:(h+1)*d]``.  The backward keeps x, y, z and
+    one scalar per row -- nothing per edge -- and walks the storage's cached transposed structure (colptr / row_t).  fp32 only;
+    there is no fallback route: outside isplib_attention_serves the call raises."""
+    from . import cabi
+    shared = y is None
+    for name, t in (("x", x),) + (() if shared else (("y", y),)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"isplib_amd: `{name}` must be a tensor, got {type(t).__name__}")
+        if t.dim() != 2:
+            raise ValueError(f"isplib_amd: `{name}` must be 2-D [rows, k], got shape {tuple(t.shape)}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"isplib_amd: `{name}` must be float32, got {t.dtype} (the attention operator is fp32 only)")
+    if shared:
+        y = x
+    st = _storage_of(src, y)
+    m_rows, n_cols = st._rowptr.numel() - 1, st._sparse_sizes[1]
+    if shared and m_rows != n_cols:
+        raise ValueError(f"isplib_amd: y=None needs a square sparse matrix, got {m_rows} x {n_cols}")
+    if x.size(0) != m_rows:
+        raise ValueError(f"isplib_amd: `x` must have one row per row of the sparse matrix ({m_rows}), got {x.size(0)}")
+    if y.size(0) != n_cols:
+        raise ValueError(f"isplib_amd: `y` must have one row per column of the sparse matrix ({n_cols}), got {y.size(0)}")
+    k = x.size(1)
+    if y.size(1) != k:
+        raise ValueError(f"isplib_amd: `x` and `y` must have one width, got {k} and {y.size(1)}")
+    if not 1 <= k <= cabi.ATTENTION_K_MAX:
+        raise ValueError(f"isplib_amd: attention_matmul serves 1 <= K <= {cabi.ATTENTION_K_MAX} (a row sits in registers), got K = {k}")
+    for name, t, rows in (("x", x, m_rows), ("y", y, n_cols)):     # y is gathered by the forward, x by the backward over the columns
+        pitch = t.stride(0) if rows > 1 and t.stride(1) == 1 and t.stride(0) >= k else k
+        if not cabi.attention_serves(rows, k, pitch):
+            raise ValueError(f"isplib_amd: `{name}` ({rows} rows at a pitch of {pitch} floats) is outside the attention kernels' domain: "
+                             f"rows < 2^31 and rows * pitch * 4 <= {cabi.DENSE_BYTES_MAX} bytes (3.5 GiB, one buffer descriptor)")
+    if not x.is_cuda or not y.is_cuda:
+        raise TypeError("isplib_amd: `x` and `y` must be GPU tensors -- there is no CPU path")
+    if x.device != y.device or st._rowptr.device != x.device:
+        raise ValueError("isplib_amd: `x`, `y` and the sparse matrix must be on one device")
+    p = float(scale) if scale is not None else 1.0 / float(k) ** 0.5
+    return torch.ops.isplib.attention_spmm(st._rowptr, st._col, st.colptr(), st.row_t(), x, y, p)
+
+
 def gcn_norm_matmul(src, other: torch.Tensor, bias: Optional[torch.Tensor] = None, relu: bool = False) -> torch.Tensor:
     """relu(D^-1/2 (A + I) D^-1/2 @ other + bias) for an UNWEIGHTED square graph, without materialising the
     normalised edge weights: the SpMM runs on the unit-weight fast path, the self loop, the left D^-1/2, bias

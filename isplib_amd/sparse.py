@@ -336,3 +336,8 @@ class SparseTensor:
         return matmul(self, other, reduce)
 
     __matmul__ = matmul
+
+    def attention_matmul(self, x: torch.Tensor, y: Optional[torch.Tensor] = None, scale: Optional[float] = None) -> torch.Tensor:
+        """Row-softmax attention aggregation over this matrix's stored entries (plugin.attention_matmul)."""
+        from .plugin import attention_matmul
+        return attention_matmul(self, x, y, scale)
