@@ -730,6 +730,61 @@ int    isplib_attention_bw_cols_hip(int64_t m, int64_t n, int64_t k, int64_t nnz
                                     const float *g, int64_t ldg, const float *lse, const float *dsum, float *dy, int64_t lddy,
                                     void *stream);
 /*
+ * The row-softmax attention aggregation above for dense operands of 16-bit elements (dtype: ISPLIB_DTYPE_BF16 | _F16), forward and
+ * backward, on the same mapping (one wave per row or column, one 16-byte gather of EIGHT columns per lane and edge, one chunk per
+ * lane).  x, y and g are `dtype` and no operand is widened in memory; widening is exact, every product, sum, exponential and division
+ * is fp32, and z, dx and dy are rounded ONCE, to nearest even, to `dtype` (an fp16 result beyond 65504 rounds to Inf as the cast does;
+ * nothing is clamped or flushed).  lse and dsum (D_i) stay fp32.  The special values are the fp32 entries': an empty row has z_i = 0,
+ * lse_i = -inf, dx_i = 0, D_i = 0; a column no entry points at has dy_j = 0; a row of one entry returns y_j's 16 bits unchanged; a
+ * +inf score, or a NaN anywhere in a row's operands, makes that row NaN and no other.
+ *   isplib_attention16_csr_hip      writes z (m x ldz, `dtype`) and lse (m, fp32).
+ *   isplib_attention16_bw_rows_hip  reads x, y, g and lse -- NOT z: the rounded z would carry u * sum_c |g_ic z_ic| into every ds_e
+ *                                   through D_i = <g_i, z_i>.  D_i = sum_e a_e t_e is formed in fp32 from the row's own edges, in the
+ *                                   same pass as dx (D_i = Dacc / l, dx_i = p (A1 - D_i Z) with l = sum a_e, Dacc = sum a_e t_e,
+ *                                   Z = sum a_e y_j, A1 = sum a_e t_e y_j).  Writes dx (m x lddx, `dtype`) and dsum (m, fp32).
+ *   isplib_attention16_bw_cols_hip  on the transposed structure; reads x, y, g, lse and dsum, writes dy (n x lddy, `dtype`).
+ * Nothing is kept per edge and autograd needs x, y and lse only.  Outputs are write-only, every element of every row is written,
+ * nothing between the rows of a pitched output, nothing outside a row's k columns is used (a head view of a wider tensor goes in as
+ * it lies).  No atomics, no LDS, a fixed order of operations: two launches give equal bits.  The entries neither allocate nor
+ * synchronise.
+ * Domain: isplib_attention16_serves(rows_gathered, k, ld) for every GATHERED operand (y with n rows in the first two entries; x and g
+ * with m rows in the third): 8 <= k <= 512 (a lane holds eight columns, one chunk per lane), k and the pitch even, ld >= k,
+ * rows_gathered < 2^31 and the operand inside one buffer descriptor at 2 bytes per element; the pitches of the row-resident operands
+ * and of the output must be even too.  Outside the domain: ISPLIB_NO_OPT_IMPL.  Another dtype, a negative dimension, a null operand, a
+ * pitch of a row-resident operand or output below k, or a 16-bit base that is not 4-byte aligned: ISPLIB_FAIL.  All refusals come
+ * before any launch and leave the outputs untouched.  m == 0 or k == 0 (n == 0 or k == 0 in the third entry) succeeds without a launch.
+ * isplib_attention16_native_pays is the measured rule of the layers above (forward + backward against "widen, the fp32 entries,
+ * narrow"; profiles/attention16_ab.txt), over the family's classes (the gathered operand beyond 256 MiB at 2 bytes per
+ * element or not): nonzero only where EVERY native run was faster than EVERY run of the conversion route on every measured shape of the
+ * class.
+ */
+#define ISPLIB_ATTENTION16_K_MIN       8            /* a lane gathers eight columns */
+#define ISPLIB_ATTENTION16_K_MAX       512          /* one 16-byte chunk per lane, 64 lanes */
+static inline int isplib_attention16_serves(int64_t rows_gathered, int64_t k, int64_t ld) {
+   return k >= ISPLIB_ATTENTION16_K_MIN && k <= ISPLIB_ATTENTION16_K_MAX && (k % 2) == 0 && (ld % 2) == 0 && ld >= k &&
+          rows_gathered < (1LL << 31) && isplib_rows_within(rows_gathered, ld, 2ull * ISPLIB_DENSE_BYTES_MAX);
+}
+int    isplib_attention16_domain(int64_t rows_gathered, int64_t k, int64_t ld);   /* isplib_attention16_serves as a symbol */
+int    isplib_attention16_csr_hip(int dtype /* ISPLIB_DTYPE_BF16 | _F16 */, int64_t m, int64_t n, int64_t k, int64_t nnz,
+                                  const int64_t *indx, const int64_t *pntrb, const int64_t *pntre, const void *x, int64_t ldx,
+                                  const void *y, int64_t ldy, float scale, void *z, int64_t ldz, float *lse /* m */, void *stream);
+int    isplib_attention16_bw_rows_hip(int dtype, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                                      const int64_t *pntre, const void *x, int64_t ldx, const void *y, int64_t ldy, float scale,
+                                      const void *g, int64_t ldg, const float *lse, void *dx, int64_t lddx, float *dsum /* m */,
+                                      void *stream);
+int    isplib_attention16_bw_cols_hip(int dtype, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t, const int64_t *colb,
+                                      const int64_t *cole, const void *x, int64_t ldx, const void *y, int64_t ldy, float scale,
+                                      const void *g, int64_t ldg, const float *lse, const float *dsum, void *dy, int64_t lddy,
+                                      void *stream);
+static inline int isplib_attention16_native_pays(int64_t rows_gathered, int64_t ld) {
+   /* measured (profiles/attention16_ab.txt: the Reddit shape at K = 64 and 128 -- gathered operand inside 256 MiB -- and the ogbn-products
+    * shape at K = 128 -- beyond it; bf16, forward + backward, 5 alternating runs of 5 steps): every native run is below every run of the
+    * conversion route in both classes -- 0.51-0.52 of its time inside 256 MiB, 0.55 beyond (forward alone 0.47-0.52), at 0.09-0.10 of its
+    * peak memory.  Both classes pay. */
+   return (rows_gathered > 0 && ld > 0) ? 1 : 0;
+}
+int    isplib_attention16_auto(int64_t rows_gathered, int64_t ld);                /* the same rule as a symbol */
+/*
  * Staged column panels (sum / mean on 64-column slots only).  What a gather of a 128-byte line costs depends on the line's
  * ADDRESS: profiles/line_classes.txt (scripts/ubench/line_classes.hip) is the table, DESIGN.md section 5 reads it.  Before the
  * dispatches of a panel whose lines sit in a slow class, fusedMM_csr_stream_hip may copy the panel's 64 columns into the tail

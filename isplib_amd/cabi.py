@@ -127,6 +127,24 @@ def attention_serves(rows_gathered: int, k: int, ld: int) -> bool:
             (rows_gathered <= 0 or rows_gathered * ld * 4 <= DENSE_BYTES_MAX))
 
 
+ATTENTION16_K_MIN, ATTENTION16_K_MAX = 8, 512   # the 16-bit attention entries: eight columns per lane, one 16-byte chunk per lane
+
+
+def attention16_serves(rows_gathered: int, k: int, ld: int) -> bool:
+    """isplib_attention16_serves of the header: the 16-bit attention entries (isplib_attention16_csr_hip and its two backward entries)
+    gather `rows_gathered` rows of k 2-byte elements at leading dimension ld through one buffer descriptor."""
+    return (ATTENTION16_K_MIN <= k <= ATTENTION16_K_MAX and k % 2 == 0 and ld % 2 == 0 and ld >= k and rows_gathered < 2 ** 31 and
+            (rows_gathered <= 0 or rows_gathered * ld * 2 <= DENSE_BYTES_MAX))
+
+
+def attention16_native_pays(rows_gathered: int, ld: int) -> bool:
+    """isplib_attention16_native_pays of the header: the classes of calls (the gathered operand beyond 256 MiB at 2 bytes per element or
+    not) in which every native run of the 16-bit attention operator (forward + backward) measured faster than every run of the
+    conversion route (profiles/attention16_ab.txt: both classes do -- the Reddit shape at K = 64 / 128 inside 256 MiB, the ogbn-products
+    shape at K = 128 beyond it); tests/test_attention16_host.py compares the two."""
+    return bool(rows_gathered > 0 and ld > 0)
+
+
 def owner_exchange_serves(m: int, k: int, world: int, cuts) -> bool:
     """isplib_owner_exchange_serves of the header: m x k winners split for `world` owners at the row boundaries `cuts`."""
     if not 1 <= world <= OWNER_WORLD_MAX or m < 0 or k < 0 or m * k >= MINMAX_BW_PAIRS_END:
@@ -177,6 +195,8 @@ EXPORTS = (
     "fusedMM_csr_rows16_epilogue_hip", "isplib_rows16_gcn_auto", "isplib_masked_colsum16_hip", "isplib_masked_colsum16_workspace_bytes",
     "isplib_sddmm_csr_rows16_hip", "isplib_sddmm_rows16_auto",
     "isplib_attention_csr_hip", "isplib_attention_bw_rows_hip", "isplib_attention_bw_cols_hip", "isplib_attention_domain",
+    "isplib_attention16_csr_hip", "isplib_attention16_bw_rows_hip", "isplib_attention16_bw_cols_hip", "isplib_attention16_domain",
+    "isplib_attention16_auto",
 )
 
 # include/isplib_hip_experimental.h (libisplib_hip_exp.so): forms measured slower than the defaults; tests and experiment scripts only
@@ -421,6 +441,18 @@ def lib() -> ctypes.CDLL:
         L.isplib_attention_bw_cols_hip.restype = ctypes.c_int
         L.isplib_attention_bw_cols_hip.argtypes = [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _vp, _vp,
                                                    _i64, _vp]
+        L.isplib_attention16_domain.restype = ctypes.c_int
+        L.isplib_attention16_domain.argtypes = [_i64, _i64, _i64]
+        L.isplib_attention16_auto.restype = ctypes.c_int
+        L.isplib_attention16_auto.argtypes = [_i64, _i64]
+        L.isplib_attention16_csr_hip.restype = ctypes.c_int
+        L.isplib_attention16_csr_hip.argtypes = [ctypes.c_int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _vp]
+        L.isplib_attention16_bw_rows_hip.restype = ctypes.c_int
+        L.isplib_attention16_bw_rows_hip.argtypes = [ctypes.c_int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp,
+                                                     _vp, _i64, _vp, _vp]
+        L.isplib_attention16_bw_cols_hip.restype = ctypes.c_int
+        L.isplib_attention16_bw_cols_hip.argtypes = [ctypes.c_int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp,
+                                                     _vp, _vp, _i64, _vp]
         _sigs_set = True
     return L
 
@@ -1731,6 +1763,145 @@ def attention_bw_cols(colptr, row_t, x, y, g, lse, dsum, scale: Optional[float] 
                                                 _ptr(y), ldy, _attn_scale(scale, k), _ptr(g), ldg, _ptr(lse), _ptr(dsum), _ptr(out), lddy,
                                                 _stream(y.device))
     _check(st, "isplib_attention_bw_cols_hip")
+    return out
+
+
+def _attn16_dense(t, name: str, rows: int, k: Optional[int], what: str, dtype=None) -> int:
+    """One dense operand of the 16-bit attention entries: 2-D bf16 / fp16 [rows, k] (of `dtype` when given: every operand of a call
+    has x's) on the GPU with unit inner stride, an even pitch and a 4-byte aligned base; a row-strided view keeps its pitch.  Returns
+    the pitch in elements."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2:
+        raise ValueError(f"isplib_amd: `{name}` must be a 2-D tensor, got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    if t.dtype not in HALF_DTYPES or (dtype is not None and t.dtype != dtype):
+        raise TypeError(f"isplib_amd: `{name}` must be {dtype or 'bfloat16 or float16'}, got {t.dtype} (float32 operands: cabi.attention)")
+    if t.size(0) != rows or (k is not None and t.size(1) != k):
+        raise ValueError(f"isplib_amd: `{name}` must be [{rows}, {'k' if k is None else k}] ({what}), got {tuple(t.shape)}")
+    if t.size(1) > 0 and t.size(0) > 0 and t.stride(1) != 1:
+        raise ValueError(f"isplib_amd: `{name}` must have unit inner stride")
+    ld = t.stride(0) if t.size(0) > 1 else max(t.size(1), t.stride(0))
+    if ld < t.size(1):
+        raise ValueError(f"isplib_amd: the rows of `{name}` (pitch {ld}) must not overlap: k = {t.size(1)}")
+    if t.numel() > 0 and (ld % 2 or t.data_ptr() % 4):
+        raise ValueError(f"isplib_amd: `{name}` needs an even pitch (got {ld}) and a 4-byte aligned base (the 16-bit attention entries)")
+    return int(ld)
+
+
+def _attn16_domain(rows_gathered: int, k: int, lds) -> None:
+    for ld in lds:
+        if k > 0 and not attention16_serves(rows_gathered, k, ld):
+            raise ValueError(f"isplib_amd: outside the 16-bit attention entries' domain (isplib_attention16_serves: {ATTENTION16_K_MIN} <= k <= "
+                             f"{ATTENTION16_K_MAX}, k and the pitch even, gathered rows < 2^31, rows * pitch * 2 <= 3.5 GiB), got "
+                             f"rows={rows_gathered}, k={k}, pitch={ld}")
+
+
+def attention16(rowptr, col, x, y, scale: Optional[float] = None, *, out=None, check: bool = True):
+    """`attention` for bf16 / fp16 operands (isplib_attention16_csr_hip): x [m, k] and y [n, k] of one 16-bit dtype go in as they lie,
+    every product, sum and exponential is fp32, z is rounded once to the operands' dtype.  Returns (z [m, k] 16-bit, lse [m] fp32);
+    `out` = (z, lse).  The operand checks are attention's, with the 16-bit family's (even k and pitches, 4-byte aligned bases)."""
+    if not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1 or rowptr.numel() < 1:
+        raise ValueError("isplib_amd: `rowptr` (m + 1 entries) must be a 1-D tensor")
+    m = rowptr.numel() - 1
+    ldx = _attn16_dense(x, "x", m, None, "one row per row of the sparse operand")
+    k = x.size(1)
+    if not isinstance(y, torch.Tensor) or y.dim() != 2:
+        raise ValueError("isplib_amd: `y` must be a 2-D tensor [n, k]")
+    n = y.size(0)
+    ldy = _attn16_dense(y, "y", n, k, "x's width", x.dtype)
+    rowptr, col = _attn_structure(rowptr, col, "rowptr", "col", n, check)
+    if out is not None:
+        z, lse = out
+        ldz = _attn16_dense(z, "out[0]", m, k, "z", x.dtype)
+        _attn_vector(lse, "out[1]", m)
+    _attn16_domain(n, k, (ldy,))
+    _same_gpu((("x", x), ("y", y), ("rowptr", rowptr), ("col", col)) + ((("out[0]", out[0]), ("out[1]", out[1])) if out is not None else ()))
+    if out is None:
+        z = torch.empty((m, k), dtype=x.dtype, device=x.device)
+        lse = torch.empty(m, dtype=torch.float32, device=x.device)
+        ldz = max(k, 1)
+    if m == 0 or k == 0:
+        if k == 0 and m > 0:
+            lse.fill_(float("-inf"))
+        return z, lse
+    rp = rowptr.data_ptr()
+    with torch.cuda.device(x.device):
+        st = lib().isplib_attention16_csr_hip(HALF_DTYPES[x.dtype], m, n, k, col.numel(), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8),
+                                              _ptr(x), ldx, _ptr(y), ldy, _attn_scale(scale, k), _ptr(z), ldz, _ptr(lse), _stream(x.device))
+    _check(st, "isplib_attention16_csr_hip")
+    return z, lse
+
+
+def attention16_bw_rows(rowptr, col, x, y, g, lse, scale: Optional[float] = None, *, out=None, check: bool = True):
+    """The backward of `attention16` over the rows (isplib_attention16_bw_rows_hip): for g = dL/dz [m, k] (the operands' dtype) and the
+    forward's lse -- z is NOT read: D_i = sum_e a_e <g_i, y_j> is formed in fp32 from the row's edges -- returns (dx [m, k] 16-bit,
+    D [m] fp32).  `out` = (dx, D); the operand checks are attention16's."""
+    if not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1 or rowptr.numel() < 1:
+        raise ValueError("isplib_amd: `rowptr` (m + 1 entries) must be a 1-D tensor")
+    m = rowptr.numel() - 1
+    ldx = _attn16_dense(x, "x", m, None, "one row per row of the sparse operand")
+    k = x.size(1)
+    if not isinstance(y, torch.Tensor) or y.dim() != 2:
+        raise ValueError("isplib_amd: `y` must be a 2-D tensor [n, k]")
+    n = y.size(0)
+    ldy = _attn16_dense(y, "y", n, k, "x's width", x.dtype)
+    ldg = _attn16_dense(g, "g", m, k, "the gradient of z", x.dtype)
+    _attn_vector(lse, "lse", m)
+    rowptr, col = _attn_structure(rowptr, col, "rowptr", "col", n, check)
+    if out is not None:
+        dx, dsum = out
+        lddx = _attn16_dense(dx, "out[0]", m, k, "dx", x.dtype)
+        _attn_vector(dsum, "out[1]", m)
+    _attn16_domain(n, k, (ldy,))
+    _same_gpu((("x", x), ("y", y), ("g", g), ("lse", lse), ("rowptr", rowptr), ("col", col)) +
+              ((("out[0]", out[0]), ("out[1]", out[1])) if out is not None else ()))
+    if out is None:
+        dx = torch.empty((m, k), dtype=x.dtype, device=x.device)
+        dsum = torch.empty(m, dtype=torch.float32, device=x.device)
+        lddx = max(k, 1)
+    if m == 0 or k == 0:
+        if k == 0 and m > 0:
+            dsum.zero_()
+        return dx, dsum
+    rp = rowptr.data_ptr()
+    with torch.cuda.device(x.device):
+        st = lib().isplib_attention16_bw_rows_hip(HALF_DTYPES[x.dtype], m, n, k, col.numel(), _ptr(col), ctypes.c_void_p(rp),
+                                                  ctypes.c_void_p(rp + 8), _ptr(x), ldx, _ptr(y), ldy, _attn_scale(scale, k), _ptr(g), ldg,
+                                                  _ptr(lse), _ptr(dx), lddx, _ptr(dsum), _stream(x.device))
+    _check(st, "isplib_attention16_bw_rows_hip")
+    return dx, dsum
+
+
+def attention16_bw_cols(colptr, row_t, x, y, g, lse, dsum, scale: Optional[float] = None, *, out=None, check: bool = True):
+    """The backward of `attention16` over the columns (isplib_attention16_bw_cols_hip), on the transposed structure: dy_j = sum over the
+    entries e = (i, j) of column j of a_e g_i + scale ds_e x_i, with `lse` of the forward and `dsum` = D of attention16_bw_rows (both
+    fp32).  Returns dy [n, k] in the operands' dtype; `out` = dy; the operand checks are attention16's."""
+    if not isinstance(colptr, torch.Tensor) or colptr.dim() != 1 or colptr.numel() < 1:
+        raise ValueError("isplib_amd: `colptr` (n + 1 entries) must be a 1-D tensor")
+    n = colptr.numel() - 1
+    ldy = _attn16_dense(y, "y", n, None, "one row per column of the sparse operand")
+    k = y.size(1)
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise ValueError("isplib_amd: `x` must be a 2-D tensor [m, k]")
+    m = x.size(0)
+    ldx = _attn16_dense(x, "x", m, k, "y's width", y.dtype)
+    ldg = _attn16_dense(g, "g", m, k, "the gradient of z", y.dtype)
+    _attn_vector(lse, "lse", m)
+    _attn_vector(dsum, "dsum", m)
+    colptr, row_t = _attn_structure(colptr, row_t, "colptr", "row_t", m, check)
+    if out is not None:
+        lddy = _attn16_dense(out, "out", n, k, "dy", y.dtype)
+    _attn16_domain(m, k, (ldx, ldg))
+    _same_gpu((("x", x), ("y", y), ("g", g), ("lse", lse), ("dsum", dsum), ("colptr", colptr), ("row_t", row_t), ("out", out)))
+    if out is None:
+        out = torch.empty((n, k), dtype=y.dtype, device=y.device)
+        lddy = max(k, 1)
+    if n == 0 or k == 0:
+        return out
+    cp = colptr.data_ptr()
+    with torch.cuda.device(y.device):
+        st = lib().isplib_attention16_bw_cols_hip(HALF_DTYPES[y.dtype], m, n, k, row_t.numel(), _ptr(row_t), ctypes.c_void_p(cp),
+                                                  ctypes.c_void_p(cp + 8), _ptr(x), ldx, _ptr(y), ldy, _attn_scale(scale, k), _ptr(g), ldg,
+                                                  _ptr(lse), _ptr(dsum), _ptr(out), lddy, _stream(y.device))
+    _check(st, "isplib_attention16_bw_cols_hip")
     return out
 
 

@@ -1273,6 +1273,106 @@ Tensor attention_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Te
    return AttentionSpmm::apply(rowptr, col, colptr, row_t, x, y, scale)[0];
 }
 
+// ---- the same aggregation for bf16 / fp16 operands (isplib_attention16_*_hip) ----------
+// x and y go in as they lie, z / dx / dy come back in their dtype, lse and D stay fp32: no fp32 [*, K] tensor in either direction.  Saved
+// for backward: the structure, x, y and lse -- NOT z: the rows kernel forms D_i from the row's edges (the rounded z would cost every
+// ds_e an error of u * sum |g z|).  An operand is copied only without unit inner stride, or where the domain admits it packed but not at
+// its pitch or alignment.
+static AttnOperand attn16_operand(const Tensor &src, const char *name, int64_t rows, int64_t k, at::ScalarType dtype) {
+   TORCH_CHECK(src.defined() && src.scalar_type() == dtype, "isplib: attention_spmm16: `", name, "` must be ", dtype, " (x and y both bfloat16 or both "
+               "float16), got ", src.defined() ? src.scalar_type() : at::ScalarType::Undefined);
+   TORCH_CHECK(src.is_cuda(), "isplib: attention_spmm16: `", name, "` must be a GPU tensor -- there is no CPU path");
+   TORCH_CHECK(src.dim() == 2 && src.size(0) == rows && src.size(1) == k, "isplib: attention_spmm16: `", name, "` must be [", rows, ", ", k,
+               "], got ", src.sizes());
+   if (rows == 0 || k == 0) return {src, std::max<int64_t>(k, 1)};
+   const int64_t ld = rows > 1 ? src.stride(0) : k;
+   const bool as_is = src.stride(1) == 1 && ld >= k && ((uintptr_t)src.data_ptr() & 3) == 0 && isplib_attention16_serves(rows, k, ld);
+   if (as_is) return {src, ld};
+   return {src.clone(at::MemoryFormat::Contiguous), k};
+}
+
+class AttentionSpmm16 : public torch::autograd::Function<AttentionSpmm16> {
+ public:
+   static variable_list forward(AutogradContext *ctx, Variable rowptr, Variable col, Variable colptr, Variable row_t, Variable x, Variable y,
+                                double scale) {
+      check_index(rowptr, "rowptr"); check_index(col, "col"); check_index(colptr, "colptr"); check_index(row_t, "row_t");
+      TORCH_CHECK(x.defined() && x.dim() == 2 && y.defined() && y.dim() == 2, "isplib: attention_spmm16 needs 2-D `x` [M, K] and `y` [N, K]");
+      TORCH_CHECK(is_half(x), "isplib: attention_spmm16: `x` and `y` must both be bfloat16 or both float16, got ", x.scalar_type(), " and ",
+                  y.scalar_type(), " (float32: attention_spmm)");
+      OpTimer timer("FUSEDMM_ATTENTION_FW", x);
+      const int64_t M = rowptr.numel() - 1, N = colptr.numel() - 1, K = x.size(1), nnz = col.numel();
+      TORCH_CHECK(M >= 0 && N >= 0 && row_t.numel() == nnz, "isplib: attention_spmm16: `rowptr` / `colptr` need one entry more than rows / columns, "
+                                                             "`row_t` one entry per stored entry");
+      const at::ScalarType dt = x.scalar_type();
+      const AttnOperand xo = attn16_operand(x, "x", M, K, dt), yo = attn16_operand(y, "y", N, K, dt);
+      for (const Tensor *t : {&rowptr, &col, &colptr, &row_t, &y})
+         TORCH_CHECK(t->device() == x.device(), "isplib: attention_spmm16: every operand must be on x's device");
+      TORCH_CHECK(K == 0 || (isplib_attention16_serves(N, K, yo.ld) && xo.ld % 2 == 0),
+                  "isplib: attention_spmm16: outside isplib_attention16_serves (", ISPLIB_ATTENTION16_K_MIN, " <= K <= ", ISPLIB_ATTENTION16_K_MAX,
+                  ", K even, N < 2^31, N * pitch * 2 <= 3.5 GiB): N = ", N, ", K = ", K, ", pitch = ", yo.ld);
+      c10::DeviceGuard guard(x.device());
+      const int code = dt == at::kBFloat16 ? ISPLIB_DTYPE_BF16 : ISPLIB_DTYPE_F16;
+      const Tensor rp = rowptr.contiguous(), cl = col.contiguous();
+      Tensor z = at::empty({M, K}, x.options()), lse = at::empty({M}, x.options().dtype(at::kFloat));
+      if (M > 0 && K > 0) {
+         const int st = isplib_attention16_csr_hip(code, M, N, K, nnz, cl.data_ptr<int64_t>(), rp.data_ptr<int64_t>(), rp.data_ptr<int64_t>() + 1,
+                                                   xo.t.data_ptr(), xo.ld, nnz > 0 ? yo.t.data_ptr() : nullptr, yo.ld, (float)scale, z.data_ptr(), K,
+                                                   lse.data_ptr<float>(), current_stream(x));
+         check_status(st, "isplib_attention16_csr_hip");
+      } else if (M > 0) {
+         lse.fill_(-std::numeric_limits<float>::infinity());
+      }
+      ctx->saved_data["scale"] = scale;
+      ctx->save_for_backward({rp, cl, colptr, row_t, x, y, lse});
+      return {z};
+   }
+
+   static variable_list backward(AutogradContext *ctx, variable_list grad_outs) {
+      OpTimer timer("FUSEDMM_ATTENTION_BW", grad_outs[0]);
+      const bool need_x = ctx->needs_input_grad(4), need_y = ctx->needs_input_grad(5);
+      auto grad_x = Variable(), grad_y = Variable();
+      if (need_x || need_y) {
+         auto saved = ctx->get_saved_variables();
+         auto rp = saved[0], cl = saved[1], colptr = saved[2].contiguous(), row_t = saved[3].contiguous(), x = saved[4], y = saved[5], lse = saved[6];
+         const float scale = (float)ctx->saved_data["scale"].toDouble();
+         const int64_t M = rp.numel() - 1, N = colptr.numel() - 1, K = x.size(1), nnz = cl.numel();
+         const at::ScalarType dt = x.scalar_type();
+         const AttnOperand xo = attn16_operand(x, "x", M, K, dt), yo = attn16_operand(y, "y", N, K, dt);
+         const AttnOperand go = attn16_operand(grad_outs[0].to(dt), "grad_out", M, K, dt);      // a grad of another dtype is cast to the operands'
+         c10::DeviceGuard guard(x.device());
+         const int code = dt == at::kBFloat16 ? ISPLIB_DTYPE_BF16 : ISPLIB_DTYPE_F16;
+         // the rows kernel always runs: its D_i feeds the columns kernel; the columns kernel only when y asks
+         Tensor dx = at::empty({M, K}, x.options()), dsum = at::empty({M}, x.options().dtype(at::kFloat));
+         if (M > 0 && K > 0) {
+            const int st = isplib_attention16_bw_rows_hip(code, M, N, K, nnz, cl.data_ptr<int64_t>(), rp.data_ptr<int64_t>(),
+                                                          rp.data_ptr<int64_t>() + 1, xo.t.data_ptr(), xo.ld, nnz > 0 ? yo.t.data_ptr() : nullptr,
+                                                          yo.ld, scale, go.t.data_ptr(), go.ld, lse.data_ptr<float>(), dx.data_ptr(), K,
+                                                          dsum.data_ptr<float>(), current_stream(x));
+            check_status(st, "isplib_attention16_bw_rows_hip");
+         }
+         if (need_x) grad_x = dx;
+         if (need_y) {
+            TORCH_CHECK(K == 0 || (isplib_attention16_serves(M, K, xo.ld) && isplib_attention16_serves(M, K, go.ld)),
+                        "isplib: attention_spmm16 backward: outside isplib_attention16_serves for the gathered rows of x: M = ", M, ", K = ", K);
+            grad_y = at::empty({N, K}, y.options());
+            if (N > 0 && K > 0) {
+               const int st = isplib_attention16_bw_cols_hip(code, M, N, K, nnz, row_t.data_ptr<int64_t>(), colptr.data_ptr<int64_t>(),
+                                                             colptr.data_ptr<int64_t>() + 1, nnz > 0 ? xo.t.data_ptr() : nullptr, xo.ld,
+                                                             yo.t.data_ptr(), yo.ld, scale, nnz > 0 ? go.t.data_ptr() : nullptr, go.ld,
+                                                             lse.data_ptr<float>(), dsum.data_ptr<float>(), grad_y.data_ptr(), K,
+                                                             current_stream(x));
+               check_status(st, "isplib_attention16_bw_cols_hip");
+            }
+         }
+      }
+      return {Variable(), Variable(), Variable(), Variable(), grad_x, grad_y, Variable()};
+   }
+};
+
+Tensor attention_spmm16(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor x, Tensor y, double scale) {
+   return AttentionSpmm16::apply(rowptr, col, colptr, row_t, x, y, scale)[0];
+}
+
 // introspection / housekeeping of the per-graph handle cache of the reference-schema operators
 int64_t graph_cache_size() {
    std::lock_guard<std::mutex> lock(g_graph_mutex);
@@ -1322,4 +1422,5 @@ TORCH_LIBRARY(isplib, m) {
          "Tensor[] plan_t, Tensor? bias, bool relu) -> Tensor",
          &gcn_norm_spmm);
    m.def("attention_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor x, Tensor y, float scale) -> Tensor", &attention_spmm);
+   m.def("attention_spmm16(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor x, Tensor y, float scale) -> Tensor", &attention_spmm16);
 }

@@ -26,7 +26,8 @@ ISPLIB_HALF=auto|native|convert picks the route of bf16 / fp16 features (half_ro
 ISPLIB_HALF_MINMAX=convert|native|auto does the same for max / min (rows16_minmax_route), ISPLIB_HALF_MEAN_BW=convert|native|auto
 for the backward of a 16-bit `mean` on an unweighted graph (rows16_mean_bw_route), ISPLIB_HALF_DA=convert|native|auto for the value
 gradient of a 16-bit sum / mean (rows16_da_route), ISPLIB_HALF_GCN=convert|native|auto for gcn_norm_matmul on 16-bit features
-(rows16_gcn_route; unset: such a call raises, as it always did); the first three default to convert;
+(rows16_gcn_route; unset: such a call raises, as it always did), ISPLIB_HALF_ATTENTION=convert|native|auto for attention_matmul on
+16-bit operands (attention16_route; unset: such a call raises, as it always did); the first three default to convert;
 ISPLIB_TUNE_FILE names a tuning table to load at import; ISPLIB_DEBUG=1 prints per-operator device times.
 """
 from __future__ import annotations
@@ -387,6 +388,35 @@ def rows16_gcn_route(dtype, k: int, pitch: int, n: int, ordered: bool = False, m
     return _rows16_gate(dtype, mode, "ISPLIB_HALF_GCN", n, k, pitch, lambda cabi, ld: cabi.rows16_gcn_native_pays(n, ld, bool(ordered)))
 
 
+def attention16_route(dtype, k: int, pitch: int, n: int, mode: Optional[str] = None) -> str:
+    """Which way attention_matmul with 16-bit operands goes once ISPLIB_HALF_ATTENTION is set, asked per GATHERED operand (y with its
+    rows for the forward, x with its rows for the backward over the columns): "attention16" (torch.ops.isplib.attention_spmm16 on the
+    16-bit kernels, isplib_attention16_*_hip: x, y and the gradients as they lie, half the gathered bytes, no fp32 [*, K] tensor in
+    either direction) or "convert" (`x.float()` -> the fp32 operator -> `.to(dtype)`).  A pure function -- no device, no library call:
+      * attention16 needs bf16 / fp16 and the operand's shape, [n, k] at its own row pitch or, failing that, packed, inside the
+        entries' domain (cabi.attention16_serves: 8 <= k <= 512, k and the pitch even);
+      * `mode` is ISPLIB_HALF_ATTENTION (None: read from the environment; unset counts as "convert" here -- attention_matmul itself
+        raises before it asks -- and ISPLIB_HALF=convert wins over it): "convert" always converts, "native" takes the kernels wherever
+        the above holds, "auto" only in the classes -- the gathered operand beyond 256 MiB or not -- where every native run measured
+        faster than every run of the conversion route (cabi.attention16_native_pays, profiles/attention16_ab.txt).  Nothing raises."""
+    if dtype not in HALF_DTYPES:
+        return "convert"
+    from . import cabi
+    if mode is None:
+        mode = os.environ.get("ISPLIB_HALF", "auto")
+        if mode != "convert":
+            mode = os.environ.get("ISPLIB_HALF_ATTENTION", "convert")
+    if mode not in ("native", "auto"):
+        return "convert"
+    if cabi.attention16_serves(n, k, pitch):
+        ld = pitch
+    elif cabi.attention16_serves(n, k, k):
+        ld = k
+    else:
+        return "convert"
+    return "attention16" if mode == "native" or cabi.attention16_native_pays(n, ld) else "convert"
+
+
 _ROWS16_MARK = torch.tensor([16], dtype=torch.int32)      # second tensor of a 16-bit row plan (torch_ops.cpp: is_rows16_plan)
 _ROWS16_DA_MARK = torch.tensor([0xDA], dtype=torch.int32)  # third tensor of a forward plan whose dA runs in 16 bits (is_rows16_da_plan)
 
@@ -586,19 +616,25 @@ def attention_matmul(src, x: torch.Tensor, y: Optional[torch.Tensor] = None, sca
     stored values of `src` are not read; an empty row gives 0.  `x` [M, K], `y` [N, K] float32 GPU tensors; ``y=None`` means
     ``y = x`` (a square `src`; ``x.grad`` receives both contributions); ``scale=None`` means ``1 / sqrt(K)``.  Row-strided views keep
     their pitch, so multi-head use is one call per head on column views such as ``x[:, h*d:(h+1)*d]``.  The backward keeps x, y, z and
-    one scalar per row -- nothing per edge -- and walks the storage's cached transposed structure (colptr / row_t).  fp32 only;
-    there is no fallback route: outside isplib_attention_serves the call raises."""
+    one scalar per row -- nothing per edge -- and walks the storage's cached transposed structure (colptr / row_t).  fp32 only by
+    default; there is no fallback route: outside isplib_attention_serves the call raises.  bf16 / fp16 operands (both of one dtype) are
+    opt-in: with ISPLIB_HALF_ATTENTION=convert|native|auto set they go where attention16_route says -- the 16-bit operator
+    (torch.ops.isplib.attention_spmm16, which keeps x, y and lse for its backward and no z) or `x.float()` -> this function ->
+    `.to(dtype)`; the result and the gradients have the operands' dtype."""
     from . import cabi
     shared = y is None
+    half = isinstance(x, torch.Tensor) and x.dtype in HALF_DTYPES and os.environ.get("ISPLIB_HALF_ATTENTION") is not None
     for name, t in (("x", x),) + (() if shared else (("y", y),)):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"isplib_amd: `{name}` must be a tensor, got {type(t).__name__}")
         if t.dim() != 2:
             raise ValueError(f"isplib_amd: `{name}` must be 2-D [rows, k], got shape {tuple(t.shape)}")
-        if t.dtype != torch.float32:
+        if t.dtype != torch.float32 and not (half and t.dtype in HALF_DTYPES):
             raise TypeError(f"isplib_amd: `{name}` must be float32, got {t.dtype} (the attention operator is fp32 only)")
     if shared:
         y = x
+    if half and y.dtype != x.dtype:
+        raise TypeError(f"isplib_amd: `x` and `y` must have one dtype (both bfloat16 or both float16), got {x.dtype} and {y.dtype}")
     st = _storage_of(src, y)
     m_rows, n_cols = st._rowptr.numel() - 1, st._sparse_sizes[1]
     if shared and m_rows != n_cols:
@@ -610,6 +646,19 @@ def attention_matmul(src, x: torch.Tensor, y: Optional[torch.Tensor] = None, sca
     k = x.size(1)
     if y.size(1) != k:
         raise ValueError(f"isplib_amd: `x` and `y` must have one width, got {k} and {y.size(1)}")
+    if half:
+        # bf16 / fp16 operands, opt-in (ISPLIB_HALF_ATTENTION): the 16-bit operator where attention16_route admits BOTH gathered operands
+        # (y by the forward and the rows kernel, x by the columns kernel), else the conversion route, which raises what fp32 raises
+        def pitch_of(t, rows):
+            return t.stride(0) if rows > 1 and t.stride(1) == 1 and t.stride(0) >= k else k
+        native = all(attention16_route(t.dtype, k, pitch_of(t, rows), rows) == "attention16" for t, rows in ((y, n_cols), (x, m_rows)))
+        if not native or not x.is_cuda or not y.is_cuda:
+            x32 = x.float()
+            return attention_matmul(src, x32, None if shared else y.float(), scale).to(x.dtype)
+        if x.device != y.device or st._rowptr.device != x.device:
+            raise ValueError("isplib_amd: `x`, `y` and the sparse matrix must be on one device")
+        p = float(scale) if scale is not None else 1.0 / float(k) ** 0.5
+        return torch.ops.isplib.attention_spmm16(st._rowptr, st._col, st.colptr(), st.row_t(), x, y, p)
     if not 1 <= k <= cabi.ATTENTION_K_MAX:
         raise ValueError(f"isplib_amd: attention_matmul serves 1 <= K <= {cabi.ATTENTION_K_MAX} (a row sits in registers), got K = {k}")
     for name, t, rows in (("x", x, m_rows), ("y", y, n_cols)):     # y is gathered by the forward, x by the backward over the columns
