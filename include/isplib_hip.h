@@ -433,6 +433,36 @@ typedef struct isplib_stream_plan {
 int  isplib_stream_plan_build_hip(int64_t m, int64_t n, int64_t nnz, const int64_t *rowptr, const int64_t *col,
                                   const float *val, int streams, int slices, int chunk, int waves_per_gen,
                                   isplib_stream_plan *out /*host*/, void *stream);
+/* LEVELLED DEAL (profiles/stream_level.txt).  The workgroups of a dispatch do not all gather at the same speed:
+ * the eight XCDs differ by 1-2 %, a CU's second workgroup runs ~4 % behind its first, both persistently, and a dispatch ends
+ * with its slowest wave.  Step 2 of the construction therefore
+ * gives every stream a CAPACITY (fixed point, ISPLIB_STREAM_CAP_ONE = nominal) and orders the streams of a round by
+ * load * ISPLIB_STREAM_CAP_ONE / capacity (integer division, saturated at 2^32 - 1) instead of by load: a slow XCD's streams get
+ * fewer edges.  The deal only decides WHICH wave holds a row: every row's words and their order are unchanged; equal capacities
+ * give today's plan arrays exactly.  A row's sum has the unlevelled plan's bits wherever the row is flushed at every column-slice
+ * boundary in both plans -- the kernel adds a running sum to the row's LDS line when its stream turns to ANOTHER row, so a row
+ * with no other row of its stream between its words of two slices is summed straight through, and which rows share a stream is
+ * what the deal changes.  Streams of many rows with entries in every slice carry nothing (the headline: the whole output bitwise
+ * equal); a plan of two or three short rows per stream may differ in the last bits of such rows, as it does between two slice
+ * counts.  For a given plan every sum is formed in one fixed order, as before.
+ * A capacity belongs to a wave of the generation (all its streams, in every generation): caps[w], w < waves_per_gen.
+ * isplib_stream_capacities_hip fills caps for the sum / mean kernel of `streams` slots on `device` (< 0: the current one): a
+ * calibration made once per (device, streams, waves_per_gen) and process -- one generation of the stream kernel itself, timed
+ * per wave, on a synthetic plan (~11 ms; 2.7 GB of device memory at its peak, measured, released before it returns; no room: equal
+ * capacities, *levelled = 0, no error, and the next plan build asks again), averaged per
+ * XCD (workgroup index modulo 8) and residency order (the first or a later workgroup of its CU): speed assumptions only -- or
+ * equal capacities where levelling does not apply: ISPLIB_STREAM_LEVEL=0, a waves_per_gen other than the resident waves
+ * isplib_spmm_stream_geometry reports (<= 0 means those), and under auto (unset) nnz < 4 Mi, where the stream schedule is not
+ * offered either.  *levelled (may be NULL) tells which.  ISPLIB_STREAM_LEVEL=auto|0|1 is read once; 1 levels at any nnz.
+ * Max / min and FusedMM plans are never levelled.  The calibration never runs inside a call.
+ * isplib_stream_plan_build_hip asks it itself; isplib_stream_plan_build_caps_hip takes the capacities from the caller
+ * (host array of waves_per_gen entries in [ISPLIB_STREAM_CAP_ONE / 16, ISPLIB_STREAM_CAP_ONE * 16]; NULL: equal). */
+#define ISPLIB_STREAM_CAP_ONE 4096u
+int  isplib_stream_capacities_hip(int device, int streams, int waves_per_gen, int64_t nnz, uint32_t *caps /*host, out*/,
+                                  int *levelled /*out*/, void *stream);
+int  isplib_stream_plan_build_caps_hip(int64_t m, int64_t n, int64_t nnz, const int64_t *rowptr, const int64_t *col,
+                                       const float *val, int streams, int slices, int chunk, int waves_per_gen,
+                                       const uint32_t *caps /*host*/, isplib_stream_plan *out /*host*/, void *stream);
 int  isplib_stream_plan_set_values_hip(isplib_stream_plan *plan, const float *val /*[dev] nnz | NULL*/, void *stream);
 void isplib_stream_plan_free(isplib_stream_plan *plan);
 int    isplib_spmm_stream_geometry(int streams, int *rows_per_wave /*out*/, int *waves_resident /*out*/);

@@ -182,7 +182,7 @@ EXPORTS = (
     "isplib_sddmm_csr_tasks_hip", "fusedMM_csr_tasks_epilogue_hip", "fusedMM_csr_udef_hip", "fusedMM_csr_udef_tasks_hip", "isplib_pack_indices_hip",
     "isplib_suggest_slices", "isplib_graph_create", "isplib_graph_set_slices", "isplib_graph_set_values", "isplib_graph_spmm", "isplib_graph_spmm_backward",
     "isplib_graph_destroy", "isplib_suggest_slices_whole_rows", "isplib_graph_sddmm",
-    "fusedMM_csr_stream_hip", "isplib_spmm_stream_workspace_bytes", "isplib_spmm_stream_geometry", "isplib_suggest_stream", "isplib_suggest_stream_weighted", "isplib_stream_plan_build_hip", "isplib_stream_plan_build_minmax_hip", "fusedMM_csr_stream_minmax_hip", "isplib_spmm_stream_minmax_geometry", "isplib_suggest_stream_minmax", "isplib_spmm_stream_minmax_workspace_bytes", "isplib_stream_plan_set_values_hip", "isplib_stream_plan_free", "isplib_spmm_minmax_bw_det_hip", "isplib_spmm_minmax_bw_workspace_bytes", "isplib_scatter_rows_det_hip",
+    "fusedMM_csr_stream_hip", "isplib_spmm_stream_workspace_bytes", "isplib_spmm_stream_geometry", "isplib_suggest_stream", "isplib_suggest_stream_weighted", "isplib_stream_plan_build_hip", "isplib_stream_plan_build_caps_hip", "isplib_stream_capacities_hip", "isplib_stream_plan_build_minmax_hip", "fusedMM_csr_stream_minmax_hip", "isplib_spmm_stream_minmax_geometry", "isplib_suggest_stream_minmax", "isplib_spmm_stream_minmax_workspace_bytes", "isplib_stream_plan_set_values_hip", "isplib_stream_plan_free", "isplib_spmm_minmax_bw_det_hip", "isplib_spmm_minmax_bw_workspace_bytes", "isplib_scatter_rows_det_hip",
     "isplib_minmax_bw_bucket_workspace_bytes", "isplib_minmax_bw_bucket_hip", "isplib_scatter_keys_workspace_bytes", "isplib_scatter_keys_det_hip",
     "isplib_fusedmm_stream_geometry", "isplib_suggest_fusedmm_stream", "isplib_stream_plan_build_fusedmm_hip", "fusedMM_csr_udef_stream_hip",
     "isplib_row_scale_hip", "isplib_masked_scale_colsum_hip", "isplib_masked_scale_colsum_workspace_bytes",
@@ -360,6 +360,13 @@ def lib() -> ctypes.CDLL:
         L.isplib_stream_plan_build_hip.restype = ctypes.c_int
         L.isplib_stream_plan_build_hip.argtypes = [_i64, _i64, _i64, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                    ctypes.POINTER(StreamPlanStruct), _vp]
+        L.isplib_stream_plan_build_caps_hip.restype = ctypes.c_int
+        L.isplib_stream_plan_build_caps_hip.argtypes = [_i64, _i64, _i64, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                        _vp, ctypes.POINTER(StreamPlanStruct), _vp]
+        L.isplib_stream_capacities_hip.restype = ctypes.c_int
+        L.isplib_stream_capacities_hip.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, _vp, ctypes.POINTER(ctypes.c_int), _vp]
+        L.isplib_stream_level_set.restype = ctypes.c_int
+        L.isplib_stream_level_set.argtypes = [ctypes.c_int]
         L.isplib_stream_plan_build_minmax_hip.restype = ctypes.c_int
         L.isplib_stream_plan_build_minmax_hip.argtypes = [_i64, _i64, _i64, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                           ctypes.POINTER(StreamPlanStruct), _vp]
@@ -2040,7 +2047,10 @@ class NativeStreamPlan:
     isplib_amd.plan.build_stream_plan; same interface as plan.StreamPlan for the boundary wrappers."""
 
     def __init__(self, rowptr, col, val, ncols: int, streams: int, slices: int, chunk: int, waves_per_gen: int = 0,
-                 minmax: bool = False, fusedmm: bool = False):
+                 minmax: bool = False, fusedmm: bool = False, capacities=None):
+        """capacities (sum / mean plans): the levelled deal with the caller's capacities, one per wave of a generation
+        (isplib_stream_plan_build_caps_hip); None: the library's own (isplib_stream_plan_build_hip)."""
+        assert capacities is None or not (minmax or fusedmm), "max / min and FusedMM plans keep equal capacities"
         self._s = StreamPlanStruct()
         self.device = col.device
         m = rowptr.numel() - 1
@@ -2053,6 +2063,14 @@ class NativeStreamPlan:
                 _check(lib().isplib_stream_plan_build_minmax_hip(m, int(ncols), col.numel(), _ptr(rowptr), _ptr(col), _ptr(val),
                                                                  int(streams), int(slices), int(chunk), int(waves_per_gen), ctypes.byref(self._s),
                                                                  _stream(col.device)), "isplib_stream_plan_build_minmax_hip")
+            elif capacities is not None:
+                caps = (ctypes.c_uint32 * len(capacities))(*[int(c) for c in capacities])
+                rpw, resident = stream_geometry(streams)
+                if len(caps) != (int(waves_per_gen) if waves_per_gen > 0 else resident):
+                    raise ValueError("one capacity per wave of a generation")
+                _check(lib().isplib_stream_plan_build_caps_hip(m, int(ncols), col.numel(), _ptr(rowptr), _ptr(col), _ptr(val), int(streams),
+                                                               int(slices), int(chunk), int(waves_per_gen), ctypes.cast(caps, _vp),
+                                                               ctypes.byref(self._s), _stream(col.device)), "isplib_stream_plan_build_caps_hip")
             else:
                 _check(lib().isplib_stream_plan_build_hip(m, int(ncols), col.numel(), _ptr(rowptr), _ptr(col), _ptr(val), int(streams),
                                                           int(slices), int(chunk), int(waves_per_gen), ctypes.byref(self._s),
@@ -2109,6 +2127,31 @@ class NativeStreamPlan:
             self.close()
         except Exception:  # noqa: BLE001 - interpreter shutdown
             pass
+
+
+STREAM_CAP_ONE = 4096          # ISPLIB_STREAM_CAP_ONE: the nominal capacity of the levelled deal
+
+
+def stream_capacities(device, streams: int, waves_per_gen: int, nnz: int):
+    """The capacities of the levelled deal for a sum / mean plan of this geometry on `device` (isplib_stream_capacities_hip: the
+    library's rule and its once-per-process calibration): a list of waves_per_gen integers, or None where the deal stays
+    unlevelled (ISPLIB_STREAM_LEVEL=0, another waves_per_gen than the resident waves, a small graph under auto)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        return None
+    _, resident = stream_geometry(streams)
+    wpg = int(waves_per_gen) if waves_per_gen > 0 else resident
+    caps = (ctypes.c_uint32 * wpg)()
+    levelled = ctypes.c_int(0)
+    with torch.cuda.device(device):
+        _check(lib().isplib_stream_capacities_hip(-1, int(streams), wpg, int(nnz), ctypes.cast(caps, _vp), ctypes.byref(levelled),
+                                                  _stream(device)), "isplib_stream_capacities_hip")
+    return list(caps) if levelled.value else None
+
+
+def stream_level_set(mode: int) -> None:
+    """A/B runs and tests: 0 off, 1 on, 2 auto (overrides ISPLIB_STREAM_LEVEL; plans built afterwards)."""
+    _check(lib().isplib_stream_level_set(int(mode)), "isplib_stream_level_set")
 
 
 def stream_geometry(streams: int = 4):

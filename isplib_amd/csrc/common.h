@@ -13,6 +13,10 @@ int empty_row_init();   // 1: an empty row of max / min keeps the reference laun
 
 int stream_stage_mode();                     // ISPLIB_STAGE_*: staged column panels of the stream schedule (ISPLIB_STREAM_STAGE; runtime.hip)
 void stream_stage_report(unsigned panels);   // which panels the call staged (isplib_stream_stage_last)
+// mean loop ticks of every wave of one generation of the sum / mean stream kernel on a synthetic plan (spmm_sweep.hip): the calibration
+// behind isplib_stream_capacities_hip (stream_plan.hip); `launches` timed launches after one that is not counted
+int stream_kernel_calibrate(int streams, int waves_per_gen, int launches, int degree, int col_mult, double *wave_ticks, hipStream_t st);
+int stream_level_mode();                     // 0 off, 1 on, 2 auto: the levelled deal of the stream plans (ISPLIB_STREAM_LEVEL; runtime.hip)
 
 inline void clear_error() { error_buffer()[0] = '\0'; }
 

@@ -62,5 +62,26 @@ extern "C" int isplib_stream_stage_set(int mode) {
 }
 extern "C" unsigned isplib_stream_stage_last(void) { return isplib::g_stream_stage_last; }
 
+// The levelled deal of the stream plans (include/isplib_hip.h, isplib_stream_capacities_hip): ISPLIB_STREAM_LEVEL=auto|0|1 read
+// once; unset: auto (profiles/stream_level_ab.txt holds the A/B).  isplib_stream_level_set overrides it for A/B runs and tests
+// (0 off, 1 on, 2 auto; not declared in the header).  0 gives the unlevelled plan, and with it the unlevelled launch, exactly.
+namespace isplib {
+static int g_stream_level = -1;
+int stream_level_mode() {
+   if (g_stream_level < 0) {
+      const char *e = getenv("ISPLIB_STREAM_LEVEL");
+      g_stream_level = !e ? 2 : strcmp(e, "0") == 0 ? 0 : strcmp(e, "1") == 0 ? 1 : 2;
+   }
+   return g_stream_level;
+}
+}  // namespace isplib
+
+extern "C" int isplib_stream_level_set(int mode) {
+   isplib::clear_error();
+   if (mode < 0 || mode > 2) return isplib::fail(ISPLIB_FAIL, "isplib_stream_level_set: 0 (off), 1 (on) or 2 (auto)");
+   isplib::g_stream_level = mode;
+   return ISPLIB_SUCCESS;
+}
+
 extern "C" int isplib_hip_abi_version(void) { return ISPLIB_HIP_ABI_VERSION; }
 extern "C" const char *isplib_hip_last_error(void) { return isplib::error_buffer(); }

@@ -10,7 +10,11 @@
 // finished rows ever leaves the CU: no partial rows (but for hub rows cut into virtual rows), no fold, z written once.
 // (The file keeps its name from the round-2 "sweep" schedule, the first of this family; that kernel, the LDS hot-row hybrid
 // and the stream-plan SDDMM -- all measured slower than what is here -- live in experimental/experimental.hip.)
+#include <vector>
+
 #include "sweep_common.h"
+
+extern "C" void isplib_debug_wave_times(unsigned long long *buf);
 
 namespace isplib {
 
@@ -24,7 +28,9 @@ namespace isplib {
 // wave own disjoint rows and a wave's LDS operations execute in order, so every sum is formed in one fixed order.
 // U gathers are in flight per wave at all times, across row and slice boundaries alike; there is no butterfly, no
 // masked tail, no per-segment bookkeeping.  Sum / mean only.
-template <int LPR, bool HAS_VAL, int NVMAX, int NBW, int WGS>
+// TIMED (the calibration of the levelled deal, isplib_stream_capacities_hip, and scripts/exp_wave_times.py): the same kernel, and
+// every wave also reports when it started, entered and left its loop and finished (s_memtime), and where it ran.
+template <int LPR, bool HAS_VAL, int NVMAX, int NBW, int WGS, bool TIMED = false>
 __global__ __launch_bounds__(256, (stream_wgs_per_cu<LPR, NVMAX, WGS>())) void spmm_stream_kernel(const SweepArgs a) {
    using Wave = StreamWave<LPR, NVMAX, NBW>;
    constexpr int WAVES = Wave::WAVES, G = Wave::G, PANEL = Wave::PANEL, U = Wave::U, PER = Wave::PER;
@@ -34,9 +40,8 @@ __global__ __launch_bounds__(256, (stream_wgs_per_cu<LPR, NVMAX, WGS>())) void s
    Wave sw;
    if (!stream_wave_id(a, sw)) return;                   // no barrier anywhere below
    const int lane = sw.lane;
-#ifdef ISPLIB_EXP_WAVE_TIMES
-   const unsigned long long t_start = __builtin_amdgcn_s_memtime();
-#endif
+   unsigned long long t_start = 0, t_loop = 0, t_loop_end = 0;
+   if constexpr (TIMED) t_start = __builtin_amdgcn_s_memtime();
    float *my = s_all + sw.wave * WAVE_FLOATS;
    for (int i = lane * 4; i < WAVE_FLOATS; i += 256)
       *reinterpret_cast<float4 *>(my + i) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -62,9 +67,7 @@ __global__ __launch_bounds__(256, (stream_wgs_per_cu<LPR, NVMAX, WGS>())) void s
    unsigned cur = (unsigned)(sw.g * PER * PANEL);         // the row whose running sum the registers hold (stream_flush)
    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
    const int64_t nb = (sw.nwords + 64 * NBW - 1) / (64 * NBW);
-#ifdef ISPLIB_EXP_WAVE_TIMES
-   const unsigned long long t_loop = __builtin_amdgcn_s_memtime();
-#endif
+   if constexpr (TIMED) t_loop = __builtin_amdgcn_s_memtime();
    for (int64_t b = 0; b < nb; b++) {
       // the U gathers of batch b are in flight; each one consumed is replaced by the same step of batch b + 1
       float vnext = HAS_VAL ? __shfl(v0[0], sw.g) : 0.0f;
@@ -90,9 +93,7 @@ __global__ __launch_bounds__(256, (stream_wgs_per_cu<LPR, NVMAX, WGS>())) void s
       if (HAS_VAL) stream_load_batch(sw, vp, (b + 2) * 64 * NBW, 0.0f, v1);
    }
    stream_flush(lane_base + cur, acc);
-#ifdef ISPLIB_EXP_WAVE_TIMES
-   const unsigned long long t_loop_end = __builtin_amdgcn_s_memtime();
-#endif
+   if constexpr (TIMED) t_loop_end = __builtin_amdgcn_s_memtime();
    // write-out: slot q owns the local rows [q * PER, (q + 1) * PER); its LPR lanes hold one row of the panel.  The rows' ids
    // (two dependent global loads per row) are fetched for the whole slot first and the rows then go out four at a time: a
    // row-at-a-time loop pays every row's memory latencies one after the other (2 % of a dispatch, scripts/exp_wave_times.py)
@@ -120,14 +121,14 @@ __global__ __launch_bounds__(256, (stream_wgs_per_cu<LPR, NVMAX, WGS>())) void s
       finish_row<OP_ADD>(a, row, c, v, bi, arg);
       store_tail<4>(a.z + (size_t)row * (size_t)a.ldz + c, v, sw.vfirst);
    }
-#ifdef ISPLIB_EXP_WAVE_TIMES
-   if (a.dbg && lane == 0) {
-      a.dbg[(size_t)sw.wl * 4 + 0] = t_start;
-      a.dbg[(size_t)sw.wl * 4 + 1] = t_loop;
-      a.dbg[(size_t)sw.wl * 4 + 2] = t_loop_end;
-      a.dbg[(size_t)sw.wl * 4 + 3] = __builtin_amdgcn_s_memtime();
+   if constexpr (TIMED) if (a.dbg && lane == 0) {
+      a.dbg[(size_t)sw.wl * 5 + 0] = t_start;
+      a.dbg[(size_t)sw.wl * 5 + 1] = t_loop;
+      a.dbg[(size_t)sw.wl * 5 + 2] = t_loop_end;
+      a.dbg[(size_t)sw.wl * 5 + 3] = __builtin_amdgcn_s_memtime();
+      // where the wave ran: (XCC id << 24) | bits 8..23 of HW_ID (CU, SH, SE); s_getreg operand = id | (bits - 1) << 11
+      a.dbg[(size_t)sw.wl * 5 + 4] = (__builtin_amdgcn_s_getreg(20u | (3u << 11)) << 24) | ((__builtin_amdgcn_s_getreg(4u | (31u << 11)) >> 8) & 0xFFFFu);
    }
-#endif
 }
 
 // max / min on the stream schedule.  The running sum becomes the best value so far and the WORD INDEX (position in the
@@ -360,19 +361,23 @@ static int launch_stage_copy(const float *y, int64_t ldy, int64_t n, float *dst,
    return check_launch("stream_stage_copy_kernel");
 }
 
-#ifdef ISPLIB_EXP_WAVE_TIMES
-static unsigned long long *g_dbg = nullptr;      // set by isplib_debug_wave_times; one slab per launch, four launches
-static int g_dbg_launch = 0;
-#endif
+// set by isplib_debug_wave_times, for the calling thread's launches: [dispatch % 4][wave][5], the TIMED kernel's stamps
+static thread_local unsigned long long *g_dbg = nullptr;
+static thread_local int g_dbg_launch = 0;
 template <int STREAMS, bool HAS_VAL>
 static int launch_stream(const SweepArgs &a_in, hipStream_t st) {
    constexpr StreamGeom ge = stream_geom(STREAM_SUM, STREAMS);
    SweepArgs a = a_in;
-#ifdef ISPLIB_EXP_WAVE_TIMES
-   a.dbg = g_dbg ? g_dbg + (size_t)(g_dbg_launch++ % 4) * (size_t)a.wave_count * 4 : nullptr;
-#endif
    const unsigned blocks = (unsigned)((a.wave_count + 3) / 4);
    if (blocks == 0) return ISPLIB_SUCCESS;
+   // the TIMED instance exists for unit-weight plans only: what the calibration and the experiment scripts launch
+   if constexpr (!HAS_VAL) {
+      if (g_dbg) {
+         a.dbg = g_dbg + (size_t)(g_dbg_launch++ % 4) * (size_t)a.wave_count * 5;
+         hipLaunchKernelGGL((spmm_stream_kernel<ge.lpr, false, ge.nvmax, ge.nbw, ge.wgs, true>), dim3(blocks), dim3(256), 0, st, a);
+         return check_launch("spmm_stream_kernel");
+      }
+   }
    hipLaunchKernelGGL((spmm_stream_kernel<ge.lpr, HAS_VAL, ge.nvmax, ge.nbw, ge.wgs>), dim3(blocks), dim3(256), 0, st, a);
    return check_launch("spmm_stream_kernel");
 }
@@ -559,7 +564,69 @@ extern "C" int fusedMM_csr_stream_minmax_hip(int32_t imessage, int64_t m, int64_
    return stream_run(imessage, m, n, k, nnz, pntrb, pntre, plan, y, ldy, z, ldz, z_arg, workspace, workspace_bytes, nullptr, stream);
 }
 
-#ifdef ISPLIB_EXP_WAVE_TIMES
-// experiment builds only (scripts/exp_wave_times.py; not declared in include/isplib_hip.h)
+// ---- the calibration of the levelled deal (isplib_stream_capacities_hip, stream_plan.hip) ---------------------------------------
+// One generation of the stream kernel, TIMED, on a synthetic graph: waves_per_gen * rows_per_wave rows of `degree` stored entries
+// each in pseudo-random columns of a matrix with col_mult times as many columns, one column panel, the plan built with equal
+// capacities -- every wave the same work, in L2-sized slices like a real launch's.  What differs between the waves' loop times is
+// then where and when they ran.  ~11 ms and 2.7 GB of device memory at its peak at 512 entries per row; once per (device, geometry) and process, never inside a call.
+namespace isplib {
+__global__ __launch_bounds__(256) void stream_calib_graph_kernel(int64_t n, int64_t ncols, int64_t degree, int64_t *__restrict__ rowptr, int64_t *__restrict__ col) {
+   const int64_t stride = (int64_t)gridDim.x * blockDim.x, nnz = n * degree;
+   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= n; i += stride) rowptr[i] = i * degree;
+   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < nnz; e += stride) {
+      uint64_t h = (uint64_t)e * 0x9E3779B97F4A7C15ull;
+      h ^= h >> 29; h *= 0xBF58476D1CE4E5B9ull; h ^= h >> 32;
+      col[e] = (int64_t)(h % (uint64_t)ncols);
+   }
+}
+
+int stream_kernel_calibrate(int streams, int waves_per_gen, int launches, int degree, int col_mult, double *wave_ticks, hipStream_t st) {
+   int rpw = 0, resident = 0;
+   if (isplib_spmm_stream_geometry(streams, &rpw, &resident) != ISPLIB_SUCCESS) return ISPLIB_FAIL;
+   if (waves_per_gen < 4 || waves_per_gen % 4 != 0 || waves_per_gen > resident || launches < 1 || launches > 16 || degree < 1 || degree > 1024 ||
+       col_mult < 1 || col_mult > 8)
+      return fail(ISPLIB_FAIL, "stream calibration: whole workgroups of one resident generation, 1..16 launches");
+   const int64_t n = (int64_t)waves_per_gen * rpw, ncols = n * col_mult, nnz = n * degree, k = 256 / streams;
+   struct Temps {
+      std::vector<void *> p;
+      isplib_stream_plan plan;
+      unsigned long long *callers_dbg = g_dbg;                // a buffer the caller holds (an experiment script) is put back
+      Temps() { memset(&plan, 0, sizeof(plan)); }
+      ~Temps() { isplib_debug_wave_times(callers_dbg); isplib_stream_plan_free(&plan); for (void *q : p) (void)hipFree(q); }
+      void *get(size_t bytes) { void *q = nullptr; if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; } p.push_back(q); return q; }
+   } T;
+   int64_t *rowptr = (int64_t *)T.get((size_t)(n + 1) * 8), *col = (int64_t *)T.get((size_t)nnz * 8);
+   float *y = (float *)T.get((size_t)ncols * k * 4), *z = (float *)T.get((size_t)n * k * 4);
+   unsigned long long *dbg = (unsigned long long *)T.get((size_t)4 * waves_per_gen * 5 * 8);
+   if (!rowptr || !col || !y || !z || !dbg) return fail(ISPLIB_NOT_ENOUGH_MEM, "stream calibration: device allocation failed");
+   hipLaunchKernelGGL(stream_calib_graph_kernel, dim3(4096), dim3(256), 0, st, n, ncols, (int64_t)degree, rowptr, col);
+   int rc = check_launch("stream_calib_graph_kernel");
+   if (rc) return rc;
+   ISPLIB_HIP_TRY(hipMemsetAsync(y, 0, (size_t)ncols * k * 4, st));
+   int slices = (int)((ncols * k * 4 + 1900000 - 1) / 1900000);
+   if (slices < 1) slices = 1;
+   if ((rc = isplib_stream_plan_build_caps_hip(n, ncols, nnz, rowptr, col, nullptr, streams, slices, 4 * degree, waves_per_gen, nullptr, &T.plan, st)) != ISPLIB_SUCCESS) return rc;
+   if (T.plan.gens != 1 || T.plan.n_hub != 0) return fail(ISPLIB_FAIL, "stream calibration: internal: the synthetic plan is not one generation");
+   std::vector<unsigned long long> h((size_t)waves_per_gen * 5);
+   for (int w = 0; w < waves_per_gen; w++) wave_ticks[w] = 0.0;
+   for (int l = 0; l <= launches; l++) {
+      isplib_debug_wave_times(l ? dbg : nullptr);            // (the first launch is not counted)
+      rc = fusedMM_csr_stream_hip(ISPLIB_MSG_SPMM_SUM, n, ncols, k, nnz, rowptr, rowptr + 1, &T.plan, y, k, z, k, nullptr, 0, nullptr, st);
+      isplib_debug_wave_times(nullptr);                      // (and nothing else of this thread's is timed into dbg)
+      if (rc) return rc;
+      if (!l) continue;
+      ISPLIB_HIP_TRY(hipMemcpyAsync(h.data(), dbg, h.size() * 8, hipMemcpyDeviceToHost, st));
+      ISPLIB_HIP_TRY(hipStreamSynchronize(st));
+      for (int w = 0; w < waves_per_gen; w++) wave_ticks[w] += (double)(h[(size_t)w * 5 + 2] - h[(size_t)w * 5 + 1]) / launches;
+   }
+   return ISPLIB_SUCCESS;
+}
+}  // namespace isplib
+
+// experiments (scripts/exp_wave_times.py, scripts/exp_stream_level.py; not declared in include/isplib_hip.h): while buf is set, the
+// unit-weight sum / mean dispatches of THIS THREAD run the TIMED kernel and write their stamps to it.  The contract of buf: device
+// memory of 4 x W x 5 unsigned 64-bit words, W = the largest wave count of a dispatch launched meanwhile (the plan's
+// waves_per_gen); dispatch number d since the call writes slab d % 4, wave w of it the five words at (d % 4) * wave_count * 5 +
+// w * 5: s_memtime at start / loop entry / loop exit / end, then (XCC id << 24) | HW_ID bits 8..23.  Nothing checks the size: the
+// caller sizes it by the plan it launches.  NULL ends it.  A calibration that runs meanwhile puts the buffer back when it is done.
 extern "C" void isplib_debug_wave_times(unsigned long long *buf) { isplib::g_dbg = buf; isplib::g_dbg_launch = 0; }
-#endif

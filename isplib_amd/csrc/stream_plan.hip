@@ -3,7 +3,8 @@
 // releases them.  The same construction as isplib_amd/plan.py: stream_plan_arrays (which the tests replay on the CPU):
 //   1. rows over `chunk` edges are dealt edge by edge, round robin, to ceil(deg / chunk) virtual rows;
 //   2. virtual rows, longest first (stable radix sort), are dealt to the streams in rounds of one row per stream, the
-//      longest row of a round to the stream holding the fewest edges so far (stable sort of the loads per round);
+//      longest row of a round to the stream holding the fewest edges so far (stable sort of the loads per round) -- fewest in
+//      proportion to the stream's CAPACITY where the deal is levelled (include/isplib_hip.h, isplib_stream_capacities_hip);
 //   3. every edge gets the key (stream, column slice, row of the stream); a stable radix sort of the keys yields each
 //      stream's words in walking order -- slice by slice, row by row, CSR order inside;
 //   4. the `streams` streams of a wave are interleaved step by step and padded to the longest.
@@ -12,13 +13,17 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <map>
+#include <mutex>
 #include <new>
+#include <tuple>
 #include <vector>
 
 #include "../../include/isplib_hip.h"
 #include "common.h"
 
 #include "prims.h"
+#include "sweep_common.h"
 
 namespace isplib {
 
@@ -84,6 +89,17 @@ __global__ __launch_bounds__(256) void sp_deal_kernel(int64_t cnt, int round, co
       sid[item] = (int)s;
       rnd[item] = round;
       loads[s] += (uint32_t)vlen[item];
+   }
+}
+
+// levelled deal: the sort key of a stream is its load in units of its capacity (caps: one per wave of a generation); the same
+// integer expression as plan.py: stream_plan_arrays
+__global__ __launch_bounds__(256) void sp_deal_keys_kernel(int64_t ns, int streams, int waves_per_gen, const uint32_t *__restrict__ loads,
+                                                           const uint32_t *__restrict__ caps, uint32_t *__restrict__ keys) {
+   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+   for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < ns; s += stride) {
+      const uint64_t key = (uint64_t)loads[s] * ISPLIB_STREAM_CAP_ONE / caps[(s / streams) % waves_per_gen];
+      keys[s] = key > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)key;
    }
 }
 
@@ -250,7 +266,7 @@ extern "C" int isplib_stream_plan_set_values_hip(isplib_stream_plan *plan, const
 
 static int stream_plan_build(int64_t m, int64_t n, int64_t nnz, const int64_t *rowptr, const int64_t *col, const float *val,
                              int streams, int rpw, int resident, int slices, int chunk, int waves_per_gen,
-                             isplib_stream_plan *out, void *stream, int pad_row = -1) {
+                             isplib_stream_plan *out, void *stream, int pad_row = -1, const uint32_t *caps = nullptr) {
    if (!out) return fail(ISPLIB_FAIL, "isplib_stream_plan_build_hip: out is NULL");
    memset(out, 0, sizeof(*out));
    if (m <= 0 || n <= 0 || nnz < 0 || !rowptr || (nnz > 0 && !col)) return fail(ISPLIB_FAIL, "isplib_stream_plan_build_hip: bad operand");
@@ -260,6 +276,15 @@ static int stream_plan_build(int64_t m, int64_t n, int64_t nnz, const int64_t *r
    const int per = rpw / streams;
    hipStream_t st = (hipStream_t)stream;
    SpTemp T;
+   if (caps) {                                              // equal capacities ARE the unlevelled deal (whatever their common value)
+      bool equal = true;
+      for (int w = 0; w < waves_per_gen; w++) {
+         if (caps[w] < ISPLIB_STREAM_CAP_ONE / 16 || caps[w] > ISPLIB_STREAM_CAP_ONE * 16)
+            return fail(ISPLIB_FAIL, "isplib_stream_plan_build_caps_hip: a capacity outside [ISPLIB_STREAM_CAP_ONE / 16, ISPLIB_STREAM_CAP_ONE * 16]");
+         equal = equal && caps[w] == caps[0];
+      }
+      if (equal) caps = nullptr;
+   }
    // 1. virtual rows
    int *nchunk, *hub_flag, *first, *hub_idx;
    if (!T.alloc(&nchunk, (size_t)m) || !T.alloc(&hub_flag, (size_t)m) || !T.alloc(&first, (size_t)m + 1) || !T.alloc(&hub_idx, (size_t)m + 1))
@@ -292,12 +317,14 @@ static int stream_plan_build(int64_t m, int64_t n, int64_t nnz, const int64_t *r
    if (gens > 4096 || ns >= (1LL << 31) || (double)ns * slices * per >= 4294967295.0)
       return fail(ISPLIB_FAIL, "isplib_stream_plan_build_hip: graph too large for this geometry (32-bit stream keys)");
    int *vrow_row, *vlen, *vhub, *part_of, *sid, *rnd;
-   uint32_t *k_in, *k_out, *v_in, *v_out, *loads, *lk_out, *lv_in, *lv_out;
+   uint32_t *k_in, *k_out, *v_in, *v_out, *loads, *lk_out, *lv_in, *lv_out, *lk_in = nullptr, *d_caps = nullptr;
    const size_t big = (size_t)(nnz > nv ? nnz : nv) + 1;
    if (!T.alloc(&vrow_row, (size_t)nv) || !T.alloc(&vlen, (size_t)nv) || !T.alloc(&vhub, (size_t)nv) || !T.alloc(&part_of, (size_t)nv + 1) ||
        !T.alloc(&sid, (size_t)nv) || !T.alloc(&rnd, (size_t)nv) || !T.alloc(&k_in, big) || !T.alloc(&k_out, big) || !T.alloc(&v_in, big) ||
        !T.alloc(&v_out, big) || !T.alloc(&loads, (size_t)ns) || !T.alloc(&lk_out, (size_t)ns) || !T.alloc(&lv_in, (size_t)ns) ||
        !T.alloc(&lv_out, (size_t)ns))
+      return fail(ISPLIB_NOT_ENOUGH_MEM, "isplib_stream_plan_build_hip: device allocation failed");
+   if (caps && (!T.alloc(&lk_in, (size_t)ns) || !T.alloc(&d_caps, (size_t)waves_per_gen)))
       return fail(ISPLIB_NOT_ENOUGH_MEM, "isplib_stream_plan_build_hip: device allocation failed");
    int32_t *hub_row = nullptr, *hub_off = nullptr;
    if (!sp_alloc_out(&hub_row, (size_t)n_hub) || !sp_alloc_out(&hub_off, (size_t)n_hub + 1)) {
@@ -330,12 +357,17 @@ static int stream_plan_build(int64_t m, int64_t n, int64_t nnz, const int64_t *r
    SP_TRY(hipMemsetAsync(loads, 0, (size_t)ns * sizeof(uint32_t), st));
    hipLaunchKernelGGL(sp_iota_kernel, dim3(sp_grid(ns)), dim3(256), 0, st, ns, lv_in);
    SP_LAUNCHED("sp_iota_kernel");
+   if (caps) SP_TRY(hipMemcpyAsync(d_caps, caps, (size_t)waves_per_gen * sizeof(uint32_t), hipMemcpyHostToDevice, st));
    const int rounds = (int)((nv + ns - 1) / ns);
    if (rounds > per) SP_FAIL(ISPLIB_FAIL, "isplib_stream_plan_build_hip: internal: more rounds than rows per stream");
    for (int r = 0; r < rounds; r++) {
       const int64_t cnt = nv - (int64_t)r * ns < ns ? nv - (int64_t)r * ns : ns;
       tb = sort_small;
-      SP_TRY(sp_sort(sort_tmp, tb, loads, lk_out, lv_in, lv_out, (size_t)ns, 32, st));
+      if (caps) {
+         hipLaunchKernelGGL(sp_deal_keys_kernel, dim3(sp_grid(ns)), dim3(256), 0, st, ns, streams, waves_per_gen, loads, d_caps, lk_in);
+         SP_LAUNCHED("sp_deal_keys_kernel");
+      }
+      SP_TRY(sp_sort(sort_tmp, tb, caps ? lk_in : loads, lk_out, lv_in, lv_out, (size_t)ns, 32, st));
       hipLaunchKernelGGL(sp_deal_kernel, dim3(sp_grid(cnt)), dim3(256), 0, st, cnt, r, v_out + (int64_t)r * ns, lv_out, vlen, sid, rnd, loads);
       SP_LAUNCHED("sp_deal_kernel");
    }
@@ -409,13 +441,102 @@ static int stream_plan_build(int64_t m, int64_t n, int64_t nnz, const int64_t *r
    return ISPLIB_SUCCESS;
 }
 
+// ---- the capacities of the levelled deal -------------------------------------------------------------------------------------
+// What the calibration (spmm_sweep.hip: stream_kernel_calibrate -- the stream kernel itself, timed per wave, on a synthetic plan of one
+// generation) is reduced to: one factor per GROUP of workgroups, a group being the workgroups of one XCD (index modulo 8:
+// round-robin placement) in one residency ORDER (the first, second, ... workgroup that a CU receives: index * wgs / workgroups).
+// profiles/stream_level.txt: those two coordinates carry what persists from dispatch to dispatch and process to process -- the XCDs
+// differ by 1-2 %, and a CU's second workgroup runs ~4 % behind its first.  They are speed assumptions only.
+namespace isplib {
+// the synthetic graph: entries per row, columns per row -- the headline's shape (Reddit: 492, 1.8), which of the shapes tried
+// follows the headline launch's factors best (profiles/stream_level.txt: correlation 0.97 by group; 64 entries per row: 0.89)
+constexpr int SP_CALIB_DEGREE = 512, SP_CALIB_COLS = 2;
+constexpr double SP_CAP_CLAMP = 0.08;                       // no calibration moves a capacity further than this from nominal
+static std::mutex g_caps_mutex;
+static std::map<std::tuple<int, int, int>, std::vector<uint32_t>> g_caps;      // (device, streams, waves_per_gen)
+
+static void caps_from_ticks(int streams, int waves_per_gen, const double *ticks, uint32_t *caps) {
+   const int wgs_per_cu = with_streams<STREAM_SUM>(streams, [&](auto s) {
+      constexpr StreamGeom ge = stream_geom(STREAM_SUM, s());
+      return lds_wgs_per_cu(stream_lds_bytes(ge.lpr, ge.nvmax), ge.wgs);
+   });
+   const int nwg = waves_per_gen / 4;
+   std::vector<double> sum((size_t)8 * wgs_per_cu, 0.0);
+   std::vector<int> cnt((size_t)8 * wgs_per_cu, 0);
+   double all = 0.0;
+   auto group = [&](int w) { const int wg = w / 4; return (wg % 8) * wgs_per_cu + (int)((int64_t)wg * wgs_per_cu / nwg); };
+   for (int w = 0; w < waves_per_gen; w++) { sum[group(w)] += ticks[w]; cnt[group(w)]++; all += ticks[w]; }
+   for (int w = 0; w < waves_per_gen; w++) {
+      double f = all > 0.0 && cnt[group(w)] ? (sum[group(w)] / cnt[group(w)]) / (all / waves_per_gen) - 1.0 : 0.0;
+      f = f > SP_CAP_CLAMP ? SP_CAP_CLAMP : (f < -SP_CAP_CLAMP ? -SP_CAP_CLAMP : f);
+      caps[w] = (uint32_t)((double)ISPLIB_STREAM_CAP_ONE / (1.0 + f) + 0.5);
+   }
+}
+}  // namespace isplib
+
+// experiments only (scripts/exp_stream_level.py; not declared in include/isplib_hip.h): the raw calibration, mean loop ticks per wave
+extern "C" int isplib_stream_calibrate_raw(int streams, int waves_per_gen, int launches, int degree, int col_mult, double *wave_ticks /*host [waves_per_gen]*/, void *stream) {
+   clear_error();
+   int rpw = 0, resident = 0;
+   if (isplib_spmm_stream_geometry(streams, &rpw, &resident) != ISPLIB_SUCCESS) return ISPLIB_FAIL;
+   if (!wave_ticks) return fail(ISPLIB_FAIL, "isplib_stream_calibrate_raw: wave_ticks is NULL");
+   std::lock_guard<std::mutex> lock(g_caps_mutex);
+   return stream_kernel_calibrate(streams, waves_per_gen, launches, degree, col_mult, wave_ticks, (hipStream_t)stream);
+}
+
+extern "C" int isplib_stream_capacities_hip(int device, int streams, int waves_per_gen, int64_t nnz, uint32_t *caps, int *levelled, void *stream) {
+   clear_error();
+   if (levelled) *levelled = 0;
+   int rpw = 0, resident = 0;
+   if (isplib_spmm_stream_geometry(streams, &rpw, &resident) != ISPLIB_SUCCESS) return ISPLIB_FAIL;
+   if (waves_per_gen <= 0) waves_per_gen = resident;
+   if (!caps) return fail(ISPLIB_FAIL, "isplib_stream_capacities_hip: caps is NULL");
+   for (int w = 0; w < waves_per_gen; w++) caps[w] = ISPLIB_STREAM_CAP_ONE;
+   const int mode = stream_level_mode();
+   // the generation the kernel is built to hold, in whole rounds of the eight XCDs
+   if (mode == 0 || waves_per_gen != resident || resident % 32 != 0 || (mode == 2 && nnz < STREAM_MIN_NNZ)) return ISPLIB_SUCCESS;
+   int current = 0;
+   ISPLIB_HIP_TRY(hipGetDevice(&current));
+   if (device < 0) device = current;
+   std::lock_guard<std::mutex> lock(g_caps_mutex);
+   const auto key = std::make_tuple(device, streams, waves_per_gen);
+   auto it = g_caps.find(key);
+   if (it == g_caps.end()) {
+      std::vector<double> ticks((size_t)waves_per_gen);
+      if (device != current) ISPLIB_HIP_TRY(hipSetDevice(device));
+      const int rc = stream_kernel_calibrate(streams, waves_per_gen, 3, SP_CALIB_DEGREE, SP_CALIB_COLS, ticks.data(), device == current ? (hipStream_t)stream : (hipStream_t) nullptr);
+      if (device != current) (void)hipSetDevice(current);
+      if (rc == ISPLIB_NOT_ENOUGH_MEM) { clear_error(); return ISPLIB_SUCCESS; }      // no room to calibrate (2.7 GB at its peak): the unlevelled deal, asked again next time
+      if (rc) return rc;
+      std::vector<uint32_t> c((size_t)waves_per_gen);
+      caps_from_ticks(streams, waves_per_gen, ticks.data(), c.data());
+      it = g_caps.emplace(key, std::move(c)).first;
+   }
+   memcpy(caps, it->second.data(), (size_t)waves_per_gen * sizeof(uint32_t));
+   if (levelled) *levelled = 1;
+   return ISPLIB_SUCCESS;
+}
+
+extern "C" int isplib_stream_plan_build_caps_hip(int64_t m, int64_t n, int64_t nnz, const int64_t *rowptr, const int64_t *col,
+                                                 const float *val, int streams, int slices, int chunk, int waves_per_gen,
+                                                 const uint32_t *caps, isplib_stream_plan *out, void *stream) {
+   clear_error();
+   int rpw = 0, resident = 0;
+   if (isplib_spmm_stream_geometry(streams, &rpw, &resident) != ISPLIB_SUCCESS) return ISPLIB_FAIL;
+   return stream_plan_build(m, n, nnz, rowptr, col, val, streams, rpw, resident, slices, chunk, waves_per_gen, out, stream, -1, caps);
+}
+
 extern "C" int isplib_stream_plan_build_hip(int64_t m, int64_t n, int64_t nnz, const int64_t *rowptr, const int64_t *col,
                                             const float *val, int streams, int slices, int chunk, int waves_per_gen,
                                             isplib_stream_plan *out, void *stream) {
    clear_error();
-   int rpw = 0, resident = 0;
+   int rpw = 0, resident = 0, levelled = 0;
    if (isplib_spmm_stream_geometry(streams, &rpw, &resident) != ISPLIB_SUCCESS) return ISPLIB_FAIL;
-   return stream_plan_build(m, n, nnz, rowptr, col, val, streams, rpw, resident, slices, chunk, waves_per_gen, out, stream);
+   std::vector<uint32_t> caps((size_t)(waves_per_gen > 0 ? waves_per_gen : resident));
+   const int rc = isplib_stream_capacities_hip(-1, streams, waves_per_gen, nnz, caps.data(), &levelled, stream);
+   if (rc) return rc;
+   return stream_plan_build(m, n, nnz, rowptr, col, val, streams, rpw, resident, slices, chunk, waves_per_gen, out, stream, -1,
+                            levelled ? caps.data() : nullptr);
 }
 
 // 1 if some row's columns do not ascend (duplicates are fine)

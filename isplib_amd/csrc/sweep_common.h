@@ -124,9 +124,7 @@ struct SweepArgs {
    const float *g;                 // [m][ldg] the other dense operand (grad_out)
    int64_t ldg;
    float *dval;                    // [nnz]
-#ifdef ISPLIB_EXP_WAVE_TIMES
-   unsigned long long *dbg;        // experiment (scripts/exp_wave_times.py): [wave][4] s_memtime at start / loop entry / loop exit / end
-#endif
+   unsigned long long *dbg;        // the TIMED stream kernel (calibration, scripts/exp_wave_times.py), else null: [wave][5] s_memtime at start / loop entry / loop exit / end, and where the wave ran
    float *part_val;                // [n_parts][k]
    int *part_idx;                  // [n_parts][k] row-relative edge ids (max/min)
    const int32_t *hub_row, *hub_off;

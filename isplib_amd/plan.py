@@ -262,7 +262,8 @@ class StreamPlan:
 
 
 def stream_plan_arrays(rowptr: torch.Tensor, col: torch.Tensor, ncols: int, slices: int, waves_per_gen: int,
-                       rows_per_wave: int = 16, streams: int = 4, chunk: int = 2048, pad_row: Optional[int] = None) -> dict:
+                       rows_per_wave: int = 16, streams: int = 4, chunk: int = 2048, pad_row: Optional[int] = None,
+                       capacities=None) -> dict:
     """The arrays of a stream plan; plain torch ops on the device of `col` (once per graph and geometry).
 
       * rows over `chunk` edges are dealt edge by edge, round robin, to ceil(deg / chunk) virtual rows: every
@@ -272,7 +273,12 @@ def stream_plan_arrays(rowptr: torch.Tensor, col: torch.Tensor, ncols: int, slic
         one slot of one wave, rows_per_wave / streams rows): equal rows and, within a fraction of a percent, equal
         edges per stream; `streams` neighbouring streams form a wave and advance together;
       * a stream lists its rows' edges slice by slice (then row by row, then in CSR order) as words
-        (local row << 24) | column; streams of a wave are interleaved step by step and padded to the longest."""
+        (local row << 24) | column; streams of a wave are interleaved step by step and padded to the longest.
+
+    `capacities` (the levelled deal, include/isplib_hip.h: isplib_stream_capacities_hip): one integer per wave of a generation,
+    cabi.STREAM_CAP_ONE = nominal; the streams of a round are then ordered by load * STREAM_CAP_ONE // capacity instead of by
+    load, so a wave of a slow place gets fewer edges.  Which wave holds a row is all that changes (a row's sum keeps its bits wherever the
+    row is flushed at every slice boundary in both plans: include/isplib_hip.h).  None, or all equal: today's deal."""
     assert 1 <= slices <= 4096 and streams in (2, 4, 8) and waves_per_gen >= 1
     assert rows_per_wave % streams == 0 and rows_per_wave <= 128
     assert ncols < (1 << 24), "column ids share a 32-bit word with the local row and are multiplied in 24 bits"
@@ -301,19 +307,19 @@ def stream_plan_arrays(rowptr: torch.Tensor, col: torch.Tensor, ncols: int, slic
     sid = torch.empty(nv, **i64)
     rnd = torch.empty(nv, **i64)
     loads = torch.zeros(ns, **i64)
-    # experiment (scripts/exp_xcd_bias.py): workgroups on even XCDs run 1-2 % slower than the mean:
-    # count an edge dealt to one of their streams as 1 + bias edges, so that they get fewer
-    bias = float(os.environ.get("ISPLIB_EXP_XCD_BIAS", "0"))
-    cost = None
-    if bias != 0.0:
-        blk = (torch.arange(ns, **i64) // streams % waves_per_gen) // 4          # workgroup of the stream inside its launch
-        cost = torch.where(blk % 2 == 0, 1024 + int(round(1024 * bias)), 1024 - int(round(1024 * bias))).to(torch.int64)
+    cap_s = None
+    if capacities is not None:
+        caps = torch.as_tensor(capacities, dtype=torch.int64).to(dev)
+        assert caps.numel() == waves_per_gen and int(caps.min()) >= cabi.STREAM_CAP_ONE // 16 and int(caps.max()) <= cabi.STREAM_CAP_ONE * 16
+        if bool((caps != caps[0]).any()):
+            cap_s = caps[torch.arange(ns, **i64) // streams % waves_per_gen]      # of every stream
     for r in range(-(-nv // ns)):
         items = order[r * ns:(r + 1) * ns]
-        to = torch.sort(loads, stable=True).indices[:items.numel()]
+        keys = loads if cap_s is None else (loads * cabi.STREAM_CAP_ONE // cap_s).clamp(max=2 ** 32 - 1)
+        to = torch.sort(keys, stable=True).indices[:items.numel()]
         sid[items] = to
         rnd[items] = r
-        loads[to] += vlen[items] if cost is None else vlen[items] * cost[to]
+        loads[to] += vlen[items]
     wave, slot = sid // streams, sid % streams
     lrow = slot * per + rnd                                      # local row inside the wave
     is_hub = nchunk[vrow] > 1
@@ -395,14 +401,16 @@ def build_stream_plan(rowptr: torch.Tensor, col: torch.Tensor, val: Optional[tor
         rpw, resident = cabi.stream_geometry(streams)
     rows_per_wave = rpw if rows_per_wave is None else rows_per_wave
     waves_per_gen = resident if waves_per_gen is None else waves_per_gen
+    # the levelled deal: the library's own rule and calibration, as its native builder asks them (sum / mean plans only)
+    capacities = None if minmax or rows_per_wave != rpw else cabi.stream_capacities(col.device, streams, waves_per_gen, col.numel())
     plan = StreamPlan(**stream_plan_arrays(rowptr, col, ncols, slices, waves_per_gen, rows_per_wave, streams, chunk,
-                                           pad_row=rows_per_wave if minmax else None))
+                                           pad_row=rows_per_wave if minmax else None, capacities=capacities))
     plan.set_values(val)
     return plan
 
 
 def build_stream_plan_native(rowptr: torch.Tensor, col: torch.Tensor, ncols: int, slices: int, streams: int = 4,
-                             chunk: int = 512, minmax: bool = False) -> Optional[StreamPlan]:
+                             chunk: int = 512, minmax: bool = False, waves_per_gen: int = 0, capacities=None) -> Optional[StreamPlan]:
     """The same plan through the library's own builder (``isplib_stream_plan_build_hip`` / ``_minmax_hip``: rocPRIM sorts
     and HIP kernels, ~10 ms on the Reddit shape against 27-30 ms for the torch ops above; identical arrays,
     tests/test_gpu_sweep.py::test_native_stream_plan_equals_the_torch_built_one) -- what the plug-in uses.  The arrays
@@ -412,7 +420,7 @@ def build_stream_plan_native(rowptr: torch.Tensor, col: torch.Tensor, ncols: int
     if ncols >= cabi.STREAM_N_END or col.numel() >= cabi.STREAM_NNZ_END:
         return None
     try:
-        native = cabi.NativeStreamPlan(rowptr, col, None, ncols, streams, slices, chunk, 0, minmax)
+        native = cabi.NativeStreamPlan(rowptr, col, None, ncols, streams, slices, chunk, waves_per_gen, minmax, capacities=capacities)
     except cabi.IsplibError as e:
         if e.status == cabi.ISPLIB_FAIL:          # outside the builder's domain / unsorted rows: the caller's other schedules
             return None

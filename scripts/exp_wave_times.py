@@ -1,5 +1,5 @@
-"""Experiment (library built with -DISPLIB_EXP_WAVE_TIMES, e.g. scripts/exp_build_variants.sh "python3 scripts/exp_wave_times.py" "-DISPLIB_EXP_WAVE_TIMES=1"): when do the waves of a stream dispatch start, enter their loop,
-leave it and finish?  Prints, per dispatch of one K=128 launch, the spread of those four times over the 2,048 waves
+"""Experiment (the TIMED instance of spmm_stream_kernel, which runs while isplib_debug_wave_times holds a buffer): when do the waves
+of a stream dispatch start, enter their loop, leave it and finish?  Prints, per dispatch of one K=128 launch, the spread of those four times over the 2,048 waves
 (s_memtime ticks of 10 ns).  What it answers: how much of a dispatch is ramp / tail rather than steady gathering."""
 import ctypes
 import os
@@ -25,12 +25,12 @@ for _ in range(3):
     cabi.fusedMM_csr_stream_hip(cabi.MSG_SPMM_SUM, rowptr, nnz, plan, x, out, ws)
 torch.cuda.synchronize()
 nw = plan.waves_per_gen
-buf = torch.zeros(4 * nw * 4, dtype=torch.int64, device=dev)
+buf = torch.zeros(4 * nw * 5, dtype=torch.int64, device=dev)
 L.isplib_debug_wave_times(ctypes.c_void_p(buf.data_ptr()))
 cabi.fusedMM_csr_stream_hip(cabi.MSG_SPMM_SUM, rowptr, nnz, plan, x, out, ws)
 torch.cuda.synchronize()
 L.isplib_debug_wave_times(None)
-t = buf.view(4, nw, 4).cpu().double()
+t = buf.view(4, nw, 5).cpu().double()
 steps = (plan.wave_step_off[1:] - plan.wave_step_off[:-1]).cpu().double().view(-1, nw)
 for d in range(4):
     a = t[d]
