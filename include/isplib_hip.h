@@ -760,6 +760,55 @@ int    isplib_attention_bw_cols_hip(int64_t m, int64_t n, int64_t k, int64_t nnz
                                     const float *g, int64_t ldg, const float *lse, const float *dsum, float *dy, int64_t lddy,
                                     void *stream);
 /*
+ * GAT attention aggregation over the stored entries e = (i, j) of a CSR matrix A [m, n], all heads in one launch, forward and
+ * backward, fp32.  With y: n x ldy of k = heads * d columns (head h owns the columns [h*d, (h+1)*d)), the per-node scores
+ * a_dst [m, heads] and a_src [n, heads] (dense: a row pitch of `heads`) and a slope `negative_slope` = ns, for every head h:
+ *   u_e  = a_dst[i,h] + a_src[j,h]      s_e = u_e > 0 ? u_e : ns u_e
+ *   a_e  = exp(s_e - lse[i,h]),  lse[i,h] = log sum_{e in row i} exp(s_e)          z_i[head h] = sum_e a_e y_j[head h]
+ * and, for g = dL/dz (m x ldg),
+ *   D[i,h] = <g_i, z_i>_h       t_e = <g_i, y_j>_h       du_e = a_e (t_e - D[i,h]) (u_e > 0 ? 1 : ns)
+ *   d a_dst[i,h] = sum_e du_e   d a_src[j,h] = sum_{e -> j} du_e                   dy_j[head h] = sum_{e -> j} a_e g_i[head h].
+ * This is the aggregation of GATConv (GATv2 is not: its nonlinearity sits inside the dot product).  Stored values of A are not read;
+ * every stored entry is its own edge, so a duplicate counts twice; the column order inside a row is free.  u_e is one fp32 add, so
+ * the slope branch is decided by the sign of the exact sum.  An empty row has z_i = 0, lse = -inf, D = 0 and d a_dst = 0; a column
+ * no entry points at has dy_j = 0 and d a_src = 0.  The softmax is computed relative to a running maximum, so no score overflows: a
+ * row of one entry returns y_j bit for bit and lse = s_e.  A NaN in y_j reaches the rows that reference j, a NaN in a_src[j,h] head h
+ * of those rows, and nothing else.
+ *   isplib_gat_csr_hip      writes z (m x ldz) and lse (m x heads).
+ *   isplib_gat_bw_rows_hip  reads a_dst, y, a_src, g, z and lse, writes d_a_dst (m x heads) and dsum (m x heads: D, which the next
+ *                           entry reads).
+ *   isplib_gat_bw_cols_hip  runs on the transposed structure (colb / cole: n column ranges into row_t); reads a_dst, y, a_src, g,
+ *                           lse and dsum, writes dy (n x lddy) and d_a_src (n x heads).
+ * Nothing is kept per edge: the backward recomputes a_e from lse.  Outputs are write-only and every element of every row is
+ * written, nothing between the rows of a pitched output.  One wave per row (per column), no atomics, no LDS, a fixed order of
+ * operations: two launches give equal bits.  The entries neither allocate nor synchronise.
+ * Domain: isplib_gat_serves(rows_gathered, heads, d, ld) for the GATHERED wide operand (y with n rows in the first two entries, g
+ * with m rows in the third): 1 <= heads, 1 <= d, heads * d <= 512; heads == 1 (any d) or d a power of two >= 4 (a head is then an
+ * aligned group of lanes and a lane's four columns never straddle heads); ld >= heads * d; rows_gathered < 2^31 and the operand
+ * inside one buffer descriptor.  Outside the domain: ISPLIB_NO_OPT_IMPL.  A negative dimension, a null operand, a k that is no
+ * multiple of heads, or a pitch of a row-resident operand or output below k: ISPLIB_FAIL.  All refusals come before any launch.
+ * m == 0 or k == 0 (n == 0 or k == 0 in the third entry) succeeds without a launch.
+ */
+#define ISPLIB_GAT_K_MAX               512          /* heads * d: a row sits in registers, two 16-byte chunks per lane */
+static inline int isplib_gat_serves(int64_t rows_gathered, int64_t heads, int64_t d, int64_t ld) {
+   if (heads < 1 || d < 1 || heads > ISPLIB_GAT_K_MAX || d > ISPLIB_GAT_K_MAX || heads * d > ISPLIB_GAT_K_MAX) return 0;
+   if (heads > 1 && (d < 4 || (d & (d - 1)) != 0)) return 0;
+   return ld >= heads * d && rows_gathered < (1LL << 31) && isplib_dense_in_descriptor(rows_gathered, ld);
+}
+int    isplib_gat_domain(int64_t rows_gathered, int64_t heads, int64_t d, int64_t ld);   /* isplib_gat_serves as a symbol */
+int    isplib_gat_csr_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                          const int64_t *pntre, const float *a_dst /* m x heads */, const float *y, int64_t ldy,
+                          const float *a_src /* n x heads */, int64_t heads, float negative_slope, float *z, int64_t ldz,
+                          float *lse /* m x heads */, void *stream);
+int    isplib_gat_bw_rows_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                              const int64_t *pntre, const float *a_dst, const float *y, int64_t ldy, const float *a_src,
+                              int64_t heads, float negative_slope, const float *g, int64_t ldg, const float *z, int64_t ldz,
+                              const float *lse, float *d_a_dst /* m x heads */, float *dsum /* m x heads */, void *stream);
+int    isplib_gat_bw_cols_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t, const int64_t *colb,
+                              const int64_t *cole, const float *a_dst, const float *y, int64_t ldy, const float *a_src,
+                              int64_t heads, float negative_slope, const float *g, int64_t ldg, const float *lse,
+                              const float *dsum, float *dy, int64_t lddy, float *d_a_src /* n x heads */, void *stream);
+/*
  * The row-softmax attention aggregation above for dense operands of 16-bit elements (dtype: ISPLIB_DTYPE_BF16 | _F16), forward and
  * backward, on the same mapping (one wave per row or column, one 16-byte gather of EIGHT columns per lane and edge, one chunk per
  * lane).  x, y and g are `dtype` and no operand is widened in memory; widening is exact, every product, sum, exponential and division

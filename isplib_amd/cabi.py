@@ -127,6 +127,20 @@ def attention_serves(rows_gathered: int, k: int, ld: int) -> bool:
             (rows_gathered <= 0 or rows_gathered * ld * 4 <= DENSE_BYTES_MAX))
 
 
+GAT_K_MAX = 512                         # the GAT entries: heads * d, a row in registers, two 16-byte chunks per lane
+
+
+def gat_serves(rows_gathered: int, heads: int, d: int, ld: int) -> bool:
+    """isplib_gat_serves of the header: the GAT entries (isplib_gat_csr_hip and its two backward entries) gather `rows_gathered` rows of
+    heads * d floats at leading dimension ld through one buffer descriptor; with more than one head, d is a power of two >= 4 (a head
+    is an aligned group of lanes and a lane's four columns never straddle heads)."""
+    if heads < 1 or d < 1 or heads * d > GAT_K_MAX:
+        return False
+    if heads > 1 and (d < 4 or d & (d - 1)):
+        return False
+    return ld >= heads * d and rows_gathered < 2 ** 31 and (rows_gathered <= 0 or rows_gathered * ld * 4 <= DENSE_BYTES_MAX)
+
+
 ATTENTION16_K_MIN, ATTENTION16_K_MAX = 8, 512   # the 16-bit attention entries: eight columns per lane, one 16-byte chunk per lane
 
 
@@ -197,6 +211,7 @@ EXPORTS = (
     "isplib_attention_csr_hip", "isplib_attention_bw_rows_hip", "isplib_attention_bw_cols_hip", "isplib_attention_domain",
     "isplib_attention16_csr_hip", "isplib_attention16_bw_rows_hip", "isplib_attention16_bw_cols_hip", "isplib_attention16_domain",
     "isplib_attention16_auto",
+    "isplib_gat_csr_hip", "isplib_gat_bw_rows_hip", "isplib_gat_bw_cols_hip", "isplib_gat_domain",
 )
 
 # include/isplib_hip_experimental.h (libisplib_hip_exp.so): forms measured slower than the defaults; tests and experiment scripts only
@@ -448,6 +463,16 @@ def lib() -> ctypes.CDLL:
         L.isplib_attention_bw_cols_hip.restype = ctypes.c_int
         L.isplib_attention_bw_cols_hip.argtypes = [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _vp, _vp,
                                                    _i64, _vp]
+        L.isplib_gat_domain.restype = ctypes.c_int
+        L.isplib_gat_domain.argtypes = [_i64, _i64, _i64, _i64]
+        L.isplib_gat_csr_hip.restype = ctypes.c_int
+        L.isplib_gat_csr_hip.argtypes = [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _vp]
+        L.isplib_gat_bw_rows_hip.restype = ctypes.c_int
+        L.isplib_gat_bw_rows_hip.argtypes = [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _i64, _vp,
+                                             _vp, _vp, _vp]
+        L.isplib_gat_bw_cols_hip.restype = ctypes.c_int
+        L.isplib_gat_bw_cols_hip.argtypes = [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _vp, _vp,
+                                             _i64, _vp, _vp]
         L.isplib_attention16_domain.restype = ctypes.c_int
         L.isplib_attention16_domain.argtypes = [_i64, _i64, _i64]
         L.isplib_attention16_auto.restype = ctypes.c_int
@@ -1771,6 +1796,159 @@ def attention_bw_cols(colptr, row_t, x, y, g, lse, dsum, scale: Optional[float] 
                                                 _stream(y.device))
     _check(st, "isplib_attention_bw_cols_hip")
     return out
+
+
+def _gat_heads(heads, k: int) -> int:
+    if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
+        raise ValueError(f"isplib_amd: `heads` must be a positive int, got {heads!r}")
+    if k % heads:
+        raise ValueError(f"isplib_amd: the width of `y` ({k}) must be heads * d, got heads = {heads}")
+    return k // heads
+
+
+def _gat_table(t, name: str, rows: int, heads: int) -> None:
+    """One per-node table of the GAT entries: a dense float32 [rows, heads] tensor."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2:
+        raise ValueError(f"isplib_amd: `{name}` must be a 2-D tensor [{rows}, {heads}], got "
+                         f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    if t.dtype != torch.float32:
+        raise TypeError(f"isplib_amd: `{name}` must be float32, got {t.dtype} (the attention operator is fp32 only)")
+    if t.size(0) != rows or t.size(1) != heads:
+        raise ValueError(f"isplib_amd: `{name}` must be [{rows}, {heads}] (one entry per row and head), got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"isplib_amd: `{name}` must be contiguous (the [rows, heads] tables are dense)")
+
+
+def _gat_domain(rows_gathered: int, heads: int, d: int, ld: int) -> None:
+    if d > 0 and not gat_serves(rows_gathered, heads, d, ld):
+        raise ValueError(f"isplib_amd: outside the GAT entries' domain (isplib_gat_serves: heads * d <= {GAT_K_MAX}, heads == 1 or d a power "
+                         f"of two >= 4, gathered rows < 2^31, rows * pitch * 4 <= 3.5 GiB), got rows={rows_gathered}, heads={heads}, d={d}, "
+                         f"pitch={ld}")
+
+
+def gat(rowptr, col, y, a_dst, a_src, heads: int = 1, negative_slope: float = 0.2, *, out=None, check: bool = True):
+    """GAT attention aggregation, all heads in one launch (isplib_gat_csr_hip): over the stored entries e = (i, j) of the CSR structure
+    and every head h, s_e = leaky_relu(a_dst[i,h] + a_src[j,h]), a_e = softmax of s over the row's entries, z_i[head h] = sum_e a_e
+    y_j[head h].  Returns (z [m, heads * d], lse [m, heads]); an empty row has z_i = 0 and lse = -inf.  `y` [n, heads * d] float32 (a
+    row-strided view keeps its pitch), `a_dst` [m, heads] and `a_src` [n, heads] dense float32; `out` = (z, lse) to write in place.
+    Every operand is checked BEFORE the call (`check`: also the two checks that read the structure on the device)."""
+    if not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1 or rowptr.numel() < 1:
+        raise ValueError("isplib_amd: `rowptr` (m + 1 entries) must be a 1-D tensor")
+    m = rowptr.numel() - 1
+    if not isinstance(y, torch.Tensor) or y.dim() != 2:
+        raise ValueError("isplib_amd: `y` must be a 2-D tensor [n, heads * d]")
+    n, k = y.size(0), y.size(1)
+    ldy = _attn_dense(y, "y", n, None, "one row per column of the sparse operand")
+    d = _gat_heads(heads, k)
+    _gat_table(a_dst, "a_dst", m, heads)
+    _gat_table(a_src, "a_src", n, heads)
+    rowptr, col = _attn_structure(rowptr, col, "rowptr", "col", n, check)
+    if out is not None:
+        z, lse = out
+        ldz = _attn_dense(z, "out[0]", m, k, "z")
+        _gat_table(lse, "out[1]", m, heads)
+    _gat_domain(n, heads, d, ldy)
+    _same_gpu((("y", y), ("a_dst", a_dst), ("a_src", a_src), ("rowptr", rowptr), ("col", col)) +
+              ((("out[0]", out[0]), ("out[1]", out[1])) if out is not None else ()))
+    if out is None:
+        z = torch.empty((m, k), dtype=torch.float32, device=y.device)
+        lse = torch.empty((m, heads), dtype=torch.float32, device=y.device)
+        ldz = max(k, 1)
+    if m == 0 or k == 0:
+        if k == 0 and m > 0:
+            lse.fill_(float("-inf"))
+        return z, lse
+    rp = rowptr.data_ptr()
+    with torch.cuda.device(y.device):
+        st = lib().isplib_gat_csr_hip(m, n, k, col.numel(), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8), _ptr(a_dst), _ptr(y), ldy,
+                                      _ptr(a_src), heads, float(negative_slope), _ptr(z), ldz, _ptr(lse), _stream(y.device))
+    _check(st, "isplib_gat_csr_hip")
+    return z, lse
+
+
+def gat_bw_rows(rowptr, col, y, a_dst, a_src, g, z, lse, heads: int = 1, negative_slope: float = 0.2, *, out=None, check: bool = True):
+    """The backward of `gat` over the rows (isplib_gat_bw_rows_hip): for g = dL/dz [m, heads * d] and the forward's z and lse,
+    D[i,h] = <g_i, z_i>_h, du_e = a_e (<g_i, y_j>_h - D[i,h]) * (1 or negative_slope) with a_e recomputed from lse, d a_dst[i,h] =
+    sum_e du_e.  Returns (d_a_dst [m, heads], D [m, heads]); an empty row has both 0.  `out` = (d_a_dst, D); the operand checks are
+    gat's."""
+    if not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1 or rowptr.numel() < 1:
+        raise ValueError("isplib_amd: `rowptr` (m + 1 entries) must be a 1-D tensor")
+    m = rowptr.numel() - 1
+    if not isinstance(y, torch.Tensor) or y.dim() != 2:
+        raise ValueError("isplib_amd: `y` must be a 2-D tensor [n, heads * d]")
+    n, k = y.size(0), y.size(1)
+    ldy = _attn_dense(y, "y", n, None, "one row per column of the sparse operand")
+    d = _gat_heads(heads, k)
+    _gat_table(a_dst, "a_dst", m, heads)
+    _gat_table(a_src, "a_src", n, heads)
+    ldg = _attn_dense(g, "g", m, k, "the gradient of z")
+    ldz = _attn_dense(z, "z", m, k, "the forward's output")
+    _gat_table(lse, "lse", m, heads)
+    rowptr, col = _attn_structure(rowptr, col, "rowptr", "col", n, check)
+    if out is not None:
+        _gat_table(out[0], "out[0]", m, heads)
+        _gat_table(out[1], "out[1]", m, heads)
+    _gat_domain(n, heads, d, ldy)
+    _same_gpu((("y", y), ("a_dst", a_dst), ("a_src", a_src), ("g", g), ("z", z), ("lse", lse), ("rowptr", rowptr), ("col", col)) +
+              ((("out[0]", out[0]), ("out[1]", out[1])) if out is not None else ()))
+    if out is None:
+        out = (torch.empty((m, heads), dtype=torch.float32, device=y.device), torch.empty((m, heads), dtype=torch.float32, device=y.device))
+    dadst, dsum = out
+    if m == 0 or k == 0:
+        if k == 0 and m > 0:
+            dadst.zero_()
+            dsum.zero_()
+        return dadst, dsum
+    rp = rowptr.data_ptr()
+    with torch.cuda.device(y.device):
+        st = lib().isplib_gat_bw_rows_hip(m, n, k, col.numel(), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8), _ptr(a_dst), _ptr(y),
+                                          ldy, _ptr(a_src), heads, float(negative_slope), _ptr(g), ldg, _ptr(z), ldz, _ptr(lse), _ptr(dadst),
+                                          _ptr(dsum), _stream(y.device))
+    _check(st, "isplib_gat_bw_rows_hip")
+    return dadst, dsum
+
+
+def gat_bw_cols(colptr, row_t, y, a_dst, a_src, g, lse, dsum, heads: int = 1, negative_slope: float = 0.2, *, out=None, check: bool = True):
+    """The backward of `gat` over the columns (isplib_gat_bw_cols_hip), on the transposed structure (`colptr` [n + 1], `row_t`: the row
+    ids of the entries in column-major order): dy_j[head h] = sum over the entries e = (i, j) of column j of a_e g_i[head h] and
+    d a_src[j,h] = sum of du_e, with `lse` of the forward and `dsum` = D of gat_bw_rows.  Returns (dy [n, heads * d], d_a_src
+    [n, heads]); a column no entry points at has both 0.  `out` = (dy, d_a_src); the operand checks are gat's."""
+    if not isinstance(colptr, torch.Tensor) or colptr.dim() != 1 or colptr.numel() < 1:
+        raise ValueError("isplib_amd: `colptr` (n + 1 entries) must be a 1-D tensor")
+    n = colptr.numel() - 1
+    ldy = _attn_dense(y, "y", n, None, "one row per column of the sparse operand")
+    k = y.size(1)
+    d = _gat_heads(heads, k)
+    if not isinstance(g, torch.Tensor) or g.dim() != 2:
+        raise ValueError("isplib_amd: `g` must be a 2-D tensor [m, heads * d]")
+    m = g.size(0)
+    ldg = _attn_dense(g, "g", m, k, "the gradient of z")
+    _gat_table(a_dst, "a_dst", m, heads)
+    _gat_table(a_src, "a_src", n, heads)
+    _gat_table(lse, "lse", m, heads)
+    _gat_table(dsum, "dsum", m, heads)
+    colptr, row_t = _attn_structure(colptr, row_t, "colptr", "row_t", m, check)
+    if out is not None:
+        lddy = _attn_dense(out[0], "out[0]", n, k, "dy")
+        _gat_table(out[1], "out[1]", n, heads)
+    _gat_domain(m, heads, d, ldg)
+    _same_gpu((("y", y), ("a_dst", a_dst), ("a_src", a_src), ("g", g), ("lse", lse), ("dsum", dsum), ("colptr", colptr), ("row_t", row_t)) +
+              ((("out[0]", out[0]), ("out[1]", out[1])) if out is not None else ()))
+    if out is None:
+        out = (torch.empty((n, k), dtype=torch.float32, device=y.device), torch.empty((n, heads), dtype=torch.float32, device=y.device))
+        lddy = max(k, 1)
+    dy, dasrc = out
+    if n == 0 or k == 0:
+        if k == 0 and n > 0:
+            dasrc.zero_()
+        return dy, dasrc
+    cp = colptr.data_ptr()
+    with torch.cuda.device(y.device):
+        st = lib().isplib_gat_bw_cols_hip(m, n, k, row_t.numel(), _ptr(row_t), ctypes.c_void_p(cp), ctypes.c_void_p(cp + 8), _ptr(a_dst),
+                                          _ptr(y), ldy, _ptr(a_src), heads, float(negative_slope), _ptr(g), ldg, _ptr(lse), _ptr(dsum),
+                                          _ptr(dy), lddy, _ptr(dasrc), _stream(y.device))
+    _check(st, "isplib_gat_bw_cols_hip")
+    return dy, dasrc
 
 
 def _attn16_dense(t, name: str, rows: int, k: Optional[int], what: str, dtype=None) -> int:

@@ -1273,6 +1273,116 @@ Tensor attention_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Te
    return AttentionSpmm::apply(rowptr, col, colptr, row_t, x, y, scale)[0];
 }
 
+// ---- GAT attention aggregation, all heads in one launch (isplib_gat_*_hip; not an operator of the reference) ----------
+// z_i[head h] = sum_e softmax_e(leaky_relu(a_dst[i,h] + a_src[j,h])) y_j[head h].  Saved for backward: y, a_dst, a_src, z and lse [M, H]
+// -- nothing of length nnz.  Every shape is checked before a launch: a mis-shaped dense operand must raise, never launch.
+static Tensor gat_table(const Tensor &src, const char *name, int64_t rows, int64_t heads) {
+   check_float(src, name);
+   TORCH_CHECK(src.dim() == 2 && src.size(0) == rows && src.size(1) == heads, "isplib: gat_spmm: `", name, "` must be [", rows, ", ", heads,
+               "] (one entry per row and head), got ", src.sizes());
+   return src.contiguous();
+}
+
+static AttnOperand gat_operand(const Tensor &src, const char *name, int64_t rows, int64_t k) {
+   check_float(src, name);
+   TORCH_CHECK(src.dim() == 2 && src.size(0) == rows && src.size(1) == k, "isplib: gat_spmm: `", name, "` must be [", rows, ", ", k, "], got ",
+               src.sizes());
+   const bool as_is = src.size(0) == 0 || src.size(1) == 0 || (src.stride(1) == 1 && (src.size(0) == 1 || src.stride(0) >= k));
+   const Tensor t = as_is ? src : src.contiguous();
+   return {t, t.size(0) > 1 ? t.stride(0) : std::max<int64_t>(k, 1)};
+}
+
+class GatSpmm : public torch::autograd::Function<GatSpmm> {
+ public:
+   static variable_list forward(AutogradContext *ctx, Variable rowptr, Variable col, Variable colptr, Variable row_t, Variable y, Variable a_dst,
+                                Variable a_src, int64_t heads, double negative_slope) {
+      check_index(rowptr, "rowptr"); check_index(col, "col"); check_index(colptr, "colptr"); check_index(row_t, "row_t");
+      TORCH_CHECK(y.defined() && y.dim() == 2, "isplib: gat_spmm needs a 2-D `y` [N, heads * d]");
+      OpTimer timer("FUSEDMM_GAT_FW", y);
+      const int64_t M = rowptr.numel() - 1, N = colptr.numel() - 1, K = y.size(1), nnz = col.numel();
+      TORCH_CHECK(M >= 0 && N >= 0 && row_t.numel() == nnz, "isplib: gat_spmm: `rowptr` / `colptr` need one entry more than rows / columns, "
+                                                             "`row_t` one entry per stored entry");
+      TORCH_CHECK(heads >= 1 && K % heads == 0, "isplib: gat_spmm: the width of `y` (", K, ") must be heads * d, got heads = ", heads);
+      const AttnOperand yo = gat_operand(y, "y", N, K);
+      TORCH_CHECK(a_dst.defined() && a_src.defined(), "isplib: gat_spmm needs `a_dst` [M, heads] and `a_src` [N, heads]");
+      const Tensor ad = gat_table(a_dst, "a_dst", M, heads), as = gat_table(a_src, "a_src", N, heads);
+      for (const Tensor *t : {&rowptr, &col, &colptr, &row_t, &a_dst, &a_src})
+         TORCH_CHECK(t->device() == y.device(), "isplib: gat_spmm: every operand must be on y's device");
+      TORCH_CHECK(K == 0 || isplib_gat_serves(N, heads, K / heads, yo.ld), "isplib: gat_spmm: outside isplib_gat_serves (heads * d <= ",
+                  ISPLIB_GAT_K_MAX, ", heads == 1 or d a power of two >= 4, N < 2^31, N * pitch * 4 <= 3.5 GiB): N = ", N, ", heads = ", heads,
+                  ", d = ", K / heads, ", pitch = ", yo.ld);
+      c10::DeviceGuard guard(y.device());
+      const Tensor rp = rowptr.contiguous(), cl = col.contiguous();
+      Tensor z = at::empty({M, K}, y.options()), lse = at::empty({M, heads}, y.options());
+      if (M > 0 && K > 0) {
+         const int st = isplib_gat_csr_hip(M, N, K, nnz, cl.data_ptr<int64_t>(), rp.data_ptr<int64_t>(), rp.data_ptr<int64_t>() + 1,
+                                           ad.data_ptr<float>(), nnz > 0 ? yo.t.data_ptr<float>() : nullptr, yo.ld,
+                                           nnz > 0 ? as.data_ptr<float>() : nullptr, heads, (float)negative_slope, z.data_ptr<float>(), K,
+                                           lse.data_ptr<float>(), current_stream(y));
+         check_status(st, "isplib_gat_csr_hip");
+      } else if (M > 0) {
+         lse.fill_(-std::numeric_limits<float>::infinity());
+      }
+      ctx->saved_data["heads"] = heads;
+      ctx->saved_data["negative_slope"] = negative_slope;
+      ctx->save_for_backward({rp, cl, colptr, row_t, y, a_dst, a_src, z, lse});
+      return {z};
+   }
+
+   static variable_list backward(AutogradContext *ctx, variable_list grad_outs) {
+      OpTimer timer("FUSEDMM_GAT_BW", grad_outs[0]);
+      const bool need_y = ctx->needs_input_grad(4), need_dst = ctx->needs_input_grad(5), need_src = ctx->needs_input_grad(6);
+      auto grad_y = Variable(), grad_dst = Variable(), grad_src = Variable();
+      if (need_y || need_dst || need_src) {
+         auto saved = ctx->get_saved_variables();
+         auto rp = saved[0], cl = saved[1], colptr = saved[2].contiguous(), row_t = saved[3].contiguous(), y = saved[4], z = saved[7], lse = saved[8];
+         const int64_t heads = ctx->saved_data["heads"].toInt();
+         const float ns = (float)ctx->saved_data["negative_slope"].toDouble();
+         const int64_t M = rp.numel() - 1, N = colptr.numel() - 1, K = y.size(1), nnz = cl.numel();
+         const AttnOperand yo = gat_operand(y, "y", N, K);
+         const Tensor ad = gat_table(saved[5], "a_dst", M, heads), as = gat_table(saved[6], "a_src", N, heads);
+         const AttnOperand go = gat_operand(grad_outs[0].to(at::kFloat), "grad_out", M, K);
+         c10::DeviceGuard guard(y.device());
+         // the rows kernel always runs: its D[i,h] = <g_i, z_i>_h feeds the columns kernel; the columns kernel only when y or a_src asks
+         Tensor dadst = at::empty({M, heads}, y.options()), dsum = at::empty({M, heads}, y.options());
+         if (M > 0 && K > 0) {
+            const int st = isplib_gat_bw_rows_hip(M, N, K, nnz, cl.data_ptr<int64_t>(), rp.data_ptr<int64_t>(), rp.data_ptr<int64_t>() + 1,
+                                                  ad.data_ptr<float>(), nnz > 0 ? yo.t.data_ptr<float>() : nullptr, yo.ld,
+                                                  nnz > 0 ? as.data_ptr<float>() : nullptr, heads, ns, go.t.data_ptr<float>(), go.ld,
+                                                  z.data_ptr<float>(), K, lse.data_ptr<float>(), dadst.data_ptr<float>(), dsum.data_ptr<float>(),
+                                                  current_stream(y));
+            check_status(st, "isplib_gat_bw_rows_hip");
+         } else if (M > 0) {
+            dadst.zero_();
+         }
+         if (need_dst) grad_dst = dadst;
+         if (need_y || need_src) {
+            TORCH_CHECK(K == 0 || isplib_gat_serves(M, heads, K / heads, go.ld),
+                        "isplib: gat_spmm backward: outside isplib_gat_serves for the gathered rows of the gradient: M = ", M, ", K = ", K);
+            Tensor dy = at::empty({N, K}, y.options()), dasrc = at::empty({N, heads}, y.options());
+            if (N > 0 && K > 0) {
+               const int st = isplib_gat_bw_cols_hip(M, N, K, nnz, row_t.data_ptr<int64_t>(), colptr.data_ptr<int64_t>(),
+                                                     colptr.data_ptr<int64_t>() + 1, nnz > 0 ? ad.data_ptr<float>() : nullptr,
+                                                     yo.t.data_ptr<float>(), yo.ld, as.data_ptr<float>(), heads, ns,
+                                                     nnz > 0 ? go.t.data_ptr<float>() : nullptr, go.ld, lse.data_ptr<float>(),
+                                                     dsum.data_ptr<float>(), dy.data_ptr<float>(), K, dasrc.data_ptr<float>(), current_stream(y));
+               check_status(st, "isplib_gat_bw_cols_hip");
+            } else if (N > 0) {
+               dasrc.zero_();
+            }
+            if (need_y) grad_y = dy;
+            if (need_src) grad_src = dasrc;
+         }
+      }
+      return {Variable(), Variable(), Variable(), Variable(), grad_y, grad_dst, grad_src, Variable(), Variable()};
+   }
+};
+
+Tensor gat_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor y, Tensor a_dst, Tensor a_src, int64_t heads,
+                double negative_slope) {
+   return GatSpmm::apply(rowptr, col, colptr, row_t, y, a_dst, a_src, heads, negative_slope)[0];
+}
+
 // ---- the same aggregation for bf16 / fp16 operands (isplib_attention16_*_hip) ----------
 // x and y go in as they lie, z / dx / dy come back in their dtype, lse and D stay fp32: no fp32 [*, K] tensor in either direction.  Saved
 // for backward: the structure, x, y and lse -- NOT z: the rows kernel forms D_i from the row's edges (the rounded z would cost every
@@ -1422,5 +1532,7 @@ TORCH_LIBRARY(isplib, m) {
          "Tensor[] plan_t, Tensor? bias, bool relu) -> Tensor",
          &gcn_norm_spmm);
    m.def("attention_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor x, Tensor y, float scale) -> Tensor", &attention_spmm);
+   m.def("gat_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor y, Tensor a_dst, Tensor a_src, int heads, float negative_slope) -> Tensor",
+         &gat_spmm);
    m.def("attention_spmm16(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor x, Tensor y, float scale) -> Tensor", &attention_spmm16);
 }

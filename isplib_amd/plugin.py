@@ -674,6 +674,55 @@ def attention_matmul(src, x: torch.Tensor, y: Optional[torch.Tensor] = None, sca
     return torch.ops.isplib.attention_spmm(st._rowptr, st._col, st.colptr(), st.row_t(), x, y, p)
 
 
+def gat_matmul(src, y: torch.Tensor, a_dst: torch.Tensor, a_src: torch.Tensor, heads: int = 1, negative_slope: float = 0.2) -> torch.Tensor:
+    """GAT attention aggregation over the stored entries of `src`, all heads in one launch (include/isplib_hip.h, isplib_gat_csr_hip):
+    ``z[i, head h] = sum_j softmax_j(leaky_relu(a_dst[i, h] + a_src[j, h])) y[j, head h]`` over the entries (i, j) of row i -- the
+    aggregation of GATConv, with its autograd backward in `y`, `a_dst` and `a_src` (torch.ops.isplib.gat_spmm).  `y` [N, heads * d]
+    (head h owns the columns [h*d, (h+1)*d)), `a_dst` [M, heads], `a_src` [N, heads] float32 GPU tensors; with ``heads == 1`` the two
+    scores may be 1-D [rows].  On a square graph the same tensor may be passed for both scores: its gradient receives both parts.
+    The stored values of `src` are not read; an empty row gives 0.  The backward keeps y, the scores, z and one scalar per row and
+    head -- nothing per edge.  fp32 only (bf16 / fp16 operands raise TypeError); there is no fallback route: outside isplib_gat_serves
+    (heads * d <= 512; heads == 1 or d a power of two >= 4) the call raises ValueError.  GATv2 is not this operator."""
+    from . import cabi
+    for name, t in (("y", y), ("a_dst", a_dst), ("a_src", a_src)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"isplib_amd: `{name}` must be a tensor, got {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"isplib_amd: `{name}` must be float32, got {t.dtype} (the attention operator is fp32 only)")
+    if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
+        raise ValueError(f"isplib_amd: `heads` must be a positive int, got {heads!r}")
+    if y.dim() != 2:
+        raise ValueError(f"isplib_amd: `y` must be 2-D [rows, heads * d], got shape {tuple(y.shape)}")
+    st = _storage_of(src, y)
+    m_rows, n_cols = st._rowptr.numel() - 1, st._sparse_sizes[1]
+    if y.size(0) != n_cols:
+        raise ValueError(f"isplib_amd: `y` must have one row per column of the sparse matrix ({n_cols}), got {y.size(0)}")
+    k = y.size(1)
+    if k % heads:
+        raise ValueError(f"isplib_amd: the width of `y` ({k}) must be heads * d, got heads = {heads}")
+    d = k // heads
+    if heads == 1:
+        a_dst = a_dst.unsqueeze(1) if a_dst.dim() == 1 else a_dst
+        a_src = a_src.unsqueeze(1) if a_src.dim() == 1 else a_src
+    for name, t, rows, what in (("a_dst", a_dst, m_rows, "row"), ("a_src", a_src, n_cols, "column")):
+        if t.dim() != 2 or t.size(0) != rows or t.size(1) != heads:
+            raise ValueError(f"isplib_amd: `{name}` must be [{rows}, {heads}] (one entry per {what} of the sparse matrix and head), got "
+                             f"shape {tuple(t.shape)}")
+    if not (1 <= k <= cabi.GAT_K_MAX) or (heads > 1 and (d < 4 or d & (d - 1))):
+        raise ValueError(f"isplib_amd: gat_matmul serves 1 <= heads * d <= {cabi.GAT_K_MAX} with heads == 1 or d a power of two >= 4 (a head "
+                         f"is an aligned group of lanes), got heads = {heads}, d = {d}")
+    pitch = y.stride(0) if n_cols > 1 and y.stride(1) == 1 and y.stride(0) >= k else k
+    for rows, ld, what in ((n_cols, pitch, "`y`"), (m_rows, k, "the gradient of the result")):   # y: forward, rows; g: the columns kernel
+        if not cabi.gat_serves(rows, heads, d, ld):
+            raise ValueError(f"isplib_amd: {what} ({rows} rows at a pitch of {ld} floats) is outside the GAT kernels' domain: "
+                             f"rows < 2^31 and rows * pitch * 4 <= {cabi.DENSE_BYTES_MAX} bytes (3.5 GiB, one buffer descriptor)")
+    if not y.is_cuda or not a_dst.is_cuda or not a_src.is_cuda:
+        raise TypeError("isplib_amd: `y`, `a_dst` and `a_src` must be GPU tensors -- there is no CPU path")
+    if a_dst.device != y.device or a_src.device != y.device or st._rowptr.device != y.device:
+        raise ValueError("isplib_amd: `y`, `a_dst`, `a_src` and the sparse matrix must be on one device")
+    return torch.ops.isplib.gat_spmm(st._rowptr, st._col, st.colptr(), st.row_t(), y, a_dst, a_src, heads, float(negative_slope))
+
+
 def gcn_norm_matmul(src, other: torch.Tensor, bias: Optional[torch.Tensor] = None, relu: bool = False) -> torch.Tensor:
     """relu(D^-1/2 (A + I) D^-1/2 @ other + bias) for an UNWEIGHTED square graph, without materialising the
     normalised edge weights: the SpMM runs on the unit-weight fast path, the self loop, the left D^-1/2, bias
