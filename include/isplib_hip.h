@@ -864,6 +864,67 @@ static inline int isplib_attention16_native_pays(int64_t rows_gathered, int64_t 
 }
 int    isplib_attention16_auto(int64_t rows_gathered, int64_t ld);                /* the same rule as a symbol */
 /*
+ * The GAT attention aggregation above (isplib_gat_*) for a wide operand of 16-bit elements (dtype: ISPLIB_DTYPE_BF16 | _F16), all heads
+ * in one launch, forward and backward, on the mapping of the 16-bit attention entries (one wave per row or column, one 16-byte gather
+ * of EIGHT columns per lane and edge, one chunk per lane).  y, g, z and dy are `dtype` and are never widened in memory; widening is
+ * exact, every product, sum, exponential and division is fp32, and z and dy are rounded ONCE, to nearest even, to `dtype`.  a_dst,
+ * a_src, lse, dsum (D), d_a_dst and d_a_src are fp32 [rows, heads] tables exactly as in the fp32 entries (1/d of y), so u_e is one fp32
+ * add and the slope branch is decided by the sign of the exact sum.  The special values are the fp32 entries': an empty row has
+ * z_i = 0, lse = -inf, D = 0, d a_dst = 0; a column no entry points at has dy_j = 0 and d a_src = 0; a row of one entry returns y_j's
+ * 16 bits unchanged and lse = s_e; a NaN in a_src[j,h] reaches head h of the rows that reference j and nothing else.
+ *   isplib_gat16_csr_hip      writes z (m x ldz, `dtype`) and lse (m x heads, fp32).
+ *   isplib_gat16_bw_rows_hip  reads a_dst, y, a_src, g and lse -- NOT z: the rounded z would carry u * sum_c |g_ic z_ic| into every du_e
+ *                             through D = <g_i, z_i>_h.  In one pass over the row's edges it forms, per head, l = sum a_e, Dacc = sum a_e
+ *                             t_e, P = sum a_e sl_e t_e and Q = sum a_e sl_e (sl_e the slope, t_e = <g_i, y_j>_h), then D = Dacc / l and
+ *                             d a_dst = P - D Q.  Writes d_a_dst and dsum (both m x heads, fp32).
+ *   isplib_gat16_bw_cols_hip  on the transposed structure; reads a_dst, y, a_src, g, lse and dsum, writes dy (n x lddy, `dtype`) and
+ *                             d_a_src (n x heads, fp32).
+ * Nothing is kept per edge and autograd needs y, the two score tables and lse only.  Outputs are write-only, every element of every row
+ * is written, nothing between the rows of a pitched output, nothing outside a row's k columns is used.  No atomics, no LDS, a fixed
+ * order of operations: two launches give equal bits.  The entries neither allocate nor synchronise.
+ * Domain: isplib_gat16_serves(rows_gathered, heads, d, ld) for the GATHERED wide operand (y with n rows in the first two entries, g
+ * with m rows in the third): 1 <= heads, 8 <= heads * d <= 512 (a lane holds eight columns, one chunk per lane); heads == 1 with d
+ * even, or d a power of two >= 8 (a head is then an aligned group of d / 8 lanes and a lane's eight columns never straddle heads);
+ * ld even and >= heads * d; rows_gathered < 2^31 and the operand inside one buffer descriptor at 2 bytes per element; the pitches of
+ * the row-resident operand and of the wide output must be even too.  Outside the domain: ISPLIB_NO_OPT_IMPL.  Another dtype, a negative
+ * dimension, a null operand, a k that is no multiple of heads, a pitch of a row-resident operand or output below k, or a 16-bit base
+ * that is not 4-byte aligned: ISPLIB_FAIL.  All refusals come before any launch and leave the outputs untouched.  m == 0 or k == 0
+ * (n == 0 or k == 0 in the third entry) succeeds without a launch.
+ * isplib_gat16_native_pays is the measured rule of the layers above (forward + backward against "widen, the fp32 entries, narrow";
+ * profiles/gat16_ab.txt), over the family's classes (the gathered operand beyond 256 MiB at 2 bytes per element or
+ * not): nonzero only where EVERY native run was faster than EVERY run of the conversion route on every measured shape of the class.
+ */
+#define ISPLIB_GAT16_K_MIN             8            /* heads * d: a lane gathers eight columns */
+#define ISPLIB_GAT16_K_MAX             512          /* heads * d: one 16-byte chunk per lane, 64 lanes */
+static inline int isplib_gat16_serves(int64_t rows_gathered, int64_t heads, int64_t d, int64_t ld) {
+   if (heads < 1 || d < 1 || heads > ISPLIB_GAT16_K_MAX || d > ISPLIB_GAT16_K_MAX) return 0;
+   if (heads * d < ISPLIB_GAT16_K_MIN || heads * d > ISPLIB_GAT16_K_MAX) return 0;
+   if (heads == 1 ? (d % 2) != 0 : (d < 8 || (d & (d - 1)) != 0)) return 0;
+   return (ld % 2) == 0 && ld >= heads * d && rows_gathered < (1LL << 31) &&
+          isplib_rows_within(rows_gathered, ld, 2ull * ISPLIB_DENSE_BYTES_MAX);
+}
+int    isplib_gat16_domain(int64_t rows_gathered, int64_t heads, int64_t d, int64_t ld);   /* isplib_gat16_serves as a symbol */
+int    isplib_gat16_csr_hip(int dtype /* ISPLIB_DTYPE_BF16 | _F16 */, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx,
+                            const int64_t *pntrb, const int64_t *pntre, const float *a_dst /* m x heads */, const void *y, int64_t ldy,
+                            const float *a_src /* n x heads */, int64_t heads, float negative_slope, void *z, int64_t ldz,
+                            float *lse /* m x heads */, void *stream);
+int    isplib_gat16_bw_rows_hip(int dtype, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                                const int64_t *pntre, const float *a_dst, const void *y, int64_t ldy, const float *a_src, int64_t heads,
+                                float negative_slope, const void *g, int64_t ldg, const float *lse, float *d_a_dst /* m x heads */,
+                                float *dsum /* m x heads */, void *stream);
+int    isplib_gat16_bw_cols_hip(int dtype, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t, const int64_t *colb,
+                                const int64_t *cole, const float *a_dst, const void *y, int64_t ldy, const float *a_src, int64_t heads,
+                                float negative_slope, const void *g, int64_t ldg, const float *lse, const float *dsum, void *dy,
+                                int64_t lddy, float *d_a_src /* n x heads */, void *stream);
+static inline int isplib_gat16_native_pays(int64_t rows_gathered, int64_t ld) {
+   /* measured (profiles/gat16_ab.txt: the Reddit shape at (H, d) = (8, 8) and (8, 16) -- gathered operand inside 256 MiB -- and the
+    * ogbn-products shape at (8, 16) -- beyond it; bf16, forward + backward, 5 alternating runs of 5 steps): every native run is below every
+    * run of the conversion route in both classes -- 0.63-0.68 of its time inside 256 MiB, 0.62 beyond (forward alone 0.57-0.60), at
+    * 0.19-0.24 of its peak memory.  Both classes pay. */
+   return (rows_gathered > 0 && ld > 0) ? 1 : 0;
+}
+int    isplib_gat16_auto(int64_t rows_gathered, int64_t ld);                      /* the same rule as a symbol */
+/*
  * Staged column panels (sum / mean on 64-column slots only).  What a gather of a 128-byte line costs depends on the line's
  * ADDRESS: profiles/line_classes.txt (scripts/ubench/line_classes.hip) is the table, DESIGN.md section 5 reads it.  Before the
  * dispatches of a panel whose lines sit in a slow class, fusedMM_csr_stream_hip may copy the panel's 64 columns into the tail

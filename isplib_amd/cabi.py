@@ -159,6 +159,29 @@ def attention16_native_pays(rows_gathered: int, ld: int) -> bool:
     return bool(rows_gathered > 0 and ld > 0)
 
 
+GAT16_K_MIN, GAT16_K_MAX = 8, 512      # the 16-bit GAT entries: heads * d, eight columns per lane, one 16-byte chunk per lane
+
+
+def gat16_serves(rows_gathered: int, heads: int, d: int, ld: int) -> bool:
+    """isplib_gat16_serves of the header: the 16-bit GAT entries (isplib_gat16_csr_hip and its two backward entries) gather
+    `rows_gathered` rows of heads * d 2-byte elements at leading dimension ld through one buffer descriptor; with one head d is even,
+    with more d is a power of two >= 8 (a head is an aligned group of d / 8 lanes and a lane's eight columns never straddle heads)."""
+    if heads < 1 or d < 1 or not GAT16_K_MIN <= heads * d <= GAT16_K_MAX:
+        return False
+    if (d % 2) if heads == 1 else (d < 8 or d & (d - 1)):
+        return False
+    return (ld % 2 == 0 and ld >= heads * d and rows_gathered < 2 ** 31 and
+            (rows_gathered <= 0 or rows_gathered * ld * 2 <= DENSE_BYTES_MAX))
+
+
+def gat16_native_pays(rows_gathered: int, ld: int) -> bool:
+    """isplib_gat16_native_pays of the header: the classes of calls (the gathered operand beyond 256 MiB at 2 bytes per element or not)
+    in which every native run of the 16-bit GAT operator (forward + backward) measured faster than every run of the conversion route
+    (profiles/gat16_ab.txt: both classes do -- the Reddit shape at (H, d) = (8, 8) / (8, 16) inside 256 MiB, the ogbn-products shape at
+    (8, 16) beyond it); tests/test_gat16_host.py compares the two."""
+    return bool(rows_gathered > 0 and ld > 0)
+
+
 def owner_exchange_serves(m: int, k: int, world: int, cuts) -> bool:
     """isplib_owner_exchange_serves of the header: m x k winners split for `world` owners at the row boundaries `cuts`."""
     if not 1 <= world <= OWNER_WORLD_MAX or m < 0 or k < 0 or m * k >= MINMAX_BW_PAIRS_END:
@@ -212,6 +235,7 @@ EXPORTS = (
     "isplib_attention16_csr_hip", "isplib_attention16_bw_rows_hip", "isplib_attention16_bw_cols_hip", "isplib_attention16_domain",
     "isplib_attention16_auto",
     "isplib_gat_csr_hip", "isplib_gat_bw_rows_hip", "isplib_gat_bw_cols_hip", "isplib_gat_domain",
+    "isplib_gat16_csr_hip", "isplib_gat16_bw_rows_hip", "isplib_gat16_bw_cols_hip", "isplib_gat16_domain", "isplib_gat16_auto",
 )
 
 # include/isplib_hip_experimental.h (libisplib_hip_exp.so): forms measured slower than the defaults; tests and experiment scripts only
@@ -473,6 +497,18 @@ def lib() -> ctypes.CDLL:
         L.isplib_gat_bw_cols_hip.restype = ctypes.c_int
         L.isplib_gat_bw_cols_hip.argtypes = [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _vp, _vp,
                                              _i64, _vp, _vp]
+        L.isplib_gat16_domain.restype = ctypes.c_int
+        L.isplib_gat16_domain.argtypes = [_i64, _i64, _i64, _i64]
+        L.isplib_gat16_auto.restype = ctypes.c_int
+        L.isplib_gat16_auto.argtypes = [_i64, _i64]
+        L.isplib_gat16_csr_hip.restype = ctypes.c_int
+        L.isplib_gat16_csr_hip.argtypes = [ctypes.c_int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _vp]
+        L.isplib_gat16_bw_rows_hip.restype = ctypes.c_int
+        L.isplib_gat16_bw_rows_hip.argtypes = [ctypes.c_int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp,
+                                               _vp, _vp, _vp]
+        L.isplib_gat16_bw_cols_hip.restype = ctypes.c_int
+        L.isplib_gat16_bw_cols_hip.argtypes = [ctypes.c_int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp,
+                                               _vp, _vp, _i64, _vp, _vp]
         L.isplib_attention16_domain.restype = ctypes.c_int
         L.isplib_attention16_domain.argtypes = [_i64, _i64, _i64]
         L.isplib_attention16_auto.restype = ctypes.c_int
@@ -2088,6 +2124,137 @@ def attention16_bw_cols(colptr, row_t, x, y, g, lse, dsum, scale: Optional[float
                                                   _ptr(lse), _ptr(dsum), _ptr(out), lddy, _stream(y.device))
     _check(st, "isplib_attention16_bw_cols_hip")
     return out
+
+
+def _gat16_domain(rows_gathered: int, heads: int, d: int, ld: int) -> None:
+    if d > 0 and not gat16_serves(rows_gathered, heads, d, ld):
+        raise ValueError(f"isplib_amd: outside the 16-bit GAT entries' domain (isplib_gat16_serves: {GAT16_K_MIN} <= heads * d <= {GAT16_K_MAX}, "
+                         f"heads == 1 with d even or d a power of two >= 8, the pitch even, gathered rows < 2^31, rows * pitch * 2 <= 3.5 GiB), "
+                         f"got rows={rows_gathered}, heads={heads}, d={d}, pitch={ld}")
+
+
+def gat16_forward(rowptr, col, y, a_dst, a_src, heads: int = 1, negative_slope: float = 0.2, *, out=None, check: bool = True):
+    """`gat` for a bf16 / fp16 `y` (isplib_gat16_csr_hip): y [n, heads * d] goes in as it lies, the scores a_dst [m, heads] and a_src
+    [n, heads] are dense float32 as in `gat`, every product, sum and exponential is fp32, z is rounded once to y's dtype.  Returns
+    (z [m, heads * d] 16-bit, lse [m, heads] fp32); `out` = (z, lse).  The operand checks are gat's, with the 16-bit family's (even
+    pitches, 4-byte aligned bases)."""
+    if not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1 or rowptr.numel() < 1:
+        raise ValueError("isplib_amd: `rowptr` (m + 1 entries) must be a 1-D tensor")
+    m = rowptr.numel() - 1
+    if not isinstance(y, torch.Tensor) or y.dim() != 2:
+        raise ValueError("isplib_amd: `y` must be a 2-D tensor [n, heads * d]")
+    n, k = y.size(0), y.size(1)
+    ldy = _attn16_dense(y, "y", n, None, "one row per column of the sparse operand")
+    d = _gat_heads(heads, k)
+    _gat_table(a_dst, "a_dst", m, heads)
+    _gat_table(a_src, "a_src", n, heads)
+    rowptr, col = _attn_structure(rowptr, col, "rowptr", "col", n, check)
+    if out is not None:
+        z, lse = out
+        ldz = _attn16_dense(z, "out[0]", m, k, "z", y.dtype)
+        _gat_table(lse, "out[1]", m, heads)
+    _gat16_domain(n, heads, d, ldy)
+    _same_gpu((("y", y), ("a_dst", a_dst), ("a_src", a_src), ("rowptr", rowptr), ("col", col)) +
+              ((("out[0]", out[0]), ("out[1]", out[1])) if out is not None else ()))
+    if out is None:
+        z = torch.empty((m, k), dtype=y.dtype, device=y.device)
+        lse = torch.empty((m, heads), dtype=torch.float32, device=y.device)
+        ldz = max(k, 1)
+    if m == 0 or k == 0:
+        if k == 0 and m > 0:
+            lse.fill_(float("-inf"))
+        return z, lse
+    rp = rowptr.data_ptr()
+    with torch.cuda.device(y.device):
+        st = lib().isplib_gat16_csr_hip(HALF_DTYPES[y.dtype], m, n, k, col.numel(), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8),
+                                        _ptr(a_dst), _ptr(y), ldy, _ptr(a_src), heads, float(negative_slope), _ptr(z), ldz, _ptr(lse),
+                                        _stream(y.device))
+    _check(st, "isplib_gat16_csr_hip")
+    return z, lse
+
+
+def gat16_backward_rows(rowptr, col, y, a_dst, a_src, g, lse, heads: int = 1, negative_slope: float = 0.2, *, out=None, check: bool = True):
+    """The backward of `gat16_forward` over the rows (isplib_gat16_bw_rows_hip): for g = dL/dz [m, heads * d] (y's dtype) and the
+    forward's lse -- z is NOT read: D[i,h] = sum_e a_e <g_i, y_j>_h is formed in fp32 from the row's edges, in the same pass as
+    d a_dst = P - D Q.  Returns (d_a_dst [m, heads], D [m, heads]), both fp32; an empty row has both 0.  `out` = (d_a_dst, D)."""
+    if not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1 or rowptr.numel() < 1:
+        raise ValueError("isplib_amd: `rowptr` (m + 1 entries) must be a 1-D tensor")
+    m = rowptr.numel() - 1
+    if not isinstance(y, torch.Tensor) or y.dim() != 2:
+        raise ValueError("isplib_amd: `y` must be a 2-D tensor [n, heads * d]")
+    n, k = y.size(0), y.size(1)
+    ldy = _attn16_dense(y, "y", n, None, "one row per column of the sparse operand")
+    d = _gat_heads(heads, k)
+    _gat_table(a_dst, "a_dst", m, heads)
+    _gat_table(a_src, "a_src", n, heads)
+    ldg = _attn16_dense(g, "g", m, k, "the gradient of z", y.dtype)
+    _gat_table(lse, "lse", m, heads)
+    rowptr, col = _attn_structure(rowptr, col, "rowptr", "col", n, check)
+    if out is not None:
+        _gat_table(out[0], "out[0]", m, heads)
+        _gat_table(out[1], "out[1]", m, heads)
+    _gat16_domain(n, heads, d, ldy)
+    _same_gpu((("y", y), ("a_dst", a_dst), ("a_src", a_src), ("g", g), ("lse", lse), ("rowptr", rowptr), ("col", col)) +
+              ((("out[0]", out[0]), ("out[1]", out[1])) if out is not None else ()))
+    if out is None:
+        out = (torch.empty((m, heads), dtype=torch.float32, device=y.device), torch.empty((m, heads), dtype=torch.float32, device=y.device))
+    dadst, dsum = out
+    if m == 0 or k == 0:
+        if k == 0 and m > 0:
+            dadst.zero_()
+            dsum.zero_()
+        return dadst, dsum
+    rp = rowptr.data_ptr()
+    with torch.cuda.device(y.device):
+        st = lib().isplib_gat16_bw_rows_hip(HALF_DTYPES[y.dtype], m, n, k, col.numel(), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8),
+                                            _ptr(a_dst), _ptr(y), ldy, _ptr(a_src), heads, float(negative_slope), _ptr(g), ldg, _ptr(lse),
+                                            _ptr(dadst), _ptr(dsum), _stream(y.device))
+    _check(st, "isplib_gat16_bw_rows_hip")
+    return dadst, dsum
+
+
+def gat16_backward_cols(colptr, row_t, y, a_dst, a_src, g, lse, dsum, heads: int = 1, negative_slope: float = 0.2, *, out=None,
+                        check: bool = True):
+    """The backward of `gat16_forward` over the columns (isplib_gat16_bw_cols_hip), on the transposed structure: dy_j[head h] = sum over
+    the entries e = (i, j) of column j of a_e g_i[head h], rounded once to y's dtype, and d a_src[j,h] = sum of du_e (fp32), with `lse`
+    of the forward and `dsum` = D of gat16_backward_rows.  Returns (dy [n, heads * d] 16-bit, d_a_src [n, heads] fp32); `out` = (dy,
+    d_a_src)."""
+    if not isinstance(colptr, torch.Tensor) or colptr.dim() != 1 or colptr.numel() < 1:
+        raise ValueError("isplib_amd: `colptr` (n + 1 entries) must be a 1-D tensor")
+    n = colptr.numel() - 1
+    ldy = _attn16_dense(y, "y", n, None, "one row per column of the sparse operand")
+    k = y.size(1)
+    d = _gat_heads(heads, k)
+    if not isinstance(g, torch.Tensor) or g.dim() != 2:
+        raise ValueError("isplib_amd: `g` must be a 2-D tensor [m, heads * d]")
+    m = g.size(0)
+    ldg = _attn16_dense(g, "g", m, k, "the gradient of z", y.dtype)
+    _gat_table(a_dst, "a_dst", m, heads)
+    _gat_table(a_src, "a_src", n, heads)
+    _gat_table(lse, "lse", m, heads)
+    _gat_table(dsum, "dsum", m, heads)
+    colptr, row_t = _attn_structure(colptr, row_t, "colptr", "row_t", m, check)
+    if out is not None:
+        lddy = _attn16_dense(out[0], "out[0]", n, k, "dy", y.dtype)
+        _gat_table(out[1], "out[1]", n, heads)
+    _gat16_domain(m, heads, d, ldg)
+    _same_gpu((("y", y), ("a_dst", a_dst), ("a_src", a_src), ("g", g), ("lse", lse), ("dsum", dsum), ("colptr", colptr), ("row_t", row_t)) +
+              ((("out[0]", out[0]), ("out[1]", out[1])) if out is not None else ()))
+    if out is None:
+        out = (torch.empty((n, k), dtype=y.dtype, device=y.device), torch.empty((n, heads), dtype=torch.float32, device=y.device))
+        lddy = max(k, 1)
+    dy, dasrc = out
+    if n == 0 or k == 0:
+        if k == 0 and n > 0:
+            dasrc.zero_()
+        return dy, dasrc
+    cp = colptr.data_ptr()
+    with torch.cuda.device(y.device):
+        st = lib().isplib_gat16_bw_cols_hip(HALF_DTYPES[y.dtype], m, n, k, row_t.numel(), _ptr(row_t), ctypes.c_void_p(cp),
+                                            ctypes.c_void_p(cp + 8), _ptr(a_dst), _ptr(y), ldy, _ptr(a_src), heads, float(negative_slope),
+                                            _ptr(g), ldg, _ptr(lse), _ptr(dsum), _ptr(dy), lddy, _ptr(dasrc), _stream(y.device))
+    _check(st, "isplib_gat16_bw_cols_hip")
+    return dy, dasrc
 
 
 def fusedMM_csr_rows16_minmax_hip(imessage: int, rowptr, col, val, order, y, z, z_arg=None, check: bool = True, dtype=None, k=None, ldy=None,

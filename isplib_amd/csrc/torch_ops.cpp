@@ -1483,6 +1483,128 @@ Tensor attention_spmm16(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, 
    return AttentionSpmm16::apply(rowptr, col, colptr, row_t, x, y, scale)[0];
 }
 
+// ---- the GAT aggregation for a bf16 / fp16 `y` (isplib_gat16_*_hip) ----------
+// y goes in as it lies, z and dy come back in its dtype; the two score tables, lse, D and the score gradients stay fp32: no fp32 [*, K]
+// tensor in either direction.  Saved for backward: the structure, y, a_dst, a_src and lse -- NOT z: the rows kernel forms D[i,h] from the
+// row's edges.  y (or the gradient) is copied only without unit inner stride, or where the domain admits it packed but not at its pitch
+// or alignment.
+static AttnOperand gat16_operand(const Tensor &src, const char *name, int64_t rows, int64_t k, int64_t heads, at::ScalarType dtype) {
+   TORCH_CHECK(src.defined() && src.scalar_type() == dtype, "isplib: gat_spmm16: `", name, "` must be ", dtype, ", got ",
+               src.defined() ? src.scalar_type() : at::ScalarType::Undefined);
+   TORCH_CHECK(src.is_cuda(), "isplib: gat_spmm16: `", name, "` must be a GPU tensor -- there is no CPU path");
+   TORCH_CHECK(src.dim() == 2 && src.size(0) == rows && src.size(1) == k, "isplib: gat_spmm16: `", name, "` must be [", rows, ", ", k, "], got ",
+               src.sizes());
+   if (rows == 0 || k == 0) return {src, std::max<int64_t>(k, 1)};
+   const int64_t ld = rows > 1 ? src.stride(0) : k;
+   const bool as_is = src.stride(1) == 1 && ld >= k && ((uintptr_t)src.data_ptr() & 3) == 0 && isplib_gat16_serves(rows, heads, k / heads, ld);
+   if (as_is) return {src, ld};
+   return {src.clone(at::MemoryFormat::Contiguous), k};
+}
+
+static Tensor gat16_table(const Tensor &src, const char *name, int64_t rows, int64_t heads) {
+   TORCH_CHECK(src.defined() && src.scalar_type() == at::kFloat, "isplib: gat_spmm16: `", name, "` must be float32 (the score tables stay fp32), got ",
+               src.defined() ? src.scalar_type() : at::ScalarType::Undefined);
+   TORCH_CHECK(src.is_cuda(), "isplib: gat_spmm16: `", name, "` must be a GPU tensor -- there is no CPU path");
+   TORCH_CHECK(src.dim() == 2 && src.size(0) == rows && src.size(1) == heads, "isplib: gat_spmm16: `", name, "` must be [", rows, ", ", heads,
+               "] (one entry per row and head), got ", src.sizes());
+   return src.contiguous();
+}
+
+class GatSpmm16 : public torch::autograd::Function<GatSpmm16> {
+ public:
+   static variable_list forward(AutogradContext *ctx, Variable rowptr, Variable col, Variable colptr, Variable row_t, Variable y, Variable a_dst,
+                                Variable a_src, int64_t heads, double negative_slope) {
+      check_index(rowptr, "rowptr"); check_index(col, "col"); check_index(colptr, "colptr"); check_index(row_t, "row_t");
+      TORCH_CHECK(y.defined() && y.dim() == 2, "isplib: gat_spmm16 needs a 2-D `y` [N, heads * d]");
+      TORCH_CHECK(is_half(y), "isplib: gat_spmm16: `y` must be bfloat16 or float16, got ", y.scalar_type(), " (float32: gat_spmm)");
+      OpTimer timer("FUSEDMM_GAT_FW", y);
+      const int64_t M = rowptr.numel() - 1, N = colptr.numel() - 1, K = y.size(1), nnz = col.numel();
+      TORCH_CHECK(M >= 0 && N >= 0 && row_t.numel() == nnz, "isplib: gat_spmm16: `rowptr` / `colptr` need one entry more than rows / columns, "
+                                                             "`row_t` one entry per stored entry");
+      TORCH_CHECK(heads >= 1 && K % heads == 0, "isplib: gat_spmm16: the width of `y` (", K, ") must be heads * d, got heads = ", heads);
+      const at::ScalarType dt = y.scalar_type();
+      const AttnOperand yo = gat16_operand(y, "y", N, K, heads, dt);
+      const Tensor ad = gat16_table(a_dst, "a_dst", M, heads), as = gat16_table(a_src, "a_src", N, heads);
+      for (const Tensor *t : {&rowptr, &col, &colptr, &row_t, &a_dst, &a_src})
+         TORCH_CHECK(t->device() == y.device(), "isplib: gat_spmm16: every operand must be on y's device");
+      TORCH_CHECK(K == 0 || isplib_gat16_serves(N, heads, K / heads, yo.ld), "isplib: gat_spmm16: outside isplib_gat16_serves (",
+                  ISPLIB_GAT16_K_MIN, " <= heads * d <= ", ISPLIB_GAT16_K_MAX, ", heads == 1 with d even or d a power of two >= 8, N < 2^31, "
+                  "N * pitch * 2 <= 3.5 GiB): N = ", N, ", heads = ", heads, ", d = ", K / heads, ", pitch = ", yo.ld);
+      c10::DeviceGuard guard(y.device());
+      const int code = dt == at::kBFloat16 ? ISPLIB_DTYPE_BF16 : ISPLIB_DTYPE_F16;
+      const Tensor rp = rowptr.contiguous(), cl = col.contiguous();
+      Tensor z = at::empty({M, K}, y.options()), lse = at::empty({M, heads}, y.options().dtype(at::kFloat));
+      if (M > 0 && K > 0) {
+         const int st = isplib_gat16_csr_hip(code, M, N, K, nnz, cl.data_ptr<int64_t>(), rp.data_ptr<int64_t>(), rp.data_ptr<int64_t>() + 1,
+                                             ad.data_ptr<float>(), nnz > 0 ? yo.t.data_ptr() : nullptr, yo.ld,
+                                             nnz > 0 ? as.data_ptr<float>() : nullptr, heads, (float)negative_slope, z.data_ptr(), K,
+                                             lse.data_ptr<float>(), current_stream(y));
+         check_status(st, "isplib_gat16_csr_hip");
+      } else if (M > 0) {
+         lse.fill_(-std::numeric_limits<float>::infinity());
+      }
+      ctx->saved_data["heads"] = heads;
+      ctx->saved_data["negative_slope"] = negative_slope;
+      ctx->save_for_backward({rp, cl, colptr, row_t, y, a_dst, a_src, lse});
+      return {z};
+   }
+
+   static variable_list backward(AutogradContext *ctx, variable_list grad_outs) {
+      OpTimer timer("FUSEDMM_GAT_BW", grad_outs[0]);
+      const bool need_y = ctx->needs_input_grad(4), need_dst = ctx->needs_input_grad(5), need_src = ctx->needs_input_grad(6);
+      auto grad_y = Variable(), grad_dst = Variable(), grad_src = Variable();
+      if (need_y || need_dst || need_src) {
+         auto saved = ctx->get_saved_variables();
+         auto rp = saved[0], cl = saved[1], colptr = saved[2].contiguous(), row_t = saved[3].contiguous(), y = saved[4], lse = saved[7];
+         const int64_t heads = ctx->saved_data["heads"].toInt();
+         const float ns = (float)ctx->saved_data["negative_slope"].toDouble();
+         const int64_t M = rp.numel() - 1, N = colptr.numel() - 1, K = y.size(1), nnz = cl.numel();
+         const at::ScalarType dt = y.scalar_type();
+         const AttnOperand yo = gat16_operand(y, "y", N, K, heads, dt);
+         const Tensor ad = gat16_table(saved[5], "a_dst", M, heads), as = gat16_table(saved[6], "a_src", N, heads);
+         const AttnOperand go = gat16_operand(grad_outs[0].to(dt), "grad_out", M, K, heads, dt);      // a grad of another dtype is cast to y's
+         c10::DeviceGuard guard(y.device());
+         const int code = dt == at::kBFloat16 ? ISPLIB_DTYPE_BF16 : ISPLIB_DTYPE_F16;
+         const auto f32 = y.options().dtype(at::kFloat);
+         // the rows kernel always runs: its D[i,h] feeds the columns kernel; the columns kernel only when y or a_src asks
+         Tensor dadst = at::empty({M, heads}, f32), dsum = at::empty({M, heads}, f32);
+         if (M > 0 && K > 0) {
+            const int st = isplib_gat16_bw_rows_hip(code, M, N, K, nnz, cl.data_ptr<int64_t>(), rp.data_ptr<int64_t>(), rp.data_ptr<int64_t>() + 1,
+                                                    ad.data_ptr<float>(), nnz > 0 ? yo.t.data_ptr() : nullptr, yo.ld,
+                                                    nnz > 0 ? as.data_ptr<float>() : nullptr, heads, ns, go.t.data_ptr(), go.ld,
+                                                    lse.data_ptr<float>(), dadst.data_ptr<float>(), dsum.data_ptr<float>(), current_stream(y));
+            check_status(st, "isplib_gat16_bw_rows_hip");
+         } else if (M > 0) {
+            dadst.zero_();
+         }
+         if (need_dst) grad_dst = dadst;
+         if (need_y || need_src) {
+            TORCH_CHECK(K == 0 || isplib_gat16_serves(M, heads, K / heads, go.ld),
+                        "isplib: gat_spmm16 backward: outside isplib_gat16_serves for the gathered rows of the gradient: M = ", M, ", K = ", K);
+            Tensor dy = at::empty({N, K}, y.options()), dasrc = at::empty({N, heads}, f32);
+            if (N > 0 && K > 0) {
+               const int st = isplib_gat16_bw_cols_hip(code, M, N, K, nnz, row_t.data_ptr<int64_t>(), colptr.data_ptr<int64_t>(),
+                                                       colptr.data_ptr<int64_t>() + 1, nnz > 0 ? ad.data_ptr<float>() : nullptr, yo.t.data_ptr(),
+                                                       yo.ld, as.data_ptr<float>(), heads, ns, nnz > 0 ? go.t.data_ptr() : nullptr, go.ld,
+                                                       lse.data_ptr<float>(), dsum.data_ptr<float>(), dy.data_ptr(), K, dasrc.data_ptr<float>(),
+                                                       current_stream(y));
+               check_status(st, "isplib_gat16_bw_cols_hip");
+            } else if (N > 0) {
+               dasrc.zero_();
+            }
+            if (need_y) grad_y = dy;
+            if (need_src) grad_src = dasrc;
+         }
+      }
+      return {Variable(), Variable(), Variable(), Variable(), grad_y, grad_dst, grad_src, Variable(), Variable()};
+   }
+};
+
+Tensor gat_spmm16(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor y, Tensor a_dst, Tensor a_src, int64_t heads,
+                  double negative_slope) {
+   return GatSpmm16::apply(rowptr, col, colptr, row_t, y, a_dst, a_src, heads, negative_slope)[0];
+}
+
 // introspection / housekeeping of the per-graph handle cache of the reference-schema operators
 int64_t graph_cache_size() {
    std::lock_guard<std::mutex> lock(g_graph_mutex);
@@ -1535,4 +1657,6 @@ TORCH_LIBRARY(isplib, m) {
    m.def("gat_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor y, Tensor a_dst, Tensor a_src, int heads, float negative_slope) -> Tensor",
          &gat_spmm);
    m.def("attention_spmm16(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor x, Tensor y, float scale) -> Tensor", &attention_spmm16);
+   m.def("gat_spmm16(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor y, Tensor a_dst, Tensor a_src, int heads, float negative_slope) -> Tensor",
+         &gat_spmm16);
 }

@@ -27,7 +27,8 @@ ISPLIB_HALF_MINMAX=convert|native|auto does the same for max / min (rows16_minma
 for the backward of a 16-bit `mean` on an unweighted graph (rows16_mean_bw_route), ISPLIB_HALF_DA=convert|native|auto for the value
 gradient of a 16-bit sum / mean (rows16_da_route), ISPLIB_HALF_GCN=convert|native|auto for gcn_norm_matmul on 16-bit features
 (rows16_gcn_route; unset: such a call raises, as it always did), ISPLIB_HALF_ATTENTION=convert|native|auto for attention_matmul on
-16-bit operands (attention16_route; unset: such a call raises, as it always did); the first three default to convert;
+16-bit operands (attention16_route; unset: such a call raises, as it always did), ISPLIB_HALF_GAT=convert|native|auto for gat_matmul on
+a 16-bit `y` (gat16_route; unset: such a call raises, as it always did); the first three default to convert;
 ISPLIB_TUNE_FILE names a tuning table to load at import; ISPLIB_DEBUG=1 prints per-operator device times.
 """
 from __future__ import annotations
@@ -417,6 +418,37 @@ def attention16_route(dtype, k: int, pitch: int, n: int, mode: Optional[str] = N
     return "attention16" if mode == "native" or cabi.attention16_native_pays(n, ld) else "convert"
 
 
+def gat16_route(dtype, heads: int, d: int, pitch: int, n: int, mode: Optional[str] = None) -> str:
+    """Which way gat_matmul with a 16-bit `y` goes once ISPLIB_HALF_GAT is set, asked per GATHERED wide operand (y with its rows for the
+    forward and the rows kernel, the gradient with its rows, packed, for the backward over the columns): "gat16"
+    (torch.ops.isplib.gat_spmm16 on the 16-bit kernels, isplib_gat16_*_hip: y and the gradients as they lie, half the gathered bytes, no
+    fp32 [*, K] tensor in either direction) or "convert" (`y.float()` -> the fp32 operator -> `.to(dtype)`).  A pure function -- no
+    device, no library call:
+      * gat16 needs bf16 / fp16 and the operand's shape, [n, heads * d] at its own row pitch or, failing that, packed, inside the
+        entries' domain (cabi.gat16_serves: 8 <= heads * d <= 512, heads == 1 with d even or d a power of two >= 8, the pitch even);
+      * `mode` is ISPLIB_HALF_GAT (None: read from the environment; unset counts as "convert" here -- gat_matmul itself raises before
+        it asks -- and ISPLIB_HALF=convert wins over it): "convert" always converts, "native" takes the kernels wherever the above
+        holds, "auto" only in the classes -- the gathered operand beyond 256 MiB or not -- where every native run measured faster than
+        every run of the conversion route (cabi.gat16_native_pays, profiles/gat16_ab.txt).  Nothing raises."""
+    if dtype not in HALF_DTYPES:
+        return "convert"
+    from . import cabi
+    if mode is None:
+        mode = os.environ.get("ISPLIB_HALF", "auto")
+        if mode != "convert":
+            mode = os.environ.get("ISPLIB_HALF_GAT", "convert")
+    if mode not in ("native", "auto"):
+        return "convert"
+    k = heads * d
+    if cabi.gat16_serves(n, heads, d, pitch):
+        ld = pitch
+    elif cabi.gat16_serves(n, heads, d, k):
+        ld = k
+    else:
+        return "convert"
+    return "gat16" if mode == "native" or cabi.gat16_native_pays(n, ld) else "convert"
+
+
 _ROWS16_MARK = torch.tensor([16], dtype=torch.int32)      # second tensor of a 16-bit row plan (torch_ops.cpp: is_rows16_plan)
 _ROWS16_DA_MARK = torch.tensor([0xDA], dtype=torch.int32)  # third tensor of a forward plan whose dA runs in 16 bits (is_rows16_da_plan)
 
@@ -681,14 +713,25 @@ def gat_matmul(src, y: torch.Tensor, a_dst: torch.Tensor, a_src: torch.Tensor, h
     (head h owns the columns [h*d, (h+1)*d)), `a_dst` [M, heads], `a_src` [N, heads] float32 GPU tensors; with ``heads == 1`` the two
     scores may be 1-D [rows].  On a square graph the same tensor may be passed for both scores: its gradient receives both parts.
     The stored values of `src` are not read; an empty row gives 0.  The backward keeps y, the scores, z and one scalar per row and
-    head -- nothing per edge.  fp32 only (bf16 / fp16 operands raise TypeError); there is no fallback route: outside isplib_gat_serves
-    (heads * d <= 512; heads == 1 or d a power of two >= 4) the call raises ValueError.  GATv2 is not this operator."""
+    head -- nothing per edge.  fp32 only by default (bf16 / fp16 operands raise TypeError); there is no fallback route: outside
+    isplib_gat_serves (heads * d <= 512; heads == 1 or d a power of two >= 4) the call raises ValueError.  GATv2 is not this operator.
+    A bf16 / fp16 `y` is opt-in: with ISPLIB_HALF_GAT=convert|native|auto set it goes where gat16_route says -- the 16-bit operator
+    (torch.ops.isplib.gat_spmm16, which keeps y, the scores and lse for its backward and no z) where BOTH gathered operands are admitted
+    (y with its rows, the gradient with M rows at pitch K), else `y.float()` -> this function -> `.to(dtype)`, which raises only what the
+    fp32 call raises.  Each score may then be float32 or of y's dtype (a 16-bit score is widened by `.float()`, which is exact, and its
+    gradient returns in its own dtype through that cast); the result and y's gradient have y's dtype.  fp32 calls do not read the
+    variable."""
     from . import cabi
+    half = isinstance(y, torch.Tensor) and y.dtype in HALF_DTYPES and os.environ.get("ISPLIB_HALF_GAT") is not None
     for name, t in (("y", y), ("a_dst", a_dst), ("a_src", a_src)):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"isplib_amd: `{name}` must be a tensor, got {type(t).__name__}")
-        if t.dtype != torch.float32:
+        if half and name != "y" and t.dtype not in (torch.float32, y.dtype):
+            raise TypeError(f"isplib_amd: `{name}` must be float32 or of `y`'s dtype ({y.dtype}), got {t.dtype}")
+        if not half and t.dtype != torch.float32:
             raise TypeError(f"isplib_amd: `{name}` must be float32, got {t.dtype} (the attention operator is fp32 only)")
+    if half:
+        return _gat_matmul16(src, y, a_dst, a_src, heads, negative_slope)
     if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
         raise ValueError(f"isplib_amd: `heads` must be a positive int, got {heads!r}")
     if y.dim() != 2:
@@ -721,6 +764,32 @@ def gat_matmul(src, y: torch.Tensor, a_dst: torch.Tensor, a_src: torch.Tensor, h
     if a_dst.device != y.device or a_src.device != y.device or st._rowptr.device != y.device:
         raise ValueError("isplib_amd: `y`, `a_dst`, `a_src` and the sparse matrix must be on one device")
     return torch.ops.isplib.gat_spmm(st._rowptr, st._col, st.colptr(), st.row_t(), y, a_dst, a_src, heads, float(negative_slope))
+
+
+def _gat_matmul16(src, y, a_dst, a_src, heads, negative_slope):
+    """gat_matmul for a bf16 / fp16 `y` under ISPLIB_HALF_GAT: the 16-bit operator where gat16_route admits BOTH gathered operands (y by
+    the forward and the rows kernel, the gradient -- M rows, packed -- by the columns kernel), else the conversion route."""
+    a_dst, a_src = a_dst.float(), a_src.float()       # exact, and no copy of an fp32 score; a gradient returns through the cast
+    native = False
+    if isinstance(heads, int) and not isinstance(heads, bool) and heads >= 1 and y.dim() == 2 and y.size(1) % heads == 0 and y.is_cuda:
+        st = _storage_of(src, y)
+        m_rows, n_cols, k = st._rowptr.numel() - 1, st._sparse_sizes[1], y.size(1)
+        d = k // heads
+        pitch = y.stride(0) if n_cols > 1 and y.stride(1) == 1 and y.stride(0) >= k else k
+        native = (y.size(0) == n_cols and a_dst.is_cuda and a_src.is_cuda and
+                  gat16_route(y.dtype, heads, d, pitch, n_cols) == "gat16" and gat16_route(y.dtype, heads, d, k, m_rows) == "gat16")
+    if not native:
+        return gat_matmul(src, y.float(), a_dst, a_src, heads, negative_slope).to(y.dtype)
+    if heads == 1:
+        a_dst = a_dst.unsqueeze(1) if a_dst.dim() == 1 else a_dst
+        a_src = a_src.unsqueeze(1) if a_src.dim() == 1 else a_src
+    for name, t, rows, what in (("a_dst", a_dst, m_rows, "row"), ("a_src", a_src, n_cols, "column")):
+        if t.dim() != 2 or t.size(0) != rows or t.size(1) != heads:
+            raise ValueError(f"isplib_amd: `{name}` must be [{rows}, {heads}] (one entry per {what} of the sparse matrix and head), got "
+                             f"shape {tuple(t.shape)}")
+    if a_dst.device != y.device or a_src.device != y.device or st._rowptr.device != y.device:
+        raise ValueError("isplib_amd: `y`, `a_dst`, `a_src` and the sparse matrix must be on one device")
+    return torch.ops.isplib.gat_spmm16(st._rowptr, st._col, st.colptr(), st.row_t(), y, a_dst, a_src, heads, float(negative_slope))
 
 
 def gcn_norm_matmul(src, other: torch.Tensor, bias: Optional[torch.Tensor] = None, relu: bool = False) -> torch.Tensor:

@@ -343,6 +343,7 @@ class SparseTensor:
         return attention_matmul(self, x, y, scale)
 
     def gat_matmul(self, y: torch.Tensor, a_dst: torch.Tensor, a_src: torch.Tensor, heads: int = 1, negative_slope: float = 0.2) -> torch.Tensor:
-        """GAT attention aggregation over this matrix's stored entries, all heads in one launch (plugin.gat_matmul)."""
+        """GAT attention aggregation over this matrix's stored entries, all heads in one launch (plugin.gat_matmul); a bf16 / fp16 `y`
+        is opt-in through ISPLIB_HALF_GAT."""
         from .plugin import gat_matmul
         return gat_matmul(self, y, a_dst, a_src, heads, negative_slope)
