@@ -925,6 +925,56 @@ static inline int isplib_gat16_native_pays(int64_t rows_gathered, int64_t ld) {
 }
 int    isplib_gat16_auto(int64_t rows_gathered, int64_t ld);                      /* the same rule as a symbol */
 /*
+ * GATv2 attention aggregation over the stored entries e = (i, j) of a CSR matrix A [m, n], all heads in one launch, forward and
+ * backward, fp32.  With x: m x ldx (the target side, the wave's own row), y: n x ldy (the source side: gathered, and what is
+ * aggregated), both of k = heads * d columns (head h owns the columns [h*d, (h+1)*d)), att: heads x d (k contiguous floats) and a
+ * slope `negative_slope` = ns, for every head h and c over the head's columns:
+ *   u_ec = x_ic + y_jc         sl_ec = u_ec > 0 ? 1 : ns       v_ec = sl_ec u_ec           s_e = sum_c att_c v_ec
+ *   a_e  = exp(s_e - lse[i,h]),  lse[i,h] = log sum_{e in row i} exp(s_e)                  z_i[head h] = sum_e a_e y_j[head h]
+ * and, for g = dL/dz (m x ldg),
+ *   D[i,h] = <g_i, z_i>_h      t_e = <g_i, y_j>_h              ds_e = a_e (t_e - D[i,h])   q_ec = ds_e att_c sl_ec
+ *   dx_ic  = sum_e q_ec        dy_jc = sum_{e -> j} (a_e g_ic + q_ec)                      datt_c = sum_{all e} ds_e v_ec.
+ * This is the aggregation of GATv2Conv: the nonlinearity sits inside the dot product, so the score is no sum of per-node scalars
+ * and isplib_gat_csr_hip cannot express it.  Stored values of A are not read; every stored entry is its own edge, so a duplicate
+ * counts twice; the column order inside a row is free.  u_ec is one fp32 add, so the slope branch is decided by the sign of the
+ * exact sum; u_ec == 0 takes ns.  An empty row has z_i = 0, lse = -inf, D = 0 and dx_i = 0; a column no entry points at has
+ * dy_j = 0.  The softmax is computed relative to a running maximum, so no score overflows: a row of one entry returns y_j bit for
+ * bit.  A NaN in y_jc reaches the head of c in the rows that reference j, and nothing else.
+ *   isplib_gatv2_csr_hip      writes z (m x ldz) and lse (m x heads).
+ *   isplib_gatv2_bw_rows_hip  reads x, y, att, g, z and lse, writes dx (m x lddx) and dsum (m x heads: D, which the next entry
+ *                             reads) and, where datt is not NULL, datt (k floats): every block of the kernel writes one partial
+ *                             row into `workspace` (at least isplib_gatv2_bw_rows_workspace_bytes(m, k) bytes, 256-byte aligned;
+ *                             too small: ISPLIB_NOT_ENOUGH_MEM) and a second kernel adds the rows up in a fixed order.  datt ==
+ *                             NULL runs a kernel without that sum and ignores the workspace.
+ *   isplib_gatv2_bw_cols_hip  runs on the transposed structure (colb / cole: n column ranges into row_t); reads x, y, att, g, lse
+ *                             and dsum, writes dy (n x lddy).
+ * Nothing is kept per edge: the backward recomputes a_e from lse.  Outputs and the workspace are write-only and every element of
+ * every row is written, nothing between the rows of a pitched output.  One wave per row (per column), no atomics, a fixed order of
+ * operations: two launches give equal bits, datt included.  The entries neither allocate nor synchronise.
+ * Domain: isplib_gatv2_serves(rows_gathered, heads, d, ld) = isplib_gat_serves, for every GATHERED wide operand (y with n rows in
+ * the first two entries; x and g with m rows in the third).  Outside the domain: ISPLIB_NO_OPT_IMPL.  A negative dimension, a null
+ * operand, a k that is no multiple of heads, or a pitch of a row-resident operand or output below k: ISPLIB_FAIL.  All refusals
+ * come before any launch.  m == 0 or k == 0 (n == 0 or k == 0 in the third entry) succeeds without a launch and writes nothing.
+ */
+static inline int isplib_gatv2_serves(int64_t rows_gathered, int64_t heads, int64_t d, int64_t ld) {
+   return isplib_gat_serves(rows_gathered, heads, d, ld);
+}
+int    isplib_gatv2_domain(int64_t rows_gathered, int64_t heads, int64_t d, int64_t ld);   /* isplib_gatv2_serves as a symbol */
+int    isplib_gatv2_csr_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                            const int64_t *pntre, const float *x, int64_t ldx, const float *y, int64_t ldy,
+                            const float *att /* heads x d */, int64_t heads, float negative_slope, float *z, int64_t ldz,
+                            float *lse /* m x heads */, void *stream);
+size_t isplib_gatv2_bw_rows_workspace_bytes(int64_t m, int64_t k);
+int    isplib_gatv2_bw_rows_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                                const int64_t *pntre, const float *x, int64_t ldx, const float *y, int64_t ldy, const float *att,
+                                int64_t heads, float negative_slope, const float *g, int64_t ldg, const float *z, int64_t ldz,
+                                const float *lse, float *dx, int64_t lddx, float *dsum /* m x heads */, float *datt /* k, or NULL */,
+                                void *workspace, size_t workspace_bytes, void *stream);
+int    isplib_gatv2_bw_cols_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t, const int64_t *colb,
+                                const int64_t *cole, const float *x, int64_t ldx, const float *y, int64_t ldy, const float *att,
+                                int64_t heads, float negative_slope, const float *g, int64_t ldg, const float *lse,
+                                const float *dsum, float *dy, int64_t lddy, void *stream);
+/*
  * Staged column panels (sum / mean on 64-column slots only).  What a gather of a 128-byte line costs depends on the line's
  * ADDRESS: profiles/line_classes.txt (scripts/ubench/line_classes.hip) is the table, DESIGN.md section 5 reads it.  Before the
  * dispatches of a panel whose lines sit in a slow class, fusedMM_csr_stream_hip may copy the panel's 64 columns into the tail

@@ -141,6 +141,11 @@ def gat_serves(rows_gathered: int, heads: int, d: int, ld: int) -> bool:
     return ld >= heads * d and rows_gathered < 2 ** 31 and (rows_gathered <= 0 or rows_gathered * ld * 4 <= DENSE_BYTES_MAX)
 
 
+def gatv2_serves(rows_gathered: int, heads: int, d: int, ld: int) -> bool:
+    """isplib_gatv2_serves of the header: the GATv2 entries' domain IS isplib_gat_serves -- stated once."""
+    return gat_serves(rows_gathered, heads, d, ld)
+
+
 ATTENTION16_K_MIN, ATTENTION16_K_MAX = 8, 512   # the 16-bit attention entries: eight columns per lane, one 16-byte chunk per lane
 
 
@@ -236,6 +241,8 @@ EXPORTS = (
     "isplib_attention16_auto",
     "isplib_gat_csr_hip", "isplib_gat_bw_rows_hip", "isplib_gat_bw_cols_hip", "isplib_gat_domain",
     "isplib_gat16_csr_hip", "isplib_gat16_bw_rows_hip", "isplib_gat16_bw_cols_hip", "isplib_gat16_domain", "isplib_gat16_auto",
+    "isplib_gatv2_csr_hip", "isplib_gatv2_bw_rows_hip", "isplib_gatv2_bw_rows_workspace_bytes", "isplib_gatv2_bw_cols_hip",
+    "isplib_gatv2_domain",
 )
 
 # include/isplib_hip_experimental.h (libisplib_hip_exp.so): forms measured slower than the defaults; tests and experiment scripts only
@@ -497,6 +504,18 @@ def lib() -> ctypes.CDLL:
         L.isplib_gat_bw_cols_hip.restype = ctypes.c_int
         L.isplib_gat_bw_cols_hip.argtypes = [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _vp, _vp,
                                              _i64, _vp, _vp]
+        L.isplib_gatv2_domain.restype = ctypes.c_int
+        L.isplib_gatv2_domain.argtypes = [_i64, _i64, _i64, _i64]
+        L.isplib_gatv2_bw_rows_workspace_bytes.restype = ctypes.c_size_t
+        L.isplib_gatv2_bw_rows_workspace_bytes.argtypes = [_i64, _i64]
+        L.isplib_gatv2_csr_hip.restype = ctypes.c_int
+        L.isplib_gatv2_csr_hip.argtypes = [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _vp]
+        L.isplib_gatv2_bw_rows_hip.restype = ctypes.c_int
+        L.isplib_gatv2_bw_rows_hip.argtypes = [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _i64,
+                                               _vp, _vp, _i64, _vp, _vp, _vp, ctypes.c_size_t, _vp]
+        L.isplib_gatv2_bw_cols_hip.restype = ctypes.c_int
+        L.isplib_gatv2_bw_cols_hip.argtypes = [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _vp,
+                                               _vp, _i64, _vp]
         L.isplib_gat16_domain.restype = ctypes.c_int
         L.isplib_gat16_domain.argtypes = [_i64, _i64, _i64, _i64]
         L.isplib_gat16_auto.restype = ctypes.c_int
@@ -1985,6 +2004,176 @@ def gat_bw_cols(colptr, row_t, y, a_dst, a_src, g, lse, dsum, heads: int = 1, ne
                                           _ptr(dy), lddy, _ptr(dasrc), _stream(y.device))
     _check(st, "isplib_gat_bw_cols_hip")
     return dy, dasrc
+
+
+def _gatv2_att(att, name: str, heads: int, d: int) -> None:
+    """The attention vector of the GATv2 entries: a contiguous float32 [heads, d] tensor (k floats)."""
+    if not isinstance(att, torch.Tensor) or att.dim() != 2:
+        raise ValueError(f"isplib_amd: `{name}` must be a 2-D tensor [{heads}, {d}], got "
+                         f"{tuple(att.shape) if isinstance(att, torch.Tensor) else type(att).__name__}")
+    if att.dtype != torch.float32:
+        raise TypeError(f"isplib_amd: `{name}` must be float32, got {att.dtype} (the attention operator is fp32 only)")
+    if att.size(0) != heads or att.size(1) != d:
+        raise ValueError(f"isplib_amd: `{name}` must be [{heads}, {d}] (heads x d), got {tuple(att.shape)}")
+    if not att.is_contiguous():
+        raise ValueError(f"isplib_amd: `{name}` must be contiguous (k floats)")
+
+
+def _gatv2_domain(rows_gathered: int, heads: int, d: int, lds) -> None:
+    for ld in lds:
+        if d > 0 and not gatv2_serves(rows_gathered, heads, d, ld):
+            raise ValueError(f"isplib_amd: outside the GATv2 entries' domain (isplib_gatv2_serves = isplib_gat_serves: heads * d <= {GAT_K_MAX}, "
+                             f"heads == 1 or d a power of two >= 4, gathered rows < 2^31, rows * pitch * 4 <= 3.5 GiB), got "
+                             f"rows={rows_gathered}, heads={heads}, d={d}, pitch={ld}")
+
+
+def gatv2_bw_rows_workspace_bytes(m: int, k: int) -> int:
+    """isplib_gatv2_bw_rows_workspace_bytes: what `gatv2_bw_rows` needs behind `workspace` when `datt` is asked for."""
+    return int(lib().isplib_gatv2_bw_rows_workspace_bytes(int(m), int(k)))
+
+
+def gatv2(rowptr, col, x, y, att, heads: int = 1, negative_slope: float = 0.2, *, out=None, check: bool = True):
+    """GATv2 attention aggregation, all heads in one launch (isplib_gatv2_csr_hip): over the stored entries e = (i, j) of the CSR
+    structure and every head h, s_e = sum over the head's columns of att_c leaky_relu(x_ic + y_jc), a_e = softmax of s over the row's
+    entries, z_i[head h] = sum_e a_e y_j[head h].  Returns (z [m, heads * d], lse [m, heads]); an empty row has z_i = 0 and lse = -inf.
+    `x` [m, heads * d] and `y` [n, heads * d] float32 (row-strided views keep their pitch), `att` [heads, d] contiguous float32; `out` =
+    (z, lse) to write in place.  Every operand is checked BEFORE the call (`check`: also the two checks that read the structure on the
+    device)."""
+    if not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1 or rowptr.numel() < 1:
+        raise ValueError("isplib_amd: `rowptr` (m + 1 entries) must be a 1-D tensor")
+    m = rowptr.numel() - 1
+    ldx = _attn_dense(x, "x", m, None, "one row per row of the sparse operand")
+    k = x.size(1)
+    if not isinstance(y, torch.Tensor) or y.dim() != 2:
+        raise ValueError("isplib_amd: `y` must be a 2-D tensor [n, heads * d]")
+    n = y.size(0)
+    ldy = _attn_dense(y, "y", n, k, "one row per column of the sparse operand, x's width")
+    d = _gat_heads(heads, k)
+    _gatv2_att(att, "att", heads, d)
+    rowptr, col = _attn_structure(rowptr, col, "rowptr", "col", n, check)
+    if out is not None:
+        z, lse = out
+        ldz = _attn_dense(z, "out[0]", m, k, "z")
+        _gat_table(lse, "out[1]", m, heads)
+    _gatv2_domain(n, heads, d, (ldy,))
+    _same_gpu((("x", x), ("y", y), ("att", att), ("rowptr", rowptr), ("col", col)) +
+              ((("out[0]", out[0]), ("out[1]", out[1])) if out is not None else ()))
+    if out is None:
+        z = torch.empty((m, k), dtype=torch.float32, device=x.device)
+        lse = torch.empty((m, heads), dtype=torch.float32, device=x.device)
+        ldz = max(k, 1)
+    if m == 0 or k == 0:
+        if k == 0 and m > 0:
+            lse.fill_(float("-inf"))
+        return z, lse
+    rp = rowptr.data_ptr()
+    with torch.cuda.device(x.device):
+        st = lib().isplib_gatv2_csr_hip(m, n, k, col.numel(), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8), _ptr(x), ldx, _ptr(y),
+                                        ldy, _ptr(att), heads, float(negative_slope), _ptr(z), ldz, _ptr(lse), _stream(x.device))
+    _check(st, "isplib_gatv2_csr_hip")
+    return z, lse
+
+
+def gatv2_bw_rows(rowptr, col, x, y, att, g, z, lse, heads: int = 1, negative_slope: float = 0.2, *, want_datt: bool = True, out=None,
+                  workspace=None, check: bool = True):
+    """The backward of `gatv2` over the rows (isplib_gatv2_bw_rows_hip): for g = dL/dz [m, heads * d] and the forward's z and lse,
+    D[i,h] = <g_i, z_i>_h, ds_e = a_e (<g_i, y_j>_h - D[i,h]) with a_e recomputed from lse, dx_ic = sum_e ds_e att_c sl_ec and, with
+    `want_datt`, datt_c = sum over every edge of ds_e v_ec.  Returns (dx [m, heads * d], D [m, heads], datt [heads, d] or None); an empty
+    row has dx_i = 0 and D = 0.  `out` = (dx, D, datt or None); `workspace`: a uint8 GPU tensor of at least
+    gatv2_bw_rows_workspace_bytes(m, k) bytes (allocated when None); the operand checks are gatv2's."""
+    if not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1 or rowptr.numel() < 1:
+        raise ValueError("isplib_amd: `rowptr` (m + 1 entries) must be a 1-D tensor")
+    m = rowptr.numel() - 1
+    ldx = _attn_dense(x, "x", m, None, "one row per row of the sparse operand")
+    k = x.size(1)
+    if not isinstance(y, torch.Tensor) or y.dim() != 2:
+        raise ValueError("isplib_amd: `y` must be a 2-D tensor [n, heads * d]")
+    n = y.size(0)
+    ldy = _attn_dense(y, "y", n, k, "one row per column of the sparse operand, x's width")
+    d = _gat_heads(heads, k)
+    _gatv2_att(att, "att", heads, d)
+    ldg = _attn_dense(g, "g", m, k, "the gradient of z")
+    ldz = _attn_dense(z, "z", m, k, "the forward's output")
+    _gat_table(lse, "lse", m, heads)
+    rowptr, col = _attn_structure(rowptr, col, "rowptr", "col", n, check)
+    if out is not None:
+        if len(out) != 3:
+            raise ValueError("isplib_amd: `out` must be (dx, D, datt or None)")
+        lddx = _attn_dense(out[0], "out[0]", m, k, "dx")
+        _gat_table(out[1], "out[1]", m, heads)
+        if (out[2] is not None) != bool(want_datt):
+            raise ValueError("isplib_amd: `out[2]` (datt) must be given exactly when `want_datt`")
+        if out[2] is not None:
+            _gatv2_att(out[2], "out[2]", heads, d)
+    if workspace is not None:
+        if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.dim() != 1 or not workspace.is_contiguous():
+            raise ValueError("isplib_amd: `workspace` must be a contiguous 1-D uint8 tensor")
+    _gatv2_domain(n, heads, d, (ldy,))
+    _same_gpu((("x", x), ("y", y), ("att", att), ("g", g), ("z", z), ("lse", lse), ("rowptr", rowptr), ("col", col), ("workspace", workspace)) +
+              ((("out[0]", out[0]), ("out[1]", out[1]), ("out[2]", out[2])) if out is not None else ()))
+    if out is None:
+        out = (torch.empty((m, k), dtype=torch.float32, device=x.device), torch.empty((m, heads), dtype=torch.float32, device=x.device),
+               torch.empty((heads, d), dtype=torch.float32, device=x.device) if want_datt else None)
+        lddx = max(k, 1)
+    dx, dsum, datt = out
+    if m == 0 or k == 0:
+        if k == 0 and m > 0:
+            dsum.zero_()
+        if datt is not None:
+            datt.zero_()
+        return dx, dsum, datt
+    rp = rowptr.data_ptr()
+    with torch.cuda.device(x.device):
+        if datt is not None:
+            need = gatv2_bw_rows_workspace_bytes(m, k)
+            if workspace is None:
+                workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=x.device)
+            elif workspace.numel() < need:
+                raise ValueError(f"isplib_amd: `workspace` holds {workspace.numel()} bytes, isplib_gatv2_bw_rows_workspace_bytes asks for {need}")
+        st = lib().isplib_gatv2_bw_rows_hip(m, n, k, col.numel(), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8), _ptr(x), ldx, _ptr(y),
+                                            ldy, _ptr(att), heads, float(negative_slope), _ptr(g), ldg, _ptr(z), ldz, _ptr(lse), _ptr(dx), lddx,
+                                            _ptr(dsum), _ptr(datt), _ptr(workspace) if datt is not None else None,
+                                            workspace.numel() if datt is not None else 0, _stream(x.device))
+    _check(st, "isplib_gatv2_bw_rows_hip")
+    return dx, dsum, datt
+
+
+def gatv2_bw_cols(colptr, row_t, x, y, att, g, lse, dsum, heads: int = 1, negative_slope: float = 0.2, *, out=None, check: bool = True):
+    """The backward of `gatv2` over the columns (isplib_gatv2_bw_cols_hip), on the transposed structure (`colptr` [n + 1], `row_t`: the
+    row ids of the entries in column-major order): dy_jc = sum over the entries e = (i, j) of column j of a_e g_ic + ds_e att_c sl_ec,
+    with `lse` of the forward and `dsum` = D of gatv2_bw_rows.  Returns dy [n, heads * d]; a column no entry points at has 0.  `out` =
+    dy; the operand checks are gatv2's."""
+    if not isinstance(colptr, torch.Tensor) or colptr.dim() != 1 or colptr.numel() < 1:
+        raise ValueError("isplib_amd: `colptr` (n + 1 entries) must be a 1-D tensor")
+    n = colptr.numel() - 1
+    ldy = _attn_dense(y, "y", n, None, "one row per column of the sparse operand")
+    k = y.size(1)
+    d = _gat_heads(heads, k)
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise ValueError("isplib_amd: `x` must be a 2-D tensor [m, heads * d]")
+    m = x.size(0)
+    ldx = _attn_dense(x, "x", m, k, "one row per row of the sparse operand, y's width")
+    ldg = _attn_dense(g, "g", m, k, "the gradient of z")
+    _gatv2_att(att, "att", heads, d)
+    _gat_table(lse, "lse", m, heads)
+    _gat_table(dsum, "dsum", m, heads)
+    colptr, row_t = _attn_structure(colptr, row_t, "colptr", "row_t", m, check)
+    if out is not None:
+        lddy = _attn_dense(out, "out", n, k, "dy")
+    _gatv2_domain(m, heads, d, (ldx, ldg))
+    _same_gpu((("x", x), ("y", y), ("att", att), ("g", g), ("lse", lse), ("dsum", dsum), ("colptr", colptr), ("row_t", row_t), ("out", out)))
+    if out is None:
+        out = torch.empty((n, k), dtype=torch.float32, device=y.device)
+        lddy = max(k, 1)
+    if n == 0 or k == 0:
+        return out
+    cp = colptr.data_ptr()
+    with torch.cuda.device(y.device):
+        st = lib().isplib_gatv2_bw_cols_hip(m, n, k, row_t.numel(), _ptr(row_t), ctypes.c_void_p(cp), ctypes.c_void_p(cp + 8), _ptr(x), ldx,
+                                            _ptr(y), ldy, _ptr(att), heads, float(negative_slope), _ptr(g), ldg, _ptr(lse), _ptr(dsum),
+                                            _ptr(out), lddy, _stream(y.device))
+    _check(st, "isplib_gatv2_bw_cols_hip")
+    return out
 
 
 def _attn16_dense(t, name: str, rows: int, k: Optional[int], what: str, dtype=None) -> int:

@@ -1605,6 +1605,122 @@ Tensor gat_spmm16(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor
    return GatSpmm16::apply(rowptr, col, colptr, row_t, y, a_dst, a_src, heads, negative_slope)[0];
 }
 
+// ---- GATv2 attention aggregation, all heads in one launch (isplib_gatv2_*_hip; not an operator of the reference) ----------
+// z_i[head h] = sum_e softmax_e(sum_c att_c leaky_relu(x_ic + y_jc)) y_j[head h].  Saved for backward: the structure, x, y, att, z and lse
+// [M, H] -- nothing of length nnz.  Every shape is checked before a launch: a mis-shaped dense operand must raise, never launch.
+static AttnOperand gatv2_operand(const Tensor &src, const char *name, int64_t rows, int64_t k) {
+   check_float(src, name);
+   TORCH_CHECK(src.dim() == 2 && src.size(0) == rows && src.size(1) == k, "isplib: gatv2_spmm: `", name, "` must be [", rows, ", ", k,
+               "], got ", src.sizes());
+   const bool as_is = src.size(0) == 0 || src.size(1) == 0 || (src.stride(1) == 1 && (src.size(0) == 1 || src.stride(0) >= k));
+   const Tensor t = as_is ? src : src.contiguous();
+   return {t, t.size(0) > 1 ? t.stride(0) : std::max<int64_t>(k, 1)};
+}
+
+static Tensor gatv2_att(const Tensor &src, int64_t heads, int64_t d) {
+   check_float(src, "att");
+   TORCH_CHECK(src.dim() == 2 && src.size(0) == heads && src.size(1) == d, "isplib: gatv2_spmm: `att` must be [", heads, ", ", d,
+               "] (heads x d), got ", src.sizes());
+   return src.contiguous();
+}
+
+class Gatv2Spmm : public torch::autograd::Function<Gatv2Spmm> {
+ public:
+   static variable_list forward(AutogradContext *ctx, Variable rowptr, Variable col, Variable colptr, Variable row_t, Variable x, Variable y,
+                                Variable att, int64_t heads, double negative_slope) {
+      check_index(rowptr, "rowptr"); check_index(col, "col"); check_index(colptr, "colptr"); check_index(row_t, "row_t");
+      TORCH_CHECK(x.defined() && x.dim() == 2 && y.defined() && y.dim() == 2, "isplib: gatv2_spmm needs 2-D `x` [M, heads * d] and `y` "
+                                                                              "[N, heads * d]");
+      OpTimer timer("FUSEDMM_GATV2_FW", y);
+      const int64_t M = rowptr.numel() - 1, N = colptr.numel() - 1, K = y.size(1), nnz = col.numel();
+      TORCH_CHECK(M >= 0 && N >= 0 && row_t.numel() == nnz, "isplib: gatv2_spmm: `rowptr` / `colptr` need one entry more than rows / columns, "
+                                                             "`row_t` one entry per stored entry");
+      TORCH_CHECK(heads >= 1 && K % heads == 0, "isplib: gatv2_spmm: the width of `y` (", K, ") must be heads * d, got heads = ", heads);
+      const AttnOperand xo = gatv2_operand(x, "x", M, K), yo = gatv2_operand(y, "y", N, K);
+      TORCH_CHECK(att.defined(), "isplib: gatv2_spmm needs `att` [heads, d]");
+      const Tensor av = gatv2_att(att, heads, K / heads);
+      for (const Tensor *t : {&rowptr, &col, &colptr, &row_t, &x, &att})
+         TORCH_CHECK(t->device() == y.device(), "isplib: gatv2_spmm: every operand must be on y's device");
+      TORCH_CHECK(K == 0 || isplib_gatv2_serves(N, heads, K / heads, yo.ld), "isplib: gatv2_spmm: outside isplib_gatv2_serves (heads * d <= ",
+                  ISPLIB_GAT_K_MAX, ", heads == 1 or d a power of two >= 4, N < 2^31, N * pitch * 4 <= 3.5 GiB): N = ", N, ", heads = ", heads,
+                  ", d = ", K / heads, ", pitch = ", yo.ld);
+      c10::DeviceGuard guard(y.device());
+      const Tensor rp = rowptr.contiguous(), cl = col.contiguous();
+      Tensor z = at::empty({M, K}, y.options()), lse = at::empty({M, heads}, y.options());
+      if (M > 0 && K > 0) {
+         const int st = isplib_gatv2_csr_hip(M, N, K, nnz, cl.data_ptr<int64_t>(), rp.data_ptr<int64_t>(), rp.data_ptr<int64_t>() + 1,
+                                             xo.t.data_ptr<float>(), xo.ld, nnz > 0 ? yo.t.data_ptr<float>() : nullptr, yo.ld,
+                                             av.data_ptr<float>(), heads, (float)negative_slope, z.data_ptr<float>(), K, lse.data_ptr<float>(),
+                                             current_stream(y));
+         check_status(st, "isplib_gatv2_csr_hip");
+      } else if (M > 0) {
+         lse.fill_(-std::numeric_limits<float>::infinity());
+      }
+      ctx->saved_data["heads"] = heads;
+      ctx->saved_data["negative_slope"] = negative_slope;
+      ctx->save_for_backward({rp, cl, colptr, row_t, x, y, att, z, lse});
+      return {z};
+   }
+
+   static variable_list backward(AutogradContext *ctx, variable_list grad_outs) {
+      OpTimer timer("FUSEDMM_GATV2_BW", grad_outs[0]);
+      const bool need_x = ctx->needs_input_grad(4), need_y = ctx->needs_input_grad(5), need_att = ctx->needs_input_grad(6);
+      auto grad_x = Variable(), grad_y = Variable(), grad_att = Variable();
+      if (need_x || need_y || need_att) {
+         auto saved = ctx->get_saved_variables();
+         auto rp = saved[0], cl = saved[1], colptr = saved[2].contiguous(), row_t = saved[3].contiguous(), x = saved[4], y = saved[5], z = saved[7],
+              lse = saved[8];
+         const int64_t heads = ctx->saved_data["heads"].toInt();
+         const float ns = (float)ctx->saved_data["negative_slope"].toDouble();
+         const int64_t M = rp.numel() - 1, N = colptr.numel() - 1, K = y.size(1), nnz = cl.numel();
+         const AttnOperand xo = gatv2_operand(x, "x", M, K), yo = gatv2_operand(y, "y", N, K);
+         const Tensor av = gatv2_att(saved[6], heads, K / heads);
+         const AttnOperand go = gatv2_operand(grad_outs[0].to(at::kFloat), "grad_out", M, K);
+         c10::DeviceGuard guard(y.device());
+         // the rows kernel always runs: its D[i,h] = <g_i, z_i>_h feeds the columns kernel; its datt instantiation only when att asks; the
+         // columns kernel only when y asks
+         Tensor dx = at::empty({M, K}, y.options()), dsum = at::empty({M, heads}, y.options());
+         Tensor datt = need_att ? at::empty({heads, K / heads}, y.options()) : Tensor();
+         if (M > 0 && K > 0) {
+            const size_t ws = need_att ? isplib_gatv2_bw_rows_workspace_bytes(M, K) : 0;
+            Tensor work = need_att ? at::empty({(int64_t)ws}, y.options().dtype(at::kByte)) : Tensor();
+            const int st = isplib_gatv2_bw_rows_hip(M, N, K, nnz, cl.data_ptr<int64_t>(), rp.data_ptr<int64_t>(), rp.data_ptr<int64_t>() + 1,
+                                                    xo.t.data_ptr<float>(), xo.ld, nnz > 0 ? yo.t.data_ptr<float>() : nullptr, yo.ld,
+                                                    av.data_ptr<float>(), heads, ns, go.t.data_ptr<float>(), go.ld, z.data_ptr<float>(), K,
+                                                    lse.data_ptr<float>(), dx.data_ptr<float>(), K, dsum.data_ptr<float>(),
+                                                    need_att ? datt.data_ptr<float>() : nullptr, need_att ? work.data_ptr() : nullptr, ws,
+                                                    current_stream(y));
+            check_status(st, "isplib_gatv2_bw_rows_hip");
+         } else if (need_att) {
+            datt.zero_();
+         }
+         if (need_x) grad_x = dx;
+         if (need_att) grad_att = datt;
+         if (need_y) {
+            TORCH_CHECK(K == 0 || (isplib_gatv2_serves(M, heads, K / heads, xo.ld) && isplib_gatv2_serves(M, heads, K / heads, go.ld)),
+                        "isplib: gatv2_spmm backward: outside isplib_gatv2_serves for the gathered rows of x and of the gradient: M = ", M,
+                        ", K = ", K);
+            Tensor dy = at::empty({N, K}, y.options());
+            if (N > 0 && K > 0) {
+               const int st = isplib_gatv2_bw_cols_hip(M, N, K, nnz, row_t.data_ptr<int64_t>(), colptr.data_ptr<int64_t>(),
+                                                       colptr.data_ptr<int64_t>() + 1, nnz > 0 ? xo.t.data_ptr<float>() : nullptr, xo.ld,
+                                                       yo.t.data_ptr<float>(), yo.ld, av.data_ptr<float>(), heads, ns,
+                                                       nnz > 0 ? go.t.data_ptr<float>() : nullptr, go.ld, lse.data_ptr<float>(),
+                                                       dsum.data_ptr<float>(), dy.data_ptr<float>(), K, current_stream(y));
+               check_status(st, "isplib_gatv2_bw_cols_hip");
+            }
+            grad_y = dy;
+         }
+      }
+      return {Variable(), Variable(), Variable(), Variable(), grad_x, grad_y, grad_att, Variable(), Variable()};
+   }
+};
+
+Tensor gatv2_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor x, Tensor y, Tensor att, int64_t heads,
+                  double negative_slope) {
+   return Gatv2Spmm::apply(rowptr, col, colptr, row_t, x, y, att, heads, negative_slope)[0];
+}
+
 // introspection / housekeeping of the per-graph handle cache of the reference-schema operators
 int64_t graph_cache_size() {
    std::lock_guard<std::mutex> lock(g_graph_mutex);
@@ -1659,4 +1775,6 @@ TORCH_LIBRARY(isplib, m) {
    m.def("attention_spmm16(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor x, Tensor y, float scale) -> Tensor", &attention_spmm16);
    m.def("gat_spmm16(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor y, Tensor a_dst, Tensor a_src, int heads, float negative_slope) -> Tensor",
          &gat_spmm16);
+   m.def("gatv2_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor x, Tensor y, Tensor att, int heads, float negative_slope) -> Tensor",
+         &gatv2_spmm);
 }

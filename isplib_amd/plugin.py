@@ -766,6 +766,64 @@ def gat_matmul(src, y: torch.Tensor, a_dst: torch.Tensor, a_src: torch.Tensor, h
     return torch.ops.isplib.gat_spmm(st._rowptr, st._col, st.colptr(), st.row_t(), y, a_dst, a_src, heads, float(negative_slope))
 
 
+def gatv2_matmul(src, x: torch.Tensor, att: torch.Tensor, y: Optional[torch.Tensor] = None, heads: int = 1,
+                 negative_slope: float = 0.2) -> torch.Tensor:
+    """GATv2 attention aggregation over the stored entries of `src`, all heads in one launch (include/isplib_hip.h,
+    isplib_gatv2_csr_hip): ``z[i, head h] = sum_j softmax_j(sum_c att[h, c] leaky_relu(x[i, c] + y[j, c])) y[j, head h]`` over the
+    entries (i, j) of row i, c over the columns of head h -- the aggregation of GATv2Conv, with its autograd backward in `x`, `y` and
+    `att` (torch.ops.isplib.gatv2_spmm).  `x` [M, heads * d] is the target side (PyG's ``lin_r(x)``), `y` [N, heads * d] the source
+    side (``lin_l(x)``: gathered, and what is aggregated), head h in the columns [h*d, (h+1)*d); `att` is [heads, d], or [d] / [K] with
+    one head.  ``y=None`` means ``y = x`` (``share_weights=True``) and needs a square `src`; the one tensor's gradient then receives
+    both parts.  The stored values of `src` are not read; an empty row gives 0.  The backward keeps x, y, att, z and one scalar per row
+    and head -- nothing per edge.  fp32 only (bf16 / fp16 operands raise TypeError); there is no fallback route: outside
+    isplib_gatv2_serves (= isplib_gat_serves: heads * d <= 512; heads == 1 or d a power of two >= 4) the call raises ValueError."""
+    from . import cabi
+    shared = y is None
+    if shared:
+        y = x
+    for name, t in (("x", x), ("y", y), ("att", att)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"isplib_amd: `{name}` must be a tensor, got {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"isplib_amd: `{name}` must be float32, got {t.dtype} (the GATv2 operator is fp32 only)")
+    if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
+        raise ValueError(f"isplib_amd: `heads` must be a positive int, got {heads!r}")
+    if x.dim() != 2 or y.dim() != 2:
+        raise ValueError(f"isplib_amd: `x` and `y` must be 2-D [rows, heads * d], got shapes {tuple(x.shape)} and {tuple(y.shape)}")
+    st = _storage_of(src, y)
+    m_rows, n_cols = st._rowptr.numel() - 1, st._sparse_sizes[1]
+    if shared and m_rows != n_cols:
+        raise ValueError(f"isplib_amd: `y=None` (y = x) needs a square sparse matrix, got {m_rows} x {n_cols}")
+    if x.size(0) != m_rows:
+        raise ValueError(f"isplib_amd: `x` must have one row per row of the sparse matrix ({m_rows}), got {x.size(0)}")
+    if y.size(0) != n_cols:
+        raise ValueError(f"isplib_amd: `y` must have one row per column of the sparse matrix ({n_cols}), got {y.size(0)}")
+    k = y.size(1)
+    if x.size(1) != k:
+        raise ValueError(f"isplib_amd: `x` and `y` must have the same width, got {x.size(1)} and {k}")
+    if k % heads:
+        raise ValueError(f"isplib_amd: the width of `y` ({k}) must be heads * d, got heads = {heads}")
+    d = k // heads
+    if heads == 1 and att.dim() == 1:
+        att = att.unsqueeze(0)
+    if att.dim() != 2 or att.size(0) != heads or att.size(1) != d:
+        raise ValueError(f"isplib_amd: `att` must be [{heads}, {d}] (heads x d; [d] with one head), got shape {tuple(att.shape)}")
+    if not (1 <= k <= cabi.GAT_K_MAX) or (heads > 1 and (d < 4 or d & (d - 1))):
+        raise ValueError(f"isplib_amd: gatv2_matmul serves 1 <= heads * d <= {cabi.GAT_K_MAX} with heads == 1 or d a power of two >= 4 (a "
+                         f"head is an aligned group of lanes), got heads = {heads}, d = {d}")
+    pitch_y = y.stride(0) if n_cols > 1 and y.stride(1) == 1 and y.stride(0) >= k else k
+    pitch_x = x.stride(0) if m_rows > 1 and x.stride(1) == 1 and x.stride(0) >= k else k
+    for rows, ld, what in ((n_cols, pitch_y, "`y`"), (m_rows, pitch_x, "`x`"), (m_rows, k, "the gradient of the result")):
+        if not cabi.gatv2_serves(rows, heads, d, ld):              # y: forward, rows; x and g: the columns kernel
+            raise ValueError(f"isplib_amd: {what} ({rows} rows at a pitch of {ld} floats) is outside the GATv2 kernels' domain: "
+                             f"rows < 2^31 and rows * pitch * 4 <= {cabi.DENSE_BYTES_MAX} bytes (3.5 GiB, one buffer descriptor)")
+    if not x.is_cuda or not y.is_cuda or not att.is_cuda:
+        raise TypeError("isplib_amd: `x`, `y` and `att` must be GPU tensors -- there is no CPU path")
+    if x.device != y.device or att.device != y.device or st._rowptr.device != y.device:
+        raise ValueError("isplib_amd: `x`, `y`, `att` and the sparse matrix must be on one device")
+    return torch.ops.isplib.gatv2_spmm(st._rowptr, st._col, st.colptr(), st.row_t(), x, y, att, heads, float(negative_slope))
+
+
 def _gat_matmul16(src, y, a_dst, a_src, heads, negative_slope):
     """gat_matmul for a bf16 / fp16 `y` under ISPLIB_HALF_GAT: the 16-bit operator where gat16_route admits BOTH gathered operands (y by
     the forward and the rows kernel, the gradient -- M rows, packed -- by the columns kernel), else the conversion route."""

@@ -347,3 +347,9 @@ class SparseTensor:
         is opt-in through ISPLIB_HALF_GAT."""
         from .plugin import gat_matmul
         return gat_matmul(self, y, a_dst, a_src, heads, negative_slope)
+
+    def gatv2_matmul(self, x: torch.Tensor, att: torch.Tensor, y: Optional[torch.Tensor] = None, heads: int = 1,
+                     negative_slope: float = 0.2) -> torch.Tensor:
+        """GATv2 attention aggregation over this matrix's stored entries, all heads in one launch (plugin.gatv2_matmul)."""
+        from .plugin import gatv2_matmul
+        return gatv2_matmul(self, x, att, y, heads, negative_slope)
