@@ -1267,4 +1267,8 @@ void isplib_graph_destroy(isplib_graph *g);
 #ifdef __cplusplus
 }
 #endif
+
+/* the GATv2 aggregation for bf16 / fp16 operands (isplib_gatv2_16_*): part of this interface, declared in a file of its own */
+#include "isplib_hip_gatv2_16.h"
+
 #endif /* ISPLIB_HIP_H */

@@ -187,6 +187,20 @@ def gat16_native_pays(rows_gathered: int, ld: int) -> bool:
     return bool(rows_gathered > 0 and ld > 0)
 
 
+def gatv2_16_serves(rows_gathered: int, heads: int, d: int, ld: int) -> bool:
+    """isplib_gatv2_16_serves of the header: the 16-bit GATv2 entries' domain IS isplib_gat16_serves -- stated once.  It is asked of
+    every gathered wide operand: y with its rows (forward, rows kernel), x and the gradient with theirs (columns kernel)."""
+    return gat16_serves(rows_gathered, heads, d, ld)
+
+
+def gatv2_16_native_pays(rows_gathered: int, ld: int) -> bool:
+    """isplib_gatv2_16_native_pays of the header: the classes of calls (the gathered operand beyond 256 MiB at 2 bytes per element or
+    not) in which every native run of the 16-bit GATv2 operator (forward + backward) measured faster than every run of the conversion
+    route (profiles/gatv2_16_ab.txt: both classes do -- the Reddit shape at (H, d) = (8, 8) / (8, 16) inside 256 MiB, 0.715-0.754 of the
+    conversion route's time; the ogbn-products shape at (8, 16) beyond it, 0.825); tests/test_gatv2_16_host.py compares the two."""
+    return bool(rows_gathered > 0 and ld > 0)
+
+
 def owner_exchange_serves(m: int, k: int, world: int, cuts) -> bool:
     """isplib_owner_exchange_serves of the header: m x k winners split for `world` owners at the row boundaries `cuts`."""
     if not 1 <= world <= OWNER_WORLD_MAX or m < 0 or k < 0 or m * k >= MINMAX_BW_PAIRS_END:
@@ -243,6 +257,13 @@ EXPORTS = (
     "isplib_gat16_csr_hip", "isplib_gat16_bw_rows_hip", "isplib_gat16_bw_cols_hip", "isplib_gat16_domain", "isplib_gat16_auto",
     "isplib_gatv2_csr_hip", "isplib_gatv2_bw_rows_hip", "isplib_gatv2_bw_rows_workspace_bytes", "isplib_gatv2_bw_cols_hip",
     "isplib_gatv2_domain",
+)
+
+# include/isplib_hip_gatv2_16.h (which isplib_hip.h includes; the same library): the 16-bit GATv2 entries, listed apart because EXPORTS
+# is what isplib_hip.h itself declares; tests/test_gatv2_16_host.py compares this list with that header and the library's symbols
+GATV2_16_EXPORTS = (
+    "isplib_gatv2_16_csr_hip", "isplib_gatv2_16_bw_rows_hip", "isplib_gatv2_16_bw_rows_workspace_bytes", "isplib_gatv2_16_bw_cols_hip",
+    "isplib_gatv2_16_domain", "isplib_gatv2_16_auto",
 )
 
 # include/isplib_hip_experimental.h (libisplib_hip_exp.so): forms measured slower than the defaults; tests and experiment scripts only
@@ -516,6 +537,21 @@ def lib() -> ctypes.CDLL:
         L.isplib_gatv2_bw_cols_hip.restype = ctypes.c_int
         L.isplib_gatv2_bw_cols_hip.argtypes = [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _vp,
                                                _vp, _i64, _vp]
+        L.isplib_gatv2_16_domain.restype = ctypes.c_int
+        L.isplib_gatv2_16_domain.argtypes = [_i64, _i64, _i64, _i64]
+        L.isplib_gatv2_16_auto.restype = ctypes.c_int
+        L.isplib_gatv2_16_auto.argtypes = [_i64, _i64]
+        L.isplib_gatv2_16_bw_rows_workspace_bytes.restype = ctypes.c_size_t
+        L.isplib_gatv2_16_bw_rows_workspace_bytes.argtypes = [_i64, _i64]
+        L.isplib_gatv2_16_csr_hip.restype = ctypes.c_int
+        L.isplib_gatv2_16_csr_hip.argtypes = [ctypes.c_int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _f32, _vp,
+                                              _i64, _vp, _vp]
+        L.isplib_gatv2_16_bw_rows_hip.restype = ctypes.c_int
+        L.isplib_gatv2_16_bw_rows_hip.argtypes = [ctypes.c_int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _f32,
+                                                  _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, ctypes.c_size_t, _vp]
+        L.isplib_gatv2_16_bw_cols_hip.restype = ctypes.c_int
+        L.isplib_gatv2_16_bw_cols_hip.argtypes = [ctypes.c_int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _f32,
+                                                  _vp, _i64, _vp, _vp, _vp, _i64, _vp]
         L.isplib_gat16_domain.restype = ctypes.c_int
         L.isplib_gat16_domain.argtypes = [_i64, _i64, _i64, _i64]
         L.isplib_gat16_auto.restype = ctypes.c_int
@@ -2444,6 +2480,161 @@ def gat16_backward_cols(colptr, row_t, y, a_dst, a_src, g, lse, dsum, heads: int
                                             _ptr(g), ldg, _ptr(lse), _ptr(dsum), _ptr(dy), lddy, _ptr(dasrc), _stream(y.device))
     _check(st, "isplib_gat16_bw_cols_hip")
     return dy, dasrc
+
+
+def _gatv2_16_domain(rows_gathered: int, heads: int, d: int, lds) -> None:
+    for ld in lds:
+        if d > 0 and not gatv2_16_serves(rows_gathered, heads, d, ld):
+            raise ValueError(f"isplib_amd: outside the 16-bit GATv2 entries' domain (isplib_gatv2_16_serves = isplib_gat16_serves: "
+                             f"{GAT16_K_MIN} <= heads * d <= {GAT16_K_MAX}, heads == 1 with d even or d a power of two >= 8, the pitch even, "
+                             f"gathered rows < 2^31, rows * pitch * 2 <= 3.5 GiB), got rows={rows_gathered}, heads={heads}, d={d}, pitch={ld}")
+
+
+def gatv2_16_bw_rows_workspace_bytes(m: int, k: int) -> int:
+    """isplib_gatv2_16_bw_rows_workspace_bytes: what `gatv2_16_backward_rows` needs behind `workspace` when `datt` is asked for."""
+    return int(lib().isplib_gatv2_16_bw_rows_workspace_bytes(int(m), int(k)))
+
+
+def gatv2_16_forward(rowptr, col, x, y, att, heads: int = 1, negative_slope: float = 0.2, *, out=None, check: bool = True):
+    """`gatv2` for bf16 / fp16 `x` and `y` of one dtype (isplib_gatv2_16_csr_hip): x [m, heads * d] and y [n, heads * d] go in as they
+    lie, att [heads, d] is contiguous float32 as in `gatv2`, every sum, product and exponential is fp32, z is rounded once to the
+    operands' dtype.  Returns (z [m, heads * d] 16-bit, lse [m, heads] fp32); `out` = (z, lse).  The operand checks are gatv2's, with
+    the 16-bit family's (even pitches, 4-byte aligned bases)."""
+    if not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1 or rowptr.numel() < 1:
+        raise ValueError("isplib_amd: `rowptr` (m + 1 entries) must be a 1-D tensor")
+    m = rowptr.numel() - 1
+    ldx = _attn16_dense(x, "x", m, None, "one row per row of the sparse operand")
+    k = x.size(1)
+    if not isinstance(y, torch.Tensor) or y.dim() != 2:
+        raise ValueError("isplib_amd: `y` must be a 2-D tensor [n, heads * d]")
+    n = y.size(0)
+    ldy = _attn16_dense(y, "y", n, k, "one row per column of the sparse operand, x's width", x.dtype)
+    d = _gat_heads(heads, k)
+    _gatv2_att(att, "att", heads, d)
+    rowptr, col = _attn_structure(rowptr, col, "rowptr", "col", n, check)
+    if out is not None:
+        z, lse = out
+        ldz = _attn16_dense(z, "out[0]", m, k, "z", x.dtype)
+        _gat_table(lse, "out[1]", m, heads)
+    _gatv2_16_domain(n, heads, d, (ldy,))
+    _same_gpu((("x", x), ("y", y), ("att", att), ("rowptr", rowptr), ("col", col)) +
+              ((("out[0]", out[0]), ("out[1]", out[1])) if out is not None else ()))
+    if out is None:
+        z = torch.empty((m, k), dtype=x.dtype, device=x.device)
+        lse = torch.empty((m, heads), dtype=torch.float32, device=x.device)
+        ldz = max(k, 1)
+    if m == 0 or k == 0:
+        if k == 0 and m > 0:
+            lse.fill_(float("-inf"))
+        return z, lse
+    rp = rowptr.data_ptr()
+    with torch.cuda.device(x.device):
+        st = lib().isplib_gatv2_16_csr_hip(HALF_DTYPES[x.dtype], m, n, k, col.numel(), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8),
+                                           _ptr(x), ldx, _ptr(y), ldy, _ptr(att), heads, float(negative_slope), _ptr(z), ldz, _ptr(lse),
+                                           _stream(x.device))
+    _check(st, "isplib_gatv2_16_csr_hip")
+    return z, lse
+
+
+def gatv2_16_backward_rows(rowptr, col, x, y, att, g, lse, heads: int = 1, negative_slope: float = 0.2, *, want_datt: bool = True, out=None,
+                           workspace=None, check: bool = True):
+    """The backward of `gatv2_16_forward` over the rows (isplib_gatv2_16_bw_rows_hip): for g = dL/dz [m, heads * d] (x's dtype) and the
+    forward's lse -- z is NOT read: D[i,h] = sum_e a_e <g_i, y_j>_h is formed in fp32 from the row's edges, in the same pass as
+    dx_ic = att_c (P_c - D Q_c) and, with `want_datt`, the row's part R_c - D S_c of datt_c.  Returns (dx [m, heads * d] 16-bit,
+    D [m, heads] fp32, datt [heads, d] fp32 or None); an empty row has dx_i = 0 and D = 0.  `out` = (dx, D, datt or None);
+    `workspace`: a uint8 GPU tensor of at least gatv2_16_bw_rows_workspace_bytes(m, k) bytes (allocated when None)."""
+    if not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1 or rowptr.numel() < 1:
+        raise ValueError("isplib_amd: `rowptr` (m + 1 entries) must be a 1-D tensor")
+    m = rowptr.numel() - 1
+    ldx = _attn16_dense(x, "x", m, None, "one row per row of the sparse operand")
+    k = x.size(1)
+    if not isinstance(y, torch.Tensor) or y.dim() != 2:
+        raise ValueError("isplib_amd: `y` must be a 2-D tensor [n, heads * d]")
+    n = y.size(0)
+    ldy = _attn16_dense(y, "y", n, k, "one row per column of the sparse operand, x's width", x.dtype)
+    d = _gat_heads(heads, k)
+    _gatv2_att(att, "att", heads, d)
+    ldg = _attn16_dense(g, "g", m, k, "the gradient of z", x.dtype)
+    _gat_table(lse, "lse", m, heads)
+    rowptr, col = _attn_structure(rowptr, col, "rowptr", "col", n, check)
+    if out is not None:
+        if len(out) != 3:
+            raise ValueError("isplib_amd: `out` must be (dx, D, datt or None)")
+        lddx = _attn16_dense(out[0], "out[0]", m, k, "dx", x.dtype)
+        _gat_table(out[1], "out[1]", m, heads)
+        if (out[2] is not None) != bool(want_datt):
+            raise ValueError("isplib_amd: `out[2]` (datt) must be given exactly when `want_datt`")
+        if out[2] is not None:
+            _gatv2_att(out[2], "out[2]", heads, d)
+    if workspace is not None:
+        if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.dim() != 1 or not workspace.is_contiguous():
+            raise ValueError("isplib_amd: `workspace` must be a contiguous 1-D uint8 tensor")
+    _gatv2_16_domain(n, heads, d, (ldy,))
+    _same_gpu((("x", x), ("y", y), ("att", att), ("g", g), ("lse", lse), ("rowptr", rowptr), ("col", col), ("workspace", workspace)) +
+              ((("out[0]", out[0]), ("out[1]", out[1]), ("out[2]", out[2])) if out is not None else ()))
+    if out is None:
+        out = (torch.empty((m, k), dtype=x.dtype, device=x.device), torch.empty((m, heads), dtype=torch.float32, device=x.device),
+               torch.empty((heads, d), dtype=torch.float32, device=x.device) if want_datt else None)
+        lddx = max(k, 1)
+    dx, dsum, datt = out
+    if m == 0 or k == 0:
+        if k == 0 and m > 0:
+            dsum.zero_()
+        if datt is not None:
+            datt.zero_()
+        return dx, dsum, datt
+    rp = rowptr.data_ptr()
+    with torch.cuda.device(x.device):
+        if datt is not None:
+            need = gatv2_16_bw_rows_workspace_bytes(m, k)
+            if workspace is None:
+                workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=x.device)
+            elif workspace.numel() < need:
+                raise ValueError(f"isplib_amd: `workspace` holds {workspace.numel()} bytes, isplib_gatv2_16_bw_rows_workspace_bytes asks for {need}")
+        st = lib().isplib_gatv2_16_bw_rows_hip(HALF_DTYPES[x.dtype], m, n, k, col.numel(), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8),
+                                               _ptr(x), ldx, _ptr(y), ldy, _ptr(att), heads, float(negative_slope), _ptr(g), ldg, _ptr(lse),
+                                               _ptr(dx), lddx, _ptr(dsum), _ptr(datt), _ptr(workspace) if datt is not None else None,
+                                               workspace.numel() if datt is not None else 0, _stream(x.device))
+    _check(st, "isplib_gatv2_16_bw_rows_hip")
+    return dx, dsum, datt
+
+
+def gatv2_16_backward_cols(colptr, row_t, x, y, att, g, lse, dsum, heads: int = 1, negative_slope: float = 0.2, *, out=None,
+                           check: bool = True):
+    """The backward of `gatv2_16_forward` over the columns (isplib_gatv2_16_bw_cols_hip), on the transposed structure: dy_jc = sum over
+    the entries e = (i, j) of column j of a_e g_ic + ds_e att_c sl_ec, rounded once to the operands' dtype, with `lse` of the forward
+    and `dsum` = D of gatv2_16_backward_rows.  Returns dy [n, heads * d] 16-bit; a column no entry points at has 0.  `out` = dy."""
+    if not isinstance(colptr, torch.Tensor) or colptr.dim() != 1 or colptr.numel() < 1:
+        raise ValueError("isplib_amd: `colptr` (n + 1 entries) must be a 1-D tensor")
+    n = colptr.numel() - 1
+    ldy = _attn16_dense(y, "y", n, None, "one row per column of the sparse operand")
+    k = y.size(1)
+    d = _gat_heads(heads, k)
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise ValueError("isplib_amd: `x` must be a 2-D tensor [m, heads * d]")
+    m = x.size(0)
+    ldx = _attn16_dense(x, "x", m, k, "one row per row of the sparse operand, y's width", y.dtype)
+    ldg = _attn16_dense(g, "g", m, k, "the gradient of z", y.dtype)
+    _gatv2_att(att, "att", heads, d)
+    _gat_table(lse, "lse", m, heads)
+    _gat_table(dsum, "dsum", m, heads)
+    colptr, row_t = _attn_structure(colptr, row_t, "colptr", "row_t", m, check)
+    if out is not None:
+        lddy = _attn16_dense(out, "out", n, k, "dy", y.dtype)
+    _gatv2_16_domain(m, heads, d, (ldx, ldg))
+    _same_gpu((("x", x), ("y", y), ("att", att), ("g", g), ("lse", lse), ("dsum", dsum), ("colptr", colptr), ("row_t", row_t), ("out", out)))
+    if out is None:
+        out = torch.empty((n, k), dtype=y.dtype, device=y.device)
+        lddy = max(k, 1)
+    if n == 0 or k == 0:
+        return out
+    cp = colptr.data_ptr()
+    with torch.cuda.device(y.device):
+        st = lib().isplib_gatv2_16_bw_cols_hip(HALF_DTYPES[y.dtype], m, n, k, row_t.numel(), _ptr(row_t), ctypes.c_void_p(cp),
+                                               ctypes.c_void_p(cp + 8), _ptr(x), ldx, _ptr(y), ldy, _ptr(att), heads, float(negative_slope),
+                                               _ptr(g), ldg, _ptr(lse), _ptr(dsum), _ptr(out), lddy, _stream(y.device))
+    _check(st, "isplib_gatv2_16_bw_cols_hip")
+    return out
 
 
 def fusedMM_csr_rows16_minmax_hip(imessage: int, rowptr, col, val, order, y, z, z_arg=None, check: bool = True, dtype=None, k=None, ldy=None,

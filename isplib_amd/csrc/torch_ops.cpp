@@ -1721,6 +1721,131 @@ Tensor gatv2_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor
    return Gatv2Spmm::apply(rowptr, col, colptr, row_t, x, y, att, heads, negative_slope)[0];
 }
 
+// ---- the GATv2 aggregation for bf16 / fp16 `x` and `y` (isplib_gatv2_16_*_hip) ----------
+// x and y go in as they lie, z, dx and dy come back in their dtype; att, lse, D and datt stay fp32: no fp32 [*, K] tensor in either
+// direction.  Saved for backward: the structure, x, y, att and lse -- NOT z: the rows kernel forms D[i,h] from the row's edges.  A wide
+// operand is copied only without unit inner stride, or where the domain admits it packed but not at its pitch or alignment.
+static AttnOperand gatv2_16_operand(const Tensor &src, const char *name, int64_t rows, int64_t k, int64_t heads, at::ScalarType dtype) {
+   TORCH_CHECK(src.defined() && src.scalar_type() == dtype, "isplib: gatv2_spmm16: `", name, "` must be ", dtype, ", got ",
+               src.defined() ? src.scalar_type() : at::ScalarType::Undefined);
+   TORCH_CHECK(src.is_cuda(), "isplib: gatv2_spmm16: `", name, "` must be a GPU tensor -- there is no CPU path");
+   TORCH_CHECK(src.dim() == 2 && src.size(0) == rows && src.size(1) == k, "isplib: gatv2_spmm16: `", name, "` must be [", rows, ", ", k,
+               "], got ", src.sizes());
+   if (rows == 0 || k == 0) return {src, std::max<int64_t>(k, 1)};
+   const int64_t ld = rows > 1 ? src.stride(0) : k;
+   const bool as_is = src.stride(1) == 1 && ld >= k && ((uintptr_t)src.data_ptr() & 3) == 0 && isplib_gatv2_16_serves(rows, heads, k / heads, ld);
+   if (as_is) return {src, ld};
+   return {src.clone(at::MemoryFormat::Contiguous), k};
+}
+
+static Tensor gatv2_16_att(const Tensor &src, int64_t heads, int64_t d) {
+   TORCH_CHECK(src.defined() && src.scalar_type() == at::kFloat, "isplib: gatv2_spmm16: `att` must be float32 (att stays fp32), got ",
+               src.defined() ? src.scalar_type() : at::ScalarType::Undefined);
+   TORCH_CHECK(src.is_cuda(), "isplib: gatv2_spmm16: `att` must be a GPU tensor -- there is no CPU path");
+   TORCH_CHECK(src.dim() == 2 && src.size(0) == heads && src.size(1) == d, "isplib: gatv2_spmm16: `att` must be [", heads, ", ", d,
+               "] (heads x d), got ", src.sizes());
+   return src.contiguous();
+}
+
+class Gatv2Spmm16 : public torch::autograd::Function<Gatv2Spmm16> {
+ public:
+   static variable_list forward(AutogradContext *ctx, Variable rowptr, Variable col, Variable colptr, Variable row_t, Variable x, Variable y,
+                                Variable att, int64_t heads, double negative_slope) {
+      check_index(rowptr, "rowptr"); check_index(col, "col"); check_index(colptr, "colptr"); check_index(row_t, "row_t");
+      TORCH_CHECK(x.defined() && x.dim() == 2 && y.defined() && y.dim() == 2, "isplib: gatv2_spmm16 needs 2-D `x` [M, heads * d] and `y` "
+                                                                              "[N, heads * d]");
+      TORCH_CHECK(is_half(y), "isplib: gatv2_spmm16: `y` must be bfloat16 or float16, got ", y.scalar_type(), " (float32: gatv2_spmm)");
+      OpTimer timer("FUSEDMM_GATV2_FW", y);
+      const int64_t M = rowptr.numel() - 1, N = colptr.numel() - 1, K = y.size(1), nnz = col.numel();
+      TORCH_CHECK(M >= 0 && N >= 0 && row_t.numel() == nnz, "isplib: gatv2_spmm16: `rowptr` / `colptr` need one entry more than rows / "
+                                                             "columns, `row_t` one entry per stored entry");
+      TORCH_CHECK(heads >= 1 && K % heads == 0, "isplib: gatv2_spmm16: the width of `y` (", K, ") must be heads * d, got heads = ", heads);
+      const at::ScalarType dt = y.scalar_type();
+      const AttnOperand yo = gatv2_16_operand(y, "y", N, K, heads, dt), xo = gatv2_16_operand(x, "x", M, K, heads, dt);
+      TORCH_CHECK(att.defined(), "isplib: gatv2_spmm16 needs `att` [heads, d]");
+      const Tensor av = gatv2_16_att(att, heads, K / heads);
+      for (const Tensor *t : {&rowptr, &col, &colptr, &row_t, &x, &att})
+         TORCH_CHECK(t->device() == y.device(), "isplib: gatv2_spmm16: every operand must be on y's device");
+      TORCH_CHECK(K == 0 || isplib_gatv2_16_serves(N, heads, K / heads, yo.ld), "isplib: gatv2_spmm16: outside isplib_gatv2_16_serves (",
+                  ISPLIB_GAT16_K_MIN, " <= heads * d <= ", ISPLIB_GAT16_K_MAX, ", heads == 1 with d even or d a power of two >= 8, N < 2^31, "
+                  "N * pitch * 2 <= 3.5 GiB): N = ", N, ", heads = ", heads, ", d = ", K / heads, ", pitch = ", yo.ld);
+      c10::DeviceGuard guard(y.device());
+      const int code = dt == at::kBFloat16 ? ISPLIB_DTYPE_BF16 : ISPLIB_DTYPE_F16;
+      const Tensor rp = rowptr.contiguous(), cl = col.contiguous();
+      Tensor z = at::empty({M, K}, y.options()), lse = at::empty({M, heads}, y.options().dtype(at::kFloat));
+      if (M > 0 && K > 0) {
+         const int st = isplib_gatv2_16_csr_hip(code, M, N, K, nnz, cl.data_ptr<int64_t>(), rp.data_ptr<int64_t>(), rp.data_ptr<int64_t>() + 1,
+                                                xo.t.data_ptr(), xo.ld, nnz > 0 ? yo.t.data_ptr() : nullptr, yo.ld, av.data_ptr<float>(), heads,
+                                                (float)negative_slope, z.data_ptr(), K, lse.data_ptr<float>(), current_stream(y));
+         check_status(st, "isplib_gatv2_16_csr_hip");
+      } else if (M > 0) {
+         lse.fill_(-std::numeric_limits<float>::infinity());
+      }
+      ctx->saved_data["heads"] = heads;
+      ctx->saved_data["negative_slope"] = negative_slope;
+      ctx->save_for_backward({rp, cl, colptr, row_t, x, y, att, lse});
+      return {z};
+   }
+
+   static variable_list backward(AutogradContext *ctx, variable_list grad_outs) {
+      OpTimer timer("FUSEDMM_GATV2_BW", grad_outs[0]);
+      const bool need_x = ctx->needs_input_grad(4), need_y = ctx->needs_input_grad(5), need_att = ctx->needs_input_grad(6);
+      auto grad_x = Variable(), grad_y = Variable(), grad_att = Variable();
+      if (need_x || need_y || need_att) {
+         auto saved = ctx->get_saved_variables();
+         auto rp = saved[0], cl = saved[1], colptr = saved[2].contiguous(), row_t = saved[3].contiguous(), x = saved[4], y = saved[5], lse = saved[7];
+         const int64_t heads = ctx->saved_data["heads"].toInt();
+         const float ns = (float)ctx->saved_data["negative_slope"].toDouble();
+         const int64_t M = rp.numel() - 1, N = colptr.numel() - 1, K = y.size(1), nnz = cl.numel();
+         const at::ScalarType dt = y.scalar_type();
+         const AttnOperand yo = gatv2_16_operand(y, "y", N, K, heads, dt), xo = gatv2_16_operand(x, "x", M, K, heads, dt);
+         const Tensor av = gatv2_16_att(saved[6], heads, K / heads);
+         const AttnOperand go = gatv2_16_operand(grad_outs[0].to(dt), "grad_out", M, K, heads, dt);   // a grad of another dtype is cast to y's
+         c10::DeviceGuard guard(y.device());
+         const int code = dt == at::kBFloat16 ? ISPLIB_DTYPE_BF16 : ISPLIB_DTYPE_F16;
+         const auto f32 = y.options().dtype(at::kFloat);
+         // the rows kernel always runs: its D[i,h] feeds the columns kernel; its datt instantiation and workspace only when att asks; the
+         // columns kernel only when y asks
+         Tensor dx = at::empty({M, K}, y.options()), dsum = at::empty({M, heads}, f32);
+         Tensor datt = need_att ? at::empty({heads, K / heads}, f32) : Tensor();
+         if (M > 0 && K > 0) {
+            const size_t ws = need_att ? isplib_gatv2_16_bw_rows_workspace_bytes(M, K) : 0;
+            Tensor work = need_att ? at::empty({(int64_t)ws}, y.options().dtype(at::kByte)) : Tensor();
+            const int st = isplib_gatv2_16_bw_rows_hip(code, M, N, K, nnz, cl.data_ptr<int64_t>(), rp.data_ptr<int64_t>(),
+                                                       rp.data_ptr<int64_t>() + 1, xo.t.data_ptr(), xo.ld, nnz > 0 ? yo.t.data_ptr() : nullptr, yo.ld,
+                                                       av.data_ptr<float>(), heads, ns, go.t.data_ptr(), go.ld, lse.data_ptr<float>(), dx.data_ptr(), K,
+                                                       dsum.data_ptr<float>(), need_att ? datt.data_ptr<float>() : nullptr,
+                                                       need_att ? work.data_ptr() : nullptr, ws, current_stream(y));
+            check_status(st, "isplib_gatv2_16_bw_rows_hip");
+         } else if (need_att) {
+            datt.zero_();
+         }
+         if (need_x) grad_x = dx;
+         if (need_att) grad_att = datt;
+         if (need_y) {
+            TORCH_CHECK(K == 0 || (isplib_gatv2_16_serves(M, heads, K / heads, xo.ld) && isplib_gatv2_16_serves(M, heads, K / heads, go.ld)),
+                        "isplib: gatv2_spmm16 backward: outside isplib_gatv2_16_serves for the gathered rows of x and of the gradient: M = ", M,
+                        ", K = ", K);
+            Tensor dy = at::empty({N, K}, y.options());
+            if (N > 0 && K > 0) {
+               const int st = isplib_gatv2_16_bw_cols_hip(code, M, N, K, nnz, row_t.data_ptr<int64_t>(), colptr.data_ptr<int64_t>(),
+                                                          colptr.data_ptr<int64_t>() + 1, nnz > 0 ? xo.t.data_ptr() : nullptr, xo.ld, yo.t.data_ptr(),
+                                                          yo.ld, av.data_ptr<float>(), heads, ns, nnz > 0 ? go.t.data_ptr() : nullptr, go.ld,
+                                                          lse.data_ptr<float>(), dsum.data_ptr<float>(), dy.data_ptr(), K, current_stream(y));
+               check_status(st, "isplib_gatv2_16_bw_cols_hip");
+            }
+            grad_y = dy;
+         }
+      }
+      return {Variable(), Variable(), Variable(), Variable(), grad_x, grad_y, grad_att, Variable(), Variable()};
+   }
+};
+
+Tensor gatv2_spmm16(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor x, Tensor y, Tensor att, int64_t heads,
+                    double negative_slope) {
+   return Gatv2Spmm16::apply(rowptr, col, colptr, row_t, x, y, att, heads, negative_slope)[0];
+}
+
 // introspection / housekeeping of the per-graph handle cache of the reference-schema operators
 int64_t graph_cache_size() {
    std::lock_guard<std::mutex> lock(g_graph_mutex);
@@ -1777,4 +1902,6 @@ TORCH_LIBRARY(isplib, m) {
          &gat_spmm16);
    m.def("gatv2_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor x, Tensor y, Tensor att, int heads, float negative_slope) -> Tensor",
          &gatv2_spmm);
+   m.def("gatv2_spmm16(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor x, Tensor y, Tensor att, int heads, float negative_slope) -> Tensor",
+         &gatv2_spmm16);
 }

@@ -28,7 +28,8 @@ for the backward of a 16-bit `mean` on an unweighted graph (rows16_mean_bw_route
 gradient of a 16-bit sum / mean (rows16_da_route), ISPLIB_HALF_GCN=convert|native|auto for gcn_norm_matmul on 16-bit features
 (rows16_gcn_route; unset: such a call raises, as it always did), ISPLIB_HALF_ATTENTION=convert|native|auto for attention_matmul on
 16-bit operands (attention16_route; unset: such a call raises, as it always did), ISPLIB_HALF_GAT=convert|native|auto for gat_matmul on
-a 16-bit `y` (gat16_route; unset: such a call raises, as it always did); the first three default to convert;
+a 16-bit `y` (gat16_route; unset: such a call raises, as it always did), ISPLIB_HALF_GATV2=convert|native|auto for gatv2_matmul on
+16-bit `x` and `y` (gatv2_16_route; unset: such a call raises, as it always did); the first three default to convert;
 ISPLIB_TUNE_FILE names a tuning table to load at import; ISPLIB_DEBUG=1 prints per-operator device times.
 """
 from __future__ import annotations
@@ -449,6 +450,38 @@ def gat16_route(dtype, heads: int, d: int, pitch: int, n: int, mode: Optional[st
     return "gat16" if mode == "native" or cabi.gat16_native_pays(n, ld) else "convert"
 
 
+def gatv2_16_route(dtype, heads: int, d: int, pitch: int, n: int, mode: Optional[str] = None) -> str:
+    """Which way gatv2_matmul with 16-bit `x` and `y` goes once ISPLIB_HALF_GATV2 is set, asked per GATHERED wide operand (y with its
+    rows for the forward and the rows kernel; x with its rows and the gradient with its rows, packed, for the backward over the
+    columns): "gatv2_16" (torch.ops.isplib.gatv2_spmm16 on the 16-bit kernels, isplib_gatv2_16_*_hip: x, y and the gradients as they
+    lie, half the gathered bytes, no fp32 [*, K] tensor in either direction) or "convert" (`x.float()`, `y.float()` -> the fp32
+    operator -> `.to(dtype)`).  A pure function -- no device, no library call:
+      * gatv2_16 needs bf16 / fp16 and the operand's shape, [n, heads * d] at its own row pitch or, failing that, packed, inside the
+        entries' domain (cabi.gatv2_16_serves = gat16_serves: 8 <= heads * d <= 512, heads == 1 with d even or d a power of two >= 8,
+        the pitch even);
+      * `mode` is ISPLIB_HALF_GATV2 (None: read from the environment; unset counts as "convert" here -- gatv2_matmul itself raises
+        before it asks -- and ISPLIB_HALF=convert wins over it): "convert" always converts, "native" takes the kernels wherever the
+        above holds, "auto" only in the classes -- the gathered operand beyond 256 MiB or not -- where every native run measured
+        faster than every run of the conversion route (cabi.gatv2_16_native_pays, profiles/gatv2_16_ab.txt).  Nothing raises."""
+    if dtype not in HALF_DTYPES:
+        return "convert"
+    from . import cabi
+    if mode is None:
+        mode = os.environ.get("ISPLIB_HALF", "auto")
+        if mode != "convert":
+            mode = os.environ.get("ISPLIB_HALF_GATV2", "convert")
+    if mode not in ("native", "auto"):
+        return "convert"
+    k = heads * d
+    if cabi.gatv2_16_serves(n, heads, d, pitch):
+        ld = pitch
+    elif cabi.gatv2_16_serves(n, heads, d, k):
+        ld = k
+    else:
+        return "convert"
+    return "gatv2_16" if mode == "native" or cabi.gatv2_16_native_pays(n, ld) else "convert"
+
+
 _ROWS16_MARK = torch.tensor([16], dtype=torch.int32)      # second tensor of a 16-bit row plan (torch_ops.cpp: is_rows16_plan)
 _ROWS16_DA_MARK = torch.tensor([0xDA], dtype=torch.int32)  # third tensor of a forward plan whose dA runs in 16 bits (is_rows16_da_plan)
 
@@ -775,17 +808,32 @@ def gatv2_matmul(src, x: torch.Tensor, att: torch.Tensor, y: Optional[torch.Tens
     side (``lin_l(x)``: gathered, and what is aggregated), head h in the columns [h*d, (h+1)*d); `att` is [heads, d], or [d] / [K] with
     one head.  ``y=None`` means ``y = x`` (``share_weights=True``) and needs a square `src`; the one tensor's gradient then receives
     both parts.  The stored values of `src` are not read; an empty row gives 0.  The backward keeps x, y, att, z and one scalar per row
-    and head -- nothing per edge.  fp32 only (bf16 / fp16 operands raise TypeError); there is no fallback route: outside
-    isplib_gatv2_serves (= isplib_gat_serves: heads * d <= 512; heads == 1 or d a power of two >= 4) the call raises ValueError."""
+    and head -- nothing per edge.  fp32 only by default (bf16 / fp16 operands raise TypeError); there is no fallback route: outside
+    isplib_gatv2_serves (= isplib_gat_serves: heads * d <= 512; heads == 1 or d a power of two >= 4) the call raises ValueError.
+    bf16 / fp16 `x` and `y` (both of one dtype) are opt-in through the GATv2 variable of the module docstring (convert|native|auto):
+    once it is set the call goes where gatv2_16_route says -- the 16-bit operator (torch.ops.isplib.gatv2_spmm16, which keeps x, y,
+    att and lse for its backward and no z) where ALL three gathered operands are admitted (y with its rows, x with its rows, the
+    gradient with M rows at pitch K), else `x.float()`, `y.float()` -> this function -> `.to(dtype)`, which raises only what the fp32
+    call raises.  `att` may then be float32 or of that dtype (a 16-bit `att` is widened by `.float()`, which is exact, and its gradient
+    returns in its own dtype through that cast); the result and the gradients of `x` and `y` have their dtype.  fp32 calls do not read
+    the variable."""
     from . import cabi
     shared = y is None
     if shared:
         y = x
+    half = (isinstance(x, torch.Tensor) and isinstance(y, torch.Tensor) and (x.dtype in HALF_DTYPES or y.dtype in HALF_DTYPES) and
+            os.environ.get("ISPLIB_HALF_GATV2") is not None)
     for name, t in (("x", x), ("y", y), ("att", att)):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"isplib_amd: `{name}` must be a tensor, got {type(t).__name__}")
-        if t.dtype != torch.float32:
+        if half and name != "att" and (t.dtype not in HALF_DTYPES or t.dtype != x.dtype):
+            raise TypeError(f"isplib_amd: `x` and `y` must share one 16-bit dtype, got {x.dtype} and {y.dtype}")
+        if half and name == "att" and t.dtype not in (torch.float32, x.dtype):
+            raise TypeError(f"isplib_amd: `att` must be float32 or of `x`'s dtype ({x.dtype}), got {t.dtype}")
+        if not half and t.dtype != torch.float32:
             raise TypeError(f"isplib_amd: `{name}` must be float32, got {t.dtype} (the GATv2 operator is fp32 only)")
+    if half:
+        return _gatv2_matmul16(src, x, att, None if shared else y, heads, negative_slope)
     if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
         raise ValueError(f"isplib_amd: `heads` must be a positive int, got {heads!r}")
     if x.dim() != 2 or y.dim() != 2:
@@ -822,6 +870,35 @@ def gatv2_matmul(src, x: torch.Tensor, att: torch.Tensor, y: Optional[torch.Tens
     if x.device != y.device or att.device != y.device or st._rowptr.device != y.device:
         raise ValueError("isplib_amd: `x`, `y`, `att` and the sparse matrix must be on one device")
     return torch.ops.isplib.gatv2_spmm(st._rowptr, st._col, st.colptr(), st.row_t(), x, y, att, heads, float(negative_slope))
+
+
+def _gatv2_matmul16(src, x, att, y, heads, negative_slope):
+    """gatv2_matmul for bf16 / fp16 `x` and `y` under ISPLIB_HALF_GATV2: the 16-bit operator where gatv2_16_route admits ALL three
+    gathered operands (y by the forward and the rows kernel; x and the gradient -- M rows, packed -- by the columns kernel), else the
+    conversion route.  `y` None: y = x, on both routes the one tensor's gradient receives dx + dy."""
+    att = att.float()                                 # exact, and no copy of an fp32 att; a gradient returns through the cast
+    shared = y is None
+    yy = x if shared else y
+    native = False
+    if (isinstance(heads, int) and not isinstance(heads, bool) and heads >= 1 and x.dim() == 2 and yy.dim() == 2 and
+            x.size(1) == yy.size(1) and x.size(1) % heads == 0 and x.is_cuda and yy.is_cuda and att.is_cuda):
+        st = _storage_of(src, yy)
+        m_rows, n_cols, k = st._rowptr.numel() - 1, st._sparse_sizes[1], yy.size(1)
+        d = k // heads
+        pitch_y = yy.stride(0) if n_cols > 1 and yy.stride(1) == 1 and yy.stride(0) >= k else k
+        pitch_x = x.stride(0) if m_rows > 1 and x.stride(1) == 1 and x.stride(0) >= k else k
+        native = (yy.size(0) == n_cols and x.size(0) == m_rows and
+                  all(gatv2_16_route(x.dtype, heads, d, ld, rows) == "gatv2_16"
+                      for rows, ld in ((n_cols, pitch_y), (m_rows, pitch_x), (m_rows, k))))
+    if not native:
+        return gatv2_matmul(src, x.float(), att, None if shared else y.float(), heads, negative_slope).to(x.dtype)
+    if heads == 1 and att.dim() == 1:
+        att = att.unsqueeze(0)
+    if att.dim() != 2 or att.size(0) != heads or att.size(1) != d:
+        raise ValueError(f"isplib_amd: `att` must be [{heads}, {d}] (heads x d; [d] with one head), got shape {tuple(att.shape)}")
+    if x.device != yy.device or att.device != yy.device or st._rowptr.device != yy.device:
+        raise ValueError("isplib_amd: `x`, `y`, `att` and the sparse matrix must be on one device")
+    return torch.ops.isplib.gatv2_spmm16(st._rowptr, st._col, st.colptr(), st.row_t(), x, yy, att, heads, float(negative_slope))
 
 
 def _gat_matmul16(src, y, a_dst, a_src, heads, negative_slope):

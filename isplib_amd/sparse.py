@@ -350,6 +350,7 @@ class SparseTensor:
 
     def gatv2_matmul(self, x: torch.Tensor, att: torch.Tensor, y: Optional[torch.Tensor] = None, heads: int = 1,
                      negative_slope: float = 0.2) -> torch.Tensor:
-        """GATv2 attention aggregation over this matrix's stored entries, all heads in one launch (plugin.gatv2_matmul)."""
+        """GATv2 attention aggregation over this matrix's stored entries, all heads in one launch (plugin.gatv2_matmul); bf16 / fp16
+        `x` and `y` are opt-in through ISPLIB_HALF_GATV2."""
         from .plugin import gatv2_matmul
         return gatv2_matmul(self, x, att, y, heads, negative_slope)
