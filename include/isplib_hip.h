@@ -809,6 +809,46 @@ int    isplib_gat_bw_cols_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, cons
                               int64_t heads, float negative_slope, const float *g, int64_t ldg, const float *lse,
                               const float *dsum, float *dy, int64_t lddy, float *d_a_src /* n x heads */, void *stream);
 /*
+ * The GAT aggregation above with a per-edge score term (GATConv's edge_dim), fp32: a_edge [nnz, heads] (dense: a row pitch of
+ * `heads`), one row per stored entry IN CSR POSITION ORDER -- row e of a_edge belongs to the entry indx[e] -- and
+ *   u_e  = (a_dst[i,h] + a_src[j,h]) + a_edge[e,h]       TWO fp32 adds, in this order, in all three entries
+ *   s_e, a_e, lse, z, D, t_e, du_e, d a_dst, d a_src, dy  as above          d a_edge[e,h] = du_e
+ * The slope branch is taken on this fp32 u_e (u_e == 0 takes ns): with three terms its sign is no longer the sign of the exact sum,
+ * so the order of the adds is part of the contract -- the forward and both backward entries agree on the branch of every edge.
+ * Every stored entry is its own edge: duplicates (i, j) each have their own a_edge row.  With a_edge = 0 the results are those of the
+ * entries above bit for bit ((a + b) + 0 is exact).  A NaN in a_edge[e,h] reaches head h of row i(e) and nothing else.
+ *   isplib_gat_edge_csr_hip      isplib_gat_csr_hip with `a_edge` after `a_src`; a_edge is a streamed read.
+ *   isplib_gat_edge_bw_rows_hip  isplib_gat_bw_rows_hip with `a_edge` after `a_src` and a TRAILING `d_a_edge` (nnz x heads, after
+ *                                `stream`), which may be NULL: then nothing per edge is written.  Otherwise every element of
+ *                                d_a_edge is written exactly once (write-only).
+ *   isplib_gat_edge_bw_cols_hip  isplib_gat_bw_cols_hip with `csr2csc` after `cole` (int64 [nnz]: the CSR position of every entry of
+ *                                the transposed structure, what isplib_csr2csc_hip writes as its permutation) and `a_edge` after
+ *                                `a_src`; a_edge[csr2csc[q], h] is a 4-byte gather behind one descriptor.  A csr2csc value outside
+ *                                [0, nnz) reads as 0, never outside a_edge.
+ * Domain: isplib_gat_serves as above AND isplib_gat_edge_serves(nnz, heads): 1 <= heads, 0 <= nnz < 2^31 and a_edge inside one buffer
+ * descriptor, nnz * heads * 4 <= ISPLIB_DENSE_BYTES_MAX (the way out: fewer heads per call, on column views of y).  Outside either:
+ * ISPLIB_NO_OPT_IMPL; null operands (a_edge or csr2csc with nnz > 0 included) and the refusals above: ISPLIB_FAIL; all before any
+ * launch.  Nothing outside [0, nnz * heads) of a_edge is read.
+ */
+static inline int isplib_gat_edge_serves(int64_t nnz, int64_t heads) {
+   return heads >= 1 && nnz >= 0 && nnz < (1LL << 31) && isplib_dense_in_descriptor(nnz, heads);
+}
+int    isplib_gat_edge_domain(int64_t nnz, int64_t heads);                        /* isplib_gat_edge_serves as a symbol */
+int    isplib_gat_edge_csr_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                               const int64_t *pntre, const float *a_dst /* m x heads */, const float *y, int64_t ldy,
+                               const float *a_src /* n x heads */, const float *a_edge /* nnz x heads */, int64_t heads,
+                               float negative_slope, float *z, int64_t ldz, float *lse /* m x heads */, void *stream);
+int    isplib_gat_edge_bw_rows_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                                   const int64_t *pntre, const float *a_dst, const float *y, int64_t ldy, const float *a_src,
+                                   const float *a_edge, int64_t heads, float negative_slope, const float *g, int64_t ldg,
+                                   const float *z, int64_t ldz, const float *lse, float *d_a_dst /* m x heads */,
+                                   float *dsum /* m x heads */, void *stream, float *d_a_edge /* nnz x heads, or NULL */);
+int    isplib_gat_edge_bw_cols_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t, const int64_t *colb,
+                                   const int64_t *cole, const int64_t *csr2csc /* nnz */, const float *a_dst, const float *y,
+                                   int64_t ldy, const float *a_src, const float *a_edge, int64_t heads, float negative_slope,
+                                   const float *g, int64_t ldg, const float *lse, const float *dsum, float *dy, int64_t lddy,
+                                   float *d_a_src /* n x heads */, void *stream);
+/*
  * The row-softmax attention aggregation above for dense operands of 16-bit elements (dtype: ISPLIB_DTYPE_BF16 | _F16), forward and
  * backward, on the same mapping (one wave per row or column, one 16-byte gather of EIGHT columns per lane and edge, one chunk per
  * lane).  x, y and g are `dtype` and no operand is widened in memory; widening is exact, every product, sum, exponential and division

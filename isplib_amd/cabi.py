@@ -141,6 +141,12 @@ def gat_serves(rows_gathered: int, heads: int, d: int, ld: int) -> bool:
     return ld >= heads * d and rows_gathered < 2 ** 31 and (rows_gathered <= 0 or rows_gathered * ld * 4 <= DENSE_BYTES_MAX)
 
 
+def gat_edge_serves(nnz: int, heads: int) -> bool:
+    """isplib_gat_edge_serves of the header: the per-edge score term a_edge [nnz, heads] of the isplib_gat_edge_* entries sits behind one
+    buffer descriptor and an entry's CSR position is a 32-bit int."""
+    return heads >= 1 and 0 <= nnz < 2 ** 31 and nnz * heads * 4 <= DENSE_BYTES_MAX
+
+
 def gatv2_serves(rows_gathered: int, heads: int, d: int, ld: int) -> bool:
     """isplib_gatv2_serves of the header: the GATv2 entries' domain IS isplib_gat_serves -- stated once."""
     return gat_serves(rows_gathered, heads, d, ld)
@@ -254,6 +260,7 @@ EXPORTS = (
     "isplib_attention16_csr_hip", "isplib_attention16_bw_rows_hip", "isplib_attention16_bw_cols_hip", "isplib_attention16_domain",
     "isplib_attention16_auto",
     "isplib_gat_csr_hip", "isplib_gat_bw_rows_hip", "isplib_gat_bw_cols_hip", "isplib_gat_domain",
+    "isplib_gat_edge_csr_hip", "isplib_gat_edge_bw_rows_hip", "isplib_gat_edge_bw_cols_hip", "isplib_gat_edge_domain",
     "isplib_gat16_csr_hip", "isplib_gat16_bw_rows_hip", "isplib_gat16_bw_cols_hip", "isplib_gat16_domain", "isplib_gat16_auto",
     "isplib_gatv2_csr_hip", "isplib_gatv2_bw_rows_hip", "isplib_gatv2_bw_rows_workspace_bytes", "isplib_gatv2_bw_cols_hip",
     "isplib_gatv2_domain",
@@ -525,6 +532,16 @@ def lib() -> ctypes.CDLL:
         L.isplib_gat_bw_cols_hip.restype = ctypes.c_int
         L.isplib_gat_bw_cols_hip.argtypes = [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _vp, _vp,
                                              _i64, _vp, _vp]
+        L.isplib_gat_edge_domain.restype = ctypes.c_int
+        L.isplib_gat_edge_domain.argtypes = [_i64, _i64]
+        L.isplib_gat_edge_csr_hip.restype = ctypes.c_int          # isplib_gat_csr_hip with a_edge after a_src
+        L.isplib_gat_edge_csr_hip.argtypes = [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _f32, _vp, _i64, _vp, _vp]
+        L.isplib_gat_edge_bw_rows_hip.restype = ctypes.c_int      # ... and a trailing d_a_edge (after the stream), which may be NULL
+        L.isplib_gat_edge_bw_rows_hip.argtypes = [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _f32, _vp, _i64, _vp,
+                                                  _i64, _vp, _vp, _vp, _vp, _vp]
+        L.isplib_gat_edge_bw_cols_hip.restype = ctypes.c_int      # isplib_gat_bw_cols_hip with csr2csc after cole, a_edge after a_src
+        L.isplib_gat_edge_bw_cols_hip.argtypes = [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _f32, _vp, _i64,
+                                                  _vp, _vp, _vp, _i64, _vp, _vp]
         L.isplib_gatv2_domain.restype = ctypes.c_int
         L.isplib_gatv2_domain.argtypes = [_i64, _i64, _i64, _i64]
         L.isplib_gatv2_bw_rows_workspace_bytes.restype = ctypes.c_size_t
@@ -2039,6 +2056,162 @@ def gat_bw_cols(colptr, row_t, y, a_dst, a_src, g, lse, dsum, heads: int = 1, ne
                                           _ptr(y), ldy, _ptr(a_src), heads, float(negative_slope), _ptr(g), ldg, _ptr(lse), _ptr(dsum),
                                           _ptr(dy), lddy, _ptr(dasrc), _stream(y.device))
     _check(st, "isplib_gat_bw_cols_hip")
+    return dy, dasrc
+
+
+def _gat_edge_domain(nnz: int, heads: int) -> None:
+    if not gat_edge_serves(nnz, heads):
+        raise ValueError(f"isplib_amd: outside the GAT edge entries' domain (isplib_gat_edge_serves: nnz < 2^31, nnz * heads * 4 <= "
+                         f"{DENSE_BYTES_MAX} bytes = 3.5 GiB, `a_edge` behind one buffer descriptor), got nnz={nnz}, heads={heads}; pass fewer "
+                         f"heads per call, on column views of `y`")
+
+
+def _gat_edge_positions(csr2csc, nnz: int, check: bool):
+    if not isinstance(csr2csc, torch.Tensor) or csr2csc.dim() != 1 or csr2csc.numel() != nnz:
+        raise ValueError(f"isplib_amd: `csr2csc` must be a 1-D tensor of {nnz} entries (the CSR position of every entry of the transposed "
+                         f"structure), got {tuple(csr2csc.shape) if isinstance(csr2csc, torch.Tensor) else type(csr2csc).__name__}")
+    if csr2csc.dtype != torch.int64:
+        raise TypeError(f"isplib_amd: `csr2csc` must be int64, got {csr2csc.dtype}")
+    if check and csr2csc.is_cuda and nnz > 0 and (int(csr2csc.min()) < 0 or int(csr2csc.max()) >= nnz):
+        raise ValueError(f"isplib_amd: the positions of `csr2csc` must lie in [0, {nnz})")
+    return csr2csc.contiguous()
+
+
+def gat_edge(rowptr, col, y, a_dst, a_src, a_edge, heads: int = 1, negative_slope: float = 0.2, *, out=None, check: bool = True):
+    """`gat` with a per-edge score term (isplib_gat_edge_csr_hip): u_e = (a_dst[i,h] + a_src[j,h]) + a_edge[e,h], two fp32 adds in this
+    order; `a_edge` is a dense float32 [nnz, heads], row e belonging to the entry col[e] (CSR position order).  Returns (z, lse); every
+    operand, the domain of `a_edge` (gat_edge_serves) included, is checked BEFORE the call."""
+    if not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1 or rowptr.numel() < 1:
+        raise ValueError("isplib_amd: `rowptr` (m + 1 entries) must be a 1-D tensor")
+    m = rowptr.numel() - 1
+    if not isinstance(y, torch.Tensor) or y.dim() != 2:
+        raise ValueError("isplib_amd: `y` must be a 2-D tensor [n, heads * d]")
+    n, k = y.size(0), y.size(1)
+    ldy = _attn_dense(y, "y", n, None, "one row per column of the sparse operand")
+    d = _gat_heads(heads, k)
+    _gat_table(a_dst, "a_dst", m, heads)
+    _gat_table(a_src, "a_src", n, heads)
+    rowptr, col = _attn_structure(rowptr, col, "rowptr", "col", n, check)
+    _gat_table(a_edge, "a_edge", col.numel(), heads)
+    if out is not None:
+        z, lse = out
+        ldz = _attn_dense(z, "out[0]", m, k, "z")
+        _gat_table(lse, "out[1]", m, heads)
+    _gat_domain(n, heads, d, ldy)
+    _gat_edge_domain(col.numel(), heads)
+    _same_gpu((("y", y), ("a_dst", a_dst), ("a_src", a_src), ("a_edge", a_edge), ("rowptr", rowptr), ("col", col)) +
+              ((("out[0]", out[0]), ("out[1]", out[1])) if out is not None else ()))
+    if out is None:
+        z = torch.empty((m, k), dtype=torch.float32, device=y.device)
+        lse = torch.empty((m, heads), dtype=torch.float32, device=y.device)
+        ldz = max(k, 1)
+    if m == 0 or k == 0:
+        if k == 0 and m > 0:
+            lse.fill_(float("-inf"))
+        return z, lse
+    rp = rowptr.data_ptr()
+    with torch.cuda.device(y.device):
+        st = lib().isplib_gat_edge_csr_hip(m, n, k, col.numel(), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8), _ptr(a_dst), _ptr(y),
+                                           ldy, _ptr(a_src), _ptr(a_edge), heads, float(negative_slope), _ptr(z), ldz, _ptr(lse),
+                                           _stream(y.device))
+    _check(st, "isplib_gat_edge_csr_hip")
+    return z, lse
+
+
+def gat_edge_bw_rows(rowptr, col, y, a_dst, a_src, a_edge, g, z, lse, heads: int = 1, negative_slope: float = 0.2, *, out=None,
+                     want_edge: bool = True, check: bool = True):
+    """The backward of `gat_edge` over the rows (isplib_gat_edge_bw_rows_hip): `gat_bw_rows` with the per-edge term, and d a_edge[e,h] =
+    du_e written once per entry.  Returns (d_a_dst [m, heads], D [m, heads], d_a_edge [nnz, heads]); with want_edge=False nothing per
+    edge is allocated or written and the third result is None.  `out` = (d_a_dst, D, d_a_edge or None)."""
+    if not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1 or rowptr.numel() < 1:
+        raise ValueError("isplib_amd: `rowptr` (m + 1 entries) must be a 1-D tensor")
+    m = rowptr.numel() - 1
+    if not isinstance(y, torch.Tensor) or y.dim() != 2:
+        raise ValueError("isplib_amd: `y` must be a 2-D tensor [n, heads * d]")
+    n, k = y.size(0), y.size(1)
+    ldy = _attn_dense(y, "y", n, None, "one row per column of the sparse operand")
+    d = _gat_heads(heads, k)
+    _gat_table(a_dst, "a_dst", m, heads)
+    _gat_table(a_src, "a_src", n, heads)
+    ldg = _attn_dense(g, "g", m, k, "the gradient of z")
+    ldz = _attn_dense(z, "z", m, k, "the forward's output")
+    _gat_table(lse, "lse", m, heads)
+    rowptr, col = _attn_structure(rowptr, col, "rowptr", "col", n, check)
+    nnz = col.numel()
+    _gat_table(a_edge, "a_edge", nnz, heads)
+    if out is not None:
+        _gat_table(out[0], "out[0]", m, heads)
+        _gat_table(out[1], "out[1]", m, heads)
+        if out[2] is not None:
+            _gat_table(out[2], "out[2]", nnz, heads)
+    _gat_domain(n, heads, d, ldy)
+    _gat_edge_domain(nnz, heads)
+    _same_gpu((("y", y), ("a_dst", a_dst), ("a_src", a_src), ("a_edge", a_edge), ("g", g), ("z", z), ("lse", lse), ("rowptr", rowptr),
+               ("col", col)) + ((("out[0]", out[0]), ("out[1]", out[1]), ("out[2]", out[2])) if out is not None else ()))
+    if out is None:
+        out = (torch.empty((m, heads), dtype=torch.float32, device=y.device), torch.empty((m, heads), dtype=torch.float32, device=y.device),
+               torch.empty((nnz, heads), dtype=torch.float32, device=y.device) if want_edge else None)
+    dadst, dsum, dedge = out
+    if m == 0 or k == 0:
+        if k == 0 and m > 0:
+            dadst.zero_()
+            dsum.zero_()
+            if dedge is not None:
+                dedge.zero_()
+        return dadst, dsum, dedge
+    rp = rowptr.data_ptr()
+    with torch.cuda.device(y.device):
+        st = lib().isplib_gat_edge_bw_rows_hip(m, n, k, nnz, _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8), _ptr(a_dst), _ptr(y), ldy,
+                                               _ptr(a_src), _ptr(a_edge), heads, float(negative_slope), _ptr(g), ldg, _ptr(z), ldz, _ptr(lse),
+                                               _ptr(dadst), _ptr(dsum), _stream(y.device), _ptr(dedge) if nnz > 0 else None)
+    _check(st, "isplib_gat_edge_bw_rows_hip")
+    return dadst, dsum, dedge
+
+
+def gat_edge_bw_cols(colptr, row_t, csr2csc, y, a_dst, a_src, a_edge, g, lse, dsum, heads: int = 1, negative_slope: float = 0.2, *, out=None,
+                     check: bool = True):
+    """The backward of `gat_edge` over the columns (isplib_gat_edge_bw_cols_hip): `gat_bw_cols` with the per-edge term; `csr2csc`
+    (int64 [nnz], what `csr2csc` returns and SparseStorage.csr2csc() caches) is the CSR position of every entry of the transposed
+    structure, by which `a_edge` is gathered.  Returns (dy, d_a_src)."""
+    if not isinstance(colptr, torch.Tensor) or colptr.dim() != 1 or colptr.numel() < 1:
+        raise ValueError("isplib_amd: `colptr` (n + 1 entries) must be a 1-D tensor")
+    n = colptr.numel() - 1
+    ldy = _attn_dense(y, "y", n, None, "one row per column of the sparse operand")
+    k = y.size(1)
+    d = _gat_heads(heads, k)
+    if not isinstance(g, torch.Tensor) or g.dim() != 2:
+        raise ValueError("isplib_amd: `g` must be a 2-D tensor [m, heads * d]")
+    m = g.size(0)
+    ldg = _attn_dense(g, "g", m, k, "the gradient of z")
+    _gat_table(a_dst, "a_dst", m, heads)
+    _gat_table(a_src, "a_src", n, heads)
+    _gat_table(lse, "lse", m, heads)
+    _gat_table(dsum, "dsum", m, heads)
+    colptr, row_t = _attn_structure(colptr, row_t, "colptr", "row_t", m, check)
+    nnz = row_t.numel()
+    csr2csc = _gat_edge_positions(csr2csc, nnz, check)
+    _gat_table(a_edge, "a_edge", nnz, heads)
+    if out is not None:
+        lddy = _attn_dense(out[0], "out[0]", n, k, "dy")
+        _gat_table(out[1], "out[1]", n, heads)
+    _gat_domain(m, heads, d, ldg)
+    _gat_edge_domain(nnz, heads)
+    _same_gpu((("y", y), ("a_dst", a_dst), ("a_src", a_src), ("a_edge", a_edge), ("g", g), ("lse", lse), ("dsum", dsum), ("colptr", colptr),
+               ("row_t", row_t), ("csr2csc", csr2csc)) + ((("out[0]", out[0]), ("out[1]", out[1])) if out is not None else ()))
+    if out is None:
+        out = (torch.empty((n, k), dtype=torch.float32, device=y.device), torch.empty((n, heads), dtype=torch.float32, device=y.device))
+        lddy = max(k, 1)
+    dy, dasrc = out
+    if n == 0 or k == 0:
+        if k == 0 and n > 0:
+            dasrc.zero_()
+        return dy, dasrc
+    cp = colptr.data_ptr()
+    with torch.cuda.device(y.device):
+        st = lib().isplib_gat_edge_bw_cols_hip(m, n, k, nnz, _ptr(row_t), ctypes.c_void_p(cp), ctypes.c_void_p(cp + 8), _ptr(csr2csc),
+                                               _ptr(a_dst), _ptr(y), ldy, _ptr(a_src), _ptr(a_edge), heads, float(negative_slope), _ptr(g),
+                                               ldg, _ptr(lse), _ptr(dsum), _ptr(dy), lddy, _ptr(dasrc), _stream(y.device))
+    _check(st, "isplib_gat_edge_bw_cols_hip")
     return dy, dasrc
 
 

@@ -26,6 +26,17 @@
 //
 // Every gathered table sits behind a buffer descriptor of exactly the extent it owns; dead edges and lanes past k carry BUF_OOB, which
 // the descriptor answers with 0.  No LDS, no atomics, a fixed order of operations: two launches give equal bits.  DESIGN.md 4.6d.
+//
+// The per-edge score term (isplib_gat_edge_*_hip): the three kernels are templates on EDGE.  With a_edge [nnz, H], one row
+// per stored entry in CSR position order,
+//    u_e = (a_dst[i,h] + a_src[j,h]) + a_edge[e,h]        TWO fp32 adds, in this order, in all three kernels
+// so that the forward and both backward kernels take the same branch of the slope on every edge (with three terms the sign of the fp32
+// u_e is no longer the sign of the exact sum).  The forward and the rows kernel walk CSR positions, so the term is a streamed read: the
+// edge in slot s of the batch at `base` is entry base + s, behind a descriptor rebased per batch on a_edge + base*H with the extent of
+// the batch's live entries -- exact, and a dead slot is answered with 0.  The rows kernel also writes d a_edge[e,h] = du_e, every entry
+// once (every stored entry belongs to one row).  The columns kernel walks the transposed structure and gathers a_edge[csr2csc[q], h]
+// behind one descriptor of nnz*H*4 bytes.  EDGE = false is the code of the entries without the term, instruction for instruction
+// (profiles/gat_edge_isa.txt).
 #include <cfloat>
 #include <cmath>
 
@@ -61,6 +72,11 @@ struct GatArgs {
    unsigned ybytes;
    const float *t0, *t1, *t2;              // forward, rows: t0 = a_src | columns: a_dst, lse, D; all [gathered rows, H]
    unsigned tbytes;
+   // EDGE only (appended: the layout of everything above is that of the kernels without the term)
+   const float *edge;                      // a_edge [nnz, H], rows in CSR position order
+   const int64_t *epos;                    // columns: csr2csc [nnz], the CSR position of every entry of the transposed structure
+   float *dedge;                           // rows: d a_edge [nnz, H], or NULL
+   unsigned ebytes;                        // columns: nnz * H * 4
 };
 
 template <int LPR, int NCH> struct GatCols {
@@ -123,6 +139,15 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t gat_rsrc(const float *p, unsig
    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p), 0, (int)bytes, 0x00020000);
 }
 
+// a descriptor whose base moves with the wave's batch: its inputs made provably wave-uniform, so that it is built with scalar
+// instructions and no buffer load through it sits in a waterfall loop
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t gat_rsrc_uniform(const float *p, unsigned bytes) {
+   const unsigned long long v = (unsigned long long)p;
+   const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
+   const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+   return gat_rsrc((const float *)(((unsigned long long)hi << 32) | (unsigned long long)lo), (unsigned)__builtin_amdgcn_readfirstlane((int)bytes));
+}
+
 // sum over the lanes that share a head (an aligned group of `hlanes` lanes, a power of two <= LPR); every lane of the group ends
 // with the same bits (each level adds the same two numbers on both sides)
 template <int LPR, int O = 1> __device__ __forceinline__ float gat_head_sum(float v, int hlanes) {
@@ -159,7 +184,14 @@ __device__ __forceinline__ float gat_score(float adst, float asrc, float ns, flo
    return u > 0.0f ? u : ns * u;
 }
 
-template <int LPR, int NCH, int WAVES>
+// with the per-edge term: (a_dst + a_src) + a_edge, TWO fp32 adds in this order in every kernel; the branch is taken on this fp32 u
+__device__ __forceinline__ float gat_score_edge(float adst, float asrc, float aedge, float ns, float &slope) {
+   const float u = (adst + asrc) + aedge;
+   slope = u > 0.0f ? 1.0f : ns;
+   return u > 0.0f ? u : ns * u;
+}
+
+template <int LPR, int NCH, int WAVES, bool EDGE>
 __global__ __launch_bounds__(WAVES * 64) void gat_fw_kernel(const GatArgs a) {
    constexpr int G = 64 / LPR, U = 4;
    const int lane = threadIdx.x & 63;
@@ -188,16 +220,19 @@ __global__ __launch_bounds__(WAVES * 64) void gat_fw_kernel(const GatArgs a) {
       const int id_l = pos < ee ? (int)a.indx[pos] : -1;
       const int64_t left = ee - base;
       const int cnt = left < 64 ? (int)left : 64;
+      [[maybe_unused]] __amdgpu_buffer_rsrc_t rse;      // EDGE: the batch's rows of a_edge and nothing else
+      if constexpr (EDGE) rse = gat_rsrc_uniform(a.edge + (size_t)base * (size_t)a.heads, (unsigned)cnt * hb);
 #pragma unroll 1
       for (int s0 = 0; s0 < cnt; s0 += G * U) {
          v4i_t yv[U][NCH];
-         float sc[U][NCH];
+         float sc[U][NCH], se[EDGE ? U : 1][NCH];
 #pragma unroll
          for (int u = 0; u < U; u++) {
             unsigned off, offh;
             gat_edge(id_l, (s0 + u * G + g) & 63, ldyb, hb, off, offh);
             gat_load_wide<LPR, NCH>(rsy, off, cm, yv[u]);
             gat_load_head<LPR, NCH>(rss, offh, cm, sc[u]);
+            if constexpr (EDGE) gat_load_head<LPR, NCH>(rse, (unsigned)((s0 + u * G + g) & 63) * hb, cm, se[u]);      // a slot past cnt: 0
          }
 #pragma unroll
          for (int j = 0; j < NCH; j++) {
@@ -205,7 +240,8 @@ __global__ __launch_bounds__(WAVES * 64) void gat_fw_kernel(const GatArgs a) {
 #pragma unroll
             for (int u = 0; u < U; u++) {
                float slope;
-               sc[u][j] = gat_score(adst[j], sc[u][j], a.ns, slope);
+               if constexpr (EDGE) sc[u][j] = gat_score_edge(adst[j], sc[u][j], se[u][j], a.ns, slope);
+               else sc[u][j] = gat_score(adst[j], sc[u][j], a.ns, slope);
                mnew = (s0 + u * G + g < cnt) ? fmaxf(mnew, sc[u][j]) : mnew;      // a NaN score is not a maximum; it enters through exp below
             }
             const float r = __expf(mrun[j] - mnew);
@@ -248,7 +284,7 @@ __global__ __launch_bounds__(WAVES * 64) void gat_fw_kernel(const GatArgs a) {
    }
 }
 
-template <int LPR, int NCH, int WAVES>
+template <int LPR, int NCH, int WAVES, bool EDGE>
 __global__ __launch_bounds__(WAVES * 64) void gat_bw_rows_kernel(const GatArgs a) {
    constexpr int G = 64 / LPR, U = 4;
    const int lane = threadIdx.x & 63;
@@ -284,6 +320,7 @@ __global__ __launch_bounds__(WAVES * 64) void gat_bw_rows_kernel(const GatArgs a
    float acc[NCH];
 #pragma unroll
    for (int j = 0; j < NCH; j++) acc[j] = 0.0f;
+   [[maybe_unused]] const bool store = EDGE && a.dedge != nullptr;      // wave-uniform: a kernel argument
 
    const unsigned ldyb = (unsigned)a.ldy * 4u, hb = (unsigned)a.heads * 4u;
    for (int64_t base = eb; base < ee; base += 64) {
@@ -291,16 +328,19 @@ __global__ __launch_bounds__(WAVES * 64) void gat_bw_rows_kernel(const GatArgs a
       const int id_l = pos < ee ? (int)a.indx[pos] : -1;
       const int64_t left = ee - base;
       const int cnt = left < 64 ? (int)left : 64;
+      [[maybe_unused]] __amdgpu_buffer_rsrc_t rse;      // EDGE: the batch's rows of a_edge and nothing else
+      if constexpr (EDGE) rse = gat_rsrc_uniform(a.edge + (size_t)base * (size_t)a.heads, (unsigned)cnt * hb);
 #pragma unroll 1
       for (int s0 = 0; s0 < cnt; s0 += G * U) {
          v4i_t yv[U][NCH];
-         float sc[U][NCH];
+         float sc[U][NCH], se[EDGE ? U : 1][NCH];
 #pragma unroll
          for (int u = 0; u < U; u++) {
             unsigned off, offh;
             gat_edge(id_l, (s0 + u * G + g) & 63, ldyb, hb, off, offh);
             gat_load_wide<LPR, NCH>(rsy, off, cm, yv[u]);
             gat_load_head<LPR, NCH>(rss, offh, cm, sc[u]);
+            if constexpr (EDGE) gat_load_head<LPR, NCH>(rse, (unsigned)((s0 + u * G + g) & 63) * hb, cm, se[u]);      // a slot past cnt: 0
          }
 #pragma unroll
          for (int u = 0; u < U; u++) {
@@ -310,8 +350,21 @@ __global__ __launch_bounds__(WAVES * 64) void gat_bw_rows_kernel(const GatArgs a
 #pragma unroll
             for (int j = 0; j < NCH; j++) {
                float slope;
-               const float s = gat_score(adst[j], sc[u][j], a.ns, slope);
-               acc[j] += live ? __expf(s - lse[j]) * (t[j] - dsum[j]) * slope : 0.0f;
+               if constexpr (EDGE) {
+                  const float s = gat_score_edge(adst[j], sc[u][j], se[u][j], a.ns, slope);
+                  const float x = __expf(s - lse[j]) * (t[j] - dsum[j]);
+                  const float du = x * slope;
+                  // the bits of the kernel without the term: with one slot (G == 1) its first edge of a step is live whenever the step
+                  // runs, and there the compiler contracts acc + x * slope into one fma; du has a second use here (the store), which
+                  // would keep it from doing so -- so the fma is written out (profiles/gat_edge_isa.txt)
+                  if (G == 1 && u == 0) acc[j] = fmaf(x, slope, acc[j]);
+                  else acc[j] += live ? du : 0.0f;
+                  if (store && live && cm.first[j])      // the lane that opens the head: every entry of d a_edge is written once
+                     a.dedge[(size_t)(base + ((s0 + u * G + g) & 63)) * (size_t)a.heads + (size_t)cm.head[j]] = du;
+               } else {
+                  const float s = gat_score(adst[j], sc[u][j], a.ns, slope);
+                  acc[j] += live ? __expf(s - lse[j]) * (t[j] - dsum[j]) * slope : 0.0f;
+               }
             }
          }
       }
@@ -331,7 +384,7 @@ __global__ __launch_bounds__(WAVES * 64) void gat_bw_rows_kernel(const GatArgs a
 }
 
 // one wave per column j of A (a row of the transposed structure): y_j and a_src[j,.] in registers; g_i, a_dst, lse, D of row i gathered
-template <int LPR, int NCH, int WAVES>
+template <int LPR, int NCH, int WAVES, bool EDGE>
 __global__ __launch_bounds__(WAVES * 64) void gat_bw_cols_kernel(const GatArgs a) {
    constexpr int G = 64 / LPR, U = NCH >= 2 ? 2 : 4;
    const int lane = threadIdx.x & 63;
@@ -342,6 +395,8 @@ __global__ __launch_bounds__(WAVES * 64) void gat_bw_cols_kernel(const GatArgs a
    const int64_t eb = a.pntrb[row], ee = a.pntre[row];
    const __amdgpu_buffer_rsrc_t rsg = gat_rsrc(a.y, a.ybytes);
    const __amdgpu_buffer_rsrc_t rs0 = gat_rsrc(a.t0, a.tbytes), rs1 = gat_rsrc(a.t1, a.tbytes), rs2 = gat_rsrc(a.t2, a.tbytes);
+   [[maybe_unused]] __amdgpu_buffer_rsrc_t rse;         // EDGE: all of a_edge, gathered by CSR position
+   if constexpr (EDGE) rse = gat_rsrc(a.edge, a.ebytes);
    const GatCols<LPR, NCH> cm(a, lc);
    float yv[NCH][4], asrc[NCH];
    gat_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm, yv);
@@ -359,12 +414,14 @@ __global__ __launch_bounds__(WAVES * 64) void gat_bw_cols_kernel(const GatArgs a
    for (int64_t base = eb; base < ee; base += 64) {
       const int64_t pos = base + lane;
       const int id_l = pos < ee ? (int)a.indx[pos] : -1;
+      [[maybe_unused]] int ep_l = -1;                   // EDGE: the entry's CSR position (nnz < 2^31), handed across lanes like the row id
+      if constexpr (EDGE) ep_l = pos < ee ? (int)a.epos[pos] : -1;
       const int64_t left = ee - base;
       const int cnt = left < 64 ? (int)left : 64;
 #pragma unroll 1
       for (int s0 = 0; s0 < cnt; s0 += G * U) {
          v4i_t gg[U][NCH];
-         float ad[U][NCH], ls[U][NCH], ds[U][NCH];
+         float ad[U][NCH], ls[U][NCH], ds[U][NCH], se[EDGE ? U : 1][NCH];
 #pragma unroll
          for (int u = 0; u < U; u++) {
             unsigned off, offh;
@@ -373,6 +430,10 @@ __global__ __launch_bounds__(WAVES * 64) void gat_bw_cols_kernel(const GatArgs a
             gat_load_head<LPR, NCH>(rs0, offh, cm, ad[u]);
             gat_load_head<LPR, NCH>(rs1, offh, cm, ls[u]);
             gat_load_head<LPR, NCH>(rs2, offh, cm, ds[u]);
+            if constexpr (EDGE) {
+               const int ep = __shfl(ep_l, (s0 + u * G + g) & 63);
+               gat_load_head<LPR, NCH>(rse, ep < 0 ? BUF_OOB : (unsigned)ep * hb, cm, se[u]);      // ep * hb < nnz*H*4 <= 3.5 GiB
+            }
          }
 #pragma unroll
          for (int u = 0; u < U; u++) {
@@ -382,7 +443,9 @@ __global__ __launch_bounds__(WAVES * 64) void gat_bw_cols_kernel(const GatArgs a
 #pragma unroll
             for (int j = 0; j < NCH; j++) {
                float slope;
-               const float s = gat_score(ad[u][j], asrc[j], a.ns, slope);
+               float s;
+               if constexpr (EDGE) s = gat_score_edge(ad[u][j], asrc[j], se[u][j], a.ns, slope);
+               else s = gat_score(ad[u][j], asrc[j], a.ns, slope);
                const float ae = live ? __expf(s - ls[u][j]) : 0.0f;
                accs[j] += live ? ae * (t[j] - ds[u][j]) * slope : 0.0f;
 #pragma unroll
@@ -411,26 +474,31 @@ __global__ __launch_bounds__(WAVES * 64) void gat_bw_cols_kernel(const GatArgs a
 
 enum { GAT_FW = 0, GAT_BW_ROWS = 1, GAT_BW_COLS = 2 };
 
-template <int LPR, int NCH>
+template <int LPR, int NCH, bool EDGE>
 static int launch_gat(int which, const GatArgs &a, const char *entry, hipStream_t st) {
    constexpr int WAVES = 4;
    const int64_t nb = (a.rows + WAVES - 1) / WAVES;
    if (nb > 0x7fffffffLL) return fail(ISPLIB_FAIL, entry, "too many rows for one launch");
    const dim3 grid((unsigned)nb), block(WAVES * 64);
-   if (which == GAT_FW) hipLaunchKernelGGL((gat_fw_kernel<LPR, NCH, WAVES>), grid, block, 0, st, a);
-   else if (which == GAT_BW_ROWS) hipLaunchKernelGGL((gat_bw_rows_kernel<LPR, NCH, WAVES>), grid, block, 0, st, a);
-   else hipLaunchKernelGGL((gat_bw_cols_kernel<LPR, NCH, WAVES>), grid, block, 0, st, a);
+   if (which == GAT_FW) hipLaunchKernelGGL((gat_fw_kernel<LPR, NCH, WAVES, EDGE>), grid, block, 0, st, a);
+   else if (which == GAT_BW_ROWS) hipLaunchKernelGGL((gat_bw_rows_kernel<LPR, NCH, WAVES, EDGE>), grid, block, 0, st, a);
+   else hipLaunchKernelGGL((gat_bw_cols_kernel<LPR, NCH, WAVES, EDGE>), grid, block, 0, st, a);
    return check_launch(entry);
 }
 
-// the width dispatch of attention.hip, up to two chunks per lane
-static int gat_by_width(int which, const GatArgs &a, const char *entry, hipStream_t st) {
+// the width dispatch of attention.hip, up to two chunks per lane; EDGE: the kernels with the per-edge term
+template <bool EDGE>
+static int gat_by_width_of(int which, const GatArgs &a, const char *entry, hipStream_t st) {
    const int64_t w = (a.k + 3) / 4;
-   if (w <= 8) return launch_gat<8, 1>(which, a, entry, st);
-   if (w <= 16) return launch_gat<16, 1>(which, a, entry, st);
-   if (w <= 32) return launch_gat<32, 1>(which, a, entry, st);
-   if (w <= 64) return launch_gat<64, 1>(which, a, entry, st);
-   return launch_gat<64, 2>(which, a, entry, st);
+   if (w <= 8) return launch_gat<8, 1, EDGE>(which, a, entry, st);
+   if (w <= 16) return launch_gat<16, 1, EDGE>(which, a, entry, st);
+   if (w <= 32) return launch_gat<32, 1, EDGE>(which, a, entry, st);
+   if (w <= 64) return launch_gat<64, 1, EDGE>(which, a, entry, st);
+   return launch_gat<64, 2, EDGE>(which, a, entry, st);
+}
+
+static int gat_by_width(int which, const GatArgs &a, bool edge, const char *entry, hipStream_t st) {
+   return edge ? gat_by_width_of<true>(which, a, entry, st) : gat_by_width_of<false>(which, a, entry, st);
 }
 
 // what a descriptor over `rows` rows of k floats at pitch ld may answer: the extent a row-strided view owns, not rows * ld
@@ -452,24 +520,22 @@ static void gat_heads(GatArgs &a, int64_t heads, int64_t d) {
 
 static const char *const GAT_DOMAIN = "outside isplib_gat_serves(rows_gathered, heads, d, ld): 1 <= heads, 1 <= d, heads*d <= 512, heads == 1 or "
                                       "d a power of two >= 4, ld >= heads*d, rows_gathered < 2^31, rows_gathered*ld*4 <= 3.5 GiB";
+static const char *const GAT_EDGE_DOMAIN = "outside isplib_gat_edge_serves(nnz, heads): 1 <= heads, 0 <= nnz < 2^31, nnz*heads*4 <= 3.5 GiB "
+                                           "(a_edge behind one buffer descriptor)";
 
-}  // namespace isplib
-
-using namespace isplib;
-
-extern "C" int isplib_gat_domain(int64_t rows_gathered, int64_t heads, int64_t d, int64_t ld) { return isplib_gat_serves(rows_gathered, heads, d, ld); }
-
-extern "C" int isplib_gat_csr_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb, const int64_t *pntre,
-                                  const float *a_dst, const float *y, int64_t ldy, const float *a_src, int64_t heads, float negative_slope,
-                                  float *z, int64_t ldz, float *lse, void *stream) {
-   const char *entry = "isplib_gat_csr_hip";
+// The three entries, with and without the per-edge term (edge: a_edge [nnz, heads]; csr2csc for the columns; d_a_edge may be NULL).
+static int gat_forward(const char *entry, bool edge, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                       const int64_t *pntre, const float *a_dst, const float *y, int64_t ldy, const float *a_src, const float *a_edge,
+                       int64_t heads, float negative_slope, float *z, int64_t ldz, float *lse, void *stream) {
    clear_error();
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
    if (m == 0 || k == 0) return ISPLIB_SUCCESS;
-   if (!pntrb || !pntre || !a_dst || !z || !lse || (nnz > 0 && (!indx || !y || !a_src))) return fail(ISPLIB_FAIL, entry, "null operand");
+   if (!pntrb || !pntre || !a_dst || !z || !lse || (nnz > 0 && (!indx || !y || !a_src || (edge && !a_edge))))
+      return fail(ISPLIB_FAIL, entry, "null operand");
    if (ldz < k) return fail(ISPLIB_FAIL, entry, "leading dimension smaller than k");
    if (heads >= 1 && k % heads != 0) return fail(ISPLIB_FAIL, entry, "k is not a multiple of heads");
    if (heads < 1 || !isplib_gat_serves(n, heads, k / heads, ldy)) return fail(ISPLIB_NO_OPT_IMPL, entry, GAT_DOMAIN);
+   if (edge && !isplib_gat_edge_serves(nnz, heads)) return fail(ISPLIB_NO_OPT_IMPL, entry, GAT_EDGE_DOMAIN);
    GatArgs a = {};
    a.rows = m; a.k = k; a.indx = indx; a.pntrb = pntrb; a.pntre = pntre; a.ns = negative_slope;
    gat_heads(a, heads, k / heads);
@@ -477,22 +543,23 @@ extern "C" int isplib_gat_csr_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, 
    a.out = z; a.ldout = ldz; a.hout = lse;
    a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? gat_extent(n, k, ldy) : 0u;
    a.t0 = a_src; a.tbytes = nnz > 0 ? gat_extent(n, heads, heads) : 0u;
-   return gat_by_width(GAT_FW, a, entry, (hipStream_t)stream);
+   a.edge = edge ? a_edge : nullptr;
+   return gat_by_width(GAT_FW, a, edge, entry, (hipStream_t)stream);
 }
 
-extern "C" int isplib_gat_bw_rows_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
-                                      const int64_t *pntre, const float *a_dst, const float *y, int64_t ldy, const float *a_src, int64_t heads,
-                                      float negative_slope, const float *g, int64_t ldg, const float *z, int64_t ldz, const float *lse,
-                                      float *d_a_dst, float *dsum, void *stream) {
-   const char *entry = "isplib_gat_bw_rows_hip";
+static int gat_backward_rows(const char *entry, bool edge, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx,
+                             const int64_t *pntrb, const int64_t *pntre, const float *a_dst, const float *y, int64_t ldy, const float *a_src,
+                             const float *a_edge, int64_t heads, float negative_slope, const float *g, int64_t ldg, const float *z,
+                             int64_t ldz, const float *lse, float *d_a_dst, float *dsum, float *d_a_edge, void *stream) {
    clear_error();
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
    if (m == 0 || k == 0) return ISPLIB_SUCCESS;
-   if (!pntrb || !pntre || !a_dst || !g || !z || !lse || !d_a_dst || !dsum || (nnz > 0 && (!indx || !y || !a_src)))
+   if (!pntrb || !pntre || !a_dst || !g || !z || !lse || !d_a_dst || !dsum || (nnz > 0 && (!indx || !y || !a_src || (edge && !a_edge))))
       return fail(ISPLIB_FAIL, entry, "null operand");
    if (ldg < k || ldz < k) return fail(ISPLIB_FAIL, entry, "leading dimension smaller than k");
    if (heads >= 1 && k % heads != 0) return fail(ISPLIB_FAIL, entry, "k is not a multiple of heads");
    if (heads < 1 || !isplib_gat_serves(n, heads, k / heads, ldy)) return fail(ISPLIB_NO_OPT_IMPL, entry, GAT_DOMAIN);
+   if (edge && !isplib_gat_edge_serves(nnz, heads)) return fail(ISPLIB_NO_OPT_IMPL, entry, GAT_EDGE_DOMAIN);
    GatArgs a = {};
    a.rows = m; a.k = k; a.indx = indx; a.pntrb = pntrb; a.pntre = pntre; a.ns = negative_slope;
    gat_heads(a, heads, k / heads);
@@ -500,22 +567,24 @@ extern "C" int isplib_gat_bw_rows_hip(int64_t m, int64_t n, int64_t k, int64_t n
    a.hout = d_a_dst; a.hout2 = dsum;
    a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? gat_extent(n, k, ldy) : 0u;
    a.t0 = a_src; a.tbytes = nnz > 0 ? gat_extent(n, heads, heads) : 0u;
-   return gat_by_width(GAT_BW_ROWS, a, entry, (hipStream_t)stream);
+   a.edge = edge ? a_edge : nullptr; a.dedge = edge ? d_a_edge : nullptr;
+   return gat_by_width(GAT_BW_ROWS, a, edge, entry, (hipStream_t)stream);
 }
 
-extern "C" int isplib_gat_bw_cols_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t, const int64_t *colb,
-                                      const int64_t *cole, const float *a_dst, const float *y, int64_t ldy, const float *a_src, int64_t heads,
-                                      float negative_slope, const float *g, int64_t ldg, const float *lse, const float *dsum, float *dy,
-                                      int64_t lddy, float *d_a_src, void *stream) {
-   const char *entry = "isplib_gat_bw_cols_hip";
+static int gat_backward_cols(const char *entry, bool edge, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t,
+                             const int64_t *colb, const int64_t *cole, const int64_t *csr2csc, const float *a_dst, const float *y, int64_t ldy,
+                             const float *a_src, const float *a_edge, int64_t heads, float negative_slope, const float *g, int64_t ldg,
+                             const float *lse, const float *dsum, float *dy, int64_t lddy, float *d_a_src, void *stream) {
    clear_error();
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
    if (n == 0 || k == 0) return ISPLIB_SUCCESS;
-   if (!colb || !cole || !y || !a_src || !dy || !d_a_src || (nnz > 0 && (!row_t || !a_dst || !g || !lse || !dsum)))
+   if (!colb || !cole || !y || !a_src || !dy || !d_a_src ||
+       (nnz > 0 && (!row_t || !a_dst || !g || !lse || !dsum || (edge && (!csr2csc || !a_edge)))))
       return fail(ISPLIB_FAIL, entry, "null operand");
    if (ldy < k || lddy < k) return fail(ISPLIB_FAIL, entry, "leading dimension smaller than k");
    if (heads >= 1 && k % heads != 0) return fail(ISPLIB_FAIL, entry, "k is not a multiple of heads");
    if (heads < 1 || !isplib_gat_serves(m, heads, k / heads, ldg)) return fail(ISPLIB_NO_OPT_IMPL, entry, GAT_DOMAIN);
+   if (edge && !isplib_gat_edge_serves(nnz, heads)) return fail(ISPLIB_NO_OPT_IMPL, entry, GAT_EDGE_DOMAIN);
    GatArgs a = {};
    a.rows = n; a.k = k; a.indx = row_t; a.pntrb = colb; a.pntre = cole; a.ns = negative_slope;
    gat_heads(a, heads, k / heads);
@@ -523,5 +592,66 @@ extern "C" int isplib_gat_bw_cols_hip(int64_t m, int64_t n, int64_t k, int64_t n
    a.out = dy; a.ldout = lddy; a.hout = d_a_src;
    a.y = g; a.ldy = ldg; a.ybytes = nnz > 0 ? gat_extent(m, k, ldg) : 0u;
    a.t0 = a_dst; a.t1 = lse; a.t2 = dsum; a.tbytes = nnz > 0 ? gat_extent(m, heads, heads) : 0u;
-   return gat_by_width(GAT_BW_COLS, a, entry, (hipStream_t)stream);
+   if (edge) {
+      a.edge = a_edge; a.epos = csr2csc; a.ebytes = nnz > 0 ? gat_extent(nnz, heads, heads) : 0u;
+   }
+   return gat_by_width(GAT_BW_COLS, a, edge, entry, (hipStream_t)stream);
 }
+
+}  // namespace isplib
+
+using namespace isplib;
+
+extern "C" int isplib_gat_domain(int64_t rows_gathered, int64_t heads, int64_t d, int64_t ld) { return isplib_gat_serves(rows_gathered, heads, d, ld); }
+
+extern "C" int isplib_gat_edge_domain(int64_t nnz, int64_t heads) { return isplib_gat_edge_serves(nnz, heads); }
+
+extern "C" int isplib_gat_csr_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb, const int64_t *pntre,
+                                  const float *a_dst, const float *y, int64_t ldy, const float *a_src, int64_t heads, float negative_slope,
+                                  float *z, int64_t ldz, float *lse, void *stream) {
+   return gat_forward("isplib_gat_csr_hip", false, m, n, k, nnz, indx, pntrb, pntre, a_dst, y, ldy, a_src, nullptr, heads, negative_slope, z, ldz,
+                      lse, stream);
+}
+
+extern "C" int isplib_gat_bw_rows_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                                      const int64_t *pntre, const float *a_dst, const float *y, int64_t ldy, const float *a_src, int64_t heads,
+                                      float negative_slope, const float *g, int64_t ldg, const float *z, int64_t ldz, const float *lse,
+                                      float *d_a_dst, float *dsum, void *stream) {
+   return gat_backward_rows("isplib_gat_bw_rows_hip", false, m, n, k, nnz, indx, pntrb, pntre, a_dst, y, ldy, a_src, nullptr, heads, negative_slope,
+                            g, ldg, z, ldz, lse, d_a_dst, dsum, nullptr, stream);
+}
+
+extern "C" int isplib_gat_bw_cols_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t, const int64_t *colb,
+                                      const int64_t *cole, const float *a_dst, const float *y, int64_t ldy, const float *a_src, int64_t heads,
+                                      float negative_slope, const float *g, int64_t ldg, const float *lse, const float *dsum, float *dy,
+                                      int64_t lddy, float *d_a_src, void *stream) {
+   return gat_backward_cols("isplib_gat_bw_cols_hip", false, m, n, k, nnz, row_t, colb, cole, nullptr, a_dst, y, ldy, a_src, nullptr, heads,
+                            negative_slope, g, ldg, lse, dsum, dy, lddy, d_a_src, stream);
+}
+
+extern "C" int isplib_gat_edge_csr_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                                       const int64_t *pntre, const float *a_dst, const float *y, int64_t ldy, const float *a_src,
+                                       const float *a_edge, int64_t heads, float negative_slope, float *z, int64_t ldz, float *lse,
+                                       void *stream) {
+   return gat_forward("isplib_gat_edge_csr_hip", true, m, n, k, nnz, indx, pntrb, pntre, a_dst, y, ldy, a_src, a_edge, heads, negative_slope, z,
+                      ldz, lse, stream);
+}
+
+extern "C" int isplib_gat_edge_bw_rows_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                                           const int64_t *pntre, const float *a_dst, const float *y, int64_t ldy, const float *a_src,
+                                           const float *a_edge, int64_t heads, float negative_slope, const float *g, int64_t ldg,
+                                           const float *z, int64_t ldz, const float *lse, float *d_a_dst, float *dsum, void *stream,
+                                           float *d_a_edge) {
+   return gat_backward_rows("isplib_gat_edge_bw_rows_hip", true, m, n, k, nnz, indx, pntrb, pntre, a_dst, y, ldy, a_src, a_edge, heads,
+                            negative_slope, g, ldg, z, ldz, lse, d_a_dst, dsum, d_a_edge, stream);
+}
+
+extern "C" int isplib_gat_edge_bw_cols_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t, const int64_t *colb,
+                                           const int64_t *cole, const int64_t *csr2csc, const float *a_dst, const float *y, int64_t ldy,
+                                           const float *a_src, const float *a_edge, int64_t heads, float negative_slope, const float *g,
+                                           int64_t ldg, const float *lse, const float *dsum, float *dy, int64_t lddy, float *d_a_src,
+                                           void *stream) {
+   return gat_backward_cols("isplib_gat_edge_bw_cols_hip", true, m, n, k, nnz, row_t, colb, cole, csr2csc, a_dst, y, ldy, a_src, a_edge, heads,
+                            negative_slope, g, ldg, lse, dsum, dy, lddy, d_a_src, stream);
+}
+

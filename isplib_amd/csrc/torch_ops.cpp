@@ -1383,6 +1383,121 @@ Tensor gat_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor y
    return GatSpmm::apply(rowptr, col, colptr, row_t, y, a_dst, a_src, heads, negative_slope)[0];
 }
 
+// ---- the GAT aggregation with a per-edge score term (isplib_gat_edge_*_hip) ----------
+// u_e = (a_dst[i,h] + a_src[j,h]) + a_edge[e,h], a_edge [nnz, heads] in CSR position order.  Saved for backward: what GatSpmm saves, plus
+// a_edge and csr2csc (the columns kernel gathers a_edge by CSR position).  d a_edge [nnz, heads] is allocated, and written by the rows
+// kernel, only when a_edge asks for a gradient.  The domain of everything the backward needs is checked in the forward.
+class GatEdgeSpmm : public torch::autograd::Function<GatEdgeSpmm> {
+ public:
+   static variable_list forward(AutogradContext *ctx, Variable rowptr, Variable col, Variable colptr, Variable row_t, Variable csr2csc,
+                                Variable y, Variable a_dst, Variable a_src, Variable a_edge, int64_t heads, double negative_slope) {
+      check_index(rowptr, "rowptr"); check_index(col, "col"); check_index(colptr, "colptr"); check_index(row_t, "row_t");
+      check_index(csr2csc, "csr2csc");
+      TORCH_CHECK(y.defined() && y.dim() == 2, "isplib: gat_edge_spmm needs a 2-D `y` [N, heads * d]");
+      OpTimer timer("FUSEDMM_GAT_EDGE_FW", y);
+      const int64_t M = rowptr.numel() - 1, N = colptr.numel() - 1, K = y.size(1), nnz = col.numel();
+      TORCH_CHECK(M >= 0 && N >= 0 && row_t.numel() == nnz && csr2csc.numel() == nnz,
+                  "isplib: gat_edge_spmm: `rowptr` / `colptr` need one entry more than rows / columns, `row_t` and `csr2csc` one entry per "
+                  "stored entry (", nnz, "), got ", row_t.numel(), " and ", csr2csc.numel());
+      TORCH_CHECK(heads >= 1 && K % heads == 0, "isplib: gat_edge_spmm: the width of `y` (", K, ") must be heads * d, got heads = ", heads);
+      const AttnOperand yo = gat_operand(y, "y", N, K);
+      TORCH_CHECK(a_dst.defined() && a_src.defined() && a_edge.defined(),
+                  "isplib: gat_edge_spmm needs `a_dst` [M, heads], `a_src` [N, heads] and `a_edge` [nnz, heads]");
+      const Tensor ad = gat_table(a_dst, "a_dst", M, heads), as = gat_table(a_src, "a_src", N, heads);
+      check_float(a_edge, "a_edge");
+      TORCH_CHECK(a_edge.dim() == 2 && a_edge.size(0) == nnz && a_edge.size(1) == heads, "isplib: gat_edge_spmm: `a_edge` must be [", nnz, ", ",
+                  heads, "] (one row per stored entry, in the order of `col`), got ", a_edge.sizes());
+      const Tensor ae = a_edge.contiguous();
+      for (const Tensor *t : {&rowptr, &col, &colptr, &row_t, &csr2csc, &a_dst, &a_src, &a_edge})
+         TORCH_CHECK(t->device() == y.device(), "isplib: gat_edge_spmm: every operand must be on y's device");
+      TORCH_CHECK(K == 0 || isplib_gat_serves(N, heads, K / heads, yo.ld), "isplib: gat_edge_spmm: outside isplib_gat_serves (heads * d <= ",
+                  ISPLIB_GAT_K_MAX, ", heads == 1 or d a power of two >= 4, N < 2^31, N * pitch * 4 <= 3.5 GiB): N = ", N, ", heads = ", heads,
+                  ", d = ", K / heads, ", pitch = ", yo.ld);
+      TORCH_CHECK(K == 0 || isplib_gat_serves(M, heads, K / heads, K),
+                  "isplib: gat_edge_spmm: outside isplib_gat_serves for the gathered rows of the gradient: M = ", M, ", K = ", K);
+      TORCH_CHECK(isplib_gat_edge_serves(nnz, heads), "isplib: gat_edge_spmm: outside isplib_gat_edge_serves (nnz < 2^31, nnz * heads * 4 <= "
+                  "3.5 GiB, `a_edge` behind one buffer descriptor): nnz = ", nnz, ", heads = ", heads,
+                  " -- pass fewer heads per call, on column views of `y`");
+      c10::DeviceGuard guard(y.device());
+      const Tensor rp = rowptr.contiguous(), cl = col.contiguous();
+      Tensor z = at::empty({M, K}, y.options()), lse = at::empty({M, heads}, y.options());
+      if (M > 0 && K > 0) {
+         const int st = isplib_gat_edge_csr_hip(M, N, K, nnz, cl.data_ptr<int64_t>(), rp.data_ptr<int64_t>(), rp.data_ptr<int64_t>() + 1,
+                                                ad.data_ptr<float>(), nnz > 0 ? yo.t.data_ptr<float>() : nullptr, yo.ld,
+                                                nnz > 0 ? as.data_ptr<float>() : nullptr, nnz > 0 ? ae.data_ptr<float>() : nullptr, heads,
+                                                (float)negative_slope, z.data_ptr<float>(), K, lse.data_ptr<float>(), current_stream(y));
+         check_status(st, "isplib_gat_edge_csr_hip");
+      } else if (M > 0) {
+         lse.fill_(-std::numeric_limits<float>::infinity());
+      }
+      ctx->saved_data["heads"] = heads;
+      ctx->saved_data["negative_slope"] = negative_slope;
+      ctx->save_for_backward({rp, cl, colptr, row_t, y, a_dst, a_src, z, lse, a_edge, csr2csc});
+      return {z};
+   }
+
+   static variable_list backward(AutogradContext *ctx, variable_list grad_outs) {
+      OpTimer timer("FUSEDMM_GAT_EDGE_BW", grad_outs[0]);
+      const bool need_y = ctx->needs_input_grad(5), need_dst = ctx->needs_input_grad(6), need_src = ctx->needs_input_grad(7),
+                 need_edge = ctx->needs_input_grad(8);
+      auto grad_y = Variable(), grad_dst = Variable(), grad_src = Variable(), grad_edge = Variable();
+      if (need_y || need_dst || need_src || need_edge) {
+         auto saved = ctx->get_saved_variables();
+         auto rp = saved[0], cl = saved[1], colptr = saved[2].contiguous(), row_t = saved[3].contiguous(), y = saved[4], z = saved[7], lse = saved[8];
+         const Tensor csr2csc = saved[10].contiguous();
+         const int64_t heads = ctx->saved_data["heads"].toInt();
+         const float ns = (float)ctx->saved_data["negative_slope"].toDouble();
+         const int64_t M = rp.numel() - 1, N = colptr.numel() - 1, K = y.size(1), nnz = cl.numel();
+         const AttnOperand yo = gat_operand(y, "y", N, K);
+         const Tensor ad = gat_table(saved[5], "a_dst", M, heads), as = gat_table(saved[6], "a_src", N, heads), ae = saved[9].contiguous();
+         const AttnOperand go = gat_operand(grad_outs[0].to(at::kFloat), "grad_out", M, K);
+         c10::DeviceGuard guard(y.device());
+         // the rows kernel always runs (D feeds the columns kernel); it gets d a_edge only when a_edge asks -- no [nnz, H] tensor otherwise
+         Tensor dadst = at::empty({M, heads}, y.options()), dsum = at::empty({M, heads}, y.options());
+         Tensor dedge = need_edge ? at::empty({nnz, heads}, y.options()) : Tensor();
+         if (M > 0 && K > 0) {
+            const int st = isplib_gat_edge_bw_rows_hip(M, N, K, nnz, cl.data_ptr<int64_t>(), rp.data_ptr<int64_t>(), rp.data_ptr<int64_t>() + 1,
+                                                       ad.data_ptr<float>(), nnz > 0 ? yo.t.data_ptr<float>() : nullptr, yo.ld,
+                                                       nnz > 0 ? as.data_ptr<float>() : nullptr, nnz > 0 ? ae.data_ptr<float>() : nullptr, heads,
+                                                       ns, go.t.data_ptr<float>(), go.ld, z.data_ptr<float>(), K, lse.data_ptr<float>(),
+                                                       dadst.data_ptr<float>(), dsum.data_ptr<float>(), current_stream(y),
+                                                       need_edge && nnz > 0 ? dedge.data_ptr<float>() : nullptr);
+            check_status(st, "isplib_gat_edge_bw_rows_hip");
+         } else if (M > 0) {
+            dadst.zero_();
+            if (need_edge) dedge.zero_();                // K == 0: heads * d with d == 0 -- every du_e is 0
+         }
+         if (need_dst) grad_dst = dadst;
+         if (need_edge) grad_edge = dedge;
+         if (need_y || need_src) {
+            TORCH_CHECK(K == 0 || isplib_gat_serves(M, heads, K / heads, go.ld),
+                        "isplib: gat_edge_spmm backward: outside isplib_gat_serves for the gathered rows of the gradient: M = ", M, ", K = ", K);
+            Tensor dy = at::empty({N, K}, y.options()), dasrc = at::empty({N, heads}, y.options());
+            if (N > 0 && K > 0) {
+               const int st = isplib_gat_edge_bw_cols_hip(M, N, K, nnz, row_t.data_ptr<int64_t>(), colptr.data_ptr<int64_t>(),
+                                                          colptr.data_ptr<int64_t>() + 1, nnz > 0 ? csr2csc.data_ptr<int64_t>() : nullptr,
+                                                          nnz > 0 ? ad.data_ptr<float>() : nullptr, yo.t.data_ptr<float>(), yo.ld,
+                                                          as.data_ptr<float>(), nnz > 0 ? ae.data_ptr<float>() : nullptr, heads, ns,
+                                                          nnz > 0 ? go.t.data_ptr<float>() : nullptr, go.ld, lse.data_ptr<float>(),
+                                                          dsum.data_ptr<float>(), dy.data_ptr<float>(), K, dasrc.data_ptr<float>(),
+                                                          current_stream(y));
+               check_status(st, "isplib_gat_edge_bw_cols_hip");
+            } else if (N > 0) {
+               dasrc.zero_();
+            }
+            if (need_y) grad_y = dy;
+            if (need_src) grad_src = dasrc;
+         }
+      }
+      return {Variable(), Variable(), Variable(), Variable(), Variable(), grad_y, grad_dst, grad_src, grad_edge, Variable(), Variable()};
+   }
+};
+
+Tensor gat_edge_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor csr2csc, Tensor y, Tensor a_dst, Tensor a_src,
+                     Tensor a_edge, int64_t heads, double negative_slope) {
+   return GatEdgeSpmm::apply(rowptr, col, colptr, row_t, csr2csc, y, a_dst, a_src, a_edge, heads, negative_slope)[0];
+}
+
 // ---- the same aggregation for bf16 / fp16 operands (isplib_attention16_*_hip) ----------
 // x and y go in as they lie, z / dx / dy come back in their dtype, lse and D stay fp32: no fp32 [*, K] tensor in either direction.  Saved
 // for backward: the structure, x, y and lse -- NOT z: the rows kernel forms D_i from the row's edges (the rounded z would cost every
@@ -1897,6 +2012,8 @@ TORCH_LIBRARY(isplib, m) {
    m.def("attention_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor x, Tensor y, float scale) -> Tensor", &attention_spmm);
    m.def("gat_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor y, Tensor a_dst, Tensor a_src, int heads, float negative_slope) -> Tensor",
          &gat_spmm);
+   m.def("gat_edge_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor csr2csc, Tensor y, Tensor a_dst, Tensor a_src, Tensor a_edge, int heads, float negative_slope) -> Tensor",
+         &gat_edge_spmm);
    m.def("attention_spmm16(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor x, Tensor y, float scale) -> Tensor", &attention_spmm16);
    m.def("gat_spmm16(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor y, Tensor a_dst, Tensor a_src, int heads, float negative_slope) -> Tensor",
          &gat_spmm16);

@@ -739,7 +739,8 @@ def attention_matmul(src, x: torch.Tensor, y: Optional[torch.Tensor] = None, sca
     return torch.ops.isplib.attention_spmm(st._rowptr, st._col, st.colptr(), st.row_t(), x, y, p)
 
 
-def gat_matmul(src, y: torch.Tensor, a_dst: torch.Tensor, a_src: torch.Tensor, heads: int = 1, negative_slope: float = 0.2) -> torch.Tensor:
+def gat_matmul(src, y: torch.Tensor, a_dst: torch.Tensor, a_src: torch.Tensor, heads: int = 1, negative_slope: float = 0.2,
+               a_edge: Optional[torch.Tensor] = None) -> torch.Tensor:
     """GAT attention aggregation over the stored entries of `src`, all heads in one launch (include/isplib_hip.h, isplib_gat_csr_hip):
     ``z[i, head h] = sum_j softmax_j(leaky_relu(a_dst[i, h] + a_src[j, h])) y[j, head h]`` over the entries (i, j) of row i -- the
     aggregation of GATConv, with its autograd backward in `y`, `a_dst` and `a_src` (torch.ops.isplib.gat_spmm).  `y` [N, heads * d]
@@ -753,7 +754,19 @@ def gat_matmul(src, y: torch.Tensor, a_dst: torch.Tensor, a_src: torch.Tensor, h
     (y with its rows, the gradient with M rows at pitch K), else `y.float()` -> this function -> `.to(dtype)`, which raises only what the
     fp32 call raises.  Each score may then be float32 or of y's dtype (a 16-bit score is widened by `.float()`, which is exact, and its
     gradient returns in its own dtype through that cast); the result and y's gradient have y's dtype.  fp32 calls do not read the
-    variable."""
+    variable.
+    `a_edge` (GATConv's ``edge_dim``; None: the call above, unchanged) adds a per-edge, per-head score term with its gradient
+    (torch.ops.isplib.gat_edge_spmm): ``u = (a_dst[i, h] + a_src[j, h]) + a_edge[e, h]`` before the leaky_relu -- two fp32 adds in this
+    order, the slope branch taken on that fp32 u.  It is a float32 GPU tensor [nnz, heads] ([nnz] with one head; a non-contiguous one
+    is copied) with ONE ROW PER STORED ENTRY IN THE STORAGE'S ENTRY ORDER: the order of ``storage.col()`` / ``storage.value()``, i.e.
+    CSR positions (sorted by row; inside a row, the order the entries were stored in).  Duplicates (i, j) are separate entries with a
+    row each.  A caller who built the matrix from unsorted COO passes ``value=torch.arange(nnz)`` once: ``storage.value()`` is then
+    the COO index of every entry, by which the edge attributes are permuted.  Outside isplib_gat_edge_serves (nnz < 2^31 and
+    nnz * heads * 4 <= 3.5 GiB) the call raises ValueError: pass fewer heads per call, on column views of `y`.  With a 16-bit `y`
+    and ISPLIB_HALF_GAT set (to any value) the call takes the conversion route -- there is no 16-bit edge kernel; `a_edge` may then
+    be float32 or of y's dtype."""
+    if a_edge is not None:
+        return _gat_edge_matmul(src, y, a_dst, a_src, a_edge, heads, negative_slope)
     from . import cabi
     half = isinstance(y, torch.Tensor) and y.dtype in HALF_DTYPES and os.environ.get("ISPLIB_HALF_GAT") is not None
     for name, t in (("y", y), ("a_dst", a_dst), ("a_src", a_src)):
@@ -797,6 +810,62 @@ def gat_matmul(src, y: torch.Tensor, a_dst: torch.Tensor, a_src: torch.Tensor, h
     if a_dst.device != y.device or a_src.device != y.device or st._rowptr.device != y.device:
         raise ValueError("isplib_amd: `y`, `a_dst`, `a_src` and the sparse matrix must be on one device")
     return torch.ops.isplib.gat_spmm(st._rowptr, st._col, st.colptr(), st.row_t(), y, a_dst, a_src, heads, float(negative_slope))
+
+
+def _gat_edge_matmul(src, y, a_dst, a_src, a_edge, heads, negative_slope):
+    """gat_matmul with the per-edge score term: every check of gat_matmul, `a_edge` and its domain, all before anything touches a
+    device; then torch.ops.isplib.gat_edge_spmm.  There is no fallback route."""
+    from . import cabi
+    half = isinstance(y, torch.Tensor) and y.dtype in HALF_DTYPES and os.environ.get("ISPLIB_HALF_GAT") is not None
+    for name, t in (("y", y), ("a_dst", a_dst), ("a_src", a_src), ("a_edge", a_edge)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"isplib_amd: `{name}` must be a tensor, got {type(t).__name__}")
+        if half and name != "y" and t.dtype not in (torch.float32, y.dtype):
+            raise TypeError(f"isplib_amd: `{name}` must be float32 or of `y`'s dtype ({y.dtype}), got {t.dtype}")
+        if not half and t.dtype != torch.float32:
+            raise TypeError(f"isplib_amd: `{name}` must be float32, got {t.dtype} (the attention operator is fp32 only)")
+    if half:        # the conversion route (no 16-bit edge kernel): .float() is exact, and every gradient returns in its own dtype through the cast
+        return _gat_edge_matmul(src, y.float(), a_dst.float(), a_src.float(), a_edge.float(), heads, negative_slope).to(y.dtype)
+    if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
+        raise ValueError(f"isplib_amd: `heads` must be a positive int, got {heads!r}")
+    if y.dim() != 2:
+        raise ValueError(f"isplib_amd: `y` must be 2-D [rows, heads * d], got shape {tuple(y.shape)}")
+    st = _storage_of(src, y)
+    m_rows, n_cols, nnz = st._rowptr.numel() - 1, st._sparse_sizes[1], st._col.numel()
+    if y.size(0) != n_cols:
+        raise ValueError(f"isplib_amd: `y` must have one row per column of the sparse matrix ({n_cols}), got {y.size(0)}")
+    k = y.size(1)
+    if k % heads:
+        raise ValueError(f"isplib_amd: the width of `y` ({k}) must be heads * d, got heads = {heads}")
+    d = k // heads
+    if heads == 1:
+        a_dst = a_dst.unsqueeze(1) if a_dst.dim() == 1 else a_dst
+        a_src = a_src.unsqueeze(1) if a_src.dim() == 1 else a_src
+        a_edge = a_edge.unsqueeze(1) if a_edge.dim() == 1 else a_edge
+    for name, t, rows, what in (("a_dst", a_dst, m_rows, "row"), ("a_src", a_src, n_cols, "column"), ("a_edge", a_edge, nnz, "stored entry")):
+        if t.dim() != 2 or t.size(0) != rows or t.size(1) != heads:
+            raise ValueError(f"isplib_amd: `{name}` must be [{rows}, {heads}] (one entry per {what} of the sparse matrix and head), got "
+                             f"shape {tuple(t.shape)}")
+    if not (1 <= k <= cabi.GAT_K_MAX) or (heads > 1 and (d < 4 or d & (d - 1))):
+        raise ValueError(f"isplib_amd: gat_matmul serves 1 <= heads * d <= {cabi.GAT_K_MAX} with heads == 1 or d a power of two >= 4 (a head "
+                         f"is an aligned group of lanes), got heads = {heads}, d = {d}")
+    pitch = y.stride(0) if n_cols > 1 and y.stride(1) == 1 and y.stride(0) >= k else k
+    for rows, ld, what in ((n_cols, pitch, "`y`"), (m_rows, k, "the gradient of the result")):   # y: forward, rows; g: the columns kernel
+        if not cabi.gat_serves(rows, heads, d, ld):
+            raise ValueError(f"isplib_amd: {what} ({rows} rows at a pitch of {ld} floats) is outside the GAT kernels' domain: "
+                             f"rows < 2^31 and rows * pitch * 4 <= {cabi.DENSE_BYTES_MAX} bytes (3.5 GiB, one buffer descriptor)")
+    if not cabi.gat_edge_serves(nnz, heads):
+        raise ValueError(f"isplib_amd: `a_edge` ({nnz} stored entries x {heads} heads) is outside the GAT edge kernels' domain "
+                         f"(isplib_gat_edge_serves): nnz < 2^31 and nnz * heads * 4 <= {cabi.DENSE_BYTES_MAX} bytes (3.5 GiB, one buffer "
+                         f"descriptor); pass fewer heads per call, on column views of `y`")
+    if not y.is_cuda or not a_dst.is_cuda or not a_src.is_cuda or not a_edge.is_cuda:
+        raise TypeError("isplib_amd: `y`, `a_dst`, `a_src` and `a_edge` must be GPU tensors -- there is no CPU path")
+    if a_dst.device != y.device or a_src.device != y.device or a_edge.device != y.device or st._rowptr.device != y.device:
+        raise ValueError("isplib_amd: `y`, `a_dst`, `a_src`, `a_edge` and the sparse matrix must be on one device")
+    if not a_edge.is_contiguous():
+        a_edge = a_edge.contiguous()
+    return torch.ops.isplib.gat_edge_spmm(st._rowptr, st._col, st.colptr(), st.row_t(), st.csr2csc(), y, a_dst, a_src, a_edge, heads,
+                                          float(negative_slope))
 
 
 def gatv2_matmul(src, x: torch.Tensor, att: torch.Tensor, y: Optional[torch.Tensor] = None, heads: int = 1,
