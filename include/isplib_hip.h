@@ -424,7 +424,50 @@ typedef struct isplib_stream_plan {
    const int32_t *perm;             /* [dev] n_steps*streams: CSR position of every word, -1 = padding (for re-gathering
                                        weights; the arg candidates of max / min); NULL in plans that do not carry it -- the
                                        sum / mean kernel never reads it */
+   const uint32_t *packed;          /* [dev] the PACKED WORD STREAM (below): isplib_stream_packed_dwords(plan) dwords, or NULL */
+   int32_t has_packed;              /* nonzero: `packed` holds every batch of `words`; 0: the plan has no packed stream (not
+                                       representable, not a 4-stream sum / mean plan, no room) and every call reads `words` */
 } isplib_stream_plan;
+/* PACKED WORD STREAM (profiles/stream_packed_words.txt).  A launch reads the plan's words from beyond the L2 once per
+ * 64-column panel, 4 bytes per entry; a word carries 4 bits of local row inside its slot and a column that, relative to its column
+ * slice, needs 13 bits.  4-stream sum / mean plans therefore carry a second, bit-packed copy of `words`, built from them by one device
+ * pass at plan build, which the sum / mean kernel decodes once per batch into the registers it loaded from `words` before -- the loop
+ * that consumes them, `words`, `vals`, `perm` and every other kernel are unchanged, and the decoded values ARE the words, padding
+ * included, so every sum has the bits it had.
+ * A BATCH is the 128 consecutive words of one wave that the kernel holds in its two batch registers: entry e of batch b of a wave is
+ * word b * 128 + e of the wave's stream = (step b * 32 + e / 4, slot e % 4); words past the end of the wave are padding.  A batch
+ * takes ISPLIB_STREAM_PACK_DWORDS = 76 dwords (304 bytes instead of 512), and batch b of wave w (w counted through the whole plan,
+ * its first step s0 = wave_step_off[w]) starts at dword ((s0 * 4) / 128 + w + b) * 76: the place follows from the wave's position
+ * alone, no table (a wave's ceil(nwords / 128) batches never reach the next wave's first; up to one batch per wave stays unused).
+ *   dwords 0..63   dword i: bits 0..12 the column of entry i, bits 13..25 the column of entry 64 + i, each relative to the first
+ *                  column of its DECODED slice (below); bits 26..29 the local row of entry i inside its slot (word >> 24 minus
+ *                  slot * 16); bit 30 / bit 31: the slice-advance flag of entry i / of entry 64 + i
+ *   dwords 64..71  the local rows of entries 64..127, 4 bits each: entry 64 + i, i = 4 t + slot, is nibble t % 8 of dword
+ *                  64 + slot * 2 + t / 8
+ *   dwords 72..75  one header per slot: bits 0..11 the slot's base slice (the true slice of its first entry of the batch), bits 12..17 the
+ *                  number of its entries (0..32, in step order) that are NOT padding -- a slot's padding words are the tail of its
+ *                  stream, they decode to the kernel's own padding word ((slot * 16) << 24 | n) and their other bits are 0
+ * The decoded slice of an entry is the header's slice plus the number of advance flags of its slot's entries up to and including
+ * itself; its column is slice * W + the 13-bit field, W = ceil(cols / slices) the plan's slice width.  The packer sets a flag
+ * whenever the entry's true slice is ahead of the decoded one, so the decoded slice follows the true one by at most one step per
+ * entry: where a slot's stream skips slices (rows with no entry in them) the decoded slice may lag, and the entry is representable
+ * while its column is still within 8,191 of the lagging slice's first column (narrow slices absorb any skip; with slices wider
+ * than 4,096 columns a skip inside a batch is not representable -- a batch's first entry always is, the header is free).
+ * Representable plans: streams == 4, rows_per_wave == 64 (16 rows per slot), W <= 8,192, slices <= 4,096, and every entry as above;
+ * any other plan gets packed == NULL, has_packed == 0 and runs as before.  isplib_stream_pack_hip is the packing pass for callers
+ * that build the plan's arrays themselves: `out` [dev] of isplib_stream_packed_dwords(plan) dwords (0: the geometry is not
+ * representable); *representable (host, out) = 0 where an entry is not, and then `out` must not be attached to the plan.  It
+ * synchronises `stream`.  The native builders call it themselves; isplib_stream_plan_free releases the array they attached.
+ * fusedMM_csr_stream_hip reads the packed stream when the plan carries one and ISPLIB_STREAM_PACK (auto | 0 | 1, read once)
+ * allows it: 0 never (the launch of a plan without one, exactly), 1 whenever the plan has one, auto (unset) from
+ * ISPLIB_STREAM_PACK_MIN_WORDS stored entries on (where the stream schedule is offered at all).  Staged panels and the levelled
+ * deal compose with it unchanged; the 16-bit-feature entry, max / min, FusedMM and the SDDMM over stream plans read `words`. */
+#define ISPLIB_STREAM_PACK_DWORDS 76
+#define ISPLIB_STREAM_PACK_COL_BITS 13
+#define ISPLIB_STREAM_PACK_MIN_WORDS (4 * 1048576)
+size_t isplib_stream_packed_dwords(const isplib_stream_plan *plan /*host*/);
+int  isplib_stream_pack_hip(const isplib_stream_plan *plan /*host*/, uint32_t *out /*[dev]*/, int64_t out_dwords,
+                            int *representable /*host, out*/, void *stream);
 /* Native plan builder (the same construction as isplib_amd/plan.py, on the device with rocPRIM sorts): allocates the
  * plan's device arrays -- release them with isplib_stream_plan_free -- and synchronises `stream` (twice: the sizes of
  * the plan are data dependent).  streams / slices / chunk: from isplib_suggest_stream; waves_per_gen <= 0: what

@@ -244,7 +244,7 @@ EXPORTS = (
     "isplib_sddmm_csr_tasks_hip", "fusedMM_csr_tasks_epilogue_hip", "fusedMM_csr_udef_hip", "fusedMM_csr_udef_tasks_hip", "isplib_pack_indices_hip",
     "isplib_suggest_slices", "isplib_graph_create", "isplib_graph_set_slices", "isplib_graph_set_values", "isplib_graph_spmm", "isplib_graph_spmm_backward",
     "isplib_graph_destroy", "isplib_suggest_slices_whole_rows", "isplib_graph_sddmm",
-    "fusedMM_csr_stream_hip", "isplib_spmm_stream_workspace_bytes", "isplib_spmm_stream_geometry", "isplib_suggest_stream", "isplib_suggest_stream_weighted", "isplib_stream_plan_build_hip", "isplib_stream_plan_build_caps_hip", "isplib_stream_capacities_hip", "isplib_stream_plan_build_minmax_hip", "fusedMM_csr_stream_minmax_hip", "isplib_spmm_stream_minmax_geometry", "isplib_suggest_stream_minmax", "isplib_spmm_stream_minmax_workspace_bytes", "isplib_stream_plan_set_values_hip", "isplib_stream_plan_free", "isplib_spmm_minmax_bw_det_hip", "isplib_spmm_minmax_bw_workspace_bytes", "isplib_scatter_rows_det_hip",
+    "fusedMM_csr_stream_hip", "isplib_spmm_stream_workspace_bytes", "isplib_spmm_stream_geometry", "isplib_suggest_stream", "isplib_suggest_stream_weighted", "isplib_stream_plan_build_hip", "isplib_stream_plan_build_caps_hip", "isplib_stream_capacities_hip", "isplib_stream_plan_build_minmax_hip", "fusedMM_csr_stream_minmax_hip", "isplib_spmm_stream_minmax_geometry", "isplib_suggest_stream_minmax", "isplib_spmm_stream_minmax_workspace_bytes", "isplib_stream_plan_set_values_hip", "isplib_stream_plan_free", "isplib_stream_packed_dwords", "isplib_stream_pack_hip", "isplib_spmm_minmax_bw_det_hip", "isplib_spmm_minmax_bw_workspace_bytes", "isplib_scatter_rows_det_hip",
     "isplib_minmax_bw_bucket_workspace_bytes", "isplib_minmax_bw_bucket_hip", "isplib_scatter_keys_workspace_bytes", "isplib_scatter_keys_det_hip",
     "isplib_fusedmm_stream_geometry", "isplib_suggest_fusedmm_stream", "isplib_stream_plan_build_fusedmm_hip", "fusedMM_csr_udef_stream_hip",
     "isplib_row_scale_hip", "isplib_masked_scale_colsum_hip", "isplib_masked_scale_colsum_workspace_bytes",
@@ -305,7 +305,8 @@ class StreamPlanStruct(ctypes.Structure):  # isplib_stream_plan
                 ("chunk", ctypes.c_int32), ("n_steps", ctypes.c_int64), ("n_parts", ctypes.c_int64), ("n_hub", ctypes.c_int64),
                 ("words", ctypes.c_void_p), ("vals", ctypes.c_void_p), ("wave_step_off", ctypes.c_void_p),
                 ("wave_row", ctypes.c_void_p), ("wave_part", ctypes.c_void_p),
-                ("hub_row", ctypes.c_void_p), ("hub_off", ctypes.c_void_p), ("perm", ctypes.c_void_p)]
+                ("hub_row", ctypes.c_void_p), ("hub_off", ctypes.c_void_p), ("perm", ctypes.c_void_p),
+                ("packed", ctypes.c_void_p), ("has_packed", ctypes.c_int32)]      # the packed word stream (None / 0: none)
 
 
 class HybridPlanStruct(ctypes.Structure):  # isplib_hybrid_plan
@@ -439,6 +440,14 @@ def lib() -> ctypes.CDLL:
                                                         _vp, ctypes.POINTER(StreamPlanStruct), _vp]
         L.isplib_stream_capacities_hip.restype = ctypes.c_int
         L.isplib_stream_capacities_hip.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, _vp, ctypes.POINTER(ctypes.c_int), _vp]
+        L.isplib_stream_packed_dwords.restype = ctypes.c_size_t
+        L.isplib_stream_packed_dwords.argtypes = [ctypes.POINTER(StreamPlanStruct)]
+        L.isplib_stream_pack_hip.restype = ctypes.c_int
+        L.isplib_stream_pack_hip.argtypes = [ctypes.POINTER(StreamPlanStruct), _vp, _i64, ctypes.POINTER(ctypes.c_int), _vp]
+        L.isplib_stream_pack_set.restype = ctypes.c_int
+        L.isplib_stream_pack_set.argtypes = [ctypes.c_int]
+        L.isplib_stream_pack_last.restype = ctypes.c_int
+        L.isplib_stream_pack_last.argtypes = []
         L.isplib_stream_level_set.restype = ctypes.c_int
         L.isplib_stream_level_set.argtypes = [ctypes.c_int]
         L.isplib_stream_plan_build_minmax_hip.restype = ctypes.c_int
@@ -2979,6 +2988,10 @@ class NativeStreamPlan:
     def struct(self):
         return self._s
 
+    def packed_dwords(self) -> int:
+        """Dwords of the plan's packed word stream (the bit pattern of uint32 in an int32 view); 0: the plan has none."""
+        return int(lib().isplib_stream_packed_dwords(ctypes.byref(self._s))) if self._s.has_packed else 0
+
     def workspace(self, minmax: bool = False):
         L = lib()
         nbytes = (L.isplib_spmm_stream_minmax_workspace_bytes if minmax else L.isplib_spmm_stream_workspace_bytes)(ctypes.byref(self._s))
@@ -2994,7 +3007,8 @@ class NativeStreamPlan:
         count, typestr = {"words": (self.n_steps * self.streams, "<i4"), "perm": (self.n_steps * self.streams, "<i4"),
                           "vals": (self.n_steps * self.streams, "<f4"), "wave_step_off": (nw + 1, "<i8"),
                           "wave_row": (nw * self.rows_per_wave, "<i4"), "wave_part": (nw * self.rows_per_wave, "<i4"),
-                          "hub_row": (self.n_hub, "<i4"), "hub_off": (self.n_hub + 1, "<i4")}[name]
+                          "hub_row": (self.n_hub, "<i4"), "hub_off": (self.n_hub + 1, "<i4"),
+                          "packed": (self.packed_dwords(), "<i4")}[name]
         ptr = getattr(self._s, name)
         if not ptr or count == 0:
             return torch.empty(0, device=self.device)
@@ -3008,7 +3022,7 @@ class NativeStreamPlan:
         count, typestr = {"words": (self.n_steps * self.streams, "<i4"), "perm": (self.n_steps * self.streams, "<i4"),
                           "wave_step_off": (nw + 1, "<i8"), "wave_row": (nw * self.rows_per_wave, "<i4"),
                           "wave_part": (nw * self.rows_per_wave, "<i4"), "hub_row": (self.n_hub, "<i4"),
-                          "hub_off": (self.n_hub + 1, "<i4")}[name]
+                          "hub_off": (self.n_hub + 1, "<i4"), "packed": (self.packed_dwords(), "<i4")}[name]
         ptr = getattr(self._s, name)
         if not ptr or count == 0:
             return torch.empty(0, dtype=dtype, device=self.device)
@@ -3045,6 +3059,31 @@ def stream_capacities(device, streams: int, waves_per_gen: int, nnz: int):
         _check(lib().isplib_stream_capacities_hip(-1, int(streams), wpg, int(nnz), ctypes.cast(caps, _vp), ctypes.byref(levelled),
                                                   _stream(device)), "isplib_stream_capacities_hip")
     return list(caps) if levelled.value else None
+
+
+def stream_pack(plan) -> Optional[torch.Tensor]:
+    """The packed word stream of a plan whose arrays are torch tensors (isplib_stream_pack_hip: the library's packing pass over
+    `plan.words`): an int32 tensor holding the uint32 dwords, or None where the plan is not representable (include/isplib_hip.h)."""
+    ps = plan.struct()
+    ps.packed, ps.has_packed = None, 0
+    dwords = int(lib().isplib_stream_packed_dwords(ctypes.byref(ps)))
+    if dwords <= 0 or not plan.words.is_cuda:
+        return None
+    out = torch.empty(dwords, dtype=torch.int32, device=plan.words.device)
+    ok = ctypes.c_int(0)
+    with torch.cuda.device(out.device):
+        _check(lib().isplib_stream_pack_hip(ctypes.byref(ps), _ptr(out), dwords, ctypes.byref(ok), _stream(out.device)), "isplib_stream_pack_hip")
+    return out if ok.value else None
+
+
+def stream_pack_set(mode: int) -> None:
+    """A/B runs and tests: 0 off, 1 every plan that has a packed stream, 2 auto (overrides ISPLIB_STREAM_PACK)."""
+    _check(lib().isplib_stream_pack_set(int(mode)), "isplib_stream_pack_set")
+
+
+def stream_pack_last() -> bool:
+    """Whether the last fusedMM_csr_stream_hip of this thread read the plan's packed word stream."""
+    return bool(lib().isplib_stream_pack_last())
 
 
 def stream_level_set(mode: int) -> None:

@@ -16,6 +16,10 @@ void stream_stage_report(unsigned panels);   // which panels the call staged (is
 // mean loop ticks of every wave of one generation of the sum / mean stream kernel on a synthetic plan (spmm_sweep.hip): the calibration
 // behind isplib_stream_capacities_hip (stream_plan.hip); `launches` timed launches after one that is not counted
 int stream_kernel_calibrate(int streams, int waves_per_gen, int launches, int degree, int col_mult, double *wave_ticks, hipStream_t st);
+// the packed word stream of the sum / mean stream kernel (ISPLIB_STREAM_PACK; runtime.hip)
+enum { ISPLIB_PACK_OFF = 0, ISPLIB_PACK_FORCE = 1, ISPLIB_PACK_AUTO = 2 };
+int stream_pack_mode();
+void stream_pack_report(int packed);         // whether the call launched the PACKED instance (isplib_stream_pack_last)
 int stream_level_mode();                     // 0 off, 1 on, 2 auto: the levelled deal of the stream plans (ISPLIB_STREAM_LEVEL; runtime.hip)
 
 inline void clear_error() { error_buffer()[0] = '\0'; }

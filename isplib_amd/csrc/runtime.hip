@@ -83,5 +83,31 @@ extern "C" int isplib_stream_level_set(int mode) {
    return ISPLIB_SUCCESS;
 }
 
+// The packed word stream of the sum / mean stream kernel (include/isplib_hip.h, PACKED WORD STREAM): ISPLIB_STREAM_PACK=auto|0|1 read
+// once; unset: auto (profiles/stream_packed_words.txt holds the A/B).  0 is the launch of a plan without a packed stream, exactly.  For
+// A/B runs and tests, not declared in the header: isplib_stream_pack_set overrides the mode (0 off, 1 whenever the plan has a packed
+// stream, 2 auto), isplib_stream_pack_last tells whether the last call of fusedMM_csr_stream_hip on this thread read the packed stream.
+namespace isplib {
+static int g_stream_pack = -1;
+static thread_local int g_stream_pack_last = 0;
+int stream_pack_mode() {
+   if (g_stream_pack < 0) {
+      const char *e = getenv("ISPLIB_STREAM_PACK");
+      g_stream_pack = !e ? ISPLIB_PACK_AUTO : strcmp(e, "0") == 0 ? ISPLIB_PACK_OFF : strcmp(e, "1") == 0 ? ISPLIB_PACK_FORCE : ISPLIB_PACK_AUTO;
+   }
+   return g_stream_pack;
+}
+void stream_pack_report(int packed) { g_stream_pack_last = packed; }
+}  // namespace isplib
+
+extern "C" int isplib_stream_pack_set(int mode) {
+   isplib::clear_error();
+   if (mode != isplib::ISPLIB_PACK_OFF && mode != isplib::ISPLIB_PACK_FORCE && mode != isplib::ISPLIB_PACK_AUTO)
+      return isplib::fail(ISPLIB_FAIL, "isplib_stream_pack_set: 0 (off), 1 (every plan that has a packed stream) or 2 (auto)");
+   isplib::g_stream_pack = mode;
+   return ISPLIB_SUCCESS;
+}
+extern "C" int isplib_stream_pack_last(void) { return isplib::g_stream_pack_last; }
+
 extern "C" int isplib_hip_abi_version(void) { return ISPLIB_HIP_ABI_VERSION; }
 extern "C" const char *isplib_hip_last_error(void) { return isplib::error_buffer(); }

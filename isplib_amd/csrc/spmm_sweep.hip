@@ -30,7 +30,11 @@ namespace isplib {
 // masked tail, no per-segment bookkeeping.  Sum / mean only.
 // TIMED (the calibration of the levelled deal, isplib_stream_capacities_hip, and scripts/exp_wave_times.py): the same kernel, and
 // every wave also reports when it started, entered and left its loop and finished (s_memtime), and where it ran.
-template <int LPR, bool HAS_VAL, int NVMAX, int NBW, int WGS, bool TIMED = false>
+// PACKED (64-column geometry, not TIMED): the words come out of the plan's packed stream (include/isplib_hip.h, PACKED WORD STREAM) --
+// 304 bytes a batch from beyond the L2 instead of 512.  Only the batch loader differs: where the other instances load a batch of
+// words into w2 and move it to w1 a batch later, this one loads the packed batch into two registers and DECODES it into w1 a
+// batch later (two cross-lane reads, two ballots); the loads keep their places and the 32 steps that follow are the same instructions.
+template <int LPR, bool HAS_VAL, int NVMAX, int NBW, int WGS, bool TIMED = false, bool PACKED = false>
 __global__ __launch_bounds__(256, (stream_wgs_per_cu<LPR, NVMAX, WGS>())) void spmm_stream_kernel(const SweepArgs a) {
    using Wave = StreamWave<LPR, NVMAX, NBW>;
    constexpr int WAVES = Wave::WAVES, G = Wave::G, PANEL = Wave::PANEL, U = Wave::U, PER = Wave::PER;
@@ -57,16 +61,33 @@ __global__ __launch_bounds__(256, (stream_wgs_per_cu<LPR, NVMAX, WGS>())) void s
    // (a weight is fetched from its batch register when its gather is consumed, one step ahead: a ring of U weights
    // beside the U gathers in flight costs 30 registers)
    const unsigned pad_word = stream_pad_own_row(a, sw);
-   stream_load_batch(sw, sw.wp, 0, pad_word, w1);
+   const int64_t nb = (sw.nwords + 64 * NBW - 1) / (64 * NBW);
+   // PACKED: the wave's first packed batch follows from its position alone; w2 holds a packed batch, not words
+   [[maybe_unused]] const uint32_t *pk = nullptr;
+   [[maybe_unused]] StreamPackLane pl;
+   if constexpr (PACKED) {
+      static_assert(!TIMED, "the TIMED instance reads the words");
+      pk = a.packed + ((sw.s0 * G) / (64 * NBW) + sw.w) * ISPLIB_STREAM_PACK_DWORDS;
+      pl = stream_pack_lane(sw);
+      stream_load_packed(sw, pk, 0, nb, w2);
+      stream_decode_packed<Wave>(pl, a.pack_width, pad_word, w2, w1);
+   } else {
+      stream_load_batch(sw, sw.wp, 0, pad_word, w1);
+   }
    if (HAS_VAL) stream_load_batch(sw, vp, 0, 0.0f, v0);
 #pragma unroll
    for (int u = 0; u < U; u++) stream_issue<ISPLIB_EXP_GATHER_AUX>(sw, rsrc, w1, u, la[u], t[u]);
-   stream_load_batch(sw, sw.wp, 64 * NBW, pad_word, w1);
+   if constexpr (PACKED) {
+      stream_load_packed(sw, pk, 1, nb, w2);
+      stream_decode_packed<Wave>(pl, a.pack_width, pad_word, w2, w1);
+   } else {
+      stream_load_batch(sw, sw.wp, 64 * NBW, pad_word, w1);
+   }
    if (HAS_VAL) stream_load_batch(sw, vp, 64 * NBW, 0.0f, v1);
-   stream_load_batch(sw, sw.wp, 128 * NBW, pad_word, w2);
+   if constexpr (PACKED) stream_load_packed(sw, pk, 2, nb, w2);
+   else stream_load_batch(sw, sw.wp, 128 * NBW, pad_word, w2);
    unsigned cur = (unsigned)(sw.g * PER * PANEL);         // the row whose running sum the registers hold (stream_flush)
    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-   const int64_t nb = (sw.nwords + 64 * NBW - 1) / (64 * NBW);
    if constexpr (TIMED) t_loop = __builtin_amdgcn_s_memtime();
    for (int64_t b = 0; b < nb; b++) {
       // the U gathers of batch b are in flight; each one consumed is replaced by the same step of batch b + 1
@@ -88,8 +109,15 @@ __global__ __launch_bounds__(256, (stream_wgs_per_cu<LPR, NVMAX, WGS>())) void s
          stream_issue<ISPLIB_EXP_GATHER_AUX>(sw, rsrc, w1, u, la[u], t[u]);
       }
 #pragma unroll
-      for (int q = 0; q < NBW; q++) { w1[q] = w2[q]; v0[q] = v1[q]; }
-      stream_load_batch(sw, sw.wp, (b + 3) * 64 * NBW, pad_word, w2);
+      for (int q = 0; q < NBW; q++) v0[q] = v1[q];
+      if constexpr (PACKED) {
+         stream_decode_packed<Wave>(pl, a.pack_width, pad_word, w2, w1);      // batch b + 2, loaded a batch ago
+         stream_load_packed(sw, pk, b + 3, nb, w2);
+      } else {
+#pragma unroll
+         for (int q = 0; q < NBW; q++) w1[q] = w2[q];
+         stream_load_batch(sw, sw.wp, (b + 3) * 64 * NBW, pad_word, w2);
+      }
       if (HAS_VAL) stream_load_batch(sw, vp, (b + 2) * 64 * NBW, 0.0f, v1);
    }
    stream_flush(lane_base + cur, acc);
@@ -378,6 +406,13 @@ static int launch_stream(const SweepArgs &a_in, hipStream_t st) {
          return check_launch("spmm_stream_kernel");
       }
    }
+   // the plan's packed word stream (the entry attached it): the 64-column geometry's PACKED instance
+   if constexpr (STREAMS == 4 && ge.nbw == 2 && ge.nvmax == 64) {
+      if (a.packed) {
+         hipLaunchKernelGGL((spmm_stream_kernel<ge.lpr, HAS_VAL, ge.nvmax, ge.nbw, ge.wgs, false, true>), dim3(blocks), dim3(256), 0, st, a);
+         return check_launch("spmm_stream_kernel");
+      }
+   }
    hipLaunchKernelGGL((spmm_stream_kernel<ge.lpr, HAS_VAL, ge.nvmax, ge.nbw, ge.wgs>), dim3(blocks), dim3(256), 0, st, a);
    return check_launch("spmm_stream_kernel");
 }
@@ -507,6 +542,16 @@ static int stream_run(int32_t imessage, int64_t m, int64_t n, int64_t k, int64_t
    if ((rc = set_epilogue(entry, ep, a)) != ISPLIB_SUCCESS) return rc;
    hipStream_t st = (hipStream_t)stream;
    const bool has_val = plan->vals != nullptr;
+   // sum / mean on a plan that carries a packed word stream (4-stream plans of the kernel's own geometry: the builders pack no
+   // other), where ISPLIB_STREAM_PACK allows it: 0 never, 1 always, auto from the size on where the stream schedule is offered
+   const int pack_mode = mm ? ISPLIB_PACK_OFF : stream_pack_mode();
+   const bool packed = pack_mode != ISPLIB_PACK_OFF && plan->has_packed && plan->packed && plan->streams == 4 && plan->slices >= 1 &&
+                       (pack_mode == ISPLIB_PACK_FORCE || nnz >= ISPLIB_STREAM_PACK_MIN_WORDS);
+   if (packed) {
+      a.packed = plan->packed;
+      a.pack_width = (unsigned)((plan->cols + plan->slices - 1) / plan->slices);
+   }
+   if (!mm) stream_pack_report(packed ? 1 : 0);
    // sum / mean: the staging area follows the partial rows, from the first 512-byte boundary on; a workspace without one (sized
    // by the partial rows alone, or NULL for a plan without hub rows) leaves every panel where it is
    const int stage_mode = mm ? ISPLIB_STAGE_OFF : stream_stage_mode();

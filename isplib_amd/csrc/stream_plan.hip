@@ -205,6 +205,67 @@ __global__ __launch_bounds__(256) void sp_gather_vals_kernel(int64_t n_words, co
    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_words; i += stride) vals[i] = perm[i] >= 0 ? src[perm[i]] : 0.0f;
 }
 
+// The packed word stream (include/isplib_hip.h, PACKED WORD STREAM): one thread per (batch, slot) walks the slot's 32 entries of the
+// batch in step order and writes the 16 column dwords, the two local-row dwords and the header that are the slot's own -- every
+// dword of a batch is written by exactly one thread, nothing is atomic but the "not representable" flag.  Integer work on `words`
+// alone: the same array on every build.
+__global__ __launch_bounds__(256) void sp_pack_words_kernel(int64_t nw, int64_t nbatch_slots, unsigned width, unsigned n, const int32_t *__restrict__ words,
+                                                            const int64_t *__restrict__ wave_step_off, uint32_t *__restrict__ packed,
+                                                            int *__restrict__ bad) {
+   constexpr unsigned CM = (1u << ISPLIB_STREAM_PACK_COL_BITS) - 1u;
+   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nbatch_slots; i += stride) {
+      const int64_t pb = i >> 2;                             // packed batch (of the whole array), slot
+      const unsigned slot = (unsigned)(i & 3);
+      // the wave whose batch this is: the last one with first_batch(w) = (wave_step_off[w] * 4) / 128 + w <= pb
+      int64_t lo = 0, hi = nw;
+      while (hi - lo > 1) {
+         const int64_t mid = lo + (hi - lo) / 2;
+         if ((wave_step_off[mid] * 4) / 128 + mid <= pb) lo = mid; else hi = mid;
+      }
+      const int64_t s0 = wave_step_off[lo], nwords = (wave_step_off[lo + 1] - s0) * 4;
+      const int64_t b = pb - ((s0 * 4) / 128 + lo);
+      if (b * 128 >= nwords) continue;                       // the unused batch between two waves: never read
+      const int32_t *wp = words + s0 * 4 + b * 128;
+      const int64_t left = nwords - b * 128;                 // words of the wave from this batch on
+      uint32_t *out = packed + pb * ISPLIB_STREAM_PACK_DWORDS;
+      const unsigned pad = ((slot * 16u) << 24) | n;
+      unsigned real = 0, base = 0, cur = 0, rows1[2] = {0u, 0u}, cols[16];
+      bool seen_pad = false, ok = true;
+#pragma unroll
+      for (int t = 0; t < 32; t++) {
+         const int e = t * 4 + (int)slot;
+         const unsigned w = e < left ? (unsigned)wp[e] : pad;
+         unsigned field = 0, row = 0, flag = 0;
+         if ((w & 0xFFFFFFu) == n) {                         // padding: the tail of the slot's stream, and nothing but the padding word
+            seen_pad = true;
+            ok = ok && w == pad;
+         } else {
+            ok = ok && !seen_pad;
+            const unsigned col = w & 0xFFFFFFu, sl = col / width;
+            if (real == 0) base = cur = sl;
+            flag = sl > cur ? 1u : 0u;
+            cur += flag;
+            field = col - cur * width;                       // (sl >= cur: a stream's slices ascend; checked through the field's range)
+            row = (w >> 24) - slot * 16u;
+            ok = ok && sl >= cur && field <= CM && row < 16u && base < 4096u;
+            real = (unsigned)t + 1u;
+         }
+         if (t < 16) cols[t] = (field & CM) | ((row & 15u) << 26) | (flag << 30);
+         else {
+            cols[t - 16] |= ((field & CM) << ISPLIB_STREAM_PACK_COL_BITS) | (flag << 31);
+            rows1[(t - 16) >> 3] |= (row & 15u) << (((t - 16) & 7) * 4);
+         }
+      }
+#pragma unroll
+      for (int t = 0; t < 16; t++) out[t * 4 + (int)slot] = cols[t];
+      out[64 + slot * 2] = rows1[0];
+      out[64 + slot * 2 + 1] = rows1[1];
+      out[72 + slot] = (base & 0xFFFu) | (real << 12);
+      if (!ok) atomicOr(bad, 1);
+   }
+}
+
 struct SpTemp {                                             // frees every temporary on every exit path
    std::vector<void *> ptrs;
    ~SpTemp() { for (void *p : ptrs) (void)hipFree(p); }
@@ -233,6 +294,62 @@ static hipError_t sp_sort(void *temp, size_t &temp_bytes, const uint32_t *kin, u
 
 using namespace isplib;
 
+// packed batches of a plan: every wave's first batch follows from its position ((first step * 4) / 128 + wave), so the array
+// ends after the last wave's
+static inline int64_t sp_packed_batches(const isplib_stream_plan *plan) {
+   const int64_t nw = (int64_t)plan->gens * plan->waves_per_gen;
+   return (plan->n_steps * 4) / 128 + nw + 1;
+}
+
+extern "C" size_t isplib_stream_packed_dwords(const isplib_stream_plan *plan) {
+   if (!plan || plan->streams != 4 || plan->rows_per_wave != 64 || plan->gens < 1 || plan->waves_per_gen < 1 || plan->n_steps < 0) return 0;
+   if (plan->slices < 1 || plan->slices > 4096 || plan->cols < 1 || plan->cols >= ISPLIB_STREAM_N_END) return 0;
+   if ((plan->cols + plan->slices - 1) / plan->slices > (1 << ISPLIB_STREAM_PACK_COL_BITS)) return 0;
+   return (size_t)sp_packed_batches(plan) * ISPLIB_STREAM_PACK_DWORDS;
+}
+
+extern "C" int isplib_stream_pack_hip(const isplib_stream_plan *plan, uint32_t *out, int64_t out_dwords, int *representable, void *stream) {
+   clear_error();
+   if (representable) *representable = 0;
+   const int64_t need = (int64_t)isplib_stream_packed_dwords(plan);
+   if (need <= 0) return fail(ISPLIB_FAIL, "isplib_stream_pack_hip: the plan's geometry has no packed form (isplib_stream_packed_dwords)");
+   if (!out || out_dwords < need || !representable) return fail(ISPLIB_FAIL, "isplib_stream_pack_hip: out of isplib_stream_packed_dwords(plan) dwords and representable are required");
+   if (!plan->wave_step_off || (plan->n_steps > 0 && !plan->words)) return fail(ISPLIB_FAIL, "isplib_stream_pack_hip: null operand");
+   hipStream_t st = (hipStream_t)stream;
+   int *bad = nullptr, host = 1;
+   if (hipMalloc((void **)&bad, 256) != hipSuccess) { (void)hipGetLastError(); return fail(ISPLIB_NOT_ENOUGH_MEM, "isplib_stream_pack_hip: device allocation failed"); }
+   hipError_t e = hipMemsetAsync(bad, 0, sizeof(int), st);
+   if (e == hipSuccess) e = hipMemsetAsync(out, 0, (size_t)need * sizeof(uint32_t), st);      // the unused batches too: the same array on every build
+   if (e == hipSuccess) {
+      const int64_t nbs = sp_packed_batches(plan) * 4;
+      hipLaunchKernelGGL(sp_pack_words_kernel, dim3(sp_grid(nbs)), dim3(256), 0, st, (int64_t)plan->gens * plan->waves_per_gen, nbs,
+                         (unsigned)((plan->cols + plan->slices - 1) / plan->slices), (unsigned)plan->cols, plan->words, plan->wave_step_off, out, bad);
+      e = hipGetLastError();
+   }
+   if (e == hipSuccess) e = hipMemcpyAsync(&host, bad, sizeof(int), hipMemcpyDeviceToHost, st);
+   if (e == hipSuccess) e = hipStreamSynchronize(st);
+   (void)hipFree(bad);
+   if (e != hipSuccess) return hip_fail(e, "isplib_stream_pack_hip");
+   *representable = host ? 0 : 1;
+   return ISPLIB_SUCCESS;
+}
+
+// the native builders' own packing: a plan that has no packed form, or no room for it, is a plan without one -- never an error
+static void sp_attach_packed(isplib_stream_plan *out, hipStream_t st) {
+   const int64_t dwords = (int64_t)isplib_stream_packed_dwords(out);
+   if (dwords <= 0) return;
+   uint32_t *packed = nullptr;
+   if (!sp_alloc_out(&packed, (size_t)dwords)) return;
+   int ok = 0;
+   if (isplib_stream_pack_hip(out, packed, dwords, &ok, st) != ISPLIB_SUCCESS || !ok) {
+      (void)hipFree(packed);
+      clear_error();
+      return;
+   }
+   out->packed = packed;
+   out->has_packed = 1;
+}
+
 extern "C" void isplib_stream_plan_free(isplib_stream_plan *plan) {
    if (!plan) return;
    (void)hipDeviceSynchronize();                           // nothing of the plan's may still be in flight
@@ -240,6 +357,7 @@ extern "C" void isplib_stream_plan_free(isplib_stream_plan *plan) {
    (void)hipFree(const_cast<int64_t *>(plan->wave_step_off)); (void)hipFree(const_cast<int32_t *>(plan->wave_row));
    (void)hipFree(const_cast<int32_t *>(plan->wave_part)); (void)hipFree(const_cast<int32_t *>(plan->hub_row));
    (void)hipFree(const_cast<int32_t *>(plan->hub_off)); (void)hipFree(const_cast<int32_t *>(plan->perm));
+   (void)hipFree(const_cast<uint32_t *>(plan->packed));
    memset(plan, 0, sizeof(*plan));
 }
 
@@ -523,7 +641,9 @@ extern "C" int isplib_stream_plan_build_caps_hip(int64_t m, int64_t n, int64_t n
    clear_error();
    int rpw = 0, resident = 0;
    if (isplib_spmm_stream_geometry(streams, &rpw, &resident) != ISPLIB_SUCCESS) return ISPLIB_FAIL;
-   return stream_plan_build(m, n, nnz, rowptr, col, val, streams, rpw, resident, slices, chunk, waves_per_gen, out, stream, -1, caps);
+   const int rc = stream_plan_build(m, n, nnz, rowptr, col, val, streams, rpw, resident, slices, chunk, waves_per_gen, out, stream, -1, caps);
+   if (rc == ISPLIB_SUCCESS) sp_attach_packed(out, (hipStream_t)stream);      // (after the builder's temporaries are gone)
+   return rc;
 }
 
 extern "C" int isplib_stream_plan_build_hip(int64_t m, int64_t n, int64_t nnz, const int64_t *rowptr, const int64_t *col,
@@ -535,8 +655,10 @@ extern "C" int isplib_stream_plan_build_hip(int64_t m, int64_t n, int64_t nnz, c
    std::vector<uint32_t> caps((size_t)(waves_per_gen > 0 ? waves_per_gen : resident));
    const int rc = isplib_stream_capacities_hip(-1, streams, waves_per_gen, nnz, caps.data(), &levelled, stream);
    if (rc) return rc;
-   return stream_plan_build(m, n, nnz, rowptr, col, val, streams, rpw, resident, slices, chunk, waves_per_gen, out, stream, -1,
-                            levelled ? caps.data() : nullptr);
+   const int rc2 = stream_plan_build(m, n, nnz, rowptr, col, val, streams, rpw, resident, slices, chunk, waves_per_gen, out, stream, -1,
+                                     levelled ? caps.data() : nullptr);
+   if (rc2 == ISPLIB_SUCCESS) sp_attach_packed(out, (hipStream_t)stream);     // (after the builder's temporaries are gone)
+   return rc2;
 }
 
 // 1 if some row's columns do not ascend (duplicates are fine)

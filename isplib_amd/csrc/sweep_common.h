@@ -132,6 +132,9 @@ struct SweepArgs {
    const float *ep_row_scale, *ep_self, *ep_bias;
    int64_t ep_ld_self;
    int ep_relu;
+   // packed word stream (include/isplib_hip.h; the PACKED instance of spmm_stream_kernel): the plan's packed copy of `words`, or null
+   const uint32_t *packed;
+   unsigned pack_width;            // the plan's slice width, ceil(n / slices)
 };
 
 // finished value of a whole row: mean scale / epilogue (sum, mean), empty-row value and absolute arg (max, min),
@@ -296,6 +299,58 @@ __device__ __forceinline__ void stream_load_batch(const SW &sw, const S *src, in
       const int64_t i = first + q * 64 + sw.lane;
       reg[q] = i < sw.nwords ? (T)src[i] : pad;
    }
+}
+
+// The same batch of WORDS out of the plan's packed stream (include/isplib_hip.h, PACKED WORD STREAM): 304 bytes instead of 512.
+// The load and the decode are apart by a whole batch, like the load of w2 and its move to w1: decoding where the batch is loaded
+// would wait for the load, and with it for every gather issued before it.  stream_load_packed: 76 dwords, one per lane and 12 more;
+// a batch past the wave's last loads nothing and holds 0, which decodes to padding (a header that says "no entry is real").
+template <class SW>
+__device__ __forceinline__ void stream_load_packed(const SW &sw, const uint32_t *wave_packed, int64_t batch, int64_t nbatches, unsigned (&raw)[2]) {
+   static_assert(SW::NBW == 2 && SW::G == 4 && SW::PER == 16, "the packed stream is the 64-column sum geometry's: 128 words a batch, 16 rows a slot");
+   const uint32_t *p = wave_packed + batch * ISPLIB_STREAM_PACK_DWORDS;
+   const bool in = batch < nbatches;
+   raw[0] = in ? p[sw.lane] : 0u;
+   raw[1] = in && sw.lane < ISPLIB_STREAM_PACK_DWORDS - 64 ? p[64 + sw.lane] : 0u;
+}
+// what of a lane's place in the packed batch does not change from batch to batch
+struct StreamPackLane {
+   unsigned row_hi;                // the slot's first local row as the top byte of a word
+   unsigned mask_lo, mask_hi;      // the lanes of this lane's slot up to and including itself
+   unsigned slot_lanes;            // the lanes of the slot among any 32 (the same pattern in both halves of the wave)
+   int nib_addr, hdr_addr;         // ds_bpermute addresses: the lane that holds this lane's second local row; its slot's header
+   unsigned nib_shift, step;       // where that row is in the dword; this lane's step in the batch's first register
+};
+template <class SW> __device__ __forceinline__ StreamPackLane stream_pack_lane(const SW &sw) {
+   StreamPackLane pl;
+   const unsigned t = (unsigned)sw.lane >> 2, slot = (unsigned)sw.lane & 3u;
+   pl.row_hi = (slot * (unsigned)SW::PER) << 24;
+   pl.slot_lanes = 0x11111111u << slot;
+   pl.mask_lo = pl.slot_lanes & (sw.lane < 32 ? (2u << sw.lane) - 1u : 0xFFFFFFFFu);
+   pl.mask_hi = sw.lane < 32 ? 0u : pl.slot_lanes & ((2u << (sw.lane - 32)) - 1u);
+   pl.nib_addr = (int)(slot * 2u + (t >> 3)) * 4;
+   pl.hdr_addr = (int)(8u + slot) * 4;
+   pl.nib_shift = (t & 7u) * 4u;
+   pl.step = t;
+   return pl;
+}
+// raw (loaded a batch ago) -> the two batch registers, exactly what stream_load_batch reads from `words`
+template <class SW>
+__device__ __forceinline__ void stream_decode_packed(const StreamPackLane &pl, unsigned width, unsigned pad_word, const unsigned (&raw)[2], unsigned (&reg)[2]) {
+   const unsigned d = raw[0];
+   const unsigned rows1 = (unsigned)__builtin_amdgcn_ds_bpermute(pl.nib_addr, (int)raw[1]);
+   const unsigned hdr = (unsigned)__builtin_amdgcn_ds_bpermute(pl.hdr_addr, (int)raw[1]);
+   const unsigned long long f0 = __ballot((d & 0x40000000u) != 0u), f1 = __ballot((int)d < 0);
+   const unsigned f0lo = (unsigned)f0, f0hi = (unsigned)(f0 >> 32), f1lo = (unsigned)f1, f1hi = (unsigned)(f1 >> 32);
+   // advance flags of the slot's entries up to and including this lane's: of the first register, and of the second (after all of the first)
+   const unsigned c0 = __popc(f0lo & pl.mask_lo) + __popc(f0hi & pl.mask_hi);
+   const unsigned c1 = __popc(f0lo & pl.slot_lanes) + __popc(f0hi & pl.slot_lanes) + __popc(f1lo & pl.mask_lo) + __popc(f1hi & pl.mask_hi);
+   const unsigned base = hdr & 0xFFFu, real = (hdr >> 12) & 0x3Fu;
+   constexpr unsigned CM = (1u << ISPLIB_STREAM_PACK_COL_BITS) - 1u;
+   const unsigned w0 = __umul24(base + c0, width) + (d & CM) + (pl.row_hi + (((d >> 26) & 15u) << 24));
+   const unsigned w1 = __umul24(base + c1, width) + ((d >> ISPLIB_STREAM_PACK_COL_BITS) & CM) + (pl.row_hi + (((rows1 >> pl.nib_shift) & 15u) << 24));
+   reg[0] = pl.step < real ? w0 : pad_word;
+   reg[1] = pl.step + 16u < real ? w1 : pad_word;
 }
 
 // the gather of step u of a batch.  One cross-lane read (ds_bpermute) hands a slot its word of the step (the LDS pipe is otherwise
@@ -496,6 +551,7 @@ static inline SweepArgs stream_args(const StreamCall &c, float *z, int64_t ldz) 
    a.words = plan->words; a.vals = plan->vals; a.wave_step_off = plan->wave_step_off; a.null_word = (unsigned)c.n;
    a.hub_row = plan->hub_row; a.hub_off = plan->hub_off; a.n_hub = plan->n_hub;
    a.part_val = (float *)c.workspace;
+   a.packed = nullptr;              // the sum / mean entry alone attaches the packed stream (spmm_sweep.hip)
    return a;
 }
 

@@ -173,6 +173,7 @@ static isplib_stream_plan stream_plan_of(const Plan &plan) {
    sp.hub_row = sp.n_hub ? hub_row.data_ptr<int32_t>() : nullptr;
    sp.hub_off = hub_off.data_ptr<int32_t>();
    sp.perm = nullptr;
+   sp.packed = nullptr; sp.has_packed = 0;      // a tensor-list plan carries no packed word stream: these calls read `words`
    if (plan.size() == 9) {
       TORCH_CHECK(plan[8].is_cuda() && plan[8].scalar_type() == at::kInt && plan[8].numel() == words.numel(), "isplib: stream plan perm must be int32, one per word");
       sp.perm = plan[8].data_ptr<int32_t>();

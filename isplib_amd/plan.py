@@ -235,13 +235,15 @@ class StreamPlan:
     hub_row: torch.Tensor        # int32 [n_hub]
     hub_off: torch.Tensor        # int32 [n_hub + 1]
     chunk: int
+    packed: Optional[torch.Tensor] = None   # int32 view of the packed word stream (include/isplib_hip.h), or None: the plan has none
 
     def struct(self) -> "cabi.StreamPlanStruct":
         p = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
         return cabi.StreamPlanStruct(self.rows, self.cols, self.slices, self.gens, self.waves_per_gen, self.rows_per_wave,
                                      self.streams, int(self.chunk), self.n_steps, self.n_parts, self.n_hub, p(self.words), p(self.vals),
                                      p(self.wave_step_off), p(self.wave_row), p(self.wave_part), p(self.hub_row), p(self.hub_off),
-                                     p(self.perm) if self.perm.dtype == torch.int32 else None)
+                                     p(self.perm) if self.perm.dtype == torch.int32 else None,
+                                     p(self.packed), 1 if p(self.packed) else 0)
 
     def workspace(self, minmax: bool = False) -> torch.Tensor:
         import ctypes
@@ -406,7 +408,102 @@ def build_stream_plan(rowptr: torch.Tensor, col: torch.Tensor, val: Optional[tor
     plan = StreamPlan(**stream_plan_arrays(rowptr, col, ncols, slices, waves_per_gen, rows_per_wave, streams, chunk,
                                            pad_row=rows_per_wave if minmax else None, capacities=capacities))
     plan.set_values(val)
+    if not minmax and streams == 4 and rows_per_wave == rpw:
+        plan.packed = cabi.stream_pack(plan)        # the library's packing pass over `words` (None: not representable)
     return plan
+
+
+# ---- the packed word stream (include/isplib_hip.h, PACKED WORD STREAM): the format, in numpy -------------------------------------
+# What the library's packing pass (stream_plan.hip: sp_pack_words_kernel) writes and its sum / mean kernel decodes, spelled out on
+# the CPU: tests pin the format with these two and compare the native array with pack's.
+STREAM_PACK_DWORDS = 76          # ISPLIB_STREAM_PACK_DWORDS: 64 column dwords, 8 local-row dwords, 4 slot headers
+STREAM_PACK_COL_BITS = 13        # ISPLIB_STREAM_PACK_COL_BITS
+
+
+def stream_pack_batches(wave_step_off) -> int:
+    """Batches of the packed array of a plan with these wave_step_off (batch b of wave w is batch (s0 * 4) // 128 + w + b)."""
+    return int(wave_step_off[-1]) * 4 // 128 + (len(wave_step_off) - 1) + 1
+
+
+def stream_pack_words(words, wave_step_off, ncols: int, slices: int):
+    """(packed, representable): the packed stream of a 4-stream sum / mean plan of 64 rows per wave as a numpy uint32 array, and
+    whether every entry could be represented (False: the array must not be used).  `words`, `wave_step_off`: the plan's, as numpy."""
+    import numpy as np
+    words = np.asarray(words).astype(np.int64) & 0xFFFFFFFF
+    off = np.asarray(wave_step_off).astype(np.int64)
+    width = -(-int(ncols) // int(slices))
+    cm = (1 << STREAM_PACK_COL_BITS) - 1
+    ok = width <= cm + 1 and slices <= 4096
+    out = np.zeros(stream_pack_batches(off) * STREAM_PACK_DWORDS, dtype=np.uint32)
+    for w in range(len(off) - 1):
+        s0, nwords = int(off[w]), int(off[w + 1] - off[w]) * 4
+        first = s0 * 4 // 128 + w
+        for b in range(-(-nwords // 128)):
+            o = (first + b) * STREAM_PACK_DWORDS
+            for slot in range(4):
+                pad = ((slot * 16) << 24) | int(ncols)
+                real = base = cur = 0
+                seen_pad = False
+                for t in range(32):
+                    e = b * 128 + t * 4 + slot
+                    word = int(words[s0 * 4 + e]) if e < nwords else pad
+                    field = row = flag = 0
+                    if word & 0xFFFFFF == int(ncols):
+                        seen_pad = True
+                        ok = ok and word == pad
+                    else:
+                        col = word & 0xFFFFFF
+                        sl = col // width
+                        if real == 0:
+                            base = cur = sl
+                        flag = 1 if sl > cur else 0
+                        cur += flag
+                        field = col - cur * width
+                        row = (word >> 24) - slot * 16
+                        ok = ok and not seen_pad and sl >= cur and 0 <= field <= cm and 0 <= row < 16
+                        real = t + 1
+                    field, row = field & cm, row & 15
+                    lane = (t % 16) * 4 + slot
+                    if t < 16:
+                        out[o + lane] |= np.uint32(field | (row << 26) | (flag << 30))
+                    else:
+                        out[o + lane] |= np.uint32((field << STREAM_PACK_COL_BITS) | (flag << 31))
+                        out[o + 64 + slot * 2 + (t - 16) // 8] |= np.uint32(row << (((t - 16) % 8) * 4))
+                out[o + 72 + slot] = np.uint32((base & 0xFFF) | (real << 12))
+    return out, bool(ok)
+
+
+def stream_unpack_words(packed, wave_step_off, ncols: int, slices: int):
+    """The words that the kernel's decoder makes of `packed` (stream_pack_words): the plan's `words` as a numpy int32 array, every
+    wave's batches decoded as the lanes of a wave decode them (ballots as bit masks, the cross-lane reads as array reads)."""
+    import numpy as np
+    packed = np.asarray(packed).view(np.uint32).astype(np.int64)
+    off = np.asarray(wave_step_off).astype(np.int64)
+    width = -(-int(ncols) // int(slices))
+    cm = (1 << STREAM_PACK_COL_BITS) - 1
+    words = np.zeros(int(off[-1]) * 4, dtype=np.int64)
+    lane = np.arange(64)
+    t, slot = lane >> 2, lane & 3
+    same_slot_upto = (slot[None, :] == slot[:, None]) & (lane[None, :] <= lane[:, None])      # [lane, other lane]
+    for w in range(len(off) - 1):
+        s0, nwords = int(off[w]), int(off[w + 1] - off[w]) * 4
+        first = s0 * 4 // 128 + w
+        for b in range(-(-nwords // 128)):
+            raw = packed[(first + b) * STREAM_PACK_DWORDS:(first + b + 1) * STREAM_PACK_DWORDS]
+            d = raw[:64]
+            rows1 = (raw[64 + slot * 2 + (t >> 3)] >> ((t & 7) * 4)) & 15
+            hdr = raw[72 + slot]
+            f0, f1 = (d >> 30) & 1, (d >> 31) & 1
+            c0 = (same_slot_upto * f0[None, :]).sum(axis=1)
+            c1 = np.array([f0[slot == g].sum() for g in slot]) + (same_slot_upto * f1[None, :]).sum(axis=1)
+            base, real = hdr & 0xFFF, (hdr >> 12) & 0x3F
+            pad = ((slot * 16) << 24) | int(ncols)
+            w0 = (base + c0) * width + (d & cm) + ((slot * 16 + ((d >> 26) & 15)) << 24)
+            w1 = (base + c1) * width + ((d >> STREAM_PACK_COL_BITS) & cm) + ((slot * 16 + rows1) << 24)
+            both = np.concatenate([np.where(t < real, w0, pad), np.where(t + 16 < real, w1, pad)])
+            n_here = min(128, nwords - b * 128)
+            words[s0 * 4 + b * 128:s0 * 4 + b * 128 + n_here] = both[:n_here]
+    return (words & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
 
 
 def build_stream_plan_native(rowptr: torch.Tensor, col: torch.Tensor, ncols: int, slices: int, streams: int = 4,
@@ -434,7 +531,8 @@ def build_stream_plan_native(rowptr: torch.Tensor, col: torch.Tensor, ncols: int
                       n_hub=native.n_hub, words=native.view("words", i32), vals=None, perm=native.view("perm", i32),
                       wave_step_off=native.view("wave_step_off", i64), wave_row=native.view("wave_row", i32),
                       wave_part=native.view("wave_part", i32), hub_row=native.view("hub_row", i32),
-                      hub_off=native.view("hub_off", i32), chunk=chunk)
+                      hub_off=native.view("hub_off", i32), chunk=chunk,
+                      packed=native.view("packed", i32) if native.packed_dwords() else None)
     plan._native = native            # owns the device arrays the tensors above look at
     return plan
 
