@@ -892,6 +892,51 @@ int    isplib_gat_edge_bw_cols_hip(int64_t m, int64_t n, int64_t k, int64_t nnz,
                                    const float *g, int64_t ldg, const float *lse, const float *dsum, float *dy, int64_t lddy,
                                    float *d_a_src /* n x heads */, void *stream);
 /*
+ * The GAT aggregation above with attention dropout (GATConv's `dropout`: the coefficients are dropped after the softmax, per stored
+ * entry and per head), fp32, with or without the per-edge term.  With the keep bit q_e,h in {0, 1} and c = `scale` =
+ * float32(1 / (1 - p)):
+ *   a_e, lse, s_e, u_e   exactly as without dropout: the softmax runs over ALL stored entries, lse does not see the mask
+ *   z_i[head h]  = c sum_e q_e a_e y_j[head h]            D[i,h] = <g_i, z_i>_h  (= sum_e a_e t_e)
+ *   t_e          = q_e c <g_i, y_j>_h                     du_e   = a_e (t_e - D[i,h]) slope_e      (a dropped edge still gets -a_e D slope)
+ *   d a_dst, d a_src, d a_edge  sums of du_e as above     dy_j[head h] = c sum_{e -> j} q_e a_e g_i[head h]
+ * The keep bit is a pure function of (seed, CSR position of the entry, head), recomputed in all three entries -- no mask is stored, no
+ * RNG state is kept, and equal arguments give equal bits:
+ *   fmix32(x): x ^= x >> 16; x *= 0x85ebca6b; x ^= x >> 13; x *= 0xc2b2ae35; x ^= x >> 16                  (uint32 arithmetic)
+ *   word(seed, pos, h) = fmix32( fmix32(uint32(pos) ^ uint32(seed)) + uint32(h) * 0x9E3779B9 + uint32(seed >> 32) )
+ *   T(p) = min(2^32 - 1, floor(p * 2^32))  in double           q = word >= T                               T(0) = 0 keeps everything
+ * isplib_gat_drop_threshold(p) is T(p) and isplib_gat_drop_word(seed, pos, head) is `word` (host functions; isplib_amd/csrc/
+ * gat_dropout.h states both for the kernels and the host).  seed < 2^63, pos < 2^31 (the position in indx), heads numbered from 0.
+ * Every stored entry has its own bit, duplicates (i, j) included.  An empty row has z = 0, lse = -inf, D = 0; a row whose entries are
+ * all dropped for head h has z = 0 exactly there and a finite lse.  With threshold = 0 and scale = 1 the results are those of the
+ * entries without dropout bit for bit.
+ *   isplib_gat_drop_csr_hip      the arguments of isplib_gat_edge_csr_hip, then threshold, scale, seed.
+ *   isplib_gat_drop_bw_rows_hip  the arguments of isplib_gat_edge_bw_rows_hip (d_a_edge after stream), then threshold, scale, seed.
+ *   isplib_gat_drop_bw_cols_hip  the arguments of isplib_gat_edge_bw_cols_hip, then threshold, scale, seed; csr2csc is REQUIRED (the
+ *                                keep bit is a function of the CSR position), with or without a_edge.
+ * a_edge may be NULL in all three (and d_a_edge with it): then there is no per-edge term, u_e = a_dst[i,h] + a_src[j,h].
+ * Domain: isplib_gat_serves; with a_edge also isplib_gat_edge_serves.  Outside: ISPLIB_NO_OPT_IMPL.  A scale that is not a positive
+ * finite number, a null csr2csc with nnz > 0, and the refusals of the entries above: ISPLIB_FAIL; all before any launch.
+ */
+uint32_t isplib_gat_drop_threshold(double p);
+uint32_t isplib_gat_drop_word(uint64_t seed, int64_t pos, int64_t head);
+int    isplib_gat_drop_csr_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                               const int64_t *pntre, const float *a_dst /* m x heads */, const float *y, int64_t ldy,
+                               const float *a_src /* n x heads */, const float *a_edge /* nnz x heads, or NULL */, int64_t heads,
+                               float negative_slope, float *z, int64_t ldz, float *lse /* m x heads */, void *stream,
+                               uint32_t threshold, float scale, uint64_t seed);
+int    isplib_gat_drop_bw_rows_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                                   const int64_t *pntre, const float *a_dst, const float *y, int64_t ldy, const float *a_src,
+                                   const float *a_edge /* or NULL */, int64_t heads, float negative_slope, const float *g,
+                                   int64_t ldg, const float *z, int64_t ldz, const float *lse, float *d_a_dst /* m x heads */,
+                                   float *dsum /* m x heads */, void *stream, float *d_a_edge /* nnz x heads, or NULL */,
+                                   uint32_t threshold, float scale, uint64_t seed);
+int    isplib_gat_drop_bw_cols_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t, const int64_t *colb,
+                                   const int64_t *cole, const int64_t *csr2csc /* nnz */, const float *a_dst, const float *y,
+                                   int64_t ldy, const float *a_src, const float *a_edge /* or NULL */, int64_t heads,
+                                   float negative_slope, const float *g, int64_t ldg, const float *lse, const float *dsum, float *dy,
+                                   int64_t lddy, float *d_a_src /* n x heads */, void *stream, uint32_t threshold, float scale,
+                                   uint64_t seed);
+/*
  * The row-softmax attention aggregation above for dense operands of 16-bit elements (dtype: ISPLIB_DTYPE_BF16 | _F16), forward and
  * backward, on the same mapping (one wave per row or column, one 16-byte gather of EIGHT columns per lane and edge, one chunk per
  * lane).  x, y and g are `dtype` and no operand is widened in memory; widening is exact, every product, sum, exponential and division

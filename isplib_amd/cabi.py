@@ -9,7 +9,9 @@ stream.  Every function raises ``RuntimeError`` on a non-zero status.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
+import struct
 from typing import Optional
 
 import torch
@@ -261,6 +263,7 @@ EXPORTS = (
     "isplib_attention16_auto",
     "isplib_gat_csr_hip", "isplib_gat_bw_rows_hip", "isplib_gat_bw_cols_hip", "isplib_gat_domain",
     "isplib_gat_edge_csr_hip", "isplib_gat_edge_bw_rows_hip", "isplib_gat_edge_bw_cols_hip", "isplib_gat_edge_domain",
+    "isplib_gat_drop_csr_hip", "isplib_gat_drop_bw_rows_hip", "isplib_gat_drop_bw_cols_hip",
     "isplib_gat16_csr_hip", "isplib_gat16_bw_rows_hip", "isplib_gat16_bw_cols_hip", "isplib_gat16_domain", "isplib_gat16_auto",
     "isplib_gatv2_csr_hip", "isplib_gatv2_bw_rows_hip", "isplib_gatv2_bw_rows_workspace_bytes", "isplib_gatv2_bw_cols_hip",
     "isplib_gatv2_domain",
@@ -272,6 +275,9 @@ GATV2_16_EXPORTS = (
     "isplib_gatv2_16_csr_hip", "isplib_gatv2_16_bw_rows_hip", "isplib_gatv2_16_bw_rows_workspace_bytes", "isplib_gatv2_16_bw_cols_hip",
     "isplib_gatv2_16_domain", "isplib_gatv2_16_auto",
 )
+
+# the two host functions of the dropout keep bit (isplib_hip.h declares them; they return uint32_t, not a status, and are listed apart)
+GAT_DROP_HOST_EXPORTS = ("isplib_gat_drop_threshold", "isplib_gat_drop_word")
 
 # include/isplib_hip_experimental.h (libisplib_hip_exp.so): forms measured slower than the defaults; tests and experiment scripts only
 EXP_EXPORTS = ("fusedMM_csr_sweep_hip", "isplib_spmm_sweep_workspace_bytes", "isplib_spmm_sweep_resident_waves",
@@ -551,6 +557,18 @@ def lib() -> ctypes.CDLL:
         L.isplib_gat_edge_bw_cols_hip.restype = ctypes.c_int      # isplib_gat_bw_cols_hip with csr2csc after cole, a_edge after a_src
         L.isplib_gat_edge_bw_cols_hip.argtypes = [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _f32, _vp, _i64,
                                                   _vp, _vp, _vp, _i64, _vp, _vp]
+        # the isplib_gat_edge_* argument lists (a_edge / d_a_edge may be NULL), then threshold, scale, seed
+        L.isplib_gat_drop_threshold.restype = ctypes.c_uint32
+        L.isplib_gat_drop_threshold.argtypes = [ctypes.c_double]
+        L.isplib_gat_drop_word.restype = ctypes.c_uint32
+        L.isplib_gat_drop_word.argtypes = [ctypes.c_uint64, _i64, _i64]
+        _drop = [ctypes.c_uint32, _f32, ctypes.c_uint64]
+        L.isplib_gat_drop_csr_hip.restype = ctypes.c_int
+        L.isplib_gat_drop_csr_hip.argtypes = L.isplib_gat_edge_csr_hip.argtypes + _drop
+        L.isplib_gat_drop_bw_rows_hip.restype = ctypes.c_int
+        L.isplib_gat_drop_bw_rows_hip.argtypes = L.isplib_gat_edge_bw_rows_hip.argtypes + _drop
+        L.isplib_gat_drop_bw_cols_hip.restype = ctypes.c_int
+        L.isplib_gat_drop_bw_cols_hip.argtypes = L.isplib_gat_edge_bw_cols_hip.argtypes + _drop
         L.isplib_gatv2_domain.restype = ctypes.c_int
         L.isplib_gatv2_domain.argtypes = [_i64, _i64, _i64, _i64]
         L.isplib_gatv2_bw_rows_workspace_bytes.restype = ctypes.c_size_t
@@ -2221,6 +2239,194 @@ def gat_edge_bw_cols(colptr, row_t, csr2csc, y, a_dst, a_src, a_edge, g, lse, ds
                                                _ptr(a_dst), _ptr(y), ldy, _ptr(a_src), _ptr(a_edge), heads, float(negative_slope), _ptr(g),
                                                ldg, _ptr(lse), _ptr(dsum), _ptr(dy), lddy, _ptr(dasrc), _stream(y.device))
     _check(st, "isplib_gat_edge_bw_cols_hip")
+    return dy, dasrc
+
+
+SEED_END = 2 ** 63                      # a dropout seed: a non-negative int64
+
+
+def gat_drop_threshold_py(p: float) -> int:
+    """T(p) = min(2^32 - 1, floor(p * 2^32)), the pure-Python mirror of isplib_gat_drop_threshold (p * 2^32 is exact in double)."""
+    v = math.floor(float(p) * 4294967296.0) if p == p and p > 0 else 0
+    return min(2 ** 32 - 1, max(0, int(v)))
+
+
+def gat_drop_threshold(p: float) -> int:
+    """isplib_gat_drop_threshold: the uint32 T(p) of the dropout keep bit, keep = word >= T."""
+    return int(lib().isplib_gat_drop_threshold(float(p)))
+
+
+def gat_drop_word(seed: int, pos: int, head: int) -> int:
+    """isplib_gat_drop_word: the 32-bit word of (seed, CSR position, head) the kernels compare with T(p) (csrc/gat_dropout.h)."""
+    return int(lib().isplib_gat_drop_word(int(seed), int(pos), int(head)))
+
+
+def gat_drop_scale(p: float) -> float:
+    """c = float32(1 / (1 - p)), as a Python float."""
+    return struct.unpack("f", struct.pack("f", 1.0 / (1.0 - float(p))))[0]
+
+
+def _gat_drop_args(threshold, scale, seed):
+    if isinstance(threshold, bool) or not isinstance(threshold, int) or not 0 <= threshold < 2 ** 32:
+        raise ValueError(f"isplib_amd: `threshold` must be an int in [0, 2^32), got {threshold!r}")
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < SEED_END:
+        raise ValueError(f"isplib_amd: `seed` must be an int in [0, 2^63), got {seed!r}")
+    scale = float(scale)
+    if not (0.0 < scale < float("inf")):
+        raise ValueError(f"isplib_amd: `scale` must be a positive finite number, got {scale!r}")
+    return threshold, scale, seed
+
+
+def gat_drop(rowptr, col, y, a_dst, a_src, a_edge, threshold: int, scale: float, seed: int, heads: int = 1, negative_slope: float = 0.2, *,
+             out=None, check: bool = True):
+    """`gat` / `gat_edge` (a_edge None or [nnz, heads]) with attention dropout (isplib_gat_drop_csr_hip): entry e and head h are kept where
+    gat_drop_word(seed, e, h) >= threshold, and z is scaled by `scale`; lse is that of the call without dropout.  Returns (z, lse)."""
+    threshold, scale, seed = _gat_drop_args(threshold, scale, seed)
+    if not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1 or rowptr.numel() < 1:
+        raise ValueError("isplib_amd: `rowptr` (m + 1 entries) must be a 1-D tensor")
+    m = rowptr.numel() - 1
+    if not isinstance(y, torch.Tensor) or y.dim() != 2:
+        raise ValueError("isplib_amd: `y` must be a 2-D tensor [n, heads * d]")
+    n, k = y.size(0), y.size(1)
+    ldy = _attn_dense(y, "y", n, None, "one row per column of the sparse operand")
+    d = _gat_heads(heads, k)
+    _gat_table(a_dst, "a_dst", m, heads)
+    _gat_table(a_src, "a_src", n, heads)
+    rowptr, col = _attn_structure(rowptr, col, "rowptr", "col", n, check)
+    if a_edge is not None:
+        _gat_table(a_edge, "a_edge", col.numel(), heads)
+    if out is not None:
+        z, lse = out
+        ldz = _attn_dense(z, "out[0]", m, k, "z")
+        _gat_table(lse, "out[1]", m, heads)
+    _gat_domain(n, heads, d, ldy)
+    if a_edge is not None:
+        _gat_edge_domain(col.numel(), heads)
+    _same_gpu((("y", y), ("a_dst", a_dst), ("a_src", a_src), ("rowptr", rowptr), ("col", col)) +
+              ((("a_edge", a_edge),) if a_edge is not None else ()) + ((("out[0]", out[0]), ("out[1]", out[1])) if out is not None else ()))
+    if out is None:
+        z = torch.empty((m, k), dtype=torch.float32, device=y.device)
+        lse = torch.empty((m, heads), dtype=torch.float32, device=y.device)
+        ldz = max(k, 1)
+    if m == 0 or k == 0:
+        if k == 0 and m > 0:
+            lse.fill_(float("-inf"))
+        return z, lse
+    rp = rowptr.data_ptr()
+    with torch.cuda.device(y.device):
+        st = lib().isplib_gat_drop_csr_hip(m, n, k, col.numel(), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8), _ptr(a_dst), _ptr(y),
+                                           ldy, _ptr(a_src), _ptr(a_edge) if a_edge is not None and col.numel() > 0 else None, heads,
+                                           float(negative_slope), _ptr(z), ldz, _ptr(lse), _stream(y.device), threshold, scale, seed)
+    _check(st, "isplib_gat_drop_csr_hip")
+    return z, lse
+
+
+def gat_drop_bw_rows(rowptr, col, y, a_dst, a_src, a_edge, g, z, lse, threshold: int, scale: float, seed: int, heads: int = 1,
+                     negative_slope: float = 0.2, *, out=None, want_edge: bool = True, check: bool = True):
+    """The backward of `gat_drop` over the rows (isplib_gat_drop_bw_rows_hip), with the mask of the same (threshold, seed).  Returns
+    (d_a_dst, D, d_a_edge); d_a_edge is None without `a_edge` or with want_edge=False.  `out` = (d_a_dst, D, d_a_edge or None)."""
+    threshold, scale, seed = _gat_drop_args(threshold, scale, seed)
+    if not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1 or rowptr.numel() < 1:
+        raise ValueError("isplib_amd: `rowptr` (m + 1 entries) must be a 1-D tensor")
+    m = rowptr.numel() - 1
+    if not isinstance(y, torch.Tensor) or y.dim() != 2:
+        raise ValueError("isplib_amd: `y` must be a 2-D tensor [n, heads * d]")
+    n, k = y.size(0), y.size(1)
+    ldy = _attn_dense(y, "y", n, None, "one row per column of the sparse operand")
+    d = _gat_heads(heads, k)
+    _gat_table(a_dst, "a_dst", m, heads)
+    _gat_table(a_src, "a_src", n, heads)
+    ldg = _attn_dense(g, "g", m, k, "the gradient of z")
+    ldz = _attn_dense(z, "z", m, k, "the forward's output")
+    _gat_table(lse, "lse", m, heads)
+    rowptr, col = _attn_structure(rowptr, col, "rowptr", "col", n, check)
+    nnz = col.numel()
+    want_edge = want_edge and a_edge is not None
+    if a_edge is not None:
+        _gat_table(a_edge, "a_edge", nnz, heads)
+    if out is not None:
+        _gat_table(out[0], "out[0]", m, heads)
+        _gat_table(out[1], "out[1]", m, heads)
+        if out[2] is not None:
+            if a_edge is None:
+                raise ValueError("isplib_amd: `out[2]` (d_a_edge) needs `a_edge`")
+            _gat_table(out[2], "out[2]", nnz, heads)
+    _gat_domain(n, heads, d, ldy)
+    if a_edge is not None:
+        _gat_edge_domain(nnz, heads)
+    _same_gpu((("y", y), ("a_dst", a_dst), ("a_src", a_src), ("g", g), ("z", z), ("lse", lse), ("rowptr", rowptr), ("col", col)) +
+              ((("a_edge", a_edge),) if a_edge is not None else ()) +
+              ((("out[0]", out[0]), ("out[1]", out[1]), ("out[2]", out[2])) if out is not None else ()))
+    if out is None:
+        out = (torch.empty((m, heads), dtype=torch.float32, device=y.device), torch.empty((m, heads), dtype=torch.float32, device=y.device),
+               torch.empty((nnz, heads), dtype=torch.float32, device=y.device) if want_edge else None)
+    dadst, dsum, dedge = out
+    if m == 0 or k == 0:
+        if k == 0 and m > 0:
+            dadst.zero_()
+            dsum.zero_()
+            if dedge is not None:
+                dedge.zero_()
+        return dadst, dsum, dedge
+    rp = rowptr.data_ptr()
+    with torch.cuda.device(y.device):
+        st = lib().isplib_gat_drop_bw_rows_hip(m, n, k, nnz, _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8), _ptr(a_dst), _ptr(y), ldy,
+                                               _ptr(a_src), _ptr(a_edge) if a_edge is not None and nnz > 0 else None, heads,
+                                               float(negative_slope), _ptr(g), ldg, _ptr(z), ldz, _ptr(lse), _ptr(dadst), _ptr(dsum),
+                                               _stream(y.device), _ptr(dedge) if dedge is not None and nnz > 0 else None, threshold, scale,
+                                               seed)
+    _check(st, "isplib_gat_drop_bw_rows_hip")
+    return dadst, dsum, dedge
+
+
+def gat_drop_bw_cols(colptr, row_t, csr2csc, y, a_dst, a_src, a_edge, g, lse, dsum, threshold: int, scale: float, seed: int, heads: int = 1,
+                     negative_slope: float = 0.2, *, out=None, check: bool = True):
+    """The backward of `gat_drop` over the columns (isplib_gat_drop_bw_cols_hip); `csr2csc` is required with or without `a_edge`: the
+    keep bit is a function of the entry's CSR position.  Returns (dy, d_a_src)."""
+    threshold, scale, seed = _gat_drop_args(threshold, scale, seed)
+    if not isinstance(colptr, torch.Tensor) or colptr.dim() != 1 or colptr.numel() < 1:
+        raise ValueError("isplib_amd: `colptr` (n + 1 entries) must be a 1-D tensor")
+    n = colptr.numel() - 1
+    ldy = _attn_dense(y, "y", n, None, "one row per column of the sparse operand")
+    k = y.size(1)
+    d = _gat_heads(heads, k)
+    if not isinstance(g, torch.Tensor) or g.dim() != 2:
+        raise ValueError("isplib_amd: `g` must be a 2-D tensor [m, heads * d]")
+    m = g.size(0)
+    ldg = _attn_dense(g, "g", m, k, "the gradient of z")
+    _gat_table(a_dst, "a_dst", m, heads)
+    _gat_table(a_src, "a_src", n, heads)
+    _gat_table(lse, "lse", m, heads)
+    _gat_table(dsum, "dsum", m, heads)
+    colptr, row_t = _attn_structure(colptr, row_t, "colptr", "row_t", m, check)
+    nnz = row_t.numel()
+    csr2csc = _gat_edge_positions(csr2csc, nnz, check)
+    if a_edge is not None:
+        _gat_table(a_edge, "a_edge", nnz, heads)
+    if out is not None:
+        lddy = _attn_dense(out[0], "out[0]", n, k, "dy")
+        _gat_table(out[1], "out[1]", n, heads)
+    _gat_domain(m, heads, d, ldg)
+    if a_edge is not None:
+        _gat_edge_domain(nnz, heads)
+    _same_gpu((("y", y), ("a_dst", a_dst), ("a_src", a_src), ("g", g), ("lse", lse), ("dsum", dsum), ("colptr", colptr), ("row_t", row_t),
+               ("csr2csc", csr2csc)) + ((("a_edge", a_edge),) if a_edge is not None else ()) +
+              ((("out[0]", out[0]), ("out[1]", out[1])) if out is not None else ()))
+    if out is None:
+        out = (torch.empty((n, k), dtype=torch.float32, device=y.device), torch.empty((n, heads), dtype=torch.float32, device=y.device))
+        lddy = max(k, 1)
+    dy, dasrc = out
+    if n == 0 or k == 0:
+        if k == 0 and n > 0:
+            dasrc.zero_()
+        return dy, dasrc
+    cp = colptr.data_ptr()
+    with torch.cuda.device(y.device):
+        st = lib().isplib_gat_drop_bw_cols_hip(m, n, k, nnz, _ptr(row_t), ctypes.c_void_p(cp), ctypes.c_void_p(cp + 8), _ptr(csr2csc),
+                                               _ptr(a_dst), _ptr(y), ldy, _ptr(a_src), _ptr(a_edge) if a_edge is not None and nnz > 0 else None,
+                                               heads, float(negative_slope), _ptr(g), ldg, _ptr(lse), _ptr(dsum), _ptr(dy), lddy, _ptr(dasrc),
+                                               _stream(y.device), threshold, scale, seed)
+    _check(st, "isplib_gat_drop_bw_cols_hip")
     return dy, dasrc
 
 

@@ -37,11 +37,21 @@
 // once (every stored entry belongs to one row).  The columns kernel walks the transposed structure and gathers a_edge[csr2csc[q], h]
 // behind one descriptor of nnz*H*4 bytes.  EDGE = false is the code of the entries without the term, instruction for instruction
 // (profiles/gat_edge_isa.txt).
+//
+// Attention dropout (isplib_gat_drop_*_hip): the three kernels are templates on DROP as well.  Every stored entry e and
+// head h has a keep bit q_e,h = word(seed, CSR position of e, h) >= T (gat_dropout.h: a pure function, recomputed in all three
+// kernels, nothing stored), and with c = float32(1 / (1 - p))
+//    z_i = c sum_e q_e a_e y_j      t_e = q_e c <g_i, y_j>_h      dy_j = c sum_{e -> j} q_e a_e g_i      a_e, lse, s_e, du_e's form unchanged
+// The softmax runs over ALL stored entries: l, m and lse do not see the mask.  The lane that loads an entry's index hashes the entry's
+// position (base + lane in the forward and the rows kernel; csr2csc[pos] in the columns kernel, which therefore needs csr2csc whenever
+// DROP is set) and hands the word across with the index; per edge and chunk one add of a per-lane constant, one fmix32, one compare and
+// one select remain.  c multiplies the finished rows of z and dy, and t_e per edge.  DROP = false is the code it was.
 #include <cfloat>
 #include <cmath>
 
 #include "common.h"
 #include "gather.h"
+#include "gat_dropout.h"
 
 namespace isplib {
 
@@ -77,6 +87,10 @@ struct GatArgs {
    const int64_t *epos;                    // columns: csr2csc [nnz], the CSR position of every entry of the transposed structure
    float *dedge;                           // rows: d a_edge [nnz, H], or NULL
    unsigned ebytes;                        // columns: nnz * H * 4
+   // DROP only (appended)
+   unsigned seed_lo, seed_hi;              // the two halves of the seed
+   unsigned T;                             // keep: word >= T
+   float c;                                // float32(1 / (1 - p))
 };
 
 template <int LPR, int NCH> struct GatCols {
@@ -191,7 +205,14 @@ __device__ __forceinline__ float gat_score_edge(float adst, float asrc, float ae
    return u > 0.0f ? u : ns * u;
 }
 
-template <int LPR, int NCH, int WAVES, bool EDGE>
+// DROP: the per-lane constant of each chunk's head (gat_dropout.h)
+template <int LPR, int NCH>
+__device__ __forceinline__ void gat_drop_heads(const GatArgs &a, const GatCols<LPR, NCH> &cm, unsigned (&hk)[NCH]) {
+#pragma unroll
+   for (int j = 0; j < NCH; j++) hk[j] = gat_drop_head(a.seed_hi, (unsigned)cm.head[j]);
+}
+
+template <int LPR, int NCH, int WAVES, bool EDGE, bool DROP>
 __global__ __launch_bounds__(WAVES * 64) void gat_fw_kernel(const GatArgs a) {
    constexpr int G = 64 / LPR, U = 4;
    const int lane = threadIdx.x & 63;
@@ -204,6 +225,8 @@ __global__ __launch_bounds__(WAVES * 64) void gat_fw_kernel(const GatArgs a) {
    const GatCols<LPR, NCH> cm(a, lc);
    float adst[NCH];
    gat_own_head<LPR, NCH>(a.own_score, row, a.heads, cm, adst);
+   [[maybe_unused]] unsigned hk[NCH];
+   if constexpr (DROP) gat_drop_heads<LPR, NCH>(a, cm, hk);
 
    float mrun[NCH], l[NCH], acc[NCH][4];
 #pragma unroll
@@ -218,6 +241,8 @@ __global__ __launch_bounds__(WAVES * 64) void gat_fw_kernel(const GatArgs a) {
    for (int64_t base = eb; base < ee; base += 64) {
       const int64_t pos = base + lane;
       const int id_l = pos < ee ? (int)a.indx[pos] : -1;
+      [[maybe_unused]] unsigned hw_l = 0u;               // DROP: the entry's part of the word, handed across lanes like the column id
+      if constexpr (DROP) hw_l = gat_drop_entry(a.seed_lo, (unsigned)pos);
       const int64_t left = ee - base;
       const int cnt = left < 64 ? (int)left : 64;
       [[maybe_unused]] __amdgpu_buffer_rsrc_t rse;      // EDGE: the batch's rows of a_edge and nothing else
@@ -226,6 +251,7 @@ __global__ __launch_bounds__(WAVES * 64) void gat_fw_kernel(const GatArgs a) {
       for (int s0 = 0; s0 < cnt; s0 += G * U) {
          v4i_t yv[U][NCH];
          float sc[U][NCH], se[EDGE ? U : 1][NCH];
+         [[maybe_unused]] unsigned hw[DROP ? U : 1];
 #pragma unroll
          for (int u = 0; u < U; u++) {
             unsigned off, offh;
@@ -233,6 +259,7 @@ __global__ __launch_bounds__(WAVES * 64) void gat_fw_kernel(const GatArgs a) {
             gat_load_wide<LPR, NCH>(rsy, off, cm, yv[u]);
             gat_load_head<LPR, NCH>(rss, offh, cm, sc[u]);
             if constexpr (EDGE) gat_load_head<LPR, NCH>(rse, (unsigned)((s0 + u * G + g) & 63) * hb, cm, se[u]);      // a slot past cnt: 0
+            if constexpr (DROP) hw[u] = (unsigned)__shfl((int)hw_l, (s0 + u * G + g) & 63);
          }
 #pragma unroll
          for (int j = 0; j < NCH; j++) {
@@ -252,9 +279,11 @@ __global__ __launch_bounds__(WAVES * 64) void gat_fw_kernel(const GatArgs a) {
 #pragma unroll
             for (int u = 0; u < U; u++) {
                const float w = (s0 + u * G + g < cnt) ? __expf(sc[u][j] - mnew) : 0.0f;
-               l[j] += w;
+               l[j] += w;                                 // the softmax runs over every stored entry: the mask reaches the values only
+               float wk = w;
+               if constexpr (DROP) wk = gat_drop_mix(hw[u], hk[j]) >= a.T ? w : 0.0f;
 #pragma unroll
-               for (int v = 0; v < 4; v++) acc[j][v] = fmaf(w, __int_as_float(yv[u][j][v]), acc[j][v]);
+               for (int v = 0; v < 4; v++) acc[j][v] = fmaf(wk, __int_as_float(yv[u][j][v]), acc[j][v]);
             }
          }
       }
@@ -279,12 +308,16 @@ __global__ __launch_bounds__(WAVES * 64) void gat_fw_kernel(const GatArgs a) {
    for (int j = 0; j < NCH; j++) {
 #pragma unroll
       for (int v = 0; v < 4; v++)
-         if (cm.ok[j][v]) a.out[(size_t)row * (size_t)a.ldout + (size_t)((j * LPR + lc) * 4 + v)] = empty ? 0.0f : acc[j][v] / l[j];
+         if (cm.ok[j][v]) {
+            float zv = empty ? 0.0f : acc[j][v] / l[j];
+            if constexpr (DROP) zv *= a.c;
+            a.out[(size_t)row * (size_t)a.ldout + (size_t)((j * LPR + lc) * 4 + v)] = zv;
+         }
       if (cm.first[j]) a.hout[(size_t)row * (size_t)a.heads + (size_t)cm.head[j]] = empty ? -INFINITY : mrun[j] + logf(l[j]);
    }
 }
 
-template <int LPR, int NCH, int WAVES, bool EDGE>
+template <int LPR, int NCH, int WAVES, bool EDGE, bool DROP>
 __global__ __launch_bounds__(WAVES * 64) void gat_bw_rows_kernel(const GatArgs a) {
    constexpr int G = 64 / LPR, U = 4;
    const int lane = threadIdx.x & 63;
@@ -321,11 +354,15 @@ __global__ __launch_bounds__(WAVES * 64) void gat_bw_rows_kernel(const GatArgs a
 #pragma unroll
    for (int j = 0; j < NCH; j++) acc[j] = 0.0f;
    [[maybe_unused]] const bool store = EDGE && a.dedge != nullptr;      // wave-uniform: a kernel argument
+   [[maybe_unused]] unsigned hk[NCH];
+   if constexpr (DROP) gat_drop_heads<LPR, NCH>(a, cm, hk);
 
    const unsigned ldyb = (unsigned)a.ldy * 4u, hb = (unsigned)a.heads * 4u;
    for (int64_t base = eb; base < ee; base += 64) {
       const int64_t pos = base + lane;
       const int id_l = pos < ee ? (int)a.indx[pos] : -1;
+      [[maybe_unused]] unsigned hw_l = 0u;               // DROP: the entry's part of the word, handed across lanes like the column id
+      if constexpr (DROP) hw_l = gat_drop_entry(a.seed_lo, (unsigned)pos);
       const int64_t left = ee - base;
       const int cnt = left < 64 ? (int)left : 64;
       [[maybe_unused]] __amdgpu_buffer_rsrc_t rse;      // EDGE: the batch's rows of a_edge and nothing else
@@ -334,6 +371,7 @@ __global__ __launch_bounds__(WAVES * 64) void gat_bw_rows_kernel(const GatArgs a
       for (int s0 = 0; s0 < cnt; s0 += G * U) {
          v4i_t yv[U][NCH];
          float sc[U][NCH], se[EDGE ? U : 1][NCH];
+         [[maybe_unused]] unsigned hw[DROP ? U : 1];
 #pragma unroll
          for (int u = 0; u < U; u++) {
             unsigned off, offh;
@@ -341,6 +379,7 @@ __global__ __launch_bounds__(WAVES * 64) void gat_bw_rows_kernel(const GatArgs a
             gat_load_wide<LPR, NCH>(rsy, off, cm, yv[u]);
             gat_load_head<LPR, NCH>(rss, offh, cm, sc[u]);
             if constexpr (EDGE) gat_load_head<LPR, NCH>(rse, (unsigned)((s0 + u * G + g) & 63) * hb, cm, se[u]);      // a slot past cnt: 0
+            if constexpr (DROP) hw[u] = (unsigned)__shfl((int)hw_l, (s0 + u * G + g) & 63);
          }
 #pragma unroll
          for (int u = 0; u < U; u++) {
@@ -350,6 +389,7 @@ __global__ __launch_bounds__(WAVES * 64) void gat_bw_rows_kernel(const GatArgs a
 #pragma unroll
             for (int j = 0; j < NCH; j++) {
                float slope;
+               if constexpr (DROP) t[j] *= gat_drop_mix(hw[u], hk[j]) >= a.T ? a.c : 0.0f;      // t_e = q_e c <g_i, y_j>_h
                if constexpr (EDGE) {
                   const float s = gat_score_edge(adst[j], sc[u][j], se[u][j], a.ns, slope);
                   const float x = __expf(s - lse[j]) * (t[j] - dsum[j]);
@@ -384,7 +424,7 @@ __global__ __launch_bounds__(WAVES * 64) void gat_bw_rows_kernel(const GatArgs a
 }
 
 // one wave per column j of A (a row of the transposed structure): y_j and a_src[j,.] in registers; g_i, a_dst, lse, D of row i gathered
-template <int LPR, int NCH, int WAVES, bool EDGE>
+template <int LPR, int NCH, int WAVES, bool EDGE, bool DROP>
 __global__ __launch_bounds__(WAVES * 64) void gat_bw_cols_kernel(const GatArgs a) {
    constexpr int G = 64 / LPR, U = NCH >= 2 ? 2 : 4;
    const int lane = threadIdx.x & 63;
@@ -401,6 +441,8 @@ __global__ __launch_bounds__(WAVES * 64) void gat_bw_cols_kernel(const GatArgs a
    float yv[NCH][4], asrc[NCH];
    gat_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm, yv);
    gat_own_head<LPR, NCH>(a.own_score, row, a.heads, cm, asrc);
+   [[maybe_unused]] unsigned hk[NCH];
+   if constexpr (DROP) gat_drop_heads<LPR, NCH>(a, cm, hk);
 
    float acc[NCH][4], accs[NCH];
 #pragma unroll
@@ -415,13 +457,16 @@ __global__ __launch_bounds__(WAVES * 64) void gat_bw_cols_kernel(const GatArgs a
       const int64_t pos = base + lane;
       const int id_l = pos < ee ? (int)a.indx[pos] : -1;
       [[maybe_unused]] int ep_l = -1;                   // EDGE: the entry's CSR position (nnz < 2^31), handed across lanes like the row id
-      if constexpr (EDGE) ep_l = pos < ee ? (int)a.epos[pos] : -1;
+      if constexpr (EDGE || DROP) ep_l = pos < ee ? (int)a.epos[pos] : -1;
+      [[maybe_unused]] unsigned hw_l = 0u;               // DROP: the entry's part of the word, of its CSR position
+      if constexpr (DROP) hw_l = gat_drop_entry(a.seed_lo, (unsigned)ep_l);
       const int64_t left = ee - base;
       const int cnt = left < 64 ? (int)left : 64;
 #pragma unroll 1
       for (int s0 = 0; s0 < cnt; s0 += G * U) {
          v4i_t gg[U][NCH];
          float ad[U][NCH], ls[U][NCH], ds[U][NCH], se[EDGE ? U : 1][NCH];
+         [[maybe_unused]] unsigned hw[DROP ? U : 1];
 #pragma unroll
          for (int u = 0; u < U; u++) {
             unsigned off, offh;
@@ -434,6 +479,7 @@ __global__ __launch_bounds__(WAVES * 64) void gat_bw_cols_kernel(const GatArgs a
                const int ep = __shfl(ep_l, (s0 + u * G + g) & 63);
                gat_load_head<LPR, NCH>(rse, ep < 0 ? BUF_OOB : (unsigned)ep * hb, cm, se[u]);      // ep * hb < nnz*H*4 <= 3.5 GiB
             }
+            if constexpr (DROP) hw[u] = (unsigned)__shfl((int)hw_l, (s0 + u * G + g) & 63);
          }
 #pragma unroll
          for (int u = 0; u < U; u++) {
@@ -447,9 +493,15 @@ __global__ __launch_bounds__(WAVES * 64) void gat_bw_cols_kernel(const GatArgs a
                if constexpr (EDGE) s = gat_score_edge(ad[u][j], asrc[j], se[u][j], a.ns, slope);
                else s = gat_score(ad[u][j], asrc[j], a.ns, slope);
                const float ae = live ? __expf(s - ls[u][j]) : 0.0f;
+               [[maybe_unused]] bool keep = true;
+               if constexpr (DROP) {
+                  keep = gat_drop_mix(hw[u], hk[j]) >= a.T;
+                  t[j] *= keep ? a.c : 0.0f;              // t_e = q_e c <g_i, y_j>_h
+               }
                accs[j] += live ? ae * (t[j] - ds[u][j]) * slope : 0.0f;
+               const float aek = keep ? ae : 0.0f;
 #pragma unroll
-               for (int v = 0; v < 4; v++) acc[j][v] = fmaf(ae, __int_as_float(gg[u][j][v]), acc[j][v]);
+               for (int v = 0; v < 4; v++) acc[j][v] = fmaf(aek, __int_as_float(gg[u][j][v]), acc[j][v]);
             }
          }
       }
@@ -467,38 +519,53 @@ __global__ __launch_bounds__(WAVES * 64) void gat_bw_cols_kernel(const GatArgs a
    for (int j = 0; j < NCH; j++) {
 #pragma unroll
       for (int v = 0; v < 4; v++)
-         if (cm.ok[j][v]) a.out[(size_t)row * (size_t)a.ldout + (size_t)((j * LPR + lc) * 4 + v)] = acc[j][v];      // no incoming entry: 0
+         if (cm.ok[j][v])                               // no incoming entry: 0
+            a.out[(size_t)row * (size_t)a.ldout + (size_t)((j * LPR + lc) * 4 + v)] = DROP ? acc[j][v] * a.c : acc[j][v];
       if (cm.first[j]) a.hout[(size_t)row * (size_t)a.heads + (size_t)cm.head[j]] = accs[j];
    }
 }
 
 enum { GAT_FW = 0, GAT_BW_ROWS = 1, GAT_BW_COLS = 2 };
 
-template <int LPR, int NCH, bool EDGE>
+template <int LPR, int NCH, bool EDGE, bool DROP>
 static int launch_gat(int which, const GatArgs &a, const char *entry, hipStream_t st) {
    constexpr int WAVES = 4;
    const int64_t nb = (a.rows + WAVES - 1) / WAVES;
    if (nb > 0x7fffffffLL) return fail(ISPLIB_FAIL, entry, "too many rows for one launch");
    const dim3 grid((unsigned)nb), block(WAVES * 64);
-   if (which == GAT_FW) hipLaunchKernelGGL((gat_fw_kernel<LPR, NCH, WAVES, EDGE>), grid, block, 0, st, a);
-   else if (which == GAT_BW_ROWS) hipLaunchKernelGGL((gat_bw_rows_kernel<LPR, NCH, WAVES, EDGE>), grid, block, 0, st, a);
-   else hipLaunchKernelGGL((gat_bw_cols_kernel<LPR, NCH, WAVES, EDGE>), grid, block, 0, st, a);
+   if (which == GAT_FW) hipLaunchKernelGGL((gat_fw_kernel<LPR, NCH, WAVES, EDGE, DROP>), grid, block, 0, st, a);
+   else if (which == GAT_BW_ROWS) hipLaunchKernelGGL((gat_bw_rows_kernel<LPR, NCH, WAVES, EDGE, DROP>), grid, block, 0, st, a);
+   else hipLaunchKernelGGL((gat_bw_cols_kernel<LPR, NCH, WAVES, EDGE, DROP>), grid, block, 0, st, a);
    return check_launch(entry);
 }
 
-// the width dispatch of attention.hip, up to two chunks per lane; EDGE: the kernels with the per-edge term
-template <bool EDGE>
+// the width dispatch of attention.hip, up to two chunks per lane; EDGE: the kernels with the per-edge term; DROP: with attention dropout
+template <bool EDGE, bool DROP>
 static int gat_by_width_of(int which, const GatArgs &a, const char *entry, hipStream_t st) {
    const int64_t w = (a.k + 3) / 4;
-   if (w <= 8) return launch_gat<8, 1, EDGE>(which, a, entry, st);
-   if (w <= 16) return launch_gat<16, 1, EDGE>(which, a, entry, st);
-   if (w <= 32) return launch_gat<32, 1, EDGE>(which, a, entry, st);
-   if (w <= 64) return launch_gat<64, 1, EDGE>(which, a, entry, st);
-   return launch_gat<64, 2, EDGE>(which, a, entry, st);
+   if (w <= 8) return launch_gat<8, 1, EDGE, DROP>(which, a, entry, st);
+   if (w <= 16) return launch_gat<16, 1, EDGE, DROP>(which, a, entry, st);
+   if (w <= 32) return launch_gat<32, 1, EDGE, DROP>(which, a, entry, st);
+   if (w <= 64) return launch_gat<64, 1, EDGE, DROP>(which, a, entry, st);
+   return launch_gat<64, 2, EDGE, DROP>(which, a, entry, st);
 }
 
-static int gat_by_width(int which, const GatArgs &a, bool edge, const char *entry, hipStream_t st) {
-   return edge ? gat_by_width_of<true>(which, a, entry, st) : gat_by_width_of<false>(which, a, entry, st);
+static int gat_by_width(int which, const GatArgs &a, bool edge, bool drop, const char *entry, hipStream_t st) {
+   if (drop) return edge ? gat_by_width_of<true, true>(which, a, entry, st) : gat_by_width_of<false, true>(which, a, entry, st);
+   return edge ? gat_by_width_of<true, false>(which, a, entry, st) : gat_by_width_of<false, false>(which, a, entry, st);
+}
+
+// the dropout of one call (isplib_gat_drop_*_hip): the threshold T(p), c = float32(1 / (1 - p)) and the seed; none: the entries without it
+struct GatDrop {
+   bool on;
+   uint32_t threshold;
+   float scale;
+   uint64_t seed;
+};
+static const GatDrop GAT_NO_DROP = {false, 0u, 1.0f, 0ull};
+
+static void gat_set_drop(GatArgs &a, const GatDrop &dr) {
+   a.seed_lo = (unsigned)dr.seed; a.seed_hi = (unsigned)(dr.seed >> 32); a.T = dr.threshold; a.c = dr.scale;
 }
 
 // what a descriptor over `rows` rows of k floats at pitch ld may answer: the extent a row-strided view owns, not rows * ld
@@ -526,7 +593,8 @@ static const char *const GAT_EDGE_DOMAIN = "outside isplib_gat_edge_serves(nnz, 
 // The three entries, with and without the per-edge term (edge: a_edge [nnz, heads]; csr2csc for the columns; d_a_edge may be NULL).
 static int gat_forward(const char *entry, bool edge, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
                        const int64_t *pntre, const float *a_dst, const float *y, int64_t ldy, const float *a_src, const float *a_edge,
-                       int64_t heads, float negative_slope, float *z, int64_t ldz, float *lse, void *stream) {
+                       int64_t heads, float negative_slope, float *z, int64_t ldz, float *lse, void *stream,
+                       const GatDrop &dr = GAT_NO_DROP) {
    clear_error();
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
    if (m == 0 || k == 0) return ISPLIB_SUCCESS;
@@ -544,13 +612,15 @@ static int gat_forward(const char *entry, bool edge, int64_t m, int64_t n, int64
    a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? gat_extent(n, k, ldy) : 0u;
    a.t0 = a_src; a.tbytes = nnz > 0 ? gat_extent(n, heads, heads) : 0u;
    a.edge = edge ? a_edge : nullptr;
-   return gat_by_width(GAT_FW, a, edge, entry, (hipStream_t)stream);
+   gat_set_drop(a, dr);
+   return gat_by_width(GAT_FW, a, edge, dr.on, entry, (hipStream_t)stream);
 }
 
 static int gat_backward_rows(const char *entry, bool edge, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx,
                              const int64_t *pntrb, const int64_t *pntre, const float *a_dst, const float *y, int64_t ldy, const float *a_src,
                              const float *a_edge, int64_t heads, float negative_slope, const float *g, int64_t ldg, const float *z,
-                             int64_t ldz, const float *lse, float *d_a_dst, float *dsum, float *d_a_edge, void *stream) {
+                             int64_t ldz, const float *lse, float *d_a_dst, float *dsum, float *d_a_edge, void *stream,
+                             const GatDrop &dr = GAT_NO_DROP) {
    clear_error();
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
    if (m == 0 || k == 0) return ISPLIB_SUCCESS;
@@ -568,18 +638,20 @@ static int gat_backward_rows(const char *entry, bool edge, int64_t m, int64_t n,
    a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? gat_extent(n, k, ldy) : 0u;
    a.t0 = a_src; a.tbytes = nnz > 0 ? gat_extent(n, heads, heads) : 0u;
    a.edge = edge ? a_edge : nullptr; a.dedge = edge ? d_a_edge : nullptr;
-   return gat_by_width(GAT_BW_ROWS, a, edge, entry, (hipStream_t)stream);
+   gat_set_drop(a, dr);
+   return gat_by_width(GAT_BW_ROWS, a, edge, dr.on, entry, (hipStream_t)stream);
 }
 
 static int gat_backward_cols(const char *entry, bool edge, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t,
                              const int64_t *colb, const int64_t *cole, const int64_t *csr2csc, const float *a_dst, const float *y, int64_t ldy,
                              const float *a_src, const float *a_edge, int64_t heads, float negative_slope, const float *g, int64_t ldg,
-                             const float *lse, const float *dsum, float *dy, int64_t lddy, float *d_a_src, void *stream) {
+                             const float *lse, const float *dsum, float *dy, int64_t lddy, float *d_a_src, void *stream,
+                             const GatDrop &dr = GAT_NO_DROP) {
    clear_error();
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
    if (n == 0 || k == 0) return ISPLIB_SUCCESS;
    if (!colb || !cole || !y || !a_src || !dy || !d_a_src ||
-       (nnz > 0 && (!row_t || !a_dst || !g || !lse || !dsum || (edge && (!csr2csc || !a_edge)))))
+       (nnz > 0 && (!row_t || !a_dst || !g || !lse || !dsum || (edge && !a_edge) || ((edge || dr.on) && !csr2csc))))
       return fail(ISPLIB_FAIL, entry, "null operand");
    if (ldy < k || lddy < k) return fail(ISPLIB_FAIL, entry, "leading dimension smaller than k");
    if (heads >= 1 && k % heads != 0) return fail(ISPLIB_FAIL, entry, "k is not a multiple of heads");
@@ -593,9 +665,11 @@ static int gat_backward_cols(const char *entry, bool edge, int64_t m, int64_t n,
    a.y = g; a.ldy = ldg; a.ybytes = nnz > 0 ? gat_extent(m, k, ldg) : 0u;
    a.t0 = a_dst; a.t1 = lse; a.t2 = dsum; a.tbytes = nnz > 0 ? gat_extent(m, heads, heads) : 0u;
    if (edge) {
-      a.edge = a_edge; a.epos = csr2csc; a.ebytes = nnz > 0 ? gat_extent(nnz, heads, heads) : 0u;
+      a.edge = a_edge; a.ebytes = nnz > 0 ? gat_extent(nnz, heads, heads) : 0u;
    }
-   return gat_by_width(GAT_BW_COLS, a, edge, entry, (hipStream_t)stream);
+   if (edge || dr.on) a.epos = csr2csc;                  // DROP: the keep bit is a function of the entry's CSR position
+   gat_set_drop(a, dr);
+   return gat_by_width(GAT_BW_COLS, a, edge, dr.on, entry, (hipStream_t)stream);
 }
 
 }  // namespace isplib
@@ -655,3 +729,43 @@ extern "C" int isplib_gat_edge_bw_cols_hip(int64_t m, int64_t n, int64_t k, int6
                             negative_slope, g, ldg, lse, dsum, dy, lddy, d_a_src, stream);
 }
 
+
+// attention dropout: the argument lists of the isplib_gat_edge_* entries, a_edge / d_a_edge may be NULL (no per-edge term), then
+// threshold, scale, seed.  A scale that is no positive finite number is refused: it would poison every row.
+static bool gat_drop_ok(float scale) { return scale > 0.0f && scale <= FLT_MAX; }
+
+extern "C" uint32_t isplib_gat_drop_threshold(double p) { return gat_drop_threshold(p); }
+
+extern "C" uint32_t isplib_gat_drop_word(uint64_t seed, int64_t pos, int64_t head) { return gat_drop_word(seed, pos, head); }
+
+extern "C" int isplib_gat_drop_csr_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                                       const int64_t *pntre, const float *a_dst, const float *y, int64_t ldy, const float *a_src,
+                                       const float *a_edge, int64_t heads, float negative_slope, float *z, int64_t ldz, float *lse,
+                                       void *stream, uint32_t threshold, float scale, uint64_t seed) {
+   clear_error();
+   if (!gat_drop_ok(scale)) return fail(ISPLIB_FAIL, "isplib_gat_drop_csr_hip", "scale must be a positive finite number");
+   return gat_forward("isplib_gat_drop_csr_hip", a_edge != nullptr, m, n, k, nnz, indx, pntrb, pntre, a_dst, y, ldy, a_src, a_edge, heads,
+                      negative_slope, z, ldz, lse, stream, GatDrop{true, threshold, scale, seed});
+}
+
+extern "C" int isplib_gat_drop_bw_rows_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                                           const int64_t *pntre, const float *a_dst, const float *y, int64_t ldy, const float *a_src,
+                                           const float *a_edge, int64_t heads, float negative_slope, const float *g, int64_t ldg,
+                                           const float *z, int64_t ldz, const float *lse, float *d_a_dst, float *dsum, void *stream,
+                                           float *d_a_edge, uint32_t threshold, float scale, uint64_t seed) {
+   clear_error();
+   if (!gat_drop_ok(scale)) return fail(ISPLIB_FAIL, "isplib_gat_drop_bw_rows_hip", "scale must be a positive finite number");
+   return gat_backward_rows("isplib_gat_drop_bw_rows_hip", a_edge != nullptr, m, n, k, nnz, indx, pntrb, pntre, a_dst, y, ldy, a_src, a_edge,
+                            heads, negative_slope, g, ldg, z, ldz, lse, d_a_dst, dsum, d_a_edge, stream, GatDrop{true, threshold, scale, seed});
+}
+
+extern "C" int isplib_gat_drop_bw_cols_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t, const int64_t *colb,
+                                           const int64_t *cole, const int64_t *csr2csc, const float *a_dst, const float *y, int64_t ldy,
+                                           const float *a_src, const float *a_edge, int64_t heads, float negative_slope, const float *g,
+                                           int64_t ldg, const float *lse, const float *dsum, float *dy, int64_t lddy, float *d_a_src,
+                                           void *stream, uint32_t threshold, float scale, uint64_t seed) {
+   clear_error();
+   if (!gat_drop_ok(scale)) return fail(ISPLIB_FAIL, "isplib_gat_drop_bw_cols_hip", "scale must be a positive finite number");
+   return gat_backward_cols("isplib_gat_drop_bw_cols_hip", a_edge != nullptr, m, n, k, nnz, row_t, colb, cole, csr2csc, a_dst, y, ldy, a_src,
+                            a_edge, heads, negative_slope, g, ldg, lse, dsum, dy, lddy, d_a_src, stream, GatDrop{true, threshold, scale, seed});
+}

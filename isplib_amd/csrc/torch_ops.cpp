@@ -1499,6 +1499,142 @@ Tensor gat_edge_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Ten
    return GatEdgeSpmm::apply(rowptr, col, colptr, row_t, csr2csc, y, a_dst, a_src, a_edge, heads, negative_slope)[0];
 }
 
+// ---- the GAT aggregation with attention dropout (isplib_gat_drop_*_hip) ----------
+// The coefficients are dropped after the softmax, per stored entry and head; the keep bit is a pure function of (seed, CSR position,
+// head), so the backward regenerates the mask from the seed.  a_edge is optional (`edge` false: no per-edge term).  Saved for backward: what
+// GatEdgeSpmm saves, plus the two scalars p and seed.  Only the kernels whose gradients are asked for run.
+class GatDropSpmm : public torch::autograd::Function<GatDropSpmm> {
+ public:
+   static variable_list forward(AutogradContext *ctx, Variable rowptr, Variable col, Variable colptr, Variable row_t, Variable csr2csc,
+                                Variable y, Variable a_dst, Variable a_src, Variable a_edge, bool edge, int64_t heads, double negative_slope,
+                                double p, int64_t seed) {
+      check_index(rowptr, "rowptr"); check_index(col, "col"); check_index(colptr, "colptr"); check_index(row_t, "row_t");
+      check_index(csr2csc, "csr2csc");
+      TORCH_CHECK(y.defined() && y.dim() == 2, "isplib: gat_drop_spmm needs a 2-D `y` [N, heads * d]");
+      TORCH_CHECK(p > 0.0 && p < 1.0, "isplib: gat_drop_spmm: `p` must lie in (0, 1), got ", p, " (p == 0: gat_spmm / gat_edge_spmm)");
+      TORCH_CHECK(seed >= 0, "isplib: gat_drop_spmm: `seed` must be a non-negative int64, got ", seed);
+      OpTimer timer("FUSEDMM_GAT_DROP_FW", y);
+      const int64_t M = rowptr.numel() - 1, N = colptr.numel() - 1, K = y.size(1), nnz = col.numel();
+      TORCH_CHECK(M >= 0 && N >= 0 && row_t.numel() == nnz && csr2csc.numel() == nnz,
+                  "isplib: gat_drop_spmm: `rowptr` / `colptr` need one entry more than rows / columns, `row_t` and `csr2csc` one entry per "
+                  "stored entry (", nnz, "), got ", row_t.numel(), " and ", csr2csc.numel());
+      TORCH_CHECK(heads >= 1 && K % heads == 0, "isplib: gat_drop_spmm: the width of `y` (", K, ") must be heads * d, got heads = ", heads);
+      const AttnOperand yo = gat_operand(y, "y", N, K);
+      TORCH_CHECK(a_dst.defined() && a_src.defined(), "isplib: gat_drop_spmm needs `a_dst` [M, heads] and `a_src` [N, heads]");
+      const Tensor ad = gat_table(a_dst, "a_dst", M, heads), as = gat_table(a_src, "a_src", N, heads);
+      Tensor ae;
+      if (edge) {
+         check_float(a_edge, "a_edge");
+         TORCH_CHECK(a_edge.dim() == 2 && a_edge.size(0) == nnz && a_edge.size(1) == heads, "isplib: gat_drop_spmm: `a_edge` must be [", nnz,
+                     ", ", heads, "] (one row per stored entry, in the order of `col`), got ", a_edge.sizes());
+         TORCH_CHECK(a_edge.device() == y.device(), "isplib: gat_drop_spmm: every operand must be on y's device");
+         ae = a_edge.contiguous();
+      }
+      for (const Tensor *t : {&rowptr, &col, &colptr, &row_t, &csr2csc, &a_dst, &a_src})
+         TORCH_CHECK(t->device() == y.device(), "isplib: gat_drop_spmm: every operand must be on y's device");
+      TORCH_CHECK(K == 0 || isplib_gat_serves(N, heads, K / heads, yo.ld), "isplib: gat_drop_spmm: outside isplib_gat_serves (heads * d <= ",
+                  ISPLIB_GAT_K_MAX, ", heads == 1 or d a power of two >= 4, N < 2^31, N * pitch * 4 <= 3.5 GiB): N = ", N, ", heads = ", heads,
+                  ", d = ", K / heads, ", pitch = ", yo.ld);
+      TORCH_CHECK(K == 0 || isplib_gat_serves(M, heads, K / heads, K),
+                  "isplib: gat_drop_spmm: outside isplib_gat_serves for the gathered rows of the gradient: M = ", M, ", K = ", K);
+      TORCH_CHECK(nnz < (1LL << 31), "isplib: gat_drop_spmm: the keep bit is defined for CSR positions below 2^31, got nnz = ", nnz);
+      TORCH_CHECK(!edge || isplib_gat_edge_serves(nnz, heads), "isplib: gat_drop_spmm: outside isplib_gat_edge_serves (nnz < 2^31, nnz * heads "
+                  "* 4 <= 3.5 GiB, `a_edge` behind one buffer descriptor): nnz = ", nnz, ", heads = ", heads,
+                  " -- pass fewer heads per call, on column views of `y`");
+      c10::DeviceGuard guard(y.device());
+      const Tensor rp = rowptr.contiguous(), cl = col.contiguous();
+      Tensor z = at::empty({M, K}, y.options()), lse = at::empty({M, heads}, y.options());
+      if (M > 0 && K > 0) {
+         const int st = isplib_gat_drop_csr_hip(M, N, K, nnz, cl.data_ptr<int64_t>(), rp.data_ptr<int64_t>(), rp.data_ptr<int64_t>() + 1,
+                                                ad.data_ptr<float>(), nnz > 0 ? yo.t.data_ptr<float>() : nullptr, yo.ld,
+                                                nnz > 0 ? as.data_ptr<float>() : nullptr, edge && nnz > 0 ? ae.data_ptr<float>() : nullptr,
+                                                heads, (float)negative_slope, z.data_ptr<float>(), K, lse.data_ptr<float>(), current_stream(y),
+                                                isplib_gat_drop_threshold(p), (float)(1.0 / (1.0 - p)), (uint64_t)seed);
+         check_status(st, "isplib_gat_drop_csr_hip");
+      } else if (M > 0) {
+         lse.fill_(-std::numeric_limits<float>::infinity());
+      }
+      ctx->saved_data["heads"] = heads;
+      ctx->saved_data["negative_slope"] = negative_slope;
+      ctx->saved_data["p"] = p;
+      ctx->saved_data["seed"] = seed;
+      ctx->saved_data["edge"] = edge;
+      ctx->save_for_backward({rp, cl, colptr, row_t, y, a_dst, a_src, z, lse, a_edge, csr2csc});
+      return {z};
+   }
+
+   static variable_list backward(AutogradContext *ctx, variable_list grad_outs) {
+      OpTimer timer("FUSEDMM_GAT_DROP_BW", grad_outs[0]);
+      const bool edge = ctx->saved_data["edge"].toBool();
+      const bool need_y = ctx->needs_input_grad(5), need_dst = ctx->needs_input_grad(6), need_src = ctx->needs_input_grad(7),
+                 need_edge = edge && ctx->needs_input_grad(8);
+      auto grad_y = Variable(), grad_dst = Variable(), grad_src = Variable(), grad_edge = Variable();
+      if (need_y || need_dst || need_src || need_edge) {
+         auto saved = ctx->get_saved_variables();
+         auto rp = saved[0], cl = saved[1], colptr = saved[2].contiguous(), row_t = saved[3].contiguous(), y = saved[4], z = saved[7], lse = saved[8];
+         const Tensor csr2csc = saved[10].contiguous();
+         const int64_t heads = ctx->saved_data["heads"].toInt();
+         const float ns = (float)ctx->saved_data["negative_slope"].toDouble();
+         const double p = ctx->saved_data["p"].toDouble();
+         const uint32_t threshold = isplib_gat_drop_threshold(p);
+         const float scale = (float)(1.0 / (1.0 - p));
+         const uint64_t seed = (uint64_t)ctx->saved_data["seed"].toInt();
+         const int64_t M = rp.numel() - 1, N = colptr.numel() - 1, K = y.size(1), nnz = cl.numel();
+         const AttnOperand yo = gat_operand(y, "y", N, K);
+         const Tensor ad = gat_table(saved[5], "a_dst", M, heads), as = gat_table(saved[6], "a_src", N, heads);
+         const Tensor ae = edge ? saved[9].contiguous() : Tensor();
+         const float *aep = edge && nnz > 0 ? ae.data_ptr<float>() : nullptr;
+         const AttnOperand go = gat_operand(grad_outs[0].to(at::kFloat), "grad_out", M, K);
+         c10::DeviceGuard guard(y.device());
+         // the rows kernel always runs (D feeds the columns kernel); it gets d a_edge only when a_edge asks -- no [nnz, H] tensor otherwise
+         Tensor dadst = at::empty({M, heads}, y.options()), dsum = at::empty({M, heads}, y.options());
+         Tensor dedge = need_edge ? at::empty({nnz, heads}, y.options()) : Tensor();
+         if (M > 0 && K > 0) {
+            const int st = isplib_gat_drop_bw_rows_hip(M, N, K, nnz, cl.data_ptr<int64_t>(), rp.data_ptr<int64_t>(), rp.data_ptr<int64_t>() + 1,
+                                                       ad.data_ptr<float>(), nnz > 0 ? yo.t.data_ptr<float>() : nullptr, yo.ld,
+                                                       nnz > 0 ? as.data_ptr<float>() : nullptr, aep, heads, ns, go.t.data_ptr<float>(), go.ld,
+                                                       z.data_ptr<float>(), K, lse.data_ptr<float>(), dadst.data_ptr<float>(),
+                                                       dsum.data_ptr<float>(), current_stream(y),
+                                                       need_edge && nnz > 0 ? dedge.data_ptr<float>() : nullptr, threshold, scale, seed);
+            check_status(st, "isplib_gat_drop_bw_rows_hip");
+         } else if (M > 0) {
+            dadst.zero_();
+            if (need_edge) dedge.zero_();
+         }
+         if (need_dst) grad_dst = dadst;
+         if (need_edge) grad_edge = dedge;
+         if (need_y || need_src) {
+            TORCH_CHECK(K == 0 || isplib_gat_serves(M, heads, K / heads, go.ld),
+                        "isplib: gat_drop_spmm backward: outside isplib_gat_serves for the gathered rows of the gradient: M = ", M, ", K = ", K);
+            Tensor dy = at::empty({N, K}, y.options()), dasrc = at::empty({N, heads}, y.options());
+            if (N > 0 && K > 0) {
+               const int st = isplib_gat_drop_bw_cols_hip(M, N, K, nnz, row_t.data_ptr<int64_t>(), colptr.data_ptr<int64_t>(),
+                                                          colptr.data_ptr<int64_t>() + 1, nnz > 0 ? csr2csc.data_ptr<int64_t>() : nullptr,
+                                                          nnz > 0 ? ad.data_ptr<float>() : nullptr, yo.t.data_ptr<float>(), yo.ld,
+                                                          as.data_ptr<float>(), aep, heads, ns, nnz > 0 ? go.t.data_ptr<float>() : nullptr, go.ld,
+                                                          lse.data_ptr<float>(), dsum.data_ptr<float>(), dy.data_ptr<float>(), K,
+                                                          dasrc.data_ptr<float>(), current_stream(y), threshold, scale, seed);
+               check_status(st, "isplib_gat_drop_bw_cols_hip");
+            } else if (N > 0) {
+               dasrc.zero_();
+            }
+            if (need_y) grad_y = dy;
+            if (need_src) grad_src = dasrc;
+         }
+      }
+      return {Variable(), Variable(), Variable(), Variable(), Variable(), grad_y, grad_dst, grad_src, grad_edge, Variable(), Variable(),
+              Variable(), Variable(), Variable()};
+   }
+};
+
+Tensor gat_drop_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor csr2csc, Tensor y, Tensor a_dst, Tensor a_src,
+                     c10::optional<Tensor> a_edge, int64_t heads, double negative_slope, double p, int64_t seed) {
+   // without the per-edge term the slot holds an empty placeholder (an autograd function takes defined tensors)
+   const bool edge = a_edge.has_value() && a_edge->defined();
+   return GatDropSpmm::apply(rowptr, col, colptr, row_t, csr2csc, y, a_dst, a_src, edge ? *a_edge : at::empty({0}, y.options()), edge, heads,
+                             negative_slope, p, seed)[0];
+}
+
 // ---- the same aggregation for bf16 / fp16 operands (isplib_attention16_*_hip) ----------
 // x and y go in as they lie, z / dx / dy come back in their dtype, lse and D stay fp32: no fp32 [*, K] tensor in either direction.  Saved
 // for backward: the structure, x, y and lse -- NOT z: the rows kernel forms D_i from the row's edges (the rounded z would cost every
@@ -2015,6 +2151,8 @@ TORCH_LIBRARY(isplib, m) {
          &gat_spmm);
    m.def("gat_edge_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor csr2csc, Tensor y, Tensor a_dst, Tensor a_src, Tensor a_edge, int heads, float negative_slope) -> Tensor",
          &gat_edge_spmm);
+   m.def("gat_drop_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor csr2csc, Tensor y, Tensor a_dst, Tensor a_src, Tensor? a_edge, int heads, float negative_slope, float p, int seed) -> Tensor",
+         &gat_drop_spmm);
    m.def("attention_spmm16(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor x, Tensor y, float scale) -> Tensor", &attention_spmm16);
    m.def("gat_spmm16(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor y, Tensor a_dst, Tensor a_src, int heads, float negative_slope) -> Tensor",
          &gat_spmm16);

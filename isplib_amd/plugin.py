@@ -740,7 +740,7 @@ def attention_matmul(src, x: torch.Tensor, y: Optional[torch.Tensor] = None, sca
 
 
 def gat_matmul(src, y: torch.Tensor, a_dst: torch.Tensor, a_src: torch.Tensor, heads: int = 1, negative_slope: float = 0.2,
-               a_edge: Optional[torch.Tensor] = None) -> torch.Tensor:
+               a_edge: Optional[torch.Tensor] = None, dropout: float = 0.0, training: bool = True, seed: Optional[int] = None) -> torch.Tensor:
     """GAT attention aggregation over the stored entries of `src`, all heads in one launch (include/isplib_hip.h, isplib_gat_csr_hip):
     ``z[i, head h] = sum_j softmax_j(leaky_relu(a_dst[i, h] + a_src[j, h])) y[j, head h]`` over the entries (i, j) of row i -- the
     aggregation of GATConv, with its autograd backward in `y`, `a_dst` and `a_src` (torch.ops.isplib.gat_spmm).  `y` [N, heads * d]
@@ -764,7 +764,20 @@ def gat_matmul(src, y: torch.Tensor, a_dst: torch.Tensor, a_src: torch.Tensor, h
     the COO index of every entry, by which the edge attributes are permuted.  Outside isplib_gat_edge_serves (nnz < 2^31 and
     nnz * heads * 4 <= 3.5 GiB) the call raises ValueError: pass fewer heads per call, on column views of `y`.  With a 16-bit `y`
     and ISPLIB_HALF_GAT set (to any value) the call takes the conversion route -- there is no 16-bit edge kernel; `a_edge` may then
-    be float32 or of y's dtype."""
+    be float32 or of y's dtype.
+    `dropout` (GATConv's ``dropout``; a Python float or int in [0, 1)) drops attention coefficients AFTER the softmax, per stored entry
+    and per head, and scales the kept ones by ``float32(1 / (1 - dropout))`` (torch.ops.isplib.gat_drop_spmm): the softmax still runs
+    over every stored entry.  ``dropout == 0`` or ``training=False`` is the call above, unchanged, bit for bit.  The mask is a pure
+    function of (`seed`, the entry's position in ``storage.col()``, head) -- include/isplib_hip.h states it, `gat_dropout_mask`
+    returns it -- which the backward recomputes: nothing per edge is stored and no RNG state is kept.  ``seed=None`` draws one int64 in
+    [0, 2^63) from torch's default CPU generator (reproducible under ``torch.manual_seed``, no device sync); an explicit `seed` is an
+    int in [0, 2^63).  The seed is a kernel ARGUMENT: a captured graph replays ONE mask -- draw the seed outside the capture and
+    re-capture, or do not capture a training step that needs fresh masks.  A caller who splits the heads over several calls (column
+    views of `y`) gets heads numbered from 0 in each call: pass a different seed per call, or the calls share masks.  With `a_edge` both
+    apply.  A 16-bit `y` under ISPLIB_HALF_GAT takes the conversion route, as with `a_edge`."""
+    drop = _gat_dropout_args(dropout, training, seed)
+    if drop is not None:
+        return _gat_drop_matmul(src, y, a_dst, a_src, a_edge, heads, negative_slope, *drop)
     if a_edge is not None:
         return _gat_edge_matmul(src, y, a_dst, a_src, a_edge, heads, negative_slope)
     from . import cabi
@@ -866,6 +879,133 @@ def _gat_edge_matmul(src, y, a_dst, a_src, a_edge, heads, negative_slope):
         a_edge = a_edge.contiguous()
     return torch.ops.isplib.gat_edge_spmm(st._rowptr, st._col, st.colptr(), st.row_t(), st.csr2csc(), y, a_dst, a_src, a_edge, heads,
                                           float(negative_slope))
+
+
+def _gat_dropout_args(dropout, training, seed):
+    """The dropout arguments of gat_matmul, checked before anything touches a device.  -> None (no dropout: `dropout == 0` or not
+    training) or (p, seed) with the seed drawn from torch's default CPU generator where none was given."""
+    if isinstance(dropout, bool) or not isinstance(dropout, (int, float)):
+        raise TypeError(f"isplib_amd: `dropout` must be a Python float or int in [0, 1), got {type(dropout).__name__}")
+    p = float(dropout)
+    if not 0.0 <= p < 1.0:                                              # NaN fails both comparisons
+        raise ValueError(f"isplib_amd: `dropout` must lie in [0, 1), got {dropout!r}")
+    if seed is not None:
+        if isinstance(seed, bool) or not isinstance(seed, int):
+            raise TypeError(f"isplib_amd: `seed` must be an int in [0, 2^63) or None, got {type(seed).__name__}")
+        if not 0 <= seed < 2 ** 63:
+            raise ValueError(f"isplib_amd: `seed` must lie in [0, 2^63), got {seed!r}")
+    if p == 0.0 or not training:
+        return None
+    if seed is None:                                                    # one int64 from the default CPU generator: no device sync
+        seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+    return p, seed
+
+
+def _gat_drop_matmul(src, y, a_dst, a_src, a_edge, heads, negative_slope, p, seed):
+    """gat_matmul with attention dropout, with or without the per-edge term: every check of gat_matmul (and of `a_edge` and its domain),
+    all before anything touches a device; then torch.ops.isplib.gat_drop_spmm.  There is no fallback route."""
+    from . import cabi
+    edge = a_edge is not None
+    half = isinstance(y, torch.Tensor) and y.dtype in HALF_DTYPES and os.environ.get("ISPLIB_HALF_GAT") is not None
+    for name, t in (("y", y), ("a_dst", a_dst), ("a_src", a_src)) + ((("a_edge", a_edge),) if edge else ()):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"isplib_amd: `{name}` must be a tensor, got {type(t).__name__}")
+        if half and name != "y" and t.dtype not in (torch.float32, y.dtype):
+            raise TypeError(f"isplib_amd: `{name}` must be float32 or of `y`'s dtype ({y.dtype}), got {t.dtype}")
+        if not half and t.dtype != torch.float32:
+            raise TypeError(f"isplib_amd: `{name}` must be float32, got {t.dtype} (the attention operator is fp32 only)")
+    if half:        # the conversion route (no 16-bit dropout kernel): .float() is exact, and every gradient returns in its own dtype through the cast
+        return _gat_drop_matmul(src, y.float(), a_dst.float(), a_src.float(), a_edge.float() if edge else None, heads, negative_slope, p,
+                                seed).to(y.dtype)
+    if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
+        raise ValueError(f"isplib_amd: `heads` must be a positive int, got {heads!r}")
+    if y.dim() != 2:
+        raise ValueError(f"isplib_amd: `y` must be 2-D [rows, heads * d], got shape {tuple(y.shape)}")
+    st = _storage_of(src, y)
+    m_rows, n_cols, nnz = st._rowptr.numel() - 1, st._sparse_sizes[1], st._col.numel()
+    if y.size(0) != n_cols:
+        raise ValueError(f"isplib_amd: `y` must have one row per column of the sparse matrix ({n_cols}), got {y.size(0)}")
+    k = y.size(1)
+    if k % heads:
+        raise ValueError(f"isplib_amd: the width of `y` ({k}) must be heads * d, got heads = {heads}")
+    d = k // heads
+    if heads == 1:
+        a_dst = a_dst.unsqueeze(1) if a_dst.dim() == 1 else a_dst
+        a_src = a_src.unsqueeze(1) if a_src.dim() == 1 else a_src
+        a_edge = a_edge.unsqueeze(1) if edge and a_edge.dim() == 1 else a_edge
+    for name, t, rows, what in (("a_dst", a_dst, m_rows, "row"), ("a_src", a_src, n_cols, "column")) + \
+            ((("a_edge", a_edge, nnz, "stored entry"),) if edge else ()):
+        if t.dim() != 2 or t.size(0) != rows or t.size(1) != heads:
+            raise ValueError(f"isplib_amd: `{name}` must be [{rows}, {heads}] (one entry per {what} of the sparse matrix and head), got "
+                             f"shape {tuple(t.shape)}")
+    if not (1 <= k <= cabi.GAT_K_MAX) or (heads > 1 and (d < 4 or d & (d - 1))):
+        raise ValueError(f"isplib_amd: gat_matmul serves 1 <= heads * d <= {cabi.GAT_K_MAX} with heads == 1 or d a power of two >= 4 (a head "
+                         f"is an aligned group of lanes), got heads = {heads}, d = {d}")
+    pitch = y.stride(0) if n_cols > 1 and y.stride(1) == 1 and y.stride(0) >= k else k
+    for rows, ld, what in ((n_cols, pitch, "`y`"), (m_rows, k, "the gradient of the result")):   # y: forward, rows; g: the columns kernel
+        if not cabi.gat_serves(rows, heads, d, ld):
+            raise ValueError(f"isplib_amd: {what} ({rows} rows at a pitch of {ld} floats) is outside the GAT kernels' domain: "
+                             f"rows < 2^31 and rows * pitch * 4 <= {cabi.DENSE_BYTES_MAX} bytes (3.5 GiB, one buffer descriptor)")
+    if nnz >= 2 ** 31:
+        raise ValueError(f"isplib_amd: the dropout keep bit is defined for fewer than 2^31 stored entries, got {nnz}")
+    if edge and not cabi.gat_edge_serves(nnz, heads):
+        raise ValueError(f"isplib_amd: `a_edge` ({nnz} stored entries x {heads} heads) is outside the GAT edge kernels' domain "
+                         f"(isplib_gat_edge_serves): nnz < 2^31 and nnz * heads * 4 <= {cabi.DENSE_BYTES_MAX} bytes (3.5 GiB, one buffer "
+                         f"descriptor); pass fewer heads per call, on column views of `y`")
+    operands = (y, a_dst, a_src) + ((a_edge,) if edge else ())
+    if not all(t.is_cuda for t in operands):
+        raise TypeError("isplib_amd: `y`, `a_dst`, `a_src` and `a_edge` must be GPU tensors -- there is no CPU path")
+    if any(t.device != y.device for t in operands) or st._rowptr.device != y.device:
+        raise ValueError("isplib_amd: `y`, `a_dst`, `a_src`, `a_edge` and the sparse matrix must be on one device")
+    if edge and not a_edge.is_contiguous():
+        a_edge = a_edge.contiguous()
+    return torch.ops.isplib.gat_drop_spmm(st._rowptr, st._col, st.colptr(), st.row_t(), st.csr2csc(), y, a_dst, a_src, a_edge, heads,
+                                          float(negative_slope), p, seed)
+
+
+_MASK32 = 0xFFFFFFFF
+
+
+def _mul32(x: torch.Tensor, c: int) -> torch.Tensor:
+    """(x * c) mod 2^32 for an int64 tensor of 32-bit values, through 16-bit halves: no intermediate reaches 2^63."""
+    return ((x & 0xFFFF) * c + ((((x >> 16) * c) & 0xFFFF) << 16)) & _MASK32
+
+
+def _fmix32(x: torch.Tensor) -> torch.Tensor:
+    x = x ^ (x >> 16)
+    x = _mul32(x, 0x85EBCA6B)
+    x = x ^ (x >> 13)
+    x = _mul32(x, 0xC2B2AE35)
+    return x ^ (x >> 16)
+
+
+def gat_dropout_mask(adj_or_nnz, heads: int, dropout: float, seed: int, device=None) -> torch.Tensor:
+    """The keep mask of ``gat_matmul(..., dropout=dropout, seed=seed)``: a bool tensor [nnz, heads], row e belonging to the stored entry
+    ``storage.col()[e]``; True = kept.  The realised coefficients are ``mask * a / (1 - dropout)``.  `adj_or_nnz` is the sparse matrix
+    (the mask is built on its device) or the number of stored entries (on `device`, the CPU by default).  Written with torch integer
+    operations on int64 values masked to 32 bits -- the function of include/isplib_hip.h:
+        word(seed, pos, h) = fmix32(fmix32(uint32(pos) ^ uint32(seed)) + uint32(h) * 0x9E3779B9 + uint32(seed >> 32)),  keep = word >= T(p)
+    """
+    from . import cabi
+    if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
+        raise ValueError(f"isplib_amd: `heads` must be a positive int, got {heads!r}")
+    if isinstance(dropout, bool) or not isinstance(dropout, (int, float)) or not 0.0 <= float(dropout) < 1.0:
+        raise ValueError(f"isplib_amd: `dropout` must be a Python float or int in [0, 1), got {dropout!r}")
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 63:
+        raise ValueError(f"isplib_amd: `seed` must be an int in [0, 2^63), got {seed!r}")
+    if isinstance(adj_or_nnz, int) and not isinstance(adj_or_nnz, bool):
+        nnz = adj_or_nnz
+    else:
+        st = adj_or_nnz.storage if hasattr(adj_or_nnz, "storage") else adj_or_nnz
+        nnz = st._col.numel()
+        device = st._col.device if device is None else device
+    if not 0 <= nnz < 2 ** 31:
+        raise ValueError(f"isplib_amd: the keep bit is defined for 0 <= nnz < 2^31 stored entries, got {nnz}")
+    pos = torch.arange(nnz, dtype=torch.int64, device=device)
+    entry = _fmix32(pos ^ (seed & _MASK32))
+    headk = torch.tensor([(h * 0x9E3779B9 + (seed >> 32)) & _MASK32 for h in range(heads)], dtype=torch.int64, device=device)
+    word = _fmix32((entry[:, None] + headk[None, :]) & _MASK32)
+    return word >= cabi.gat_drop_threshold_py(float(dropout))
 
 
 def gatv2_matmul(src, x: torch.Tensor, att: torch.Tensor, y: Optional[torch.Tensor] = None, heads: int = 1,

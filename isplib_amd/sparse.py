@@ -343,12 +343,14 @@ class SparseTensor:
         return attention_matmul(self, x, y, scale)
 
     def gat_matmul(self, y: torch.Tensor, a_dst: torch.Tensor, a_src: torch.Tensor, heads: int = 1, negative_slope: float = 0.2,
-                   a_edge: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   a_edge: Optional[torch.Tensor] = None, dropout: float = 0.0, training: bool = True,
+                   seed: Optional[int] = None) -> torch.Tensor:
         """GAT attention aggregation over this matrix's stored entries, all heads in one launch (plugin.gat_matmul); a bf16 / fp16 `y`
         is opt-in through ISPLIB_HALF_GAT.  `a_edge` [nnz, heads]: a per-edge score term, one row per stored entry in the order of
-        ``storage.col()`` / ``storage.value()``."""
+        ``storage.col()`` / ``storage.value()``.  `dropout` with `training`: attention dropout after the softmax, its mask a function
+        of `seed` (None: drawn from torch's default CPU generator), the entry's position and the head."""
         from .plugin import gat_matmul
-        return gat_matmul(self, y, a_dst, a_src, heads, negative_slope, a_edge)
+        return gat_matmul(self, y, a_dst, a_src, heads, negative_slope, a_edge, dropout, training, seed)
 
     def gatv2_matmul(self, x: torch.Tensor, att: torch.Tensor, y: Optional[torch.Tensor] = None, heads: int = 1,
                      negative_slope: float = 0.2) -> torch.Tensor:
