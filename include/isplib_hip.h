@@ -1399,4 +1399,7 @@ void isplib_graph_destroy(isplib_graph *g);
 /* the GATv2 aggregation for bf16 / fp16 operands (isplib_gatv2_16_*): part of this interface, declared in a file of its own */
 #include "isplib_hip_gatv2_16.h"
 
+/* the GATv2 aggregation with attention dropout (isplib_gatv2_drop_*): part of this interface, declared in a file of its own */
+#include "isplib_hip_gatv2_drop.h"
+
 #endif /* ISPLIB_HIP_H */

@@ -276,6 +276,10 @@ GATV2_16_EXPORTS = (
     "isplib_gatv2_16_domain", "isplib_gatv2_16_auto",
 )
 
+# include/isplib_hip_gatv2_drop.h (which isplib_hip.h includes; the same library): the GATv2 entries with attention dropout, listed
+# apart for the reason the 16-bit GATv2 entries are -- EXPORTS is what isplib_hip.h itself declares, and its GATv2 names are pinned
+GATV2_DROP_EXPORTS = ("isplib_gatv2_drop_csr_hip", "isplib_gatv2_drop_bw_rows_hip", "isplib_gatv2_drop_bw_cols_hip")
+
 # the two host functions of the dropout keep bit (isplib_hip.h declares them; they return uint32_t, not a status, and are listed apart)
 GAT_DROP_HOST_EXPORTS = ("isplib_gat_drop_threshold", "isplib_gat_drop_word")
 
@@ -581,6 +585,14 @@ def lib() -> ctypes.CDLL:
         L.isplib_gatv2_bw_cols_hip.restype = ctypes.c_int
         L.isplib_gatv2_bw_cols_hip.argtypes = [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _f32, _vp, _i64, _vp, _vp,
                                                _vp, _i64, _vp]
+        # the isplib_gatv2_* argument lists (the columns entry with csr2csc after cole), then threshold, scale, seed
+        L.isplib_gatv2_drop_csr_hip.restype = ctypes.c_int
+        L.isplib_gatv2_drop_csr_hip.argtypes = L.isplib_gatv2_csr_hip.argtypes + _drop
+        L.isplib_gatv2_drop_bw_rows_hip.restype = ctypes.c_int
+        L.isplib_gatv2_drop_bw_rows_hip.argtypes = L.isplib_gatv2_bw_rows_hip.argtypes + _drop
+        L.isplib_gatv2_drop_bw_cols_hip.restype = ctypes.c_int
+        L.isplib_gatv2_drop_bw_cols_hip.argtypes = (L.isplib_gatv2_bw_cols_hip.argtypes[:7] + [_vp] + L.isplib_gatv2_bw_cols_hip.argtypes[7:] +
+                                                    _drop)
         L.isplib_gatv2_16_domain.restype = ctypes.c_int
         L.isplib_gatv2_16_domain.argtypes = [_i64, _i64, _i64, _i64]
         L.isplib_gatv2_16_auto.restype = ctypes.c_int
@@ -2463,6 +2475,16 @@ def gatv2(rowptr, col, x, y, att, heads: int = 1, negative_slope: float = 0.2, *
     `x` [m, heads * d] and `y` [n, heads * d] float32 (row-strided views keep their pitch), `att` [heads, d] contiguous float32; `out` =
     (z, lse) to write in place.  Every operand is checked BEFORE the call (`check`: also the two checks that read the structure on the
     device)."""
+    return _gatv2_forward(rowptr, col, x, y, att, heads, negative_slope, out, check, None)
+
+
+def _gatv2_nnz(nnz: int) -> None:
+    if nnz >= 2 ** 31:
+        raise ValueError(f"isplib_amd: the dropout keep bit is defined for fewer than 2^31 stored entries, got {nnz}")
+
+
+def _gatv2_forward(rowptr, col, x, y, att, heads, negative_slope, out, check, drop):
+    """`gatv2` (drop None) and `gatv2_drop` (drop = (threshold, scale, seed), checked): one set of operand checks, all before the call."""
     if not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1 or rowptr.numel() < 1:
         raise ValueError("isplib_amd: `rowptr` (m + 1 entries) must be a 1-D tensor")
     m = rowptr.numel() - 1
@@ -2475,6 +2497,8 @@ def gatv2(rowptr, col, x, y, att, heads: int = 1, negative_slope: float = 0.2, *
     d = _gat_heads(heads, k)
     _gatv2_att(att, "att", heads, d)
     rowptr, col = _attn_structure(rowptr, col, "rowptr", "col", n, check)
+    if drop is not None:
+        _gatv2_nnz(col.numel())
     if out is not None:
         z, lse = out
         ldz = _attn_dense(z, "out[0]", m, k, "z")
@@ -2491,11 +2515,20 @@ def gatv2(rowptr, col, x, y, att, heads: int = 1, negative_slope: float = 0.2, *
             lse.fill_(float("-inf"))
         return z, lse
     rp = rowptr.data_ptr()
+    entry = "isplib_gatv2_csr_hip" if drop is None else "isplib_gatv2_drop_csr_hip"
     with torch.cuda.device(x.device):
-        st = lib().isplib_gatv2_csr_hip(m, n, k, col.numel(), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8), _ptr(x), ldx, _ptr(y),
-                                        ldy, _ptr(att), heads, float(negative_slope), _ptr(z), ldz, _ptr(lse), _stream(x.device))
-    _check(st, "isplib_gatv2_csr_hip")
+        st = getattr(lib(), entry)(m, n, k, col.numel(), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8), _ptr(x), ldx, _ptr(y), ldy,
+                                   _ptr(att), heads, float(negative_slope), _ptr(z), ldz, _ptr(lse), _stream(x.device), *(drop or ()))
+    _check(st, entry)
     return z, lse
+
+
+def gatv2_drop(rowptr, col, x, y, att, threshold: int, scale: float, seed: int, heads: int = 1, negative_slope: float = 0.2, *, out=None,
+               check: bool = True):
+    """`gatv2` with attention dropout (isplib_gatv2_drop_csr_hip): entry e (its position in `col`) and head h are kept where
+    gat_drop_word(seed, e, h) >= threshold -- the keep bit of `gat_drop` -- and z is scaled by `scale`; lse is that of the call without
+    dropout.  Returns (z, lse); the operand checks are gatv2's, and nnz < 2^31."""
+    return _gatv2_forward(rowptr, col, x, y, att, heads, negative_slope, out, check, _gat_drop_args(threshold, scale, seed))
 
 
 def gatv2_bw_rows(rowptr, col, x, y, att, g, z, lse, heads: int = 1, negative_slope: float = 0.2, *, want_datt: bool = True, out=None,
@@ -2505,6 +2538,11 @@ def gatv2_bw_rows(rowptr, col, x, y, att, g, z, lse, heads: int = 1, negative_sl
     `want_datt`, datt_c = sum over every edge of ds_e v_ec.  Returns (dx [m, heads * d], D [m, heads], datt [heads, d] or None); an empty
     row has dx_i = 0 and D = 0.  `out` = (dx, D, datt or None); `workspace`: a uint8 GPU tensor of at least
     gatv2_bw_rows_workspace_bytes(m, k) bytes (allocated when None); the operand checks are gatv2's."""
+    return _gatv2_backward_rows(rowptr, col, x, y, att, g, z, lse, heads, negative_slope, want_datt, out, workspace, check, None)
+
+
+def _gatv2_backward_rows(rowptr, col, x, y, att, g, z, lse, heads, negative_slope, want_datt, out, workspace, check, drop):
+    """`gatv2_bw_rows` (drop None) and `gatv2_drop_bw_rows` (drop = (threshold, scale, seed), checked)."""
     if not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1 or rowptr.numel() < 1:
         raise ValueError("isplib_amd: `rowptr` (m + 1 entries) must be a 1-D tensor")
     m = rowptr.numel() - 1
@@ -2520,6 +2558,8 @@ def gatv2_bw_rows(rowptr, col, x, y, att, g, z, lse, heads: int = 1, negative_sl
     ldz = _attn_dense(z, "z", m, k, "the forward's output")
     _gat_table(lse, "lse", m, heads)
     rowptr, col = _attn_structure(rowptr, col, "rowptr", "col", n, check)
+    if drop is not None:
+        _gatv2_nnz(col.numel())
     if out is not None:
         if len(out) != 3:
             raise ValueError("isplib_amd: `out` must be (dx, D, datt or None)")
@@ -2547,6 +2587,7 @@ def gatv2_bw_rows(rowptr, col, x, y, att, g, z, lse, heads: int = 1, negative_sl
             datt.zero_()
         return dx, dsum, datt
     rp = rowptr.data_ptr()
+    entry = "isplib_gatv2_bw_rows_hip" if drop is None else "isplib_gatv2_drop_bw_rows_hip"
     with torch.cuda.device(x.device):
         if datt is not None:
             need = gatv2_bw_rows_workspace_bytes(m, k)
@@ -2554,12 +2595,20 @@ def gatv2_bw_rows(rowptr, col, x, y, att, g, z, lse, heads: int = 1, negative_sl
                 workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=x.device)
             elif workspace.numel() < need:
                 raise ValueError(f"isplib_amd: `workspace` holds {workspace.numel()} bytes, isplib_gatv2_bw_rows_workspace_bytes asks for {need}")
-        st = lib().isplib_gatv2_bw_rows_hip(m, n, k, col.numel(), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8), _ptr(x), ldx, _ptr(y),
-                                            ldy, _ptr(att), heads, float(negative_slope), _ptr(g), ldg, _ptr(z), ldz, _ptr(lse), _ptr(dx), lddx,
-                                            _ptr(dsum), _ptr(datt), _ptr(workspace) if datt is not None else None,
-                                            workspace.numel() if datt is not None else 0, _stream(x.device))
-    _check(st, "isplib_gatv2_bw_rows_hip")
+        st = getattr(lib(), entry)(m, n, k, col.numel(), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8), _ptr(x), ldx, _ptr(y), ldy,
+                                   _ptr(att), heads, float(negative_slope), _ptr(g), ldg, _ptr(z), ldz, _ptr(lse), _ptr(dx), lddx, _ptr(dsum),
+                                   _ptr(datt), _ptr(workspace) if datt is not None else None,
+                                   workspace.numel() if datt is not None else 0, _stream(x.device), *(drop or ()))
+    _check(st, entry)
     return dx, dsum, datt
+
+
+def gatv2_drop_bw_rows(rowptr, col, x, y, att, g, z, lse, threshold: int, scale: float, seed: int, heads: int = 1,
+                       negative_slope: float = 0.2, *, want_datt: bool = True, out=None, workspace=None, check: bool = True):
+    """The backward of `gatv2_drop` over the rows (isplib_gatv2_drop_bw_rows_hip), with the mask of the same (threshold, seed):
+    t_e = q_e scale <g_i, y_j>_h, everything else as `gatv2_bw_rows` (z is the forward's, under the mask).  Returns (dx, D, datt or None)."""
+    return _gatv2_backward_rows(rowptr, col, x, y, att, g, z, lse, heads, negative_slope, want_datt, out, workspace, check,
+                                _gat_drop_args(threshold, scale, seed))
 
 
 def gatv2_bw_cols(colptr, row_t, x, y, att, g, lse, dsum, heads: int = 1, negative_slope: float = 0.2, *, out=None, check: bool = True):
@@ -2567,6 +2616,11 @@ def gatv2_bw_cols(colptr, row_t, x, y, att, g, lse, dsum, heads: int = 1, negati
     row ids of the entries in column-major order): dy_jc = sum over the entries e = (i, j) of column j of a_e g_ic + ds_e att_c sl_ec,
     with `lse` of the forward and `dsum` = D of gatv2_bw_rows.  Returns dy [n, heads * d]; a column no entry points at has 0.  `out` =
     dy; the operand checks are gatv2's."""
+    return _gatv2_backward_cols(colptr, row_t, None, x, y, att, g, lse, dsum, heads, negative_slope, out, check, None)
+
+
+def _gatv2_backward_cols(colptr, row_t, csr2csc, x, y, att, g, lse, dsum, heads, negative_slope, out, check, drop):
+    """`gatv2_bw_cols` (drop None, no csr2csc) and `gatv2_drop_bw_cols` (drop = (threshold, scale, seed), checked; csr2csc required)."""
     if not isinstance(colptr, torch.Tensor) or colptr.dim() != 1 or colptr.numel() < 1:
         raise ValueError("isplib_amd: `colptr` (n + 1 entries) must be a 1-D tensor")
     n = colptr.numel() - 1
@@ -2582,22 +2636,37 @@ def gatv2_bw_cols(colptr, row_t, x, y, att, g, lse, dsum, heads: int = 1, negati
     _gat_table(lse, "lse", m, heads)
     _gat_table(dsum, "dsum", m, heads)
     colptr, row_t = _attn_structure(colptr, row_t, "colptr", "row_t", m, check)
+    if drop is not None:
+        _gatv2_nnz(row_t.numel())
+        csr2csc = _gat_edge_positions(csr2csc, row_t.numel(), check)
     if out is not None:
         lddy = _attn_dense(out, "out", n, k, "dy")
     _gatv2_domain(m, heads, d, (ldx, ldg))
-    _same_gpu((("x", x), ("y", y), ("att", att), ("g", g), ("lse", lse), ("dsum", dsum), ("colptr", colptr), ("row_t", row_t), ("out", out)))
+    _same_gpu((("x", x), ("y", y), ("att", att), ("g", g), ("lse", lse), ("dsum", dsum), ("colptr", colptr), ("row_t", row_t), ("out", out)) +
+              ((("csr2csc", csr2csc),) if drop is not None else ()))
     if out is None:
         out = torch.empty((n, k), dtype=torch.float32, device=y.device)
         lddy = max(k, 1)
     if n == 0 or k == 0:
         return out
     cp = colptr.data_ptr()
+    entry = "isplib_gatv2_bw_cols_hip" if drop is None else "isplib_gatv2_drop_bw_cols_hip"
     with torch.cuda.device(y.device):
-        st = lib().isplib_gatv2_bw_cols_hip(m, n, k, row_t.numel(), _ptr(row_t), ctypes.c_void_p(cp), ctypes.c_void_p(cp + 8), _ptr(x), ldx,
-                                            _ptr(y), ldy, _ptr(att), heads, float(negative_slope), _ptr(g), ldg, _ptr(lse), _ptr(dsum),
-                                            _ptr(out), lddy, _stream(y.device))
-    _check(st, "isplib_gatv2_bw_cols_hip")
+        st = getattr(lib(), entry)(m, n, k, row_t.numel(), _ptr(row_t), ctypes.c_void_p(cp), ctypes.c_void_p(cp + 8),
+                                   *((_ptr(csr2csc),) if drop is not None else ()), _ptr(x), ldx, _ptr(y), ldy, _ptr(att), heads,
+                                   float(negative_slope), _ptr(g), ldg, _ptr(lse), _ptr(dsum), _ptr(out), lddy, _stream(y.device),
+                                   *(drop or ()))
+    _check(st, entry)
     return out
+
+
+def gatv2_drop_bw_cols(colptr, row_t, csr2csc, x, y, att, g, lse, dsum, threshold: int, scale: float, seed: int, heads: int = 1,
+                       negative_slope: float = 0.2, *, out=None, check: bool = True):
+    """The backward of `gatv2_drop` over the columns (isplib_gatv2_drop_bw_cols_hip): dy_jc = sum over the entries of column j of
+    q_e scale a_e g_ic + r_ec.  `csr2csc` [nnz] int64 is required: the keep bit is a function of the entry's CSR position, and this
+    entry walks the transposed structure.  Returns dy."""
+    return _gatv2_backward_cols(colptr, row_t, csr2csc, x, y, att, g, lse, dsum, heads, negative_slope, out, check,
+                                _gat_drop_args(threshold, scale, seed))
 
 
 def _attn16_dense(t, name: str, rows: int, k: Optional[int], what: str, dtype=None) -> int:

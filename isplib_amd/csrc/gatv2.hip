@@ -27,11 +27,24 @@
 // Every gathered table sits behind a buffer descriptor of exactly the extent it owns; dead edges and lanes past k carry BUF_OOB, which
 // the descriptor answers with 0.  No atomics, a fixed order of operations: two launches give equal bits.  gat.hip and attention.hip are
 // untouched; their small helpers are restated here under names of their own.  DESIGN.md 4.6f.
+//
+// Attention dropout (include/isplib_hip_gatv2_drop.h: isplib_gatv2_drop_*_hip): the three kernels are templates on
+// DROP.  Every stored entry e and head h has a keep bit q_e,h = word(seed, CSR position of e, h) >= T (gat_dropout.h: the bit of
+// gat.hip, a pure function, recomputed in all three kernels, nothing stored), and with c = float32(1 / (1 - p)), r_ec the q_ec above:
+//    z_i = c sum_e q_e a_e y_j      t_e = q_e c <g_i, y_j>_h      dy_jc = sum_{e -> j} (q_e c a_e g_ic + r_ec)
+//    a_e, lse, s_e and the form of ds_e unchanged
+// The softmax runs over ALL stored entries: l, m and lse do not see the mask, and a dropped edge still gets ds_e = -a_e D.  The lane that
+// loads an entry's index hashes the entry's position (base + lane in the forward and the rows kernel; csr2csc[pos] in the columns
+// kernel, which walks the transposed structure and therefore takes csr2csc) and hands the word across with the index; per edge and chunk
+// one add of a per-lane constant, one fmix32, one compare and one select remain.  c multiplies the finished row of z and t_e per edge; dy
+// mixes a masked term with an unmasked one, so its value coefficient is q_e ? a_e c : 0 per edge and head.  The seed is a kernel
+// argument: a captured graph replays one mask.  DROP = false is the code it was (profiles/gatv2_dropout_isa.txt).
 #include <cfloat>
 #include <cmath>
 
 #include "common.h"
 #include "gather.h"
+#include "gat_dropout.h"
 
 namespace isplib {
 
@@ -70,6 +83,11 @@ struct Gatv2Args {
    unsigned y2bytes;
    const float *t1, *t2;                   // columns: lse, D; both [gathered rows, H]
    unsigned tbytes;
+   // DROP only (appended)
+   const int64_t *epos;                    // columns: csr2csc [nnz], the CSR position of every entry of the transposed structure
+   unsigned seed_lo, seed_hi;              // the two halves of the seed
+   unsigned T;                             // keep: word >= T
+   float c;                                // float32(1 / (1 - p))
 };
 
 template <int LPR, int NCH> struct Gatv2Cols {
@@ -195,7 +213,14 @@ __device__ __forceinline__ unsigned gatv2_off(int id, unsigned pitch_bytes) {
    return id < 0 ? BUF_OOB : (unsigned)id * pitch_bytes;     // BUF_OOB + cbyte / hbyte (< 2^24) cannot wrap
 }
 
-template <int LPR, int NCH, int WAVES>
+// DROP: the per-lane constant of each chunk's head (gat_dropout.h)
+template <int LPR, int NCH>
+__device__ __forceinline__ void gatv2_drop_heads(const Gatv2Args &a, const Gatv2Cols<LPR, NCH> &cm, unsigned (&hk)[NCH]) {
+#pragma unroll
+   for (int j = 0; j < NCH; j++) hk[j] = gat_drop_head(a.seed_hi, (unsigned)cm.head[j]);
+}
+
+template <int LPR, int NCH, int WAVES, bool DROP>
 __global__ __launch_bounds__(WAVES * 64) void gatv2_fw_kernel(const Gatv2Args a) {
    constexpr int G = 64 / LPR, U = 4;
    const int lane = threadIdx.x & 63;
@@ -209,6 +234,8 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_fw_kernel(const Gatv2Args a)
    float xv[NCH][4], av[NCH][4];
    gatv2_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm, xv);
    gatv2_own_row<LPR, NCH>(a.att, 0, a.k, lc, cm, av);
+   [[maybe_unused]] unsigned hk[NCH];
+   if constexpr (DROP) gatv2_drop_heads<LPR, NCH>(a, cm, hk);
 
    float mrun[NCH], l[NCH], acc[NCH][4];
 #pragma unroll
@@ -223,13 +250,19 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_fw_kernel(const Gatv2Args a)
    for (int64_t base = eb; base < ee; base += 64) {
       const int64_t pos = base + lane;
       const int id_l = pos < ee ? (int)a.indx[pos] : -1;
+      [[maybe_unused]] unsigned hw_l = 0u;               // DROP: the entry's part of the word, handed across lanes like the column id
+      if constexpr (DROP) hw_l = gat_drop_entry(a.seed_lo, (unsigned)pos);
       const int64_t left = ee - base;
       const int cnt = left < 64 ? (int)left : 64;
 #pragma unroll 1
       for (int s0 = 0; s0 < cnt; s0 += G * U) {
          v4i_t yv[U][NCH];
+         [[maybe_unused]] unsigned hw[DROP ? U : 1];
 #pragma unroll
-         for (int u = 0; u < U; u++) gatv2_load_wide<LPR, NCH>(rsy, gatv2_off(__shfl(id_l, (s0 + u * G + g) & 63), ldyb), cm, yv[u]);
+         for (int u = 0; u < U; u++) {
+            gatv2_load_wide<LPR, NCH>(rsy, gatv2_off(__shfl(id_l, (s0 + u * G + g) & 63), ldyb), cm, yv[u]);
+            if constexpr (DROP) hw[u] = (unsigned)__shfl((int)hw_l, (s0 + u * G + g) & 63);
+         }
          float sc[U][NCH];
 #pragma unroll
          for (int u = 0; u < U; u++)
@@ -250,9 +283,11 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_fw_kernel(const Gatv2Args a)
 #pragma unroll
             for (int u = 0; u < U; u++) {
                const float w = (s0 + u * G + g < cnt) ? __expf(sc[u][j] - mnew) : 0.0f;
-               l[j] += w;
+               l[j] += w;                                 // the softmax runs over every stored entry: the mask reaches the values only
+               float wk = w;
+               if constexpr (DROP) wk = gat_drop_mix(hw[u], hk[j]) >= a.T ? w : 0.0f;
 #pragma unroll
-               for (int v = 0; v < 4; v++) acc[j][v] = fmaf(w, __int_as_float(yv[u][j][v]), acc[j][v]);
+               for (int v = 0; v < 4; v++) acc[j][v] = fmaf(wk, __int_as_float(yv[u][j][v]), acc[j][v]);
             }
          }
       }
@@ -277,14 +312,18 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_fw_kernel(const Gatv2Args a)
    for (int j = 0; j < NCH; j++) {
 #pragma unroll
       for (int v = 0; v < 4; v++)
-         if (cm.ok[j][v]) a.out[(size_t)row * (size_t)a.ldout + (size_t)((j * LPR + lc) * 4 + v)] = empty ? 0.0f : acc[j][v] / l[j];
+         if (cm.ok[j][v]) {
+            float zv = empty ? 0.0f : acc[j][v] / l[j];
+            if constexpr (DROP) zv *= a.c;
+            a.out[(size_t)row * (size_t)a.ldout + (size_t)((j * LPR + lc) * 4 + v)] = zv;
+         }
       if (cm.first[j]) a.hout[(size_t)row * (size_t)a.heads + (size_t)cm.head[j]] = empty ? -INFINITY : mrun[j] + logf(l[j]);
    }
 }
 
 // DATT: every lane also sums ds_e v_ec; the block folds its waves' sums through LDS and writes one partial row.  That instantiation has
 // a barrier, so no wave leaves before it: a wave whose row is past a.rows walks an empty row and contributes zeros.
-template <int LPR, int NCH, int WAVES, bool DATT>
+template <int LPR, int NCH, int WAVES, bool DATT, bool DROP>
 __global__ __launch_bounds__(WAVES * 64) void gatv2_bw_rows_kernel(const Gatv2Args a) {
    constexpr int G = 64 / LPR, U = 4, WCOLS = NCH * LPR * 4;
    const int lane = threadIdx.x & 63;
@@ -330,18 +369,26 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_bw_rows_kernel(const Gatv2Ar
    for (int j = 0; j < NCH; j++)
 #pragma unroll
       for (int v = 0; v < 4; v++) acc[j][v] = pa[j][v] = 0.0f;
+   [[maybe_unused]] unsigned hk[NCH];
+   if constexpr (DROP) gatv2_drop_heads<LPR, NCH>(a, cm, hk);
 
    const unsigned ldyb = (unsigned)a.ldy * 4u;
    for (int64_t base = eb; base < ee; base += 64) {
       const int64_t pos = base + lane;
       const int id_l = pos < ee ? (int)a.indx[pos] : -1;
+      [[maybe_unused]] unsigned hw_l = 0u;               // DROP: the entry's part of the word, handed across lanes like the column id
+      if constexpr (DROP) hw_l = gat_drop_entry(a.seed_lo, (unsigned)pos);
       const int64_t left = ee - base;
       const int cnt = left < 64 ? (int)left : 64;
 #pragma unroll 1
       for (int s0 = 0; s0 < cnt; s0 += G * U) {
          v4i_t yv[U][NCH];
+         [[maybe_unused]] unsigned hw[DROP ? U : 1];
 #pragma unroll
-         for (int u = 0; u < U; u++) gatv2_load_wide<LPR, NCH>(rsy, gatv2_off(__shfl(id_l, (s0 + u * G + g) & 63), ldyb), cm, yv[u]);
+         for (int u = 0; u < U; u++) {
+            gatv2_load_wide<LPR, NCH>(rsy, gatv2_off(__shfl(id_l, (s0 + u * G + g) & 63), ldyb), cm, yv[u]);
+            if constexpr (DROP) hw[u] = (unsigned)__shfl((int)hw_l, (s0 + u * G + g) & 63);
+         }
          float part[2 * U][NCH];                       // s_e and t_e of the step through one butterfly
 #pragma unroll
          for (int u = 0; u < U; u++)
@@ -356,6 +403,7 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_bw_rows_kernel(const Gatv2Ar
             const bool live = s0 + u * G + g < cnt;
 #pragma unroll
             for (int j = 0; j < NCH; j++) {
+               if constexpr (DROP) part[U + u][j] *= gat_drop_mix(hw[u], hk[j]) >= a.T ? a.c : 0.0f;      // t_e = q_e c <g_i, y_j>_h
                const float ds = live ? __expf(part[u][j] - lse[j]) * (part[U + u][j] - dsum[j]) : 0.0f;
 #pragma unroll
                for (int v = 0; v < 4; v++) {
@@ -408,7 +456,7 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_bw_rows_kernel(const Gatv2Ar
 }
 
 // one wave per column j of A (a row of the transposed structure): y_j and att in registers; x_i, g_i and lse, D of [i, head] gathered
-template <int LPR, int NCH, int WAVES>
+template <int LPR, int NCH, int WAVES, bool DROP>
 __global__ __launch_bounds__(WAVES * 64) void gatv2_bw_cols_kernel(const Gatv2Args a) {
    constexpr int G = 64 / LPR, U = NCH >= 2 ? 2 : 4;   // two gather streams: half the edges per step where a lane holds two chunks
    const int lane = threadIdx.x & 63;
@@ -423,6 +471,8 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_bw_cols_kernel(const Gatv2Ar
    float yv[NCH][4], av[NCH][4];
    gatv2_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm, yv);
    gatv2_own_row<LPR, NCH>(a.att, 0, a.k, lc, cm, av);
+   [[maybe_unused]] unsigned hk[NCH];
+   if constexpr (DROP) gatv2_drop_heads<LPR, NCH>(a, cm, hk);
 
    float acc[NCH][4];
 #pragma unroll
@@ -434,12 +484,15 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_bw_cols_kernel(const Gatv2Ar
    for (int64_t base = eb; base < ee; base += 64) {
       const int64_t pos = base + lane;
       const int id_l = pos < ee ? (int)a.indx[pos] : -1;
+      [[maybe_unused]] unsigned hw_l = 0u;               // DROP: the entry's part of the word, of its CSR position (nnz < 2^31)
+      if constexpr (DROP) hw_l = gat_drop_entry(a.seed_lo, pos < ee ? (unsigned)a.epos[pos] : 0u);
       const int64_t left = ee - base;
       const int cnt = left < 64 ? (int)left : 64;
 #pragma unroll 1
       for (int s0 = 0; s0 < cnt; s0 += G * U) {
          v4i_t xg[U][NCH], gg[U][NCH];
          float ls[U][NCH], dd[U][NCH];
+         [[maybe_unused]] unsigned hw[DROP ? U : 1];
 #pragma unroll
          for (int u = 0; u < U; u++) {
             const int id = __shfl(id_l, (s0 + u * G + g) & 63);
@@ -447,6 +500,7 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_bw_cols_kernel(const Gatv2Ar
             gatv2_load_wide<LPR, NCH>(rsg, gatv2_off(id, ldgb), cm, gg[u]);
             gatv2_load_head<LPR, NCH>(rs1, gatv2_off(id, hb), cm, ls[u]);
             gatv2_load_head<LPR, NCH>(rs2, gatv2_off(id, hb), cm, dd[u]);
+            if constexpr (DROP) hw[u] = (unsigned)__shfl((int)hw_l, (s0 + u * G + g) & 63);
          }
          float part[2 * U][NCH];
 #pragma unroll
@@ -463,13 +517,19 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_bw_cols_kernel(const Gatv2Ar
 #pragma unroll
             for (int j = 0; j < NCH; j++) {
                const float ae = live ? __expf(part[u][j] - ls[u][j]) : 0.0f;
+               float aev = ae;                            // the value coefficient: q_e c a_e; dy mixes it with the unmasked r_ec
+               if constexpr (DROP) {
+                  const bool keep = gat_drop_mix(hw[u], hk[j]) >= a.T;
+                  part[U + u][j] *= keep ? a.c : 0.0f;    // t_e = q_e c <g_i, y_j>_h
+                  aev = keep ? ae * a.c : 0.0f;
+               }
                const float ds = live ? ae * (part[U + u][j] - dd[u][j]) : 0.0f;
 #pragma unroll
                for (int v = 0; v < 4; v++) {
                   bool pos;
                   gatv2_leaky(yv[j][v], cm.ok[j][v] ? __int_as_float(xg[u][j][v]) : 0.0f, a.ns, pos);
                   const float dsa = ds * av[j][v];
-                  acc[j][v] += fmaf(ae, __int_as_float(gg[u][j][v]), pos ? dsa : a.ns * dsa);
+                  acc[j][v] += fmaf(aev, __int_as_float(gg[u][j][v]), pos ? dsa : a.ns * dsa);
                }
             }
          }
@@ -504,27 +564,54 @@ __global__ __launch_bounds__(256) void gatv2_fold_kernel(int64_t blocks, int64_t
 
 enum { GATV2_FW = 0, GATV2_BW_ROWS = 1, GATV2_BW_ROWS_DATT = 2, GATV2_BW_COLS = 3 };
 
-template <int LPR, int NCH>
+template <int LPR, int NCH, bool DROP>
 static int launch_gatv2(int which, const Gatv2Args &a, const char *entry, hipStream_t st) {
    const int waves = which == GATV2_BW_ROWS || which == GATV2_BW_ROWS_DATT ? GATV2_ROWS_WAVES : GATV2_WAVES;
    const int64_t nb = (a.rows + waves - 1) / waves;
    if (nb > 0x7fffffffLL) return fail(ISPLIB_FAIL, entry, "too many rows for one launch");
    const dim3 grid((unsigned)nb), block((unsigned)waves * 64u);
-   if (which == GATV2_FW) hipLaunchKernelGGL((gatv2_fw_kernel<LPR, NCH, GATV2_WAVES>), grid, block, 0, st, a);
-   else if (which == GATV2_BW_ROWS) hipLaunchKernelGGL((gatv2_bw_rows_kernel<LPR, NCH, GATV2_ROWS_WAVES, false>), grid, block, 0, st, a);
-   else if (which == GATV2_BW_ROWS_DATT) hipLaunchKernelGGL((gatv2_bw_rows_kernel<LPR, NCH, GATV2_ROWS_WAVES, true>), grid, block, 0, st, a);
-   else hipLaunchKernelGGL((gatv2_bw_cols_kernel<LPR, NCH, GATV2_WAVES>), grid, block, 0, st, a);
+   if (which == GATV2_FW) hipLaunchKernelGGL((gatv2_fw_kernel<LPR, NCH, GATV2_WAVES, DROP>), grid, block, 0, st, a);
+   else if (which == GATV2_BW_ROWS) hipLaunchKernelGGL((gatv2_bw_rows_kernel<LPR, NCH, GATV2_ROWS_WAVES, false, DROP>), grid, block, 0, st, a);
+   else if (which == GATV2_BW_ROWS_DATT) hipLaunchKernelGGL((gatv2_bw_rows_kernel<LPR, NCH, GATV2_ROWS_WAVES, true, DROP>), grid, block, 0, st, a);
+   else hipLaunchKernelGGL((gatv2_bw_cols_kernel<LPR, NCH, GATV2_WAVES, DROP>), grid, block, 0, st, a);
    return check_launch(entry);
 }
 
-// the width dispatch of gat.hip, up to two chunks per lane
-static int gatv2_by_width(int which, const Gatv2Args &a, const char *entry, hipStream_t st) {
+// the width dispatch of gat.hip, up to two chunks per lane; DROP: the kernels with attention dropout
+template <bool DROP>
+static int gatv2_by_width_of(int which, const Gatv2Args &a, const char *entry, hipStream_t st) {
    const int64_t w = (a.k + 3) / 4;
-   if (w <= 8) return launch_gatv2<8, 1>(which, a, entry, st);
-   if (w <= 16) return launch_gatv2<16, 1>(which, a, entry, st);
-   if (w <= 32) return launch_gatv2<32, 1>(which, a, entry, st);
-   if (w <= 64) return launch_gatv2<64, 1>(which, a, entry, st);
-   return launch_gatv2<64, 2>(which, a, entry, st);
+   if (w <= 8) return launch_gatv2<8, 1, DROP>(which, a, entry, st);
+   if (w <= 16) return launch_gatv2<16, 1, DROP>(which, a, entry, st);
+   if (w <= 32) return launch_gatv2<32, 1, DROP>(which, a, entry, st);
+   if (w <= 64) return launch_gatv2<64, 1, DROP>(which, a, entry, st);
+   return launch_gatv2<64, 2, DROP>(which, a, entry, st);
+}
+
+static int gatv2_by_width(int which, const Gatv2Args &a, bool drop, const char *entry, hipStream_t st) {
+   return drop ? gatv2_by_width_of<true>(which, a, entry, st) : gatv2_by_width_of<false>(which, a, entry, st);
+}
+
+// the dropout of one call (isplib_gatv2_drop_*_hip): the threshold T(p), c = float32(1 / (1 - p)) and the seed; none: the entries without it
+struct Gatv2Drop {
+   bool on;
+   uint32_t threshold;
+   float scale;
+   uint64_t seed;
+};
+static const Gatv2Drop GATV2_NO_DROP = {false, 0u, 1.0f, 0ull};
+
+// what the dropout entries refuse before a launch: a scale that is no positive finite number would poison every row, and the keep bit is
+// a function of a position below 2^31
+static const char *gatv2_drop_refusal(const Gatv2Drop &dr, int64_t nnz) {
+   if (!dr.on) return nullptr;
+   if (!(dr.scale > 0.0f && dr.scale <= FLT_MAX)) return "scale must be a positive finite number";
+   if (nnz >= (1LL << 31)) return "nnz must be below 2^31";
+   return nullptr;
+}
+
+static void gatv2_set_drop(Gatv2Args &a, const Gatv2Drop &dr) {
+   a.seed_lo = (unsigned)dr.seed; a.seed_hi = (unsigned)(dr.seed >> 32); a.T = dr.threshold; a.c = dr.scale;
 }
 
 // what a descriptor over `rows` rows of k floats at pitch ld may answer: the extent a row-strided view owns, not rows * ld
@@ -562,11 +649,12 @@ extern "C" size_t isplib_gatv2_bw_rows_workspace_bytes(int64_t m, int64_t k) {
    return (blocks * (size_t)k * sizeof(float) + 255) & ~(size_t)255;
 }
 
-extern "C" int isplib_gatv2_csr_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
-                                    const int64_t *pntre, const float *x, int64_t ldx, const float *y, int64_t ldy, const float *att,
-                                    int64_t heads, float negative_slope, float *z, int64_t ldz, float *lse, void *stream) {
-   const char *entry = "isplib_gatv2_csr_hip";
+// The three entries, with and without attention dropout.
+static int gatv2_forward(const char *entry, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                         const int64_t *pntre, const float *x, int64_t ldx, const float *y, int64_t ldy, const float *att, int64_t heads,
+                         float negative_slope, float *z, int64_t ldz, float *lse, void *stream, const Gatv2Drop &dr = GATV2_NO_DROP) {
    clear_error();
+   if (const char *why = gatv2_drop_refusal(dr, nnz)) return fail(ISPLIB_FAIL, entry, why);
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
    if (m == 0 || k == 0) return ISPLIB_SUCCESS;
    if (!pntrb || !pntre || !x || !att || !z || !lse || (nnz > 0 && (!indx || !y))) return fail(ISPLIB_FAIL, entry, "null operand");
@@ -579,16 +667,17 @@ extern "C" int isplib_gatv2_csr_hip(int64_t m, int64_t n, int64_t k, int64_t nnz
    a.own = x; a.ldown = ldx; a.att = att;
    a.out = z; a.ldout = ldz; a.hout = lse;
    a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? gatv2_extent(n, k, ldy) : 0u;
-   return gatv2_by_width(GATV2_FW, a, entry, (hipStream_t)stream);
+   gatv2_set_drop(a, dr);
+   return gatv2_by_width(GATV2_FW, a, dr.on, entry, (hipStream_t)stream);
 }
 
-extern "C" int isplib_gatv2_bw_rows_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
-                                        const int64_t *pntre, const float *x, int64_t ldx, const float *y, int64_t ldy, const float *att,
-                                        int64_t heads, float negative_slope, const float *g, int64_t ldg, const float *z, int64_t ldz,
-                                        const float *lse, float *dx, int64_t lddx, float *dsum, float *datt, void *workspace,
-                                        size_t workspace_bytes, void *stream) {
-   const char *entry = "isplib_gatv2_bw_rows_hip";
+static int gatv2_backward_rows(const char *entry, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                               const int64_t *pntre, const float *x, int64_t ldx, const float *y, int64_t ldy, const float *att,
+                               int64_t heads, float negative_slope, const float *g, int64_t ldg, const float *z, int64_t ldz,
+                               const float *lse, float *dx, int64_t lddx, float *dsum, float *datt, void *workspace,
+                               size_t workspace_bytes, void *stream, const Gatv2Drop &dr = GATV2_NO_DROP) {
    clear_error();
+   if (const char *why = gatv2_drop_refusal(dr, nnz)) return fail(ISPLIB_FAIL, entry, why);
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
    if (m == 0 || k == 0) return ISPLIB_SUCCESS;
    if (!pntrb || !pntre || !x || !att || !g || !z || !lse || !dx || !dsum || (nnz > 0 && (!indx || !y)))
@@ -606,20 +695,22 @@ extern "C" int isplib_gatv2_bw_rows_hip(int64_t m, int64_t n, int64_t k, int64_t
    a.own = x; a.ldown = ldx; a.att = att; a.g = g; a.ldg = ldg; a.zin = z; a.ldzin = ldz; a.lse_in = lse;
    a.out = dx; a.ldout = lddx; a.hout = dsum; a.part = datt ? (float *)workspace : nullptr;
    a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? gatv2_extent(n, k, ldy) : 0u;
-   int rc = gatv2_by_width(datt ? GATV2_BW_ROWS_DATT : GATV2_BW_ROWS, a, entry, (hipStream_t)stream);
+   gatv2_set_drop(a, dr);
+   int rc = gatv2_by_width(datt ? GATV2_BW_ROWS_DATT : GATV2_BW_ROWS, a, dr.on, entry, (hipStream_t)stream);
    if (rc || !datt) return rc;
    const int64_t blocks = (m + GATV2_ROWS_WAVES - 1) / GATV2_ROWS_WAVES;
    hipLaunchKernelGGL(gatv2_fold_kernel, dim3((unsigned)((k + 3) / 4)), dim3(256), 0, (hipStream_t)stream, blocks, k, a.part, datt);
    return check_launch(entry);
 }
 
-extern "C" int isplib_gatv2_bw_cols_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t, const int64_t *colb,
-                                        const int64_t *cole, const float *x, int64_t ldx, const float *y, int64_t ldy, const float *att,
-                                        int64_t heads, float negative_slope, const float *g, int64_t ldg, const float *lse,
-                                        const float *dsum, float *dy, int64_t lddy, void *stream) {
-   const char *entry = "isplib_gatv2_bw_cols_hip";
+static int gatv2_backward_cols(const char *entry, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t, const int64_t *colb,
+                               const int64_t *cole, const int64_t *csr2csc, const float *x, int64_t ldx, const float *y, int64_t ldy,
+                               const float *att, int64_t heads, float negative_slope, const float *g, int64_t ldg, const float *lse,
+                               const float *dsum, float *dy, int64_t lddy, void *stream, const Gatv2Drop &dr = GATV2_NO_DROP) {
    clear_error();
+   if (const char *why = gatv2_drop_refusal(dr, nnz)) return fail(ISPLIB_FAIL, entry, why);
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
+   if (dr.on && nnz > 0 && !csr2csc) return fail(ISPLIB_FAIL, entry, "null csr2csc: the keep bit is a function of the CSR position");
    if (n == 0 || k == 0) return ISPLIB_SUCCESS;
    if (!colb || !cole || !y || !att || !dy || (nnz > 0 && (!row_t || !x || !g || !lse || !dsum))) return fail(ISPLIB_FAIL, entry, "null operand");
    if (ldy < k || lddy < k) return fail(ISPLIB_FAIL, entry, "leading dimension smaller than k");
@@ -634,5 +725,60 @@ extern "C" int isplib_gatv2_bw_cols_hip(int64_t m, int64_t n, int64_t k, int64_t
    a.y = x; a.ldy = ldx; a.ybytes = nnz > 0 ? gatv2_extent(m, k, ldx) : 0u;
    a.y2 = g; a.ldy2 = ldg; a.y2bytes = nnz > 0 ? gatv2_extent(m, k, ldg) : 0u;
    a.t1 = lse; a.t2 = dsum; a.tbytes = nnz > 0 ? gatv2_extent(m, heads, heads) : 0u;
-   return gatv2_by_width(GATV2_BW_COLS, a, entry, (hipStream_t)stream);
+   if (dr.on) a.epos = csr2csc;
+   gatv2_set_drop(a, dr);
+   return gatv2_by_width(GATV2_BW_COLS, a, dr.on, entry, (hipStream_t)stream);
+}
+
+extern "C" int isplib_gatv2_csr_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                                    const int64_t *pntre, const float *x, int64_t ldx, const float *y, int64_t ldy, const float *att,
+                                    int64_t heads, float negative_slope, float *z, int64_t ldz, float *lse, void *stream) {
+   return gatv2_forward("isplib_gatv2_csr_hip", m, n, k, nnz, indx, pntrb, pntre, x, ldx, y, ldy, att, heads, negative_slope, z, ldz, lse,
+                        stream);
+}
+
+extern "C" int isplib_gatv2_bw_rows_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                                        const int64_t *pntre, const float *x, int64_t ldx, const float *y, int64_t ldy, const float *att,
+                                        int64_t heads, float negative_slope, const float *g, int64_t ldg, const float *z, int64_t ldz,
+                                        const float *lse, float *dx, int64_t lddx, float *dsum, float *datt, void *workspace,
+                                        size_t workspace_bytes, void *stream) {
+   return gatv2_backward_rows("isplib_gatv2_bw_rows_hip", m, n, k, nnz, indx, pntrb, pntre, x, ldx, y, ldy, att, heads, negative_slope, g,
+                              ldg, z, ldz, lse, dx, lddx, dsum, datt, workspace, workspace_bytes, stream);
+}
+
+extern "C" int isplib_gatv2_bw_cols_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t, const int64_t *colb,
+                                        const int64_t *cole, const float *x, int64_t ldx, const float *y, int64_t ldy, const float *att,
+                                        int64_t heads, float negative_slope, const float *g, int64_t ldg, const float *lse,
+                                        const float *dsum, float *dy, int64_t lddy, void *stream) {
+   return gatv2_backward_cols("isplib_gatv2_bw_cols_hip", m, n, k, nnz, row_t, colb, cole, nullptr, x, ldx, y, ldy, att, heads,
+                              negative_slope, g, ldg, lse, dsum, dy, lddy, stream);
+}
+
+// attention dropout: the argument lists of the entries above (the columns entry with csr2csc after cole), then threshold, scale, seed
+extern "C" int isplib_gatv2_drop_csr_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                                         const int64_t *pntre, const float *x, int64_t ldx, const float *y, int64_t ldy, const float *att,
+                                         int64_t heads, float negative_slope, float *z, int64_t ldz, float *lse, void *stream,
+                                         uint32_t threshold, float scale, uint64_t seed) {
+   return gatv2_forward("isplib_gatv2_drop_csr_hip", m, n, k, nnz, indx, pntrb, pntre, x, ldx, y, ldy, att, heads, negative_slope, z, ldz,
+                        lse, stream, Gatv2Drop{true, threshold, scale, seed});
+}
+
+extern "C" int isplib_gatv2_drop_bw_rows_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                                             const int64_t *pntre, const float *x, int64_t ldx, const float *y, int64_t ldy,
+                                             const float *att, int64_t heads, float negative_slope, const float *g, int64_t ldg,
+                                             const float *z, int64_t ldz, const float *lse, float *dx, int64_t lddx, float *dsum,
+                                             float *datt, void *workspace, size_t workspace_bytes, void *stream, uint32_t threshold,
+                                             float scale, uint64_t seed) {
+   return gatv2_backward_rows("isplib_gatv2_drop_bw_rows_hip", m, n, k, nnz, indx, pntrb, pntre, x, ldx, y, ldy, att, heads,
+                              negative_slope, g, ldg, z, ldz, lse, dx, lddx, dsum, datt, workspace, workspace_bytes, stream,
+                              Gatv2Drop{true, threshold, scale, seed});
+}
+
+extern "C" int isplib_gatv2_drop_bw_cols_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t, const int64_t *colb,
+                                             const int64_t *cole, const int64_t *csr2csc, const float *x, int64_t ldx, const float *y,
+                                             int64_t ldy, const float *att, int64_t heads, float negative_slope, const float *g,
+                                             int64_t ldg, const float *lse, const float *dsum, float *dy, int64_t lddy, void *stream,
+                                             uint32_t threshold, float scale, uint64_t seed) {
+   return gatv2_backward_cols("isplib_gatv2_drop_bw_cols_hip", m, n, k, nnz, row_t, colb, cole, csr2csc, x, ldx, y, ldy, att, heads,
+                              negative_slope, g, ldg, lse, dsum, dy, lddy, stream, Gatv2Drop{true, threshold, scale, seed});
 }

@@ -1973,6 +1973,123 @@ Tensor gatv2_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor
    return Gatv2Spmm::apply(rowptr, col, colptr, row_t, x, y, att, heads, negative_slope)[0];
 }
 
+// ---- the GATv2 aggregation with attention dropout (isplib_gatv2_drop_*_hip) ----------
+// The coefficients are dropped after the softmax, per stored entry and head; the keep bit is the pure function of (seed, CSR position,
+// head) of gat_drop_spmm, so the backward regenerates the mask from the seed.  Saved for backward: what Gatv2Spmm saves, plus the two
+// scalars p and seed and csr2csc (the columns kernel walks the transposed structure).  Only the kernels whose gradients are asked for run.
+class Gatv2DropSpmm : public torch::autograd::Function<Gatv2DropSpmm> {
+ public:
+   static variable_list forward(AutogradContext *ctx, Variable rowptr, Variable col, Variable colptr, Variable row_t, Variable csr2csc,
+                                Variable x, Variable y, Variable att, int64_t heads, double negative_slope, double p, int64_t seed) {
+      check_index(rowptr, "rowptr"); check_index(col, "col"); check_index(colptr, "colptr"); check_index(row_t, "row_t");
+      check_index(csr2csc, "csr2csc");
+      TORCH_CHECK(x.defined() && x.dim() == 2 && y.defined() && y.dim() == 2, "isplib: gatv2_drop_spmm needs 2-D `x` [M, heads * d] and "
+                                                                              "`y` [N, heads * d]");
+      TORCH_CHECK(p > 0.0 && p < 1.0, "isplib: gatv2_drop_spmm: `p` must lie in (0, 1), got ", p, " (p == 0: gatv2_spmm)");
+      TORCH_CHECK(seed >= 0, "isplib: gatv2_drop_spmm: `seed` must be a non-negative int64, got ", seed);
+      OpTimer timer("FUSEDMM_GATV2_DROP_FW", y);
+      const int64_t M = rowptr.numel() - 1, N = colptr.numel() - 1, K = y.size(1), nnz = col.numel();
+      TORCH_CHECK(M >= 0 && N >= 0 && row_t.numel() == nnz && csr2csc.numel() == nnz,
+                  "isplib: gatv2_drop_spmm: `rowptr` / `colptr` need one entry more than rows / columns, `row_t` and `csr2csc` one entry per "
+                  "stored entry (", nnz, "), got ", row_t.numel(), " and ", csr2csc.numel());
+      TORCH_CHECK(heads >= 1 && K % heads == 0, "isplib: gatv2_drop_spmm: the width of `y` (", K, ") must be heads * d, got heads = ", heads);
+      const AttnOperand xo = gatv2_operand(x, "x", M, K), yo = gatv2_operand(y, "y", N, K);
+      TORCH_CHECK(att.defined(), "isplib: gatv2_drop_spmm needs `att` [heads, d]");
+      const Tensor av = gatv2_att(att, heads, K / heads);
+      for (const Tensor *t : {&rowptr, &col, &colptr, &row_t, &csr2csc, &x, &att})
+         TORCH_CHECK(t->device() == y.device(), "isplib: gatv2_drop_spmm: every operand must be on y's device");
+      TORCH_CHECK(K == 0 || isplib_gatv2_serves(N, heads, K / heads, yo.ld), "isplib: gatv2_drop_spmm: outside isplib_gatv2_serves (heads * d "
+                  "<= ", ISPLIB_GAT_K_MAX, ", heads == 1 or d a power of two >= 4, N < 2^31, N * pitch * 4 <= 3.5 GiB): N = ", N, ", heads = ",
+                  heads, ", d = ", K / heads, ", pitch = ", yo.ld);
+      TORCH_CHECK(nnz < (1LL << 31), "isplib: gatv2_drop_spmm: the keep bit is defined for CSR positions below 2^31, got nnz = ", nnz);
+      c10::DeviceGuard guard(y.device());
+      const Tensor rp = rowptr.contiguous(), cl = col.contiguous();
+      Tensor z = at::empty({M, K}, y.options()), lse = at::empty({M, heads}, y.options());
+      if (M > 0 && K > 0) {
+         const int st = isplib_gatv2_drop_csr_hip(M, N, K, nnz, cl.data_ptr<int64_t>(), rp.data_ptr<int64_t>(), rp.data_ptr<int64_t>() + 1,
+                                                  xo.t.data_ptr<float>(), xo.ld, nnz > 0 ? yo.t.data_ptr<float>() : nullptr, yo.ld,
+                                                  av.data_ptr<float>(), heads, (float)negative_slope, z.data_ptr<float>(), K,
+                                                  lse.data_ptr<float>(), current_stream(y), isplib_gat_drop_threshold(p),
+                                                  (float)(1.0 / (1.0 - p)), (uint64_t)seed);
+         check_status(st, "isplib_gatv2_drop_csr_hip");
+      } else if (M > 0) {
+         lse.fill_(-std::numeric_limits<float>::infinity());
+      }
+      ctx->saved_data["heads"] = heads;
+      ctx->saved_data["negative_slope"] = negative_slope;
+      ctx->saved_data["p"] = p;
+      ctx->saved_data["seed"] = seed;
+      ctx->save_for_backward({rp, cl, colptr, row_t, x, y, att, z, lse, csr2csc});
+      return {z};
+   }
+
+   static variable_list backward(AutogradContext *ctx, variable_list grad_outs) {
+      OpTimer timer("FUSEDMM_GATV2_DROP_BW", grad_outs[0]);
+      const bool need_x = ctx->needs_input_grad(5), need_y = ctx->needs_input_grad(6), need_att = ctx->needs_input_grad(7);
+      auto grad_x = Variable(), grad_y = Variable(), grad_att = Variable();
+      if (need_x || need_y || need_att) {
+         auto saved = ctx->get_saved_variables();
+         auto rp = saved[0], cl = saved[1], colptr = saved[2].contiguous(), row_t = saved[3].contiguous(), x = saved[4], y = saved[5], z = saved[7],
+              lse = saved[8];
+         const int64_t heads = ctx->saved_data["heads"].toInt();
+         const float ns = (float)ctx->saved_data["negative_slope"].toDouble();
+         const double p = ctx->saved_data["p"].toDouble();
+         const uint32_t threshold = isplib_gat_drop_threshold(p);
+         const float scale = (float)(1.0 / (1.0 - p));
+         const uint64_t seed = (uint64_t)ctx->saved_data["seed"].toInt();
+         const int64_t M = rp.numel() - 1, N = colptr.numel() - 1, K = y.size(1), nnz = cl.numel();
+         const AttnOperand xo = gatv2_operand(x, "x", M, K), yo = gatv2_operand(y, "y", N, K);
+         const Tensor av = gatv2_att(saved[6], heads, K / heads);
+         const AttnOperand go = gatv2_operand(grad_outs[0].to(at::kFloat), "grad_out", M, K);
+         c10::DeviceGuard guard(y.device());
+         // as in Gatv2Spmm: the rows kernel always runs (D feeds the columns kernel), its datt instantiation only when att asks, the
+         // columns kernel only when y asks
+         Tensor dx = at::empty({M, K}, y.options()), dsum = at::empty({M, heads}, y.options());
+         Tensor datt = need_att ? at::empty({heads, K / heads}, y.options()) : Tensor();
+         if (M > 0 && K > 0) {
+            const size_t ws = need_att ? isplib_gatv2_bw_rows_workspace_bytes(M, K) : 0;
+            Tensor work = need_att ? at::empty({(int64_t)ws}, y.options().dtype(at::kByte)) : Tensor();
+            const int st = isplib_gatv2_drop_bw_rows_hip(M, N, K, nnz, cl.data_ptr<int64_t>(), rp.data_ptr<int64_t>(),
+                                                         rp.data_ptr<int64_t>() + 1, xo.t.data_ptr<float>(), xo.ld,
+                                                         nnz > 0 ? yo.t.data_ptr<float>() : nullptr, yo.ld, av.data_ptr<float>(), heads, ns,
+                                                         go.t.data_ptr<float>(), go.ld, z.data_ptr<float>(), K, lse.data_ptr<float>(),
+                                                         dx.data_ptr<float>(), K, dsum.data_ptr<float>(),
+                                                         need_att ? datt.data_ptr<float>() : nullptr, need_att ? work.data_ptr() : nullptr, ws,
+                                                         current_stream(y), threshold, scale, seed);
+            check_status(st, "isplib_gatv2_drop_bw_rows_hip");
+         } else if (need_att) {
+            datt.zero_();
+         }
+         if (need_x) grad_x = dx;
+         if (need_att) grad_att = datt;
+         if (need_y) {
+            TORCH_CHECK(K == 0 || (isplib_gatv2_serves(M, heads, K / heads, xo.ld) && isplib_gatv2_serves(M, heads, K / heads, go.ld)),
+                        "isplib: gatv2_drop_spmm backward: outside isplib_gatv2_serves for the gathered rows of x and of the gradient: M = ",
+                        M, ", K = ", K);
+            const Tensor pos = saved[9].contiguous();
+            Tensor dy = at::empty({N, K}, y.options());
+            if (N > 0 && K > 0) {
+               const int st = isplib_gatv2_drop_bw_cols_hip(M, N, K, nnz, row_t.data_ptr<int64_t>(), colptr.data_ptr<int64_t>(),
+                                                            colptr.data_ptr<int64_t>() + 1, nnz > 0 ? pos.data_ptr<int64_t>() : nullptr,
+                                                            nnz > 0 ? xo.t.data_ptr<float>() : nullptr, xo.ld, yo.t.data_ptr<float>(), yo.ld,
+                                                            av.data_ptr<float>(), heads, ns, nnz > 0 ? go.t.data_ptr<float>() : nullptr, go.ld,
+                                                            lse.data_ptr<float>(), dsum.data_ptr<float>(), dy.data_ptr<float>(), K,
+                                                            current_stream(y), threshold, scale, seed);
+               check_status(st, "isplib_gatv2_drop_bw_cols_hip");
+            }
+            grad_y = dy;
+         }
+      }
+      return {Variable(), Variable(), Variable(), Variable(), Variable(), grad_x, grad_y, grad_att, Variable(), Variable(), Variable(),
+              Variable()};
+   }
+};
+
+Tensor gatv2_drop_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor csr2csc, Tensor x, Tensor y, Tensor att, int64_t heads,
+                       double negative_slope, double p, int64_t seed) {
+   return Gatv2DropSpmm::apply(rowptr, col, colptr, row_t, csr2csc, x, y, att, heads, negative_slope, p, seed)[0];
+}
+
 // ---- the GATv2 aggregation for bf16 / fp16 `x` and `y` (isplib_gatv2_16_*_hip) ----------
 // x and y go in as they lie, z, dx and dy come back in their dtype; att, lse, D and datt stay fp32: no fp32 [*, K] tensor in either
 // direction.  Saved for backward: the structure, x, y, att and lse -- NOT z: the rows kernel forms D[i,h] from the row's edges.  A wide
@@ -2158,6 +2275,8 @@ TORCH_LIBRARY(isplib, m) {
          &gat_spmm16);
    m.def("gatv2_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor x, Tensor y, Tensor att, int heads, float negative_slope) -> Tensor",
          &gatv2_spmm);
+   m.def("gatv2_drop_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor csr2csc, Tensor x, Tensor y, Tensor att, int heads, float negative_slope, float p, int seed) -> Tensor",
+         &gatv2_drop_spmm);
    m.def("gatv2_spmm16(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor x, Tensor y, Tensor att, int heads, float negative_slope) -> Tensor",
          &gatv2_spmm16);
 }

@@ -980,8 +980,8 @@ def _fmix32(x: torch.Tensor) -> torch.Tensor:
 
 
 def gat_dropout_mask(adj_or_nnz, heads: int, dropout: float, seed: int, device=None) -> torch.Tensor:
-    """The keep mask of ``gat_matmul(..., dropout=dropout, seed=seed)``: a bool tensor [nnz, heads], row e belonging to the stored entry
-    ``storage.col()[e]``; True = kept.  The realised coefficients are ``mask * a / (1 - dropout)``.  `adj_or_nnz` is the sparse matrix
+    """The keep mask of ``gat_matmul(..., dropout=dropout, seed=seed)`` and of ``gatv2_matmul(..., dropout=dropout, seed=seed)`` -- one
+    function serves both operators: a bool tensor [nnz, heads], row e belonging to the stored entry ``storage.col()[e]``; True = kept.  The realised coefficients are ``mask * a / (1 - dropout)``.  `adj_or_nnz` is the sparse matrix
     (the mask is built on its device) or the number of stored entries (on `device`, the CPU by default).  Written with torch integer
     operations on int64 values masked to 32 bits -- the function of include/isplib_hip.h:
         word(seed, pos, h) = fmix32(fmix32(uint32(pos) ^ uint32(seed)) + uint32(h) * 0x9E3779B9 + uint32(seed >> 32)),  keep = word >= T(p)
@@ -1009,7 +1009,7 @@ def gat_dropout_mask(adj_or_nnz, heads: int, dropout: float, seed: int, device=N
 
 
 def gatv2_matmul(src, x: torch.Tensor, att: torch.Tensor, y: Optional[torch.Tensor] = None, heads: int = 1,
-                 negative_slope: float = 0.2) -> torch.Tensor:
+                 negative_slope: float = 0.2, dropout: float = 0.0, training: bool = True, seed: Optional[int] = None) -> torch.Tensor:
     """GATv2 attention aggregation over the stored entries of `src`, all heads in one launch (include/isplib_hip.h,
     isplib_gatv2_csr_hip): ``z[i, head h] = sum_j softmax_j(sum_c att[h, c] leaky_relu(x[i, c] + y[j, c])) y[j, head h]`` over the
     entries (i, j) of row i, c over the columns of head h -- the aggregation of GATv2Conv, with its autograd backward in `x`, `y` and
@@ -1025,8 +1025,19 @@ def gatv2_matmul(src, x: torch.Tensor, att: torch.Tensor, y: Optional[torch.Tens
     gradient with M rows at pitch K), else `x.float()`, `y.float()` -> this function -> `.to(dtype)`, which raises only what the fp32
     call raises.  `att` may then be float32 or of that dtype (a 16-bit `att` is widened by `.float()`, which is exact, and its gradient
     returns in its own dtype through that cast); the result and the gradients of `x` and `y` have their dtype.  fp32 calls do not read
-    the variable."""
+    the variable.
+    `dropout` (GATv2Conv's ``dropout``; a Python float or int in [0, 1)) drops attention coefficients AFTER the softmax, per stored entry
+    and per head, and scales the kept ones by ``float32(1 / (1 - dropout))`` (torch.ops.isplib.gatv2_drop_spmm): the softmax still runs
+    over every stored entry.  ``dropout == 0`` or ``training=False`` is the call above, unchanged, bit for bit.  The mask is the one of
+    `gat_matmul` -- a pure function of (`seed`, the entry's position in ``storage.col()``, head), which `gat_dropout_mask` returns and
+    the backward recomputes: nothing per edge is stored and no RNG state is kept.  ``seed=None`` draws one int64 in [0, 2^63) from
+    torch's default CPU generator (reproducible under ``torch.manual_seed``, no device sync); an explicit `seed` is an int in [0, 2^63).
+    The seed is a kernel ARGUMENT: a captured graph replays ONE mask -- draw the seed outside the capture and re-capture, or do not
+    capture a training step that needs fresh masks.  There is no 16-bit dropout kernel: with 16-bit `x` / `y` and the GATv2 variable
+    set (to any value) a call with active dropout converts -- ``.float()`` -> the fp32 dropout operator -> ``.to(dtype)``, every
+    gradient returning in its own dtype through the casts; with the variable unset it raises the TypeError above."""
     from . import cabi
+    drop = _gat_dropout_args(dropout, training, seed)
     shared = y is None
     if shared:
         y = x
@@ -1041,6 +1052,9 @@ def gatv2_matmul(src, x: torch.Tensor, att: torch.Tensor, y: Optional[torch.Tens
             raise TypeError(f"isplib_amd: `att` must be float32 or of `x`'s dtype ({x.dtype}), got {t.dtype}")
         if not half and t.dtype != torch.float32:
             raise TypeError(f"isplib_amd: `{name}` must be float32, got {t.dtype} (the GATv2 operator is fp32 only)")
+    if half and drop is not None:         # the conversion route whatever the variable says: .float() is exact
+        return gatv2_matmul(src, x.float(), att.float(), None if shared else y.float(), heads, negative_slope, drop[0], True,
+                            drop[1]).to(x.dtype)
     if half:
         return _gatv2_matmul16(src, x, att, None if shared else y, heads, negative_slope)
     if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
@@ -1078,6 +1092,11 @@ def gatv2_matmul(src, x: torch.Tensor, att: torch.Tensor, y: Optional[torch.Tens
         raise TypeError("isplib_amd: `x`, `y` and `att` must be GPU tensors -- there is no CPU path")
     if x.device != y.device or att.device != y.device or st._rowptr.device != y.device:
         raise ValueError("isplib_amd: `x`, `y`, `att` and the sparse matrix must be on one device")
+    if drop is not None:
+        if st._col.numel() >= 2 ** 31:
+            raise ValueError(f"isplib_amd: the dropout keep bit is defined for fewer than 2^31 stored entries, got {st._col.numel()}")
+        return torch.ops.isplib.gatv2_drop_spmm(st._rowptr, st._col, st.colptr(), st.row_t(), st.csr2csc(), x, y, att, heads,
+                                                float(negative_slope), *drop)
     return torch.ops.isplib.gatv2_spmm(st._rowptr, st._col, st.colptr(), st.row_t(), x, y, att, heads, float(negative_slope))
 
 

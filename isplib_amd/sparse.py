@@ -353,8 +353,10 @@ class SparseTensor:
         return gat_matmul(self, y, a_dst, a_src, heads, negative_slope, a_edge, dropout, training, seed)
 
     def gatv2_matmul(self, x: torch.Tensor, att: torch.Tensor, y: Optional[torch.Tensor] = None, heads: int = 1,
-                     negative_slope: float = 0.2) -> torch.Tensor:
+                     negative_slope: float = 0.2, dropout: float = 0.0, training: bool = True,
+                     seed: Optional[int] = None) -> torch.Tensor:
         """GATv2 attention aggregation over this matrix's stored entries, all heads in one launch (plugin.gatv2_matmul); bf16 / fp16
-        `x` and `y` are opt-in through ISPLIB_HALF_GATV2."""
+        `x` and `y` are opt-in through ISPLIB_HALF_GATV2.  `dropout` with `training`: attention dropout after the softmax, its mask a
+        function of `seed` (None: drawn from torch's default CPU generator), the entry's position and the head."""
         from .plugin import gatv2_matmul
-        return gatv2_matmul(self, x, att, y, heads, negative_slope)
+        return gatv2_matmul(self, x, att, y, heads, negative_slope, dropout, training, seed)
