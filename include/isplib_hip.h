@@ -1402,4 +1402,8 @@ void isplib_graph_destroy(isplib_graph *g);
 /* the GATv2 aggregation with attention dropout (isplib_gatv2_drop_*): part of this interface, declared in a file of its own */
 #include "isplib_hip_gatv2_drop.h"
 
+/* sparse multi-head dot-product attention with separate keys and values (isplib_mha_*): part of this interface, declared in a file of
+ * its own */
+#include "isplib_hip_mha.h"
+
 #endif /* ISPLIB_HIP_H */

@@ -12,9 +12,9 @@ from . import _lib
 _lib.load_ops()
 
 from . import cabi  # noqa: E402
-from .plugin import attention_matmul, fusedmm, gat_dropout_mask, gat_matmul, gatv2_matmul, gcn_norm_matmul, iSpLibPlugin, isplib_autotune, matmul, spmm_autotuned  # noqa: E402
+from .plugin import attention_matmul, fusedmm, gat_dropout_mask, gat_matmul, gatv2_matmul, gcn_norm_matmul, iSpLibPlugin, isplib_autotune, matmul, mha_matmul, spmm_autotuned  # noqa: E402
 from .sparse import SparseStorage, SparseTensor  # noqa: E402
 
 __version__ = "0.1.0"
-__all__ = ["iSpLibPlugin", "isplib_autotune", "matmul", "spmm_autotuned", "gcn_norm_matmul", "fusedmm", "attention_matmul", "gat_matmul", "gat_dropout_mask", "gatv2_matmul", "SparseTensor", "SparseStorage",
+__all__ = ["iSpLibPlugin", "isplib_autotune", "matmul", "spmm_autotuned", "gcn_norm_matmul", "fusedmm", "attention_matmul", "gat_matmul", "gat_dropout_mask", "gatv2_matmul", "mha_matmul", "SparseTensor", "SparseStorage",
            "cabi"]

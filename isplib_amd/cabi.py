@@ -154,6 +154,12 @@ def gatv2_serves(rows_gathered: int, heads: int, d: int, ld: int) -> bool:
     return gat_serves(rows_gathered, heads, d, ld)
 
 
+def mha_serves(rows_gathered: int, heads: int, d: int, ld: int) -> bool:
+    """isplib_mha_serves of include/isplib_hip_mha.h: the multi-head dot-product entries' domain IS isplib_gat_serves, asked of every
+    gathered operand (key, v; q, g in the columns entry) at its own row count and pitch; tests/test_mha_host.py compares the two."""
+    return gat_serves(rows_gathered, heads, d, ld)
+
+
 ATTENTION16_K_MIN, ATTENTION16_K_MAX = 8, 512   # the 16-bit attention entries: eight columns per lane, one 16-byte chunk per lane
 
 
@@ -279,6 +285,10 @@ GATV2_16_EXPORTS = (
 # include/isplib_hip_gatv2_drop.h (which isplib_hip.h includes; the same library): the GATv2 entries with attention dropout, listed
 # apart for the reason the 16-bit GATv2 entries are -- EXPORTS is what isplib_hip.h itself declares, and its GATv2 names are pinned
 GATV2_DROP_EXPORTS = ("isplib_gatv2_drop_csr_hip", "isplib_gatv2_drop_bw_rows_hip", "isplib_gatv2_drop_bw_cols_hip")
+
+# include/isplib_hip_mha.h (which isplib_hip.h includes; the same library): multi-head dot-product attention with separate keys and
+# values, listed apart for the same reason; tests/test_mha_host.py compares this list with that header and the library's symbols
+MHA_EXPORTS = ("isplib_mha_csr_hip", "isplib_mha_bw_rows_hip", "isplib_mha_bw_cols_hip", "isplib_mha_domain")
 
 # the two host functions of the dropout keep bit (isplib_hip.h declares them; they return uint32_t, not a status, and are listed apart)
 GAT_DROP_HOST_EXPORTS = ("isplib_gat_drop_threshold", "isplib_gat_drop_word")
@@ -593,6 +603,16 @@ def lib() -> ctypes.CDLL:
         L.isplib_gatv2_drop_bw_cols_hip.restype = ctypes.c_int
         L.isplib_gatv2_drop_bw_cols_hip.argtypes = (L.isplib_gatv2_bw_cols_hip.argtypes[:7] + [_vp] + L.isplib_gatv2_bw_cols_hip.argtypes[7:] +
                                                     _drop)
+        L.isplib_mha_domain.restype = ctypes.c_int
+        L.isplib_mha_domain.argtypes = [_i64, _i64, _i64, _i64]
+        L.isplib_mha_csr_hip.restype = ctypes.c_int
+        L.isplib_mha_csr_hip.argtypes = [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _f32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]
+        L.isplib_mha_bw_rows_hip.restype = ctypes.c_int
+        L.isplib_mha_bw_rows_hip.argtypes = [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _f32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
+                                             _vp, _vp, _i64, _vp, _vp]
+        L.isplib_mha_bw_cols_hip.restype = ctypes.c_int
+        L.isplib_mha_bw_cols_hip.argtypes = [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _f32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64,
+                                             _vp, _i64, _vp, _i64, _vp]
         L.isplib_gatv2_16_domain.restype = ctypes.c_int
         L.isplib_gatv2_16_domain.argtypes = [_i64, _i64, _i64, _i64]
         L.isplib_gatv2_16_auto.restype = ctypes.c_int
@@ -2667,6 +2687,155 @@ def gatv2_drop_bw_cols(colptr, row_t, csr2csc, x, y, att, g, lse, dsum, threshol
     entry walks the transposed structure.  Returns dy."""
     return _gatv2_backward_cols(colptr, row_t, csr2csc, x, y, att, g, lse, dsum, heads, negative_slope, out, check,
                                 _gat_drop_args(threshold, scale, seed))
+
+
+def _mha_domain(rows_gathered: int, heads: int, d: int, lds) -> None:
+    for ld in lds:
+        if d > 0 and not mha_serves(rows_gathered, heads, d, ld):
+            raise ValueError(f"isplib_amd: outside the multi-head attention entries' domain (isplib_mha_serves = isplib_gat_serves: heads * d <= "
+                             f"{GAT_K_MAX}, heads == 1 or d a power of two >= 4, gathered rows < 2^31, rows * pitch * 4 <= 3.5 GiB), got "
+                             f"rows={rows_gathered}, heads={heads}, d={d}, pitch={ld}")
+
+
+def _mha_scale(scale, d: int) -> float:
+    """The scale of the scores: a finite Python number, or None for 1 / sqrt(d) -- the HEAD width, not k."""
+    if scale is None:
+        return 1.0 / float(d) ** 0.5 if d > 0 else 1.0
+    if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not math.isfinite(scale):
+        raise ValueError(f"isplib_amd: `scale` must be a finite number or None, got {scale!r}")
+    return float(scale)
+
+
+def _mha_qkv(m: int, q, k, v):
+    """q [m, K] and k, v [n, K] of the multi-head entries; returns (n, K, ldq, ldk, ldv)."""
+    ldq = _attn_dense(q, "q", m, None, "one row per row of the sparse operand")
+    kk = q.size(1)
+    if not isinstance(k, torch.Tensor) or k.dim() != 2:
+        raise ValueError("isplib_amd: `k` must be a 2-D tensor [n, heads * d]")
+    n = k.size(0)
+    ldk = _attn_dense(k, "k", n, kk, "one row per column of the sparse operand, q's width")
+    ldv = _attn_dense(v, "v", n, kk, "one row per column of the sparse operand, q's width")
+    return n, kk, ldq, ldk, ldv
+
+
+def mha(rowptr, col, q, k, v, heads: int = 1, scale: Optional[float] = None, *, out=None, check: bool = True):
+    """Sparse multi-head dot-product attention with separate keys and values, all heads in one launch (isplib_mha_csr_hip): over the
+    stored entries e = (i, j) of the CSR structure and every head h, s_e = scale <q_i, k_j>_h, a_e = softmax of s over the row's entries,
+    z_i[head h] = sum_e a_e v_j[head h].  Returns (z [m, heads * d], lse [m, heads]); an empty row has z_i = 0 and lse = -inf.  `q`
+    [m, heads * d], `k` and `v` [n, heads * d] float32 (row-strided views keep their pitch: column views of one fused projection go in
+    without a copy); `scale` None: 1 / sqrt(d); `out` = (z, lse) to write in place.  Every operand is checked BEFORE the call
+    (`check`: also the two checks that read the structure on the device)."""
+    if not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1 or rowptr.numel() < 1:
+        raise ValueError("isplib_amd: `rowptr` (m + 1 entries) must be a 1-D tensor")
+    m = rowptr.numel() - 1
+    n, kk, ldq, ldk, ldv = _mha_qkv(m, q, k, v)
+    d = _gat_heads(heads, kk)
+    p = _mha_scale(scale, d)
+    rowptr, col = _attn_structure(rowptr, col, "rowptr", "col", n, check)
+    if out is not None:
+        z, lse = out
+        ldz = _attn_dense(z, "out[0]", m, kk, "z")
+        _gat_table(lse, "out[1]", m, heads)
+    _mha_domain(n, heads, d, (ldk, ldv))
+    _same_gpu((("q", q), ("k", k), ("v", v), ("rowptr", rowptr), ("col", col)) +
+              ((("out[0]", out[0]), ("out[1]", out[1])) if out is not None else ()))
+    if out is None:
+        z = torch.empty((m, kk), dtype=torch.float32, device=q.device)
+        lse = torch.empty((m, heads), dtype=torch.float32, device=q.device)
+        ldz = max(kk, 1)
+    if m == 0 or kk == 0:
+        if kk == 0 and m > 0:
+            lse.fill_(float("-inf"))
+        return z, lse
+    rp = rowptr.data_ptr()
+    with torch.cuda.device(q.device):
+        st = lib().isplib_mha_csr_hip(m, n, kk, col.numel(), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8), heads, p, _ptr(q), ldq,
+                                      _ptr(k), ldk, _ptr(v), ldv, _ptr(z), ldz, _ptr(lse), _stream(q.device))
+    _check(st, "isplib_mha_csr_hip")
+    return z, lse
+
+
+def mha_bw_rows(rowptr, col, q, k, v, g, z, lse, heads: int = 1, scale: Optional[float] = None, *, out=None, check: bool = True):
+    """The backward of `mha` over the rows (isplib_mha_bw_rows_hip): for g = dL/dz [m, heads * d] and the forward's z and lse,
+    D[i,h] = <g_i, z_i>_h, ds_e = a_e (<g_i, v_j>_h - D[i,h]) with a_e recomputed from lse, dq_i[head h] = scale sum_e ds_e k_j[head h].
+    Returns (dq [m, heads * d], D [m, heads]); an empty row has dq_i = 0 and D = 0.  `out` = (dq, D); the operand checks are mha's."""
+    if not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1 or rowptr.numel() < 1:
+        raise ValueError("isplib_amd: `rowptr` (m + 1 entries) must be a 1-D tensor")
+    m = rowptr.numel() - 1
+    n, kk, ldq, ldk, ldv = _mha_qkv(m, q, k, v)
+    d = _gat_heads(heads, kk)
+    p = _mha_scale(scale, d)
+    ldg = _attn_dense(g, "g", m, kk, "the gradient of z")
+    ldz = _attn_dense(z, "z", m, kk, "the forward's output")
+    _gat_table(lse, "lse", m, heads)
+    rowptr, col = _attn_structure(rowptr, col, "rowptr", "col", n, check)
+    if out is not None:
+        if len(out) != 2:
+            raise ValueError("isplib_amd: `out` must be (dq, D)")
+        lddq = _attn_dense(out[0], "out[0]", m, kk, "dq")
+        _gat_table(out[1], "out[1]", m, heads)
+    _mha_domain(n, heads, d, (ldk, ldv))
+    _same_gpu((("q", q), ("k", k), ("v", v), ("g", g), ("z", z), ("lse", lse), ("rowptr", rowptr), ("col", col)) +
+              ((("out[0]", out[0]), ("out[1]", out[1])) if out is not None else ()))
+    if out is None:
+        out = (torch.empty((m, kk), dtype=torch.float32, device=q.device), torch.empty((m, heads), dtype=torch.float32, device=q.device))
+        lddq = max(kk, 1)
+    dq, dsum = out
+    if m == 0 or kk == 0:
+        if kk == 0 and m > 0:
+            dsum.zero_()
+        return dq, dsum
+    rp = rowptr.data_ptr()
+    with torch.cuda.device(q.device):
+        st = lib().isplib_mha_bw_rows_hip(m, n, kk, col.numel(), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8), heads, p, _ptr(q),
+                                          ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(g), ldg, _ptr(z), ldz, _ptr(lse), _ptr(dq), lddq, _ptr(dsum),
+                                          _stream(q.device))
+    _check(st, "isplib_mha_bw_rows_hip")
+    return dq, dsum
+
+
+def mha_bw_cols(colptr, row_t, q, k, v, g, lse, dsum, heads: int = 1, scale: Optional[float] = None, *, out=None, check: bool = True):
+    """The backward of `mha` over the columns (isplib_mha_bw_cols_hip), on the transposed structure (`colptr` [n + 1], `row_t`: the row
+    ids of the entries in column-major order): dk_j[head h] = scale sum over the entries e = (i, j) of column j of ds_e q_i[head h] and
+    dv_j[head h] = sum of a_e g_i[head h], with `lse` of the forward and `dsum` = D of mha_bw_rows.  Returns (dk, dv), both
+    [n, heads * d]; a column no entry points at has 0 in both.  `out` = (dk, dv); the operand checks are mha's."""
+    if not isinstance(colptr, torch.Tensor) or colptr.dim() != 1 or colptr.numel() < 1:
+        raise ValueError("isplib_amd: `colptr` (n + 1 entries) must be a 1-D tensor")
+    n = colptr.numel() - 1
+    ldk = _attn_dense(k, "k", n, None, "one row per column of the sparse operand")
+    kk = k.size(1)
+    ldv = _attn_dense(v, "v", n, kk, "one row per column of the sparse operand, k's width")
+    d = _gat_heads(heads, kk)
+    p = _mha_scale(scale, d)
+    if not isinstance(q, torch.Tensor) or q.dim() != 2:
+        raise ValueError("isplib_amd: `q` must be a 2-D tensor [m, heads * d]")
+    m = q.size(0)
+    ldq = _attn_dense(q, "q", m, kk, "one row per row of the sparse operand, k's width")
+    ldg = _attn_dense(g, "g", m, kk, "the gradient of z")
+    _gat_table(lse, "lse", m, heads)
+    _gat_table(dsum, "dsum", m, heads)
+    colptr, row_t = _attn_structure(colptr, row_t, "colptr", "row_t", m, check)
+    if out is not None:
+        if len(out) != 2:
+            raise ValueError("isplib_amd: `out` must be (dk, dv)")
+        lddk = _attn_dense(out[0], "out[0]", n, kk, "dk")
+        lddv = _attn_dense(out[1], "out[1]", n, kk, "dv")
+    _mha_domain(m, heads, d, (ldq, ldg))
+    _same_gpu((("q", q), ("k", k), ("v", v), ("g", g), ("lse", lse), ("dsum", dsum), ("colptr", colptr), ("row_t", row_t)) +
+              ((("out[0]", out[0]), ("out[1]", out[1])) if out is not None else ()))
+    if out is None:
+        out = (torch.empty((n, kk), dtype=torch.float32, device=k.device), torch.empty((n, kk), dtype=torch.float32, device=k.device))
+        lddk = lddv = max(kk, 1)
+    dk, dv = out
+    if n == 0 or kk == 0:
+        return dk, dv
+    cp = colptr.data_ptr()
+    with torch.cuda.device(k.device):
+        st = lib().isplib_mha_bw_cols_hip(m, n, kk, row_t.numel(), _ptr(row_t), ctypes.c_void_p(cp), ctypes.c_void_p(cp + 8), heads, p,
+                                          _ptr(q), ldq, _ptr(g), ldg, _ptr(lse), _ptr(dsum), _ptr(k), ldk, _ptr(v), ldv, _ptr(dk), lddk,
+                                          _ptr(dv), lddv, _stream(k.device))
+    _check(st, "isplib_mha_bw_cols_hip")
+    return dk, dv
 
 
 def _attn16_dense(t, name: str, rows: int, k: Optional[int], what: str, dtype=None) -> int:

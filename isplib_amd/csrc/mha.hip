@@ -1,0 +1,586 @@
+// mha.hip -- sparse multi-head dot-product attention with separate keys and values over the stored entries of a CSR matrix, all heads in
+// one launch, forward and backward (include/isplib_hip_mha.h: isplib_mha_csr_hip, isplib_mha_bw_rows_hip, isplib_mha_bw_cols_hip).  For
+// every row i, stored entry e = (i, j) and head h, with q [m, k], key [n, k], v [n, k], k = H*d (head h owns the columns [h*d, (h+1)*d))
+// and a scalar scale p:
+//    s_e  = p <q_i, key_j>_h     a_e = exp(s_e - lse[i,h]),  lse[i,h] = log sum_e exp(s_e)     z_i[head h] = sum_e a_e v_j[head h]
+// and for g = dL/dz
+//    D[i,h] = <g_i, z_i>_h       t_e = <g_i, v_j>_h          ds_e = a_e (t_e - D[i,h])
+//    dq_i[head h]   = p sum_e ds_e key_j[head h]
+//    dkey_j[head h] = p sum_{e -> j} ds_e q_i[head h]
+//    dv_j[head h]   = sum_{e -> j} a_e g_i[head h].
+// Stored values are not read; every stored entry is its own edge; an empty row has z_i = 0, lse = -inf, D = 0, dq_i = 0; a column no
+// entry references has dkey_j = dv_j = 0.
+//
+// Mapping: that of gatv2.hip -- one wave per row (per column of A in the columns kernel), G = 64 / LPR edge slots, NCH chunks of 4
+// consecutive columns per lane, the same (LPR, NCH) instantiations, head geometry and per-head butterfly.  What is new is the second
+// gathered operand: per edge and chunk the forward and the rows kernel issue TWO 16-byte gathers, key_j for the score and v_j for the
+// value, each behind its own descriptor.  The dot products of a step (U scores in the forward, U scores and U <g_i, v_j>_h in the
+// backward kernels) go through the levels of ONE butterfly together.  p multiplies the finished dot product, in all three kernels alike,
+// and the finished rows of dq and dkey.
+//
+// The softmax is the online form of gatv2.hip per chunk: (m, l, acc) rescaled once per step, a finite "no edge yet" sentinel, the G
+// slots merged pairwise at the end of the row.  The backward stores nothing per edge: a_e is recomputed from lse.  The rows kernel
+// holds q_i, g_i and z_i, forms D[i,h] from them and writes dq and D.  The columns kernel walks the transposed structure with key_j
+// and v_j in registers, gathers q_i and g_i (16 bytes each) and lse, D of [i, head] (4 bytes each, two tables, each behind its own
+// descriptor), and writes dkey and dv as two outputs.
+//
+// Every gathered table sits behind a buffer descriptor of exactly the extent it owns; dead edges and lanes past k carry BUF_OOB, which
+// the descriptor answers with 0.  No atomics, no LDS, a fixed order of operations: two launches give equal bits.  attention.hip,
+// gat.hip and gatv2.hip are untouched; their small helpers are restated here under names of their own.  DESIGN.md 4.6k.
+#include <cfloat>
+#include <cmath>
+
+#include "common.h"
+#include "gather.h"
+
+namespace isplib {
+
+constexpr float MHA_NONE = -FLT_MAX;       // the running maximum of a chunk that saw no edge
+constexpr int MHA_WAVES = 4;               // rows per block
+
+struct MhaArgs {
+   int64_t rows, k;                        // rows: one wave each (rows of A; columns of A in the columns kernel)
+   int heads;
+   int hshift;                             // head of column c: c >> hshift (H == 1: 31, every column is head 0)
+   int hlanes;                             // lanes of one chunk that share a head: d / 4 (H == 1: 64, the whole slot)
+   unsigned hmask;                         // c & hmask == 0: the first column of a head (H == 1: only column 0)
+   int whole;                              // H == 1: the head spans both chunks of a lane
+   const int64_t *indx, *pntrb, *pntre;
+   float p;                                // the scale of the scores
+   // the row-resident operands (plain loads of the wave's own row) and the outputs
+   const float *own;                       // forward, rows: q | columns: key
+   int64_t ldown;
+   const float *own2;                      // columns: v
+   int64_t ldown2;
+   const float *g;                         // rows: dL/dz
+   int64_t ldg;
+   const float *zin;                       // rows: z of the forward
+   int64_t ldzin;
+   const float *lse_in;                    // rows: lse [rows, H]
+   float *out;                             // z | dq | dkey
+   int64_t ldout;
+   float *out2;                            // columns: dv
+   int64_t ldout2;
+   float *hout;                            // [rows, H]: forward lse | rows: D
+   // the gathered operands, each behind one descriptor
+   const float *ga;                        // forward, rows: key | columns: q
+   int64_t ldga;
+   unsigned gabytes;
+   const float *gb;                        // forward, rows: v | columns: g
+   int64_t ldgb;
+   unsigned gbbytes;
+   const float *t1, *t2;                   // columns: lse, D; both [gathered rows, H]
+   unsigned tbytes;
+};
+
+template <int LPR, int NCH> struct MhaCols {
+   unsigned cbyte[NCH], poison[NCH];       // this lane's 4 consecutive columns per chunk; past k: an offset the descriptor answers with 0
+   unsigned hbyte[NCH];                    // byte offset of the chunk's head inside a row of a [., H] table
+   int head[NCH];
+   bool ok[NCH][4], first[NCH];            // first: this lane's chunk opens a head (and lies inside k)
+   __device__ __forceinline__ MhaCols(const MhaArgs &a, int lc) {
+#pragma unroll
+      for (int j = 0; j < NCH; j++) {
+         const int c = (j * LPR + lc) * 4;
+         cbyte[j] = (unsigned)c * 4u;
+         poison[j] = c < (int)a.k ? 0u : BUF_OOB;
+         head[j] = c >> a.hshift;
+         hbyte[j] = (unsigned)head[j] * 4u;
+         first[j] = c < (int)a.k && ((unsigned)c & a.hmask) == 0u;
+#pragma unroll
+         for (int v = 0; v < 4; v++) ok[j][v] = c + v < (int)a.k;
+      }
+   }
+};
+
+// this lane's columns of row `row` of a dense operand; plain loads, nothing outside the row's k columns is read
+template <int LPR, int NCH>
+__device__ __forceinline__ void mha_own_row(const float *base, int64_t row, int64_t ld, int lc, const MhaCols<LPR, NCH> &cm,
+                                            float (&r)[NCH][4]) {
+#pragma unroll
+   for (int j = 0; j < NCH; j++)
+#pragma unroll
+      for (int v = 0; v < 4; v++) r[j][v] = cm.ok[j][v] ? base[(size_t)row * (size_t)ld + (size_t)((j * LPR + lc) * 4 + v)] : 0.0f;
+}
+
+// entry [row, head of chunk j] of a dense [rows, H] table, per chunk; a chunk past k reads nothing
+template <int LPR, int NCH>
+__device__ __forceinline__ void mha_own_head(const float *base, int64_t row, int heads, const MhaCols<LPR, NCH> &cm, float (&r)[NCH]) {
+#pragma unroll
+   for (int j = 0; j < NCH; j++) r[j] = cm.ok[j][0] ? base[(size_t)row * (size_t)heads + (size_t)cm.head[j]] : 0.0f;
+}
+
+// this lane's columns of a row, stored; nothing outside the row's k columns is written
+template <int LPR, int NCH>
+__device__ __forceinline__ void mha_store_row(float *base, int64_t row, int64_t ld, int lc, const MhaCols<LPR, NCH> &cm,
+                                              const float (&r)[NCH][4]) {
+#pragma unroll
+   for (int j = 0; j < NCH; j++)
+#pragma unroll
+      for (int v = 0; v < 4; v++)
+         if (cm.ok[j][v]) base[(size_t)row * (size_t)ld + (size_t)((j * LPR + lc) * 4 + v)] = r[j][v];
+}
+
+template <int LPR, int NCH>
+__device__ __forceinline__ void mha_load_wide(const __amdgpu_buffer_rsrc_t rsrc, unsigned off, const MhaCols<LPR, NCH> &cm, v4i_t (&t)[NCH]) {
+#pragma unroll
+   for (int j = 0; j < NCH; j++) t[j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)((off + cm.cbyte[j]) | cm.poison[j]), 0, 0);
+}
+
+template <int LPR, int NCH>
+__device__ __forceinline__ void mha_load_head(const __amdgpu_buffer_rsrc_t rsrc, unsigned offh, const MhaCols<LPR, NCH> &cm, float (&t)[NCH]) {
+#pragma unroll
+   for (int j = 0; j < NCH; j++)
+      t[j] = __int_as_float((int)__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)((offh + cm.hbyte[j]) | cm.poison[j]), 0, 0));
+}
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t mha_rsrc(const float *p, unsigned bytes) {
+   return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p), 0, (int)bytes, 0x00020000);
+}
+
+// N sums over the lanes that share a head (an aligned group of `hlanes` lanes, a power of two <= LPR), level by level together; every
+// lane of the group ends with the same bits (each level adds the same two numbers on both sides).  Partners 1, 2, 4, 8 by DPP moves
+// inside the 16-lane row (gather.h), wider ones by ds_bpermute.
+template <int LPR, int N, int O = 1> __device__ __forceinline__ void mha_head_sum(float (&v)[N], int hlanes) {
+   if constexpr (O < LPR) {
+      float w[N];
+#pragma unroll
+      for (int i = 0; i < N; i++) w[i] = lane_xor<O>(v[i]);
+#pragma unroll
+      for (int i = 0; i < N; i++) v[i] = O < hlanes ? v[i] + w[i] : v[i];
+      mha_head_sum<LPR, N, 2 * O>(v, hlanes);
+   }
+}
+
+// the per-lane parts p[.][chunk] of P dot products per head -> the dot products, in every lane of the head (both chunks where the head
+// is the whole row)
+template <int LPR, int NCH, int P>
+__device__ __forceinline__ void mha_head_reduce(float (&p)[P][NCH], const MhaArgs &a) {
+   if (NCH == 2 && a.whole) {
+      float w[P];
+#pragma unroll
+      for (int i = 0; i < P; i++) w[i] = p[i][0] + p[i][NCH - 1];
+      mha_head_sum<LPR, P>(w, a.hlanes);
+#pragma unroll
+      for (int i = 0; i < P; i++) p[i][0] = p[i][NCH - 1] = w[i];
+   } else {
+      float w[P * NCH];
+#pragma unroll
+      for (int i = 0; i < P; i++)
+#pragma unroll
+         for (int j = 0; j < NCH; j++) w[i * NCH + j] = p[i][j];
+      mha_head_sum<LPR, P * NCH>(w, a.hlanes);
+#pragma unroll
+      for (int i = 0; i < P; i++)
+#pragma unroll
+         for (int j = 0; j < NCH; j++) p[i][j] = w[i * NCH + j];
+   }
+}
+
+// this lane's part of <r, t>_h for one chunk; a 16-byte load may run into the next row, the mask drops what it brought
+__device__ __forceinline__ float mha_dot_part(const float (&r)[4], const v4i_t &t, const bool (&ok)[4]) {
+   float p = 0.0f;
+#pragma unroll
+   for (int v = 0; v < 4; v++) p = fmaf(r[v], ok[v] ? __int_as_float(t[v]) : 0.0f, p);
+   return p;
+}
+
+// byte offset of the gathered row of edge `id` of the batch; a dead edge: -1
+__device__ __forceinline__ unsigned mha_off(int id, unsigned pitch_bytes) {
+   return id < 0 ? BUF_OOB : (unsigned)id * pitch_bytes;     // BUF_OOB + cbyte / hbyte (< 2^24) cannot wrap
+}
+
+template <int LPR, int NCH, int WAVES, int U>
+__global__ __launch_bounds__(WAVES * 64) void mha_fw_kernel(const MhaArgs a) {
+   constexpr int G = 64 / LPR;
+   const int lane = threadIdx.x & 63;
+   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+   const int g = lane / LPR, lc = lane % LPR;
+   const int64_t row = (int64_t)blockIdx.x * WAVES + wave;
+   if (row >= a.rows) return;
+   const int64_t eb = a.pntrb[row], ee = a.pntre[row];
+   const __amdgpu_buffer_rsrc_t rsk = mha_rsrc(a.ga, a.gabytes), rsv = mha_rsrc(a.gb, a.gbbytes);
+   const MhaCols<LPR, NCH> cm(a, lc);
+   float qv[NCH][4];
+   mha_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm, qv);
+
+   float mrun[NCH], l[NCH], acc[NCH][4];
+#pragma unroll
+   for (int j = 0; j < NCH; j++) {
+      mrun[j] = MHA_NONE;
+      l[j] = 0.0f;
+#pragma unroll
+      for (int v = 0; v < 4; v++) acc[j][v] = 0.0f;
+   }
+
+   const unsigned ldkb = (unsigned)a.ldga * 4u, ldvb = (unsigned)a.ldgb * 4u;
+   for (int64_t base = eb; base < ee; base += 64) {
+      const int64_t pos = base + lane;
+      const int id_l = pos < ee ? (int)a.indx[pos] : -1;
+      const int64_t left = ee - base;
+      const int cnt = left < 64 ? (int)left : 64;
+#pragma unroll 1
+      for (int s0 = 0; s0 < cnt; s0 += G * U) {
+         v4i_t kv[U][NCH], vv[U][NCH];
+#pragma unroll
+         for (int u = 0; u < U; u++) {
+            const int id = __shfl(id_l, (s0 + u * G + g) & 63);
+            mha_load_wide<LPR, NCH>(rsk, mha_off(id, ldkb), cm, kv[u]);
+            mha_load_wide<LPR, NCH>(rsv, mha_off(id, ldvb), cm, vv[u]);
+         }
+         float sc[U][NCH];
+#pragma unroll
+         for (int u = 0; u < U; u++)
+#pragma unroll
+            for (int j = 0; j < NCH; j++) sc[u][j] = mha_dot_part(qv[j], kv[u][j], cm.ok[j]);
+         mha_head_reduce<LPR, NCH, U>(sc, a);
+#pragma unroll
+         for (int j = 0; j < NCH; j++) {
+            float mnew = mrun[j];
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+               sc[u][j] *= a.p;
+               mnew = (s0 + u * G + g < cnt) ? fmaxf(mnew, sc[u][j]) : mnew;      // a NaN score is not a maximum; it enters through exp below
+            }
+            const float r = __expf(mrun[j] - mnew);
+            mrun[j] = mnew;
+            l[j] *= r;
+#pragma unroll
+            for (int v = 0; v < 4; v++) acc[j][v] *= r;
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+               const float w = (s0 + u * G + g < cnt) ? __expf(sc[u][j] - mnew) : 0.0f;
+               l[j] += w;
+#pragma unroll
+               for (int v = 0; v < 4; v++) acc[j][v] = fmaf(w, __int_as_float(vv[u][j][v]), acc[j][v]);
+            }
+         }
+      }
+   }
+   // merge the G slots pairwise, by the rule of a step
+#pragma unroll
+   for (int o = LPR; o < 64; o <<= 1) {
+#pragma unroll
+      for (int j = 0; j < NCH; j++) {
+         const float mo = __shfl_xor(mrun[j], o), lo = __shfl_xor(l[j], o);
+         const float mnew = fmaxf(mrun[j], mo);
+         const float ra = __expf(mrun[j] - mnew), rb = __expf(mo - mnew);
+         l[j] = l[j] * ra + lo * rb;
+#pragma unroll
+         for (int v = 0; v < 4; v++) acc[j][v] = acc[j][v] * ra + __shfl_xor(acc[j][v], o) * rb;
+         mrun[j] = mnew;
+      }
+   }
+   if (g != 0) return;
+   const bool empty = ee <= eb;
+#pragma unroll
+   for (int j = 0; j < NCH; j++) {
+#pragma unroll
+      for (int v = 0; v < 4; v++) acc[j][v] = empty ? 0.0f : acc[j][v] / l[j];
+      if (cm.first[j]) a.hout[(size_t)row * (size_t)a.heads + (size_t)cm.head[j]] = empty ? -INFINITY : mrun[j] + logf(l[j]);
+   }
+   mha_store_row<LPR, NCH>(a.out, row, a.ldout, lc, cm, acc);
+}
+
+// one wave per row i: q_i, g_i and D[i,h] in registers; key_j and v_j gathered
+template <int LPR, int NCH, int WAVES, int U>
+__global__ __launch_bounds__(WAVES * 64) void mha_bw_rows_kernel(const MhaArgs a) {
+   constexpr int G = 64 / LPR;
+   const int lane = threadIdx.x & 63;
+   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+   const int g = lane / LPR, lc = lane % LPR;
+   const int64_t row = (int64_t)blockIdx.x * WAVES + wave;
+   if (row >= a.rows) return;
+   const int64_t eb = a.pntrb[row], ee = a.pntre[row];
+   const __amdgpu_buffer_rsrc_t rsk = mha_rsrc(a.ga, a.gabytes), rsv = mha_rsrc(a.gb, a.gbbytes);
+   const MhaCols<LPR, NCH> cm(a, lc);
+   float qv[NCH][4], gv[NCH][4], lse[NCH], dsum[NCH];
+   mha_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm, qv);
+   mha_own_row<LPR, NCH>(a.g, row, a.ldg, lc, cm, gv);
+   mha_own_head<LPR, NCH>(a.lse_in, row, a.heads, cm, lse);
+   {
+      // D[i,h] = <g_i, z_i>_h: every slot holds the row, so every lane of a head ends with it
+      float zv[NCH][4], dp[1][NCH];
+      mha_own_row<LPR, NCH>(a.zin, row, a.ldzin, lc, cm, zv);
+#pragma unroll
+      for (int j = 0; j < NCH; j++) {
+         dp[0][j] = 0.0f;
+#pragma unroll
+         for (int v = 0; v < 4; v++) dp[0][j] = fmaf(gv[j][v], zv[j][v], dp[0][j]);
+      }
+      mha_head_reduce<LPR, NCH, 1>(dp, a);
+#pragma unroll
+      for (int j = 0; j < NCH; j++) dsum[j] = dp[0][j];
+   }
+
+   float acc[NCH][4];
+#pragma unroll
+   for (int j = 0; j < NCH; j++)
+#pragma unroll
+      for (int v = 0; v < 4; v++) acc[j][v] = 0.0f;
+
+   const unsigned ldkb = (unsigned)a.ldga * 4u, ldvb = (unsigned)a.ldgb * 4u;
+   for (int64_t base = eb; base < ee; base += 64) {
+      const int64_t pos = base + lane;
+      const int id_l = pos < ee ? (int)a.indx[pos] : -1;
+      const int64_t left = ee - base;
+      const int cnt = left < 64 ? (int)left : 64;
+#pragma unroll 1
+      for (int s0 = 0; s0 < cnt; s0 += G * U) {
+         v4i_t kv[U][NCH], vv[U][NCH];
+#pragma unroll
+         for (int u = 0; u < U; u++) {
+            const int id = __shfl(id_l, (s0 + u * G + g) & 63);
+            mha_load_wide<LPR, NCH>(rsk, mha_off(id, ldkb), cm, kv[u]);
+            mha_load_wide<LPR, NCH>(rsv, mha_off(id, ldvb), cm, vv[u]);
+         }
+         float part[2 * U][NCH];                       // <q_i, key_j>_h and t_e of the step through one butterfly
+#pragma unroll
+         for (int u = 0; u < U; u++)
+#pragma unroll
+            for (int j = 0; j < NCH; j++) {
+               part[u][j] = mha_dot_part(qv[j], kv[u][j], cm.ok[j]);
+               part[U + u][j] = mha_dot_part(gv[j], vv[u][j], cm.ok[j]);
+            }
+         mha_head_reduce<LPR, NCH, 2 * U>(part, a);
+#pragma unroll
+         for (int u = 0; u < U; u++) {
+            const bool live = s0 + u * G + g < cnt;
+#pragma unroll
+            for (int j = 0; j < NCH; j++) {
+               const float ds = live ? __expf(part[u][j] * a.p - lse[j]) * (part[U + u][j] - dsum[j]) : 0.0f;
+#pragma unroll
+               for (int v = 0; v < 4; v++) acc[j][v] = fmaf(ds, __int_as_float(kv[u][j][v]), acc[j][v]);
+            }
+         }
+      }
+   }
+#pragma unroll
+   for (int o = LPR; o < 64; o <<= 1)
+#pragma unroll
+      for (int j = 0; j < NCH; j++)
+#pragma unroll
+         for (int v = 0; v < 4; v++) acc[j][v] += __shfl_xor(acc[j][v], o);
+   if (g != 0) return;
+   const bool empty = ee <= eb;
+#pragma unroll
+   for (int j = 0; j < NCH; j++) {
+#pragma unroll
+      for (int v = 0; v < 4; v++) acc[j][v] = empty ? 0.0f : a.p * acc[j][v];
+      if (cm.first[j]) a.hout[(size_t)row * (size_t)a.heads + (size_t)cm.head[j]] = empty ? 0.0f : dsum[j];
+   }
+   mha_store_row<LPR, NCH>(a.out, row, a.ldout, lc, cm, acc);
+}
+
+// one wave per column j of A (a row of the transposed structure): key_j and v_j in registers; q_i, g_i and lse, D of [i, head] gathered
+template <int LPR, int NCH, int WAVES, int U>
+__global__ __launch_bounds__(WAVES * 64) void mha_bw_cols_kernel(const MhaArgs a) {
+   constexpr int G = 64 / LPR;
+   const int lane = threadIdx.x & 63;
+   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+   const int g = lane / LPR, lc = lane % LPR;
+   const int64_t row = (int64_t)blockIdx.x * WAVES + wave;
+   if (row >= a.rows) return;
+   const int64_t eb = a.pntrb[row], ee = a.pntre[row];
+   const __amdgpu_buffer_rsrc_t rsq = mha_rsrc(a.ga, a.gabytes), rsg = mha_rsrc(a.gb, a.gbbytes);
+   const __amdgpu_buffer_rsrc_t rs1 = mha_rsrc(a.t1, a.tbytes), rs2 = mha_rsrc(a.t2, a.tbytes);
+   const MhaCols<LPR, NCH> cm(a, lc);
+   float kv[NCH][4], vv[NCH][4];
+   mha_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm, kv);
+   mha_own_row<LPR, NCH>(a.own2, row, a.ldown2, lc, cm, vv);
+
+   float dk[NCH][4], dv[NCH][4];
+#pragma unroll
+   for (int j = 0; j < NCH; j++)
+#pragma unroll
+      for (int v = 0; v < 4; v++) dk[j][v] = dv[j][v] = 0.0f;
+
+   const unsigned ldqb = (unsigned)a.ldga * 4u, ldgb = (unsigned)a.ldgb * 4u, hb = (unsigned)a.heads * 4u;
+   for (int64_t base = eb; base < ee; base += 64) {
+      const int64_t pos = base + lane;
+      const int id_l = pos < ee ? (int)a.indx[pos] : -1;
+      const int64_t left = ee - base;
+      const int cnt = left < 64 ? (int)left : 64;
+#pragma unroll 1
+      for (int s0 = 0; s0 < cnt; s0 += G * U) {
+         v4i_t qg[U][NCH], gg[U][NCH];
+         float ls[U][NCH], dd[U][NCH];
+#pragma unroll
+         for (int u = 0; u < U; u++) {
+            const int id = __shfl(id_l, (s0 + u * G + g) & 63);
+            mha_load_wide<LPR, NCH>(rsq, mha_off(id, ldqb), cm, qg[u]);
+            mha_load_wide<LPR, NCH>(rsg, mha_off(id, ldgb), cm, gg[u]);
+            mha_load_head<LPR, NCH>(rs1, mha_off(id, hb), cm, ls[u]);
+            mha_load_head<LPR, NCH>(rs2, mha_off(id, hb), cm, dd[u]);
+         }
+         float part[2 * U][NCH];
+#pragma unroll
+         for (int u = 0; u < U; u++)
+#pragma unroll
+            for (int j = 0; j < NCH; j++) {
+               part[u][j] = mha_dot_part(kv[j], qg[u][j], cm.ok[j]);
+               part[U + u][j] = mha_dot_part(vv[j], gg[u][j], cm.ok[j]);
+            }
+         mha_head_reduce<LPR, NCH, 2 * U>(part, a);
+#pragma unroll
+         for (int u = 0; u < U; u++) {
+            const bool live = s0 + u * G + g < cnt;
+#pragma unroll
+            for (int j = 0; j < NCH; j++) {
+               const float ae = live ? __expf(part[u][j] * a.p - ls[u][j]) : 0.0f;
+               const float ds = live ? ae * (part[U + u][j] - dd[u][j]) : 0.0f;
+#pragma unroll
+               for (int v = 0; v < 4; v++) {
+                  dk[j][v] = fmaf(ds, __int_as_float(qg[u][j][v]), dk[j][v]);
+                  dv[j][v] = fmaf(ae, __int_as_float(gg[u][j][v]), dv[j][v]);
+               }
+            }
+         }
+      }
+   }
+#pragma unroll
+   for (int o = LPR; o < 64; o <<= 1)
+#pragma unroll
+      for (int j = 0; j < NCH; j++)
+#pragma unroll
+         for (int v = 0; v < 4; v++) {
+            dk[j][v] += __shfl_xor(dk[j][v], o);
+            dv[j][v] += __shfl_xor(dv[j][v], o);
+         }
+   if (g != 0) return;
+#pragma unroll
+   for (int j = 0; j < NCH; j++)
+#pragma unroll
+      for (int v = 0; v < 4; v++) dk[j][v] *= a.p;    // no incoming entry: 0
+   mha_store_row<LPR, NCH>(a.out, row, a.ldout, lc, cm, dk);
+   mha_store_row<LPR, NCH>(a.out2, row, a.ldout2, lc, cm, dv);
+}
+
+enum { MHA_FW = 0, MHA_BW_ROWS = 1, MHA_BW_COLS = 2 };
+
+// edges of a slot per step: 4 in the forward and the rows kernel; the columns kernel gathers four tables per edge and takes half the
+// edges per step where a lane holds two chunks (profiles/mha_isa.txt: no instantiation uses scratch)
+template <int LPR, int NCH>
+static int launch_mha(int which, const MhaArgs &a, const char *entry, hipStream_t st) {
+   constexpr int UC = NCH >= 2 ? 2 : 4;
+   const int64_t nb = (a.rows + MHA_WAVES - 1) / MHA_WAVES;
+   if (nb > 0x7fffffffLL) return fail(ISPLIB_FAIL, entry, "too many rows for one launch");
+   const dim3 grid((unsigned)nb), block((unsigned)MHA_WAVES * 64u);
+   if (which == MHA_FW) hipLaunchKernelGGL((mha_fw_kernel<LPR, NCH, MHA_WAVES, 4>), grid, block, 0, st, a);
+   else if (which == MHA_BW_ROWS) hipLaunchKernelGGL((mha_bw_rows_kernel<LPR, NCH, MHA_WAVES, 4>), grid, block, 0, st, a);
+   else hipLaunchKernelGGL((mha_bw_cols_kernel<LPR, NCH, MHA_WAVES, UC>), grid, block, 0, st, a);
+   return check_launch(entry);
+}
+
+// the width dispatch of gatv2.hip, up to two chunks per lane
+static int mha_by_width(int which, const MhaArgs &a, const char *entry, hipStream_t st) {
+   const int64_t w = (a.k + 3) / 4;
+   if (w <= 8) return launch_mha<8, 1>(which, a, entry, st);
+   if (w <= 16) return launch_mha<16, 1>(which, a, entry, st);
+   if (w <= 32) return launch_mha<32, 1>(which, a, entry, st);
+   if (w <= 64) return launch_mha<64, 1>(which, a, entry, st);
+   return launch_mha<64, 2>(which, a, entry, st);
+}
+
+// what a descriptor over `rows` rows of k floats at pitch ld may answer: the extent a row-strided view owns, not rows * ld
+static unsigned mha_extent(int64_t rows, int64_t k, int64_t ld) {
+   return rows <= 0 ? 0u : (unsigned)(((unsigned long long)(rows - 1) * (unsigned long long)ld + (unsigned long long)k) * 4ull);
+}
+
+// the head geometry of a launch; the domain (isplib_mha_serves) has been checked: H == 1, or d a power of two >= 4
+static void mha_heads(MhaArgs &a, int64_t heads, int64_t d) {
+   a.heads = (int)heads;
+   if (heads == 1) {
+      a.hshift = 31; a.hlanes = 64; a.hmask = 0x7fffffffu; a.whole = 1;
+   } else {
+      int sh = 0;
+      while ((1LL << sh) < d) sh++;
+      a.hshift = sh; a.hlanes = (int)(d / 4); a.hmask = (unsigned)(d - 1); a.whole = 0;
+   }
+}
+
+static const char *const MHA_DOMAIN = "outside isplib_mha_serves(rows_gathered, heads, d, ld) = isplib_gat_serves: 1 <= heads, 1 <= d, "
+                                      "heads*d <= 512, heads == 1 or d a power of two >= 4, ld >= heads*d, rows_gathered < 2^31, "
+                                      "rows_gathered*ld*4 <= 3.5 GiB";
+
+}  // namespace isplib
+
+using namespace isplib;
+
+extern "C" int isplib_mha_domain(int64_t rows_gathered, int64_t heads, int64_t d, int64_t ld) {
+   return isplib_mha_serves(rows_gathered, heads, d, ld);
+}
+
+extern "C" int isplib_mha_csr_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                                  const int64_t *pntre, int64_t heads, float scale, const float *q, int64_t ldq, const float *key,
+                                  int64_t ldk, const float *v, int64_t ldv, float *z, int64_t ldz, float *lse, void *stream) {
+   const char *entry = "isplib_mha_csr_hip";
+   clear_error();
+   if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
+   if (!std::isfinite(scale)) return fail(ISPLIB_FAIL, entry, "scale must be a finite number");
+   if (m == 0 || k == 0) return ISPLIB_SUCCESS;
+   if (!pntrb || !pntre || !q || !z || !lse || (nnz > 0 && (!indx || !key || !v))) return fail(ISPLIB_FAIL, entry, "null operand");
+   if (ldq < k || ldz < k) return fail(ISPLIB_FAIL, entry, "leading dimension smaller than k");
+   if (heads >= 1 && k % heads != 0) return fail(ISPLIB_FAIL, entry, "k is not a multiple of heads");
+   if (heads < 1 || !isplib_mha_serves(n, heads, k / heads, ldk) || !isplib_mha_serves(n, heads, k / heads, ldv))
+      return fail(ISPLIB_NO_OPT_IMPL, entry, MHA_DOMAIN);
+   MhaArgs a = {};
+   a.rows = m; a.k = k; a.indx = indx; a.pntrb = pntrb; a.pntre = pntre; a.p = scale;
+   mha_heads(a, heads, k / heads);
+   a.own = q; a.ldown = ldq;
+   a.out = z; a.ldout = ldz; a.hout = lse;
+   a.ga = key; a.ldga = ldk; a.gabytes = nnz > 0 ? mha_extent(n, k, ldk) : 0u;
+   a.gb = v; a.ldgb = ldv; a.gbbytes = nnz > 0 ? mha_extent(n, k, ldv) : 0u;
+   return mha_by_width(MHA_FW, a, entry, (hipStream_t)stream);
+}
+
+extern "C" int isplib_mha_bw_rows_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                                      const int64_t *pntre, int64_t heads, float scale, const float *q, int64_t ldq, const float *key,
+                                      int64_t ldk, const float *v, int64_t ldv, const float *g, int64_t ldg, const float *z,
+                                      int64_t ldz, const float *lse, float *dq, int64_t lddq, float *dsum, void *stream) {
+   const char *entry = "isplib_mha_bw_rows_hip";
+   clear_error();
+   if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
+   if (!std::isfinite(scale)) return fail(ISPLIB_FAIL, entry, "scale must be a finite number");
+   if (m == 0 || k == 0) return ISPLIB_SUCCESS;
+   if (!pntrb || !pntre || !q || !g || !z || !lse || !dq || !dsum || (nnz > 0 && (!indx || !key || !v)))
+      return fail(ISPLIB_FAIL, entry, "null operand");
+   if (ldq < k || ldg < k || ldz < k || lddq < k) return fail(ISPLIB_FAIL, entry, "leading dimension smaller than k");
+   if (heads >= 1 && k % heads != 0) return fail(ISPLIB_FAIL, entry, "k is not a multiple of heads");
+   if (heads < 1 || !isplib_mha_serves(n, heads, k / heads, ldk) || !isplib_mha_serves(n, heads, k / heads, ldv))
+      return fail(ISPLIB_NO_OPT_IMPL, entry, MHA_DOMAIN);
+   MhaArgs a = {};
+   a.rows = m; a.k = k; a.indx = indx; a.pntrb = pntrb; a.pntre = pntre; a.p = scale;
+   mha_heads(a, heads, k / heads);
+   a.own = q; a.ldown = ldq; a.g = g; a.ldg = ldg; a.zin = z; a.ldzin = ldz; a.lse_in = lse;
+   a.out = dq; a.ldout = lddq; a.hout = dsum;
+   a.ga = key; a.ldga = ldk; a.gabytes = nnz > 0 ? mha_extent(n, k, ldk) : 0u;
+   a.gb = v; a.ldgb = ldv; a.gbbytes = nnz > 0 ? mha_extent(n, k, ldv) : 0u;
+   return mha_by_width(MHA_BW_ROWS, a, entry, (hipStream_t)stream);
+}
+
+extern "C" int isplib_mha_bw_cols_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t, const int64_t *colb,
+                                      const int64_t *cole, int64_t heads, float scale, const float *q, int64_t ldq, const float *g,
+                                      int64_t ldg, const float *lse, const float *dsum, const float *key, int64_t ldk, const float *v,
+                                      int64_t ldv, float *dkey, int64_t lddk, float *dv, int64_t lddv, void *stream) {
+   const char *entry = "isplib_mha_bw_cols_hip";
+   clear_error();
+   if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
+   if (!std::isfinite(scale)) return fail(ISPLIB_FAIL, entry, "scale must be a finite number");
+   if (n == 0 || k == 0) return ISPLIB_SUCCESS;
+   if (!colb || !cole || !key || !v || !dkey || !dv || (nnz > 0 && (!row_t || !q || !g || !lse || !dsum)))
+      return fail(ISPLIB_FAIL, entry, "null operand");
+   if (ldk < k || ldv < k || lddk < k || lddv < k) return fail(ISPLIB_FAIL, entry, "leading dimension smaller than k");
+   if (heads >= 1 && k % heads != 0) return fail(ISPLIB_FAIL, entry, "k is not a multiple of heads");
+   if (heads < 1 || !isplib_mha_serves(m, heads, k / heads, ldq) || !isplib_mha_serves(m, heads, k / heads, ldg))
+      return fail(ISPLIB_NO_OPT_IMPL, entry, MHA_DOMAIN);
+   MhaArgs a = {};
+   a.rows = n; a.k = k; a.indx = row_t; a.pntrb = colb; a.pntre = cole; a.p = scale;
+   mha_heads(a, heads, k / heads);
+   a.own = key; a.ldown = ldk; a.own2 = v; a.ldown2 = ldv;
+   a.out = dkey; a.ldout = lddk; a.out2 = dv; a.ldout2 = lddv;
+   a.ga = q; a.ldga = ldq; a.gabytes = nnz > 0 ? mha_extent(m, k, ldq) : 0u;
+   a.gb = g; a.ldgb = ldg; a.gbbytes = nnz > 0 ? mha_extent(m, k, ldg) : 0u;
+   a.t1 = lse; a.t2 = dsum; a.tbytes = nnz > 0 ? mha_extent(m, heads, heads) : 0u;
+   return mha_by_width(MHA_BW_COLS, a, entry, (hipStream_t)stream);
+}

@@ -1973,6 +1973,108 @@ Tensor gatv2_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor
    return Gatv2Spmm::apply(rowptr, col, colptr, row_t, x, y, att, heads, negative_slope)[0];
 }
 
+// ---- sparse multi-head dot-product attention with separate keys and values (isplib_mha_*_hip; not an operator of the
+// reference) ----------
+// z_i[head h] = sum_e softmax_e(scale <q_i, k_j>_h) v_j[head h].  Saved for backward: the structure, q, k, v, z and lse [M, H] -- nothing of
+// length nnz.  Operands with unit column stride and a row pitch >= K go in as they lie (column views of one fused [rows, 3K] projection
+// are not copied); anything else is made contiguous.  Every shape is checked before a launch.
+static AttnOperand mha_operand(const Tensor &src, const char *name, int64_t rows, int64_t k) {
+   check_float(src, name);
+   TORCH_CHECK(src.dim() == 2 && src.size(0) == rows && src.size(1) == k, "isplib: mha_spmm: `", name, "` must be [", rows, ", ", k,
+               "], got ", src.sizes());
+   const bool as_is = src.size(0) == 0 || src.size(1) == 0 || (src.stride(1) == 1 && (src.size(0) == 1 || src.stride(0) >= k));
+   const Tensor t = as_is ? src : src.contiguous();
+   return {t, t.size(0) > 1 ? t.stride(0) : std::max<int64_t>(k, 1)};
+}
+
+class MhaSpmm : public torch::autograd::Function<MhaSpmm> {
+ public:
+   static variable_list forward(AutogradContext *ctx, Variable rowptr, Variable col, Variable colptr, Variable row_t, Variable q, Variable k,
+                                Variable v, int64_t heads, double scale) {
+      check_index(rowptr, "rowptr"); check_index(col, "col"); check_index(colptr, "colptr"); check_index(row_t, "row_t");
+      TORCH_CHECK(q.defined() && q.dim() == 2 && k.defined() && k.dim() == 2 && v.defined() && v.dim() == 2,
+                  "isplib: mha_spmm needs 2-D `q` [M, heads * d], `k` and `v` [N, heads * d]");
+      OpTimer timer("FUSEDMM_MHA_FW", q);
+      const int64_t M = rowptr.numel() - 1, N = colptr.numel() - 1, K = q.size(1), nnz = col.numel();
+      TORCH_CHECK(M >= 0 && N >= 0 && row_t.numel() == nnz, "isplib: mha_spmm: `rowptr` / `colptr` need one entry more than rows / columns, "
+                                                             "`row_t` one entry per stored entry");
+      TORCH_CHECK(heads >= 1 && K % heads == 0, "isplib: mha_spmm: the width of `q` (", K, ") must be heads * d, got heads = ", heads);
+      TORCH_CHECK(std::isfinite(scale), "isplib: mha_spmm: `scale` must be a finite number, got ", scale);
+      const AttnOperand qo = mha_operand(q, "q", M, K), ko = mha_operand(k, "k", N, K), vo = mha_operand(v, "v", N, K);
+      for (const Tensor *t : {&rowptr, &col, &colptr, &row_t, &k, &v})
+         TORCH_CHECK(t->device() == q.device(), "isplib: mha_spmm: every operand must be on q's device");
+      TORCH_CHECK(K == 0 || (isplib_mha_serves(N, heads, K / heads, ko.ld) && isplib_mha_serves(N, heads, K / heads, vo.ld)),
+                  "isplib: mha_spmm: outside isplib_mha_serves (heads * d <= ", ISPLIB_GAT_K_MAX,
+                  ", heads == 1 or d a power of two >= 4, N < 2^31, N * pitch * 4 <= 3.5 GiB): N = ", N, ", heads = ", heads, ", d = ",
+                  K / heads, ", pitches = ", ko.ld, ", ", vo.ld);
+      c10::DeviceGuard guard(q.device());
+      const Tensor rp = rowptr.contiguous(), cl = col.contiguous();
+      Tensor z = at::empty({M, K}, q.options()), lse = at::empty({M, heads}, q.options());
+      if (M > 0 && K > 0) {
+         const int st = isplib_mha_csr_hip(M, N, K, nnz, cl.data_ptr<int64_t>(), rp.data_ptr<int64_t>(), rp.data_ptr<int64_t>() + 1, heads,
+                                           (float)scale, qo.t.data_ptr<float>(), qo.ld, nnz > 0 ? ko.t.data_ptr<float>() : nullptr, ko.ld,
+                                           nnz > 0 ? vo.t.data_ptr<float>() : nullptr, vo.ld, z.data_ptr<float>(), K, lse.data_ptr<float>(),
+                                           current_stream(q));
+         check_status(st, "isplib_mha_csr_hip");
+      } else if (M > 0) {
+         lse.fill_(-std::numeric_limits<float>::infinity());
+      }
+      ctx->saved_data["heads"] = heads;
+      ctx->saved_data["scale"] = scale;
+      ctx->save_for_backward({rp, cl, colptr, row_t, q, k, v, z, lse});
+      return {z};
+   }
+
+   static variable_list backward(AutogradContext *ctx, variable_list grad_outs) {
+      OpTimer timer("FUSEDMM_MHA_BW", grad_outs[0]);
+      const bool need_q = ctx->needs_input_grad(4), need_k = ctx->needs_input_grad(5), need_v = ctx->needs_input_grad(6);
+      auto grad_q = Variable(), grad_k = Variable(), grad_v = Variable();
+      if (need_q || need_k || need_v) {
+         auto saved = ctx->get_saved_variables();
+         auto rp = saved[0], cl = saved[1], colptr = saved[2].contiguous(), row_t = saved[3].contiguous(), q = saved[4], k = saved[5], v = saved[6],
+              z = saved[7], lse = saved[8];
+         const int64_t heads = ctx->saved_data["heads"].toInt();
+         const float p = (float)ctx->saved_data["scale"].toDouble();
+         const int64_t M = rp.numel() - 1, N = colptr.numel() - 1, K = q.size(1), nnz = cl.numel();
+         const AttnOperand qo = mha_operand(q, "q", M, K), ko = mha_operand(k, "k", N, K), vo = mha_operand(v, "v", N, K);
+         const AttnOperand go = mha_operand(grad_outs[0].to(at::kFloat), "grad_out", M, K);
+         c10::DeviceGuard guard(q.device());
+         // the rows kernel always runs: its D[i,h] = <g_i, z_i>_h feeds the columns kernel; the columns kernel only when k or v asks
+         Tensor dq = at::empty({M, K}, q.options()), dsum = at::empty({M, heads}, q.options());
+         if (M > 0 && K > 0) {
+            const int st = isplib_mha_bw_rows_hip(M, N, K, nnz, cl.data_ptr<int64_t>(), rp.data_ptr<int64_t>(), rp.data_ptr<int64_t>() + 1, heads,
+                                                  p, qo.t.data_ptr<float>(), qo.ld, nnz > 0 ? ko.t.data_ptr<float>() : nullptr, ko.ld,
+                                                  nnz > 0 ? vo.t.data_ptr<float>() : nullptr, vo.ld, go.t.data_ptr<float>(), go.ld,
+                                                  z.data_ptr<float>(), K, lse.data_ptr<float>(), dq.data_ptr<float>(), K,
+                                                  dsum.data_ptr<float>(), current_stream(q));
+            check_status(st, "isplib_mha_bw_rows_hip");
+         }
+         if (need_q) grad_q = dq;
+         if (need_k || need_v) {
+            TORCH_CHECK(K == 0 || (isplib_mha_serves(M, heads, K / heads, qo.ld) && isplib_mha_serves(M, heads, K / heads, go.ld)),
+                        "isplib: mha_spmm backward: outside isplib_mha_serves for the gathered rows of q and of the gradient: M = ", M,
+                        ", K = ", K);
+            Tensor dk = at::empty({N, K}, q.options()), dv = at::empty({N, K}, q.options());
+            if (N > 0 && K > 0) {
+               const int st = isplib_mha_bw_cols_hip(M, N, K, nnz, row_t.data_ptr<int64_t>(), colptr.data_ptr<int64_t>(),
+                                                     colptr.data_ptr<int64_t>() + 1, heads, p, nnz > 0 ? qo.t.data_ptr<float>() : nullptr, qo.ld,
+                                                     nnz > 0 ? go.t.data_ptr<float>() : nullptr, go.ld, lse.data_ptr<float>(),
+                                                     dsum.data_ptr<float>(), ko.t.data_ptr<float>(), ko.ld, vo.t.data_ptr<float>(), vo.ld,
+                                                     dk.data_ptr<float>(), K, dv.data_ptr<float>(), K, current_stream(q));
+               check_status(st, "isplib_mha_bw_cols_hip");
+            }
+            if (need_k) grad_k = dk;
+            if (need_v) grad_v = dv;
+         }
+      }
+      return {Variable(), Variable(), Variable(), Variable(), grad_q, grad_k, grad_v, Variable(), Variable()};
+   }
+};
+
+Tensor mha_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor q, Tensor k, Tensor v, int64_t heads, double scale) {
+   return MhaSpmm::apply(rowptr, col, colptr, row_t, q, k, v, heads, scale)[0];
+}
+
 // ---- the GATv2 aggregation with attention dropout (isplib_gatv2_drop_*_hip) ----------
 // The coefficients are dropped after the softmax, per stored entry and head; the keep bit is the pure function of (seed, CSR position,
 // head) of gat_drop_spmm, so the backward regenerates the mask from the seed.  Saved for backward: what Gatv2Spmm saves, plus the two
@@ -2279,4 +2381,5 @@ TORCH_LIBRARY(isplib, m) {
          &gatv2_drop_spmm);
    m.def("gatv2_spmm16(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor x, Tensor y, Tensor att, int heads, float negative_slope) -> Tensor",
          &gatv2_spmm16);
+   m.def("mha_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor q, Tensor k, Tensor v, int heads, float scale) -> Tensor", &mha_spmm);
 }

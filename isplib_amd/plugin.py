@@ -35,6 +35,7 @@ ISPLIB_TUNE_FILE names a tuning table to load at import; ISPLIB_DEBUG=1 prints p
 from __future__ import annotations
 
 import json
+import math
 import os
 import weakref
 from typing import Optional
@@ -1098,6 +1099,64 @@ def gatv2_matmul(src, x: torch.Tensor, att: torch.Tensor, y: Optional[torch.Tens
         return torch.ops.isplib.gatv2_drop_spmm(st._rowptr, st._col, st.colptr(), st.row_t(), st.csr2csc(), x, y, att, heads,
                                                 float(negative_slope), *drop)
     return torch.ops.isplib.gatv2_spmm(st._rowptr, st._col, st.colptr(), st.row_t(), x, y, att, heads, float(negative_slope))
+
+
+def mha_matmul(src, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int = 1, scale: Optional[float] = None) -> torch.Tensor:
+    """Sparse multi-head dot-product attention with separate keys and values over the stored entries of `src`, all heads in one launch
+    (include/isplib_hip_mha.h, isplib_mha_csr_hip): ``z[i, head h] = sum_j softmax_j(scale * <q[i], k[j]>_h) v[j, head h]`` over the
+    entries (i, j) of row i -- the aggregation of TransformerConv and of the local attention of sparse graph transformers, with its
+    autograd backward in `q`, `k` and `v` (torch.ops.isplib.mha_spmm).  `q` [M, heads * d] is the target side, `k` and `v`
+    [N, heads * d] the source side, head h in the columns [h*d, (h+1)*d); ``scale=None`` means ``1 / sqrt(d)`` -- the HEAD width.  The
+    three may be column views of one fused ``[rows, 3 * K]`` projection: operands with unit column stride go in at their own pitch,
+    without a copy.  ``k is v`` is allowed; the one tensor's gradient receives both parts.  The stored values of `src` are not read;
+    every stored entry is its own edge; an empty row gives 0.  The backward keeps q, k, v, z and one scalar per row and head -- nothing
+    per edge.  fp32 only (bf16 / fp16 operands raise TypeError) and there is no fallback route: outside isplib_mha_serves
+    (= isplib_gat_serves: heads * d <= 512; heads == 1 or d a power of two >= 4) the call raises ValueError.  Not part of the operator:
+    attention dropout, TransformerConv's edge features, its root weight and its beta gate (dense operations outside the aggregation)."""
+    from . import cabi
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"isplib_amd: `{name}` must be a tensor, got {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"isplib_amd: `{name}` must be float32, got {t.dtype} (the multi-head attention operator is fp32 only)")
+    if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
+        raise ValueError(f"isplib_amd: `heads` must be a positive int, got {heads!r}")
+    if q.dim() != 2 or k.dim() != 2 or v.dim() != 2:
+        raise ValueError(f"isplib_amd: `q`, `k` and `v` must be 2-D [rows, heads * d], got shapes {tuple(q.shape)}, {tuple(k.shape)} and "
+                         f"{tuple(v.shape)}")
+    st = _storage_of(src, k)
+    m_rows, n_cols = st._rowptr.numel() - 1, st._sparse_sizes[1]
+    if q.size(0) != m_rows:
+        raise ValueError(f"isplib_amd: `q` must have one row per row of the sparse matrix ({m_rows}), got {q.size(0)}")
+    for name, t in (("k", k), ("v", v)):
+        if t.size(0) != n_cols:
+            raise ValueError(f"isplib_amd: `{name}` must have one row per column of the sparse matrix ({n_cols}), got {t.size(0)}")
+    kk = q.size(1)
+    if k.size(1) != kk or v.size(1) != kk:
+        raise ValueError(f"isplib_amd: `q`, `k` and `v` must have the same width, got {kk}, {k.size(1)} and {v.size(1)}")
+    if kk % heads:
+        raise ValueError(f"isplib_amd: the width of `q` ({kk}) must be heads * d, got heads = {heads}")
+    d = kk // heads
+    if not (1 <= kk <= cabi.GAT_K_MAX) or (heads > 1 and (d < 4 or d & (d - 1))):
+        raise ValueError(f"isplib_amd: mha_matmul serves 1 <= heads * d <= {cabi.GAT_K_MAX} with heads == 1 or d a power of two >= 4 (a "
+                         f"head is an aligned group of lanes), got heads = {heads}, d = {d}")
+    if scale is not None and (isinstance(scale, bool) or not isinstance(scale, (int, float)) or not math.isfinite(scale)):
+        raise ValueError(f"isplib_amd: `scale` must be a finite Python number or None (1 / sqrt(d)), got {scale!r}")
+
+    def pitch(t, rows):
+        return t.stride(0) if rows > 1 and t.stride(1) == 1 and t.stride(0) >= kk else kk
+
+    for rows, ld, what in ((n_cols, pitch(k, n_cols), "`k`"), (n_cols, pitch(v, n_cols), "`v`"), (m_rows, pitch(q, m_rows), "`q`"),
+                           (m_rows, kk, "the gradient of the result")):
+        if not cabi.mha_serves(rows, heads, d, ld):                # k, v: forward, rows; q and g: the columns kernel
+            raise ValueError(f"isplib_amd: {what} ({rows} rows at a pitch of {ld} floats) is outside the multi-head attention kernels' "
+                             f"domain: rows < 2^31 and rows * pitch * 4 <= {cabi.DENSE_BYTES_MAX} bytes (3.5 GiB, one buffer descriptor)")
+    if not q.is_cuda or not k.is_cuda or not v.is_cuda:
+        raise TypeError("isplib_amd: `q`, `k` and `v` must be GPU tensors -- there is no CPU path")
+    if k.device != q.device or v.device != q.device or st._rowptr.device != q.device:
+        raise ValueError("isplib_amd: `q`, `k`, `v` and the sparse matrix must be on one device")
+    p = float(scale) if scale is not None else 1.0 / math.sqrt(d)
+    return torch.ops.isplib.mha_spmm(st._rowptr, st._col, st.colptr(), st.row_t(), q, k, v, heads, p)
 
 
 def _gatv2_matmul16(src, x, att, y, heads, negative_slope):
