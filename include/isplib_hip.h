@@ -1406,4 +1406,7 @@ void isplib_graph_destroy(isplib_graph *g);
  * its own */
 #include "isplib_hip_mha.h"
 
+/* the same attention for bf16 / fp16 operands (isplib_qkv16_*): part of this interface, declared in a file of its own */
+#include "isplib_hip_mha16.h"
+
 #endif /* ISPLIB_HIP_H */

@@ -215,6 +215,21 @@ def gatv2_16_native_pays(rows_gathered: int, ld: int) -> bool:
     return bool(rows_gathered > 0 and ld > 0)
 
 
+def mha16_serves(rows_gathered: int, heads: int, d: int, ld: int) -> bool:
+    """isplib_qkv16_serves of include/isplib_hip_mha16.h: the 16-bit multi-head attention entries' domain IS isplib_gat16_serves --
+    stated once.  It is asked of every gathered wide operand at its own row count and pitch: key and v (forward, rows kernel), q and
+    the gradient (columns kernel)."""
+    return gat16_serves(rows_gathered, heads, d, ld)
+
+
+def mha16_native_pays(rows_gathered: int, ld: int) -> bool:
+    """isplib_qkv16_native_pays of the header: the classes of calls (the gathered operand beyond 256 MiB at 2 bytes per element or
+    not) in which every native run of the 16-bit multi-head attention operator (forward + backward) measured faster than every run of
+    the conversion route (profiles/mha16_ab.txt: both classes do -- the Reddit shape at (H, d) = (8, 8) / (8, 16) inside 256 MiB, 0.541-0.565 of the
+    conversion route's time; the ogbn-products shape at (8, 16) beyond it, 0.518); tests/test_mha16_host.py compares the two."""
+    return bool(rows_gathered > 0 and ld > 0)
+
+
 def owner_exchange_serves(m: int, k: int, world: int, cuts) -> bool:
     """isplib_owner_exchange_serves of the header: m x k winners split for `world` owners at the row boundaries `cuts`."""
     if not 1 <= world <= OWNER_WORLD_MAX or m < 0 or k < 0 or m * k >= MINMAX_BW_PAIRS_END:
@@ -289,6 +304,11 @@ GATV2_DROP_EXPORTS = ("isplib_gatv2_drop_csr_hip", "isplib_gatv2_drop_bw_rows_hi
 # include/isplib_hip_mha.h (which isplib_hip.h includes; the same library): multi-head dot-product attention with separate keys and
 # values, listed apart for the same reason; tests/test_mha_host.py compares this list with that header and the library's symbols
 MHA_EXPORTS = ("isplib_mha_csr_hip", "isplib_mha_bw_rows_hip", "isplib_mha_bw_cols_hip", "isplib_mha_domain")
+
+# include/isplib_hip_mha16.h (which isplib_hip.h includes; the same library): the 16-bit multi-head attention entries.  Their prefix is
+# isplib_qkv16_ because the symbols that start with isplib_mha are pinned to MHA_EXPORTS; tests/test_mha16_host.py compares this list
+# with that header and the library's symbols
+MHA16_EXPORTS = ("isplib_qkv16_csr_hip", "isplib_qkv16_bw_rows_hip", "isplib_qkv16_bw_cols_hip", "isplib_qkv16_domain", "isplib_qkv16_auto")
 
 # the two host functions of the dropout keep bit (isplib_hip.h declares them; they return uint32_t, not a status, and are listed apart)
 GAT_DROP_HOST_EXPORTS = ("isplib_gat_drop_threshold", "isplib_gat_drop_word")
@@ -613,6 +633,18 @@ def lib() -> ctypes.CDLL:
         L.isplib_mha_bw_cols_hip.restype = ctypes.c_int
         L.isplib_mha_bw_cols_hip.argtypes = [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _f32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64,
                                              _vp, _i64, _vp, _i64, _vp]
+        # the isplib_mha_* argument lists behind a dtype; the rows entry takes no z
+        L.isplib_qkv16_domain.restype = ctypes.c_int
+        L.isplib_qkv16_domain.argtypes = [_i64, _i64, _i64, _i64]
+        L.isplib_qkv16_auto.restype = ctypes.c_int
+        L.isplib_qkv16_auto.argtypes = [_i64, _i64]
+        L.isplib_qkv16_csr_hip.restype = ctypes.c_int
+        L.isplib_qkv16_csr_hip.argtypes = [ctypes.c_int] + L.isplib_mha_csr_hip.argtypes
+        L.isplib_qkv16_bw_rows_hip.restype = ctypes.c_int
+        L.isplib_qkv16_bw_rows_hip.argtypes = [ctypes.c_int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _f32, _vp, _i64, _vp, _i64, _vp, _i64,
+                                               _vp, _i64, _vp, _vp, _i64, _vp, _vp]
+        L.isplib_qkv16_bw_cols_hip.restype = ctypes.c_int
+        L.isplib_qkv16_bw_cols_hip.argtypes = [ctypes.c_int] + L.isplib_mha_bw_cols_hip.argtypes
         L.isplib_gatv2_16_domain.restype = ctypes.c_int
         L.isplib_gatv2_16_domain.argtypes = [_i64, _i64, _i64, _i64]
         L.isplib_gatv2_16_auto.restype = ctypes.c_int
@@ -3261,6 +3293,146 @@ def gatv2_16_backward_cols(colptr, row_t, x, y, att, g, lse, dsum, heads: int = 
                                                _ptr(g), ldg, _ptr(lse), _ptr(dsum), _ptr(out), lddy, _stream(y.device))
     _check(st, "isplib_gatv2_16_bw_cols_hip")
     return out
+
+
+def _mha16_domain(rows_gathered: int, heads: int, d: int, lds) -> None:
+    for ld in lds:
+        if d > 0 and not mha16_serves(rows_gathered, heads, d, ld):
+            raise ValueError(f"isplib_amd: outside the 16-bit multi-head attention entries' domain (isplib_qkv16_serves = isplib_gat16_serves: "
+                             f"{GAT16_K_MIN} <= heads * d <= {GAT16_K_MAX}, heads == 1 with d even or d a power of two >= 8, the pitch even, "
+                             f"gathered rows < 2^31, rows * pitch * 2 <= 3.5 GiB), got rows={rows_gathered}, heads={heads}, d={d}, pitch={ld}")
+
+
+def _mha16_qkv(m: int, q, k, v):
+    """q [m, K] and k, v [n, K] of the 16-bit multi-head entries, all of q's dtype; returns (n, K, ldq, ldk, ldv)."""
+    ldq = _attn16_dense(q, "q", m, None, "one row per row of the sparse operand")
+    kk = q.size(1)
+    if not isinstance(k, torch.Tensor) or k.dim() != 2:
+        raise ValueError("isplib_amd: `k` must be a 2-D tensor [n, heads * d]")
+    n = k.size(0)
+    ldk = _attn16_dense(k, "k", n, kk, "one row per column of the sparse operand, q's width", q.dtype)
+    ldv = _attn16_dense(v, "v", n, kk, "one row per column of the sparse operand, q's width", q.dtype)
+    return n, kk, ldq, ldk, ldv
+
+
+def mha16_forward(rowptr, col, q, k, v, heads: int = 1, scale: Optional[float] = None, *, out=None, check: bool = True):
+    """`mha` for bf16 / fp16 `q`, `k` and `v` of one dtype (isplib_qkv16_csr_hip): q [m, heads * d], k and v [n, heads * d] go in as
+    they lie (row-strided views keep their even pitch: column views of one fused 16-bit projection go in without a copy), every
+    product, sum and exponential is fp32, z is rounded once to the operands' dtype.  Returns (z [m, heads * d] 16-bit, lse [m, heads]
+    fp32); `out` = (z, lse); `scale` None: 1 / sqrt(d).  The operand checks are mha's, with the 16-bit family's (even pitches, 4-byte
+    aligned bases)."""
+    if not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1 or rowptr.numel() < 1:
+        raise ValueError("isplib_amd: `rowptr` (m + 1 entries) must be a 1-D tensor")
+    m = rowptr.numel() - 1
+    n, kk, ldq, ldk, ldv = _mha16_qkv(m, q, k, v)
+    d = _gat_heads(heads, kk)
+    p = _mha_scale(scale, d)
+    rowptr, col = _attn_structure(rowptr, col, "rowptr", "col", n, check)
+    if out is not None:
+        z, lse = out
+        ldz = _attn16_dense(z, "out[0]", m, kk, "z", q.dtype)
+        _gat_table(lse, "out[1]", m, heads)
+    _mha16_domain(n, heads, d, (ldk, ldv))
+    _same_gpu((("q", q), ("k", k), ("v", v), ("rowptr", rowptr), ("col", col)) +
+              ((("out[0]", out[0]), ("out[1]", out[1])) if out is not None else ()))
+    if out is None:
+        z = torch.empty((m, kk), dtype=q.dtype, device=q.device)
+        lse = torch.empty((m, heads), dtype=torch.float32, device=q.device)
+        ldz = max(kk, 1)
+    if m == 0 or kk == 0:
+        if kk == 0 and m > 0:
+            lse.fill_(float("-inf"))
+        return z, lse
+    rp = rowptr.data_ptr()
+    with torch.cuda.device(q.device):
+        st = lib().isplib_qkv16_csr_hip(HALF_DTYPES[q.dtype], m, n, kk, col.numel(), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8),
+                                        heads, p, _ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(z), ldz, _ptr(lse), _stream(q.device))
+    _check(st, "isplib_qkv16_csr_hip")
+    return z, lse
+
+
+def mha16_backward_rows(rowptr, col, q, k, v, g, lse, heads: int = 1, scale: Optional[float] = None, *, out=None, check: bool = True):
+    """The backward of `mha16_forward` over the rows (isplib_qkv16_bw_rows_hip): for g = dL/dz [m, heads * d] (q's dtype) and the
+    forward's lse -- z is NOT read: D[i,h] = sum_e a_e <g_i, v_j>_h is formed in fp32 from the row's edges, in the same pass as
+    dq_ic = scale (P_c - D Q_c).  Returns (dq [m, heads * d] 16-bit, D [m, heads] fp32); an empty row has dq_i = 0 and D = 0.
+    `out` = (dq, D)."""
+    if not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1 or rowptr.numel() < 1:
+        raise ValueError("isplib_amd: `rowptr` (m + 1 entries) must be a 1-D tensor")
+    m = rowptr.numel() - 1
+    n, kk, ldq, ldk, ldv = _mha16_qkv(m, q, k, v)
+    d = _gat_heads(heads, kk)
+    p = _mha_scale(scale, d)
+    ldg = _attn16_dense(g, "g", m, kk, "the gradient of z", q.dtype)
+    _gat_table(lse, "lse", m, heads)
+    rowptr, col = _attn_structure(rowptr, col, "rowptr", "col", n, check)
+    if out is not None:
+        if len(out) != 2:
+            raise ValueError("isplib_amd: `out` must be (dq, D)")
+        lddq = _attn16_dense(out[0], "out[0]", m, kk, "dq", q.dtype)
+        _gat_table(out[1], "out[1]", m, heads)
+    _mha16_domain(n, heads, d, (ldk, ldv))
+    _same_gpu((("q", q), ("k", k), ("v", v), ("g", g), ("lse", lse), ("rowptr", rowptr), ("col", col)) +
+              ((("out[0]", out[0]), ("out[1]", out[1])) if out is not None else ()))
+    if out is None:
+        out = (torch.empty((m, kk), dtype=q.dtype, device=q.device), torch.empty((m, heads), dtype=torch.float32, device=q.device))
+        lddq = max(kk, 1)
+    dq, dsum = out
+    if m == 0 or kk == 0:
+        if kk == 0 and m > 0:
+            dsum.zero_()
+        return dq, dsum
+    rp = rowptr.data_ptr()
+    with torch.cuda.device(q.device):
+        st = lib().isplib_qkv16_bw_rows_hip(HALF_DTYPES[q.dtype], m, n, kk, col.numel(), _ptr(col), ctypes.c_void_p(rp),
+                                            ctypes.c_void_p(rp + 8), heads, p, _ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(g), ldg,
+                                            _ptr(lse), _ptr(dq), lddq, _ptr(dsum), _stream(q.device))
+    _check(st, "isplib_qkv16_bw_rows_hip")
+    return dq, dsum
+
+
+def mha16_backward_cols(colptr, row_t, q, k, v, g, lse, dsum, heads: int = 1, scale: Optional[float] = None, *, out=None,
+                        check: bool = True):
+    """The backward of `mha16_forward` over the columns (isplib_qkv16_bw_cols_hip), on the transposed structure: dk_j[head h] = scale
+    sum over the entries e = (i, j) of column j of ds_e q_i[head h] and dv_j[head h] = sum of a_e g_i[head h], each rounded once to the
+    operands' dtype, with `lse` of the forward and `dsum` = D of mha16_backward_rows.  Returns (dk, dv), both [n, heads * d] 16-bit; a
+    column no entry points at has 0 in both.  `out` = (dk, dv)."""
+    if not isinstance(colptr, torch.Tensor) or colptr.dim() != 1 or colptr.numel() < 1:
+        raise ValueError("isplib_amd: `colptr` (n + 1 entries) must be a 1-D tensor")
+    n = colptr.numel() - 1
+    ldk = _attn16_dense(k, "k", n, None, "one row per column of the sparse operand")
+    kk = k.size(1)
+    ldv = _attn16_dense(v, "v", n, kk, "one row per column of the sparse operand, k's width", k.dtype)
+    d = _gat_heads(heads, kk)
+    p = _mha_scale(scale, d)
+    if not isinstance(q, torch.Tensor) or q.dim() != 2:
+        raise ValueError("isplib_amd: `q` must be a 2-D tensor [m, heads * d]")
+    m = q.size(0)
+    ldq = _attn16_dense(q, "q", m, kk, "one row per row of the sparse operand, k's width", k.dtype)
+    ldg = _attn16_dense(g, "g", m, kk, "the gradient of z", k.dtype)
+    _gat_table(lse, "lse", m, heads)
+    _gat_table(dsum, "dsum", m, heads)
+    colptr, row_t = _attn_structure(colptr, row_t, "colptr", "row_t", m, check)
+    if out is not None:
+        if len(out) != 2:
+            raise ValueError("isplib_amd: `out` must be (dk, dv)")
+        lddk = _attn16_dense(out[0], "out[0]", n, kk, "dk", k.dtype)
+        lddv = _attn16_dense(out[1], "out[1]", n, kk, "dv", k.dtype)
+    _mha16_domain(m, heads, d, (ldq, ldg))
+    _same_gpu((("q", q), ("k", k), ("v", v), ("g", g), ("lse", lse), ("dsum", dsum), ("colptr", colptr), ("row_t", row_t)) +
+              ((("out[0]", out[0]), ("out[1]", out[1])) if out is not None else ()))
+    if out is None:
+        out = (torch.empty((n, kk), dtype=k.dtype, device=k.device), torch.empty((n, kk), dtype=k.dtype, device=k.device))
+        lddk = lddv = max(kk, 1)
+    dk, dv = out
+    if n == 0 or kk == 0:
+        return dk, dv
+    cp = colptr.data_ptr()
+    with torch.cuda.device(k.device):
+        st = lib().isplib_qkv16_bw_cols_hip(HALF_DTYPES[k.dtype], m, n, kk, row_t.numel(), _ptr(row_t), ctypes.c_void_p(cp),
+                                            ctypes.c_void_p(cp + 8), heads, p, _ptr(q), ldq, _ptr(g), ldg, _ptr(lse), _ptr(dsum), _ptr(k), ldk,
+                                            _ptr(v), ldv, _ptr(dk), lddk, _ptr(dv), lddv, _stream(k.device))
+    _check(st, "isplib_qkv16_bw_cols_hip")
+    return dk, dv
 
 
 def fusedMM_csr_rows16_minmax_hip(imessage: int, rowptr, col, val, order, y, z, z_arg=None, check: bool = True, dtype=None, k=None, ldy=None,

@@ -1,0 +1,593 @@
+// mha16.hip -- the sparse multi-head dot-product attention of mha.hip (separate keys and values) for dense operands of 16-bit elements
+// (bf16, fp16), all heads in one launch, forward and backward (include/isplib_hip_mha16.h: isplib_qkv16_csr_hip,
+// isplib_qkv16_bw_rows_hip, isplib_qkv16_bw_cols_hip).  The mathematics is mha.hip's, stated in its header: for every row i, stored
+// entry e = (i, j) and head h, with q [m, k], key [n, k], v [n, k], k = H*d, a scalar scale p and g = dL/dz:
+//    s_e  = p <q_i, key_j>_h     a_e = exp(s_e - lse[i,h]),  lse[i,h] = log sum_e exp(s_e)     z_i[head h] = sum_e a_e v_j[head h]
+//    D[i,h] = sum_e a_e t_e      t_e = <g_i, v_j>_h          ds_e = a_e (t_e - D[i,h])
+//    dq_i[head h]   = p sum_e ds_e key_j[head h]
+//    dkey_j[head h] = p sum_{e -> j} ds_e q_i[head h]
+//    dv_j[head h]   = sum_{e -> j} a_e g_i[head h].
+// No wide operand is widened in memory: a gathered row of key, v, q or g is half the bytes of the fp32 kernels', and the operator is
+// bound by gathered bytes -- two wide rows per edge in every kernel.
+//
+// The 16-bit family's contract: q, key, v, g, z, dq, dkey and dv are 16-bit and widening is exact (half16.h: widen2);
+// every product, sum, exponential and division is fp32; each wide output is rounded ONCE, to nearest even (narrow2).  lse and D stay
+// fp32.  p multiplies the finished dot product, in all three kernels alike, and the finished rows of dq and dkey.
+//
+// Mapping: gatv2_16.hip's -- one wave per row (per column of A in the columns kernel), ONE 16-byte buffer load of EIGHT columns per
+// lane, edge and gathered table, one chunk per lane, LPR = 4 / 8 / 16 / 32 / 64 for ceil(k / 8) up to 4 / 8 / 16 / 32 / 64 and
+// G = 64 / LPR edge slots.  With H > 1, d is a power of two >= 8: a lane's eight columns never straddle heads and a head is an aligned
+// group of d / 8 lanes.  With H == 1 the head is the whole slot and k may be any even width >= 8; the ragged last vector (k % 8 != 0)
+// over-reads, and each over-read dword is dropped by a per-dword select before it is widened, never by a multiply.  The dot products
+// of a step (U scores in the forward, U scores and U <g_i, v_j>_h in the backward kernels) go through the levels of ONE butterfly
+// together.  Every gathered table sits behind a buffer descriptor of exactly the extent it owns (2 bytes per element for the wide
+// tables, 4 for lse / D); dead edges and lanes past k carry BUF_OOB, which the descriptor answers with 0.  No atomics, no LDS, a fixed
+// order of operations: two launches give equal bits.
+//
+// The forward is the online softmax per lane: (m, l, acc[8]), one rescale per step of U edges, -FLT_MAX for "no edge yet", the slots
+// merged pairwise.  A row of one entry has weight exp(0) = 1 and l = 1: z_i is v_j's 16 bits.  fmaxf drops a NaN score from the
+// maximum, so it enters l through exp(NaN - m): a NaN in key[j,c] makes the head of c NaN in the rows that reference j, a NaN in
+// v[j,c] column c of those rows, and nothing else.
+//
+// The backward over the rows does NOT read z: in 16 bits z is rounded, and D = <g_i, z16_i>_h would carry u * sum_c |g_ic z_ic| into
+// every ds_e.  One pass over the row's edges accumulates, per head and slot, l = sum a_e and
+// Dacc = sum a_e t_e and, per column, P_c = sum a_e t_e key_jc and Q_c = sum a_e key_jc; the slots merge by plain sums; D = Dacc / l
+// and dq_ic = p (P_c - D Q_c).  The columns kernel walks the transposed structure with key_j and v_j (widened) in registers, gathers
+// q_i and g_i (16 bytes each) and lse, D of [i, head] (4 bytes each, two tables, each behind its own descriptor), and writes dkey and
+// dv, each rounded once, each at its own pitch.  mha.hip, gatv2_16.hip and the other kernel files are untouched; their small helpers
+// are restated here under names of their own.  DESIGN.md 4.6l.
+#include <cfloat>
+#include <cmath>
+
+#include "common.h"
+#include "gather.h"
+#include "half16.h"
+
+// edges per slot and step, per kernel: measured among {2, 4}; an experiment build may override them (make EXTRA=-D...)
+#ifndef ISPLIB_MHA16_FW_U
+#define ISPLIB_MHA16_FW_U 2
+#endif
+#ifndef ISPLIB_MHA16_ROWS_U
+#define ISPLIB_MHA16_ROWS_U 2
+#endif
+#ifndef ISPLIB_MHA16_COLS_U
+#define ISPLIB_MHA16_COLS_U 2
+#endif
+
+namespace isplib {
+
+constexpr float MHA16_NONE = -FLT_MAX;       // the running maximum of a lane that saw no edge
+constexpr int MHA16_WAVES = 4;               // rows per block
+constexpr int MHA16_FW_U = ISPLIB_MHA16_FW_U;
+constexpr int MHA16_ROWS_U = ISPLIB_MHA16_ROWS_U;
+constexpr int MHA16_COLS_U = ISPLIB_MHA16_COLS_U;
+
+struct Mha16Args {
+   int64_t rows, k;                          // rows: one wave each (rows of A; columns of A in the columns kernel)
+   int heads;
+   int hshift;                               // head of column c: c >> hshift (H == 1: 31, every column is head 0)
+   int hlanes;                               // lanes that share a head: d / 8 (H == 1: 64, the whole slot)
+   unsigned hmask;                           // c & hmask == 0: the first column of a head (H == 1: only column 0)
+   const int64_t *indx, *pntrb, *pntre;
+   float p;                                  // the scale of the scores
+   // the row-resident operands (plain loads of the wave's own row) and the outputs
+   const unsigned short *own;                // forward, rows: q | columns: key
+   int64_t ldown;
+   const unsigned short *own2;               // columns: v
+   int64_t ldown2;
+   const unsigned short *g;                  // rows: dL/dz
+   int64_t ldg;
+   const float *lse_in;                      // rows: lse [rows, H]
+   unsigned short *out;                      // z | dq | dkey
+   int64_t ldout;
+   unsigned short *out2;                     // columns: dv
+   int64_t ldout2;
+   float *hout;                              // [rows, H]: forward lse | rows: D
+   // the gathered operands, each behind one descriptor
+   const void *ga;                           // forward, rows: key | columns: q
+   int64_t ldga;
+   unsigned gabytes;
+   const void *gb;                           // forward, rows: v | columns: g
+   int64_t ldgb;
+   unsigned gbbytes;
+   const float *t1, *t2;                     // columns: lse, D; both [gathered rows, H]
+   unsigned tbytes;
+};
+
+// this lane's eight consecutive columns and their head; ok[q]: the dword of columns (2q, 2q + 1) lies inside the row (k is even)
+struct Mha16Cols {
+   int col, head;
+   unsigned cbyte, hbyte, poison;            // past k: an offset the descriptors answer with 0
+   bool ok[4], first;                        // first: this lane opens a head (and lies inside k)
+   __device__ __forceinline__ Mha16Cols(const Mha16Args &a, int lc) {
+      col = lc * 8;
+      cbyte = (unsigned)col * 2u;
+      poison = col < (int)a.k ? 0u : BUF_OOB;
+      head = col >> a.hshift;
+      hbyte = (unsigned)head * 4u;
+      first = col < (int)a.k && ((unsigned)col & a.hmask) == 0u;
+#pragma unroll
+      for (int q = 0; q < 4; q++) ok[q] = col + 2 * q < (int)a.k;
+   }
+};
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t mha16_desc(const void *p, unsigned bytes) {
+   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
+}
+
+// this lane's columns of row `row` of a dense 16-bit operand as floats; plain dword loads (base, pitch and column are even), nothing
+// outside the row's k columns is read
+template <int ELT>
+__device__ __forceinline__ void mha16_own_row(const unsigned short *base, int64_t row, int64_t ld, const Mha16Cols &cm, float (&r)[8]) {
+   const unsigned *p = reinterpret_cast<const unsigned *>(base + (size_t)row * (size_t)ld + (size_t)cm.col);
+#pragma unroll
+   for (int q = 0; q < 4; q++) {
+      unsigned w = 0u;
+      if (cm.ok[q]) w = p[q];
+      widen2<ELT>(w, r[2 * q], r[2 * q + 1]);
+   }
+}
+
+// entry [row, this lane's head] of a dense fp32 [rows, H] table; a lane past k reads nothing
+__device__ __forceinline__ float mha16_own_head(const float *base, int64_t row, int heads, const Mha16Cols &cm) {
+   return cm.poison == 0u ? base[(size_t)row * (size_t)heads + (size_t)cm.head] : 0.0f;
+}
+
+// byte offset of the gathered row of edge `id` at a pitch of `pitch_bytes`; a dead edge: BUF_OOB
+__device__ __forceinline__ unsigned mha16_off(int id, unsigned pitch_bytes) {
+   return id < 0 ? BUF_OOB : (unsigned)id * pitch_bytes;     // BUF_OOB + cbyte / hbyte (< 2^10) cannot wrap
+}
+
+__device__ __forceinline__ v4i_t mha16_load_wide(const __amdgpu_buffer_rsrc_t rsrc, unsigned off, const Mha16Cols &cm) {
+   return __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)((off + cm.cbyte) | cm.poison), 0, 0);
+}
+
+__device__ __forceinline__ float mha16_load_head(const __amdgpu_buffer_rsrc_t rsrc, unsigned offh, const Mha16Cols &cm) {
+   return __int_as_float((int)__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)((offh + cm.hbyte) | cm.poison), 0, 0));
+}
+
+// a gathered vector as eight floats; a dword the 16-byte load brought from outside the row is dropped by a select, not a multiply
+template <int ELT> __device__ __forceinline__ void mha16_widen(const v4i_t &t, const Mha16Cols &cm, float (&y)[8]) {
+#pragma unroll
+   for (int q = 0; q < 4; q++) widen2<ELT>(cm.ok[q] ? (unsigned)t[q] : 0u, y[2 * q], y[2 * q + 1]);
+}
+
+// N sums over the lanes that share a head (an aligned group of `hlanes` lanes, a power of two; H == 1: the whole slot), level by level
+// together; every lane of the group ends with the same bits (each level adds the same two numbers on both sides).  Partners 1, 2, 4, 8
+// by DPP moves inside the 16-lane row (gather.h), wider ones by ds_bpermute.  hlanes == 1: no cross-lane step is taken
+template <int LPR, int N, int O = 1> __device__ __forceinline__ void mha16_head_sum(float (&v)[N], int hlanes) {
+   if constexpr (O < LPR) {
+      float w[N];
+#pragma unroll
+      for (int i = 0; i < N; i++) w[i] = lane_xor<O>(v[i]);
+#pragma unroll
+      for (int i = 0; i < N; i++) v[i] = O < hlanes ? v[i] + w[i] : v[i];
+      mha16_head_sum<LPR, N, 2 * O>(v, hlanes);
+   }
+}
+
+// this lane's part of <r, t>_h: one fma chain over its eight columns; a column past k has r = t = 0
+__device__ __forceinline__ float mha16_dot_part(const float (&r)[8], const float (&t)[8]) {
+   float p = 0.0f;
+#pragma unroll
+   for (int v = 0; v < 8; v++) p = fmaf(r[v], t[v], p);
+   return p;
+}
+
+// the lane's eight finished columns, rounded once; only the dwords inside the row are written
+template <int ELT>
+__device__ __forceinline__ void mha16_store_row(unsigned short *base, int64_t row, int64_t ld, const Mha16Cols &cm, const float (&r)[8]) {
+   if (cm.poison != 0u) return;
+   unsigned *p = reinterpret_cast<unsigned *>(base + (size_t)row * (size_t)ld + (size_t)cm.col);
+   unsigned d[4];
+#pragma unroll
+   for (int q = 0; q < 4; q++) d[q] = narrow2<ELT>(r[2 * q], r[2 * q + 1]);
+   if (cm.ok[3] && ((uintptr_t)p & 15) == 0) {
+      *reinterpret_cast<uint4 *>(p) = make_uint4(d[0], d[1], d[2], d[3]);
+   } else {
+#pragma unroll
+      for (int q = 0; q < 4; q++)
+         if (cm.ok[q]) p[q] = d[q];
+   }
+}
+
+template <int ELT, int LPR, int WAVES, int U>
+__global__ __launch_bounds__(WAVES * 64) void mha16_fw_kernel(const Mha16Args a) {
+   constexpr int G = 64 / LPR;
+   const int lane = threadIdx.x & 63;
+   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+   const int g = lane / LPR, lc = lane % LPR;
+   const int64_t row = (int64_t)blockIdx.x * WAVES + wave;
+   if (row >= a.rows) return;
+   const int64_t eb = a.pntrb[row], ee = a.pntre[row];
+   const __amdgpu_buffer_rsrc_t rsk = mha16_desc(a.ga, a.gabytes), rsv = mha16_desc(a.gb, a.gbbytes);
+   const Mha16Cols cm(a, lc);
+   float qv[8];
+   mha16_own_row<ELT>(a.own, row, a.ldown, cm, qv);
+
+   float mrun = MHA16_NONE, l = 0.0f, acc[8];
+#pragma unroll
+   for (int v = 0; v < 8; v++) acc[v] = 0.0f;
+
+   const unsigned ldkb = (unsigned)a.ldga * 2u, ldvb = (unsigned)a.ldgb * 2u;
+   for (int64_t base = eb; base < ee; base += 64) {
+      const int64_t pos = base + lane;
+      const int id_l = pos < ee ? (int)a.indx[pos] : -1;
+      const int64_t left = ee - base;
+      const int cnt = left < 64 ? (int)left : 64;
+#pragma unroll 1
+      for (int s0 = 0; s0 < cnt; s0 += G * U) {
+         v4i_t kv[U], vv[U];
+#pragma unroll
+         for (int u = 0; u < U; u++) {
+            const int id = __shfl(id_l, (s0 + u * G + g) & 63);
+            kv[u] = mha16_load_wide(rsk, mha16_off(id, ldkb), cm);
+            vv[u] = mha16_load_wide(rsv, mha16_off(id, ldvb), cm);
+         }
+         float sc[U];
+#pragma unroll
+         for (int u = 0; u < U; u++) {
+            float k8[8];
+            mha16_widen<ELT>(kv[u], cm, k8);
+            sc[u] = mha16_dot_part(qv, k8);
+         }
+         mha16_head_sum<LPR, U>(sc, a.hlanes);
+         float mnew = mrun;
+#pragma unroll
+         for (int u = 0; u < U; u++) {
+            sc[u] *= a.p;
+            mnew = (s0 + u * G + g < cnt) ? fmaxf(mnew, sc[u]) : mnew;      // a NaN score is not a maximum; it enters through exp below
+         }
+         const float r = __expf(mrun - mnew);
+         mrun = mnew;
+         l *= r;
+#pragma unroll
+         for (int v = 0; v < 8; v++) acc[v] *= r;
+#pragma unroll
+         for (int u = 0; u < U; u++) {
+            const float w = (s0 + u * G + g < cnt) ? __expf(sc[u] - mnew) : 0.0f;
+            float v8[8];
+            mha16_widen<ELT>(vv[u], cm, v8);
+            l += w;
+#pragma unroll
+            for (int v = 0; v < 8; v++) acc[v] = fmaf(w, v8[v], acc[v]);
+         }
+      }
+   }
+   // merge the G slots pairwise, by the rule of a step
+#pragma unroll
+   for (int o = LPR; o < 64; o <<= 1) {
+      const float mo = __shfl_xor(mrun, o), lo = __shfl_xor(l, o);
+      const float mnew = fmaxf(mrun, mo);
+      const float ra = __expf(mrun - mnew), rb = __expf(mo - mnew);
+      l = l * ra + lo * rb;
+#pragma unroll
+      for (int v = 0; v < 8; v++) acc[v] = acc[v] * ra + __shfl_xor(acc[v], o) * rb;
+      mrun = mnew;
+   }
+   if (g != 0) return;
+   const bool empty = ee <= eb;
+   float zr[8];
+#pragma unroll
+   for (int v = 0; v < 8; v++) zr[v] = empty ? 0.0f : acc[v] / l;
+   mha16_store_row<ELT>(a.out, row, a.ldout, cm, zr);
+   if (cm.first) a.hout[(size_t)row * (size_t)a.heads + (size_t)cm.head] = empty ? -INFINITY : mrun + logf(l);
+}
+
+// the one-pass backward over the rows: no z, D[i,h] from the row's own edges
+template <int ELT, int LPR, int WAVES, int U>
+__global__ __launch_bounds__(WAVES * 64) void mha16_bw_rows_kernel(const Mha16Args a) {
+   constexpr int G = 64 / LPR;
+   const int lane = threadIdx.x & 63;
+   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+   const int g = lane / LPR, lc = lane % LPR;
+   const int64_t row = (int64_t)blockIdx.x * WAVES + wave;
+   if (row >= a.rows) return;
+   const int64_t eb = a.pntrb[row], ee = a.pntre[row];
+   const __amdgpu_buffer_rsrc_t rsk = mha16_desc(a.ga, a.gabytes), rsv = mha16_desc(a.gb, a.gbbytes);
+   const Mha16Cols cm(a, lc);
+   float qv[8], gv[8];
+   mha16_own_row<ELT>(a.own, row, a.ldown, cm, qv);
+   mha16_own_row<ELT>(a.g, row, a.ldg, cm, gv);
+   const float lse = mha16_own_head(a.lse_in, row, a.heads, cm);
+
+   float l = 0.0f, dacc = 0.0f;                        // per head: sum a_e, sum a_e t_e
+   float pc[8], qc[8];                                 // per column: sum a_e t_e key_jc, sum a_e key_jc
+#pragma unroll
+   for (int v = 0; v < 8; v++) pc[v] = qc[v] = 0.0f;
+
+   const unsigned ldkb = (unsigned)a.ldga * 2u, ldvb = (unsigned)a.ldgb * 2u;
+   for (int64_t base = eb; base < ee; base += 64) {
+      const int64_t pos = base + lane;
+      const int id_l = pos < ee ? (int)a.indx[pos] : -1;
+      const int64_t left = ee - base;
+      const int cnt = left < 64 ? (int)left : 64;
+#pragma unroll 1
+      for (int s0 = 0; s0 < cnt; s0 += G * U) {
+         v4i_t kv[U], vv[U];
+#pragma unroll
+         for (int u = 0; u < U; u++) {
+            const int id = __shfl(id_l, (s0 + u * G + g) & 63);
+            kv[u] = mha16_load_wide(rsk, mha16_off(id, ldkb), cm);
+            vv[u] = mha16_load_wide(rsv, mha16_off(id, ldvb), cm);
+         }
+         float part[2 * U];                            // <q_i, key_j>_h and t_e of the step through one butterfly
+#pragma unroll
+         for (int u = 0; u < U; u++) {
+            float k8[8], v8[8];
+            mha16_widen<ELT>(kv[u], cm, k8);
+            mha16_widen<ELT>(vv[u], cm, v8);
+            part[u] = mha16_dot_part(qv, k8);
+            part[U + u] = mha16_dot_part(gv, v8);
+         }
+         mha16_head_sum<LPR, 2 * U>(part, a.hlanes);         // every lane takes part: not under `live`
+#pragma unroll
+         for (int u = 0; u < U; u++) {
+            const bool live = s0 + u * G + g < cnt;
+            const float ae = live ? __expf(part[u] * a.p - lse) : 0.0f;
+            const float aet = live ? ae * part[U + u] : 0.0f;
+            l += ae;
+            dacc += aet;
+            float k8[8];
+            mha16_widen<ELT>(kv[u], cm, k8);
+#pragma unroll
+            for (int v = 0; v < 8; v++) {
+               pc[v] = fmaf(aet, k8[v], pc[v]);
+               qc[v] = fmaf(ae, k8[v], qc[v]);
+            }
+         }
+      }
+   }
+#pragma unroll
+   for (int o = LPR; o < 64; o <<= 1) {
+      l += __shfl_xor(l, o);
+      dacc += __shfl_xor(dacc, o);
+#pragma unroll
+      for (int v = 0; v < 8; v++) {
+         pc[v] += __shfl_xor(pc[v], o);
+         qc[v] += __shfl_xor(qc[v], o);
+      }
+   }
+   if (g != 0) return;
+   const bool empty = ee <= eb;
+   const float dsum = (empty || cm.poison != 0u) ? 0.0f : dacc / l;      // a lane past k saw no weight: l = 0
+   float dq[8];
+#pragma unroll
+   for (int v = 0; v < 8; v++) dq[v] = empty ? 0.0f : a.p * (pc[v] - dsum * qc[v]);
+   mha16_store_row<ELT>(a.out, row, a.ldout, cm, dq);
+   if (cm.first) a.hout[(size_t)row * (size_t)a.heads + (size_t)cm.head] = dsum;
+}
+
+// one wave per column j of A (a row of the transposed structure): key_j and v_j in registers; q_i, g_i and lse, D of [i, head] gathered
+template <int ELT, int LPR, int WAVES, int U>
+__global__ __launch_bounds__(WAVES * 64) void mha16_bw_cols_kernel(const Mha16Args a) {
+   constexpr int G = 64 / LPR;
+   const int lane = threadIdx.x & 63;
+   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+   const int g = lane / LPR, lc = lane % LPR;
+   const int64_t row = (int64_t)blockIdx.x * WAVES + wave;
+   if (row >= a.rows) return;
+   const int64_t eb = a.pntrb[row], ee = a.pntre[row];
+   const __amdgpu_buffer_rsrc_t rsq = mha16_desc(a.ga, a.gabytes), rsg = mha16_desc(a.gb, a.gbbytes);
+   const __amdgpu_buffer_rsrc_t rs1 = mha16_desc(a.t1, a.tbytes), rs2 = mha16_desc(a.t2, a.tbytes);
+   const Mha16Cols cm(a, lc);
+   float kv[8], vv[8];
+   mha16_own_row<ELT>(a.own, row, a.ldown, cm, kv);
+   mha16_own_row<ELT>(a.own2, row, a.ldown2, cm, vv);
+
+   float dk[8], dv[8];
+#pragma unroll
+   for (int v = 0; v < 8; v++) dk[v] = dv[v] = 0.0f;
+
+   const unsigned ldqb = (unsigned)a.ldga * 2u, ldgb = (unsigned)a.ldgb * 2u, hb = (unsigned)a.heads * 4u;
+   for (int64_t base = eb; base < ee; base += 64) {
+      const int64_t pos = base + lane;
+      const int id_l = pos < ee ? (int)a.indx[pos] : -1;
+      const int64_t left = ee - base;
+      const int cnt = left < 64 ? (int)left : 64;
+#pragma unroll 1
+      for (int s0 = 0; s0 < cnt; s0 += G * U) {
+         v4i_t qg[U], gg[U];
+         float ls[U], dd[U];
+#pragma unroll
+         for (int u = 0; u < U; u++) {
+            const int id = __shfl(id_l, (s0 + u * G + g) & 63);
+            qg[u] = mha16_load_wide(rsq, mha16_off(id, ldqb), cm);
+            gg[u] = mha16_load_wide(rsg, mha16_off(id, ldgb), cm);
+            ls[u] = mha16_load_head(rs1, mha16_off(id, hb), cm);
+            dd[u] = mha16_load_head(rs2, mha16_off(id, hb), cm);
+         }
+         float part[2 * U];
+#pragma unroll
+         for (int u = 0; u < U; u++) {
+            float q8[8], g8[8];
+            mha16_widen<ELT>(qg[u], cm, q8);
+            mha16_widen<ELT>(gg[u], cm, g8);
+            part[u] = mha16_dot_part(q8, kv);             // the products commute bit for bit: the rows kernel's score
+            part[U + u] = mha16_dot_part(g8, vv);
+         }
+         mha16_head_sum<LPR, 2 * U>(part, a.hlanes);         // every lane takes part: not under `live`
+#pragma unroll
+         for (int u = 0; u < U; u++) {
+            const bool live = s0 + u * G + g < cnt;
+            const float ae = live ? __expf(part[u] * a.p - ls[u]) : 0.0f;
+            const float ds = live ? ae * (part[U + u] - dd[u]) : 0.0f;
+            float q8[8], g8[8];
+            mha16_widen<ELT>(qg[u], cm, q8);
+            mha16_widen<ELT>(gg[u], cm, g8);
+#pragma unroll
+            for (int v = 0; v < 8; v++) {
+               dk[v] = fmaf(ds, q8[v], dk[v]);
+               dv[v] = fmaf(ae, g8[v], dv[v]);
+            }
+         }
+      }
+   }
+#pragma unroll
+   for (int o = LPR; o < 64; o <<= 1)
+#pragma unroll
+      for (int v = 0; v < 8; v++) {
+         dk[v] += __shfl_xor(dk[v], o);
+         dv[v] += __shfl_xor(dv[v], o);
+      }
+   if (g != 0) return;
+#pragma unroll
+   for (int v = 0; v < 8; v++) dk[v] *= a.p;          // no incoming entry: 0
+   mha16_store_row<ELT>(a.out, row, a.ldout, cm, dk);
+   mha16_store_row<ELT>(a.out2, row, a.ldout2, cm, dv);
+}
+
+enum { MHA16_FW = 0, MHA16_BW_ROWS = 1, MHA16_BW_COLS = 2 };
+
+template <int ELT, int LPR>
+static int launch_mha16(int which, const Mha16Args &a, const char *entry, hipStream_t st) {
+   const int64_t nb = (a.rows + MHA16_WAVES - 1) / MHA16_WAVES;
+   if (nb > 0x7fffffffLL) return fail(ISPLIB_FAIL, entry, "too many rows for one launch");
+   const dim3 grid((unsigned)nb), block((unsigned)MHA16_WAVES * 64u);
+   if (which == MHA16_FW) hipLaunchKernelGGL((mha16_fw_kernel<ELT, LPR, MHA16_WAVES, MHA16_FW_U>), grid, block, 0, st, a);
+   else if (which == MHA16_BW_ROWS) hipLaunchKernelGGL((mha16_bw_rows_kernel<ELT, LPR, MHA16_WAVES, MHA16_ROWS_U>), grid, block, 0, st, a);
+   else hipLaunchKernelGGL((mha16_bw_cols_kernel<ELT, LPR, MHA16_WAVES, MHA16_COLS_U>), grid, block, 0, st, a);
+   return check_launch(entry);
+}
+
+// the slot width by ceil(k / 8) 16-byte vectors per row, always one chunk per lane
+template <int ELT>
+static int mha16_by_width(int which, const Mha16Args &a, const char *entry, hipStream_t st) {
+   const int64_t w = (a.k + 7) / 8;
+   if (w <= 4) return launch_mha16<ELT, 4>(which, a, entry, st);
+   if (w <= 8) return launch_mha16<ELT, 8>(which, a, entry, st);
+   if (w <= 16) return launch_mha16<ELT, 16>(which, a, entry, st);
+   if (w <= 32) return launch_mha16<ELT, 32>(which, a, entry, st);
+   return launch_mha16<ELT, 64>(which, a, entry, st);
+}
+
+static int mha16_run(int dtype, int which, const Mha16Args &a, const char *entry, void *stream) {
+   return dtype == ISPLIB_DTYPE_BF16 ? mha16_by_width<ELT_BF16>(which, a, entry, (hipStream_t)stream)
+                                     : mha16_by_width<ELT_F16>(which, a, entry, (hipStream_t)stream);
+}
+
+// what a descriptor over `rows` rows of k elements of `size` bytes at pitch ld may answer: the extent a row-strided view owns
+static unsigned mha16_extent(int64_t rows, int64_t k, int64_t ld, unsigned size) {
+   return rows <= 0 ? 0u : (unsigned)(((unsigned long long)(rows - 1) * (unsigned long long)ld + (unsigned long long)k) * size);
+}
+
+// the head geometry of a launch; the domain (isplib_qkv16_serves) has been checked: H == 1, or d a power of two >= 8
+static void mha16_heads(Mha16Args &a, int64_t heads, int64_t d) {
+   a.heads = (int)heads;
+   if (heads == 1) {
+      a.hshift = 31; a.hlanes = 64; a.hmask = 0x7fffffffu;
+   } else {
+      int sh = 0;
+      while ((1LL << sh) < d) sh++;
+      a.hshift = sh; a.hlanes = (int)(d / 8); a.hmask = (unsigned)(d - 1);
+   }
+}
+
+static const char *const MHA16_DTYPE = "dtype must be ISPLIB_DTYPE_BF16 or ISPLIB_DTYPE_F16";
+static const char *const MHA16_DOMAIN = "outside isplib_qkv16_serves(rows_gathered, heads, d, ld) = isplib_gat16_serves: 1 <= heads, "
+                                        "8 <= heads*d <= 512, heads == 1 with d even or d a power of two >= 8, every pitch even, "
+                                        "ld >= heads*d, rows_gathered < 2^31, rows_gathered*ld*2 <= 3.5 GiB (convert the operands and "
+                                        "use the fp32 entries)";
+
+static bool mha16_even(int64_t a, int64_t b, int64_t c = 0, int64_t d = 0) { return ((a | b | c | d) & 1) == 0; }
+static bool mha16_aligned(const void *a, const void *b, const void *c, const void *d, const void *e = nullptr, const void *f = nullptr) {
+   return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d | (uintptr_t)e | (uintptr_t)f) & 3) == 0;
+}
+
+}  // namespace isplib
+
+using namespace isplib;
+
+extern "C" int isplib_qkv16_domain(int64_t rows_gathered, int64_t heads, int64_t d, int64_t ld) {
+   return isplib_qkv16_serves(rows_gathered, heads, d, ld);
+}
+
+extern "C" int isplib_qkv16_auto(int64_t rows_gathered, int64_t ld) { return isplib_qkv16_native_pays(rows_gathered, ld); }
+
+// the refusals of the three entries come in one order: dtype, negative dimension, nothing to do, a pitch below k, k % heads, the scale,
+// the domain, a null operand, alignment -- all before any launch
+extern "C" int isplib_qkv16_csr_hip(int dtype, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                                    const int64_t *pntre, int64_t heads, float scale, const void *q, int64_t ldq, const void *key,
+                                    int64_t ldk, const void *v, int64_t ldv, void *z, int64_t ldz, float *lse, void *stream) {
+   const char *entry = "isplib_qkv16_csr_hip";
+   clear_error();
+   if (dtype != ISPLIB_DTYPE_BF16 && dtype != ISPLIB_DTYPE_F16) return fail(ISPLIB_FAIL, entry, MHA16_DTYPE);
+   if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
+   if (m == 0 || k == 0) return ISPLIB_SUCCESS;
+   if (ldq < k || ldz < k) return fail(ISPLIB_FAIL, entry, "leading dimension smaller than k");
+   if (heads >= 1 && k % heads != 0) return fail(ISPLIB_FAIL, entry, "k is not a multiple of heads");
+   if (!std::isfinite(scale)) return fail(ISPLIB_FAIL, entry, "scale must be a finite number");
+   if (heads < 1 || !isplib_qkv16_serves(n, heads, k / heads, ldk) || !isplib_qkv16_serves(n, heads, k / heads, ldv) ||
+       !mha16_even(ldq, ldz))
+      return fail(ISPLIB_NO_OPT_IMPL, entry, MHA16_DOMAIN);
+   if (!pntrb || !pntre || !q || !z || !lse || (nnz > 0 && (!indx || !key || !v))) return fail(ISPLIB_FAIL, entry, "null operand");
+   if (!mha16_aligned(q, key, v, z)) return fail(ISPLIB_FAIL, entry, "q, key, v and z must be 4-byte aligned");
+   Mha16Args a = {};
+   a.rows = m; a.k = k; a.indx = indx; a.pntrb = pntrb; a.pntre = pntre; a.p = scale;
+   mha16_heads(a, heads, k / heads);
+   a.own = reinterpret_cast<const unsigned short *>(q); a.ldown = ldq;
+   a.out = reinterpret_cast<unsigned short *>(z); a.ldout = ldz; a.hout = lse;
+   a.ga = key; a.ldga = ldk; a.gabytes = nnz > 0 ? mha16_extent(n, k, ldk, 2u) : 0u;
+   a.gb = v; a.ldgb = ldv; a.gbbytes = nnz > 0 ? mha16_extent(n, k, ldv, 2u) : 0u;
+   return mha16_run(dtype, MHA16_FW, a, entry, stream);
+}
+
+extern "C" int isplib_qkv16_bw_rows_hip(int dtype, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                                        const int64_t *pntre, int64_t heads, float scale, const void *q, int64_t ldq, const void *key,
+                                        int64_t ldk, const void *v, int64_t ldv, const void *g, int64_t ldg, const float *lse, void *dq,
+                                        int64_t lddq, float *dsum, void *stream) {
+   const char *entry = "isplib_qkv16_bw_rows_hip";
+   clear_error();
+   if (dtype != ISPLIB_DTYPE_BF16 && dtype != ISPLIB_DTYPE_F16) return fail(ISPLIB_FAIL, entry, MHA16_DTYPE);
+   if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
+   if (m == 0 || k == 0) return ISPLIB_SUCCESS;
+   if (ldq < k || ldg < k || lddq < k) return fail(ISPLIB_FAIL, entry, "leading dimension smaller than k");
+   if (heads >= 1 && k % heads != 0) return fail(ISPLIB_FAIL, entry, "k is not a multiple of heads");
+   if (!std::isfinite(scale)) return fail(ISPLIB_FAIL, entry, "scale must be a finite number");
+   if (heads < 1 || !isplib_qkv16_serves(n, heads, k / heads, ldk) || !isplib_qkv16_serves(n, heads, k / heads, ldv) ||
+       !mha16_even(ldq, ldg, lddq))
+      return fail(ISPLIB_NO_OPT_IMPL, entry, MHA16_DOMAIN);
+   if (!pntrb || !pntre || !q || !g || !lse || !dq || !dsum || (nnz > 0 && (!indx || !key || !v)))
+      return fail(ISPLIB_FAIL, entry, "null operand");
+   if (!mha16_aligned(q, key, v, g, dq)) return fail(ISPLIB_FAIL, entry, "q, key, v, g and dq must be 4-byte aligned");
+   Mha16Args a = {};
+   a.rows = m; a.k = k; a.indx = indx; a.pntrb = pntrb; a.pntre = pntre; a.p = scale;
+   mha16_heads(a, heads, k / heads);
+   a.own = reinterpret_cast<const unsigned short *>(q); a.ldown = ldq;
+   a.g = reinterpret_cast<const unsigned short *>(g); a.ldg = ldg; a.lse_in = lse;
+   a.out = reinterpret_cast<unsigned short *>(dq); a.ldout = lddq; a.hout = dsum;
+   a.ga = key; a.ldga = ldk; a.gabytes = nnz > 0 ? mha16_extent(n, k, ldk, 2u) : 0u;
+   a.gb = v; a.ldgb = ldv; a.gbbytes = nnz > 0 ? mha16_extent(n, k, ldv, 2u) : 0u;
+   return mha16_run(dtype, MHA16_BW_ROWS, a, entry, stream);
+}
+
+extern "C" int isplib_qkv16_bw_cols_hip(int dtype, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t, const int64_t *colb,
+                                        const int64_t *cole, int64_t heads, float scale, const void *q, int64_t ldq, const void *g,
+                                        int64_t ldg, const float *lse, const float *dsum, const void *key, int64_t ldk, const void *v,
+                                        int64_t ldv, void *dkey, int64_t lddk, void *dv, int64_t lddv, void *stream) {
+   const char *entry = "isplib_qkv16_bw_cols_hip";
+   clear_error();
+   if (dtype != ISPLIB_DTYPE_BF16 && dtype != ISPLIB_DTYPE_F16) return fail(ISPLIB_FAIL, entry, MHA16_DTYPE);
+   if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
+   if (n == 0 || k == 0) return ISPLIB_SUCCESS;
+   if (ldk < k || ldv < k || lddk < k || lddv < k) return fail(ISPLIB_FAIL, entry, "leading dimension smaller than k");
+   if (heads >= 1 && k % heads != 0) return fail(ISPLIB_FAIL, entry, "k is not a multiple of heads");
+   if (!std::isfinite(scale)) return fail(ISPLIB_FAIL, entry, "scale must be a finite number");
+   if (heads < 1 || !isplib_qkv16_serves(m, heads, k / heads, ldq) || !isplib_qkv16_serves(m, heads, k / heads, ldg) ||
+       !mha16_even(ldk, ldv, lddk, lddv))
+      return fail(ISPLIB_NO_OPT_IMPL, entry, MHA16_DOMAIN);
+   if (!colb || !cole || !key || !v || !dkey || !dv || (nnz > 0 && (!row_t || !q || !g || !lse || !dsum)))
+      return fail(ISPLIB_FAIL, entry, "null operand");
+   if (!mha16_aligned(q, g, key, v, dkey, dv)) return fail(ISPLIB_FAIL, entry, "q, g, key, v, dkey and dv must be 4-byte aligned");
+   Mha16Args a = {};
+   a.rows = n; a.k = k; a.indx = row_t; a.pntrb = colb; a.pntre = cole; a.p = scale;
+   mha16_heads(a, heads, k / heads);
+   a.own = reinterpret_cast<const unsigned short *>(key); a.ldown = ldk;
+   a.own2 = reinterpret_cast<const unsigned short *>(v); a.ldown2 = ldv;
+   a.out = reinterpret_cast<unsigned short *>(dkey); a.ldout = lddk;
+   a.out2 = reinterpret_cast<unsigned short *>(dv); a.ldout2 = lddv;
+   a.ga = q; a.ldga = ldq; a.gabytes = nnz > 0 ? mha16_extent(m, k, ldq, 2u) : 0u;
+   a.gb = g; a.ldgb = ldg; a.gbbytes = nnz > 0 ? mha16_extent(m, k, ldg, 2u) : 0u;
+   a.t1 = lse; a.t2 = dsum; a.tbytes = nnz > 0 ? mha16_extent(m, heads, heads, 4u) : 0u;
+   return mha16_run(dtype, MHA16_BW_COLS, a, entry, stream);
+}

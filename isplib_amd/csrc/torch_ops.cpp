@@ -2317,6 +2317,121 @@ Tensor gatv2_spmm16(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tens
    return Gatv2Spmm16::apply(rowptr, col, colptr, row_t, x, y, att, heads, negative_slope)[0];
 }
 
+// ---- sparse multi-head attention (q, k, v) for bf16 / fp16 operands (isplib_qkv16_*_hip) ----------
+// q, k and v go in as they lie, z, dq, dk and dv come back in their dtype; lse and D stay fp32: no fp32 [*, K] tensor in either
+// direction.  Saved for backward: the structure, q, k, v and lse -- NOT z: the rows kernel forms D[i,h] from the row's edges -- and
+// nothing of length nnz.  Operands with unit column stride go in at their own even pitch (the three column blocks of one fused 16-bit
+// [rows, 3K] projection are not copied); anything else is made contiguous.  Every shape, dtype, device and domain check comes before
+// a launch.
+static AttnOperand mha16_operand(const Tensor &src, const char *name, int64_t rows, int64_t k, int64_t heads, at::ScalarType dtype) {
+   TORCH_CHECK(src.defined() && src.scalar_type() == dtype, "isplib: mha_spmm16: `", name, "` must be ", dtype, " (q, k and v of one "
+               "16-bit dtype), got ", src.defined() ? src.scalar_type() : at::ScalarType::Undefined);
+   TORCH_CHECK(src.is_cuda(), "isplib: mha_spmm16: `", name, "` must be a GPU tensor -- there is no CPU path");
+   TORCH_CHECK(src.dim() == 2 && src.size(0) == rows && src.size(1) == k, "isplib: mha_spmm16: `", name, "` must be [", rows, ", ", k,
+               "], got ", src.sizes());
+   if (rows == 0 || k == 0) return {src, std::max<int64_t>(k, 1)};
+   const int64_t ld = rows > 1 ? src.stride(0) : k;
+   const bool as_is = src.stride(1) == 1 && ld >= k && ((uintptr_t)src.data_ptr() & 3) == 0 && isplib_qkv16_serves(rows, heads, k / heads, ld);
+   if (as_is) return {src, ld};
+   return {src.clone(at::MemoryFormat::Contiguous), k};
+}
+
+class MhaSpmm16 : public torch::autograd::Function<MhaSpmm16> {
+ public:
+   static variable_list forward(AutogradContext *ctx, Variable rowptr, Variable col, Variable colptr, Variable row_t, Variable q, Variable k,
+                                Variable v, int64_t heads, double scale) {
+      check_index(rowptr, "rowptr"); check_index(col, "col"); check_index(colptr, "colptr"); check_index(row_t, "row_t");
+      TORCH_CHECK(q.defined() && q.dim() == 2 && k.defined() && k.dim() == 2 && v.defined() && v.dim() == 2,
+                  "isplib: mha_spmm16 needs 2-D `q` [M, heads * d], `k` and `v` [N, heads * d]");
+      TORCH_CHECK(is_half(q), "isplib: mha_spmm16: `q` must be bfloat16 or float16, got ", q.scalar_type(), " (float32: mha_spmm)");
+      OpTimer timer("FUSEDMM_MHA_FW", q);
+      const int64_t M = rowptr.numel() - 1, N = colptr.numel() - 1, K = q.size(1), nnz = col.numel();
+      TORCH_CHECK(M >= 0 && N >= 0 && row_t.numel() == nnz, "isplib: mha_spmm16: `rowptr` / `colptr` need one entry more than rows / "
+                                                             "columns, `row_t` one entry per stored entry");
+      TORCH_CHECK(heads >= 1 && K % heads == 0, "isplib: mha_spmm16: the width of `q` (", K, ") must be heads * d, got heads = ", heads);
+      TORCH_CHECK(std::isfinite(scale), "isplib: mha_spmm16: `scale` must be a finite number, got ", scale);
+      const at::ScalarType dt = q.scalar_type();
+      const AttnOperand qo = mha16_operand(q, "q", M, K, heads, dt), ko = mha16_operand(k, "k", N, K, heads, dt),
+                        vo = mha16_operand(v, "v", N, K, heads, dt);
+      for (const Tensor *t : {&rowptr, &col, &colptr, &row_t, &k, &v})
+         TORCH_CHECK(t->device() == q.device(), "isplib: mha_spmm16: every operand must be on q's device");
+      TORCH_CHECK(K == 0 || (isplib_qkv16_serves(N, heads, K / heads, ko.ld) && isplib_qkv16_serves(N, heads, K / heads, vo.ld) &&
+                             qo.ld % 2 == 0),
+                  "isplib: mha_spmm16: outside isplib_qkv16_serves (", ISPLIB_GAT16_K_MIN, " <= heads * d <= ", ISPLIB_GAT16_K_MAX,
+                  ", heads == 1 with d even or d a power of two >= 8, N < 2^31, N * pitch * 2 <= 3.5 GiB): N = ", N, ", heads = ", heads,
+                  ", d = ", K / heads, ", pitches = ", ko.ld, ", ", vo.ld);
+      c10::DeviceGuard guard(q.device());
+      const int code = dt == at::kBFloat16 ? ISPLIB_DTYPE_BF16 : ISPLIB_DTYPE_F16;
+      const Tensor rp = rowptr.contiguous(), cl = col.contiguous();
+      Tensor z = at::empty({M, K}, q.options()), lse = at::empty({M, heads}, q.options().dtype(at::kFloat));
+      if (M > 0 && K > 0) {
+         const int st = isplib_qkv16_csr_hip(code, M, N, K, nnz, cl.data_ptr<int64_t>(), rp.data_ptr<int64_t>(), rp.data_ptr<int64_t>() + 1,
+                                             heads, (float)scale, qo.t.data_ptr(), qo.ld, nnz > 0 ? ko.t.data_ptr() : nullptr, ko.ld,
+                                             nnz > 0 ? vo.t.data_ptr() : nullptr, vo.ld, z.data_ptr(), K, lse.data_ptr<float>(),
+                                             current_stream(q));
+         check_status(st, "isplib_qkv16_csr_hip");
+      } else if (M > 0) {
+         lse.fill_(-std::numeric_limits<float>::infinity());
+      }
+      ctx->saved_data["heads"] = heads;
+      ctx->saved_data["scale"] = scale;
+      ctx->save_for_backward({rp, cl, colptr, row_t, q, k, v, lse});
+      return {z};
+   }
+
+   static variable_list backward(AutogradContext *ctx, variable_list grad_outs) {
+      OpTimer timer("FUSEDMM_MHA_BW", grad_outs[0]);
+      const bool need_q = ctx->needs_input_grad(4), need_k = ctx->needs_input_grad(5), need_v = ctx->needs_input_grad(6);
+      auto grad_q = Variable(), grad_k = Variable(), grad_v = Variable();
+      if (need_q || need_k || need_v) {
+         auto saved = ctx->get_saved_variables();
+         auto rp = saved[0], cl = saved[1], colptr = saved[2].contiguous(), row_t = saved[3].contiguous(), q = saved[4], k = saved[5], v = saved[6],
+              lse = saved[7];
+         const int64_t heads = ctx->saved_data["heads"].toInt();
+         const float p = (float)ctx->saved_data["scale"].toDouble();
+         const int64_t M = rp.numel() - 1, N = colptr.numel() - 1, K = q.size(1), nnz = cl.numel();
+         const at::ScalarType dt = q.scalar_type();
+         const AttnOperand qo = mha16_operand(q, "q", M, K, heads, dt), ko = mha16_operand(k, "k", N, K, heads, dt),
+                           vo = mha16_operand(v, "v", N, K, heads, dt);
+         const AttnOperand go = mha16_operand(grad_outs[0].to(dt), "grad_out", M, K, heads, dt);   // a grad of another dtype is cast to q's
+         c10::DeviceGuard guard(q.device());
+         const int code = dt == at::kBFloat16 ? ISPLIB_DTYPE_BF16 : ISPLIB_DTYPE_F16;
+         // the rows kernel always runs: its D[i,h] feeds the columns kernel; the columns kernel only when k or v asks
+         Tensor dq = at::empty({M, K}, q.options()), dsum = at::empty({M, heads}, q.options().dtype(at::kFloat));
+         if (M > 0 && K > 0) {
+            const int st = isplib_qkv16_bw_rows_hip(code, M, N, K, nnz, cl.data_ptr<int64_t>(), rp.data_ptr<int64_t>(),
+                                                    rp.data_ptr<int64_t>() + 1, heads, p, qo.t.data_ptr(), qo.ld,
+                                                    nnz > 0 ? ko.t.data_ptr() : nullptr, ko.ld, nnz > 0 ? vo.t.data_ptr() : nullptr, vo.ld,
+                                                    go.t.data_ptr(), go.ld, lse.data_ptr<float>(), dq.data_ptr(), K, dsum.data_ptr<float>(),
+                                                    current_stream(q));
+            check_status(st, "isplib_qkv16_bw_rows_hip");
+         }
+         if (need_q) grad_q = dq;
+         if (need_k || need_v) {
+            TORCH_CHECK(K == 0 || (isplib_qkv16_serves(M, heads, K / heads, qo.ld) && isplib_qkv16_serves(M, heads, K / heads, go.ld)),
+                        "isplib: mha_spmm16 backward: outside isplib_qkv16_serves for the gathered rows of q and of the gradient: M = ", M,
+                        ", K = ", K);
+            Tensor dk = at::empty({N, K}, q.options()), dv = at::empty({N, K}, q.options());
+            if (N > 0 && K > 0) {
+               const int st = isplib_qkv16_bw_cols_hip(code, M, N, K, nnz, row_t.data_ptr<int64_t>(), colptr.data_ptr<int64_t>(),
+                                                       colptr.data_ptr<int64_t>() + 1, heads, p, nnz > 0 ? qo.t.data_ptr() : nullptr, qo.ld,
+                                                       nnz > 0 ? go.t.data_ptr() : nullptr, go.ld, lse.data_ptr<float>(),
+                                                       dsum.data_ptr<float>(), ko.t.data_ptr(), ko.ld, vo.t.data_ptr(), vo.ld, dk.data_ptr(), K,
+                                                       dv.data_ptr(), K, current_stream(q));
+               check_status(st, "isplib_qkv16_bw_cols_hip");
+            }
+            if (need_k) grad_k = dk;
+            if (need_v) grad_v = dv;
+         }
+      }
+      return {Variable(), Variable(), Variable(), Variable(), grad_q, grad_k, grad_v, Variable(), Variable()};
+   }
+};
+
+Tensor mha_spmm16(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor q, Tensor k, Tensor v, int64_t heads, double scale) {
+   return MhaSpmm16::apply(rowptr, col, colptr, row_t, q, k, v, heads, scale)[0];
+}
+
 // introspection / housekeeping of the per-graph handle cache of the reference-schema operators
 int64_t graph_cache_size() {
    std::lock_guard<std::mutex> lock(g_graph_mutex);
@@ -2382,4 +2497,5 @@ TORCH_LIBRARY(isplib, m) {
    m.def("gatv2_spmm16(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor x, Tensor y, Tensor att, int heads, float negative_slope) -> Tensor",
          &gatv2_spmm16);
    m.def("mha_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor q, Tensor k, Tensor v, int heads, float scale) -> Tensor", &mha_spmm);
+   m.def("mha_spmm16(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor q, Tensor k, Tensor v, int heads, float scale) -> Tensor", &mha_spmm16);
 }

@@ -29,7 +29,8 @@ gradient of a 16-bit sum / mean (rows16_da_route), ISPLIB_HALF_GCN=convert|nativ
 (rows16_gcn_route; unset: such a call raises, as it always did), ISPLIB_HALF_ATTENTION=convert|native|auto for attention_matmul on
 16-bit operands (attention16_route; unset: such a call raises, as it always did), ISPLIB_HALF_GAT=convert|native|auto for gat_matmul on
 a 16-bit `y` (gat16_route; unset: such a call raises, as it always did), ISPLIB_HALF_GATV2=convert|native|auto for gatv2_matmul on
-16-bit `x` and `y` (gatv2_16_route; unset: such a call raises, as it always did); the first three default to convert;
+16-bit `x` and `y` (gatv2_16_route; unset: such a call raises, as it always did), ISPLIB_HALF_MHA=convert|native|auto for mha_matmul
+on 16-bit `q`, `k` and `v` (mha16_route; unset: such a call raises, as it always did); the first three default to convert;
 ISPLIB_TUNE_FILE names a tuning table to load at import; ISPLIB_DEBUG=1 prints per-operator device times.
 """
 from __future__ import annotations
@@ -481,6 +482,38 @@ def gatv2_16_route(dtype, heads: int, d: int, pitch: int, n: int, mode: Optional
     else:
         return "convert"
     return "gatv2_16" if mode == "native" or cabi.gatv2_16_native_pays(n, ld) else "convert"
+
+
+def mha16_route(dtype, heads: int, d: int, pitch: int, n: int, mode: Optional[str] = None) -> str:
+    """Which way mha_matmul with 16-bit `q`, `k` and `v` goes once ISPLIB_HALF_MHA is set, asked per GATHERED wide operand (k and v with
+    their rows for the forward and the rows kernel; q with its rows and the gradient with its rows, packed, for the backward over the
+    columns): "mha16" (torch.ops.isplib.mha_spmm16 on the 16-bit kernels, isplib_qkv16_*_hip: q, k, v and the gradients as they lie,
+    half the gathered bytes, no fp32 [*, K] tensor in either direction) or "convert" (`.float()` -> the fp32 operator ->
+    `.to(dtype)`).  A pure function -- no device, no library call:
+      * mha16 needs bf16 / fp16 and the operand's shape, [n, heads * d] at its own row pitch or, failing that, packed, inside the
+        entries' domain (cabi.mha16_serves = gat16_serves: 8 <= heads * d <= 512, heads == 1 with d even or d a power of two >= 8,
+        the pitch even);
+      * `mode` is ISPLIB_HALF_MHA (None: read from the environment; unset counts as "convert" here -- mha_matmul itself raises before
+        it asks -- and ISPLIB_HALF=convert wins over it): "convert" always converts, "native" takes the kernels wherever the above
+        holds, "auto" only in the classes -- the gathered operand beyond 256 MiB or not -- where every native run measured faster than
+        every run of the conversion route (cabi.mha16_native_pays, profiles/mha16_ab.txt).  Nothing raises."""
+    if dtype not in HALF_DTYPES:
+        return "convert"
+    from . import cabi
+    if mode is None:
+        mode = os.environ.get("ISPLIB_HALF", "auto")
+        if mode != "convert":
+            mode = os.environ.get("ISPLIB_HALF_MHA", "convert")
+    if mode not in ("native", "auto"):
+        return "convert"
+    k = heads * d
+    if cabi.mha16_serves(n, heads, d, pitch):
+        ld = pitch
+    elif cabi.mha16_serves(n, heads, d, k):
+        ld = k
+    else:
+        return "convert"
+    return "mha16" if mode == "native" or cabi.mha16_native_pays(n, ld) else "convert"
 
 
 _ROWS16_MARK = torch.tensor([16], dtype=torch.int32)      # second tensor of a 16-bit row plan (torch_ops.cpp: is_rows16_plan)
@@ -1110,15 +1143,27 @@ def mha_matmul(src, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: in
     three may be column views of one fused ``[rows, 3 * K]`` projection: operands with unit column stride go in at their own pitch,
     without a copy.  ``k is v`` is allowed; the one tensor's gradient receives both parts.  The stored values of `src` are not read;
     every stored entry is its own edge; an empty row gives 0.  The backward keeps q, k, v, z and one scalar per row and head -- nothing
-    per edge.  fp32 only (bf16 / fp16 operands raise TypeError) and there is no fallback route: outside isplib_mha_serves
+    per edge.  fp32 only by default (bf16 / fp16 operands raise TypeError) and there is no fallback route: outside isplib_mha_serves
     (= isplib_gat_serves: heads * d <= 512; heads == 1 or d a power of two >= 4) the call raises ValueError.  Not part of the operator:
-    attention dropout, TransformerConv's edge features, its root weight and its beta gate (dense operations outside the aggregation)."""
+    attention dropout, TransformerConv's edge features, its root weight and its beta gate (dense operations outside the aggregation).
+    bf16 / fp16 `q`, `k` and `v` (all three of one dtype) are opt-in through the multi-head variable of the module docstring
+    (convert|native|auto): once it is set the call goes where mha16_route says -- the 16-bit operator (torch.ops.isplib.mha_spmm16,
+    which keeps q, k, v and lse for its backward and no z; column views of one fused 16-bit projection go in at their own even pitch)
+    where ALL four gathered operands are admitted (k and v with their rows, q with its rows, the gradient with M rows at pitch K), else
+    `.float()` -> this function -> `.to(dtype)`, which raises only what the fp32 call raises.  ``k is v`` works on both routes.  fp32
+    calls do not read the variable."""
     from . import cabi
     for name, t in (("q", q), ("k", k), ("v", v)):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"isplib_amd: `{name}` must be a tensor, got {type(t).__name__}")
-        if t.dtype != torch.float32:
+    half = any(t.dtype in HALF_DTYPES for t in (q, k, v)) and os.environ.get("ISPLIB_HALF_MHA") is not None
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if half and (t.dtype not in HALF_DTYPES or t.dtype != q.dtype):
+            raise TypeError(f"isplib_amd: `q`, `k` and `v` must share one 16-bit dtype, got {q.dtype}, {k.dtype} and {v.dtype}")
+        if not half and t.dtype != torch.float32:
             raise TypeError(f"isplib_amd: `{name}` must be float32, got {t.dtype} (the multi-head attention operator is fp32 only)")
+    if half:
+        return _mha_matmul16(src, q, k, v, heads, scale)
     if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
         raise ValueError(f"isplib_amd: `heads` must be a positive int, got {heads!r}")
     if q.dim() != 2 or k.dim() != 2 or v.dim() != 2:
@@ -1157,6 +1202,33 @@ def mha_matmul(src, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: in
         raise ValueError("isplib_amd: `q`, `k`, `v` and the sparse matrix must be on one device")
     p = float(scale) if scale is not None else 1.0 / math.sqrt(d)
     return torch.ops.isplib.mha_spmm(st._rowptr, st._col, st.colptr(), st.row_t(), q, k, v, heads, p)
+
+
+def _mha_matmul16(src, q, k, v, heads, scale):
+    """mha_matmul for bf16 / fp16 `q`, `k` and `v` under ISPLIB_HALF_MHA: the 16-bit operator where mha16_route admits ALL four gathered
+    operands (k and v by the forward and the rows kernel; q and the gradient -- M rows, packed -- by the columns kernel), else the
+    conversion route.  `k is v`: on both routes the one tensor's gradient receives dk + dv."""
+    native = False
+    if (isinstance(heads, int) and not isinstance(heads, bool) and heads >= 1 and q.dim() == 2 and k.dim() == 2 and v.dim() == 2 and
+            k.size(1) == q.size(1) and v.size(1) == q.size(1) and q.size(1) % heads == 0 and q.is_cuda and k.is_cuda and v.is_cuda and
+            (scale is None or (not isinstance(scale, bool) and isinstance(scale, (int, float)) and math.isfinite(scale)))):
+        st = _storage_of(src, k)
+        m_rows, n_cols, kk = st._rowptr.numel() - 1, st._sparse_sizes[1], q.size(1)
+        d = kk // heads
+
+        def pitch(t, rows):
+            return t.stride(0) if rows > 1 and t.stride(1) == 1 and t.stride(0) >= kk else kk
+
+        native = (q.size(0) == m_rows and k.size(0) == n_cols and v.size(0) == n_cols and
+                  all(mha16_route(q.dtype, heads, d, ld, rows) == "mha16"
+                      for rows, ld in ((n_cols, pitch(k, n_cols)), (n_cols, pitch(v, n_cols)), (m_rows, pitch(q, m_rows)), (m_rows, kk))))
+    if not native:
+        kf = k.float()
+        return mha_matmul(src, q.float(), kf, kf if v is k else v.float(), heads, scale).to(q.dtype)
+    if k.device != q.device or v.device != q.device or st._rowptr.device != q.device:
+        raise ValueError("isplib_amd: `q`, `k`, `v` and the sparse matrix must be on one device")
+    p = float(scale) if scale is not None else 1.0 / math.sqrt(d)
+    return torch.ops.isplib.mha_spmm16(st._rowptr, st._col, st.colptr(), st.row_t(), q, k, v, heads, p)
 
 
 def _gatv2_matmul16(src, x, att, y, heads, negative_slope):

@@ -363,6 +363,7 @@ class SparseTensor:
 
     def mha_matmul(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int = 1, scale: Optional[float] = None) -> torch.Tensor:
         """Sparse multi-head dot-product attention with separate keys and values over this matrix's stored entries, all heads in one
-        launch (plugin.mha_matmul): q [M, heads * d], k and v [N, heads * d]; `scale` None: 1 / sqrt(d)."""
+        launch (plugin.mha_matmul): q [M, heads * d], k and v [N, heads * d]; `scale` None: 1 / sqrt(d).  bf16 / fp16
+        operands are opt-in through ISPLIB_HALF_MHA."""
         from .plugin import mha_matmul
         return mha_matmul(self, q, k, v, heads, scale)
