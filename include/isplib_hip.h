@@ -1406,6 +1406,10 @@ void isplib_graph_destroy(isplib_graph *g);
  * its own */
 #include "isplib_hip_mha.h"
 
+/* the same attention with attention dropout, fp32 (isplib_qkv_drop_*): part of this interface, declared in a file of its own, beside
+ * the entries it extends */
+#include "isplib_hip_mha_drop.h"
+
 /* the same attention for bf16 / fp16 operands (isplib_qkv16_*): part of this interface, declared in a file of its own */
 #include "isplib_hip_mha16.h"
 

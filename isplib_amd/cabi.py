@@ -308,6 +308,11 @@ MHA_EXPORTS = ("isplib_mha_csr_hip", "isplib_mha_bw_rows_hip", "isplib_mha_bw_co
 # include/isplib_hip_mha16.h (which isplib_hip.h includes; the same library): the 16-bit multi-head attention entries.  Their prefix is
 # isplib_qkv16_ because the symbols that start with isplib_mha are pinned to MHA_EXPORTS; tests/test_mha16_host.py compares this list
 # with that header and the library's symbols
+# include/isplib_hip_mha_drop.h (which isplib_hip.h includes; the same library): the fp32 multi-head attention entries with attention
+# dropout.  Their prefix is isplib_qkv_drop_ because the symbols that start with isplib_mha and isplib_qkv16 are pinned to the two lists
+# around this one; tests/test_mha_dropout_host.py compares this list with the header and the library
+MHA_DROP_EXPORTS = ("isplib_qkv_drop_csr_hip", "isplib_qkv_drop_bw_rows_hip", "isplib_qkv_drop_bw_cols_hip")
+
 MHA16_EXPORTS = ("isplib_qkv16_csr_hip", "isplib_qkv16_bw_rows_hip", "isplib_qkv16_bw_cols_hip", "isplib_qkv16_domain", "isplib_qkv16_auto")
 
 # the two host functions of the dropout keep bit (isplib_hip.h declares them; they return uint32_t, not a status, and are listed apart)
@@ -640,6 +645,14 @@ def lib() -> ctypes.CDLL:
         L.isplib_qkv16_auto.argtypes = [_i64, _i64]
         L.isplib_qkv16_csr_hip.restype = ctypes.c_int
         L.isplib_qkv16_csr_hip.argtypes = [ctypes.c_int] + L.isplib_mha_csr_hip.argtypes
+        # the isplib_mha_* argument lists (the columns entry with csr2csc after cole), then threshold, keep_scale, seed
+        L.isplib_qkv_drop_csr_hip.restype = ctypes.c_int
+        L.isplib_qkv_drop_csr_hip.argtypes = L.isplib_mha_csr_hip.argtypes + _drop
+        L.isplib_qkv_drop_bw_rows_hip.restype = ctypes.c_int
+        L.isplib_qkv_drop_bw_rows_hip.argtypes = L.isplib_mha_bw_rows_hip.argtypes + _drop
+        L.isplib_qkv_drop_bw_cols_hip.restype = ctypes.c_int
+        L.isplib_qkv_drop_bw_cols_hip.argtypes = (L.isplib_mha_bw_cols_hip.argtypes[:7] + [_vp] + L.isplib_mha_bw_cols_hip.argtypes[7:] +
+                                                  _drop)
         L.isplib_qkv16_bw_rows_hip.restype = ctypes.c_int
         L.isplib_qkv16_bw_rows_hip.argtypes = [ctypes.c_int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _f32, _vp, _i64, _vp, _i64, _vp, _i64,
                                                _vp, _i64, _vp, _vp, _i64, _vp, _vp]
@@ -2757,6 +2770,18 @@ def mha(rowptr, col, q, k, v, heads: int = 1, scale: Optional[float] = None, *, 
     [m, heads * d], `k` and `v` [n, heads * d] float32 (row-strided views keep their pitch: column views of one fused projection go in
     without a copy); `scale` None: 1 / sqrt(d); `out` = (z, lse) to write in place.  Every operand is checked BEFORE the call
     (`check`: also the two checks that read the structure on the device)."""
+    return _mha_forward(rowptr, col, q, k, v, heads, scale, out, check, None)
+
+
+def _mha_drop_args(threshold, keep_scale, seed):
+    """(threshold, keep_scale, seed) of the isplib_qkv_drop_* entries, checked: the ranges of `_gat_drop_args`, under this family's names."""
+    if isinstance(keep_scale, bool) or not isinstance(keep_scale, (int, float)) or not 0.0 < float(keep_scale) < float("inf"):
+        raise ValueError(f"isplib_amd: `keep_scale` must be a positive finite number, got {keep_scale!r}")
+    return _gat_drop_args(threshold, keep_scale, seed)
+
+
+def _mha_forward(rowptr, col, q, k, v, heads, scale, out, check, drop):
+    """`mha` (drop None) and `mha_drop` (drop = (threshold, keep_scale, seed), checked): one set of operand checks, all before the call."""
     if not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1 or rowptr.numel() < 1:
         raise ValueError("isplib_amd: `rowptr` (m + 1 entries) must be a 1-D tensor")
     m = rowptr.numel() - 1
@@ -2764,6 +2789,8 @@ def mha(rowptr, col, q, k, v, heads: int = 1, scale: Optional[float] = None, *, 
     d = _gat_heads(heads, kk)
     p = _mha_scale(scale, d)
     rowptr, col = _attn_structure(rowptr, col, "rowptr", "col", n, check)
+    if drop is not None:
+        _gatv2_nnz(col.numel())
     if out is not None:
         z, lse = out
         ldz = _attn_dense(z, "out[0]", m, kk, "z")
@@ -2780,17 +2807,31 @@ def mha(rowptr, col, q, k, v, heads: int = 1, scale: Optional[float] = None, *, 
             lse.fill_(float("-inf"))
         return z, lse
     rp = rowptr.data_ptr()
+    entry = "isplib_mha_csr_hip" if drop is None else "isplib_qkv_drop_csr_hip"
     with torch.cuda.device(q.device):
-        st = lib().isplib_mha_csr_hip(m, n, kk, col.numel(), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8), heads, p, _ptr(q), ldq,
-                                      _ptr(k), ldk, _ptr(v), ldv, _ptr(z), ldz, _ptr(lse), _stream(q.device))
-    _check(st, "isplib_mha_csr_hip")
+        st = getattr(lib(), entry)(m, n, kk, col.numel(), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8), heads, p, _ptr(q), ldq,
+                                   _ptr(k), ldk, _ptr(v), ldv, _ptr(z), ldz, _ptr(lse), _stream(q.device), *(drop or ()))
+    _check(st, entry)
     return z, lse
+
+
+def mha_drop(rowptr, col, q, k, v, threshold: int, keep_scale: float, seed: int, heads: int = 1, scale: Optional[float] = None, *,
+             out=None, check: bool = True):
+    """`mha` with attention dropout (isplib_qkv_drop_csr_hip): entry e (its position in `col`) and head h are kept where
+    gat_drop_word(seed, e, h) >= threshold -- the keep bit of `gat_drop` and `gatv2_drop` -- and z is scaled by `keep_scale`; lse is
+    that of the call without dropout.  Returns (z, lse); the operand checks are mha's, and nnz < 2^31."""
+    return _mha_forward(rowptr, col, q, k, v, heads, scale, out, check, _mha_drop_args(threshold, keep_scale, seed))
 
 
 def mha_bw_rows(rowptr, col, q, k, v, g, z, lse, heads: int = 1, scale: Optional[float] = None, *, out=None, check: bool = True):
     """The backward of `mha` over the rows (isplib_mha_bw_rows_hip): for g = dL/dz [m, heads * d] and the forward's z and lse,
     D[i,h] = <g_i, z_i>_h, ds_e = a_e (<g_i, v_j>_h - D[i,h]) with a_e recomputed from lse, dq_i[head h] = scale sum_e ds_e k_j[head h].
     Returns (dq [m, heads * d], D [m, heads]); an empty row has dq_i = 0 and D = 0.  `out` = (dq, D); the operand checks are mha's."""
+    return _mha_backward_rows(rowptr, col, q, k, v, g, z, lse, heads, scale, out, check, None)
+
+
+def _mha_backward_rows(rowptr, col, q, k, v, g, z, lse, heads, scale, out, check, drop):
+    """`mha_bw_rows` (drop None) and `mha_drop_bw_rows` (drop = (threshold, keep_scale, seed), checked)."""
     if not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1 or rowptr.numel() < 1:
         raise ValueError("isplib_amd: `rowptr` (m + 1 entries) must be a 1-D tensor")
     m = rowptr.numel() - 1
@@ -2801,6 +2842,8 @@ def mha_bw_rows(rowptr, col, q, k, v, g, z, lse, heads: int = 1, scale: Optional
     ldz = _attn_dense(z, "z", m, kk, "the forward's output")
     _gat_table(lse, "lse", m, heads)
     rowptr, col = _attn_structure(rowptr, col, "rowptr", "col", n, check)
+    if drop is not None:
+        _gatv2_nnz(col.numel())
     if out is not None:
         if len(out) != 2:
             raise ValueError("isplib_amd: `out` must be (dq, D)")
@@ -2818,12 +2861,20 @@ def mha_bw_rows(rowptr, col, q, k, v, g, z, lse, heads: int = 1, scale: Optional
             dsum.zero_()
         return dq, dsum
     rp = rowptr.data_ptr()
+    entry = "isplib_mha_bw_rows_hip" if drop is None else "isplib_qkv_drop_bw_rows_hip"
     with torch.cuda.device(q.device):
-        st = lib().isplib_mha_bw_rows_hip(m, n, kk, col.numel(), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8), heads, p, _ptr(q),
-                                          ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(g), ldg, _ptr(z), ldz, _ptr(lse), _ptr(dq), lddq, _ptr(dsum),
-                                          _stream(q.device))
-    _check(st, "isplib_mha_bw_rows_hip")
+        st = getattr(lib(), entry)(m, n, kk, col.numel(), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8), heads, p, _ptr(q), ldq,
+                                   _ptr(k), ldk, _ptr(v), ldv, _ptr(g), ldg, _ptr(z), ldz, _ptr(lse), _ptr(dq), lddq, _ptr(dsum),
+                                   _stream(q.device), *(drop or ()))
+    _check(st, entry)
     return dq, dsum
+
+
+def mha_drop_bw_rows(rowptr, col, q, k, v, g, z, lse, threshold: int, keep_scale: float, seed: int, heads: int = 1,
+                     scale: Optional[float] = None, *, out=None, check: bool = True):
+    """The backward of `mha_drop` over the rows (isplib_qkv_drop_bw_rows_hip), with the mask of the same (threshold, seed):
+    t_e = q_e keep_scale <g_i, v_j>_h, everything else as `mha_bw_rows` (z is the forward's, under the mask).  Returns (dq, D)."""
+    return _mha_backward_rows(rowptr, col, q, k, v, g, z, lse, heads, scale, out, check, _mha_drop_args(threshold, keep_scale, seed))
 
 
 def mha_bw_cols(colptr, row_t, q, k, v, g, lse, dsum, heads: int = 1, scale: Optional[float] = None, *, out=None, check: bool = True):
@@ -2831,6 +2882,11 @@ def mha_bw_cols(colptr, row_t, q, k, v, g, lse, dsum, heads: int = 1, scale: Opt
     ids of the entries in column-major order): dk_j[head h] = scale sum over the entries e = (i, j) of column j of ds_e q_i[head h] and
     dv_j[head h] = sum of a_e g_i[head h], with `lse` of the forward and `dsum` = D of mha_bw_rows.  Returns (dk, dv), both
     [n, heads * d]; a column no entry points at has 0 in both.  `out` = (dk, dv); the operand checks are mha's."""
+    return _mha_backward_cols(colptr, row_t, None, q, k, v, g, lse, dsum, heads, scale, out, check, None)
+
+
+def _mha_backward_cols(colptr, row_t, csr2csc, q, k, v, g, lse, dsum, heads, scale, out, check, drop):
+    """`mha_bw_cols` (drop None, no csr2csc) and `mha_drop_bw_cols` (drop = (threshold, keep_scale, seed), checked; csr2csc required)."""
     if not isinstance(colptr, torch.Tensor) or colptr.dim() != 1 or colptr.numel() < 1:
         raise ValueError("isplib_amd: `colptr` (n + 1 entries) must be a 1-D tensor")
     n = colptr.numel() - 1
@@ -2847,6 +2903,9 @@ def mha_bw_cols(colptr, row_t, q, k, v, g, lse, dsum, heads: int = 1, scale: Opt
     _gat_table(lse, "lse", m, heads)
     _gat_table(dsum, "dsum", m, heads)
     colptr, row_t = _attn_structure(colptr, row_t, "colptr", "row_t", m, check)
+    if drop is not None:
+        _gatv2_nnz(row_t.numel())
+        csr2csc = _gat_edge_positions(csr2csc, row_t.numel(), check)
     if out is not None:
         if len(out) != 2:
             raise ValueError("isplib_amd: `out` must be (dk, dv)")
@@ -2854,7 +2913,7 @@ def mha_bw_cols(colptr, row_t, q, k, v, g, lse, dsum, heads: int = 1, scale: Opt
         lddv = _attn_dense(out[1], "out[1]", n, kk, "dv")
     _mha_domain(m, heads, d, (ldq, ldg))
     _same_gpu((("q", q), ("k", k), ("v", v), ("g", g), ("lse", lse), ("dsum", dsum), ("colptr", colptr), ("row_t", row_t)) +
-              ((("out[0]", out[0]), ("out[1]", out[1])) if out is not None else ()))
+              ((("out[0]", out[0]), ("out[1]", out[1])) if out is not None else ()) + ((("csr2csc", csr2csc),) if drop is not None else ()))
     if out is None:
         out = (torch.empty((n, kk), dtype=torch.float32, device=k.device), torch.empty((n, kk), dtype=torch.float32, device=k.device))
         lddk = lddv = max(kk, 1)
@@ -2862,12 +2921,23 @@ def mha_bw_cols(colptr, row_t, q, k, v, g, lse, dsum, heads: int = 1, scale: Opt
     if n == 0 or kk == 0:
         return dk, dv
     cp = colptr.data_ptr()
+    entry = "isplib_mha_bw_cols_hip" if drop is None else "isplib_qkv_drop_bw_cols_hip"
     with torch.cuda.device(k.device):
-        st = lib().isplib_mha_bw_cols_hip(m, n, kk, row_t.numel(), _ptr(row_t), ctypes.c_void_p(cp), ctypes.c_void_p(cp + 8), heads, p,
-                                          _ptr(q), ldq, _ptr(g), ldg, _ptr(lse), _ptr(dsum), _ptr(k), ldk, _ptr(v), ldv, _ptr(dk), lddk,
-                                          _ptr(dv), lddv, _stream(k.device))
-    _check(st, "isplib_mha_bw_cols_hip")
+        st = getattr(lib(), entry)(m, n, kk, row_t.numel(), _ptr(row_t), ctypes.c_void_p(cp), ctypes.c_void_p(cp + 8),
+                                   *((_ptr(csr2csc),) if drop is not None else ()), heads, p, _ptr(q), ldq, _ptr(g), ldg, _ptr(lse),
+                                   _ptr(dsum), _ptr(k), ldk, _ptr(v), ldv, _ptr(dk), lddk, _ptr(dv), lddv, _stream(k.device),
+                                   *(drop or ()))
+    _check(st, entry)
     return dk, dv
+
+
+def mha_drop_bw_cols(colptr, row_t, csr2csc, q, k, v, g, lse, dsum, threshold: int, keep_scale: float, seed: int, heads: int = 1,
+                     scale: Optional[float] = None, *, out=None, check: bool = True):
+    """The backward of `mha_drop` over the columns (isplib_qkv_drop_bw_cols_hip): dk as `mha_bw_cols` with t_e under the mask, dv_j[head h]
+    = sum over the entries of column j of q_e keep_scale a_e g_i[head h].  `csr2csc` [nnz] int64 is required: the keep bit is a function of
+    the entry's CSR position, and this entry walks the transposed structure.  Returns (dk, dv)."""
+    return _mha_backward_cols(colptr, row_t, csr2csc, q, k, v, g, lse, dsum, heads, scale, out, check,
+                              _mha_drop_args(threshold, keep_scale, seed))
 
 
 def _attn16_dense(t, name: str, rows: int, k: Optional[int], what: str, dtype=None) -> int:

@@ -27,11 +27,24 @@
 // Every gathered table sits behind a buffer descriptor of exactly the extent it owns; dead edges and lanes past k carry BUF_OOB, which
 // the descriptor answers with 0.  No atomics, no LDS, a fixed order of operations: two launches give equal bits.  attention.hip,
 // gat.hip and gatv2.hip are untouched; their small helpers are restated here under names of their own.  DESIGN.md 4.6k.
+//
+// Attention dropout (include/isplib_hip_mha_drop.h: isplib_qkv_drop_*_hip): the three kernels are templates on DROP.
+// Every stored entry e and head h has a keep bit q_e,h = word(seed, CSR position of e, h) >= T (gat_dropout.h: the bit of gat.hip and
+// gatv2.hip, a pure function, recomputed in all three kernels, nothing stored), and with c = float32(1 / (1 - p)):
+//    z_i = c sum_e q_e a_e v_j      t_e = q_e c <g_i, v_j>_h      dv_j = sum_{e -> j} q_e c a_e g_i
+//    a_e, lse, s_e and the form of ds_e unchanged
+// The softmax runs over ALL stored entries: l, m and lse do not see the mask, and a dropped edge still gets ds_e = -a_e D.  The lane that
+// loads an entry's index hashes the entry's position (base + lane in the forward and the rows kernel; csr2csc[pos] in the columns
+// kernel, which walks the transposed structure and therefore takes csr2csc) and hands the word across with the index; per edge and chunk
+// one add of a per-lane constant, one fmix32, one compare and one select remain.  c multiplies the finished row of z and t_e per edge;
+// the value coefficient of dv is q_e ? a_e c : 0 per edge and head.  The seed is a kernel argument: a captured graph replays one mask.
+// DROP = false is the code it was (profiles/mha_dropout_isa.txt).
 #include <cfloat>
 #include <cmath>
 
 #include "common.h"
 #include "gather.h"
+#include "gat_dropout.h"
 
 namespace isplib {
 
@@ -71,6 +84,11 @@ struct MhaArgs {
    unsigned gbbytes;
    const float *t1, *t2;                   // columns: lse, D; both [gathered rows, H]
    unsigned tbytes;
+   // DROP only (appended)
+   const int64_t *epos;                    // columns: csr2csc [nnz], the CSR position of every entry of the transposed structure
+   unsigned seed_lo, seed_hi;              // the two halves of the seed
+   unsigned T;                             // keep: word >= T
+   float c;                                // float32(1 / (1 - p))
 };
 
 template <int LPR, int NCH> struct MhaCols {
@@ -190,7 +208,14 @@ __device__ __forceinline__ unsigned mha_off(int id, unsigned pitch_bytes) {
    return id < 0 ? BUF_OOB : (unsigned)id * pitch_bytes;     // BUF_OOB + cbyte / hbyte (< 2^24) cannot wrap
 }
 
-template <int LPR, int NCH, int WAVES, int U>
+// DROP: the per-lane constant of each chunk's head (gat_dropout.h)
+template <int LPR, int NCH>
+__device__ __forceinline__ void mha_drop_heads(const MhaArgs &a, const MhaCols<LPR, NCH> &cm, unsigned (&hk)[NCH]) {
+#pragma unroll
+   for (int j = 0; j < NCH; j++) hk[j] = gat_drop_head(a.seed_hi, (unsigned)cm.head[j]);
+}
+
+template <int LPR, int NCH, int WAVES, int U, bool DROP>
 __global__ __launch_bounds__(WAVES * 64) void mha_fw_kernel(const MhaArgs a) {
    constexpr int G = 64 / LPR;
    const int lane = threadIdx.x & 63;
@@ -203,6 +228,8 @@ __global__ __launch_bounds__(WAVES * 64) void mha_fw_kernel(const MhaArgs a) {
    const MhaCols<LPR, NCH> cm(a, lc);
    float qv[NCH][4];
    mha_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm, qv);
+   [[maybe_unused]] unsigned hk[NCH];
+   if constexpr (DROP) mha_drop_heads<LPR, NCH>(a, cm, hk);
 
    float mrun[NCH], l[NCH], acc[NCH][4];
 #pragma unroll
@@ -217,16 +244,20 @@ __global__ __launch_bounds__(WAVES * 64) void mha_fw_kernel(const MhaArgs a) {
    for (int64_t base = eb; base < ee; base += 64) {
       const int64_t pos = base + lane;
       const int id_l = pos < ee ? (int)a.indx[pos] : -1;
+      [[maybe_unused]] unsigned hw_l = 0u;               // DROP: the entry's part of the word, handed across lanes like the column id
+      if constexpr (DROP) hw_l = gat_drop_entry(a.seed_lo, (unsigned)pos);
       const int64_t left = ee - base;
       const int cnt = left < 64 ? (int)left : 64;
 #pragma unroll 1
       for (int s0 = 0; s0 < cnt; s0 += G * U) {
          v4i_t kv[U][NCH], vv[U][NCH];
+         [[maybe_unused]] unsigned hw[DROP ? U : 1];
 #pragma unroll
          for (int u = 0; u < U; u++) {
             const int id = __shfl(id_l, (s0 + u * G + g) & 63);
             mha_load_wide<LPR, NCH>(rsk, mha_off(id, ldkb), cm, kv[u]);
             mha_load_wide<LPR, NCH>(rsv, mha_off(id, ldvb), cm, vv[u]);
+            if constexpr (DROP) hw[u] = (unsigned)__shfl((int)hw_l, (s0 + u * G + g) & 63);
          }
          float sc[U][NCH];
 #pragma unroll
@@ -250,9 +281,11 @@ __global__ __launch_bounds__(WAVES * 64) void mha_fw_kernel(const MhaArgs a) {
 #pragma unroll
             for (int u = 0; u < U; u++) {
                const float w = (s0 + u * G + g < cnt) ? __expf(sc[u][j] - mnew) : 0.0f;
-               l[j] += w;
+               l[j] += w;                                 // the softmax runs over every stored entry: the mask reaches the values only
+               float wk = w;
+               if constexpr (DROP) wk = gat_drop_mix(hw[u], hk[j]) >= a.T ? w : 0.0f;
 #pragma unroll
-               for (int v = 0; v < 4; v++) acc[j][v] = fmaf(w, __int_as_float(vv[u][j][v]), acc[j][v]);
+               for (int v = 0; v < 4; v++) acc[j][v] = fmaf(wk, __int_as_float(vv[u][j][v]), acc[j][v]);
             }
          }
       }
@@ -276,14 +309,17 @@ __global__ __launch_bounds__(WAVES * 64) void mha_fw_kernel(const MhaArgs a) {
 #pragma unroll
    for (int j = 0; j < NCH; j++) {
 #pragma unroll
-      for (int v = 0; v < 4; v++) acc[j][v] = empty ? 0.0f : acc[j][v] / l[j];
+      for (int v = 0; v < 4; v++) {
+         acc[j][v] = empty ? 0.0f : acc[j][v] / l[j];
+         if constexpr (DROP) acc[j][v] *= a.c;
+      }
       if (cm.first[j]) a.hout[(size_t)row * (size_t)a.heads + (size_t)cm.head[j]] = empty ? -INFINITY : mrun[j] + logf(l[j]);
    }
    mha_store_row<LPR, NCH>(a.out, row, a.ldout, lc, cm, acc);
 }
 
 // one wave per row i: q_i, g_i and D[i,h] in registers; key_j and v_j gathered
-template <int LPR, int NCH, int WAVES, int U>
+template <int LPR, int NCH, int WAVES, int U, bool DROP>
 __global__ __launch_bounds__(WAVES * 64) void mha_bw_rows_kernel(const MhaArgs a) {
    constexpr int G = 64 / LPR;
    const int lane = threadIdx.x & 63;
@@ -318,21 +354,27 @@ __global__ __launch_bounds__(WAVES * 64) void mha_bw_rows_kernel(const MhaArgs a
    for (int j = 0; j < NCH; j++)
 #pragma unroll
       for (int v = 0; v < 4; v++) acc[j][v] = 0.0f;
+   [[maybe_unused]] unsigned hk[NCH];
+   if constexpr (DROP) mha_drop_heads<LPR, NCH>(a, cm, hk);
 
    const unsigned ldkb = (unsigned)a.ldga * 4u, ldvb = (unsigned)a.ldgb * 4u;
    for (int64_t base = eb; base < ee; base += 64) {
       const int64_t pos = base + lane;
       const int id_l = pos < ee ? (int)a.indx[pos] : -1;
+      [[maybe_unused]] unsigned hw_l = 0u;               // DROP: the entry's part of the word, handed across lanes like the column id
+      if constexpr (DROP) hw_l = gat_drop_entry(a.seed_lo, (unsigned)pos);
       const int64_t left = ee - base;
       const int cnt = left < 64 ? (int)left : 64;
 #pragma unroll 1
       for (int s0 = 0; s0 < cnt; s0 += G * U) {
          v4i_t kv[U][NCH], vv[U][NCH];
+         [[maybe_unused]] unsigned hw[DROP ? U : 1];
 #pragma unroll
          for (int u = 0; u < U; u++) {
             const int id = __shfl(id_l, (s0 + u * G + g) & 63);
             mha_load_wide<LPR, NCH>(rsk, mha_off(id, ldkb), cm, kv[u]);
             mha_load_wide<LPR, NCH>(rsv, mha_off(id, ldvb), cm, vv[u]);
+            if constexpr (DROP) hw[u] = (unsigned)__shfl((int)hw_l, (s0 + u * G + g) & 63);
          }
          float part[2 * U][NCH];                       // <q_i, key_j>_h and t_e of the step through one butterfly
 #pragma unroll
@@ -348,6 +390,7 @@ __global__ __launch_bounds__(WAVES * 64) void mha_bw_rows_kernel(const MhaArgs a
             const bool live = s0 + u * G + g < cnt;
 #pragma unroll
             for (int j = 0; j < NCH; j++) {
+               if constexpr (DROP) part[U + u][j] *= gat_drop_mix(hw[u], hk[j]) >= a.T ? a.c : 0.0f;      // t_e = q_e c <g_i, v_j>_h
                const float ds = live ? __expf(part[u][j] * a.p - lse[j]) * (part[U + u][j] - dsum[j]) : 0.0f;
 #pragma unroll
                for (int v = 0; v < 4; v++) acc[j][v] = fmaf(ds, __int_as_float(kv[u][j][v]), acc[j][v]);
@@ -373,7 +416,7 @@ __global__ __launch_bounds__(WAVES * 64) void mha_bw_rows_kernel(const MhaArgs a
 }
 
 // one wave per column j of A (a row of the transposed structure): key_j and v_j in registers; q_i, g_i and lse, D of [i, head] gathered
-template <int LPR, int NCH, int WAVES, int U>
+template <int LPR, int NCH, int WAVES, int U, bool DROP>
 __global__ __launch_bounds__(WAVES * 64) void mha_bw_cols_kernel(const MhaArgs a) {
    constexpr int G = 64 / LPR;
    const int lane = threadIdx.x & 63;
@@ -394,17 +437,22 @@ __global__ __launch_bounds__(WAVES * 64) void mha_bw_cols_kernel(const MhaArgs a
    for (int j = 0; j < NCH; j++)
 #pragma unroll
       for (int v = 0; v < 4; v++) dk[j][v] = dv[j][v] = 0.0f;
+   [[maybe_unused]] unsigned hk[NCH];
+   if constexpr (DROP) mha_drop_heads<LPR, NCH>(a, cm, hk);
 
    const unsigned ldqb = (unsigned)a.ldga * 4u, ldgb = (unsigned)a.ldgb * 4u, hb = (unsigned)a.heads * 4u;
    for (int64_t base = eb; base < ee; base += 64) {
       const int64_t pos = base + lane;
       const int id_l = pos < ee ? (int)a.indx[pos] : -1;
+      [[maybe_unused]] unsigned hw_l = 0u;               // DROP: the entry's part of the word, of its CSR position (nnz < 2^31)
+      if constexpr (DROP) hw_l = gat_drop_entry(a.seed_lo, pos < ee ? (unsigned)a.epos[pos] : 0u);
       const int64_t left = ee - base;
       const int cnt = left < 64 ? (int)left : 64;
 #pragma unroll 1
       for (int s0 = 0; s0 < cnt; s0 += G * U) {
          v4i_t qg[U][NCH], gg[U][NCH];
          float ls[U][NCH], dd[U][NCH];
+         [[maybe_unused]] unsigned hw[DROP ? U : 1];
 #pragma unroll
          for (int u = 0; u < U; u++) {
             const int id = __shfl(id_l, (s0 + u * G + g) & 63);
@@ -412,6 +460,7 @@ __global__ __launch_bounds__(WAVES * 64) void mha_bw_cols_kernel(const MhaArgs a
             mha_load_wide<LPR, NCH>(rsg, mha_off(id, ldgb), cm, gg[u]);
             mha_load_head<LPR, NCH>(rs1, mha_off(id, hb), cm, ls[u]);
             mha_load_head<LPR, NCH>(rs2, mha_off(id, hb), cm, dd[u]);
+            if constexpr (DROP) hw[u] = (unsigned)__shfl((int)hw_l, (s0 + u * G + g) & 63);
          }
          float part[2 * U][NCH];
 #pragma unroll
@@ -428,11 +477,17 @@ __global__ __launch_bounds__(WAVES * 64) void mha_bw_cols_kernel(const MhaArgs a
 #pragma unroll
             for (int j = 0; j < NCH; j++) {
                const float ae = live ? __expf(part[u][j] * a.p - ls[u][j]) : 0.0f;
+               float aev = ae;                            // the value coefficient: q_e c a_e
+               if constexpr (DROP) {
+                  const bool keep = gat_drop_mix(hw[u], hk[j]) >= a.T;
+                  part[U + u][j] *= keep ? a.c : 0.0f;    // t_e = q_e c <g_i, v_j>_h
+                  aev = keep ? ae * a.c : 0.0f;
+               }
                const float ds = live ? ae * (part[U + u][j] - dd[u][j]) : 0.0f;
 #pragma unroll
                for (int v = 0; v < 4; v++) {
                   dk[j][v] = fmaf(ds, __int_as_float(qg[u][j][v]), dk[j][v]);
-                  dv[j][v] = fmaf(ae, __int_as_float(gg[u][j][v]), dv[j][v]);
+                  dv[j][v] = fmaf(aev, __int_as_float(gg[u][j][v]), dv[j][v]);
                }
             }
          }
@@ -460,26 +515,54 @@ enum { MHA_FW = 0, MHA_BW_ROWS = 1, MHA_BW_COLS = 2 };
 
 // edges of a slot per step: 4 in the forward and the rows kernel; the columns kernel gathers four tables per edge and takes half the
 // edges per step where a lane holds two chunks (profiles/mha_isa.txt: no instantiation uses scratch)
-template <int LPR, int NCH>
+template <int LPR, int NCH, bool DROP>
 static int launch_mha(int which, const MhaArgs &a, const char *entry, hipStream_t st) {
    constexpr int UC = NCH >= 2 ? 2 : 4;
    const int64_t nb = (a.rows + MHA_WAVES - 1) / MHA_WAVES;
    if (nb > 0x7fffffffLL) return fail(ISPLIB_FAIL, entry, "too many rows for one launch");
    const dim3 grid((unsigned)nb), block((unsigned)MHA_WAVES * 64u);
-   if (which == MHA_FW) hipLaunchKernelGGL((mha_fw_kernel<LPR, NCH, MHA_WAVES, 4>), grid, block, 0, st, a);
-   else if (which == MHA_BW_ROWS) hipLaunchKernelGGL((mha_bw_rows_kernel<LPR, NCH, MHA_WAVES, 4>), grid, block, 0, st, a);
-   else hipLaunchKernelGGL((mha_bw_cols_kernel<LPR, NCH, MHA_WAVES, UC>), grid, block, 0, st, a);
+   if (which == MHA_FW) hipLaunchKernelGGL((mha_fw_kernel<LPR, NCH, MHA_WAVES, 4, DROP>), grid, block, 0, st, a);
+   else if (which == MHA_BW_ROWS) hipLaunchKernelGGL((mha_bw_rows_kernel<LPR, NCH, MHA_WAVES, 4, DROP>), grid, block, 0, st, a);
+   else hipLaunchKernelGGL((mha_bw_cols_kernel<LPR, NCH, MHA_WAVES, UC, DROP>), grid, block, 0, st, a);
    return check_launch(entry);
 }
 
-// the width dispatch of gatv2.hip, up to two chunks per lane
-static int mha_by_width(int which, const MhaArgs &a, const char *entry, hipStream_t st) {
+// the width dispatch of gatv2.hip, up to two chunks per lane; DROP: the kernels with attention dropout
+template <bool DROP>
+static int mha_by_width_of(int which, const MhaArgs &a, const char *entry, hipStream_t st) {
    const int64_t w = (a.k + 3) / 4;
-   if (w <= 8) return launch_mha<8, 1>(which, a, entry, st);
-   if (w <= 16) return launch_mha<16, 1>(which, a, entry, st);
-   if (w <= 32) return launch_mha<32, 1>(which, a, entry, st);
-   if (w <= 64) return launch_mha<64, 1>(which, a, entry, st);
-   return launch_mha<64, 2>(which, a, entry, st);
+   if (w <= 8) return launch_mha<8, 1, DROP>(which, a, entry, st);
+   if (w <= 16) return launch_mha<16, 1, DROP>(which, a, entry, st);
+   if (w <= 32) return launch_mha<32, 1, DROP>(which, a, entry, st);
+   if (w <= 64) return launch_mha<64, 1, DROP>(which, a, entry, st);
+   return launch_mha<64, 2, DROP>(which, a, entry, st);
+}
+
+static int mha_by_width(int which, const MhaArgs &a, bool drop, const char *entry, hipStream_t st) {
+   return drop ? mha_by_width_of<true>(which, a, entry, st) : mha_by_width_of<false>(which, a, entry, st);
+}
+
+// the dropout of one call (isplib_qkv_drop_*_hip): the threshold T(p), c = float32(1 / (1 - p)) and the seed; none: the entries without it
+struct MhaDrop {
+   bool on;
+   uint32_t threshold;
+   float keep_scale;
+   uint64_t seed;
+};
+static const MhaDrop MHA_NO_DROP = {false, 0u, 1.0f, 0ull};
+
+// what the dropout entries refuse before a launch: a keep scale that is no positive finite number would poison every row, the keep bit
+// is a function of a position below 2^31 and of a seed below 2^63
+static const char *mha_drop_refusal(const MhaDrop &dr, int64_t nnz) {
+   if (!dr.on) return nullptr;
+   if (!(dr.keep_scale > 0.0f && dr.keep_scale <= FLT_MAX)) return "keep_scale must be a positive finite number";
+   if (nnz >= (1LL << 31)) return "nnz must be below 2^31";
+   if (dr.seed >= (1ull << 63)) return "seed must be below 2^63";
+   return nullptr;
+}
+
+static void mha_set_drop(MhaArgs &a, const MhaDrop &dr) {
+   a.seed_lo = (unsigned)dr.seed; a.seed_hi = (unsigned)(dr.seed >> 32); a.T = dr.threshold; a.c = dr.keep_scale;
 }
 
 // what a descriptor over `rows` rows of k floats at pitch ld may answer: the extent a row-strided view owns, not rows * ld
@@ -511,11 +594,12 @@ extern "C" int isplib_mha_domain(int64_t rows_gathered, int64_t heads, int64_t d
    return isplib_mha_serves(rows_gathered, heads, d, ld);
 }
 
-extern "C" int isplib_mha_csr_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
-                                  const int64_t *pntre, int64_t heads, float scale, const float *q, int64_t ldq, const float *key,
-                                  int64_t ldk, const float *v, int64_t ldv, float *z, int64_t ldz, float *lse, void *stream) {
-   const char *entry = "isplib_mha_csr_hip";
+// The three entries, with and without attention dropout.
+static int mha_forward(const char *entry, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                       const int64_t *pntre, int64_t heads, float scale, const float *q, int64_t ldq, const float *key, int64_t ldk,
+                       const float *v, int64_t ldv, float *z, int64_t ldz, float *lse, void *stream, const MhaDrop &dr = MHA_NO_DROP) {
    clear_error();
+   if (const char *why = mha_drop_refusal(dr, nnz)) return fail(ISPLIB_FAIL, entry, why);
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
    if (!std::isfinite(scale)) return fail(ISPLIB_FAIL, entry, "scale must be a finite number");
    if (m == 0 || k == 0) return ISPLIB_SUCCESS;
@@ -531,15 +615,16 @@ extern "C" int isplib_mha_csr_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, 
    a.out = z; a.ldout = ldz; a.hout = lse;
    a.ga = key; a.ldga = ldk; a.gabytes = nnz > 0 ? mha_extent(n, k, ldk) : 0u;
    a.gb = v; a.ldgb = ldv; a.gbbytes = nnz > 0 ? mha_extent(n, k, ldv) : 0u;
-   return mha_by_width(MHA_FW, a, entry, (hipStream_t)stream);
+   mha_set_drop(a, dr);
+   return mha_by_width(MHA_FW, a, dr.on, entry, (hipStream_t)stream);
 }
 
-extern "C" int isplib_mha_bw_rows_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
-                                      const int64_t *pntre, int64_t heads, float scale, const float *q, int64_t ldq, const float *key,
-                                      int64_t ldk, const float *v, int64_t ldv, const float *g, int64_t ldg, const float *z,
-                                      int64_t ldz, const float *lse, float *dq, int64_t lddq, float *dsum, void *stream) {
-   const char *entry = "isplib_mha_bw_rows_hip";
+static int mha_backward_rows(const char *entry, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                             const int64_t *pntre, int64_t heads, float scale, const float *q, int64_t ldq, const float *key,
+                             int64_t ldk, const float *v, int64_t ldv, const float *g, int64_t ldg, const float *z, int64_t ldz,
+                             const float *lse, float *dq, int64_t lddq, float *dsum, void *stream, const MhaDrop &dr = MHA_NO_DROP) {
    clear_error();
+   if (const char *why = mha_drop_refusal(dr, nnz)) return fail(ISPLIB_FAIL, entry, why);
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
    if (!std::isfinite(scale)) return fail(ISPLIB_FAIL, entry, "scale must be a finite number");
    if (m == 0 || k == 0) return ISPLIB_SUCCESS;
@@ -556,16 +641,19 @@ extern "C" int isplib_mha_bw_rows_hip(int64_t m, int64_t n, int64_t k, int64_t n
    a.out = dq; a.ldout = lddq; a.hout = dsum;
    a.ga = key; a.ldga = ldk; a.gabytes = nnz > 0 ? mha_extent(n, k, ldk) : 0u;
    a.gb = v; a.ldgb = ldv; a.gbbytes = nnz > 0 ? mha_extent(n, k, ldv) : 0u;
-   return mha_by_width(MHA_BW_ROWS, a, entry, (hipStream_t)stream);
+   mha_set_drop(a, dr);
+   return mha_by_width(MHA_BW_ROWS, a, dr.on, entry, (hipStream_t)stream);
 }
 
-extern "C" int isplib_mha_bw_cols_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t, const int64_t *colb,
-                                      const int64_t *cole, int64_t heads, float scale, const float *q, int64_t ldq, const float *g,
-                                      int64_t ldg, const float *lse, const float *dsum, const float *key, int64_t ldk, const float *v,
-                                      int64_t ldv, float *dkey, int64_t lddk, float *dv, int64_t lddv, void *stream) {
-   const char *entry = "isplib_mha_bw_cols_hip";
+static int mha_backward_cols(const char *entry, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t, const int64_t *colb,
+                             const int64_t *cole, const int64_t *csr2csc, int64_t heads, float scale, const float *q, int64_t ldq,
+                             const float *g, int64_t ldg, const float *lse, const float *dsum, const float *key, int64_t ldk,
+                             const float *v, int64_t ldv, float *dkey, int64_t lddk, float *dv, int64_t lddv, void *stream,
+                             const MhaDrop &dr = MHA_NO_DROP) {
    clear_error();
+   if (const char *why = mha_drop_refusal(dr, nnz)) return fail(ISPLIB_FAIL, entry, why);
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
+   if (dr.on && nnz > 0 && !csr2csc) return fail(ISPLIB_FAIL, entry, "null csr2csc: the keep bit is a function of the CSR position");
    if (!std::isfinite(scale)) return fail(ISPLIB_FAIL, entry, "scale must be a finite number");
    if (n == 0 || k == 0) return ISPLIB_SUCCESS;
    if (!colb || !cole || !key || !v || !dkey || !dv || (nnz > 0 && (!row_t || !q || !g || !lse || !dsum)))
@@ -582,5 +670,56 @@ extern "C" int isplib_mha_bw_cols_hip(int64_t m, int64_t n, int64_t k, int64_t n
    a.ga = q; a.ldga = ldq; a.gabytes = nnz > 0 ? mha_extent(m, k, ldq) : 0u;
    a.gb = g; a.ldgb = ldg; a.gbbytes = nnz > 0 ? mha_extent(m, k, ldg) : 0u;
    a.t1 = lse; a.t2 = dsum; a.tbytes = nnz > 0 ? mha_extent(m, heads, heads) : 0u;
-   return mha_by_width(MHA_BW_COLS, a, entry, (hipStream_t)stream);
+   if (dr.on) a.epos = csr2csc;
+   mha_set_drop(a, dr);
+   return mha_by_width(MHA_BW_COLS, a, dr.on, entry, (hipStream_t)stream);
+}
+
+extern "C" int isplib_mha_csr_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                                  const int64_t *pntre, int64_t heads, float scale, const float *q, int64_t ldq, const float *key,
+                                  int64_t ldk, const float *v, int64_t ldv, float *z, int64_t ldz, float *lse, void *stream) {
+   return mha_forward("isplib_mha_csr_hip", m, n, k, nnz, indx, pntrb, pntre, heads, scale, q, ldq, key, ldk, v, ldv, z, ldz, lse, stream);
+}
+
+extern "C" int isplib_mha_bw_rows_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                                      const int64_t *pntre, int64_t heads, float scale, const float *q, int64_t ldq, const float *key,
+                                      int64_t ldk, const float *v, int64_t ldv, const float *g, int64_t ldg, const float *z,
+                                      int64_t ldz, const float *lse, float *dq, int64_t lddq, float *dsum, void *stream) {
+   return mha_backward_rows("isplib_mha_bw_rows_hip", m, n, k, nnz, indx, pntrb, pntre, heads, scale, q, ldq, key, ldk, v, ldv, g, ldg, z,
+                            ldz, lse, dq, lddq, dsum, stream);
+}
+
+extern "C" int isplib_mha_bw_cols_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t, const int64_t *colb,
+                                      const int64_t *cole, int64_t heads, float scale, const float *q, int64_t ldq, const float *g,
+                                      int64_t ldg, const float *lse, const float *dsum, const float *key, int64_t ldk, const float *v,
+                                      int64_t ldv, float *dkey, int64_t lddk, float *dv, int64_t lddv, void *stream) {
+   return mha_backward_cols("isplib_mha_bw_cols_hip", m, n, k, nnz, row_t, colb, cole, nullptr, heads, scale, q, ldq, g, ldg, lse, dsum,
+                            key, ldk, v, ldv, dkey, lddk, dv, lddv, stream);
+}
+
+// attention dropout: the argument lists of the entries above (the columns entry with csr2csc after cole), then threshold, keep_scale, seed
+extern "C" int isplib_qkv_drop_csr_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                                       const int64_t *pntre, int64_t heads, float scale, const float *q, int64_t ldq, const float *key,
+                                       int64_t ldk, const float *v, int64_t ldv, float *z, int64_t ldz, float *lse, void *stream,
+                                       uint32_t threshold, float keep_scale, uint64_t seed) {
+   return mha_forward("isplib_qkv_drop_csr_hip", m, n, k, nnz, indx, pntrb, pntre, heads, scale, q, ldq, key, ldk, v, ldv, z, ldz, lse,
+                      stream, MhaDrop{true, threshold, keep_scale, seed});
+}
+
+extern "C" int isplib_qkv_drop_bw_rows_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                                           const int64_t *pntre, int64_t heads, float scale, const float *q, int64_t ldq,
+                                           const float *key, int64_t ldk, const float *v, int64_t ldv, const float *g, int64_t ldg,
+                                           const float *z, int64_t ldz, const float *lse, float *dq, int64_t lddq, float *dsum,
+                                           void *stream, uint32_t threshold, float keep_scale, uint64_t seed) {
+   return mha_backward_rows("isplib_qkv_drop_bw_rows_hip", m, n, k, nnz, indx, pntrb, pntre, heads, scale, q, ldq, key, ldk, v, ldv, g,
+                            ldg, z, ldz, lse, dq, lddq, dsum, stream, MhaDrop{true, threshold, keep_scale, seed});
+}
+
+extern "C" int isplib_qkv_drop_bw_cols_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t, const int64_t *colb,
+                                           const int64_t *cole, const int64_t *csr2csc, int64_t heads, float scale, const float *q,
+                                           int64_t ldq, const float *g, int64_t ldg, const float *lse, const float *dsum,
+                                           const float *key, int64_t ldk, const float *v, int64_t ldv, float *dkey, int64_t lddk,
+                                           float *dv, int64_t lddv, void *stream, uint32_t threshold, float keep_scale, uint64_t seed) {
+   return mha_backward_cols("isplib_qkv_drop_bw_cols_hip", m, n, k, nnz, row_t, colb, cole, csr2csc, heads, scale, q, ldq, g, ldg, lse,
+                            dsum, key, ldk, v, ldv, dkey, lddk, dv, lddv, stream, MhaDrop{true, threshold, keep_scale, seed});
 }

@@ -1015,7 +1015,7 @@ def _fmix32(x: torch.Tensor) -> torch.Tensor:
 
 def gat_dropout_mask(adj_or_nnz, heads: int, dropout: float, seed: int, device=None) -> torch.Tensor:
     """The keep mask of ``gat_matmul(..., dropout=dropout, seed=seed)`` and of ``gatv2_matmul(..., dropout=dropout, seed=seed)`` -- one
-    function serves both operators: a bool tensor [nnz, heads], row e belonging to the stored entry ``storage.col()[e]``; True = kept.  The realised coefficients are ``mask * a / (1 - dropout)``.  `adj_or_nnz` is the sparse matrix
+    function serves both operators, and ``mha_matmul(..., dropout=dropout, seed=seed)`` as well, whose keep bit is the same: a bool tensor [nnz, heads], row e belonging to the stored entry ``storage.col()[e]``; True = kept.  The realised coefficients are ``mask * a / (1 - dropout)``.  `adj_or_nnz` is the sparse matrix
     (the mask is built on its device) or the number of stored entries (on `device`, the CPU by default).  Written with torch integer
     operations on int64 values masked to 32 bits -- the function of include/isplib_hip.h:
         word(seed, pos, h) = fmix32(fmix32(uint32(pos) ^ uint32(seed)) + uint32(h) * 0x9E3779B9 + uint32(seed >> 32)),  keep = word >= T(p)
@@ -1134,7 +1134,8 @@ def gatv2_matmul(src, x: torch.Tensor, att: torch.Tensor, y: Optional[torch.Tens
     return torch.ops.isplib.gatv2_spmm(st._rowptr, st._col, st.colptr(), st.row_t(), x, y, att, heads, float(negative_slope))
 
 
-def mha_matmul(src, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int = 1, scale: Optional[float] = None) -> torch.Tensor:
+def mha_matmul(src, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int = 1, scale: Optional[float] = None,
+               dropout: float = 0.0, training: bool = True, seed: Optional[int] = None) -> torch.Tensor:
     """Sparse multi-head dot-product attention with separate keys and values over the stored entries of `src`, all heads in one launch
     (include/isplib_hip_mha.h, isplib_mha_csr_hip): ``z[i, head h] = sum_j softmax_j(scale * <q[i], k[j]>_h) v[j, head h]`` over the
     entries (i, j) of row i -- the aggregation of TransformerConv and of the local attention of sparse graph transformers, with its
@@ -1145,14 +1146,27 @@ def mha_matmul(src, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: in
     every stored entry is its own edge; an empty row gives 0.  The backward keeps q, k, v, z and one scalar per row and head -- nothing
     per edge.  fp32 only by default (bf16 / fp16 operands raise TypeError) and there is no fallback route: outside isplib_mha_serves
     (= isplib_gat_serves: heads * d <= 512; heads == 1 or d a power of two >= 4) the call raises ValueError.  Not part of the operator:
-    attention dropout, TransformerConv's edge features, its root weight and its beta gate (dense operations outside the aggregation).
+    TransformerConv's edge features, its root weight and its beta gate (dense operations outside the aggregation).
     bf16 / fp16 `q`, `k` and `v` (all three of one dtype) are opt-in through the multi-head variable of the module docstring
     (convert|native|auto): once it is set the call goes where mha16_route says -- the 16-bit operator (torch.ops.isplib.mha_spmm16,
     which keeps q, k, v and lse for its backward and no z; column views of one fused 16-bit projection go in at their own even pitch)
     where ALL four gathered operands are admitted (k and v with their rows, q with its rows, the gradient with M rows at pitch K), else
     `.float()` -> this function -> `.to(dtype)`, which raises only what the fp32 call raises.  ``k is v`` works on both routes.  fp32
-    calls do not read the variable."""
+    calls do not read the variable.
+    `dropout` (TransformerConv's ``dropout``, a graph transformer's ``attn_dropout``; a Python float or int in [0, 1)) drops attention
+    coefficients AFTER the softmax, per stored entry and per head, and scales the kept ones by ``float32(1 / (1 - dropout))``
+    (torch.ops.isplib.mha_drop_spmm, autograd in `q`, `k` and `v`): the softmax still runs over every stored entry.  ``dropout == 0`` or
+    ``training=False`` is the call above, unchanged, bit for bit; it draws no seed.  The mask is the one of `gat_matmul` and
+    `gatv2_matmul` -- a pure function of (`seed`, the entry's position in ``storage.col()``, head), which `gat_dropout_mask` returns and
+    the backward recomputes: nothing per edge is stored and no RNG state is kept.  ``seed=None`` draws one int64 in [0, 2^63) from
+    torch's default CPU generator (reproducible under ``torch.manual_seed``, no device sync); an explicit `seed` is an int in [0, 2^63).
+    The seed is a kernel ARGUMENT: a captured graph replays ONE mask -- draw the seed outside the capture and re-capture, or do not
+    capture a training step that needs fresh masks.  There is no 16-bit dropout kernel: with 16-bit `q`, `k`, `v` and the multi-head
+    variable set (to any value) a call with active dropout converts -- ``.float()`` -> the fp32 dropout operator -> ``.to(dtype)``,
+    every gradient returning in its own dtype through the casts, ``k is v`` preserved; with the variable unset it raises the TypeError
+    above."""
     from . import cabi
+    drop = _gat_dropout_args(dropout, training, seed)
     for name, t in (("q", q), ("k", k), ("v", v)):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"isplib_amd: `{name}` must be a tensor, got {type(t).__name__}")
@@ -1162,6 +1176,9 @@ def mha_matmul(src, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: in
             raise TypeError(f"isplib_amd: `q`, `k` and `v` must share one 16-bit dtype, got {q.dtype}, {k.dtype} and {v.dtype}")
         if not half and t.dtype != torch.float32:
             raise TypeError(f"isplib_amd: `{name}` must be float32, got {t.dtype} (the multi-head attention operator is fp32 only)")
+    if half and drop is not None:         # the conversion route whatever the variable says: .float() is exact
+        kf = k.float()
+        return mha_matmul(src, q.float(), kf, kf if v is k else v.float(), heads, scale, drop[0], True, drop[1]).to(q.dtype)
     if half:
         return _mha_matmul16(src, q, k, v, heads, scale)
     if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
@@ -1201,6 +1218,10 @@ def mha_matmul(src, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: in
     if k.device != q.device or v.device != q.device or st._rowptr.device != q.device:
         raise ValueError("isplib_amd: `q`, `k`, `v` and the sparse matrix must be on one device")
     p = float(scale) if scale is not None else 1.0 / math.sqrt(d)
+    if drop is not None:
+        if st._col.numel() >= 2 ** 31:
+            raise ValueError(f"isplib_amd: the dropout keep bit is defined for fewer than 2^31 stored entries, got {st._col.numel()}")
+        return torch.ops.isplib.mha_drop_spmm(st._rowptr, st._col, st.colptr(), st.row_t(), st.csr2csc(), q, k, v, heads, p, *drop)
     return torch.ops.isplib.mha_spmm(st._rowptr, st._col, st.colptr(), st.row_t(), q, k, v, heads, p)
 
 

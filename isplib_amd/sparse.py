@@ -361,9 +361,11 @@ class SparseTensor:
         from .plugin import gatv2_matmul
         return gatv2_matmul(self, x, att, y, heads, negative_slope, dropout, training, seed)
 
-    def mha_matmul(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int = 1, scale: Optional[float] = None) -> torch.Tensor:
+    def mha_matmul(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int = 1, scale: Optional[float] = None,
+                   dropout: float = 0.0, training: bool = True, seed: Optional[int] = None) -> torch.Tensor:
         """Sparse multi-head dot-product attention with separate keys and values over this matrix's stored entries, all heads in one
         launch (plugin.mha_matmul): q [M, heads * d], k and v [N, heads * d]; `scale` None: 1 / sqrt(d).  bf16 / fp16
-        operands are opt-in through ISPLIB_HALF_MHA."""
+        operands are opt-in through ISPLIB_HALF_MHA.  `dropout` with `training`: attention dropout after the softmax, its mask a
+        function of `seed` (None: drawn from torch's default CPU generator), the entry's position and the head."""
         from .plugin import mha_matmul
-        return mha_matmul(self, q, k, v, heads, scale)
+        return mha_matmul(self, q, k, v, heads, scale, dropout, training, seed)
