@@ -14,6 +14,9 @@ valued, so every fp32 sum is exact in any order: sum and SDDMM must equal the or
 positions bit for bit; an fp64 sum on the device over the uncompacted operand is the second arbiter.
 
 Each test states its peak device memory; the 2.30 GB operand is shared through a module fixture.
+
+The attention families (attention, gat, gatv2, mha, their EDGE / DROP forms and 16-bit twins) came after this module: their gathers past
+2^31 bytes, up to the last pitch their domains admit, are in tests/test_gpu_attention_address_edges.py.
 """
 import gc
 
