@@ -28,6 +28,7 @@
 
 #include "common.h"
 #include "gather.h"
+#include "attn_common.h"
 
 namespace isplib {
 
@@ -72,15 +73,6 @@ template <int LPR, int NCH> struct AttnCols {
    }
 };
 
-// this lane's columns of row `row` of a dense operand; plain loads, nothing outside the row's k columns is read
-template <int LPR, int NCH>
-__device__ __forceinline__ void attn_own_row(const float *base, int64_t row, int64_t ld, int lc, const AttnCols<LPR, NCH> &cm, float (&r)[NCH][4]) {
-#pragma unroll
-   for (int j = 0; j < NCH; j++)
-#pragma unroll
-      for (int v = 0; v < 4; v++) r[j][v] = cm.ok[j][v] ? base[(size_t)row * (size_t)ld + (size_t)((j * LPR + lc) * 4 + v)] : 0.0f;
-}
-
 // the U gathers of this slot for the edges [s0, s0 + G*U) of the batch (edge s0 + u*G + g); dead edges carry BUF_OOB: they read 0
 template <int LPR, int NCH, int U>
 __device__ __forceinline__ void attn_gather(const __amdgpu_buffer_rsrc_t rsrc, unsigned off_l, int s0, int g, const AttnCols<LPR, NCH> &cm,
@@ -117,10 +109,10 @@ __global__ __launch_bounds__(WAVES * 64) void attention_fw_kernel(const AttnArgs
    const int64_t row = (int64_t)blockIdx.x * WAVES + wave;
    if (row >= a.rows) return;
    const int64_t eb = a.pntrb[row], ee = a.pntre[row];
-   __amdgpu_buffer_rsrc_t rsrc = dense_rsrc(a);
+   __amdgpu_buffer_rsrc_t rsrc = attn_rsrc(a.y, a.ybytes);
    const AttnCols<LPR, NCH> cm((int)a.k, lc);
    float xv[NCH][4];
-   attn_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm, xv);
+   attn_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm.ok, xv);
 
    float mrun = ATTN_NONE, l = 0.0f, acc[NCH][4];
 #pragma unroll
@@ -199,15 +191,15 @@ __global__ __launch_bounds__(WAVES * 64) void attention_bw_rows_kernel(const Att
    const int64_t row = (int64_t)blockIdx.x * WAVES + wave;
    if (row >= a.rows) return;
    const int64_t eb = a.pntrb[row], ee = a.pntre[row];
-   __amdgpu_buffer_rsrc_t rsrc = dense_rsrc(a);
+   __amdgpu_buffer_rsrc_t rsrc = attn_rsrc(a.y, a.ybytes);
    const AttnCols<LPR, NCH> cm((int)a.k, lc);
    float xv[NCH][4], gv[NCH][4];
-   attn_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm, xv);
-   attn_own_row<LPR, NCH>(a.g, row, a.ldg, lc, cm, gv);
+   attn_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm.ok, xv);
+   attn_own_row<LPR, NCH>(a.g, row, a.ldg, lc, cm.ok, gv);
    float dsum = 0.0f;                                  // D_i = <g_i, z_i>: every slot holds the row, so every lane ends with it
    {
       float zv[NCH][4];
-      attn_own_row<LPR, NCH>(a.zin, row, a.ldzin, lc, cm, zv);
+      attn_own_row<LPR, NCH>(a.zin, row, a.ldzin, lc, cm.ok, zv);
 #pragma unroll
       for (int j = 0; j < NCH; j++)
 #pragma unroll
@@ -279,11 +271,11 @@ __global__ __launch_bounds__(WAVES * 64) void attention_bw_cols_kernel(const Att
    const int64_t row = (int64_t)blockIdx.x * WAVES + wave;
    if (row >= a.rows) return;
    const int64_t eb = a.pntrb[row], ee = a.pntre[row];
-   __amdgpu_buffer_rsrc_t rsx = dense_rsrc(a);
-   __amdgpu_buffer_rsrc_t rsg = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.y2), 0, (int)a.y2bytes, 0x00020000);
+   __amdgpu_buffer_rsrc_t rsx = attn_rsrc(a.y, a.ybytes);
+   __amdgpu_buffer_rsrc_t rsg = attn_rsrc(a.y2, a.y2bytes);
    const AttnCols<LPR, NCH> cm((int)a.k, lc);
    float yv[NCH][4];
-   attn_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm, yv);
+   attn_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm.ok, yv);
 
    float acc[NCH][4];
 #pragma unroll
@@ -363,20 +355,9 @@ static int launch_attention(int which, const AttnArgs &a, const char *entry, hip
    return check_launch(entry);
 }
 
-// the width dispatch of general_entry (fusedmm_general.hip), up to two chunks per lane
+// the width ladder (attn_by_width)
 static int attention_by_width(int which, const AttnArgs &a, const char *entry, hipStream_t st) {
-   const int64_t w = (a.k + 3) / 4;
-   if (w <= 8) return launch_attention<8, 1>(which, a, entry, st);
-   if (w <= 16) return launch_attention<16, 1>(which, a, entry, st);
-   if (w <= 32) return launch_attention<32, 1>(which, a, entry, st);
-   if (w <= 64) return launch_attention<64, 1>(which, a, entry, st);
-   return launch_attention<64, 2>(which, a, entry, st);
-}
-
-// what a descriptor over `rows` rows of k floats at pitch ld may answer: the extent a row-strided view owns, not rows * ld (the last
-// row of the last head view of a wider tensor ends with the tensor)
-static unsigned attention_extent(int64_t rows, int64_t k, int64_t ld) {
-   return rows <= 0 ? 0u : (unsigned)(((unsigned long long)(rows - 1) * (unsigned long long)ld + (unsigned long long)k) * 4ull);
+   return attn_by_width(a.k, [&](auto lpr, auto nch) { return launch_attention<decltype(lpr)::value, decltype(nch)::value>(which, a, entry, st); });
 }
 
 static const char *const ATTN_DOMAIN = "outside isplib_attention_serves(rows_gathered, k, ld): 1 <= k <= 512, ld >= k, rows_gathered < 2^31, "
@@ -402,7 +383,7 @@ extern "C" int isplib_attention_csr_hip(int64_t m, int64_t n, int64_t k, int64_t
    a.rows = m; a.k = k; a.indx = indx; a.pntrb = pntrb; a.pntre = pntre; a.p = scale;
    a.own = x; a.ldown = ldx;
    a.out = z; a.ldout = ldz; a.lse_out = lse;
-   a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? attention_extent(n, k, ldy) : 0u;
+   a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? attn_extent(n, k, ldy) : 0u;
    return attention_by_width(ATTN_FW, a, entry, (hipStream_t)stream);
 }
 
@@ -421,7 +402,7 @@ extern "C" int isplib_attention_bw_rows_hip(int64_t m, int64_t n, int64_t k, int
    a.rows = m; a.k = k; a.indx = indx; a.pntrb = pntrb; a.pntre = pntre; a.p = scale;
    a.own = x; a.ldown = ldx; a.g = g; a.ldg = ldg; a.zin = z; a.ldzin = ldz; a.lse = lse;
    a.out = dx; a.ldout = lddx; a.dsum_out = dsum;
-   a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? attention_extent(n, k, ldy) : 0u;
+   a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? attn_extent(n, k, ldy) : 0u;
    return attention_by_width(ATTN_BW_ROWS, a, entry, (hipStream_t)stream);
 }
 
@@ -440,7 +421,7 @@ extern "C" int isplib_attention_bw_cols_hip(int64_t m, int64_t n, int64_t k, int
    a.rows = n; a.k = k; a.indx = row_t; a.pntrb = colb; a.pntre = cole; a.p = scale;
    a.own = y; a.ldown = ldy; a.lse = lse; a.dsum = dsum;
    a.out = dy; a.ldout = lddy;
-   a.y = x; a.ldy = ldx; a.ybytes = nnz > 0 ? attention_extent(m, k, ldx) : 0u;
-   a.y2 = g; a.ldy2 = ldg; a.y2bytes = nnz > 0 ? attention_extent(m, k, ldg) : 0u;
+   a.y = x; a.ldy = ldx; a.ybytes = nnz > 0 ? attn_extent(m, k, ldx) : 0u;
+   a.y2 = g; a.ldy2 = ldg; a.y2bytes = nnz > 0 ? attn_extent(m, k, ldg) : 0u;
    return attention_by_width(ATTN_BW_COLS, a, entry, (hipStream_t)stream);
 }

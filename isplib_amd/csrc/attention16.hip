@@ -35,6 +35,7 @@
 #include "common.h"
 #include "gather.h"
 #include "half16.h"
+#include "attn16_common.h"
 
 namespace isplib {
 
@@ -76,23 +77,6 @@ struct Attn16Cols {
    }
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t attn16_desc(const void *p, unsigned bytes) {
-   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
-}
-
-// this lane's columns of row `row` of a dense operand as floats; plain dword loads (base, pitch and column are even), nothing outside
-// the row's k columns is read
-template <int ELT>
-__device__ __forceinline__ void attn16_own_row(const unsigned short *base, int64_t row, int64_t ld, const Attn16Cols &cm, float (&r)[8]) {
-   const unsigned *p = reinterpret_cast<const unsigned *>(base + (size_t)row * (size_t)ld + (size_t)cm.col);
-#pragma unroll
-   for (int q = 0; q < 4; q++) {
-      unsigned w = 0u;
-      if (cm.ok[q]) w = p[q];
-      widen2<ELT>(w, r[2 * q], r[2 * q + 1]);
-   }
-}
-
 // the U gathers of this slot for the edges [s0, s0 + G*U) of the batch (edge s0 + u*G + g); dead edges carry BUF_OOB: they read 0
 template <int LPR, int U>
 __device__ __forceinline__ void attn16_gather(const __amdgpu_buffer_rsrc_t rsrc, unsigned off_l, int s0, int g, const Attn16Cols &cm,
@@ -103,36 +87,6 @@ __device__ __forceinline__ void attn16_gather(const __amdgpu_buffer_rsrc_t rsrc,
       const unsigned off = (unsigned)__shfl((int)off_l, (s0 + u * G + g) & 63);
       const unsigned o = (off + cm.cbyte) | cm.poison;      // off = BUF_OOB + cbyte (< 2^10) cannot wrap
       t[u] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)o, 0, 0);
-   }
-}
-
-// a gathered vector as eight floats; a dword the 16-byte load brought from outside the row is dropped by a select, not a multiply
-template <int ELT> __device__ __forceinline__ void attn16_widen(const v4i_t &t, const Attn16Cols &cm, float (&y)[8]) {
-#pragma unroll
-   for (int q = 0; q < 4; q++) widen2<ELT>(cm.ok[q] ? (unsigned)t[q] : 0u, y[2 * q], y[2 * q + 1]);
-}
-
-__device__ __forceinline__ float attn16_dot(const float (&r)[8], const float (&y)[8]) {
-   float d = 0.0f;
-#pragma unroll
-   for (int v = 0; v < 8; v++) d = fmaf(r[v], y[v], d);
-   return d;
-}
-
-// the lane's eight finished columns, rounded once; only the dwords inside the row are written
-template <int ELT>
-__device__ __forceinline__ void attn16_store_row(unsigned short *base, int64_t row, int64_t ld, const Attn16Cols &cm, const float (&r)[8]) {
-   if (cm.poison != 0u) return;
-   unsigned *p = reinterpret_cast<unsigned *>(base + (size_t)row * (size_t)ld + (size_t)cm.col);
-   unsigned d[4];
-#pragma unroll
-   for (int q = 0; q < 4; q++) d[q] = narrow2<ELT>(r[2 * q], r[2 * q + 1]);
-   if (cm.ok[3] && ((uintptr_t)p & 15) == 0) {
-      *reinterpret_cast<uint4 *>(p) = make_uint4(d[0], d[1], d[2], d[3]);
-   } else {
-#pragma unroll
-      for (int q = 0; q < 4; q++)
-         if (cm.ok[q]) p[q] = d[q];
    }
 }
 
@@ -148,7 +102,7 @@ __global__ __launch_bounds__(WAVES * 64) void attention16_fw_kernel(const Attn16
    __amdgpu_buffer_rsrc_t rsrc = attn16_desc(a.y, a.ybytes);
    const Attn16Cols cm((int)a.k, lc);
    float xv[8];
-   attn16_own_row<ELT>(a.own, row, a.ldown, cm, xv);
+   attn16_own_row<ELT>(a.own, row, a.ldown, cm.col, cm.ok, xv);
 
    float mrun = ATTN16_NONE, l = 0.0f, acc[8];
 #pragma unroll
@@ -168,8 +122,8 @@ __global__ __launch_bounds__(WAVES * 64) void attention16_fw_kernel(const Attn16
 #pragma unroll
          for (int u = 0; u < U; u++) {
             float yv[8];
-            attn16_widen<ELT>(t[u], cm, yv);
-            part[u] = attn16_dot(xv, yv);
+            attn16_widen<ELT>(t[u], cm.ok, yv);
+            part[u] = attn16_dot_part(xv, yv);
          }
          int mine;
          const float sum = reduce_transposed<U, LPR>(part, lc, mine);
@@ -189,7 +143,7 @@ __global__ __launch_bounds__(WAVES * 64) void attention16_fw_kernel(const Attn16
             const float w = (s0 + u * G + g < cnt) ? __expf(sc[u] - mnew) : 0.0f;
             l += w;
             float yv[8];
-            attn16_widen<ELT>(t[u], cm, yv);
+            attn16_widen<ELT>(t[u], cm.ok, yv);
 #pragma unroll
             for (int v = 0; v < 8; v++) acc[v] = fmaf(w, yv[v], acc[v]);
          }
@@ -211,7 +165,7 @@ __global__ __launch_bounds__(WAVES * 64) void attention16_fw_kernel(const Attn16
    float zr[8];
 #pragma unroll
    for (int v = 0; v < 8; v++) zr[v] = empty ? 0.0f : acc[v] / l;
-   attn16_store_row<ELT>(a.out, row, a.ldout, cm, zr);
+   attn16_store_row<ELT>(a.out, row, a.ldout, cm.col, cm.ok, zr);
    if (lc == 0) a.lse_out[row] = empty ? -INFINITY : mrun + logf(l);
 }
 
@@ -228,8 +182,8 @@ __global__ __launch_bounds__(WAVES * 64) void attention16_bw_rows_kernel(const A
    __amdgpu_buffer_rsrc_t rsrc = attn16_desc(a.y, a.ybytes);
    const Attn16Cols cm((int)a.k, lc);
    float xv[8], gv[8];
-   attn16_own_row<ELT>(a.own, row, a.ldown, cm, xv);
-   attn16_own_row<ELT>(a.g, row, a.ldg, cm, gv);
+   attn16_own_row<ELT>(a.own, row, a.ldown, cm.col, cm.ok, xv);
+   attn16_own_row<ELT>(a.g, row, a.ldg, cm.col, cm.ok, gv);
    const float lse = a.lse[row];
 
    float l = 0.0f, dacc = 0.0f, zacc[8], a1[8];      // sum a_e, sum a_e t_e, sum a_e y_j, sum a_e t_e y_j
@@ -250,9 +204,9 @@ __global__ __launch_bounds__(WAVES * 64) void attention16_bw_rows_kernel(const A
 #pragma unroll
          for (int u = 0; u < U; u++) {
             float yv[8];
-            attn16_widen<ELT>(tv[u], cm, yv);
-            part[u] = attn16_dot(xv, yv);
-            part[U + u] = attn16_dot(gv, yv);
+            attn16_widen<ELT>(tv[u], cm.ok, yv);
+            part[u] = attn16_dot_part(xv, yv);
+            part[U + u] = attn16_dot_part(gv, yv);
          }
          int mine;
          const float sum = reduce_transposed<2 * U, LPR>(part, lc, mine);
@@ -266,7 +220,7 @@ __global__ __launch_bounds__(WAVES * 64) void attention16_bw_rows_kernel(const A
             l += ae;
             dacc += at;
             float yv[8];
-            attn16_widen<ELT>(tv[u], cm, yv);
+            attn16_widen<ELT>(tv[u], cm.ok, yv);
 #pragma unroll
             for (int v = 0; v < 8; v++) {
                zacc[v] = fmaf(ae, yv[v], zacc[v]);
@@ -291,7 +245,7 @@ __global__ __launch_bounds__(WAVES * 64) void attention16_bw_rows_kernel(const A
    float dxr[8];
 #pragma unroll
    for (int v = 0; v < 8; v++) dxr[v] = empty ? 0.0f : a.p * (a1[v] - dsum * zacc[v]);
-   attn16_store_row<ELT>(a.out, row, a.ldout, cm, dxr);
+   attn16_store_row<ELT>(a.out, row, a.ldout, cm.col, cm.ok, dxr);
    if (lc == 0) a.dsum_out[row] = dsum;
 }
 
@@ -309,7 +263,7 @@ __global__ __launch_bounds__(WAVES * 64) void attention16_bw_cols_kernel(const A
    __amdgpu_buffer_rsrc_t rsg = attn16_desc(a.y2, a.y2bytes);
    const Attn16Cols cm((int)a.k, lc);
    float yv[8];
-   attn16_own_row<ELT>(a.own, row, a.ldown, cm, yv);
+   attn16_own_row<ELT>(a.own, row, a.ldown, cm.col, cm.ok, yv);
 
    float acc[8];
 #pragma unroll
@@ -338,10 +292,10 @@ __global__ __launch_bounds__(WAVES * 64) void attention16_bw_cols_kernel(const A
 #pragma unroll
          for (int u = 0; u < U; u++) {
             float xg[8], gg[8];
-            attn16_widen<ELT>(xt[u], cm, xg);
-            attn16_widen<ELT>(gt[u], cm, gg);
-            part[u] = attn16_dot(yv, xg);
-            part[U + u] = attn16_dot(yv, gg);
+            attn16_widen<ELT>(xt[u], cm.ok, xg);
+            attn16_widen<ELT>(gt[u], cm.ok, gg);
+            part[u] = attn16_dot_part(yv, xg);
+            part[U + u] = attn16_dot_part(yv, gg);
          }
          int mine;
          const float sum = reduce_transposed<2 * U, LPR>(part, lc, mine);
@@ -355,8 +309,8 @@ __global__ __launch_bounds__(WAVES * 64) void attention16_bw_cols_kernel(const A
             const float ae = live ? __expf(s - lse) : 0.0f;
             const float pds = live ? a.p * (ae * (t - dsum)) : 0.0f;
             float xg[8], gg[8];
-            attn16_widen<ELT>(xt[u], cm, xg);
-            attn16_widen<ELT>(gt[u], cm, gg);
+            attn16_widen<ELT>(xt[u], cm.ok, xg);
+            attn16_widen<ELT>(gt[u], cm.ok, gg);
 #pragma unroll
             for (int v = 0; v < 8; v++) acc[v] += fmaf(pds, xg[v], ae * gg[v]);
          }
@@ -367,7 +321,7 @@ __global__ __launch_bounds__(WAVES * 64) void attention16_bw_cols_kernel(const A
 #pragma unroll
       for (int v = 0; v < 8; v++) acc[v] += __shfl_xor(acc[v], o);
    if (g != 0) return;
-   attn16_store_row<ELT>(a.out, row, a.ldout, cm, acc);      // no incoming entry: 0
+   attn16_store_row<ELT>(a.out, row, a.ldout, cm.col, cm.ok, acc);      // no incoming entry: 0
 }
 
 enum { ATTN16_FW = 0, ATTN16_BW_ROWS = 1, ATTN16_BW_COLS = 2 };
@@ -384,35 +338,15 @@ static int launch_attention16(int which, const Attn16Args &a, const char *entry,
    return check_launch(entry);
 }
 
-// the slot width by ceil(k / 8) 16-byte vectors per row, always one chunk per lane
-template <int ELT>
-static int attention16_by_width(int which, const Attn16Args &a, const char *entry, hipStream_t st) {
-   const int64_t w = (a.k + 7) / 8;
-   if (w <= 4) return launch_attention16<ELT, 4>(which, a, entry, st);
-   if (w <= 8) return launch_attention16<ELT, 8>(which, a, entry, st);
-   if (w <= 16) return launch_attention16<ELT, 16>(which, a, entry, st);
-   if (w <= 32) return launch_attention16<ELT, 32>(which, a, entry, st);
-   return launch_attention16<ELT, 64>(which, a, entry, st);
-}
-
+// the element type and the slot width (attn16_run)
 static int attention16_run(int dtype, int which, const Attn16Args &a, const char *entry, void *stream) {
-   return dtype == ISPLIB_DTYPE_BF16 ? attention16_by_width<ELT_BF16>(which, a, entry, (hipStream_t)stream)
-                                     : attention16_by_width<ELT_F16>(which, a, entry, (hipStream_t)stream);
+   return attn16_run(dtype, a.k, [&](auto elt, auto lpr) {
+      return launch_attention16<decltype(elt)::value, decltype(lpr)::value>(which, a, entry, (hipStream_t)stream);
+   });
 }
 
-// what a descriptor over `rows` rows of k 2-byte elements at pitch ld may answer: the extent a row-strided view owns, not rows * ld
-static unsigned attention16_extent(int64_t rows, int64_t k, int64_t ld) {
-   return rows <= 0 ? 0u : (unsigned)(((unsigned long long)(rows - 1) * (unsigned long long)ld + (unsigned long long)k) * 2ull);
-}
-
-static const char *const ATTN16_DTYPE = "dtype must be ISPLIB_DTYPE_BF16 or ISPLIB_DTYPE_F16";
 static const char *const ATTN16_DOMAIN = "outside isplib_attention16_serves(rows_gathered, k, ld): 8 <= k <= 512, k and every pitch even, ld >= k, "
                                          "rows_gathered < 2^31, rows_gathered*ld*2 <= 3.5 GiB (convert the operands and use the fp32 entries)";
-
-static bool attention16_even(int64_t a, int64_t b, int64_t c = 0, int64_t d = 0) { return ((a | b | c | d) & 1) == 0; }
-static bool attention16_aligned(const void *a, const void *b, const void *c = nullptr, const void *d = nullptr) {
-   return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 3) == 0;
-}
 
 }  // namespace isplib
 
@@ -433,14 +367,14 @@ extern "C" int isplib_attention16_csr_hip(int dtype, int64_t m, int64_t n, int64
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
    if (m == 0 || k == 0) return ISPLIB_SUCCESS;
    if (ldx < k || ldz < k) return fail(ISPLIB_FAIL, entry, "leading dimension smaller than k");
-   if (!isplib_attention16_serves(n, k, ldy) || !attention16_even(ldx, ldz)) return fail(ISPLIB_NO_OPT_IMPL, entry, ATTN16_DOMAIN);
+   if (!isplib_attention16_serves(n, k, ldy) || !attn16_even(ldx, ldz)) return fail(ISPLIB_NO_OPT_IMPL, entry, ATTN16_DOMAIN);
    if (!pntrb || !pntre || !x || !z || !lse || (nnz > 0 && (!indx || !y))) return fail(ISPLIB_FAIL, entry, "null operand");
-   if (!attention16_aligned(x, y, z)) return fail(ISPLIB_FAIL, entry, "x, y and z must be 4-byte aligned");
+   if (!attn16_aligned(x, y, z)) return fail(ISPLIB_FAIL, entry, "x, y and z must be 4-byte aligned");
    Attn16Args a = {};
    a.rows = m; a.k = k; a.indx = indx; a.pntrb = pntrb; a.pntre = pntre; a.p = scale;
    a.own = reinterpret_cast<const unsigned short *>(x); a.ldown = ldx;
    a.out = reinterpret_cast<unsigned short *>(z); a.ldout = ldz; a.lse_out = lse;
-   a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? attention16_extent(n, k, ldy) : 0u;
+   a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? attn16_extent(n, k, ldy, 2u) : 0u;
    return attention16_run(dtype, ATTN16_FW, a, entry, stream);
 }
 
@@ -453,15 +387,15 @@ extern "C" int isplib_attention16_bw_rows_hip(int dtype, int64_t m, int64_t n, i
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
    if (m == 0 || k == 0) return ISPLIB_SUCCESS;
    if (ldx < k || ldg < k || lddx < k) return fail(ISPLIB_FAIL, entry, "leading dimension smaller than k");
-   if (!isplib_attention16_serves(n, k, ldy) || !attention16_even(ldx, ldg, lddx)) return fail(ISPLIB_NO_OPT_IMPL, entry, ATTN16_DOMAIN);
+   if (!isplib_attention16_serves(n, k, ldy) || !attn16_even(ldx, ldg, lddx)) return fail(ISPLIB_NO_OPT_IMPL, entry, ATTN16_DOMAIN);
    if (!pntrb || !pntre || !x || !g || !lse || !dx || !dsum || (nnz > 0 && (!indx || !y))) return fail(ISPLIB_FAIL, entry, "null operand");
-   if (!attention16_aligned(x, y, g, dx)) return fail(ISPLIB_FAIL, entry, "x, y, g and dx must be 4-byte aligned");
+   if (!attn16_aligned(x, y, g, dx)) return fail(ISPLIB_FAIL, entry, "x, y, g and dx must be 4-byte aligned");
    Attn16Args a = {};
    a.rows = m; a.k = k; a.indx = indx; a.pntrb = pntrb; a.pntre = pntre; a.p = scale;
    a.own = reinterpret_cast<const unsigned short *>(x); a.ldown = ldx;
    a.g = reinterpret_cast<const unsigned short *>(g); a.ldg = ldg; a.lse = lse;
    a.out = reinterpret_cast<unsigned short *>(dx); a.ldout = lddx; a.dsum_out = dsum;
-   a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? attention16_extent(n, k, ldy) : 0u;
+   a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? attn16_extent(n, k, ldy, 2u) : 0u;
    return attention16_run(dtype, ATTN16_BW_ROWS, a, entry, stream);
 }
 
@@ -475,15 +409,15 @@ extern "C" int isplib_attention16_bw_cols_hip(int dtype, int64_t m, int64_t n, i
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
    if (n == 0 || k == 0) return ISPLIB_SUCCESS;
    if (ldy < k || lddy < k) return fail(ISPLIB_FAIL, entry, "leading dimension smaller than k");
-   if (!isplib_attention16_serves(m, k, ldx) || !isplib_attention16_serves(m, k, ldg) || !attention16_even(ldy, lddy))
+   if (!isplib_attention16_serves(m, k, ldx) || !isplib_attention16_serves(m, k, ldg) || !attn16_even(ldy, lddy))
       return fail(ISPLIB_NO_OPT_IMPL, entry, ATTN16_DOMAIN);
    if (!colb || !cole || !y || !dy || (nnz > 0 && (!row_t || !x || !g || !lse || !dsum))) return fail(ISPLIB_FAIL, entry, "null operand");
-   if (!attention16_aligned(x, y, g, dy)) return fail(ISPLIB_FAIL, entry, "x, y, g and dy must be 4-byte aligned");
+   if (!attn16_aligned(x, y, g, dy)) return fail(ISPLIB_FAIL, entry, "x, y, g and dy must be 4-byte aligned");
    Attn16Args a = {};
    a.rows = n; a.k = k; a.indx = row_t; a.pntrb = colb; a.pntre = cole; a.p = scale;
    a.own = reinterpret_cast<const unsigned short *>(y); a.ldown = ldy; a.lse = lse; a.dsum = dsum;
    a.out = reinterpret_cast<unsigned short *>(dy); a.ldout = lddy;
-   a.y = x; a.ldy = ldx; a.ybytes = nnz > 0 ? attention16_extent(m, k, ldx) : 0u;
-   a.y2 = g; a.ldy2 = ldg; a.y2bytes = nnz > 0 ? attention16_extent(m, k, ldg) : 0u;
+   a.y = x; a.ldy = ldx; a.ybytes = nnz > 0 ? attn16_extent(m, k, ldx, 2u) : 0u;
+   a.y2 = g; a.ldy2 = ldg; a.y2bytes = nnz > 0 ? attn16_extent(m, k, ldg, 2u) : 0u;
    return attention16_run(dtype, ATTN16_BW_COLS, a, entry, stream);
 }

@@ -52,6 +52,7 @@
 #include "common.h"
 #include "gather.h"
 #include "gat_dropout.h"
+#include "attn_common.h"
 
 namespace isplib {
 
@@ -93,64 +94,11 @@ struct GatArgs {
    float c;                                // float32(1 / (1 - p))
 };
 
-template <int LPR, int NCH> struct GatCols {
-   unsigned cbyte[NCH], poison[NCH];       // this lane's 4 consecutive columns per chunk; past k: an offset the descriptor answers with 0
-   unsigned hbyte[NCH];                    // byte offset of the chunk's head inside a row of a [., H] table
-   int head[NCH];
-   bool ok[NCH][4], first[NCH];            // first: this lane's chunk opens a head (and lies inside k)
-   __device__ __forceinline__ GatCols(const GatArgs &a, int lc) {
-#pragma unroll
-      for (int j = 0; j < NCH; j++) {
-         const int c = (j * LPR + lc) * 4;
-         cbyte[j] = (unsigned)c * 4u;
-         poison[j] = c < (int)a.k ? 0u : BUF_OOB;
-         head[j] = c >> a.hshift;
-         hbyte[j] = (unsigned)head[j] * 4u;
-         first[j] = c < (int)a.k && ((unsigned)c & a.hmask) == 0u;
-#pragma unroll
-         for (int v = 0; v < 4; v++) ok[j][v] = c + v < (int)a.k;
-      }
-   }
-};
-
-// this lane's columns of row `row` of a dense operand; plain loads, nothing outside the row's k columns is read
-template <int LPR, int NCH>
-__device__ __forceinline__ void gat_own_row(const float *base, int64_t row, int64_t ld, int lc, const GatCols<LPR, NCH> &cm, float (&r)[NCH][4]) {
-#pragma unroll
-   for (int j = 0; j < NCH; j++)
-#pragma unroll
-      for (int v = 0; v < 4; v++) r[j][v] = cm.ok[j][v] ? base[(size_t)row * (size_t)ld + (size_t)((j * LPR + lc) * 4 + v)] : 0.0f;
-}
-
-// entry [row, head of chunk j] of a dense [rows, H] table, per chunk; a chunk past k reads nothing
-template <int LPR, int NCH>
-__device__ __forceinline__ void gat_own_head(const float *base, int64_t row, int heads, const GatCols<LPR, NCH> &cm, float (&r)[NCH]) {
-#pragma unroll
-   for (int j = 0; j < NCH; j++) r[j] = cm.ok[j][0] ? base[(size_t)row * (size_t)heads + (size_t)cm.head[j]] : 0.0f;
-}
-
 // byte offsets of the gathered row of edge `src` of the batch in the wide operand and in the [., H] tables; a dead edge: BUF_OOB
 __device__ __forceinline__ void gat_edge(int id_l, int src, unsigned ldb, unsigned hb, unsigned &off, unsigned &offh) {
    const int id = __shfl(id_l, src);
    off = id < 0 ? BUF_OOB : (unsigned)id * ldb;
    offh = id < 0 ? BUF_OOB : (unsigned)id * hb;              // BUF_OOB + cbyte / hbyte (< 2^24) cannot wrap
-}
-
-template <int LPR, int NCH>
-__device__ __forceinline__ void gat_load_wide(const __amdgpu_buffer_rsrc_t rsrc, unsigned off, const GatCols<LPR, NCH> &cm, v4i_t (&t)[NCH]) {
-#pragma unroll
-   for (int j = 0; j < NCH; j++) t[j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)((off + cm.cbyte[j]) | cm.poison[j]), 0, 0);
-}
-
-template <int LPR, int NCH>
-__device__ __forceinline__ void gat_load_head(const __amdgpu_buffer_rsrc_t rsrc, unsigned offh, const GatCols<LPR, NCH> &cm, float (&t)[NCH]) {
-#pragma unroll
-   for (int j = 0; j < NCH; j++)
-      t[j] = __int_as_float((int)__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)((offh + cm.hbyte[j]) | cm.poison[j]), 0, 0));
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t gat_rsrc(const float *p, unsigned bytes) {
-   return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p), 0, (int)bytes, 0x00020000);
 }
 
 // a descriptor whose base moves with the wave's batch: its inputs made provably wave-uniform, so that it is built with scalar
@@ -159,7 +107,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t gat_rsrc_uniform(const float *
    const unsigned long long v = (unsigned long long)p;
    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
-   return gat_rsrc((const float *)(((unsigned long long)hi << 32) | (unsigned long long)lo), (unsigned)__builtin_amdgcn_readfirstlane((int)bytes));
+   return attn_rsrc((const float *)(((unsigned long long)hi << 32) | (unsigned long long)lo), (unsigned)__builtin_amdgcn_readfirstlane((int)bytes));
 }
 
 // sum over the lanes that share a head (an aligned group of `hlanes` lanes, a power of two <= LPR); every lane of the group ends
@@ -175,7 +123,7 @@ template <int LPR, int O = 1> __device__ __forceinline__ float gat_head_sum(floa
 
 // <r, t>_h per chunk over this lane's columns, then over the head's lanes (and both chunks where the head is the whole row)
 template <int LPR, int NCH>
-__device__ __forceinline__ void gat_head_dot(const float (&r)[NCH][4], const v4i_t (&t)[NCH], const GatCols<LPR, NCH> &cm, const GatArgs &a,
+__device__ __forceinline__ void gat_head_dot(const float (&r)[NCH][4], const v4i_t (&t)[NCH], const AttnHeadCols<LPR, NCH> &cm, const GatArgs &a,
                                              float (&d)[NCH]) {
 #pragma unroll
    for (int j = 0; j < NCH; j++) {
@@ -205,13 +153,6 @@ __device__ __forceinline__ float gat_score_edge(float adst, float asrc, float ae
    return u > 0.0f ? u : ns * u;
 }
 
-// DROP: the per-lane constant of each chunk's head (gat_dropout.h)
-template <int LPR, int NCH>
-__device__ __forceinline__ void gat_drop_heads(const GatArgs &a, const GatCols<LPR, NCH> &cm, unsigned (&hk)[NCH]) {
-#pragma unroll
-   for (int j = 0; j < NCH; j++) hk[j] = gat_drop_head(a.seed_hi, (unsigned)cm.head[j]);
-}
-
 template <int LPR, int NCH, int WAVES, bool EDGE, bool DROP>
 __global__ __launch_bounds__(WAVES * 64) void gat_fw_kernel(const GatArgs a) {
    constexpr int G = 64 / LPR, U = 4;
@@ -221,12 +162,12 @@ __global__ __launch_bounds__(WAVES * 64) void gat_fw_kernel(const GatArgs a) {
    const int64_t row = (int64_t)blockIdx.x * WAVES + wave;
    if (row >= a.rows) return;
    const int64_t eb = a.pntrb[row], ee = a.pntre[row];
-   const __amdgpu_buffer_rsrc_t rsy = gat_rsrc(a.y, a.ybytes), rss = gat_rsrc(a.t0, a.tbytes);
-   const GatCols<LPR, NCH> cm(a, lc);
+   const __amdgpu_buffer_rsrc_t rsy = attn_rsrc(a.y, a.ybytes), rss = attn_rsrc(a.t0, a.tbytes);
+   const AttnHeadCols<LPR, NCH> cm(a.k, a.hshift, a.hmask, lc);
    float adst[NCH];
-   gat_own_head<LPR, NCH>(a.own_score, row, a.heads, cm, adst);
+   attn_own_head<LPR, NCH>(a.own_score, row, a.heads, cm, adst);
    [[maybe_unused]] unsigned hk[NCH];
-   if constexpr (DROP) gat_drop_heads<LPR, NCH>(a, cm, hk);
+   if constexpr (DROP) attn_drop_heads<LPR, NCH>(a.seed_hi, cm, hk);
 
    float mrun[NCH], l[NCH], acc[NCH][4];
 #pragma unroll
@@ -256,9 +197,9 @@ __global__ __launch_bounds__(WAVES * 64) void gat_fw_kernel(const GatArgs a) {
          for (int u = 0; u < U; u++) {
             unsigned off, offh;
             gat_edge(id_l, (s0 + u * G + g) & 63, ldyb, hb, off, offh);
-            gat_load_wide<LPR, NCH>(rsy, off, cm, yv[u]);
-            gat_load_head<LPR, NCH>(rss, offh, cm, sc[u]);
-            if constexpr (EDGE) gat_load_head<LPR, NCH>(rse, (unsigned)((s0 + u * G + g) & 63) * hb, cm, se[u]);      // a slot past cnt: 0
+            attn_load_wide<LPR, NCH>(rsy, off, cm, yv[u]);
+            attn_load_head<LPR, NCH>(rss, offh, cm, sc[u]);
+            if constexpr (EDGE) attn_load_head<LPR, NCH>(rse, (unsigned)((s0 + u * G + g) & 63) * hb, cm, se[u]);      // a slot past cnt: 0
             if constexpr (DROP) hw[u] = (unsigned)__shfl((int)hw_l, (s0 + u * G + g) & 63);
          }
 #pragma unroll
@@ -326,15 +267,15 @@ __global__ __launch_bounds__(WAVES * 64) void gat_bw_rows_kernel(const GatArgs a
    const int64_t row = (int64_t)blockIdx.x * WAVES + wave;
    if (row >= a.rows) return;
    const int64_t eb = a.pntrb[row], ee = a.pntre[row];
-   const __amdgpu_buffer_rsrc_t rsy = gat_rsrc(a.y, a.ybytes), rss = gat_rsrc(a.t0, a.tbytes);
-   const GatCols<LPR, NCH> cm(a, lc);
+   const __amdgpu_buffer_rsrc_t rsy = attn_rsrc(a.y, a.ybytes), rss = attn_rsrc(a.t0, a.tbytes);
+   const AttnHeadCols<LPR, NCH> cm(a.k, a.hshift, a.hmask, lc);
    float gv[NCH][4], adst[NCH], lse[NCH], dsum[NCH];
-   gat_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm, gv);
-   gat_own_head<LPR, NCH>(a.own_score, row, a.heads, cm, adst);
-   gat_own_head<LPR, NCH>(a.lse_in, row, a.heads, cm, lse);
+   attn_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm.ok, gv);
+   attn_own_head<LPR, NCH>(a.own_score, row, a.heads, cm, adst);
+   attn_own_head<LPR, NCH>(a.lse_in, row, a.heads, cm, lse);
    {                                                   // D[i,h] = <g_i, z_i>_h: every slot holds the row, so every lane of a head ends with it
       float zv[NCH][4];
-      gat_own_row<LPR, NCH>(a.zin, row, a.ldzin, lc, cm, zv);
+      attn_own_row<LPR, NCH>(a.zin, row, a.ldzin, lc, cm.ok, zv);
 #pragma unroll
       for (int j = 0; j < NCH; j++) {
          dsum[j] = 0.0f;
@@ -355,7 +296,7 @@ __global__ __launch_bounds__(WAVES * 64) void gat_bw_rows_kernel(const GatArgs a
    for (int j = 0; j < NCH; j++) acc[j] = 0.0f;
    [[maybe_unused]] const bool store = EDGE && a.dedge != nullptr;      // wave-uniform: a kernel argument
    [[maybe_unused]] unsigned hk[NCH];
-   if constexpr (DROP) gat_drop_heads<LPR, NCH>(a, cm, hk);
+   if constexpr (DROP) attn_drop_heads<LPR, NCH>(a.seed_hi, cm, hk);
 
    const unsigned ldyb = (unsigned)a.ldy * 4u, hb = (unsigned)a.heads * 4u;
    for (int64_t base = eb; base < ee; base += 64) {
@@ -376,9 +317,9 @@ __global__ __launch_bounds__(WAVES * 64) void gat_bw_rows_kernel(const GatArgs a
          for (int u = 0; u < U; u++) {
             unsigned off, offh;
             gat_edge(id_l, (s0 + u * G + g) & 63, ldyb, hb, off, offh);
-            gat_load_wide<LPR, NCH>(rsy, off, cm, yv[u]);
-            gat_load_head<LPR, NCH>(rss, offh, cm, sc[u]);
-            if constexpr (EDGE) gat_load_head<LPR, NCH>(rse, (unsigned)((s0 + u * G + g) & 63) * hb, cm, se[u]);      // a slot past cnt: 0
+            attn_load_wide<LPR, NCH>(rsy, off, cm, yv[u]);
+            attn_load_head<LPR, NCH>(rss, offh, cm, sc[u]);
+            if constexpr (EDGE) attn_load_head<LPR, NCH>(rse, (unsigned)((s0 + u * G + g) & 63) * hb, cm, se[u]);      // a slot past cnt: 0
             if constexpr (DROP) hw[u] = (unsigned)__shfl((int)hw_l, (s0 + u * G + g) & 63);
          }
 #pragma unroll
@@ -433,16 +374,16 @@ __global__ __launch_bounds__(WAVES * 64) void gat_bw_cols_kernel(const GatArgs a
    const int64_t row = (int64_t)blockIdx.x * WAVES + wave;
    if (row >= a.rows) return;
    const int64_t eb = a.pntrb[row], ee = a.pntre[row];
-   const __amdgpu_buffer_rsrc_t rsg = gat_rsrc(a.y, a.ybytes);
-   const __amdgpu_buffer_rsrc_t rs0 = gat_rsrc(a.t0, a.tbytes), rs1 = gat_rsrc(a.t1, a.tbytes), rs2 = gat_rsrc(a.t2, a.tbytes);
+   const __amdgpu_buffer_rsrc_t rsg = attn_rsrc(a.y, a.ybytes);
+   const __amdgpu_buffer_rsrc_t rs0 = attn_rsrc(a.t0, a.tbytes), rs1 = attn_rsrc(a.t1, a.tbytes), rs2 = attn_rsrc(a.t2, a.tbytes);
    [[maybe_unused]] __amdgpu_buffer_rsrc_t rse;         // EDGE: all of a_edge, gathered by CSR position
-   if constexpr (EDGE) rse = gat_rsrc(a.edge, a.ebytes);
-   const GatCols<LPR, NCH> cm(a, lc);
+   if constexpr (EDGE) rse = attn_rsrc(a.edge, a.ebytes);
+   const AttnHeadCols<LPR, NCH> cm(a.k, a.hshift, a.hmask, lc);
    float yv[NCH][4], asrc[NCH];
-   gat_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm, yv);
-   gat_own_head<LPR, NCH>(a.own_score, row, a.heads, cm, asrc);
+   attn_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm.ok, yv);
+   attn_own_head<LPR, NCH>(a.own_score, row, a.heads, cm, asrc);
    [[maybe_unused]] unsigned hk[NCH];
-   if constexpr (DROP) gat_drop_heads<LPR, NCH>(a, cm, hk);
+   if constexpr (DROP) attn_drop_heads<LPR, NCH>(a.seed_hi, cm, hk);
 
    float acc[NCH][4], accs[NCH];
 #pragma unroll
@@ -471,13 +412,13 @@ __global__ __launch_bounds__(WAVES * 64) void gat_bw_cols_kernel(const GatArgs a
          for (int u = 0; u < U; u++) {
             unsigned off, offh;
             gat_edge(id_l, (s0 + u * G + g) & 63, ldgb, hb, off, offh);
-            gat_load_wide<LPR, NCH>(rsg, off, cm, gg[u]);
-            gat_load_head<LPR, NCH>(rs0, offh, cm, ad[u]);
-            gat_load_head<LPR, NCH>(rs1, offh, cm, ls[u]);
-            gat_load_head<LPR, NCH>(rs2, offh, cm, ds[u]);
+            attn_load_wide<LPR, NCH>(rsg, off, cm, gg[u]);
+            attn_load_head<LPR, NCH>(rs0, offh, cm, ad[u]);
+            attn_load_head<LPR, NCH>(rs1, offh, cm, ls[u]);
+            attn_load_head<LPR, NCH>(rs2, offh, cm, ds[u]);
             if constexpr (EDGE) {
                const int ep = __shfl(ep_l, (s0 + u * G + g) & 63);
-               gat_load_head<LPR, NCH>(rse, ep < 0 ? BUF_OOB : (unsigned)ep * hb, cm, se[u]);      // ep * hb < nnz*H*4 <= 3.5 GiB
+               attn_load_head<LPR, NCH>(rse, ep < 0 ? BUF_OOB : (unsigned)ep * hb, cm, se[u]);      // ep * hb < nnz*H*4 <= 3.5 GiB
             }
             if constexpr (DROP) hw[u] = (unsigned)__shfl((int)hw_l, (s0 + u * G + g) & 63);
          }
@@ -539,50 +480,15 @@ static int launch_gat(int which, const GatArgs &a, const char *entry, hipStream_
    return check_launch(entry);
 }
 
-// the width dispatch of attention.hip, up to two chunks per lane; EDGE: the kernels with the per-edge term; DROP: with attention dropout
+// the width ladder (attn_by_width); EDGE: the kernels with the per-edge term; DROP: with attention dropout
 template <bool EDGE, bool DROP>
 static int gat_by_width_of(int which, const GatArgs &a, const char *entry, hipStream_t st) {
-   const int64_t w = (a.k + 3) / 4;
-   if (w <= 8) return launch_gat<8, 1, EDGE, DROP>(which, a, entry, st);
-   if (w <= 16) return launch_gat<16, 1, EDGE, DROP>(which, a, entry, st);
-   if (w <= 32) return launch_gat<32, 1, EDGE, DROP>(which, a, entry, st);
-   if (w <= 64) return launch_gat<64, 1, EDGE, DROP>(which, a, entry, st);
-   return launch_gat<64, 2, EDGE, DROP>(which, a, entry, st);
+   return attn_by_width(a.k, [&](auto lpr, auto nch) { return launch_gat<decltype(lpr)::value, decltype(nch)::value, EDGE, DROP>(which, a, entry, st); });
 }
 
 static int gat_by_width(int which, const GatArgs &a, bool edge, bool drop, const char *entry, hipStream_t st) {
    if (drop) return edge ? gat_by_width_of<true, true>(which, a, entry, st) : gat_by_width_of<false, true>(which, a, entry, st);
    return edge ? gat_by_width_of<true, false>(which, a, entry, st) : gat_by_width_of<false, false>(which, a, entry, st);
-}
-
-// the dropout of one call (isplib_gat_drop_*_hip): the threshold T(p), c = float32(1 / (1 - p)) and the seed; none: the entries without it
-struct GatDrop {
-   bool on;
-   uint32_t threshold;
-   float scale;
-   uint64_t seed;
-};
-static const GatDrop GAT_NO_DROP = {false, 0u, 1.0f, 0ull};
-
-static void gat_set_drop(GatArgs &a, const GatDrop &dr) {
-   a.seed_lo = (unsigned)dr.seed; a.seed_hi = (unsigned)(dr.seed >> 32); a.T = dr.threshold; a.c = dr.scale;
-}
-
-// what a descriptor over `rows` rows of k floats at pitch ld may answer: the extent a row-strided view owns, not rows * ld
-static unsigned gat_extent(int64_t rows, int64_t k, int64_t ld) {
-   return rows <= 0 ? 0u : (unsigned)(((unsigned long long)(rows - 1) * (unsigned long long)ld + (unsigned long long)k) * 4ull);
-}
-
-// the head geometry of a launch; the domain (isplib_gat_serves) has been checked: H == 1, or d a power of two >= 4
-static void gat_heads(GatArgs &a, int64_t heads, int64_t d) {
-   a.heads = (int)heads;
-   if (heads == 1) {
-      a.hshift = 31; a.hlanes = 64; a.hmask = 0x7fffffffu; a.whole = 1;
-   } else {
-      int sh = 0;
-      while ((1LL << sh) < d) sh++;
-      a.hshift = sh; a.hlanes = (int)(d / 4); a.hmask = (unsigned)(d - 1); a.whole = 0;
-   }
 }
 
 static const char *const GAT_DOMAIN = "outside isplib_gat_serves(rows_gathered, heads, d, ld): 1 <= heads, 1 <= d, heads*d <= 512, heads == 1 or "
@@ -594,7 +500,7 @@ static const char *const GAT_EDGE_DOMAIN = "outside isplib_gat_edge_serves(nnz, 
 static int gat_forward(const char *entry, bool edge, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
                        const int64_t *pntre, const float *a_dst, const float *y, int64_t ldy, const float *a_src, const float *a_edge,
                        int64_t heads, float negative_slope, float *z, int64_t ldz, float *lse, void *stream,
-                       const GatDrop &dr = GAT_NO_DROP) {
+                       const AttnDrop &dr = ATTN_NO_DROP) {
    clear_error();
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
    if (m == 0 || k == 0) return ISPLIB_SUCCESS;
@@ -606,13 +512,13 @@ static int gat_forward(const char *entry, bool edge, int64_t m, int64_t n, int64
    if (edge && !isplib_gat_edge_serves(nnz, heads)) return fail(ISPLIB_NO_OPT_IMPL, entry, GAT_EDGE_DOMAIN);
    GatArgs a = {};
    a.rows = m; a.k = k; a.indx = indx; a.pntrb = pntrb; a.pntre = pntre; a.ns = negative_slope;
-   gat_heads(a, heads, k / heads);
+   attn_head_geometry(heads, k / heads, a.heads, a.hshift, a.hlanes, a.hmask, a.whole);
    a.own_score = a_dst;
    a.out = z; a.ldout = ldz; a.hout = lse;
-   a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? gat_extent(n, k, ldy) : 0u;
-   a.t0 = a_src; a.tbytes = nnz > 0 ? gat_extent(n, heads, heads) : 0u;
+   a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? attn_extent(n, k, ldy) : 0u;
+   a.t0 = a_src; a.tbytes = nnz > 0 ? attn_extent(n, heads, heads) : 0u;
    a.edge = edge ? a_edge : nullptr;
-   gat_set_drop(a, dr);
+   attn_set_drop(dr, a.seed_lo, a.seed_hi, a.T, a.c);
    return gat_by_width(GAT_FW, a, edge, dr.on, entry, (hipStream_t)stream);
 }
 
@@ -620,7 +526,7 @@ static int gat_backward_rows(const char *entry, bool edge, int64_t m, int64_t n,
                              const int64_t *pntrb, const int64_t *pntre, const float *a_dst, const float *y, int64_t ldy, const float *a_src,
                              const float *a_edge, int64_t heads, float negative_slope, const float *g, int64_t ldg, const float *z,
                              int64_t ldz, const float *lse, float *d_a_dst, float *dsum, float *d_a_edge, void *stream,
-                             const GatDrop &dr = GAT_NO_DROP) {
+                             const AttnDrop &dr = ATTN_NO_DROP) {
    clear_error();
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
    if (m == 0 || k == 0) return ISPLIB_SUCCESS;
@@ -632,13 +538,13 @@ static int gat_backward_rows(const char *entry, bool edge, int64_t m, int64_t n,
    if (edge && !isplib_gat_edge_serves(nnz, heads)) return fail(ISPLIB_NO_OPT_IMPL, entry, GAT_EDGE_DOMAIN);
    GatArgs a = {};
    a.rows = m; a.k = k; a.indx = indx; a.pntrb = pntrb; a.pntre = pntre; a.ns = negative_slope;
-   gat_heads(a, heads, k / heads);
+   attn_head_geometry(heads, k / heads, a.heads, a.hshift, a.hlanes, a.hmask, a.whole);
    a.own = g; a.ldown = ldg; a.own_score = a_dst; a.zin = z; a.ldzin = ldz; a.lse_in = lse;
    a.hout = d_a_dst; a.hout2 = dsum;
-   a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? gat_extent(n, k, ldy) : 0u;
-   a.t0 = a_src; a.tbytes = nnz > 0 ? gat_extent(n, heads, heads) : 0u;
+   a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? attn_extent(n, k, ldy) : 0u;
+   a.t0 = a_src; a.tbytes = nnz > 0 ? attn_extent(n, heads, heads) : 0u;
    a.edge = edge ? a_edge : nullptr; a.dedge = edge ? d_a_edge : nullptr;
-   gat_set_drop(a, dr);
+   attn_set_drop(dr, a.seed_lo, a.seed_hi, a.T, a.c);
    return gat_by_width(GAT_BW_ROWS, a, edge, dr.on, entry, (hipStream_t)stream);
 }
 
@@ -646,7 +552,7 @@ static int gat_backward_cols(const char *entry, bool edge, int64_t m, int64_t n,
                              const int64_t *colb, const int64_t *cole, const int64_t *csr2csc, const float *a_dst, const float *y, int64_t ldy,
                              const float *a_src, const float *a_edge, int64_t heads, float negative_slope, const float *g, int64_t ldg,
                              const float *lse, const float *dsum, float *dy, int64_t lddy, float *d_a_src, void *stream,
-                             const GatDrop &dr = GAT_NO_DROP) {
+                             const AttnDrop &dr = ATTN_NO_DROP) {
    clear_error();
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
    if (n == 0 || k == 0) return ISPLIB_SUCCESS;
@@ -659,16 +565,16 @@ static int gat_backward_cols(const char *entry, bool edge, int64_t m, int64_t n,
    if (edge && !isplib_gat_edge_serves(nnz, heads)) return fail(ISPLIB_NO_OPT_IMPL, entry, GAT_EDGE_DOMAIN);
    GatArgs a = {};
    a.rows = n; a.k = k; a.indx = row_t; a.pntrb = colb; a.pntre = cole; a.ns = negative_slope;
-   gat_heads(a, heads, k / heads);
+   attn_head_geometry(heads, k / heads, a.heads, a.hshift, a.hlanes, a.hmask, a.whole);
    a.own = y; a.ldown = ldy; a.own_score = a_src;
    a.out = dy; a.ldout = lddy; a.hout = d_a_src;
-   a.y = g; a.ldy = ldg; a.ybytes = nnz > 0 ? gat_extent(m, k, ldg) : 0u;
-   a.t0 = a_dst; a.t1 = lse; a.t2 = dsum; a.tbytes = nnz > 0 ? gat_extent(m, heads, heads) : 0u;
+   a.y = g; a.ldy = ldg; a.ybytes = nnz > 0 ? attn_extent(m, k, ldg) : 0u;
+   a.t0 = a_dst; a.t1 = lse; a.t2 = dsum; a.tbytes = nnz > 0 ? attn_extent(m, heads, heads) : 0u;
    if (edge) {
-      a.edge = a_edge; a.ebytes = nnz > 0 ? gat_extent(nnz, heads, heads) : 0u;
+      a.edge = a_edge; a.ebytes = nnz > 0 ? attn_extent(nnz, heads, heads) : 0u;
    }
    if (edge || dr.on) a.epos = csr2csc;                  // DROP: the keep bit is a function of the entry's CSR position
-   gat_set_drop(a, dr);
+   attn_set_drop(dr, a.seed_lo, a.seed_hi, a.T, a.c);
    return gat_by_width(GAT_BW_COLS, a, edge, dr.on, entry, (hipStream_t)stream);
 }
 
@@ -745,7 +651,7 @@ extern "C" int isplib_gat_drop_csr_hip(int64_t m, int64_t n, int64_t k, int64_t 
    clear_error();
    if (!gat_drop_ok(scale)) return fail(ISPLIB_FAIL, "isplib_gat_drop_csr_hip", "scale must be a positive finite number");
    return gat_forward("isplib_gat_drop_csr_hip", a_edge != nullptr, m, n, k, nnz, indx, pntrb, pntre, a_dst, y, ldy, a_src, a_edge, heads,
-                      negative_slope, z, ldz, lse, stream, GatDrop{true, threshold, scale, seed});
+                      negative_slope, z, ldz, lse, stream, AttnDrop{true, threshold, scale, seed});
 }
 
 extern "C" int isplib_gat_drop_bw_rows_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
@@ -756,7 +662,7 @@ extern "C" int isplib_gat_drop_bw_rows_hip(int64_t m, int64_t n, int64_t k, int6
    clear_error();
    if (!gat_drop_ok(scale)) return fail(ISPLIB_FAIL, "isplib_gat_drop_bw_rows_hip", "scale must be a positive finite number");
    return gat_backward_rows("isplib_gat_drop_bw_rows_hip", a_edge != nullptr, m, n, k, nnz, indx, pntrb, pntre, a_dst, y, ldy, a_src, a_edge,
-                            heads, negative_slope, g, ldg, z, ldz, lse, d_a_dst, dsum, d_a_edge, stream, GatDrop{true, threshold, scale, seed});
+                            heads, negative_slope, g, ldg, z, ldz, lse, d_a_dst, dsum, d_a_edge, stream, AttnDrop{true, threshold, scale, seed});
 }
 
 extern "C" int isplib_gat_drop_bw_cols_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t, const int64_t *colb,
@@ -767,5 +673,5 @@ extern "C" int isplib_gat_drop_bw_cols_hip(int64_t m, int64_t n, int64_t k, int6
    clear_error();
    if (!gat_drop_ok(scale)) return fail(ISPLIB_FAIL, "isplib_gat_drop_bw_cols_hip", "scale must be a positive finite number");
    return gat_backward_cols("isplib_gat_drop_bw_cols_hip", a_edge != nullptr, m, n, k, nnz, row_t, colb, cole, csr2csc, a_dst, y, ldy, a_src,
-                            a_edge, heads, negative_slope, g, ldg, lse, dsum, dy, lddy, d_a_src, stream, GatDrop{true, threshold, scale, seed});
+                            a_edge, heads, negative_slope, g, ldg, lse, dsum, dy, lddy, d_a_src, stream, AttnDrop{true, threshold, scale, seed});
 }

@@ -39,6 +39,7 @@
 #include "common.h"
 #include "gather.h"
 #include "half16.h"
+#include "attn16_common.h"
 
 namespace isplib {
 
@@ -68,45 +69,6 @@ struct Gat16Args {
    unsigned tbytes;
 };
 
-// this lane's eight consecutive columns and their head; ok[q]: the dword of columns (2q, 2q + 1) lies inside the row (k is even)
-struct Gat16Cols {
-   int col, head;
-   unsigned cbyte, hbyte, poison;            // past k: an offset the descriptors answer with 0
-   bool ok[4], first;                        // first: this lane opens a head (and lies inside k)
-   __device__ __forceinline__ Gat16Cols(const Gat16Args &a, int lc) {
-      col = lc * 8;
-      cbyte = (unsigned)col * 2u;
-      poison = col < (int)a.k ? 0u : BUF_OOB;
-      head = col >> a.hshift;
-      hbyte = (unsigned)head * 4u;
-      first = col < (int)a.k && ((unsigned)col & a.hmask) == 0u;
-#pragma unroll
-      for (int q = 0; q < 4; q++) ok[q] = col + 2 * q < (int)a.k;
-   }
-};
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t gat16_desc(const void *p, unsigned bytes) {
-   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
-}
-
-// this lane's columns of row `row` of a dense 16-bit operand as floats; plain dword loads (base, pitch and column are even), nothing
-// outside the row's k columns is read
-template <int ELT>
-__device__ __forceinline__ void gat16_own_row(const unsigned short *base, int64_t row, int64_t ld, const Gat16Cols &cm, float (&r)[8]) {
-   const unsigned *p = reinterpret_cast<const unsigned *>(base + (size_t)row * (size_t)ld + (size_t)cm.col);
-#pragma unroll
-   for (int q = 0; q < 4; q++) {
-      unsigned w = 0u;
-      if (cm.ok[q]) w = p[q];
-      widen2<ELT>(w, r[2 * q], r[2 * q + 1]);
-   }
-}
-
-// entry [row, this lane's head] of a dense fp32 [rows, H] table; a lane past k reads nothing
-__device__ __forceinline__ float gat16_own_head(const float *base, int64_t row, int heads, const Gat16Cols &cm) {
-   return cm.poison == 0u ? base[(size_t)row * (size_t)heads + (size_t)cm.head] : 0.0f;
-}
-
 // byte offsets of the gathered row of edge `src` of the batch in the wide operand and in the [., H] tables; a dead edge: BUF_OOB
 __device__ __forceinline__ void gat16_edge(int id_l, int src, unsigned ldb, unsigned hb, unsigned &off, unsigned &offh) {
    const int id = __shfl(id_l, src);
@@ -114,60 +76,17 @@ __device__ __forceinline__ void gat16_edge(int id_l, int src, unsigned ldb, unsi
    offh = id < 0 ? BUF_OOB : (unsigned)id * hb;              // BUF_OOB + cbyte / hbyte (< 2^10) cannot wrap
 }
 
-__device__ __forceinline__ v4i_t gat16_load_wide(const __amdgpu_buffer_rsrc_t rsrc, unsigned off, const Gat16Cols &cm) {
-   return __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)((off + cm.cbyte) | cm.poison), 0, 0);
-}
-
-__device__ __forceinline__ float gat16_load_head(const __amdgpu_buffer_rsrc_t rsrc, unsigned offh, const Gat16Cols &cm) {
-   return __int_as_float((int)__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)((offh + cm.hbyte) | cm.poison), 0, 0));
-}
-
-// a gathered vector as eight floats; a dword the 16-byte load brought from outside the row is dropped by a select, not a multiply
-template <int ELT> __device__ __forceinline__ void gat16_widen(const v4i_t &t, const Gat16Cols &cm, float (&y)[8]) {
-#pragma unroll
-   for (int q = 0; q < 4; q++) widen2<ELT>(cm.ok[q] ? (unsigned)t[q] : 0u, y[2 * q], y[2 * q + 1]);
-}
-
-// sum over the lanes that share a head (an aligned group of `hlanes` lanes, a power of two; H == 1: the whole slot); every lane of the
-// group ends with the same bits (each level adds the same two numbers on both sides).  hlanes == 1: no cross-lane step is taken
-template <int LPR, int O = 1> __device__ __forceinline__ float gat16_head_sum(float v, int hlanes) {
-   if constexpr (O < LPR) {
-      const float w = lane_xor<O>(v);        // partners 1, 2, 4, 8 by DPP moves inside the 16-lane row (gather.h), wider ones by ds_bpermute
-      return gat16_head_sum<LPR, 2 * O>(O < hlanes ? v + w : v, hlanes);
-   } else {
-      return v;
-   }
-}
-
 // <r, y>_h: over this lane's eight columns, then over the head's lanes
 template <int LPR> __device__ __forceinline__ float gat16_head_dot(const float (&r)[8], const float (&y)[8], int hlanes) {
-   float d = 0.0f;
-#pragma unroll
-   for (int v = 0; v < 8; v++) d = fmaf(r[v], y[v], d);
-   return gat16_head_sum<LPR>(d, hlanes);
+   float d[1] = {attn16_dot_part(r, y)};
+   attn16_head_sum<LPR, 1>(d, hlanes);
+   return d[0];
 }
 
 __device__ __forceinline__ float gat16_score(float adst, float asrc, float ns, float &slope) {
    const float u = adst + asrc;              // ONE fp32 add: its sign is the sign of the exact sum
    slope = u > 0.0f ? 1.0f : ns;
    return u > 0.0f ? u : ns * u;
-}
-
-// the lane's eight finished columns, rounded once; only the dwords inside the row are written
-template <int ELT>
-__device__ __forceinline__ void gat16_store_row(unsigned short *base, int64_t row, int64_t ld, const Gat16Cols &cm, const float (&r)[8]) {
-   if (cm.poison != 0u) return;
-   unsigned *p = reinterpret_cast<unsigned *>(base + (size_t)row * (size_t)ld + (size_t)cm.col);
-   unsigned d[4];
-#pragma unroll
-   for (int q = 0; q < 4; q++) d[q] = narrow2<ELT>(r[2 * q], r[2 * q + 1]);
-   if (cm.ok[3] && ((uintptr_t)p & 15) == 0) {
-      *reinterpret_cast<uint4 *>(p) = make_uint4(d[0], d[1], d[2], d[3]);
-   } else {
-#pragma unroll
-      for (int q = 0; q < 4; q++)
-         if (cm.ok[q]) p[q] = d[q];
-   }
 }
 
 template <int ELT, int LPR, int WAVES>
@@ -179,9 +98,9 @@ __global__ __launch_bounds__(WAVES * 64) void gat16_fw_kernel(const Gat16Args a)
    const int64_t row = (int64_t)blockIdx.x * WAVES + wave;
    if (row >= a.rows) return;
    const int64_t eb = a.pntrb[row], ee = a.pntre[row];
-   const __amdgpu_buffer_rsrc_t rsy = gat16_desc(a.y, a.ybytes), rss = gat16_desc(a.t0, a.tbytes);
-   const Gat16Cols cm(a, lc);
-   const float adst = gat16_own_head(a.own_score, row, a.heads, cm);
+   const __amdgpu_buffer_rsrc_t rsy = attn16_desc(a.y, a.ybytes), rss = attn16_desc(a.t0, a.tbytes);
+   const Attn16HeadCols cm(a.k, a.hshift, a.hmask, lc);
+   const float adst = attn16_own_head(a.own_score, row, a.heads, cm);
 
    float mrun = GAT16_NONE, l = 0.0f, acc[8];
 #pragma unroll
@@ -201,8 +120,8 @@ __global__ __launch_bounds__(WAVES * 64) void gat16_fw_kernel(const Gat16Args a)
          for (int u = 0; u < U; u++) {
             unsigned off, offh;
             gat16_edge(id_l, (s0 + u * G + g) & 63, ldyb, hb, off, offh);
-            yv[u] = gat16_load_wide(rsy, off, cm);
-            sc[u] = gat16_load_head(rss, offh, cm);
+            yv[u] = attn16_load_wide(rsy, off, cm);
+            sc[u] = attn16_load_head(rss, offh, cm);
          }
          float mnew = mrun;
 #pragma unroll
@@ -221,7 +140,7 @@ __global__ __launch_bounds__(WAVES * 64) void gat16_fw_kernel(const Gat16Args a)
             const float w = (s0 + u * G + g < cnt) ? __expf(sc[u] - mnew) : 0.0f;
             l += w;
             float y8[8];
-            gat16_widen<ELT>(yv[u], cm, y8);
+            attn16_widen<ELT>(yv[u], cm.ok, y8);
 #pragma unroll
             for (int v = 0; v < 8; v++) acc[v] = fmaf(w, y8[v], acc[v]);
          }
@@ -243,7 +162,7 @@ __global__ __launch_bounds__(WAVES * 64) void gat16_fw_kernel(const Gat16Args a)
    float zr[8];
 #pragma unroll
    for (int v = 0; v < 8; v++) zr[v] = empty ? 0.0f : acc[v] / l;
-   gat16_store_row<ELT>(a.out, row, a.ldout, cm, zr);
+   attn16_store_row<ELT>(a.out, row, a.ldout, cm.col, cm.ok, zr);
    if (cm.first) a.hout[(size_t)row * (size_t)a.heads + (size_t)cm.head] = empty ? -INFINITY : mrun + logf(l);
 }
 
@@ -257,11 +176,11 @@ __global__ __launch_bounds__(WAVES * 64) void gat16_bw_rows_kernel(const Gat16Ar
    const int64_t row = (int64_t)blockIdx.x * WAVES + wave;
    if (row >= a.rows) return;
    const int64_t eb = a.pntrb[row], ee = a.pntre[row];
-   const __amdgpu_buffer_rsrc_t rsy = gat16_desc(a.y, a.ybytes), rss = gat16_desc(a.t0, a.tbytes);
-   const Gat16Cols cm(a, lc);
+   const __amdgpu_buffer_rsrc_t rsy = attn16_desc(a.y, a.ybytes), rss = attn16_desc(a.t0, a.tbytes);
+   const Attn16HeadCols cm(a.k, a.hshift, a.hmask, lc);
    float gv[8];
-   gat16_own_row<ELT>(a.own, row, a.ldown, cm, gv);
-   const float adst = gat16_own_head(a.own_score, row, a.heads, cm), lse = gat16_own_head(a.lse_in, row, a.heads, cm);
+   attn16_own_row<ELT>(a.own, row, a.ldown, cm.col, cm.ok, gv);
+   const float adst = attn16_own_head(a.own_score, row, a.heads, cm), lse = attn16_own_head(a.lse_in, row, a.heads, cm);
 
    float l = 0.0f, dacc = 0.0f, pacc = 0.0f, qacc = 0.0f;      // sum a_e, sum a_e t_e, sum a_e sl_e t_e, sum a_e sl_e
 
@@ -279,13 +198,13 @@ __global__ __launch_bounds__(WAVES * 64) void gat16_bw_rows_kernel(const Gat16Ar
          for (int u = 0; u < U; u++) {
             unsigned off, offh;
             gat16_edge(id_l, (s0 + u * G + g) & 63, ldyb, hb, off, offh);
-            yv[u] = gat16_load_wide(rsy, off, cm);
-            sc[u] = gat16_load_head(rss, offh, cm);
+            yv[u] = attn16_load_wide(rsy, off, cm);
+            sc[u] = attn16_load_head(rss, offh, cm);
          }
 #pragma unroll
          for (int u = 0; u < U; u++) {
             float y8[8];
-            gat16_widen<ELT>(yv[u], cm, y8);
+            attn16_widen<ELT>(yv[u], cm.ok, y8);
             const float t = gat16_head_dot<LPR>(gv, y8, a.hlanes);      // every lane takes part: not under `live`
             const bool live = s0 + u * G + g < cnt;
             float slope;
@@ -323,12 +242,12 @@ __global__ __launch_bounds__(WAVES * 64) void gat16_bw_cols_kernel(const Gat16Ar
    const int64_t row = (int64_t)blockIdx.x * WAVES + wave;
    if (row >= a.rows) return;
    const int64_t eb = a.pntrb[row], ee = a.pntre[row];
-   const __amdgpu_buffer_rsrc_t rsg = gat16_desc(a.y, a.ybytes);
-   const __amdgpu_buffer_rsrc_t rs0 = gat16_desc(a.t0, a.tbytes), rs1 = gat16_desc(a.t1, a.tbytes), rs2 = gat16_desc(a.t2, a.tbytes);
-   const Gat16Cols cm(a, lc);
+   const __amdgpu_buffer_rsrc_t rsg = attn16_desc(a.y, a.ybytes);
+   const __amdgpu_buffer_rsrc_t rs0 = attn16_desc(a.t0, a.tbytes), rs1 = attn16_desc(a.t1, a.tbytes), rs2 = attn16_desc(a.t2, a.tbytes);
+   const Attn16HeadCols cm(a.k, a.hshift, a.hmask, lc);
    float yv[8];
-   gat16_own_row<ELT>(a.own, row, a.ldown, cm, yv);
-   const float asrc = gat16_own_head(a.own_score, row, a.heads, cm);
+   attn16_own_row<ELT>(a.own, row, a.ldown, cm.col, cm.ok, yv);
+   const float asrc = attn16_own_head(a.own_score, row, a.heads, cm);
 
    float acc[8], accs = 0.0f;
 #pragma unroll
@@ -348,15 +267,15 @@ __global__ __launch_bounds__(WAVES * 64) void gat16_bw_cols_kernel(const Gat16Ar
          for (int u = 0; u < U; u++) {
             unsigned off, offh;
             gat16_edge(id_l, (s0 + u * G + g) & 63, ldgb, hb, off, offh);
-            gg[u] = gat16_load_wide(rsg, off, cm);
-            ad[u] = gat16_load_head(rs0, offh, cm);
-            ls[u] = gat16_load_head(rs1, offh, cm);
-            ds[u] = gat16_load_head(rs2, offh, cm);
+            gg[u] = attn16_load_wide(rsg, off, cm);
+            ad[u] = attn16_load_head(rs0, offh, cm);
+            ls[u] = attn16_load_head(rs1, offh, cm);
+            ds[u] = attn16_load_head(rs2, offh, cm);
          }
 #pragma unroll
          for (int u = 0; u < U; u++) {
             float g8[8];
-            gat16_widen<ELT>(gg[u], cm, g8);
+            attn16_widen<ELT>(gg[u], cm.ok, g8);
             const float t = gat16_head_dot<LPR>(yv, g8, a.hlanes);      // every lane takes part: not under `live`
             const bool live = s0 + u * G + g < cnt;
             float slope;
@@ -375,7 +294,7 @@ __global__ __launch_bounds__(WAVES * 64) void gat16_bw_cols_kernel(const Gat16Ar
       for (int v = 0; v < 8; v++) acc[v] += __shfl_xor(acc[v], o);
    }
    if (g != 0) return;
-   gat16_store_row<ELT>(a.out, row, a.ldout, cm, acc);      // no incoming entry: 0
+   attn16_store_row<ELT>(a.out, row, a.ldout, cm.col, cm.ok, acc);      // no incoming entry: 0
    if (cm.first) a.hout[(size_t)row * (size_t)a.heads + (size_t)cm.head] = accs;
 }
 
@@ -393,46 +312,16 @@ static int launch_gat16(int which, const Gat16Args &a, const char *entry, hipStr
    return check_launch(entry);
 }
 
-// the slot width by ceil(k / 8) 16-byte vectors per row, always one chunk per lane
-template <int ELT>
-static int gat16_by_width(int which, const Gat16Args &a, const char *entry, hipStream_t st) {
-   const int64_t w = (a.k + 7) / 8;
-   if (w <= 4) return launch_gat16<ELT, 4>(which, a, entry, st);
-   if (w <= 8) return launch_gat16<ELT, 8>(which, a, entry, st);
-   if (w <= 16) return launch_gat16<ELT, 16>(which, a, entry, st);
-   if (w <= 32) return launch_gat16<ELT, 32>(which, a, entry, st);
-   return launch_gat16<ELT, 64>(which, a, entry, st);
-}
-
+// the element type and the slot width (attn16_run)
 static int gat16_run(int dtype, int which, const Gat16Args &a, const char *entry, void *stream) {
-   return dtype == ISPLIB_DTYPE_BF16 ? gat16_by_width<ELT_BF16>(which, a, entry, (hipStream_t)stream)
-                                     : gat16_by_width<ELT_F16>(which, a, entry, (hipStream_t)stream);
+   return attn16_run(dtype, a.k, [&](auto elt, auto lpr) {
+      return launch_gat16<decltype(elt)::value, decltype(lpr)::value>(which, a, entry, (hipStream_t)stream);
+   });
 }
 
-// what a descriptor over `rows` rows of k elements of `size` bytes at pitch ld may answer: the extent a row-strided view owns
-static unsigned gat16_extent(int64_t rows, int64_t k, int64_t ld, unsigned size) {
-   return rows <= 0 ? 0u : (unsigned)(((unsigned long long)(rows - 1) * (unsigned long long)ld + (unsigned long long)k) * size);
-}
-
-// the head geometry of a launch; the domain (isplib_gat16_serves) has been checked: H == 1, or d a power of two >= 8
-static void gat16_heads(Gat16Args &a, int64_t heads, int64_t d) {
-   a.heads = (int)heads;
-   if (heads == 1) {
-      a.hshift = 31; a.hlanes = 64; a.hmask = 0x7fffffffu;
-   } else {
-      int sh = 0;
-      while ((1LL << sh) < d) sh++;
-      a.hshift = sh; a.hlanes = (int)(d / 8); a.hmask = (unsigned)(d - 1);
-   }
-}
-
-static const char *const GAT16_DTYPE = "dtype must be ISPLIB_DTYPE_BF16 or ISPLIB_DTYPE_F16";
 static const char *const GAT16_DOMAIN = "outside isplib_gat16_serves(rows_gathered, heads, d, ld): 1 <= heads, 8 <= heads*d <= 512, heads == 1 with d "
                                         "even or d a power of two >= 8, every pitch even, ld >= heads*d, rows_gathered < 2^31, "
                                         "rows_gathered*ld*2 <= 3.5 GiB (convert the operands and use the fp32 entries)";
-
-static bool gat16_even(int64_t a, int64_t b) { return ((a | b) & 1) == 0; }
-static bool gat16_aligned(const void *a, const void *b, const void *c = nullptr) { return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 3) == 0; }
 
 }  // namespace isplib
 
@@ -451,21 +340,21 @@ extern "C" int isplib_gat16_csr_hip(int dtype, int64_t m, int64_t n, int64_t k, 
                                     float negative_slope, void *z, int64_t ldz, float *lse, void *stream) {
    const char *entry = "isplib_gat16_csr_hip";
    clear_error();
-   if (dtype != ISPLIB_DTYPE_BF16 && dtype != ISPLIB_DTYPE_F16) return fail(ISPLIB_FAIL, entry, GAT16_DTYPE);
+   if (dtype != ISPLIB_DTYPE_BF16 && dtype != ISPLIB_DTYPE_F16) return fail(ISPLIB_FAIL, entry, ATTN16_DTYPE);
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
    if (m == 0 || k == 0) return ISPLIB_SUCCESS;
    if (ldz < k) return fail(ISPLIB_FAIL, entry, "leading dimension smaller than k");
    if (heads >= 1 && k % heads != 0) return fail(ISPLIB_FAIL, entry, "k is not a multiple of heads");
-   if (heads < 1 || !isplib_gat16_serves(n, heads, k / heads, ldy) || !gat16_even(ldz, 0)) return fail(ISPLIB_NO_OPT_IMPL, entry, GAT16_DOMAIN);
+   if (heads < 1 || !isplib_gat16_serves(n, heads, k / heads, ldy) || !attn16_even(ldz, 0)) return fail(ISPLIB_NO_OPT_IMPL, entry, GAT16_DOMAIN);
    if (!pntrb || !pntre || !a_dst || !z || !lse || (nnz > 0 && (!indx || !y || !a_src))) return fail(ISPLIB_FAIL, entry, "null operand");
-   if (!gat16_aligned(y, z)) return fail(ISPLIB_FAIL, entry, "y and z must be 4-byte aligned");
+   if (!attn16_aligned(y, z)) return fail(ISPLIB_FAIL, entry, "y and z must be 4-byte aligned");
    Gat16Args a = {};
    a.rows = m; a.k = k; a.indx = indx; a.pntrb = pntrb; a.pntre = pntre; a.ns = negative_slope;
-   gat16_heads(a, heads, k / heads);
+   attn16_head_geometry(heads, k / heads, a.heads, a.hshift, a.hlanes, a.hmask);
    a.own_score = a_dst;
    a.out = reinterpret_cast<unsigned short *>(z); a.ldout = ldz; a.hout = lse;
-   a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? gat16_extent(n, k, ldy, 2u) : 0u;
-   a.t0 = a_src; a.tbytes = nnz > 0 ? gat16_extent(n, heads, heads, 4u) : 0u;
+   a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? attn16_extent(n, k, ldy, 2u) : 0u;
+   a.t0 = a_src; a.tbytes = nnz > 0 ? attn16_extent(n, heads, heads, 4u) : 0u;
    return gat16_run(dtype, GAT16_FW, a, entry, stream);
 }
 
@@ -475,22 +364,22 @@ extern "C" int isplib_gat16_bw_rows_hip(int dtype, int64_t m, int64_t n, int64_t
                                         void *stream) {
    const char *entry = "isplib_gat16_bw_rows_hip";
    clear_error();
-   if (dtype != ISPLIB_DTYPE_BF16 && dtype != ISPLIB_DTYPE_F16) return fail(ISPLIB_FAIL, entry, GAT16_DTYPE);
+   if (dtype != ISPLIB_DTYPE_BF16 && dtype != ISPLIB_DTYPE_F16) return fail(ISPLIB_FAIL, entry, ATTN16_DTYPE);
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
    if (m == 0 || k == 0) return ISPLIB_SUCCESS;
    if (ldg < k) return fail(ISPLIB_FAIL, entry, "leading dimension smaller than k");
    if (heads >= 1 && k % heads != 0) return fail(ISPLIB_FAIL, entry, "k is not a multiple of heads");
-   if (heads < 1 || !isplib_gat16_serves(n, heads, k / heads, ldy) || !gat16_even(ldg, 0)) return fail(ISPLIB_NO_OPT_IMPL, entry, GAT16_DOMAIN);
+   if (heads < 1 || !isplib_gat16_serves(n, heads, k / heads, ldy) || !attn16_even(ldg, 0)) return fail(ISPLIB_NO_OPT_IMPL, entry, GAT16_DOMAIN);
    if (!pntrb || !pntre || !a_dst || !g || !lse || !d_a_dst || !dsum || (nnz > 0 && (!indx || !y || !a_src)))
       return fail(ISPLIB_FAIL, entry, "null operand");
-   if (!gat16_aligned(y, g)) return fail(ISPLIB_FAIL, entry, "y and g must be 4-byte aligned");
+   if (!attn16_aligned(y, g)) return fail(ISPLIB_FAIL, entry, "y and g must be 4-byte aligned");
    Gat16Args a = {};
    a.rows = m; a.k = k; a.indx = indx; a.pntrb = pntrb; a.pntre = pntre; a.ns = negative_slope;
-   gat16_heads(a, heads, k / heads);
+   attn16_head_geometry(heads, k / heads, a.heads, a.hshift, a.hlanes, a.hmask);
    a.own = reinterpret_cast<const unsigned short *>(g); a.ldown = ldg; a.own_score = a_dst; a.lse_in = lse;
    a.hout = d_a_dst; a.hout2 = dsum;
-   a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? gat16_extent(n, k, ldy, 2u) : 0u;
-   a.t0 = a_src; a.tbytes = nnz > 0 ? gat16_extent(n, heads, heads, 4u) : 0u;
+   a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? attn16_extent(n, k, ldy, 2u) : 0u;
+   a.t0 = a_src; a.tbytes = nnz > 0 ? attn16_extent(n, heads, heads, 4u) : 0u;
    return gat16_run(dtype, GAT16_BW_ROWS, a, entry, stream);
 }
 
@@ -500,21 +389,21 @@ extern "C" int isplib_gat16_bw_cols_hip(int dtype, int64_t m, int64_t n, int64_t
                                         int64_t lddy, float *d_a_src, void *stream) {
    const char *entry = "isplib_gat16_bw_cols_hip";
    clear_error();
-   if (dtype != ISPLIB_DTYPE_BF16 && dtype != ISPLIB_DTYPE_F16) return fail(ISPLIB_FAIL, entry, GAT16_DTYPE);
+   if (dtype != ISPLIB_DTYPE_BF16 && dtype != ISPLIB_DTYPE_F16) return fail(ISPLIB_FAIL, entry, ATTN16_DTYPE);
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
    if (n == 0 || k == 0) return ISPLIB_SUCCESS;
    if (ldy < k || lddy < k) return fail(ISPLIB_FAIL, entry, "leading dimension smaller than k");
    if (heads >= 1 && k % heads != 0) return fail(ISPLIB_FAIL, entry, "k is not a multiple of heads");
-   if (heads < 1 || !isplib_gat16_serves(m, heads, k / heads, ldg) || !gat16_even(ldy, lddy)) return fail(ISPLIB_NO_OPT_IMPL, entry, GAT16_DOMAIN);
+   if (heads < 1 || !isplib_gat16_serves(m, heads, k / heads, ldg) || !attn16_even(ldy, lddy)) return fail(ISPLIB_NO_OPT_IMPL, entry, GAT16_DOMAIN);
    if (!colb || !cole || !y || !a_src || !dy || !d_a_src || (nnz > 0 && (!row_t || !a_dst || !g || !lse || !dsum)))
       return fail(ISPLIB_FAIL, entry, "null operand");
-   if (!gat16_aligned(y, g, dy)) return fail(ISPLIB_FAIL, entry, "y, g and dy must be 4-byte aligned");
+   if (!attn16_aligned(y, g, dy)) return fail(ISPLIB_FAIL, entry, "y, g and dy must be 4-byte aligned");
    Gat16Args a = {};
    a.rows = n; a.k = k; a.indx = row_t; a.pntrb = colb; a.pntre = cole; a.ns = negative_slope;
-   gat16_heads(a, heads, k / heads);
+   attn16_head_geometry(heads, k / heads, a.heads, a.hshift, a.hlanes, a.hmask);
    a.own = reinterpret_cast<const unsigned short *>(y); a.ldown = ldy; a.own_score = a_src;
    a.out = reinterpret_cast<unsigned short *>(dy); a.ldout = lddy; a.hout = d_a_src;
-   a.y = g; a.ldy = ldg; a.ybytes = nnz > 0 ? gat16_extent(m, k, ldg, 2u) : 0u;
-   a.t0 = a_dst; a.t1 = lse; a.t2 = dsum; a.tbytes = nnz > 0 ? gat16_extent(m, heads, heads, 4u) : 0u;
+   a.y = g; a.ldy = ldg; a.ybytes = nnz > 0 ? attn16_extent(m, k, ldg, 2u) : 0u;
+   a.t0 = a_dst; a.t1 = lse; a.t2 = dsum; a.tbytes = nnz > 0 ? attn16_extent(m, heads, heads, 4u) : 0u;
    return gat16_run(dtype, GAT16_BW_COLS, a, entry, stream);
 }

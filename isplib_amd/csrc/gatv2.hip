@@ -25,8 +25,8 @@
 // g_i (16 bytes each) and lse, D of [i, head] (4 bytes each, two tables, each behind its own descriptor), and writes dy.
 //
 // Every gathered table sits behind a buffer descriptor of exactly the extent it owns; dead edges and lanes past k carry BUF_OOB, which
-// the descriptor answers with 0.  No atomics, a fixed order of operations: two launches give equal bits.  gat.hip and attention.hip are
-// untouched; their small helpers are restated here under names of their own.  DESIGN.md 4.6f.
+// the descriptor answers with 0.  No atomics, a fixed order of operations: two launches give equal bits.  The column map, the
+// descriptor, the gathers and the butterfly are those of attn_common.h, shared with gat.hip and mha.hip.  DESIGN.md 4.6f, 4.6n.
 //
 // Attention dropout (include/isplib_hip_gatv2_drop.h: isplib_gatv2_drop_*_hip): the three kernels are templates on
 // DROP.  Every stored entry e and head h has a keep bit q_e,h = word(seed, CSR position of e, h) >= T (gat_dropout.h: the bit of
@@ -45,6 +45,7 @@
 #include "common.h"
 #include "gather.h"
 #include "gat_dropout.h"
+#include "attn_common.h"
 
 namespace isplib {
 
@@ -90,99 +91,6 @@ struct Gatv2Args {
    float c;                                // float32(1 / (1 - p))
 };
 
-template <int LPR, int NCH> struct Gatv2Cols {
-   unsigned cbyte[NCH], poison[NCH];       // this lane's 4 consecutive columns per chunk; past k: an offset the descriptor answers with 0
-   unsigned hbyte[NCH];                    // byte offset of the chunk's head inside a row of a [., H] table
-   int head[NCH];
-   bool ok[NCH][4], first[NCH];            // first: this lane's chunk opens a head (and lies inside k)
-   __device__ __forceinline__ Gatv2Cols(const Gatv2Args &a, int lc) {
-#pragma unroll
-      for (int j = 0; j < NCH; j++) {
-         const int c = (j * LPR + lc) * 4;
-         cbyte[j] = (unsigned)c * 4u;
-         poison[j] = c < (int)a.k ? 0u : BUF_OOB;
-         head[j] = c >> a.hshift;
-         hbyte[j] = (unsigned)head[j] * 4u;
-         first[j] = c < (int)a.k && ((unsigned)c & a.hmask) == 0u;
-#pragma unroll
-         for (int v = 0; v < 4; v++) ok[j][v] = c + v < (int)a.k;
-      }
-   }
-};
-
-// this lane's columns of row `row` of a dense operand; plain loads, nothing outside the row's k columns is read
-template <int LPR, int NCH>
-__device__ __forceinline__ void gatv2_own_row(const float *base, int64_t row, int64_t ld, int lc, const Gatv2Cols<LPR, NCH> &cm,
-                                              float (&r)[NCH][4]) {
-#pragma unroll
-   for (int j = 0; j < NCH; j++)
-#pragma unroll
-      for (int v = 0; v < 4; v++) r[j][v] = cm.ok[j][v] ? base[(size_t)row * (size_t)ld + (size_t)((j * LPR + lc) * 4 + v)] : 0.0f;
-}
-
-// entry [row, head of chunk j] of a dense [rows, H] table, per chunk; a chunk past k reads nothing
-template <int LPR, int NCH>
-__device__ __forceinline__ void gatv2_own_head(const float *base, int64_t row, int heads, const Gatv2Cols<LPR, NCH> &cm, float (&r)[NCH]) {
-#pragma unroll
-   for (int j = 0; j < NCH; j++) r[j] = cm.ok[j][0] ? base[(size_t)row * (size_t)heads + (size_t)cm.head[j]] : 0.0f;
-}
-
-template <int LPR, int NCH>
-__device__ __forceinline__ void gatv2_load_wide(const __amdgpu_buffer_rsrc_t rsrc, unsigned off, const Gatv2Cols<LPR, NCH> &cm, v4i_t (&t)[NCH]) {
-#pragma unroll
-   for (int j = 0; j < NCH; j++) t[j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)((off + cm.cbyte[j]) | cm.poison[j]), 0, 0);
-}
-
-template <int LPR, int NCH>
-__device__ __forceinline__ void gatv2_load_head(const __amdgpu_buffer_rsrc_t rsrc, unsigned offh, const Gatv2Cols<LPR, NCH> &cm, float (&t)[NCH]) {
-#pragma unroll
-   for (int j = 0; j < NCH; j++)
-      t[j] = __int_as_float((int)__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)((offh + cm.hbyte[j]) | cm.poison[j]), 0, 0));
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t gatv2_rsrc(const float *p, unsigned bytes) {
-   return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p), 0, (int)bytes, 0x00020000);
-}
-
-// N sums over the lanes that share a head (an aligned group of `hlanes` lanes, a power of two <= LPR), level by level together; every
-// lane of the group ends with the same bits (each level adds the same two numbers on both sides).  Partners 1, 2, 4, 8 by DPP moves
-// inside the 16-lane row (gather.h), wider ones by ds_bpermute.
-template <int LPR, int N, int O = 1> __device__ __forceinline__ void gatv2_head_sum(float (&v)[N], int hlanes) {
-   if constexpr (O < LPR) {
-      float w[N];
-#pragma unroll
-      for (int i = 0; i < N; i++) w[i] = lane_xor<O>(v[i]);
-#pragma unroll
-      for (int i = 0; i < N; i++) v[i] = O < hlanes ? v[i] + w[i] : v[i];
-      gatv2_head_sum<LPR, N, 2 * O>(v, hlanes);
-   }
-}
-
-// the per-lane parts p[.][chunk] of P dot products per head -> the dot products, in every lane of the head (both chunks where the head
-// is the whole row)
-template <int LPR, int NCH, int P>
-__device__ __forceinline__ void gatv2_head_reduce(float (&p)[P][NCH], const Gatv2Args &a) {
-   if (NCH == 2 && a.whole) {
-      float w[P];
-#pragma unroll
-      for (int i = 0; i < P; i++) w[i] = p[i][0] + p[i][NCH - 1];
-      gatv2_head_sum<LPR, P>(w, a.hlanes);
-#pragma unroll
-      for (int i = 0; i < P; i++) p[i][0] = p[i][NCH - 1] = w[i];
-   } else {
-      float w[P * NCH];
-#pragma unroll
-      for (int i = 0; i < P; i++)
-#pragma unroll
-         for (int j = 0; j < NCH; j++) w[i * NCH + j] = p[i][j];
-      gatv2_head_sum<LPR, P * NCH>(w, a.hlanes);
-#pragma unroll
-      for (int i = 0; i < P; i++)
-#pragma unroll
-         for (int j = 0; j < NCH; j++) p[i][j] = w[i * NCH + j];
-   }
-}
-
 // v_ec = leaky_relu(u_ec), u_ec = r + t: ONE fp32 add, so its sign is the sign of the exact sum; u == 0 takes ns
 __device__ __forceinline__ float gatv2_leaky(float r, float t, float ns, bool &pos) {
    const float u = r + t;
@@ -201,25 +109,6 @@ __device__ __forceinline__ float gatv2_score_part(const float (&r)[4], const v4i
    return p;
 }
 
-__device__ __forceinline__ float gatv2_dot_part(const float (&r)[4], const v4i_t &t, const bool (&ok)[4]) {
-   float p = 0.0f;
-#pragma unroll
-   for (int v = 0; v < 4; v++) p = fmaf(r[v], ok[v] ? __int_as_float(t[v]) : 0.0f, p);
-   return p;
-}
-
-// byte offset factor of the gathered row of edge `src` of the batch; a dead edge: -1
-__device__ __forceinline__ unsigned gatv2_off(int id, unsigned pitch_bytes) {
-   return id < 0 ? BUF_OOB : (unsigned)id * pitch_bytes;     // BUF_OOB + cbyte / hbyte (< 2^24) cannot wrap
-}
-
-// DROP: the per-lane constant of each chunk's head (gat_dropout.h)
-template <int LPR, int NCH>
-__device__ __forceinline__ void gatv2_drop_heads(const Gatv2Args &a, const Gatv2Cols<LPR, NCH> &cm, unsigned (&hk)[NCH]) {
-#pragma unroll
-   for (int j = 0; j < NCH; j++) hk[j] = gat_drop_head(a.seed_hi, (unsigned)cm.head[j]);
-}
-
 template <int LPR, int NCH, int WAVES, bool DROP>
 __global__ __launch_bounds__(WAVES * 64) void gatv2_fw_kernel(const Gatv2Args a) {
    constexpr int G = 64 / LPR, U = 4;
@@ -229,13 +118,13 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_fw_kernel(const Gatv2Args a)
    const int64_t row = (int64_t)blockIdx.x * WAVES + wave;
    if (row >= a.rows) return;
    const int64_t eb = a.pntrb[row], ee = a.pntre[row];
-   const __amdgpu_buffer_rsrc_t rsy = gatv2_rsrc(a.y, a.ybytes);
-   const Gatv2Cols<LPR, NCH> cm(a, lc);
+   const __amdgpu_buffer_rsrc_t rsy = attn_rsrc(a.y, a.ybytes);
+   const AttnHeadCols<LPR, NCH> cm(a.k, a.hshift, a.hmask, lc);
    float xv[NCH][4], av[NCH][4];
-   gatv2_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm, xv);
-   gatv2_own_row<LPR, NCH>(a.att, 0, a.k, lc, cm, av);
+   attn_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm.ok, xv);
+   attn_own_row<LPR, NCH>(a.att, 0, a.k, lc, cm.ok, av);
    [[maybe_unused]] unsigned hk[NCH];
-   if constexpr (DROP) gatv2_drop_heads<LPR, NCH>(a, cm, hk);
+   if constexpr (DROP) attn_drop_heads<LPR, NCH>(a.seed_hi, cm, hk);
 
    float mrun[NCH], l[NCH], acc[NCH][4];
 #pragma unroll
@@ -260,7 +149,7 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_fw_kernel(const Gatv2Args a)
          [[maybe_unused]] unsigned hw[DROP ? U : 1];
 #pragma unroll
          for (int u = 0; u < U; u++) {
-            gatv2_load_wide<LPR, NCH>(rsy, gatv2_off(__shfl(id_l, (s0 + u * G + g) & 63), ldyb), cm, yv[u]);
+            attn_load_wide<LPR, NCH>(rsy, attn_off(__shfl(id_l, (s0 + u * G + g) & 63), ldyb), cm, yv[u]);
             if constexpr (DROP) hw[u] = (unsigned)__shfl((int)hw_l, (s0 + u * G + g) & 63);
          }
          float sc[U][NCH];
@@ -268,7 +157,7 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_fw_kernel(const Gatv2Args a)
          for (int u = 0; u < U; u++)
 #pragma unroll
             for (int j = 0; j < NCH; j++) sc[u][j] = gatv2_score_part(xv[j], yv[u][j], av[j], cm.ok[j], a.ns);
-         gatv2_head_reduce<LPR, NCH, U>(sc, a);
+         attn_head_reduce<LPR, NCH, U>(sc, a.whole, a.hlanes);
 #pragma unroll
          for (int j = 0; j < NCH; j++) {
             float mnew = mrun[j];
@@ -335,8 +224,8 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_bw_rows_kernel(const Gatv2Ar
       if (!valid) return;
    }
    const int64_t eb = valid ? a.pntrb[row] : 0, ee = valid ? a.pntre[row] : 0;
-   const __amdgpu_buffer_rsrc_t rsy = gatv2_rsrc(a.y, a.ybytes);
-   const Gatv2Cols<LPR, NCH> cm(a, lc);
+   const __amdgpu_buffer_rsrc_t rsy = attn_rsrc(a.y, a.ybytes);
+   const AttnHeadCols<LPR, NCH> cm(a.k, a.hshift, a.hmask, lc);
    float xv[NCH][4], gv[NCH][4], av[NCH][4], lse[NCH], dsum[NCH];
 #pragma unroll
    for (int j = 0; j < NCH; j++) {
@@ -345,21 +234,21 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_bw_rows_kernel(const Gatv2Ar
 #pragma unroll
       for (int v = 0; v < 4; v++) xv[j][v] = gv[j][v] = 0.0f;
    }
-   gatv2_own_row<LPR, NCH>(a.att, 0, a.k, lc, cm, av);
+   attn_own_row<LPR, NCH>(a.att, 0, a.k, lc, cm.ok, av);
    if (valid) {
-      gatv2_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm, xv);
-      gatv2_own_row<LPR, NCH>(a.g, row, a.ldg, lc, cm, gv);
-      gatv2_own_head<LPR, NCH>(a.lse_in, row, a.heads, cm, lse);
+      attn_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm.ok, xv);
+      attn_own_row<LPR, NCH>(a.g, row, a.ldg, lc, cm.ok, gv);
+      attn_own_head<LPR, NCH>(a.lse_in, row, a.heads, cm, lse);
       // D[i,h] = <g_i, z_i>_h: every slot holds the row, so every lane of a head ends with it
       float zv[NCH][4], dp[1][NCH];
-      gatv2_own_row<LPR, NCH>(a.zin, row, a.ldzin, lc, cm, zv);
+      attn_own_row<LPR, NCH>(a.zin, row, a.ldzin, lc, cm.ok, zv);
 #pragma unroll
       for (int j = 0; j < NCH; j++) {
          dp[0][j] = 0.0f;
 #pragma unroll
          for (int v = 0; v < 4; v++) dp[0][j] = fmaf(gv[j][v], zv[j][v], dp[0][j]);
       }
-      gatv2_head_reduce<LPR, NCH, 1>(dp, a);
+      attn_head_reduce<LPR, NCH, 1>(dp, a.whole, a.hlanes);
 #pragma unroll
       for (int j = 0; j < NCH; j++) dsum[j] = dp[0][j];
    }
@@ -370,7 +259,7 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_bw_rows_kernel(const Gatv2Ar
 #pragma unroll
       for (int v = 0; v < 4; v++) acc[j][v] = pa[j][v] = 0.0f;
    [[maybe_unused]] unsigned hk[NCH];
-   if constexpr (DROP) gatv2_drop_heads<LPR, NCH>(a, cm, hk);
+   if constexpr (DROP) attn_drop_heads<LPR, NCH>(a.seed_hi, cm, hk);
 
    const unsigned ldyb = (unsigned)a.ldy * 4u;
    for (int64_t base = eb; base < ee; base += 64) {
@@ -386,7 +275,7 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_bw_rows_kernel(const Gatv2Ar
          [[maybe_unused]] unsigned hw[DROP ? U : 1];
 #pragma unroll
          for (int u = 0; u < U; u++) {
-            gatv2_load_wide<LPR, NCH>(rsy, gatv2_off(__shfl(id_l, (s0 + u * G + g) & 63), ldyb), cm, yv[u]);
+            attn_load_wide<LPR, NCH>(rsy, attn_off(__shfl(id_l, (s0 + u * G + g) & 63), ldyb), cm, yv[u]);
             if constexpr (DROP) hw[u] = (unsigned)__shfl((int)hw_l, (s0 + u * G + g) & 63);
          }
          float part[2 * U][NCH];                       // s_e and t_e of the step through one butterfly
@@ -395,9 +284,9 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_bw_rows_kernel(const Gatv2Ar
 #pragma unroll
             for (int j = 0; j < NCH; j++) {
                part[u][j] = gatv2_score_part(xv[j], yv[u][j], av[j], cm.ok[j], a.ns);
-               part[U + u][j] = gatv2_dot_part(gv[j], yv[u][j], cm.ok[j]);
+               part[U + u][j] = attn_dot_part(gv[j], yv[u][j], cm.ok[j]);
             }
-         gatv2_head_reduce<LPR, NCH, 2 * U>(part, a);
+         attn_head_reduce<LPR, NCH, 2 * U>(part, a.whole, a.hlanes);
 #pragma unroll
          for (int u = 0; u < U; u++) {
             const bool live = s0 + u * G + g < cnt;
@@ -465,14 +354,14 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_bw_cols_kernel(const Gatv2Ar
    const int64_t row = (int64_t)blockIdx.x * WAVES + wave;
    if (row >= a.rows) return;
    const int64_t eb = a.pntrb[row], ee = a.pntre[row];
-   const __amdgpu_buffer_rsrc_t rsx = gatv2_rsrc(a.y, a.ybytes), rsg = gatv2_rsrc(a.y2, a.y2bytes);
-   const __amdgpu_buffer_rsrc_t rs1 = gatv2_rsrc(a.t1, a.tbytes), rs2 = gatv2_rsrc(a.t2, a.tbytes);
-   const Gatv2Cols<LPR, NCH> cm(a, lc);
+   const __amdgpu_buffer_rsrc_t rsx = attn_rsrc(a.y, a.ybytes), rsg = attn_rsrc(a.y2, a.y2bytes);
+   const __amdgpu_buffer_rsrc_t rs1 = attn_rsrc(a.t1, a.tbytes), rs2 = attn_rsrc(a.t2, a.tbytes);
+   const AttnHeadCols<LPR, NCH> cm(a.k, a.hshift, a.hmask, lc);
    float yv[NCH][4], av[NCH][4];
-   gatv2_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm, yv);
-   gatv2_own_row<LPR, NCH>(a.att, 0, a.k, lc, cm, av);
+   attn_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm.ok, yv);
+   attn_own_row<LPR, NCH>(a.att, 0, a.k, lc, cm.ok, av);
    [[maybe_unused]] unsigned hk[NCH];
-   if constexpr (DROP) gatv2_drop_heads<LPR, NCH>(a, cm, hk);
+   if constexpr (DROP) attn_drop_heads<LPR, NCH>(a.seed_hi, cm, hk);
 
    float acc[NCH][4];
 #pragma unroll
@@ -496,10 +385,10 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_bw_cols_kernel(const Gatv2Ar
 #pragma unroll
          for (int u = 0; u < U; u++) {
             const int id = __shfl(id_l, (s0 + u * G + g) & 63);
-            gatv2_load_wide<LPR, NCH>(rsx, gatv2_off(id, ldxb), cm, xg[u]);
-            gatv2_load_wide<LPR, NCH>(rsg, gatv2_off(id, ldgb), cm, gg[u]);
-            gatv2_load_head<LPR, NCH>(rs1, gatv2_off(id, hb), cm, ls[u]);
-            gatv2_load_head<LPR, NCH>(rs2, gatv2_off(id, hb), cm, dd[u]);
+            attn_load_wide<LPR, NCH>(rsx, attn_off(id, ldxb), cm, xg[u]);
+            attn_load_wide<LPR, NCH>(rsg, attn_off(id, ldgb), cm, gg[u]);
+            attn_load_head<LPR, NCH>(rs1, attn_off(id, hb), cm, ls[u]);
+            attn_load_head<LPR, NCH>(rs2, attn_off(id, hb), cm, dd[u]);
             if constexpr (DROP) hw[u] = (unsigned)__shfl((int)hw_l, (s0 + u * G + g) & 63);
          }
          float part[2 * U][NCH];
@@ -508,9 +397,9 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_bw_cols_kernel(const Gatv2Ar
 #pragma unroll
             for (int j = 0; j < NCH; j++) {
                part[u][j] = gatv2_score_part(yv[j], xg[u][j], av[j], cm.ok[j], a.ns);      // x_ic + y_jc: the add commutes bit for bit
-               part[U + u][j] = gatv2_dot_part(yv[j], gg[u][j], cm.ok[j]);
+               part[U + u][j] = attn_dot_part(yv[j], gg[u][j], cm.ok[j]);
             }
-         gatv2_head_reduce<LPR, NCH, 2 * U>(part, a);
+         attn_head_reduce<LPR, NCH, 2 * U>(part, a.whole, a.hlanes);
 #pragma unroll
          for (int u = 0; u < U; u++) {
             const bool live = s0 + u * G + g < cnt;
@@ -577,58 +466,17 @@ static int launch_gatv2(int which, const Gatv2Args &a, const char *entry, hipStr
    return check_launch(entry);
 }
 
-// the width dispatch of gat.hip, up to two chunks per lane; DROP: the kernels with attention dropout
-template <bool DROP>
-static int gatv2_by_width_of(int which, const Gatv2Args &a, const char *entry, hipStream_t st) {
-   const int64_t w = (a.k + 3) / 4;
-   if (w <= 8) return launch_gatv2<8, 1, DROP>(which, a, entry, st);
-   if (w <= 16) return launch_gatv2<16, 1, DROP>(which, a, entry, st);
-   if (w <= 32) return launch_gatv2<32, 1, DROP>(which, a, entry, st);
-   if (w <= 64) return launch_gatv2<64, 1, DROP>(which, a, entry, st);
-   return launch_gatv2<64, 2, DROP>(which, a, entry, st);
-}
-
+// the width ladder (attn_by_width); DROP: the kernels with attention dropout
 static int gatv2_by_width(int which, const Gatv2Args &a, bool drop, const char *entry, hipStream_t st) {
-   return drop ? gatv2_by_width_of<true>(which, a, entry, st) : gatv2_by_width_of<false>(which, a, entry, st);
+   return attn_by_width(a.k, [&](auto lpr, auto nch) {
+      constexpr int LPR = decltype(lpr)::value, NCH = decltype(nch)::value;
+      return drop ? launch_gatv2<LPR, NCH, true>(which, a, entry, st) : launch_gatv2<LPR, NCH, false>(which, a, entry, st);
+   });
 }
 
-// the dropout of one call (isplib_gatv2_drop_*_hip): the threshold T(p), c = float32(1 / (1 - p)) and the seed; none: the entries without it
-struct Gatv2Drop {
-   bool on;
-   uint32_t threshold;
-   float scale;
-   uint64_t seed;
-};
-static const Gatv2Drop GATV2_NO_DROP = {false, 0u, 1.0f, 0ull};
-
-// what the dropout entries refuse before a launch: a scale that is no positive finite number would poison every row, and the keep bit is
-// a function of a position below 2^31
-static const char *gatv2_drop_refusal(const Gatv2Drop &dr, int64_t nnz) {
-   if (!dr.on) return nullptr;
-   if (!(dr.scale > 0.0f && dr.scale <= FLT_MAX)) return "scale must be a positive finite number";
-   if (nnz >= (1LL << 31)) return "nnz must be below 2^31";
-   return nullptr;
-}
-
-static void gatv2_set_drop(Gatv2Args &a, const Gatv2Drop &dr) {
-   a.seed_lo = (unsigned)dr.seed; a.seed_hi = (unsigned)(dr.seed >> 32); a.T = dr.threshold; a.c = dr.scale;
-}
-
-// what a descriptor over `rows` rows of k floats at pitch ld may answer: the extent a row-strided view owns, not rows * ld
-static unsigned gatv2_extent(int64_t rows, int64_t k, int64_t ld) {
-   return rows <= 0 ? 0u : (unsigned)(((unsigned long long)(rows - 1) * (unsigned long long)ld + (unsigned long long)k) * 4ull);
-}
-
-// the head geometry of a launch; the domain (isplib_gatv2_serves) has been checked: H == 1, or d a power of two >= 4
-static void gatv2_heads(Gatv2Args &a, int64_t heads, int64_t d) {
-   a.heads = (int)heads;
-   if (heads == 1) {
-      a.hshift = 31; a.hlanes = 64; a.hmask = 0x7fffffffu; a.whole = 1;
-   } else {
-      int sh = 0;
-      while ((1LL << sh) < d) sh++;
-      a.hshift = sh; a.hlanes = (int)(d / 4); a.hmask = (unsigned)(d - 1); a.whole = 0;
-   }
+// what the dropout entries (isplib_gatv2_drop_*_hip) refuse before a launch
+static const char *gatv2_drop_refusal(const AttnDrop &dr, int64_t nnz) {
+   return attn_drop_refusal(dr, nnz, "scale must be a positive finite number");
 }
 
 static const char *const GATV2_DOMAIN = "outside isplib_gatv2_serves(rows_gathered, heads, d, ld) = isplib_gat_serves: 1 <= heads, 1 <= d, "
@@ -652,7 +500,7 @@ extern "C" size_t isplib_gatv2_bw_rows_workspace_bytes(int64_t m, int64_t k) {
 // The three entries, with and without attention dropout.
 static int gatv2_forward(const char *entry, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
                          const int64_t *pntre, const float *x, int64_t ldx, const float *y, int64_t ldy, const float *att, int64_t heads,
-                         float negative_slope, float *z, int64_t ldz, float *lse, void *stream, const Gatv2Drop &dr = GATV2_NO_DROP) {
+                         float negative_slope, float *z, int64_t ldz, float *lse, void *stream, const AttnDrop &dr = ATTN_NO_DROP) {
    clear_error();
    if (const char *why = gatv2_drop_refusal(dr, nnz)) return fail(ISPLIB_FAIL, entry, why);
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
@@ -663,11 +511,11 @@ static int gatv2_forward(const char *entry, int64_t m, int64_t n, int64_t k, int
    if (heads < 1 || !isplib_gatv2_serves(n, heads, k / heads, ldy)) return fail(ISPLIB_NO_OPT_IMPL, entry, GATV2_DOMAIN);
    Gatv2Args a = {};
    a.rows = m; a.k = k; a.indx = indx; a.pntrb = pntrb; a.pntre = pntre; a.ns = negative_slope;
-   gatv2_heads(a, heads, k / heads);
+   attn_head_geometry(heads, k / heads, a.heads, a.hshift, a.hlanes, a.hmask, a.whole);
    a.own = x; a.ldown = ldx; a.att = att;
    a.out = z; a.ldout = ldz; a.hout = lse;
-   a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? gatv2_extent(n, k, ldy) : 0u;
-   gatv2_set_drop(a, dr);
+   a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? attn_extent(n, k, ldy) : 0u;
+   attn_set_drop(dr, a.seed_lo, a.seed_hi, a.T, a.c);
    return gatv2_by_width(GATV2_FW, a, dr.on, entry, (hipStream_t)stream);
 }
 
@@ -675,7 +523,7 @@ static int gatv2_backward_rows(const char *entry, int64_t m, int64_t n, int64_t 
                                const int64_t *pntre, const float *x, int64_t ldx, const float *y, int64_t ldy, const float *att,
                                int64_t heads, float negative_slope, const float *g, int64_t ldg, const float *z, int64_t ldz,
                                const float *lse, float *dx, int64_t lddx, float *dsum, float *datt, void *workspace,
-                               size_t workspace_bytes, void *stream, const Gatv2Drop &dr = GATV2_NO_DROP) {
+                               size_t workspace_bytes, void *stream, const AttnDrop &dr = ATTN_NO_DROP) {
    clear_error();
    if (const char *why = gatv2_drop_refusal(dr, nnz)) return fail(ISPLIB_FAIL, entry, why);
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
@@ -691,11 +539,11 @@ static int gatv2_backward_rows(const char *entry, int64_t m, int64_t n, int64_t 
    }
    Gatv2Args a = {};
    a.rows = m; a.k = k; a.indx = indx; a.pntrb = pntrb; a.pntre = pntre; a.ns = negative_slope;
-   gatv2_heads(a, heads, k / heads);
+   attn_head_geometry(heads, k / heads, a.heads, a.hshift, a.hlanes, a.hmask, a.whole);
    a.own = x; a.ldown = ldx; a.att = att; a.g = g; a.ldg = ldg; a.zin = z; a.ldzin = ldz; a.lse_in = lse;
    a.out = dx; a.ldout = lddx; a.hout = dsum; a.part = datt ? (float *)workspace : nullptr;
-   a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? gatv2_extent(n, k, ldy) : 0u;
-   gatv2_set_drop(a, dr);
+   a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? attn_extent(n, k, ldy) : 0u;
+   attn_set_drop(dr, a.seed_lo, a.seed_hi, a.T, a.c);
    int rc = gatv2_by_width(datt ? GATV2_BW_ROWS_DATT : GATV2_BW_ROWS, a, dr.on, entry, (hipStream_t)stream);
    if (rc || !datt) return rc;
    const int64_t blocks = (m + GATV2_ROWS_WAVES - 1) / GATV2_ROWS_WAVES;
@@ -706,7 +554,7 @@ static int gatv2_backward_rows(const char *entry, int64_t m, int64_t n, int64_t 
 static int gatv2_backward_cols(const char *entry, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t, const int64_t *colb,
                                const int64_t *cole, const int64_t *csr2csc, const float *x, int64_t ldx, const float *y, int64_t ldy,
                                const float *att, int64_t heads, float negative_slope, const float *g, int64_t ldg, const float *lse,
-                               const float *dsum, float *dy, int64_t lddy, void *stream, const Gatv2Drop &dr = GATV2_NO_DROP) {
+                               const float *dsum, float *dy, int64_t lddy, void *stream, const AttnDrop &dr = ATTN_NO_DROP) {
    clear_error();
    if (const char *why = gatv2_drop_refusal(dr, nnz)) return fail(ISPLIB_FAIL, entry, why);
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
@@ -719,14 +567,14 @@ static int gatv2_backward_cols(const char *entry, int64_t m, int64_t n, int64_t 
       return fail(ISPLIB_NO_OPT_IMPL, entry, GATV2_DOMAIN);
    Gatv2Args a = {};
    a.rows = n; a.k = k; a.indx = row_t; a.pntrb = colb; a.pntre = cole; a.ns = negative_slope;
-   gatv2_heads(a, heads, k / heads);
+   attn_head_geometry(heads, k / heads, a.heads, a.hshift, a.hlanes, a.hmask, a.whole);
    a.own = y; a.ldown = ldy; a.att = att;
    a.out = dy; a.ldout = lddy;
-   a.y = x; a.ldy = ldx; a.ybytes = nnz > 0 ? gatv2_extent(m, k, ldx) : 0u;
-   a.y2 = g; a.ldy2 = ldg; a.y2bytes = nnz > 0 ? gatv2_extent(m, k, ldg) : 0u;
-   a.t1 = lse; a.t2 = dsum; a.tbytes = nnz > 0 ? gatv2_extent(m, heads, heads) : 0u;
+   a.y = x; a.ldy = ldx; a.ybytes = nnz > 0 ? attn_extent(m, k, ldx) : 0u;
+   a.y2 = g; a.ldy2 = ldg; a.y2bytes = nnz > 0 ? attn_extent(m, k, ldg) : 0u;
+   a.t1 = lse; a.t2 = dsum; a.tbytes = nnz > 0 ? attn_extent(m, heads, heads) : 0u;
    if (dr.on) a.epos = csr2csc;
-   gatv2_set_drop(a, dr);
+   attn_set_drop(dr, a.seed_lo, a.seed_hi, a.T, a.c);
    return gatv2_by_width(GATV2_BW_COLS, a, dr.on, entry, (hipStream_t)stream);
 }
 
@@ -760,7 +608,7 @@ extern "C" int isplib_gatv2_drop_csr_hip(int64_t m, int64_t n, int64_t k, int64_
                                          int64_t heads, float negative_slope, float *z, int64_t ldz, float *lse, void *stream,
                                          uint32_t threshold, float scale, uint64_t seed) {
    return gatv2_forward("isplib_gatv2_drop_csr_hip", m, n, k, nnz, indx, pntrb, pntre, x, ldx, y, ldy, att, heads, negative_slope, z, ldz,
-                        lse, stream, Gatv2Drop{true, threshold, scale, seed});
+                        lse, stream, AttnDrop{true, threshold, scale, seed});
 }
 
 extern "C" int isplib_gatv2_drop_bw_rows_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
@@ -771,7 +619,7 @@ extern "C" int isplib_gatv2_drop_bw_rows_hip(int64_t m, int64_t n, int64_t k, in
                                              float scale, uint64_t seed) {
    return gatv2_backward_rows("isplib_gatv2_drop_bw_rows_hip", m, n, k, nnz, indx, pntrb, pntre, x, ldx, y, ldy, att, heads,
                               negative_slope, g, ldg, z, ldz, lse, dx, lddx, dsum, datt, workspace, workspace_bytes, stream,
-                              Gatv2Drop{true, threshold, scale, seed});
+                              AttnDrop{true, threshold, scale, seed});
 }
 
 extern "C" int isplib_gatv2_drop_bw_cols_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t, const int64_t *colb,
@@ -780,5 +628,5 @@ extern "C" int isplib_gatv2_drop_bw_cols_hip(int64_t m, int64_t n, int64_t k, in
                                              int64_t ldg, const float *lse, const float *dsum, float *dy, int64_t lddy, void *stream,
                                              uint32_t threshold, float scale, uint64_t seed) {
    return gatv2_backward_cols("isplib_gatv2_drop_bw_cols_hip", m, n, k, nnz, row_t, colb, cole, csr2csc, x, ldx, y, ldy, att, heads,
-                              negative_slope, g, ldg, lse, dsum, dy, lddy, stream, Gatv2Drop{true, threshold, scale, seed});
+                              negative_slope, g, ldg, lse, dsum, dy, lddy, stream, AttnDrop{true, threshold, scale, seed});
 }

@@ -45,6 +45,7 @@
 #include "common.h"
 #include "gather.h"
 #include "half16.h"
+#include "attn16_common.h"
 
 namespace isplib {
 
@@ -84,82 +85,10 @@ struct Gatv2h16Args {
    unsigned tbytes;
 };
 
-// this lane's eight consecutive columns and their head; ok[q]: the dword of columns (2q, 2q + 1) lies inside the row (k is even)
-struct Gatv2h16Cols {
-   int col, head;
-   unsigned cbyte, hbyte, poison;            // past k: an offset the descriptors answer with 0
-   bool ok[4], first;                        // first: this lane opens a head (and lies inside k)
-   __device__ __forceinline__ Gatv2h16Cols(const Gatv2h16Args &a, int lc) {
-      col = lc * 8;
-      cbyte = (unsigned)col * 2u;
-      poison = col < (int)a.k ? 0u : BUF_OOB;
-      head = col >> a.hshift;
-      hbyte = (unsigned)head * 4u;
-      first = col < (int)a.k && ((unsigned)col & a.hmask) == 0u;
-#pragma unroll
-      for (int q = 0; q < 4; q++) ok[q] = col + 2 * q < (int)a.k;
-   }
-};
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t gatv2_16_desc(const void *p, unsigned bytes) {
-   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
-}
-
-// this lane's columns of row `row` of a dense 16-bit operand as floats; plain dword loads (base, pitch and column are even), nothing
-// outside the row's k columns is read
-template <int ELT>
-__device__ __forceinline__ void gatv2_16_own_row(const unsigned short *base, int64_t row, int64_t ld, const Gatv2h16Cols &cm, float (&r)[8]) {
-   const unsigned *p = reinterpret_cast<const unsigned *>(base + (size_t)row * (size_t)ld + (size_t)cm.col);
-#pragma unroll
-   for (int q = 0; q < 4; q++) {
-      unsigned w = 0u;
-      if (cm.ok[q]) w = p[q];
-      widen2<ELT>(w, r[2 * q], r[2 * q + 1]);
-   }
-}
-
 // this lane's eight columns of att (k contiguous floats); a column past k: 0
-__device__ __forceinline__ void gatv2_16_own_att(const float *att, const Gatv2h16Cols &cm, float (&r)[8]) {
+__device__ __forceinline__ void gatv2_16_own_att(const float *att, const Attn16HeadCols &cm, float (&r)[8]) {
 #pragma unroll
    for (int v = 0; v < 8; v++) r[v] = cm.ok[v >> 1] ? att[cm.col + v] : 0.0f;
-}
-
-// entry [row, this lane's head] of a dense fp32 [rows, H] table; a lane past k reads nothing
-__device__ __forceinline__ float gatv2_16_own_head(const float *base, int64_t row, int heads, const Gatv2h16Cols &cm) {
-   return cm.poison == 0u ? base[(size_t)row * (size_t)heads + (size_t)cm.head] : 0.0f;
-}
-
-// byte offset of the gathered row of edge `id` at a pitch of `pitch_bytes`; a dead edge: BUF_OOB
-__device__ __forceinline__ unsigned gatv2_16_off(int id, unsigned pitch_bytes) {
-   return id < 0 ? BUF_OOB : (unsigned)id * pitch_bytes;     // BUF_OOB + cbyte / hbyte (< 2^10) cannot wrap
-}
-
-__device__ __forceinline__ v4i_t gatv2_16_load_wide(const __amdgpu_buffer_rsrc_t rsrc, unsigned off, const Gatv2h16Cols &cm) {
-   return __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)((off + cm.cbyte) | cm.poison), 0, 0);
-}
-
-__device__ __forceinline__ float gatv2_16_load_head(const __amdgpu_buffer_rsrc_t rsrc, unsigned offh, const Gatv2h16Cols &cm) {
-   return __int_as_float((int)__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)((offh + cm.hbyte) | cm.poison), 0, 0));
-}
-
-// a gathered vector as eight floats; a dword the 16-byte load brought from outside the row is dropped by a select, not a multiply
-template <int ELT> __device__ __forceinline__ void gatv2_16_widen(const v4i_t &t, const Gatv2h16Cols &cm, float (&y)[8]) {
-#pragma unroll
-   for (int q = 0; q < 4; q++) widen2<ELT>(cm.ok[q] ? (unsigned)t[q] : 0u, y[2 * q], y[2 * q + 1]);
-}
-
-// N sums over the lanes that share a head (an aligned group of `hlanes` lanes, a power of two; H == 1: the whole slot), level by level
-// together; every lane of the group ends with the same bits (each level adds the same two numbers on both sides).  Partners 1, 2, 4, 8
-// by DPP moves inside the 16-lane row (gather.h), wider ones by ds_bpermute.  hlanes == 1: no cross-lane step is taken
-template <int LPR, int N, int O = 1> __device__ __forceinline__ void gatv2_16_head_sum(float (&v)[N], int hlanes) {
-   if constexpr (O < LPR) {
-      float w[N];
-#pragma unroll
-      for (int i = 0; i < N; i++) w[i] = lane_xor<O>(v[i]);
-#pragma unroll
-      for (int i = 0; i < N; i++) v[i] = O < hlanes ? v[i] + w[i] : v[i];
-      gatv2_16_head_sum<LPR, N, 2 * O>(v, hlanes);
-   }
 }
 
 // v_ec = leaky_relu(u_ec), u_ec = r + t: ONE fp32 add, so its sign is the sign of the exact sum; u == 0 takes ns
@@ -180,30 +109,6 @@ __device__ __forceinline__ float gatv2_16_score_part(const float (&r)[8], const 
    return p;
 }
 
-__device__ __forceinline__ float gatv2_16_dot_part(const float (&r)[8], const float (&t)[8]) {
-   float p = 0.0f;
-#pragma unroll
-   for (int v = 0; v < 8; v++) p = fmaf(r[v], t[v], p);
-   return p;
-}
-
-// the lane's eight finished columns, rounded once; only the dwords inside the row are written
-template <int ELT>
-__device__ __forceinline__ void gatv2_16_store_row(unsigned short *base, int64_t row, int64_t ld, const Gatv2h16Cols &cm, const float (&r)[8]) {
-   if (cm.poison != 0u) return;
-   unsigned *p = reinterpret_cast<unsigned *>(base + (size_t)row * (size_t)ld + (size_t)cm.col);
-   unsigned d[4];
-#pragma unroll
-   for (int q = 0; q < 4; q++) d[q] = narrow2<ELT>(r[2 * q], r[2 * q + 1]);
-   if (cm.ok[3] && ((uintptr_t)p & 15) == 0) {
-      *reinterpret_cast<uint4 *>(p) = make_uint4(d[0], d[1], d[2], d[3]);
-   } else {
-#pragma unroll
-      for (int q = 0; q < 4; q++)
-         if (cm.ok[q]) p[q] = d[q];
-   }
-}
-
 template <int ELT, int LPR, int WAVES>
 __global__ __launch_bounds__(WAVES * 64) void gatv2_16_fw_kernel(const Gatv2h16Args a) {
    constexpr int G = 64 / LPR, U = GATV2_16_FW_U;
@@ -213,10 +118,10 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_16_fw_kernel(const Gatv2h16A
    const int64_t row = (int64_t)blockIdx.x * WAVES + wave;
    if (row >= a.rows) return;
    const int64_t eb = a.pntrb[row], ee = a.pntre[row];
-   const __amdgpu_buffer_rsrc_t rsy = gatv2_16_desc(a.y, a.ybytes);
-   const Gatv2h16Cols cm(a, lc);
+   const __amdgpu_buffer_rsrc_t rsy = attn16_desc(a.y, a.ybytes);
+   const Attn16HeadCols cm(a.k, a.hshift, a.hmask, lc);
    float xv[8], av[8];
-   gatv2_16_own_row<ELT>(a.own, row, a.ldown, cm, xv);
+   attn16_own_row<ELT>(a.own, row, a.ldown, cm.col, cm.ok, xv);
    gatv2_16_own_att(a.att, cm, av);
 
    float mrun = GATV2_16_NONE, l = 0.0f, acc[8];
@@ -233,14 +138,14 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_16_fw_kernel(const Gatv2h16A
       for (int s0 = 0; s0 < cnt; s0 += G * U) {
          v4i_t yv[U];
 #pragma unroll
-         for (int u = 0; u < U; u++) yv[u] = gatv2_16_load_wide(rsy, gatv2_16_off(__shfl(id_l, (s0 + u * G + g) & 63), ldyb), cm);
+         for (int u = 0; u < U; u++) yv[u] = attn16_load_wide(rsy, attn16_off(__shfl(id_l, (s0 + u * G + g) & 63), ldyb), cm);
          float y8[U][8], sc[U];
 #pragma unroll
          for (int u = 0; u < U; u++) {
-            gatv2_16_widen<ELT>(yv[u], cm, y8[u]);
+            attn16_widen<ELT>(yv[u], cm.ok, y8[u]);
             sc[u] = gatv2_16_score_part(xv, y8[u], av, a.ns);
          }
-         gatv2_16_head_sum<LPR, U>(sc, a.hlanes);
+         attn16_head_sum<LPR, U>(sc, a.hlanes);
          float mnew = mrun;
 #pragma unroll
          for (int u = 0; u < U; u++)
@@ -275,7 +180,7 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_16_fw_kernel(const Gatv2h16A
    float zr[8];
 #pragma unroll
    for (int v = 0; v < 8; v++) zr[v] = empty ? 0.0f : acc[v] / l;
-   gatv2_16_store_row<ELT>(a.out, row, a.ldout, cm, zr);
+   attn16_store_row<ELT>(a.out, row, a.ldout, cm.col, cm.ok, zr);
    if (cm.first) a.hout[(size_t)row * (size_t)a.heads + (size_t)cm.head] = empty ? -INFINITY : mrun + logf(l);
 }
 
@@ -294,16 +199,16 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_16_bw_rows_kernel(const Gatv
       if (!valid) return;
    }
    const int64_t eb = valid ? a.pntrb[row] : 0, ee = valid ? a.pntre[row] : 0;
-   const __amdgpu_buffer_rsrc_t rsy = gatv2_16_desc(a.y, a.ybytes);
-   const Gatv2h16Cols cm(a, lc);
+   const __amdgpu_buffer_rsrc_t rsy = attn16_desc(a.y, a.ybytes);
+   const Attn16HeadCols cm(a.k, a.hshift, a.hmask, lc);
    float xv[8], gv[8], av[8], lse = 0.0f;
 #pragma unroll
    for (int v = 0; v < 8; v++) xv[v] = gv[v] = 0.0f;
    gatv2_16_own_att(a.att, cm, av);
    if (valid) {
-      gatv2_16_own_row<ELT>(a.own, row, a.ldown, cm, xv);
-      gatv2_16_own_row<ELT>(a.g, row, a.ldg, cm, gv);
-      lse = gatv2_16_own_head(a.lse_in, row, a.heads, cm);
+      attn16_own_row<ELT>(a.own, row, a.ldown, cm.col, cm.ok, xv);
+      attn16_own_row<ELT>(a.g, row, a.ldg, cm.col, cm.ok, gv);
+      lse = attn16_own_head(a.lse_in, row, a.heads, cm);
    }
 
    float l = 0.0f, dacc = 0.0f;                        // per head: sum a_e, sum a_e t_e
@@ -321,16 +226,16 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_16_bw_rows_kernel(const Gatv
       for (int s0 = 0; s0 < cnt; s0 += G * U) {
          v4i_t yv[U];
 #pragma unroll
-         for (int u = 0; u < U; u++) yv[u] = gatv2_16_load_wide(rsy, gatv2_16_off(__shfl(id_l, (s0 + u * G + g) & 63), ldyb), cm);
+         for (int u = 0; u < U; u++) yv[u] = attn16_load_wide(rsy, attn16_off(__shfl(id_l, (s0 + u * G + g) & 63), ldyb), cm);
          float part[2 * U];                            // s_e and t_e of the step through one butterfly
 #pragma unroll
          for (int u = 0; u < U; u++) {
             float y8[8];
-            gatv2_16_widen<ELT>(yv[u], cm, y8);
+            attn16_widen<ELT>(yv[u], cm.ok, y8);
             part[u] = gatv2_16_score_part(xv, y8, av, a.ns);
-            part[U + u] = gatv2_16_dot_part(gv, y8);
+            part[U + u] = attn16_dot_part(gv, y8);
          }
-         gatv2_16_head_sum<LPR, 2 * U>(part, a.hlanes);      // every lane takes part: not under `live`
+         attn16_head_sum<LPR, 2 * U>(part, a.hlanes);      // every lane takes part: not under `live`
 #pragma unroll
          for (int u = 0; u < U; u++) {
             const bool live = s0 + u * G + g < cnt;
@@ -340,7 +245,7 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_16_bw_rows_kernel(const Gatv
             l += ae;
             dacc += aet;
             float y8[8];
-            gatv2_16_widen<ELT>(yv[u], cm, y8);
+            attn16_widen<ELT>(yv[u], cm.ok, y8);
 #pragma unroll
             for (int v = 0; v < 8; v++) {
                bool pos;
@@ -375,7 +280,7 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_16_bw_rows_kernel(const Gatv
       float dx[8];
 #pragma unroll
       for (int v = 0; v < 8; v++) dx[v] = empty ? 0.0f : av[v] * (pc[v] - dsum * qc[v]);
-      gatv2_16_store_row<ELT>(a.out, row, a.ldout, cm, dx);
+      attn16_store_row<ELT>(a.out, row, a.ldout, cm.col, cm.ok, dx);
       if (cm.first) a.hout[(size_t)row * (size_t)a.heads + (size_t)cm.head] = dsum;
    }
    if constexpr (DATT) {
@@ -405,11 +310,11 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_16_bw_cols_kernel(const Gatv
    const int64_t row = (int64_t)blockIdx.x * WAVES + wave;
    if (row >= a.rows) return;
    const int64_t eb = a.pntrb[row], ee = a.pntre[row];
-   const __amdgpu_buffer_rsrc_t rsx = gatv2_16_desc(a.y, a.ybytes), rsg = gatv2_16_desc(a.y2, a.y2bytes);
-   const __amdgpu_buffer_rsrc_t rs1 = gatv2_16_desc(a.t1, a.tbytes), rs2 = gatv2_16_desc(a.t2, a.tbytes);
-   const Gatv2h16Cols cm(a, lc);
+   const __amdgpu_buffer_rsrc_t rsx = attn16_desc(a.y, a.ybytes), rsg = attn16_desc(a.y2, a.y2bytes);
+   const __amdgpu_buffer_rsrc_t rs1 = attn16_desc(a.t1, a.tbytes), rs2 = attn16_desc(a.t2, a.tbytes);
+   const Attn16HeadCols cm(a.k, a.hshift, a.hmask, lc);
    float yv[8], av[8];
-   gatv2_16_own_row<ELT>(a.own, row, a.ldown, cm, yv);
+   attn16_own_row<ELT>(a.own, row, a.ldown, cm.col, cm.ok, yv);
    gatv2_16_own_att(a.att, cm, av);
 
    float acc[8];
@@ -429,29 +334,29 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_16_bw_cols_kernel(const Gatv
 #pragma unroll
          for (int u = 0; u < U; u++) {
             const int id = __shfl(id_l, (s0 + u * G + g) & 63);
-            xg[u] = gatv2_16_load_wide(rsx, gatv2_16_off(id, ldxb), cm);
-            gg[u] = gatv2_16_load_wide(rsg, gatv2_16_off(id, ldgb), cm);
-            ls[u] = gatv2_16_load_head(rs1, gatv2_16_off(id, hb), cm);
-            dd[u] = gatv2_16_load_head(rs2, gatv2_16_off(id, hb), cm);
+            xg[u] = attn16_load_wide(rsx, attn16_off(id, ldxb), cm);
+            gg[u] = attn16_load_wide(rsg, attn16_off(id, ldgb), cm);
+            ls[u] = attn16_load_head(rs1, attn16_off(id, hb), cm);
+            dd[u] = attn16_load_head(rs2, attn16_off(id, hb), cm);
          }
          float part[2 * U];
 #pragma unroll
          for (int u = 0; u < U; u++) {
             float x8[8], g8[8];
-            gatv2_16_widen<ELT>(xg[u], cm, x8);
-            gatv2_16_widen<ELT>(gg[u], cm, g8);
+            attn16_widen<ELT>(xg[u], cm.ok, x8);
+            attn16_widen<ELT>(gg[u], cm.ok, g8);
             part[u] = gatv2_16_score_part(yv, x8, av, a.ns);      // x_ic + y_jc: the add commutes bit for bit
-            part[U + u] = gatv2_16_dot_part(yv, g8);
+            part[U + u] = attn16_dot_part(yv, g8);
          }
-         gatv2_16_head_sum<LPR, 2 * U>(part, a.hlanes);      // every lane takes part: not under `live`
+         attn16_head_sum<LPR, 2 * U>(part, a.hlanes);      // every lane takes part: not under `live`
 #pragma unroll
          for (int u = 0; u < U; u++) {
             const bool live = s0 + u * G + g < cnt;
             const float ae = live ? __expf(part[u] - ls[u]) : 0.0f;
             const float ds = live ? ae * (part[U + u] - dd[u]) : 0.0f;
             float x8[8], g8[8];
-            gatv2_16_widen<ELT>(xg[u], cm, x8);
-            gatv2_16_widen<ELT>(gg[u], cm, g8);
+            attn16_widen<ELT>(xg[u], cm.ok, x8);
+            attn16_widen<ELT>(gg[u], cm.ok, g8);
 #pragma unroll
             for (int v = 0; v < 8; v++) {
                bool pos;
@@ -467,7 +372,7 @@ __global__ __launch_bounds__(WAVES * 64) void gatv2_16_bw_cols_kernel(const Gatv
 #pragma unroll
       for (int v = 0; v < 8; v++) acc[v] += __shfl_xor(acc[v], o);
    if (g != 0) return;
-   gatv2_16_store_row<ELT>(a.out, row, a.ldout, cm, acc);      // no incoming entry: 0
+   attn16_store_row<ELT>(a.out, row, a.ldout, cm.col, cm.ok, acc);      // no incoming entry: 0
 }
 
 // datt[c] = the sum of the partial rows, one wave per column: lane l adds the rows l, l + 64, ... in ascending order, then the 64 lane
@@ -498,49 +403,17 @@ static int launch_gatv2_16(int which, const Gatv2h16Args &a, const char *entry, 
    return check_launch(entry);
 }
 
-// the slot width by ceil(k / 8) 16-byte vectors per row, always one chunk per lane
-template <int ELT>
-static int gatv2_16_by_width(int which, const Gatv2h16Args &a, const char *entry, hipStream_t st) {
-   const int64_t w = (a.k + 7) / 8;
-   if (w <= 4) return launch_gatv2_16<ELT, 4>(which, a, entry, st);
-   if (w <= 8) return launch_gatv2_16<ELT, 8>(which, a, entry, st);
-   if (w <= 16) return launch_gatv2_16<ELT, 16>(which, a, entry, st);
-   if (w <= 32) return launch_gatv2_16<ELT, 32>(which, a, entry, st);
-   return launch_gatv2_16<ELT, 64>(which, a, entry, st);
-}
-
+// the element type and the slot width (attn16_run)
 static int gatv2_16_run(int dtype, int which, const Gatv2h16Args &a, const char *entry, void *stream) {
-   return dtype == ISPLIB_DTYPE_BF16 ? gatv2_16_by_width<ELT_BF16>(which, a, entry, (hipStream_t)stream)
-                                     : gatv2_16_by_width<ELT_F16>(which, a, entry, (hipStream_t)stream);
+   return attn16_run(dtype, a.k, [&](auto elt, auto lpr) {
+      return launch_gatv2_16<decltype(elt)::value, decltype(lpr)::value>(which, a, entry, (hipStream_t)stream);
+   });
 }
 
-// what a descriptor over `rows` rows of k elements of `size` bytes at pitch ld may answer: the extent a row-strided view owns
-static unsigned gatv2_16_extent(int64_t rows, int64_t k, int64_t ld, unsigned size) {
-   return rows <= 0 ? 0u : (unsigned)(((unsigned long long)(rows - 1) * (unsigned long long)ld + (unsigned long long)k) * size);
-}
-
-// the head geometry of a launch; the domain (isplib_gatv2_16_serves) has been checked: H == 1, or d a power of two >= 8
-static void gatv2_16_heads(Gatv2h16Args &a, int64_t heads, int64_t d) {
-   a.heads = (int)heads;
-   if (heads == 1) {
-      a.hshift = 31; a.hlanes = 64; a.hmask = 0x7fffffffu;
-   } else {
-      int sh = 0;
-      while ((1LL << sh) < d) sh++;
-      a.hshift = sh; a.hlanes = (int)(d / 8); a.hmask = (unsigned)(d - 1);
-   }
-}
-
-static const char *const GATV2_16_DTYPE = "dtype must be ISPLIB_DTYPE_BF16 or ISPLIB_DTYPE_F16";
 static const char *const GATV2_16_DOMAIN = "outside isplib_gatv2_16_serves(rows_gathered, heads, d, ld) = isplib_gat16_serves: 1 <= heads, "
                                            "8 <= heads*d <= 512, heads == 1 with d even or d a power of two >= 8, every pitch even, "
                                            "ld >= heads*d, rows_gathered < 2^31, rows_gathered*ld*2 <= 3.5 GiB (convert the operands and "
                                            "use the fp32 entries)";
-
-static bool gatv2_16_even(int64_t a, int64_t b, int64_t c = 0) { return ((a | b | c) & 1) == 0; }
-static bool gatv2_16_aligned(const void *a, const void *b, const void *c, const void *d = nullptr) {
-   return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 3) == 0;
-}
 
 }  // namespace isplib
 
@@ -565,21 +438,21 @@ extern "C" int isplib_gatv2_16_csr_hip(int dtype, int64_t m, int64_t n, int64_t 
                                        int64_t heads, float negative_slope, void *z, int64_t ldz, float *lse, void *stream) {
    const char *entry = "isplib_gatv2_16_csr_hip";
    clear_error();
-   if (dtype != ISPLIB_DTYPE_BF16 && dtype != ISPLIB_DTYPE_F16) return fail(ISPLIB_FAIL, entry, GATV2_16_DTYPE);
+   if (dtype != ISPLIB_DTYPE_BF16 && dtype != ISPLIB_DTYPE_F16) return fail(ISPLIB_FAIL, entry, ATTN16_DTYPE);
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
    if (m == 0 || k == 0) return ISPLIB_SUCCESS;
    if (ldx < k || ldz < k) return fail(ISPLIB_FAIL, entry, "leading dimension smaller than k");
    if (heads >= 1 && k % heads != 0) return fail(ISPLIB_FAIL, entry, "k is not a multiple of heads");
-   if (heads < 1 || !isplib_gatv2_16_serves(n, heads, k / heads, ldy) || !gatv2_16_even(ldx, ldz))
+   if (heads < 1 || !isplib_gatv2_16_serves(n, heads, k / heads, ldy) || !attn16_even(ldx, ldz))
       return fail(ISPLIB_NO_OPT_IMPL, entry, GATV2_16_DOMAIN);
    if (!pntrb || !pntre || !x || !att || !z || !lse || (nnz > 0 && (!indx || !y))) return fail(ISPLIB_FAIL, entry, "null operand");
-   if (!gatv2_16_aligned(x, y, z)) return fail(ISPLIB_FAIL, entry, "x, y and z must be 4-byte aligned");
+   if (!attn16_aligned(x, y, z)) return fail(ISPLIB_FAIL, entry, "x, y and z must be 4-byte aligned");
    Gatv2h16Args a = {};
    a.rows = m; a.k = k; a.indx = indx; a.pntrb = pntrb; a.pntre = pntre; a.ns = negative_slope;
-   gatv2_16_heads(a, heads, k / heads);
+   attn16_head_geometry(heads, k / heads, a.heads, a.hshift, a.hlanes, a.hmask);
    a.own = reinterpret_cast<const unsigned short *>(x); a.ldown = ldx; a.att = att;
    a.out = reinterpret_cast<unsigned short *>(z); a.ldout = ldz; a.hout = lse;
-   a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? gatv2_16_extent(n, k, ldy, 2u) : 0u;
+   a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? attn16_extent(n, k, ldy, 2u) : 0u;
    return gatv2_16_run(dtype, GATV2_16_FW, a, entry, stream);
 }
 
@@ -590,12 +463,12 @@ extern "C" int isplib_gatv2_16_bw_rows_hip(int dtype, int64_t m, int64_t n, int6
                                            size_t workspace_bytes, void *stream) {
    const char *entry = "isplib_gatv2_16_bw_rows_hip";
    clear_error();
-   if (dtype != ISPLIB_DTYPE_BF16 && dtype != ISPLIB_DTYPE_F16) return fail(ISPLIB_FAIL, entry, GATV2_16_DTYPE);
+   if (dtype != ISPLIB_DTYPE_BF16 && dtype != ISPLIB_DTYPE_F16) return fail(ISPLIB_FAIL, entry, ATTN16_DTYPE);
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
    if (m == 0 || k == 0) return ISPLIB_SUCCESS;
    if (ldx < k || ldg < k || lddx < k) return fail(ISPLIB_FAIL, entry, "leading dimension smaller than k");
    if (heads >= 1 && k % heads != 0) return fail(ISPLIB_FAIL, entry, "k is not a multiple of heads");
-   if (heads < 1 || !isplib_gatv2_16_serves(n, heads, k / heads, ldy) || !gatv2_16_even(ldx, ldg, lddx))
+   if (heads < 1 || !isplib_gatv2_16_serves(n, heads, k / heads, ldy) || !attn16_even(ldx, ldg, lddx))
       return fail(ISPLIB_NO_OPT_IMPL, entry, GATV2_16_DOMAIN);
    if (!pntrb || !pntre || !x || !att || !g || !lse || !dx || !dsum || (nnz > 0 && (!indx || !y)))
       return fail(ISPLIB_FAIL, entry, "null operand");
@@ -604,14 +477,14 @@ extern "C" int isplib_gatv2_16_bw_rows_hip(int dtype, int64_t m, int64_t n, int6
          return fail(ISPLIB_NOT_ENOUGH_MEM, entry, "workspace too small");
       if (((uintptr_t)workspace & 255) != 0) return fail(ISPLIB_FAIL, entry, "workspace must be 256-byte aligned");
    }
-   if (!gatv2_16_aligned(x, y, g, dx)) return fail(ISPLIB_FAIL, entry, "x, y, g and dx must be 4-byte aligned");
+   if (!attn16_aligned(x, y, g, dx)) return fail(ISPLIB_FAIL, entry, "x, y, g and dx must be 4-byte aligned");
    Gatv2h16Args a = {};
    a.rows = m; a.k = k; a.indx = indx; a.pntrb = pntrb; a.pntre = pntre; a.ns = negative_slope;
-   gatv2_16_heads(a, heads, k / heads);
+   attn16_head_geometry(heads, k / heads, a.heads, a.hshift, a.hlanes, a.hmask);
    a.own = reinterpret_cast<const unsigned short *>(x); a.ldown = ldx; a.att = att;
    a.g = reinterpret_cast<const unsigned short *>(g); a.ldg = ldg; a.lse_in = lse;
    a.out = reinterpret_cast<unsigned short *>(dx); a.ldout = lddx; a.hout = dsum; a.part = datt ? (float *)workspace : nullptr;
-   a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? gatv2_16_extent(n, k, ldy, 2u) : 0u;
+   a.y = y; a.ldy = ldy; a.ybytes = nnz > 0 ? attn16_extent(n, k, ldy, 2u) : 0u;
    int rc = gatv2_16_run(dtype, datt ? GATV2_16_BW_ROWS_DATT : GATV2_16_BW_ROWS, a, entry, stream);
    if (rc || !datt) return rc;
    const int64_t blocks = (m + GATV2_16_ROWS_WAVES - 1) / GATV2_16_ROWS_WAVES;
@@ -625,23 +498,23 @@ extern "C" int isplib_gatv2_16_bw_cols_hip(int dtype, int64_t m, int64_t n, int6
                                            const float *lse, const float *dsum, void *dy, int64_t lddy, void *stream) {
    const char *entry = "isplib_gatv2_16_bw_cols_hip";
    clear_error();
-   if (dtype != ISPLIB_DTYPE_BF16 && dtype != ISPLIB_DTYPE_F16) return fail(ISPLIB_FAIL, entry, GATV2_16_DTYPE);
+   if (dtype != ISPLIB_DTYPE_BF16 && dtype != ISPLIB_DTYPE_F16) return fail(ISPLIB_FAIL, entry, ATTN16_DTYPE);
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
    if (n == 0 || k == 0) return ISPLIB_SUCCESS;
    if (ldy < k || lddy < k) return fail(ISPLIB_FAIL, entry, "leading dimension smaller than k");
    if (heads >= 1 && k % heads != 0) return fail(ISPLIB_FAIL, entry, "k is not a multiple of heads");
    if (heads < 1 || !isplib_gatv2_16_serves(m, heads, k / heads, ldx) || !isplib_gatv2_16_serves(m, heads, k / heads, ldg) ||
-       !gatv2_16_even(ldy, lddy))
+       !attn16_even(ldy, lddy))
       return fail(ISPLIB_NO_OPT_IMPL, entry, GATV2_16_DOMAIN);
    if (!colb || !cole || !y || !att || !dy || (nnz > 0 && (!row_t || !x || !g || !lse || !dsum))) return fail(ISPLIB_FAIL, entry, "null operand");
-   if (!gatv2_16_aligned(x, y, g, dy)) return fail(ISPLIB_FAIL, entry, "x, y, g and dy must be 4-byte aligned");
+   if (!attn16_aligned(x, y, g, dy)) return fail(ISPLIB_FAIL, entry, "x, y, g and dy must be 4-byte aligned");
    Gatv2h16Args a = {};
    a.rows = n; a.k = k; a.indx = row_t; a.pntrb = colb; a.pntre = cole; a.ns = negative_slope;
-   gatv2_16_heads(a, heads, k / heads);
+   attn16_head_geometry(heads, k / heads, a.heads, a.hshift, a.hlanes, a.hmask);
    a.own = reinterpret_cast<const unsigned short *>(y); a.ldown = ldy; a.att = att;
    a.out = reinterpret_cast<unsigned short *>(dy); a.ldout = lddy;
-   a.y = x; a.ldy = ldx; a.ybytes = nnz > 0 ? gatv2_16_extent(m, k, ldx, 2u) : 0u;
-   a.y2 = g; a.ldy2 = ldg; a.y2bytes = nnz > 0 ? gatv2_16_extent(m, k, ldg, 2u) : 0u;
-   a.t1 = lse; a.t2 = dsum; a.tbytes = nnz > 0 ? gatv2_16_extent(m, heads, heads, 4u) : 0u;
+   a.y = x; a.ldy = ldx; a.ybytes = nnz > 0 ? attn16_extent(m, k, ldx, 2u) : 0u;
+   a.y2 = g; a.ldy2 = ldg; a.y2bytes = nnz > 0 ? attn16_extent(m, k, ldg, 2u) : 0u;
+   a.t1 = lse; a.t2 = dsum; a.tbytes = nnz > 0 ? attn16_extent(m, heads, heads, 4u) : 0u;
    return gatv2_16_run(dtype, GATV2_16_BW_COLS, a, entry, stream);
 }

@@ -25,8 +25,8 @@
 // descriptor), and writes dkey and dv as two outputs.
 //
 // Every gathered table sits behind a buffer descriptor of exactly the extent it owns; dead edges and lanes past k carry BUF_OOB, which
-// the descriptor answers with 0.  No atomics, no LDS, a fixed order of operations: two launches give equal bits.  attention.hip,
-// gat.hip and gatv2.hip are untouched; their small helpers are restated here under names of their own.  DESIGN.md 4.6k.
+// the descriptor answers with 0.  No atomics, no LDS, a fixed order of operations: two launches give equal bits.  The column
+// map, the descriptor, the gathers and the butterfly are those of attn_common.h, shared with gat.hip and gatv2.hip.  DESIGN.md 4.6k, 4.6n.
 //
 // Attention dropout (include/isplib_hip_mha_drop.h: isplib_qkv_drop_*_hip): the three kernels are templates on DROP.
 // Every stored entry e and head h has a keep bit q_e,h = word(seed, CSR position of e, h) >= T (gat_dropout.h: the bit of gat.hip and
@@ -45,6 +45,7 @@
 #include "common.h"
 #include "gather.h"
 #include "gat_dropout.h"
+#include "attn_common.h"
 
 namespace isplib {
 
@@ -91,130 +92,6 @@ struct MhaArgs {
    float c;                                // float32(1 / (1 - p))
 };
 
-template <int LPR, int NCH> struct MhaCols {
-   unsigned cbyte[NCH], poison[NCH];       // this lane's 4 consecutive columns per chunk; past k: an offset the descriptor answers with 0
-   unsigned hbyte[NCH];                    // byte offset of the chunk's head inside a row of a [., H] table
-   int head[NCH];
-   bool ok[NCH][4], first[NCH];            // first: this lane's chunk opens a head (and lies inside k)
-   __device__ __forceinline__ MhaCols(const MhaArgs &a, int lc) {
-#pragma unroll
-      for (int j = 0; j < NCH; j++) {
-         const int c = (j * LPR + lc) * 4;
-         cbyte[j] = (unsigned)c * 4u;
-         poison[j] = c < (int)a.k ? 0u : BUF_OOB;
-         head[j] = c >> a.hshift;
-         hbyte[j] = (unsigned)head[j] * 4u;
-         first[j] = c < (int)a.k && ((unsigned)c & a.hmask) == 0u;
-#pragma unroll
-         for (int v = 0; v < 4; v++) ok[j][v] = c + v < (int)a.k;
-      }
-   }
-};
-
-// this lane's columns of row `row` of a dense operand; plain loads, nothing outside the row's k columns is read
-template <int LPR, int NCH>
-__device__ __forceinline__ void mha_own_row(const float *base, int64_t row, int64_t ld, int lc, const MhaCols<LPR, NCH> &cm,
-                                            float (&r)[NCH][4]) {
-#pragma unroll
-   for (int j = 0; j < NCH; j++)
-#pragma unroll
-      for (int v = 0; v < 4; v++) r[j][v] = cm.ok[j][v] ? base[(size_t)row * (size_t)ld + (size_t)((j * LPR + lc) * 4 + v)] : 0.0f;
-}
-
-// entry [row, head of chunk j] of a dense [rows, H] table, per chunk; a chunk past k reads nothing
-template <int LPR, int NCH>
-__device__ __forceinline__ void mha_own_head(const float *base, int64_t row, int heads, const MhaCols<LPR, NCH> &cm, float (&r)[NCH]) {
-#pragma unroll
-   for (int j = 0; j < NCH; j++) r[j] = cm.ok[j][0] ? base[(size_t)row * (size_t)heads + (size_t)cm.head[j]] : 0.0f;
-}
-
-// this lane's columns of a row, stored; nothing outside the row's k columns is written
-template <int LPR, int NCH>
-__device__ __forceinline__ void mha_store_row(float *base, int64_t row, int64_t ld, int lc, const MhaCols<LPR, NCH> &cm,
-                                              const float (&r)[NCH][4]) {
-#pragma unroll
-   for (int j = 0; j < NCH; j++)
-#pragma unroll
-      for (int v = 0; v < 4; v++)
-         if (cm.ok[j][v]) base[(size_t)row * (size_t)ld + (size_t)((j * LPR + lc) * 4 + v)] = r[j][v];
-}
-
-template <int LPR, int NCH>
-__device__ __forceinline__ void mha_load_wide(const __amdgpu_buffer_rsrc_t rsrc, unsigned off, const MhaCols<LPR, NCH> &cm, v4i_t (&t)[NCH]) {
-#pragma unroll
-   for (int j = 0; j < NCH; j++) t[j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)((off + cm.cbyte[j]) | cm.poison[j]), 0, 0);
-}
-
-template <int LPR, int NCH>
-__device__ __forceinline__ void mha_load_head(const __amdgpu_buffer_rsrc_t rsrc, unsigned offh, const MhaCols<LPR, NCH> &cm, float (&t)[NCH]) {
-#pragma unroll
-   for (int j = 0; j < NCH; j++)
-      t[j] = __int_as_float((int)__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)((offh + cm.hbyte[j]) | cm.poison[j]), 0, 0));
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t mha_rsrc(const float *p, unsigned bytes) {
-   return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p), 0, (int)bytes, 0x00020000);
-}
-
-// N sums over the lanes that share a head (an aligned group of `hlanes` lanes, a power of two <= LPR), level by level together; every
-// lane of the group ends with the same bits (each level adds the same two numbers on both sides).  Partners 1, 2, 4, 8 by DPP moves
-// inside the 16-lane row (gather.h), wider ones by ds_bpermute.
-template <int LPR, int N, int O = 1> __device__ __forceinline__ void mha_head_sum(float (&v)[N], int hlanes) {
-   if constexpr (O < LPR) {
-      float w[N];
-#pragma unroll
-      for (int i = 0; i < N; i++) w[i] = lane_xor<O>(v[i]);
-#pragma unroll
-      for (int i = 0; i < N; i++) v[i] = O < hlanes ? v[i] + w[i] : v[i];
-      mha_head_sum<LPR, N, 2 * O>(v, hlanes);
-   }
-}
-
-// the per-lane parts p[.][chunk] of P dot products per head -> the dot products, in every lane of the head (both chunks where the head
-// is the whole row)
-template <int LPR, int NCH, int P>
-__device__ __forceinline__ void mha_head_reduce(float (&p)[P][NCH], const MhaArgs &a) {
-   if (NCH == 2 && a.whole) {
-      float w[P];
-#pragma unroll
-      for (int i = 0; i < P; i++) w[i] = p[i][0] + p[i][NCH - 1];
-      mha_head_sum<LPR, P>(w, a.hlanes);
-#pragma unroll
-      for (int i = 0; i < P; i++) p[i][0] = p[i][NCH - 1] = w[i];
-   } else {
-      float w[P * NCH];
-#pragma unroll
-      for (int i = 0; i < P; i++)
-#pragma unroll
-         for (int j = 0; j < NCH; j++) w[i * NCH + j] = p[i][j];
-      mha_head_sum<LPR, P * NCH>(w, a.hlanes);
-#pragma unroll
-      for (int i = 0; i < P; i++)
-#pragma unroll
-         for (int j = 0; j < NCH; j++) p[i][j] = w[i * NCH + j];
-   }
-}
-
-// this lane's part of <r, t>_h for one chunk; a 16-byte load may run into the next row, the mask drops what it brought
-__device__ __forceinline__ float mha_dot_part(const float (&r)[4], const v4i_t &t, const bool (&ok)[4]) {
-   float p = 0.0f;
-#pragma unroll
-   for (int v = 0; v < 4; v++) p = fmaf(r[v], ok[v] ? __int_as_float(t[v]) : 0.0f, p);
-   return p;
-}
-
-// byte offset of the gathered row of edge `id` of the batch; a dead edge: -1
-__device__ __forceinline__ unsigned mha_off(int id, unsigned pitch_bytes) {
-   return id < 0 ? BUF_OOB : (unsigned)id * pitch_bytes;     // BUF_OOB + cbyte / hbyte (< 2^24) cannot wrap
-}
-
-// DROP: the per-lane constant of each chunk's head (gat_dropout.h)
-template <int LPR, int NCH>
-__device__ __forceinline__ void mha_drop_heads(const MhaArgs &a, const MhaCols<LPR, NCH> &cm, unsigned (&hk)[NCH]) {
-#pragma unroll
-   for (int j = 0; j < NCH; j++) hk[j] = gat_drop_head(a.seed_hi, (unsigned)cm.head[j]);
-}
-
 template <int LPR, int NCH, int WAVES, int U, bool DROP>
 __global__ __launch_bounds__(WAVES * 64) void mha_fw_kernel(const MhaArgs a) {
    constexpr int G = 64 / LPR;
@@ -224,12 +101,12 @@ __global__ __launch_bounds__(WAVES * 64) void mha_fw_kernel(const MhaArgs a) {
    const int64_t row = (int64_t)blockIdx.x * WAVES + wave;
    if (row >= a.rows) return;
    const int64_t eb = a.pntrb[row], ee = a.pntre[row];
-   const __amdgpu_buffer_rsrc_t rsk = mha_rsrc(a.ga, a.gabytes), rsv = mha_rsrc(a.gb, a.gbbytes);
-   const MhaCols<LPR, NCH> cm(a, lc);
+   const __amdgpu_buffer_rsrc_t rsk = attn_rsrc(a.ga, a.gabytes), rsv = attn_rsrc(a.gb, a.gbbytes);
+   const AttnHeadCols<LPR, NCH> cm(a.k, a.hshift, a.hmask, lc);
    float qv[NCH][4];
-   mha_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm, qv);
+   attn_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm.ok, qv);
    [[maybe_unused]] unsigned hk[NCH];
-   if constexpr (DROP) mha_drop_heads<LPR, NCH>(a, cm, hk);
+   if constexpr (DROP) attn_drop_heads<LPR, NCH>(a.seed_hi, cm, hk);
 
    float mrun[NCH], l[NCH], acc[NCH][4];
 #pragma unroll
@@ -255,16 +132,16 @@ __global__ __launch_bounds__(WAVES * 64) void mha_fw_kernel(const MhaArgs a) {
 #pragma unroll
          for (int u = 0; u < U; u++) {
             const int id = __shfl(id_l, (s0 + u * G + g) & 63);
-            mha_load_wide<LPR, NCH>(rsk, mha_off(id, ldkb), cm, kv[u]);
-            mha_load_wide<LPR, NCH>(rsv, mha_off(id, ldvb), cm, vv[u]);
+            attn_load_wide<LPR, NCH>(rsk, attn_off(id, ldkb), cm, kv[u]);
+            attn_load_wide<LPR, NCH>(rsv, attn_off(id, ldvb), cm, vv[u]);
             if constexpr (DROP) hw[u] = (unsigned)__shfl((int)hw_l, (s0 + u * G + g) & 63);
          }
          float sc[U][NCH];
 #pragma unroll
          for (int u = 0; u < U; u++)
 #pragma unroll
-            for (int j = 0; j < NCH; j++) sc[u][j] = mha_dot_part(qv[j], kv[u][j], cm.ok[j]);
-         mha_head_reduce<LPR, NCH, U>(sc, a);
+            for (int j = 0; j < NCH; j++) sc[u][j] = attn_dot_part(qv[j], kv[u][j], cm.ok[j]);
+         attn_head_reduce<LPR, NCH, U>(sc, a.whole, a.hlanes);
 #pragma unroll
          for (int j = 0; j < NCH; j++) {
             float mnew = mrun[j];
@@ -315,7 +192,7 @@ __global__ __launch_bounds__(WAVES * 64) void mha_fw_kernel(const MhaArgs a) {
       }
       if (cm.first[j]) a.hout[(size_t)row * (size_t)a.heads + (size_t)cm.head[j]] = empty ? -INFINITY : mrun[j] + logf(l[j]);
    }
-   mha_store_row<LPR, NCH>(a.out, row, a.ldout, lc, cm, acc);
+   attn_store_row<LPR, NCH>(a.out, row, a.ldout, lc, cm.ok, acc);
 }
 
 // one wave per row i: q_i, g_i and D[i,h] in registers; key_j and v_j gathered
@@ -328,23 +205,23 @@ __global__ __launch_bounds__(WAVES * 64) void mha_bw_rows_kernel(const MhaArgs a
    const int64_t row = (int64_t)blockIdx.x * WAVES + wave;
    if (row >= a.rows) return;
    const int64_t eb = a.pntrb[row], ee = a.pntre[row];
-   const __amdgpu_buffer_rsrc_t rsk = mha_rsrc(a.ga, a.gabytes), rsv = mha_rsrc(a.gb, a.gbbytes);
-   const MhaCols<LPR, NCH> cm(a, lc);
+   const __amdgpu_buffer_rsrc_t rsk = attn_rsrc(a.ga, a.gabytes), rsv = attn_rsrc(a.gb, a.gbbytes);
+   const AttnHeadCols<LPR, NCH> cm(a.k, a.hshift, a.hmask, lc);
    float qv[NCH][4], gv[NCH][4], lse[NCH], dsum[NCH];
-   mha_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm, qv);
-   mha_own_row<LPR, NCH>(a.g, row, a.ldg, lc, cm, gv);
-   mha_own_head<LPR, NCH>(a.lse_in, row, a.heads, cm, lse);
+   attn_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm.ok, qv);
+   attn_own_row<LPR, NCH>(a.g, row, a.ldg, lc, cm.ok, gv);
+   attn_own_head<LPR, NCH>(a.lse_in, row, a.heads, cm, lse);
    {
       // D[i,h] = <g_i, z_i>_h: every slot holds the row, so every lane of a head ends with it
       float zv[NCH][4], dp[1][NCH];
-      mha_own_row<LPR, NCH>(a.zin, row, a.ldzin, lc, cm, zv);
+      attn_own_row<LPR, NCH>(a.zin, row, a.ldzin, lc, cm.ok, zv);
 #pragma unroll
       for (int j = 0; j < NCH; j++) {
          dp[0][j] = 0.0f;
 #pragma unroll
          for (int v = 0; v < 4; v++) dp[0][j] = fmaf(gv[j][v], zv[j][v], dp[0][j]);
       }
-      mha_head_reduce<LPR, NCH, 1>(dp, a);
+      attn_head_reduce<LPR, NCH, 1>(dp, a.whole, a.hlanes);
 #pragma unroll
       for (int j = 0; j < NCH; j++) dsum[j] = dp[0][j];
    }
@@ -355,7 +232,7 @@ __global__ __launch_bounds__(WAVES * 64) void mha_bw_rows_kernel(const MhaArgs a
 #pragma unroll
       for (int v = 0; v < 4; v++) acc[j][v] = 0.0f;
    [[maybe_unused]] unsigned hk[NCH];
-   if constexpr (DROP) mha_drop_heads<LPR, NCH>(a, cm, hk);
+   if constexpr (DROP) attn_drop_heads<LPR, NCH>(a.seed_hi, cm, hk);
 
    const unsigned ldkb = (unsigned)a.ldga * 4u, ldvb = (unsigned)a.ldgb * 4u;
    for (int64_t base = eb; base < ee; base += 64) {
@@ -372,8 +249,8 @@ __global__ __launch_bounds__(WAVES * 64) void mha_bw_rows_kernel(const MhaArgs a
 #pragma unroll
          for (int u = 0; u < U; u++) {
             const int id = __shfl(id_l, (s0 + u * G + g) & 63);
-            mha_load_wide<LPR, NCH>(rsk, mha_off(id, ldkb), cm, kv[u]);
-            mha_load_wide<LPR, NCH>(rsv, mha_off(id, ldvb), cm, vv[u]);
+            attn_load_wide<LPR, NCH>(rsk, attn_off(id, ldkb), cm, kv[u]);
+            attn_load_wide<LPR, NCH>(rsv, attn_off(id, ldvb), cm, vv[u]);
             if constexpr (DROP) hw[u] = (unsigned)__shfl((int)hw_l, (s0 + u * G + g) & 63);
          }
          float part[2 * U][NCH];                       // <q_i, key_j>_h and t_e of the step through one butterfly
@@ -381,10 +258,10 @@ __global__ __launch_bounds__(WAVES * 64) void mha_bw_rows_kernel(const MhaArgs a
          for (int u = 0; u < U; u++)
 #pragma unroll
             for (int j = 0; j < NCH; j++) {
-               part[u][j] = mha_dot_part(qv[j], kv[u][j], cm.ok[j]);
-               part[U + u][j] = mha_dot_part(gv[j], vv[u][j], cm.ok[j]);
+               part[u][j] = attn_dot_part(qv[j], kv[u][j], cm.ok[j]);
+               part[U + u][j] = attn_dot_part(gv[j], vv[u][j], cm.ok[j]);
             }
-         mha_head_reduce<LPR, NCH, 2 * U>(part, a);
+         attn_head_reduce<LPR, NCH, 2 * U>(part, a.whole, a.hlanes);
 #pragma unroll
          for (int u = 0; u < U; u++) {
             const bool live = s0 + u * G + g < cnt;
@@ -412,7 +289,7 @@ __global__ __launch_bounds__(WAVES * 64) void mha_bw_rows_kernel(const MhaArgs a
       for (int v = 0; v < 4; v++) acc[j][v] = empty ? 0.0f : a.p * acc[j][v];
       if (cm.first[j]) a.hout[(size_t)row * (size_t)a.heads + (size_t)cm.head[j]] = empty ? 0.0f : dsum[j];
    }
-   mha_store_row<LPR, NCH>(a.out, row, a.ldout, lc, cm, acc);
+   attn_store_row<LPR, NCH>(a.out, row, a.ldout, lc, cm.ok, acc);
 }
 
 // one wave per column j of A (a row of the transposed structure): key_j and v_j in registers; q_i, g_i and lse, D of [i, head] gathered
@@ -425,12 +302,12 @@ __global__ __launch_bounds__(WAVES * 64) void mha_bw_cols_kernel(const MhaArgs a
    const int64_t row = (int64_t)blockIdx.x * WAVES + wave;
    if (row >= a.rows) return;
    const int64_t eb = a.pntrb[row], ee = a.pntre[row];
-   const __amdgpu_buffer_rsrc_t rsq = mha_rsrc(a.ga, a.gabytes), rsg = mha_rsrc(a.gb, a.gbbytes);
-   const __amdgpu_buffer_rsrc_t rs1 = mha_rsrc(a.t1, a.tbytes), rs2 = mha_rsrc(a.t2, a.tbytes);
-   const MhaCols<LPR, NCH> cm(a, lc);
+   const __amdgpu_buffer_rsrc_t rsq = attn_rsrc(a.ga, a.gabytes), rsg = attn_rsrc(a.gb, a.gbbytes);
+   const __amdgpu_buffer_rsrc_t rs1 = attn_rsrc(a.t1, a.tbytes), rs2 = attn_rsrc(a.t2, a.tbytes);
+   const AttnHeadCols<LPR, NCH> cm(a.k, a.hshift, a.hmask, lc);
    float kv[NCH][4], vv[NCH][4];
-   mha_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm, kv);
-   mha_own_row<LPR, NCH>(a.own2, row, a.ldown2, lc, cm, vv);
+   attn_own_row<LPR, NCH>(a.own, row, a.ldown, lc, cm.ok, kv);
+   attn_own_row<LPR, NCH>(a.own2, row, a.ldown2, lc, cm.ok, vv);
 
    float dk[NCH][4], dv[NCH][4];
 #pragma unroll
@@ -438,7 +315,7 @@ __global__ __launch_bounds__(WAVES * 64) void mha_bw_cols_kernel(const MhaArgs a
 #pragma unroll
       for (int v = 0; v < 4; v++) dk[j][v] = dv[j][v] = 0.0f;
    [[maybe_unused]] unsigned hk[NCH];
-   if constexpr (DROP) mha_drop_heads<LPR, NCH>(a, cm, hk);
+   if constexpr (DROP) attn_drop_heads<LPR, NCH>(a.seed_hi, cm, hk);
 
    const unsigned ldqb = (unsigned)a.ldga * 4u, ldgb = (unsigned)a.ldgb * 4u, hb = (unsigned)a.heads * 4u;
    for (int64_t base = eb; base < ee; base += 64) {
@@ -456,10 +333,10 @@ __global__ __launch_bounds__(WAVES * 64) void mha_bw_cols_kernel(const MhaArgs a
 #pragma unroll
          for (int u = 0; u < U; u++) {
             const int id = __shfl(id_l, (s0 + u * G + g) & 63);
-            mha_load_wide<LPR, NCH>(rsq, mha_off(id, ldqb), cm, qg[u]);
-            mha_load_wide<LPR, NCH>(rsg, mha_off(id, ldgb), cm, gg[u]);
-            mha_load_head<LPR, NCH>(rs1, mha_off(id, hb), cm, ls[u]);
-            mha_load_head<LPR, NCH>(rs2, mha_off(id, hb), cm, dd[u]);
+            attn_load_wide<LPR, NCH>(rsq, attn_off(id, ldqb), cm, qg[u]);
+            attn_load_wide<LPR, NCH>(rsg, attn_off(id, ldgb), cm, gg[u]);
+            attn_load_head<LPR, NCH>(rs1, attn_off(id, hb), cm, ls[u]);
+            attn_load_head<LPR, NCH>(rs2, attn_off(id, hb), cm, dd[u]);
             if constexpr (DROP) hw[u] = (unsigned)__shfl((int)hw_l, (s0 + u * G + g) & 63);
          }
          float part[2 * U][NCH];
@@ -467,10 +344,10 @@ __global__ __launch_bounds__(WAVES * 64) void mha_bw_cols_kernel(const MhaArgs a
          for (int u = 0; u < U; u++)
 #pragma unroll
             for (int j = 0; j < NCH; j++) {
-               part[u][j] = mha_dot_part(kv[j], qg[u][j], cm.ok[j]);
-               part[U + u][j] = mha_dot_part(vv[j], gg[u][j], cm.ok[j]);
+               part[u][j] = attn_dot_part(kv[j], qg[u][j], cm.ok[j]);
+               part[U + u][j] = attn_dot_part(vv[j], gg[u][j], cm.ok[j]);
             }
-         mha_head_reduce<LPR, NCH, 2 * U>(part, a);
+         attn_head_reduce<LPR, NCH, 2 * U>(part, a.whole, a.hlanes);
 #pragma unroll
          for (int u = 0; u < U; u++) {
             const bool live = s0 + u * G + g < cnt;
@@ -507,8 +384,8 @@ __global__ __launch_bounds__(WAVES * 64) void mha_bw_cols_kernel(const MhaArgs a
    for (int j = 0; j < NCH; j++)
 #pragma unroll
       for (int v = 0; v < 4; v++) dk[j][v] *= a.p;    // no incoming entry: 0
-   mha_store_row<LPR, NCH>(a.out, row, a.ldout, lc, cm, dk);
-   mha_store_row<LPR, NCH>(a.out2, row, a.ldout2, lc, cm, dv);
+   attn_store_row<LPR, NCH>(a.out, row, a.ldout, lc, cm.ok, dk);
+   attn_store_row<LPR, NCH>(a.out2, row, a.ldout2, lc, cm.ok, dv);
 }
 
 enum { MHA_FW = 0, MHA_BW_ROWS = 1, MHA_BW_COLS = 2 };
@@ -527,59 +404,19 @@ static int launch_mha(int which, const MhaArgs &a, const char *entry, hipStream_
    return check_launch(entry);
 }
 
-// the width dispatch of gatv2.hip, up to two chunks per lane; DROP: the kernels with attention dropout
-template <bool DROP>
-static int mha_by_width_of(int which, const MhaArgs &a, const char *entry, hipStream_t st) {
-   const int64_t w = (a.k + 3) / 4;
-   if (w <= 8) return launch_mha<8, 1, DROP>(which, a, entry, st);
-   if (w <= 16) return launch_mha<16, 1, DROP>(which, a, entry, st);
-   if (w <= 32) return launch_mha<32, 1, DROP>(which, a, entry, st);
-   if (w <= 64) return launch_mha<64, 1, DROP>(which, a, entry, st);
-   return launch_mha<64, 2, DROP>(which, a, entry, st);
-}
-
+// the width ladder (attn_by_width); DROP: the kernels with attention dropout
 static int mha_by_width(int which, const MhaArgs &a, bool drop, const char *entry, hipStream_t st) {
-   return drop ? mha_by_width_of<true>(which, a, entry, st) : mha_by_width_of<false>(which, a, entry, st);
+   return attn_by_width(a.k, [&](auto lpr, auto nch) {
+      constexpr int LPR = decltype(lpr)::value, NCH = decltype(nch)::value;
+      return drop ? launch_mha<LPR, NCH, true>(which, a, entry, st) : launch_mha<LPR, NCH, false>(which, a, entry, st);
+   });
 }
 
-// the dropout of one call (isplib_qkv_drop_*_hip): the threshold T(p), c = float32(1 / (1 - p)) and the seed; none: the entries without it
-struct MhaDrop {
-   bool on;
-   uint32_t threshold;
-   float keep_scale;
-   uint64_t seed;
-};
-static const MhaDrop MHA_NO_DROP = {false, 0u, 1.0f, 0ull};
-
-// what the dropout entries refuse before a launch: a keep scale that is no positive finite number would poison every row, the keep bit
-// is a function of a position below 2^31 and of a seed below 2^63
-static const char *mha_drop_refusal(const MhaDrop &dr, int64_t nnz) {
-   if (!dr.on) return nullptr;
-   if (!(dr.keep_scale > 0.0f && dr.keep_scale <= FLT_MAX)) return "keep_scale must be a positive finite number";
-   if (nnz >= (1LL << 31)) return "nnz must be below 2^31";
-   if (dr.seed >= (1ull << 63)) return "seed must be below 2^63";
-   return nullptr;
-}
-
-static void mha_set_drop(MhaArgs &a, const MhaDrop &dr) {
-   a.seed_lo = (unsigned)dr.seed; a.seed_hi = (unsigned)(dr.seed >> 32); a.T = dr.threshold; a.c = dr.keep_scale;
-}
-
-// what a descriptor over `rows` rows of k floats at pitch ld may answer: the extent a row-strided view owns, not rows * ld
-static unsigned mha_extent(int64_t rows, int64_t k, int64_t ld) {
-   return rows <= 0 ? 0u : (unsigned)(((unsigned long long)(rows - 1) * (unsigned long long)ld + (unsigned long long)k) * 4ull);
-}
-
-// the head geometry of a launch; the domain (isplib_mha_serves) has been checked: H == 1, or d a power of two >= 4
-static void mha_heads(MhaArgs &a, int64_t heads, int64_t d) {
-   a.heads = (int)heads;
-   if (heads == 1) {
-      a.hshift = 31; a.hlanes = 64; a.hmask = 0x7fffffffu; a.whole = 1;
-   } else {
-      int sh = 0;
-      while ((1LL << sh) < d) sh++;
-      a.hshift = sh; a.hlanes = (int)(d / 4); a.hmask = (unsigned)(d - 1); a.whole = 0;
-   }
+// what the dropout entries (isplib_qkv_drop_*_hip) refuse before a launch: attn_drop_refusal, and the keep bit is a function of a seed
+// below 2^63
+static const char *mha_drop_refusal(const AttnDrop &dr, int64_t nnz) {
+   if (const char *why = attn_drop_refusal(dr, nnz, "keep_scale must be a positive finite number")) return why;
+   return dr.on && dr.seed >= (1ull << 63) ? "seed must be below 2^63" : nullptr;
 }
 
 static const char *const MHA_DOMAIN = "outside isplib_mha_serves(rows_gathered, heads, d, ld) = isplib_gat_serves: 1 <= heads, 1 <= d, "
@@ -597,7 +434,7 @@ extern "C" int isplib_mha_domain(int64_t rows_gathered, int64_t heads, int64_t d
 // The three entries, with and without attention dropout.
 static int mha_forward(const char *entry, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
                        const int64_t *pntre, int64_t heads, float scale, const float *q, int64_t ldq, const float *key, int64_t ldk,
-                       const float *v, int64_t ldv, float *z, int64_t ldz, float *lse, void *stream, const MhaDrop &dr = MHA_NO_DROP) {
+                       const float *v, int64_t ldv, float *z, int64_t ldz, float *lse, void *stream, const AttnDrop &dr = ATTN_NO_DROP) {
    clear_error();
    if (const char *why = mha_drop_refusal(dr, nnz)) return fail(ISPLIB_FAIL, entry, why);
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
@@ -610,19 +447,19 @@ static int mha_forward(const char *entry, int64_t m, int64_t n, int64_t k, int64
       return fail(ISPLIB_NO_OPT_IMPL, entry, MHA_DOMAIN);
    MhaArgs a = {};
    a.rows = m; a.k = k; a.indx = indx; a.pntrb = pntrb; a.pntre = pntre; a.p = scale;
-   mha_heads(a, heads, k / heads);
+   attn_head_geometry(heads, k / heads, a.heads, a.hshift, a.hlanes, a.hmask, a.whole);
    a.own = q; a.ldown = ldq;
    a.out = z; a.ldout = ldz; a.hout = lse;
-   a.ga = key; a.ldga = ldk; a.gabytes = nnz > 0 ? mha_extent(n, k, ldk) : 0u;
-   a.gb = v; a.ldgb = ldv; a.gbbytes = nnz > 0 ? mha_extent(n, k, ldv) : 0u;
-   mha_set_drop(a, dr);
+   a.ga = key; a.ldga = ldk; a.gabytes = nnz > 0 ? attn_extent(n, k, ldk) : 0u;
+   a.gb = v; a.ldgb = ldv; a.gbbytes = nnz > 0 ? attn_extent(n, k, ldv) : 0u;
+   attn_set_drop(dr, a.seed_lo, a.seed_hi, a.T, a.c);
    return mha_by_width(MHA_FW, a, dr.on, entry, (hipStream_t)stream);
 }
 
 static int mha_backward_rows(const char *entry, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
                              const int64_t *pntre, int64_t heads, float scale, const float *q, int64_t ldq, const float *key,
                              int64_t ldk, const float *v, int64_t ldv, const float *g, int64_t ldg, const float *z, int64_t ldz,
-                             const float *lse, float *dq, int64_t lddq, float *dsum, void *stream, const MhaDrop &dr = MHA_NO_DROP) {
+                             const float *lse, float *dq, int64_t lddq, float *dsum, void *stream, const AttnDrop &dr = ATTN_NO_DROP) {
    clear_error();
    if (const char *why = mha_drop_refusal(dr, nnz)) return fail(ISPLIB_FAIL, entry, why);
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
@@ -636,12 +473,12 @@ static int mha_backward_rows(const char *entry, int64_t m, int64_t n, int64_t k,
       return fail(ISPLIB_NO_OPT_IMPL, entry, MHA_DOMAIN);
    MhaArgs a = {};
    a.rows = m; a.k = k; a.indx = indx; a.pntrb = pntrb; a.pntre = pntre; a.p = scale;
-   mha_heads(a, heads, k / heads);
+   attn_head_geometry(heads, k / heads, a.heads, a.hshift, a.hlanes, a.hmask, a.whole);
    a.own = q; a.ldown = ldq; a.g = g; a.ldg = ldg; a.zin = z; a.ldzin = ldz; a.lse_in = lse;
    a.out = dq; a.ldout = lddq; a.hout = dsum;
-   a.ga = key; a.ldga = ldk; a.gabytes = nnz > 0 ? mha_extent(n, k, ldk) : 0u;
-   a.gb = v; a.ldgb = ldv; a.gbbytes = nnz > 0 ? mha_extent(n, k, ldv) : 0u;
-   mha_set_drop(a, dr);
+   a.ga = key; a.ldga = ldk; a.gabytes = nnz > 0 ? attn_extent(n, k, ldk) : 0u;
+   a.gb = v; a.ldgb = ldv; a.gbbytes = nnz > 0 ? attn_extent(n, k, ldv) : 0u;
+   attn_set_drop(dr, a.seed_lo, a.seed_hi, a.T, a.c);
    return mha_by_width(MHA_BW_ROWS, a, dr.on, entry, (hipStream_t)stream);
 }
 
@@ -649,7 +486,7 @@ static int mha_backward_cols(const char *entry, int64_t m, int64_t n, int64_t k,
                              const int64_t *cole, const int64_t *csr2csc, int64_t heads, float scale, const float *q, int64_t ldq,
                              const float *g, int64_t ldg, const float *lse, const float *dsum, const float *key, int64_t ldk,
                              const float *v, int64_t ldv, float *dkey, int64_t lddk, float *dv, int64_t lddv, void *stream,
-                             const MhaDrop &dr = MHA_NO_DROP) {
+                             const AttnDrop &dr = ATTN_NO_DROP) {
    clear_error();
    if (const char *why = mha_drop_refusal(dr, nnz)) return fail(ISPLIB_FAIL, entry, why);
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
@@ -664,14 +501,14 @@ static int mha_backward_cols(const char *entry, int64_t m, int64_t n, int64_t k,
       return fail(ISPLIB_NO_OPT_IMPL, entry, MHA_DOMAIN);
    MhaArgs a = {};
    a.rows = n; a.k = k; a.indx = row_t; a.pntrb = colb; a.pntre = cole; a.p = scale;
-   mha_heads(a, heads, k / heads);
+   attn_head_geometry(heads, k / heads, a.heads, a.hshift, a.hlanes, a.hmask, a.whole);
    a.own = key; a.ldown = ldk; a.own2 = v; a.ldown2 = ldv;
    a.out = dkey; a.ldout = lddk; a.out2 = dv; a.ldout2 = lddv;
-   a.ga = q; a.ldga = ldq; a.gabytes = nnz > 0 ? mha_extent(m, k, ldq) : 0u;
-   a.gb = g; a.ldgb = ldg; a.gbbytes = nnz > 0 ? mha_extent(m, k, ldg) : 0u;
-   a.t1 = lse; a.t2 = dsum; a.tbytes = nnz > 0 ? mha_extent(m, heads, heads) : 0u;
+   a.ga = q; a.ldga = ldq; a.gabytes = nnz > 0 ? attn_extent(m, k, ldq) : 0u;
+   a.gb = g; a.ldgb = ldg; a.gbbytes = nnz > 0 ? attn_extent(m, k, ldg) : 0u;
+   a.t1 = lse; a.t2 = dsum; a.tbytes = nnz > 0 ? attn_extent(m, heads, heads) : 0u;
    if (dr.on) a.epos = csr2csc;
-   mha_set_drop(a, dr);
+   attn_set_drop(dr, a.seed_lo, a.seed_hi, a.T, a.c);
    return mha_by_width(MHA_BW_COLS, a, dr.on, entry, (hipStream_t)stream);
 }
 
@@ -703,7 +540,7 @@ extern "C" int isplib_qkv_drop_csr_hip(int64_t m, int64_t n, int64_t k, int64_t 
                                        int64_t ldk, const float *v, int64_t ldv, float *z, int64_t ldz, float *lse, void *stream,
                                        uint32_t threshold, float keep_scale, uint64_t seed) {
    return mha_forward("isplib_qkv_drop_csr_hip", m, n, k, nnz, indx, pntrb, pntre, heads, scale, q, ldq, key, ldk, v, ldv, z, ldz, lse,
-                      stream, MhaDrop{true, threshold, keep_scale, seed});
+                      stream, AttnDrop{true, threshold, keep_scale, seed});
 }
 
 extern "C" int isplib_qkv_drop_bw_rows_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
@@ -712,7 +549,7 @@ extern "C" int isplib_qkv_drop_bw_rows_hip(int64_t m, int64_t n, int64_t k, int6
                                            const float *z, int64_t ldz, const float *lse, float *dq, int64_t lddq, float *dsum,
                                            void *stream, uint32_t threshold, float keep_scale, uint64_t seed) {
    return mha_backward_rows("isplib_qkv_drop_bw_rows_hip", m, n, k, nnz, indx, pntrb, pntre, heads, scale, q, ldq, key, ldk, v, ldv, g,
-                            ldg, z, ldz, lse, dq, lddq, dsum, stream, MhaDrop{true, threshold, keep_scale, seed});
+                            ldg, z, ldz, lse, dq, lddq, dsum, stream, AttnDrop{true, threshold, keep_scale, seed});
 }
 
 extern "C" int isplib_qkv_drop_bw_cols_hip(int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t, const int64_t *colb,
@@ -721,5 +558,5 @@ extern "C" int isplib_qkv_drop_bw_cols_hip(int64_t m, int64_t n, int64_t k, int6
                                            const float *key, int64_t ldk, const float *v, int64_t ldv, float *dkey, int64_t lddk,
                                            float *dv, int64_t lddv, void *stream, uint32_t threshold, float keep_scale, uint64_t seed) {
    return mha_backward_cols("isplib_qkv_drop_bw_cols_hip", m, n, k, nnz, row_t, colb, cole, csr2csc, heads, scale, q, ldq, g, ldg, lse,
-                            dsum, key, ldk, v, ldv, dkey, lddk, dv, lddv, stream, MhaDrop{true, threshold, keep_scale, seed});
+                            dsum, key, ldk, v, ldv, dkey, lddk, dv, lddv, stream, AttnDrop{true, threshold, keep_scale, seed});
 }

@@ -34,14 +34,15 @@
 // Dacc = sum a_e t_e and, per column, P_c = sum a_e t_e key_jc and Q_c = sum a_e key_jc; the slots merge by plain sums; D = Dacc / l
 // and dq_ic = p (P_c - D Q_c).  The columns kernel walks the transposed structure with key_j and v_j (widened) in registers, gathers
 // q_i and g_i (16 bytes each) and lse, D of [i, head] (4 bytes each, two tables, each behind its own descriptor), and writes dkey and
-// dv, each rounded once, each at its own pitch.  mha.hip, gatv2_16.hip and the other kernel files are untouched; their small helpers
-// are restated here under names of their own.  DESIGN.md 4.6l.
+// dv, each rounded once, each at its own pitch.  The column map, the descriptor, the gathers, the widening and the butterfly are those
+// of attn16_common.h, shared with gat16.hip and gatv2_16.hip.  DESIGN.md 4.6l, 4.6n.
 #include <cfloat>
 #include <cmath>
 
 #include "common.h"
 #include "gather.h"
 #include "half16.h"
+#include "attn16_common.h"
 
 // edges per slot and step, per kernel: measured among {2, 4}; an experiment build may override them (make EXTRA=-D...)
 #ifndef ISPLIB_MHA16_FW_U
@@ -94,103 +95,6 @@ struct Mha16Args {
    unsigned tbytes;
 };
 
-// this lane's eight consecutive columns and their head; ok[q]: the dword of columns (2q, 2q + 1) lies inside the row (k is even)
-struct Mha16Cols {
-   int col, head;
-   unsigned cbyte, hbyte, poison;            // past k: an offset the descriptors answer with 0
-   bool ok[4], first;                        // first: this lane opens a head (and lies inside k)
-   __device__ __forceinline__ Mha16Cols(const Mha16Args &a, int lc) {
-      col = lc * 8;
-      cbyte = (unsigned)col * 2u;
-      poison = col < (int)a.k ? 0u : BUF_OOB;
-      head = col >> a.hshift;
-      hbyte = (unsigned)head * 4u;
-      first = col < (int)a.k && ((unsigned)col & a.hmask) == 0u;
-#pragma unroll
-      for (int q = 0; q < 4; q++) ok[q] = col + 2 * q < (int)a.k;
-   }
-};
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t mha16_desc(const void *p, unsigned bytes) {
-   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
-}
-
-// this lane's columns of row `row` of a dense 16-bit operand as floats; plain dword loads (base, pitch and column are even), nothing
-// outside the row's k columns is read
-template <int ELT>
-__device__ __forceinline__ void mha16_own_row(const unsigned short *base, int64_t row, int64_t ld, const Mha16Cols &cm, float (&r)[8]) {
-   const unsigned *p = reinterpret_cast<const unsigned *>(base + (size_t)row * (size_t)ld + (size_t)cm.col);
-#pragma unroll
-   for (int q = 0; q < 4; q++) {
-      unsigned w = 0u;
-      if (cm.ok[q]) w = p[q];
-      widen2<ELT>(w, r[2 * q], r[2 * q + 1]);
-   }
-}
-
-// entry [row, this lane's head] of a dense fp32 [rows, H] table; a lane past k reads nothing
-__device__ __forceinline__ float mha16_own_head(const float *base, int64_t row, int heads, const Mha16Cols &cm) {
-   return cm.poison == 0u ? base[(size_t)row * (size_t)heads + (size_t)cm.head] : 0.0f;
-}
-
-// byte offset of the gathered row of edge `id` at a pitch of `pitch_bytes`; a dead edge: BUF_OOB
-__device__ __forceinline__ unsigned mha16_off(int id, unsigned pitch_bytes) {
-   return id < 0 ? BUF_OOB : (unsigned)id * pitch_bytes;     // BUF_OOB + cbyte / hbyte (< 2^10) cannot wrap
-}
-
-__device__ __forceinline__ v4i_t mha16_load_wide(const __amdgpu_buffer_rsrc_t rsrc, unsigned off, const Mha16Cols &cm) {
-   return __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)((off + cm.cbyte) | cm.poison), 0, 0);
-}
-
-__device__ __forceinline__ float mha16_load_head(const __amdgpu_buffer_rsrc_t rsrc, unsigned offh, const Mha16Cols &cm) {
-   return __int_as_float((int)__builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)((offh + cm.hbyte) | cm.poison), 0, 0));
-}
-
-// a gathered vector as eight floats; a dword the 16-byte load brought from outside the row is dropped by a select, not a multiply
-template <int ELT> __device__ __forceinline__ void mha16_widen(const v4i_t &t, const Mha16Cols &cm, float (&y)[8]) {
-#pragma unroll
-   for (int q = 0; q < 4; q++) widen2<ELT>(cm.ok[q] ? (unsigned)t[q] : 0u, y[2 * q], y[2 * q + 1]);
-}
-
-// N sums over the lanes that share a head (an aligned group of `hlanes` lanes, a power of two; H == 1: the whole slot), level by level
-// together; every lane of the group ends with the same bits (each level adds the same two numbers on both sides).  Partners 1, 2, 4, 8
-// by DPP moves inside the 16-lane row (gather.h), wider ones by ds_bpermute.  hlanes == 1: no cross-lane step is taken
-template <int LPR, int N, int O = 1> __device__ __forceinline__ void mha16_head_sum(float (&v)[N], int hlanes) {
-   if constexpr (O < LPR) {
-      float w[N];
-#pragma unroll
-      for (int i = 0; i < N; i++) w[i] = lane_xor<O>(v[i]);
-#pragma unroll
-      for (int i = 0; i < N; i++) v[i] = O < hlanes ? v[i] + w[i] : v[i];
-      mha16_head_sum<LPR, N, 2 * O>(v, hlanes);
-   }
-}
-
-// this lane's part of <r, t>_h: one fma chain over its eight columns; a column past k has r = t = 0
-__device__ __forceinline__ float mha16_dot_part(const float (&r)[8], const float (&t)[8]) {
-   float p = 0.0f;
-#pragma unroll
-   for (int v = 0; v < 8; v++) p = fmaf(r[v], t[v], p);
-   return p;
-}
-
-// the lane's eight finished columns, rounded once; only the dwords inside the row are written
-template <int ELT>
-__device__ __forceinline__ void mha16_store_row(unsigned short *base, int64_t row, int64_t ld, const Mha16Cols &cm, const float (&r)[8]) {
-   if (cm.poison != 0u) return;
-   unsigned *p = reinterpret_cast<unsigned *>(base + (size_t)row * (size_t)ld + (size_t)cm.col);
-   unsigned d[4];
-#pragma unroll
-   for (int q = 0; q < 4; q++) d[q] = narrow2<ELT>(r[2 * q], r[2 * q + 1]);
-   if (cm.ok[3] && ((uintptr_t)p & 15) == 0) {
-      *reinterpret_cast<uint4 *>(p) = make_uint4(d[0], d[1], d[2], d[3]);
-   } else {
-#pragma unroll
-      for (int q = 0; q < 4; q++)
-         if (cm.ok[q]) p[q] = d[q];
-   }
-}
-
 template <int ELT, int LPR, int WAVES, int U>
 __global__ __launch_bounds__(WAVES * 64) void mha16_fw_kernel(const Mha16Args a) {
    constexpr int G = 64 / LPR;
@@ -200,10 +104,10 @@ __global__ __launch_bounds__(WAVES * 64) void mha16_fw_kernel(const Mha16Args a)
    const int64_t row = (int64_t)blockIdx.x * WAVES + wave;
    if (row >= a.rows) return;
    const int64_t eb = a.pntrb[row], ee = a.pntre[row];
-   const __amdgpu_buffer_rsrc_t rsk = mha16_desc(a.ga, a.gabytes), rsv = mha16_desc(a.gb, a.gbbytes);
-   const Mha16Cols cm(a, lc);
+   const __amdgpu_buffer_rsrc_t rsk = attn16_desc(a.ga, a.gabytes), rsv = attn16_desc(a.gb, a.gbbytes);
+   const Attn16HeadCols cm(a.k, a.hshift, a.hmask, lc);
    float qv[8];
-   mha16_own_row<ELT>(a.own, row, a.ldown, cm, qv);
+   attn16_own_row<ELT>(a.own, row, a.ldown, cm.col, cm.ok, qv);
 
    float mrun = MHA16_NONE, l = 0.0f, acc[8];
 #pragma unroll
@@ -221,17 +125,17 @@ __global__ __launch_bounds__(WAVES * 64) void mha16_fw_kernel(const Mha16Args a)
 #pragma unroll
          for (int u = 0; u < U; u++) {
             const int id = __shfl(id_l, (s0 + u * G + g) & 63);
-            kv[u] = mha16_load_wide(rsk, mha16_off(id, ldkb), cm);
-            vv[u] = mha16_load_wide(rsv, mha16_off(id, ldvb), cm);
+            kv[u] = attn16_load_wide(rsk, attn16_off(id, ldkb), cm);
+            vv[u] = attn16_load_wide(rsv, attn16_off(id, ldvb), cm);
          }
          float sc[U];
 #pragma unroll
          for (int u = 0; u < U; u++) {
             float k8[8];
-            mha16_widen<ELT>(kv[u], cm, k8);
-            sc[u] = mha16_dot_part(qv, k8);
+            attn16_widen<ELT>(kv[u], cm.ok, k8);
+            sc[u] = attn16_dot_part(qv, k8);
          }
-         mha16_head_sum<LPR, U>(sc, a.hlanes);
+         attn16_head_sum<LPR, U>(sc, a.hlanes);
          float mnew = mrun;
 #pragma unroll
          for (int u = 0; u < U; u++) {
@@ -247,7 +151,7 @@ __global__ __launch_bounds__(WAVES * 64) void mha16_fw_kernel(const Mha16Args a)
          for (int u = 0; u < U; u++) {
             const float w = (s0 + u * G + g < cnt) ? __expf(sc[u] - mnew) : 0.0f;
             float v8[8];
-            mha16_widen<ELT>(vv[u], cm, v8);
+            attn16_widen<ELT>(vv[u], cm.ok, v8);
             l += w;
 #pragma unroll
             for (int v = 0; v < 8; v++) acc[v] = fmaf(w, v8[v], acc[v]);
@@ -270,7 +174,7 @@ __global__ __launch_bounds__(WAVES * 64) void mha16_fw_kernel(const Mha16Args a)
    float zr[8];
 #pragma unroll
    for (int v = 0; v < 8; v++) zr[v] = empty ? 0.0f : acc[v] / l;
-   mha16_store_row<ELT>(a.out, row, a.ldout, cm, zr);
+   attn16_store_row<ELT>(a.out, row, a.ldout, cm.col, cm.ok, zr);
    if (cm.first) a.hout[(size_t)row * (size_t)a.heads + (size_t)cm.head] = empty ? -INFINITY : mrun + logf(l);
 }
 
@@ -284,12 +188,12 @@ __global__ __launch_bounds__(WAVES * 64) void mha16_bw_rows_kernel(const Mha16Ar
    const int64_t row = (int64_t)blockIdx.x * WAVES + wave;
    if (row >= a.rows) return;
    const int64_t eb = a.pntrb[row], ee = a.pntre[row];
-   const __amdgpu_buffer_rsrc_t rsk = mha16_desc(a.ga, a.gabytes), rsv = mha16_desc(a.gb, a.gbbytes);
-   const Mha16Cols cm(a, lc);
+   const __amdgpu_buffer_rsrc_t rsk = attn16_desc(a.ga, a.gabytes), rsv = attn16_desc(a.gb, a.gbbytes);
+   const Attn16HeadCols cm(a.k, a.hshift, a.hmask, lc);
    float qv[8], gv[8];
-   mha16_own_row<ELT>(a.own, row, a.ldown, cm, qv);
-   mha16_own_row<ELT>(a.g, row, a.ldg, cm, gv);
-   const float lse = mha16_own_head(a.lse_in, row, a.heads, cm);
+   attn16_own_row<ELT>(a.own, row, a.ldown, cm.col, cm.ok, qv);
+   attn16_own_row<ELT>(a.g, row, a.ldg, cm.col, cm.ok, gv);
+   const float lse = attn16_own_head(a.lse_in, row, a.heads, cm);
 
    float l = 0.0f, dacc = 0.0f;                        // per head: sum a_e, sum a_e t_e
    float pc[8], qc[8];                                 // per column: sum a_e t_e key_jc, sum a_e key_jc
@@ -308,19 +212,19 @@ __global__ __launch_bounds__(WAVES * 64) void mha16_bw_rows_kernel(const Mha16Ar
 #pragma unroll
          for (int u = 0; u < U; u++) {
             const int id = __shfl(id_l, (s0 + u * G + g) & 63);
-            kv[u] = mha16_load_wide(rsk, mha16_off(id, ldkb), cm);
-            vv[u] = mha16_load_wide(rsv, mha16_off(id, ldvb), cm);
+            kv[u] = attn16_load_wide(rsk, attn16_off(id, ldkb), cm);
+            vv[u] = attn16_load_wide(rsv, attn16_off(id, ldvb), cm);
          }
          float part[2 * U];                            // <q_i, key_j>_h and t_e of the step through one butterfly
 #pragma unroll
          for (int u = 0; u < U; u++) {
             float k8[8], v8[8];
-            mha16_widen<ELT>(kv[u], cm, k8);
-            mha16_widen<ELT>(vv[u], cm, v8);
-            part[u] = mha16_dot_part(qv, k8);
-            part[U + u] = mha16_dot_part(gv, v8);
+            attn16_widen<ELT>(kv[u], cm.ok, k8);
+            attn16_widen<ELT>(vv[u], cm.ok, v8);
+            part[u] = attn16_dot_part(qv, k8);
+            part[U + u] = attn16_dot_part(gv, v8);
          }
-         mha16_head_sum<LPR, 2 * U>(part, a.hlanes);         // every lane takes part: not under `live`
+         attn16_head_sum<LPR, 2 * U>(part, a.hlanes);         // every lane takes part: not under `live`
 #pragma unroll
          for (int u = 0; u < U; u++) {
             const bool live = s0 + u * G + g < cnt;
@@ -329,7 +233,7 @@ __global__ __launch_bounds__(WAVES * 64) void mha16_bw_rows_kernel(const Mha16Ar
             l += ae;
             dacc += aet;
             float k8[8];
-            mha16_widen<ELT>(kv[u], cm, k8);
+            attn16_widen<ELT>(kv[u], cm.ok, k8);
 #pragma unroll
             for (int v = 0; v < 8; v++) {
                pc[v] = fmaf(aet, k8[v], pc[v]);
@@ -354,7 +258,7 @@ __global__ __launch_bounds__(WAVES * 64) void mha16_bw_rows_kernel(const Mha16Ar
    float dq[8];
 #pragma unroll
    for (int v = 0; v < 8; v++) dq[v] = empty ? 0.0f : a.p * (pc[v] - dsum * qc[v]);
-   mha16_store_row<ELT>(a.out, row, a.ldout, cm, dq);
+   attn16_store_row<ELT>(a.out, row, a.ldout, cm.col, cm.ok, dq);
    if (cm.first) a.hout[(size_t)row * (size_t)a.heads + (size_t)cm.head] = dsum;
 }
 
@@ -368,12 +272,12 @@ __global__ __launch_bounds__(WAVES * 64) void mha16_bw_cols_kernel(const Mha16Ar
    const int64_t row = (int64_t)blockIdx.x * WAVES + wave;
    if (row >= a.rows) return;
    const int64_t eb = a.pntrb[row], ee = a.pntre[row];
-   const __amdgpu_buffer_rsrc_t rsq = mha16_desc(a.ga, a.gabytes), rsg = mha16_desc(a.gb, a.gbbytes);
-   const __amdgpu_buffer_rsrc_t rs1 = mha16_desc(a.t1, a.tbytes), rs2 = mha16_desc(a.t2, a.tbytes);
-   const Mha16Cols cm(a, lc);
+   const __amdgpu_buffer_rsrc_t rsq = attn16_desc(a.ga, a.gabytes), rsg = attn16_desc(a.gb, a.gbbytes);
+   const __amdgpu_buffer_rsrc_t rs1 = attn16_desc(a.t1, a.tbytes), rs2 = attn16_desc(a.t2, a.tbytes);
+   const Attn16HeadCols cm(a.k, a.hshift, a.hmask, lc);
    float kv[8], vv[8];
-   mha16_own_row<ELT>(a.own, row, a.ldown, cm, kv);
-   mha16_own_row<ELT>(a.own2, row, a.ldown2, cm, vv);
+   attn16_own_row<ELT>(a.own, row, a.ldown, cm.col, cm.ok, kv);
+   attn16_own_row<ELT>(a.own2, row, a.ldown2, cm.col, cm.ok, vv);
 
    float dk[8], dv[8];
 #pragma unroll
@@ -392,29 +296,29 @@ __global__ __launch_bounds__(WAVES * 64) void mha16_bw_cols_kernel(const Mha16Ar
 #pragma unroll
          for (int u = 0; u < U; u++) {
             const int id = __shfl(id_l, (s0 + u * G + g) & 63);
-            qg[u] = mha16_load_wide(rsq, mha16_off(id, ldqb), cm);
-            gg[u] = mha16_load_wide(rsg, mha16_off(id, ldgb), cm);
-            ls[u] = mha16_load_head(rs1, mha16_off(id, hb), cm);
-            dd[u] = mha16_load_head(rs2, mha16_off(id, hb), cm);
+            qg[u] = attn16_load_wide(rsq, attn16_off(id, ldqb), cm);
+            gg[u] = attn16_load_wide(rsg, attn16_off(id, ldgb), cm);
+            ls[u] = attn16_load_head(rs1, attn16_off(id, hb), cm);
+            dd[u] = attn16_load_head(rs2, attn16_off(id, hb), cm);
          }
          float part[2 * U];
 #pragma unroll
          for (int u = 0; u < U; u++) {
             float q8[8], g8[8];
-            mha16_widen<ELT>(qg[u], cm, q8);
-            mha16_widen<ELT>(gg[u], cm, g8);
-            part[u] = mha16_dot_part(q8, kv);             // the products commute bit for bit: the rows kernel's score
-            part[U + u] = mha16_dot_part(g8, vv);
+            attn16_widen<ELT>(qg[u], cm.ok, q8);
+            attn16_widen<ELT>(gg[u], cm.ok, g8);
+            part[u] = attn16_dot_part(q8, kv);             // the products commute bit for bit: the rows kernel's score
+            part[U + u] = attn16_dot_part(g8, vv);
          }
-         mha16_head_sum<LPR, 2 * U>(part, a.hlanes);         // every lane takes part: not under `live`
+         attn16_head_sum<LPR, 2 * U>(part, a.hlanes);         // every lane takes part: not under `live`
 #pragma unroll
          for (int u = 0; u < U; u++) {
             const bool live = s0 + u * G + g < cnt;
             const float ae = live ? __expf(part[u] * a.p - ls[u]) : 0.0f;
             const float ds = live ? ae * (part[U + u] - dd[u]) : 0.0f;
             float q8[8], g8[8];
-            mha16_widen<ELT>(qg[u], cm, q8);
-            mha16_widen<ELT>(gg[u], cm, g8);
+            attn16_widen<ELT>(qg[u], cm.ok, q8);
+            attn16_widen<ELT>(gg[u], cm.ok, g8);
 #pragma unroll
             for (int v = 0; v < 8; v++) {
                dk[v] = fmaf(ds, q8[v], dk[v]);
@@ -433,8 +337,8 @@ __global__ __launch_bounds__(WAVES * 64) void mha16_bw_cols_kernel(const Mha16Ar
    if (g != 0) return;
 #pragma unroll
    for (int v = 0; v < 8; v++) dk[v] *= a.p;          // no incoming entry: 0
-   mha16_store_row<ELT>(a.out, row, a.ldout, cm, dk);
-   mha16_store_row<ELT>(a.out2, row, a.ldout2, cm, dv);
+   attn16_store_row<ELT>(a.out, row, a.ldout, cm.col, cm.ok, dk);
+   attn16_store_row<ELT>(a.out2, row, a.ldout2, cm.col, cm.ok, dv);
 }
 
 enum { MHA16_FW = 0, MHA16_BW_ROWS = 1, MHA16_BW_COLS = 2 };
@@ -450,49 +354,17 @@ static int launch_mha16(int which, const Mha16Args &a, const char *entry, hipStr
    return check_launch(entry);
 }
 
-// the slot width by ceil(k / 8) 16-byte vectors per row, always one chunk per lane
-template <int ELT>
-static int mha16_by_width(int which, const Mha16Args &a, const char *entry, hipStream_t st) {
-   const int64_t w = (a.k + 7) / 8;
-   if (w <= 4) return launch_mha16<ELT, 4>(which, a, entry, st);
-   if (w <= 8) return launch_mha16<ELT, 8>(which, a, entry, st);
-   if (w <= 16) return launch_mha16<ELT, 16>(which, a, entry, st);
-   if (w <= 32) return launch_mha16<ELT, 32>(which, a, entry, st);
-   return launch_mha16<ELT, 64>(which, a, entry, st);
-}
-
+// the element type and the slot width (attn16_run)
 static int mha16_run(int dtype, int which, const Mha16Args &a, const char *entry, void *stream) {
-   return dtype == ISPLIB_DTYPE_BF16 ? mha16_by_width<ELT_BF16>(which, a, entry, (hipStream_t)stream)
-                                     : mha16_by_width<ELT_F16>(which, a, entry, (hipStream_t)stream);
+   return attn16_run(dtype, a.k, [&](auto elt, auto lpr) {
+      return launch_mha16<decltype(elt)::value, decltype(lpr)::value>(which, a, entry, (hipStream_t)stream);
+   });
 }
 
-// what a descriptor over `rows` rows of k elements of `size` bytes at pitch ld may answer: the extent a row-strided view owns
-static unsigned mha16_extent(int64_t rows, int64_t k, int64_t ld, unsigned size) {
-   return rows <= 0 ? 0u : (unsigned)(((unsigned long long)(rows - 1) * (unsigned long long)ld + (unsigned long long)k) * size);
-}
-
-// the head geometry of a launch; the domain (isplib_qkv16_serves) has been checked: H == 1, or d a power of two >= 8
-static void mha16_heads(Mha16Args &a, int64_t heads, int64_t d) {
-   a.heads = (int)heads;
-   if (heads == 1) {
-      a.hshift = 31; a.hlanes = 64; a.hmask = 0x7fffffffu;
-   } else {
-      int sh = 0;
-      while ((1LL << sh) < d) sh++;
-      a.hshift = sh; a.hlanes = (int)(d / 8); a.hmask = (unsigned)(d - 1);
-   }
-}
-
-static const char *const MHA16_DTYPE = "dtype must be ISPLIB_DTYPE_BF16 or ISPLIB_DTYPE_F16";
 static const char *const MHA16_DOMAIN = "outside isplib_qkv16_serves(rows_gathered, heads, d, ld) = isplib_gat16_serves: 1 <= heads, "
                                         "8 <= heads*d <= 512, heads == 1 with d even or d a power of two >= 8, every pitch even, "
                                         "ld >= heads*d, rows_gathered < 2^31, rows_gathered*ld*2 <= 3.5 GiB (convert the operands and "
                                         "use the fp32 entries)";
-
-static bool mha16_even(int64_t a, int64_t b, int64_t c = 0, int64_t d = 0) { return ((a | b | c | d) & 1) == 0; }
-static bool mha16_aligned(const void *a, const void *b, const void *c, const void *d, const void *e = nullptr, const void *f = nullptr) {
-   return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d | (uintptr_t)e | (uintptr_t)f) & 3) == 0;
-}
 
 }  // namespace isplib
 
@@ -511,24 +383,24 @@ extern "C" int isplib_qkv16_csr_hip(int dtype, int64_t m, int64_t n, int64_t k, 
                                     int64_t ldk, const void *v, int64_t ldv, void *z, int64_t ldz, float *lse, void *stream) {
    const char *entry = "isplib_qkv16_csr_hip";
    clear_error();
-   if (dtype != ISPLIB_DTYPE_BF16 && dtype != ISPLIB_DTYPE_F16) return fail(ISPLIB_FAIL, entry, MHA16_DTYPE);
+   if (dtype != ISPLIB_DTYPE_BF16 && dtype != ISPLIB_DTYPE_F16) return fail(ISPLIB_FAIL, entry, ATTN16_DTYPE);
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
    if (m == 0 || k == 0) return ISPLIB_SUCCESS;
    if (ldq < k || ldz < k) return fail(ISPLIB_FAIL, entry, "leading dimension smaller than k");
    if (heads >= 1 && k % heads != 0) return fail(ISPLIB_FAIL, entry, "k is not a multiple of heads");
    if (!std::isfinite(scale)) return fail(ISPLIB_FAIL, entry, "scale must be a finite number");
    if (heads < 1 || !isplib_qkv16_serves(n, heads, k / heads, ldk) || !isplib_qkv16_serves(n, heads, k / heads, ldv) ||
-       !mha16_even(ldq, ldz))
+       !attn16_even(ldq, ldz))
       return fail(ISPLIB_NO_OPT_IMPL, entry, MHA16_DOMAIN);
    if (!pntrb || !pntre || !q || !z || !lse || (nnz > 0 && (!indx || !key || !v))) return fail(ISPLIB_FAIL, entry, "null operand");
-   if (!mha16_aligned(q, key, v, z)) return fail(ISPLIB_FAIL, entry, "q, key, v and z must be 4-byte aligned");
+   if (!attn16_aligned(q, key, v, z)) return fail(ISPLIB_FAIL, entry, "q, key, v and z must be 4-byte aligned");
    Mha16Args a = {};
    a.rows = m; a.k = k; a.indx = indx; a.pntrb = pntrb; a.pntre = pntre; a.p = scale;
-   mha16_heads(a, heads, k / heads);
+   attn16_head_geometry(heads, k / heads, a.heads, a.hshift, a.hlanes, a.hmask);
    a.own = reinterpret_cast<const unsigned short *>(q); a.ldown = ldq;
    a.out = reinterpret_cast<unsigned short *>(z); a.ldout = ldz; a.hout = lse;
-   a.ga = key; a.ldga = ldk; a.gabytes = nnz > 0 ? mha16_extent(n, k, ldk, 2u) : 0u;
-   a.gb = v; a.ldgb = ldv; a.gbbytes = nnz > 0 ? mha16_extent(n, k, ldv, 2u) : 0u;
+   a.ga = key; a.ldga = ldk; a.gabytes = nnz > 0 ? attn16_extent(n, k, ldk, 2u) : 0u;
+   a.gb = v; a.ldgb = ldv; a.gbbytes = nnz > 0 ? attn16_extent(n, k, ldv, 2u) : 0u;
    return mha16_run(dtype, MHA16_FW, a, entry, stream);
 }
 
@@ -538,26 +410,26 @@ extern "C" int isplib_qkv16_bw_rows_hip(int dtype, int64_t m, int64_t n, int64_t
                                         int64_t lddq, float *dsum, void *stream) {
    const char *entry = "isplib_qkv16_bw_rows_hip";
    clear_error();
-   if (dtype != ISPLIB_DTYPE_BF16 && dtype != ISPLIB_DTYPE_F16) return fail(ISPLIB_FAIL, entry, MHA16_DTYPE);
+   if (dtype != ISPLIB_DTYPE_BF16 && dtype != ISPLIB_DTYPE_F16) return fail(ISPLIB_FAIL, entry, ATTN16_DTYPE);
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
    if (m == 0 || k == 0) return ISPLIB_SUCCESS;
    if (ldq < k || ldg < k || lddq < k) return fail(ISPLIB_FAIL, entry, "leading dimension smaller than k");
    if (heads >= 1 && k % heads != 0) return fail(ISPLIB_FAIL, entry, "k is not a multiple of heads");
    if (!std::isfinite(scale)) return fail(ISPLIB_FAIL, entry, "scale must be a finite number");
    if (heads < 1 || !isplib_qkv16_serves(n, heads, k / heads, ldk) || !isplib_qkv16_serves(n, heads, k / heads, ldv) ||
-       !mha16_even(ldq, ldg, lddq))
+       !attn16_even(ldq, ldg, lddq))
       return fail(ISPLIB_NO_OPT_IMPL, entry, MHA16_DOMAIN);
    if (!pntrb || !pntre || !q || !g || !lse || !dq || !dsum || (nnz > 0 && (!indx || !key || !v)))
       return fail(ISPLIB_FAIL, entry, "null operand");
-   if (!mha16_aligned(q, key, v, g, dq)) return fail(ISPLIB_FAIL, entry, "q, key, v, g and dq must be 4-byte aligned");
+   if (!attn16_aligned(q, key, v, g, dq)) return fail(ISPLIB_FAIL, entry, "q, key, v, g and dq must be 4-byte aligned");
    Mha16Args a = {};
    a.rows = m; a.k = k; a.indx = indx; a.pntrb = pntrb; a.pntre = pntre; a.p = scale;
-   mha16_heads(a, heads, k / heads);
+   attn16_head_geometry(heads, k / heads, a.heads, a.hshift, a.hlanes, a.hmask);
    a.own = reinterpret_cast<const unsigned short *>(q); a.ldown = ldq;
    a.g = reinterpret_cast<const unsigned short *>(g); a.ldg = ldg; a.lse_in = lse;
    a.out = reinterpret_cast<unsigned short *>(dq); a.ldout = lddq; a.hout = dsum;
-   a.ga = key; a.ldga = ldk; a.gabytes = nnz > 0 ? mha16_extent(n, k, ldk, 2u) : 0u;
-   a.gb = v; a.ldgb = ldv; a.gbbytes = nnz > 0 ? mha16_extent(n, k, ldv, 2u) : 0u;
+   a.ga = key; a.ldga = ldk; a.gabytes = nnz > 0 ? attn16_extent(n, k, ldk, 2u) : 0u;
+   a.gb = v; a.ldgb = ldv; a.gbbytes = nnz > 0 ? attn16_extent(n, k, ldv, 2u) : 0u;
    return mha16_run(dtype, MHA16_BW_ROWS, a, entry, stream);
 }
 
@@ -567,27 +439,27 @@ extern "C" int isplib_qkv16_bw_cols_hip(int dtype, int64_t m, int64_t n, int64_t
                                         int64_t ldv, void *dkey, int64_t lddk, void *dv, int64_t lddv, void *stream) {
    const char *entry = "isplib_qkv16_bw_cols_hip";
    clear_error();
-   if (dtype != ISPLIB_DTYPE_BF16 && dtype != ISPLIB_DTYPE_F16) return fail(ISPLIB_FAIL, entry, MHA16_DTYPE);
+   if (dtype != ISPLIB_DTYPE_BF16 && dtype != ISPLIB_DTYPE_F16) return fail(ISPLIB_FAIL, entry, ATTN16_DTYPE);
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
    if (n == 0 || k == 0) return ISPLIB_SUCCESS;
    if (ldk < k || ldv < k || lddk < k || lddv < k) return fail(ISPLIB_FAIL, entry, "leading dimension smaller than k");
    if (heads >= 1 && k % heads != 0) return fail(ISPLIB_FAIL, entry, "k is not a multiple of heads");
    if (!std::isfinite(scale)) return fail(ISPLIB_FAIL, entry, "scale must be a finite number");
    if (heads < 1 || !isplib_qkv16_serves(m, heads, k / heads, ldq) || !isplib_qkv16_serves(m, heads, k / heads, ldg) ||
-       !mha16_even(ldk, ldv, lddk, lddv))
+       !attn16_even(ldk, ldv, lddk, lddv))
       return fail(ISPLIB_NO_OPT_IMPL, entry, MHA16_DOMAIN);
    if (!colb || !cole || !key || !v || !dkey || !dv || (nnz > 0 && (!row_t || !q || !g || !lse || !dsum)))
       return fail(ISPLIB_FAIL, entry, "null operand");
-   if (!mha16_aligned(q, g, key, v, dkey, dv)) return fail(ISPLIB_FAIL, entry, "q, g, key, v, dkey and dv must be 4-byte aligned");
+   if (!attn16_aligned(q, g, key, v, dkey, dv)) return fail(ISPLIB_FAIL, entry, "q, g, key, v, dkey and dv must be 4-byte aligned");
    Mha16Args a = {};
    a.rows = n; a.k = k; a.indx = row_t; a.pntrb = colb; a.pntre = cole; a.p = scale;
-   mha16_heads(a, heads, k / heads);
+   attn16_head_geometry(heads, k / heads, a.heads, a.hshift, a.hlanes, a.hmask);
    a.own = reinterpret_cast<const unsigned short *>(key); a.ldown = ldk;
    a.own2 = reinterpret_cast<const unsigned short *>(v); a.ldown2 = ldv;
    a.out = reinterpret_cast<unsigned short *>(dkey); a.ldout = lddk;
    a.out2 = reinterpret_cast<unsigned short *>(dv); a.ldout2 = lddv;
-   a.ga = q; a.ldga = ldq; a.gabytes = nnz > 0 ? mha16_extent(m, k, ldq, 2u) : 0u;
-   a.gb = g; a.ldgb = ldg; a.gbbytes = nnz > 0 ? mha16_extent(m, k, ldg, 2u) : 0u;
-   a.t1 = lse; a.t2 = dsum; a.tbytes = nnz > 0 ? mha16_extent(m, heads, heads, 4u) : 0u;
+   a.ga = q; a.ldga = ldq; a.gabytes = nnz > 0 ? attn16_extent(m, k, ldq, 2u) : 0u;
+   a.gb = g; a.ldgb = ldg; a.gbbytes = nnz > 0 ? attn16_extent(m, k, ldg, 2u) : 0u;
+   a.t1 = lse; a.t2 = dsum; a.tbytes = nnz > 0 ? attn16_extent(m, heads, heads, 4u) : 0u;
    return mha16_run(dtype, MHA16_BW_COLS, a, entry, stream);
 }
