@@ -1410,6 +1410,10 @@ void isplib_graph_destroy(isplib_graph *g);
  * the entries it extends */
 #include "isplib_hip_mha_drop.h"
 
+/* the same attention with attention dropout for bf16 / fp16 operands (isplib_qkv_half_drop_*): part of this interface, declared in a
+ * file of its own */
+#include "isplib_hip_mha16_drop.h"
+
 /* the same attention for bf16 / fp16 operands (isplib_qkv16_*): part of this interface, declared in a file of its own */
 #include "isplib_hip_mha16.h"
 

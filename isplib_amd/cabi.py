@@ -230,6 +230,15 @@ def mha16_native_pays(rows_gathered: int, ld: int) -> bool:
     return bool(rows_gathered > 0 and ld > 0)
 
 
+def mha16_drop_native_pays(rows_gathered: int, ld: int) -> bool:
+    """isplib_qkv_half_drop_native_pays of include/isplib_hip_mha16_drop.h: the classes of calls (the gathered operand beyond 256 MiB
+    at 2 bytes per element or not) in which every native run of the 16-bit multi-head attention operator WITH dropout (forward +
+    backward through mha_matmul) measured faster than every run of the conversion route (profiles/mha16_dropout_ab.txt: both classes
+    do -- the Reddit shape at (H, d) = (8, 8) / (8, 16) inside 256 MiB, 0.562-0.564 of the conversion route's time; the ogbn-products
+    shape at (8, 16) beyond it, 0.494); tests/test_mha16_dropout_host.py compares the two."""
+    return bool(rows_gathered > 0 and ld > 0)
+
+
 def owner_exchange_serves(m: int, k: int, world: int, cuts) -> bool:
     """isplib_owner_exchange_serves of the header: m x k winners split for `world` owners at the row boundaries `cuts`."""
     if not 1 <= world <= OWNER_WORLD_MAX or m < 0 or k < 0 or m * k >= MINMAX_BW_PAIRS_END:
@@ -312,6 +321,12 @@ MHA_EXPORTS = ("isplib_mha_csr_hip", "isplib_mha_bw_rows_hip", "isplib_mha_bw_co
 # dropout.  Their prefix is isplib_qkv_drop_ because the symbols that start with isplib_mha and isplib_qkv16 are pinned to the two lists
 # around this one; tests/test_mha_dropout_host.py compares this list with the header and the library
 MHA_DROP_EXPORTS = ("isplib_qkv_drop_csr_hip", "isplib_qkv_drop_bw_rows_hip", "isplib_qkv_drop_bw_cols_hip")
+
+# include/isplib_hip_mha16_drop.h (which isplib_hip.h includes; the same library): the 16-bit multi-head attention entries with attention
+# dropout.  Their prefix is isplib_qkv_half_drop_ because the symbols that start with isplib_mha, isplib_qkv16 and isplib_qkv_drop are
+# pinned to the three lists above; tests/test_mha16_dropout_host.py compares this list with the header and the library
+MHA16_DROP_EXPORTS = ("isplib_qkv_half_drop_csr_hip", "isplib_qkv_half_drop_bw_rows_hip", "isplib_qkv_half_drop_bw_cols_hip",
+                      "isplib_qkv_half_drop_auto")
 
 MHA16_EXPORTS = ("isplib_qkv16_csr_hip", "isplib_qkv16_bw_rows_hip", "isplib_qkv16_bw_cols_hip", "isplib_qkv16_domain", "isplib_qkv16_auto")
 
@@ -658,6 +673,16 @@ def lib() -> ctypes.CDLL:
                                                _vp, _i64, _vp, _vp, _i64, _vp, _vp]
         L.isplib_qkv16_bw_cols_hip.restype = ctypes.c_int
         L.isplib_qkv16_bw_cols_hip.argtypes = [ctypes.c_int] + L.isplib_mha_bw_cols_hip.argtypes
+        # the isplib_qkv16_* argument lists (the columns entry with csr2csc after cole), then threshold, keep_scale, seed
+        L.isplib_qkv_half_drop_auto.restype = ctypes.c_int
+        L.isplib_qkv_half_drop_auto.argtypes = [_i64, _i64]
+        L.isplib_qkv_half_drop_csr_hip.restype = ctypes.c_int
+        L.isplib_qkv_half_drop_csr_hip.argtypes = L.isplib_qkv16_csr_hip.argtypes + _drop
+        L.isplib_qkv_half_drop_bw_rows_hip.restype = ctypes.c_int
+        L.isplib_qkv_half_drop_bw_rows_hip.argtypes = L.isplib_qkv16_bw_rows_hip.argtypes + _drop
+        L.isplib_qkv_half_drop_bw_cols_hip.restype = ctypes.c_int
+        L.isplib_qkv_half_drop_bw_cols_hip.argtypes = (L.isplib_qkv16_bw_cols_hip.argtypes[:8] + [_vp] + L.isplib_qkv16_bw_cols_hip.argtypes[8:] +
+                                                       _drop)
         L.isplib_gatv2_16_domain.restype = ctypes.c_int
         L.isplib_gatv2_16_domain.argtypes = [_i64, _i64, _i64, _i64]
         L.isplib_gatv2_16_auto.restype = ctypes.c_int
@@ -3391,6 +3416,19 @@ def mha16_forward(rowptr, col, q, k, v, heads: int = 1, scale: Optional[float] =
     product, sum and exponential is fp32, z is rounded once to the operands' dtype.  Returns (z [m, heads * d] 16-bit, lse [m, heads]
     fp32); `out` = (z, lse); `scale` None: 1 / sqrt(d).  The operand checks are mha's, with the 16-bit family's (even pitches, 4-byte
     aligned bases)."""
+    return _mha16_forward(rowptr, col, q, k, v, heads, scale, out, check, None)
+
+
+def mha16_drop_forward(rowptr, col, q, k, v, threshold: int, keep_scale: float, seed: int, heads: int = 1, scale: Optional[float] = None,
+                       *, out=None, check: bool = True):
+    """`mha16_forward` with attention dropout (isplib_qkv_half_drop_csr_hip): the keep bit and the keep scale of `mha_drop`, the 16-bit
+    family's contract -- the finished row times `keep_scale`, then the one rounding; lse is that of the call without dropout.  Returns
+    (z 16-bit, lse fp32); the operand checks are mha16_forward's, and nnz < 2^31."""
+    return _mha16_forward(rowptr, col, q, k, v, heads, scale, out, check, _mha_drop_args(threshold, keep_scale, seed))
+
+
+def _mha16_forward(rowptr, col, q, k, v, heads, scale, out, check, drop):
+    """`mha16_forward` (drop None) and `mha16_drop_forward` (drop = (threshold, keep_scale, seed), checked)."""
     if not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1 or rowptr.numel() < 1:
         raise ValueError("isplib_amd: `rowptr` (m + 1 entries) must be a 1-D tensor")
     m = rowptr.numel() - 1
@@ -3398,6 +3436,8 @@ def mha16_forward(rowptr, col, q, k, v, heads: int = 1, scale: Optional[float] =
     d = _gat_heads(heads, kk)
     p = _mha_scale(scale, d)
     rowptr, col = _attn_structure(rowptr, col, "rowptr", "col", n, check)
+    if drop is not None:
+        _gatv2_nnz(col.numel())
     if out is not None:
         z, lse = out
         ldz = _attn16_dense(z, "out[0]", m, kk, "z", q.dtype)
@@ -3414,10 +3454,12 @@ def mha16_forward(rowptr, col, q, k, v, heads: int = 1, scale: Optional[float] =
             lse.fill_(float("-inf"))
         return z, lse
     rp = rowptr.data_ptr()
+    entry = "isplib_qkv16_csr_hip" if drop is None else "isplib_qkv_half_drop_csr_hip"
     with torch.cuda.device(q.device):
-        st = lib().isplib_qkv16_csr_hip(HALF_DTYPES[q.dtype], m, n, kk, col.numel(), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8),
-                                        heads, p, _ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(z), ldz, _ptr(lse), _stream(q.device))
-    _check(st, "isplib_qkv16_csr_hip")
+        st = getattr(lib(), entry)(HALF_DTYPES[q.dtype], m, n, kk, col.numel(), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8),
+                                   heads, p, _ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(z), ldz, _ptr(lse), _stream(q.device),
+                                   *(drop or ()))
+    _check(st, entry)
     return z, lse
 
 
@@ -3426,6 +3468,19 @@ def mha16_backward_rows(rowptr, col, q, k, v, g, lse, heads: int = 1, scale: Opt
     forward's lse -- z is NOT read: D[i,h] = sum_e a_e <g_i, v_j>_h is formed in fp32 from the row's edges, in the same pass as
     dq_ic = scale (P_c - D Q_c).  Returns (dq [m, heads * d] 16-bit, D [m, heads] fp32); an empty row has dq_i = 0 and D = 0.
     `out` = (dq, D)."""
+    return _mha16_backward_rows(rowptr, col, q, k, v, g, lse, heads, scale, out, check, None)
+
+
+def mha16_drop_backward_rows(rowptr, col, q, k, v, g, lse, threshold: int, keep_scale: float, seed: int, heads: int = 1,
+                             scale: Optional[float] = None, *, out=None, check: bool = True):
+    """The backward of `mha16_drop_forward` over the rows (isplib_qkv_half_drop_bw_rows_hip), with the mask of the same (threshold,
+    seed): t_e = q_e keep_scale <g_i, v_j>_h, D = sum_e a_e t_e from the row's edges (z is not read), everything else as
+    `mha16_backward_rows`.  Returns (dq 16-bit, D fp32)."""
+    return _mha16_backward_rows(rowptr, col, q, k, v, g, lse, heads, scale, out, check, _mha_drop_args(threshold, keep_scale, seed))
+
+
+def _mha16_backward_rows(rowptr, col, q, k, v, g, lse, heads, scale, out, check, drop):
+    """`mha16_backward_rows` (drop None) and `mha16_drop_backward_rows` (drop = (threshold, keep_scale, seed), checked)."""
     if not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1 or rowptr.numel() < 1:
         raise ValueError("isplib_amd: `rowptr` (m + 1 entries) must be a 1-D tensor")
     m = rowptr.numel() - 1
@@ -3435,6 +3490,8 @@ def mha16_backward_rows(rowptr, col, q, k, v, g, lse, heads: int = 1, scale: Opt
     ldg = _attn16_dense(g, "g", m, kk, "the gradient of z", q.dtype)
     _gat_table(lse, "lse", m, heads)
     rowptr, col = _attn_structure(rowptr, col, "rowptr", "col", n, check)
+    if drop is not None:
+        _gatv2_nnz(col.numel())
     if out is not None:
         if len(out) != 2:
             raise ValueError("isplib_amd: `out` must be (dq, D)")
@@ -3452,11 +3509,12 @@ def mha16_backward_rows(rowptr, col, q, k, v, g, lse, heads: int = 1, scale: Opt
             dsum.zero_()
         return dq, dsum
     rp = rowptr.data_ptr()
+    entry = "isplib_qkv16_bw_rows_hip" if drop is None else "isplib_qkv_half_drop_bw_rows_hip"
     with torch.cuda.device(q.device):
-        st = lib().isplib_qkv16_bw_rows_hip(HALF_DTYPES[q.dtype], m, n, kk, col.numel(), _ptr(col), ctypes.c_void_p(rp),
-                                            ctypes.c_void_p(rp + 8), heads, p, _ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(g), ldg,
-                                            _ptr(lse), _ptr(dq), lddq, _ptr(dsum), _stream(q.device))
-    _check(st, "isplib_qkv16_bw_rows_hip")
+        st = getattr(lib(), entry)(HALF_DTYPES[q.dtype], m, n, kk, col.numel(), _ptr(col), ctypes.c_void_p(rp), ctypes.c_void_p(rp + 8),
+                                   heads, p, _ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(g), ldg, _ptr(lse), _ptr(dq), lddq,
+                                   _ptr(dsum), _stream(q.device), *(drop or ()))
+    _check(st, entry)
     return dq, dsum
 
 
@@ -3466,6 +3524,21 @@ def mha16_backward_cols(colptr, row_t, q, k, v, g, lse, dsum, heads: int = 1, sc
     sum over the entries e = (i, j) of column j of ds_e q_i[head h] and dv_j[head h] = sum of a_e g_i[head h], each rounded once to the
     operands' dtype, with `lse` of the forward and `dsum` = D of mha16_backward_rows.  Returns (dk, dv), both [n, heads * d] 16-bit; a
     column no entry points at has 0 in both.  `out` = (dk, dv)."""
+    return _mha16_backward_cols(colptr, row_t, None, q, k, v, g, lse, dsum, heads, scale, out, check, None)
+
+
+def mha16_drop_backward_cols(colptr, row_t, csr2csc, q, k, v, g, lse, dsum, threshold: int, keep_scale: float, seed: int, heads: int = 1,
+                             scale: Optional[float] = None, *, out=None, check: bool = True):
+    """The backward of `mha16_drop_forward` over the columns (isplib_qkv_half_drop_bw_cols_hip): dk as `mha16_backward_cols` with t_e
+    under the mask, dv_j[head h] = sum over the entries of column j of q_e keep_scale a_e g_i[head h], each rounded once.  `csr2csc`
+    [nnz] int64 is required: the keep bit is a function of the entry's CSR position.  Returns (dk, dv)."""
+    return _mha16_backward_cols(colptr, row_t, csr2csc, q, k, v, g, lse, dsum, heads, scale, out, check,
+                                _mha_drop_args(threshold, keep_scale, seed))
+
+
+def _mha16_backward_cols(colptr, row_t, csr2csc, q, k, v, g, lse, dsum, heads, scale, out, check, drop):
+    """`mha16_backward_cols` (drop None, no csr2csc) and `mha16_drop_backward_cols` (drop = (threshold, keep_scale, seed), checked;
+    csr2csc required)."""
     if not isinstance(colptr, torch.Tensor) or colptr.dim() != 1 or colptr.numel() < 1:
         raise ValueError("isplib_amd: `colptr` (n + 1 entries) must be a 1-D tensor")
     n = colptr.numel() - 1
@@ -3482,6 +3555,9 @@ def mha16_backward_cols(colptr, row_t, q, k, v, g, lse, dsum, heads: int = 1, sc
     _gat_table(lse, "lse", m, heads)
     _gat_table(dsum, "dsum", m, heads)
     colptr, row_t = _attn_structure(colptr, row_t, "colptr", "row_t", m, check)
+    if drop is not None:
+        _gatv2_nnz(row_t.numel())
+        csr2csc = _gat_edge_positions(csr2csc, row_t.numel(), check)
     if out is not None:
         if len(out) != 2:
             raise ValueError("isplib_amd: `out` must be (dk, dv)")
@@ -3489,7 +3565,7 @@ def mha16_backward_cols(colptr, row_t, q, k, v, g, lse, dsum, heads: int = 1, sc
         lddv = _attn16_dense(out[1], "out[1]", n, kk, "dv", k.dtype)
     _mha16_domain(m, heads, d, (ldq, ldg))
     _same_gpu((("q", q), ("k", k), ("v", v), ("g", g), ("lse", lse), ("dsum", dsum), ("colptr", colptr), ("row_t", row_t)) +
-              ((("out[0]", out[0]), ("out[1]", out[1])) if out is not None else ()))
+              ((("out[0]", out[0]), ("out[1]", out[1])) if out is not None else ()) + ((("csr2csc", csr2csc),) if drop is not None else ()))
     if out is None:
         out = (torch.empty((n, kk), dtype=k.dtype, device=k.device), torch.empty((n, kk), dtype=k.dtype, device=k.device))
         lddk = lddv = max(kk, 1)
@@ -3497,11 +3573,13 @@ def mha16_backward_cols(colptr, row_t, q, k, v, g, lse, dsum, heads: int = 1, sc
     if n == 0 or kk == 0:
         return dk, dv
     cp = colptr.data_ptr()
+    entry = "isplib_qkv16_bw_cols_hip" if drop is None else "isplib_qkv_half_drop_bw_cols_hip"
     with torch.cuda.device(k.device):
-        st = lib().isplib_qkv16_bw_cols_hip(HALF_DTYPES[k.dtype], m, n, kk, row_t.numel(), _ptr(row_t), ctypes.c_void_p(cp),
-                                            ctypes.c_void_p(cp + 8), heads, p, _ptr(q), ldq, _ptr(g), ldg, _ptr(lse), _ptr(dsum), _ptr(k), ldk,
-                                            _ptr(v), ldv, _ptr(dk), lddk, _ptr(dv), lddv, _stream(k.device))
-    _check(st, "isplib_qkv16_bw_cols_hip")
+        st = getattr(lib(), entry)(HALF_DTYPES[k.dtype], m, n, kk, row_t.numel(), _ptr(row_t), ctypes.c_void_p(cp), ctypes.c_void_p(cp + 8),
+                                   *((_ptr(csr2csc),) if drop is not None else ()), heads, p, _ptr(q), ldq, _ptr(g), ldg, _ptr(lse),
+                                   _ptr(dsum), _ptr(k), ldk, _ptr(v), ldv, _ptr(dk), lddk, _ptr(dv), lddv, _stream(k.device),
+                                   *(drop or ()))
+    _check(st, entry)
     return dk, dv
 
 

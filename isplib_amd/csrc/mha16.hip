@@ -36,12 +36,28 @@
 // q_i and g_i (16 bytes each) and lse, D of [i, head] (4 bytes each, two tables, each behind its own descriptor), and writes dkey and
 // dv, each rounded once, each at its own pitch.  The column map, the descriptor, the gathers, the widening and the butterfly are those
 // of attn16_common.h, shared with gat16.hip and gatv2_16.hip.  DESIGN.md 4.6l, 4.6n.
+//
+// Attention dropout (include/isplib_hip_mha16_drop.h: isplib_qkv_half_drop_*_hip): the three kernels are templates on
+// DROP, with the mathematics of mha.hip's DROP kernels under this family's contract.  Every stored entry e and head h has the keep bit
+// q_e,h = word(seed, CSR position of e, h) >= T of gat_dropout.h, a pure function recomputed in all three kernels, and with
+// c = float32(1 / (1 - p)):
+//    z_i = c sum_e q_e a_e v_j      t_e = q_e c <g_i, v_j>_h      dv_j = sum_{e -> j} q_e c a_e g_i
+//    a_e, lse, s_e and the form of ds_e unchanged
+// m, l and lse do not see the mask; the value accumulation takes q_e ? w : 0 and the finished row is (acc / l) * c, then the one
+// rounding.  The rows kernel stays one pass and does not read z: t_e takes the mask after the butterfly, Dacc = sum a_e t_e and
+// P_c = sum a_e t_e key_jc carry it, l and Q_c = sum a_e key_jc do not, so a dropped edge still gives -a_e D.  A lane's eight columns
+// lie in ONE head: the head's part of the word is a single per-lane constant.  The lane that loads an entry's index hashes the entry's
+// position (base + lane in the forward and the rows kernel; csr2csc[pos] in the columns kernel) and hands the word across with the
+// index, by the same __shfl and slot; per edge one add, one fmix32, one compare and one select remain.  T = 0 and c = 1 give the bits
+// of DROP = false, and DROP = false is the code it was (profiles/mha16_dropout_isa.txt).
 #include <cfloat>
 #include <cmath>
 
 #include "common.h"
 #include "gather.h"
 #include "half16.h"
+#include "gat_dropout.h"
+#include "attn_common.h"          // AttnDrop, attn_drop_refusal, attn_set_drop
 #include "attn16_common.h"
 
 // edges per slot and step, per kernel: measured among {2, 4}; an experiment build may override them (make EXTRA=-D...)
@@ -95,8 +111,21 @@ struct Mha16Args {
    unsigned tbytes;
 };
 
-template <int ELT, int LPR, int WAVES, int U>
-__global__ __launch_bounds__(WAVES * 64) void mha16_fw_kernel(const Mha16Args a) {
+// DROP only: the dropout fields, appended to the end of Mha16Args.  They are appended by derivation, not written into Mha16Args itself:
+// the kernels without dropout take Mha16Args as it was, because a kernel argument beyond 240 bytes (232 + these 24) changes the
+// compiler's register allocation and block layout in 16 of the 30 kernels that were there (profiles/mha16_dropout_isa.txt), whatever
+// the kernels do with the new bytes.  The host fills one Mha16DropArgs per call; a launch without dropout passes its Mha16Args part.
+struct Mha16DropArgs : Mha16Args {
+   unsigned seed_lo, seed_hi;                // the two halves of the seed
+   unsigned T;                               // keep: word >= T
+   float c;                                  // float32(1 / (1 - p))
+   const int64_t *epos;                      // columns: csr2csc [nnz], the CSR position of every entry of the transposed structure
+};
+template <bool DROP> struct Mha16KernelArgs { using type = Mha16Args; };
+template <> struct Mha16KernelArgs<true> { using type = Mha16DropArgs; };
+
+template <int ELT, int LPR, int WAVES, int U, bool DROP>
+__global__ __launch_bounds__(WAVES * 64) void mha16_fw_kernel(const typename Mha16KernelArgs<DROP>::type a) {
    constexpr int G = 64 / LPR;
    const int lane = threadIdx.x & 63;
    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -108,6 +137,8 @@ __global__ __launch_bounds__(WAVES * 64) void mha16_fw_kernel(const Mha16Args a)
    const Attn16HeadCols cm(a.k, a.hshift, a.hmask, lc);
    float qv[8];
    attn16_own_row<ELT>(a.own, row, a.ldown, cm.col, cm.ok, qv);
+   [[maybe_unused]] unsigned hk = 0u;                   // DROP: the head's part of the word, one constant per lane
+   if constexpr (DROP) hk = gat_drop_head(a.seed_hi, (unsigned)cm.head);
 
    float mrun = MHA16_NONE, l = 0.0f, acc[8];
 #pragma unroll
@@ -117,16 +148,20 @@ __global__ __launch_bounds__(WAVES * 64) void mha16_fw_kernel(const Mha16Args a)
    for (int64_t base = eb; base < ee; base += 64) {
       const int64_t pos = base + lane;
       const int id_l = pos < ee ? (int)a.indx[pos] : -1;
+      [[maybe_unused]] unsigned hw_l = 0u;               // DROP: the entry's part of the word, handed across lanes like the column id
+      if constexpr (DROP) hw_l = gat_drop_entry(a.seed_lo, (unsigned)pos);
       const int64_t left = ee - base;
       const int cnt = left < 64 ? (int)left : 64;
 #pragma unroll 1
       for (int s0 = 0; s0 < cnt; s0 += G * U) {
          v4i_t kv[U], vv[U];
+         [[maybe_unused]] unsigned hw[DROP ? U : 1];
 #pragma unroll
          for (int u = 0; u < U; u++) {
             const int id = __shfl(id_l, (s0 + u * G + g) & 63);
             kv[u] = attn16_load_wide(rsk, attn16_off(id, ldkb), cm);
             vv[u] = attn16_load_wide(rsv, attn16_off(id, ldvb), cm);
+            if constexpr (DROP) hw[u] = (unsigned)__shfl((int)hw_l, (s0 + u * G + g) & 63);
          }
          float sc[U];
 #pragma unroll
@@ -152,9 +187,11 @@ __global__ __launch_bounds__(WAVES * 64) void mha16_fw_kernel(const Mha16Args a)
             const float w = (s0 + u * G + g < cnt) ? __expf(sc[u] - mnew) : 0.0f;
             float v8[8];
             attn16_widen<ELT>(vv[u], cm.ok, v8);
-            l += w;
+            l += w;                                       // the softmax runs over every stored entry: the mask reaches the values only
+            float wk = w;
+            if constexpr (DROP) wk = gat_drop_mix(hw[u], hk) >= a.T ? w : 0.0f;
 #pragma unroll
-            for (int v = 0; v < 8; v++) acc[v] = fmaf(w, v8[v], acc[v]);
+            for (int v = 0; v < 8; v++) acc[v] = fmaf(wk, v8[v], acc[v]);
          }
       }
    }
@@ -173,14 +210,17 @@ __global__ __launch_bounds__(WAVES * 64) void mha16_fw_kernel(const Mha16Args a)
    const bool empty = ee <= eb;
    float zr[8];
 #pragma unroll
-   for (int v = 0; v < 8; v++) zr[v] = empty ? 0.0f : acc[v] / l;
+   for (int v = 0; v < 8; v++) {
+      zr[v] = empty ? 0.0f : acc[v] / l;
+      if constexpr (DROP) zr[v] *= a.c;
+   }
    attn16_store_row<ELT>(a.out, row, a.ldout, cm.col, cm.ok, zr);
    if (cm.first) a.hout[(size_t)row * (size_t)a.heads + (size_t)cm.head] = empty ? -INFINITY : mrun + logf(l);
 }
 
 // the one-pass backward over the rows: no z, D[i,h] from the row's own edges
-template <int ELT, int LPR, int WAVES, int U>
-__global__ __launch_bounds__(WAVES * 64) void mha16_bw_rows_kernel(const Mha16Args a) {
+template <int ELT, int LPR, int WAVES, int U, bool DROP>
+__global__ __launch_bounds__(WAVES * 64) void mha16_bw_rows_kernel(const typename Mha16KernelArgs<DROP>::type a) {
    constexpr int G = 64 / LPR;
    const int lane = threadIdx.x & 63;
    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -194,6 +234,8 @@ __global__ __launch_bounds__(WAVES * 64) void mha16_bw_rows_kernel(const Mha16Ar
    attn16_own_row<ELT>(a.own, row, a.ldown, cm.col, cm.ok, qv);
    attn16_own_row<ELT>(a.g, row, a.ldg, cm.col, cm.ok, gv);
    const float lse = attn16_own_head(a.lse_in, row, a.heads, cm);
+   [[maybe_unused]] unsigned hk = 0u;                   // DROP: the head's part of the word, one constant per lane
+   if constexpr (DROP) hk = gat_drop_head(a.seed_hi, (unsigned)cm.head);
 
    float l = 0.0f, dacc = 0.0f;                        // per head: sum a_e, sum a_e t_e
    float pc[8], qc[8];                                 // per column: sum a_e t_e key_jc, sum a_e key_jc
@@ -204,16 +246,20 @@ __global__ __launch_bounds__(WAVES * 64) void mha16_bw_rows_kernel(const Mha16Ar
    for (int64_t base = eb; base < ee; base += 64) {
       const int64_t pos = base + lane;
       const int id_l = pos < ee ? (int)a.indx[pos] : -1;
+      [[maybe_unused]] unsigned hw_l = 0u;               // DROP: the entry's part of the word, handed across lanes like the column id
+      if constexpr (DROP) hw_l = gat_drop_entry(a.seed_lo, (unsigned)pos);
       const int64_t left = ee - base;
       const int cnt = left < 64 ? (int)left : 64;
 #pragma unroll 1
       for (int s0 = 0; s0 < cnt; s0 += G * U) {
          v4i_t kv[U], vv[U];
+         [[maybe_unused]] unsigned hw[DROP ? U : 1];
 #pragma unroll
          for (int u = 0; u < U; u++) {
             const int id = __shfl(id_l, (s0 + u * G + g) & 63);
             kv[u] = attn16_load_wide(rsk, attn16_off(id, ldkb), cm);
             vv[u] = attn16_load_wide(rsv, attn16_off(id, ldvb), cm);
+            if constexpr (DROP) hw[u] = (unsigned)__shfl((int)hw_l, (s0 + u * G + g) & 63);
          }
          float part[2 * U];                            // <q_i, key_j>_h and t_e of the step through one butterfly
 #pragma unroll
@@ -228,6 +274,7 @@ __global__ __launch_bounds__(WAVES * 64) void mha16_bw_rows_kernel(const Mha16Ar
 #pragma unroll
          for (int u = 0; u < U; u++) {
             const bool live = s0 + u * G + g < cnt;
+            if constexpr (DROP) part[U + u] *= gat_drop_mix(hw[u], hk) >= a.T ? a.c : 0.0f;      // t_e = q_e c <g_i, v_j>_h
             const float ae = live ? __expf(part[u] * a.p - lse) : 0.0f;
             const float aet = live ? ae * part[U + u] : 0.0f;
             l += ae;
@@ -263,8 +310,8 @@ __global__ __launch_bounds__(WAVES * 64) void mha16_bw_rows_kernel(const Mha16Ar
 }
 
 // one wave per column j of A (a row of the transposed structure): key_j and v_j in registers; q_i, g_i and lse, D of [i, head] gathered
-template <int ELT, int LPR, int WAVES, int U>
-__global__ __launch_bounds__(WAVES * 64) void mha16_bw_cols_kernel(const Mha16Args a) {
+template <int ELT, int LPR, int WAVES, int U, bool DROP>
+__global__ __launch_bounds__(WAVES * 64) void mha16_bw_cols_kernel(const typename Mha16KernelArgs<DROP>::type a) {
    constexpr int G = 64 / LPR;
    const int lane = threadIdx.x & 63;
    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -278,6 +325,8 @@ __global__ __launch_bounds__(WAVES * 64) void mha16_bw_cols_kernel(const Mha16Ar
    float kv[8], vv[8];
    attn16_own_row<ELT>(a.own, row, a.ldown, cm.col, cm.ok, kv);
    attn16_own_row<ELT>(a.own2, row, a.ldown2, cm.col, cm.ok, vv);
+   [[maybe_unused]] unsigned hk = 0u;                   // DROP: the head's part of the word, one constant per lane
+   if constexpr (DROP) hk = gat_drop_head(a.seed_hi, (unsigned)cm.head);
 
    float dk[8], dv[8];
 #pragma unroll
@@ -287,12 +336,15 @@ __global__ __launch_bounds__(WAVES * 64) void mha16_bw_cols_kernel(const Mha16Ar
    for (int64_t base = eb; base < ee; base += 64) {
       const int64_t pos = base + lane;
       const int id_l = pos < ee ? (int)a.indx[pos] : -1;
+      [[maybe_unused]] unsigned hw_l = 0u;               // DROP: the entry's part of the word, of its CSR position (nnz < 2^31)
+      if constexpr (DROP) hw_l = gat_drop_entry(a.seed_lo, pos < ee ? (unsigned)a.epos[pos] : 0u);
       const int64_t left = ee - base;
       const int cnt = left < 64 ? (int)left : 64;
 #pragma unroll 1
       for (int s0 = 0; s0 < cnt; s0 += G * U) {
          v4i_t qg[U], gg[U];
          float ls[U], dd[U];
+         [[maybe_unused]] unsigned hw[DROP ? U : 1];
 #pragma unroll
          for (int u = 0; u < U; u++) {
             const int id = __shfl(id_l, (s0 + u * G + g) & 63);
@@ -300,6 +352,7 @@ __global__ __launch_bounds__(WAVES * 64) void mha16_bw_cols_kernel(const Mha16Ar
             gg[u] = attn16_load_wide(rsg, attn16_off(id, ldgb), cm);
             ls[u] = attn16_load_head(rs1, attn16_off(id, hb), cm);
             dd[u] = attn16_load_head(rs2, attn16_off(id, hb), cm);
+            if constexpr (DROP) hw[u] = (unsigned)__shfl((int)hw_l, (s0 + u * G + g) & 63);
          }
          float part[2 * U];
 #pragma unroll
@@ -315,6 +368,12 @@ __global__ __launch_bounds__(WAVES * 64) void mha16_bw_cols_kernel(const Mha16Ar
          for (int u = 0; u < U; u++) {
             const bool live = s0 + u * G + g < cnt;
             const float ae = live ? __expf(part[u] * a.p - ls[u]) : 0.0f;
+            float aev = ae;                               // the value coefficient: q_e c a_e
+            if constexpr (DROP) {
+               const bool keep = gat_drop_mix(hw[u], hk) >= a.T;
+               part[U + u] *= keep ? a.c : 0.0f;          // t_e = q_e c <g_i, v_j>_h
+               aev = keep ? ae * a.c : 0.0f;
+            }
             const float ds = live ? ae * (part[U + u] - dd[u]) : 0.0f;
             float q8[8], g8[8];
             attn16_widen<ELT>(qg[u], cm.ok, q8);
@@ -322,7 +381,7 @@ __global__ __launch_bounds__(WAVES * 64) void mha16_bw_cols_kernel(const Mha16Ar
 #pragma unroll
             for (int v = 0; v < 8; v++) {
                dk[v] = fmaf(ds, q8[v], dk[v]);
-               dv[v] = fmaf(ae, g8[v], dv[v]);
+               dv[v] = fmaf(aev, g8[v], dv[v]);
             }
          }
       }
@@ -343,22 +402,32 @@ __global__ __launch_bounds__(WAVES * 64) void mha16_bw_cols_kernel(const Mha16Ar
 
 enum { MHA16_FW = 0, MHA16_BW_ROWS = 1, MHA16_BW_COLS = 2 };
 
-template <int ELT, int LPR>
-static int launch_mha16(int which, const Mha16Args &a, const char *entry, hipStream_t st) {
+template <int ELT, int LPR, bool DROP>
+static int launch_mha16(int which, const Mha16DropArgs &full, const char *entry, hipStream_t st) {
+   const typename Mha16KernelArgs<DROP>::type &a = full;
    const int64_t nb = (a.rows + MHA16_WAVES - 1) / MHA16_WAVES;
    if (nb > 0x7fffffffLL) return fail(ISPLIB_FAIL, entry, "too many rows for one launch");
    const dim3 grid((unsigned)nb), block((unsigned)MHA16_WAVES * 64u);
-   if (which == MHA16_FW) hipLaunchKernelGGL((mha16_fw_kernel<ELT, LPR, MHA16_WAVES, MHA16_FW_U>), grid, block, 0, st, a);
-   else if (which == MHA16_BW_ROWS) hipLaunchKernelGGL((mha16_bw_rows_kernel<ELT, LPR, MHA16_WAVES, MHA16_ROWS_U>), grid, block, 0, st, a);
-   else hipLaunchKernelGGL((mha16_bw_cols_kernel<ELT, LPR, MHA16_WAVES, MHA16_COLS_U>), grid, block, 0, st, a);
+   if (which == MHA16_FW) hipLaunchKernelGGL((mha16_fw_kernel<ELT, LPR, MHA16_WAVES, MHA16_FW_U, DROP>), grid, block, 0, st, a);
+   else if (which == MHA16_BW_ROWS) hipLaunchKernelGGL((mha16_bw_rows_kernel<ELT, LPR, MHA16_WAVES, MHA16_ROWS_U, DROP>), grid, block, 0, st, a);
+   else hipLaunchKernelGGL((mha16_bw_cols_kernel<ELT, LPR, MHA16_WAVES, MHA16_COLS_U, DROP>), grid, block, 0, st, a);
    return check_launch(entry);
 }
 
-// the element type and the slot width (attn16_run)
-static int mha16_run(int dtype, int which, const Mha16Args &a, const char *entry, void *stream) {
+// the element type and the slot width (attn16_run); drop: the kernels with attention dropout
+static int mha16_run(int dtype, int which, const Mha16DropArgs &a, bool drop, const char *entry, void *stream) {
    return attn16_run(dtype, a.k, [&](auto elt, auto lpr) {
-      return launch_mha16<decltype(elt)::value, decltype(lpr)::value>(which, a, entry, (hipStream_t)stream);
+      constexpr int ELT = decltype(elt)::value, LPR = decltype(lpr)::value;
+      return drop ? launch_mha16<ELT, LPR, true>(which, a, entry, (hipStream_t)stream)
+                  : launch_mha16<ELT, LPR, false>(which, a, entry, (hipStream_t)stream);
    });
+}
+
+// what the dropout entries (isplib_qkv_half_drop_*_hip) refuse AFTER the refusals of the entries without dropout, in the order of the
+// fp32 dropout entries: attn_drop_refusal, then a seed of 2^63 or more
+static const char *mha16_drop_refusal(const AttnDrop &dr, int64_t nnz) {
+   if (const char *why = attn_drop_refusal(dr, nnz, "keep_scale must be a positive finite number")) return why;
+   return dr.on && dr.seed >= (1ull << 63) ? "seed must be below 2^63" : nullptr;
 }
 
 static const char *const MHA16_DOMAIN = "outside isplib_qkv16_serves(rows_gathered, heads, d, ld) = isplib_gat16_serves: 1 <= heads, "
@@ -376,12 +445,15 @@ extern "C" int isplib_qkv16_domain(int64_t rows_gathered, int64_t heads, int64_t
 
 extern "C" int isplib_qkv16_auto(int64_t rows_gathered, int64_t ld) { return isplib_qkv16_native_pays(rows_gathered, ld); }
 
-// the refusals of the three entries come in one order: dtype, negative dimension, nothing to do, a pitch below k, k % heads, the scale,
-// the domain, a null operand, alignment -- all before any launch
-extern "C" int isplib_qkv16_csr_hip(int dtype, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
-                                    const int64_t *pntre, int64_t heads, float scale, const void *q, int64_t ldq, const void *key,
-                                    int64_t ldk, const void *v, int64_t ldv, void *z, int64_t ldz, float *lse, void *stream) {
-   const char *entry = "isplib_qkv16_csr_hip";
+extern "C" int isplib_qkv_half_drop_auto(int64_t rows_gathered, int64_t ld) { return isplib_qkv_half_drop_native_pays(rows_gathered, ld); }
+
+// The three entries, with and without attention dropout.  Their refusals come in one order: dtype, negative dimension, nothing to do, a
+// pitch below k, k % heads, the scale, the domain, a null operand, alignment; then, with dropout, the keep scale, nnz >= 2^31, the seed
+// and (columns) a null csr2csc -- all before any launch
+static int mha16_forward(const char *entry, int dtype, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx,
+                         const int64_t *pntrb, const int64_t *pntre, int64_t heads, float scale, const void *q, int64_t ldq,
+                         const void *key, int64_t ldk, const void *v, int64_t ldv, void *z, int64_t ldz, float *lse, void *stream,
+                         const AttnDrop &dr = ATTN_NO_DROP) {
    clear_error();
    if (dtype != ISPLIB_DTYPE_BF16 && dtype != ISPLIB_DTYPE_F16) return fail(ISPLIB_FAIL, entry, ATTN16_DTYPE);
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
@@ -394,21 +466,22 @@ extern "C" int isplib_qkv16_csr_hip(int dtype, int64_t m, int64_t n, int64_t k, 
       return fail(ISPLIB_NO_OPT_IMPL, entry, MHA16_DOMAIN);
    if (!pntrb || !pntre || !q || !z || !lse || (nnz > 0 && (!indx || !key || !v))) return fail(ISPLIB_FAIL, entry, "null operand");
    if (!attn16_aligned(q, key, v, z)) return fail(ISPLIB_FAIL, entry, "q, key, v and z must be 4-byte aligned");
-   Mha16Args a = {};
+   if (const char *why = mha16_drop_refusal(dr, nnz)) return fail(ISPLIB_FAIL, entry, why);
+   Mha16DropArgs a = {};
    a.rows = m; a.k = k; a.indx = indx; a.pntrb = pntrb; a.pntre = pntre; a.p = scale;
    attn16_head_geometry(heads, k / heads, a.heads, a.hshift, a.hlanes, a.hmask);
    a.own = reinterpret_cast<const unsigned short *>(q); a.ldown = ldq;
    a.out = reinterpret_cast<unsigned short *>(z); a.ldout = ldz; a.hout = lse;
    a.ga = key; a.ldga = ldk; a.gabytes = nnz > 0 ? attn16_extent(n, k, ldk, 2u) : 0u;
    a.gb = v; a.ldgb = ldv; a.gbbytes = nnz > 0 ? attn16_extent(n, k, ldv, 2u) : 0u;
-   return mha16_run(dtype, MHA16_FW, a, entry, stream);
+   attn_set_drop(dr, a.seed_lo, a.seed_hi, a.T, a.c);
+   return mha16_run(dtype, MHA16_FW, a, dr.on, entry, stream);
 }
 
-extern "C" int isplib_qkv16_bw_rows_hip(int dtype, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
-                                        const int64_t *pntre, int64_t heads, float scale, const void *q, int64_t ldq, const void *key,
-                                        int64_t ldk, const void *v, int64_t ldv, const void *g, int64_t ldg, const float *lse, void *dq,
-                                        int64_t lddq, float *dsum, void *stream) {
-   const char *entry = "isplib_qkv16_bw_rows_hip";
+static int mha16_backward_rows(const char *entry, int dtype, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx,
+                               const int64_t *pntrb, const int64_t *pntre, int64_t heads, float scale, const void *q, int64_t ldq,
+                               const void *key, int64_t ldk, const void *v, int64_t ldv, const void *g, int64_t ldg, const float *lse,
+                               void *dq, int64_t lddq, float *dsum, void *stream, const AttnDrop &dr = ATTN_NO_DROP) {
    clear_error();
    if (dtype != ISPLIB_DTYPE_BF16 && dtype != ISPLIB_DTYPE_F16) return fail(ISPLIB_FAIL, entry, ATTN16_DTYPE);
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
@@ -422,7 +495,8 @@ extern "C" int isplib_qkv16_bw_rows_hip(int dtype, int64_t m, int64_t n, int64_t
    if (!pntrb || !pntre || !q || !g || !lse || !dq || !dsum || (nnz > 0 && (!indx || !key || !v)))
       return fail(ISPLIB_FAIL, entry, "null operand");
    if (!attn16_aligned(q, key, v, g, dq)) return fail(ISPLIB_FAIL, entry, "q, key, v, g and dq must be 4-byte aligned");
-   Mha16Args a = {};
+   if (const char *why = mha16_drop_refusal(dr, nnz)) return fail(ISPLIB_FAIL, entry, why);
+   Mha16DropArgs a = {};
    a.rows = m; a.k = k; a.indx = indx; a.pntrb = pntrb; a.pntre = pntre; a.p = scale;
    attn16_head_geometry(heads, k / heads, a.heads, a.hshift, a.hlanes, a.hmask);
    a.own = reinterpret_cast<const unsigned short *>(q); a.ldown = ldq;
@@ -430,14 +504,15 @@ extern "C" int isplib_qkv16_bw_rows_hip(int dtype, int64_t m, int64_t n, int64_t
    a.out = reinterpret_cast<unsigned short *>(dq); a.ldout = lddq; a.hout = dsum;
    a.ga = key; a.ldga = ldk; a.gabytes = nnz > 0 ? attn16_extent(n, k, ldk, 2u) : 0u;
    a.gb = v; a.ldgb = ldv; a.gbbytes = nnz > 0 ? attn16_extent(n, k, ldv, 2u) : 0u;
-   return mha16_run(dtype, MHA16_BW_ROWS, a, entry, stream);
+   attn_set_drop(dr, a.seed_lo, a.seed_hi, a.T, a.c);
+   return mha16_run(dtype, MHA16_BW_ROWS, a, dr.on, entry, stream);
 }
 
-extern "C" int isplib_qkv16_bw_cols_hip(int dtype, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t, const int64_t *colb,
-                                        const int64_t *cole, int64_t heads, float scale, const void *q, int64_t ldq, const void *g,
-                                        int64_t ldg, const float *lse, const float *dsum, const void *key, int64_t ldk, const void *v,
-                                        int64_t ldv, void *dkey, int64_t lddk, void *dv, int64_t lddv, void *stream) {
-   const char *entry = "isplib_qkv16_bw_cols_hip";
+static int mha16_backward_cols(const char *entry, int dtype, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t,
+                               const int64_t *colb, const int64_t *cole, const int64_t *csr2csc, int64_t heads, float scale,
+                               const void *q, int64_t ldq, const void *g, int64_t ldg, const float *lse, const float *dsum,
+                               const void *key, int64_t ldk, const void *v, int64_t ldv, void *dkey, int64_t lddk, void *dv,
+                               int64_t lddv, void *stream, const AttnDrop &dr = ATTN_NO_DROP) {
    clear_error();
    if (dtype != ISPLIB_DTYPE_BF16 && dtype != ISPLIB_DTYPE_F16) return fail(ISPLIB_FAIL, entry, ATTN16_DTYPE);
    if (m < 0 || n < 0 || k < 0 || nnz < 0) return fail(ISPLIB_FAIL, entry, "negative dimension");
@@ -451,7 +526,9 @@ extern "C" int isplib_qkv16_bw_cols_hip(int dtype, int64_t m, int64_t n, int64_t
    if (!colb || !cole || !key || !v || !dkey || !dv || (nnz > 0 && (!row_t || !q || !g || !lse || !dsum)))
       return fail(ISPLIB_FAIL, entry, "null operand");
    if (!attn16_aligned(q, g, key, v, dkey, dv)) return fail(ISPLIB_FAIL, entry, "q, g, key, v, dkey and dv must be 4-byte aligned");
-   Mha16Args a = {};
+   if (const char *why = mha16_drop_refusal(dr, nnz)) return fail(ISPLIB_FAIL, entry, why);
+   if (dr.on && nnz > 0 && !csr2csc) return fail(ISPLIB_FAIL, entry, "null csr2csc: the keep bit is a function of the CSR position");
+   Mha16DropArgs a = {};
    a.rows = n; a.k = k; a.indx = row_t; a.pntrb = colb; a.pntre = cole; a.p = scale;
    attn16_head_geometry(heads, k / heads, a.heads, a.hshift, a.hlanes, a.hmask);
    a.own = reinterpret_cast<const unsigned short *>(key); a.ldown = ldk;
@@ -461,5 +538,58 @@ extern "C" int isplib_qkv16_bw_cols_hip(int dtype, int64_t m, int64_t n, int64_t
    a.ga = q; a.ldga = ldq; a.gabytes = nnz > 0 ? attn16_extent(m, k, ldq, 2u) : 0u;
    a.gb = g; a.ldgb = ldg; a.gbbytes = nnz > 0 ? attn16_extent(m, k, ldg, 2u) : 0u;
    a.t1 = lse; a.t2 = dsum; a.tbytes = nnz > 0 ? attn16_extent(m, heads, heads, 4u) : 0u;
-   return mha16_run(dtype, MHA16_BW_COLS, a, entry, stream);
+   if (dr.on) a.epos = csr2csc;
+   attn_set_drop(dr, a.seed_lo, a.seed_hi, a.T, a.c);
+   return mha16_run(dtype, MHA16_BW_COLS, a, dr.on, entry, stream);
+}
+
+extern "C" int isplib_qkv16_csr_hip(int dtype, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                                    const int64_t *pntre, int64_t heads, float scale, const void *q, int64_t ldq, const void *key,
+                                    int64_t ldk, const void *v, int64_t ldv, void *z, int64_t ldz, float *lse, void *stream) {
+   return mha16_forward("isplib_qkv16_csr_hip", dtype, m, n, k, nnz, indx, pntrb, pntre, heads, scale, q, ldq, key, ldk, v, ldv, z, ldz,
+                        lse, stream);
+}
+
+extern "C" int isplib_qkv16_bw_rows_hip(int dtype, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx, const int64_t *pntrb,
+                                        const int64_t *pntre, int64_t heads, float scale, const void *q, int64_t ldq, const void *key,
+                                        int64_t ldk, const void *v, int64_t ldv, const void *g, int64_t ldg, const float *lse, void *dq,
+                                        int64_t lddq, float *dsum, void *stream) {
+   return mha16_backward_rows("isplib_qkv16_bw_rows_hip", dtype, m, n, k, nnz, indx, pntrb, pntre, heads, scale, q, ldq, key, ldk, v, ldv,
+                              g, ldg, lse, dq, lddq, dsum, stream);
+}
+
+extern "C" int isplib_qkv16_bw_cols_hip(int dtype, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t, const int64_t *colb,
+                                        const int64_t *cole, int64_t heads, float scale, const void *q, int64_t ldq, const void *g,
+                                        int64_t ldg, const float *lse, const float *dsum, const void *key, int64_t ldk, const void *v,
+                                        int64_t ldv, void *dkey, int64_t lddk, void *dv, int64_t lddv, void *stream) {
+   return mha16_backward_cols("isplib_qkv16_bw_cols_hip", dtype, m, n, k, nnz, row_t, colb, cole, nullptr, heads, scale, q, ldq, g, ldg,
+                              lse, dsum, key, ldk, v, ldv, dkey, lddk, dv, lddv, stream);
+}
+
+// attention dropout: the argument lists of the entries above (the columns entry with csr2csc after cole), then threshold, keep_scale, seed
+extern "C" int isplib_qkv_half_drop_csr_hip(int dtype, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx,
+                                            const int64_t *pntrb, const int64_t *pntre, int64_t heads, float scale, const void *q,
+                                            int64_t ldq, const void *key, int64_t ldk, const void *v, int64_t ldv, void *z, int64_t ldz,
+                                            float *lse, void *stream, uint32_t threshold, float keep_scale, uint64_t seed) {
+   return mha16_forward("isplib_qkv_half_drop_csr_hip", dtype, m, n, k, nnz, indx, pntrb, pntre, heads, scale, q, ldq, key, ldk, v, ldv, z,
+                        ldz, lse, stream, AttnDrop{true, threshold, keep_scale, seed});
+}
+
+extern "C" int isplib_qkv_half_drop_bw_rows_hip(int dtype, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *indx,
+                                                const int64_t *pntrb, const int64_t *pntre, int64_t heads, float scale, const void *q,
+                                                int64_t ldq, const void *key, int64_t ldk, const void *v, int64_t ldv, const void *g,
+                                                int64_t ldg, const float *lse, void *dq, int64_t lddq, float *dsum, void *stream,
+                                                uint32_t threshold, float keep_scale, uint64_t seed) {
+   return mha16_backward_rows("isplib_qkv_half_drop_bw_rows_hip", dtype, m, n, k, nnz, indx, pntrb, pntre, heads, scale, q, ldq, key, ldk,
+                              v, ldv, g, ldg, lse, dq, lddq, dsum, stream, AttnDrop{true, threshold, keep_scale, seed});
+}
+
+extern "C" int isplib_qkv_half_drop_bw_cols_hip(int dtype, int64_t m, int64_t n, int64_t k, int64_t nnz, const int64_t *row_t,
+                                                const int64_t *colb, const int64_t *cole, const int64_t *csr2csc, int64_t heads,
+                                                float scale, const void *q, int64_t ldq, const void *g, int64_t ldg, const float *lse,
+                                                const float *dsum, const void *key, int64_t ldk, const void *v, int64_t ldv, void *dkey,
+                                                int64_t lddk, void *dv, int64_t lddv, void *stream, uint32_t threshold, float keep_scale,
+                                                uint64_t seed) {
+   return mha16_backward_cols("isplib_qkv_half_drop_bw_cols_hip", dtype, m, n, k, nnz, row_t, colb, cole, csr2csc, heads, scale, q, ldq, g,
+                              ldg, lse, dsum, key, ldk, v, ldv, dkey, lddk, dv, lddv, stream, AttnDrop{true, threshold, keep_scale, seed});
 }

@@ -2545,6 +2545,126 @@ Tensor mha_spmm16(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor
    return MhaSpmm16::apply(rowptr, col, colptr, row_t, q, k, v, heads, scale)[0];
 }
 
+// ---- the same 16-bit attention with attention dropout (isplib_qkv_half_drop_*_hip) ----------
+// MhaSpmm16 with the keep bit of MhaDropSpmm: the checks of both, the operands as they lie (mha16_operand), z, dq, dk and dv in their
+// dtype, lse and D fp32.  Saved for backward: the structure, q, k, v, lse, csr2csc and the three scalars (threshold, keep scale, seed)
+// -- NOT z, and nothing of length nnz that the call did not receive.  The columns kernel runs only when k or v asks for a gradient.
+class MhaDropSpmm16 : public torch::autograd::Function<MhaDropSpmm16> {
+ public:
+   static variable_list forward(AutogradContext *ctx, Variable rowptr, Variable col, Variable colptr, Variable row_t, Variable csr2csc,
+                                Variable q, Variable k, Variable v, int64_t heads, double scale, double p, int64_t seed) {
+      check_index(rowptr, "rowptr"); check_index(col, "col"); check_index(colptr, "colptr"); check_index(row_t, "row_t");
+      check_index(csr2csc, "csr2csc");
+      TORCH_CHECK(q.defined() && q.dim() == 2 && k.defined() && k.dim() == 2 && v.defined() && v.dim() == 2,
+                  "isplib: mha_drop_spmm16 needs 2-D `q` [M, heads * d], `k` and `v` [N, heads * d]");
+      TORCH_CHECK(is_half(q), "isplib: mha_drop_spmm16: `q` must be bfloat16 or float16, got ", q.scalar_type(), " (float32: mha_drop_spmm)");
+      TORCH_CHECK(p > 0.0 && p < 1.0, "isplib: mha_drop_spmm16: `p` must lie in (0, 1), got ", p, " (p == 0: mha_spmm16)");
+      TORCH_CHECK(seed >= 0, "isplib: mha_drop_spmm16: `seed` must be a non-negative int64, got ", seed);
+      OpTimer timer("FUSEDMM_MHA_DROP_FW", q);
+      const int64_t M = rowptr.numel() - 1, N = colptr.numel() - 1, K = q.size(1), nnz = col.numel();
+      TORCH_CHECK(M >= 0 && N >= 0 && row_t.numel() == nnz && csr2csc.numel() == nnz,
+                  "isplib: mha_drop_spmm16: `rowptr` / `colptr` need one entry more than rows / columns, `row_t` and `csr2csc` one entry per "
+                  "stored entry (", nnz, "), got ", row_t.numel(), " and ", csr2csc.numel());
+      TORCH_CHECK(heads >= 1 && K % heads == 0, "isplib: mha_drop_spmm16: the width of `q` (", K, ") must be heads * d, got heads = ", heads);
+      TORCH_CHECK(std::isfinite(scale), "isplib: mha_drop_spmm16: `scale` must be a finite number, got ", scale);
+      const at::ScalarType dt = q.scalar_type();
+      const AttnOperand qo = mha16_operand(q, "q", M, K, heads, dt), ko = mha16_operand(k, "k", N, K, heads, dt),
+                        vo = mha16_operand(v, "v", N, K, heads, dt);
+      for (const Tensor *t : {&rowptr, &col, &colptr, &row_t, &csr2csc, &k, &v})
+         TORCH_CHECK(t->device() == q.device(), "isplib: mha_drop_spmm16: every operand must be on q's device");
+      TORCH_CHECK(K == 0 || (isplib_qkv16_serves(N, heads, K / heads, ko.ld) && isplib_qkv16_serves(N, heads, K / heads, vo.ld) &&
+                             qo.ld % 2 == 0),
+                  "isplib: mha_drop_spmm16: outside isplib_qkv16_serves (", ISPLIB_GAT16_K_MIN, " <= heads * d <= ", ISPLIB_GAT16_K_MAX,
+                  ", heads == 1 with d even or d a power of two >= 8, N < 2^31, N * pitch * 2 <= 3.5 GiB): N = ", N, ", heads = ", heads,
+                  ", d = ", K / heads, ", pitches = ", ko.ld, ", ", vo.ld);
+      TORCH_CHECK(nnz < (1LL << 31), "isplib: mha_drop_spmm16: the keep bit is defined for CSR positions below 2^31, got nnz = ", nnz);
+      const uint32_t threshold = isplib_gat_drop_threshold(p);
+      const float keep_scale = (float)(1.0 / (1.0 - p));
+      c10::DeviceGuard guard(q.device());
+      const int code = dt == at::kBFloat16 ? ISPLIB_DTYPE_BF16 : ISPLIB_DTYPE_F16;
+      const Tensor rp = rowptr.contiguous(), cl = col.contiguous();
+      Tensor z = at::empty({M, K}, q.options()), lse = at::empty({M, heads}, q.options().dtype(at::kFloat));
+      if (M > 0 && K > 0) {
+         const int st = isplib_qkv_half_drop_csr_hip(code, M, N, K, nnz, cl.data_ptr<int64_t>(), rp.data_ptr<int64_t>(),
+                                                     rp.data_ptr<int64_t>() + 1, heads, (float)scale, qo.t.data_ptr(), qo.ld,
+                                                     nnz > 0 ? ko.t.data_ptr() : nullptr, ko.ld, nnz > 0 ? vo.t.data_ptr() : nullptr, vo.ld,
+                                                     z.data_ptr(), K, lse.data_ptr<float>(), current_stream(q), threshold, keep_scale,
+                                                     (uint64_t)seed);
+         check_status(st, "isplib_qkv_half_drop_csr_hip");
+      } else if (M > 0) {
+         lse.fill_(-std::numeric_limits<float>::infinity());
+      }
+      ctx->saved_data["heads"] = heads;
+      ctx->saved_data["scale"] = scale;
+      ctx->saved_data["threshold"] = (int64_t)threshold;
+      ctx->saved_data["keep_scale"] = (double)keep_scale;
+      ctx->saved_data["seed"] = seed;
+      ctx->save_for_backward({rp, cl, colptr, row_t, q, k, v, lse, csr2csc});
+      return {z};
+   }
+
+   static variable_list backward(AutogradContext *ctx, variable_list grad_outs) {
+      OpTimer timer("FUSEDMM_MHA_DROP_BW", grad_outs[0]);
+      const bool need_q = ctx->needs_input_grad(5), need_k = ctx->needs_input_grad(6), need_v = ctx->needs_input_grad(7);
+      auto grad_q = Variable(), grad_k = Variable(), grad_v = Variable();
+      if (need_q || need_k || need_v) {
+         auto saved = ctx->get_saved_variables();
+         auto rp = saved[0], cl = saved[1], colptr = saved[2].contiguous(), row_t = saved[3].contiguous(), q = saved[4], k = saved[5], v = saved[6],
+              lse = saved[7];
+         const int64_t heads = ctx->saved_data["heads"].toInt();
+         const float ps = (float)ctx->saved_data["scale"].toDouble();
+         const uint32_t threshold = (uint32_t)ctx->saved_data["threshold"].toInt();
+         const float keep_scale = (float)ctx->saved_data["keep_scale"].toDouble();
+         const uint64_t seed = (uint64_t)ctx->saved_data["seed"].toInt();
+         const int64_t M = rp.numel() - 1, N = colptr.numel() - 1, K = q.size(1), nnz = cl.numel();
+         const at::ScalarType dt = q.scalar_type();
+         const AttnOperand qo = mha16_operand(q, "q", M, K, heads, dt), ko = mha16_operand(k, "k", N, K, heads, dt),
+                           vo = mha16_operand(v, "v", N, K, heads, dt);
+         const AttnOperand go = mha16_operand(grad_outs[0].to(dt), "grad_out", M, K, heads, dt);   // a grad of another dtype is cast to q's
+         c10::DeviceGuard guard(q.device());
+         const int code = dt == at::kBFloat16 ? ISPLIB_DTYPE_BF16 : ISPLIB_DTYPE_F16;
+         // as in MhaSpmm16: the rows kernel always runs (D feeds the columns kernel), the columns kernel only when k or v asks
+         Tensor dq = at::empty({M, K}, q.options()), dsum = at::empty({M, heads}, q.options().dtype(at::kFloat));
+         if (M > 0 && K > 0) {
+            const int st = isplib_qkv_half_drop_bw_rows_hip(code, M, N, K, nnz, cl.data_ptr<int64_t>(), rp.data_ptr<int64_t>(),
+                                                            rp.data_ptr<int64_t>() + 1, heads, ps, qo.t.data_ptr(), qo.ld,
+                                                            nnz > 0 ? ko.t.data_ptr() : nullptr, ko.ld,
+                                                            nnz > 0 ? vo.t.data_ptr() : nullptr, vo.ld, go.t.data_ptr(), go.ld,
+                                                            lse.data_ptr<float>(), dq.data_ptr(), K, dsum.data_ptr<float>(),
+                                                            current_stream(q), threshold, keep_scale, seed);
+            check_status(st, "isplib_qkv_half_drop_bw_rows_hip");
+         }
+         if (need_q) grad_q = dq;
+         if (need_k || need_v) {
+            TORCH_CHECK(K == 0 || (isplib_qkv16_serves(M, heads, K / heads, qo.ld) && isplib_qkv16_serves(M, heads, K / heads, go.ld)),
+                        "isplib: mha_drop_spmm16 backward: outside isplib_qkv16_serves for the gathered rows of q and of the gradient: M = ",
+                        M, ", K = ", K);
+            const Tensor pos = saved[8].contiguous();
+            Tensor dk = at::empty({N, K}, q.options()), dv = at::empty({N, K}, q.options());
+            if (N > 0 && K > 0) {
+               const int st = isplib_qkv_half_drop_bw_cols_hip(code, M, N, K, nnz, row_t.data_ptr<int64_t>(), colptr.data_ptr<int64_t>(),
+                                                               colptr.data_ptr<int64_t>() + 1, nnz > 0 ? pos.data_ptr<int64_t>() : nullptr,
+                                                               heads, ps, nnz > 0 ? qo.t.data_ptr() : nullptr, qo.ld,
+                                                               nnz > 0 ? go.t.data_ptr() : nullptr, go.ld, lse.data_ptr<float>(),
+                                                               dsum.data_ptr<float>(), ko.t.data_ptr(), ko.ld, vo.t.data_ptr(), vo.ld,
+                                                               dk.data_ptr(), K, dv.data_ptr(), K, current_stream(q), threshold, keep_scale,
+                                                               seed);
+               check_status(st, "isplib_qkv_half_drop_bw_cols_hip");
+            }
+            if (need_k) grad_k = dk;
+            if (need_v) grad_v = dv;
+         }
+      }
+      return {Variable(), Variable(), Variable(), Variable(), Variable(), grad_q, grad_k, grad_v, Variable(), Variable(), Variable(),
+              Variable()};
+   }
+};
+
+Tensor mha_drop_spmm16(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor csr2csc, Tensor q, Tensor k, Tensor v, int64_t heads,
+                       double scale, double p, int64_t seed) {
+   return MhaDropSpmm16::apply(rowptr, col, colptr, row_t, csr2csc, q, k, v, heads, scale, p, seed)[0];
+}
+
 // introspection / housekeeping of the per-graph handle cache of the reference-schema operators
 int64_t graph_cache_size() {
    std::lock_guard<std::mutex> lock(g_graph_mutex);
@@ -2613,4 +2733,6 @@ TORCH_LIBRARY(isplib, m) {
    m.def("mha_drop_spmm(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor csr2csc, Tensor q, Tensor k, Tensor v, int heads, float scale, float p, int seed) -> Tensor",
          &mha_drop_spmm);
    m.def("mha_spmm16(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor q, Tensor k, Tensor v, int heads, float scale) -> Tensor", &mha_spmm16);
+   m.def("mha_drop_spmm16(Tensor rowptr, Tensor col, Tensor colptr, Tensor row_t, Tensor csr2csc, Tensor q, Tensor k, Tensor v, int heads, float scale, float p, int seed) -> Tensor",
+         &mha_drop_spmm16);
 }

@@ -30,7 +30,9 @@ gradient of a 16-bit sum / mean (rows16_da_route), ISPLIB_HALF_GCN=convert|nativ
 16-bit operands (attention16_route; unset: such a call raises, as it always did), ISPLIB_HALF_GAT=convert|native|auto for gat_matmul on
 a 16-bit `y` (gat16_route; unset: such a call raises, as it always did), ISPLIB_HALF_GATV2=convert|native|auto for gatv2_matmul on
 16-bit `x` and `y` (gatv2_16_route; unset: such a call raises, as it always did), ISPLIB_HALF_MHA=convert|native|auto for mha_matmul
-on 16-bit `q`, `k` and `v` (mha16_route; unset: such a call raises, as it always did); the first three default to convert;
+on 16-bit `q`, `k` and `v` (mha16_route; unset: such a call raises, as it always did), and on top of it
+ISPLIB_HALF_MHA_DROP=convert|native|auto for such a call with active dropout (mha16_drop_route; unset: convert, and it is read only
+where ISPLIB_HALF_MHA is set); the first three default to convert;
 ISPLIB_TUNE_FILE names a tuning table to load at import; ISPLIB_DEBUG=1 prints per-operator device times.
 """
 from __future__ import annotations
@@ -514,6 +516,28 @@ def mha16_route(dtype, heads: int, d: int, pitch: int, n: int, mode: Optional[st
     else:
         return "convert"
     return "mha16" if mode == "native" or cabi.mha16_native_pays(n, ld) else "convert"
+
+
+def mha16_drop_route(dtype, heads: int, d: int, pitch: int, n: int, mode: Optional[str] = None) -> str:
+    """Which way mha_matmul with 16-bit `q`, `k` and `v` AND active dropout goes once ISPLIB_HALF_MHA is set, asked per GATHERED wide
+    operand as mha16_route is: "mha16drop" (torch.ops.isplib.mha_drop_spmm16 on the 16-bit DROP kernels, isplib_qkv_half_drop_*_hip) or
+    "convert" (`.float()` -> the fp32 dropout operator -> `.to(dtype)`).  A pure function -- no device, no library call:
+      * "mha16drop" only where mha16_route says "mha16" for the operand: ISPLIB_HALF=convert, ISPLIB_HALF_MHA=convert (or unset) and the
+        family's domain all win;
+      * on top of that `mode`, which is ISPLIB_HALF_MHA_DROP (None: read from the environment; unset counts as "convert"), must be
+        "native", or "auto" with cabi.mha16_drop_native_pays(n, ld) for the pitch the operand goes in at -- the classes in which every
+        native run measured faster than every run of the conversion route (profiles/mha16_dropout_ab.txt).  Nothing raises."""
+    if mha16_route(dtype, heads, d, pitch, n) != "mha16":
+        return "convert"
+    from . import cabi
+    if mode is None:
+        mode = os.environ.get("ISPLIB_HALF_MHA_DROP", "convert")
+    if mode == "native":
+        return "mha16drop"
+    if mode != "auto":
+        return "convert"
+    ld = pitch if cabi.mha16_serves(n, heads, d, pitch) else heads * d
+    return "mha16drop" if cabi.mha16_drop_native_pays(n, ld) else "convert"
 
 
 _ROWS16_MARK = torch.tensor([16], dtype=torch.int32)      # second tensor of a 16-bit row plan (torch_ops.cpp: is_rows16_plan)
@@ -1161,10 +1185,14 @@ def mha_matmul(src, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: in
     the backward recomputes: nothing per edge is stored and no RNG state is kept.  ``seed=None`` draws one int64 in [0, 2^63) from
     torch's default CPU generator (reproducible under ``torch.manual_seed``, no device sync); an explicit `seed` is an int in [0, 2^63).
     The seed is a kernel ARGUMENT: a captured graph replays ONE mask -- draw the seed outside the capture and re-capture, or do not
-    capture a training step that needs fresh masks.  There is no 16-bit dropout kernel: with 16-bit `q`, `k`, `v` and the multi-head
-    variable set (to any value) a call with active dropout converts -- ``.float()`` -> the fp32 dropout operator -> ``.to(dtype)``,
-    every gradient returning in its own dtype through the casts, ``k is v`` preserved; with the variable unset it raises the TypeError
-    above."""
+    capture a training step that needs fresh masks.  With 16-bit `q`, `k`, `v`, the multi-head variable set and active dropout, the
+    call goes where mha16_drop_route says: with ISPLIB_HALF_MHA_DROP unset no 16-bit dropout kernel runs: the call converts --
+    ``.float()`` -> the fp32 dropout operator -> ``.to(dtype)``, every gradient returning in its own dtype through the casts,
+    ``k is v`` preserved -- whatever the multi-head variable says; with ISPLIB_HALF_MHA_DROP=native (or auto, where
+    cabi.mha16_drop_native_pays says the class pays) and ALL four gathered operands admitted as above it takes the 16-bit dropout
+    operator (torch.ops.isplib.mha_drop_spmm16: the DROP kernels of mha16.hip, the same keep bit, q, k, v and lse kept for the
+    backward and no z), else it converts as before and nothing raises.  With the multi-head variable unset the call raises the
+    TypeError above and ISPLIB_HALF_MHA_DROP is not read."""
     from . import cabi
     drop = _gat_dropout_args(dropout, training, seed)
     for name, t in (("q", q), ("k", k), ("v", v)):
@@ -1176,11 +1204,8 @@ def mha_matmul(src, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: in
             raise TypeError(f"isplib_amd: `q`, `k` and `v` must share one 16-bit dtype, got {q.dtype}, {k.dtype} and {v.dtype}")
         if not half and t.dtype != torch.float32:
             raise TypeError(f"isplib_amd: `{name}` must be float32, got {t.dtype} (the multi-head attention operator is fp32 only)")
-    if half and drop is not None:         # the conversion route whatever the variable says: .float() is exact
-        kf = k.float()
-        return mha_matmul(src, q.float(), kf, kf if v is k else v.float(), heads, scale, drop[0], True, drop[1]).to(q.dtype)
     if half:
-        return _mha_matmul16(src, q, k, v, heads, scale)
+        return _mha_matmul16(src, q, k, v, heads, scale, drop)
     if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
         raise ValueError(f"isplib_amd: `heads` must be a positive int, got {heads!r}")
     if q.dim() != 2 or k.dim() != 2 or v.dim() != 2:
@@ -1225,10 +1250,13 @@ def mha_matmul(src, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: in
     return torch.ops.isplib.mha_spmm(st._rowptr, st._col, st.colptr(), st.row_t(), q, k, v, heads, p)
 
 
-def _mha_matmul16(src, q, k, v, heads, scale):
+def _mha_matmul16(src, q, k, v, heads, scale, drop=None):
     """mha_matmul for bf16 / fp16 `q`, `k` and `v` under ISPLIB_HALF_MHA: the 16-bit operator where mha16_route admits ALL four gathered
     operands (k and v by the forward and the rows kernel; q and the gradient -- M rows, packed -- by the columns kernel), else the
-    conversion route.  `k is v`: on both routes the one tensor's gradient receives dk + dv."""
+    conversion route.  `k is v`: on both routes the one tensor's gradient receives dk + dv.  `drop` = (p, seed) of an active dropout:
+    the same with mha16_drop_route and the 16-bit dropout operator; its conversion route is the fp32 dropout operator (.float() is
+    exact)."""
+    route, want = (mha16_route, "mha16") if drop is None else (mha16_drop_route, "mha16drop")
     native = False
     if (isinstance(heads, int) and not isinstance(heads, bool) and heads >= 1 and q.dim() == 2 and k.dim() == 2 and v.dim() == 2 and
             k.size(1) == q.size(1) and v.size(1) == q.size(1) and q.size(1) % heads == 0 and q.is_cuda and k.is_cuda and v.is_cuda and
@@ -1241,14 +1269,20 @@ def _mha_matmul16(src, q, k, v, heads, scale):
             return t.stride(0) if rows > 1 and t.stride(1) == 1 and t.stride(0) >= kk else kk
 
         native = (q.size(0) == m_rows and k.size(0) == n_cols and v.size(0) == n_cols and
-                  all(mha16_route(q.dtype, heads, d, ld, rows) == "mha16"
+                  all(route(q.dtype, heads, d, ld, rows) == want
                       for rows, ld in ((n_cols, pitch(k, n_cols)), (n_cols, pitch(v, n_cols)), (m_rows, pitch(q, m_rows)), (m_rows, kk))))
+    if drop is not None and native and st._col.numel() >= 2 ** 31:
+        native = False                                   # the fp32 call raises what it always raised
     if not native:
         kf = k.float()
+        if drop is not None:
+            return mha_matmul(src, q.float(), kf, kf if v is k else v.float(), heads, scale, drop[0], True, drop[1]).to(q.dtype)
         return mha_matmul(src, q.float(), kf, kf if v is k else v.float(), heads, scale).to(q.dtype)
     if k.device != q.device or v.device != q.device or st._rowptr.device != q.device:
         raise ValueError("isplib_amd: `q`, `k`, `v` and the sparse matrix must be on one device")
     p = float(scale) if scale is not None else 1.0 / math.sqrt(d)
+    if drop is not None:
+        return torch.ops.isplib.mha_drop_spmm16(st._rowptr, st._col, st.colptr(), st.row_t(), st.csr2csc(), q, k, v, heads, p, *drop)
     return torch.ops.isplib.mha_spmm16(st._rowptr, st._col, st.colptr(), st.row_t(), q, k, v, heads, p)
 
 
